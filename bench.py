@@ -11,7 +11,11 @@ gathered over RCCL and rank 0 replays the reference heap.  Inputs are synthetic 
 timed region: the quantized index is synthesised directly (scan time is value-independent); a smaller
 real fp32 -> quantize -> search run provides recall@100 against an fp32 brute force.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus "roofline" and "cpu_baseline".
+A plain run measures the headline alone: set-up, --warmup steps, the --steps timed steps, the line.  --full adds every other leg
+(recall probe, CPU baselines, full-size parity against the oracle, latency, the batched / raw-query / strict-HBM / multi-device legs,
+the other BASELINE configs, the 8-GPU shard shape, N-API).  --dump-outputs DIR writes the last timed step's answers as .npy files.
+
+Prints ONE JSON line (rank 0) with the driver's contract plus "roofline" (and, with --full, "cpu_baseline" and the other legs).
 """
 import argparse
 import datetime
@@ -247,7 +251,7 @@ def roofline_object(strict_gbps, algorithmic_gbps, resident_frac, extra):
     Infinity Cache (resident fraction >= 0.9) is labelled as bound by the cache in its default mode."""
     r = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
          "achieved": strict_gbps, "frac": (strict_gbps / HBM_PEAK_GBS) if strict_gbps else None,
-         "frac_is": "strict HBM: dominant launch with nothing kept in the Infinity Cache (resident_mb 0)" if strict_gbps else "not measured (--no-hbm-only)",
+         "frac_is": "strict HBM: dominant launch with nothing kept in the Infinity Cache (resident_mb 0)" if strict_gbps else "not measured (the hbm_only leg runs with --full, not with --no-hbm-only)",
          "achieved_algorithmic": algorithmic_gbps, "frac_algorithmic": algorithmic_gbps / HBM_PEAK_GBS,
          "default_mode_bound": "infinity_cache" if resident_frac >= 0.9 else "hbm + infinity_cache (%.0f %% of a sweep's bytes cache-resident)" % (100 * resident_frac),
          "cache_resident_frac_of_sweep": resident_frac, "note": RESIDENT_NOTE}
@@ -552,6 +556,36 @@ def dry_run(args):
     return 0
 
 
+def headline_only(args):
+    """a run without --full: the headline step and nothing else - every leg that measures or checks something besides it is off,
+    whatever its own option says"""
+    args.no_recall = args.no_cpu_baseline = args.no_parity = True
+    args.latency_calls = 0
+    args.shared_sweep = 0
+    args.no_raw = args.no_hbm_only = args.no_napi = args.no_configs = args.no_c1 = args.no_shard_shape = True
+    args.inprocess_shards = 0
+
+
+DUMP_LIMIT_BYTES = 60_000_000   # the dumps stay under 64 MB, headers included
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what search_batch handed the caller in the last timed step, one .npy per array - indices.npy (row numbers,
+    float64: exact for int32), scores.npy (float32, as returned), counts.npy (answers per query, float64).  A step larger than 60 MB
+    in this form keeps a fixed, seeded sample of its queries, listed in query_rows.npy."""
+    idx, sc, cnt = res
+    nq = idx.shape[0]
+    per_query = idx.shape[1] * (8 + 4) + 8 + 8
+    rows = np.arange(nq)
+    if nq * per_query > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, DUMP_LIMIT_BYTES // per_query, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "indices.npy"), idx[rows].astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), np.ascontiguousarray(sc[rows], np.float32))
+    np.save(os.path.join(path, "counts.npy"), np.asarray(cnt)[rows].astype(np.float64))
+    np.save(os.path.join(path, "query_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -598,7 +632,16 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch rehearsal without a device: start the ranks, form the process group, run the barriers and the max-over-ranks "
                          "reduction, print the line with value null - NO measurement is made (CPU test of the --gpus N launch path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (recall, CPU baselines, parity, latency, batched, raw queries, hbm_only, "
+                         "in-process multi-device, configs c1/c2/c4/c5, shard shape, N-API); without it those legs stay off whatever their own options say")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's answers (indices, scores, counts) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        headline_only(args)
     if args.config == "c2":
         args.rows, args.dim = 1_000_000, 768
     elif args.config == "c4":
@@ -735,6 +778,8 @@ def main():
         t = torch.tensor([dt], device="cuda" if args.backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results[-1])
     st = ix.stats()
     sharded = None
     if dist is not None:

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in "$@"; do
   out=/tmp/ab_$(basename "$lib" .so)
   rm -rf "$out"
-  BBQ_LIB=$R/$lib rocprofv3 --kernel-trace --output-format csv -d "$out" -- python3 $R/bench.py --no-configs --no-napi --no-hbm-only --no-raw --no-cpu-baseline \
+  BBQ_LIB=$R/$lib rocprofv3 --kernel-trace --output-format csv -d "$out" -- python3 $R/bench.py --full --no-configs --no-napi --no-hbm-only --no-raw --no-cpu-baseline \
     --inprocess-shards 0 --latency-calls 0 --no-recall --no-shard-shape --no-c1 --no-parity --steps 3 --warmup 1 --slots 1 > /dev/null 2>&1
   python3 - "$out" "$lib" <<'PY'
 import csv, glob, sys, collections

@@ -4,7 +4,7 @@
 OUT=${1:-gpurun_out/qb}; shift
 R=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p $R/$OUT
-COMMON="--no-configs --no-napi --no-hbm-only --no-raw --no-cpu-baseline --inprocess-shards 0 --latency-calls 0 --no-recall"
+COMMON="--full --no-configs --no-napi --no-hbm-only --no-raw --no-cpu-baseline --inprocess-shards 0 --latency-calls 0 --no-recall"
 python3 $R/bench.py $COMMON "$@" > $R/$OUT/bench.json 2> $R/$OUT/bench.err || { tail -5 $R/$OUT/bench.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/qb_tr

@@ -32,7 +32,7 @@ s = replace_row(s, rnd + "_c2_*",
                 % (rnd, c["trace_avg_GBps"] / 1e3, c["trace_avg_GBps"] / 8000, c["launches"], c["trace_avg_us"] / 1e3, 100 * c["pmc"]["traffic_over_algorithmic"]))
 cf, ho, na = d["configs"], d["hbm_only"], d["napi"]
 s = replace_row(s, rnd + "_bench_n1.json",
-                "| `%s_bench_n1.json` | `python bench.py` (un-profiled, the driver's default invocation, ≈ 60 s): %.2f K q/s (%.3f of the HBM peak end to end), dominant launch %.3f by HIP events, "
+                "| `%s_bench_n1.json` | `python bench.py --full` (un-profiled, every leg, ≈ 60 s): %.2f K q/s (%.3f of the HBM peak end to end), dominant launch %.3f by HIP events, "
                 "%.0f %% of the bytes a query sweeps cache-resident (`roofline.cache_resident_frac_of_sweep`), full-size parity true; **`hbm_only`** (the same step with `resident_mb` 0: everything "
                 "streamed from HBM): %.2f K q/s, %.3f end to end, dominant launch %.3f, identical answers; **`configs`**: c2 %.1f K q/s (%.3f end to end, kernel %.3f, cache-resident), c4 %.2f K (%.3f), "
                 "c5 %.1f K (%.3f), each with its own full-size parity check; **`latency`** p50 %.3f ms; **`raw_queries`** %.2f K q/s (`bbq_search_raw_batch`); **`napi`**: node over the saved 10 M-row "
