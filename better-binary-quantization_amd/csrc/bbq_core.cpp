@@ -664,9 +664,6 @@ struct RawFeed {
         ready[(size_t)ci].store(state, std::memory_order_release);
       }
     };
-    // one chunk (the reference's call shape: ONE query per call): on the calling thread.  Creating a thread per call cost more than the
-    // quantization (~15 us) and, now and then, a millisecond: the 0.8 ms p99 of a 0.2 ms call through the N-API host
-    if (n_chunks() <= 1) { work(); return; }
     for (int t = 0; t < T; ++t) threads.emplace_back(work);
   }
   // blocks until queries [first, first + count) are quantized; on a failed query returns its index through *bad
@@ -714,6 +711,22 @@ struct ExtOut {
   int64_t answers_stride = 0;
 };
 
+// the FinalizeArgs fields every finalize launch takes from its slot: the query lists (a sharded scan's are the caller's), their
+// counters (the append counters only behind a sweep that appended), the running top-k keys, the threshold, the flags and the rank
+static FinalizeArgs slot_finalize_args(const Slot &s, uint64_t *lists, int32_t *list_counts, int64_t list_cap, bool appended, int64_t k) {
+  FinalizeArgs f{};
+  f.append_counts = appended ? s.d_append_counts : nullptr;
+  f.lists = lists;
+  f.list_counts = list_counts;
+  f.list_cap = list_cap;
+  f.topk_keys = s.d_topk;
+  f.topk_counts = s.d_topk_counts;
+  f.theta = s.d_theta;
+  f.flags = s.d_flags;
+  f.k = (int32_t)k;
+  return f;
+}
+
 int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const ExtOut *ext) {
   bbq_index *ix = c.ix;
   uint64_t *d_lists_ext = ext ? ext->lists : nullptr;
@@ -727,7 +740,8 @@ int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const 
     fill_query(ix, hp + (size_t)i * qb, hq + i, c.qquant + (size_t)(q_first + i) * ix->dim, c.qcorr + (size_t)(q_first + i) * 4,
                c.planes, c.one_bit, c.sim);
   size_t bytes = (size_t)nq * qb + (size_t)nq * sizeof(QueryParams);
-  bool use_mfma = ix->opt_share == 32 && c.maxq <= 127 && ix->store_bits == 1;
+  // the matrix-core shared sweep appends its candidates to the lists, so it runs only where they are this slot's own
+  bool use_mfma = !d_lists_ext && ix->opt_share == 32 && c.maxq <= 127 && ix->store_bits == 1;
   for (int i = 0; i < nq && use_mfma; ++i) use_mfma = mfma_query_ok(hq[i]);
   const bool mfma_fp = c.maxq <= 15;  // queryBits <= 4: rows as FP4, queries as FP6 - 64 dimensions per MFMA in the time the int8 form takes for 32
   const int mfma_scale8 = c.maxq <= 3 ? 8 : c.maxq <= 7 ? 4 : 2;   // products of scale8 / 8 * q: the accumulator's quarter-unit grain is 1, 1/2 or 1/4 of a qcDist unit
@@ -771,7 +785,7 @@ int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const 
   const bool use_final = !d_lists_ext && p.final_k > 0 && !p.segs.empty();
   // few queries: the sparse launches append their candidates to the list themselves (ScanArgs::append_lists)
   const bool append = use_final && p.latency && ix->opt_latency_append && !ix->has_pilot && ix->opt_share == 1;
-  s.appended = append || (use_mfma && !d_lists_ext);
+  s.appended = append || use_mfma;
   s.timed = false;
   ix->sweep_resident_acc = 0;
   for (const Segment &g : p.segs) {
@@ -795,9 +809,7 @@ int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const 
     a.ovf_cap = (int32_t)p.flood_cap;
     a.dense_score32 = g.dense ? s.d_dense0 : nullptr;
     a.dense_stride = s.dense_cap;
-    // the matrix-core shared sweep appends as well whenever the lists are this slot's own: its waves then never wait for each other
-    const bool mfma_append = use_mfma && !g.dense && !d_lists_ext;
-    const bool append_here = (append && !g.dense && (ix->opt_append_last || &g != &p.segs.back())) || mfma_append;
+    const bool append_here = !g.dense && ((append && (ix->opt_append_last || &g != &p.segs.back())) || use_mfma);
     if (append_here) {
       a.append_lists = d_lists;
       a.append_base = d_list_counts;
@@ -834,7 +846,7 @@ int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const 
                                            : sto.view.layout == kLayoutCompact ? (int64_t)sto.view.w16 * 16 + 24 : (int64_t)sto.view.tile_stride / kTileRows;
       s.timed_bytes = g.rows * ((nq + share - 1) / share) * row_bytes;
     }
-    FinalizeArgs f{};
+    FinalizeArgs f = slot_finalize_args(s, d_lists, d_list_counts, list_cap, append_here, c.k);
     f.counts = s.d_counts;
     f.entries = s.d_entries;
     f.dense_score32 = s.d_dense0;
@@ -845,16 +857,7 @@ int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const 
     f.cap = g.cap;
     f.ovf = a.ovf;
     f.ovf_cap = a.ovf_cap;
-    f.append_counts = append_here ? s.d_append_counts : nullptr;
-    f.lists = d_lists;
-    f.list_counts = d_list_counts;
-    f.list_cap = list_cap;
     f.emit = g.emit ? 1 : 0;
-    f.topk_keys = s.d_topk;
-    f.topk_counts = s.d_topk_counts;
-    f.theta = s.d_theta;
-    f.flags = s.d_flags;
-    f.k = (int32_t)c.k;
     f.need_theta = g.need_theta ? 1 : 0;
     if (use_final && &g == &p.segs.back()) {
       f.final_out = s.d_final;
@@ -1152,6 +1155,42 @@ int wait_latency_answer(DeviceCtx *ctx, Slot &s, uint64_t seq) {
   return fail(BBQ_ERR_HIP, "latency path: the device finished without an answer");
 }
 
+// the LatScanArgs both latency chains sweep the main storage with: the slot's control words and list, the query in the arguments
+static LatScanArgs lat_scan_args(const BatchCtx &c, const BatchCtx &cs, Slot &s) {
+  bbq_index *ix = c.ix;
+  LatScanArgs a{};
+  a.idx = launch_view(ix, ix->main);
+  a.row_id_base = ix->main.row_id_base;
+  a.theta = s.d_theta;
+  a.flags = s.d_flags;
+  a.list_counts = s.d_list_counts;
+  a.append_count = s.d_append_counts;
+  a.list = s.d_lists;
+  a.list_cap = s.list_cap;
+  fill_query(ix, reinterpret_cast<uint8_t *>(a.planes), &a.p, c.qquant, c.qcorr, cs.planes, cs.one_bit, cs.sim);
+  return a;
+}
+
+// the header the last finalize launch of a latency chain leaves in mapped host memory: {list count, flags}, {answer entries, replay}
+struct LatAnswer {
+  const uint64_t *hdr;
+  uint32_t listed, flags, m, replay;
+  explicit LatAnswer(const DeviceCtx *ctx)
+      : hdr(ctx->h_lat + kLatAnswerOffset), listed((uint32_t)hdr[0]), flags((uint32_t)(hdr[0] >> 32)), m((uint32_t)hdr[1]), replay((uint32_t)(hdr[1] >> 32)) {}
+  // the answer proven on the device (the m entries behind the header) goes to the caller
+  void take(bbq_index *ix, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) const {
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint64_t e = hdr[2 + j];
+      const uint32_t bits = (uint32_t)e;
+      out_idx[j] = (int32_t)(uint32_t)(e >> 32);
+      memcpy(&out_score[j], &bits, 4);
+    }
+    out_n[0] = m;
+    ix->stats.candidates += listed;
+    *done = true;
+  }
+};
+
 // The single-query call on a large index: threshold from a pre-sampled prefix (bbq_lat_pre_kernel + bbq_lat_select_kernel: two small
 // launches), ONE sweep over all rows with it, final selection on the list alone - four launches where the segmented chain has six,
 // and nothing in front of the large sweep but the two small ones.  The list is every row above the threshold, not a heap history: a
@@ -1186,18 +1225,9 @@ int search_latency_presampled(const BatchCtx &c, const BatchCtx &cs, int32_t *ou
     HIPCHK(hipMemsetAsync(s.d_block, 0, (size_t)s.ctrl_bytes, st));
     s.ctrl_clean = true;
   }
-  LatScanArgs a{};
   ix->sweep_resident_acc = 0;
-  a.idx = launch_view(ix, ix->main);
+  LatScanArgs a = lat_scan_args(c, cs, s);
   ix->stats.resident_bytes = ix->sweep_resident_acc;  // the one sweep over all rows
-  a.row_id_base = ix->main.row_id_base;
-  a.theta = s.d_theta;
-  a.flags = s.d_flags;
-  a.list_counts = s.d_list_counts;
-  a.append_count = s.d_append_counts;
-  a.list = s.d_lists;
-  a.list_cap = s.list_cap;
-  fill_query(ix, reinterpret_cast<uint8_t *>(a.planes), &a.p, c.qquant, c.qcorr, cs.planes, cs.one_bit, cs.sim);
   LatPreArgs pre{};
   pre.idx = launch_view(ix, ix->main);
   pre.rows = (int32_t)P;
@@ -1214,17 +1244,8 @@ int search_latency_presampled(const BatchCtx &c, const BatchCtx &cs, int32_t *ou
   a.first = 0;
   HIPCHK(launch_lat_scan(a, cs.planes, st));
   const uint64_t seq = ++ctx->lat_seq;
-  FinalizeArgs f{};
-  f.append_counts = s.d_append_counts;
-  f.lists = s.d_lists;
-  f.list_counts = s.d_list_counts;
-  f.list_cap = s.list_cap;
+  FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, cs.k);
   f.emit = 1;
-  f.topk_keys = s.d_topk;
-  f.topk_counts = s.d_topk_counts;
-  f.theta = s.d_theta;
-  f.flags = s.d_flags;
-  f.k = (int32_t)cs.k;
   f.final_out = ctx->d_lat + kLatAnswerOffset;
   f.final_stride = kFinalSelectMax + 2;
   f.final_k = (int32_t)k2;
@@ -1234,22 +1255,13 @@ int search_latency_presampled(const BatchCtx &c, const BatchCtx &cs, int32_t *ou
   HIPCHK(hipEventRecord(s.ev_done, st));
   rc = wait_latency_answer(ctx, s, seq);
   if (rc != BBQ_OK) return rc;
-  const uint64_t *hdr = ctx->h_lat + kLatAnswerOffset;
-  const uint32_t listed = (uint32_t)hdr[0], flags = (uint32_t)(hdr[0] >> 32), m = (uint32_t)hdr[1], replay = (uint32_t)(hdr[1] >> 32);
+  const LatAnswer r(ctx);
   s.timed = false;
   // The list holds the rows ABOVE the sampled threshold only, so the selection's "take every listed row" case (total <= k2) proves
   // nothing here: equal keys at ranks k2+1 / k2+2 of the sample can leave fewer than k2 rows above it (N >= 262144 > k2, so a
   // complete answer has exactly k2 entries).  Anything else goes to the segmented chain.
-  if (flags != 0 || replay != 0 || m != (uint32_t)k2) return BBQ_OK;
-  for (uint32_t j = 0; j < m; ++j) {
-    const uint64_t e = hdr[2 + j];
-    const uint32_t bits = (uint32_t)e;
-    out_idx[j] = (int32_t)(uint32_t)(e >> 32);
-    memcpy(&out_score[j], &bits, 4);
-  }
-  out_n[0] = m;
-  ix->stats.candidates += listed;
-  *done = true;
+  if (r.flags != 0 || r.replay != 0 || r.m != (uint32_t)k2) return BBQ_OK;
+  r.take(ix, out_idx, out_score, out_n, done);
   return BBQ_OK;
 }
 
@@ -1274,16 +1286,7 @@ int search_latency_chain(const BatchCtx &c, const BatchCtx &cs, int32_t *out_idx
     HIPCHK(hipMemsetAsync(s.d_block, 0, (size_t)s.ctrl_bytes, st));
     s.ctrl_clean = true;
   }
-  LatScanArgs a{};
-  a.idx = launch_view(ix, ix->main);
-  a.row_id_base = ix->main.row_id_base;
-  a.theta = s.d_theta;
-  a.flags = s.d_flags;
-  a.list_counts = s.d_list_counts;
-  a.append_count = s.d_append_counts;
-  a.list = s.d_lists;
-  a.list_cap = s.list_cap;
-  fill_query(ix, reinterpret_cast<uint8_t *>(a.planes), &a.p, c.qquant, c.qcorr, cs.planes, cs.one_bit, cs.sim);
+  LatScanArgs a = lat_scan_args(c, cs, s);
   const uint64_t seq = ++ctx->lat_seq;
   for (size_t i = 0; i < p.segs.size(); ++i) {
     const Segment &g = p.segs[i];
@@ -1291,17 +1294,8 @@ int search_latency_chain(const BatchCtx &c, const BatchCtx &cs, int32_t *out_idx
     a.n_chunks = (int32_t)g.n_chunks;
     a.first = i == 0 ? 1 : 0;
     HIPCHK(launch_lat_scan(a, cs.planes, st));
-    FinalizeArgs f{};
-    f.append_counts = s.d_append_counts;
-    f.lists = s.d_lists;
-    f.list_counts = s.d_list_counts;
-    f.list_cap = s.list_cap;
+    FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, cs.k);
     f.emit = 1;
-    f.topk_keys = s.d_topk;
-    f.topk_counts = s.d_topk_counts;
-    f.theta = s.d_theta;
-    f.flags = s.d_flags;
-    f.k = (int32_t)cs.k;
     f.need_theta = i + 1 < p.segs.size() ? 1 : 0;
     if (i + 1 == p.segs.size()) {
       f.final_out = ctx->d_lat + kLatAnswerOffset;
@@ -1315,26 +1309,15 @@ int search_latency_chain(const BatchCtx &c, const BatchCtx &cs, int32_t *out_idx
   HIPCHK(hipEventRecord(s.ev_done, st));
   rc = wait_latency_answer(ctx, s, seq);
   if (rc != BBQ_OK) return rc;
-  const uint64_t *hdr = ctx->h_lat + kLatAnswerOffset;
-  const uint32_t listed = (uint32_t)hdr[0], flags = (uint32_t)(hdr[0] >> 32), m = (uint32_t)hdr[1], replay = (uint32_t)(hdr[1] >> 32);
+  const LatAnswer r(ctx);
   s.timed = false;
-  if (flags == 0 && replay == 0) {  // answered on the device
-    const int64_t k = c.k;
-    for (uint32_t j = 0; j < m; ++j) {
-      const uint64_t e = hdr[2 + j];
-      const uint32_t bits = (uint32_t)e;
-      out_idx[j] = (int32_t)(uint32_t)(e >> 32);
-      memcpy(&out_score[j], &bits, 4);
-    }
-    (void)k;
-    out_n[0] = m;
-    ix->stats.candidates += listed;
-    *done = true;
+  if (r.flags == 0 && r.replay == 0) {  // answered on the device
+    r.take(ix, out_idx, out_score, out_n, done);
     return BBQ_OK;
   }
   // equal scores in or at the edge of the answer (or a flagged query): hand over to the general path's collection - the list on the
   // device is complete and it is this slot's
-  s.h_final[0] = (uint64_t)listed | ((uint64_t)flags << 32);
+  s.h_final[0] = (uint64_t)r.listed | ((uint64_t)r.flags << 32);
   s.h_final[1] = (uint64_t)1 << 32;
   s.busy = true;
   s.nq = 1;

@@ -1,6 +1,7 @@
-// bbq_kernel_common.h - device functions shared by the kernels of bbq_kernels.hip and bbq_latency_kernels.hip (gfx950 only): the
-// reference's float64 score formulas, the per-tile popcount loop, the score bound of the compact layout, block-wide scan and
-// order-statistic selection.  Everything here is __forceinline__: each kernel file gets its own copy.
+// bbq_kernel_common.h - device functions shared by the sweep kernels of bbq_kernels.hip, bbq_latency_kernels.hip and
+// bbq_mfma_kernels.hip (gfx950 only): the reference's float64 score formulas, the per-tile popcount loop, the score bound of the
+// compact layout, the per-row candidate test and the ways candidates leave a workgroup, block-wide scan and order-statistic
+// selection.  Everything here is __forceinline__: each kernel file gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbq_device.h"
@@ -100,9 +101,19 @@ __device__ __forceinline__ double score_f64(double qc, double ax, double ux, dou
   return t < 0.0 ? 1.0 / (1.0 - t / FBS) : t / FBS + 1.0;
 }
 
-// One tile = 64 rows, one row per lane.  W = compile-time number of 16-byte chunks per row: the chunks come in registers (load_tile)
+// qcDist of a 1-bit row from the popcounts of its AND with the query's bit-planes: plane p weighs 2^p
+template <int QB> __device__ __forceinline__ uint32_t plane_dot(const uint32_t (&acc)[QB]) {
+  uint32_t qc = 0;
+#pragma unroll
+  for (int p = 0; p < QB; ++p) qc += acc[p] << p;
+  return qc;
+}
+
+// One tile = 64 rows, one row per lane.  W = compile-time number of 16-byte chunks per row: the chunks come in registers (load_tile).
+// Returns qcDist; `ones` = the row's popcount
 template <int QB, int W>
-__device__ __forceinline__ void tile_popcounts(const u32x4 (&c)[W], const u32x4 *__restrict__ s_planes, uint32_t (&acc)[QB], uint32_t &ones) {
+__device__ __forceinline__ uint32_t tile_popcounts(const u32x4 (&c)[W], const u32x4 *__restrict__ s_planes, uint32_t &ones) {
+  uint32_t acc[QB];
 #pragma unroll
   for (int p = 0; p < QB; ++p) acc[p] = 0;
   ones = 0;
@@ -112,12 +123,14 @@ __device__ __forceinline__ void tile_popcounts(const u32x4 (&c)[W], const u32x4 
     for (int p = 0; p < QB; ++p) acc[p] = popc4_acc(c[j] & s_planes[j * QB + p], acc[p]);
     ones = popc4_acc(c[j], ones);
   }
+  return plane_dot<QB>(acc);
 }
 // any width (w16 chunks, known at run time): streamed chunk by chunk
 template <int QB>
-__device__ __forceinline__ void tile_popcounts_any(const uint8_t *__restrict__ tp, int lane, int w16, const u32x4 *__restrict__ s_planes,
-                                                   uint32_t (&acc)[QB], uint32_t &ones) {
+__device__ __forceinline__ uint32_t tile_popcounts_any(const uint8_t *__restrict__ tp, int lane, int w16, const u32x4 *__restrict__ s_planes,
+                                                       uint32_t &ones) {
   const u32x4 *__restrict__ cp = reinterpret_cast<const u32x4 *>(tp) + lane;
+  uint32_t acc[QB];
 #pragma unroll
   for (int p = 0; p < QB; ++p) acc[p] = 0;
   ones = 0;
@@ -127,6 +140,7 @@ __device__ __forceinline__ void tile_popcounts_any(const uint8_t *__restrict__ t
     for (int p = 0; p < QB; ++p) acc[p] += popc4(c & s_planes[j * QB + p]);
     ones += popc4(c);
   }
+  return plane_dot<QB>(acc);
 }
 
 // Upper bound of the score when only the COMPACT corrections are known (kLayoutCompact).
@@ -174,6 +188,72 @@ __device__ __forceinline__ double score_upper_bound(double qc, double al, double
     u = t_up < 0.0 ? 1.0 / (1.0 - t_up / FBS) : t_up / FBS + 1.0;
   }
   return u + kRoundRel * (fabs(u) + 1.0);
+}
+
+// ---- one row of a sweep ----------------------------------------------------------------------------------------------------------
+// the tile's additive-correction range in the compact layout: EUCLIDEAN scores fall with it (take the minimum), the others rise (maximum)
+__device__ __forceinline__ float tile_add_bound(const IndexView &v, int64_t tile, int sim) { return v.add_range[tile * 2 + (sim == 0 ? 0 : 1)]; }
+
+// compact layout: the row's bf16 {lower, upper} word and the tile's additive bound give an upper bound of its score.  NaN (no bound)
+// passes; otherwise the row can only matter if even its upper bound beats the threshold
+__device__ __forceinline__ bool compact_bound_passes(bool valid, uint32_t qc, uint32_t cw, float aadd, double x1, const QueryParams &p, uint32_t theta) {
+  const double al = (double)__uint_as_float(cw << 16);
+  const double au = (double)__uint_as_float(cw & 0xffff0000u);
+  const double ub = score_upper_bound((double)qc, al, au, (double)aadd, x1, p);
+  const float ub32 = (float)ub;
+  return valid && ((ub32 != ub32) || key_of_bits(__float_as_uint(ub32)) > theta);
+}
+
+// the row's exact corrections from the compact layout's side array: {lower, upper} and additionalCorrection.  STREAM: the dense paths,
+// which read every row once (non-temporal loads)
+template <bool STREAM = false>
+__device__ __forceinline__ void exact_corrections(const double *exact, int64_t row, f64x2 &lu, double &xadd) {
+  const f64x2 *__restrict__ ex = reinterpret_cast<const f64x2 *>(exact + row * 4);
+  if constexpr (STREAM) {
+    lu = BBQ_STREAM_LOAD(ex);
+    xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(ex + 1));
+  } else {
+    lu = ex[0];
+    xadd = reinterpret_cast<const double *>(ex + 1)[0];
+  }
+}
+
+// the candidate test on the exact score, rounded to f32 as the reference stores it (Float32Array, src/binaryQuantizationFormat.ts:353,378):
+// a valid row is a candidate iff its score is no NaN and its key beats the threshold.  A valid row with a NaN score sets `nan_seen`.
+__device__ __forceinline__ bool exact_key_passes(bool valid, float s32, uint32_t theta, bool &nan_seen) {
+  if (valid && (s32 != s32)) nan_seen = true;
+  return valid && (s32 == s32) && key_of_bits(__float_as_uint(s32)) > theta;
+}
+// a candidate entry: global row << 32 | f32 score bits - entries of distinct rows order like their rows
+__device__ __forceinline__ uint64_t candidate_entry(int64_t row_id, float s32) { return ((uint64_t)(uint32_t)row_id << 32) | __float_as_uint(s32); }
+
+// ---- candidates leaving a workgroup ------------------------------------------------------------------------------------------------
+// the cnt staged entries of a chunk into its slot, row-ordered: rows are distinct, so ranking by counting puts them in row order
+// (thread `t` of `nt` takes entries t, t + nt, ...)
+__device__ __forceinline__ void write_ranked(const uint64_t *__restrict__ src, uint32_t cnt, uint64_t *__restrict__ out, int t, int nt) {
+  for (uint32_t i = t; i < cnt; i += nt) {
+    const uint64_t e = src[i];
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < cnt; ++j) rank += (src[j] < e) ? 1u : 0u;
+    out[rank] = e;
+  }
+}
+
+// the workgroup's cnt > 0 staged entries (workgroup-uniform) into the query's list behind the `base` entries of the earlier segments,
+// unordered: ONE atomic on the query's append counter reserves the room for all of them, handed to the workgroup through the LDS word
+// s_at.  A list without that room flags the query (kFlagOverflow) and takes none of them.
+template <int NT>
+__device__ __forceinline__ void append_to_list(const uint64_t *s_ent, uint32_t cnt, uint32_t *counter, int64_t base, uint64_t *__restrict__ list,
+                                               int64_t list_cap, uint32_t *flags, uint32_t *s_at) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *s_at = atomicAdd(counter, cnt);
+  __syncthreads();
+  const int64_t at = base + *s_at;
+  if (at + cnt > list_cap) {
+    if (tid == 0) atomicOr(flags, kFlagOverflow);
+    return;
+  }
+  for (uint32_t i = tid; i < cnt; i += NT) list[at + i] = s_ent[i];
 }
 
 __device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32_t *s_wave, uint32_t &total) {

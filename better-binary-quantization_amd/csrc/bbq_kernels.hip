@@ -133,69 +133,41 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a) 
     // every load of the tile is issued up front: the row's code chunks and its corrections
     f64x2 lu = {0.0, 0.0};
     double xadd = 0.0, x1 = 0.0;
-    uint32_t cpk0 = 0, cpk1 = 0;
-    uint32_t qc = 0, ones;
+    uint32_t cw = 0;
+    float aadd = 0.0f;
+    uint32_t qc, ones;
     constexpr int CORR = !COMPACT ? 2 : (DENSE ? 0 : 1);
     if constexpr (W > 0) {
       u32x4 c[W];
-      load_tile<W, CORR>(tp, lane, a.idx.has_x1 != 0, resident, a.idx.nt_delta, c, cpk0, lu, xadd, x1);
-      if constexpr (COMPACT && DENSE) {
-        const f64x2 *__restrict__ ex = reinterpret_cast<const f64x2 *>(a.idx.exact + row * 4);
-        lu = BBQ_STREAM_LOAD(ex);
-        xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(ex + 1));
-      }
-      // the tile's additive-correction range: EUCLIDEAN scores fall with it (take the minimum), the others rise (maximum)
-      if constexpr (COMPACT && !DENSE) cpk1 = __float_as_uint(a.idx.add_range[tile * 2 + (p.sim == 0 ? 0 : 1)]);
-      if constexpr (SB == 1) {
-        uint32_t acc[QB];
-        tile_popcounts<QB, W>(c, s_planes, acc, ones);
-#pragma unroll
-        for (int pl = 0; pl < QB; ++pl) qc += acc[pl] << pl;
-      } else {
-        tile_dot_multibit<QB, W, SB>(c, s_planes, qc, ones);
-      }
+      load_tile<W, CORR>(tp, lane, a.idx.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
+      if constexpr (COMPACT && DENSE) exact_corrections<true>(a.idx.exact, row, lu, xadd);
+      if constexpr (COMPACT && !DENSE) aadd = tile_add_bound(a.idx, tile, p.sim);
+      if constexpr (SB == 1) qc = tile_popcounts<QB, W>(c, s_planes, ones);
+      else tile_dot_multibit<QB, W, SB>(c, s_planes, qc, ones);
     } else {  // a row width without a compiled kernel: streamed chunk by chunk
       if constexpr (!COMPACT) {
         lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(cr) + lane);
         xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + 1024) + lane);
         if (a.idx.has_x1) x1 = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + 1536) + lane);
       } else if constexpr (DENSE) {
-        const f64x2 *__restrict__ ex = reinterpret_cast<const f64x2 *>(a.idx.exact + row * 4);
-        lu = BBQ_STREAM_LOAD(ex);
-        xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(ex + 1));
+        exact_corrections<true>(a.idx.exact, row, lu, xadd);
       } else {
-        cpk0 = BBQ_STREAM_LOAD(reinterpret_cast<const uint32_t *>(cr) + lane);
-        cpk1 = __float_as_uint(a.idx.add_range[tile * 2 + (p.sim == 0 ? 0 : 1)]);
+        cw = BBQ_STREAM_LOAD(reinterpret_cast<const uint32_t *>(cr) + lane);
+        aadd = tile_add_bound(a.idx, tile, p.sim);
       }
-      if constexpr (SB == 1) {
-        uint32_t acc[QB];
-        tile_popcounts_any<QB>(tp, lane, w16, s_planes, acc, ones);
-#pragma unroll
-        for (int pl = 0; pl < QB; ++pl) qc += acc[pl] << pl;
-      } else {
-        tile_dot_multibit_any<QB, SB>(tp, lane, w16, s_planes, qc, ones);
-      }
+      if constexpr (SB == 1) qc = tile_popcounts_any<QB>(tp, lane, w16, s_planes, ones);
+      else tile_dot_multibit_any<QB, SB>(tp, lane, w16, s_planes, qc, ones);
     }
     if (!a.idx.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
 
     bool need_exact = true;
     if constexpr (COMPACT && !DENSE) {
-      const double al = (double)__uint_as_float(cpk0 << 16);
-      const double au = (double)__uint_as_float(cpk0 & 0xffff0000u);
-      const double aadd = (double)__uint_as_float(cpk1);
-      // NaN (no bound) passes; otherwise the row can only matter if even its upper bound beats the threshold
-      const double ub = score_upper_bound((double)qc, al, au, aadd, x1, p);
-      const float ub32 = (float)ub;
-      need_exact = valid && ((ub32 != ub32) || key_of_bits(__float_as_uint(ub32)) > theta);
-      if (need_exact) {
-        const f64x2 *__restrict__ ex = reinterpret_cast<const f64x2 *>(a.idx.exact + row * 4);
-        lu = ex[0];
-        xadd = reinterpret_cast<const double *>(ex + 1)[0];
-      }
+      need_exact = compact_bound_passes(valid, qc, cw, aadd, x1, p, theta);
+      if (need_exact) exact_corrections(a.idx.exact, row, lu, xadd);
     }
     if (need_exact) {
       const double s64 = score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
-      const float s32 = (float)s64;  // Float32Array store, src/binaryQuantizationFormat.ts:353,378
+      const float s32 = (float)s64;
       const uint32_t bits = __float_as_uint(s32);
       if (valid && (s32 != s32)) nan_seen = true;
       if constexpr (DENSE) {
@@ -205,11 +177,9 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a) 
           if (a.dense_qcdist) a.dense_qcdist[o] = (int32_t)qc;
           if (a.dense_score64) a.dense_score64[o] = s64;
         }
-      } else {
-        if (valid && (s32 == s32) && key_of_bits(bits) > theta) {
-          const uint32_t slot = atomicAdd(s_cnt, 1u);
-          if (slot < stage_cap) s_ent[slot] = ((uint64_t)(uint32_t)(a.row_id_base + row) << 32) | bits;
-        }
+      } else if (valid && (s32 == s32) && key_of_bits(bits) > theta) {
+        const uint32_t slot = atomicAdd(s_cnt, 1u);
+        if (slot < stage_cap) s_ent[slot] = candidate_entry(a.row_id_base + row, s32);
       }
     }
   }
@@ -220,16 +190,9 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a) 
     if (a.append_lists) {  // workgroup-uniform
       const uint32_t cnt = *s_cnt;
       if (cnt == 0) return;
-      __syncthreads();  // everyone has read *s_cnt
-      if (tid == 0) *s_cnt = atomicAdd(a.append_counts + (size_t)q * kAppendStride, cnt);
-      __syncthreads();
-      const int64_t at = (int64_t)a.append_base[2 * q] + *s_cnt;
-      if (at + cnt > a.append_cap) {
-        if (tid == 0) atomicOr(a.flags + q, kFlagOverflow);
-        return;
-      }
-      uint64_t *__restrict__ dst = a.append_lists + (size_t)q * a.append_cap + at;
-      for (uint32_t i = tid; i < cnt; i += NT) dst[i] = s_ent[i];
+      __syncthreads();  // everyone has read *s_cnt: it takes the reserved offset
+      append_to_list<NT>(s_ent, cnt, a.append_counts + (size_t)q * kAppendStride, a.append_base[2 * q], a.append_lists + (size_t)q * a.append_cap,
+                         a.append_cap, a.flags + q, s_cnt);
       return;
     }
     uint32_t cnt = *s_cnt;
@@ -258,12 +221,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a) 
         count_word = cnt;
       }
     }
-    for (uint32_t i = tid; i < cnt; i += NT) {  // rows are distinct: rank by counting puts them in row order
-      const uint64_t e = s_ent[i];
-      uint32_t rank = 0;
-      for (uint32_t j = 0; j < cnt; ++j) rank += (s_ent[j] < e) ? 1u : 0u;
-      out[rank] = e;
-    }
+    write_ranked(s_ent, cnt, out, tid, NT);
     if (tid == 0) a.counts[(size_t)q * a.n_chunks + blockIdx.x] = count_word;
   }
 }
@@ -310,16 +268,12 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_shared_kernel(const ScanA
     const bool valid = row < a.idx.n_rows;
     u32x4 c[W];
     f64x2 lu = {0.0, 0.0};
-    double xadd = 0.0, x1 = 0.0, al = 0.0, au = 0.0, aadd = 0.0;
+    double xadd = 0.0, x1 = 0.0;
     uint32_t cw = 0;
+    float aadd = 0.0f;
     load_tile<W, COMPACT ? 1 : 2>(tp, lane, a.idx.has_x1 != 0, chunk_is_resident(chunk, a.idx), a.idx.nt_delta, c, cw, lu, xadd, x1);
     bool have_exact = !COMPACT;
-    if constexpr (COMPACT) {
-      al = (double)__uint_as_float(cw << 16);
-      au = (double)__uint_as_float(cw & 0xffff0000u);
-      // tile range of the additive correction; the queries of one call share the similarity function
-      aadd = (double)a.idx.add_range[tile * 2 + (s_qp[0].sim == 0 ? 0 : 1)];
-    }
+    if constexpr (COMPACT) aadd = tile_add_bound(a.idx, tile, s_qp[0].sim);  // the queries of one call share the similarity function
     uint32_t ones = 0;
 #pragma unroll
     for (int j = 0; j < W; ++j) ones += popc4(c[j]);
@@ -343,24 +297,18 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_shared_kernel(const ScanA
       const uint32_t theta = s_theta[b];
       bool need_exact = valid;
       if constexpr (COMPACT) {
-        const double ub = score_upper_bound((double)qc, al, au, aadd, x1, p);
-        const float ub32 = (float)ub;
-        need_exact = valid && ((ub32 != ub32) || key_of_bits(__float_as_uint(ub32)) > theta);
+        need_exact = compact_bound_passes(valid, qc, cw, aadd, x1, p, theta);
         if (need_exact && !have_exact) {
-          const f64x2 *__restrict__ ex = reinterpret_cast<const f64x2 *>(a.idx.exact + row * 4);
-          lu = ex[0];
-          xadd = reinterpret_cast<const double *>(ex + 1)[0];
+          exact_corrections(a.idx.exact, row, lu, xadd);
           have_exact = true;
         }
       }
       if (need_exact) {
-        const double s64 = score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
-        const float s32 = (float)s64;
-        const uint32_t bits = __float_as_uint(s32);
+        const float s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
         if (s32 != s32) nan_mask |= 1u << b;
-        if ((s32 == s32) && key_of_bits(bits) > theta) {
+        if ((s32 == s32) && key_of_bits(__float_as_uint(s32)) > theta) {
           const uint32_t slot = atomicAdd(&s_cnt[b], 1u);
-          if (slot < (uint32_t)a.cap) s_ent[(size_t)b * a.cap + slot] = ((uint64_t)(uint32_t)(a.row_id_base + row) << 32) | bits;
+          if (slot < (uint32_t)a.cap) s_ent[(size_t)b * a.cap + slot] = candidate_entry(a.row_id_base + row, s32);
         }
       }
     }
@@ -375,14 +323,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_shared_kernel(const ScanA
       if (tid == 0) atomicOr(a.flags + q0 + b, kFlagOverflow);
       cnt = (uint32_t)a.cap;
     }
-    const uint64_t *__restrict__ src = s_ent + (size_t)b * a.cap;
-    uint64_t *__restrict__ out = a.entries + ((size_t)(q0 + b) * a.n_chunks + blockIdx.x) * (size_t)a.cap;
-    for (uint32_t i = tid; i < cnt; i += NT) {
-      const uint64_t e = src[i];
-      uint32_t rank = 0;
-      for (uint32_t j = 0; j < cnt; ++j) rank += (src[j] < e) ? 1u : 0u;
-      out[rank] = e;
-    }
+    write_ranked(s_ent + (size_t)b * a.cap, cnt, a.entries + ((size_t)(q0 + b) * a.n_chunks + blockIdx.x) * (size_t)a.cap, tid, NT);
     if (tid == 0) a.counts[(size_t)(q0 + b) * a.n_chunks + blockIdx.x] = cnt;
   }
 }

@@ -1,8 +1,8 @@
 // bbq_latency_kernels.hip - the sweeps of the single-query call (the reference's own call shape: one synchronous
 // searchNearestNeighbors per query, src/binaryQuantizationFormat.ts:308-412).
 //
-//   bbq_lat_scan_kernel     the sweep of one segment: exactly the rows / bound test / exact scores / candidates of bbq_scan_kernel in
-//                           append mode, but the query arrives in the KERNEL ARGUMENTS of every launch: no host-to-device copy stands
+//   bbq_lat_scan_kernel     the sweep of one segment: the rows of bbq_scan_kernel in append mode, through the same per-row pieces
+//                           (bbq_kernel_common.h), but the query arrives in the KERNEL ARGUMENTS of every launch: no host-to-device copy stands
 //                           in front of the chain (bbq_core.cpp search_latency_chain; the answer leaves through mapped host memory
 //                           the same way, written by the last finalize launch).  The first launch covers the dense prefix: its
 //                           threshold is zero, so every row is scored exactly and listed (the reference heap is still filling there).
@@ -23,8 +23,7 @@ namespace bbq {
 
 constexpr int kLatThreads = kChunkRows;          // scan workgroup
 
-// one segment of the single-query sweep: the sparse path of bbq_scan_kernel in append mode (same rows, same bound test, same exact
-// scores, same candidates) with the query in the kernel arguments
+// one segment of the single-query sweep: the sparse path of bbq_scan_kernel in append mode with the query in the kernel arguments
 template <int QB, int W, bool COMPACT>
 __global__ __launch_bounds__(kLatThreads) void bbq_lat_scan_kernel(const LatScanArgs a) {
   __shared__ __attribute__((aligned(16))) u32x4 s_planes[W * QB];
@@ -54,53 +53,32 @@ __global__ __launch_bounds__(kLatThreads) void bbq_lat_scan_kernel(const LatScan
     const bool valid = row < a.idx.n_rows;
     f64x2 lu = {0.0, 0.0};
     double xadd = 0.0, x1 = 0.0;
-    uint32_t cpk0 = 0, cpk1 = 0;
+    uint32_t cw = 0;
+    float aadd = 0.0f;
     u32x4 c[W];
-    load_tile<W, COMPACT ? 1 : 2>(tp, lane, a.idx.has_x1 != 0, chunk_is_resident(chunk, a.idx), a.idx.nt_delta, c, cpk0, lu, xadd, x1);
-    if constexpr (COMPACT) cpk1 = __float_as_uint(a.idx.add_range[tile * 2 + (p.sim == 0 ? 0 : 1)]);
-    uint32_t acc[QB], ones, qc = 0;
-    tile_popcounts<QB, W>(c, s_planes, acc, ones);
-#pragma unroll
-    for (int pl = 0; pl < QB; ++pl) qc += acc[pl] << pl;
+    load_tile<W, COMPACT ? 1 : 2>(tp, lane, a.idx.has_x1 != 0, chunk_is_resident(chunk, a.idx), a.idx.nt_delta, c, cw, lu, xadd, x1);
+    if constexpr (COMPACT) aadd = tile_add_bound(a.idx, tile, p.sim);
+    uint32_t ones;
+    const uint32_t qc = tile_popcounts<QB, W>(c, s_planes, ones);
     if (!a.idx.has_x1) x1 = (double)ones;
     bool need_exact = true;
     if constexpr (COMPACT) {
-      const double al = (double)__uint_as_float(cpk0 << 16);
-      const double au = (double)__uint_as_float(cpk0 & 0xffff0000u);
-      const double aadd = (double)__uint_as_float(cpk1);
-      const double ub = score_upper_bound((double)qc, al, au, aadd, x1, p);
-      const float ub32 = (float)ub;
-      need_exact = valid && ((ub32 != ub32) || key_of_bits(__float_as_uint(ub32)) > theta);
-      if (need_exact) {
-        const f64x2 *__restrict__ ex = reinterpret_cast<const f64x2 *>(a.idx.exact + row * 4);
-        lu = ex[0];
-        xadd = reinterpret_cast<const double *>(ex + 1)[0];
-      }
+      need_exact = compact_bound_passes(valid, qc, cw, aadd, x1, p, theta);
+      if (need_exact) exact_corrections(a.idx.exact, row, lu, xadd);
     }
     if (need_exact) {
-      const double s64 = score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
-      const float s32 = (float)s64;
-      const uint32_t bits = __float_as_uint(s32);
-      if (valid && (s32 != s32)) nan_seen = true;
-      if (valid && (s32 == s32) && key_of_bits(bits) > theta) {
+      const float s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
+      if (exact_key_passes(valid, s32, theta, nan_seen)) {
         const uint32_t slot = atomicAdd(&s_misc[14], 1u);
-        s_ent[slot] = ((uint64_t)(uint32_t)(a.row_id_base + row) << 32) | bits;  // at most one per thread: slot < kChunkRows
+        s_ent[slot] = candidate_entry(a.row_id_base + row, s32);  // at most one per thread: slot < kChunkRows
       }
     }
   }
   if (__any(nan_seen) && lane == 0) atomicOr(a.flags, kFlagNaN);
   __syncthreads();
   const uint32_t cnt = s_misc[14];
-  if (cnt) {  // workgroup-uniform
-    if (tid == 0) s_misc[15] = atomicAdd(a.append_count, cnt);
-    __syncthreads();
-    const int64_t at = (a.first ? 0 : (int64_t)a.list_counts[0]) + s_misc[15];
-    if (at + cnt > a.list_cap) {
-      if (tid == 0) atomicOr(a.flags, kFlagOverflow);
-    } else {
-      for (uint32_t i = tid; i < cnt; i += kLatThreads) a.list[at + i] = s_ent[i];
-    }
-  }
+  if (cnt)  // workgroup-uniform
+    append_to_list<kLatThreads>(s_ent, cnt, a.append_count, a.first ? 0 : (int64_t)a.list_counts[0], a.list, a.list_cap, a.flags, &s_misc[15]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -129,15 +107,9 @@ __global__ __launch_bounds__(kLatThreads) void bbq_lat_pre_kernel(const LatPreAr
     u32x4 c[W];
     // the prefix the threshold is sampled from is also the part of the index that stays cache-resident
     load_tile<W, COMPACT ? 0 : 2>(tp, lane, a.idx.has_x1 != 0, chunk_is_resident((int64_t)blockIdx.x, a.idx), a.idx.nt_delta, c, unused, lu, xadd, x1);
-    if constexpr (COMPACT) {
-      const f64x2 *__restrict__ ex = reinterpret_cast<const f64x2 *>(a.idx.exact + (valid ? row : 0) * 4);
-      lu = BBQ_STREAM_LOAD(ex);
-      xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(ex + 1));
-    }
-    uint32_t acc[QB], ones, qc = 0;
-    tile_popcounts<QB, W>(c, s_planes, acc, ones);
-#pragma unroll
-    for (int pl = 0; pl < QB; ++pl) qc += acc[pl] << pl;
+    if constexpr (COMPACT) exact_corrections<true>(a.idx.exact, valid ? row : 0, lu, xadd);
+    uint32_t ones;
+    const uint32_t qc = tile_popcounts<QB, W>(c, s_planes, ones);
     if (!a.idx.has_x1) x1 = (double)ones;
     const float s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
     const bool nan = valid && (s32 != s32);

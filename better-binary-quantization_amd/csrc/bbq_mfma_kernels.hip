@@ -56,6 +56,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "bbq_device.h"
+#include "bbq_kernel_common.h"
 #include "bbq_launch.h"
 
 #pragma clang fp contract(off)
@@ -85,27 +86,6 @@ template <> struct MfmaNum<false> {
 template <> struct MfmaNum<true> {   // S is chosen per call: 1/4 for query values up to 15, 1/2 up to 7, 1 up to 3 (MfmaArgs::fp_scale)
   static constexpr float S = 0.25f, ulp = 0.0625f, bias = 786432.0f, mag_limit = 110000.0f, pass_all = 786432.0f + 131072.0f;
 };
-
-// ---- exact pieces shared with bbq_kernels.hip (kept textually identical: same operation order) ----------------------
-__device__ __forceinline__ double m_js_max0(double x) { return (x != x) ? x : (x > 0.0 ? x : 0.0); }
-
-__device__ __forceinline__ double m_score_f64(double qc, double ax, double ux, double xadd, double x1, const QueryParams &p) {
-  const double lx = ux - ax;
-  const double t1 = (ax * p.ay) * p.dimd;
-  const double t2 = (p.ay * lx) * x1;
-  const double t3 = (ax * p.ly) * p.y1;
-  const double t4 = (lx * p.ly) * qc;
-  const double s = ((t1 + t2) + t3) + t4;
-  if (p.sim == 0) {
-    const double e = (p.qadd + xadd) - (2.0 * s);
-    return m_js_max0(1.0 / (1.0 + e));
-  }
-  const double t = p.one_bit ? (s + ((p.qadd + xadd) - p.cdp)) : (((s + p.qadd) + xadd) - p.cdp);
-  if (p.sim == 1) return m_js_max0((1.0 + t) / 2.0);
-  if (p.one_bit) return t < 0.0 ? 1.0 / (1.0 - t) : t + 1.0;
-  const double FBS = 1.0 / 15.0;
-  return t < 0.0 ? 1.0 / (1.0 - t / FBS) : t / FBS + 1.0;
-}
 
 // conservative lower edge, in z-space, of "score > theta" for one query.
 //   COSINE / MIP: z = s + xadd,  score = f(z + qadd - cdp) with f increasing
@@ -198,14 +178,14 @@ struct MfmaArgs {
   int32_t chunks_per_block;  // consecutive chunks one workgroup walks with the same queries (launch_mfma_t)
   float fp_scale;            // FP form: every product is fp_scale * q (1/4, 1/2 or 1: the largest the query values leave room for in e2m3)
   int32_t groups_per_block;  // 1 or 2 groups of 32 queries per workgroup: a tile is loaded (and its row constants derived) once for all of them
-  int32_t stage_cap;         // candidates per query a workgroup stages in LDS (slot mode: the chunk slots' capacity)
+  int32_t stage_cap;         // candidates per query a workgroup stages in LDS before they go to the query's list
   int32_t queue_cap;         // survivors per wave, tile and group that wait for their exact scores
 };
 
 // Pairs that pass the pre-filter are pushed to a per-wave LDS queue (packed qc | row-in-tile << 20 | query << 26) and
 // scored exactly afterwards by ONE copy of the exact code, 64 pairs at a time.
 constexpr int kMfmaQueueCap = 512;        // one group per workgroup
-constexpr int kMfmaQueueCapTwo = 128;     // two groups per workgroup (append mode only): LDS for two workgroups per CU
+constexpr int kMfmaQueueCapTwo = 128;     // two groups per workgroup: LDS for two workgroups per CU
 constexpr int kMfmaStageCapTwo = 32;
 constexpr int kMfmaMaxChunksPerBlock = 16;
 
@@ -589,67 +569,44 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
         const int64_t row = tile * kTileRows + rit;
         const f64x2m lu = s_lu[wave * 64 + rit], ax = s_ax[wave * 64 + rit];
         const double lo = lu.x, up = lu.y, ad = ax.x, x1d = ax.y;
-        const double s64 = m_score_f64((double)qc, lo, up, ad, x1d, pq);
-        const float s32 = (float)s64;
-        const uint32_t bits = __float_as_uint(s32);
-        if (s32 != s32) atomicOr(a.s.flags + q0 + qn, kFlagNaN);
-        else if (key_of_bits(bits) > s_theta[qn]) {
-          const uint64_t ent = ((uint64_t)(uint32_t)(a.s.row_id_base + row) << 32) | bits;
-          // staged in the workgroup's LDS lists.  Slot mode: written row-ordered after every chunk.  Append mode: flushed once, when the
-          // workgroup is done - one atomic per query and workgroup reserves the room (an atomic that returns a value is a trip to the
-          // memory side: per survivor it cost the early segments, where a few per cent of the pairs survive, more than the sweep itself)
+        const float s32 = (float)score_f64((double)qc, lo, up, ad, x1d, pq);
+        bool nan = false;
+        if (exact_key_passes(true, s32, s_theta[qn], nan)) {
+          const uint64_t ent = candidate_entry(a.s.row_id_base + row, s32);
+          // staged in the workgroup's LDS lists, flushed once, when the workgroup is done - one atomic per query and workgroup reserves
+          // the room (an atomic that returns a value is a trip to the memory side: per survivor it cost the early segments, where a few
+          // per cent of the pairs survive, more than the sweep itself)
           const uint32_t slot = atomicAdd(&s_cnt[qn], 1u);
           if (slot < (uint32_t)scap) s_ent[(size_t)qn * scap + slot] = ent;
-          else if (a.s.append_lists) {  // the staging list is full: straight into the query's list
+          else {  // the staging list is full: straight into the query's list
             const uint32_t gs = atomicAdd(a.s.append_counts + (size_t)(q0 + qn) * kAppendStride, 1u);
             const int64_t at = (int64_t)a.s.append_base[2 * (q0 + qn)] + gs;
             if (at < a.s.append_cap) a.s.append_lists[(size_t)(q0 + qn) * a.s.append_cap + at] = ent;
             else atomicOr(a.s.flags + q0 + qn, kFlagOverflow);
           }
         }
+        if (nan) atomicOr(a.s.flags + q0 + qn, kFlagNaN);
       }
       s_qcount[wave] = 0;  // this wave's queue is its own: ready for its next group or tile
     }
     }  // groups of this workgroup
   }
-  if (a.s.append_lists) continue;  // workgroup-uniform: nothing to flush per chunk, nobody to wait for
-  __syncthreads();
-  for (int b = wave; b < nb; b += NW) {  // each wave writes the lists of its share of the queries
-    uint32_t cnt = s_cnt[b];
-    if (cnt > (uint32_t)scap) {
-      if (lane == 0) atomicOr(a.s.flags + q0 + b, kFlagOverflow);
-      cnt = (uint32_t)scap;
-    }
-    const uint64_t *__restrict__ src = s_ent + (size_t)b * scap;
-    uint64_t *__restrict__ out = a.s.entries + ((size_t)(q0 + b) * a.s.n_chunks + lc) * (size_t)a.s.cap;
-    for (uint32_t i = lane; i < cnt; i += 64) {
-      const uint64_t e = src[i];
-      uint32_t rank = 0;
-      for (uint32_t j = 0; j < cnt; ++j) rank += (src[j] < e) ? 1u : 0u;
-      out[rank] = e;
-    }
-    if (lane == 0) a.s.counts[(size_t)(q0 + b) * a.s.n_chunks + lc] = cnt;
-  }
-  __syncthreads();                       // everybody has read the counters of this chunk ...
-  if (tid < nqb) s_cnt[tid] = 0;
-  __syncthreads();                       // ... and sees them cleared before the next chunk's survivors arrive
   }  // chunks of this workgroup
-  if (a.s.append_lists) {  // append mode: the workgroup's staged candidates go to the queries' lists (unordered inside the segment; the
-                           // finalize launch takes its keys from there and the rare host replay sorts)
-    __syncthreads();
-    for (int b = wave; b < nb; b += NW) {
-      const uint32_t cnt = min(s_cnt[b], (uint32_t)scap);
-      if (cnt == 0) continue;  // wave-uniform
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(a.s.append_counts + (size_t)(q0 + b) * kAppendStride, cnt);
-      base = __builtin_amdgcn_readfirstlane(base);
-      const int64_t at0 = (int64_t)a.s.append_base[2 * (q0 + b)] + base;
-      const uint64_t *__restrict__ src = s_ent + (size_t)b * scap;
-      uint64_t *__restrict__ out = a.s.append_lists + (size_t)(q0 + b) * a.s.append_cap;
-      for (uint32_t i = lane; i < cnt; i += 64) {
-        if (at0 + i < a.s.append_cap) out[at0 + i] = src[i];
-        else atomicOr(a.s.flags + q0 + b, kFlagOverflow);
-      }
+  // the workgroup's staged candidates go to the queries' lists (unordered inside the segment; the finalize launch takes its keys from
+  // there and the rare host replay sorts)
+  __syncthreads();
+  for (int b = wave; b < nb; b += NW) {
+    const uint32_t cnt = min(s_cnt[b], (uint32_t)scap);
+    if (cnt == 0) continue;  // wave-uniform
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(a.s.append_counts + (size_t)(q0 + b) * kAppendStride, cnt);
+    base = __builtin_amdgcn_readfirstlane(base);
+    const int64_t at0 = (int64_t)a.s.append_base[2 * (q0 + b)] + base;
+    const uint64_t *__restrict__ src = s_ent + (size_t)b * scap;
+    uint64_t *__restrict__ out = a.s.append_lists + (size_t)(q0 + b) * a.s.append_cap;
+    for (uint32_t i = lane; i < cnt; i += 64) {
+      if (at0 + i < a.s.append_cap) out[at0 + i] = src[i];
+      else atomicOr(a.s.flags + q0 + b, kFlagOverflow);
     }
   }
 }
@@ -663,12 +620,12 @@ static size_t mfma_smem_bytes(int w16, int stage_cap, bool fp, int gpb, int queu
          nqb * (sizeof(QueryParams) + 4 + 4) + 32 + nqb * (size_t)stage_cap * 8 + 64;
 }
 
-// Two groups per workgroup where the staging fits the CU as before (two workgroups per CU up to 1024-d, one beyond) - in append mode
-// only, where the staged lists may be shorter than the chunk slots (a full list overflows into the query's list in memory)
+// Two groups per workgroup where the staging fits the CU as before (two workgroups per CU up to 1024-d, one beyond): the staged lists
+// may be shorter than the chunk slots (a full list overflows into the query's list in memory)
 // (the int8 form up to 1024-d stays at one group: with two its fragment reads are scheduled across the groups and spill)
 constexpr bool mfma_two_groups_built(int w16, bool fp) { return fp || w16 > 8; }
 static int mfma_groups_per_block(const ScanArgs &a, int groups, bool fp) {
-  if (groups < 2 || !a.append_lists || !mfma_two_groups_built(a.idx.w16, fp)) return 1;
+  if (groups < 2 || !mfma_two_groups_built(a.idx.w16, fp)) return 1;
   // the chunk slots' capacity says how many candidates the plan expects here (cap_for: lam + 8 sqrt(lam) + 16 for lam candidates per
   // chunk and query): up to 64 slots a tile and group has 4 lam <= 62 survivors on average, eight standard deviations below the queue
   if (a.cap > 64) return 1;
@@ -712,9 +669,10 @@ static hipError_t launch_mfma_w(const MfmaArgs &a, bool compact, bool fp, int nq
   return fp ? launch_mfma_t<W, false, true>(a, nq, nc, s) : launch_mfma_t<W, false, false>(a, nq, nc, s);
 }
 
+// the sweep appends its candidates to the queries' lists (ScanArgs::append_lists): it has no chunk-slot output
 bool mfma_sweep_supported(const ScanArgs &a) {
   const int w = a.idx.w16;
-  if (a.idx.store_bits != 1 || !(w == 1 || w == 6 || w == 8 || w == 12)) return false;
+  if (!a.append_lists || a.idx.store_bits != 1 || !(w == 1 || w == 6 || w == 8 || w == 12)) return false;
   return mfma_smem_bytes(w, a.cap, false, 1, kMfmaQueueCap) <= 150 * 1024;
 }
 
@@ -725,6 +683,7 @@ int mfma_queries_per_tile_load(const ScanArgs &a, int n_queries, bool fp) {
 }
 
 hipError_t launch_scan_mfma(const ScanArgs &sa, const uint8_t *qbytes, const float *qmax, float fp_scale, int n_queries, int n_chunks, hipStream_t s) {
+  if (!sa.append_lists) return hipErrorInvalidValue;
   if (n_chunks <= 0 || n_queries <= 0) return hipSuccess;
   const bool fp = fp_scale > 0.0f;
   MfmaArgs a{sa, qbytes, qmax, n_queries, 1, fp_scale, 1, sa.cap, kMfmaQueueCap};

@@ -377,7 +377,7 @@ def test_bound_filter_nonfinite_corrections_take_the_exact_path():
 
 
 @pytest.mark.parametrize("sim", [0, 1, 2])
-@pytest.mark.parametrize("qb,dim", [(1, 128), (2, 768), (3, 128), (4, 768), (4, 1024), (7, 128), (4, 1536)])
+@pytest.mark.parametrize("qb,dim", [(1, 128), (2, 768), (3, 128), (4, 768), (4, 1024), (7, 128), (4, 1536), (7, 768), (7, 1024), (7, 1536)])
 def test_matrix_core_sweep_hostile_rows_and_queries(sim, qb, dim):
     """the shared sweep on the matrix cores (sweep_share 32: the threshold on the integer dot product as the MFMA's start value, FP6 x FP4
     operands for query values <= 15, int8 above) on rows its threshold cannot bound - zero and NEGATIVE interval widths, widths lost in
