@@ -37,13 +37,8 @@ int bbq_index_build_opts(const float *vectors, int64_t n, int32_t dim, int32_t s
   if (sim < 0 || sim > 2) return fail(BBQ_ERR_INVALID_ARG, "不支持的相似性函数: %d", sim);
   if (iters < 0 || lambda != lambda) return fail(BBQ_ERR_INVALID_ARG, "bad lambda/iters");
   if (n > 0xFFFFFFFFll) return fail(BBQ_ERR_UNSUPPORTED, "more than 2^32 rows");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(BBQ_ERR_NO_DEVICE, "no HIP device available: libbbq has no CPU fallback (hipGetDeviceCount found %d)", ndev);
-  if (device < 0 || device >= ndev) return fail(BBQ_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-  HIPCHK(hipSetDevice(device));
   DeviceCtx *ctx = nullptr;
-  int rc = get_ctx(device, &ctx);
+  int rc = open_device(device, &ctx);
   if (rc != BBQ_OK) return rc;
   std::lock_guard<std::mutex> lk(ctx->mu);
   hipStream_t st = ctx->aux_stream;
@@ -102,16 +97,8 @@ int bbq_index_build_opts(const float *vectors, int64_t n, int32_t dim, int32_t s
   BCHK(launch_build_centroid(d_vT4, n, dim, npad, d_cen, st));  // :214
   BCHK(hipMemcpyAsync(centroid, d_cen, (size_t)dim * 4, hipMemcpyDeviceToHost, st));
 
-  ix->device = device;
-  ix->ctx = ctx;
-  ix->slots = ctx->slots;
-  ix->aux_stream = ctx->aux_stream;
-  ix->d_aux_flags = ctx->d_aux_flags;
-  ix->dim = dim;
-  ix->index_bits = index_bits;
-  ix->store_bits = dim == 1 ? 1 : store_bits_of(index_bits);
-  ix->pb = row_bytes_of(dim, ix->store_bits);
-  ix->w16 = (ix->pb + 15) / 16;
+  rc = attach_index(ix.get(), ctx, device, dim, index_bits);
+  if (rc != BBQ_OK) { cleanup(); destroy_unlocked(ix.release()); return rc; }
   ix->n_rows = n;
   ix->row_base = 0;
   ix->want_compact = want_compact_of(opts);
@@ -128,7 +115,6 @@ int bbq_index_build_opts(const float *vectors, int64_t n, int32_t dim, int32_t s
     rc = storage_from_device_rows(ix.get(), ix->main, d_codes, d_corr, n, 0, true);
     if (rc == BBQ_OK && corr && hipMemcpy(corr, d_corr, (size_t)n * 32, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(BBQ_ERR_HIP, "bbq_index_build: copy of the corrections failed");
     if (rc == BBQ_OK && codes && hipMemcpy(codes, d_codes, (size_t)n * dim, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(BBQ_ERR_HIP, "bbq_index_build: copy of the codes failed");
-    if (rc == BBQ_OK) rc = ensure_aux_qbuf(ctx, qbuf_bytes_per_query_w(ix->w16));
     cleanup();
     if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
     *out = ix.release();
@@ -167,8 +153,6 @@ int bbq_index_build_opts(const float *vectors, int64_t n, int32_t dim, int32_t s
   sto.view.layout = ix->layout;
   sto.view.store_bits = 1;
   ix->centroid_dp = bbq_centroid_dp(centroid, dim);  // getCentroidDP(undefined), :113-121
-  rc = ensure_aux_qbuf(ctx, qbuf_bytes_per_query_w(ix->w16));
-  if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
   *out = ix.release();
   return BBQ_OK;
 }

@@ -10,32 +10,15 @@
 // reference walks segment j: rows at or below it can never enter the heap (bbq_replay.cpp).
 // Queries are processed in sub-batches (grid.y = queries, each query sweeps the index on its own), and
 // sub-batches are pipelined over NSLOT streams so the host replay of one overlaps the scan of the next.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
-#include <algorithm>
-#include <chrono>
-#include <atomic>
 #include <condition_variable>
 #include <deque>
 #include <functional>
 #include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-#include "bbq_host.h"
+#include "bbq_search.h"
 
 using namespace bbq;
-
-namespace bbq {
-
-// per query: bit-planes (up to 8) + int8 values in MFMA fragment order + score uniforms + group maxima
-int64_t qbuf_bytes_per_query_w(int w16) { return (int64_t)w16 * 8 * 16 + (int64_t)w16 * 128 + (int64_t)sizeof(QueryParams) + 16; }
-
-}  // namespace bbq
 
 namespace {
 
@@ -78,197 +61,71 @@ class ReplayPool {
   std::vector<std::thread> th_;
 };
 
-}  // namespace
-
-namespace bbq {
-
-std::mutex g_ctx_mu;
-DeviceCtx *g_ctx[64] = {nullptr};
-
-// returns the (lazily created, never destroyed) context of a device; call with hipSetDevice(device) done
-int get_ctx(int device, DeviceCtx **out) {
-  std::lock_guard<std::mutex> lk(g_ctx_mu);
-  if (device < 0 || device >= 64) return fail(BBQ_ERR_INVALID_ARG, "device %d out of range", device);
-  if (!g_ctx[device]) {
-    DeviceCtx *c = new DeviceCtx();
-    c->device = device;
-    for (int i = 0; i < kMaxSlots; ++i) {
-      HIPCHK(hipStreamCreateWithFlags(&c->slots[i].stream, hipStreamNonBlocking));
-      HIPCHK(hipEventCreate(&c->slots[i].ev0));
-      HIPCHK(hipEventCreate(&c->slots[i].ev1));
-      HIPCHK(hipEventCreateWithFlags(&c->slots[i].ev_done, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->slots[i].ev_big, hipEventDisableTiming));
+// Raw queries of bbq_search_raw_batch being quantized on host threads, chunk by chunk, while the sub-batches in front are already
+// on the device: the quantizer (~15 us per 768-d query and core) never stands in front of a sweep except for the first chunk.
+struct RawFeed {
+  const float *queries = nullptr, *centroid = nullptr;
+  int32_t n = 0, dim = 0, sim = 0, qb = 0, iters = 0, chunk = 8;  // small chunks: the first sub-batch waits for its own queries only (8 x ~15 us)
+  double lambda = 0;
+  uint8_t *qq = nullptr;
+  double *qc = nullptr;
+  std::unique_ptr<std::atomic<int>[]> ready;  // per chunk: 0 pending, 1 done, 2 failed
+  std::atomic<int> next{0};
+  std::vector<std::thread> threads;
+  int n_chunks() const { return (n + chunk - 1) / chunk; }
+  void start(int n_threads) {
+    ready.reset(new std::atomic<int>[(size_t)n_chunks()]);
+    for (int i = 0; i < n_chunks(); ++i) ready[(size_t)i].store(0);
+    const int T = std::max(1, std::min(n_threads, n_chunks()));
+    auto work = [this] {
+      for (;;) {
+        const int ci = next.fetch_add(1);
+        if (ci >= n_chunks()) return;
+        int state = 1;
+        for (int i = ci * chunk; i < std::min(n, (ci + 1) * chunk); ++i)
+          if (bbq_quantize_query(queries + (size_t)i * dim, dim, centroid, sim, qb, lambda, iters, qq + (size_t)i * dim, qc + (size_t)i * 4) != BBQ_OK) {
+            state = 2;
+            break;
+          }
+        ready[(size_t)ci].store(state, std::memory_order_release);
+      }
+    };
+    for (int t = 0; t < T; ++t) threads.emplace_back(work);
+  }
+  // blocks until queries [first, first + count) are quantized; on a failed query returns its index through *bad
+  int wait(int64_t first, int count, int32_t *bad) {
+    for (int ci = (int)(first / chunk); ci <= (int)((first + count - 1) / chunk); ++ci) {
+      int st;
+      while ((st = ready[(size_t)ci].load(std::memory_order_acquire)) == 0) std::this_thread::yield();
+      if (st == 2) {
+        // which query, and its message on THIS thread (the worker's is thread-local)
+        for (int i = ci * chunk; i < std::min(n, (ci + 1) * chunk); ++i) {
+          const int rc = bbq_quantize_query(queries + (size_t)i * dim, dim, centroid, sim, qb, lambda, iters, qq + (size_t)i * dim, qc + (size_t)i * 4);
+          if (rc != BBQ_OK) { if (bad) *bad = i; return rc; }
+        }
+        return fail(BBQ_ERR_INVALID_ARG, "query quantization failed");
+      }
     }
-    HIPCHK(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc((void **)&c->d_aux_flags, 4));
-    HIPCHK(hipMemset(c->d_aux_flags, 0, 4));
-    HIPCHK(hipHostMalloc((void **)&c->h_lat, (size_t)(kLatAnswerOffset + kFinalSelectMax + 8) * 8, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(c->h_lat, 0, (size_t)(kLatAnswerOffset + kFinalSelectMax + 8) * 8);
-    HIPCHK(hipHostGetDevicePointer((void **)&c->d_lat, c->h_lat, 0));
-    HIPCHK(hipMalloc((void **)&c->d_pre_keys, (size_t)kLatPreKeys * 4));
-    c->ready = true;
-    g_ctx[device] = c;
+    return BBQ_OK;
   }
-  *out = g_ctx[device];
-  return BBQ_OK;
-}
-
-int ensure_aux_qbuf(DeviceCtx *c, int64_t bytes) {
-  if (c->aux_qbuf_bytes >= bytes) return BBQ_OK;
-  if (c->d_aux_qbuf) HIPCHK(hipFree(c->d_aux_qbuf));
-  c->d_aux_qbuf = nullptr;
-  HIPCHK(hipMalloc((void **)&c->d_aux_qbuf, (size_t)bytes));
-  c->aux_qbuf_bytes = bytes;
-  return BBQ_OK;
-}
-
-}  // namespace bbq
-
-namespace {
-
-// ------------------------------------------------------------------------------------------------ storage
-
-int make_storage(bbq_index *ix, Storage &st, const uint8_t *codes, const double *corr, int64_t n_rows, int64_t row_id_base,
-                 bool check_x1) {
-  const int64_t pb = ix->store_bits > 1 ? ix->dim : ix->pb;  // bytes per row as the caller hands them over (multi-bit: one byte per dimension)
-  DevMem m_codes, m_corr;
-  hipStream_t s = ix->aux_stream;
-  if (n_rows > 0) {
-    HIPCHK(m_codes.alloc((size_t)(n_rows * pb)));
-    HIPCHK(m_corr.alloc((size_t)n_rows * 32));
-    HIPCHK(hipMemcpyAsync(m_codes.p, codes, (size_t)(n_rows * pb), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m_corr.p, corr, (size_t)n_rows * 32, hipMemcpyHostToDevice, s));
+  void join() {
+    next.store(1 << 30);
+    for (auto &t : threads) t.join();
+    threads.clear();
   }
-  return storage_from_device_rows(ix, st, m_codes.as<uint8_t>(), m_corr.as<double>(), n_rows, row_id_base, check_x1);  // synchronises before the scratch rows go
-}
+  ~RawFeed() { join(); }
+};
 
 }  // namespace
 
 namespace bbq {
-
-// rows already in device memory (codes in the caller's shape, corrections [n][4]) -> tile records of `st`; decides the layout of
-// the index on the way (check_x1).  Returns after the device work has completed.
-int storage_from_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const double *d_corr, int64_t n_rows, int64_t row_id_base,
-                             bool check_x1) {
-  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
-  const bool multibit = ix->store_bits > 1;
-  const int64_t pb = multibit ? ix->dim : ix->pb;
-  DevMem m_mis;
-  hipStream_t s = ix->aux_stream;
-  if (check_x1) {
-    // quantizedComponentSum of a 1-bit row is its popcount (src/optimizedScalarQuantizer.ts:204-209); if that
-    // holds for every row the 8 bytes need not be stored or read.  Decided once per index, over all storages.
-    uint32_t mis = 0;
-    HIPCHK(m_mis.alloc(4));
-    uint32_t *d_mis = m_mis.as<uint32_t>();
-    HIPCHK(hipMemsetAsync(d_mis, 0, 4, s));
-    if (multibit) HIPCHK(launch_check_x1_multibit(d_codes, d_corr, n_rows, ix->dim, d_mis, s));
-    else HIPCHK(launch_check_x1(d_codes, d_corr, n_rows, (int32_t)pb, d_mis, s));
-    HIPCHK(hipMemcpyAsync(&mis, d_mis, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (mis) ix->has_x1 = 1;
-  }
-  // compact corrections (4 B/row streamed + exact and add-range side arrays) need the implicit component sum; otherwise inline
-  ix->layout = (ix->want_compact && !ix->has_x1) ? kLayoutCompact : kLayoutInline;
-  ix->tile_stride = tile_stride_of(ix->w16, ix->layout, ix->has_x1);
-  ix->bytes_per_row = ix->tile_stride / kTileRows;
-  st.row_id_base = row_id_base;
-  st.view.n_rows = n_rows;
-  st.view.w16 = ix->w16;
-  st.view.tile_stride = ix->tile_stride;
-  st.view.has_x1 = ix->has_x1;
-  st.view.dim = ix->dim;
-  st.view.layout = ix->layout;
-  st.view.store_bits = ix->store_bits;
-  if (n_tiles > 0) {
-    HIPCHK(hipMalloc((void **)&st.d_tiles, (size_t)(n_tiles * ix->tile_stride)));
-    if (ix->layout == kLayoutCompact) HIPCHK(hipMalloc((void **)&st.d_exact, (size_t)compact_side_bytes(n_tiles)));
-    if (multibit) {
-      uint32_t bad = 0;
-      if (!m_mis.p) HIPCHK(m_mis.alloc(4));
-      HIPCHK(hipMemsetAsync(m_mis.p, 0, 4, s));
-      HIPCHK(launch_retile_multibit(d_codes, d_corr, n_rows, ix->dim, ix->store_bits, ix->index_bits, st.d_tiles, ix->w16, ix->tile_stride, ix->has_x1, ix->layout,
-                                    st.d_exact, m_mis.as<uint32_t>(), s));
-      HIPCHK(hipMemcpyAsync(&bad, m_mis.p, 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      if (bad) return fail(BBQ_ERR_INVALID_ARG, "indexBits=%d: a quantized value is not below %d", ix->index_bits, 1 << ix->index_bits);
-    } else {
-      HIPCHK(launch_retile(d_codes, d_corr, n_rows, (int32_t)pb, st.d_tiles, ix->w16, ix->tile_stride, ix->has_x1, ix->layout, st.d_exact, s));
-    }
-    if (ix->layout == kLayoutCompact) HIPCHK(launch_tile_add_range(st.d_exact, n_rows, const_cast<float *>(add_range_of(st.d_exact, n_tiles)), s));
-    HIPCHK(hipStreamSynchronize(s));
-  }
-  st.view.exact = st.d_exact;
-  st.view.add_range = add_range_of(st.d_exact, n_tiles);
-  st.view.tiles = st.d_tiles;
-  HIPCHK(hipStreamSynchronize(s));  // the scratch rows are released on return
-  return BBQ_OK;
-}
-
-}  // namespace bbq
-
-namespace {
-
-// The view a launch gets: the stored view + which chunks it loads cache-resident.  The indexes that have launched sweeps on the device
-// lately (kCacheWindow) share its 256 MiB Infinity Cache in proportion to their sizes (resident_mb >= 0: that many MiB per launch,
-// whatever else is there).  Called with the device context locked.
-constexpr int64_t kResidentAutoBytes = 224ll << 20;  // per launch; measured: 192 / 224 / 240 MiB within noise of each other at 10 M x 768, a resident set of 248 MiB gains nothing
-constexpr uint64_t kCacheWindow = 100'000'000;  // ns: an index that has launched nothing for 0.1 s is not competing for the cache
-static int64_t cache_sharers_bytes(bbq_index *ix, int64_t own) {
-  DeviceCtx *c = ix->ctx;
-  if (!c) return own;
-  const uint64_t now = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  int64_t all = 0;
-  bool found = false;
-  for (size_t i = 0; i < c->cache_users.size();) {
-    DeviceCtx::CacheUser &u = c->cache_users[i];
-    if (u.index == ix) { u.bytes = own; u.tick = now; found = true; }
-    if (now - u.tick > kCacheWindow) { c->cache_users.erase(c->cache_users.begin() + (long)i); continue; }
-    all += u.bytes;
-    ++i;
-  }
-  if (!found) { c->cache_users.push_back({ix, own, now}); all += own; }
-  return all;
-}
-// One launch sweeps chunks [chunk_begin, chunk_begin + n_chunks) of `sto` once per query of its sub-batch, back to back: what it can
-// keep in the cache is a part of ITS range (the launches of a sub-batch run one after the other, each over its own rows).
-static IndexView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin = 0, int64_t n_chunks = -1) {
-  IndexView v = sto.view;
-  const int64_t all_chunks = sto.n_chunks();
-  if (n_chunks < 0) n_chunks = all_chunks - chunk_begin;
-  const int64_t chunk_bytes = (int64_t)kTilesPerChunk * v.tile_stride;
-  const int64_t own = ix->main.n_chunks() * (int64_t)kTilesPerChunk * ix->main.view.tile_stride;
-  const int64_t all = std::max<int64_t>(1, cache_sharers_bytes(ix, own));
-  const int64_t budget = ix->opt_resident_mb >= 0 ? ((int64_t)ix->opt_resident_mb << 20)
-                                            : (int64_t)((double)kResidentAutoBytes * ((double)own / (double)all));
-  int64_t fit = std::min(n_chunks, budget / std::max<int64_t>(1, chunk_bytes));  // chunks of this launch's range that stay resident
-  // an index only a little larger than the budget: its launches are short and overlap (the small ones of the next sub-batch run beside
-  // the large one), so their resident sets must fit TOGETHER - the same share of every launch's range
-  if (own > budget && own <= budget + budget / 4 && ix->opt_resident_mb < 0) fit = std::min(n_chunks, (int64_t)((double)n_chunks * (double)budget / (double)own));
-  int64_t resident_chunks;
-  if (fit >= n_chunks) {  // everything this launch reads
-    v.resident_share = -1;
-    v.resident_tiles = (chunk_begin + n_chunks) * kTilesPerChunk;
-    resident_chunks = n_chunks;
-  } else if (ix->opt_resident_interleave && n_chunks >= 64) {  // of every 64 chunks the first `share`: cache and HBM deliver side by side
-    v.resident_share = fit * 64 / n_chunks;  // rounded down: never more than the budget
-    v.resident_tiles = 0;
-    resident_chunks = n_chunks * v.resident_share / 64;
-  } else {  // the first chunks of the range
-    v.resident_share = -1;
-    v.resident_tiles = (chunk_begin + fit) * kTilesPerChunk;
-    resident_chunks = fit;
-  }
-  ix->sweep_resident_acc += resident_chunks * chunk_bytes;  // the caller books it per sweep of the index (bbq_stats.resident_bytes)
-  return v;
-}
 
 // queries per launch sequence (sub-batch).  The largest sweep of a sub-batch should run for about a millisecond: shorter ones pay the
 // device's dependent-launch gaps and their own ramp (1.25 M rows x 2048 queries: 52.5 K q/s with 32 per sub-batch, 56.5 K with 64,
 // 57 K with 96-128; at 10 M rows 32 is as good as 64 and needs half the workspace).  A call should also be cut into at least four
 // sub-batches where it can: the first sub-batch's small segments run alone on the device and only the later ones hide theirs behind
 // another sub-batch's large sweep (1 M rows x 256 queries per call: 0.849 of the roofline end to end with 2 x 128, 0.855 with 4 x 64)
-int effective_batch(const bbq_index *ix, int64_t n_queries = 0) {
+int effective_batch(const bbq_index *ix, int64_t n_queries) {
   if (ix->opt_batch > 0) return ix->opt_batch;
   const int64_t rows = ix->main.view.n_rows;
   int q = rows >= 6000000 ? 32 : rows >= 2500000 ? 64 : 128;
@@ -280,7 +137,7 @@ int effective_batch(const bbq_index *ix, int64_t n_queries = 0) {
 
 // ------------------------------------------------------------------------------------------------ plan
 
-int cap_for(int64_t k, int64_t rows_before) {
+static int cap_for(int64_t k, int64_t rows_before) {
   const double lam = (double)k * kChunkRows / (double)std::max<int64_t>(rows_before, 1);
   int64_t c = (int64_t)ceil(lam + 8.0 * sqrt(lam) + 16.0);
   c = (c + 7) / 8 * 8;
@@ -290,7 +147,7 @@ int cap_for(int64_t k, int64_t rows_before) {
 // have_theta: a threshold derived from earlier rows (the pilot replica) already exists when this storage starts;
 // otherwise the storage's own first rows form the dense segment (for a shard without a replica that gives
 // thresholds from the shard's local prefix: weaker than global ones, still valid)
-void add_storage_segments(const bbq_index *ix, Plan &p, int storage, const Storage &st, int64_t rows_before, bool have_theta,
+static void add_storage_segments(const bbq_index *ix, Plan &p, int storage, const Storage &st, int64_t rows_before, bool have_theta,
                           bool emit, double &expected) {
   const int64_t R = st.view.n_rows;
   if (R <= 0) return;
@@ -318,7 +175,7 @@ void add_storage_segments(const bbq_index *ix, Plan &p, int storage, const Stora
 }
 
 // k: the rank the device selects thresholds with; final_k > 0: k == final_k + 1 and the last finalize launch selects the answer
-void build_plan(bbq_index *ix, int64_t k, int64_t final_k = 0, bool latency = false) {
+void build_plan(bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
   Plan &p = ix->plan;
   const int growth = latency ? ix->opt_latency_growth : ix->opt_growth;
   if (p.k == k && p.final_k == final_k && p.growth == growth && p.latency == latency) return;
@@ -365,7 +222,7 @@ void build_plan(bbq_index *ix, int64_t k, int64_t final_k = 0, bool latency = fa
 
 // ------------------------------------------------------------------------------------------------ slots
 
-void free_slot_buffers(Slot &s) {
+static void free_slot_buffers(Slot &s) {
   if (s.d_block) (void)hipFree(s.d_block);
   if (s.h_block) (void)hipHostFree(s.h_block);
   s.d_block = s.h_block = nullptr;
@@ -391,7 +248,7 @@ void free_slot_buffers(Slot &s) {
   s.q_cap = 0;
 }
 
-int64_t qbuf_bytes_per_query(const bbq_index *ix) { return qbuf_bytes_per_query_w(ix->w16); }
+static int64_t qbuf_bytes_per_query(const bbq_index *ix) { return qbuf_bytes_per_query_w(ix->w16); }
 
 int ensure_slot(bbq_index *ix, Slot &s, int nq, bool own_lists) {
   const Plan &p = ix->plan;
@@ -451,269 +308,11 @@ int ensure_slot(bbq_index *ix, Slot &s, int nq, bool own_lists) {
   return BBQ_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ query prep
-
-struct PreparedQueries {
-  int planes = 4;
-  int one_bit = 0;
-};
-
-int max_value(const uint8_t *q, int64_t count) {
-  uint8_t m = 0;
-  for (int64_t i = 0; i < count; ++i) m = std::max(m, q[i]);
-  return m;
-}
-
-int planes_for(const uint8_t *q, int64_t count) {
-  uint8_t m = 0;
-  for (int64_t i = 0; i < count; ++i) m |= q[i];
-  if (m <= 1) return 1;
-  if (m <= 3) return 2;
-  if (m <= 15) return 4;
-  return 8;
-}
-
-// bytes of staged query data per query (bit-planes, or the nibble / byte dwords of a multi-bit index)
-int64_t query_data_bytes(const bbq_index *ix, int planes) { return (int64_t)ix->w16 * query_units_per_chunk(planes, ix->store_bits) * 16; }
-
-// kernel variant for a call: 1-bit index -> number of bit-planes the query values need; multi-bit index -> 4 (values <= 15: low
-// nibbles only) or 8
-int planes_of_call(const bbq_index *ix, const uint8_t *q, int64_t count, int one_bit) {
-  if (ix->store_bits == 1) return one_bit ? 1 : planes_for(q, count);
-  if (ix->store_bits == 8) return 8;
-  return max_value(q, count) <= 15 ? 4 : 8;
-}
-
-// writes the query data and the score uniforms of one query into the staging buffer.
-// 1-bit index: bit-planes ([j][p] 16-byte blocks, packed like the rows: dim d -> byte d>>3, bit 7-(d&7)).
-// multi-bit index: per row dword w the dwords the kernel multiplies its unfolded fields with (dot_chunk_multibit):
-//   store_bits 2: {lo nibbles of dims 16w+0,2,..,14 | lo nibbles of dims 16w+1,3,..,15 [| hi nibbles of the same, planes == 8]}
-//   store_bits 4: {lo nibbles of dims 8w..8w+7 [| hi nibbles]}          store_bits 8: {bytes of dims 4w..4w+3}
-void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const uint8_t *q, const double *qc, int planes,
-                int one_bit, int sim) {
-  memset(planes_dst, 0, (size_t)query_data_bytes(ix, planes));
-  if (ix->store_bits == 1) {
-    // eight dimensions (one byte of every plane) at a time: bit p of the eight query bytes, gathered MSB-first by one multiply -
-    // source bit 8i (dimension 8*byte + i) goes to bit 63 - i of the product, no two partial products share a position
-    const int full = ix->dim >> 3;
-    for (int byte = 0; byte < full; ++byte) {
-      uint64_t x;
-      memcpy(&x, q + (size_t)byte * 8, 8);
-      if (!x) continue;
-      const int j = byte >> 4, b = byte & 15;
-      for (int p = 0; p < planes; ++p)
-        planes_dst[((size_t)j * planes + p) * 16 + b] = (uint8_t)((((x >> p) & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56);
-    }
-    for (int d = full * 8; d < ix->dim; ++d) {  // the last, partial byte
-      const uint8_t v = q[d];
-      if (!v) continue;
-      const int byte = d >> 3, j = byte >> 4, b = byte & 15;
-      const uint8_t bit = (uint8_t)(0x80u >> (d & 7));
-      for (int p = 0; p < planes; ++p)
-        if ((v >> p) & 1) planes_dst[((size_t)j * planes + p) * 16 + b] |= bit;
-    }
-  } else {
-    const int sb = ix->store_bits, per = 32 / sb, qn = query_units_per_chunk(planes, sb);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(planes_dst);
-    for (int d = 0; d < ix->dim; ++d) {
-      const uint32_t v = q[d];
-      if (!v) continue;
-      const int w = d / per, f = d % per;
-      uint32_t *qw = dst + (size_t)w * qn;
-      if (sb == 2) {
-        const int half = f & 1, nib = f >> 1;
-        qw[half] |= (v & 15u) << (4 * nib);
-        if (planes > 4) qw[2 + half] |= (v >> 4) << (4 * nib);
-      } else if (sb == 4) {
-        qw[0] |= (v & 15u) << (4 * f);
-        if (planes > 4) qw[1] |= (v >> 4) << (4 * f);
-      } else {
-        qw[0] |= v << (8 * f);
-      }
-    }
-  }
-  const double FBS = 1.0 / 15.0;  // src/constants.ts:20
-  pp->ay = qc[0];
-  pp->ly = one_bit ? (qc[1] - qc[0]) : (qc[1] - qc[0]) * FBS;  // src/batchDotProduct.ts:498 / :574
-  pp->y1 = qc[3];
-  pp->qadd = qc[2];
-  // multi-bit index: the reference's batch scorer throws on unpacked rows and its per-row scorer answers
-  // (src/binaryQuantizedScorer.ts:403-419): centroidDP is 0 for every query width but 1 (searchNearestNeighbors passes no
-  // original query, :290) and MAXIMUM_INNER_PRODUCT is not divided by FOUR_BIT_SCALE (:207-209)
-  const bool per_row_form = ix->store_bits > 1;
-  pp->cdp = (per_row_form && !one_bit) ? 0.0 : ix->centroid_dp;
-  pp->dimd = (double)ix->dim;
-  pp->sim = sim;
-  pp->one_bit = one_bit;
-  pp->mip_plain = per_row_form ? 1 : 0;
-  pp->pad_ = 0;
-}
-
-// MFMA shared sweep, int8 form (query values up to 127): the int8 query values in the order the code bits fall out of the packed
-// words.  For 32-dim word g, half h, dword c, byte i the kernel extracts bit p = 4h + c + 8i of the little-endian word, which is row
-// byte 4g + (p >> 3), bit (p & 7), i.e. dimension 32g + 8*(p >> 3) + 7 - (p & 7) (MSB-first packing,
-// src/optimizedScalarQuantizer.ts:420-446).  Layout: [group][g][h][n][16 B], n = query in its group of 32.
-void fill_query_mfma(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q) {
-  const int words = ix->w16 * 4, group = q_in_batch / 32, n = q_in_batch % 32;
-  uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->w16, false);
-  for (int g = 0; g < words; ++g)
-    for (int h = 0; h < 2; ++h) {
-      uint8_t *o = gb + (((size_t)g * 2 + h) * 32 + n) * 16;
-      for (int cc = 0; cc < 4; ++cc)
-        for (int i = 0; i < 4; ++i) {
-          const int p = 4 * h + cc + 8 * i;
-          const int d = 32 * g + 8 * (p >> 3) + 7 - (p & 7);
-          o[4 * cc + i] = d < ix->dim ? q[d] : 0;
-        }
-    }
-}
-
-// FP form (query values <= 15): v_mfma_f32_32x32x64_f8f6f4 with the rows as FP4 and the queries as FP6 (e2m3).  Step g covers the
-// code words 2g (lower half-wave) and 2g + 1 (upper); element i of a lane is bit p = 4 (i & 7) + (i >> 3) of its word - the kernel
-// masks bit c = i >> 3 of every nibble where it stands, an FP4 number of 0.5, 1.0, 2.0 and (bit 3, shifted down) 0.5 - and the query
-// value carries 1/2, 1/4, 1/8, 1/2 against it: every product is q / 4 (q / 2 or q for smaller query values, see below).  e2m3 holds q / 2, q / 4 and q / 8 exactly for q <= 15
-// (exponent 0: m / 8; exponent e: (1 + m / 8) 2^(e-1)).  A lane's 32 six-bit codes are 24 bytes: the first 16 in [g][h][n][16 B],
-// the last 8 in [g][h][n][8 B] behind all of them (two aligned LDS reads per lane and step).
-static uint32_t fp6_code_of_eighths(int eighths) {
-  if (eighths < 8) return (uint32_t)eighths;                   // exponent field 0: m / 8
-  int e = 1;
-  while (eighths >= (8 << e)) ++e;                             // 2^(e-1) <= value < 2^e
-  return ((uint32_t)e << 3) | (uint32_t)((eighths >> (e - 1)) - 8);   // exact: the low e - 1 bits of eighths are zero for q <= 15
-}
-
-void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q, int scale8) {
-  const int steps = ix->w16 * 2, group = q_in_batch / 32, n = q_in_batch % 32;
-  uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->w16, true);
-  uint8_t *gb2 = gb + (size_t)steps * 2 * 32 * 16;
-  // the value x 8: q/2, q/4, q/8, q/2 at scale8 = 2 (products q/4: values up to 15); twice that for values up to 7 (scale8 = 4,
-  // products q/2), four times for values up to 3 (scale8 = 8, products q): the finest grain e2m3's range (7.5) allows
-  uint8_t lut[4][16];
-  for (int cls = 0; cls < 4; ++cls)
-    for (int v = 0; v < 16; ++v) lut[cls][v] = (uint8_t)fp6_code_of_eighths(v * (cls == 1 ? 2 : cls == 2 ? 1 : 4) * (scale8 / 2));
-  // element i = 8 cls + j of a lane is bit p = 4 j + cls of its word: row byte j >> 1, bit 4 (j & 1) + cls, i.e. dimension
-  // 8 (j >> 1) + 7 - 4 (j & 1) - cls of the word's 32.  The eight six-bit codes of a class are 48 bits: bytes [6 cls, 6 cls + 6)
-  static const int off[8] = {7, 3, 15, 11, 23, 19, 31, 27};
-  for (int g = 0; g < steps; ++g)
-    for (int h = 0; h < 2; ++h) {
-      const int base = 32 * (2 * g + h);
-      uint8_t bits[24];
-      for (int cls = 0; cls < 4; ++cls) {
-        uint64_t v48 = 0;
-        if (base + 32 <= ix->dim) {
-          for (int j = 0; j < 8; ++j) v48 |= (uint64_t)lut[cls][q[base + off[j] - cls] & 15] << (6 * j);
-        } else {
-          for (int j = 0; j < 8; ++j) {
-            const int d = base + off[j] - cls;
-            v48 |= (uint64_t)lut[cls][d < ix->dim ? (q[d] & 15) : 0] << (6 * j);
-          }
-        }
-        for (int b = 0; b < 6; ++b) bits[6 * cls + b] = (uint8_t)(v48 >> (8 * b));
-      }
-      memcpy(gb + (((size_t)g * 2 + h) * 32 + n) * 16, bits, 16);
-      memcpy(gb2 + (((size_t)g * 2 + h) * 32 + n) * 8, bits + 16, 8);
-    }
-}
-
-// The matrix-core sweep tests "score > threshold" as an inequality on the integer dot product (bbq_mfma_kernels.hip), which divides by
-// the query's interval width: it takes queries with a positive, finite width and finite corrections; any other sub-batch sweeps on
-// the vector ALUs.
-bool mfma_query_ok(const QueryParams &p) {
-  return p.ly > 0.0 && p.ly < 1e30 && 1.0 / p.ly < 1e30 && fabs(p.ay) < 1e30 && fabs(p.y1) < 1e30 && fabs(p.qadd) < 1e30 && fabs(p.cdp) < 1e30;
-}
-
-int validate_query_args(const bbq_index *ix, int32_t nq, const uint8_t *qquant, const double *qcorr, int32_t query_bits,
-                        int32_t sim, int64_t k, bool values_pending = false) {
-  if (!ix) return fail(BBQ_ERR_INVALID_ARG, "目标向量集合不能为空");
-  if (nq < 0) return fail(BBQ_ERR_INVALID_ARG, "n_queries < 0");
-  if (nq > 0 && (!qquant || !qcorr)) return fail(BBQ_ERR_INVALID_ARG, "查询向量不能为空");
-  if (k < 0) return fail(BBQ_ERR_NEGATIVE_K, "k值不能为负数");
-  if (query_bits < 1 || query_bits > 8) return fail(BBQ_ERR_INVALID_ARG, "queryBits必须在1-8之间");
-  if (sim < 0 || sim > 2) return fail(BBQ_ERR_INVALID_ARG, "不支持的相似性函数: %d", sim);
-  if (query_bits == 1 && !values_pending)  // (values_pending: the library's own quantizer is still producing them)
-    for (int64_t i = 0; i < (int64_t)nq * ix->dim; ++i)
-      if (qquant[i] > 1) return fail(BBQ_ERR_INVALID_ARG, "1位量化值必须为0或1");
-  return BBQ_OK;
-}
-
-// Raw queries of bbq_search_raw_batch being quantized on host threads, chunk by chunk, while the sub-batches in front are already
-// on the device: the quantizer (~15 us per 768-d query and core) never stands in front of a sweep except for the first chunk.
-struct RawFeed {
-  const float *queries = nullptr, *centroid = nullptr;
-  int32_t n = 0, dim = 0, sim = 0, qb = 0, iters = 0, chunk = 8;  // small chunks: the first sub-batch waits for its own queries only (8 x ~15 us)
-  double lambda = 0;
-  uint8_t *qq = nullptr;
-  double *qc = nullptr;
-  std::unique_ptr<std::atomic<int>[]> ready;  // per chunk: 0 pending, 1 done, 2 failed
-  std::atomic<int> next{0};
-  std::vector<std::thread> threads;
-  int n_chunks() const { return (n + chunk - 1) / chunk; }
-  void start(int n_threads) {
-    ready.reset(new std::atomic<int>[(size_t)n_chunks()]);
-    for (int i = 0; i < n_chunks(); ++i) ready[(size_t)i].store(0);
-    const int T = std::max(1, std::min(n_threads, n_chunks()));
-    auto work = [this] {
-      for (;;) {
-        const int ci = next.fetch_add(1);
-        if (ci >= n_chunks()) return;
-        int state = 1;
-        for (int i = ci * chunk; i < std::min(n, (ci + 1) * chunk); ++i)
-          if (bbq_quantize_query(queries + (size_t)i * dim, dim, centroid, sim, qb, lambda, iters, qq + (size_t)i * dim, qc + (size_t)i * 4) != BBQ_OK) {
-            state = 2;
-            break;
-          }
-        ready[(size_t)ci].store(state, std::memory_order_release);
-      }
-    };
-    for (int t = 0; t < T; ++t) threads.emplace_back(work);
-  }
-  // blocks until queries [first, first + count) are quantized; on a failed query returns its index through *bad
-  int wait(int64_t first, int count, int32_t *bad) {
-    for (int ci = (int)(first / chunk); ci <= (int)((first + count - 1) / chunk); ++ci) {
-      int st;
-      while ((st = ready[(size_t)ci].load(std::memory_order_acquire)) == 0) std::this_thread::yield();
-      if (st == 2) {
-        // which query, and its message on THIS thread (the worker's is thread-local)
-        for (int i = ci * chunk; i < std::min(n, (ci + 1) * chunk); ++i) {
-          const int rc = bbq_quantize_query(queries + (size_t)i * dim, dim, centroid, sim, qb, lambda, iters, qq + (size_t)i * dim, qc + (size_t)i * 4);
-          if (rc != BBQ_OK) { if (bad) *bad = i; return rc; }
-        }
-        return fail(BBQ_ERR_INVALID_ARG, "query quantization failed");
-      }
-    }
-    return BBQ_OK;
-  }
-  void join() {
-    next.store(1 << 30);
-    for (auto &t : threads) t.join();
-    threads.clear();
-  }
-  ~RawFeed() { join(); }
-};
-
 // ------------------------------------------------------------------------------------------------ enqueue / complete
-
-struct BatchCtx {
-  bbq_index *ix;
-  const uint8_t *qquant;
-  const double *qcorr;
-  int planes, one_bit, sim;
-  int64_t k;
-  int maxq = 255;  // largest quantized query value of the call (the MFMA sweep needs <= 127)
-};
-
-// outputs of a sharded scan: the per-query lists live in the index's own buffers and (optionally) the shard-local answers go straight
-// into the caller's device memory (bbq_shard_scan_begin)
-struct ExtOut {
-  uint64_t *lists = nullptr;     // [nq of the batch][list_cap], this sub-batch's first row
-  int64_t list_cap = 0;
-  int32_t *counts = nullptr;     // [nq][2]
-  uint64_t *answers = nullptr;   // this sub-batch's first row of the caller's [n_queries][answers_stride], or null
-  int64_t answers_stride = 0;
-};
 
 // the FinalizeArgs fields every finalize launch takes from its slot: the query lists (a sharded scan's are the caller's), their
 // counters (the append counters only behind a sweep that appended), the running top-k keys, the threshold, the flags and the rank
-static FinalizeArgs slot_finalize_args(const Slot &s, uint64_t *lists, int32_t *list_counts, int64_t list_cap, bool appended, int64_t k) {
+FinalizeArgs slot_finalize_args(const Slot &s, uint64_t *lists, int32_t *list_counts, int64_t list_cap, bool appended, int64_t k) {
   FinalizeArgs f{};
   f.append_counts = appended ? s.d_append_counts : nullptr;
   f.lists = lists;
@@ -784,7 +383,7 @@ int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const 
 
   const bool use_final = !d_lists_ext && p.final_k > 0 && !p.segs.empty();
   // few queries: the sparse launches append their candidates to the list themselves (ScanArgs::append_lists)
-  const bool append = use_final && p.latency && ix->opt_latency_append && !ix->has_pilot && ix->opt_share == 1;
+  const bool append = use_final && p.latency && !ix->has_pilot && ix->opt_share == 1;
   s.appended = append || use_mfma;
   s.timed = false;
   ix->sweep_resident_acc = 0;
@@ -905,57 +504,6 @@ void account_timing(bbq_index *ix, Slot &s) {
     ix->stats.total_scan_bytes += s.timed_bytes;
     ix->stats.total_scan_launches += 1;
   }
-}
-
-// every f32 score of one query to the host (out [n_rows] of this index)
-int dense_scores_one(const BatchCtx &c, int64_t qi, float *out) {
-  bbq_index *ix = c.ix;
-  const int64_t n = ix->main.view.n_rows;
-  const int64_t chunks = ix->main.n_chunks();
-  if (ix->dense_all_cap < n) {
-    if (ix->d_dense_all) HIPCHK(hipFree(ix->d_dense_all));
-    ix->d_dense_all = nullptr;
-    HIPCHK(hipMalloc((void **)&ix->d_dense_all, (size_t)std::max<int64_t>(n, 1) * 4));
-    ix->dense_all_cap = n;
-  }
-  int rc_aux = ensure_aux_qbuf(ix->ctx, qbuf_bytes_per_query_w(ix->w16));
-  if (rc_aux != BBQ_OK) return rc_aux;
-  const int64_t qb = query_data_bytes(ix, c.planes);
-  std::vector<uint8_t> hb((size_t)qb + sizeof(QueryParams));
-  fill_query(ix, hb.data(), reinterpret_cast<QueryParams *>(hb.data() + qb), c.qquant + (size_t)qi * ix->dim, c.qcorr + (size_t)qi * 4,
-             c.planes, c.one_bit, c.sim);
-  hipStream_t st = ix->aux_stream;
-  HIPCHK(hipMemcpyAsync(ix->ctx->d_aux_qbuf, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  ScanArgs a{};
-  a.idx = launch_view(ix, ix->main);
-  a.qplanes = reinterpret_cast<const uint4 *>(ix->ctx->d_aux_qbuf);
-  a.qparams = reinterpret_cast<const QueryParams *>(ix->ctx->d_aux_qbuf + qb);
-  a.chunk_begin = 0;
-  a.row_id_base = ix->main.row_id_base;
-  a.flags = ix->d_aux_flags;
-  a.dense_score32 = ix->d_dense_all;
-  a.dense_stride = n;
-  // gridDim.x is limited to 2^31-1: fine for any index that fits in HBM
-  HIPCHK(launch_scan(a, c.planes, true, 1, (int)chunks, st));
-  HIPCHK(hipMemcpyAsync(out, ix->d_dense_all, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return BBQ_OK;
-}
-
-// dense path for one query: every f32 score to the host, full replay of the reference loop
-int dense_search_one(const BatchCtx &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n) {
-  bbq_index *ix = c.ix;
-  const int64_t n = ix->main.view.n_rows;
-  std::vector<float> h((size_t)std::max<int64_t>(n, 1));
-  int rc = dense_scores_one(c, qi, h.data());
-  if (rc != BBQ_OK) return rc;
-  HeapReplay hr(c.k, n);
-  for (int64_t i = 0; i < n; ++i) hr.offer(h[(size_t)i], (int32_t)(ix->main.row_id_base + i));
-  *out_n = hr.finish(out_idx, out_score);
-  ix->stats.dense_fallbacks += 1;
-  ix->stats.candidates += n;
-  return BBQ_OK;
 }
 
 // device work of the slot's sub-batch is done: collect it and start the heap replays (on the pool when replay_threads > 1)
@@ -1125,7 +673,7 @@ int finish_replay(const BatchCtx &c, Slot &s, int32_t *out_idx, float *out_score
 }
 
 // brings a slot back to "free": collect + replay + wait, whatever is still outstanding
-int reclaim_slot(const BatchCtx &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
+static int reclaim_slot(const BatchCtx &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
   int rc = BBQ_OK;
   if (s.busy) rc = begin_replay(c, s, out_idx, out_score, out_n);
   if (rc == BBQ_OK && s.replaying) rc = finish_replay(c, s, out_idx, out_score, out_n);
@@ -1138,358 +686,14 @@ int drain(bbq_index *ix) {
   return BBQ_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ single-query latency path
-
-// waits for the sequence word the last finalize launch of a latency chain raises in mapped host memory (polling: no event, no copy)
-int wait_latency_answer(DeviceCtx *ctx, Slot &s, uint64_t seq) {
-  volatile uint64_t *flag = ctx->h_lat;
-  for (int64_t spin = 0; spin < (1ll << 31); ++spin) {
-    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return BBQ_OK;
-    if ((spin & 0xffff) == 0xffff && hipEventQuery(s.ev_done) != hipErrorNotReady) break;  // the launch chain is over (or failed)
-    __builtin_ia32_pause();
-  }
-  const hipError_t e = hipEventSynchronize(s.ev_done);
-  if (e == hipSuccess && __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return BBQ_OK;
-  s.ctrl_clean = false;  // whatever the chain left behind
-  if (e != hipSuccess) return fail(BBQ_ERR_HIP, "latency path: %s", hipGetErrorString(e));
-  return fail(BBQ_ERR_HIP, "latency path: the device finished without an answer");
-}
-
-// the LatScanArgs both latency chains sweep the main storage with: the slot's control words and list, the query in the arguments
-static LatScanArgs lat_scan_args(const BatchCtx &c, const BatchCtx &cs, Slot &s) {
-  bbq_index *ix = c.ix;
-  LatScanArgs a{};
-  a.idx = launch_view(ix, ix->main);
-  a.row_id_base = ix->main.row_id_base;
-  a.theta = s.d_theta;
-  a.flags = s.d_flags;
-  a.list_counts = s.d_list_counts;
-  a.append_count = s.d_append_counts;
-  a.list = s.d_lists;
-  a.list_cap = s.list_cap;
-  fill_query(ix, reinterpret_cast<uint8_t *>(a.planes), &a.p, c.qquant, c.qcorr, cs.planes, cs.one_bit, cs.sim);
-  return a;
-}
-
-// the header the last finalize launch of a latency chain leaves in mapped host memory: {list count, flags}, {answer entries, replay}
-struct LatAnswer {
-  const uint64_t *hdr;
-  uint32_t listed, flags, m, replay;
-  explicit LatAnswer(const DeviceCtx *ctx)
-      : hdr(ctx->h_lat + kLatAnswerOffset), listed((uint32_t)hdr[0]), flags((uint32_t)(hdr[0] >> 32)), m((uint32_t)hdr[1]), replay((uint32_t)(hdr[1] >> 32)) {}
-  // the answer proven on the device (the m entries behind the header) goes to the caller
-  void take(bbq_index *ix, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) const {
-    for (uint32_t j = 0; j < m; ++j) {
-      const uint64_t e = hdr[2 + j];
-      const uint32_t bits = (uint32_t)e;
-      out_idx[j] = (int32_t)(uint32_t)(e >> 32);
-      memcpy(&out_score[j], &bits, 4);
-    }
-    out_n[0] = m;
-    ix->stats.candidates += listed;
-    *done = true;
-  }
-};
-
-// The single-query call on a large index: threshold from a pre-sampled prefix (bbq_lat_pre_kernel + bbq_lat_select_kernel: two small
-// launches), ONE sweep over all rows with it, final selection on the list alone - four launches where the segmented chain has six,
-// and nothing in front of the large sweep but the two small ones.  The list is every row above the threshold, not a heap history: a
-// query whose answer the device cannot prove (equal scores, NaN, more candidates than the selection holds) is handed to the
-// segmented chain (*done = false), which replays it exactly.
-int search_latency_presampled(const BatchCtx &c, const BatchCtx &cs, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) {
-  bbq_index *ix = c.ix;
-  const Plan &p = ix->plan;
-  *done = false;
-  const int64_t N = ix->main.view.n_rows, k2 = p.final_k;
-  if (!ix->opt_latency_presample || !ix->opt_latency_fused || !ix->opt_latency_append || ix->has_pilot || ix->opt_share != 1 || !p.latency ||
-      k2 < 1 || k2 > kFinalSelectMax || N < 262144 || !latency_path_supported(ix->main.view, cs.planes))
-    return BBQ_OK;
-  // sample enough rows for ~6000 candidates in the sweep (the selection holds kFinalizeKeyCap of them)
-  int64_t P = ((k2 + 2) * N / 6000 + kChunkRows - 1) / kChunkRows * kChunkRows;
-  P = std::max<int64_t>(P, 8192);
-  if (P > N / 4) return BBQ_OK;
-  // Keys per wave of the sample: ONE (the wave's maximum) when the sample has at least eight times as many waves as the rank asks for -
-  // two of the rank's best rows then rarely share a wave, the threshold is all but the prefix's true order statistic, and the selection
-  // launch has a quarter of the keys to go through (10 M rows, k = 100: 2 656 instead of 10 624 keys, select 11.6 -> 6.6 us, pre-sample
-  // 9.4 -> 8.0 us); four otherwise.  Either way the threshold is an order statistic of a SUBSET of the rows: a valid lower bound.
-  int per_wave = (P / kTileRows >= 8 * (k2 + 2)) ? 1 : 4;
-  if (P / kTileRows * per_wave > kLatPreKeys) per_wave = 1;
-  const int64_t n_keys = P / kTileRows * per_wave;
-  if (n_keys > kLatPreKeys || n_keys < k2 + 2) return BBQ_OK;
-  Slot &s = ix->slots[0];
-  int rc = ensure_slot(ix, s, 1, true);
-  if (rc != BBQ_OK) return rc;
-  DeviceCtx *ctx = ix->ctx;
-  hipStream_t st = s.stream;
-  if (!s.ctrl_clean) {
-    HIPCHK(hipMemsetAsync(s.d_block, 0, (size_t)s.ctrl_bytes, st));
-    s.ctrl_clean = true;
-  }
-  ix->sweep_resident_acc = 0;
-  LatScanArgs a = lat_scan_args(c, cs, s);
-  ix->stats.resident_bytes = ix->sweep_resident_acc;  // the one sweep over all rows
-  LatPreArgs pre{};
-  pre.idx = launch_view(ix, ix->main);
-  pre.rows = (int32_t)P;
-  pre.per_wave = per_wave;
-  pre.pre_keys = ctx->d_pre_keys;
-  pre.flags = s.d_flags;
-  pre.p = a.p;
-  memcpy(pre.planes, a.planes, sizeof pre.planes);
-  HIPCHK(launch_lat_pre(pre, cs.planes, st));
-  // rank k2 + 2: the sweep must list at least k2 + 1 rows for the selection to see the boundary of the answer
-  HIPCHK(launch_lat_select(ctx->d_pre_keys, (int)n_keys, (int)(k2 + 2), s.d_theta, st));
-  a.chunk_begin = 0;
-  a.n_chunks = (int32_t)ix->main.n_chunks();
-  a.first = 0;
-  HIPCHK(launch_lat_scan(a, cs.planes, st));
-  const uint64_t seq = ++ctx->lat_seq;
-  FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, cs.k);
-  f.emit = 1;
-  f.final_out = ctx->d_lat + kLatAnswerOffset;
-  f.final_stride = kFinalSelectMax + 2;
-  f.final_k = (int32_t)k2;
-  f.done_flag = ctx->d_lat;
-  f.seq = seq;
-  HIPCHK(launch_finalize(f, 1, st));
-  HIPCHK(hipEventRecord(s.ev_done, st));
-  rc = wait_latency_answer(ctx, s, seq);
-  if (rc != BBQ_OK) return rc;
-  const LatAnswer r(ctx);
-  s.timed = false;
-  // The list holds the rows ABOVE the sampled threshold only, so the selection's "take every listed row" case (total <= k2) proves
-  // nothing here: equal keys at ranks k2+1 / k2+2 of the sample can leave fewer than k2 rows above it (N >= 262144 > k2, so a
-  // complete answer has exactly k2 entries).  Anything else goes to the segmented chain.
-  if (r.flags != 0 || r.replay != 0 || r.m != (uint32_t)k2) return BBQ_OK;
-  r.take(ix, out_idx, out_score, out_n, done);
-  return BBQ_OK;
-}
-
-// one query, no copies: every sweep takes the query from its kernel arguments (bbq_latency_kernels.hip), the last finalize launch
-// writes the answer to mapped host memory and raises the sequence word this thread polls.  Returns BBQ_OK with *done = false when the
-// call has to take the general path (index shape without an instantiation).
-int search_latency_chain(const BatchCtx &c, const BatchCtx &cs, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) {
-  bbq_index *ix = c.ix;
-  const Plan &p = ix->plan;
-  *done = false;
-  if (!ix->opt_latency_fused || !ix->opt_latency_append || !ix->opt_append_last || ix->has_pilot || ix->opt_share != 1 || !p.latency ||
-      p.final_k < 1 || p.final_k > kFinalSelectMax || p.segs.empty() || !p.segs[0].dense || !latency_path_supported(ix->main.view, cs.planes))
-    return BBQ_OK;
-  for (size_t i = 1; i < p.segs.size(); ++i)
-    if (p.segs[i].dense || p.segs[i].storage != 1) return BBQ_OK;
-  Slot &s = ix->slots[0];
-  int rc = ensure_slot(ix, s, 1, true);
-  if (rc != BBQ_OK) return rc;
-  DeviceCtx *ctx = ix->ctx;
-  hipStream_t st = s.stream;
-  if (!s.ctrl_clean) {  // the slot's last user was not this chain
-    HIPCHK(hipMemsetAsync(s.d_block, 0, (size_t)s.ctrl_bytes, st));
-    s.ctrl_clean = true;
-  }
-  LatScanArgs a = lat_scan_args(c, cs, s);
-  const uint64_t seq = ++ctx->lat_seq;
-  for (size_t i = 0; i < p.segs.size(); ++i) {
-    const Segment &g = p.segs[i];
-    a.chunk_begin = g.chunk_begin;
-    a.n_chunks = (int32_t)g.n_chunks;
-    a.first = i == 0 ? 1 : 0;
-    HIPCHK(launch_lat_scan(a, cs.planes, st));
-    FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, cs.k);
-    f.emit = 1;
-    f.need_theta = i + 1 < p.segs.size() ? 1 : 0;
-    if (i + 1 == p.segs.size()) {
-      f.final_out = ctx->d_lat + kLatAnswerOffset;
-      f.final_stride = kFinalSelectMax + 2;
-      f.final_k = (int32_t)p.final_k;
-      f.done_flag = ctx->d_lat;
-      f.seq = seq;
-    }
-    HIPCHK(launch_finalize(f, 1, st));
-  }
-  HIPCHK(hipEventRecord(s.ev_done, st));
-  rc = wait_latency_answer(ctx, s, seq);
-  if (rc != BBQ_OK) return rc;
-  const LatAnswer r(ctx);
-  s.timed = false;
-  if (r.flags == 0 && r.replay == 0) {  // answered on the device
-    r.take(ix, out_idx, out_score, out_n, done);
-    return BBQ_OK;
-  }
-  // equal scores in or at the edge of the answer (or a flagged query): hand over to the general path's collection - the list on the
-  // device is complete and it is this slot's
-  s.h_final[0] = (uint64_t)r.listed | ((uint64_t)r.flags << 32);
-  s.h_final[1] = (uint64_t)1 << 32;
-  s.busy = true;
-  s.nq = 1;
-  s.q_first = 0;
-  s.final_used = true;
-  s.appended = true;
-  rc = begin_replay(c, s, out_idx, out_score, out_n);
-  if (rc == BBQ_OK) rc = finish_replay(c, s, out_idx, out_score, out_n);
-  if (rc != BBQ_OK) return rc;
-  *done = true;
-  return BBQ_OK;
-}
-
-}  // namespace
-
-namespace bbq {
-
-int settle_shard_slots(DeviceCtx *ctx, bbq_index *owner) {
-  for (int i = 0; i < kMaxSlots; ++i) {
-    Slot &s = ctx->slots[i];
-    if (!s.busy || !s.shard_owner || (owner && s.shard_owner != owner)) continue;
-    HIPCHK(hipEventSynchronize(s.ev_done));
-    s.busy = false;
-    account_timing(s.shard_owner, s);
-    s.shard_owner = nullptr;
-  }
-  return BBQ_OK;
-}
-
-// every f32 score of one query on this index (shard), to host memory: the dense path of a multi-device index
-int dense_scores_host(bbq_index *ix, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim, float *out) {
-  std::lock_guard<std::mutex> lk(ix->ctx->mu);
-  HIPCHK(hipSetDevice(ix->device));
-  if (ix->n_rows == 0) return BBQ_OK;
-  BatchCtx c{ix, qquant, qcorr, planes_of_call(ix, qquant, ix->dim, query_bits == 1), query_bits == 1 ? 1 : 0, sim, 0};
-  ix->stats.dense_fallbacks += 1;
-  return dense_scores_one(c, 0, out);
-}
-
-// frees what the index owns; the device context (streams, workspace) stays
-void destroy_unlocked(bbq_index *ix) {
-  if (!ix) return;
-  (void)hipSetDevice(ix->device);
-  if (ix->pilot.d_tiles) (void)hipFree(ix->pilot.d_tiles);
-  if (ix->main.d_tiles) (void)hipFree(ix->main.d_tiles);
-  if (ix->pilot.d_exact) (void)hipFree(ix->pilot.d_exact);
-  if (ix->main.d_exact) (void)hipFree(ix->main.d_exact);
-  if (ix->d_dense_all) (void)hipFree(ix->d_dense_all);
-  if (ix->ctx)
-    for (size_t i = 0; i < ix->ctx->cache_users.size(); ++i)
-      if (ix->ctx->cache_users[i].index == ix) { ix->ctx->cache_users.erase(ix->ctx->cache_users.begin() + (long)i); break; }
-  if (ix->ctx) (void)settle_shard_slots(ix->ctx, ix);  // sub-batches of an asynchronous scan that was never waited for
-  for (bbq_index::ShardSet &set : ix->shard_set) {
-    if (set.done) { (void)hipEventSynchronize(set.done); (void)hipEventDestroy(set.done); }
-    if (set.h_total) (void)hipHostFree(set.h_total);
-    if (set.d_lists) (void)hipFree(set.d_lists);
-    if (set.d_counts) (void)hipFree(set.d_counts);
-  }
-  delete ix;
+// candidates, dense_fallbacks and host_replays count per call
+static void reset_call_stats(bbq_index *ix) {
+  ix->stats.candidates = 0;
+  ix->stats.dense_fallbacks = 0;
+  ix->stats.host_replays = 0;
 }
 
 }  // namespace bbq
-
-// ================================================================================================ C ABI
-
-extern "C" {
-
-int bbq_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-int bbq_index_create_shard(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t index_bits,
-                           double centroid_dp, int64_t row_base, const uint8_t *pilot_codes, const double *pilot_corr,
-                           int64_t n_pilot, int32_t device, bbq_index **out) {
-  return bbq_index_create_shard_opts(codes, corr, n_rows, dim, index_bits, centroid_dp, row_base, pilot_codes, pilot_corr, n_pilot, device, nullptr, out);
-}
-
-int bbq_index_create_shard_opts(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t index_bits,
-                                double centroid_dp, int64_t row_base, const uint8_t *pilot_codes, const double *pilot_corr,
-                                int64_t n_pilot, int32_t device, const bbq_index_options *opts, bbq_index **out) {
-  clear_error();
-  if (!out) return fail(BBQ_ERR_INVALID_ARG, "bbq_index_create: out is null");
-  *out = nullptr;
-  if (n_rows < 0 || dim <= 0 || row_base < 0 || n_pilot < 0) return fail(BBQ_ERR_INVALID_ARG, "bbq_index_create: bad size");
-  if (n_rows > 0 && (!codes || !corr)) return fail(BBQ_ERR_INVALID_ARG, "目标向量集合不能为空");
-  if (index_bits < 1 || index_bits > 8) return fail(BBQ_ERR_INVALID_ARG, "indexBits必须在1-8之间");
-  if (check_options(opts) != BBQ_OK) return BBQ_ERR_INVALID_ARG;
-  if (!dim_supported(dim, dim == 1 ? 1 : store_bits_of(index_bits)))
-    return fail(BBQ_ERR_UNSUPPORTED, "dimension %d at indexBits %d: the integer dot product would not fit 31 bits", dim, index_bits);
-  if (n_pilot > 0 && (!pilot_codes || !pilot_corr)) return fail(BBQ_ERR_INVALID_ARG, "pilot arrays are null");
-  if (n_pilot > 0 && row_base == 0) return fail(BBQ_ERR_INVALID_ARG, "the shard that owns row 0 takes no pilot replica");
-  if (n_pilot > 0 && n_pilot > row_base) return fail(BBQ_ERR_INVALID_ARG, "pilot rows must precede the shard (n_pilot <= row_base)");
-  if (n_pilot > 0 && n_pilot != row_base && n_pilot % kChunkRows != 0)
-    return fail(BBQ_ERR_INVALID_ARG, "n_pilot must be a multiple of %d", kChunkRows);
-  if (row_base + n_rows > 0xFFFFFFFFll) return fail(BBQ_ERR_UNSUPPORTED, "more than 2^32 rows");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(BBQ_ERR_NO_DEVICE, "no HIP device available: libbbq has no CPU fallback (hipGetDeviceCount found %d)", ndev);
-  if (device < 0 || device >= ndev) return fail(BBQ_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-  HIPCHK(hipSetDevice(device));
-
-  std::unique_ptr<bbq_index> ix(new bbq_index());
-  ix->device = device;
-  ix->dim = dim;
-  ix->index_bits = index_bits;
-  // a multi-bit index of dimension 1 is the one shape the reference's BATCH scorer accepts (the unpacked byte is read as a
-  // packed row, src/batchDotProduct.ts:425-433): it is stored and scored as the packed 1-bit row it is taken for
-  ix->store_bits = dim == 1 ? 1 : store_bits_of(index_bits);
-  ix->pb = row_bytes_of(dim, ix->store_bits);
-  ix->w16 = (ix->pb + 15) / 16;
-  ix->n_rows = n_rows;
-  ix->row_base = row_base;
-  ix->centroid_dp = centroid_dp;
-  ix->has_pilot = n_pilot > 0;
-  ix->want_compact = want_compact_of(opts);
-  DeviceCtx *ctx = nullptr;
-  int rc0 = get_ctx(device, &ctx);
-  if (rc0 != BBQ_OK) return rc0;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  ix->ctx = ctx;
-  ix->slots = ctx->slots;
-  ix->aux_stream = ctx->aux_stream;
-  ix->d_aux_flags = ctx->d_aux_flags;
-  rc0 = ensure_aux_qbuf(ctx, qbuf_bytes_per_query_w(ix->w16));
-  if (rc0 != BBQ_OK) return rc0;
-  int rc;
-  if (ix->has_pilot) {
-    rc = make_storage(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, 0, true);
-    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
-    const int had = ix->has_x1;
-    rc = make_storage(ix.get(), ix->main, codes, corr, n_rows, row_base, true);
-    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
-    if (ix->has_x1 != had) {  // main needs explicit sums but pilot was built without: rebuild the pilot
-      if (ix->pilot.d_tiles) (void)hipFree(ix->pilot.d_tiles);
-      if (ix->pilot.d_exact) (void)hipFree(ix->pilot.d_exact);
-      ix->pilot.d_tiles = nullptr;
-      ix->pilot.d_exact = nullptr;
-      rc = make_storage(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, 0, false);
-      if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
-    }
-  } else {
-    rc = make_storage(ix.get(), ix->main, codes, corr, n_rows, row_base, true);
-    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
-  }
-  *out = ix.release();
-  return BBQ_OK;
-}
-
-int bbq_index_create(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t index_bits,
-                     double centroid_dp, int32_t device, bbq_index **out) {
-  return bbq_index_create_shard(codes, corr, n_rows, dim, index_bits, centroid_dp, 0, nullptr, nullptr, 0, device, out);
-}
-
-void bbq_index_destroy(bbq_index *ix) {
-  if (!ix) return;
-  if (ix->multi) { multi_destroy(ix); return; }
-  if (ix->ctx) {
-    std::lock_guard<std::mutex> lk(ix->ctx->mu);
-    destroy_unlocked(ix);
-  } else {
-    destroy_unlocked(ix);
-  }
-}
-
-int64_t bbq_index_size(const bbq_index *ix) { return ix ? ix->n_rows : 0; }
-int32_t bbq_index_dimension(const bbq_index *ix) { return ix ? ix->dim : 0; }
-int32_t bbq_index_bytes_per_row(const bbq_index *ix) { return ix ? ix->bytes_per_row : 0; }
-int32_t bbq_index_bits(const bbq_index *ix) { return ix ? ix->index_bits : 0; }
-
-}  // extern "C"
 
 // bbq_search_batch, and - with `feed` - bbq_search_raw_batch: the quantized queries of a sub-batch are waited for right before it is
 // enqueued
@@ -1502,9 +706,7 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
   if (k == 0 || n_queries == 0) return BBQ_OK;  // src/binaryQuantizationFormat.ts:332-334
   if (!out_idx || !out_score) return fail(BBQ_ERR_INVALID_ARG, "output arrays are null");
   if (ix->multi) {
-    ix->stats.candidates = 0;
-    ix->stats.dense_fallbacks = 0;
-    ix->stats.host_replays = 0;
+    reset_call_stats(ix);
     if (ix->n_rows == 0) return BBQ_OK;
     return multi_search_batch(ix, n_queries, qquant, qcorr, query_bits, sim, k, out_idx, out_score, out_n);
   }
@@ -1514,9 +716,7 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
   HIPCHK(hipSetDevice(ix->device));
   rc = settle_shard_slots(ix->ctx, nullptr);  // an asynchronous sharded scan on this device may have left slots busy
   if (rc != BBQ_OK) return rc;
-  ix->stats.candidates = 0;
-  ix->stats.dense_fallbacks = 0;
-  ix->stats.host_replays = 0;
+  reset_call_stats(ix);
   if (ix->n_rows == 0) return BBQ_OK;
 
   BatchCtx c{ix, qquant, qcorr, 0, query_bits == 1 ? 1 : 0, sim, k};
@@ -1615,7 +815,7 @@ int bbq_search_raw_batch(bbq_index *ix, int32_t n_queries, const float *queries,
   double *qc = qcorr_out;
   if (!qq) { own_q.resize((size_t)n_queries * dim); qq = own_q.data(); }
   if (!qc) { own_c.resize((size_t)n_queries * 4); qc = own_c.data(); }
-  const int T = n_threads > 0 ? n_threads : (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2));
+  const int T = n_threads > 0 ? n_threads : default_host_threads();
   // few queries, k == 0 (the quantizer's errors still surface, as in the reference's order of checks) or a multi-device handle
   // (its rounds take whole arrays): quantize first, then search
   if (n_queries <= 64 || k == 0 || ix->multi) {
@@ -1640,263 +840,6 @@ int bbq_search_raw_batch(bbq_index *ix, int32_t n_queries, const float *queries,
 int bbq_search(bbq_index *ix, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim, int64_t k,
                int32_t *out_idx, float *out_score, int64_t *out_n) {
   return bbq_search_batch(ix, 1, qquant, qcorr, query_bits, sim, k, out_idx, out_score, out_n);
-}
-
-int bbq_score_rows(bbq_index *ix, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim,
-                   int64_t row_begin, int64_t row_count, int32_t *out_qcdist, double *out_score64, float *out_score32) {
-  clear_error();
-  int rc = validate_query_args(ix, 1, qquant, qcorr, query_bits, sim, 0);
-  if (rc != BBQ_OK) return rc;
-  if (row_begin < 0 || row_count < 0 || row_begin + row_count > ix->n_rows)
-    return fail(BBQ_ERR_INVALID_ARG, "向量索引 %lld 不存在", (long long)(row_begin + row_count - 1));
-  if (row_count == 0) return BBQ_OK;
-  if (ix->multi) return multi_score_rows(ix, qquant, qcorr, query_bits, sim, row_begin, row_count, out_qcdist, out_score64, out_score32);
-  std::lock_guard<std::mutex> lk(ix->ctx->mu);
-  HIPCHK(hipSetDevice(ix->device));
-  BatchCtx c{ix, qquant, qcorr, planes_of_call(ix, qquant, ix->dim, query_bits == 1), query_bits == 1 ? 1 : 0, sim, 0};
-  rc = ensure_aux_qbuf(ix->ctx, qbuf_bytes_per_query_w(ix->w16));
-  if (rc != BBQ_OK) return rc;
-  const int64_t qb = query_data_bytes(ix, c.planes);
-  std::vector<uint8_t> hb((size_t)qb + sizeof(QueryParams));
-  fill_query(ix, hb.data(), reinterpret_cast<QueryParams *>(hb.data() + qb), qquant, qcorr, c.planes, c.one_bit, sim);
-  hipStream_t st = ix->aux_stream;
-  HIPCHK(hipMemcpyAsync(ix->ctx->d_aux_qbuf, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const int64_t piece_chunks = 1024;  // 1M rows per piece
-  const int64_t c_first = row_begin / kChunkRows, c_last = (row_begin + row_count + kChunkRows - 1) / kChunkRows;
-  const int64_t piece_rows = std::min(piece_chunks, c_last - c_first) * kChunkRows;
-  DevMem m32, mqc, m64;
-  HIPCHK(m32.alloc((size_t)piece_rows * 4));
-  HIPCHK(mqc.alloc((size_t)piece_rows * 4));
-  HIPCHK(m64.alloc((size_t)piece_rows * 8));
-  float *d32 = m32.as<float>();
-  int32_t *dqc = mqc.as<int32_t>();
-  double *d64 = m64.as<double>();
-  std::vector<float> h32((size_t)piece_rows);
-  std::vector<int32_t> hqc((size_t)piece_rows);
-  std::vector<double> h64((size_t)piece_rows);
-  rc = BBQ_OK;
-  for (int64_t cb = c_first; cb < c_last && rc == BBQ_OK; cb += piece_chunks) {
-    const int64_t nc = std::min(piece_chunks, c_last - cb);
-    ScanArgs a{};
-    a.idx = launch_view(ix, ix->main);
-    a.qplanes = reinterpret_cast<const uint4 *>(ix->ctx->d_aux_qbuf);
-    a.qparams = reinterpret_cast<const QueryParams *>(ix->ctx->d_aux_qbuf + qb);
-    a.chunk_begin = cb;
-    a.row_id_base = ix->main.row_id_base;
-    a.flags = ix->d_aux_flags;
-    a.dense_score32 = d32;
-    a.dense_qcdist = dqc;
-    a.dense_score64 = d64;
-    a.dense_stride = piece_rows;
-    hipError_t e = launch_scan(a, c.planes, true, 1, (int)nc, st);
-    const int64_t r0 = cb * kChunkRows, r1 = std::min((cb + nc) * kChunkRows, ix->main.view.n_rows);
-    if (e == hipSuccess) e = hipMemcpyAsync(h32.data(), d32, (size_t)(r1 - r0) * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(hqc.data(), dqc, (size_t)(r1 - r0) * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h64.data(), d64, (size_t)(r1 - r0) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { rc = fail(BBQ_ERR_HIP, "bbq_score_rows: %s", hipGetErrorString(e)); break; }
-    const int64_t lo = std::max(r0, row_begin), hi = std::min(r1, row_begin + row_count);
-    for (int64_t r = lo; r < hi; ++r) {
-      if (out_score32) out_score32[r - row_begin] = h32[(size_t)(r - r0)];
-      if (out_qcdist) out_qcdist[r - row_begin] = hqc[(size_t)(r - r0)];
-      if (out_score64) out_score64[r - row_begin] = h64[(size_t)(r - r0)];
-    }
-  }
-  return rc;
-}
-
-int64_t bbq_shard_list_cap(const bbq_index *cix, int64_t k) {
-  if (!cix || k <= 0 || cix->multi) return 0;
-  bbq_index *ix = const_cast<bbq_index *>(cix);
-  // the scan runs with rank k + 1 whenever it can leave shard-local answers (k <= kFinalSelectMax): size for that plan
-  const int64_t keff = std::min<int64_t>(k, kMaxFastK);
-  std::lock_guard<std::mutex> lk(ix->ctx->mu);
-  if (keff <= kFinalSelectMax) build_plan(ix, keff + 1, keff);
-  else build_plan(ix, keff);
-  return ix->plan.list_cap;
-}
-
-int bbq_shard_scan_begin(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim,
-                         int64_t k, void *dev_packed, int64_t packed_cap, void *dev_offsets, void *dev_flags, void *dev_answers,
-                         int64_t answers_stride) {
-  clear_error();
-  int rc = validate_query_args(ix, n_queries, qquant, qcorr, query_bits, sim, k);
-  if (rc != BBQ_OK) return rc;
-  if (n_queries <= 0) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan: n_queries must be positive");
-  if (!dev_packed || !dev_offsets || !dev_flags || packed_cap <= 0) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan: null output buffers");
-  if (k == 0 || k > kMaxFastK) return fail(BBQ_ERR_UNSUPPORTED, "bbq_shard_scan: k must be in 1..%lld", (long long)kMaxFastK);
-  if (dev_answers && answers_stride < k + 3) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan: answers_stride must be at least k + 3");
-  if (dev_answers && k > kFinalSelectMax)
-    return fail(BBQ_ERR_UNSUPPORTED, "bbq_shard_scan: shard-local answers exist for k <= %d (pass dev_answers = NULL and merge the lists)", kFinalSelectMax);
-  if (ix->multi) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan: the handle is a multi-device index (it shards by itself)");
-  std::lock_guard<std::mutex> lk(ix->ctx->mu);
-  HIPCHK(hipSetDevice(ix->device));
-  if (ix->shard_begun - ix->shard_waited >= 2) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan_begin: two batches are already in flight on this index (wait for one first)");
-  BatchCtx c{ix, qquant, qcorr, planes_of_call(ix, qquant, (int64_t)n_queries * ix->dim, query_bits == 1), query_bits == 1 ? 1 : 0, sim, k};
-  // with answers the shard runs with rank k + 1, like the single index does: its last finalize launch then knows the (k + 1)-th largest
-  // key of everything it has seen (the cut) and the rows above it.  Lists for rank k + 1 are supersets of the lists for rank k.
-  const bool answers = dev_answers != nullptr;
-  if (answers) { c.k = k + 1; build_plan(ix, k + 1, k); }
-  else build_plan(ix, k);
-  bbq_index::ShardSet &set = ix->shard_set[ix->shard_begun & 1];
-  if (!set.done) {
-    HIPCHK(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
-    HIPCHK(hipHostMalloc((void **)&set.h_total, 8, hipHostMallocDefault));
-  }
-  // per-query lists with room for a flood (rows stored cluster by cluster); what travels is packed, so the headroom costs
-  // device memory only
-  const int64_t list_cap = ix->plan.list_cap + std::min<int64_t>(ix->plan.flood_cap, 65536);
-  if (set.q_cap < n_queries || set.list_cap < list_cap) {  // per-query lists the finalize kernels build (the set is idle: its last batch was waited for)
-    if (set.d_lists) HIPCHK(hipFree(set.d_lists));
-    if (set.d_counts) HIPCHK(hipFree(set.d_counts));
-    set.d_lists = nullptr;
-    set.d_counts = nullptr;
-    HIPCHK(hipMalloc((void **)&set.d_lists, (size_t)n_queries * (size_t)list_cap * 8));
-    HIPCHK(hipMalloc((void **)&set.d_counts, (size_t)n_queries * 8 + 16));
-    set.q_cap = n_queries;
-    set.list_cap = list_cap;
-  }
-  const int Q = effective_batch(ix, n_queries);
-  const int nslots = std::min(std::max(1, ix->opt_slots), kMaxSlots);
-  const int64_t nsub = ((int64_t)n_queries + Q - 1) / Q;
-  auto bail = [&](int code) {
-    (void)settle_shard_slots(ix->ctx, nullptr);
-    drain(ix);
-    return code;
-  };
-  // slots other indexes (or the previous batch of this one) have left busy are retired one by one as they are needed: the device
-  // keeps working on them while this batch is being enqueued behind
-  for (int64_t i = 0; i < nsub; ++i) {
-    Slot &s = ix->slots[i % nslots];
-    if (s.busy) {
-      const hipError_t e = hipEventSynchronize(s.ev_done);
-      if (e != hipSuccess) return bail(fail(BBQ_ERR_HIP, "bbq_shard_scan_begin: %s", hipGetErrorString(e)));
-      s.busy = false;
-      account_timing(s.shard_owner ? s.shard_owner : ix, s);
-      s.shard_owner = nullptr;
-    }
-    const int nq = (int)std::min<int64_t>(Q, n_queries - i * Q);
-    rc = ensure_slot(ix, s, nq, false);
-    if (rc != BBQ_OK) return bail(rc);
-    ExtOut ext;
-    ext.lists = set.d_lists + (size_t)(i * Q) * list_cap;
-    ext.list_cap = list_cap;
-    ext.counts = set.d_counts + (size_t)(i * Q) * 2;
-    if (answers) {
-      ext.answers = reinterpret_cast<uint64_t *>(dev_answers) + (size_t)(i * Q) * (size_t)answers_stride;
-      ext.answers_stride = answers_stride;
-    }
-    rc = enqueue_subbatch(c, s, i * Q, nq, &ext);
-    if (rc != BBQ_OK) return bail(rc);
-    s.shard_owner = ix;
-  }
-  // the packing runs on the auxiliary stream behind the last sub-batch of every slot this batch has used
-  hipStream_t aux = ix->aux_stream;
-  for (int j = 0; j < nslots; ++j)
-    if (ix->slots[j].busy && ix->slots[j].shard_owner == ix) HIPCHK(hipStreamWaitEvent(aux, ix->slots[j].ev_done, 0));
-  // pack: [nq][list_cap] -> contiguous entries + offsets, what the host framework sends over RCCL
-  int64_t *d_total = reinterpret_cast<int64_t *>(set.d_counts + (size_t)n_queries * 2);
-  d_total = reinterpret_cast<int64_t *>(((uintptr_t)d_total + 7) & ~(uintptr_t)7);
-  HIPCHK(launch_pack(set.d_counts, set.d_lists, list_cap, ix->plan.list_cap, n_queries, reinterpret_cast<int64_t *>(dev_offsets),
-                     reinterpret_cast<int32_t *>(dev_flags), d_total, reinterpret_cast<uint64_t *>(dev_packed), packed_cap, aux));
-  HIPCHK(hipMemcpyAsync(set.h_total, d_total, 8, hipMemcpyDeviceToHost, aux));
-  HIPCHK(hipEventRecord(set.done, aux));
-  set.packed_cap = packed_cap;
-  set.in_flight = true;
-  ix->shard_begun += 1;
-  return BBQ_OK;
-}
-
-int bbq_shard_scan_wait(bbq_index *ix, int64_t *out_total) {
-  clear_error();
-  if (!ix || ix->multi || !ix->ctx) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan_wait: not a shard handle");
-  if (out_total) *out_total = 0;
-  hipEvent_t ev = nullptr;
-  bbq_index::ShardSet *set = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(ix->ctx->mu);
-    if (ix->shard_begun == ix->shard_waited) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan_wait: no batch in flight");
-    set = &ix->shard_set[ix->shard_waited & 1];
-    ev = set->done;
-  }
-  // outside the device mutex: the next batch is being enqueued by another thread meanwhile
-  hipError_t e = hipEventSynchronize(ev);
-  std::lock_guard<std::mutex> lk(ix->ctx->mu);
-  set->in_flight = false;
-  ix->shard_waited += 1;
-  if (e != hipSuccess) return fail(BBQ_ERR_HIP, "bbq_shard_scan_wait: %s", hipGetErrorString(e));
-  const int64_t total = *set->h_total;
-  if (out_total) *out_total = total;
-  if (total > set->packed_cap) return fail(BBQ_ERR_OOM, "bbq_shard_scan: %lld candidates do not fit packed_cap %lld", (long long)total, (long long)set->packed_cap);
-  return BBQ_OK;
-}
-
-int bbq_shard_scan(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits,
-                   int32_t sim, int64_t k, void *dev_packed, int64_t packed_cap, void *dev_offsets, void *dev_flags,
-                   int64_t *out_total) {
-  if (out_total) *out_total = 0;
-  if (n_queries == 0) {
-    clear_error();
-    return validate_query_args(ix, n_queries, qquant, qcorr, query_bits, sim, k);
-  }
-  if (!out_total) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan: null output buffers");
-  int rc = bbq_shard_scan_begin(ix, n_queries, qquant, qcorr, query_bits, sim, k, dev_packed, packed_cap, dev_offsets, dev_flags, nullptr, 0);
-  if (rc != BBQ_OK) return rc;
-  rc = bbq_shard_scan_wait(ix, out_total);
-  if (rc != BBQ_OK) return rc;
-  std::lock_guard<std::mutex> lk(ix->ctx->mu);  // the synchronous form leaves nothing in flight: timings are booked when it returns
-  return settle_shard_slots(ix->ctx, ix);
-}
-
-int bbq_get_stats(bbq_index *ix, bbq_stats *out) {
-  if (!ix || !out) return fail(BBQ_ERR_INVALID_ARG, "bbq_get_stats: null");
-  if (ix->multi) return multi_get_stats(ix, out);
-  if (ix->ctx) {
-    std::lock_guard<std::mutex> lk(ix->ctx->mu);
-    int prev = -1;  // a getter must not change the calling thread's current device
-    (void)hipGetDevice(&prev);
-    HIPCHK(hipSetDevice(ix->device));
-    int rc = settle_shard_slots(ix->ctx, ix);  // timings of an asynchronous scan are booked when its slots are retired
-    if (prev >= 0 && prev != ix->device) (void)hipSetDevice(prev);
-    if (rc != BBQ_OK) return rc;
-    *out = ix->stats;
-    return BBQ_OK;
-  }
-  *out = ix->stats;
-  return BBQ_OK;
-}
-int bbq_reset_stats(bbq_index *ix) {
-  if (!ix) return fail(BBQ_ERR_INVALID_ARG, "bbq_reset_stats: null");
-  if (ix->multi) return multi_reset_stats(ix);
-  ix->stats = bbq_stats{};
-  return BBQ_OK;
-}
-
-int bbq_set_option(bbq_index *ix, const char *name, int64_t v) {
-  if (!ix || !name) return fail(BBQ_ERR_INVALID_ARG, "bbq_set_option: null");
-  if (ix->multi) return multi_set_option(ix, name, v);
-  const std::string n(name);
-  if (n == "batch_queries" && v >= 0 && v <= 1024) ix->opt_batch = (int)v;  // 0: by index size
-  else if (n == "pipeline_slots" && v >= 1 && v <= kMaxSlots) ix->opt_slots = (int)v;
-  else if (n == "segment_growth" && v >= 2 && v <= 1024) { ix->opt_growth = (int)v; ix->plan.k = -1; }
-  else if (n == "first_segment_rows" && v >= 1024 && v <= 8192 && v % kChunkRows == 0) { ix->opt_s0 = v; ix->plan.k = -1; }
-  else if (n == "resident_interleave" && (v == 0 || v == 1)) ix->opt_resident_interleave = (int)v;
-  else if (n == "resident_mb" && v >= -1 && v <= 1 << 20) ix->opt_resident_mb = (int)v;
-  else if (n == "replay_threads" && v >= 1 && v <= 256) ix->opt_replay_threads = (int)v;
-  else if (n == "force_dense" && (v == 0 || v == 1)) ix->opt_force_dense = (int)v;
-  else if (n == "device_select" && (v == 0 || v == 1)) ix->opt_device_select = (int)v;
-  else if (n == "latency_queries" && v >= 0 && v <= 1024) ix->opt_latency_queries = (int)v;
-  else if (n == "append_last" && (v == 0 || v == 1)) ix->opt_append_last = (int)v;
-  else if (n == "latency_append" && (v == 0 || v == 1)) ix->opt_latency_append = (int)v;
-  else if (n == "latency_fused" && (v == 0 || v == 1)) ix->opt_latency_fused = (int)v;
-  else if (n == "latency_presample" && (v == 0 || v == 1)) ix->opt_latency_presample = (int)v;
-  else if (n == "latency_growth" && v >= 2 && v <= 4096) ix->opt_latency_growth = (int)v;
-  else if (n == "sweep_share" && (v == 1 || v == 4 || v == 8 || v == 32)) ix->opt_share = (int)v;
-  else if (n == "flood_rows" && v >= 0 && v <= (1 << 24)) ix->opt_flood = (v + 1023) / 1024 * 1024;
-  else return fail(BBQ_ERR_INVALID_ARG, "bbq_set_option: unknown option or value out of range: %s=%lld", name, (long long)v);
-  ix->plan.k = -1;  // workspace is grow-only and re-checked by ensure_slot on the next call
-  return BBQ_OK;
 }
 
 }  // extern "C"

@@ -1,6 +1,10 @@
 // bbq_host.h - host-side internals of libbbq shared by its translation units: the device-resident index object, the
 // per-device context (streams, events, per-slot workspace) and the helpers every entry point needs.
-//   bbq_core.cpp     index creation from rows, segment plan, pipelined search, sharded scan, options
+//   bbq_index.cpp    device context, index creation from rows, tile storage, cache budget of a launch, statistics, options
+//   bbq_core.cpp     segment plan, slot workspace, pipelined batch search with host replay (shares bbq_search.h with the next four)
+//   bbq_query.cpp    query staging    bbq_latency.cpp  single-query chains    bbq_dense.cpp  dense path, bbq_score_rows
+//   bbq_shard.cpp    scan of one shard of a row-sharded index (bbq_shard_scan*)
+//   bbq_multi.cpp    one index over several devices of a process
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
@@ -113,9 +117,7 @@ struct Slot {
 // to create (~10 ms per index with hipStreamCreate/Destroy) and quickSearch builds a fresh index on every call
 // (src/index.ts:109), so they live for the process.  One API call at a time per device (mutex).
 struct DeviceCtx {
-  int device = 0;
   std::mutex mu;
-  bool ready = false;
   Slot slots[kMaxSlots];
   hipStream_t aux_stream = nullptr;   // dense path / bbq_score_rows / index build: never touches an in-flight slot
   uint8_t *d_aux_qbuf = nullptr;
@@ -127,10 +129,9 @@ struct DeviceCtx {
   uint64_t *h_lat = nullptr, *d_lat = nullptr;
   uint64_t lat_seq = 0;
   uint32_t *d_pre_keys = nullptr;     // [kLatPreKeys] per-wave top keys of the pre-sampled threshold
-  // the indexes that launched sweeps on this device lately share its Infinity Cache (launch_view, bbq_core.cpp); under `mu`
+  // the indexes that launched sweeps on this device lately share its Infinity Cache (launch_view, bbq_index.cpp); under `mu`
   struct CacheUser { const void *index; int64_t bytes; uint64_t tick; };
   std::vector<CacheUser> cache_users;
-
 };
 constexpr int kLatAnswerOffset = 8;   // words in front of the answer block inside DeviceCtx::h_lat
 
@@ -139,6 +140,8 @@ int64_t qbuf_bytes_per_query_w(int w16);
 // returns the (lazily created, never destroyed) context of a device; call with hipSetDevice(device) done
 int get_ctx(int device, DeviceCtx **out);
 int ensure_aux_qbuf(DeviceCtx *c, int64_t bytes);
+// default number of host threads (heap replays, query quantization): half the cores, at most 16
+inline int default_host_threads() { return (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2)); }
 // bytes of the compact layout's side arrays for n_tiles tiles: exact corrections + add ranges
 inline int64_t compact_side_bytes(int64_t n_tiles) { return n_tiles * kTileRows * 32 + n_tiles * 8; }
 inline const float *add_range_of(const double *d_exact, int64_t n_tiles) {
@@ -162,9 +165,6 @@ struct bbq_index {
   bool has_pilot = false;
   bbq::Storage pilot, main;
   bbq::Plan plan;
-  hipStream_t aux_stream = nullptr;  // = ctx->aux_stream
-  uint8_t *d_aux_qbuf = nullptr;     // = ctx->d_aux_qbuf
-  uint32_t *d_aux_flags = nullptr;
   float *d_dense_all = nullptr;
   int64_t dense_all_cap = 0;
   // bbq_shard_scan_begin / _wait: per-query lists before packing, two sets (two batches may be in flight) and their tickets
@@ -175,7 +175,6 @@ struct bbq_index {
     hipEvent_t done = nullptr;    // recorded behind the packing of the batch
     int64_t *h_total = nullptr;   // pinned
     int64_t packed_cap = 0;
-    bool in_flight = false;
   } shard_set[2];
   int64_t shard_begun = 0, shard_waited = 0;  // batches begun / waited for: ticket t uses set t & 1
   // options
@@ -183,17 +182,16 @@ struct bbq_index {
   // a call with few queries is latency-bound: every segment costs a dependent scan + finalize launch pair (~15-20 us), so such calls
   // walk the index in fewer, faster-growing segments (more candidates per query - the device selects the answer itself anyway)
   int opt_latency_queries = 4, opt_latency_growth = 64;
-  int opt_latency_append = 1;  // 0: calls with few queries keep the chunk slots (and the finalize launches their compaction)
   int64_t sweep_resident_acc = 0;  // cache-resident bytes of the launches of one sweep of the index, summed by launch_view()
   int opt_resident_interleave = 1;  // the resident chunks of a launch are spread over its range (of every 64 chunks the first n) instead of being its head
   int opt_resident_mb = -1;  // MiB of its row range that ONE sweep launch loads with the default cache policy, so that they stay in the Infinity
-                             // Cache from one query's sweep to the next (launch_view(), bbq_core.cpp); -1: this index's share of kResidentAutoBytes
+                             // Cache from one query's sweep to the next (launch_view(), bbq_index.cpp); -1: this index's share of kResidentAutoBytes
   int opt_latency_presample = 1;  // ... and on large indexes get their threshold from per-wave top keys of a prefix (two small launches) instead of two scan / finalize pairs
   int opt_latency_fused = 1;  // single-query calls take the three-launch latency path (bbq_latency_kernels.hip) when the index shape has one
   int opt_append_last = 1;  // append mode also for the last (largest) segment: its finalize launch gets cheaper, its sweep slower (one
                             // atomic per workgroup with candidates); measured at 10 M x 768: 0.250 ms per call with, 0.263 without
   // host threads replaying the heaps of one sub-batch: half the cores, at most 8 (a batch of 32 answers 1.4x sooner than with 1)
-  int opt_replay_threads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2));
+  int opt_replay_threads = bbq::default_host_threads();
   int64_t opt_s0 = 4096;
   // flood tier: candidates one query may pile up beyond the planned list (rows stored cluster by cluster make the
   // query's own cluster beat a threshold that was derived from other clusters) before it has to take the dense path
@@ -217,6 +215,19 @@ inline int check_options(const bbq_index_options *opts) {
 }
 // the integer dot product of one row must fit 31 bits: dim * 255 for packed 1-bit rows (query values <= 255), dim * 255 * 255 for multi-bit fields
 inline bool dim_supported(int64_t dim, int store_bits) { return dim * 255 * (store_bits > 1 ? 255 : 1) <= 0x7fffffffll; }
+#pragma GCC visibility push(hidden)  // bbq_index.cpp, for the other units only (not among the library's dynamic symbols)
+// what an entry point that takes a device number does first: BBQ_ERR_NO_DEVICE without a usable device (require_devices), the range
+// check (check_device), then the device made current and its context (open_device)
+int require_devices(int *ndev);
+int check_device(int device);
+int open_device(int device, DeviceCtx **ctx);
+// dim, index_bits and what follows from them: store_bits, pb, w16
+void set_index_geometry(bbq_index *ix, int32_t dim, int32_t index_bits);
+// a new index on its device: the geometry, the context and its slots, the auxiliary query buffer grown to this index's queries
+int attach_index(bbq_index *ix, DeviceCtx *ctx, int device, int32_t dim, int32_t index_bits);
+// The view a launch gets: the stored view + which chunks it loads cache-resident.  Context mutex held by the caller.
+IndexView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin = 0, int64_t n_chunks = -1);
+#pragma GCC visibility pop
 // frees what the index owns; the device context (streams, workspace) stays.  Call with the context mutex held.
 void destroy_unlocked(bbq_index *ix);
 // rows already in device memory (codes in the caller's shape: packed bits, or one byte per dimension for a multi-bit index;

@@ -1,0 +1,382 @@
+// bbq_index.cpp - the per-device context and the index object: creation from rows, tile storage, the Infinity-Cache budget of a
+// launch (launch_view), statistics, options.
+#include <string.h>
+#include <chrono>
+#include <memory>
+#include "bbq_host.h"
+
+using namespace bbq;
+
+namespace bbq {
+
+std::mutex g_ctx_mu;
+DeviceCtx *g_ctx[64] = {nullptr};
+
+// returns the (lazily created, never destroyed) context of a device; call with hipSetDevice(device) done
+int get_ctx(int device, DeviceCtx **out) {
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  if (device < 0 || device >= 64) return fail(BBQ_ERR_INVALID_ARG, "device %d out of range", device);
+  if (!g_ctx[device]) {
+    DeviceCtx *c = new DeviceCtx();
+    for (int i = 0; i < kMaxSlots; ++i) {
+      HIPCHK(hipStreamCreateWithFlags(&c->slots[i].stream, hipStreamNonBlocking));
+      HIPCHK(hipEventCreate(&c->slots[i].ev0));
+      HIPCHK(hipEventCreate(&c->slots[i].ev1));
+      HIPCHK(hipEventCreateWithFlags(&c->slots[i].ev_done, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&c->slots[i].ev_big, hipEventDisableTiming));
+    }
+    HIPCHK(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
+    HIPCHK(hipMalloc((void **)&c->d_aux_flags, 4));
+    HIPCHK(hipMemset(c->d_aux_flags, 0, 4));
+    HIPCHK(hipHostMalloc((void **)&c->h_lat, (size_t)(kLatAnswerOffset + kFinalSelectMax + 8) * 8, hipHostMallocMapped | hipHostMallocCoherent));
+    memset(c->h_lat, 0, (size_t)(kLatAnswerOffset + kFinalSelectMax + 8) * 8);
+    HIPCHK(hipHostGetDevicePointer((void **)&c->d_lat, c->h_lat, 0));
+    HIPCHK(hipMalloc((void **)&c->d_pre_keys, (size_t)kLatPreKeys * 4));
+    g_ctx[device] = c;
+  }
+  *out = g_ctx[device];
+  return BBQ_OK;
+}
+
+int ensure_aux_qbuf(DeviceCtx *c, int64_t bytes) {
+  if (c->aux_qbuf_bytes >= bytes) return BBQ_OK;
+  if (c->d_aux_qbuf) HIPCHK(hipFree(c->d_aux_qbuf));
+  c->d_aux_qbuf = nullptr;
+  HIPCHK(hipMalloc((void **)&c->d_aux_qbuf, (size_t)bytes));
+  c->aux_qbuf_bytes = bytes;
+  return BBQ_OK;
+}
+
+int require_devices(int *ndev) {
+  *ndev = 0;
+  if (hipGetDeviceCount(ndev) != hipSuccess || *ndev <= 0)
+    return fail(BBQ_ERR_NO_DEVICE, "no HIP device available: libbbq has no CPU fallback (hipGetDeviceCount found %d)", *ndev);
+  return BBQ_OK;
+}
+
+int check_device(int device) {
+  int ndev = 0;
+  const int rc = require_devices(&ndev);
+  if (rc != BBQ_OK) return rc;
+  if (device < 0 || device >= ndev) return fail(BBQ_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
+  return BBQ_OK;
+}
+
+int open_device(int device, DeviceCtx **ctx) {
+  const int rc = check_device(device);
+  if (rc != BBQ_OK) return rc;
+  HIPCHK(hipSetDevice(device));  // before get_ctx: a new context creates its streams on the current device
+  return get_ctx(device, ctx);
+}
+
+void set_index_geometry(bbq_index *ix, int32_t dim, int32_t index_bits) {
+  ix->dim = dim;
+  ix->index_bits = index_bits;
+  // a multi-bit index of dimension 1 is the one shape the reference's BATCH scorer accepts (the unpacked byte is read as a
+  // packed row, src/batchDotProduct.ts:425-433): it is stored and scored as the packed 1-bit row it is taken for
+  ix->store_bits = dim == 1 ? 1 : store_bits_of(index_bits);
+  ix->pb = row_bytes_of(dim, ix->store_bits);
+  ix->w16 = (ix->pb + 15) / 16;
+}
+
+int attach_index(bbq_index *ix, DeviceCtx *ctx, int device, int32_t dim, int32_t index_bits) {
+  set_index_geometry(ix, dim, index_bits);
+  ix->device = device;
+  ix->ctx = ctx;
+  ix->slots = ctx->slots;
+  return ensure_aux_qbuf(ctx, qbuf_bytes_per_query_w(ix->w16));
+}
+
+// ------------------------------------------------------------------------------------------------ storage
+
+static int make_storage(bbq_index *ix, Storage &st, const uint8_t *codes, const double *corr, int64_t n_rows, int64_t row_id_base,
+                        bool check_x1) {
+  const int64_t pb = ix->store_bits > 1 ? ix->dim : ix->pb;  // bytes per row as the caller hands them over (multi-bit: one byte per dimension)
+  DevMem m_codes, m_corr;
+  hipStream_t s = ix->ctx->aux_stream;
+  if (n_rows > 0) {
+    HIPCHK(m_codes.alloc((size_t)(n_rows * pb)));
+    HIPCHK(m_corr.alloc((size_t)n_rows * 32));
+    HIPCHK(hipMemcpyAsync(m_codes.p, codes, (size_t)(n_rows * pb), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(m_corr.p, corr, (size_t)n_rows * 32, hipMemcpyHostToDevice, s));
+  }
+  return storage_from_device_rows(ix, st, m_codes.as<uint8_t>(), m_corr.as<double>(), n_rows, row_id_base, check_x1);  // synchronises before the scratch rows go
+}
+
+// rows already in device memory (codes in the caller's shape, corrections [n][4]) -> tile records of `st`; decides the layout of
+// the index on the way (check_x1).  Returns after the device work has completed.
+int storage_from_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const double *d_corr, int64_t n_rows, int64_t row_id_base,
+                             bool check_x1) {
+  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
+  const bool multibit = ix->store_bits > 1;
+  const int64_t pb = multibit ? ix->dim : ix->pb;
+  DevMem m_mis;
+  hipStream_t s = ix->ctx->aux_stream;
+  if (check_x1) {
+    // quantizedComponentSum of a 1-bit row is its popcount (src/optimizedScalarQuantizer.ts:204-209); if that
+    // holds for every row the 8 bytes need not be stored or read.  Decided once per index, over all storages.
+    uint32_t mis = 0;
+    HIPCHK(m_mis.alloc(4));
+    uint32_t *d_mis = m_mis.as<uint32_t>();
+    HIPCHK(hipMemsetAsync(d_mis, 0, 4, s));
+    if (multibit) HIPCHK(launch_check_x1_multibit(d_codes, d_corr, n_rows, ix->dim, d_mis, s));
+    else HIPCHK(launch_check_x1(d_codes, d_corr, n_rows, (int32_t)pb, d_mis, s));
+    HIPCHK(hipMemcpyAsync(&mis, d_mis, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (mis) ix->has_x1 = 1;
+  }
+  // compact corrections (4 B/row streamed + exact and add-range side arrays) need the implicit component sum; otherwise inline
+  ix->layout = (ix->want_compact && !ix->has_x1) ? kLayoutCompact : kLayoutInline;
+  ix->tile_stride = tile_stride_of(ix->w16, ix->layout, ix->has_x1);
+  ix->bytes_per_row = ix->tile_stride / kTileRows;
+  st.row_id_base = row_id_base;
+  st.view.n_rows = n_rows;
+  st.view.w16 = ix->w16;
+  st.view.tile_stride = ix->tile_stride;
+  st.view.has_x1 = ix->has_x1;
+  st.view.dim = ix->dim;
+  st.view.layout = ix->layout;
+  st.view.store_bits = ix->store_bits;
+  if (n_tiles > 0) {
+    HIPCHK(hipMalloc((void **)&st.d_tiles, (size_t)(n_tiles * ix->tile_stride)));
+    if (ix->layout == kLayoutCompact) HIPCHK(hipMalloc((void **)&st.d_exact, (size_t)compact_side_bytes(n_tiles)));
+    if (multibit) {
+      uint32_t bad = 0;
+      if (!m_mis.p) HIPCHK(m_mis.alloc(4));
+      HIPCHK(hipMemsetAsync(m_mis.p, 0, 4, s));
+      HIPCHK(launch_retile_multibit(d_codes, d_corr, n_rows, ix->dim, ix->store_bits, ix->index_bits, st.d_tiles, ix->w16, ix->tile_stride, ix->has_x1, ix->layout,
+                                    st.d_exact, m_mis.as<uint32_t>(), s));
+      HIPCHK(hipMemcpyAsync(&bad, m_mis.p, 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      if (bad) return fail(BBQ_ERR_INVALID_ARG, "indexBits=%d: a quantized value is not below %d", ix->index_bits, 1 << ix->index_bits);
+    } else {
+      HIPCHK(launch_retile(d_codes, d_corr, n_rows, (int32_t)pb, st.d_tiles, ix->w16, ix->tile_stride, ix->has_x1, ix->layout, st.d_exact, s));
+    }
+    if (ix->layout == kLayoutCompact) HIPCHK(launch_tile_add_range(st.d_exact, n_rows, const_cast<float *>(add_range_of(st.d_exact, n_tiles)), s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  st.view.exact = st.d_exact;
+  st.view.add_range = add_range_of(st.d_exact, n_tiles);
+  st.view.tiles = st.d_tiles;
+  HIPCHK(hipStreamSynchronize(s));  // the scratch rows are released on return
+  return BBQ_OK;
+}
+
+// The view a launch gets: the stored view + which chunks it loads cache-resident.  The indexes that have launched sweeps on the device
+// lately (kCacheWindow) share its 256 MiB Infinity Cache in proportion to their sizes (resident_mb >= 0: that many MiB per launch,
+// whatever else is there).  Called with the device context locked.
+constexpr int64_t kResidentAutoBytes = 224ll << 20;  // per launch; measured: 192 / 224 / 240 MiB within noise of each other at 10 M x 768, a resident set of 248 MiB gains nothing
+constexpr uint64_t kCacheWindow = 100'000'000;  // ns: an index that has launched nothing for 0.1 s is not competing for the cache
+static int64_t cache_sharers_bytes(bbq_index *ix, int64_t own) {
+  DeviceCtx *c = ix->ctx;
+  if (!c) return own;
+  const uint64_t now = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  int64_t all = 0;
+  bool found = false;
+  for (size_t i = 0; i < c->cache_users.size();) {
+    DeviceCtx::CacheUser &u = c->cache_users[i];
+    if (u.index == ix) { u.bytes = own; u.tick = now; found = true; }
+    if (now - u.tick > kCacheWindow) { c->cache_users.erase(c->cache_users.begin() + (long)i); continue; }
+    all += u.bytes;
+    ++i;
+  }
+  if (!found) { c->cache_users.push_back({ix, own, now}); all += own; }
+  return all;
+}
+// One launch sweeps chunks [chunk_begin, chunk_begin + n_chunks) of `sto` once per query of its sub-batch, back to back: what it can
+// keep in the cache is a part of ITS range (the launches of a sub-batch run one after the other, each over its own rows).
+IndexView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin, int64_t n_chunks) {
+  IndexView v = sto.view;
+  const int64_t all_chunks = sto.n_chunks();
+  if (n_chunks < 0) n_chunks = all_chunks - chunk_begin;
+  const int64_t chunk_bytes = (int64_t)kTilesPerChunk * v.tile_stride;
+  const int64_t own = ix->main.n_chunks() * (int64_t)kTilesPerChunk * ix->main.view.tile_stride;
+  const int64_t all = std::max<int64_t>(1, cache_sharers_bytes(ix, own));
+  const int64_t budget = ix->opt_resident_mb >= 0 ? ((int64_t)ix->opt_resident_mb << 20)
+                                            : (int64_t)((double)kResidentAutoBytes * ((double)own / (double)all));
+  int64_t fit = std::min(n_chunks, budget / std::max<int64_t>(1, chunk_bytes));  // chunks of this launch's range that stay resident
+  // an index only a little larger than the budget: its launches are short and overlap (the small ones of the next sub-batch run beside
+  // the large one), so their resident sets must fit TOGETHER - the same share of every launch's range
+  if (own > budget && own <= budget + budget / 4 && ix->opt_resident_mb < 0) fit = std::min(n_chunks, (int64_t)((double)n_chunks * (double)budget / (double)own));
+  int64_t resident_chunks;
+  if (fit >= n_chunks) {  // everything this launch reads
+    v.resident_share = -1;
+    v.resident_tiles = (chunk_begin + n_chunks) * kTilesPerChunk;
+    resident_chunks = n_chunks;
+  } else if (ix->opt_resident_interleave && n_chunks >= 64) {  // of every 64 chunks the first `share`: cache and HBM deliver side by side
+    v.resident_share = fit * 64 / n_chunks;  // rounded down: never more than the budget
+    v.resident_tiles = 0;
+    resident_chunks = n_chunks * v.resident_share / 64;
+  } else {  // the first chunks of the range
+    v.resident_share = -1;
+    v.resident_tiles = (chunk_begin + fit) * kTilesPerChunk;
+    resident_chunks = fit;
+  }
+  ix->sweep_resident_acc += resident_chunks * chunk_bytes;  // the caller books it per sweep of the index (bbq_stats.resident_bytes)
+  return v;
+}
+
+// frees what the index owns; the device context (streams, workspace) stays
+void destroy_unlocked(bbq_index *ix) {
+  if (!ix) return;
+  (void)hipSetDevice(ix->device);
+  if (ix->pilot.d_tiles) (void)hipFree(ix->pilot.d_tiles);
+  if (ix->main.d_tiles) (void)hipFree(ix->main.d_tiles);
+  if (ix->pilot.d_exact) (void)hipFree(ix->pilot.d_exact);
+  if (ix->main.d_exact) (void)hipFree(ix->main.d_exact);
+  if (ix->d_dense_all) (void)hipFree(ix->d_dense_all);
+  if (ix->ctx)
+    for (size_t i = 0; i < ix->ctx->cache_users.size(); ++i)
+      if (ix->ctx->cache_users[i].index == ix) { ix->ctx->cache_users.erase(ix->ctx->cache_users.begin() + (long)i); break; }
+  if (ix->ctx) (void)settle_shard_slots(ix->ctx, ix);  // sub-batches of an asynchronous scan that was never waited for
+  for (bbq_index::ShardSet &set : ix->shard_set) {
+    if (set.done) { (void)hipEventSynchronize(set.done); (void)hipEventDestroy(set.done); }
+    if (set.h_total) (void)hipHostFree(set.h_total);
+    if (set.d_lists) (void)hipFree(set.d_lists);
+    if (set.d_counts) (void)hipFree(set.d_counts);
+  }
+  delete ix;
+}
+
+}  // namespace bbq
+
+// ================================================================================================ C ABI
+
+extern "C" {
+
+int bbq_device_count(void) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+  return n;
+}
+
+int bbq_index_create_shard(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t index_bits,
+                           double centroid_dp, int64_t row_base, const uint8_t *pilot_codes, const double *pilot_corr,
+                           int64_t n_pilot, int32_t device, bbq_index **out) {
+  return bbq_index_create_shard_opts(codes, corr, n_rows, dim, index_bits, centroid_dp, row_base, pilot_codes, pilot_corr, n_pilot, device, nullptr, out);
+}
+
+int bbq_index_create_shard_opts(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t index_bits,
+                                double centroid_dp, int64_t row_base, const uint8_t *pilot_codes, const double *pilot_corr,
+                                int64_t n_pilot, int32_t device, const bbq_index_options *opts, bbq_index **out) {
+  clear_error();
+  if (!out) return fail(BBQ_ERR_INVALID_ARG, "bbq_index_create: out is null");
+  *out = nullptr;
+  if (n_rows < 0 || dim <= 0 || row_base < 0 || n_pilot < 0) return fail(BBQ_ERR_INVALID_ARG, "bbq_index_create: bad size");
+  if (n_rows > 0 && (!codes || !corr)) return fail(BBQ_ERR_INVALID_ARG, "目标向量集合不能为空");
+  if (index_bits < 1 || index_bits > 8) return fail(BBQ_ERR_INVALID_ARG, "indexBits必须在1-8之间");
+  if (check_options(opts) != BBQ_OK) return BBQ_ERR_INVALID_ARG;
+  if (!dim_supported(dim, dim == 1 ? 1 : store_bits_of(index_bits)))
+    return fail(BBQ_ERR_UNSUPPORTED, "dimension %d at indexBits %d: the integer dot product would not fit 31 bits", dim, index_bits);
+  if (n_pilot > 0 && (!pilot_codes || !pilot_corr)) return fail(BBQ_ERR_INVALID_ARG, "pilot arrays are null");
+  if (n_pilot > 0 && row_base == 0) return fail(BBQ_ERR_INVALID_ARG, "the shard that owns row 0 takes no pilot replica");
+  if (n_pilot > 0 && n_pilot > row_base) return fail(BBQ_ERR_INVALID_ARG, "pilot rows must precede the shard (n_pilot <= row_base)");
+  if (n_pilot > 0 && n_pilot != row_base && n_pilot % kChunkRows != 0)
+    return fail(BBQ_ERR_INVALID_ARG, "n_pilot must be a multiple of %d", kChunkRows);
+  if (row_base + n_rows > 0xFFFFFFFFll) return fail(BBQ_ERR_UNSUPPORTED, "more than 2^32 rows");
+  DeviceCtx *ctx = nullptr;
+  int rc = open_device(device, &ctx);
+  if (rc != BBQ_OK) return rc;
+
+  std::unique_ptr<bbq_index> ix(new bbq_index());
+  ix->n_rows = n_rows;
+  ix->row_base = row_base;
+  ix->centroid_dp = centroid_dp;
+  ix->has_pilot = n_pilot > 0;
+  ix->want_compact = want_compact_of(opts);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  rc = attach_index(ix.get(), ctx, device, dim, index_bits);
+  if (rc != BBQ_OK) return rc;
+  if (ix->has_pilot) {
+    rc = make_storage(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, 0, true);
+    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
+    const int had = ix->has_x1;
+    rc = make_storage(ix.get(), ix->main, codes, corr, n_rows, row_base, true);
+    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
+    if (ix->has_x1 != had) {  // main needs explicit sums but pilot was built without: rebuild the pilot
+      if (ix->pilot.d_tiles) (void)hipFree(ix->pilot.d_tiles);
+      if (ix->pilot.d_exact) (void)hipFree(ix->pilot.d_exact);
+      ix->pilot.d_tiles = nullptr;
+      ix->pilot.d_exact = nullptr;
+      rc = make_storage(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, 0, false);
+      if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
+    }
+  } else {
+    rc = make_storage(ix.get(), ix->main, codes, corr, n_rows, row_base, true);
+    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
+  }
+  *out = ix.release();
+  return BBQ_OK;
+}
+
+int bbq_index_create(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t index_bits,
+                     double centroid_dp, int32_t device, bbq_index **out) {
+  return bbq_index_create_shard(codes, corr, n_rows, dim, index_bits, centroid_dp, 0, nullptr, nullptr, 0, device, out);
+}
+
+void bbq_index_destroy(bbq_index *ix) {
+  if (!ix) return;
+  if (ix->multi) { multi_destroy(ix); return; }
+  if (ix->ctx) {
+    std::lock_guard<std::mutex> lk(ix->ctx->mu);
+    destroy_unlocked(ix);
+  } else {
+    destroy_unlocked(ix);
+  }
+}
+
+int64_t bbq_index_size(const bbq_index *ix) { return ix ? ix->n_rows : 0; }
+int32_t bbq_index_dimension(const bbq_index *ix) { return ix ? ix->dim : 0; }
+int32_t bbq_index_bytes_per_row(const bbq_index *ix) { return ix ? ix->bytes_per_row : 0; }
+int32_t bbq_index_bits(const bbq_index *ix) { return ix ? ix->index_bits : 0; }
+
+int bbq_get_stats(bbq_index *ix, bbq_stats *out) {
+  if (!ix || !out) return fail(BBQ_ERR_INVALID_ARG, "bbq_get_stats: null");
+  if (ix->multi) return multi_get_stats(ix, out);
+  if (ix->ctx) {
+    std::lock_guard<std::mutex> lk(ix->ctx->mu);
+    int prev = -1;  // a getter must not change the calling thread's current device
+    (void)hipGetDevice(&prev);
+    HIPCHK(hipSetDevice(ix->device));
+    int rc = settle_shard_slots(ix->ctx, ix);  // timings of an asynchronous scan are booked when its slots are retired
+    if (prev >= 0 && prev != ix->device) (void)hipSetDevice(prev);
+    if (rc != BBQ_OK) return rc;
+    *out = ix->stats;
+    return BBQ_OK;
+  }
+  *out = ix->stats;
+  return BBQ_OK;
+}
+int bbq_reset_stats(bbq_index *ix) {
+  if (!ix) return fail(BBQ_ERR_INVALID_ARG, "bbq_reset_stats: null");
+  if (ix->multi) return multi_reset_stats(ix);
+  ix->stats = bbq_stats{};
+  return BBQ_OK;
+}
+
+int bbq_set_option(bbq_index *ix, const char *name, int64_t v) {
+  if (!ix || !name) return fail(BBQ_ERR_INVALID_ARG, "bbq_set_option: null");
+  if (ix->multi) return multi_set_option(ix, name, v);
+  const std::string n(name);
+  if (n == "batch_queries" && v >= 0 && v <= 1024) ix->opt_batch = (int)v;  // 0: by index size
+  else if (n == "pipeline_slots" && v >= 1 && v <= kMaxSlots) ix->opt_slots = (int)v;
+  else if (n == "segment_growth" && v >= 2 && v <= 1024) { ix->opt_growth = (int)v; ix->plan.k = -1; }
+  else if (n == "first_segment_rows" && v >= 1024 && v <= 8192 && v % kChunkRows == 0) { ix->opt_s0 = v; ix->plan.k = -1; }
+  else if (n == "resident_interleave" && (v == 0 || v == 1)) ix->opt_resident_interleave = (int)v;
+  else if (n == "resident_mb" && v >= -1 && v <= 1 << 20) ix->opt_resident_mb = (int)v;
+  else if (n == "replay_threads" && v >= 1 && v <= 256) ix->opt_replay_threads = (int)v;
+  else if (n == "force_dense" && (v == 0 || v == 1)) ix->opt_force_dense = (int)v;
+  else if (n == "device_select" && (v == 0 || v == 1)) ix->opt_device_select = (int)v;
+  else if (n == "latency_queries" && v >= 0 && v <= 1024) ix->opt_latency_queries = (int)v;
+  else if (n == "append_last" && (v == 0 || v == 1)) ix->opt_append_last = (int)v;
+  else if (n == "latency_fused" && (v == 0 || v == 1)) ix->opt_latency_fused = (int)v;
+  else if (n == "latency_presample" && (v == 0 || v == 1)) ix->opt_latency_presample = (int)v;
+  else if (n == "latency_growth" && v >= 2 && v <= 4096) ix->opt_latency_growth = (int)v;
+  else if (n == "sweep_share" && (v == 1 || v == 4 || v == 8 || v == 32)) ix->opt_share = (int)v;
+  else if (n == "flood_rows" && v >= 0 && v <= (1 << 24)) ix->opt_flood = (v + 1023) / 1024 * 1024;
+  else return fail(BBQ_ERR_INVALID_ARG, "bbq_set_option: unknown option or value out of range: %s=%lld", name, (long long)v);
+  ix->plan.k = -1;  // workspace is grow-only and re-checked by ensure_slot on the next call
+  return BBQ_OK;
+}
+
+}  // extern "C"

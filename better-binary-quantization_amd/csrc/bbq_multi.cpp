@@ -160,7 +160,7 @@ int shard_begin(MultiShard &sh, ShardBuf &b, int32_t nq, const uint8_t *qq, cons
                             b.answers_stride);
   if (rc != BBQ_OK) return rc;
   HIPCHK(hipSetDevice(sh.device));
-  hipStream_t st = sh.ix->aux_stream;  // the stream the packing of this batch was enqueued on
+  hipStream_t st = sh.ix->ctx->aux_stream;  // the stream the packing of this batch was enqueued on
   if (answers) HIPCHK(hipMemcpyAsync(b.h_answers, b.d_answers, (size_t)nq * (size_t)b.answers_stride * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(b.landed, st));
   return BBQ_OK;
@@ -456,11 +456,7 @@ int multi_assemble(bbq_index *const *shards, const int32_t *devices, int32_t n_s
                    double centroid_dp, bbq_index **out) {
   if (n_shards < 1 || n_shards > 64 || !shards || !out) return fail(BBQ_ERR_INVALID_ARG, "multi_assemble: bad arguments");
   std::unique_ptr<bbq_index> ix(new bbq_index());
-  ix->dim = dim;
-  ix->index_bits = index_bits;
-  ix->store_bits = dim == 1 ? 1 : store_bits_of(index_bits);
-  ix->pb = row_bytes_of(dim, ix->store_bits);
-  ix->w16 = (ix->pb + 15) / 16;
+  set_index_geometry(ix.get(), dim, index_bits);
   ix->n_rows = n_rows;
   ix->centroid_dp = centroid_dp;
   ix->device = devices[0];
@@ -543,12 +539,9 @@ int bbq_index_create_multi_opts(const uint8_t *codes, const double *corr, int64_
   if (n_rows > 0 && (!codes || !corr)) return fail(BBQ_ERR_INVALID_ARG, "目标向量集合不能为空");
   if (index_bits < 1 || index_bits > 8) return fail(BBQ_ERR_INVALID_ARG, "indexBits必须在1-8之间");
   if (n_shards < 1 || n_shards > 64) return fail(BBQ_ERR_INVALID_ARG, "bbq_index_create_multi: n_shards must be in 1..64");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(BBQ_ERR_NO_DEVICE, "no HIP device available: libbbq has no CPU fallback (hipGetDeviceCount found %d)", ndev);
-  for (int s = 0; s < n_shards; ++s) {
-    const int d = devices ? devices[s] : s;
-    if (d < 0 || d >= ndev) return fail(BBQ_ERR_INVALID_ARG, "device %d out of range (0..%d)", d, ndev - 1);
+  for (int s = 0; s < n_shards; ++s) {  // (n_shards >= 1: a machine without a device is reported here, before the remaining checks)
+    const int rc = check_device(devices ? devices[s] : s);
+    if (rc != BBQ_OK) return rc;
   }
   if (n_rows > 0xFFFFFFFFll) return fail(BBQ_ERR_UNSUPPORTED, "more than 2^32 rows");
   if (check_options(opts) != BBQ_OK) return BBQ_ERR_INVALID_ARG;
@@ -557,11 +550,7 @@ int bbq_index_create_multi_opts(const uint8_t *codes, const double *corr, int64_
   bbq_index_options shard_opts{(int32_t)sizeof(bbq_index_options), want_compact_of(opts) ? BBQ_CORRECTIONS_COMPACT : BBQ_CORRECTIONS_INLINE};
 
   std::unique_ptr<bbq_index> ix(new bbq_index());
-  ix->dim = dim;
-  ix->index_bits = index_bits;
-  ix->store_bits = dim == 1 ? 1 : store_bits_of(index_bits);
-  ix->pb = row_bytes_of(dim, ix->store_bits);
-  ix->w16 = (ix->pb + 15) / 16;
+  set_index_geometry(ix.get(), dim, index_bits);
   ix->n_rows = n_rows;
   ix->centroid_dp = centroid_dp;
   ix->device = devices ? devices[0] : 0;

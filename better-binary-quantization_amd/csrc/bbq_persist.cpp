@@ -309,8 +309,8 @@ int bbq_index_load_multi(const char *prefix, int32_t n_devices, const int32_t *d
   int rc = read_manifest(prefix, &m);
   if (rc != BBQ_OK) return rc;
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(BBQ_ERR_NO_DEVICE, "no HIP device available: libbbq has no CPU fallback (hipGetDeviceCount found %d)", ndev);
+  rc = require_devices(&ndev);
+  if (rc != BBQ_OK) return rc;
   std::vector<bbq_index *> shards;
   std::vector<int32_t> devs;
   auto bail = [&](int code) {
@@ -352,21 +352,13 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
   if (fseeko(fc.f, 0, SEEK_END) != 0 || ftello(fc.f) < h.vectorDataOffset + h.vectorDataLength)
     return fail(BBQ_ERR_INVALID_ARG, "%s: shorter than vectorDataOffset + vectorDataLength", dpath.c_str());
   if (fseeko(fc.f, h.vectorDataOffset, SEEK_SET) != 0) return fail(BBQ_ERR_INVALID_ARG, "%s: seek failed", dpath.c_str());
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(BBQ_ERR_NO_DEVICE, "no HIP device available: libbbq has no CPU fallback (hipGetDeviceCount found %d)", ndev);
-  if (device < 0 || device >= ndev) return fail(BBQ_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-  HIPCHK(hipSetDevice(device));
   DeviceCtx *ctx = nullptr;
-  rc = get_ctx(device, &ctx);
+  rc = open_device(device, &ctx);
   if (rc != BBQ_OK) return rc;
   std::lock_guard<std::mutex> lk(ctx->mu);
   std::unique_ptr<bbq_index> ix(new bbq_index());
-  ix->device = device;
-  ix->dim = h.dimensions;
-  ix->index_bits = h.indexBits;
-  ix->store_bits = h.dimensions == 1 ? 1 : store_bits_of(h.indexBits);
-  ix->pb = row_bytes_of(h.dimensions, ix->store_bits);
+  rc = attach_index(ix.get(), ctx, device, h.dimensions, h.indexBits);
+  if (rc != BBQ_OK) return rc;
   ix->w16 = h.w16;
   ix->n_rows = h.vectorCount;
   ix->row_base = h.rowBase;
@@ -377,12 +369,6 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
   ix->has_x1 = h.hasX1;
   ix->tile_stride = h.tileStride;
   ix->bytes_per_row = h.tileStride / kTileRows;
-  ix->ctx = ctx;
-  ix->slots = ctx->slots;
-  ix->aux_stream = ctx->aux_stream;
-  ix->d_aux_flags = ctx->d_aux_flags;
-  rc = ensure_aux_qbuf(ctx, qbuf_bytes_per_query_w(ix->w16));
-  if (rc != BBQ_OK) return rc;
   auto bail = [&](int code) {
     destroy_unlocked(ix.release());
     return code;

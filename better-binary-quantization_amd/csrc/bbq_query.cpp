@@ -1,0 +1,189 @@
+// bbq_query.cpp - query staging: bit-planes and multi-bit dwords, the int8 and FP6 MFMA operands, and the checks of a call's query
+// arguments.
+#include <math.h>
+#include <string.h>
+#include "bbq_search.h"
+
+namespace bbq {
+
+// per query: bit-planes (up to 8) + int8 values in MFMA fragment order + score uniforms + group maxima
+int64_t qbuf_bytes_per_query_w(int w16) { return (int64_t)w16 * 8 * 16 + (int64_t)w16 * 128 + (int64_t)sizeof(QueryParams) + 16; }
+
+int max_value(const uint8_t *q, int64_t count) {
+  uint8_t m = 0;
+  for (int64_t i = 0; i < count; ++i) m = std::max(m, q[i]);
+  return m;
+}
+
+static int planes_for(const uint8_t *q, int64_t count) {
+  uint8_t m = 0;
+  for (int64_t i = 0; i < count; ++i) m |= q[i];
+  if (m <= 1) return 1;
+  if (m <= 3) return 2;
+  if (m <= 15) return 4;
+  return 8;
+}
+
+// bytes of staged query data per query (bit-planes, or the nibble / byte dwords of a multi-bit index)
+int64_t query_data_bytes(const bbq_index *ix, int planes) { return (int64_t)ix->w16 * query_units_per_chunk(planes, ix->store_bits) * 16; }
+
+// kernel variant for a call: 1-bit index -> number of bit-planes the query values need; multi-bit index -> 4 (values <= 15: low
+// nibbles only) or 8
+int planes_of_call(const bbq_index *ix, const uint8_t *q, int64_t count, int one_bit) {
+  if (ix->store_bits == 1) return one_bit ? 1 : planes_for(q, count);
+  if (ix->store_bits == 8) return 8;
+  return max_value(q, count) <= 15 ? 4 : 8;
+}
+
+// writes the query data and the score uniforms of one query into the staging buffer.
+// 1-bit index: bit-planes ([j][p] 16-byte blocks, packed like the rows: dim d -> byte d>>3, bit 7-(d&7)).
+// multi-bit index: per row dword w the dwords the kernel multiplies its unfolded fields with (dot_chunk_multibit):
+//   store_bits 2: {lo nibbles of dims 16w+0,2,..,14 | lo nibbles of dims 16w+1,3,..,15 [| hi nibbles of the same, planes == 8]}
+//   store_bits 4: {lo nibbles of dims 8w..8w+7 [| hi nibbles]}          store_bits 8: {bytes of dims 4w..4w+3}
+void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const uint8_t *q, const double *qc, int planes,
+                int one_bit, int sim) {
+  memset(planes_dst, 0, (size_t)query_data_bytes(ix, planes));
+  if (ix->store_bits == 1) {
+    // eight dimensions (one byte of every plane) at a time: bit p of the eight query bytes, gathered MSB-first by one multiply -
+    // source bit 8i (dimension 8*byte + i) goes to bit 63 - i of the product, no two partial products share a position
+    const int full = ix->dim >> 3;
+    for (int byte = 0; byte < full; ++byte) {
+      uint64_t x;
+      memcpy(&x, q + (size_t)byte * 8, 8);
+      if (!x) continue;
+      const int j = byte >> 4, b = byte & 15;
+      for (int p = 0; p < planes; ++p)
+        planes_dst[((size_t)j * planes + p) * 16 + b] = (uint8_t)((((x >> p) & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56);
+    }
+    for (int d = full * 8; d < ix->dim; ++d) {  // the last, partial byte
+      const uint8_t v = q[d];
+      if (!v) continue;
+      const int byte = d >> 3, j = byte >> 4, b = byte & 15;
+      const uint8_t bit = (uint8_t)(0x80u >> (d & 7));
+      for (int p = 0; p < planes; ++p)
+        if ((v >> p) & 1) planes_dst[((size_t)j * planes + p) * 16 + b] |= bit;
+    }
+  } else {
+    const int sb = ix->store_bits, per = 32 / sb, qn = query_units_per_chunk(planes, sb);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(planes_dst);
+    for (int d = 0; d < ix->dim; ++d) {
+      const uint32_t v = q[d];
+      if (!v) continue;
+      const int w = d / per, f = d % per;
+      uint32_t *qw = dst + (size_t)w * qn;
+      if (sb == 2) {
+        const int half = f & 1, nib = f >> 1;
+        qw[half] |= (v & 15u) << (4 * nib);
+        if (planes > 4) qw[2 + half] |= (v >> 4) << (4 * nib);
+      } else if (sb == 4) {
+        qw[0] |= (v & 15u) << (4 * f);
+        if (planes > 4) qw[1] |= (v >> 4) << (4 * f);
+      } else {
+        qw[0] |= v << (8 * f);
+      }
+    }
+  }
+  const double FBS = 1.0 / 15.0;  // src/constants.ts:20
+  pp->ay = qc[0];
+  pp->ly = one_bit ? (qc[1] - qc[0]) : (qc[1] - qc[0]) * FBS;  // src/batchDotProduct.ts:498 / :574
+  pp->y1 = qc[3];
+  pp->qadd = qc[2];
+  // multi-bit index: the reference's batch scorer throws on unpacked rows and its per-row scorer answers
+  // (src/binaryQuantizedScorer.ts:403-419): centroidDP is 0 for every query width but 1 (searchNearestNeighbors passes no
+  // original query, :290) and MAXIMUM_INNER_PRODUCT is not divided by FOUR_BIT_SCALE (:207-209)
+  const bool per_row_form = ix->store_bits > 1;
+  pp->cdp = (per_row_form && !one_bit) ? 0.0 : ix->centroid_dp;
+  pp->dimd = (double)ix->dim;
+  pp->sim = sim;
+  pp->one_bit = one_bit;
+  pp->mip_plain = per_row_form ? 1 : 0;
+  pp->pad_ = 0;
+}
+
+// MFMA shared sweep, int8 form (query values up to 127): the int8 query values in the order the code bits fall out of the packed
+// words.  For 32-dim word g, half h, dword c, byte i the kernel extracts bit p = 4h + c + 8i of the little-endian word, which is row
+// byte 4g + (p >> 3), bit (p & 7), i.e. dimension 32g + 8*(p >> 3) + 7 - (p & 7) (MSB-first packing,
+// src/optimizedScalarQuantizer.ts:420-446).  Layout: [group][g][h][n][16 B], n = query in its group of 32.
+void fill_query_mfma(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q) {
+  const int words = ix->w16 * 4, group = q_in_batch / 32, n = q_in_batch % 32;
+  uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->w16, false);
+  for (int g = 0; g < words; ++g)
+    for (int h = 0; h < 2; ++h) {
+      uint8_t *o = gb + (((size_t)g * 2 + h) * 32 + n) * 16;
+      for (int cc = 0; cc < 4; ++cc)
+        for (int i = 0; i < 4; ++i) {
+          const int p = 4 * h + cc + 8 * i;
+          const int d = 32 * g + 8 * (p >> 3) + 7 - (p & 7);
+          o[4 * cc + i] = d < ix->dim ? q[d] : 0;
+        }
+    }
+}
+
+// FP form (query values <= 15): v_mfma_f32_32x32x64_f8f6f4 with the rows as FP4 and the queries as FP6 (e2m3).  Step g covers the
+// code words 2g (lower half-wave) and 2g + 1 (upper); element i of a lane is bit p = 4 (i & 7) + (i >> 3) of its word - the kernel
+// masks bit c = i >> 3 of every nibble where it stands, an FP4 number of 0.5, 1.0, 2.0 and (bit 3, shifted down) 0.5 - and the query
+// value carries 1/2, 1/4, 1/8, 1/2 against it: every product is q / 4 (q / 2 or q for smaller query values, see below).  e2m3 holds q / 2, q / 4 and q / 8 exactly for q <= 15
+// (exponent 0: m / 8; exponent e: (1 + m / 8) 2^(e-1)).  A lane's 32 six-bit codes are 24 bytes: the first 16 in [g][h][n][16 B],
+// the last 8 in [g][h][n][8 B] behind all of them (two aligned LDS reads per lane and step).
+static uint32_t fp6_code_of_eighths(int eighths) {
+  if (eighths < 8) return (uint32_t)eighths;                   // exponent field 0: m / 8
+  int e = 1;
+  while (eighths >= (8 << e)) ++e;                             // 2^(e-1) <= value < 2^e
+  return ((uint32_t)e << 3) | (uint32_t)((eighths >> (e - 1)) - 8);   // exact: the low e - 1 bits of eighths are zero for q <= 15
+}
+
+void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q, int scale8) {
+  const int steps = ix->w16 * 2, group = q_in_batch / 32, n = q_in_batch % 32;
+  uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->w16, true);
+  uint8_t *gb2 = gb + (size_t)steps * 2 * 32 * 16;
+  // the value x 8: q/2, q/4, q/8, q/2 at scale8 = 2 (products q/4: values up to 15); twice that for values up to 7 (scale8 = 4,
+  // products q/2), four times for values up to 3 (scale8 = 8, products q): the finest grain e2m3's range (7.5) allows
+  uint8_t lut[4][16];
+  for (int cls = 0; cls < 4; ++cls)
+    for (int v = 0; v < 16; ++v) lut[cls][v] = (uint8_t)fp6_code_of_eighths(v * (cls == 1 ? 2 : cls == 2 ? 1 : 4) * (scale8 / 2));
+  // element i = 8 cls + j of a lane is bit p = 4 j + cls of its word: row byte j >> 1, bit 4 (j & 1) + cls, i.e. dimension
+  // 8 (j >> 1) + 7 - 4 (j & 1) - cls of the word's 32.  The eight six-bit codes of a class are 48 bits: bytes [6 cls, 6 cls + 6)
+  static const int off[8] = {7, 3, 15, 11, 23, 19, 31, 27};
+  for (int g = 0; g < steps; ++g)
+    for (int h = 0; h < 2; ++h) {
+      const int base = 32 * (2 * g + h);
+      uint8_t bits[24];
+      for (int cls = 0; cls < 4; ++cls) {
+        uint64_t v48 = 0;
+        if (base + 32 <= ix->dim) {
+          for (int j = 0; j < 8; ++j) v48 |= (uint64_t)lut[cls][q[base + off[j] - cls] & 15] << (6 * j);
+        } else {
+          for (int j = 0; j < 8; ++j) {
+            const int d = base + off[j] - cls;
+            v48 |= (uint64_t)lut[cls][d < ix->dim ? (q[d] & 15) : 0] << (6 * j);
+          }
+        }
+        for (int b = 0; b < 6; ++b) bits[6 * cls + b] = (uint8_t)(v48 >> (8 * b));
+      }
+      memcpy(gb + (((size_t)g * 2 + h) * 32 + n) * 16, bits, 16);
+      memcpy(gb2 + (((size_t)g * 2 + h) * 32 + n) * 8, bits + 16, 8);
+    }
+}
+
+// The matrix-core sweep tests "score > threshold" as an inequality on the integer dot product (bbq_mfma_kernels.hip), which divides by
+// the query's interval width: it takes queries with a positive, finite width and finite corrections; any other sub-batch sweeps on
+// the vector ALUs.
+bool mfma_query_ok(const QueryParams &p) {
+  return p.ly > 0.0 && p.ly < 1e30 && 1.0 / p.ly < 1e30 && fabs(p.ay) < 1e30 && fabs(p.y1) < 1e30 && fabs(p.qadd) < 1e30 && fabs(p.cdp) < 1e30;
+}
+
+int validate_query_args(const bbq_index *ix, int32_t nq, const uint8_t *qquant, const double *qcorr, int32_t query_bits,
+                        int32_t sim, int64_t k, bool values_pending) {
+  if (!ix) return fail(BBQ_ERR_INVALID_ARG, "目标向量集合不能为空");
+  if (nq < 0) return fail(BBQ_ERR_INVALID_ARG, "n_queries < 0");
+  if (nq > 0 && (!qquant || !qcorr)) return fail(BBQ_ERR_INVALID_ARG, "查询向量不能为空");
+  if (k < 0) return fail(BBQ_ERR_NEGATIVE_K, "k值不能为负数");
+  if (query_bits < 1 || query_bits > 8) return fail(BBQ_ERR_INVALID_ARG, "queryBits必须在1-8之间");
+  if (sim < 0 || sim > 2) return fail(BBQ_ERR_INVALID_ARG, "不支持的相似性函数: %d", sim);
+  if (query_bits == 1 && !values_pending)  // (values_pending: the library's own quantizer is still producing them)
+    for (int64_t i = 0; i < (int64_t)nq * ix->dim; ++i)
+      if (qquant[i] > 1) return fail(BBQ_ERR_INVALID_ARG, "1位量化值必须为0或1");
+  return BBQ_OK;
+}
+
+}  // namespace bbq

@@ -181,7 +181,7 @@ class OptimizedScalarQuantizer {
   static discretize(value, bucket) { return Math.floor((value + (bucket - 1)) / bucket) * bucket; }
   /**
    * transposeHalfByte(q, quantQueryByte): the four bit-planes of a 4-bit query, ONE BYTE PER BIT (plane p of dimension i at
-   * i + p * q.length), :476-517.  (The device keeps the planes packed eight dimensions to a byte: bbq_core.cpp fill_query.)
+   * i + p * q.length), :476-517.  (The device keeps the planes packed eight dimensions to a byte: bbq_query.cpp fill_query.)
    */
   static transposeHalfByte(q, quantQueryByte) {
     if (!q || !quantQueryByte) throw new Error('输入数组不能为空');

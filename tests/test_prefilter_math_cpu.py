@@ -62,7 +62,7 @@ FORMS = {"int8": dict(S=1.0, ulp=1.0, bias=12582912.0, mag_limit=4000000.0, pass
 
 
 def fp_scale(max_q):
-    """bbq_core.cpp enqueue_subbatch: products of q, q / 2 or q / 4 - the largest the query values leave room for in e2m3"""
+    """bbq_core.cpp enqueue_subbatch (operands: bbq_query.cpp fill_query_mfma_fp): products of q, q / 2 or q / 4 - the largest the query values leave room for in e2m3"""
     return 1.0 if max_q <= 3 else 0.5 if max_q <= 7 else 0.25
 
 
@@ -202,7 +202,7 @@ def test_prefilter_slack_is_small_on_a_real_shape(form, qb):
 
 
 def test_fp6_codes_of_the_staged_query_values():
-    """fill_query_mfma_fp (bbq_core.cpp): e2m3 holds q / 2, q / 4, q / 8 exactly for q = 0..15; restated here and decoded again"""
+    """fill_query_mfma_fp (bbq_query.cpp): e2m3 holds q / 2, q / 4, q / 8 exactly for q = 0..15; restated here and decoded again"""
     for q in range(16):
         for mult in (4, 2, 1, 8, 16):                # the value x 8 (x 2 and x 4 on top for query values up to 7 and up to 3)
             if (mult == 8 and q > 7) or (mult == 16 and q > 3):
