@@ -45,78 +45,59 @@ int bbq_index_build_opts(const float *vectors, int64_t n, int32_t dim, int32_t s
 
   const int64_t npad = (n + kTileRows - 1) / kTileRows * kTileRows;
   const int dim4 = (dim + 3) / 4;
-  float *d_in = nullptr, *d_vT4 = nullptr, *d_cen = nullptr;
-  unsigned long long *d_bad = nullptr;
-  double *d_corr = nullptr;
-  uint8_t *d_codes = nullptr;
-  std::unique_ptr<bbq_index> ix(new bbq_index());
-  auto cleanup = [&]() {
-    if (d_in) (void)hipFree(d_in);
-    if (d_vT4) (void)hipFree(d_vT4);
-    if (d_cen) (void)hipFree(d_cen);
-    if (d_bad) (void)hipFree(d_bad);
-    if (d_corr) (void)hipFree(d_corr);
-    if (d_codes) (void)hipFree(d_codes);
-  };
-#define BCHK(expr)                                                                                   \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) {                                                                          \
-      cleanup();                                                                                     \
-      destroy_unlocked(ix.release());                                                                \
-      return fail(BBQ_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));                      \
-    }                                                                                                \
-  } while (0)
-  BCHK(hipMalloc((void **)&d_in, (size_t)n * dim * 4));
-  BCHK(hipMalloc((void **)&d_vT4, (size_t)dim4 * npad * 16));
-  BCHK(hipMemcpyAsync(d_in, vectors, (size_t)n * dim * 4, hipMemcpyHostToDevice, st));
-  BCHK(launch_build_transpose(d_in, n, dim, npad, d_vT4, st));
-  BCHK(hipStreamSynchronize(st));
-  BCHK(hipFree(d_in));
-  d_in = nullptr;
-  if (sim == BBQ_COSINE) BCHK(launch_build_normalize(d_vT4, n, dim, npad, st));  // src/binaryQuantizationFormat.ts:174-176
+  DevBuf<float> d_in, d_vT4, d_cen;
+  DevBuf<unsigned long long> d_bad;
+  DevBuf<double> d_corr;
+  DevBuf<uint8_t> d_codes;
+  // every exit below that does not hand the index out retires it through destroy_unlocked (the context mutex is held)
+  std::unique_ptr<bbq_index, void (*)(bbq_index *)> ix(new bbq_index(), destroy_unlocked);
+  ix->device = device;
+  HIPCHK(d_in.alloc((size_t)n * dim));
+  HIPCHK(d_vT4.alloc((size_t)dim4 * npad * 4));
+  HIPCHK(hipMemcpyAsync(d_in, vectors, (size_t)n * dim * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(launch_build_transpose(d_in, n, dim, npad, d_vT4, st));
+  HIPCHK(hipStreamSynchronize(st));
+  d_in.reset();  // the peak footprint of a build: the transposed copy alone from here on
+  if (sim == BBQ_COSINE) HIPCHK(launch_build_normalize(d_vT4, n, dim, npad, st));  // src/binaryQuantizationFormat.ts:174-176
   // :196-211 NaN / Infinity validation on the processed vectors, first offender in row-major order
   unsigned long long bad = ~0ull;
-  BCHK(hipMalloc((void **)&d_bad, 8));
-  BCHK(hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, st));
-  BCHK(launch_build_validate(d_vT4, n, dim, npad, d_bad, st));
-  BCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
-  BCHK(hipStreamSynchronize(st));
+  HIPCHK(d_bad.alloc(1));
+  HIPCHK(hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, st));
+  HIPCHK(launch_build_validate(d_vT4, n, dim, npad, d_bad, st));
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   if (bad != ~0ull) {
     const int64_t r = (int64_t)(bad / (unsigned long long)dim);
     const int c = (int)(bad % (unsigned long long)dim);
     float v = 0;
-    BCHK(hipMemcpy(&v, d_vT4 + ((size_t)(c / 4) * npad + r) * 4 + (c & 3), 4, hipMemcpyDeviceToHost));
-    cleanup();
+    HIPCHK(hipMemcpy(&v, d_vT4 + ((size_t)(c / 4) * npad + r) * 4 + (c & 3), 4, hipMemcpyDeviceToHost));
     if (bad_row) *bad_row = r;
     if (bad_col) *bad_col = c;
     if (v != v) return fail(BBQ_ERR_NAN_INPUT, "向量 %lld 位置 %d 包含NaN值", (long long)r, c);
     return fail(BBQ_ERR_INF_INPUT, "向量 %lld 位置 %d 包含Infinity值", (long long)r, c);
   }
-  BCHK(hipMalloc((void **)&d_cen, (size_t)dim4 * 16));
-  BCHK(launch_build_centroid(d_vT4, n, dim, npad, d_cen, st));  // :214
-  BCHK(hipMemcpyAsync(centroid, d_cen, (size_t)dim * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(d_cen.alloc((size_t)dim4 * 4));
+  HIPCHK(launch_build_centroid(d_vT4, n, dim, npad, d_cen, st));  // :214
+  HIPCHK(hipMemcpyAsync(centroid, d_cen, (size_t)dim * 4, hipMemcpyDeviceToHost, st));
 
   rc = attach_index(ix.get(), ctx, device, dim, index_bits);
-  if (rc != BBQ_OK) { cleanup(); destroy_unlocked(ix.release()); return rc; }
+  if (rc != BBQ_OK) return rc;
   ix->n_rows = n;
   ix->row_base = 0;
   ix->want_compact = want_compact_of(opts);
   if (index_bits > 1) {
     // more than one bit: the kernel leaves what the reference keeps for such an index - one byte per dimension - and the corrections
     // in device memory; the tile records are built from there exactly as bbq_index_create builds them from host rows
-    BCHK(hipMalloc((void **)&d_codes, (size_t)n * dim));
-    BCHK(hipMalloc((void **)&d_corr, (size_t)n * 32));
-    BCHK(launch_build_quantize_bits(d_vT4, n, dim, npad, d_cen, sim, lambda, iters, index_bits, d_codes, d_corr, st));  // :221-249
-    BCHK(hipStreamSynchronize(st));
-    BCHK(hipFree(d_vT4));
-    d_vT4 = nullptr;
+    HIPCHK(d_codes.alloc((size_t)n * dim));
+    HIPCHK(d_corr.alloc((size_t)n * 4));
+    HIPCHK(launch_build_quantize_bits(d_vT4, n, dim, npad, d_cen, sim, lambda, iters, index_bits, d_codes, d_corr, st));  // :221-249
+    HIPCHK(hipStreamSynchronize(st));
+    d_vT4.reset();  // before the tile records are allocated
     ix->centroid_dp = bbq_centroid_dp(centroid, dim);
     rc = storage_from_device_rows(ix.get(), ix->main, d_codes, d_corr, n, 0, true);
     if (rc == BBQ_OK && corr && hipMemcpy(corr, d_corr, (size_t)n * 32, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(BBQ_ERR_HIP, "bbq_index_build: copy of the corrections failed");
     if (rc == BBQ_OK && codes && hipMemcpy(codes, d_codes, (size_t)n * dim, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(BBQ_ERR_HIP, "bbq_index_build: copy of the codes failed");
-    cleanup();
-    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
+    if (rc != BBQ_OK) return rc;
     *out = ix.release();
     return BBQ_OK;
   }
@@ -126,32 +107,20 @@ int bbq_index_build_opts(const float *vectors, int64_t n, int32_t dim, int32_t s
   ix->bytes_per_row = ix->tile_stride / kTileRows;
   Storage &sto = ix->main;
   const int64_t n_tiles = npad / kTileRows;
-  BCHK(hipMalloc((void **)&sto.d_tiles, (size_t)n_tiles * ix->tile_stride));
-  if (ix->layout == kLayoutCompact) BCHK(hipMalloc((void **)&sto.d_exact, (size_t)compact_side_bytes(n_tiles)));
-  if (corr) BCHK(hipMalloc((void **)&d_corr, (size_t)n * 32));
-  BCHK(launch_build_quantize1(d_vT4, n, dim, npad, d_cen, sim, lambda, iters, sto.d_tiles, sto.d_exact, d_corr, ix->w16, ix->tile_stride,
+  HIPCHK(sto.d_tiles.alloc((size_t)n_tiles * ix->tile_stride));
+  if (ix->layout == kLayoutCompact) HIPCHK(sto.d_exact.alloc((size_t)compact_side_bytes(n_tiles) / 8));
+  if (corr) HIPCHK(d_corr.alloc((size_t)n * 4));
+  HIPCHK(launch_build_quantize1(d_vT4, n, dim, npad, d_cen, sim, lambda, iters, sto.d_tiles, sto.d_exact, d_corr, ix->w16, ix->tile_stride,
                               ix->layout, st));  // :221-249
-  if (ix->layout == kLayoutCompact) BCHK(launch_tile_add_range(sto.d_exact, n, const_cast<float *>(add_range_of(sto.d_exact, n_tiles)), st));
-  if (corr) BCHK(hipMemcpyAsync(corr, d_corr, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+  if (ix->layout == kLayoutCompact) HIPCHK(launch_tile_add_range(sto.d_exact, n, const_cast<float *>(add_range_of(sto.d_exact, n_tiles)), st));
+  if (corr) HIPCHK(hipMemcpyAsync(corr, d_corr, (size_t)n * 32, hipMemcpyDeviceToHost, st));
   if (codes) {
-    BCHK(hipMalloc((void **)&d_codes, (size_t)n * ix->pb));
-    BCHK(launch_build_untile(sto.d_tiles, n, ix->pb, ix->w16, ix->tile_stride, d_codes, st));
-    BCHK(hipMemcpyAsync(codes, d_codes, (size_t)n * ix->pb, hipMemcpyDeviceToHost, st));
+    HIPCHK(d_codes.alloc((size_t)n * ix->pb));
+    HIPCHK(launch_build_untile(sto.d_tiles, n, ix->pb, ix->w16, ix->tile_stride, d_codes, st));
+    HIPCHK(hipMemcpyAsync(codes, d_codes, (size_t)n * ix->pb, hipMemcpyDeviceToHost, st));
   }
-  BCHK(hipStreamSynchronize(st));
-#undef BCHK
-  cleanup();
-  sto.row_id_base = 0;
-  sto.view.tiles = sto.d_tiles;
-  sto.view.exact = sto.d_exact;
-  sto.view.add_range = add_range_of(sto.d_exact, n_tiles);
-  sto.view.n_rows = n;
-  sto.view.w16 = ix->w16;
-  sto.view.tile_stride = ix->tile_stride;
-  sto.view.has_x1 = 0;
-  sto.view.dim = dim;
-  sto.view.layout = ix->layout;
-  sto.view.store_bits = 1;
+  HIPCHK(hipStreamSynchronize(st));
+  set_storage_view(ix.get(), sto, n, 0);
   ix->centroid_dp = bbq_centroid_dp(centroid, dim);  // getCentroidDP(undefined), :113-121
   *out = ix.release();
   return BBQ_OK;

@@ -222,32 +222,6 @@ void build_plan(bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
 
 // ------------------------------------------------------------------------------------------------ slots
 
-static void free_slot_buffers(Slot &s) {
-  if (s.d_block) (void)hipFree(s.d_block);
-  if (s.h_block) (void)hipHostFree(s.h_block);
-  s.d_block = s.h_block = nullptr;
-  if (s.d_counts) (void)hipFree(s.d_counts);
-  if (s.d_topk) (void)hipFree(s.d_topk);
-  if (s.h_list_counts) (void)hipHostFree(s.h_list_counts);
-  if (s.d_entries) (void)hipFree(s.d_entries);
-  if (s.d_lists) (void)hipFree(s.d_lists);
-  if (s.h_lists) (void)hipHostFree(s.h_lists);
-  if (s.d_dense0) (void)hipFree(s.d_dense0);
-  if (s.d_ovf) (void)hipFree(s.d_ovf);
-  if (s.d_final) (void)hipFree(s.d_final);
-  if (s.h_final) (void)hipHostFree(s.h_final);
-  s.d_final = s.h_final = nullptr;
-  s.final_stride = 0;
-  s.d_ovf = nullptr;
-  s.d_ovf_counts = nullptr;
-  s.d_qbuf = s.h_qbuf = nullptr;
-  s.d_theta = s.d_flags = s.d_counts = s.d_topk = nullptr;
-  s.d_topk_counts = s.d_list_counts = s.h_list_counts = nullptr;
-  s.d_entries = s.d_lists = s.h_lists = nullptr;
-  s.d_dense0 = nullptr;
-  s.q_cap = 0;
-}
-
 static int64_t qbuf_bytes_per_query(const bbq_index *ix) { return qbuf_bytes_per_query_w(ix->w16); }
 
 int ensure_slot(bbq_index *ix, Slot &s, int nq, bool own_lists) {
@@ -261,13 +235,11 @@ int ensure_slot(bbq_index *ix, Slot &s, int nq, bool own_lists) {
   if (ok) return BBQ_OK;
   // grow-only in every dimension: a process that alternates between call shapes (single queries use another segment plan than
   // batches, k varies) would otherwise free and allocate the workspace at every switch - each time sized for the plan at hand and
-  // therefore too small for the other one (milliseconds per switch)
-  const int old_q = s.q_cap;
-  const int64_t old_final = s.final_stride;
-  const bool had_lists = s.d_lists != nullptr;
-  free_slot_buffers(s);
-  own_lists = own_lists || had_lists;
-  const int Q = std::max((std::max(nq, effective_batch(ix)) + 31) / 32 * 32, old_q);  // multiple of 32: the MFMA query layout is per group of 32
+  // therefore too small for the other one (milliseconds per switch).  Every buffer grows on its own: one that is large enough stays
+  own_lists = own_lists || s.d_lists != nullptr;
+  const int Q = std::max((std::max(nq, effective_batch(ix)) + 31) / 32 * 32, s.q_cap);  // multiple of 32: the MFMA query layout is per group of 32
+  const bool valid = s.q_cap > 0;
+  s.q_cap = 0;  // the capacities below describe the buffers only once all of them are in place: a call after a failure grows again
   s.qbuf_bytes = std::max(s.qbuf_bytes, qb);
   s.chunks_cap = std::max<int64_t>(s.chunks_cap, std::max<int64_t>(p.max_chunks, 1));
   s.slots_cap = std::max<int64_t>(s.slots_cap, std::max<int64_t>(p.max_slots, 1));
@@ -276,34 +248,38 @@ int ensure_slot(bbq_index *ix, Slot &s, int nq, bool own_lists) {
   s.list_cap = std::max<int64_t>(s.list_cap, p.list_cap + (own_lists ? s.flood_cap : 0));  // own lists can take a flood; external ones are the caller's size
   s.k_cap = std::max<int64_t>(s.k_cap, std::max<int64_t>(p.k, 1));
   s.hprefix = std::max<int64_t>(s.hprefix, hprefix);
+  s.final_stride = std::max<int64_t>(s.final_stride, std::max<int64_t>(p.final_k, 126) + 2);
   // theta | flags | topk_counts | list_counts | ovf_counts | append_counts live in one control block in front of the staged queries: the copy that
   // brings a sub-batch's queries also resets them (the host twin's control part stays zero)
-  s.ctrl_bytes = ((int64_t)Q * (24 + 4 * kAppendStride) + 255) / 256 * 256;  // the append counters sit one per 128-byte line (kAppendStride)
-  HIPCHK(hipMalloc((void **)&s.d_block, (size_t)(s.ctrl_bytes + Q * s.qbuf_bytes)));
-  s.ctrl_clean = false;
-  HIPCHK(hipHostMalloc((void **)&s.h_block, (size_t)(s.ctrl_bytes + Q * s.qbuf_bytes), hipHostMallocDefault));
-  memset(s.h_block, 0, (size_t)s.ctrl_bytes);
-  s.d_qbuf = s.d_block + s.ctrl_bytes;
-  s.h_qbuf = s.h_block + s.ctrl_bytes;
-  s.d_theta = reinterpret_cast<uint32_t *>(s.d_block);
-  s.d_flags = s.d_theta + Q;
-  s.d_topk_counts = reinterpret_cast<int32_t *>(s.d_theta + 2 * (size_t)Q);
-  s.d_list_counts = reinterpret_cast<int32_t *>(s.d_theta + 3 * (size_t)Q);
-  s.d_ovf_counts = s.d_theta + 5 * (size_t)Q;
-  s.d_append_counts = s.d_theta + 6 * (size_t)Q;
-  if (s.flood_cap > 0) HIPCHK(hipMalloc((void **)&s.d_ovf, (size_t)(Q * s.flood_cap) * 8));
-  HIPCHK(hipMalloc((void **)&s.d_counts, (size_t)(Q * s.chunks_cap) * 4));
-  HIPCHK(hipMalloc((void **)&s.d_topk, (size_t)(Q * s.k_cap) * 4));
-  HIPCHK(hipHostMalloc((void **)&s.h_list_counts, (size_t)Q * 8, hipHostMallocDefault));
-  HIPCHK(hipMalloc((void **)&s.d_entries, (size_t)(Q * s.slots_cap) * 8));
-  HIPCHK(hipMalloc((void **)&s.d_dense0, (size_t)(Q * s.dense_cap) * 4));
-  if (own_lists) {
-    HIPCHK(hipMalloc((void **)&s.d_lists, (size_t)(Q * s.list_cap) * 8));
-    HIPCHK(hipHostMalloc((void **)&s.h_lists, (size_t)(Q * s.hprefix) * 8, hipHostMallocDefault));
+  const int64_t ctrl_bytes = ((int64_t)Q * (24 + 4 * kAppendStride) + 255) / 256 * 256;  // the append counters sit one per 128-byte line (kAppendStride)
+  const size_t block = (size_t)(ctrl_bytes + Q * s.qbuf_bytes);
+  if (!valid || s.d_block.size() < block) {  // (the control layout depends on Q alone, and a larger Q is a larger block)
+    s.ctrl_bytes = ctrl_bytes;
+    HIPCHK(s.d_block.alloc(block));
+    s.ctrl_clean = false;
+    HIPCHK(s.h_block.alloc(block));
+    memset(s.h_block, 0, (size_t)s.ctrl_bytes);
+    s.d_qbuf = s.d_block + s.ctrl_bytes;
+    s.h_qbuf = s.h_block + s.ctrl_bytes;
+    s.d_theta = reinterpret_cast<uint32_t *>(s.d_block.get());
+    s.d_flags = s.d_theta + Q;
+    s.d_topk_counts = reinterpret_cast<int32_t *>(s.d_theta + 2 * (size_t)Q);
+    s.d_list_counts = reinterpret_cast<int32_t *>(s.d_theta + 3 * (size_t)Q);
+    s.d_ovf_counts = s.d_theta + 5 * (size_t)Q;
+    s.d_append_counts = s.d_theta + 6 * (size_t)Q;
   }
-  s.final_stride = std::max<int64_t>(old_final, std::max<int64_t>(p.final_k, 126) + 2);
-  HIPCHK(hipMalloc((void **)&s.d_final, (size_t)(Q * s.final_stride) * 8));
-  HIPCHK(hipHostMalloc((void **)&s.h_final, (size_t)(Q * s.final_stride) * 8, hipHostMallocDefault));
+  if (s.flood_cap > 0) HIPCHK(s.d_ovf.reserve((size_t)(Q * s.flood_cap)));
+  HIPCHK(s.d_counts.reserve((size_t)(Q * s.chunks_cap)));
+  HIPCHK(s.d_topk.reserve((size_t)(Q * s.k_cap)));
+  HIPCHK(s.h_list_counts.reserve((size_t)Q * 2));
+  HIPCHK(s.d_entries.reserve((size_t)(Q * s.slots_cap)));
+  HIPCHK(s.d_dense0.reserve((size_t)(Q * s.dense_cap)));
+  if (own_lists) {
+    HIPCHK(s.d_lists.reserve((size_t)(Q * s.list_cap)));
+    HIPCHK(s.h_lists.reserve((size_t)(Q * s.hprefix)));
+  }
+  HIPCHK(s.d_final.reserve((size_t)(Q * s.final_stride)));
+  HIPCHK(s.h_final.reserve((size_t)(Q * s.final_stride)));
   s.q_cap = Q;
   return BBQ_OK;
 }

@@ -26,7 +26,7 @@ ScanArgs dense_scan_args(const BatchCtx &c, int64_t chunk_begin) {
   bbq_index *ix = c.ix;
   ScanArgs a{};
   a.idx = launch_view(ix, ix->main);
-  a.qplanes = reinterpret_cast<const uint4 *>(ix->ctx->d_aux_qbuf);
+  a.qplanes = reinterpret_cast<const uint4 *>(ix->ctx->d_aux_qbuf.get());
   a.qparams = reinterpret_cast<const QueryParams *>(ix->ctx->d_aux_qbuf + query_data_bytes(ix, c.planes));
   a.chunk_begin = chunk_begin;
   a.row_id_base = ix->main.row_id_base;
@@ -39,12 +39,7 @@ int dense_scores_one(const BatchCtx &c, int64_t qi, float *out) {
   bbq_index *ix = c.ix;
   const int64_t n = ix->main.view.n_rows;
   const int64_t chunks = ix->main.n_chunks();
-  if (ix->dense_all_cap < n) {
-    if (ix->d_dense_all) HIPCHK(hipFree(ix->d_dense_all));
-    ix->d_dense_all = nullptr;
-    HIPCHK(hipMalloc((void **)&ix->d_dense_all, (size_t)std::max<int64_t>(n, 1) * 4));
-    ix->dense_all_cap = n;
-  }
+  HIPCHK(ix->d_dense_all.reserve((size_t)std::max<int64_t>(n, 1)));
   int rc = stage_aux_query(c, qi);
   if (rc != BBQ_OK) return rc;
   hipStream_t st = ix->ctx->aux_stream;
@@ -109,13 +104,12 @@ int bbq_score_rows(bbq_index *ix, const uint8_t *qquant, const double *qcorr, in
   const int64_t piece_chunks = 1024;  // 1M rows per piece
   const int64_t c_first = row_begin / kChunkRows, c_last = (row_begin + row_count + kChunkRows - 1) / kChunkRows;
   const int64_t piece_rows = std::min(piece_chunks, c_last - c_first) * kChunkRows;
-  DevMem m32, mqc, m64;
-  HIPCHK(m32.alloc((size_t)piece_rows * 4));
-  HIPCHK(mqc.alloc((size_t)piece_rows * 4));
-  HIPCHK(m64.alloc((size_t)piece_rows * 8));
-  float *d32 = m32.as<float>();
-  int32_t *dqc = mqc.as<int32_t>();
-  double *d64 = m64.as<double>();
+  DevBuf<float> d32;
+  DevBuf<int32_t> dqc;
+  DevBuf<double> d64;
+  HIPCHK(d32.alloc((size_t)piece_rows));
+  HIPCHK(dqc.alloc((size_t)piece_rows));
+  HIPCHK(d64.alloc((size_t)piece_rows));
   std::vector<float> h32((size_t)piece_rows);
   std::vector<int32_t> hqc((size_t)piece_rows);
   std::vector<double> h64((size_t)piece_rows);

@@ -8,6 +8,7 @@
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
+// HIP memory and events are held in the owning types of bbq_mem.h: what a struct below owns goes with it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@
 #include <vector>
 #include "bbq_internal.h"
 #include "bbq_launch.h"
+#include "bbq_mem.h"
 
 #define HIPCHK(expr)                                                                          \
   do {                                                                                        \
@@ -29,23 +31,12 @@
 
 namespace bbq {
 
-// device scratch that is released on every exit path
-struct DevMem {
-  void *p = nullptr;
-  DevMem() = default;
-  DevMem(const DevMem &) = delete;
-  DevMem &operator=(const DevMem &) = delete;
-  ~DevMem() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-  template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
 constexpr int kMaxSlots = 4;
 constexpr int64_t kMaxFastK = 4096;  // beyond this the dense path is used: the finalize kernel selects thresholds among at most 12288 keys (running top-k + new), and with k close to that the thresholds get too weak to pay (k = 4096: 4 ms per 10 M-row query, dense path 16 ms, k = 6000 on the sparse path 23 ms)
 
 struct Storage {
-  uint8_t *d_tiles = nullptr;
-  double *d_exact = nullptr;  // kLayoutCompact: exact corrections, gathered for the rows whose bound passes; the per-tile
+  DevBuf<uint8_t> d_tiles;
+  DevBuf<double> d_exact;     // kLayoutCompact: exact corrections, gathered for the rows whose bound passes; the per-tile
                               // additive-correction ranges (view.add_range) live behind them in the same allocation
   IndexView view{};
   int64_t row_id_base = 0;
@@ -75,23 +66,28 @@ struct Plan {
 
 struct Slot {
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr, ev_big = nullptr;
-  // capacities the buffers below were allocated for
+  Event ev0, ev1, ev_done, ev_big;
+  // capacities the buffers below hold (grow-only maxima over the plans seen; kernels take them as strides and limits)
   int q_cap = 0;
   int64_t qbuf_bytes = 0, chunks_cap = 0, slots_cap = 0, dense_cap = 0, list_cap = 0, k_cap = 0, hprefix = 0, flood_cap = 0;
   // one device block [control words of the sub-batch | staged queries] and its pinned host twin whose control part stays zero: ONE
   // host-to-device copy resets the thresholds / counters and brings the queries (d_theta.. and d_qbuf point into it)
-  uint8_t *d_block = nullptr, *h_block = nullptr;
+  DevBuf<uint8_t> d_block;
+  PinnedBuf<uint8_t> h_block;
   int64_t ctrl_bytes = 0;
+  // views into d_block / h_block, derived again whenever the block is reallocated (ensure_slot)
   uint8_t *d_qbuf = nullptr, *h_qbuf = nullptr;
-  uint32_t *d_theta = nullptr, *d_flags = nullptr, *d_counts = nullptr, *d_topk = nullptr, *d_append_counts = nullptr;
+  uint32_t *d_theta = nullptr, *d_flags = nullptr, *d_append_counts = nullptr, *d_ovf_counts = nullptr;
+  int32_t *d_topk_counts = nullptr, *d_list_counts = nullptr;
   bool appended = false;  // the in-flight sub-batch's lists are unordered inside their segments (append mode)
-  int32_t *d_topk_counts = nullptr, *d_list_counts = nullptr, *h_list_counts = nullptr;
-  uint64_t *d_entries = nullptr, *d_lists = nullptr, *h_lists = nullptr, *d_ovf = nullptr;
-  uint32_t *d_ovf_counts = nullptr;
-  float *d_dense0 = nullptr;
+  DevBuf<uint32_t> d_counts, d_topk;
+  PinnedBuf<int32_t> h_list_counts;
+  DevBuf<uint64_t> d_entries, d_lists, d_ovf;
+  PinnedBuf<uint64_t> h_lists;
+  DevBuf<float> d_dense0;
   // final selection on the device (FinalizeArgs::final_out): the sorted answer + {count, needs-host-replay} per query
-  uint64_t *d_final = nullptr, *h_final = nullptr;  // [q_cap][final_stride]: 2 header slots + the answer per query
+  DevBuf<uint64_t> d_final;  // [q_cap][final_stride]: 2 header slots + the answer per query
+  PinnedBuf<uint64_t> h_final;
   int64_t final_stride = 0;
   bool final_used = false;  // the in-flight sub-batch was enqueued with the final selection (its list prefix was NOT copied to the host)
   // in-flight sub-batch: busy = device work enqueued and not yet collected; replaying = host replay jobs outstanding
@@ -120,18 +116,24 @@ struct DeviceCtx {
   std::mutex mu;
   Slot slots[kMaxSlots];
   hipStream_t aux_stream = nullptr;   // dense path / bbq_score_rows / index build: never touches an in-flight slot
-  uint8_t *d_aux_qbuf = nullptr;
-  int64_t aux_qbuf_bytes = 0;
-  uint32_t *d_aux_flags = nullptr;
+  DevBuf<uint8_t> d_aux_qbuf;
+  DevBuf<uint32_t> d_aux_flags;
   int last_big_slot = -1;             // slot whose ev_big marks the end of the most recently enqueued big sweep
   // latency path (bbq_latency_kernels.hip): the answer of a single-query call lands in mapped, coherent host memory and the host
   // polls a sequence word behind it: [0] sequence, [8 ..) header + entries
-  uint64_t *h_lat = nullptr, *d_lat = nullptr;
+  PinnedBuf<uint64_t> h_lat{hipHostMallocMapped | hipHostMallocCoherent};
+  uint64_t *d_lat = nullptr;          // h_lat as the device sees it
   uint64_t lat_seq = 0;
-  uint32_t *d_pre_keys = nullptr;     // [kLatPreKeys] per-wave top keys of the pre-sampled threshold
+  DevBuf<uint32_t> d_pre_keys;        // [kLatPreKeys] per-wave top keys of the pre-sampled threshold
   // the indexes that launched sweeps on this device lately share its Infinity Cache (launch_view, bbq_index.cpp); under `mu`
   struct CacheUser { const void *index; int64_t bytes; uint64_t tick; };
   std::vector<CacheUser> cache_users;
+  // only ever runs for a context that get_ctx could not finish: a published one lives until the process ends
+  ~DeviceCtx() {
+    for (Slot &s : slots)
+      if (s.stream) (void)hipStreamDestroy(s.stream);
+    if (aux_stream) (void)hipStreamDestroy(aux_stream);
+  }
 };
 constexpr int kLatAnswerOffset = 8;   // words in front of the answer block inside DeviceCtx::h_lat
 
@@ -165,15 +167,14 @@ struct bbq_index {
   bool has_pilot = false;
   bbq::Storage pilot, main;
   bbq::Plan plan;
-  float *d_dense_all = nullptr;
-  int64_t dense_all_cap = 0;
+  bbq::DevBuf<float> d_dense_all;
   // bbq_shard_scan_begin / _wait: per-query lists before packing, two sets (two batches may be in flight) and their tickets
   struct ShardSet {
-    uint64_t *d_lists = nullptr;
-    int32_t *d_counts = nullptr;  // [q_cap][2] + the packed total (int64) behind them
+    bbq::DevBuf<uint64_t> d_lists;
+    bbq::DevBuf<int32_t> d_counts;  // [q_cap][2] + the packed total (int64) behind them
     int64_t q_cap = 0, list_cap = 0;
-    hipEvent_t done = nullptr;    // recorded behind the packing of the batch
-    int64_t *h_total = nullptr;   // pinned
+    bbq::Event done;                // recorded behind the packing of the batch
+    bbq::PinnedBuf<int64_t> h_total;
     int64_t packed_cap = 0;
   } shard_set[2];
   int64_t shard_begun = 0, shard_waited = 0;  // batches begun / waited for: ticket t uses set t & 1
@@ -228,8 +229,23 @@ int attach_index(bbq_index *ix, DeviceCtx *ctx, int device, int32_t dim, int32_t
 // The view a launch gets: the stored view + which chunks it loads cache-resident.  Context mutex held by the caller.
 IndexView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin = 0, int64_t n_chunks = -1);
 #pragma GCC visibility pop
-// frees what the index owns; the device context (streams, workspace) stays.  Call with the context mutex held.
+// retires what the device still runs for the index and deletes it (its members release their memory); the device context (streams,
+// workspace) stays.  Call with the context mutex held.
 void destroy_unlocked(bbq_index *ix);
+// the view of a storage whose buffers are in place: its rows + the geometry of the index (layout, tile_stride, has_x1 decided)
+inline void set_storage_view(const bbq_index *ix, Storage &st, int64_t n_rows, int64_t row_id_base) {
+  st.row_id_base = row_id_base;
+  st.view.n_rows = n_rows;
+  st.view.w16 = ix->w16;
+  st.view.tile_stride = ix->tile_stride;
+  st.view.has_x1 = ix->has_x1;
+  st.view.dim = ix->dim;
+  st.view.layout = ix->layout;
+  st.view.store_bits = ix->store_bits;
+  st.view.tiles = st.d_tiles;
+  st.view.exact = st.d_exact;
+  st.view.add_range = add_range_of(st.d_exact, (n_rows + kTileRows - 1) / kTileRows);
+}
 // rows already in device memory (codes in the caller's shape: packed bits, or one byte per dimension for a multi-bit index;
 // corrections [n][4]) -> tile records of `st`, deciding the index's layout on the way.  Context mutex held by the caller.
 int storage_from_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const double *d_corr, int64_t n_rows, int64_t row_id_base,

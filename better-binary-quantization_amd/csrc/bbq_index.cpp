@@ -17,33 +17,29 @@ int get_ctx(int device, DeviceCtx **out) {
   std::lock_guard<std::mutex> lk(g_ctx_mu);
   if (device < 0 || device >= 64) return fail(BBQ_ERR_INVALID_ARG, "device %d out of range", device);
   if (!g_ctx[device]) {
-    DeviceCtx *c = new DeviceCtx();
+    std::unique_ptr<DeviceCtx> c(new DeviceCtx());  // a context that cannot be completed is taken down again
     for (int i = 0; i < kMaxSlots; ++i) {
       HIPCHK(hipStreamCreateWithFlags(&c->slots[i].stream, hipStreamNonBlocking));
-      HIPCHK(hipEventCreate(&c->slots[i].ev0));
-      HIPCHK(hipEventCreate(&c->slots[i].ev1));
-      HIPCHK(hipEventCreateWithFlags(&c->slots[i].ev_done, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->slots[i].ev_big, hipEventDisableTiming));
+      HIPCHK(c->slots[i].ev0.create());
+      HIPCHK(c->slots[i].ev1.create());
+      HIPCHK(c->slots[i].ev_done.create(hipEventDisableTiming));
+      HIPCHK(c->slots[i].ev_big.create(hipEventDisableTiming));
     }
     HIPCHK(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc((void **)&c->d_aux_flags, 4));
+    HIPCHK(c->d_aux_flags.alloc(1));
     HIPCHK(hipMemset(c->d_aux_flags, 0, 4));
-    HIPCHK(hipHostMalloc((void **)&c->h_lat, (size_t)(kLatAnswerOffset + kFinalSelectMax + 8) * 8, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(c->h_lat, 0, (size_t)(kLatAnswerOffset + kFinalSelectMax + 8) * 8);
+    HIPCHK(c->h_lat.alloc((size_t)(kLatAnswerOffset + kFinalSelectMax + 8)));
+    memset(c->h_lat, 0, c->h_lat.size() * 8);
     HIPCHK(hipHostGetDevicePointer((void **)&c->d_lat, c->h_lat, 0));
-    HIPCHK(hipMalloc((void **)&c->d_pre_keys, (size_t)kLatPreKeys * 4));
-    g_ctx[device] = c;
+    HIPCHK(c->d_pre_keys.alloc((size_t)kLatPreKeys));
+    g_ctx[device] = c.release();  // published: from here on it is never destroyed (no HIP call may run at process exit)
   }
   *out = g_ctx[device];
   return BBQ_OK;
 }
 
 int ensure_aux_qbuf(DeviceCtx *c, int64_t bytes) {
-  if (c->aux_qbuf_bytes >= bytes) return BBQ_OK;
-  if (c->d_aux_qbuf) HIPCHK(hipFree(c->d_aux_qbuf));
-  c->d_aux_qbuf = nullptr;
-  HIPCHK(hipMalloc((void **)&c->d_aux_qbuf, (size_t)bytes));
-  c->aux_qbuf_bytes = bytes;
+  HIPCHK(c->d_aux_qbuf.reserve((size_t)bytes));
   return BBQ_OK;
 }
 
@@ -92,15 +88,16 @@ int attach_index(bbq_index *ix, DeviceCtx *ctx, int device, int32_t dim, int32_t
 static int make_storage(bbq_index *ix, Storage &st, const uint8_t *codes, const double *corr, int64_t n_rows, int64_t row_id_base,
                         bool check_x1) {
   const int64_t pb = ix->store_bits > 1 ? ix->dim : ix->pb;  // bytes per row as the caller hands them over (multi-bit: one byte per dimension)
-  DevMem m_codes, m_corr;
+  DevBuf<uint8_t> d_codes;
+  DevBuf<double> d_corr;
   hipStream_t s = ix->ctx->aux_stream;
   if (n_rows > 0) {
-    HIPCHK(m_codes.alloc((size_t)(n_rows * pb)));
-    HIPCHK(m_corr.alloc((size_t)n_rows * 32));
-    HIPCHK(hipMemcpyAsync(m_codes.p, codes, (size_t)(n_rows * pb), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m_corr.p, corr, (size_t)n_rows * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(d_codes.alloc((size_t)(n_rows * pb)));
+    HIPCHK(d_corr.alloc((size_t)n_rows * 4));
+    HIPCHK(hipMemcpyAsync(d_codes, codes, (size_t)(n_rows * pb), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_corr, corr, (size_t)n_rows * 32, hipMemcpyHostToDevice, s));
   }
-  return storage_from_device_rows(ix, st, m_codes.as<uint8_t>(), m_corr.as<double>(), n_rows, row_id_base, check_x1);  // synchronises before the scratch rows go
+  return storage_from_device_rows(ix, st, d_codes, d_corr, n_rows, row_id_base, check_x1);  // synchronises before the scratch rows go
 }
 
 // rows already in device memory (codes in the caller's shape, corrections [n][4]) -> tile records of `st`; decides the layout of
@@ -110,14 +107,13 @@ int storage_from_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes,
   const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
   const bool multibit = ix->store_bits > 1;
   const int64_t pb = multibit ? ix->dim : ix->pb;
-  DevMem m_mis;
+  DevBuf<uint32_t> d_mis;
   hipStream_t s = ix->ctx->aux_stream;
   if (check_x1) {
     // quantizedComponentSum of a 1-bit row is its popcount (src/optimizedScalarQuantizer.ts:204-209); if that
     // holds for every row the 8 bytes need not be stored or read.  Decided once per index, over all storages.
     uint32_t mis = 0;
-    HIPCHK(m_mis.alloc(4));
-    uint32_t *d_mis = m_mis.as<uint32_t>();
+    HIPCHK(d_mis.alloc(1));
     HIPCHK(hipMemsetAsync(d_mis, 0, 4, s));
     if (multibit) HIPCHK(launch_check_x1_multibit(d_codes, d_corr, n_rows, ix->dim, d_mis, s));
     else HIPCHK(launch_check_x1(d_codes, d_corr, n_rows, (int32_t)pb, d_mis, s));
@@ -129,24 +125,16 @@ int storage_from_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes,
   ix->layout = (ix->want_compact && !ix->has_x1) ? kLayoutCompact : kLayoutInline;
   ix->tile_stride = tile_stride_of(ix->w16, ix->layout, ix->has_x1);
   ix->bytes_per_row = ix->tile_stride / kTileRows;
-  st.row_id_base = row_id_base;
-  st.view.n_rows = n_rows;
-  st.view.w16 = ix->w16;
-  st.view.tile_stride = ix->tile_stride;
-  st.view.has_x1 = ix->has_x1;
-  st.view.dim = ix->dim;
-  st.view.layout = ix->layout;
-  st.view.store_bits = ix->store_bits;
   if (n_tiles > 0) {
-    HIPCHK(hipMalloc((void **)&st.d_tiles, (size_t)(n_tiles * ix->tile_stride)));
-    if (ix->layout == kLayoutCompact) HIPCHK(hipMalloc((void **)&st.d_exact, (size_t)compact_side_bytes(n_tiles)));
+    HIPCHK(st.d_tiles.alloc((size_t)(n_tiles * ix->tile_stride)));
+    if (ix->layout == kLayoutCompact) HIPCHK(st.d_exact.alloc((size_t)compact_side_bytes(n_tiles) / 8));
     if (multibit) {
       uint32_t bad = 0;
-      if (!m_mis.p) HIPCHK(m_mis.alloc(4));
-      HIPCHK(hipMemsetAsync(m_mis.p, 0, 4, s));
+      HIPCHK(d_mis.reserve(1));
+      HIPCHK(hipMemsetAsync(d_mis, 0, 4, s));
       HIPCHK(launch_retile_multibit(d_codes, d_corr, n_rows, ix->dim, ix->store_bits, ix->index_bits, st.d_tiles, ix->w16, ix->tile_stride, ix->has_x1, ix->layout,
-                                    st.d_exact, m_mis.as<uint32_t>(), s));
-      HIPCHK(hipMemcpyAsync(&bad, m_mis.p, 4, hipMemcpyDeviceToHost, s));
+                                    st.d_exact, d_mis, s));
+      HIPCHK(hipMemcpyAsync(&bad, d_mis, 4, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       if (bad) return fail(BBQ_ERR_INVALID_ARG, "indexBits=%d: a quantized value is not below %d", ix->index_bits, 1 << ix->index_bits);
     } else {
@@ -155,9 +143,7 @@ int storage_from_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes,
     if (ix->layout == kLayoutCompact) HIPCHK(launch_tile_add_range(st.d_exact, n_rows, const_cast<float *>(add_range_of(st.d_exact, n_tiles)), s));
     HIPCHK(hipStreamSynchronize(s));
   }
-  st.view.exact = st.d_exact;
-  st.view.add_range = add_range_of(st.d_exact, n_tiles);
-  st.view.tiles = st.d_tiles;
+  set_storage_view(ix, st, n_rows, row_id_base);
   HIPCHK(hipStreamSynchronize(s));  // the scratch rows are released on return
   return BBQ_OK;
 }
@@ -216,25 +202,17 @@ IndexView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin, in
   return v;
 }
 
-// frees what the index owns; the device context (streams, workspace) stays
+// retires what the device still runs for the index, then deletes it: its storages, dense scores and shard sets go with it.  The
+// device context (streams, workspace) stays
 void destroy_unlocked(bbq_index *ix) {
   if (!ix) return;
   (void)hipSetDevice(ix->device);
-  if (ix->pilot.d_tiles) (void)hipFree(ix->pilot.d_tiles);
-  if (ix->main.d_tiles) (void)hipFree(ix->main.d_tiles);
-  if (ix->pilot.d_exact) (void)hipFree(ix->pilot.d_exact);
-  if (ix->main.d_exact) (void)hipFree(ix->main.d_exact);
-  if (ix->d_dense_all) (void)hipFree(ix->d_dense_all);
   if (ix->ctx)
     for (size_t i = 0; i < ix->ctx->cache_users.size(); ++i)
       if (ix->ctx->cache_users[i].index == ix) { ix->ctx->cache_users.erase(ix->ctx->cache_users.begin() + (long)i); break; }
   if (ix->ctx) (void)settle_shard_slots(ix->ctx, ix);  // sub-batches of an asynchronous scan that was never waited for
-  for (bbq_index::ShardSet &set : ix->shard_set) {
-    if (set.done) { (void)hipEventSynchronize(set.done); (void)hipEventDestroy(set.done); }
-    if (set.h_total) (void)hipHostFree(set.h_total);
-    if (set.d_lists) (void)hipFree(set.d_lists);
-    if (set.d_counts) (void)hipFree(set.d_counts);
-  }
+  for (bbq_index::ShardSet &set : ix->shard_set)
+    if (set.done) (void)hipEventSynchronize(set.done);  // a batch whose packing was never waited for
   delete ix;
 }
 
@@ -294,10 +272,7 @@ int bbq_index_create_shard_opts(const uint8_t *codes, const double *corr, int64_
     rc = make_storage(ix.get(), ix->main, codes, corr, n_rows, row_base, true);
     if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
     if (ix->has_x1 != had) {  // main needs explicit sums but pilot was built without: rebuild the pilot
-      if (ix->pilot.d_tiles) (void)hipFree(ix->pilot.d_tiles);
-      if (ix->pilot.d_exact) (void)hipFree(ix->pilot.d_exact);
-      ix->pilot.d_tiles = nullptr;
-      ix->pilot.d_exact = nullptr;
+      ix->pilot = Storage();
       rc = make_storage(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, 0, false);
       if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
     }

@@ -79,13 +79,15 @@ class ShardWorker {
 };
 
 struct ShardBuf {  // one round's output of one shard: answers + packed lists on the device, answers landed in pinned host memory
-  uint64_t *d_packed = nullptr, *h_packed = nullptr;
-  int64_t *d_offsets = nullptr, *h_offsets = nullptr;
-  int32_t *d_flags = nullptr, *h_flags = nullptr;
-  uint64_t *d_answers = nullptr, *h_answers = nullptr;
+  DevBuf<uint64_t> d_packed, d_answers;
+  DevBuf<int64_t> d_offsets;
+  DevBuf<int32_t> d_flags;
+  PinnedBuf<uint64_t> h_packed, h_answers;  // h_packed grows on its own, with the lists a round has to fetch (shard_fetch_lists)
+  PinnedBuf<int64_t> h_offsets;
+  PinnedBuf<int32_t> h_flags;
   int64_t answers_stride = 0;
-  hipEvent_t landed = nullptr;  // behind the copy of the answers
-  int64_t packed_cap = 0, h_packed_cap = 0;
+  Event landed;  // behind the copy of the answers
+  int64_t packed_cap = 0;
   int32_t q_cap = 0;
   int64_t total = 0;
   bool lists_on_host = false;
@@ -116,33 +118,20 @@ struct MultiState {
 
 namespace {
 
-void free_buf(ShardBuf &b) {
-  if (b.d_packed) (void)hipFree(b.d_packed);
-  if (b.d_offsets) (void)hipFree(b.d_offsets);
-  if (b.d_flags) (void)hipFree(b.d_flags);
-  if (b.d_answers) (void)hipFree(b.d_answers);
-  if (b.h_packed) (void)hipHostFree(b.h_packed);
-  if (b.h_offsets) (void)hipHostFree(b.h_offsets);
-  if (b.h_answers) (void)hipHostFree(b.h_answers);
-  if (b.h_flags) (void)hipHostFree(b.h_flags);
-  if (b.landed) (void)hipEventDestroy(b.landed);
-  b = ShardBuf();
-}
-
 int ensure_buf(MultiShard &sh, ShardBuf &b, int32_t nq, int64_t k) {
   const int64_t want = std::max<int64_t>(bbq_shard_list_cap(sh.ix, k), 1024) * nq;
   const int64_t stride = k + 3;
   if (b.q_cap >= nq && b.packed_cap >= want && b.answers_stride >= stride) return BBQ_OK;
   HIPCHK(hipSetDevice(sh.device));
-  free_buf(b);
-  HIPCHK(hipMalloc((void **)&b.d_packed, (size_t)want * 8));
-  HIPCHK(hipMalloc((void **)&b.d_offsets, (size_t)(nq + 1) * 8));
-  HIPCHK(hipMalloc((void **)&b.d_flags, (size_t)nq * 4));
-  HIPCHK(hipMalloc((void **)&b.d_answers, (size_t)nq * (size_t)stride * 8));
-  HIPCHK(hipHostMalloc((void **)&b.h_offsets, (size_t)(nq + 1) * 8, hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void **)&b.h_answers, (size_t)nq * (size_t)stride * 8, hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void **)&b.h_flags, (size_t)nq * 4, hipHostMallocDefault));
-  HIPCHK(hipEventCreateWithFlags(&b.landed, hipEventDisableTiming));
+  b = ShardBuf();  // everything of the smaller shape goes, the fetched lists' host buffer included
+  HIPCHK(b.d_packed.alloc((size_t)want));
+  HIPCHK(b.d_offsets.alloc((size_t)nq + 1));
+  HIPCHK(b.d_flags.alloc((size_t)nq));
+  HIPCHK(b.d_answers.alloc((size_t)nq * (size_t)stride));
+  HIPCHK(b.h_offsets.alloc((size_t)nq + 1));
+  HIPCHK(b.h_answers.alloc((size_t)nq * (size_t)stride));
+  HIPCHK(b.h_flags.alloc((size_t)nq));
+  HIPCHK(b.landed.create(hipEventDisableTiming));
   b.packed_cap = want;
   b.q_cap = nq;
   b.answers_stride = stride;
@@ -189,12 +178,7 @@ int shard_fetch_lists(MultiShard &sh, ShardBuf &b, int32_t nq, const std::vector
   int64_t need = 0;
   for (int32_t q = 0; q < nq; ++q)
     if (all || status[(size_t)q] != 0) need += b.h_offsets[q + 1] - b.h_offsets[q];
-  if (b.h_packed_cap < std::max<int64_t>(need, 1)) {
-    if (b.h_packed) HIPCHK(hipHostFree(b.h_packed));
-    b.h_packed = nullptr;
-    b.h_packed_cap = std::max<int64_t>(need, 1024) * 5 / 4;
-    HIPCHK(hipHostMalloc((void **)&b.h_packed, (size_t)b.h_packed_cap * 8, hipHostMallocDefault));
-  }
+  if ((int64_t)b.h_packed.size() < std::max<int64_t>(need, 1)) HIPCHK(b.h_packed.alloc((size_t)(std::max<int64_t>(need, 1024) * 5 / 4)));
   // h_list_at[q] = where query q's entries sit in h_packed (-1: not fetched)
   b.h_list_at.assign((size_t)nq, -1);
   int64_t at = 0;
@@ -235,8 +219,8 @@ void multi_destroy(bbq_index *ix) {
   for (MultiShard &sh : ms->shards) {
     sh.worker.reset();  // joins the thread
     (void)hipSetDevice(sh.device);
-    free_buf(sh.buf[0]);
-    free_buf(sh.buf[1]);
+    sh.buf[0] = ShardBuf();
+    sh.buf[1] = ShardBuf();
     if (sh.ix) bbq_index_destroy(sh.ix);
   }
   delete ms;

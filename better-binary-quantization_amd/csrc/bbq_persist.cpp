@@ -238,7 +238,7 @@ int bbq_index_save(bbq_index *ix, const char *prefix, const float *centroid, int
     if (!fc.f) return fail(BBQ_ERR_INVALID_ARG, "cannot create %s", dpath.c_str());
     const size_t piece = 64u << 20;  // multiple of 8: the checksum words never straddle pieces
     std::vector<uint8_t> buf(piece);
-    const uint8_t *src[4] = {ix->main.d_tiles, (const uint8_t *)ix->main.d_exact, ix->pilot.d_tiles, (const uint8_t *)ix->pilot.d_exact};
+    const uint8_t *src[4] = {ix->main.d_tiles, (const uint8_t *)ix->main.d_exact.get(), ix->pilot.d_tiles, (const uint8_t *)ix->pilot.d_exact.get()};
     const int64_t len[4] = {h.tilesBytes, h.exactBytes, px.pilotTilesBytes, px.pilotExactBytes};
     for (int part = 0; part < 4; ++part) {
       for (int64_t o = 0; o < len[part]; o += (int64_t)piece) {
@@ -374,17 +374,17 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
     return code;
   };
   Storage &st = ix->main, &pt = ix->pilot;
-  if (h.tilesBytes > 0 && hipMalloc((void **)&st.d_tiles, (size_t)h.tilesBytes) != hipSuccess)
+  if (h.tilesBytes > 0 && st.d_tiles.alloc((size_t)h.tilesBytes) != hipSuccess)
     return bail(fail(BBQ_ERR_OOM, "bbq_index_load: %lld bytes of tiles", (long long)h.tilesBytes));
-  if (h.exactBytes > 0 && hipMalloc((void **)&st.d_exact, (size_t)h.exactBytes) != hipSuccess)
+  if (h.exactBytes > 0 && st.d_exact.alloc((size_t)h.exactBytes / 8) != hipSuccess)  // (whole doubles: read_meta has checked the size)
     return bail(fail(BBQ_ERR_OOM, "bbq_index_load: %lld bytes of exact corrections", (long long)h.exactBytes));
-  if (px.pilotTilesBytes > 0 && hipMalloc((void **)&pt.d_tiles, (size_t)px.pilotTilesBytes) != hipSuccess)
+  if (px.pilotTilesBytes > 0 && pt.d_tiles.alloc((size_t)px.pilotTilesBytes) != hipSuccess)
     return bail(fail(BBQ_ERR_OOM, "bbq_index_load: %lld bytes of pilot tiles", (long long)px.pilotTilesBytes));
-  if (px.pilotExactBytes > 0 && hipMalloc((void **)&pt.d_exact, (size_t)px.pilotExactBytes) != hipSuccess)
+  if (px.pilotExactBytes > 0 && pt.d_exact.alloc((size_t)px.pilotExactBytes / 8) != hipSuccess)
     return bail(fail(BBQ_ERR_OOM, "bbq_index_load: %lld bytes of pilot corrections", (long long)px.pilotExactBytes));
   const size_t piece = 64u << 20;
   std::vector<uint8_t> buf(piece);
-  uint8_t *dst[4] = {st.d_tiles, (uint8_t *)st.d_exact, pt.d_tiles, (uint8_t *)pt.d_exact};
+  uint8_t *dst[4] = {st.d_tiles, (uint8_t *)st.d_exact.get(), pt.d_tiles, (uint8_t *)pt.d_exact.get()};
   const int64_t len[4] = {h.tilesBytes, h.exactBytes, px.pilotTilesBytes, px.pilotExactBytes};
   uint64_t dsum = kFnvSeed;
   for (int part = 0; part < 4; ++part) {
@@ -397,21 +397,8 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
     }
   }
   if (dsum != want_sum) return bail(fail(BBQ_ERR_INVALID_ARG, "%s: vector data checksum mismatch", dpath.c_str()));
-  auto fill_view = [&](Storage &sto, int64_t rows, int64_t row_id_base) {
-    sto.row_id_base = row_id_base;
-    sto.view.n_rows = rows;
-    sto.view.w16 = h.w16;
-    sto.view.tile_stride = h.tileStride;
-    sto.view.has_x1 = h.hasX1;
-    sto.view.dim = h.dimensions;
-    sto.view.layout = h.layout;
-    sto.view.store_bits = ix->store_bits;
-    sto.view.tiles = sto.d_tiles;
-    sto.view.exact = sto.d_exact;
-    sto.view.add_range = add_range_of(sto.d_exact, (rows + kTileRows - 1) / kTileRows);
-  };
-  fill_view(st, h.vectorCount, h.rowBase);
-  if (ix->has_pilot) fill_view(pt, px.pilotRows, 0);
+  set_storage_view(ix.get(), st, h.vectorCount, h.rowBase);
+  if (ix->has_pilot) set_storage_view(ix.get(), pt, px.pilotRows, 0);
   if (centroid_out) memcpy(centroid_out, cen.data(), cen.size() * 4);
   *out = ix.release();
   return BBQ_OK;

@@ -13,31 +13,22 @@ using namespace bbq;
 struct bbq_vectors {
   int device = 0;
   DeviceCtx *ctx = nullptr;
-  float *d = nullptr;
+  DevBuf<float> d;
   int64_t n = 0;
   int32_t dim = 0;
   // grow-only staging for bbq_rerank_scores
-  float *d_q = nullptr;
-  int64_t q_cap = 0;
-  int64_t *d_off = nullptr;
-  int64_t off_cap = 0;
-  int32_t *d_rows = nullptr;
-  double *d_out = nullptr;
-  int64_t cand_cap = 0;
+  DevBuf<float> d_q;
+  DevBuf<int64_t> d_off;
+  DevBuf<int32_t> d_rows;
+  DevBuf<double> d_out;
 };
 
 namespace {
 
+// staging that a larger call outgrows is replaced with half as much again
 template <class T>
-int grow(T **p, int64_t *cap, int64_t need) {
-  if (need <= *cap) return BBQ_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const int64_t c = need + need / 2 + 64;
-  HIPCHK(hipMalloc((void **)p, (size_t)c * sizeof(T)));
-  *cap = c;
-  return BBQ_OK;
+hipError_t grow_staging(DevBuf<T> &b, int64_t need) {
+  return (int64_t)b.size() >= need ? hipSuccess : b.alloc((size_t)(need + need / 2 + 64));
 }
 
 struct Ranked { double score; int32_t pos; };
@@ -73,28 +64,21 @@ int bbq_vectors_create(const float *vectors, int64_t n, int32_t dim, int32_t dev
   int rc = open_device(device, &ctx);
   if (rc != BBQ_OK) return rc;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  bbq_vectors *v = new bbq_vectors();
+  std::unique_ptr<bbq_vectors> v(new bbq_vectors());
   v->device = device;
   v->ctx = ctx;
   v->n = n;
   v->dim = dim;
   if (n > 0) {
-    hipError_t e = hipMalloc((void **)&v->d, (size_t)n * dim * sizeof(float));
-    if (e != hipSuccess) {
-      delete v;
-      return fail(BBQ_ERR_OOM, "bbq_vectors_create: %lld x %d fp32: %s", (long long)n, dim, hipGetErrorString(e));
-    }
+    hipError_t e = v->d.alloc((size_t)n * dim);
+    if (e != hipSuccess) return fail(BBQ_ERR_OOM, "bbq_vectors_create: %lld x %d fp32: %s", (long long)n, dim, hipGetErrorString(e));
     const int64_t total = n * dim, piece = 64LL << 20;  // 256 MB pieces keep the runtime's pinned staging bounded
     for (int64_t o = 0; o < total; o += piece) {
       e = hipMemcpy(v->d + o, vectors + o, (size_t)std::min(piece, total - o) * sizeof(float), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        (void)hipFree(v->d);
-        delete v;
-        return fail(BBQ_ERR_HIP, "bbq_vectors_create: copy: %s", hipGetErrorString(e));
-      }
+      if (e != hipSuccess) return fail(BBQ_ERR_HIP, "bbq_vectors_create: copy: %s", hipGetErrorString(e));
     }
   }
-  *out = v;
+  *out = v.release();
   return BBQ_OK;
 }
 
@@ -102,11 +86,6 @@ void bbq_vectors_destroy(bbq_vectors *v) {
   if (!v) return;
   std::lock_guard<std::mutex> lk(v->ctx->mu);
   (void)hipSetDevice(v->device);
-  if (v->d) (void)hipFree(v->d);
-  if (v->d_q) (void)hipFree(v->d_q);
-  if (v->d_off) (void)hipFree(v->d_off);
-  if (v->d_rows) (void)hipFree(v->d_rows);
-  if (v->d_out) (void)hipFree(v->d_out);
   delete v;
 }
 
@@ -135,15 +114,10 @@ int bbq_rerank_scores(bbq_vectors *v, int32_t n_queries, const float *queries, c
     if (rows[i] < 0 || rows[i] >= v->n) return fail(BBQ_ERR_INVALID_ARG, "基础向量%d不存在", rows[i]);
   std::lock_guard<std::mutex> lk(v->ctx->mu);
   HIPCHK(hipSetDevice(v->device));
-  int rc = grow(&v->d_q, &v->q_cap, (int64_t)n_queries * v->dim);
-  if (rc == BBQ_OK) rc = grow(&v->d_off, &v->off_cap, (int64_t)n_queries + 1);
-  if (rc == BBQ_OK && total > v->cand_cap) {
-    int64_t c1 = v->cand_cap, c2 = v->cand_cap;
-    rc = grow(&v->d_rows, &c1, total);
-    if (rc == BBQ_OK) rc = grow(&v->d_out, &c2, total);
-    v->cand_cap = rc == BBQ_OK ? std::min(c1, c2) : 0;
-  }
-  if (rc != BBQ_OK) return rc;
+  HIPCHK(grow_staging(v->d_q, (int64_t)n_queries * v->dim));
+  HIPCHK(grow_staging(v->d_off, (int64_t)n_queries + 1));
+  HIPCHK(grow_staging(v->d_rows, total));
+  HIPCHK(grow_staging(v->d_out, total));
   hipStream_t st = v->ctx->aux_stream;
   HIPCHK(hipMemcpyAsync(v->d_q, queries, (size_t)n_queries * v->dim * sizeof(float), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(v->d_off, offsets, (size_t)(n_queries + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));

@@ -56,20 +56,17 @@ int bbq_shard_scan_begin(bbq_index *ix, int32_t n_queries, const uint8_t *qquant
   if (answers) { c.k = k + 1; build_plan(ix, k + 1, k); }
   else build_plan(ix, k);
   bbq_index::ShardSet &set = ix->shard_set[ix->shard_begun & 1];
-  if (!set.done) {
-    HIPCHK(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
-    HIPCHK(hipHostMalloc((void **)&set.h_total, 8, hipHostMallocDefault));
+  if (!set.h_total) {
+    HIPCHK(set.done.create(hipEventDisableTiming));
+    HIPCHK(set.h_total.alloc(1));
   }
   // per-query lists with room for a flood (rows stored cluster by cluster); what travels is packed, so the headroom costs
   // device memory only
   const int64_t list_cap = ix->plan.list_cap + std::min<int64_t>(ix->plan.flood_cap, 65536);
   if (set.q_cap < n_queries || set.list_cap < list_cap) {  // per-query lists the finalize kernels build (the set is idle: its last batch was waited for)
-    if (set.d_lists) HIPCHK(hipFree(set.d_lists));
-    if (set.d_counts) HIPCHK(hipFree(set.d_counts));
-    set.d_lists = nullptr;
-    set.d_counts = nullptr;
-    HIPCHK(hipMalloc((void **)&set.d_lists, (size_t)n_queries * (size_t)list_cap * 8));
-    HIPCHK(hipMalloc((void **)&set.d_counts, (size_t)n_queries * 8 + 16));
+    set.q_cap = 0;  // until both are in place
+    HIPCHK(set.d_lists.alloc((size_t)n_queries * (size_t)list_cap));
+    HIPCHK(set.d_counts.alloc((size_t)n_queries * 2 + 4));
     set.q_cap = n_queries;
     set.list_cap = list_cap;
   }
