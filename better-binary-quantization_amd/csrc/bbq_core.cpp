@@ -1,4 +1,4 @@
-// bbq_core.cpp - device-resident index shard, segment plan, pipelined search, C ABI (see include/bbq.h).
+// bbq_core.cpp - segment plan, slot workspace, pipelined search (enqueue, collection, host replay), C ABI (see include/bbq.h).
 //
 // Search of one query = a short sequence of launches over row SEGMENTS of the index:
 //   segment 0   rows [0, s0)           dense: every f32 score is written; the finalize kernel lists all of
@@ -12,11 +12,9 @@
 // sub-batches are pipelined over NSLOT streams so the host replay of one overlaps the scan of the next.
 #include <math.h>
 #include <string.h>
-#include <condition_variable>
-#include <deque>
-#include <functional>
 #include <memory>
 #include "bbq_search.h"
+#include "bbq_workqueue.h"
 
 using namespace bbq;
 
@@ -24,42 +22,10 @@ namespace {
 
 // Host worker pool for the heap replays: persistent threads (spawning per sub-batch cost more than the replay itself
 // once sweeps are shared), fed while the device already works on the next sub-batches.
-class ReplayPool {
- public:
-  static ReplayPool &get() {
-    static ReplayPool *p = new ReplayPool();  // intentionally never destroyed: workers may outlive static destructors
-    return *p;
-  }
-  void ensure(int n) {
-    std::lock_guard<std::mutex> lk(m_);
-    while ((int)th_.size() < n) th_.emplace_back([this] { run(); });
-  }
-  void submit(std::function<void()> f) {
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      q_.push_back(std::move(f));
-    }
-    cv_.notify_one();
-  }
-
- private:
-  void run() {
-    for (;;) {
-      std::function<void()> f;
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [this] { return !q_.empty(); });
-        f = std::move(q_.front());
-        q_.pop_front();
-      }
-      f();
-    }
-  }
-  std::mutex m_;
-  std::condition_variable cv_;
-  std::deque<std::function<void()>> q_;
-  std::vector<std::thread> th_;
-};
+WorkQueue &replay_pool() {
+  static WorkQueue *p = new WorkQueue();  // intentionally never destroyed: workers may outlive static destructors
+  return *p;
+}
 
 // Raw queries of bbq_search_raw_batch being quantized on host threads, chunk by chunk, while the sub-batches in front are already
 // on the device: the quantizer (~15 us per 768-d query and core) never stands in front of a sweep except for the first chunk.
@@ -174,15 +140,13 @@ static void add_storage_segments(const bbq_index *ix, Plan &p, int storage, cons
   }
 }
 
-// k: the rank the device selects thresholds with; final_k > 0: k == final_k + 1 and the last finalize launch selects the answer
-void build_plan(bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
-  Plan &p = ix->plan;
-  const int growth = latency ? ix->opt_latency_growth : ix->opt_growth;
-  if (p.k == k && p.final_k == final_k && p.growth == growth && p.latency == latency) return;
-  p = Plan();
+// k: the rank the device selects thresholds with; final_k > 0: k == final_k + 1 and the last finalize launch selects the answer.
+// A value of its inputs and the index's options: the call that asked for it owns it.
+Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
+  Plan p;
   p.k = k;
   p.final_k = final_k;
-  p.growth = growth;
+  p.growth = latency ? ix->opt_latency_growth : ix->opt_growth;
   p.latency = latency;
   p.s0 = std::max<int64_t>(ix->opt_s0, (4 * k + kChunkRows - 1) / kChunkRows * kChunkRows);
   p.s0 = std::min<int64_t>(p.s0, 8192);
@@ -206,26 +170,26 @@ void build_plan(bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
   if (best >= 0) p.segs[best].dominant = true;
   for (Segment &sg : p.segs) sg.big = best >= 0 && sg.rows * 32 >= p.segs[best].rows && sg.rows >= 65536;
   // list capacity: everything dense + 4x the expected sparse candidates + slack
-  double sparse = 0;
   int64_t dense_rows = 0;
   for (const Segment &s : p.segs)
     if (s.emit && s.dense) dense_rows += s.rows;
-  sparse = expected_emit - (double)dense_rows;
-  if (sparse < 0) sparse = 0;
+  const double sparse = std::max(0.0, expected_emit - (double)dense_rows);
   p.list_cap = dense_rows + (int64_t)(4.0 * sparse) + 4096;
   p.list_cap = (p.list_cap + 1023) / 1024 * 1024;
   // per query; bounded so that the overflow areas of one pipeline slot stay within 512 MB however many queries a sub-batch has
   p.flood_cap = std::min<int64_t>(ix->opt_flood, (ix->main.view.n_rows + 1023) / 1024 * 1024);
   if (p.flood_cap > 0)
     p.flood_cap = std::min<int64_t>(p.flood_cap, std::max<int64_t>(16384, ((64ll << 20) / std::max(32, effective_batch(ix))) / 1024 * 1024));
+  return p;
 }
 
 // ------------------------------------------------------------------------------------------------ slots
 
 static int64_t qbuf_bytes_per_query(const bbq_index *ix) { return qbuf_bytes_per_query_w(ix->w16); }
 
-int ensure_slot(bbq_index *ix, Slot &s, int nq, bool own_lists) {
-  const Plan &p = ix->plan;
+int ensure_slot(const SearchCall &c, Slot &s, int nq, bool own_lists) {
+  const bbq_index *ix = c.ix;
+  const Plan &p = *c.plan;
   const int64_t qb = qbuf_bytes_per_query(ix);
   const int64_t hprefix = std::min<int64_t>(p.list_cap, 16384);
   const bool ok = s.q_cap >= nq && s.qbuf_bytes >= qb && s.chunks_cap >= p.max_chunks && s.slots_cap >= p.max_slots &&
@@ -302,152 +266,137 @@ FinalizeArgs slot_finalize_args(const Slot &s, uint64_t *lists, int32_t *list_co
   return f;
 }
 
-int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const ExtOut *ext) {
+// the ScanArgs of segment g for the slot's sub-batch of nq queries (the caller adds the append mode)
+static ScanArgs segment_scan_args(const Plan &p, const Slot &s, const Segment &g, const Storage &sto, const IndexView &view, int nq, int64_t qb) {
+  ScanArgs a{};
+  a.idx = view;
+  a.qplanes = reinterpret_cast<const uint4 *>(s.d_qbuf);
+  a.qparams = reinterpret_cast<const QueryParams *>(s.d_qbuf + (size_t)nq * qb);
+  a.chunk_begin = g.chunk_begin;
+  a.row_id_base = sto.row_id_base;
+  a.theta = s.d_theta;
+  a.counts = s.d_counts;
+  a.entries = s.d_entries;
+  a.flags = s.d_flags;
+  a.cap = g.cap;
+  a.n_chunks = (int32_t)g.n_chunks;
+  // the slot's area may be larger than this plan asks for (slots are shared and grow-only): the plan's size governs
+  a.ovf = p.flood_cap > 0 ? s.d_ovf : nullptr;
+  a.ovf_counts = s.d_ovf_counts;
+  a.ovf_cap = (int32_t)p.flood_cap;
+  a.dense_score32 = g.dense ? s.d_dense0 : nullptr;
+  a.dense_stride = s.dense_cap;
+  return a;
+}
+
+// ... and of the finalize launch behind that sweep (the caller adds where a last segment leaves its answer)
+static FinalizeArgs segment_finalize_args(FinalizeArgs f, const Slot &s, const Segment &g, const ScanArgs &a) {
+  f.counts = s.d_counts;
+  f.entries = s.d_entries;
+  f.dense_score32 = s.d_dense0;
+  f.dense_stride = s.dense_cap;
+  f.dense_rows = g.dense ? (int32_t)g.rows : 0;
+  f.dense_row_id_base = a.row_id_base + g.chunk_begin * kChunkRows;
+  f.n_chunks = (int32_t)g.n_chunks;
+  f.cap = g.cap;
+  f.ovf = a.ovf;
+  f.ovf_cap = a.ovf_cap;
+  f.emit = g.emit ? 1 : 0;
+  f.need_theta = g.need_theta ? 1 : 0;
+  return f;
+}
+
+int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, const ExtOut *ext) {
   bbq_index *ix = c.ix;
-  uint64_t *d_lists_ext = ext ? ext->lists : nullptr;
-  const int64_t list_cap_ext = ext ? ext->list_cap : 0;
-  int32_t *d_counts_ext = ext ? ext->counts : nullptr;
-  const Plan &p = ix->plan;
+  const Plan &p = *c.plan;
   const int64_t qb = query_data_bytes(ix, c.planes);
-  uint8_t *hp = s.h_qbuf;
   QueryParams *hq = reinterpret_cast<QueryParams *>(s.h_qbuf + (size_t)nq * qb);
   for (int i = 0; i < nq; ++i)
-    fill_query(ix, hp + (size_t)i * qb, hq + i, c.qquant + (size_t)(q_first + i) * ix->dim, c.qcorr + (size_t)(q_first + i) * 4,
+    fill_query(ix, s.h_qbuf + (size_t)i * qb, hq + i, c.qquant + (size_t)(q_first + i) * ix->dim, c.qcorr + (size_t)(q_first + i) * 4,
                c.planes, c.one_bit, c.sim);
   size_t bytes = (size_t)nq * qb + (size_t)nq * sizeof(QueryParams);
   // the matrix-core shared sweep appends its candidates to the lists, so it runs only where they are this slot's own
-  bool use_mfma = !d_lists_ext && ix->opt_share == 32 && c.maxq <= 127 && ix->store_bits == 1;
+  bool use_mfma = !ext && c.share == 32 && c.maxq <= 127 && ix->store_bits == 1;
   for (int i = 0; i < nq && use_mfma; ++i) use_mfma = mfma_query_ok(hq[i]);
-  const bool mfma_fp = c.maxq <= 15;  // queryBits <= 4: rows as FP4, queries as FP6 - 64 dimensions per MFMA in the time the int8 form takes for 32
-  const int mfma_scale8 = c.maxq <= 3 ? 8 : c.maxq <= 7 ? 4 : 2;   // products of scale8 / 8 * q: the accumulator's quarter-unit grain is 1, 1/2 or 1/4 of a qcDist unit
-  size_t off_qbytes = 0, off_qmax = 0;
-  if (use_mfma) {  // second copy of the queries as MFMA operands in fragment order + per-group maxima for the rows' magnitude budget
-    const int groups = (nq + 31) / 32;
-    off_qbytes = (bytes + 15) / 16 * 16;
-    const size_t qbytes_len = (size_t)groups * (size_t)mfma_query_bytes_per_group(ix->w16, mfma_fp);
-    off_qmax = off_qbytes + qbytes_len;
-    bytes = off_qmax + (size_t)groups * 16;
-    memset(s.h_qbuf + off_qbytes, 0, qbytes_len);
-    float *qm = reinterpret_cast<float *>(s.h_qbuf + off_qmax);
-    for (int gidx = 0; gidx < groups; ++gidx) qm[4 * gidx] = qm[4 * gidx + 1] = qm[4 * gidx + 2] = qm[4 * gidx + 3] = 0.f;
-    for (int i = 0; i < nq; ++i) {
-      if (mfma_fp) fill_query_mfma_fp(ix, s.h_qbuf + off_qbytes, i, c.qquant + (size_t)(q_first + i) * ix->dim, mfma_scale8);
-      else fill_query_mfma(ix, s.h_qbuf + off_qbytes, i, c.qquant + (size_t)(q_first + i) * ix->dim);
-      float *m = qm + 4 * (i / 32);
-      // upper bounds (rounded up) of the group's |ay / ly|, |y1|, 1 / (cs * ly) and of the sum of a query's values (the largest
-      // qcDist there can be, whatever y1 the caller passed)
-      double qsum = 0;
-      const uint8_t *qv = c.qquant + (size_t)(q_first + i) * ix->dim;
-      for (int d = 0; d < ix->dim; ++d) qsum += qv[d];
-      m[0] = std::max(m[0], (float)(fabs(hq[i].ay / hq[i].ly) * 1.000001));
-      m[1] = std::max(m[1], (float)(fabs(hq[i].y1) * 1.000001));
-      m[2] = std::max(m[2], (float)(1.0 / ((c.sim == 0 ? 2.0 : 1.0) * hq[i].ly) * 1.000001));
-      m[3] = std::max(m[3], (float)(qsum * 1.000001));
-    }
-  }
+  const MfmaStage ms = use_mfma ? stage_queries_mfma(c, s.h_qbuf, hq, q_first, nq, bytes) : MfmaStage{};
+  if (use_mfma) bytes = ms.bytes;
   hipStream_t st = s.stream;
   HIPCHK(hipMemcpyAsync(s.d_block, s.h_block, (size_t)s.ctrl_bytes + bytes, hipMemcpyHostToDevice, st));  // control words := 0, queries
   s.ctrl_clean = false;
-  uint64_t *d_lists = d_lists_ext ? d_lists_ext : s.d_lists;
-  const int64_t list_cap = d_lists_ext ? list_cap_ext : s.list_cap;
-  int32_t *d_list_counts = d_counts_ext ? d_counts_ext : s.d_list_counts;
-  if (d_counts_ext) HIPCHK(hipMemsetAsync(d_counts_ext, 0, (size_t)nq * 8, st));
+  uint64_t *d_lists = ext ? ext->lists : s.d_lists.get();
+  const int64_t list_cap = ext ? ext->list_cap : s.list_cap;
+  int32_t *d_list_counts = ext ? ext->counts : s.d_list_counts;
+  if (ext) HIPCHK(hipMemsetAsync(ext->counts, 0, (size_t)nq * 8, st));
   // a shard without rows (and without a pilot replica) launches nothing that would write its answer blocks: all-zero blocks say
   // "nothing listed, no cut, no flags", which is what bbq_merge_answers expects of such a shard
   if (ext && ext->answers && p.segs.empty())
-    HIPCHK(hipMemsetAsync(ext->answers, 0, ((size_t)(nq - 1) * (size_t)ext->answers_stride + (size_t)c.k + 2) * 8, st));
+    HIPCHK(hipMemsetAsync(ext->answers, 0, ((size_t)(nq - 1) * (size_t)ext->answers_stride + (size_t)c.k_dev + 2) * 8, st));
 
-  const bool use_final = !d_lists_ext && p.final_k > 0 && !p.segs.empty();
+  const bool use_final = !ext && p.final_k > 0 && !p.segs.empty();
   // few queries: the sparse launches append their candidates to the list themselves (ScanArgs::append_lists)
-  const bool append = use_final && p.latency && !ix->has_pilot && ix->opt_share == 1;
-  s.appended = append || use_mfma;
-  s.timed = false;
-  ix->sweep_resident_acc = 0;
+  const bool append = use_final && p.latency && !ix->has_pilot && c.share == 1;
+  Slot::InFlight &fl = s.fl;
+  fl.appended = append || use_mfma;
+  fl.timed = false;
+  int64_t resident = 0;  // of one query's sweep over all segments
   for (const Segment &g : p.segs) {
     const Storage &sto = g.storage == 0 ? ix->pilot : ix->main;
-    ScanArgs a{};
-    a.idx = launch_view(ix, sto, g.chunk_begin, g.n_chunks);
-    ix->stats.resident_bytes = ix->sweep_resident_acc;  // of one query's sweep over all segments (complete after the last one)
-    a.qplanes = reinterpret_cast<const uint4 *>(s.d_qbuf);
-    a.qparams = reinterpret_cast<const QueryParams *>(s.d_qbuf + (size_t)nq * qb);
-    a.chunk_begin = g.chunk_begin;
-    a.row_id_base = sto.row_id_base;
-    a.theta = s.d_theta;
-    a.counts = s.d_counts;
-    a.entries = s.d_entries;
-    a.flags = s.d_flags;
-    a.cap = g.cap;
-    a.n_chunks = (int32_t)g.n_chunks;
-    // the slot's area may be larger than this plan asks for (slots are shared and grow-only): the plan's size governs
-    a.ovf = p.flood_cap > 0 ? s.d_ovf : nullptr;
-    a.ovf_counts = s.d_ovf_counts;
-    a.ovf_cap = (int32_t)p.flood_cap;
-    a.dense_score32 = g.dense ? s.d_dense0 : nullptr;
-    a.dense_stride = s.dense_cap;
-    const bool append_here = !g.dense && ((append && (ix->opt_append_last || &g != &p.segs.back())) || use_mfma);
+    const bool last = &g == &p.segs.back();
+    const LaunchView lv = launch_view(ix, sto, g.chunk_begin, g.n_chunks);
+    resident += lv.resident_bytes;
+    ScanArgs a = segment_scan_args(p, s, g, sto, lv.view, nq, qb);
+    const bool append_here = !g.dense && ((append && (ix->opt_append_last || !last)) || use_mfma);
     if (append_here) {
       a.append_lists = d_lists;
       a.append_base = d_list_counts;
       a.append_counts = s.d_append_counts;
       a.append_cap = list_cap;
     }
+    // how this segment is swept, decided once: on the matrix cores, shared between c.share queries, or (neither) every query on its own
+    const bool on_mfma = use_mfma && !g.dense && mfma_sweep_supported(a);
+    const bool shared = !on_mfma && !g.dense && c.share > 1 && shared_sweep_supported(a, c.share);
     const int my_slot = (int)(&s - ix->slots);
     // one big sweep at a time on the device - for the memory-bound sweeps, which share the Infinity Cache's budget.  The chains of the
     // matrix-core sweep are issue-bound and run side by side: serialised, the finalize launch and the launch gaps between a chain's two
     // large sweeps were idle time (128 -> 138 K q/s at 10 M x 768)
-    const bool mfma_here = use_mfma && !g.dense && mfma_sweep_supported(a);
-    if (g.big && !mfma_here && ix->ctx->last_big_slot >= 0 && ix->ctx->last_big_slot != my_slot)
+    const bool chained = g.big && !on_mfma;
+    if (chained && ix->ctx->last_big_slot >= 0 && ix->ctx->last_big_slot != my_slot)
       HIPCHK(hipStreamWaitEvent(st, ix->slots[ix->ctx->last_big_slot].ev_big, 0));
     if (g.dominant) HIPCHK(hipEventRecord(s.ev0, st));
-    if (mfma_here)
-      HIPCHK(launch_scan_mfma(a, s.d_qbuf + off_qbytes, reinterpret_cast<const float *>(s.d_qbuf + off_qmax), mfma_fp ? mfma_scale8 / 8.0f : 0.0f, nq, (int)g.n_chunks, st));
-    else if (!g.dense && ix->opt_share > 1 && shared_sweep_supported(a, ix->opt_share))
-      HIPCHK(launch_scan_shared(a, c.planes, ix->opt_share, nq, (int)g.n_chunks, st));
+    if (on_mfma)
+      HIPCHK(launch_scan_mfma(a, s.d_qbuf + ms.off_qbytes, reinterpret_cast<const float *>(s.d_qbuf + ms.off_qmax), ms.fp ? ms.scale8 / 8.0f : 0.0f, nq, (int)g.n_chunks, st));
+    else if (shared)
+      HIPCHK(launch_scan_shared(a, c.planes, c.share, nq, (int)g.n_chunks, st));
     else
       HIPCHK(launch_scan(a, c.planes, g.dense, nq, (int)g.n_chunks, st));
-    if (g.big && !mfma_here) {
+    if (chained) {
       HIPCHK(hipEventRecord(s.ev_big, st));
       ix->ctx->last_big_slot = my_slot;
     }
     if (g.dominant) {
       HIPCHK(hipEventRecord(s.ev1, st));
-      s.timed = true;
-      s.timed_rows = g.rows * nq;
+      fl.timed = true;
+      fl.timed_rows = g.rows * nq;
       // a shared sweep reads each row once for `share` queries
-      const int share = mfma_here ? mfma_queries_per_tile_load(a, nq, mfma_fp) : (!g.dense && ix->opt_share > 1 && shared_sweep_supported(a, ix->opt_share)) ? ix->opt_share : 1;
+      const int share = on_mfma ? mfma_queries_per_tile_load(a, nq, ms.fp) : shared ? c.share : 1;
       // the matrix-core sweep reads the codes and the EXACT corrections (compact layout: 24 of the side array's 32 B per row instead of
       // the tile's 4-byte word), once per 32 queries
-      const int64_t row_bytes = !mfma_here ? (int64_t)ix->bytes_per_row
-                                           : sto.view.layout == kLayoutCompact ? (int64_t)sto.view.w16 * 16 + 24 : (int64_t)sto.view.tile_stride / kTileRows;
-      s.timed_bytes = g.rows * ((nq + share - 1) / share) * row_bytes;
+      const int64_t row_bytes = !on_mfma ? (int64_t)ix->bytes_per_row
+                                : sto.view.layout == kLayoutCompact ? (int64_t)sto.view.w16 * 16 + 24 : (int64_t)sto.view.tile_stride / kTileRows;
+      fl.timed_bytes = g.rows * ((nq + share - 1) / share) * row_bytes;
     }
-    FinalizeArgs f = slot_finalize_args(s, d_lists, d_list_counts, list_cap, append_here, c.k);
-    f.counts = s.d_counts;
-    f.entries = s.d_entries;
-    f.dense_score32 = s.d_dense0;
-    f.dense_stride = s.dense_cap;
-    f.dense_rows = g.dense ? (int32_t)g.rows : 0;
-    f.dense_row_id_base = sto.row_id_base + g.chunk_begin * kChunkRows;
-    f.n_chunks = (int32_t)g.n_chunks;
-    f.cap = g.cap;
-    f.ovf = a.ovf;
-    f.ovf_cap = a.ovf_cap;
-    f.emit = g.emit ? 1 : 0;
-    f.need_theta = g.need_theta ? 1 : 0;
-    if (use_final && &g == &p.segs.back()) {
-      f.final_out = s.d_final;
-      f.final_stride = (int32_t)s.final_stride;
+    FinalizeArgs f = segment_finalize_args(slot_finalize_args(s, d_lists, d_list_counts, list_cap, append_here, c.k_dev), s, g, a);
+    if (last && p.final_k > 0 && (use_final || (ext && ext->answers))) {  // the answer: to the slot, or a shard's to its caller
+      f.final_out = use_final ? s.d_final.get() : ext->answers;
+      f.final_stride = (int32_t)(use_final ? s.final_stride : ext->answers_stride);
       f.final_k = (int32_t)p.final_k;
-    } else if (ext && ext->answers && p.final_k > 0 && &g == &p.segs.back()) {
-      f.final_out = ext->answers;
-      f.final_stride = (int32_t)ext->answers_stride;
-      f.final_k = (int32_t)p.final_k;
-      f.final_shard = 1;
+      f.final_shard = use_final ? 0 : 1;
     }
     HIPCHK(launch_finalize(f, nq, st));
   }
-  s.final_used = use_final;
-  if (!d_lists_ext) {
+  ix->stats.resident_bytes = resident;
+  fl.final_used = use_final;
+  if (!ext) {
     if (use_final) {
       // the answer itself (header + k entries per query, one copy) instead of the candidate list: the list is fetched only for a
       // query whose answer the device could not prove (ties), see begin_replay
@@ -463,196 +412,216 @@ int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const 
     }
   }
   HIPCHK(hipEventRecord(s.ev_done, st));
-  s.busy = true;
-  s.nq = nq;
-  s.q_first = q_first;
+  fl.busy = true;
+  fl.nq = nq;
+  fl.q_first = q_first;
   return BBQ_OK;
 }
 
 void account_timing(bbq_index *ix, Slot &s) {
-  if (!s.timed) return;
   float ms = 0;
-  if (hipEventElapsedTime(&ms, s.ev0, s.ev1) == hipSuccess) {
-    ix->stats.last_scan_ms = ms;
-    ix->stats.last_scan_rows = s.timed_rows;
-    ix->stats.last_scan_bytes = s.timed_bytes;
-    ix->stats.total_scan_ms += ms;
-    ix->stats.total_scan_bytes += s.timed_bytes;
-    ix->stats.total_scan_launches += 1;
-  }
+  if (!s.fl.timed || hipEventElapsedTime(&ms, s.ev0, s.ev1) != hipSuccess) return;
+  ix->stats.last_scan_ms = ms;
+  ix->stats.last_scan_rows = s.fl.timed_rows;
+  ix->stats.last_scan_bytes = s.fl.timed_bytes;
+  ix->stats.total_scan_ms += ms;
+  ix->stats.total_scan_bytes += s.fl.timed_bytes;
+  ix->stats.total_scan_launches += 1;
 }
 
-// device work of the slot's sub-batch is done: collect it and start the heap replays (on the pool when replay_threads > 1)
-int begin_replay(const BatchCtx &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
-  bbq_index *ix = c.ix;
-  HIPCHK(hipEventSynchronize(s.ev_done));
-  s.busy = false;
-  account_timing(ix, s);
-  const int nq = s.nq;
-  s.dense_q.clear();
-  s.tails.assign((size_t)nq, std::vector<uint64_t>());
-  const bool fin = s.final_used;
-  if (fin)  // the header slots of the answer block carry what the two small copies used to bring
-    for (int i = 0; i < nq; ++i) {
-      const uint64_t *hdr = s.h_final + (size_t)i * s.final_stride;
-      s.h_list_counts[2 * i] = (int32_t)(uint32_t)hdr[0];
-      s.h_list_counts[2 * i + 1] = (int32_t)(uint32_t)(hdr[0] >> 32);
+// ------------------------------------------------------------------------------------------------ collection, step by step
+
+// step 0: the per-query collection state of a sub-batch of nq queries, the first of which is query q_first of the call
+static void open_collection(Slot &s, int nq, int64_t q_first) {
+  Slot::InFlight &fl = s.fl;
+  fl.nq = nq;
+  fl.q_first = q_first;
+  fl.dense_q.clear();
+  fl.tails.assign((size_t)nq, std::vector<uint64_t>());
+  fl.host_cnt.assign((size_t)nq, 0);
+  fl.host_replay.assign((size_t)nq, 0);
+}
+
+// step 1: what the device said about query i: entries listed, flags (non-zero: it could not bound the query, which goes to
+// finish_replay's dense handling) and whether the host has to replay its heap over the list
+static void set_verdict(bbq_index *ix, Slot &s, int i, uint32_t listed, uint32_t flags, bool replay) {
+  s.h_list_counts[2 * i] = (int32_t)listed;
+  s.h_list_counts[2 * i + 1] = (int32_t)flags;
+  if (flags != 0) s.fl.dense_q.push_back(i);
+  else if (replay) { s.fl.host_replay[(size_t)i] = 1; ix->stats.host_replays += 1; }
+}
+
+// ... for a sub-batch: from the header slots of the answer blocks (which carry what the two small copies used to bring), or from the
+// copied counters - without the final selection every bounded query is replayed
+static void read_verdicts(bbq_index *ix, Slot &s) {
+  for (int i = 0; i < s.fl.nq; ++i)
+    if (s.fl.final_used) {
+      const AnswerHeader h(s.h_final + (size_t)i * s.final_stride);
+      set_verdict(ix, s, i, h.listed, h.flags, h.needs_replay != 0);
+    } else {
+      set_verdict(ix, s, i, (uint32_t)s.h_list_counts[2 * i], (uint32_t)s.h_list_counts[2 * i + 1], true);
     }
-  auto final_cnt = [&s](int i) { return (int32_t)(uint32_t)s.h_final[(size_t)i * s.final_stride + 1]; };
-  auto final_replay = [&s](int i) { return (uint32_t)(s.h_final[(size_t)i * s.final_stride + 1] >> 32) != 0; };
-  // list entries of query i that sit in the pinned h_lists row: the prefix the enqueue-time copy brought over, or - when the device was
-  // to answer and could not (equal scores) - the whole list, fetched below with ONE batch of asynchronous copies on the slot's stream
-  // (a synchronous pageable copy per query on the null stream stalled every other slot: duplicated vectors make such queries common)
-  s.host_cnt.assign((size_t)nq, 0);
-  int n_replay = 0;
-  struct CountReplays {  // on every exit path
-    bbq_index *ix; int &n;
-    ~CountReplays() { ix->stats.host_replays += n; }
-  } count_replays{ix, n_replay};
+}
+
+// step 2: the lists of the queries to replay into the pinned h_lists rows.  prefix_on_host: the enqueue-time copy brought the first
+// hprefix entries; otherwise (the device was to answer and could not: equal scores) the whole list is fetched - with ONE batch of
+// asynchronous copies on the slot's stream (a synchronous pageable copy per query on the null stream stalled every other slot:
+// duplicated vectors make such queries common)
+static int fetch_lists(Slot &s, bool prefix_on_host) {
+  Slot::InFlight &fl = s.fl;
   bool fetched = false;
-  for (int i = 0; i < nq; ++i) {
-    const int32_t cnt = s.h_list_counts[2 * i], flags = s.h_list_counts[2 * i + 1];
-    if (flags != 0) { s.dense_q.push_back(i); continue; }
-    if (fin && !final_replay(i)) continue;  // answered on the device
-    ++n_replay;
-    int64_t have = fin ? 0 : std::min<int64_t>(cnt, s.hprefix);
-    if (fin && cnt > 0) {
-      have = std::min<int64_t>(cnt, s.hprefix);
+  for (int i = 0; i < fl.nq; ++i) {
+    if (!fl.host_replay[(size_t)i]) continue;
+    const int64_t cnt = s.h_list_counts[2 * i], have = std::min<int64_t>(cnt, s.hprefix);
+    if (!prefix_on_host && cnt > 0) {
       HIPCHK(hipMemcpyAsync(s.h_lists + (size_t)i * s.hprefix, s.d_lists + (size_t)i * s.list_cap, (size_t)have * 8, hipMemcpyDeviceToHost, s.stream));
       fetched = true;
     }
-    s.host_cnt[(size_t)i] = have;
+    fl.host_cnt[(size_t)i] = have;
     if (cnt > have) {  // rare (a flood): the rest of a list longer than the pinned row
-      s.tails[(size_t)i].resize((size_t)(cnt - have));
-      HIPCHK(hipMemcpyAsync(s.tails[(size_t)i].data(), s.d_lists + (size_t)i * s.list_cap + have, (size_t)(cnt - have) * 8, hipMemcpyDeviceToHost, s.stream));
+      fl.tails[(size_t)i].resize((size_t)(cnt - have));
+      HIPCHK(hipMemcpyAsync(fl.tails[(size_t)i].data(), s.d_lists + (size_t)i * s.list_cap + have, (size_t)(cnt - have) * 8, hipMemcpyDeviceToHost, s.stream));
       fetched = true;
     }
   }
   if (fetched) HIPCHK(hipStreamSynchronize(s.stream));
-  if (s.appended)  // append mode leaves the entries of a segment in arrival order: the reference loop wants them by row (row << 32 | score bits)
-    for (int i = 0; i < nq; ++i) {
-      if (s.host_cnt[(size_t)i] == 0 && s.tails[(size_t)i].empty()) continue;
-      uint64_t *l = s.h_lists + (size_t)i * s.hprefix;
-      std::vector<uint64_t> &t = s.tails[(size_t)i];
-      if (t.empty()) {
-        std::sort(l, l + s.host_cnt[(size_t)i]);
-      } else {  // list longer than the pinned row: sort the whole of it in the tail vector
-        t.insert(t.begin(), l, l + s.host_cnt[(size_t)i]);
-        s.host_cnt[(size_t)i] = 0;
-        std::sort(t.begin(), t.end());
-      }
-    }
-  const int64_t k = c.k, n_total = ix->main.row_id_base + ix->main.view.n_rows;
-  Slot *sp = &s;
-  if (fin) {  // queries the last finalize launch answered: the sorted rows are the result
-    for (int i = 0; i < nq; ++i) {
-      if (s.h_list_counts[2 * i + 1] != 0 || final_replay(i)) continue;
-      const int64_t qi = s.q_first + i;
-      const int32_t m = final_cnt(i);
-      const uint64_t *fo = s.h_final + (size_t)i * s.final_stride + 2;
-      for (int32_t j = 0; j < m; ++j) {
-        const uint32_t bits = (uint32_t)fo[j];
-        out_idx[qi * k + j] = (int32_t)(uint32_t)(fo[j] >> 32);
-        memcpy(&out_score[qi * k + j], &bits, 4);
-      }
-      out_n[qi] = m;
-    }
-  }
-  auto replay_range = [sp, k, n_total, out_idx, out_score, out_n, fin](int lo, int hi) {
-    Slot &s = *sp;
-    for (int i = lo; i < hi; ++i) {
-      const int32_t cnt = s.h_list_counts[2 * i], flags = s.h_list_counts[2 * i + 1];
-      if (flags != 0) continue;
-      if (fin && (uint32_t)(s.h_final[(size_t)i * s.final_stride + 1] >> 32) == 0) continue;
-      HeapReplay hr(k, n_total);
-      const uint64_t *l = s.h_lists + (size_t)i * s.hprefix;
-      const int64_t head = s.host_cnt[(size_t)i];
-      (void)cnt;
-      for (int64_t j = 0; j < head; ++j) {
-        const uint32_t bits = (uint32_t)l[j];
-        float sc;
-        memcpy(&sc, &bits, 4);
-        hr.offer(sc, (int32_t)(uint32_t)(l[j] >> 32));
-      }
-      for (uint64_t e : s.tails[(size_t)i]) {
-        const uint32_t bits = (uint32_t)e;
-        float sc;
-        memcpy(&sc, &bits, 4);
-        hr.offer(sc, (int32_t)(uint32_t)(e >> 32));
-      }
-      const int64_t qi = s.q_first + i;
-      out_n[qi] = hr.finish(out_idx + qi * k, out_score + qi * k);
-    }
-  };
-  const int T = std::min(ix->opt_replay_threads, n_replay);
-  s.replaying = true;
-  if (n_replay == 0) {
-    // nothing to replay
-  } else if (T <= 1) {
-    replay_range(0, nq);
-  } else {
-    ReplayPool &pool = ReplayPool::get();
-    pool.ensure(ix->opt_replay_threads);
-    const int jobs = std::min(nq, T * 2);  // a few more jobs than threads: uneven lists balance out
-    s.pending.store(jobs);
-    for (int t = 0; t < jobs; ++t) {
-      const int lo = (int)((int64_t)nq * t / jobs), hi = (int)((int64_t)nq * (t + 1) / jobs);
-      pool.submit([sp, replay_range, lo, hi] {
-        replay_range(lo, hi);
-        sp->pending.fetch_sub(1, std::memory_order_release);
-      });
-    }
-  }
   return BBQ_OK;
 }
 
+// step 3: append mode leaves the entries of a segment in arrival order: the reference loop wants them by row (entries order like rows)
+static void order_lists_by_row(Slot &s) {
+  Slot::InFlight &fl = s.fl;
+  for (int i = 0; i < fl.nq; ++i) {
+    if (fl.host_cnt[(size_t)i] == 0 && fl.tails[(size_t)i].empty()) continue;
+    uint64_t *l = s.h_lists + (size_t)i * s.hprefix;
+    std::vector<uint64_t> &t = fl.tails[(size_t)i];
+    if (t.empty()) {
+      std::sort(l, l + fl.host_cnt[(size_t)i]);
+    } else {  // list longer than the pinned row: sort the whole of it in the tail vector
+      t.insert(t.begin(), l, l + fl.host_cnt[(size_t)i]);
+      fl.host_cnt[(size_t)i] = 0;
+      std::sort(t.begin(), t.end());
+    }
+  }
+}
+
+// step 4: queries the last finalize launch answered: the sorted rows are the result
+static void take_device_answers(const SearchCall &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
+  for (int i = 0; i < s.fl.nq; ++i) {
+    if (s.h_list_counts[2 * i + 1] != 0 || s.fl.host_replay[(size_t)i]) continue;
+    const uint64_t *block = s.h_final + (size_t)i * s.final_stride;
+    const int64_t qi = s.fl.q_first + i, m = AnswerHeader(block).count;
+    unpack_entries(block + 2, m, out_idx + qi * c.k_out, out_score + qi * c.k_out);
+    out_n[qi] = m;
+  }
+}
+
+// step 5: the heap replays, on the pool when replay_threads > 1; finish_replay waits for them
+static void schedule_replays(const SearchCall &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
+  const int64_t k = c.k_out, n_total = c.ix->main.row_id_base + c.ix->main.view.n_rows;
+  Slot *sp = &s;
+  auto replay_range = [sp, k, n_total, out_idx, out_score, out_n](int lo, int hi) {
+    Slot &s = *sp;
+    for (int i = lo; i < hi; ++i) {
+      if (!s.fl.host_replay[(size_t)i]) continue;
+      HeapReplay hr(k, n_total);
+      const uint64_t *l = s.h_lists + (size_t)i * s.hprefix;
+      for (int64_t j = 0; j < s.fl.host_cnt[(size_t)i]; ++j) hr.offer(entry_score(l[j]), (int32_t)entry_row(l[j]));
+      for (uint64_t e : s.fl.tails[(size_t)i]) hr.offer(entry_score(e), (int32_t)entry_row(e));
+      const int64_t qi = s.fl.q_first + i;
+      out_n[qi] = hr.finish(out_idx + qi * k, out_score + qi * k);
+    }
+  };
+  const int nq = s.fl.nq, n_replay = (int)std::count(s.fl.host_replay.begin(), s.fl.host_replay.end(), 1);
+  const int T = std::min(c.ix->opt_replay_threads, n_replay);
+  s.fl.replaying = true;
+  if (T == 1) replay_range(0, nq);
+  if (T <= 1) return;  // nothing to replay, or replayed on this thread
+  replay_pool().ensure(c.ix->opt_replay_threads);
+  const int jobs = std::min(nq, T * 2);  // a few more jobs than threads: uneven lists balance out
+  s.fl.pending.store(jobs);
+  for (int t = 0; t < jobs; ++t) {
+    const int lo = (int)((int64_t)nq * t / jobs), hi = (int)((int64_t)nq * (t + 1) / jobs);
+    replay_pool().post([sp, replay_range, lo, hi] {
+      replay_range(lo, hi);
+      sp->fl.pending.fetch_sub(1, std::memory_order_release);
+    });
+  }
+}
+
+// device work of the slot's sub-batch is done: collect it and start the heap replays
+int begin_replay(const SearchCall &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
+  HIPCHK(hipEventSynchronize(s.ev_done));
+  s.fl.busy = false;
+  account_timing(c.ix, s);
+  open_collection(s, s.fl.nq, s.fl.q_first);
+  read_verdicts(c.ix, s);
+  int rc = fetch_lists(s, !s.fl.final_used);
+  if (rc != BBQ_OK) return rc;
+  if (s.fl.appended) order_lists_by_row(s);
+  if (s.fl.final_used) take_device_answers(c, s, out_idx, out_score, out_n);
+  schedule_replays(c, s, out_idx, out_score, out_n);
+  return BBQ_OK;
+}
+
+// The call's one query (query 0) whose complete, unordered list sits in s.d_lists and whose answer a latency chain could not prove
+// ({listed, flags}: what its answer header said; nothing of the slot is in flight): the collection steps it needs, to the end.
+int replay_listed_query(const SearchCall &c, Slot &s, uint32_t listed, uint32_t flags, int32_t *out_idx, float *out_score, int64_t *out_n) {
+  open_collection(s, 1, 0);
+  set_verdict(c.ix, s, 0, listed, flags, true);
+  int rc = fetch_lists(s, false);
+  if (rc != BBQ_OK) return rc;
+  order_lists_by_row(s);
+  schedule_replays(c, s, out_idx, out_score, out_n);
+  return finish_replay(c, s, out_idx, out_score, out_n);
+}
+
 // waits for the slot's replays, then serves the queries the device could not bound (dense path)
-int finish_replay(const BatchCtx &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
+int finish_replay(const SearchCall &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
   bbq_index *ix = c.ix;
-  while (s.pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
-  s.replaying = false;
-  const int64_t k = c.k;
-  for (int i = 0; i < s.nq; ++i)
+  Slot::InFlight &fl = s.fl;
+  auto wait_replays = [&fl] {
+    while (fl.pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
+    fl.replaying = false;
+  };
+  wait_replays();
+  for (int i = 0; i < fl.nq; ++i)
     if (s.h_list_counts[2 * i + 1] == 0) ix->stats.candidates += s.h_list_counts[2 * i];
-  if (s.dense_q.empty()) return BBQ_OK;
+  if (fl.dense_q.empty()) return BBQ_OK;
   // queries the device could not bound.  The shared sweeps have no flood tier: a query whose candidate slots overflowed
   // there first gets one sweep of its own (slot s is free again at this point) before it pays for the dense path.
-  const std::vector<int> flagged = s.dense_q;
+  const std::vector<int> flagged = fl.dense_q;
   std::vector<uint32_t> why;
   for (int i : flagged) why.push_back((uint32_t)s.h_list_counts[2 * i + 1]);
-  const int64_t first = s.q_first;
-  s.dense_q.clear();
+  const int64_t first = fl.q_first;
+  fl.dense_q.clear();
   for (size_t j = 0; j < flagged.size(); ++j) {
     const int64_t qi = first + flagged[j];
-    if (ix->opt_share > 1 && ix->plan.flood_cap > 0 && why[j] == kFlagOverflow) {
-      BatchCtx cs = c;
-      cs.k = ix->plan.k;  // the rank the device runs this call with
-      const int share = ix->opt_share;
-      ix->opt_share = 1;
-      int rc = enqueue_subbatch(cs, s, qi, 1, nullptr);
-      ix->opt_share = share;
-      if (rc == BBQ_OK) rc = begin_replay(c, s, out_idx, out_score, out_n);
+    if (c.share > 1 && c.plan->flood_cap > 0 && why[j] == kFlagOverflow) {
+      SearchCall alone = c;
+      alone.share = 1;
+      int rc = enqueue_subbatch(alone, s, qi, 1, nullptr);
+      if (rc == BBQ_OK) rc = begin_replay(alone, s, out_idx, out_score, out_n);
       if (rc != BBQ_OK) return rc;
-      while (s.pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
-      s.replaying = false;
-      const bool solved = s.dense_q.empty();
-      s.dense_q.clear();
+      wait_replays();
+      const bool solved = fl.dense_q.empty();
+      fl.dense_q.clear();
       if (solved) {
         ix->stats.candidates += s.h_list_counts[0];
         continue;
       }
     }
-    int rc = dense_search_one(c, qi, out_idx + qi * k, out_score + qi * k, out_n + qi);
+    int rc = dense_search_one(c, qi, out_idx + qi * c.k_out, out_score + qi * c.k_out, out_n + qi);
     if (rc != BBQ_OK) return rc;
   }
   return BBQ_OK;
 }
 
 // brings a slot back to "free": collect + replay + wait, whatever is still outstanding
-static int reclaim_slot(const BatchCtx &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
+static int reclaim_slot(const SearchCall &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
   int rc = BBQ_OK;
-  if (s.busy) rc = begin_replay(c, s, out_idx, out_score, out_n);
-  if (rc == BBQ_OK && s.replaying) rc = finish_replay(c, s, out_idx, out_score, out_n);
+  if (s.fl.busy) rc = begin_replay(c, s, out_idx, out_score, out_n);
+  if (rc == BBQ_OK && s.fl.replaying) rc = finish_replay(c, s, out_idx, out_score, out_n);
   return rc;
 }
 
@@ -663,11 +632,7 @@ int drain(bbq_index *ix) {
 }
 
 // candidates, dense_fallbacks and host_replays count per call
-static void reset_call_stats(bbq_index *ix) {
-  ix->stats.candidates = 0;
-  ix->stats.dense_fallbacks = 0;
-  ix->stats.host_replays = 0;
-}
+static void reset_call_stats(bbq_index *ix) { ix->stats.candidates = ix->stats.dense_fallbacks = ix->stats.host_replays = 0; }
 
 }  // namespace bbq
 
@@ -695,7 +660,7 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
   reset_call_stats(ix);
   if (ix->n_rows == 0) return BBQ_OK;
 
-  BatchCtx c{ix, qquant, qcorr, 0, query_bits == 1 ? 1 : 0, sim, k};
+  SearchCall c(ix, qquant, qcorr, 0, query_bits, sim, k);
   if (feed) {  // the values are still being produced: the kernel variant follows from the bit width they are quantized to
     const int pq = query_bits <= 1 ? 1 : query_bits <= 2 ? 2 : query_bits <= 4 ? 4 : 8;
     c.planes = ix->store_bits == 1 ? pq : ix->store_bits == 8 ? 8 : (query_bits <= 4 ? 4 : 8);
@@ -705,7 +670,6 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
     c.maxq = c.planes <= 4 ? 15 : max_value(qquant, (int64_t)n_queries * ix->dim);
   }
   const int64_t keff = std::min<int64_t>(k, ix->n_rows);
-  c.k = k;
   if (keff > kMaxFastK || ix->opt_force_dense) {
     for (int32_t i = 0; i < n_queries; ++i) {
       if (feed && (rc = feed->wait(i, 1, bad_query)) != BBQ_OK) return rc;
@@ -714,19 +678,18 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
     }
     return BBQ_OK;
   }
-  // thresholds are order statistics of rank k2 = min(k, N): selecting with a larger k would be wrong.
-  // cs drives the device (k2); c (the caller's k) strides the outputs and sizes the replayed heap.
-  BatchCtx cs = c;
-  // up to kFinalSelectMax the device runs with rank keff + 1 and the last finalize launch selects and sorts the answer itself
-  // (FinalizeArgs::final_out); the host replays the heap only for queries with equal scores in or at the edge of their answer
+  // thresholds are order statistics of rank min(k, N): selecting with a larger k would be wrong.  Up to kFinalSelectMax the device
+  // runs with rank keff + 1 and the last finalize launch selects and sorts the answer itself (FinalizeArgs::final_out); the host
+  // replays the heap only for queries with equal scores in or at the edge of their answer
   const int64_t final_k = (keff <= kFinalSelectMax && ix->opt_device_select) ? keff : 0;
-  cs.k = final_k > 0 ? keff + 1 : keff;
-  build_plan(ix, cs.k, final_k, final_k > 0 && n_queries <= ix->opt_latency_queries);
-  if (n_queries == 1 && ix->plan.latency && !feed) {
+  c.k_dev = final_k > 0 ? keff + 1 : keff;
+  const Plan plan = build_plan(ix, c.k_dev, final_k, final_k > 0 && n_queries <= ix->opt_latency_queries);
+  c.plan = &plan;
+  if (n_queries == 1 && plan.latency && !feed) {
     bool done = false;
-    rc = search_latency_presampled(c, cs, out_idx, out_score, out_n, &done);
+    rc = search_latency_presampled(c, out_idx, out_score, out_n, &done);
     if (rc != BBQ_OK || done) return rc;
-    rc = search_latency_chain(c, cs, out_idx, out_score, out_n, &done);
+    rc = search_latency_chain(c, out_idx, out_score, out_n, &done);
     if (rc != BBQ_OK || done) return rc;
   }
   const int Q = effective_batch(ix, n_queries);
@@ -734,9 +697,9 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
   const int64_t nsub = ((int64_t)n_queries + Q - 1) / Q;
   auto fail_out = [&](int code) {
     for (int i = 0; i < kMaxSlots; ++i)  // never leave pool jobs pointing at a caller's buffers
-      while (ix->slots[i].pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
+      while (ix->slots[i].fl.pending.load(std::memory_order_acquire) > 0) std::this_thread::yield();
     drain(ix);
-    for (int i = 0; i < kMaxSlots; ++i) ix->slots[i].busy = ix->slots[i].replaying = false;
+    for (int i = 0; i < kMaxSlots; ++i) ix->slots[i].fl.reset();
     return code;
   };
   for (int64_t i = 0; i < nsub; ++i) {
@@ -744,15 +707,15 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
     rc = reclaim_slot(c, s, out_idx, out_score, out_n);
     if (rc != BBQ_OK) return fail_out(rc);
     const int nq = (int)std::min<int64_t>(Q, n_queries - i * Q);
-    rc = ensure_slot(ix, s, nq, true);
+    rc = ensure_slot(c, s, nq, true);
     if (rc != BBQ_OK) return fail_out(rc);
     if (feed && (rc = feed->wait(i * Q, nq, bad_query)) != BBQ_OK) return fail_out(rc);
-    rc = enqueue_subbatch(cs, s, i * Q, nq, nullptr);
+    rc = enqueue_subbatch(c, s, i * Q, nq, nullptr);
     if (rc != BBQ_OK) return fail_out(rc);
     // hand finished sub-batches to the replay workers as early as possible (their slot is needed again soon)
     for (int j = 0; j < nslots; ++j) {
       Slot &t = ix->slots[j];
-      if (&t != &s && t.busy && hipEventQuery(t.ev_done) == hipSuccess) {
+      if (&t != &s && t.fl.busy && hipEventQuery(t.ev_done) == hipSuccess) {
         rc = begin_replay(c, t, out_idx, out_score, out_n);
         if (rc != BBQ_OK) return fail_out(rc);
       }

@@ -7,7 +7,7 @@ using namespace bbq;
 namespace {
 
 // query qi of the call into the device's auxiliary query buffer, on the auxiliary stream; returns when it is there
-int stage_aux_query(const BatchCtx &c, int64_t qi) {
+int stage_aux_query(const SearchCall &c, int64_t qi) {
   bbq_index *ix = c.ix;
   int rc = ensure_aux_qbuf(ix->ctx, qbuf_bytes_per_query_w(ix->w16));
   if (rc != BBQ_OK) return rc;
@@ -22,10 +22,10 @@ int stage_aux_query(const BatchCtx &c, int64_t qi) {
 }
 
 // a dense sweep of the main storage from chunk_begin on with the staged query; the caller adds where the scores go
-ScanArgs dense_scan_args(const BatchCtx &c, int64_t chunk_begin) {
+ScanArgs dense_scan_args(const SearchCall &c, int64_t chunk_begin) {
   bbq_index *ix = c.ix;
   ScanArgs a{};
-  a.idx = launch_view(ix, ix->main);
+  a.idx = launch_view(ix, ix->main).view;
   a.qplanes = reinterpret_cast<const uint4 *>(ix->ctx->d_aux_qbuf.get());
   a.qparams = reinterpret_cast<const QueryParams *>(ix->ctx->d_aux_qbuf + query_data_bytes(ix, c.planes));
   a.chunk_begin = chunk_begin;
@@ -35,7 +35,7 @@ ScanArgs dense_scan_args(const BatchCtx &c, int64_t chunk_begin) {
 }
 
 // every f32 score of one query to the host (out [n_rows] of this index)
-int dense_scores_one(const BatchCtx &c, int64_t qi, float *out) {
+int dense_scores_one(const SearchCall &c, int64_t qi, float *out) {
   bbq_index *ix = c.ix;
   const int64_t n = ix->main.view.n_rows;
   const int64_t chunks = ix->main.n_chunks();
@@ -58,13 +58,13 @@ int dense_scores_one(const BatchCtx &c, int64_t qi, float *out) {
 namespace bbq {
 
 // dense path for one query: every f32 score to the host, full replay of the reference loop
-int dense_search_one(const BatchCtx &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n) {
+int dense_search_one(const SearchCall &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n) {
   bbq_index *ix = c.ix;
   const int64_t n = ix->main.view.n_rows;
   std::vector<float> h((size_t)std::max<int64_t>(n, 1));
   int rc = dense_scores_one(c, qi, h.data());
   if (rc != BBQ_OK) return rc;
-  HeapReplay hr(c.k, n);
+  HeapReplay hr(c.k_out, n);
   for (int64_t i = 0; i < n; ++i) hr.offer(h[(size_t)i], (int32_t)(ix->main.row_id_base + i));
   *out_n = hr.finish(out_idx, out_score);
   ix->stats.dense_fallbacks += 1;
@@ -77,7 +77,7 @@ int dense_scores_host(bbq_index *ix, const uint8_t *qquant, const double *qcorr,
   std::lock_guard<std::mutex> lk(ix->ctx->mu);
   HIPCHK(hipSetDevice(ix->device));
   if (ix->n_rows == 0) return BBQ_OK;
-  BatchCtx c{ix, qquant, qcorr, planes_of_call(ix, qquant, ix->dim, query_bits == 1), query_bits == 1 ? 1 : 0, sim, 0};
+  const SearchCall c(ix, qquant, qcorr, planes_of_call(ix, qquant, ix->dim, query_bits == 1), query_bits, sim, 0);
   ix->stats.dense_fallbacks += 1;
   return dense_scores_one(c, 0, out);
 }
@@ -97,7 +97,7 @@ int bbq_score_rows(bbq_index *ix, const uint8_t *qquant, const double *qcorr, in
   if (ix->multi) return multi_score_rows(ix, qquant, qcorr, query_bits, sim, row_begin, row_count, out_qcdist, out_score64, out_score32);
   std::lock_guard<std::mutex> lk(ix->ctx->mu);
   HIPCHK(hipSetDevice(ix->device));
-  BatchCtx c{ix, qquant, qcorr, planes_of_call(ix, qquant, ix->dim, query_bits == 1), query_bits == 1 ? 1 : 0, sim, 0};
+  const SearchCall c(ix, qquant, qcorr, planes_of_call(ix, qquant, ix->dim, query_bits == 1), query_bits, sim, 0);
   rc = stage_aux_query(c, 0);
   if (rc != BBQ_OK) return rc;
   hipStream_t st = ix->ctx->aux_stream;

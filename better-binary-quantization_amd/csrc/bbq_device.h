@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "bbq_entry.h"
 
 namespace bbq {
 
@@ -228,7 +229,5 @@ constexpr int kFinalizeCountCap = 24576; // chunk counters one launch stages in 
 constexpr int kFinalizeLdsBytes = (kFinalizeKeyCap + 3 * kFinalizeJobs + 512 + 16 + 16) * 4 + kFinalizeCountCap * 2;  // 146 KB of the CU's 160 KB
 // a finalize launch behind an appending or a dense sweep: keys, histogram, scratch and the 8 KB of the job table the final selection sorts in
 constexpr int kFinalizeLdsBytesSmall = (kFinalizeKeyCap + 512 + 16 + 16) * 4 + kFinalSelectMax * 8;
-
-__host__ __device__ inline uint32_t key_of_bits(uint32_t b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 
 }  // namespace bbq

@@ -1,13 +1,14 @@
 // bbq_host.h - host-side internals of libbbq shared by its translation units: the device-resident index object, the
 // per-device context (streams, events, per-slot workspace) and the helpers every entry point needs.
 //   bbq_index.cpp    device context, index creation from rows, tile storage, cache budget of a launch, statistics, options
-//   bbq_core.cpp     segment plan, slot workspace, pipelined batch search with host replay (shares bbq_search.h with the next four)
+//   bbq_core.cpp     segment plan, slot workspace, pipelined batch search: enqueue, collection in steps, host replay (shares bbq_search.h - the SearchCall - with the next four)
 //   bbq_query.cpp    query staging    bbq_latency.cpp  single-query chains    bbq_dense.cpp  dense path, bbq_score_rows
 //   bbq_shard.cpp    scan of one shard of a row-sharded index (bbq_shard_scan*)
 //   bbq_multi.cpp    one index over several devices of a process
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
+// bbq_entry.h is the codec of the 64-bit entries, keys and answer headers; bbq_workqueue.h the host threads' job queue.
 // HIP memory and events are held in the owning types of bbq_mem.h: what a struct below owns goes with it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -51,8 +52,9 @@ struct Segment {
   bool big = false;  // large sweeps of different sub-batches are serialised through an event chain
 };
 
+// the segments of one call and the sizes that follow from them: built per call (build_plan) and handed on through its SearchCall
 struct Plan {
-  int64_t k = -1;
+  int64_t k = 0;          // the rank the device selects thresholds with
   std::vector<Segment> segs;
   int64_t s0 = 0;
   int64_t list_cap = 0;
@@ -79,7 +81,6 @@ struct Slot {
   uint8_t *d_qbuf = nullptr, *h_qbuf = nullptr;
   uint32_t *d_theta = nullptr, *d_flags = nullptr, *d_append_counts = nullptr, *d_ovf_counts = nullptr;
   int32_t *d_topk_counts = nullptr, *d_list_counts = nullptr;
-  bool appended = false;  // the in-flight sub-batch's lists are unordered inside their segments (append mode)
   DevBuf<uint32_t> d_counts, d_topk;
   PinnedBuf<int32_t> h_list_counts;
   DevBuf<uint64_t> d_entries, d_lists, d_ovf;
@@ -89,21 +90,26 @@ struct Slot {
   DevBuf<uint64_t> d_final;  // [q_cap][final_stride]: 2 header slots + the answer per query
   PinnedBuf<uint64_t> h_final;
   int64_t final_stride = 0;
-  bool final_used = false;  // the in-flight sub-batch was enqueued with the final selection (its list prefix was NOT copied to the host)
-  // in-flight sub-batch: busy = device work enqueued and not yet collected; replaying = host replay jobs outstanding
-  bool busy = false;
-  bool replaying = false;
-  std::atomic<int> pending{0};
-  std::vector<std::vector<uint64_t>> tails;
-  std::vector<int64_t> host_cnt;  // entries of query i in its h_lists row (the rest, if any, in tails[i])
-  std::vector<int> dense_q;
-  int nq = 0;
-  int64_t q_first = 0;
-  bool timed = false;
-  int64_t timed_rows = 0, timed_bytes = 0;
-  // non-null: the in-flight sub-batch belongs to an asynchronous sharded scan of that index (bbq_shard_scan_begin); nothing is to be
-  // collected from it but the timing.  Such slots stay busy ACROSS API calls: every entry point that uses the slots settles them first.
-  bbq_index *shard_owner = nullptr;
+  // what is in flight on the slot (everything above is workspace).  busy: device work enqueued, not yet collected; replaying: host replay jobs outstanding
+  struct InFlight {
+    bool busy = false, replaying = false, timed = false;
+    bool appended = false;    // the lists are unordered inside their segments (append mode)
+    bool final_used = false;  // enqueued with the final selection (the list prefix was NOT copied to the host)
+    std::atomic<int> pending{0};
+    int nq = 0;               // queries of the sub-batch ...
+    int64_t q_first = 0;      // ... from this query of the call on
+    // collection (begin_replay): per query, does the host replay its heap; entries of query i in its h_lists row (the rest, if any, in
+    // tails[i]); the queries the device could not bound
+    std::vector<uint8_t> host_replay;
+    std::vector<int64_t> host_cnt;
+    std::vector<std::vector<uint64_t>> tails;
+    std::vector<int> dense_q;
+    int64_t timed_rows = 0, timed_bytes = 0;  // timed: of the dominant sweep between ev0 and ev1
+    // non-null: the sub-batch belongs to an asynchronous sharded scan of that index (bbq_shard_scan_begin); nothing is to be collected
+    // from it but the timing.  Such slots stay busy ACROSS API calls: every entry point that uses the slots settles them first.
+    bbq_index *shard_owner = nullptr;
+    void reset() { busy = replaying = appended = final_used = timed = false; nq = 0; dense_q.clear(); shard_owner = nullptr; }  // no job pending
+  } fl;
   // the control words are all zero (the latency chain leaves them so and expects them so; every other use of the slot dirties them
   // and resets them with its own host-to-device copy)
   bool ctrl_clean = false;
@@ -166,7 +172,6 @@ struct bbq_index {
   double centroid_dp = 0;
   bool has_pilot = false;
   bbq::Storage pilot, main;
-  bbq::Plan plan;
   bbq::DevBuf<float> d_dense_all;
   // bbq_shard_scan_begin / _wait: per-query lists before packing, two sets (two batches may be in flight) and their tickets
   struct ShardSet {
@@ -183,7 +188,6 @@ struct bbq_index {
   // a call with few queries is latency-bound: every segment costs a dependent scan + finalize launch pair (~15-20 us), so such calls
   // walk the index in fewer, faster-growing segments (more candidates per query - the device selects the answer itself anyway)
   int opt_latency_queries = 4, opt_latency_growth = 64;
-  int64_t sweep_resident_acc = 0;  // cache-resident bytes of the launches of one sweep of the index, summed by launch_view()
   int opt_resident_interleave = 1;  // the resident chunks of a launch are spread over its range (of every 64 chunks the first n) instead of being its head
   int opt_resident_mb = -1;  // MiB of its row range that ONE sweep launch loads with the default cache policy, so that they stay in the Infinity
                              // Cache from one query's sweep to the next (launch_view(), bbq_index.cpp); -1: this index's share of kResidentAutoBytes
@@ -226,8 +230,10 @@ int open_device(int device, DeviceCtx **ctx);
 void set_index_geometry(bbq_index *ix, int32_t dim, int32_t index_bits);
 // a new index on its device: the geometry, the context and its slots, the auxiliary query buffer grown to this index's queries
 int attach_index(bbq_index *ix, DeviceCtx *ctx, int device, int32_t dim, int32_t index_bits);
-// The view a launch gets: the stored view + which chunks it loads cache-resident.  Context mutex held by the caller.
-IndexView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin = 0, int64_t n_chunks = -1);
+// The view a launch gets: the stored view + which chunks it loads cache-resident, and the bytes of them (the caller that sweeps the index
+// sums them into bbq_stats.resident_bytes).  Context mutex held by the caller.
+struct LaunchView { IndexView view; int64_t resident_bytes; };
+LaunchView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin = 0, int64_t n_chunks = -1);
 #pragma GCC visibility pop
 // retires what the device still runs for the index and deletes it (its members release their memory); the device context (streams,
 // workspace) stays.  Call with the context mutex held.

@@ -171,7 +171,7 @@ static int64_t cache_sharers_bytes(bbq_index *ix, int64_t own) {
 }
 // One launch sweeps chunks [chunk_begin, chunk_begin + n_chunks) of `sto` once per query of its sub-batch, back to back: what it can
 // keep in the cache is a part of ITS range (the launches of a sub-batch run one after the other, each over its own rows).
-IndexView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin, int64_t n_chunks) {
+LaunchView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin, int64_t n_chunks) {
   IndexView v = sto.view;
   const int64_t all_chunks = sto.n_chunks();
   if (n_chunks < 0) n_chunks = all_chunks - chunk_begin;
@@ -198,8 +198,7 @@ IndexView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin, in
     v.resident_tiles = (chunk_begin + fit) * kTilesPerChunk;
     resident_chunks = fit;
   }
-  ix->sweep_resident_acc += resident_chunks * chunk_bytes;  // the caller books it per sweep of the index (bbq_stats.resident_bytes)
-  return v;
+  return LaunchView{v, resident_chunks * chunk_bytes};
 }
 
 // retires what the device still runs for the index, then deletes it: its storages, dense scores and shard sets go with it.  The
@@ -335,8 +334,8 @@ int bbq_set_option(bbq_index *ix, const char *name, int64_t v) {
   const std::string n(name);
   if (n == "batch_queries" && v >= 0 && v <= 1024) ix->opt_batch = (int)v;  // 0: by index size
   else if (n == "pipeline_slots" && v >= 1 && v <= kMaxSlots) ix->opt_slots = (int)v;
-  else if (n == "segment_growth" && v >= 2 && v <= 1024) { ix->opt_growth = (int)v; ix->plan.k = -1; }
-  else if (n == "first_segment_rows" && v >= 1024 && v <= 8192 && v % kChunkRows == 0) { ix->opt_s0 = v; ix->plan.k = -1; }
+  else if (n == "segment_growth" && v >= 2 && v <= 1024) ix->opt_growth = (int)v;
+  else if (n == "first_segment_rows" && v >= 1024 && v <= 8192 && v % kChunkRows == 0) ix->opt_s0 = v;
   else if (n == "resident_interleave" && (v == 0 || v == 1)) ix->opt_resident_interleave = (int)v;
   else if (n == "resident_mb" && v >= -1 && v <= 1 << 20) ix->opt_resident_mb = (int)v;
   else if (n == "replay_threads" && v >= 1 && v <= 256) ix->opt_replay_threads = (int)v;
@@ -350,7 +349,6 @@ int bbq_set_option(bbq_index *ix, const char *name, int64_t v) {
   else if (n == "sweep_share" && (v == 1 || v == 4 || v == 8 || v == 32)) ix->opt_share = (int)v;
   else if (n == "flood_rows" && v >= 0 && v <= (1 << 24)) ix->opt_flood = (v + 1023) / 1024 * 1024;
   else return fail(BBQ_ERR_INVALID_ARG, "bbq_set_option: unknown option or value out of range: %s=%lld", name, (long long)v);
-  ix->plan.k = -1;  // workspace is grow-only and re-checked by ensure_slot on the next call
   return BBQ_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 #include "../../include/bbq.h"
+#include "bbq_entry.h"
 
 namespace bbq {
 

@@ -224,8 +224,8 @@ __device__ __forceinline__ bool exact_key_passes(bool valid, float s32, uint32_t
   if (valid && (s32 != s32)) nan_seen = true;
   return valid && (s32 == s32) && key_of_bits(__float_as_uint(s32)) > theta;
 }
-// a candidate entry: global row << 32 | f32 score bits - entries of distinct rows order like their rows
-__device__ __forceinline__ uint64_t candidate_entry(int64_t row_id, float s32) { return ((uint64_t)(uint32_t)row_id << 32) | __float_as_uint(s32); }
+// a candidate entry (bbq_entry.h) of a row and its f32 score
+__device__ __forceinline__ uint64_t candidate_entry(int64_t row_id, float s32) { return make_entry((uint32_t)row_id, __float_as_uint(s32)); }
 
 // ---- candidates leaving a workgroup ------------------------------------------------------------------------------------------------
 // the cnt staged entries of a chunk into its slot, row-ordered: rows are distinct, so ranking by counting puts them in row order

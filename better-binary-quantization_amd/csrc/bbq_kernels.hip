@@ -501,7 +501,6 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_finalize_kernel(const Fi
     bool ok = f_all == 0 && a.emit && total <= a.list_cap && k2 >= 1 && k2 <= kFinalSelectMax && k2 + hdr_slots <= a.final_stride &&
               m_new <= (uint32_t)kFinalizeKeyCap - tcount && a.k == k2 + 1;
     uint64_t *__restrict__ s_sel = reinterpret_cast<uint64_t *>(s_jobs);  // the copy jobs are done with
-    auto bits_of = [](uint32_t key) -> uint32_t { return (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key; };
     uint32_t n_sel = 0, th1 = 0;  // rows with key > th1 are the answer
     // single index: a list of at most k2 rows holds every row of the index.  Shard: fewer than k2 + 1 rows SEEN (pilot replica included)
     // means no cut exists yet and every listed row stays in the running
@@ -569,18 +568,18 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_finalize_kernel(const Fi
       // anywhere in the answer or at its boundary mean that the heap's history decides: flagged, the host replays (a shard leaves
       // that check to the merge, which sees the global answer)
       uint64_t *__restrict__ fo = a.final_out + (size_t)q * a.final_stride + hdr_slots;
-      const float fth = __uint_as_float(bits_of(th1));
+      const float fth = __uint_as_float(bits_of_key(th1));
       for (uint32_t i = tid; i < n_sel; i += kFinalizeThreads) {
         const uint64_t x = s_sel[i];
-        const float fx = __uint_as_float(bits_of((uint32_t)(x >> 32)));
+        const float fx = __uint_as_float(bits_of_key((uint32_t)(x >> 32)));
         uint32_t rank = 0, same = 0;
         for (uint32_t j = 0; j < n_sel; ++j) {
           const uint64_t y = s_sel[j];
           rank += y > x ? 1u : 0u;
-          same += __uint_as_float(bits_of((uint32_t)(y >> 32))) == fx ? 1u : 0u;
+          same += __uint_as_float(bits_of_key((uint32_t)(y >> 32))) == fx ? 1u : 0u;
         }
         if (!shard && (same > 1u || (!take_all && fx == fth))) s_misc[3] = 1;
-        fo[rank] = ((uint64_t)(uint32_t)x << 32) | bits_of((uint32_t)(x >> 32));
+        fo[rank] = make_entry((uint32_t)x, bits_of_key((uint32_t)(x >> 32)));
       }
       __syncthreads();
       ok = s_misc[3] == 0;
@@ -592,8 +591,8 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_finalize_kernel(const Fi
     if (tid == 0) {
       uint64_t *__restrict__ hdr = a.final_out + (size_t)q * a.final_stride;
       const uint32_t listed = a.emit ? (uint32_t)min((int64_t)(base + m_new), a.list_cap) : 0u;
-      hdr[0] = (uint64_t)listed | ((uint64_t)f_all << 32);
-      hdr[1] = (uint64_t)(ok ? n_sel : 0u) | ((uint64_t)(ok ? 0u : 1u) << 32);
+      hdr[0] = header_word(listed, f_all);
+      hdr[1] = header_word(ok ? n_sel : 0u, ok ? 0u : 1u);
       if (shard) hdr[2] = (ok && !take_all) ? (uint64_t)th1 : 0ull;
       if (a.done_flag) {
         // the next call's chain starts without a copy that would reset the control words: leave them clean

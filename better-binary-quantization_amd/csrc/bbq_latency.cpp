@@ -7,8 +7,11 @@ using namespace bbq;
 
 namespace {
 
-// waits for the sequence word the last finalize launch of a latency chain raises in mapped host memory (polling: no event, no copy)
-int wait_latency_answer(DeviceCtx *ctx, Slot &s, uint64_t seq) {
+// behind the last launch of a chain: the event that ends it, then the wait for the sequence word that launch raises in mapped host
+// memory (polling: no copy) - the answer block it left is there when this returns BBQ_OK
+int await_latency_answer(DeviceCtx *ctx, Slot &s, uint64_t seq) {
+  HIPCHK(hipEventRecord(s.ev_done, s.stream));
+  s.fl.timed = false;
   volatile uint64_t *flag = ctx->h_lat;
   for (int64_t spin = 0; spin < (1ll << 31); ++spin) {
     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return BBQ_OK;
@@ -22,11 +25,13 @@ int wait_latency_answer(DeviceCtx *ctx, Slot &s, uint64_t seq) {
   return fail(BBQ_ERR_HIP, "latency path: the device finished without an answer");
 }
 
-// the LatScanArgs both latency chains sweep the main storage with: the slot's control words and list, the query in the arguments
-static LatScanArgs lat_scan_args(const BatchCtx &c, const BatchCtx &cs, Slot &s) {
+// what both latency chains sweep the main storage with: the slot's control words and list, the query (*resident_bytes: of a sweep over all rows)
+static LatScanArgs lat_scan_args(const SearchCall &c, Slot &s, int64_t *resident_bytes = nullptr) {
   bbq_index *ix = c.ix;
   LatScanArgs a{};
-  a.idx = launch_view(ix, ix->main);
+  const LaunchView lv = launch_view(ix, ix->main);
+  if (resident_bytes) *resident_bytes = lv.resident_bytes;
+  a.idx = lv.view;
   a.row_id_base = ix->main.row_id_base;
   a.theta = s.d_theta;
   a.flags = s.d_flags;
@@ -34,34 +39,21 @@ static LatScanArgs lat_scan_args(const BatchCtx &c, const BatchCtx &cs, Slot &s)
   a.append_count = s.d_append_counts;
   a.list = s.d_lists;
   a.list_cap = s.list_cap;
-  fill_query(ix, reinterpret_cast<uint8_t *>(a.planes), &a.p, c.qquant, c.qcorr, cs.planes, cs.one_bit, cs.sim);
+  fill_query(ix, reinterpret_cast<uint8_t *>(a.planes), &a.p, c.qquant, c.qcorr, c.planes, c.one_bit, c.sim);
   return a;
 }
 
-// the header the last finalize launch of a latency chain leaves in mapped host memory: {list count, flags}, {answer entries, replay}
-struct LatAnswer {
-  const uint64_t *hdr = nullptr;
-  uint32_t listed = 0, flags = 0, m = 0, replay = 0;
-  LatAnswer() = default;
-  explicit LatAnswer(const DeviceCtx *ctx)
-      : hdr(ctx->h_lat + kLatAnswerOffset), listed((uint32_t)hdr[0]), flags((uint32_t)(hdr[0] >> 32)), m((uint32_t)hdr[1]), replay((uint32_t)(hdr[1] >> 32)) {}
-  // the answer proven on the device (the m entries behind the header) goes to the caller
-  void take(bbq_index *ix, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) const {
-    for (uint32_t j = 0; j < m; ++j) {
-      const uint64_t e = hdr[2 + j];
-      const uint32_t bits = (uint32_t)e;
-      out_idx[j] = (int32_t)(uint32_t)(e >> 32);
-      memcpy(&out_score[j], &bits, 4);
-    }
-    out_n[0] = m;
-    ix->stats.candidates += listed;
-    *done = true;
-  }
-};
+// the answer the device proved (the entries behind header h of the block in mapped host memory) goes to the caller
+void take_answer(bbq_index *ix, const uint64_t *block, const AnswerHeader &h, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) {
+  unpack_entries(block + 2, h.count, out_idx, out_score);
+  out_n[0] = h.count;
+  ix->stats.candidates += h.listed;
+  *done = true;
+}
 
 // the chain's slot gets the workspace of the plan at hand and all-zero control words
-int prepare_latency_slot(bbq_index *ix, Slot &s) {
-  int rc = ensure_slot(ix, s, 1, true);
+int prepare_latency_slot(const SearchCall &c, Slot &s) {
+  int rc = ensure_slot(c, s, 1, true);
   if (rc != BBQ_OK) return rc;
   if (!s.ctrl_clean) {  // the slot's last user was not a latency chain
     HIPCHK(hipMemsetAsync(s.d_block, 0, (size_t)s.ctrl_bytes, s.stream));
@@ -79,16 +71,6 @@ void answer_to_host(FinalizeArgs &f, DeviceCtx *ctx, int64_t final_k, uint64_t s
   f.seq = seq;
 }
 
-// behind the last launch of a chain: the event that ends it, the wait for its sequence word, the header it left
-int await_latency_answer(DeviceCtx *ctx, Slot &s, uint64_t seq, LatAnswer *r) {
-  HIPCHK(hipEventRecord(s.ev_done, s.stream));
-  int rc = wait_latency_answer(ctx, s, seq);
-  if (rc != BBQ_OK) return rc;
-  *r = LatAnswer(ctx);
-  s.timed = false;
-  return BBQ_OK;
-}
-
 }  // namespace
 
 namespace bbq {
@@ -98,13 +80,13 @@ namespace bbq {
 // and nothing in front of the large sweep but the two small ones.  The list is every row above the threshold, not a heap history: a
 // query whose answer the device cannot prove (equal scores, NaN, more candidates than the selection holds) is handed to the
 // segmented chain (*done = false), which replays it exactly.
-int search_latency_presampled(const BatchCtx &c, const BatchCtx &cs, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) {
+int search_latency_presampled(const SearchCall &c, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) {
   bbq_index *ix = c.ix;
-  const Plan &p = ix->plan;
+  const Plan &p = *c.plan;
   *done = false;
   const int64_t N = ix->main.view.n_rows, k2 = p.final_k;
-  if (!ix->opt_latency_presample || !ix->opt_latency_fused || ix->has_pilot || ix->opt_share != 1 || !p.latency ||
-      k2 < 1 || k2 > kFinalSelectMax || N < 262144 || !latency_path_supported(ix->main.view, cs.planes))
+  if (!ix->opt_latency_presample || !ix->opt_latency_fused || ix->has_pilot || c.share != 1 || !p.latency ||
+      k2 < 1 || k2 > kFinalSelectMax || N < 262144 || !latency_path_supported(ix->main.view, c.planes))
     return BBQ_OK;
   // sample enough rows for ~6000 candidates in the sweep (the selection holds kFinalizeKeyCap of them)
   int64_t P = ((k2 + 2) * N / 6000 + kChunkRows - 1) / kChunkRows * kChunkRows;
@@ -119,93 +101,83 @@ int search_latency_presampled(const BatchCtx &c, const BatchCtx &cs, int32_t *ou
   const int64_t n_keys = P / kTileRows * per_wave;
   if (n_keys > kLatPreKeys || n_keys < k2 + 2) return BBQ_OK;
   Slot &s = ix->slots[0];
-  int rc = prepare_latency_slot(ix, s);
+  int rc = prepare_latency_slot(c, s);
   if (rc != BBQ_OK) return rc;
   DeviceCtx *ctx = ix->ctx;
   hipStream_t st = s.stream;
-  ix->sweep_resident_acc = 0;
-  LatScanArgs a = lat_scan_args(c, cs, s);
-  ix->stats.resident_bytes = ix->sweep_resident_acc;  // the one sweep over all rows
+  LatScanArgs a = lat_scan_args(c, s, &ix->stats.resident_bytes);  // of the one sweep over all rows, not sweep + prefix
   LatPreArgs pre{};
-  pre.idx = launch_view(ix, ix->main);
+  pre.idx = launch_view(ix, ix->main).view;
   pre.rows = (int32_t)P;
   pre.per_wave = per_wave;
   pre.pre_keys = ctx->d_pre_keys;
   pre.flags = s.d_flags;
   pre.p = a.p;
   memcpy(pre.planes, a.planes, sizeof pre.planes);
-  HIPCHK(launch_lat_pre(pre, cs.planes, st));
+  HIPCHK(launch_lat_pre(pre, c.planes, st));
   // rank k2 + 2: the sweep must list at least k2 + 1 rows for the selection to see the boundary of the answer
   HIPCHK(launch_lat_select(ctx->d_pre_keys, (int)n_keys, (int)(k2 + 2), s.d_theta, st));
   a.chunk_begin = 0;
   a.n_chunks = (int32_t)ix->main.n_chunks();
   a.first = 0;
-  HIPCHK(launch_lat_scan(a, cs.planes, st));
+  HIPCHK(launch_lat_scan(a, c.planes, st));
   const uint64_t seq = ++ctx->lat_seq;
-  FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, cs.k);
+  FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, c.k_dev);
   f.emit = 1;
   answer_to_host(f, ctx, k2, seq);
   HIPCHK(launch_finalize(f, 1, st));
-  LatAnswer r;
-  rc = await_latency_answer(ctx, s, seq, &r);
+  rc = await_latency_answer(ctx, s, seq);
   if (rc != BBQ_OK) return rc;
+  const AnswerHeader r(ctx->h_lat + kLatAnswerOffset);
   // The list holds the rows ABOVE the sampled threshold only, so the selection's "take every listed row" case (total <= k2) proves
   // nothing here: equal keys at ranks k2+1 / k2+2 of the sample can leave fewer than k2 rows above it (N >= 262144 > k2, so a
   // complete answer has exactly k2 entries).  Anything else goes to the segmented chain.
-  if (r.flags != 0 || r.replay != 0 || r.m != (uint32_t)k2) return BBQ_OK;
-  r.take(ix, out_idx, out_score, out_n, done);
+  if (r.flags != 0 || r.needs_replay != 0 || r.count != (uint32_t)k2) return BBQ_OK;
+  take_answer(ix, ctx->h_lat + kLatAnswerOffset, r, out_idx, out_score, out_n, done);
   return BBQ_OK;
 }
 
 // one query, no copies: every sweep takes the query from its kernel arguments (bbq_latency_kernels.hip), the last finalize launch
 // writes the answer to mapped host memory and raises the sequence word this thread polls.  Returns BBQ_OK with *done = false when the
 // call has to take the general path (index shape without an instantiation).
-int search_latency_chain(const BatchCtx &c, const BatchCtx &cs, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) {
+int search_latency_chain(const SearchCall &c, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done) {
   bbq_index *ix = c.ix;
-  const Plan &p = ix->plan;
+  const Plan &p = *c.plan;
   *done = false;
-  if (!ix->opt_latency_fused || !ix->opt_append_last || ix->has_pilot || ix->opt_share != 1 || !p.latency ||
-      p.final_k < 1 || p.final_k > kFinalSelectMax || p.segs.empty() || !p.segs[0].dense || !latency_path_supported(ix->main.view, cs.planes))
+  if (!ix->opt_latency_fused || !ix->opt_append_last || ix->has_pilot || c.share != 1 || !p.latency ||
+      p.final_k < 1 || p.final_k > kFinalSelectMax || p.segs.empty() || !p.segs[0].dense || !latency_path_supported(ix->main.view, c.planes))
     return BBQ_OK;
   for (size_t i = 1; i < p.segs.size(); ++i)
     if (p.segs[i].dense || p.segs[i].storage != 1) return BBQ_OK;
   Slot &s = ix->slots[0];
-  int rc = prepare_latency_slot(ix, s);
+  int rc = prepare_latency_slot(c, s);
   if (rc != BBQ_OK) return rc;
   DeviceCtx *ctx = ix->ctx;
   hipStream_t st = s.stream;
-  LatScanArgs a = lat_scan_args(c, cs, s);
+  LatScanArgs a = lat_scan_args(c, s);
   const uint64_t seq = ++ctx->lat_seq;
   for (size_t i = 0; i < p.segs.size(); ++i) {
     const Segment &g = p.segs[i];
     a.chunk_begin = g.chunk_begin;
     a.n_chunks = (int32_t)g.n_chunks;
     a.first = i == 0 ? 1 : 0;
-    HIPCHK(launch_lat_scan(a, cs.planes, st));
-    FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, cs.k);
+    HIPCHK(launch_lat_scan(a, c.planes, st));
+    FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, c.k_dev);
     f.emit = 1;
     f.need_theta = i + 1 < p.segs.size() ? 1 : 0;
     if (i + 1 == p.segs.size()) answer_to_host(f, ctx, p.final_k, seq);
     HIPCHK(launch_finalize(f, 1, st));
   }
-  LatAnswer r;
-  rc = await_latency_answer(ctx, s, seq, &r);
+  rc = await_latency_answer(ctx, s, seq);
   if (rc != BBQ_OK) return rc;
-  if (r.flags == 0 && r.replay == 0) {  // answered on the device
-    r.take(ix, out_idx, out_score, out_n, done);
+  const AnswerHeader r(ctx->h_lat + kLatAnswerOffset);
+  if (r.flags == 0 && r.needs_replay == 0) {  // answered on the device
+    take_answer(ix, ctx->h_lat + kLatAnswerOffset, r, out_idx, out_score, out_n, done);
     return BBQ_OK;
   }
-  // equal scores in or at the edge of the answer (or a flagged query): hand over to the general path's collection - the list on the
-  // device is complete and it is this slot's
-  s.h_final[0] = (uint64_t)r.listed | ((uint64_t)r.flags << 32);
-  s.h_final[1] = (uint64_t)1 << 32;
-  s.busy = true;
-  s.nq = 1;
-  s.q_first = 0;
-  s.final_used = true;
-  s.appended = true;
-  rc = begin_replay(c, s, out_idx, out_score, out_n);
-  if (rc == BBQ_OK) rc = finish_replay(c, s, out_idx, out_score, out_n);
+  // equal scores in or at the edge of the answer (or a flagged query): the general path's collection steps for this one query - the
+  // list on the device is complete and it is this slot's
+  rc = replay_listed_query(c, s, r.listed, r.flags, out_idx, out_score, out_n);
   if (rc != BBQ_OK) return rc;
   *done = true;
   return BBQ_OK;

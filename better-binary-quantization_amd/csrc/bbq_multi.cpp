@@ -24,59 +24,17 @@
 #include <string.h>
 #include <algorithm>
 #include <condition_variable>
-#include <deque>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 #include "bbq_host.h"
+#include "bbq_workqueue.h"
 
 using namespace bbq;
 
 namespace bbq {
-
-// a persistent host thread per shard: spawning threads per call would cost more than a small sweep
-class ShardWorker {
- public:
-  ShardWorker() : th_([this] { run(); }) {}
-  ~ShardWorker() {
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    th_.join();
-  }
-  void post(std::function<void()> f) {
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      q_.push_back(std::move(f));
-    }
-    cv_.notify_one();
-  }
-
- private:
-  void run() {
-    for (;;) {
-      std::function<void()> f;
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [this] { return stop_ || !q_.empty(); });
-        if (q_.empty()) return;
-        f = std::move(q_.front());
-        q_.pop_front();
-      }
-      f();
-    }
-  }
-  std::mutex m_;
-  std::condition_variable cv_;
-  std::deque<std::function<void()>> q_;
-  bool stop_ = false;
-  std::thread th_;
-};
 
 struct ShardBuf {  // one round's output of one shard: answers + packed lists on the device, answers landed in pinned host memory
   DevBuf<uint64_t> d_packed, d_answers;
@@ -101,7 +59,7 @@ struct MultiShard {
   int device = 0;
   int64_t r0 = 0, r1 = 0;
   ShardBuf buf[2];
-  std::unique_ptr<ShardWorker> worker;
+  std::unique_ptr<WorkQueue> worker;  // a persistent host thread per shard: spawning threads per call would cost more than a small sweep
 };
 
 struct MultiState {
@@ -335,7 +293,7 @@ int multi_search_batch(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, 
       }
       for (int32_t q = 0; q < nq && rc_all == BBQ_OK; ++q) {
         if (status[(size_t)q] == 0) {  // answered from the shards' answers: the entries that were merged count as its candidates
-          for (int s = 0; s < S; ++s) ix->stats.candidates += (int64_t)(uint32_t)blocks[(size_t)s][(size_t)q * (size_t)strides[(size_t)s] + 1];
+          for (int s = 0; s < S; ++s) ix->stats.candidates += AnswerHeader(blocks[(size_t)s] + (size_t)q * (size_t)strides[(size_t)s]).count;
           continue;
         }
         const int64_t qi = q0 + q;
@@ -451,7 +409,7 @@ int multi_assemble(bbq_index *const *shards, const int32_t *devices, int32_t n_s
     sh.device = devices[s];
     sh.r0 = shards[s]->row_base;
     sh.r1 = sh.r0 + shards[s]->n_rows;
-    sh.worker.reset(new ShardWorker());
+    sh.worker.reset(new WorkQueue(1));
     ms->shards.push_back(std::move(sh));
   }
   adopt_shard_geometry(ix.get(), ms.get());
@@ -559,7 +517,7 @@ int bbq_index_create_multi_opts(const uint8_t *codes, const double *corr, int64_
     int rc = bbq_index_create_shard_opts(codes ? codes + r0 * row_bytes : nullptr, corr ? corr + r0 * 4 : nullptr, r1 - r0, dim, index_bits, centroid_dp,
                                          r0, P > 0 ? codes : nullptr, P > 0 ? corr : nullptr, P, sh.device, &shard_opts, &sh.ix);
     if (rc != BBQ_OK) return bail(rc);
-    sh.worker.reset(new ShardWorker());
+    sh.worker.reset(new WorkQueue(1));
     ms->shards.push_back(std::move(sh));
   }
   adopt_shard_geometry(ix.get(), ms.get());

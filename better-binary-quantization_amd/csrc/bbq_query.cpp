@@ -104,7 +104,7 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
 // words.  For 32-dim word g, half h, dword c, byte i the kernel extracts bit p = 4h + c + 8i of the little-endian word, which is row
 // byte 4g + (p >> 3), bit (p & 7), i.e. dimension 32g + 8*(p >> 3) + 7 - (p & 7) (MSB-first packing,
 // src/optimizedScalarQuantizer.ts:420-446).  Layout: [group][g][h][n][16 B], n = query in its group of 32.
-void fill_query_mfma(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q) {
+static void fill_query_mfma(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q) {
   const int words = ix->w16 * 4, group = q_in_batch / 32, n = q_in_batch % 32;
   uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->w16, false);
   for (int g = 0; g < words; ++g)
@@ -132,7 +132,7 @@ static uint32_t fp6_code_of_eighths(int eighths) {
   return ((uint32_t)e << 3) | (uint32_t)((eighths >> (e - 1)) - 8);   // exact: the low e - 1 bits of eighths are zero for q <= 15
 }
 
-void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q, int scale8) {
+static void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q, int scale8) {
   const int steps = ix->w16 * 2, group = q_in_batch / 32, n = q_in_batch % 32;
   uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->w16, true);
   uint8_t *gb2 = gb + (size_t)steps * 2 * 32 * 16;
@@ -163,6 +163,37 @@ void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const
       memcpy(gb + (((size_t)g * 2 + h) * 32 + n) * 16, bits, 16);
       memcpy(gb2 + (((size_t)g * 2 + h) * 32 + n) * 8, bits + 16, 8);
     }
+}
+
+// second copy of a sub-batch's queries as MFMA operands in fragment order + per-group maxima for the rows' magnitude budget
+MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryParams *hq, int64_t q_first, int nq, size_t bytes) {
+  const bbq_index *ix = c.ix;
+  MfmaStage m{};
+  m.fp = c.maxq <= 15;  // queryBits <= 4: rows as FP4, queries as FP6 - 64 dimensions per MFMA in the time the int8 form takes for 32
+  m.scale8 = c.maxq <= 3 ? 8 : c.maxq <= 7 ? 4 : 2;  // products of scale8 / 8 * q: the accumulator's quarter-unit grain is 1, 1/2 or 1/4 of a qcDist unit
+  const int groups = (nq + 31) / 32;
+  m.off_qbytes = (bytes + 15) / 16 * 16;
+  const size_t qbytes_len = (size_t)groups * (size_t)mfma_query_bytes_per_group(ix->w16, m.fp);
+  m.off_qmax = m.off_qbytes + qbytes_len;
+  m.bytes = m.off_qmax + (size_t)groups * 16;
+  memset(h_qbuf + m.off_qbytes, 0, qbytes_len);
+  float *qm = reinterpret_cast<float *>(h_qbuf + m.off_qmax);
+  for (int i = 0; i < 4 * groups; ++i) qm[i] = 0.f;
+  for (int i = 0; i < nq; ++i) {
+    const uint8_t *qv = c.qquant + (size_t)(q_first + i) * ix->dim;
+    if (m.fp) fill_query_mfma_fp(ix, h_qbuf + m.off_qbytes, i, qv, m.scale8);
+    else fill_query_mfma(ix, h_qbuf + m.off_qbytes, i, qv);
+    float *g = qm + 4 * (i / 32);
+    // upper bounds (rounded up) of the group's |ay / ly|, |y1|, 1 / (cs * ly) and of the sum of a query's values (the largest
+    // qcDist there can be, whatever y1 the caller passed)
+    double qsum = 0;
+    for (int d = 0; d < ix->dim; ++d) qsum += qv[d];
+    g[0] = std::max(g[0], (float)(fabs(hq[i].ay / hq[i].ly) * 1.000001));
+    g[1] = std::max(g[1], (float)(fabs(hq[i].y1) * 1.000001));
+    g[2] = std::max(g[2], (float)(1.0 / ((c.sim == 0 ? 2.0 : 1.0) * hq[i].ly) * 1.000001));
+    g[3] = std::max(g[3], (float)(qsum * 1.000001));
+  }
+  return m;
 }
 
 // The matrix-core sweep tests "score > threshold" as an inequality on the integer dot product (bbq_mfma_kernels.hip), which divides by

@@ -99,6 +99,25 @@ int64_t HeapReplay::drain_ascending(int32_t *out_tag, double *out_score) {
 
 }  // namespace bbq
 
+// offers the entries of one list to the heap; false at the first row that does not ascend (*prev: the last row offered, -1 none)
+static bool offer_ascending(bbq::HeapReplay &h, const bbq_cand *l, int64_t n, int64_t *prev) {
+  for (int64_t j = 0; j < n; ++j) {
+    const int64_t row = bbq::entry_row(l[j]);
+    if (row <= *prev) return false;
+    *prev = row;
+    h.offer(bbq::entry_score(l[j]), (int32_t)row);
+  }
+  return true;
+}
+
+// work(lo, hi) over [0, n) on T threads (T <= 1: on this one)
+template <class F> static void run_split(int T, int32_t n, F &work) {
+  if (T <= 1) return work(0, n);
+  std::vector<std::thread> th;
+  for (int t = 0; t < T; ++t) th.emplace_back(work, (int32_t)((int64_t)n * t / T), (int32_t)((int64_t)n * (t + 1) / T));
+  for (auto &x : th) x.join();
+}
+
 extern "C" {
 
 const char *bbq_last_error(void) { return bbq::last_error_cstr(); }
@@ -113,25 +132,12 @@ int bbq_replay(int32_t n_lists, const bbq_cand *const *lists, const int64_t *cou
   *out_n = 0;
   if (k == 0) return BBQ_OK;
   bbq::HeapReplay h(k, n_total);
-  uint32_t prev = 0;
-  bool first = true;
-  for (int32_t i = 0; i < n_lists; ++i) {
-    const bbq_cand *l = lists[i];
-    for (int64_t j = 0; j < counts[i]; ++j) {
-      const uint32_t row = (uint32_t)(l[j] >> 32);
-      if (!first && row <= prev) return bbq::fail(BBQ_ERR_INVALID_ARG, "bbq_replay: candidates not in ascending row order");
-      prev = row;
-      first = false;
-      const uint32_t bits = (uint32_t)l[j];
-      float s;
-      memcpy(&s, &bits, 4);
-      h.offer(s, (int32_t)row);
-    }
-  }
+  int64_t prev = -1;
+  for (int32_t i = 0; i < n_lists; ++i)
+    if (!offer_ascending(h, lists[i], counts[i], &prev)) return bbq::fail(BBQ_ERR_INVALID_ARG, "bbq_replay: candidates not in ascending row order");
   *out_n = h.finish(out_idx, out_score);
   return BBQ_OK;
 }
-
 
 int bbq_replay_batch(int32_t n_sources, const bbq_cand *const *packed, const int64_t *const *offsets, int32_t n_queries,
                      int64_t n_total, int64_t k, int32_t n_threads, int32_t *out_idx, float *out_score, int64_t *out_n) {
@@ -146,52 +152,24 @@ int bbq_replay_batch(int32_t n_sources, const bbq_cand *const *packed, const int
   auto work = [&](int32_t lo, int32_t hi) {
     for (int32_t q = lo; q < hi; ++q) {
       bbq::HeapReplay h(k, n_total);
-      uint32_t prev = 0;
-      bool first = true;
-      for (int32_t s = 0; s < n_sources && !bad[(size_t)q]; ++s) {
-        const bbq_cand *l = packed[s] + offsets[s][q];
-        const int64_t cnt = offsets[s][q + 1] - offsets[s][q];
-        for (int64_t j = 0; j < cnt; ++j) {
-          const uint32_t row = (uint32_t)(l[j] >> 32);
-          if (!first && row <= prev) { bad[(size_t)q] = 1; break; }
-          prev = row;
-          first = false;
-          const uint32_t bits = (uint32_t)l[j];
-          float sc;
-          memcpy(&sc, &bits, 4);
-          h.offer(sc, (int32_t)row);
-        }
-      }
+      int64_t prev = -1;
+      for (int32_t s = 0; s < n_sources && !bad[(size_t)q]; ++s)
+        if (!offer_ascending(h, packed[s] + offsets[s][q], offsets[s][q + 1] - offsets[s][q], &prev)) bad[(size_t)q] = 1;
       out_n[q] = h.finish(out_idx + (int64_t)q * k, out_score + (int64_t)q * k);
     }
   };
   int T = n_threads > 0 ? n_threads : 1;
   if (T > n_queries) T = n_queries;
-  if (T <= 1) {
-    work(0, n_queries);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t) th.emplace_back(work, (int32_t)((int64_t)n_queries * t / T), (int32_t)((int64_t)n_queries * (t + 1) / T));
-    for (auto &x : th) x.join();
-  }
+  run_split(T, n_queries, work);
   for (int32_t q = 0; q < n_queries; ++q)
     if (bad[(size_t)q]) return bbq::fail(BBQ_ERR_INVALID_ARG, "bbq_replay_batch: candidates of query %d not in ascending row order", q);
   return BBQ_OK;
 }
 
-
-static inline uint32_t key_of_score_bits(uint32_t b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-static inline float score_of_key(uint32_t key) {
-  const uint32_t b = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-  float f;
-  memcpy(&f, &b, 4);
-  return f;
-}
-
 uint32_t bbq_key_of_score(float score) {
   uint32_t b;
   memcpy(&b, &score, 4);
-  return key_of_score_bits(b);
+  return bbq::key_of_bits(b);
 }
 
 // The global answer from the shards' answer blocks (include/bbq.h, bbq_shard_scan_begin).  Every source s lists its own rows above
@@ -219,11 +197,12 @@ int bbq_merge_answers(int32_t n_sources, const uint64_t *const *answers, const i
       uint32_t cut = 0, flags = 0, unproven = 0;
       for (int32_t s = 0; s < n_sources; ++s) {
         const uint64_t *b = answers[s] + (size_t)q * (size_t)strides[s];
-        flags |= (uint32_t)(b[0] >> 32);
-        unproven |= (uint32_t)(b[1] >> 32);
-        const uint64_t m = (uint32_t)b[1];
+        const bbq::AnswerHeader hd(b);
+        flags |= hd.flags;
+        unproven |= hd.needs_replay;
+        const uint64_t m = hd.count;
         if ((int64_t)m + 3 > strides[s]) { bad[(size_t)q] = 1; unproven = 1; }
-        cut = std::max(cut, (uint32_t)b[2]);
+        cut = std::max(cut, bbq::shard_cut(b));
         head[(size_t)s] = b + 3;
         end[(size_t)s] = b + 3 + ((int64_t)m + 3 > strides[s] ? 0 : m);
       }
@@ -236,7 +215,7 @@ int bbq_merge_answers(int32_t n_sources, const uint64_t *const *answers, const i
         uint32_t best_key = 0;
         for (int32_t s = 0; s < n_sources; ++s) {
           if (head[(size_t)s] == end[(size_t)s]) continue;
-          const uint32_t key = key_of_score_bits((uint32_t)*head[(size_t)s]);
+          const uint32_t key = bbq::key_of_bits(bbq::entry_bits(*head[(size_t)s]));
           if (best < 0 || key > best_key) { best = s; best_key = key; }
         }
         if (best < 0 || best_key <= cut) break;
@@ -244,27 +223,18 @@ int bbq_merge_answers(int32_t n_sources, const uint64_t *const *answers, const i
       }
       const int64_t have = (int64_t)sel.size();
       bool ok = have >= k2;
-      auto fscore = [](uint64_t e) { const uint32_t b = (uint32_t)e; float f; memcpy(&f, &b, 4); return f; };
-      for (int64_t j = 0; ok && j + 1 < have; ++j) ok = fscore(sel[(size_t)j]) != fscore(sel[(size_t)j + 1]);  // sorted: equal scores are neighbours (+0 / -0 too)
-      if (ok && have == k2 && cut != 0u) ok = fscore(sel[(size_t)k2 - 1]) != score_of_key(cut);       // the boundary is the cut itself
+      using bbq::entry_score;
+      for (int64_t j = 0; ok && j + 1 < have; ++j) ok = entry_score(sel[(size_t)j]) != entry_score(sel[(size_t)j + 1]);  // sorted: equal scores are neighbours (+0 / -0 too)
+      if (ok && have == k2 && cut != 0u) ok = entry_score(sel[(size_t)k2 - 1]) != entry_score(bbq::bits_of_key(cut));  // the boundary is the cut itself
       if (!ok) { status[q] = 1; continue; }
-      for (int64_t j = 0; j < k2; ++j) {
-        out_idx[(int64_t)q * k + j] = (int32_t)(uint32_t)(sel[(size_t)j] >> 32);
-        out_score[(int64_t)q * k + j] = fscore(sel[(size_t)j]);
-      }
+      bbq::unpack_entries(sel.data(), k2, out_idx + (int64_t)q * k, out_score + (int64_t)q * k);
       out_n[q] = k2;
       status[q] = 0;
     }
   };
   int T = n_threads > 0 ? n_threads : 1;
   if (T > n_queries / 64) T = std::max(1, n_queries / 64);  // a query merges in a few microseconds: threads only pay for large batches
-  if (T <= 1) {
-    work(0, n_queries);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t) th.emplace_back(work, (int32_t)((int64_t)n_queries * t / T), (int32_t)((int64_t)n_queries * (t + 1) / T));
-    for (auto &x : th) x.join();
-  }
+  run_split(T, n_queries, work);
   for (int32_t q = 0; q < n_queries; ++q)
     if (bad[(size_t)q]) return bbq::fail(BBQ_ERR_INVALID_ARG, "bbq_merge_answers: query %d: an answer block claims more entries than its stride holds", q);
   return BBQ_OK;

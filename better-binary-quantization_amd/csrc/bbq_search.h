@@ -1,4 +1,4 @@
-// bbq_search.h - what the search-side translation units share on top of bbq_host.h: the context of one call, and the functions
+// bbq_search.h - what the search-side translation units share on top of bbq_host.h: the one object of a call, and the functions
 // that cross a file boundary (their comments stand at the definitions).
 #pragma once
 #include "bbq_host.h"
@@ -6,13 +6,20 @@
 #pragma GCC visibility push(hidden)  // internal: none of this joins the library's dynamic symbols
 namespace bbq {
 
-struct BatchCtx {
+// One search call: the queries, how they are scored, its two ranks and its plan.  Every function below takes it; a step that runs with
+// another sweep share (finish_replay's re-sweep) passes a copy.
+struct SearchCall {
   bbq_index *ix;
   const uint8_t *qquant;
   const double *qcorr;
   int planes, one_bit, sim;
-  int64_t k;
-  int maxq = 255;  // largest quantized query value of the call (the MFMA sweep needs <= 127)
+  int64_t k_out;               // the caller's k: strides the outputs, sizes the replayed heap
+  int64_t k_dev = 0;           // the rank the device selects thresholds with: min(k, rows), + 1 when the device selects the answer itself
+  int maxq = 255;              // largest quantized query value of the call (the MFMA sweep needs <= 127)
+  int share;                   // queries per row load of the sparse sweeps of this enqueue: the index's sweep_share unless a step overrides it
+  const Plan *plan = nullptr;  // the call's segment plan; null in a call that only takes the dense path
+  SearchCall(bbq_index *ix, const uint8_t *qquant, const double *qcorr, int planes, int32_t query_bits, int32_t sim, int64_t k)
+      : ix(ix), qquant(qquant), qcorr(qcorr), planes(planes), one_bit(query_bits == 1 ? 1 : 0), sim(sim), k_out(k), share(ix->opt_share) {}
 };
 
 // outputs of a sharded scan: the per-query lists live in the index's own buffers and (optionally) the shard-local answers go straight
@@ -31,27 +38,29 @@ int64_t query_data_bytes(const bbq_index *ix, int planes);
 int planes_of_call(const bbq_index *ix, const uint8_t *q, int64_t count, int one_bit);
 void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const uint8_t *q, const double *qc, int planes,
                 int one_bit, int sim);
-void fill_query_mfma(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q);
-void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q, int scale8);
+// the sub-batch's queries once more as matrix-core operands + group maxima behind the `bytes` already staged in h_qbuf
+struct MfmaStage { bool fp; int scale8; size_t off_qbytes, off_qmax, bytes; };
+MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryParams *hq, int64_t q_first, int nq, size_t bytes);
 bool mfma_query_ok(const QueryParams &p);
 int validate_query_args(const bbq_index *ix, int32_t nq, const uint8_t *qquant, const double *qcorr, int32_t query_bits,
                         int32_t sim, int64_t k, bool values_pending = false);
 
 // ---- bbq_core.cpp
 int effective_batch(const bbq_index *ix, int64_t n_queries = 0);
-void build_plan(bbq_index *ix, int64_t k, int64_t final_k = 0, bool latency = false);
-int ensure_slot(bbq_index *ix, Slot &s, int nq, bool own_lists);
+Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k = 0, bool latency = false);
+int ensure_slot(const SearchCall &c, Slot &s, int nq, bool own_lists);
 FinalizeArgs slot_finalize_args(const Slot &s, uint64_t *lists, int32_t *list_counts, int64_t list_cap, bool appended, int64_t k);
-int enqueue_subbatch(const BatchCtx &c, Slot &s, int64_t q_first, int nq, const ExtOut *ext);
+int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, const ExtOut *ext);
 void account_timing(bbq_index *ix, Slot &s);
-int begin_replay(const BatchCtx &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n);
-int finish_replay(const BatchCtx &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n);
+int begin_replay(const SearchCall &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n);
+int finish_replay(const SearchCall &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n);
+int replay_listed_query(const SearchCall &c, Slot &s, uint32_t listed, uint32_t flags, int32_t *out_idx, float *out_score, int64_t *out_n);
 int drain(bbq_index *ix);
 // ---- bbq_latency.cpp: *done = false with BBQ_OK sends the call on to the next, more general path
-int search_latency_presampled(const BatchCtx &c, const BatchCtx &cs, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done);
-int search_latency_chain(const BatchCtx &c, const BatchCtx &cs, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done);
+int search_latency_presampled(const SearchCall &c, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done);
+int search_latency_chain(const SearchCall &c, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done);
 // ---- bbq_dense.cpp
-int dense_search_one(const BatchCtx &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n);
+int dense_search_one(const SearchCall &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n);
 
 }  // namespace bbq
 #pragma GCC visibility pop

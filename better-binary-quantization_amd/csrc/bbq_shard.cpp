@@ -9,11 +9,11 @@ namespace bbq {
 int settle_shard_slots(DeviceCtx *ctx, bbq_index *owner) {
   for (int i = 0; i < kMaxSlots; ++i) {
     Slot &s = ctx->slots[i];
-    if (!s.busy || !s.shard_owner || (owner && s.shard_owner != owner)) continue;
+    if (!s.fl.busy || !s.fl.shard_owner || (owner && s.fl.shard_owner != owner)) continue;
     HIPCHK(hipEventSynchronize(s.ev_done));
-    s.busy = false;
-    account_timing(s.shard_owner, s);
-    s.shard_owner = nullptr;
+    s.fl.busy = false;
+    account_timing(s.fl.shard_owner, s);
+    s.fl.shard_owner = nullptr;
   }
   return BBQ_OK;
 }
@@ -22,15 +22,12 @@ int settle_shard_slots(DeviceCtx *ctx, bbq_index *owner) {
 
 extern "C" {
 
-int64_t bbq_shard_list_cap(const bbq_index *cix, int64_t k) {
-  if (!cix || k <= 0 || cix->multi) return 0;
-  bbq_index *ix = const_cast<bbq_index *>(cix);
+int64_t bbq_shard_list_cap(const bbq_index *ix, int64_t k) {
+  if (!ix || k <= 0 || ix->multi) return 0;
   // the scan runs with rank k + 1 whenever it can leave shard-local answers (k <= kFinalSelectMax): size for that plan
   const int64_t keff = std::min<int64_t>(k, kMaxFastK);
   std::lock_guard<std::mutex> lk(ix->ctx->mu);
-  if (keff <= kFinalSelectMax) build_plan(ix, keff + 1, keff);
-  else build_plan(ix, keff);
-  return ix->plan.list_cap;
+  return (keff <= kFinalSelectMax ? build_plan(ix, keff + 1, keff) : build_plan(ix, keff)).list_cap;
 }
 
 int bbq_shard_scan_begin(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim,
@@ -49,12 +46,13 @@ int bbq_shard_scan_begin(bbq_index *ix, int32_t n_queries, const uint8_t *qquant
   std::lock_guard<std::mutex> lk(ix->ctx->mu);
   HIPCHK(hipSetDevice(ix->device));
   if (ix->shard_begun - ix->shard_waited >= 2) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan_begin: two batches are already in flight on this index (wait for one first)");
-  BatchCtx c{ix, qquant, qcorr, planes_of_call(ix, qquant, (int64_t)n_queries * ix->dim, query_bits == 1), query_bits == 1 ? 1 : 0, sim, k};
+  SearchCall c(ix, qquant, qcorr, planes_of_call(ix, qquant, (int64_t)n_queries * ix->dim, query_bits == 1), query_bits, sim, k);
   // with answers the shard runs with rank k + 1, like the single index does: its last finalize launch then knows the (k + 1)-th largest
   // key of everything it has seen (the cut) and the rows above it.  Lists for rank k + 1 are supersets of the lists for rank k.
   const bool answers = dev_answers != nullptr;
-  if (answers) { c.k = k + 1; build_plan(ix, k + 1, k); }
-  else build_plan(ix, k);
+  c.k_dev = answers ? k + 1 : k;
+  const Plan plan = build_plan(ix, c.k_dev, answers ? k : 0);
+  c.plan = &plan;
   bbq_index::ShardSet &set = ix->shard_set[ix->shard_begun & 1];
   if (!set.h_total) {
     HIPCHK(set.done.create(hipEventDisableTiming));
@@ -62,7 +60,7 @@ int bbq_shard_scan_begin(bbq_index *ix, int32_t n_queries, const uint8_t *qquant
   }
   // per-query lists with room for a flood (rows stored cluster by cluster); what travels is packed, so the headroom costs
   // device memory only
-  const int64_t list_cap = ix->plan.list_cap + std::min<int64_t>(ix->plan.flood_cap, 65536);
+  const int64_t list_cap = plan.list_cap + std::min<int64_t>(plan.flood_cap, 65536);
   if (set.q_cap < n_queries || set.list_cap < list_cap) {  // per-query lists the finalize kernels build (the set is idle: its last batch was waited for)
     set.q_cap = 0;  // until both are in place
     HIPCHK(set.d_lists.alloc((size_t)n_queries * (size_t)list_cap));
@@ -82,15 +80,15 @@ int bbq_shard_scan_begin(bbq_index *ix, int32_t n_queries, const uint8_t *qquant
   // keeps working on them while this batch is being enqueued behind
   for (int64_t i = 0; i < nsub; ++i) {
     Slot &s = ix->slots[i % nslots];
-    if (s.busy) {
+    if (s.fl.busy) {
       const hipError_t e = hipEventSynchronize(s.ev_done);
       if (e != hipSuccess) return bail(fail(BBQ_ERR_HIP, "bbq_shard_scan_begin: %s", hipGetErrorString(e)));
-      s.busy = false;
-      account_timing(s.shard_owner ? s.shard_owner : ix, s);
-      s.shard_owner = nullptr;
+      s.fl.busy = false;
+      account_timing(s.fl.shard_owner ? s.fl.shard_owner : ix, s);
+      s.fl.shard_owner = nullptr;
     }
     const int nq = (int)std::min<int64_t>(Q, n_queries - i * Q);
-    rc = ensure_slot(ix, s, nq, false);
+    rc = ensure_slot(c, s, nq, false);
     if (rc != BBQ_OK) return bail(rc);
     ExtOut ext;
     ext.lists = set.d_lists + (size_t)(i * Q) * list_cap;
@@ -102,16 +100,16 @@ int bbq_shard_scan_begin(bbq_index *ix, int32_t n_queries, const uint8_t *qquant
     }
     rc = enqueue_subbatch(c, s, i * Q, nq, &ext);
     if (rc != BBQ_OK) return bail(rc);
-    s.shard_owner = ix;
+    s.fl.shard_owner = ix;
   }
   // the packing runs on the auxiliary stream behind the last sub-batch of every slot this batch has used
   hipStream_t aux = ix->ctx->aux_stream;
   for (int j = 0; j < nslots; ++j)
-    if (ix->slots[j].busy && ix->slots[j].shard_owner == ix) HIPCHK(hipStreamWaitEvent(aux, ix->slots[j].ev_done, 0));
+    if (ix->slots[j].fl.busy && ix->slots[j].fl.shard_owner == ix) HIPCHK(hipStreamWaitEvent(aux, ix->slots[j].ev_done, 0));
   // pack: [nq][list_cap] -> contiguous entries + offsets, what the host framework sends over RCCL
   int64_t *d_total = reinterpret_cast<int64_t *>(set.d_counts + (size_t)n_queries * 2);
   d_total = reinterpret_cast<int64_t *>(((uintptr_t)d_total + 7) & ~(uintptr_t)7);
-  HIPCHK(launch_pack(set.d_counts, set.d_lists, list_cap, ix->plan.list_cap, n_queries, reinterpret_cast<int64_t *>(dev_offsets),
+  HIPCHK(launch_pack(set.d_counts, set.d_lists, list_cap, plan.list_cap, n_queries, reinterpret_cast<int64_t *>(dev_offsets),
                      reinterpret_cast<int32_t *>(dev_flags), d_total, reinterpret_cast<uint64_t *>(dev_packed), packed_cap, aux));
   HIPCHK(hipMemcpyAsync(set.h_total, d_total, 8, hipMemcpyDeviceToHost, aux));
   HIPCHK(hipEventRecord(set.done, aux));

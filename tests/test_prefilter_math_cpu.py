@@ -62,7 +62,7 @@ FORMS = {"int8": dict(S=1.0, ulp=1.0, bias=12582912.0, mag_limit=4000000.0, pass
 
 
 def fp_scale(max_q):
-    """bbq_core.cpp enqueue_subbatch (operands: bbq_query.cpp fill_query_mfma_fp): products of q, q / 2 or q / 4 - the largest the query values leave room for in e2m3"""
+    """bbq_query.cpp stage_queries_mfma (operands: fill_query_mfma_fp): products of q, q / 2 or q / 4 - the largest the query values leave room for in e2m3"""
     return 1.0 if max_q <= 3 else 0.5 if max_q <= 7 else 0.25
 
 
