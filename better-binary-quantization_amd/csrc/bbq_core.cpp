@@ -140,9 +140,8 @@ static void add_storage_segments(const bbq_index *ix, Plan &p, int storage, cons
   }
 }
 
-// k: the rank the device selects thresholds with; final_k > 0: k == final_k + 1 and the last finalize launch selects the answer.
-// A value of its inputs and the index's options: the call that asked for it owns it.
-Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
+// what a plan is built from before its segments: the ranks, the growth and the size of the first segment
+static Plan start_plan(const bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
   Plan p;
   p.k = k;
   p.final_k = final_k;
@@ -150,13 +149,12 @@ Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
   p.latency = latency;
   p.s0 = std::max<int64_t>(ix->opt_s0, (4 * k + kChunkRows - 1) / kChunkRows * kChunkRows);
   p.s0 = std::min<int64_t>(p.s0, 8192);
-  double expected_emit = 0, dummy = 0;
-  if (ix->has_pilot) {
-    add_storage_segments(ix, p, 0, ix->pilot, 0, false, false, dummy);
-    add_storage_segments(ix, p, 1, ix->main, ix->pilot.view.n_rows, true, true, expected_emit);
-  } else {
-    add_storage_segments(ix, p, 1, ix->main, 0, false, true, expected_emit);
-  }
+  return p;
+}
+
+// ... and what follows from its segments: the workspace sizes, the dominant and the big sweeps, the list and flood capacities.
+// listed_whole: rows that are listed whatever they score (the first segment); expected_emit: those + the expected sparse candidates
+static void size_plan(const bbq_index *ix, Plan &p, int64_t listed_whole, double expected_emit) {
   if (!p.segs.empty()) p.segs.back().need_theta = false;
   int64_t best = -1;
   for (size_t i = 0; i < p.segs.size(); ++i) {
@@ -169,17 +167,69 @@ Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
   }
   if (best >= 0) p.segs[best].dominant = true;
   for (Segment &sg : p.segs) sg.big = best >= 0 && sg.rows * 32 >= p.segs[best].rows && sg.rows >= 65536;
-  // list capacity: everything dense + 4x the expected sparse candidates + slack
-  int64_t dense_rows = 0;
-  for (const Segment &s : p.segs)
-    if (s.emit && s.dense) dense_rows += s.rows;
-  const double sparse = std::max(0.0, expected_emit - (double)dense_rows);
-  p.list_cap = dense_rows + (int64_t)(4.0 * sparse) + 4096;
+  // list capacity: everything listed whole + 4x the expected sparse candidates + slack
+  const double sparse = std::max(0.0, expected_emit - (double)listed_whole);
+  p.list_cap = listed_whole + (int64_t)(4.0 * sparse) + 4096;
   p.list_cap = (p.list_cap + 1023) / 1024 * 1024;
   // per query; bounded so that the overflow areas of one pipeline slot stay within 512 MB however many queries a sub-batch has
   p.flood_cap = std::min<int64_t>(ix->opt_flood, (ix->main.view.n_rows + 1023) / 1024 * 1024);
   if (p.flood_cap > 0)
     p.flood_cap = std::min<int64_t>(p.flood_cap, std::max<int64_t>(16384, ((64ll << 20) / std::max(32, effective_batch(ix))) / 1024 * 1024));
+}
+
+// k: the rank the device selects thresholds with; final_k > 0: k == final_k + 1 and the last finalize launch selects the answer.
+// A value of its inputs and the index's options: the call that asked for it owns it.
+Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k, bool latency) {
+  Plan p = start_plan(ix, k, final_k, latency);
+  double expected_emit = 0, dummy = 0;
+  if (ix->has_pilot) {
+    add_storage_segments(ix, p, 0, ix->pilot, 0, false, false, dummy);
+    add_storage_segments(ix, p, 1, ix->main, ix->pilot.view.n_rows, true, true, expected_emit);
+  } else {
+    add_storage_segments(ix, p, 1, ix->main, 0, false, true, expected_emit);
+  }
+  int64_t dense_rows = 0;
+  for (const Segment &s : p.segs)
+    if (s.emit && s.dense) dense_rows += s.rows;
+  size_plan(ix, p, dense_rows, expected_emit);
+  return p;
+}
+
+// The plan of a filtered call lives in ACCEPTED-ROW space: a threshold is an order statistic over the accepted rows seen so far and only
+// tightens at a segment boundary, so the boundaries are set by accepted rows seen (the filter's cumulative counts per chunk), not by
+// rows swept - cut by rows, a filter whose rows cluster at the end of the index would meet them all in one last segment with a
+// threshold from next to nothing.  The sweep starts at the first chunk with an accepted row and stops after the last; the first
+// segment ends where s0 accepted rows have been seen, every later boundary where the accepted count has grown `growth`-fold (while
+// that is within half of |A|, the unfiltered plan's R/2 rule).  The first segment runs SPARSE with the zeroed threshold (every key of
+// a non-NaN score is > 0, bbq_entry.h): a dense first segment would bring rejected rows into the running top keys.  Expected
+// candidates per chunk are k * accepted_in_chunk / accepted_before <= k * kChunkRows / accepted_before: cap_for carries over with
+// that substitution, and no chunk can list more than the accepted rows it holds.
+Plan build_filtered_plan(const bbq_index *ix, const bbq_filter &f, int64_t k, int64_t final_k, bool latency) {
+  Plan p = start_plan(ix, k, final_k, latency);
+  if (f.count == 0) return p;
+  const std::vector<int32_t> &cum = f.cum;
+  const int64_t end = f.last_chunk + 1, R = ix->main.view.n_rows;
+  // the first chunk boundary at which `acc` accepted rows have been seen
+  auto chunk_where = [&cum](int64_t acc) { return (int64_t)(std::lower_bound(cum.begin(), cum.end(), acc) - cum.begin()); };
+  auto add = [&](int64_t b, int64_t e, int cap_bound) {
+    int32_t most = 0;
+    for (int64_t c = b; c < e; ++c) most = std::max(most, cum[(size_t)c + 1] - cum[(size_t)c]);
+    const int cap = std::min(cap_bound, std::max(16, (most + 7) / 8 * 8));
+    p.segs.push_back(Segment{1, b, e - b, std::min(e * kChunkRows, R) - b * kChunkRows, false, true, true, false, cap});
+  };
+  int64_t b = f.first_chunk;
+  int64_t e = std::min(std::max(chunk_where(p.s0), b + 1), end);
+  add(b, e, kChunkRows);
+  const int64_t first_listed = cum[(size_t)e];
+  double expected_emit = (double)first_listed;
+  for (b = e; b < end; b = e) {
+    const int64_t before = cum[(size_t)b];
+    const int64_t nb = chunk_where(before * p.growth);
+    e = (nb > b && nb < end && cum[(size_t)nb] <= f.count / 2) ? nb : end;
+    add(b, e, cap_for(p.k, before));
+    expected_emit += (double)p.k * (double)(cum[(size_t)e] - before) / (double)before;
+  }
+  size_plan(ix, p, first_listed, expected_emit);
   return p;
 }
 
@@ -316,7 +366,7 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
                c.planes, c.one_bit, c.sim);
   size_t bytes = (size_t)nq * qb + (size_t)nq * sizeof(QueryParams);
   // the matrix-core shared sweep appends its candidates to the lists, so it runs only where they are this slot's own
-  bool use_mfma = !ext && c.share == 32 && c.maxq <= 127 && ix->store_bits == 1;
+  bool use_mfma = !ext && !c.filter && c.share == 32 && c.maxq <= 127 && ix->store_bits == 1;
   for (int i = 0; i < nq && use_mfma; ++i) use_mfma = mfma_query_ok(hq[i]);
   const MfmaStage ms = use_mfma ? stage_queries_mfma(c, s.h_qbuf, hq, q_first, nq, bytes) : MfmaStage{};
   if (use_mfma) bytes = ms.bytes;
@@ -367,6 +417,8 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
       HIPCHK(launch_scan_mfma(a, s.d_qbuf + ms.off_qbytes, reinterpret_cast<const float *>(s.d_qbuf + ms.off_qmax), ms.fp ? ms.scale8 / 8.0f : 0.0f, nq, (int)g.n_chunks, st));
     else if (shared)
       HIPCHK(launch_scan_shared(a, c.planes, c.share, nq, (int)g.n_chunks, st));
+    else if (c.filter)  // (its plan has sparse segments only, and c.share == 1)
+      HIPCHK(launch_scan_filtered(a, c.filter->d_bits, c.planes, nq, (int)g.n_chunks, st));
     else
       HIPCHK(launch_scan(a, c.planes, g.dense, nq, (int)g.n_chunks, st));
     if (chained) {
@@ -518,7 +570,7 @@ static void take_device_answers(const SearchCall &c, Slot &s, int32_t *out_idx, 
 
 // step 5: the heap replays, on the pool when replay_threads > 1; finish_replay waits for them
 static void schedule_replays(const SearchCall &c, Slot &s, int32_t *out_idx, float *out_score, int64_t *out_n) {
-  const int64_t k = c.k_out, n_total = c.ix->main.row_id_base + c.ix->main.view.n_rows;
+  const int64_t k = c.k_out, n_total = c.filter ? c.n_eff : c.ix->main.row_id_base + c.ix->main.view.n_rows;
   Slot *sp = &s;
   auto replay_range = [sp, k, n_total, out_idx, out_score, out_n](int lo, int hi) {
     Slot &s = *sp;
@@ -637,11 +689,20 @@ static void reset_call_stats(bbq_index *ix) { ix->stats.candidates = ix->stats.d
 }  // namespace bbq
 
 // bbq_search_batch, and - with `feed` - bbq_search_raw_batch: the quantized queries of a sub-batch are waited for right before it is
-// enqueued
+// enqueued; with `flt` - bbq_search_filtered_batch: the same call over the accepted rows only, always on the pipelined per-query
+// sweep (the single-query chains, the shared and the matrix-core sweeps derive their thresholds in ways of their own)
 static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits,
-                             int32_t sim, int64_t k, int32_t *out_idx, float *out_score, int64_t *out_n, RawFeed *feed, int32_t *bad_query) {
+                             int32_t sim, int64_t k, int32_t *out_idx, float *out_score, int64_t *out_n, RawFeed *feed, int32_t *bad_query,
+                             const bbq_filter *flt = nullptr) {
   int rc = validate_query_args(ix, n_queries, qquant, qcorr, query_bits, sim, k, feed != nullptr);
   if (rc != BBQ_OK) return rc;
+  // a filter is checked against the index before anything returns: k == 0 does not excuse a filter of another index
+  if (flt && ix->multi) return fail(BBQ_ERR_UNSUPPORTED, "filtered search is not supported on a multi-device index");
+  if (flt && (ix->has_pilot || ix->row_base != 0))
+    return fail(BBQ_ERR_UNSUPPORTED, "filtered search is not supported on a row shard or an index with a pilot replica");
+  if (flt && (flt->device != ix->device || flt->n_rows != ix->n_rows))
+    return fail(BBQ_ERR_INVALID_ARG, "the filter was made for an index of %lld rows on device %d, this one has %lld rows on device %d",
+                (long long)flt->n_rows, flt->device, (long long)ix->n_rows, ix->device);
   if (n_queries > 0 && !out_n) return fail(BBQ_ERR_INVALID_ARG, "out_n is null");
   for (int32_t i = 0; i < n_queries; ++i) out_n[i] = 0;
   if (k == 0 || n_queries == 0) return BBQ_OK;  // src/binaryQuantizationFormat.ts:332-334
@@ -658,9 +719,15 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
   rc = settle_shard_slots(ix->ctx, nullptr);  // an asynchronous sharded scan on this device may have left slots busy
   if (rc != BBQ_OK) return rc;
   reset_call_stats(ix);
-  if (ix->n_rows == 0) return BBQ_OK;
+  const int64_t n_eff = flt ? flt->count : ix->n_rows;  // the rows that exist for this call
+  if (n_eff == 0) return BBQ_OK;
 
   SearchCall c(ix, qquant, qcorr, 0, query_bits, sim, k);
+  if (flt) {
+    c.filter = flt;
+    c.n_eff = n_eff;
+    c.share = 1;
+  }
   if (feed) {  // the values are still being produced: the kernel variant follows from the bit width they are quantized to
     const int pq = query_bits <= 1 ? 1 : query_bits <= 2 ? 2 : query_bits <= 4 ? 4 : 8;
     c.planes = ix->store_bits == 1 ? pq : ix->store_bits == 8 ? 8 : (query_bits <= 4 ? 4 : 8);
@@ -669,7 +736,7 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
     c.planes = planes_of_call(ix, qquant, (int64_t)n_queries * ix->dim, query_bits == 1);
     c.maxq = c.planes <= 4 ? 15 : max_value(qquant, (int64_t)n_queries * ix->dim);
   }
-  const int64_t keff = std::min<int64_t>(k, ix->n_rows);
+  const int64_t keff = std::min<int64_t>(k, n_eff);
   if (keff > kMaxFastK || ix->opt_force_dense) {
     for (int32_t i = 0; i < n_queries; ++i) {
       if (feed && (rc = feed->wait(i, 1, bad_query)) != BBQ_OK) return rc;
@@ -683,9 +750,10 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
   // replays the heap only for queries with equal scores in or at the edge of their answer
   const int64_t final_k = (keff <= kFinalSelectMax && ix->opt_device_select) ? keff : 0;
   c.k_dev = final_k > 0 ? keff + 1 : keff;
-  const Plan plan = build_plan(ix, c.k_dev, final_k, final_k > 0 && n_queries <= ix->opt_latency_queries);
+  const bool latency = final_k > 0 && n_queries <= ix->opt_latency_queries;
+  const Plan plan = flt ? build_filtered_plan(ix, *flt, c.k_dev, final_k, latency) : build_plan(ix, c.k_dev, final_k, latency);
   c.plan = &plan;
-  if (n_queries == 1 && plan.latency && !feed) {
+  if (n_queries == 1 && plan.latency && !feed && !flt) {
     bool done = false;
     rc = search_latency_presampled(c, out_idx, out_score, out_n, &done);
     if (rc != BBQ_OK || done) return rc;
@@ -734,6 +802,13 @@ int bbq_search_batch(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, co
                      int32_t sim, int64_t k, int32_t *out_idx, float *out_score, int64_t *out_n) {
   clear_error();
   return search_batch_impl(ix, n_queries, qquant, qcorr, query_bits, sim, k, out_idx, out_score, out_n, nullptr, nullptr);
+}
+
+int bbq_search_filtered_batch(bbq_index *ix, const bbq_filter *f, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
+                              int32_t query_bits, int32_t sim, int64_t k, int32_t *out_idx, float *out_score, int64_t *out_n) {
+  clear_error();
+  if (!f) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_filtered_batch: the filter is null");
+  return search_batch_impl(ix, n_queries, qquant, qcorr, query_bits, sim, k, out_idx, out_score, out_n, nullptr, nullptr, f);
 }
 
 int bbq_search_raw_batch(bbq_index *ix, int32_t n_queries, const float *queries, const float *centroid, int32_t sim, int32_t query_bits,

@@ -57,18 +57,27 @@ int dense_scores_one(const SearchCall &c, int64_t qi, float *out) {
 
 namespace bbq {
 
-// dense path for one query: every f32 score to the host, full replay of the reference loop
+// dense path for one query: every f32 score to the host, full replay of the reference loop - of a filtered call: over the accepted
+// rows only, ascending, which is the loop the filter's contract names
 int dense_search_one(const SearchCall &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n) {
   bbq_index *ix = c.ix;
   const int64_t n = ix->main.view.n_rows;
   std::vector<float> h((size_t)std::max<int64_t>(n, 1));
   int rc = dense_scores_one(c, qi, h.data());
   if (rc != BBQ_OK) return rc;
-  HeapReplay hr(c.k_out, n);
-  for (int64_t i = 0; i < n; ++i) hr.offer(h[(size_t)i], (int32_t)(ix->main.row_id_base + i));
+  HeapReplay hr(c.k_out, c.filter ? c.n_eff : n);
+  if (c.filter) {
+    for (size_t w = 0; w < c.filter->h_bits.size(); ++w)
+      for (uint64_t bits = c.filter->h_bits[w]; bits; bits &= bits - 1) {
+        const int64_t i = (int64_t)w * 64 + __builtin_ctzll(bits);
+        hr.offer(h[(size_t)i], (int32_t)(ix->main.row_id_base + i));
+      }
+  } else {
+    for (int64_t i = 0; i < n; ++i) hr.offer(h[(size_t)i], (int32_t)(ix->main.row_id_base + i));
+  }
   *out_n = hr.finish(out_idx, out_score);
   ix->stats.dense_fallbacks += 1;
-  ix->stats.candidates += n;
+  ix->stats.candidates += c.filter ? c.n_eff : n;
   return BBQ_OK;
 }
 

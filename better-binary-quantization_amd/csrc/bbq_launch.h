@@ -7,6 +7,8 @@ namespace bbq {
 
 // planes: number of query bit-planes (1, 2, 4 or 8); multi-bit index: 4 (query values <= 15) or 8
 hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries, int n_chunks, hipStream_t s);
+// the sparse sweep of a filtered search: accept[tile] = the tile's accept word (bit l = row l of the tile), one word per tile of a.idx
+hipError_t launch_scan_filtered(const ScanArgs &a, const uint64_t *accept, int planes, int n_queries, int n_chunks, hipStream_t s);
 // shared sweep: `share` (4 or 8) queries per workgroup reuse every loaded row (sparse segments, fixed-width dims only)
 bool shared_sweep_supported(const ScanArgs &a, int share);
 hipError_t launch_scan_shared(const ScanArgs &a, int planes, int share, int n_queries, int n_chunks, hipStream_t s);

@@ -1,0 +1,282 @@
+// bbq_scan_body.h - the per-query sweep (bbq_scan_kernel), unfiltered and filtered from one template, and the dispatch over its
+// instantiations.  Included by bbq_kernels.hip (FILT = false) and bbq_filter_kernels.hip (FILT = true): each
+// translation unit instantiates its own kernels only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "bbq_device.h"
+#include "bbq_kernel_common.h"
+
+#pragma clang fp contract(off)
+
+namespace bbq {
+
+// Multi-bit index rows (indexBits > 1): qcDist = sum_d q[d] * x[d] (computeQuantizedDotProduct, src/bitwiseDotProduct.ts:14-30)
+// over SB-bit fields with the packed-nibble / packed-byte dot instructions - 8 (v_dot8_u32_u4) or 4 (v_dot4_u32_u8) exact
+// integer products per lane and instruction.  2-bit fields are unfolded in registers into two dwords of nibbles (even / odd
+// fields: one AND, one shift + AND); query values above 15 (QB == 8) are split into low and high nibbles,
+// q = lo + 16 hi, so the dot is dot(x, lo) + 16 dot(x, hi).  s_q holds, per row dword, the matching query dwords
+// (query_units_per_chunk; written by the host in exactly this order).  `sum` = the row's component sum (= quantizedComponentSum
+// of a freshly quantized row, src/optimizedScalarQuantizer.ts:204-209).
+template <int QB, int SB>
+__device__ __forceinline__ void dot_chunk_multibit(const u32x4 c, const uint32_t *__restrict__ sq, uint32_t &lo, uint32_t &hi, uint32_t &sum) {
+  const uint32_t x[4] = {c.x, c.y, c.z, c.w};
+  constexpr int QN = query_units_per_chunk(QB, SB);  // query dwords per row dword
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const uint32_t *__restrict__ qw = sq + t * QN;
+    if constexpr (SB == 2) {
+      const uint32_t e = x[t] & 0x33333333u, o = (x[t] >> 2) & 0x33333333u;
+      lo = __builtin_amdgcn_udot8(e, qw[0], lo, false);
+      lo = __builtin_amdgcn_udot8(o, qw[1], lo, false);
+      if constexpr (QB > 4) {
+        hi = __builtin_amdgcn_udot8(e, qw[2], hi, false);
+        hi = __builtin_amdgcn_udot8(o, qw[3], hi, false);
+      }
+      sum = __builtin_amdgcn_udot8(e + o, 0x11111111u, sum, false);  // nibbles of e + o are at most 6
+    } else if constexpr (SB == 4) {
+      lo = __builtin_amdgcn_udot8(x[t], qw[0], lo, false);
+      if constexpr (QB > 4) hi = __builtin_amdgcn_udot8(x[t], qw[1], hi, false);
+      sum = __builtin_amdgcn_udot8(x[t], 0x11111111u, sum, false);
+    } else {
+      lo = __builtin_amdgcn_udot4(x[t], qw[0], lo, false);
+      sum = __builtin_amdgcn_udot4(x[t], 0x01010101u, sum, false);
+    }
+  }
+}
+
+template <int QB, int W, int SB>
+__device__ __forceinline__ void tile_dot_multibit(const u32x4 (&c)[W], const u32x4 *__restrict__ s_planes, uint32_t &qc, uint32_t &sum) {
+  const uint32_t *__restrict__ sq = reinterpret_cast<const uint32_t *>(s_planes);
+  constexpr int QN = query_units_per_chunk(QB, SB);
+  uint32_t lo = 0, hi = 0;
+  sum = 0;
+#pragma unroll
+  for (int j = 0; j < W; ++j) dot_chunk_multibit<QB, SB>(c[j], sq + j * 4 * QN, lo, hi, sum);
+  qc = lo + (hi << 4);
+}
+template <int QB, int SB>
+__device__ __forceinline__ void tile_dot_multibit_any(const uint8_t *__restrict__ tp, int lane, int w16, const u32x4 *__restrict__ s_planes,
+                                                      uint32_t &qc, uint32_t &sum) {
+  const u32x4 *__restrict__ cp = reinterpret_cast<const u32x4 *>(tp) + lane;
+  const uint32_t *__restrict__ sq = reinterpret_cast<const uint32_t *>(s_planes);
+  constexpr int QN = query_units_per_chunk(QB, SB);
+  uint32_t lo = 0, hi = 0;
+  sum = 0;
+  for (int j = 0; j < w16; ++j) {
+    const u32x4 c = BBQ_STREAM_LOAD(cp + j * kTileRows);
+    dot_chunk_multibit<QB, SB>(c, sq + j * 4 * QN, lo, hi, sum);
+  }
+  qc = lo + (hi << 4);
+}
+
+// MODE: 0 sparse / inline corrections, 1 dense / inline, 2 sparse / compact corrections + exact gather, 3 dense / compact
+// grid = (chunks of kChunkRows rows, queries); block = kChunkRows/64 waves: wave w handles tile w of its chunk (one row per lane)
+// SB = bits per stored field: 1 = packed 1-bit rows (QB bit-planes of the query), 2 / 4 / 8 = multi-bit rows (QB = 4: query values
+// <= 15, QB = 8: any)
+// Accept: empty - the unfiltered sweep, exactly the kernel it was - or one `const uint64_t *`, the accept bitset of a filtered search
+// (FILT; sparse modes only).  accept[tile] is the tile's accept word (bit l = lane l's row, bbq_filter.cpp): the wave reads it once
+// through a wave-uniform address; a wave whose word is 0 issues no load of its tile at all, and a lane whose bit is clear is not a
+// valid row - it gathers no exact corrections, lists nothing and raises no NaN flag.  The end of the chunk (count word, flood tier,
+// append path) is the same for both.  (One kernel template and a parameter pack rather than a shared __device__ body under two
+// kernels: inlined through a function the unfiltered instantiations came out with other instruction schedules.)
+template <int QB, int W, int MODE, int SB = 1, class... Accept>
+__global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, const Accept... accept_arg) {
+  constexpr bool FILT = sizeof...(Accept) > 0;
+  static_assert(sizeof...(Accept) <= 1 && !(FILT && (MODE & 1)), "at most the accept bitset, and a filtered sweep is sparse");
+  const uint64_t *__restrict__ accept = nullptr;
+  if constexpr (FILT) accept = (accept_arg, ...);
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int NT = kChunkRows;
+  constexpr bool DENSE = (MODE & 1) != 0;
+  constexpr bool COMPACT = (MODE & 2) != 0;
+  constexpr int QU = query_units_per_chunk(QB, SB);
+  const int w16 = W > 0 ? W : a.idx.w16;
+  u32x4 *s_planes = reinterpret_cast<u32x4 *>(smem);
+  uint64_t *s_ent = reinterpret_cast<uint64_t *>(smem + (size_t)w16 * QU * 16);
+  // with a flood tier every passing row of the chunk is staged (it may have to move to the overflow area as a whole)
+  const uint32_t stage_cap = DENSE ? 0u : ((a.ovf || a.append_lists) ? (uint32_t)kChunkRows : (uint32_t)a.cap);
+  uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_ent + stage_cap);
+
+  const int q = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+
+  // the tile's accept word first: its address depends on blockIdx and the wave number alone, so the scalar load travels while the
+  // planes are staged and is there when the barrier opens (behind the barrier every wave paid its latency in front of its first HBM request)
+  uint64_t aw = 0;
+  if constexpr (FILT) {
+    const int64_t my_tile = (a.chunk_begin + blockIdx.x) * kTilesPerChunk + __builtin_amdgcn_readfirstlane(wave);
+    if (my_tile < (a.idx.n_rows + kTileRows - 1) / kTileRows) aw = accept[my_tile];
+  }
+  {  // stage the query bit-planes once per workgroup
+    const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)q * w16 * QU;
+    for (int i = tid; i < w16 * QU; i += NT) s_planes[i] = gp[i];
+    if (!DENSE && tid == 0) *s_cnt = 0;
+  }
+  const QueryParams p = a.qparams[q];
+  const uint32_t theta = DENSE ? 0u : a.theta[q];
+  __syncthreads();
+
+  const int64_t chunk = a.chunk_begin + blockIdx.x;
+  const int64_t n_tiles = (a.idx.n_rows + kTileRows - 1) / kTileRows;
+  const int64_t tile = chunk * kTilesPerChunk + wave;
+  bool nan_seen = false;
+
+  if (tile < n_tiles && (!FILT || aw != 0)) {  // wave-uniform
+    const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.tile_stride;
+    const uint8_t *__restrict__ cr = tp + (size_t)w16 * (kTileRows * 16);
+    const int64_t row = tile * kTileRows + lane;
+    const bool valid = row < a.idx.n_rows && (!FILT || ((aw >> lane) & 1ull) != 0);
+    const bool resident = chunk_is_resident(chunk, a.idx);
+
+    // every load of the tile is issued up front: the row's code chunks and its corrections
+    f64x2 lu = {0.0, 0.0};
+    double xadd = 0.0, x1 = 0.0;
+    uint32_t cw = 0;
+    float aadd = 0.0f;
+    uint32_t qc, ones;
+    constexpr int CORR = !COMPACT ? 2 : (DENSE ? 0 : 1);
+    if constexpr (W > 0) {
+      u32x4 c[W];
+      load_tile<W, CORR>(tp, lane, a.idx.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
+      if constexpr (COMPACT && DENSE) exact_corrections<true>(a.idx.exact, row, lu, xadd);
+      if constexpr (COMPACT && !DENSE) aadd = tile_add_bound(a.idx, tile, p.sim);
+      if constexpr (SB == 1) qc = tile_popcounts<QB, W>(c, s_planes, ones);
+      else tile_dot_multibit<QB, W, SB>(c, s_planes, qc, ones);
+    } else {  // a row width without a compiled kernel: streamed chunk by chunk
+      if constexpr (!COMPACT) {
+        lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(cr) + lane);
+        xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + 1024) + lane);
+        if (a.idx.has_x1) x1 = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + 1536) + lane);
+      } else if constexpr (DENSE) {
+        exact_corrections<true>(a.idx.exact, row, lu, xadd);
+      } else {
+        cw = BBQ_STREAM_LOAD(reinterpret_cast<const uint32_t *>(cr) + lane);
+        aadd = tile_add_bound(a.idx, tile, p.sim);
+      }
+      if constexpr (SB == 1) qc = tile_popcounts_any<QB>(tp, lane, w16, s_planes, ones);
+      else tile_dot_multibit_any<QB, SB>(tp, lane, w16, s_planes, qc, ones);
+    }
+    if (!a.idx.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
+
+    bool need_exact = true;
+    if constexpr (COMPACT && !DENSE) {
+      need_exact = compact_bound_passes(valid, qc, cw, aadd, x1, p, theta);
+      if (need_exact) exact_corrections(a.idx.exact, row, lu, xadd);
+    }
+    if (need_exact) {
+      const double s64 = score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
+      const float s32 = (float)s64;
+      const uint32_t bits = __float_as_uint(s32);
+      if (valid && (s32 != s32)) nan_seen = true;
+      if constexpr (DENSE) {
+        if (valid) {
+          const int64_t o = (int64_t)q * a.dense_stride + (row - a.chunk_begin * kChunkRows);
+          if (a.dense_score32) a.dense_score32[o] = s32;
+          if (a.dense_qcdist) a.dense_qcdist[o] = (int32_t)qc;
+          if (a.dense_score64) a.dense_score64[o] = s64;
+        }
+      } else if (valid && (s32 == s32) && key_of_bits(bits) > theta) {
+        const uint32_t slot = atomicAdd(s_cnt, 1u);
+        if (slot < stage_cap) s_ent[slot] = candidate_entry(a.row_id_base + row, s32);
+      }
+    }
+  }
+  if (__any(nan_seen) && lane == 0) atomicOr(a.flags + q, kFlagNaN);
+
+  if constexpr (!DENSE) {
+    __syncthreads();
+    if (a.append_lists) {  // workgroup-uniform
+      const uint32_t cnt = *s_cnt;
+      if (cnt == 0) return;
+      __syncthreads();  // everyone has read *s_cnt: it takes the reserved offset
+      append_to_list<NT>(s_ent, cnt, a.append_counts + (size_t)q * kAppendStride, a.append_base[2 * q], a.append_lists + (size_t)q * a.append_cap,
+                         a.append_cap, a.flags + q, s_cnt);
+      return;
+    }
+    uint32_t cnt = *s_cnt;
+    uint64_t *__restrict__ slot0 = a.entries + ((size_t)q * a.n_chunks + blockIdx.x) * (size_t)a.cap;
+    uint64_t *__restrict__ out = slot0;
+    uint32_t count_word = cnt;
+    if (cnt > (uint32_t)a.cap) {  // workgroup-uniform
+      bool parked = false;
+      if (a.ovf) {
+        // flood (e.g. rows stored cluster by cluster and this is the query's cluster): one block of the query's overflow
+        // area takes the whole chunk, so the list stays row-ordered and the query stays on the sparse path
+        __syncthreads();  // everyone has read *s_cnt
+        if (tid == 0) *s_cnt = atomicAdd(a.ovf_counts + q, cnt);
+        __syncthreads();
+        const uint32_t off = *s_cnt;
+        if ((uint64_t)off + cnt <= (uint64_t)a.ovf_cap) {
+          out = a.ovf + (size_t)q * a.ovf_cap + off;
+          count_word = kCountRedirect | cnt;
+          if (tid == 0) slot0[0] = off;
+          parked = true;
+        }
+      }
+      if (!parked) {
+        if (tid == 0) atomicOr(a.flags + q, kFlagOverflow);
+        cnt = min(cnt, (uint32_t)a.cap);
+        count_word = cnt;
+      }
+    }
+    write_ranked(s_ent, cnt, out, tid, NT);
+    if (tid == 0) a.counts[(size_t)q * a.n_chunks + blockIdx.x] = count_word;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// dispatch over the instantiations: FILT selects the kernel family, `accept` is its accept bitset (null without)
+
+template <bool FILT, int QB, int W, int MODE, int SB = 1>
+static hipError_t launch_scan_t(const ScanArgs &a, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s) {
+  const int w16 = W > 0 ? W : a.idx.w16;
+  const size_t smem = (size_t)w16 * query_units_per_chunk(QB, SB) * 16 + ((MODE & 1) ? 0 : (size_t)((a.ovf || a.append_lists) ? kChunkRows : a.cap) * 8) + 16;
+  dim3 grid((unsigned)n_chunks, (unsigned)n_queries, 1), block(kChunkRows, 1, 1);
+  if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, const uint64_t *>), grid, block, smem, s, a, accept);
+  else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB>), grid, block, smem, s, a);
+  return hipGetLastError();
+}
+
+// multi-bit rows: compile-time widths for 768-d / 1024-d at 2 bits (12 / 16 chunks; 16 is also 512-d at 4 bits), runtime loop otherwise
+template <bool FILT, int QB, int MODE, int SB>
+static hipError_t launch_scan_mb_w(const ScanArgs &a, const uint64_t *accept, int nq, int nc, hipStream_t s) {
+  switch (a.idx.w16) {
+    case 12: return launch_scan_t<FILT, QB, 12, MODE, SB>(a, accept, nq, nc, s);
+    case 16: return launch_scan_t<FILT, QB, 16, MODE, SB>(a, accept, nq, nc, s);
+    default: return launch_scan_t<FILT, QB, 0, MODE, SB>(a, accept, nq, nc, s);
+  }
+}
+template <bool FILT, int MODE>
+static hipError_t launch_scan_mb(const ScanArgs &a, const uint64_t *accept, int planes, int nq, int nc, hipStream_t s) {
+  switch (a.idx.store_bits) {
+    case 2: return planes > 4 ? launch_scan_mb_w<FILT, 8, MODE, 2>(a, accept, nq, nc, s) : launch_scan_mb_w<FILT, 4, MODE, 2>(a, accept, nq, nc, s);
+    case 4: return planes > 4 ? launch_scan_mb_w<FILT, 8, MODE, 4>(a, accept, nq, nc, s) : launch_scan_mb_w<FILT, 4, MODE, 4>(a, accept, nq, nc, s);
+    case 8: return launch_scan_t<FILT, 8, 0, MODE, 8>(a, accept, nq, nc, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+template <bool FILT, int QB, int MODE>
+static hipError_t launch_scan_w(const ScanArgs &a, const uint64_t *accept, int nq, int nc, hipStream_t s) {
+  switch (a.idx.w16) {
+    case 1: return launch_scan_t<FILT, QB, 1, MODE>(a, accept, nq, nc, s);    // dim <= 128
+    case 6: return launch_scan_t<FILT, QB, 6, MODE>(a, accept, nq, nc, s);    // dim 768
+    case 8: return launch_scan_t<FILT, QB, 8, MODE>(a, accept, nq, nc, s);    // dim 1024
+    case 12: return launch_scan_t<FILT, QB, 12, MODE>(a, accept, nq, nc, s);  // dim 1536
+    default: return launch_scan_t<FILT, QB, 0, MODE>(a, accept, nq, nc, s);
+  }
+}
+
+template <bool FILT, int MODE>
+static hipError_t launch_scan_q(const ScanArgs &a, const uint64_t *accept, int planes, int nq, int nc, hipStream_t s) {
+  switch (planes) {
+    case 1: return launch_scan_w<FILT, 1, MODE>(a, accept, nq, nc, s);
+    case 2: return launch_scan_w<FILT, 2, MODE>(a, accept, nq, nc, s);
+    case 4: return launch_scan_w<FILT, 4, MODE>(a, accept, nq, nc, s);
+    default: return launch_scan_w<FILT, 8, MODE>(a, accept, nq, nc, s);
+  }
+}
+
+}  // namespace bbq

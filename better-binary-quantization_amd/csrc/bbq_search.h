@@ -3,6 +3,18 @@
 #pragma once
 #include "bbq_host.h"
 
+// The accept set of a filtered search (bbq_filter.cpp): read-only after creation, so any number of calls and threads may share it.
+struct bbq_filter {
+  int device = 0;
+  bbq::DeviceCtx *ctx = nullptr;
+  int64_t n_rows = 0;                // rows of the index it was made for
+  int64_t count = 0;                 // |A|
+  bbq::DevBuf<uint64_t> d_bits;      // [ceil(n_rows / 64)] word t = tile t, bit l = lane l; bits at and beyond n_rows are clear
+  std::vector<uint64_t> h_bits;      // the same on the host: the dense path offers the accepted rows from it
+  std::vector<int32_t> cum;          // [chunks + 1] accepted rows in the chunks before chunk c: what the accepted-space plan is cut by
+  int64_t first_chunk = -1, last_chunk = -1;  // the first and the last chunk that holds an accepted row (-1: none)
+};
+
 #pragma GCC visibility push(hidden)  // internal: none of this joins the library's dynamic symbols
 namespace bbq {
 
@@ -18,6 +30,10 @@ struct SearchCall {
   int maxq = 255;              // largest quantized query value of the call (the MFMA sweep needs <= 127)
   int share;                   // queries per row load of the sparse sweeps of this enqueue: the index's sweep_share unless a step overrides it
   const Plan *plan = nullptr;  // the call's segment plan; null in a call that only takes the dense path
+  // a filtered call (bbq_search_filtered_batch): only rows of `filter` exist for it, so n_eff = |A| stands wherever the unfiltered
+  // call bounds a rank by the rows of the index (k_dev, the plan's final_k, the replayed heap)
+  const bbq_filter *filter = nullptr;
+  int64_t n_eff = 0;
   SearchCall(bbq_index *ix, const uint8_t *qquant, const double *qcorr, int planes, int32_t query_bits, int32_t sim, int64_t k)
       : ix(ix), qquant(qquant), qcorr(qcorr), planes(planes), one_bit(query_bits == 1 ? 1 : 0), sim(sim), k_out(k), share(ix->opt_share) {}
 };
@@ -48,6 +64,7 @@ int validate_query_args(const bbq_index *ix, int32_t nq, const uint8_t *qquant, 
 // ---- bbq_core.cpp
 int effective_batch(const bbq_index *ix, int64_t n_queries = 0);
 Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k = 0, bool latency = false);
+Plan build_filtered_plan(const bbq_index *ix, const bbq_filter &f, int64_t k, int64_t final_k, bool latency);
 int ensure_slot(const SearchCall &c, Slot &s, int nq, bool own_lists);
 FinalizeArgs slot_finalize_args(const Slot &s, uint64_t *lists, int32_t *list_counts, int64_t list_cap, bool appended, int64_t k);
 int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, const ExtOut *ext);

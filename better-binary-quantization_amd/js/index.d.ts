@@ -54,6 +54,10 @@ export declare class BinaryQuantizationFormat {
   searchNearestNeighbors(queryVector: Float32Array, targetVectors: BinarizedByteVectorValues, k: number): Array<{ index: number; score: number }>;
   /** extension: many independent queries per call, pipelined on the device */
   searchNearestNeighborsBatch(queryVectors: Float32Array[], targetVectors: BinarizedByteVectorValues, k: number): Array<Array<{ index: number; score: number }>>;
+  /** extension: searchNearestNeighbors over the ords `filter` accepts (what the reference's loop returns when it visits only those, ascending) */
+  searchNearestNeighborsFiltered(query: Float32Array, targetVectors: BinarizedByteVectorValues, filter: RowFilter, k: number): Array<{ index: number; score: number }>;
+  /** extension: the same for many queries per call; one filter serves all of them */
+  searchNearestNeighborsBatchFiltered(queries: Float32Array[], targetVectors: BinarizedByteVectorValues, filter: RowFilter, k: number): Array<Array<{ index: number; score: number }>>;
   /** src/binaryQuantizationFormat.ts:483-566 with the double-pack bug fixed: binaryValues is the packed row */
   serializeVectorData(vectors: Float32Array[]): { vectorData: VectorDataFormat[]; metadata: MetadataFormat };
   deserializeVectorData(vectorData: VectorDataFormat[], metadata: MetadataFormat): BinarizedByteVectorValues;
@@ -95,6 +99,13 @@ export declare class DeviceVectors {
   dispose(): void;
 }
 export declare function createDeviceVectors(vectors: Float32Array[], device?: number): DeviceVectors;
+/** extension: an accept set of the rows of one index, resident on its device; not supported on a multi-device index (BBQ_DEVICES) */
+export declare class RowFilter {
+  constructor(targetVectors: BinarizedByteVectorValues, accept: Uint8Array | Int32Array | number[] | ((ord: number) => boolean));
+  readonly count: number;
+  dispose(): void;
+}
+export declare function createRowFilter(targetVectors: BinarizedByteVectorValues, accept: Uint8Array | Int32Array | number[] | ((ord: number) => boolean)): RowFilter;
 export declare function getOversampledTopKWithHeap(query: Float32Array, quantizedVectors: any, vectors: Float32Array[] | DeviceVectors, k: number, oversampleFactor: number, format: BinaryQuantizationFormat): TopKCandidate[];
 export declare function getOversampledTopKWithSort(query: Float32Array, quantizedVectors: any, vectors: Float32Array[] | DeviceVectors, k: number, oversampleFactor: number, format: BinaryQuantizationFormat): TopKCandidate[];
 /** extension: the whole recipe for many queries in one native call */

@@ -460,14 +460,13 @@ class BinaryQuantizationFormat {
     return res;
   }
 
-  /** extension (not in the reference): many queries per call, pipelined on the device; each query sweeps the index itself */
-  searchNearestNeighborsBatch(queryVectors, targetVectors, k) {
+  // the argument checks of a batch call (the reference's messages, in searchNearestNeighbors' order) and its queries as one flat array
+  _flatQueries(queryVectors, targetVectors, k) {
     if (!queryVectors) throw new Error('查询向量不能为空');
     if (!targetVectors) throw new Error('目标向量集合不能为空');
     if (k < 0) throw new Error('k值不能为负数');
     const dim = targetVectors.dimension(), nq = queryVectors.length;
-    if (k === 0) return queryVectors.map(function () { return []; });
-    const q = this.quantizer, sim = simOrdinal(q.similarityFunction);
+    if (k === 0) return null;
     if (isMultiBit(targetVectors) && nq > 0) {
       // the reference answers a multi-bit index through its per-row fallback, warning once per batch of 1000 rows
       // (src/binaryQuantizedScorer.ts:403-405), and throws for queryBits its fallback does not know (:95-97); one warning per call here
@@ -481,12 +480,53 @@ class BinaryQuantizationFormat {
       if (v.length !== dim) throw new Error('查询向量维度与目标向量维度不匹配');
       flat.set(v, i * dim);
     }
+    return flat;
+  }
+
+  /** extension (not in the reference): many queries per call, pipelined on the device; each query sweeps the index itself */
+  searchNearestNeighborsBatch(queryVectors, targetVectors, k) {
+    const flat = this._flatQueries(queryVectors, targetVectors, k);
+    if (flat === null) return queryVectors.map(function () { return []; });
+    const nq = queryVectors.length, q = this.quantizer, sim = simOrdinal(q.similarityFunction);
     // searchNearestNeighbors normalises for COSINE and quantizeQueryVector normalises again (:337-347, :279-281); both happen behind
     // bbq_search_raw_batch, on host threads, chunk by chunk while the sub-batches in front are already on the device (one 768-d query
     // costs ~15 us on one core, more than its sweep of 1 M rows on the device)
     const tNative = process.hrtime.bigint();
     const r = native.searchRawBatch(targetVectors._deviceIndex(), nq, flat, targetVectors.getCentroid(), sim, this.config.queryBits, q.lambda, q.iters,
       Number(process.env.BBQ_THREADS || 0), k);
+    hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
+    const out = new Array(nq), indices = r.indices, scores = r.scores, stride = r.stride;
+    for (let i = 0; i < nq; i++) {
+      const n = r.counts[i], base = i * stride, res = new Array(n);
+      for (let j = 0; j < n; j++) res[j] = { index: indices[base + j], score: scores[base + j] };
+      out[i] = res;
+    }
+    return out;
+  }
+
+  /**
+   * extension (not in the reference): searchNearestNeighbors over the rows `filter` (createRowFilter) accepts - what the reference's
+   * loop (:349-411) returns when it visits only those ords, ascending, with a heap of min(k, filter.count).  Same validation and
+   * messages as searchNearestNeighbors.  A multi-device index (BBQ_DEVICES) throws the library's unsupported message.
+   */
+  searchNearestNeighborsFiltered(queryVector, targetVectors, filter, k) {
+    if (!queryVector) throw new Error('查询向量不能为空');
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (k < 0) throw new Error('k值不能为负数');
+    if (queryVector.length !== targetVectors.dimension()) throw new Error('查询向量维度与目标向量维度不匹配');
+    return this.searchNearestNeighborsBatchFiltered([queryVector], targetVectors, filter, k)[0];
+  }
+
+  /** extension (not in the reference): searchNearestNeighborsFiltered for many queries per call; one filter serves all of them */
+  searchNearestNeighborsBatchFiltered(queryVectors, targetVectors, filter, k) {
+    const flat = this._flatQueries(queryVectors, targetVectors, k);
+    if (!(filter instanceof RowFilter)) throw new Error('searchNearestNeighborsFiltered needs createRowFilter(targetVectors, accept)');
+    if (flat === null) return queryVectors.map(function () { return []; });
+    const nq = queryVectors.length, q = this.quantizer, sim = simOrdinal(q.similarityFunction), qb = this.config.queryBits;
+    const tNative = process.hrtime.bigint();
+    // the queries are prepared as searchNearestNeighbors prepares them (:337-347: normalised for COSINE, then quantizeQueryVector)
+    const qz = native.quantizeQueries(flat, nq, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, Number(process.env.BBQ_THREADS || 0));
+    const r = native.searchFilteredBatch(targetVectors._deviceIndex(), filter._handle(), nq, qz.quantized, qz.corrections, qb, sim, k);
     hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
     const out = new Array(nq), indices = r.indices, scores = r.scores, stride = r.stride;
     for (let i = 0; i < nq; i++) {
@@ -713,6 +753,35 @@ class DeviceVectors {
 }
 function createDeviceVectors(vectors, device) { return new DeviceVectors(vectors, device); }
 
+/**
+ * extension (not in the reference): an accept set of the rows of `targetVectors`, resident on its device (libbbq bbq_filter_*), for
+ * searchNearestNeighborsFiltered.  `accept`: a Uint8Array mask of length size() (non-zero = accepted), an Int32Array / array of ords
+ * (any order, duplicates allowed), or a predicate (ord) => boolean.  Read-only; any number of searches may share it.
+ */
+class RowFilter {
+  constructor(targetVectors, accept) {
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    const n = targetVectors.size();
+    let arg = accept;
+    if (typeof accept === 'function') {
+      arg = new Uint8Array(n);
+      for (let i = 0; i < n; i++) arg[i] = accept(i) ? 1 : 0;
+    } else if (Array.isArray(accept)) {
+      // Int32Array.from would wrap an ord outside int32 and drop a fraction: another row would be accepted in its place
+      for (let i = 0; i < accept.length; i++) if (!Number.isInteger(accept[i]) || accept[i] < 0 || accept[i] >= n) throw new Error('向量索引 ' + accept[i] + ' 不存在');
+      arg = Int32Array.from(accept);
+    }
+    if (!(arg instanceof Uint8Array) && !(arg instanceof Int32Array)) throw new Error('createRowFilter: accept is a Uint8Array mask, an Int32Array / array of ords, or a function');
+    if (arg instanceof Uint8Array && arg.length !== n) throw new Error('createRowFilter: a mask has one entry per vector');
+    const r = native.filterCreate(targetVectors._deviceIndex(), arg);
+    this._h = r.handle;
+    this.count = r.count;
+  }
+  _handle() { if (!this._h) throw new Error('createRowFilter: the filter has been disposed'); return this._h; }
+  dispose() { if (this._h) { native.filterDestroy(this._h); this._h = null; } }
+}
+function createRowFilter(targetVectors, accept) { return new RowFilter(targetVectors, accept); }
+
 // candidates of the oversampled search with their true scores; host arrays follow the reference line by line,
 // a DeviceVectors handle moves the similarity loop to the GPU (missing vectors cannot occur there: rows < length)
 function rerankCandidates(query, results, vectors) {
@@ -857,7 +926,7 @@ module.exports = Object.assign({}, require('./helpers'), {
   BinaryQuantizationFormat, OptimizedScalarQuantizer, BinaryQuantizedScorer, MinHeap,
   createBinaryQuantizationFormat, quickQuantize, quickSearch,
   getOversampledTopKWithHeap, getOversampledTopKWithSort, getOversampledTopKBatch, computeCosineSimilarity,
-  DeviceVectors, createDeviceVectors, loadSiftVectors, loadSiftDataset, loadSiftQueries,
+  DeviceVectors, createDeviceVectors, RowFilter, createRowFilter, loadSiftVectors, loadSiftDataset, loadSiftQueries,
   normalizeVector, computeCentroid, computeDotProduct, computeEuclideanDistance, computeEuclideanSimilarity, computeMaximumInnerProduct,
   computeSimilarity, computeQuantizedDotProduct, computeInt4BitDotProduct: computeQuantizedDotProduct, computeInt1BitDotProduct: computeQuantizedDotProduct,
   deviceCount: native.deviceCount,

@@ -272,6 +272,105 @@ static napi_value SearchBatch(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* ---- filtered search (bbq_filter_*, bbq_search_filtered_batch) ---- */
+static void finalize_filter(napi_env env, void *data, void *hint) {
+  (void)env; (void)hint;
+  bbq_filter **box = (bbq_filter **)data;
+  if (*box) bbq_filter_destroy(*box);
+  free(box);
+}
+
+/* filterCreate(index handle, Uint8Array mask [size()] (non-zero = accepted) | Int32Array rows) -> {handle, count} */
+static napi_value FilterCreate(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  bool is = false;
+  napi_typedarray_type t;
+  napi_value ab;
+  size_t len, off;
+  void *data;
+  if (napi_is_typedarray(env, a[1], &is) != napi_ok || !is || napi_get_typedarray_info(env, a[1], &t, &len, &data, &ab, &off) != napi_ok ||
+      (t != napi_uint8_array && t != napi_int32_array)) {
+    napi_throw_type_error(env, NULL, "bbq_napi: a filter is a Uint8Array mask or an Int32Array of rows");
+    return NULL;
+  }
+  bbq_filter **box = (bbq_filter **)calloc(1, sizeof *box);
+  if (!box) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc;
+  if (t == napi_int32_array) {
+    rc = bbq_filter_create_rows(ix, (const int32_t *)data, (int64_t)len, box);
+  } else {
+    const int64_t n = bbq_index_size(ix), nw = (n + 63) / 64;
+    if ((int64_t)len != n) { free(box); napi_throw_range_error(env, NULL, "bbq_napi: a filter mask has one entry per row of the index"); return NULL; }
+    uint64_t *words = (uint64_t *)calloc((size_t)nw + 1, sizeof *words);
+    if (!words) { free(box); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+    for (int64_t r = 0; r < n; ++r)
+      if (((const uint8_t *)data)[r]) words[r >> 6] |= 1ull << (r & 63);
+    rc = bbq_filter_create(ix, words, nw, box);
+    free(words);
+  }
+  if (rc != BBQ_OK) { free(box); return throw_bbq(env, rc); }
+  napi_value ext, o, cnt;
+  if (napi_create_external(env, box, finalize_filter, NULL, &ext) != napi_ok) { bbq_filter_destroy(*box); free(box); napi_throw_error(env, NULL, "bbq_napi: external"); return NULL; }
+  NAPI_CALL(env, napi_create_object(env, &o));
+  NAPI_CALL(env, napi_create_double(env, (double)bbq_filter_count(*box), &cnt));
+  set_prop(env, o, "handle", ext); set_prop(env, o, "count", cnt);
+  return o;
+}
+
+/* filterDestroy(handle) */
+static napi_value FilterDestroy(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  void *p = NULL;
+  if (napi_get_value_external(env, a[0], &p) == napi_ok && p) {
+    bbq_filter **box = (bbq_filter **)p;
+    if (*box) { bbq_filter_destroy(*box); *box = NULL; }
+  }
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
+/* searchFilteredBatch(index handle, filter handle, nq, qquant, qcorr, queryBits, sim, k) -> as searchBatch, rows strided by min(k, |A|) */
+static napi_value SearchFilteredBatch(napi_env env, napi_callback_info info) {
+  napi_value a[8];
+  if (!get_args(env, info, 8, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *fp = NULL;
+  if (napi_get_value_external(env, a[1], &fp) != napi_ok || !fp || !*(bbq_filter **)fp) {
+    napi_throw_error(env, "BBQ1", "bbq_search_filtered_batch: the filter is null");
+    return NULL;
+  }
+  const bbq_filter *flt = *(bbq_filter **)fp;
+  void *qq, *qc; size_t ql, cl;
+  int64_t nq, qb, sim, k;
+  if (!get_i64(env, a[2], &nq) || !get_typed(env, a[3], napi_uint8_array, &qq, &ql) || !get_typed(env, a[4], napi_float64_array, &qc, &cl) ||
+      !get_i64(env, a[5], &qb) || !get_i64(env, a[6], &sim) || !get_i64(env, a[7], &k)) return NULL;
+  if (nq < 0 || ql != (size_t)nq * (size_t)bbq_index_dimension(ix) || cl != (size_t)nq * 4) {
+    napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return NULL;
+  }
+  if (k < 0) { napi_throw_error(env, "BBQ7", "k值不能为负数"); return NULL; }
+  int64_t keff = k < bbq_filter_count(flt) ? k : bbq_filter_count(flt);
+  void *oi, *os, *on;
+  napi_value ti = new_typed(env, napi_int32_array, (size_t)(nq * keff), 4, &oi);
+  napi_value ts = new_typed(env, napi_float32_array, (size_t)(nq * keff), 4, &os);
+  napi_value tn = new_typed(env, napi_float64_array, (size_t)nq, 8, &on);
+  if (!ti || !ts || !tn) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int64_t *cnt = (int64_t *)calloc((size_t)nq + 1, sizeof(int64_t));
+  if (!cnt) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_search_filtered_batch(ix, flt, (int32_t)nq, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff, (int32_t *)oi, (float *)os, cnt);
+  if (rc != BBQ_OK) { free(cnt); return throw_bbq(env, rc); }
+  for (int64_t i = 0; i < nq; ++i) ((double *)on)[i] = (double)cnt[i];
+  free(cnt);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "indices", ti); set_prop(env, o, "scores", ts); set_prop(env, o, "counts", tn);
+  napi_value kv; napi_create_double(env, (double)keff, &kv); set_prop(env, o, "stride", kv);
+  return o;
+}
+
 /* searchRawBatch(handle, nq, flat Float32Array[nq*dim] raw queries, centroid Float32Array[dim], sim, queryBits, lambda, iters, threads, k)
  *   -> {indices, scores, counts, stride}   (bbq_search_raw_batch: quantization on host threads pipelined with the sweeps) */
 static napi_value SearchRawBatch(napi_env env, napi_callback_info info) {
@@ -621,6 +720,9 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"indexBuild", NULL, IndexBuild, NULL, NULL, NULL, napi_default, NULL},
       {"indexDestroy", NULL, IndexDestroy, NULL, NULL, NULL, napi_default, NULL},
       {"searchBatch", NULL, SearchBatch, NULL, NULL, NULL, napi_default, NULL},
+      {"filterCreate", NULL, FilterCreate, NULL, NULL, NULL, napi_default, NULL},
+      {"filterDestroy", NULL, FilterDestroy, NULL, NULL, NULL, napi_default, NULL},
+      {"searchFilteredBatch", NULL, SearchFilteredBatch, NULL, NULL, NULL, napi_default, NULL},
       {"searchRawBatch", NULL, SearchRawBatch, NULL, NULL, NULL, napi_default, NULL},
       {"searchRawInto", NULL, SearchRawInto, NULL, NULL, NULL, napi_default, NULL},
       {"scoreRows", NULL, ScoreRows, NULL, NULL, NULL, napi_default, NULL},

@@ -106,6 +106,16 @@ class BinaryQuantizationFormat:
                                                           "additionalCorrection": qc[2], "quantizedComponentSum": qc[3]}}
 
     def searchNearestNeighbors(self, queryVector, targetVectors, k):
+        return self._search(queryVector, targetVectors, k, None)
+
+    def searchNearestNeighborsFiltered(self, queryVector, targetVectors, rowFilter, k):
+        """extension: searchNearestNeighbors over the rows `rowFilter` (createRowFilter) accepts - what the reference's loop
+        returns when it visits only those ords, ascending"""
+        if rowFilter is None:
+            raise Exception("行过滤器不能为空")
+        return self._search(queryVector, targetVectors, k, rowFilter)
+
+    def _search(self, queryVector, targetVectors, k, rowFilter):
         if queryVector is None:
             raise Exception("查询向量不能为空")
         if targetVectors is None:
@@ -124,7 +134,10 @@ class BinaryQuantizationFormat:
         try:
             qq, qc = capi.quantize_query(queryVector, targetVectors.getCentroid(), sim, self._config["queryBits"], self._lambda,
                                          self._iters, search_path=True)
-            idx, sc = targetVectors._device().search(qq, qc, self._config["queryBits"], sim, k)
+            if rowFilter is None:
+                idx, sc = targetVectors._device().search(qq, qc, self._config["queryBits"], sim, k)
+            else:
+                idx, sc = targetVectors._device().search_filtered(qq, qc, self._config["queryBits"], sim, k, rowFilter)
         except capi.BBQError as e:
             raise Exception(str(e))
         return [{"index": int(i), "score": float(s)} for i, s in zip(idx, sc)]
@@ -141,6 +154,17 @@ def quickQuantize(vectors, similarityFunction=VectorSimilarityFunction.COSINE):
 def quickSearch(queryVector, targetVectors, k, similarityFunction=VectorSimilarityFunction.COSINE):
     f = BinaryQuantizationFormat({"quantizer": {"similarityFunction": similarityFunction, "lambda": 0.1, "iters": 5}})
     return f.searchNearestNeighbors(queryVector, f.quantizeVectors(targetVectors)["quantizedVectors"], k)
+
+
+def createRowFilter(targetVectors, accept):
+    """extension: an accept set of `targetVectors` for searchNearestNeighborsFiltered; `accept` is a bool mask of length size(), an
+    array of ords, or a predicate ord -> bool.  Returns a capi.Filter (.count, .close(), context manager)."""
+    if callable(accept):
+        accept = np.fromiter((bool(accept(i)) for i in range(targetVectors.size())), np.bool_, targetVectors.size())
+    try:
+        return capi.Filter(targetVectors._device(), accept)
+    except capi.BBQError as e:
+        raise Exception(str(e))
 
 
 def createDeviceVectors(vectors, device=0):

@@ -26,6 +26,7 @@ SYMBOLS = [
     "bbq_index_create_shard_opts", "bbq_index_create_multi_opts", "bbq_index_build_opts",
     "bbq_shard_scan_begin", "bbq_shard_scan_wait", "bbq_merge_answers", "bbq_key_of_score", "bbq_index_load_multi", "bbq_index_file_shards",
     "bbq_search_raw_batch",
+    "bbq_filter_create", "bbq_filter_create_rows", "bbq_filter_destroy", "bbq_filter_count", "bbq_search_filtered_batch", "bbq_filter_plan",
 ]
 
 
@@ -98,6 +99,14 @@ def lib():
     L.bbq_search_batch.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp]
     L.bbq_search_raw_batch.argtypes = [vp, i32, vp, vp, i32, i32, dbl, i32, i32, i64, vp, vp, vp, vp, vp, C.POINTER(i32)]
     L.bbq_score_rows.argtypes = [vp, vp, vp, i32, i32, i64, i64, vp, vp, vp]
+    L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
+    L.bbq_filter_create_rows.argtypes = [vp, vp, i64, C.POINTER(vp)]
+    L.bbq_filter_destroy.argtypes = [vp]
+    L.bbq_filter_destroy.restype = None
+    L.bbq_filter_count.argtypes = [vp]
+    L.bbq_filter_count.restype = i64
+    L.bbq_filter_plan.argtypes = [vp, i64, i64, i64, i32, i32, vp, C.POINTER(i32)]
+    L.bbq_search_filtered_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, i64, vp, vp, vp]
     L.bbq_shard_scan.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, i64, vp, vp, C.POINTER(i64)]
     L.bbq_shard_scan_begin.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, i64, vp, vp, vp, i64]
     L.bbq_shard_scan_wait.argtypes = [vp, C.POINTER(i64)]
@@ -338,6 +347,26 @@ class Index:
         _chk(lib().bbq_search_batch(self._h, nq, _ptr(qq), _ptr(qc), query_bits, sim, k, _ptr(idx), _ptr(sc), _ptr(cnt)))
         return idx, sc, cnt
 
+    def search_filtered(self, qquant, qcorr, query_bits, sim, k, flt):
+        """bbq_search restricted to the rows `flt` (a Filter of this index) accepts"""
+        idx, sc, n = self.search_filtered_batch(np.asarray(qquant)[None, :], np.asarray(qcorr)[None, :], query_bits, sim, k, flt)
+        return idx[0, :n[0]], sc[0, :n[0]]
+
+    def search_filtered_batch(self, qquant, qcorr, query_bits, sim, k, flt):
+        """bbq_search_filtered_batch: search_batch over the accepted rows only; one filter serves every query of the call"""
+        qq = np.ascontiguousarray(qquant, np.uint8)
+        qc = np.ascontiguousarray(qcorr, np.float64)
+        nq = qq.shape[0]
+        if nq and qq.shape[1] != self.dim:
+            raise BBQError(ERR_DIM_MISMATCH, "查询向量维度与目标向量维度不匹配")
+        kk = max(int(k), 0)
+        idx = np.zeros((nq, kk), np.int32)
+        sc = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.int64)
+        _chk(lib().bbq_search_filtered_batch(self._h, flt._h if flt is not None else None, nq, _ptr(qq), _ptr(qc), query_bits, sim, k,
+                                            _ptr(idx), _ptr(sc), _ptr(cnt)))
+        return idx, sc, cnt
+
     def search_raw_batch(self, queries, centroid, sim, query_bits, k, lam=0.1, iters=5, n_threads=0, want_quantized=False):
         """searchNearestNeighbors from raw fp32 queries [nq, dim]: quantization on host threads pipelined with the sweeps
         (bbq_search_raw_batch).  Returns (idx, score, count[, qquant, qcorr])."""
@@ -422,6 +451,68 @@ def file_info(path_prefix):
     n, dim, sim, cdp, rb = C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_double(0), C.c_int64(0)
     _chk(lib().bbq_index_file_info(os.fsencode(path_prefix), C.byref(n), C.byref(dim), C.byref(sim), C.byref(cdp), C.byref(rb)))
     return {"n_rows": n.value, "dim": dim.value, "sim": sim.value, "centroid_dp": cdp.value, "row_base": rb.value}
+
+
+def pack_mask(mask):
+    """a bool mask over the rows -> the accept words of bbq_filter_create: row r is bit r & 63 of word r >> 6"""
+    m = np.ascontiguousarray(mask, np.bool_).ravel()
+    padded = np.zeros((m.shape[0] + 63) // 64 * 64, np.bool_)
+    padded[:m.shape[0]] = m
+    return np.ascontiguousarray(np.packbits(padded, bitorder="little")).view("<u8")
+
+
+def filter_plan(mask, k_dev, first_segment_rows=4096, growth=8):
+    """the segments a filtered call sweeps for this mask (bbq_filter_plan; host only): [(first chunk, chunks, slots per chunk)]"""
+    words = pack_mask(mask)
+    segs = np.zeros((64, 3), np.int64)
+    n = C.c_int32(0)
+    _chk(lib().bbq_filter_plan(_ptr(words), len(mask), k_dev, first_segment_rows, growth, 64, _ptr(segs), C.byref(n)))
+    return [tuple(int(v) for v in row) for row in segs[:n.value]]
+
+
+class Filter:
+    """an accept set of one Index, resident on its device (bbq_filter_*): `mask_or_rows` is a bool mask of length index.n or
+    an integer array of row ids (any order, duplicates allowed).  Read-only after creation; any number of searches may share it."""
+
+    def __init__(self, index, mask_or_rows):
+        a = np.asarray(mask_or_rows)
+        h = C.c_void_p()
+        if a.dtype == np.bool_:
+            if a.ndim != 1 or a.shape[0] != index.n:
+                raise BBQError(ERR_INVALID_ARG, "a filter mask has one entry per row of the index")
+            words = pack_mask(a)
+            _chk(lib().bbq_filter_create(index._h, _ptr(words), words.shape[0], C.byref(h)))
+        else:
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise BBQError(ERR_INVALID_ARG, "a filter is a bool mask or an array of row ids")
+            wide = np.asarray(a, np.int64).ravel()
+            if wide.size and (wide.min() < -2**31 or wide.max() >= 2**31):
+                raise BBQError(ERR_INVALID_ARG, "向量索引 %d 不存在" % int(wide.max() if wide.max() >= 2**31 else wide.min()))
+            rows = np.ascontiguousarray(wide, np.int32)
+            _chk(lib().bbq_filter_create_rows(index._h, _ptr(rows), rows.shape[0], C.byref(h)))
+        self._h = h
+
+    @property
+    def count(self):
+        """|A|: the rows the filter accepts"""
+        return int(lib().bbq_filter_count(self._h)) if self._h else 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().bbq_filter_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Vectors:

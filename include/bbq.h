@@ -32,7 +32,8 @@ extern "C" {
 
 #define BBQ_ABI_VERSION 3  /* 2: multi-bit and multi-device indexes, bbq_stats.host_replays
                               3: creation options (corrections layout), asynchronous shard scans with shard-local answers,
-                                 bbq_merge_answers, persistence of shards and multi-device indexes */
+                                 bbq_merge_answers, persistence of shards and multi-device indexes
+                              (still 3: filtered search - bbq_filter_*, bbq_search_filtered_batch - only adds symbols) */
 
 /* status codes */
 enum {
@@ -204,6 +205,35 @@ int bbq_search_batch(bbq_index *idx, int32_t n_queries, const uint8_t *qquant, c
 int bbq_search_raw_batch(bbq_index *idx, int32_t n_queries, const float *queries, const float *centroid, int32_t sim,
                          int32_t query_bits, double lambda, int32_t iters, int32_t n_threads, int64_t k, int32_t *out_idx,
                          float *out_score, int64_t *out_n, uint8_t *qquant_out, double *qcorr_out, int32_t *bad_query);
+
+/* ------------------------------------------------------------------------------------------
+ * Filtered search (new; the reference has no filter): exact top-k over a subset A of the rows - rows deleted since the build, one
+ * tenant's rows, the rows a metadata predicate accepts.  The result is what the reference's searchNearestNeighbors loop
+ * (src/binaryQuantizationFormat.ts:349-411) returns when it visits only the ords in A, ascending, each pushed with its original ord
+ * and its f32 score, with a heap of min(k, |A|): indices, score bits and order match bit for bit, ties included
+ * (DESIGN.md "Filtered search").  |A| == 0 or k == 0 -> *out_n = 0; k < 0 -> BBQ_ERR_NEGATIVE_K; k > |A| -> |A| results.
+ * A filter belongs to ONE single-device index (its size, its device), owns its device memory, is read-only after creation and may
+ * be shared by any number of calls and threads.  Using it with an index of another size or device: BBQ_ERR_INVALID_ARG.
+ * Out of scope: a multi-device handle (bbq_index_create_multi), a non-root shard and an index with a pilot replica return
+ * BBQ_ERR_UNSUPPORTED.  A filtered call always takes the pipelined per-query sweep (sweep_share and the latency_* options do not
+ * change its path); k > 4096 and force_dense take the dense path over the accepted rows. */
+typedef struct bbq_filter bbq_filter;   /* opaque: an accept set of one index, resident on that index's device */
+/* accept_bits [ceil(n_rows/64)] little-endian words: row r is accepted iff (accept_bits[r >> 6] >> (r & 63)) & 1; bits at and beyond
+ * n_rows are ignored.  n_words must be ceil(bbq_index_size(idx)/64). */
+int bbq_filter_create(bbq_index *idx, const uint64_t *accept_bits, int64_t n_words, bbq_filter **out);
+/* the same from a list of global row ids (any order, duplicates allowed; a row outside the index: BBQ_ERR_INVALID_ARG) */
+int bbq_filter_create_rows(bbq_index *idx, const int32_t *rows, int64_t n, bbq_filter **out);
+void bbq_filter_destroy(bbq_filter *f);
+int64_t bbq_filter_count(const bbq_filter *f);      /* |A| */
+/* Host-only introspection (no device needed): the segments a filtered call sweeps for an index of n_rows rows and this accept set
+ * (accept_bits as bbq_filter_create takes them), with rank k_dev (min(k, |A|), + 1 when the device selects the answer) and the options
+ * first_segment_rows / segment_growth (bbq_set_option).  segments [max_segments][3] = {first chunk, chunks, candidate slots per chunk}
+ * (512-row chunks); *out_n = their number (0: nothing accepted).  What tests/test_filtered_cpu.py holds its numpy restatement to. */
+int bbq_filter_plan(const uint64_t *accept_bits, int64_t n_rows, int64_t k_dev, int64_t first_segment_rows, int32_t growth,
+                    int32_t max_segments, int64_t *segments, int32_t *out_n);
+/* bbq_search_batch restricted to f (arguments and outputs as bbq_search_batch); one filter serves all queries of the call */
+int bbq_search_filtered_batch(bbq_index *idx, const bbq_filter *f, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
+                              int32_t query_bits, int32_t sim, int64_t k, int32_t *out_idx, float *out_score, int64_t *out_n);
 
 /* Per-row results of computeBatchQuantizedScores (src/binaryQuantizedScorer.ts:389-400) for the
  * contiguous ords [row_begin, row_begin+row_count): bitDotProduct (integer qcDist), the f64 score and
