@@ -109,6 +109,7 @@ int bbq_index_build_opts(const float *vectors, int64_t n, int32_t dim, int32_t s
   const int64_t n_tiles = npad / kTileRows;
   HIPCHK(sto.d_tiles.alloc((size_t)n_tiles * ix->tile_stride));
   if (ix->layout == kLayoutCompact) HIPCHK(sto.d_exact.alloc((size_t)compact_side_bytes(n_tiles) / 8));
+  sto.cap_tiles = n_tiles;
   if (corr) HIPCHK(d_corr.alloc((size_t)n * 4));
   HIPCHK(launch_build_quantize1(d_vT4, n, dim, npad, d_cen, sim, lambda, iters, sto.d_tiles, sto.d_exact, d_corr, ix->w16, ix->tile_stride,
                               ix->layout, st));  // :221-249

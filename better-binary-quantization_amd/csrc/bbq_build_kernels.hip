@@ -209,15 +209,19 @@ __device__ __forceinline__ double loss_pass(const f32x4 *__restrict__ col, int64
 }
 
 // bits == 1 packs the row straight into the scan layout; bits > 1 writes what the reference keeps for such an index - one byte per
-// dimension (src/binaryQuantizationFormat.ts:241-245) - to out.codes_rm, and the caller builds the tile records from that
+// dimension (src/binaryQuantizationFormat.ts:241-245) - to out.codes_rm, and the caller builds the tile records from that.
+// Vector i becomes row row0 + i of the storage (row0 > 0: an append into the partly filled last tile; lanes below row0 are not
+// touched).  n_out threads write: the n vectors and the padding lanes up to the end of the last tile - with row0 > 0 that can be
+// more than npad, the columns of vT4, which only the valid threads read.
 __global__ __launch_bounds__(256) void bbq_quantize1_kernel(const f32x4 *__restrict__ vT4, int64_t n, int32_t dim, int32_t dim4,
                                                            int64_t npad, const float *__restrict__ centroid, int32_t sim,
-                                                           double lambda, int32_t iters, int32_t bits, BuildOut out) {
+                                                           double lambda, int32_t iters, int32_t bits, BuildOut out, int64_t row0,
+                                                           int64_t n_out) {
   extern __shared__ float s_cen[];
   for (int i = threadIdx.x; i < dim4 * 4; i += 256) s_cen[i] = i < dim ? centroid[i] : 0.f;
   __syncthreads();
   const int64_t vec = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (vec >= npad) return;
+  if (vec >= n_out) return;
   const bool valid = vec < n;
   const f32x4 *__restrict__ col = vT4 + vec;
   const double ddim = (double)dim;
@@ -356,8 +360,9 @@ __global__ __launch_bounds__(256) void bbq_quantize1_kernel(const f32x4 *__restr
 
   // final pass (:192-216): 1-bit threshold at the interval midpoint, packed MSB-first (packAsBinary :420-446) straight into
   // the tile record: 16-byte chunk j of row r at (j*64 + r)*16
-  const int64_t tile = vec / kTileRows;
-  const int r = (int)(vec % kTileRows);
+  const int64_t row = row0 + vec;
+  const int64_t tile = row / kTileRows;
+  const int r = (int)(row % kTileRows);
   uint8_t *tp = out.tiles + tile * (int64_t)out.tile_stride;
   const double a = iv0, b = iv1;
   const double thr = (a + b) / 2;
@@ -400,7 +405,7 @@ __global__ __launch_bounds__(256) void bbq_quantize1_kernel(const f32x4 *__restr
   if (out.layout == kLayoutCompact) {
     // the tiles' additive-correction ranges are computed afterwards from exact[] (launch_tile_add_range)
     reinterpret_cast<uint32_t *>(cr)[r] = (__float_as_uint((float)lower) >> 16) | ((__float_as_uint((float)upper) >> 16) << 16);
-    double *e = out.exact + vec * 4;
+    double *e = out.exact + row * 4;
     e[0] = lower; e[1] = upper; e[2] = add; e[3] = 0.0;
   } else {
     f64x2b lu = {lower, upper};
@@ -415,15 +420,16 @@ __global__ __launch_bounds__(256) void bbq_quantize1_kernel(const f32x4 *__restr
 
 // ------------------------------------------------------------------------------------------------ untile (codes for the host)
 __global__ __launch_bounds__(256) void bbq_untile_kernel(const uint8_t *__restrict__ tiles, int64_t n, int32_t pb, int32_t w16,
-                                                        int32_t tile_stride, uint8_t *__restrict__ codes_rm) {
+                                                        int32_t tile_stride, uint8_t *__restrict__ codes_rm, int64_t row0) {
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = gid / w16;
+  const int64_t i = gid / w16;  // row row0 + i of the storage -> row i of codes_rm
   const int j = (int)(gid % w16);
-  if (row >= n) return;
+  if (i >= n) return;
+  const int64_t row = row0 + i;
   const uint8_t *tp = tiles + (row / kTileRows) * (int64_t)tile_stride;
   const u32x4b c = reinterpret_cast<const u32x4b *>(tp)[j * kTileRows + (int)(row % kTileRows)];
   const uint32_t w[4] = {c.x, c.y, c.z, c.w};
-  uint8_t *dst = codes_rm + row * (int64_t)pb;
+  uint8_t *dst = codes_rm + i * (int64_t)pb;
   for (int b = 0; b < 16; ++b) {
     const int byte = j * 16 + b;
     if (byte < pb) dst[byte] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
@@ -456,11 +462,12 @@ hipError_t launch_build_centroid(const float *vT4, int64_t n, int32_t dim, int64
 }
 hipError_t launch_build_quantize1(const float *vT4, int64_t n, int32_t dim, int64_t npad, const float *centroid, int32_t sim,
                                   double lambda, int32_t iters, uint8_t *tiles, double *exact, double *corr_rm, int32_t w16,
-                                  int32_t tile_stride, int32_t layout, hipStream_t s) {
+                                  int32_t tile_stride, int32_t layout, hipStream_t s, int64_t row0) {
   const int dim4 = (dim + 3) / 4;
   BuildOut o{tiles, exact, corr_rm, nullptr, w16, tile_stride, layout};
-  hipLaunchKernelGGL(bbq_quantize1_kernel, dim3((unsigned)(npad / 256 + (npad % 256 ? 1 : 0))), dim3(256), (size_t)dim4 * 16, s,
-                     reinterpret_cast<const f32x4 *>(vT4), n, dim, dim4, npad, centroid, sim, lambda, iters, 1, o);
+  const int64_t n_out = (row0 + n + kTileRows - 1) / kTileRows * kTileRows - row0;  // row0 = 0: npad
+  hipLaunchKernelGGL(bbq_quantize1_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), (size_t)dim4 * 16, s,
+                     reinterpret_cast<const f32x4 *>(vT4), n, dim, dim4, npad, centroid, sim, lambda, iters, 1, o, row0, n_out);
   return hipGetLastError();
 }
 hipError_t launch_build_quantize_bits(const float *vT4, int64_t n, int32_t dim, int64_t npad, const float *centroid, int32_t sim,
@@ -468,14 +475,14 @@ hipError_t launch_build_quantize_bits(const float *vT4, int64_t n, int32_t dim, 
   const int dim4 = (dim + 3) / 4;
   BuildOut o{nullptr, nullptr, corr_rm, codes_rm, 0, 0, 0};
   hipLaunchKernelGGL(bbq_quantize1_kernel, dim3((unsigned)(npad / 256 + (npad % 256 ? 1 : 0))), dim3(256), (size_t)dim4 * 16, s,
-                     reinterpret_cast<const f32x4 *>(vT4), n, dim, dim4, npad, centroid, sim, lambda, iters, bits, o);
+                     reinterpret_cast<const f32x4 *>(vT4), n, dim, dim4, npad, centroid, sim, lambda, iters, bits, o, (int64_t)0, npad);
   return hipGetLastError();
 }
 hipError_t launch_build_untile(const uint8_t *tiles, int64_t n, int32_t pb, int32_t w16, int32_t tile_stride, uint8_t *codes_rm,
-                               hipStream_t s) {
+                               hipStream_t s, int64_t row0) {
   const int64_t threads = n * w16;
   if (threads <= 0) return hipSuccess;
-  hipLaunchKernelGGL(bbq_untile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, tiles, n, pb, w16, tile_stride, codes_rm);
+  hipLaunchKernelGGL(bbq_untile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, tiles, n, pb, w16, tile_stride, codes_rm, row0);
   return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 //   bbq_shard.cpp    scan of one shard of a row-sharded index (bbq_shard_scan*)
 //   bbq_multi.cpp    one index over several devices of a process
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
+//   bbq_append.cpp   rows appended to an index in place, capacity (bbq_index_append*, bbq_index_reserve)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
 // bbq_entry.h is the codec of the 64-bit entries, keys and answer headers; bbq_workqueue.h the host threads' job queue.
@@ -39,6 +40,8 @@ struct Storage {
   DevBuf<uint8_t> d_tiles;
   DevBuf<double> d_exact;     // kLayoutCompact: exact corrections, gathered for the rows whose bound passes; the per-tile
                               // additive-correction ranges (view.add_range) live behind them in the same allocation
+  int64_t cap_tiles = 0;      // tiles both allocations hold (>= the tiles in use; more after bbq_index_reserve / an append that grew):
+                              // exact[] takes cap_tiles * 64 rows and add_range[] starts behind THAT, wherever the rows end
   IndexView view{};
   int64_t row_id_base = 0;
   int64_t n_chunks() const { return (view.n_rows + kChunkRows - 1) / kChunkRows; }
@@ -150,10 +153,11 @@ int get_ctx(int device, DeviceCtx **out);
 int ensure_aux_qbuf(DeviceCtx *c, int64_t bytes);
 // default number of host threads (heap replays, query quantization): half the cores, at most 16
 inline int default_host_threads() { return (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2)); }
-// bytes of the compact layout's side arrays for n_tiles tiles: exact corrections + add ranges
+// bytes of the compact layout's side arrays for n_tiles tiles: exact corrections + add ranges (an allocation: n_tiles = its capacity;
+// a file: the tiles in use, the two parts back to back)
 inline int64_t compact_side_bytes(int64_t n_tiles) { return n_tiles * kTileRows * 32 + n_tiles * 8; }
-inline const float *add_range_of(const double *d_exact, int64_t n_tiles) {
-  return d_exact ? reinterpret_cast<const float *>(d_exact + n_tiles * kTileRows * 4) : nullptr;
+inline const float *add_range_of(const double *d_exact, int64_t cap_tiles) {
+  return d_exact ? reinterpret_cast<const float *>(d_exact + cap_tiles * kTileRows * 4) : nullptr;
 }
 
 }  // namespace bbq
@@ -238,7 +242,7 @@ LaunchView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin = 
 // retires what the device still runs for the index and deletes it (its members release their memory); the device context (streams,
 // workspace) stays.  Call with the context mutex held.
 void destroy_unlocked(bbq_index *ix);
-// the view of a storage whose buffers are in place: its rows + the geometry of the index (layout, tile_stride, has_x1 decided)
+// the view of a storage whose buffers (and cap_tiles) are in place: its rows + the geometry of the index (layout, tile_stride, has_x1 decided)
 inline void set_storage_view(const bbq_index *ix, Storage &st, int64_t n_rows, int64_t row_id_base) {
   st.row_id_base = row_id_base;
   st.view.n_rows = n_rows;
@@ -250,7 +254,7 @@ inline void set_storage_view(const bbq_index *ix, Storage &st, int64_t n_rows, i
   st.view.store_bits = ix->store_bits;
   st.view.tiles = st.d_tiles;
   st.view.exact = st.d_exact;
-  st.view.add_range = add_range_of(st.d_exact, (n_rows + kTileRows - 1) / kTileRows);
+  st.view.add_range = add_range_of(st.d_exact, st.cap_tiles);
 }
 // rows already in device memory (codes in the caller's shape: packed bits, or one byte per dimension for a multi-bit index;
 // corrections [n][4]) -> tile records of `st`, deciding the index's layout on the way.  Context mutex held by the caller.

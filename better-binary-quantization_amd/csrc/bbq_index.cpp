@@ -128,6 +128,7 @@ int storage_from_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes,
   if (n_tiles > 0) {
     HIPCHK(st.d_tiles.alloc((size_t)(n_tiles * ix->tile_stride)));
     if (ix->layout == kLayoutCompact) HIPCHK(st.d_exact.alloc((size_t)compact_side_bytes(n_tiles) / 8));
+    st.cap_tiles = n_tiles;
     if (multibit) {
       uint32_t bad = 0;
       HIPCHK(d_mis.reserve(1));

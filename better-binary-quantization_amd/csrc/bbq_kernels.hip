@@ -412,15 +412,18 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_finalize_kernel(const Fi
 
 // ---------------------------------------------------------------------------------------------------
 // index build: row-major (codes [n][pb], corr [n][4]) -> tile records.  One thread per (row, chunk).
+// The rows handed over are the global rows [row0, n_rows) (row0 = 0: a creation; row0 = the old size: an append, DESIGN.md
+// "Appending rows"): thread (i, j) owns global row row0 + i, lanes below row0 are not touched, lanes from n_rows up to the end of the
+// last tile are written as padding.
 
 __device__ __forceinline__ uint32_t bf16_trunc_bits(double v) { return __float_as_uint((float)v) >> 16; }
 
 __global__ __launch_bounds__(256) void bbq_retile_kernel(const uint8_t *__restrict__ codes, const double *__restrict__ corr,
                                                         int64_t n_rows, int32_t pb, uint8_t *__restrict__ tiles, int32_t w16,
                                                         int32_t tile_stride, int32_t has_x1, int64_t n_rows_padded, int32_t layout,
-                                                        double *__restrict__ exact) {
+                                                        double *__restrict__ exact, int64_t row0) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t row = gid / (w16 + 1);
+  const int64_t row = row0 + gid / (w16 + 1);
   const int j = (int)(gid % (w16 + 1));
   if (row >= n_rows_padded) return;
   const int64_t tile = row / kTileRows;
@@ -430,7 +433,7 @@ __global__ __launch_bounds__(256) void bbq_retile_kernel(const uint8_t *__restri
     u32x4 v = {0, 0, 0, 0};
     if (row < n_rows) {
       uint32_t w[4] = {0, 0, 0, 0};
-      const uint8_t *src = codes + row * (int64_t)pb;
+      const uint8_t *src = codes + (row - row0) * (int64_t)pb;
       for (int b = 0; b < 16; ++b) {
         const int byte = j * 16 + b;
         if (byte < pb) w[b >> 2] |= (uint32_t)src[byte] << (8 * (b & 3));
@@ -443,7 +446,8 @@ __global__ __launch_bounds__(256) void bbq_retile_kernel(const uint8_t *__restri
     f64x2 lu = {0.0, 0.0};
     double add = 0.0, x1 = 0.0;
     if (row < n_rows) {
-      lu.x = corr[row * 4 + 0]; lu.y = corr[row * 4 + 1]; add = corr[row * 4 + 2]; x1 = corr[row * 4 + 3];
+      const double *c = corr + (row - row0) * 4;
+      lu.x = c[0]; lu.y = c[1]; add = c[2]; x1 = c[3];
     }
     if (layout == kLayoutCompact) {
       reinterpret_cast<uint32_t *>(cr)[r] = bf16_trunc_bits(lu.x) | (bf16_trunc_bits(lu.y) << 16);  // the additive term: bbq_tile_add_range_kernel
@@ -462,9 +466,9 @@ __global__ __launch_bounds__(256) void bbq_retile_kernel(const uint8_t *__restri
 __global__ __launch_bounds__(256) void bbq_retile_multibit_kernel(const uint8_t *__restrict__ codes, const double *__restrict__ corr,
                                                                  int64_t n_rows, int32_t dim, int32_t store_bits, int32_t index_bits, uint8_t *__restrict__ tiles,
                                                                  int32_t w16, int32_t tile_stride, int32_t has_x1, int64_t n_rows_padded,
-                                                                 int32_t layout, double *__restrict__ exact, uint32_t *__restrict__ bad) {
+                                                                 int32_t layout, double *__restrict__ exact, uint32_t *__restrict__ bad, int64_t row0) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t row = gid / (w16 + 1);
+  const int64_t row = row0 + gid / (w16 + 1);
   const int j = (int)(gid % (w16 + 1));
   if (row >= n_rows_padded) return;
   const int64_t tile = row / kTileRows;
@@ -474,7 +478,7 @@ __global__ __launch_bounds__(256) void bbq_retile_multibit_kernel(const uint8_t 
     uint32_t w[4] = {0, 0, 0, 0};
     if (row < n_rows) {
       const int per_dword = 32 / store_bits;
-      const uint8_t *src = codes + row * (int64_t)dim;
+      const uint8_t *src = codes + (row - row0) * (int64_t)dim;
       const uint32_t limit = 1u << index_bits, field = (1u << store_bits) - 1u;  // values of an indexBits-bit quantizer are < 2^indexBits (include/bbq.h)
       for (int t = 0; t < 4; ++t)
         for (int f = 0; f < per_dword; ++f) {
@@ -493,7 +497,8 @@ __global__ __launch_bounds__(256) void bbq_retile_multibit_kernel(const uint8_t 
     f64x2 lu = {0.0, 0.0};
     double add = 0.0, x1 = 0.0;
     if (row < n_rows) {
-      lu.x = corr[row * 4 + 0]; lu.y = corr[row * 4 + 1]; add = corr[row * 4 + 2]; x1 = corr[row * 4 + 3];
+      const double *c = corr + (row - row0) * 4;
+      lu.x = c[0]; lu.y = c[1]; add = c[2]; x1 = c[3];
     }
     if (layout == kLayoutCompact) {
       reinterpret_cast<uint32_t *>(cr)[r] = bf16_trunc_bits(lu.x) | (bf16_trunc_bits(lu.y) << 16);
@@ -520,9 +525,11 @@ __global__ __launch_bounds__(256) void bbq_check_x1_multibit_kernel(const uint8_
 
 // compact layout: {min, max} of additionalCorrection over the valid rows of each tile, as f32 (one wave per tile; the f32
 // rounding is inside the bound's allowance for the additive term).  A NaN anywhere makes both ends NaN: no bound, exact path.
-__global__ __launch_bounds__(256) void bbq_tile_add_range_kernel(const double *__restrict__ exact, int64_t n_rows, float *__restrict__ add_range) {
+// Runs over the tiles [tile0, ceil(n_rows / 64)): an append starts at the tile its first new row lands in.
+__global__ __launch_bounds__(256) void bbq_tile_add_range_kernel(const double *__restrict__ exact, int64_t n_rows, float *__restrict__ add_range,
+                                                                 int64_t tile0) {
   const int lane = threadIdx.x & 63;
-  const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t tile = tile0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
   if (tile >= n_tiles) return;
   const int64_t row = tile * kTileRows + lane;
@@ -540,6 +547,14 @@ __global__ __launch_bounds__(256) void bbq_tile_add_range_kernel(const double *_
     add_range[tile * 2] = nan ? __uint_as_float(0x7fc00000u) : (float)lo;
     add_range[tile * 2 + 1] = nan ? __uint_as_float(0x7fc00000u) : (float)hi;
   }
+}
+
+// is every code of these multi-bit rows below 2^index_bits?  What bbq_retile_multibit_kernel reports while it writes, asked BEFORE
+// anything is written: an append that fails leaves the index as it was
+__global__ __launch_bounds__(256) void bbq_check_code_range_kernel(const uint8_t *__restrict__ codes, int64_t count, uint32_t limit,
+                                                                   uint32_t *__restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count && codes[i] >= limit) atomicOr(bad, 1u);
 }
 
 // does quantizedComponentSum equal the row's popcount everywhere? (then it need not be stored)
@@ -682,24 +697,25 @@ hipError_t launch_pack(const int32_t *counts, const uint64_t *lists, int64_t lis
 }
 
 hipError_t launch_retile(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t pb, uint8_t *tiles, int32_t w16,
-                         int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, hipStream_t s) {
+                         int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, hipStream_t s, int64_t row0) {
   const int64_t n_pad = (n_rows + kTileRows - 1) / kTileRows * kTileRows;
-  const int64_t threads = n_pad * (w16 + 1);
-  if (threads == 0) return hipSuccess;
+  const int64_t threads = (n_pad - row0) * (w16 + 1);
+  if (threads <= 0) return hipSuccess;
   const int64_t blocks = (threads + 255) / 256;
   hipLaunchKernelGGL(bbq_retile_kernel, dim3((unsigned)blocks), dim3(256), 0, s, codes, corr, n_rows, pb, tiles, w16, tile_stride,
-                     has_x1, n_pad, layout, exact);
+                     has_x1, n_pad, layout, exact, row0);
   return hipGetLastError();
 }
 
 hipError_t launch_retile_multibit(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t store_bits, int32_t index_bits, uint8_t *tiles,
-                                  int32_t w16, int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, uint32_t *bad, hipStream_t s) {
+                                  int32_t w16, int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, uint32_t *bad, hipStream_t s,
+                                  int64_t row0) {
   const int64_t n_pad = (n_rows + kTileRows - 1) / kTileRows * kTileRows;
-  const int64_t threads = n_pad * (w16 + 1);
-  if (threads == 0) return hipSuccess;
+  const int64_t threads = (n_pad - row0) * (w16 + 1);
+  if (threads <= 0) return hipSuccess;
   const int64_t blocks = (threads + 255) / 256;
   hipLaunchKernelGGL(bbq_retile_multibit_kernel, dim3((unsigned)blocks), dim3(256), 0, s, codes, corr, n_rows, dim, store_bits, index_bits, tiles, w16,
-                     tile_stride, has_x1, n_pad, layout, exact, bad);
+                     tile_stride, has_x1, n_pad, layout, exact, bad, row0);
   return hipGetLastError();
 }
 
@@ -710,10 +726,16 @@ hipError_t launch_check_x1_multibit(const uint8_t *codes, const double *corr, in
   return hipGetLastError();
 }
 
-hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s) {
-  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
-  if (n_tiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(bbq_tile_add_range_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, exact, n_rows, add_range);
+hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0) {
+  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows - tile0;
+  if (n_tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_tile_add_range_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, exact, n_rows, add_range, tile0);
+  return hipGetLastError();
+}
+
+hipError_t launch_check_code_range(const uint8_t *codes, int64_t count, int32_t index_bits, uint32_t *bad, hipStream_t s) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_check_code_range_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, codes, count, 1u << index_bits, bad);
   return hipGetLastError();
 }
 

@@ -238,9 +238,13 @@ int bbq_index_save(bbq_index *ix, const char *prefix, const float *centroid, int
     if (!fc.f) return fail(BBQ_ERR_INVALID_ARG, "cannot create %s", dpath.c_str());
     const size_t piece = 64u << 20;  // multiple of 8: the checksum words never straddle pieces
     std::vector<uint8_t> buf(piece);
-    const uint8_t *src[4] = {ix->main.d_tiles, (const uint8_t *)ix->main.d_exact.get(), ix->pilot.d_tiles, (const uint8_t *)ix->pilot.d_exact.get()};
-    const int64_t len[4] = {h.tilesBytes, h.exactBytes, px.pilotTilesBytes, px.pilotExactBytes};
-    for (int part = 0; part < 4; ++part) {
+    // the side arrays of a storage with spare capacity are not back to back in memory (Storage::cap_tiles): exact[] and add_range[]
+    // are written one after the other, so the file holds compact_side_bytes(n_tiles) whatever the capacity is
+    const int64_t exact_rows_bytes = h.exactBytes ? n_tiles * kTileRows * 32 : 0;
+    const uint8_t *src[5] = {ix->main.d_tiles, (const uint8_t *)ix->main.d_exact.get(), (const uint8_t *)ix->main.view.add_range, ix->pilot.d_tiles,
+                             (const uint8_t *)ix->pilot.d_exact.get()};
+    const int64_t len[5] = {h.tilesBytes, exact_rows_bytes, h.exactBytes - exact_rows_bytes, px.pilotTilesBytes, px.pilotExactBytes};
+    for (int part = 0; part < 5; ++part) {
       for (int64_t o = 0; o < len[part]; o += (int64_t)piece) {
         const size_t m = (size_t)std::min<int64_t>((int64_t)piece, len[part] - o);
         HIPCHK(hipMemcpy(buf.data(), src[part] + o, m, hipMemcpyDeviceToHost));
@@ -397,6 +401,8 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
     }
   }
   if (dsum != want_sum) return bail(fail(BBQ_ERR_INVALID_ARG, "%s: vector data checksum mismatch", dpath.c_str()));
+  st.cap_tiles = (h.vectorCount + kTileRows - 1) / kTileRows;
+  pt.cap_tiles = (px.pilotRows + kTileRows - 1) / kTileRows;
   set_storage_view(ix.get(), st, h.vectorCount, h.rowBase);
   if (ix->has_pilot) set_storage_view(ix.get(), pt, px.pilotRows, 0);
   if (centroid_out) memcpy(centroid_out, cen.data(), cen.size() * 4);

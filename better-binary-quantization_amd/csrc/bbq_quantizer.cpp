@@ -201,32 +201,25 @@ double bbq_centroid_dp(const float *c, int32_t dim) {  // src/vectorOperations.t
   return s;
 }
 
-int bbq_quantize_vectors(const float *vectors, int64_t n, int32_t dim, int32_t sim, int32_t index_bits, double lambda,
-                         int32_t iters, int32_t n_threads, uint8_t *codes, double *corr, float *centroid, int64_t *bad_row,
-                         int32_t *bad_col) {
-  bbq::clear_error();
-  if (n == 0) return bbq::fail(BBQ_ERR_EMPTY, "向量集合不能为空");  // src/binaryQuantizationFormat.ts:169-171
-  if (n < 0) return bbq::fail(BBQ_ERR_INVALID_ARG, "n < 0");
-  int rc = check_common(vectors, codes, dim, sim, index_bits, lambda, iters);
-  if (rc != BBQ_OK) return rc;
-  if (!corr || !centroid) return bbq::fail(BBQ_ERR_INVALID_ARG, "null output");
-
-  // :174-176 normalise (COSINE) into a working copy; :196-211 NaN / Infinity validation on the processed vectors,
-  // first offender in row-major order
-  std::vector<float> norm;
-  const float *proc = vectors;
+// quantizeVectors' steps that do not depend on the other rows (src/binaryQuantizationFormat.ts:174-176, :196-211): normalizeVector
+// (COSINE) into `norm`, then the NaN / Infinity validation on the processed vectors, first offender in row-major order.
+// *proc: the rows the quantizer reads (vectors, or norm's)
+static int prepare_rows(const float *vectors, int64_t n, int32_t dim, int32_t sim, int32_t n_threads, std::vector<float> &norm, const float **proc,
+                        int64_t *bad_row, int32_t *bad_col) {
+  *proc = vectors;
   if (sim == BBQ_COSINE) {
     norm.resize((size_t)n * (size_t)dim);
     parallel_rows(n, n_threads, [&](int64_t lo, int64_t hi, int) {
       for (int64_t i = lo; i < hi; ++i) normalize(vectors + i * dim, dim, norm.data() + i * dim);
     });
-    proc = norm.data();
+    *proc = norm.data();
   }
+  const float *p = *proc;
   std::atomic<int64_t> first_bad(INT64_MAX);
   parallel_rows(n, n_threads, [&](int64_t lo, int64_t hi, int) {
     for (int64_t i = lo; i < hi && i * dim < first_bad.load(std::memory_order_relaxed); ++i)
       for (int j = 0; j < dim; ++j) {
-        const float v = proc[i * dim + j];
+        const float v = p[i * dim + j];
         if (v != v || isinf(v)) {
           int64_t pos = i * dim + j, cur = first_bad.load();
           while (pos < cur && !first_bad.compare_exchange_weak(cur, pos)) {}
@@ -239,10 +232,42 @@ int bbq_quantize_vectors(const float *vectors, int64_t n, int32_t dim, int32_t s
     const int c = (int)(pos % dim);
     if (bad_row) *bad_row = r;
     if (bad_col) *bad_col = c;
-    const float v = proc[pos];
+    const float v = p[pos];
     if (v != v) return bbq::fail(BBQ_ERR_NAN_INPUT, "向量 %lld 位置 %d 包含NaN值", (long long)r, c);
     return bbq::fail(BBQ_ERR_INF_INPUT, "向量 %lld 位置 %d 包含Infinity值", (long long)r, c);
   }
+  return BBQ_OK;
+}
+
+// :221-249 scalarQuantize row by row against the centroid, packAsBinary for 1-bit rows
+static void quantize_prepared_rows(const float *proc, int64_t n, int32_t dim, const float *centroid, int32_t sim, int32_t index_bits, double lambda,
+                                   int32_t iters, int32_t n_threads, uint8_t *codes, double *corr) {
+  const int pb = (dim + 7) / 8;
+  parallel_rows(n, n_threads, [&](int64_t lo, int64_t hi, int) {
+    Quantizer qz{sim, lambda, iters, {}};
+    std::vector<uint8_t> tmp((size_t)dim);
+    for (int64_t i = lo; i < hi; ++i) {
+      qz.quantize(proc + i * dim, dim, index_bits, centroid, tmp.data(), corr + 4 * i);
+      if (index_bits == 1) pack_binary(tmp.data(), dim, codes + i * pb);  // :235-240
+      else memcpy(codes + i * (int64_t)dim, tmp.data(), (size_t)dim);    // :241-245
+    }
+  });
+}
+
+int bbq_quantize_vectors(const float *vectors, int64_t n, int32_t dim, int32_t sim, int32_t index_bits, double lambda,
+                         int32_t iters, int32_t n_threads, uint8_t *codes, double *corr, float *centroid, int64_t *bad_row,
+                         int32_t *bad_col) {
+  bbq::clear_error();
+  if (n == 0) return bbq::fail(BBQ_ERR_EMPTY, "向量集合不能为空");  // src/binaryQuantizationFormat.ts:169-171
+  if (n < 0) return bbq::fail(BBQ_ERR_INVALID_ARG, "n < 0");
+  int rc = check_common(vectors, codes, dim, sim, index_bits, lambda, iters);
+  if (rc != BBQ_OK) return rc;
+  if (!corr || !centroid) return bbq::fail(BBQ_ERR_INVALID_ARG, "null output");
+
+  std::vector<float> norm;
+  const float *proc = vectors;
+  rc = prepare_rows(vectors, n, dim, sim, n_threads, norm, &proc, bad_row, bad_col);
+  if (rc != BBQ_OK) return rc;
 
   // :214 computeCentroid (src/vectorOperations.ts:126-163): Float32Array accumulator, rounded after every += and
   // after the final /=.  Sequential over rows per dimension, so dimensions can be split across threads.
@@ -254,16 +279,23 @@ int bbq_quantize_vectors(const float *vectors, int64_t n, int32_t dim, int32_t s
     }
   });
 
-  const int pb = (dim + 7) / 8;
-  parallel_rows(n, n_threads, [&](int64_t lo, int64_t hi, int) {
-    Quantizer qz{sim, lambda, iters, {}};
-    std::vector<uint8_t> tmp((size_t)dim);
-    for (int64_t i = lo; i < hi; ++i) {
-      qz.quantize(proc + i * dim, dim, index_bits, centroid, tmp.data(), corr + 4 * i);
-      if (index_bits == 1) pack_binary(tmp.data(), dim, codes + i * pb);  // :235-240
-      else memcpy(codes + i * (int64_t)dim, tmp.data(), (size_t)dim);    // :241-245
-    }
-  });
+  quantize_prepared_rows(proc, n, dim, centroid, sim, index_bits, lambda, iters, n_threads, codes, corr);
+  return BBQ_OK;
+}
+
+int bbq_quantize_rows(const float *vectors, int64_t n, int32_t dim, const float *centroid, int32_t sim, int32_t index_bits, double lambda,
+                      int32_t iters, int32_t n_threads, uint8_t *codes, double *corr, int64_t *bad_row, int32_t *bad_col) {
+  bbq::clear_error();
+  if (n < 0) return bbq::fail(BBQ_ERR_INVALID_ARG, "n < 0");
+  if (n == 0) return BBQ_OK;
+  int rc = check_common(vectors, codes, dim, sim, index_bits, lambda, iters);
+  if (rc != BBQ_OK) return rc;
+  if (!corr || !centroid) return bbq::fail(BBQ_ERR_INVALID_ARG, "null output");
+  std::vector<float> norm;
+  const float *proc = vectors;
+  rc = prepare_rows(vectors, n, dim, sim, n_threads, norm, &proc, bad_row, bad_col);
+  if (rc != BBQ_OK) return rc;
+  quantize_prepared_rows(proc, n, dim, centroid, sim, index_bits, lambda, iters, n_threads, codes, corr);
   return BBQ_OK;
 }
 

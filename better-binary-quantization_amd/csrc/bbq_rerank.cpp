@@ -13,7 +13,7 @@ using namespace bbq;
 struct bbq_vectors {
   int device = 0;
   DeviceCtx *ctx = nullptr;
-  DevBuf<float> d;
+  DevBuf<float> d;      // [cap][dim], the first n rows in use (bbq_vectors_append grows it like the index grows)
   int64_t n = 0;
   int32_t dim = 0;
   // grow-only staging for bbq_rerank_scores
@@ -87,6 +87,37 @@ void bbq_vectors_destroy(bbq_vectors *v) {
   std::lock_guard<std::mutex> lk(v->ctx->mu);
   (void)hipSetDevice(v->device);
   delete v;
+}
+
+int bbq_vectors_append(bbq_vectors *v, const float *vectors, int64_t n) {
+  clear_error();
+  if (!v) return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_append: vectors handle is null");
+  if (n < 0) return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_append: n < 0");
+  if (n == 0) return BBQ_OK;
+  if (!vectors) return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_append: vectors is null");
+  if (v->n + n > 0x7fffffffLL) return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_append: more than 2^31-1 rows");
+  std::lock_guard<std::mutex> lk(v->ctx->mu);
+  HIPCHK(hipSetDevice(v->device));
+  HIPCHK(hipStreamSynchronize(v->ctx->aux_stream));  // bbq_rerank_scores reads the rows on it
+  const int64_t dim = v->dim, total = v->n + n;
+  DevBuf<float> grown;
+  float *dst = v->d;
+  if ((int64_t)v->d.size() < total * dim) {  // half as much again, at least what is needed; the old rows move device to device
+    const int64_t cap = std::max<int64_t>(total, (int64_t)(v->d.size() / (size_t)dim) * 3 / 2);
+    const hipError_t e = grown.alloc((size_t)(cap * dim));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "bbq_vectors_append: %lld x %d fp32: %s", (long long)cap, v->dim, hipGetErrorString(e)); }
+    if (v->n > 0) HIPCHK(hipMemcpy(grown, v->d, (size_t)(v->n * dim) * sizeof(float), hipMemcpyDeviceToDevice));
+    dst = grown;
+  }
+  const int64_t count = n * dim, piece = 64LL << 20;
+  for (int64_t o = 0; o < count; o += piece) {
+    const hipError_t e = hipMemcpy(dst + v->n * dim + o, vectors + o, (size_t)std::min(piece, count - o) * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(BBQ_ERR_HIP, "bbq_vectors_append: copy: %s", hipGetErrorString(e));
+  }
+  HIPCHK(hipDeviceSynchronize());
+  if (grown) v->d = std::move(grown);  // the old rows are released here, behind the copy
+  v->n = total;
+  return BBQ_OK;
 }
 
 int64_t bbq_vectors_size(const bbq_vectors *v) { return v ? v->n : 0; }

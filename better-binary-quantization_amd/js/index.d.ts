@@ -16,6 +16,8 @@ export interface BinarizedByteVectorValues {
   dispose(): void;
   /** libbbq tuning knob on the device index, e.g. ('sweep_share', 32), ('resident_mb', 0) (extension; include/bbq.h lists them) */
   setDeviceOption(name: string, value: number): void;
+  /** extension: room for `rows` rows in total on the device (appendVectors up to there moves nothing); returns the capacity in rows */
+  reserve(rows: number): number;
   /** libbbq counters of the last call on the device index (extension; bbq_stats in include/bbq.h) */
   deviceStats(): { lastScanMs: number; lastScanBytes: number; candidates: number; denseFallbacks: number; hostReplays: number;
                    residentBytes: number; shards: number; bytesPerRow: number };
@@ -50,6 +52,10 @@ export declare class BinaryQuantizedScorer {
 export declare class BinaryQuantizationFormat {
   constructor(config: BinaryQuantizationConfig);
   quantizeVectors(vectors: Float32Array[]): { quantizedVectors: BinarizedByteVectorValues; queryQuantizer: OptimizedScalarQuantizer };
+  /** extension: `vectors`, quantized against targetVectors' centroid like quantizeVectors quantizes its rows, become its next ords; the
+   *  device index grows in place.  Not supported on a multi-device index (BBQ_DEVICES).  A RowFilter made before the call no longer
+   *  fits the index.  Returns targetVectors. */
+  appendVectors(targetVectors: BinarizedByteVectorValues, vectors: Float32Array[]): BinarizedByteVectorValues;
   quantizeQueryVector(queryVector: Float32Array, centroid: Float32Array): { quantizedQuery: Uint8Array; queryCorrections: QuantizationResult };
   searchNearestNeighbors(queryVector: Float32Array, targetVectors: BinarizedByteVectorValues, k: number): Array<{ index: number; score: number }>;
   /** extension: many independent queries per call, pipelined on the device */
@@ -96,6 +102,8 @@ export declare class DeviceVectors {
   readonly dim: number;
   /** computeSimilarity(query, vectors[rows[j]]) (f64, bit-identical to src/vectorSimilarity.ts); default COSINE */
   trueScores(query: Float32Array, rows: ArrayLike<number>, similarityFunction?: VectorSimilarityFunction): Float64Array;
+  /** extension: the fp32 rows of a block BinaryQuantizationFormat.appendVectors has added to the index get the next ords */
+  append(vectors: Float32Array[]): DeviceVectors;
   dispose(): void;
 }
 export declare function createDeviceVectors(vectors: Float32Array[], device?: number): DeviceVectors;

@@ -110,6 +110,20 @@ class BinarizedByteVectorValuesImpl {
     return this._device;
   }
   dispose() { if (this._device) { this._host(); native.indexDestroy(this._device); this._device = null; } }
+  /** extension: room for `rows` rows in total on the device, so that appendVectors up to there moves nothing (libbbq bbq_index_reserve);
+   *  returns the capacity in rows */
+  reserve(rows) { return native.indexReserve(this._deviceIndex(), rows); }
+  /** the rows appendVectors has quantized join the host copies - or leave them to be fetched again: never a stale copy */
+  _appended(codes, corr, n) {
+    if (this._codes) {
+      const c = new Uint8Array(this._codes.length + codes.length), r = new Float64Array(this._corr.length + corr.length);
+      c.set(this._codes); c.set(codes, this._codes.length);
+      r.set(this._corr); r.set(corr, this._corr.length);
+      this._codes = c; this._corr = r;
+    }
+    if (!this._rowBytes && n > 0) this._rowBytes = codes.length / n;
+    this._size += n;
+  }
   /** tuning knobs of the device index (libbbq bbq_set_option), e.g. ('sweep_share', 32) for searchNearestNeighborsBatch */
   setDeviceOption(name, value) { native.setOption(this._deviceIndex(), name, value); }
   deviceStats() { return native.stats(this._deviceIndex()); }
@@ -422,6 +436,35 @@ class BinaryQuantizationFormat {
     return { quantizedVectors: values, queryQuantizer: this.quantizer };
   }
 
+  /**
+   * extension (not in the reference, whose index is immutable): `vectors` quantized against targetVectors' centroid - quantizeVectors'
+   * per-row part: normalizeVector for COSINE, validation, scalarQuantize, packAsBinary (:174-249 without :214) - become its next ords;
+   * size(), vectorValue, getCorrectiveTerms and every search cover them.  The device index grows in place (libbbq bbq_index_append);
+   * without a device the rows are quantized on the host.  A multi-device index (BBQ_DEVICES) throws the library's unsupported
+   * message.  A RowFilter made before the call no longer fits: make a new one.  On an error nothing has changed.  Returns targetVectors.
+   */
+  appendVectors(targetVectors, vectors) {
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (vectors.length === 0) return targetVectors;
+    const dim = targetVectors.dimension(), q = this.quantizer, ib = targetVectors._indexBits;
+    for (let i = 0; i < vectors.length; i++) {
+      const v = vectors[i];
+      if (!v) throw new Error('向量 ' + i + ' 不能为空');
+      if (v.length !== dim) throw new Error('向量 ' + i + ' 维度 ' + v.length + ' 与第一个向量维度 ' + dim + ' 不匹配');
+    }
+    if (ib !== this.config.indexBits) throw new Error('indexBits ' + this.config.indexBits + ' 与目标向量集合的 ' + ib + ' 不匹配');
+    const flat = flatten(vectors, dim), sim = simOrdinal(q.similarityFunction);
+    let r;
+    if (process.env.BBQ_HOST_QUANTIZER !== '1' && native.deviceCount() > 0) {
+      r = native.indexAppend(targetVectors._deviceIndex(), flat, vectors.length, dim, targetVectors.getCentroid(), sim, q.lambda, q.iters);
+    } else {
+      r = native.quantizeRows(flat, vectors.length, dim, targetVectors.getCentroid(), sim, ib, q.lambda, q.iters, Number(process.env.BBQ_THREADS || 0));
+      if (targetVectors._device) native.indexAppendRows(targetVectors._device, r.codes, r.corr, vectors.length);  // a device copy that exists follows
+    }
+    targetVectors._appended(r.codes, r.corr, vectors.length);
+    return targetVectors;
+  }
+
   /** quantizeQueryVector(queryVector, centroid) -> {quantizedQuery, queryCorrections}  (:271-299) */
   quantizeQueryVector(queryVector, centroid) {
     const q = this.quantizer;
@@ -587,8 +630,10 @@ class BinaryQuantizationFormat {
       native.indexDestroy(r.handle);
       throw new Error('不支持的相似性函数: file was written for ordinal ' + r.sim);
     }
-    const values = new BinarizedByteVectorValuesImpl(null, null, r.centroid, 1, r.n);
-    values._rowBytes = Math.ceil(r.dim / 8);
+    // the rows come back in the shape of the index's own indexBits (packed bits, or one byte per dimension): appendVectors and the
+    // row accessors of a loaded multi-bit index depend on it
+    const values = new BinarizedByteVectorValuesImpl(null, null, r.centroid, r.indexBits, r.n);
+    values._rowBytes = r.indexBits === 1 ? Math.ceil(r.dim / 8) : r.dim;
     values._device = r.handle;
     return values;
   }
@@ -747,6 +792,14 @@ class DeviceVectors {
     if (query.length !== this.dim) throw new Error('向量维度不匹配');
     const sim = similarityFunction === undefined ? 1 : simOrdinal(similarityFunction);
     return native.rerankScores(this._handle(), 1, Float32Array.from(query), Float64Array.of(0, rows.length), Int32Array.from(rows), sim);
+  }
+  /** extension: the fp32 rows of a block appendVectors has added to the index get the next ords (libbbq bbq_vectors_append) */
+  append(vectors) {
+    if (!vectors || vectors.length === 0) return this;
+    for (let i = 0; i < vectors.length; i++) if (!vectors[i] || vectors[i].length !== this.dim) throw new Error('向量维度不匹配');
+    native.vectorsAppend(this._handle(), flatten(vectors, this.dim), vectors.length, this.dim);
+    this.length += vectors.length;
+    return this;
   }
   _handle() { if (!this._h) throw new Error('向量不能为空'); return this._h; }
   dispose() { if (this._h) { native.vectorsDestroy(this._h); this._h = null; } }

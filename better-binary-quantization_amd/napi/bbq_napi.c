@@ -227,6 +227,91 @@ static napi_value IndexBuild(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* quantizeRows(flat Float32Array, n, dim, centroid Float32Array, sim, indexBits, lambda, iters, threads) -> {codes, corr}
+ * quantizeVectors' per-row part against a given centroid, on the host (bbq_quantize_rows) */
+static napi_value QuantizeRows(napi_env env, napi_callback_info info) {
+  napi_value a[9];
+  if (!get_args(env, info, 9, a)) return NULL;
+  void *vec, *cen; size_t vlen, clen;
+  int64_t n, dim, sim, ib, iters, threads; double lambda;
+  if (!get_typed(env, a[0], napi_float32_array, &vec, &vlen) || !get_i64(env, a[1], &n) || !get_i64(env, a[2], &dim) ||
+      !get_typed(env, a[3], napi_float32_array, &cen, &clen) || !get_i64(env, a[4], &sim) || !get_i64(env, a[5], &ib) ||
+      !get_f64(env, a[6], &lambda) || !get_i64(env, a[7], &iters) || !get_i64(env, a[8], &threads)) return NULL;
+  if (n < 0 || dim <= 0 || (size_t)(n * dim) != vlen || clen != (size_t)dim) { napi_throw_range_error(env, NULL, "bbq_napi: n*dim does not match the arrays"); return NULL; }
+  void *codes, *corr;
+  napi_value tcodes = new_typed(env, napi_uint8_array, (size_t)n * (size_t)(ib == 1 ? (dim + 7) / 8 : dim), 1, &codes);
+  napi_value tcorr = new_typed(env, napi_float64_array, (size_t)n * 4, 8, &corr);
+  if (!tcodes || !tcorr) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_quantize_rows((const float *)vec, n, (int32_t)dim, (const float *)cen, (int32_t)sim, (int32_t)ib, lambda, (int32_t)iters,
+                             (int32_t)threads, (uint8_t *)codes, (double *)corr, NULL, NULL);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "codes", tcodes); set_prop(env, o, "corr", tcorr);
+  return o;
+}
+
+/* indexAppend(handle, flat Float32Array, n, dim, centroid Float32Array, sim, lambda, iters) -> {codes, corr}
+ * raw rows quantized on the device against the index's centroid become its next ords (bbq_index_append) */
+static napi_value IndexAppend(napi_env env, napi_callback_info info) {
+  napi_value a[8];
+  if (!get_args(env, info, 8, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *vec, *cen; size_t vlen, clen;
+  int64_t n, dim, sim, iters; double lambda;
+  if (!get_typed(env, a[1], napi_float32_array, &vec, &vlen) || !get_i64(env, a[2], &n) || !get_i64(env, a[3], &dim) ||
+      !get_typed(env, a[4], napi_float32_array, &cen, &clen) || !get_i64(env, a[5], &sim) || !get_f64(env, a[6], &lambda) ||
+      !get_i64(env, a[7], &iters)) return NULL;
+  if (n < 0 || dim != bbq_index_dimension(ix) || (size_t)(n * dim) != vlen || clen != (size_t)dim) {
+    napi_throw_range_error(env, NULL, "bbq_napi: n*dim does not match the arrays or the index"); return NULL;
+  }
+  const int64_t ib = bbq_index_bits(ix);
+  void *codes, *corr;
+  napi_value tcodes = new_typed(env, napi_uint8_array, (size_t)n * (size_t)(ib == 1 ? (dim + 7) / 8 : dim), 1, &codes);
+  napi_value tcorr = new_typed(env, napi_float64_array, (size_t)n * 4, 8, &corr);
+  if (!tcodes || !tcorr) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_index_append(ix, (const float *)vec, n, (const float *)cen, (int32_t)sim, lambda, (int32_t)iters, (uint8_t *)codes, (double *)corr, NULL, NULL);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "codes", tcodes); set_prop(env, o, "corr", tcorr);
+  return o;
+}
+
+/* indexAppendRows(handle, codes Uint8Array, corr Float64Array, n): rows already quantized (bbq_index_append_rows) */
+static napi_value IndexAppendRows(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *codes, *corr; size_t cl, rl;
+  int64_t n;
+  if (!get_typed(env, a[1], napi_uint8_array, &codes, &cl) || !get_typed(env, a[2], napi_float64_array, &corr, &rl) || !get_i64(env, a[3], &n)) return NULL;
+  const int64_t dim = bbq_index_dimension(ix);
+  if (n < 0 || rl != (size_t)n * 4 || cl != (size_t)n * (size_t)(bbq_index_bits(ix) == 1 ? (dim + 7) / 8 : dim)) {
+    napi_throw_range_error(env, NULL, "bbq_napi: array sizes do not match n/dim"); return NULL;
+  }
+  int rc = bbq_index_append_rows(ix, (const uint8_t *)codes, (const double *)corr, n);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
+/* indexReserve(handle, rows) -> capacity in rows (bbq_index_reserve, bbq_index_capacity) */
+static napi_value IndexReserve(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  int64_t rows;
+  if (!get_i64(env, a[1], &rows)) return NULL;
+  int rc = bbq_index_reserve(ix, rows);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value r;
+  NAPI_CALL(env, napi_create_double(env, (double)bbq_index_capacity(ix), &r));
+  return r;
+}
+
 /* indexDestroy(handle) */
 static napi_value IndexDestroy(napi_env env, napi_callback_info info) {
   napi_value a[1];
@@ -529,6 +614,21 @@ static napi_value VectorsCreate(napi_env env, napi_callback_info info) {
   return ext;
 }
 
+/* vectorsAppend(handle, flat Float32Array, n, dim): the fp32 rows of an appended block (bbq_vectors_append) */
+static napi_value VectorsAppend(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return NULL;
+  bbq_vectors *v = unbox_vectors(env, a[0]);
+  if (!v) return NULL;
+  void *vec; size_t vlen;
+  int64_t n, dim;
+  if (!get_typed(env, a[1], napi_float32_array, &vec, &vlen) || !get_i64(env, a[2], &n) || !get_i64(env, a[3], &dim)) return NULL;
+  if (n < 0 || dim != bbq_vectors_dimension(v) || (size_t)(n * dim) != vlen) { napi_throw_range_error(env, NULL, "bbq_napi: n*dim does not match the array or the vectors"); return NULL; }
+  int rc = bbq_vectors_append(v, (const float *)vec, n);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
 /* vectorsDestroy(handle) */
 static napi_value VectorsDestroy(napi_env env, napi_callback_info info) {
   napi_value a[1];
@@ -627,7 +727,7 @@ static napi_value IndexSave(napi_env env, napi_callback_info info) {
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
-/* indexLoad(prefix, device[, devices Int32Array]) -> {handle, centroid Float32Array, n, dim, sim, centroidDP, rowBase, shards}
+/* indexLoad(prefix, device[, devices Int32Array]) -> {handle, centroid Float32Array, n, dim, sim, centroidDP, rowBase, shards, indexBits}
  * devices given and the files hold a multi-device index (a manifest): its shards go over those devices (bbq_index_load_multi) */
 static napi_value IndexLoad(napi_env env, napi_callback_info info) {
   napi_value a[3];
@@ -661,6 +761,7 @@ static napi_value IndexLoad(napi_env env, napi_callback_info info) {
   napi_create_double(env, cdp, &v); set_prop(env, o, "centroidDP", v);
   napi_create_double(env, (double)rb, &v); set_prop(env, o, "rowBase", v);
   napi_create_double(env, (double)file_shards, &v); set_prop(env, o, "shards", v);
+  napi_create_double(env, (double)bbq_index_bits(*box), &v); set_prop(env, o, "indexBits", v);
   return o;
 }
 
@@ -719,6 +820,11 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"indexCreateMulti", NULL, IndexCreateMulti, NULL, NULL, NULL, napi_default, NULL},
       {"indexBuild", NULL, IndexBuild, NULL, NULL, NULL, napi_default, NULL},
       {"indexDestroy", NULL, IndexDestroy, NULL, NULL, NULL, napi_default, NULL},
+      {"quantizeRows", NULL, QuantizeRows, NULL, NULL, NULL, napi_default, NULL},
+      {"indexAppend", NULL, IndexAppend, NULL, NULL, NULL, napi_default, NULL},
+      {"indexAppendRows", NULL, IndexAppendRows, NULL, NULL, NULL, napi_default, NULL},
+      {"indexReserve", NULL, IndexReserve, NULL, NULL, NULL, napi_default, NULL},
+      {"vectorsAppend", NULL, VectorsAppend, NULL, NULL, NULL, napi_default, NULL},
       {"searchBatch", NULL, SearchBatch, NULL, NULL, NULL, napi_default, NULL},
       {"filterCreate", NULL, FilterCreate, NULL, NULL, NULL, napi_default, NULL},
       {"filterDestroy", NULL, FilterDestroy, NULL, NULL, NULL, napi_default, NULL},

@@ -99,6 +99,34 @@ class BinaryQuantizationFormat:
             raise Exception(str(e))
         return {"quantizedVectors": values, "queryQuantizer": self}
 
+    def appendVectors(self, targetVectors, vectors):
+        """extension: `vectors` quantized against targetVectors' centroid - quantizeVectors' per-row part (normalizeVector for COSINE,
+        validation, scalarQuantize, packAsBinary) - become its next ords: size(), vectorValue, getCorrectiveTerms and every search
+        cover them.  On the device when there is one (the resident index grows in place), on the host otherwise.  Returns targetVectors."""
+        if targetVectors is None:
+            raise Exception("目标向量集合不能为空")
+        if len(vectors) == 0:
+            return targetVectors
+        dim = targetVectors.dimension()
+        for i, v in enumerate(vectors):
+            if len(v) != dim:
+                raise Exception("向量 %d 维度 %d 与第一个向量维度 %d 不匹配" % (i, len(v), dim))
+        if targetVectors._index_bits != self._config["indexBits"]:
+            raise Exception("indexBits %d 与目标向量集合的 %d 不匹配" % (self._config["indexBits"], targetVectors._index_bits))
+        v = np.asarray(vectors, np.float32)
+        sim = capi.SIMS[self._sim]
+        try:
+            if capi.device_count() > 0:
+                codes, corr = targetVectors._device().append(v, targetVectors.getCentroid(), sim, self._lambda, self._iters)
+            else:
+                codes, corr = capi.quantize_rows(v, targetVectors.getCentroid(), sim, targetVectors._index_bits, self._lambda, self._iters)
+        except capi.BBQError as e:
+            raise Exception(str(e))
+        # the host copies behind size() / vectorValue / getCorrectiveTerms follow (new arrays: rows handed out earlier stay valid)
+        targetVectors._codes = np.concatenate([targetVectors._codes, codes])
+        targetVectors._corr = np.concatenate([targetVectors._corr, corr])
+        return targetVectors
+
     def quantizeQueryVector(self, queryVector, centroid):
         qq, qc = capi.quantize_query(queryVector, centroid, capi.SIMS[self._sim], self._config["queryBits"], self._lambda,
                                      self._iters, search_path=False)

@@ -27,6 +27,7 @@ SYMBOLS = [
     "bbq_shard_scan_begin", "bbq_shard_scan_wait", "bbq_merge_answers", "bbq_key_of_score", "bbq_index_load_multi", "bbq_index_file_shards",
     "bbq_search_raw_batch",
     "bbq_filter_create", "bbq_filter_create_rows", "bbq_filter_destroy", "bbq_filter_count", "bbq_search_filtered_batch", "bbq_filter_plan",
+    "bbq_index_append_rows", "bbq_index_append", "bbq_index_reserve", "bbq_index_capacity", "bbq_vectors_append", "bbq_quantize_rows",
 ]
 
 
@@ -142,6 +143,13 @@ def lib():
     L.bbq_index_file_shards.argtypes = [C.c_char_p]
     L.bbq_index_file_shards.restype = i32
     L.bbq_index_export.argtypes = [vp, vp, vp]
+    L.bbq_index_append_rows.argtypes = [vp, vp, vp, i64]
+    L.bbq_index_append.argtypes = [vp, vp, i64, vp, i32, dbl, i32, vp, vp, C.POINTER(i64), C.POINTER(i32)]
+    L.bbq_index_reserve.argtypes = [vp, i64]
+    L.bbq_index_capacity.argtypes = [vp]
+    L.bbq_index_capacity.restype = i64
+    L.bbq_vectors_append.argtypes = [vp, vp, i64]
+    L.bbq_quantize_rows.argtypes = [vp, i64, i32, vp, i32, i32, dbl, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(i32)]
     _lib = L
     return L
 
@@ -149,6 +157,16 @@ def lib():
 def _chk(rc):
     if rc != OK:
         raise BBQError(rc, lib().bbq_last_error().decode("utf-8", "replace"))
+
+
+def _chk_pos(call):
+    """_chk for the entry points that report where a NaN / Infinity sits: the BBQError carries .bad_row / .bad_col"""
+    br, bc = C.c_int64(-1), C.c_int32(-1)
+    rc = call(C.byref(br), C.byref(bc))
+    if rc != OK:
+        e = BBQError(rc, lib().bbq_last_error().decode("utf-8", "replace"))
+        e.bad_row, e.bad_col = br.value, bc.value
+        raise e
 
 
 def _ptr(a):
@@ -175,6 +193,20 @@ def quantize_vectors(vectors, sim, index_bits=1, lam=0.1, iters=5, n_threads=0):
     _chk(lib().bbq_quantize_vectors(_ptr(v), n, dim, sim, index_bits, lam, iters, n_threads, _ptr(codes), _ptr(corr), _ptr(cen),
                                    None, None))
     return codes, corr, cen
+
+
+def quantize_rows(vectors, centroid, sim, index_bits=1, lam=0.1, iters=5, n_threads=0):
+    """quantizeVectors' per-row part against a GIVEN centroid (bbq_quantize_rows; host only): (codes, corr) - what Index.append
+    computes on the device.  A NaN / Infinity raises BBQError with .bad_row / .bad_col set."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    cen = np.ascontiguousarray(centroid, np.float32)
+    if v.ndim != 2 or cen.shape != (v.shape[1],):
+        raise BBQError(ERR_DIM_MISMATCH, "向量维度不匹配")
+    n, dim = v.shape
+    codes = np.zeros((n, (dim + 7) // 8 if index_bits == 1 else dim), np.uint8)
+    corr = np.zeros((n, 4), np.float64)
+    _chk_pos(lambda br, bc: lib().bbq_quantize_rows(_ptr(v), n, dim, _ptr(cen), sim, index_bits, lam, iters, n_threads, _ptr(codes), _ptr(corr), br, bc))
+    return codes, corr
 
 
 def quantize_query(query, centroid, sim, query_bits=4, lam=0.1, iters=5, search_path=True):
@@ -303,6 +335,40 @@ class Index:
         corr = np.zeros((self.n, 4), np.float64)
         _chk(lib().bbq_index_export(self._h, _ptr(codes), _ptr(corr)))
         return codes, corr
+
+    def append_rows(self, codes, corr):
+        """bbq_index_append_rows: rows already quantized, in the shape the constructor takes them, get the next ords"""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        corr = np.ascontiguousarray(corr, np.float64)
+        width = (self.dim + 7) // 8 if self.index_bits == 1 else self.dim
+        if codes.ndim != 2 or codes.shape[1] != width or corr.shape != (codes.shape[0], 4):
+            raise BBQError(ERR_DIM_MISMATCH, "codes must be [n, %d] and corr [n, 4]" % width)
+        _chk(lib().bbq_index_append_rows(self._h, _ptr(codes), _ptr(corr), codes.shape[0]))
+        self.n = int(lib().bbq_index_size(self._h))
+
+    def append(self, vectors, centroid, sim, lam=0.1, iters=5, want_host_copy=True):
+        """bbq_index_append: raw fp32 rows quantized on the device against `centroid` (the one the index was built with).
+        Returns (codes, corr) of the new rows, or (None, None) unless want_host_copy.  A NaN / Infinity raises BBQError with
+        .bad_row / .bad_col (position inside `vectors`) and leaves the index as it was."""
+        v = np.ascontiguousarray(vectors, np.float32)
+        cen = np.ascontiguousarray(centroid, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.dim or cen.shape != (self.dim,):
+            raise BBQError(ERR_DIM_MISMATCH, "向量维度不匹配")
+        n = v.shape[0]
+        codes = np.zeros((n, (self.dim + 7) // 8 if self.index_bits == 1 else self.dim), np.uint8) if want_host_copy else None
+        corr = np.zeros((n, 4), np.float64) if want_host_copy else None
+        _chk_pos(lambda br, bc: lib().bbq_index_append(self._h, _ptr(v), n, _ptr(cen), int(sim), lam, iters, _ptr(codes), _ptr(corr), br, bc))
+        self.n = int(lib().bbq_index_size(self._h))
+        return codes, corr
+
+    def reserve(self, rows):
+        """room for `rows` rows in total without another reallocation (bbq_index_reserve)"""
+        _chk(lib().bbq_index_reserve(self._h, int(rows)))
+
+    @property
+    def capacity(self):
+        """rows the current allocations hold (>= n)"""
+        return int(lib().bbq_index_capacity(self._h))
 
     def close(self):
         if self._h:
@@ -538,6 +604,14 @@ class Vectors:
             self.close()
         except Exception:
             pass
+
+    def append(self, vectors):
+        """bbq_vectors_append: the fp32 rows of an appended block get the next ords"""
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.dim:
+            raise BBQError(ERR_DIM_MISMATCH, "向量维度不匹配")
+        _chk(lib().bbq_vectors_append(self._h, _ptr(v), v.shape[0]))
+        self.n = int(lib().bbq_vectors_size(self._h))
 
     def rerank_scores(self, queries, rows_per_query, true_sim=1):
         """computeSimilarity(queries[q], vectors[r]) for r in rows_per_query[q]; returns a list of f64 arrays"""

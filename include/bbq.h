@@ -158,6 +158,40 @@ int bbq_index_create_multi(const uint8_t *codes, const double *corr, int64_t n_r
 int bbq_index_create_multi_opts(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t index_bits,
                                 double centroid_dp, int32_t n_shards, const int32_t *devices, int64_t pilot_rows,
                                 const bbq_index_options *opts, bbq_index **out);
+/* ------------------------------------------------------------------------------------------
+ * Appending rows (new; the reference's index is immutable): the index grows in place.  Rows are independent once the centroid is
+ * fixed - quantizeVectors computes the centroid and then calls scalarQuantize row by row (src/binaryQuantizationFormat.ts:214-249) -
+ * so "the new rows quantized against the centroid the index was built with" is fully defined by the reference.  After an append the
+ * index is indistinguishable from one created whole over the old rows followed by the new ones (same centroid_dp, index_bits,
+ * options): size, every search entry point (indices, f32 score bits, order, ties), bbq_index_export and the bytes bbq_index_save
+ * writes.  New rows get the next ords, bbq_index_size() ..., in the order given.
+ * Strong guarantee: an append that fails - bad argument, NaN / Infinity, a row the layout cannot hold, out of memory - leaves the
+ * index exactly as it was.  n == 0: BBQ_OK, nothing changes.  More than 2^32 rows in total: BBQ_ERR_UNSUPPORTED.
+ * Out of scope (BBQ_ERR_UNSUPPORTED), as for filters: a multi-device handle, a non-root shard, an index with a pilot replica.
+ * The call takes the device context's lock like every entry point and first retires what the index has in flight: a search on
+ * another thread sees the index before or after the append, never in between; a bbq_shard_scan_begin batch of this index that has
+ * not been waited for: BBQ_ERR_INVALID_ARG.
+ * A bbq_filter made BEFORE an append no longer fits the index's size: bbq_search_filtered_batch refuses it (BBQ_ERR_INVALID_ARG);
+ * make a new filter over the grown index.
+ * Capacity: the allocations hold bbq_index_capacity() rows (whole 64-row tiles).  An append that fits writes in place; one that
+ * does not moves the index into allocations of max(tiles needed, 1.5 x tiles held) tiles - a device-to-device copy, the old
+ * buffers released after it - so a run of appends costs amortised O(rows appended).  bbq_index_reserve makes room for exactly
+ * `rows` rows in total (never shrinks). */
+/* rows already quantized, in the shape bbq_index_create takes them (codes [n*ceil(dim/8)] or [n*dim], corr [n*4]).  An index without
+ * explicit component sums (compact corrections, or inline with the implicit sum) refuses a row whose quantizedComponentSum is not its
+ * popcount / code sum with BBQ_ERR_UNSUPPORTED - holding it would mean re-tiling the whole index; an index that carries explicit sums
+ * takes any row.  A multi-bit code >= 2^indexBits: BBQ_ERR_INVALID_ARG, as at creation. */
+int bbq_index_append_rows(bbq_index *idx, const uint8_t *codes, const double *corr, int64_t n);
+/* raw fp32 rows [n*dim], quantized ON THE DEVICE against `centroid` [dim] (the one the index was built with; the library does not
+ * keep it): normalizeVector for COSINE, NaN / Infinity validation, scalarQuantize(indexBits of the index), packAsBinary - what
+ * bbq_index_build does after its centroid step; 1-bit rows are quantized straight into their lanes of the tile records.
+ * codes_out / corr_out (host, may be NULL): the new rows in the reference's shape.  *bad_row / *bad_col: position inside THIS call's
+ * block; messages and codes as bbq_index_build. */
+int bbq_index_append(bbq_index *idx, const float *vectors, int64_t n, const float *centroid, int32_t sim, double lambda, int32_t iters,
+                     uint8_t *codes_out, double *corr_out, int64_t *bad_row, int32_t *bad_col);
+int bbq_index_reserve(bbq_index *idx, int64_t rows);      /* room for `rows` rows in total without another reallocation */
+int64_t bbq_index_capacity(const bbq_index *idx);         /* rows the current allocations hold (>= size) */
+
 int32_t bbq_index_shards(const bbq_index *idx);    /* 1 for a single-device index */
 void bbq_index_destroy(bbq_index *idx);
 int64_t bbq_index_size(const bbq_index *idx);      /* BinarizedByteVectorValues.size()      src/types.ts:46 */
@@ -352,6 +386,9 @@ int bbq_index_export(bbq_index *idx, uint8_t *codes, double *corr);
 typedef struct bbq_vectors bbq_vectors;
 /* vectors [n*dim] row-major (the Float32Array[] the reference's selectors take as `vectors`), copied to the device */
 int bbq_vectors_create(const float *vectors, int64_t n, int32_t dim, int32_t device, bbq_vectors **out);
+/* the fp32 side of the rerank recipe grows with the index (bbq_index_append*): the rows get the next ords; storage grows by half as
+ * much again when it runs out.  On failure nothing has changed. */
+int bbq_vectors_append(bbq_vectors *v, const float *vectors, int64_t n);
 void bbq_vectors_destroy(bbq_vectors *v);
 int64_t bbq_vectors_size(const bbq_vectors *v);
 int32_t bbq_vectors_dimension(const bbq_vectors *v);
@@ -386,6 +423,12 @@ int bbq_search_rerank_batch(bbq_index *idx, bbq_vectors *v, int32_t n_queries, c
 int bbq_quantize_vectors(const float *vectors, int64_t n, int32_t dim, int32_t sim, int32_t index_bits,
                          double lambda, int32_t iters, int32_t n_threads, uint8_t *codes, double *corr,
                          float *centroid, int64_t *bad_row, int32_t *bad_col);
+/* Host only, no device: quantizeVectors' per-row part with a GIVEN centroid - normalizeVector (COSINE), NaN / Infinity validation,
+ * scalarQuantize(index_bits, centroid), packAsBinary - which is what bbq_index_append computes on the device.  With the centroid
+ * bbq_quantize_vectors returned it reproduces that call's rows bit for bit.  Shapes, threads and errors as bbq_quantize_vectors;
+ * n == 0: BBQ_OK. */
+int bbq_quantize_rows(const float *vectors, int64_t n, int32_t dim, const float *centroid, int32_t sim, int32_t index_bits,
+                      double lambda, int32_t iters, int32_t n_threads, uint8_t *codes, double *corr, int64_t *bad_row, int32_t *bad_col);
 /* searchNearestNeighbors' query preparation, src/binaryQuantizationFormat.ts:337-347 + :271-299
  * (COSINE: the query is normalised twice) */
 int bbq_quantize_query(const float *query, int32_t dim, const float *centroid, int32_t sim, int32_t query_bits,
