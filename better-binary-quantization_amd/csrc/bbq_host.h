@@ -1,12 +1,13 @@
 // bbq_host.h - host-side internals of libbbq shared by its translation units: the device-resident index object, the
 // per-device context (streams, events, per-slot workspace) and the helpers every entry point needs.
-//   bbq_index.cpp    device context, index creation from rows, tile storage, cache budget of a launch, statistics, options
+//   bbq_index.cpp    device context, index creation from rows, cache budget of a launch, statistics, options
 //   bbq_core.cpp     segment plan, slot workspace, pipelined batch search: enqueue, collection in steps, host replay (shares bbq_search.h - the SearchCall - with the next four)
 //   bbq_query.cpp    query staging    bbq_latency.cpp  single-query chains    bbq_dense.cpp  dense path, bbq_score_rows
 //   bbq_shard.cpp    scan of one shard of a row-sharded index (bbq_shard_scan*)
 //   bbq_multi.cpp    one index over several devices of a process
+//   bbq_append.cpp   the one path that writes rows into an index - creation and build are appends to an empty one - and the entry
+//                    points that grow an index in place (bbq_index_append*, bbq_index_reserve)
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
-//   bbq_append.cpp   rows appended to an index in place, capacity (bbq_index_append*, bbq_index_reserve)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
 // bbq_entry.h is the codec of the 64-bit entries, keys and answer headers; bbq_workqueue.h the host threads' job queue.
@@ -256,10 +257,52 @@ inline void set_storage_view(const bbq_index *ix, Storage &st, int64_t n_rows, i
   st.view.exact = st.d_exact;
   st.view.add_range = add_range_of(st.d_exact, st.cap_tiles);
 }
-// rows already in device memory (codes in the caller's shape: packed bits, or one byte per dimension for a multi-bit index;
-// corrections [n][4]) -> tile records of `st`, deciding the index's layout on the way.  Context mutex held by the caller.
-int storage_from_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const double *d_corr, int64_t n_rows, int64_t row_id_base,
-                             bool check_x1);
+// bytes per row as the caller hands them over and gets them back: packed bits, or one byte per dimension for a multi-bit index
+inline int64_t caller_row_bytes(const bbq_index *ix) { return ix->store_bits > 1 ? ix->dim : ix->pb; }
+inline int64_t tiles_of(int64_t rows) { return (rows + kTileRows - 1) / kTileRows; }
+// compact corrections (4 B/row streamed + exact and add-range side arrays) need the implicit component sum; otherwise inline
+inline void decide_layout(bbq_index *ix) {
+  ix->layout = (ix->want_compact && !ix->has_x1) ? kLayoutCompact : kLayoutInline;
+  ix->tile_stride = tile_stride_of(ix->w16, ix->layout, ix->has_x1);
+  ix->bytes_per_row = ix->tile_stride / kTileRows;
+}
+
+// ---- bbq_append.cpp: the one path that writes rows into a storage.  A creation, a build and a load are appends to an empty storage;
+// all of it runs on the context's aux_stream with the context mutex held and the device current.
+#pragma GCC visibility push(hidden)
+// Room for `need_tiles` tiles of a storage.  While they fit its capacity nothing happens and the rows are written in place; otherwise
+// larger buffers are allocated HERE and the tiles in use copied over device to device - the storage itself only changes in commit(),
+// so a failure on the way costs nothing but these buffers.
+struct Room {
+  DevBuf<uint8_t> tiles;
+  DevBuf<double> exact;
+  int64_t cap_tiles = 0;
+  bool grown = false;
+  uint8_t *d_tiles = nullptr;   // where the rows are written
+  double *d_exact = nullptr;
+  float *d_add_range = nullptr;
+};
+// geometric: half as much again as the capacity, at least what is needed (an empty storage gets exactly what is needed); otherwise
+// exactly what is needed.  BBQ_ERR_OOM without device memory.
+int make_room(bbq_index *ix, Storage &st, int64_t need_tiles, Room &r, bool geometric = true);
+// the rows (or the reservation) published: called after the device has completed everything that wrote them and everything that read
+// the old buffers, which are released here.  The rows of the main storage are the rows of the index.
+void commit(bbq_index *ix, Storage &st, Room &r, int64_t n_rows);
+// What rows mean for an index that stores no explicit component sums when a row's sum is not its popcount / code sum.  kDecide (a
+// creation, whose layout is still open): the index stores the sums from now on, and the layout follows.  kRequire (an append): the
+// rows are refused with BBQ_ERR_UNSUPPORTED, as are multi-bit codes not below 2^indexBits, before anything is written.  A storage
+// that holds neither rows nor room decides whatever the mode: nothing would have to be re-tiled.
+enum class Sums { kDecide, kRequire };
+// n rows in host memory, in the caller's shape, become the rows behind those `st` holds
+int append_host_rows(bbq_index *ix, Storage &st, const uint8_t *codes, const double *corr, int64_t n, Sums mode);
+// n fp32 rows -> d_vT4, the [ceil(dim/4)][tiles_of(n) * 64] float4 transposed copy, normalized for COSINE and validated: the first NaN
+// / Infinity in row-major order is BBQ_ERR_NAN_INPUT / BBQ_ERR_INF_INPUT with its position in *bad_row, *bad_col (when non-null)
+int stage_vectors(DeviceCtx *ctx, const float *vectors, int64_t n, int32_t dim, int32_t sim, DevBuf<float> &d_vT4, int64_t *bad_row, int32_t *bad_col);
+// the n staged vectors quantized against d_cen become the rows behind those the main storage holds; codes_out / corr_out (optional) get
+// them in the caller's shape.  Releases d_vT4 as soon as it has been read where more memory is needed behind it.
+int quantize_into(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d_cen, int32_t sim, double lambda, int32_t iters, Sums mode,
+                  uint8_t *codes_out, double *corr_out);
+#pragma GCC visibility pop
 // waits for the slots an asynchronous sharded scan has left busy on this device (all, or only `owner`'s) and books their timing.
 // Context mutex held by the caller.
 int settle_shard_slots(DeviceCtx *ctx, bbq_index *owner);

@@ -1,5 +1,5 @@
-// bbq_index.cpp - the per-device context and the index object: creation from rows, tile storage, the Infinity-Cache budget of a
-// launch (launch_view), statistics, options.
+// bbq_index.cpp - the per-device context and the index object: creation from rows (written by bbq_append.cpp's path), the
+// Infinity-Cache budget of a launch (launch_view), statistics, options.
 #include <string.h>
 #include <chrono>
 #include <memory>
@@ -81,72 +81,6 @@ int attach_index(bbq_index *ix, DeviceCtx *ctx, int device, int32_t dim, int32_t
   ix->ctx = ctx;
   ix->slots = ctx->slots;
   return ensure_aux_qbuf(ctx, qbuf_bytes_per_query_w(ix->w16));
-}
-
-// ------------------------------------------------------------------------------------------------ storage
-
-static int make_storage(bbq_index *ix, Storage &st, const uint8_t *codes, const double *corr, int64_t n_rows, int64_t row_id_base,
-                        bool check_x1) {
-  const int64_t pb = ix->store_bits > 1 ? ix->dim : ix->pb;  // bytes per row as the caller hands them over (multi-bit: one byte per dimension)
-  DevBuf<uint8_t> d_codes;
-  DevBuf<double> d_corr;
-  hipStream_t s = ix->ctx->aux_stream;
-  if (n_rows > 0) {
-    HIPCHK(d_codes.alloc((size_t)(n_rows * pb)));
-    HIPCHK(d_corr.alloc((size_t)n_rows * 4));
-    HIPCHK(hipMemcpyAsync(d_codes, codes, (size_t)(n_rows * pb), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_corr, corr, (size_t)n_rows * 32, hipMemcpyHostToDevice, s));
-  }
-  return storage_from_device_rows(ix, st, d_codes, d_corr, n_rows, row_id_base, check_x1);  // synchronises before the scratch rows go
-}
-
-// rows already in device memory (codes in the caller's shape, corrections [n][4]) -> tile records of `st`; decides the layout of
-// the index on the way (check_x1).  Returns after the device work has completed.
-int storage_from_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const double *d_corr, int64_t n_rows, int64_t row_id_base,
-                             bool check_x1) {
-  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
-  const bool multibit = ix->store_bits > 1;
-  const int64_t pb = multibit ? ix->dim : ix->pb;
-  DevBuf<uint32_t> d_mis;
-  hipStream_t s = ix->ctx->aux_stream;
-  if (check_x1) {
-    // quantizedComponentSum of a 1-bit row is its popcount (src/optimizedScalarQuantizer.ts:204-209); if that
-    // holds for every row the 8 bytes need not be stored or read.  Decided once per index, over all storages.
-    uint32_t mis = 0;
-    HIPCHK(d_mis.alloc(1));
-    HIPCHK(hipMemsetAsync(d_mis, 0, 4, s));
-    if (multibit) HIPCHK(launch_check_x1_multibit(d_codes, d_corr, n_rows, ix->dim, d_mis, s));
-    else HIPCHK(launch_check_x1(d_codes, d_corr, n_rows, (int32_t)pb, d_mis, s));
-    HIPCHK(hipMemcpyAsync(&mis, d_mis, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (mis) ix->has_x1 = 1;
-  }
-  // compact corrections (4 B/row streamed + exact and add-range side arrays) need the implicit component sum; otherwise inline
-  ix->layout = (ix->want_compact && !ix->has_x1) ? kLayoutCompact : kLayoutInline;
-  ix->tile_stride = tile_stride_of(ix->w16, ix->layout, ix->has_x1);
-  ix->bytes_per_row = ix->tile_stride / kTileRows;
-  if (n_tiles > 0) {
-    HIPCHK(st.d_tiles.alloc((size_t)(n_tiles * ix->tile_stride)));
-    if (ix->layout == kLayoutCompact) HIPCHK(st.d_exact.alloc((size_t)compact_side_bytes(n_tiles) / 8));
-    st.cap_tiles = n_tiles;
-    if (multibit) {
-      uint32_t bad = 0;
-      HIPCHK(d_mis.reserve(1));
-      HIPCHK(hipMemsetAsync(d_mis, 0, 4, s));
-      HIPCHK(launch_retile_multibit(d_codes, d_corr, n_rows, ix->dim, ix->store_bits, ix->index_bits, st.d_tiles, ix->w16, ix->tile_stride, ix->has_x1, ix->layout,
-                                    st.d_exact, d_mis, s));
-      HIPCHK(hipMemcpyAsync(&bad, d_mis, 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      if (bad) return fail(BBQ_ERR_INVALID_ARG, "indexBits=%d: a quantized value is not below %d", ix->index_bits, 1 << ix->index_bits);
-    } else {
-      HIPCHK(launch_retile(d_codes, d_corr, n_rows, (int32_t)pb, st.d_tiles, ix->w16, ix->tile_stride, ix->has_x1, ix->layout, st.d_exact, s));
-    }
-    if (ix->layout == kLayoutCompact) HIPCHK(launch_tile_add_range(st.d_exact, n_rows, const_cast<float *>(add_range_of(st.d_exact, n_tiles)), s));
-    HIPCHK(hipStreamSynchronize(s));
-  }
-  set_storage_view(ix, st, n_rows, row_id_base);
-  HIPCHK(hipStreamSynchronize(s));  // the scratch rows are released on return
-  return BBQ_OK;
 }
 
 // The view a launch gets: the stored view + which chunks it loads cache-resident.  The indexes that have launched sweeps on the device
@@ -257,7 +191,6 @@ int bbq_index_create_shard_opts(const uint8_t *codes, const double *corr, int64_
   if (rc != BBQ_OK) return rc;
 
   std::unique_ptr<bbq_index> ix(new bbq_index());
-  ix->n_rows = n_rows;
   ix->row_base = row_base;
   ix->centroid_dp = centroid_dp;
   ix->has_pilot = n_pilot > 0;
@@ -265,21 +198,16 @@ int bbq_index_create_shard_opts(const uint8_t *codes, const double *corr, int64_
   std::lock_guard<std::mutex> lk(ctx->mu);
   rc = attach_index(ix.get(), ctx, device, dim, index_bits);
   if (rc != BBQ_OK) return rc;
-  if (ix->has_pilot) {
-    rc = make_storage(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, 0, true);
-    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
-    const int had = ix->has_x1;
-    rc = make_storage(ix.get(), ix->main, codes, corr, n_rows, row_base, true);
-    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
-    if (ix->has_x1 != had) {  // main needs explicit sums but pilot was built without: rebuild the pilot
-      ix->pilot = Storage();
-      rc = make_storage(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, 0, false);
-      if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
-    }
-  } else {
-    rc = make_storage(ix.get(), ix->main, codes, corr, n_rows, row_base, true);
-    if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
+  // each storage is an append to an empty one.  Whether the index stores explicit component sums is decided once, over pilot and main
+  ix->main.row_id_base = row_base;
+  if (ix->has_pilot) rc = append_host_rows(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, Sums::kDecide);
+  const int had = ix->has_x1;
+  if (rc == BBQ_OK) rc = append_host_rows(ix.get(), ix->main, codes, corr, n_rows, Sums::kDecide);
+  if (rc == BBQ_OK && ix->has_pilot && ix->has_x1 != had) {  // main needs explicit sums but pilot was built without: rebuild the pilot
+    ix->pilot = Storage();
+    rc = append_host_rows(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, Sums::kDecide);
   }
+  if (rc != BBQ_OK) { destroy_unlocked(ix.release()); return rc; }
   *out = ix.release();
   return BBQ_OK;
 }

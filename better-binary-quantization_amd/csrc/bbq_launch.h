@@ -27,16 +27,16 @@ hipError_t launch_pack(const int32_t *counts, const uint64_t *lists, int64_t lis
 // the build kernels below that take row0 (tile0) write at a row offset: codes / corr are the rows [row0, n_rows) of the storage, the
 // first of them lands in lane row0 % 64 of tile row0 / 64 and nothing below row0 is touched (0: a creation)
 hipError_t launch_retile(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t pb, uint8_t *tiles, int32_t w16,
-                         int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, hipStream_t s, int64_t row0 = 0);
+                         int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, hipStream_t s, int64_t row0);
 // multi-bit index (store_bits 2 / 4 / 8): codes are unpacked rows [n][dim]; *bad is raised by a code that is not below 2^index_bits
 hipError_t launch_retile_multibit(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t store_bits, int32_t index_bits, uint8_t *tiles,
                                   int32_t w16, int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, uint32_t *bad, hipStream_t s,
-                                  int64_t row0 = 0);
+                                  int64_t row0);
 // multi-bit rows [count bytes]: *bad is raised by a code that is not below 2^index_bits (nothing is written)
 hipError_t launch_check_code_range(const uint8_t *codes, int64_t count, int32_t index_bits, uint32_t *bad, hipStream_t s);
 hipError_t launch_check_x1_multibit(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, uint32_t *mismatch, hipStream_t s);
 // compact layout: each tile's {min, max} of additionalCorrection (read from exact[]) -> add_range[tile][2]
-hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0 = 0);
+hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0);
 hipError_t launch_check_x1(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t pb, uint32_t *mismatch,
                            hipStream_t s);
 
@@ -55,13 +55,13 @@ hipError_t launch_build_centroid(const float *vT4, int64_t n, int32_t dim, int64
 // row0 > 0: the n vectors become the rows [row0, row0 + n) of the storage (corr_rm stays indexed by the vector)
 hipError_t launch_build_quantize1(const float *vT4, int64_t n, int32_t dim, int64_t npad, const float *centroid, int32_t sim,
                                   double lambda, int32_t iters, uint8_t *tiles, double *exact, double *corr_rm, int32_t w16,
-                                  int32_t tile_stride, int32_t layout, hipStream_t s, int64_t row0 = 0);
+                                  int32_t tile_stride, int32_t layout, hipStream_t s, int64_t row0);
 // indexBits > 1: unpacked codes [n][dim] (one byte per dimension) + row-major corrections [n][4], both in device memory
 hipError_t launch_build_quantize_bits(const float *vT4, int64_t n, int32_t dim, int64_t npad, const float *centroid, int32_t sim,
                                       double lambda, int32_t iters, int32_t bits, uint8_t *codes_rm, double *corr_rm, hipStream_t s);
 // the n rows from row0 on -> codes_rm [n][pb]
 hipError_t launch_build_untile(const uint8_t *tiles, int64_t n, int32_t pb, int32_t w16, int32_t tile_stride, uint8_t *codes_rm,
-                               hipStream_t s, int64_t row0 = 0);
+                               hipStream_t s, int64_t row0);
 
 // exact rerank (bbq_rerank_kernels.hip): one wave per 64 candidates of a query; max_count = longest candidate list
 hipError_t launch_rerank(const RerankArgs &a, int n_queries, int64_t max_count, hipStream_t s);

@@ -349,7 +349,7 @@ int multi_score_rows(bbq_index *ix, const uint8_t *qquant, const double *qcorr, 
 int multi_export(bbq_index *ix, uint8_t *codes, double *corr) {
   MultiState *ms = ix->multi;
   std::lock_guard<std::mutex> lk(ms->mu);
-  const int64_t row_bytes = ix->store_bits == 1 ? ix->pb : ix->dim;
+  const int64_t row_bytes = caller_row_bytes(ix);
   for (MultiShard &sh : ms->shards) {
     int rc = bbq_index_export(sh.ix, codes ? codes + sh.r0 * row_bytes : nullptr, corr ? corr + sh.r0 * 4 : nullptr);
     if (rc != BBQ_OK) return rc;
@@ -498,7 +498,7 @@ int bbq_index_create_multi_opts(const uint8_t *codes, const double *corr, int64_
   ix->device = devices ? devices[0] : 0;
   std::unique_ptr<MultiState> ms(new MultiState());
   // contiguous shards of whole 512-row chunks (the last one takes the remainder); shards that would be empty are not created
-  const int64_t row_bytes = ix->store_bits == 1 ? ix->pb : dim;  // bytes per row as the caller hands them over
+  const int64_t row_bytes = caller_row_bytes(ix.get());
   const int64_t per = std::max<int64_t>(kChunkRows, ((n_rows + n_shards - 1) / n_shards + kChunkRows - 1) / kChunkRows * kChunkRows);
   auto bail = [&](int code) {
     ix->multi = ms.release();

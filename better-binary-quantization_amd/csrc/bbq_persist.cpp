@@ -364,7 +364,6 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
   rc = attach_index(ix.get(), ctx, device, h.dimensions, h.indexBits);
   if (rc != BBQ_OK) return rc;
   ix->w16 = h.w16;
-  ix->n_rows = h.vectorCount;
   ix->row_base = h.rowBase;
   ix->centroid_dp = h.centroidSquareMagnitude;
   ix->has_pilot = px.pilotRows > 0;
@@ -377,18 +376,17 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
     destroy_unlocked(ix.release());
     return code;
   };
+  // both storages get room for exactly the tiles in the file (read_meta has checked its sizes against them), the file's bytes go
+  // there as they are - with no spare capacity the side arrays lie back to back as the file has them - and the rows are published
   Storage &st = ix->main, &pt = ix->pilot;
-  if (h.tilesBytes > 0 && st.d_tiles.alloc((size_t)h.tilesBytes) != hipSuccess)
-    return bail(fail(BBQ_ERR_OOM, "bbq_index_load: %lld bytes of tiles", (long long)h.tilesBytes));
-  if (h.exactBytes > 0 && st.d_exact.alloc((size_t)h.exactBytes / 8) != hipSuccess)  // (whole doubles: read_meta has checked the size)
-    return bail(fail(BBQ_ERR_OOM, "bbq_index_load: %lld bytes of exact corrections", (long long)h.exactBytes));
-  if (px.pilotTilesBytes > 0 && pt.d_tiles.alloc((size_t)px.pilotTilesBytes) != hipSuccess)
-    return bail(fail(BBQ_ERR_OOM, "bbq_index_load: %lld bytes of pilot tiles", (long long)px.pilotTilesBytes));
-  if (px.pilotExactBytes > 0 && pt.d_exact.alloc((size_t)px.pilotExactBytes / 8) != hipSuccess)
-    return bail(fail(BBQ_ERR_OOM, "bbq_index_load: %lld bytes of pilot corrections", (long long)px.pilotExactBytes));
+  st.row_id_base = h.rowBase;
+  Room room, proom;
+  rc = make_room(ix.get(), st, tiles_of(h.vectorCount), room);
+  if (rc == BBQ_OK) rc = make_room(ix.get(), pt, tiles_of(px.pilotRows), proom);
+  if (rc != BBQ_OK) return bail(rc);
   const size_t piece = 64u << 20;
   std::vector<uint8_t> buf(piece);
-  uint8_t *dst[4] = {st.d_tiles, (uint8_t *)st.d_exact.get(), pt.d_tiles, (uint8_t *)pt.d_exact.get()};
+  uint8_t *dst[4] = {room.d_tiles, (uint8_t *)room.d_exact, proom.d_tiles, (uint8_t *)proom.d_exact};
   const int64_t len[4] = {h.tilesBytes, h.exactBytes, px.pilotTilesBytes, px.pilotExactBytes};
   uint64_t dsum = kFnvSeed;
   for (int part = 0; part < 4; ++part) {
@@ -401,10 +399,8 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
     }
   }
   if (dsum != want_sum) return bail(fail(BBQ_ERR_INVALID_ARG, "%s: vector data checksum mismatch", dpath.c_str()));
-  st.cap_tiles = (h.vectorCount + kTileRows - 1) / kTileRows;
-  pt.cap_tiles = (px.pilotRows + kTileRows - 1) / kTileRows;
-  set_storage_view(ix.get(), st, h.vectorCount, h.rowBase);
-  if (ix->has_pilot) set_storage_view(ix.get(), pt, px.pilotRows, 0);
+  commit(ix.get(), st, room, h.vectorCount);
+  if (ix->has_pilot) commit(ix.get(), pt, proom, px.pilotRows);
   if (centroid_out) memcpy(centroid_out, cen.data(), cen.size() * 4);
   *out = ix.release();
   return BBQ_OK;

@@ -50,6 +50,30 @@ void sort_desc_stable(std::vector<Ranked> &v) {
   }
 }
 
+// n rows behind those the handle holds.  The buffer grows by half as much again, at least to what is needed (an empty one gets exactly
+// that), and the old rows move device to device.  Context mutex held, device current; `who` names the entry point in messages.
+int append_vectors(bbq_vectors *v, const float *vectors, int64_t n, const char *who) {
+  const int64_t dim = v->dim, total = v->n + n;
+  DevBuf<float> grown;
+  float *dst = v->d;
+  if ((int64_t)v->d.size() < total * dim) {
+    const int64_t cap = std::max<int64_t>(total, (int64_t)(v->d.size() / (size_t)dim) * 3 / 2);
+    const hipError_t e = grown.alloc((size_t)(cap * dim));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "%s: %lld x %d fp32: %s", who, (long long)cap, v->dim, hipGetErrorString(e)); }
+    if (v->n > 0) HIPCHK(hipMemcpy(grown, v->d, (size_t)(v->n * dim) * sizeof(float), hipMemcpyDeviceToDevice));
+    dst = grown;
+  }
+  const int64_t count = n * dim, piece = 64LL << 20;  // 256 MB pieces keep the runtime's pinned staging bounded
+  for (int64_t o = 0; o < count; o += piece) {
+    const hipError_t e = hipMemcpy(dst + v->n * dim + o, vectors + o, (size_t)std::min(piece, count - o) * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(BBQ_ERR_HIP, "%s: copy: %s", who, hipGetErrorString(e));
+  }
+  HIPCHK(hipDeviceSynchronize());
+  if (grown) v->d = std::move(grown);  // the old rows are released here, behind the copy
+  v->n = total;
+  return BBQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -67,16 +91,10 @@ int bbq_vectors_create(const float *vectors, int64_t n, int32_t dim, int32_t dev
   std::unique_ptr<bbq_vectors> v(new bbq_vectors());
   v->device = device;
   v->ctx = ctx;
-  v->n = n;
   v->dim = dim;
-  if (n > 0) {
-    hipError_t e = v->d.alloc((size_t)n * dim);
-    if (e != hipSuccess) return fail(BBQ_ERR_OOM, "bbq_vectors_create: %lld x %d fp32: %s", (long long)n, dim, hipGetErrorString(e));
-    const int64_t total = n * dim, piece = 64LL << 20;  // 256 MB pieces keep the runtime's pinned staging bounded
-    for (int64_t o = 0; o < total; o += piece) {
-      e = hipMemcpy(v->d + o, vectors + o, (size_t)std::min(piece, total - o) * sizeof(float), hipMemcpyHostToDevice);
-      if (e != hipSuccess) return fail(BBQ_ERR_HIP, "bbq_vectors_create: copy: %s", hipGetErrorString(e));
-    }
+  if (n > 0) {  // an empty handle, and the rows appended to it
+    rc = append_vectors(v.get(), vectors, n, "bbq_vectors_create");
+    if (rc != BBQ_OK) return rc;
   }
   *out = v.release();
   return BBQ_OK;
@@ -99,25 +117,7 @@ int bbq_vectors_append(bbq_vectors *v, const float *vectors, int64_t n) {
   std::lock_guard<std::mutex> lk(v->ctx->mu);
   HIPCHK(hipSetDevice(v->device));
   HIPCHK(hipStreamSynchronize(v->ctx->aux_stream));  // bbq_rerank_scores reads the rows on it
-  const int64_t dim = v->dim, total = v->n + n;
-  DevBuf<float> grown;
-  float *dst = v->d;
-  if ((int64_t)v->d.size() < total * dim) {  // half as much again, at least what is needed; the old rows move device to device
-    const int64_t cap = std::max<int64_t>(total, (int64_t)(v->d.size() / (size_t)dim) * 3 / 2);
-    const hipError_t e = grown.alloc((size_t)(cap * dim));
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "bbq_vectors_append: %lld x %d fp32: %s", (long long)cap, v->dim, hipGetErrorString(e)); }
-    if (v->n > 0) HIPCHK(hipMemcpy(grown, v->d, (size_t)(v->n * dim) * sizeof(float), hipMemcpyDeviceToDevice));
-    dst = grown;
-  }
-  const int64_t count = n * dim, piece = 64LL << 20;
-  for (int64_t o = 0; o < count; o += piece) {
-    const hipError_t e = hipMemcpy(dst + v->n * dim + o, vectors + o, (size_t)std::min(piece, count - o) * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(BBQ_ERR_HIP, "bbq_vectors_append: copy: %s", hipGetErrorString(e));
-  }
-  HIPCHK(hipDeviceSynchronize());
-  if (grown) v->d = std::move(grown);  // the old rows are released here, behind the copy
-  v->n = total;
-  return BBQ_OK;
+  return append_vectors(v, vectors, n, "bbq_vectors_append");
 }
 
 int64_t bbq_vectors_size(const bbq_vectors *v) { return v ? v->n : 0; }

@@ -35,7 +35,7 @@ def _reference_accepts(name):
 _WANTED = ("ties_", "m_768d_", "m_100d_", "ib2_", "ib4_", "ib8_", "big_20000x128_cos", "big_50000x768_cos", "big_30000x1536_mip",
            "big_20000x1024_euc_qb8", "edge_dim1")
 CASES = [n for n in O.golden_names() if n.startswith(_WANTED) and _reference_accepts(n)]
-CUTS = (1, 63, 64, 65, 511, 512, 513)
+CUTS = (0, 1, 63, 64, 65, 511, 512, 513)   # 0: an index created over zero rows, every row appended
 VARIANTS = ({}, {"force_dense": 1}, {"sweep_share": 4}, {"sweep_share": 32}, {"device_select": 0})
 
 
@@ -114,7 +114,7 @@ def test_append_rows_parity(name, compact, tmp_path):
     ks = sorted({1, 10, 100, n, n + 5})
     twin = make_index(codes, corr, dim, cdp, compact, ib)
     twin_files = file_bytes(twin, str(tmp_path / "twin"), cen, sim)
-    splits = [[c, n] for c in sorted({c for c in CUTS + (n - 1,) if 0 < c < n})]
+    splits = [[c, n] for c in sorted({c for c in CUTS + (n - 1,) if 0 <= c < n})]
     if n >= 3:
         splits.append([n // 3, 2 * n // 3, n])   # three pieces
     try:
@@ -220,6 +220,34 @@ def test_raw_append_equals_the_oracle_recipe(sim, dim, na, nb, ib, compact, tmp_
             twin.close()
     finally:
         ix.close()
+
+
+@pytest.mark.parametrize("compact", [True, False])
+@pytest.mark.parametrize("sim,dim,n,ib", [(1, 64, 1, 1), (0, 100, 64, 1), (2, 64, 130, 1), (1, 100, 130, 2)])
+def test_build_equals_raw_append_to_empty(sim, dim, n, ib, compact, tmp_path):
+    """a build is a raw append to an empty index: one lane, exactly a tile, two tiles and a partly filled third"""
+    rows = O.mulberry32(141 + n, n * dim).reshape(n, dim)
+    queries = O.mulberry32(142, 2 * dim).reshape(2, dim)
+    ocodes, ocorr, ocen = O.build_index(rows, sim, ib=ib)
+    a, acodes, acorr, cen = B.Index.build(rows, sim, index_bits=ib, corrections="compact" if compact else "inline")
+    b = make_index(ocodes[:0], ocorr[:0], dim, O.centroid_dp(cen), compact, ib)
+    try:
+        np.testing.assert_array_equal(cen.view(np.uint32), ocen.view(np.uint32))
+        bcodes, bcorr = b.append(rows, cen, sim)
+        assert a.n == b.n == n
+        for codes, corr in ((acodes, acorr), (bcodes, bcorr)):
+            np.testing.assert_array_equal(codes, ocodes)
+            np.testing.assert_array_equal(canon64(corr), canon64(ocorr))
+        assert a.bytes_per_row == b.bytes_per_row
+        assert a.capacity == b.capacity
+        fa, fb = file_bytes(a, str(tmp_path / "built"), cen, sim), file_bytes(b, str(tmp_path / "appended"), cen, sim)
+        assert fa[0] == fb[0] and fa[1] == fb[1]
+        orc = Oracle(ocodes, ocorr, dim, ocen, sim, 4, queries, ib)
+        for ix, msg in ((a, "built"), (b, "appended to empty")):
+            orc.check_search(ix, sorted({1, 10, n}), msg)
+    finally:
+        a.close()
+        b.close()
 
 
 def test_raw_append_to_an_index_with_explicit_sums():
