@@ -1,7 +1,7 @@
 // bbq_append.cpp - the one path that writes rows into a device-resident index (DESIGN.md "Appending rows"), and the entry points that
 // grow an index in place: bbq_index_append_rows (rows already quantized), bbq_index_append (raw fp32 rows quantized on the device
 // against the index's centroid), bbq_index_reserve / _capacity.  bbq_index_create*, bbq_index_build* and bbq_index_load write their
-// rows through the same functions, as appends to an empty storage: the build kernels (bbq_build_kernels.hip, bbq_kernels.hip) take a
+// rows through the same functions, as appends to an empty storage: the build kernels (bbq_build_kernels.hip) take a
 // row offset, and a creation's is 0.  Everything here validates and allocates first, writes second and publishes the new row count
 // last: an append that fails leaves the index as it was.
 #include <string.h>
@@ -35,10 +35,10 @@ int quiesce(bbq_index *ix, const char *who) {
 
 // the one function that allocates tile records: d_tiles and, for the compact layout, the side arrays for `cap` tiles
 int alloc_tiles(const bbq_index *ix, int64_t cap, DevBuf<uint8_t> &tiles, DevBuf<double> &exact) {
-  if (tiles.alloc((size_t)(cap * ix->tile_stride)) != hipSuccess ||
-      (ix->layout == kLayoutCompact && exact.alloc((size_t)compact_side_bytes(cap) / 8) != hipSuccess)) {
+  if (tiles.alloc((size_t)(cap * ix->geom.tile_stride)) != hipSuccess ||
+      (ix->geom.layout == kLayoutCompact && exact.alloc((size_t)compact_side_bytes(cap) / 8) != hipSuccess)) {
     (void)hipGetLastError();
-    return fail(BBQ_ERR_OOM, "no device memory for %lld rows (%lld bytes of tiles)", (long long)(cap * kTileRows), (long long)(cap * ix->tile_stride));
+    return fail(BBQ_ERR_OOM, "no device memory for %lld rows (%lld bytes of tiles)", (long long)(cap * kTileRows), (long long)(cap * ix->geom.tile_stride));
   }
   return BBQ_OK;
 }
@@ -60,7 +60,7 @@ int stage_rows(const bbq_index *ix, const uint8_t *codes, const double *corr, in
 // then the device has completed and the rows may be committed
 int finish_rows(const bbq_index *ix, const Room &room, int64_t row0, int64_t total) {
   hipStream_t s = ix->ctx->aux_stream;
-  if (ix->layout == kLayoutCompact) HIPCHK(launch_tile_add_range(room.d_exact, total, room.d_add_range, s, row0 / kTileRows));
+  if (ix->geom.layout == kLayoutCompact) HIPCHK(launch_tile_add_range(room.d_exact, total, room.d_add_range, s, row0 / kTileRows));
   HIPCHK(hipStreamSynchronize(s));
   return BBQ_OK;
 }
@@ -69,25 +69,22 @@ int finish_rows(const bbq_index *ix, const Room &room, int64_t row0, int64_t tot
 // that holds for every row the 8 bytes need not be stored or read.  An index that stores the sums already takes any row.  Nothing is
 // written: an append that is refused here has not touched even a padding lane.
 int check_device_rows(bbq_index *ix, const uint8_t *d_codes, const double *d_corr, int64_t n, Sums mode) {
-  const bool multibit = ix->store_bits > 1, range = multibit && mode == Sums::kRequire;
-  if (n > 0 && (!ix->has_x1 || range)) {
+  const bool multibit = ix->geom.store_bits > 1, range = multibit && mode == Sums::kRequire;
+  if (n > 0 && (!ix->geom.has_x1 || range)) {
     hipStream_t s = ix->ctx->aux_stream;
     uint32_t flags[2] = {0, 0};  // a sum that is not the implied one; a code out of range
     DevBuf<uint32_t> d_flags;
     HIPCHK(d_flags.alloc(2));
     HIPCHK(hipMemsetAsync(d_flags, 0, 8, s));
-    if (!ix->has_x1) {
-      if (multibit) HIPCHK(launch_check_x1_multibit(d_codes, d_corr, n, ix->dim, d_flags, s));
-      else HIPCHK(launch_check_x1(d_codes, d_corr, n, ix->pb, d_flags, s));
-    }
-    if (range) HIPCHK(launch_check_code_range(d_codes, n * ix->dim, ix->index_bits, d_flags + 1, s));
+    if (!ix->geom.has_x1) HIPCHK(launch_check_x1(StagedRows{d_codes, d_corr}, n, ix->geom, d_flags, s));
+    if (range) HIPCHK(launch_check_code_range(d_codes, n * ix->geom.dim, ix->index_bits, d_flags + 1, s));
     HIPCHK(hipMemcpyAsync(flags, d_flags, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (flags[1]) return fail(BBQ_ERR_INVALID_ARG, "indexBits=%d: a quantized value is not below %d", ix->index_bits, 1 << ix->index_bits);
     if (flags[0] && mode == Sums::kRequire)
       return fail(BBQ_ERR_UNSUPPORTED, "a row's quantizedComponentSum is not its %s and the index stores no explicit sums: holding the row would mean "
                   "re-tiling the whole index (create it over all rows instead)", multibit ? "code sum" : "popcount");
-    if (flags[0]) ix->has_x1 = 1;
+    if (flags[0]) ix->geom.has_x1 = 1;
   }
   if (mode == Sums::kDecide) decide_layout(ix);  // decided once per index, over all its storages
   return BBQ_OK;
@@ -101,17 +98,14 @@ int write_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const 
   int rc = make_room(ix, st, tiles_of(total), room);
   if (rc != BBQ_OK) return rc;
   if (n > 0) {
-    uint32_t bad = 0;  // raised by retile_multibit: a code that is not below 2^indexBits (an append has asked before)
+    uint32_t bad = 0;  // raised while multi-bit rows are re-tiled: a code that is not below 2^indexBits (an append has asked before)
     DevBuf<uint32_t> d_bad;
-    if (ix->store_bits > 1) {
+    if (ix->geom.store_bits > 1) {
       HIPCHK(d_bad.alloc(1));
       HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
-      HIPCHK(launch_retile_multibit(d_codes, d_corr, total, ix->dim, ix->store_bits, ix->index_bits, room.d_tiles, ix->w16, ix->tile_stride, ix->has_x1, ix->layout,
-                                    room.d_exact, d_bad, s, row0));
-      HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
-    } else {
-      HIPCHK(launch_retile(d_codes, d_corr, total, ix->pb, room.d_tiles, ix->w16, ix->tile_stride, ix->has_x1, ix->layout, room.d_exact, s, row0));
     }
+    HIPCHK(launch_retile(tile_dest(ix, room), StagedRows{d_codes, d_corr}, total, row0, ix->index_bits, d_bad, s));
+    if (d_bad) HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
     rc = finish_rows(ix, room, row0, total);
     if (rc != BBQ_OK) return rc;
     if (bad) return fail(BBQ_ERR_INVALID_ARG, "indexBits=%d: a quantized value is not below %d", ix->index_bits, 1 << ix->index_bits);
@@ -126,11 +120,11 @@ int append_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const
   // a storage that holds neither rows nor room has nothing that would have to be re-tiled: an append to it decides as a creation does
   // (and is written into buffers of its own, so rows refused after the write have not touched the index either)
   if (st.cap_tiles == 0) mode = Sums::kDecide;
-  const int32_t had_x1 = ix->has_x1;
+  const int32_t had_x1 = ix->geom.has_x1;
   int rc = check_device_rows(ix, d_codes, d_corr, n, mode);
   if (rc == BBQ_OK) rc = write_device_rows(ix, st, d_codes, d_corr, n);
-  if (rc != BBQ_OK && ix->has_x1 != had_x1) {  // rows that were refused have decided nothing
-    ix->has_x1 = had_x1;
+  if (rc != BBQ_OK && ix->geom.has_x1 != had_x1) {  // rows that were refused have decided nothing
+    ix->geom.has_x1 = had_x1;
     decide_layout(ix);
   }
   return rc;
@@ -159,8 +153,8 @@ int make_room(bbq_index *ix, Storage &st, int64_t need_tiles, Room &r, bool geom
   const int64_t used = tiles_of(st.view.n_rows);
   hipStream_t s = ix->ctx->aux_stream;
   if (used > 0) {
-    HIPCHK(hipMemcpyAsync(r.d_tiles, st.d_tiles, (size_t)(used * ix->tile_stride), hipMemcpyDeviceToDevice, s));
-    if (ix->layout == kLayoutCompact) {
+    HIPCHK(hipMemcpyAsync(r.d_tiles, st.d_tiles, (size_t)(used * ix->geom.tile_stride), hipMemcpyDeviceToDevice, s));
+    if (ix->geom.layout == kLayoutCompact) {
       HIPCHK(hipMemcpyAsync(r.d_exact, st.d_exact, (size_t)(used * kTileRows) * 32, hipMemcpyDeviceToDevice, s));
       HIPCHK(hipMemcpyAsync(r.d_add_range, st.view.add_range, (size_t)used * 8, hipMemcpyDeviceToDevice, s));
     }
@@ -225,7 +219,7 @@ int stage_vectors(DeviceCtx *ctx, const float *vectors, int64_t n, int32_t dim, 
 int quantize_into(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d_cen, int32_t sim, double lambda, int32_t iters, Sums mode,
                   uint8_t *codes_out, double *corr_out) {
   hipStream_t st = ix->ctx->aux_stream;
-  const int32_t dim = ix->dim, pb = ix->pb;
+  const int32_t dim = ix->geom.dim, pb = pb_of(ix->geom);
   const int64_t npad = tiles_of(n) * kTileRows;
   DevBuf<double> d_corr;
   DevBuf<uint8_t> d_codes;
@@ -244,18 +238,18 @@ int quantize_into(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d
     if (codes_out) HIPCHK(hipMemcpy(codes_out, d_codes, (size_t)n * dim, hipMemcpyDeviceToHost));
     return append_device_rows(ix, ix->main, d_codes, d_corr, n, mode);
   }
-  if ((corr_out || ix->has_x1) && d_corr.alloc((size_t)n * 4) != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "no device memory for the corrections"); }
-  if (ix->has_x1) {
-    // an index with explicit sums keeps a fourth corrections block the in-place kernel does not write: such rows (rare: the index was
-    // created from rows whose sums are not their popcounts) take the row-major path, packed codes from a scratch tile set
+  if ((corr_out || ix->geom.has_x1) && d_corr.alloc((size_t)n * 4) != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "no device memory for the corrections"); }
+  if (ix->geom.has_x1) {
+    // an index with explicit sums (rare: it was created from rows whose sums are not their popcounts) takes freshly quantized rows as
+    // it takes a caller's, on the row-major path: packed codes from a scratch tile set without sums
     DevBuf<uint8_t> d_tmp;
-    const int32_t stride1 = tile_stride_of(ix->w16, kLayoutInline, 0);
-    if (d_tmp.alloc((size_t)(npad / kTileRows) * stride1) != hipSuccess || d_codes.alloc((size_t)n * pb) != hipSuccess) {
+    if (d_tmp.alloc((size_t)(npad / kTileRows) * scratch_tile_dest(ix, nullptr).geom.tile_stride) != hipSuccess || d_codes.alloc((size_t)n * pb) != hipSuccess) {
       (void)hipGetLastError();
       return fail(BBQ_ERR_OOM, "no device memory for %lld quantized rows", (long long)n);
     }
-    HIPCHK(launch_build_quantize1(d_vT4, n, dim, npad, d_cen, sim, lambda, iters, d_tmp, nullptr, d_corr, ix->w16, stride1, kLayoutInline, st, 0));
-    HIPCHK(launch_build_untile(d_tmp, n, pb, ix->w16, stride1, d_codes, st, 0));
+    const TileDest tmp = scratch_tile_dest(ix, d_tmp);
+    HIPCHK(launch_build_quantize1(d_vT4, n, npad, d_cen, sim, lambda, iters, tmp, d_corr, st, 0));
+    HIPCHK(launch_build_untile(tmp, n, d_codes, st, 0));
     HIPCHK(hipStreamSynchronize(st));
     if (corr_out) HIPCHK(hipMemcpy(corr_out, d_corr, (size_t)n * 32, hipMemcpyDeviceToHost));
     if (codes_out) HIPCHK(hipMemcpy(codes_out, d_codes, (size_t)n * pb, hipMemcpyDeviceToHost));
@@ -268,11 +262,10 @@ int quantize_into(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d
   Room room;
   int rc = make_room(ix, ix->main, tiles_of(total), room);
   if (rc != BBQ_OK) return rc;
-  HIPCHK(launch_build_quantize1(d_vT4, n, dim, npad, d_cen, sim, lambda, iters, room.d_tiles, room.d_exact, d_corr, ix->w16, ix->tile_stride, ix->layout, st,
-                                row0));  // :221-249
+  HIPCHK(launch_build_quantize1(d_vT4, n, npad, d_cen, sim, lambda, iters, tile_dest(ix, room), d_corr, st, row0));  // :221-249
   if (corr_out) HIPCHK(hipMemcpyAsync(corr_out, d_corr, (size_t)n * 32, hipMemcpyDeviceToHost, st));
   if (codes_out) {
-    HIPCHK(launch_build_untile(room.d_tiles, n, pb, ix->w16, ix->tile_stride, d_codes, st, row0));
+    HIPCHK(launch_build_untile(tile_dest(ix, room), n, d_codes, st, row0));
     HIPCHK(hipMemcpyAsync(codes_out, d_codes, (size_t)n * pb, hipMemcpyDeviceToHost, st));
   }
   rc = finish_rows(ix, room, row0, total);
@@ -338,9 +331,9 @@ int bbq_index_append(bbq_index *ix, const float *vectors, int64_t n, const float
   if (rc != BBQ_OK) return rc;
   // the rows are quantized against the centroid the index was built with: the caller's
   DevBuf<float> d_vT4, d_cen;
-  if (d_cen.alloc((size_t)(ix->dim + 3) / 4 * 4) != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "no device memory for the centroid"); }
-  HIPCHK(hipMemcpyAsync(d_cen, centroid, (size_t)ix->dim * 4, hipMemcpyHostToDevice, ix->ctx->aux_stream));
-  rc = stage_vectors(ix->ctx, vectors, n, ix->dim, sim, d_vT4, bad_row, bad_col);
+  if (d_cen.alloc((size_t)(ix->geom.dim + 3) / 4 * 4) != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "no device memory for the centroid"); }
+  HIPCHK(hipMemcpyAsync(d_cen, centroid, (size_t)ix->geom.dim * 4, hipMemcpyHostToDevice, ix->ctx->aux_stream));
+  rc = stage_vectors(ix->ctx, vectors, n, ix->geom.dim, sim, d_vT4, bad_row, bad_col);
   if (rc != BBQ_OK) return rc;
   return quantize_into(ix, d_vT4, n, d_cen, sim, lambda, iters, Sums::kRequire, codes_out, corr_out);
 }

@@ -1,5 +1,6 @@
-// bbq_build_kernels.hip - index build on the device (gfx950): BinaryQuantizationFormat.quantizeVectors
-// (reference src/binaryQuantizationFormat.ts:165-263) for every indexBits, bit-exact.
+// bbq_build_kernels.hip - every kernel that builds an index on the device (gfx950), and with that every kernel that WRITES tile records
+// (their layout: bbq_device.h).  BinaryQuantizationFormat.quantizeVectors (reference src/binaryQuantizationFormat.ts:165-263) for every
+// indexBits, bit-exact:
 //
 //   transpose_in   [n][dim] f32 (as uploaded)  ->  vT4[dim/4][npad] float4   (lane = vector => every later access is coalesced)
 //   normalize      COSINE: normalizeVector (src/vectorOperations.ts:11-34), one thread per vector, f64 sum in index order
@@ -12,6 +13,11 @@
 //                  the reference's index order, f64 without FMA contraction; the last pass packs the bits
 //                  (packAsBinary :420-446) straight into the scan kernel's tile records and writes the corrections
 //   untile         tile records -> row-major packed rows (only when the host asks for the codes)
+// and rows that arrive quantized, in the caller's shape:
+//   retile         row-major rows (packed 1-bit, or one byte per dimension) + corrections -> tile records
+//   check_x1       is every quantizedComponentSum the implied one (popcount / code sum)?   check_code_range: every multi-bit code in range?
+//   tile_add_range compact layout: each tile's {min, max} of additionalCorrection
+// Every writer takes its destination as a TileDest and writes a row's corrections through write_corrections.
 //
 // All arithmetic follows the JavaScript number model; -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -22,11 +28,6 @@
 #pragma clang fp contract(off)
 
 namespace bbq {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4b __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2b __attribute__((ext_vector_type(2)));
-typedef double f64x2b __attribute__((ext_vector_type(2)));
 
 // Math.min / Math.max / Math.round as V8 evaluates them
 __device__ __forceinline__ double jmin(double a, double b) {
@@ -174,15 +175,25 @@ __global__ __launch_bounds__(64) void bbq_centroid_kernel(const f32x4 *__restric
   }
 }
 
-// ------------------------------------------------------------------------------------------------ quantize (1 bit)
+// ------------------------------------------------------------------------------------------------ the corrections of one row
+// THE writer of a row's corrections (the tile record, bbq_device.h): lane row % 64 of the corrections block of tile row / 64.  Inline:
+// {lower, upper}, additionalCorrection and - where the geometry stores it - the component sum.  Compact: the compact word, and the exact
+// values in the side row exact[row] (the tiles' ranges of the additive term follow from there: bbq_tile_add_range_kernel).
+__device__ __forceinline__ void write_corrections(const TileDest &out, int64_t row, f64x2 lu, double add, double x1) {
+  const int r = (int)(row % kTileRows);
+  uint8_t *cr = out.tiles + (row / kTileRows) * (int64_t)out.geom.tile_stride + tile_corr_offset(out.geom.w16);
+  if (out.geom.layout == kLayoutCompact) {
+    reinterpret_cast<uint32_t *>(cr)[r] = compact_word(lu.x, lu.y);
+    double *e = out.exact + row * 4;
+    e[0] = lu.x; e[1] = lu.y; e[2] = add; e[3] = 0.0;
+  } else {
+    reinterpret_cast<f64x2 *>(cr)[r] = lu;
+    reinterpret_cast<double *>(cr + kCorrAddOffset)[r] = add;
+    if (out.geom.has_x1) reinterpret_cast<double *>(cr + kCorrSumOffset)[r] = x1;
+  }
+}
 
-struct BuildOut {
-  uint8_t *tiles;      // scan layout (bbq_device.h)
-  double *exact;       // kLayoutCompact side array, or null
-  double *corr_rm;     // [n][4] row-major corrections for the host, or null (bits > 1: required)
-  uint8_t *codes_rm;   // bits > 1: [n][dim] one byte per dimension
-  int32_t w16, tile_stride, layout;
-};
+// ------------------------------------------------------------------------------------------------ quantize (1 bit)
 
 // one pass of computeLoss over the vector (src/optimizedScalarQuantizer.ts:373-407); pm1 = points - 1 = 2^bits - 1
 __device__ __forceinline__ double loss_pass(const f32x4 *__restrict__ col, int64_t npad, const float *__restrict__ s_cen, int dim,
@@ -209,14 +220,14 @@ __device__ __forceinline__ double loss_pass(const f32x4 *__restrict__ col, int64
 }
 
 // bits == 1 packs the row straight into the scan layout; bits > 1 writes what the reference keeps for such an index - one byte per
-// dimension (src/binaryQuantizationFormat.ts:241-245) - to out.codes_rm, and the caller builds the tile records from that.
+// dimension (src/binaryQuantizationFormat.ts:241-245) - to codes_rm, and the caller builds the tile records from that.
 // Vector i becomes row row0 + i of the storage (row0 > 0: an append into the partly filled last tile; lanes below row0 are not
 // touched).  n_out threads write: the n vectors and the padding lanes up to the end of the last tile - with row0 > 0 that can be
 // more than npad, the columns of vT4, which only the valid threads read.
 __global__ __launch_bounds__(256) void bbq_quantize1_kernel(const f32x4 *__restrict__ vT4, int64_t n, int32_t dim, int32_t dim4,
                                                            int64_t npad, const float *__restrict__ centroid, int32_t sim,
-                                                           double lambda, int32_t iters, int32_t bits, BuildOut out, int64_t row0,
-                                                           int64_t n_out) {
+                                                           double lambda, int32_t iters, int32_t bits, TileDest out, double *__restrict__ corr_rm,
+                                                           uint8_t *__restrict__ codes_rm, int64_t row0, int64_t n_out) {
   extern __shared__ float s_cen[];
   for (int i = threadIdx.x; i < dim4 * 4; i += 256) s_cen[i] = i < dim ? centroid[i] : 0.f;
   __syncthreads();
@@ -335,7 +346,7 @@ __global__ __launch_bounds__(256) void bbq_quantize1_kernel(const f32x4 *__restr
     const double step_inv = step > 0 ? 1.0 / step : 0.0;
     double qsum = 0;
     if (valid) {
-      uint8_t *__restrict__ dst = out.codes_rm + vec * (int64_t)dim;
+      uint8_t *__restrict__ dst = codes_rm + vec * (int64_t)dim;
       for (int i4 = 0; i4 < dim4; ++i4) {
         const f32x4 v = col[(int64_t)i4 * npad];
         const float vv[4] = {v.x, v.y, v.z, v.w};
@@ -352,24 +363,23 @@ __global__ __launch_bounds__(256) void bbq_quantize1_kernel(const f32x4 *__restr
           }
         }
       }
-      double *cm = out.corr_rm + vec * 4;
+      double *cm = corr_rm + vec * 4;
       cm[0] = iv0; cm[1] = iv1; cm[2] = (sim == 0) ? norm2 : cdot; cm[3] = qsum;
     }
     return;
   }
 
   // final pass (:192-216): 1-bit threshold at the interval midpoint, packed MSB-first (packAsBinary :420-446) straight into
-  // the tile record: 16-byte chunk j of row r at (j*64 + r)*16
+  // the row's code chunks of its tile record
   const int64_t row = row0 + vec;
-  const int64_t tile = row / kTileRows;
   const int r = (int)(row % kTileRows);
-  uint8_t *tp = out.tiles + tile * (int64_t)out.tile_stride;
+  uint8_t *tp = out.tiles + (row / kTileRows) * (int64_t)out.geom.tile_stride;
   const double a = iv0, b = iv1;
   const double thr = (a + b) / 2;
   double qsum = 0;
   uint32_t wcur = 0;
-  u32x4b chunk = {0, 0, 0, 0};
-  for (int i4 = 0; i4 < out.w16 * 32; ++i4) {
+  u32x4 chunk = {0, 0, 0, 0};
+  for (int i4 = 0; i4 < out.geom.w16 * 32; ++i4) {
     if (valid && i4 < dim4) {
       const f32x4 v = col[(int64_t)i4 * npad];
       const float vv[4] = {v.x, v.y, v.z, v.w};
@@ -390,44 +400,132 @@ __global__ __launch_bounds__(256) void bbq_quantize1_kernel(const f32x4 *__restr
       if (wi == 0) chunk.x = wcur; else if (wi == 1) chunk.y = wcur; else if (wi == 2) chunk.z = wcur; else chunk.w = wcur;
       wcur = 0;
       if (wi == 3) {
-        reinterpret_cast<u32x4b *>(tp)[(i4 >> 5) * kTileRows + r] = chunk;
-        chunk = u32x4b{0, 0, 0, 0};
+        reinterpret_cast<u32x4 *>(tp)[tile_chunk_index(i4 >> 5, r)] = chunk;
+        chunk = u32x4{0, 0, 0, 0};
       }
     }
   }
-  double lower = 0, upper = 0, add = 0;
+  f64x2 lu = {0.0, 0.0};
+  double add = 0;
   if (valid) {
-    lower = iv0;
-    upper = iv1;
+    lu.x = iv0;
+    lu.y = iv1;
     add = (sim == 0) ? norm2 : cdot;  // :219
   }
-  uint8_t *cr = tp + (size_t)out.w16 * (kTileRows * 16);
-  if (out.layout == kLayoutCompact) {
-    // the tiles' additive-correction ranges are computed afterwards from exact[] (launch_tile_add_range)
-    reinterpret_cast<uint32_t *>(cr)[r] = (__float_as_uint((float)lower) >> 16) | ((__float_as_uint((float)upper) >> 16) << 16);
-    double *e = out.exact + row * 4;
-    e[0] = lower; e[1] = upper; e[2] = add; e[3] = 0.0;
-  } else {
-    f64x2b lu = {lower, upper};
-    reinterpret_cast<f64x2b *>(cr)[r] = lu;
-    reinterpret_cast<double *>(cr + 1024)[r] = add;
-  }
-  if (out.corr_rm && valid) {
-    double *cm = out.corr_rm + vec * 4;
-    cm[0] = lower; cm[1] = upper; cm[2] = add; cm[3] = qsum;
+  write_corrections(out, row, lu, add, qsum);  // the component sum of a freshly quantized row is its popcount: a geometry with has_x1 = 0 drops it
+  if (corr_rm && valid) {
+    double *cm = corr_rm + vec * 4;
+    cm[0] = lu.x; cm[1] = lu.y; cm[2] = add; cm[3] = qsum;
   }
 }
 
+// ------------------------------------------------------------------------------------------------ retile (rows in the caller's shape)
+// row-major rows (StagedRows) -> tile records.  One thread per (row, chunk), one more per row for its corrections.
+// The rows handed over are the global rows [row0, n_rows) (row0 = 0: a creation; row0 = the old size: an append, DESIGN.md
+// "Appending rows"): thread (i, j) owns global row row0 + i, lanes below row0 are not touched, lanes from n_rows up to the end of the
+// last tile are written as padding.  The two row shapes differ only in how a 16-byte chunk is packed: a packed 1-bit row is copied,
+// a multi-bit row (one byte per dimension) is packed into store_bits-wide fields, and a code that is not below 2^index_bits raises
+// *bad (the index is refused).
+__global__ __launch_bounds__(256) void bbq_retile_kernel(TileDest out, StagedRows in, int64_t n_rows, int64_t n_rows_padded, int64_t row0,
+                                                        int32_t index_bits, uint32_t *__restrict__ bad) {
+  const int w16 = out.geom.w16;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t row = row0 + gid / (w16 + 1);
+  const int j = (int)(gid % (w16 + 1));
+  if (row >= n_rows_padded) return;
+  const bool valid = row < n_rows;
+  if (j == w16) {
+    f64x2 lu = {0.0, 0.0};
+    double add = 0.0, x1 = 0.0;
+    if (valid) {
+      const double *c = in.corr + (row - row0) * 4;
+      lu.x = c[0]; lu.y = c[1]; add = c[2]; x1 = c[3];
+    }
+    write_corrections(out, row, lu, add, x1);
+    return;
+  }
+  uint32_t w[4] = {0, 0, 0, 0};
+  if (valid && out.geom.store_bits == 1) {
+    const int pb = pb_of(out.geom);
+    const uint8_t *src = in.codes + (row - row0) * (int64_t)pb;
+    for (int b = 0; b < 16; ++b) {
+      const int byte = j * 16 + b;
+      if (byte < pb) w[b >> 2] |= (uint32_t)src[byte] << (8 * (b & 3));
+    }
+  } else if (valid) {
+    const int dim = out.geom.dim, store_bits = out.geom.store_bits, per_dword = 32 / store_bits;
+    const uint8_t *src = in.codes + (row - row0) * (int64_t)dim;
+    const uint32_t limit = 1u << index_bits, field = (1u << store_bits) - 1u;  // values of an indexBits-bit quantizer are < 2^indexBits (include/bbq.h)
+    for (int t = 0; t < 4; ++t)
+      for (int f = 0; f < per_dword; ++f) {
+        const int d = (j * 4 + t) * per_dword + f;
+        if (d < dim) {
+          const uint32_t v = src[d];
+          if (v >= limit) atomicOr(bad, 1u);
+          w[t] |= (v & field) << (f * store_bits);
+        }
+      }
+  }
+  const u32x4 v = {w[0], w[1], w[2], w[3]};
+  reinterpret_cast<u32x4 *>(out.tiles + (row / kTileRows) * (int64_t)out.geom.tile_stride)[tile_chunk_index(j, (int)(row % kTileRows))] = v;
+}
+
+// does quantizedComponentSum equal the row's implied sum everywhere (then it need not be stored)?  The implied sum of a packed 1-bit row
+// is its popcount, of a multi-bit row (one byte per dimension) the sum of its codes: over the row_bytes bytes of the row either way
+__global__ __launch_bounds__(256) void bbq_check_x1_kernel(StagedRows in, int64_t n_rows, int32_t row_bytes, int32_t popcount,
+                                                          uint32_t *__restrict__ mismatch) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_rows) return;
+  const uint8_t *src = in.codes + row * (int64_t)row_bytes;
+  uint32_t sum = 0;
+  for (int b = 0; b < row_bytes; ++b) sum += popcount ? (uint32_t)__popc((uint32_t)src[b]) : (uint32_t)src[b];
+  if (!(in.corr[row * 4 + 3] == (double)sum)) atomicOr(mismatch, 1u);
+}
+
+// compact layout: {min, max} of additionalCorrection over the valid rows of each tile, as f32 (one wave per tile; the f32
+// rounding is inside the bound's allowance for the additive term).  A NaN anywhere makes both ends NaN: no bound, exact path.
+// Runs over the tiles [tile0, ceil(n_rows / 64)): an append starts at the tile its first new row lands in.
+__global__ __launch_bounds__(256) void bbq_tile_add_range_kernel(const double *__restrict__ exact, int64_t n_rows, float *__restrict__ add_range,
+                                                                 int64_t tile0) {
+  const int lane = threadIdx.x & 63;
+  const int64_t tile = tile0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
+  if (tile >= n_tiles) return;
+  const int64_t row = tile * kTileRows + lane;
+  const bool valid = row < n_rows;
+  const double v = valid ? exact[row * 4 + 2] : 0.0;
+  bool nan = valid && (v != v);
+  double lo = valid ? v : __longlong_as_double(0x7ff0000000000000ll), hi = valid ? v : __longlong_as_double(0xfff0000000000000ll);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    lo = fmin(lo, __shfl_xor(lo, d, 64));
+    hi = fmax(hi, __shfl_xor(hi, d, 64));
+  }
+  nan = __any(nan);
+  if (lane == 0) {
+    add_range[tile * 2] = nan ? __uint_as_float(0x7fc00000u) : (float)lo;
+    add_range[tile * 2 + 1] = nan ? __uint_as_float(0x7fc00000u) : (float)hi;
+  }
+}
+
+// is every code of these multi-bit rows below 2^index_bits?  What bbq_retile_kernel reports while it writes, asked BEFORE
+// anything is written: an append that fails leaves the index as it was
+__global__ __launch_bounds__(256) void bbq_check_code_range_kernel(const uint8_t *__restrict__ codes, int64_t count, uint32_t limit,
+                                                                   uint32_t *__restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count && codes[i] >= limit) atomicOr(bad, 1u);
+}
+
 // ------------------------------------------------------------------------------------------------ untile (codes for the host)
-__global__ __launch_bounds__(256) void bbq_untile_kernel(const uint8_t *__restrict__ tiles, int64_t n, int32_t pb, int32_t w16,
-                                                        int32_t tile_stride, uint8_t *__restrict__ codes_rm, int64_t row0) {
+__global__ __launch_bounds__(256) void bbq_untile_kernel(TileDest src, int64_t n, uint8_t *__restrict__ codes_rm, int64_t row0) {
+  const int w16 = src.geom.w16, pb = pb_of(src.geom);
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t i = gid / w16;  // row row0 + i of the storage -> row i of codes_rm
   const int j = (int)(gid % w16);
   if (i >= n) return;
   const int64_t row = row0 + i;
-  const uint8_t *tp = tiles + (row / kTileRows) * (int64_t)tile_stride;
-  const u32x4b c = reinterpret_cast<const u32x4b *>(tp)[j * kTileRows + (int)(row % kTileRows)];
+  const uint8_t *tp = src.tiles + (row / kTileRows) * (int64_t)src.geom.tile_stride;
+  const u32x4 c = reinterpret_cast<const u32x4 *>(tp)[tile_chunk_index(j, (int)(row % kTileRows))];
   const uint32_t w[4] = {c.x, c.y, c.z, c.w};
   uint8_t *dst = codes_rm + i * (int64_t)pb;
   for (int b = 0; b < 16; ++b) {
@@ -460,29 +558,53 @@ hipError_t launch_build_centroid(const float *vT4, int64_t n, int32_t dim, int64
   hipLaunchKernelGGL(bbq_centroid_kernel, dim3((unsigned)dim4), dim3(64), 0, s, reinterpret_cast<const f32x4 *>(vT4), n, dim, npad, centroid);
   return hipGetLastError();
 }
-hipError_t launch_build_quantize1(const float *vT4, int64_t n, int32_t dim, int64_t npad, const float *centroid, int32_t sim,
-                                  double lambda, int32_t iters, uint8_t *tiles, double *exact, double *corr_rm, int32_t w16,
-                                  int32_t tile_stride, int32_t layout, hipStream_t s, int64_t row0) {
-  const int dim4 = (dim + 3) / 4;
-  BuildOut o{tiles, exact, corr_rm, nullptr, w16, tile_stride, layout};
+hipError_t launch_build_quantize1(const float *vT4, int64_t n, int64_t npad, const float *centroid, int32_t sim, double lambda, int32_t iters,
+                                  const TileDest &out, double *corr_rm, hipStream_t s, int64_t row0) {
+  const int dim = out.geom.dim, dim4 = (dim + 3) / 4;
   const int64_t n_out = (row0 + n + kTileRows - 1) / kTileRows * kTileRows - row0;  // row0 = 0: npad
   hipLaunchKernelGGL(bbq_quantize1_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), (size_t)dim4 * 16, s,
-                     reinterpret_cast<const f32x4 *>(vT4), n, dim, dim4, npad, centroid, sim, lambda, iters, 1, o, row0, n_out);
+                     reinterpret_cast<const f32x4 *>(vT4), n, dim, dim4, npad, centroid, sim, lambda, iters, 1, out, corr_rm, (uint8_t *)nullptr, row0, n_out);
   return hipGetLastError();
 }
 hipError_t launch_build_quantize_bits(const float *vT4, int64_t n, int32_t dim, int64_t npad, const float *centroid, int32_t sim,
                                       double lambda, int32_t iters, int32_t bits, uint8_t *codes_rm, double *corr_rm, hipStream_t s) {
   const int dim4 = (dim + 3) / 4;
-  BuildOut o{nullptr, nullptr, corr_rm, codes_rm, 0, 0, 0};
   hipLaunchKernelGGL(bbq_quantize1_kernel, dim3((unsigned)(npad / 256 + (npad % 256 ? 1 : 0))), dim3(256), (size_t)dim4 * 16, s,
-                     reinterpret_cast<const f32x4 *>(vT4), n, dim, dim4, npad, centroid, sim, lambda, iters, bits, o, (int64_t)0, npad);
+                     reinterpret_cast<const f32x4 *>(vT4), n, dim, dim4, npad, centroid, sim, lambda, iters, bits, TileDest{}, corr_rm, codes_rm, (int64_t)0, npad);
   return hipGetLastError();
 }
-hipError_t launch_build_untile(const uint8_t *tiles, int64_t n, int32_t pb, int32_t w16, int32_t tile_stride, uint8_t *codes_rm,
-                               hipStream_t s, int64_t row0) {
-  const int64_t threads = n * w16;
+hipError_t launch_build_untile(const TileDest &src, int64_t n, uint8_t *codes_rm, hipStream_t s, int64_t row0) {
+  const int64_t threads = n * src.geom.w16;
   if (threads <= 0) return hipSuccess;
-  hipLaunchKernelGGL(bbq_untile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, tiles, n, pb, w16, tile_stride, codes_rm, row0);
+  hipLaunchKernelGGL(bbq_untile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, src, n, codes_rm, row0);
+  return hipGetLastError();
+}
+
+hipError_t launch_retile(const TileDest &out, const StagedRows &in, int64_t n_rows, int64_t row0, int32_t index_bits, uint32_t *bad, hipStream_t s) {
+  const int64_t n_pad = (n_rows + kTileRows - 1) / kTileRows * kTileRows;
+  const int64_t threads = (n_pad - row0) * (out.geom.w16 + 1);
+  if (threads <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_retile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, out, in, n_rows, n_pad, row0, index_bits, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_check_x1(const StagedRows &in, int64_t n_rows, const TileGeom &g, uint32_t *mismatch, hipStream_t s) {
+  if (n_rows == 0) return hipSuccess;
+  const bool packed = g.store_bits == 1;
+  hipLaunchKernelGGL(bbq_check_x1_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, in, n_rows, packed ? pb_of(g) : g.dim, packed ? 1 : 0, mismatch);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0) {
+  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows - tile0;
+  if (n_tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_tile_add_range_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, exact, n_rows, add_range, tile0);
+  return hipGetLastError();
+}
+
+hipError_t launch_check_code_range(const uint8_t *codes, int64_t count, int32_t index_bits, uint32_t *bad, hipStream_t s) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_check_code_range_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, codes, count, 1u << index_bits, bad);
   return hipGetLastError();
 }
 

@@ -235,7 +235,7 @@ Plan build_filtered_plan(const bbq_index *ix, const bbq_filter &f, int64_t k, in
 
 // ------------------------------------------------------------------------------------------------ slots
 
-static int64_t qbuf_bytes_per_query(const bbq_index *ix) { return qbuf_bytes_per_query_w(ix->w16); }
+static int64_t qbuf_bytes_per_query(const bbq_index *ix) { return qbuf_bytes_per_query_w(ix->geom.w16); }
 
 int ensure_slot(const SearchCall &c, Slot &s, int nq, bool own_lists) {
   const bbq_index *ix = c.ix;
@@ -362,11 +362,11 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
   const int64_t qb = query_data_bytes(ix, c.planes);
   QueryParams *hq = reinterpret_cast<QueryParams *>(s.h_qbuf + (size_t)nq * qb);
   for (int i = 0; i < nq; ++i)
-    fill_query(ix, s.h_qbuf + (size_t)i * qb, hq + i, c.qquant + (size_t)(q_first + i) * ix->dim, c.qcorr + (size_t)(q_first + i) * 4,
+    fill_query(ix, s.h_qbuf + (size_t)i * qb, hq + i, c.qquant + (size_t)(q_first + i) * ix->geom.dim, c.qcorr + (size_t)(q_first + i) * 4,
                c.planes, c.one_bit, c.sim);
   size_t bytes = (size_t)nq * qb + (size_t)nq * sizeof(QueryParams);
   // the matrix-core shared sweep appends its candidates to the lists, so it runs only where they are this slot's own
-  bool use_mfma = !ext && !c.filter && c.share == 32 && c.maxq <= 127 && ix->store_bits == 1;
+  bool use_mfma = !ext && !c.filter && c.share == 32 && c.maxq <= 127 && ix->geom.store_bits == 1;
   for (int i = 0; i < nq && use_mfma; ++i) use_mfma = mfma_query_ok(hq[i]);
   const MfmaStage ms = use_mfma ? stage_queries_mfma(c, s.h_qbuf, hq, q_first, nq, bytes) : MfmaStage{};
   if (use_mfma) bytes = ms.bytes;
@@ -433,8 +433,8 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
       const int share = on_mfma ? mfma_queries_per_tile_load(a, nq, ms.fp) : shared ? c.share : 1;
       // the matrix-core sweep reads the codes and the EXACT corrections (compact layout: 24 of the side array's 32 B per row instead of
       // the tile's 4-byte word), once per 32 queries
-      const int64_t row_bytes = !on_mfma ? (int64_t)ix->bytes_per_row
-                                : sto.view.layout == kLayoutCompact ? (int64_t)sto.view.w16 * 16 + 24 : (int64_t)sto.view.tile_stride / kTileRows;
+      const int64_t row_bytes = !on_mfma ? (int64_t)bytes_per_row_of(ix->geom)
+                                : sto.view.geom.layout == kLayoutCompact ? (int64_t)sto.view.geom.w16 * 16 + 24 : (int64_t)sto.view.geom.tile_stride / kTileRows;
       fl.timed_bytes = g.rows * ((nq + share - 1) / share) * row_bytes;
     }
     FinalizeArgs f = segment_finalize_args(slot_finalize_args(s, d_lists, d_list_counts, list_cap, append_here, c.k_dev), s, g, a);
@@ -730,11 +730,11 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
   }
   if (feed) {  // the values are still being produced: the kernel variant follows from the bit width they are quantized to
     const int pq = query_bits <= 1 ? 1 : query_bits <= 2 ? 2 : query_bits <= 4 ? 4 : 8;
-    c.planes = ix->store_bits == 1 ? pq : ix->store_bits == 8 ? 8 : (query_bits <= 4 ? 4 : 8);
+    c.planes = ix->geom.store_bits == 1 ? pq : ix->geom.store_bits == 8 ? 8 : (query_bits <= 4 ? 4 : 8);
     c.maxq = (1 << query_bits) - 1;
   } else {
-    c.planes = planes_of_call(ix, qquant, (int64_t)n_queries * ix->dim, query_bits == 1);
-    c.maxq = c.planes <= 4 ? 15 : max_value(qquant, (int64_t)n_queries * ix->dim);
+    c.planes = planes_of_call(ix, qquant, (int64_t)n_queries * ix->geom.dim, query_bits == 1);
+    c.maxq = c.planes <= 4 ? 15 : max_value(qquant, (int64_t)n_queries * ix->geom.dim);
   }
   const int64_t keff = std::min<int64_t>(k, n_eff);
   if (keff > kMaxFastK || ix->opt_force_dense) {
@@ -822,7 +822,7 @@ int bbq_search_raw_batch(bbq_index *ix, int32_t n_queries, const float *queries,
   if (k < 0) return fail(BBQ_ERR_NEGATIVE_K, "k值不能为负数");
   if (query_bits < 1 || query_bits > 8) return fail(BBQ_ERR_INVALID_ARG, "queryBits必须在1-8之间");
   if (n_queries == 0) return BBQ_OK;
-  const int dim = ix->dim;
+  const int dim = ix->geom.dim;
   std::vector<uint8_t> own_q;
   std::vector<double> own_c;
   uint8_t *qq = qquant_out;

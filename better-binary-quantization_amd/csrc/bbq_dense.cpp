@@ -9,11 +9,11 @@ namespace {
 // query qi of the call into the device's auxiliary query buffer, on the auxiliary stream; returns when it is there
 int stage_aux_query(const SearchCall &c, int64_t qi) {
   bbq_index *ix = c.ix;
-  int rc = ensure_aux_qbuf(ix->ctx, qbuf_bytes_per_query_w(ix->w16));
+  int rc = ensure_aux_qbuf(ix->ctx, qbuf_bytes_per_query_w(ix->geom.w16));
   if (rc != BBQ_OK) return rc;
   const int64_t qb = query_data_bytes(ix, c.planes);
   std::vector<uint8_t> hb((size_t)qb + sizeof(QueryParams));
-  fill_query(ix, hb.data(), reinterpret_cast<QueryParams *>(hb.data() + qb), c.qquant + (size_t)qi * ix->dim, c.qcorr + (size_t)qi * 4,
+  fill_query(ix, hb.data(), reinterpret_cast<QueryParams *>(hb.data() + qb), c.qquant + (size_t)qi * ix->geom.dim, c.qcorr + (size_t)qi * 4,
              c.planes, c.one_bit, c.sim);
   hipStream_t st = ix->ctx->aux_stream;
   HIPCHK(hipMemcpyAsync(ix->ctx->d_aux_qbuf, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
@@ -86,7 +86,7 @@ int dense_scores_host(bbq_index *ix, const uint8_t *qquant, const double *qcorr,
   std::lock_guard<std::mutex> lk(ix->ctx->mu);
   HIPCHK(hipSetDevice(ix->device));
   if (ix->n_rows == 0) return BBQ_OK;
-  const SearchCall c(ix, qquant, qcorr, planes_of_call(ix, qquant, ix->dim, query_bits == 1), query_bits, sim, 0);
+  const SearchCall c(ix, qquant, qcorr, planes_of_call(ix, qquant, ix->geom.dim, query_bits == 1), query_bits, sim, 0);
   ix->stats.dense_fallbacks += 1;
   return dense_scores_one(c, 0, out);
 }
@@ -106,7 +106,7 @@ int bbq_score_rows(bbq_index *ix, const uint8_t *qquant, const double *qcorr, in
   if (ix->multi) return multi_score_rows(ix, qquant, qcorr, query_bits, sim, row_begin, row_count, out_qcdist, out_score64, out_score32);
   std::lock_guard<std::mutex> lk(ix->ctx->mu);
   HIPCHK(hipSetDevice(ix->device));
-  const SearchCall c(ix, qquant, qcorr, planes_of_call(ix, qquant, ix->dim, query_bits == 1), query_bits, sim, 0);
+  const SearchCall c(ix, qquant, qcorr, planes_of_call(ix, qquant, ix->geom.dim, query_bits == 1), query_bits, sim, 0);
   rc = stage_aux_query(c, 0);
   if (rc != BBQ_OK) return rc;
   hipStream_t st = ix->ctx->aux_stream;

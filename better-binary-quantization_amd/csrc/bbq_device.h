@@ -1,6 +1,7 @@
 // bbq_device.h - structs shared by the HIP kernels and the host orchestration (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "bbq_entry.h"
 
@@ -49,21 +50,62 @@ __host__ __device__ inline int row_bytes_of(int dim, int store_bits) { return (d
 __host__ __device__ constexpr int query_units_per_chunk(int qb, int store_bits) {
   return store_bits == 1 ? qb : store_bits == 2 ? (qb > 4 ? 4 : 2) : store_bits == 4 ? (qb > 4 ? 2 : 1) : 1;
 }
+// ---- the tile record: the ONE definition of its bytes.  Every kernel that reads or writes a record, bbq_index_export on the host and
+// the file (<prefix>.veb holds the records as they are) take their offsets from here.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // one 16-byte code chunk
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));    // {lowerInterval, upperInterval}
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+struct TileGeom {
+  int32_t w16;          // 16-byte chunks per row = ceil(stored row bytes / 16)
+  int32_t tile_stride;  // bytes per tile record (tile_stride_of)
+  int32_t has_x1;       // 0: quantizedComponentSum == popcount / code sum of the row, recomputed on the fly
+  int32_t dim;
+  int32_t layout;
+  int32_t store_bits;   // 1: packed 1-bit rows; 2 / 4 / 8: multi-bit fields (indexBits 2 / 3-4 / 5-8)
+};
+constexpr int kChunkBytes = 16;
+// code chunk j of row r inside a record: its index among the record's chunks, and its byte offset
+__host__ __device__ constexpr int tile_chunk_index(int j, int r) { return j * kTileRows + r; }
+__host__ __device__ constexpr size_t tile_chunk_offset(int j, int r) { return (size_t)tile_chunk_index(j, r) * kChunkBytes; }
+// ... and of the corrections block, behind the w16 chunk blocks
+__host__ __device__ constexpr size_t tile_corr_offset(int w16) { return (size_t)w16 * (kTileRows * kChunkBytes); }
+// inline corrections block: [64] {lower, upper} at 0, [64] additionalCorrection, [64] quantizedComponentSum (has_x1 only)
+constexpr int kCorrAddOffset = kTileRows * 16;
+constexpr int kCorrSumOffset = kCorrAddOffset + kTileRows * 8;
+constexpr int kCorrSumBytes = kTileRows * 8;
+// compact corrections block: [64] compact words
+constexpr int kCorrCompactBytes = kTileRows * 4;
+// the compact word: the upper 16 bits (bf16 by truncation) of f32(lower) in its low half, of f32(upper) in its high half
+__host__ __device__ inline uint32_t bf16_trunc_bits(double v) { return __builtin_bit_cast(uint32_t, (float)v) >> 16; }
+__host__ __device__ inline uint32_t compact_word(double lower, double upper) { return bf16_trunc_bits(lower) | (bf16_trunc_bits(upper) << 16); }
+__host__ __device__ inline float compact_lower(uint32_t cw) { return __builtin_bit_cast(float, cw << 16); }
+__host__ __device__ inline float compact_upper(uint32_t cw) { return __builtin_bit_cast(float, cw & 0xffff0000u); }
 // bytes of one tile record
 __host__ __device__ inline int tile_stride_of(int w16, int layout, int has_x1) {
-  return w16 * 1024 + (layout == kLayoutCompact ? 4 * kTileRows : 1536 + (has_x1 ? 512 : 0));
+  return (int)tile_corr_offset(w16) + (layout == kLayoutCompact ? kCorrCompactBytes : kCorrSumOffset + (has_x1 ? kCorrSumBytes : 0));
 }
+__host__ __device__ inline int pb_of(const TileGeom &g) { return row_bytes_of(g.dim, g.store_bits); }  // stored bytes per row, before the padding
+__host__ __device__ inline int bytes_per_row_of(const TileGeom &g) { return g.tile_stride / kTileRows; }
+// where the build kernels write: the records of a storage (or a scratch tile set), the compact layout's side rows, and their geometry
+struct TileDest {
+  uint8_t *tiles;
+  double *exact;  // kLayoutCompact: [rows padded to 64][4]; null otherwise
+  TileGeom geom;
+};
+// rows staged in device memory in the caller's shape: codes [n][pb] packed bits (store_bits 1) or [n][dim] one byte per dimension,
+// corr [n][4] {lower, upper, additionalCorrection, quantizedComponentSum}
+struct StagedRows {
+  const uint8_t *codes;
+  const double *corr;
+};
+
 struct IndexView {
   const uint8_t *tiles;
   const double *exact;  // kLayoutCompact: [n_rows padded to 64][4]
   const float *add_range;  // kLayoutCompact: [tiles][2] {min, max} of additionalCorrection inside the tile
   int64_t n_rows;       // valid rows in this storage
-  int32_t w16;          // 16-byte chunks per row = ceil(ceil(dim/8)/16)
-  int32_t tile_stride;  // bytes per tile record
-  int32_t has_x1;       // 0: quantizedComponentSum == popcount(row), recomputed on the fly
-  int32_t dim;
-  int32_t layout;
-  int32_t store_bits;   // 1: packed 1-bit rows; 2 / 4 / 8: multi-bit fields (indexBits 2 / 3-4 / 5-8)
+  TileGeom geom;
   // cache residency of a launch (launch_view(), bbq_core.cpp): the chunks read with the default cache policy - they stay in the 256 MiB
   // Infinity Cache from one query's sweep to the next - the others are streamed with non-temporal loads
   int64_t resident_tiles;  // resident_share < 0: chunks whose first tile is below this
@@ -71,6 +113,9 @@ struct IndexView {
   int64_t nt_delta;        // always 0.  The streamed loads add it to their address so that the compiler sees two different addresses
                            // in the two branches: it merges loads that differ only in the cache policy into ONE plain load
 };
+// the kernels' argument loads depend on these offsets
+static_assert(offsetof(IndexView, geom) == 32 && sizeof(TileGeom) == 24 && offsetof(IndexView, resident_tiles) == 56 && sizeof(IndexView) == 80,
+              "IndexView layout");
 
 // Per-query uniforms of the score formula (src/batchDotProduct.ts:478-617)
 struct QueryParams {

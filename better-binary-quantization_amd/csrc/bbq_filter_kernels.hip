@@ -13,8 +13,8 @@ namespace bbq {
 hipError_t launch_scan_filtered(const ScanArgs &a, const uint64_t *accept, int planes, int n_queries, int n_chunks, hipStream_t s) {
   if (n_chunks <= 0 || n_queries <= 0) return hipSuccess;
   if (!accept) return hipErrorInvalidValue;
-  const bool compact = a.idx.layout == kLayoutCompact;
-  if (a.idx.store_bits > 1)
+  const bool compact = a.idx.geom.layout == kLayoutCompact;
+  if (a.idx.geom.store_bits > 1)
     return compact ? launch_scan_mb<true, 2>(a, accept, planes, n_queries, n_chunks, s) : launch_scan_mb<true, 0>(a, accept, planes, n_queries, n_chunks, s);
   return compact ? launch_scan_q<true, 2>(a, accept, planes, n_queries, n_chunks, s) : launch_scan_q<true, 0>(a, accept, planes, n_queries, n_chunks, s);
 }

@@ -171,8 +171,8 @@ struct bbq_index {
   int device = 0;
   bbq::DeviceCtx *ctx = nullptr;
   bbq::Slot *slots = nullptr;  // = ctx->slots
-  int32_t dim = 0, pb = 0, w16 = 0, tile_stride = 0, has_x1 = 0, bytes_per_row = 0, layout = 0, want_compact = 1;
-  int32_t index_bits = 1, store_bits = 1;  // pb = stored bytes per row = ceil(dim * store_bits / 8)
+  bbq::TileGeom geom{};  // of every tile record of the index: each storage's view holds a copy (set_storage_view)
+  int32_t want_compact = 1, index_bits = 1;  // geom.store_bits follows from index_bits (set_index_geometry)
   int64_t n_rows = 0, row_base = 0;
   double centroid_dp = 0;
   bool has_pilot = false;
@@ -231,7 +231,7 @@ inline bool dim_supported(int64_t dim, int store_bits) { return dim * 255 * (sto
 int require_devices(int *ndev);
 int check_device(int device);
 int open_device(int device, DeviceCtx **ctx);
-// dim, index_bits and what follows from them: store_bits, pb, w16
+// dim, index_bits and what follows from them: store_bits, w16
 void set_index_geometry(bbq_index *ix, int32_t dim, int32_t index_bits);
 // a new index on its device: the geometry, the context and its slots, the auxiliary query buffer grown to this index's queries
 int attach_index(bbq_index *ix, DeviceCtx *ctx, int device, int32_t dim, int32_t index_bits);
@@ -247,24 +247,18 @@ void destroy_unlocked(bbq_index *ix);
 inline void set_storage_view(const bbq_index *ix, Storage &st, int64_t n_rows, int64_t row_id_base) {
   st.row_id_base = row_id_base;
   st.view.n_rows = n_rows;
-  st.view.w16 = ix->w16;
-  st.view.tile_stride = ix->tile_stride;
-  st.view.has_x1 = ix->has_x1;
-  st.view.dim = ix->dim;
-  st.view.layout = ix->layout;
-  st.view.store_bits = ix->store_bits;
+  st.view.geom = ix->geom;
   st.view.tiles = st.d_tiles;
   st.view.exact = st.d_exact;
   st.view.add_range = add_range_of(st.d_exact, st.cap_tiles);
 }
 // bytes per row as the caller hands them over and gets them back: packed bits, or one byte per dimension for a multi-bit index
-inline int64_t caller_row_bytes(const bbq_index *ix) { return ix->store_bits > 1 ? ix->dim : ix->pb; }
+inline int64_t caller_row_bytes(const bbq_index *ix) { return ix->geom.store_bits > 1 ? ix->geom.dim : pb_of(ix->geom); }
 inline int64_t tiles_of(int64_t rows) { return (rows + kTileRows - 1) / kTileRows; }
 // compact corrections (4 B/row streamed + exact and add-range side arrays) need the implicit component sum; otherwise inline
 inline void decide_layout(bbq_index *ix) {
-  ix->layout = (ix->want_compact && !ix->has_x1) ? kLayoutCompact : kLayoutInline;
-  ix->tile_stride = tile_stride_of(ix->w16, ix->layout, ix->has_x1);
-  ix->bytes_per_row = ix->tile_stride / kTileRows;
+  ix->geom.layout = (ix->want_compact && !ix->geom.has_x1) ? kLayoutCompact : kLayoutInline;
+  ix->geom.tile_stride = tile_stride_of(ix->geom.w16, ix->geom.layout, ix->geom.has_x1);
 }
 
 // ---- bbq_append.cpp: the one path that writes rows into a storage.  A creation, a build and a load are appends to an empty storage;
@@ -282,6 +276,16 @@ struct Room {
   double *d_exact = nullptr;
   float *d_add_range = nullptr;
 };
+// where the build kernels write the rows that go into `r`, and the scratch tile set quantize_into's explicit-sums branch packs codes
+// into: inline records of the index's row width without a component sum (a freshly quantized row's sum is its popcount)
+inline TileDest tile_dest(const bbq_index *ix, const Room &r) { return TileDest{r.d_tiles, r.d_exact, ix->geom}; }
+inline TileDest scratch_tile_dest(const bbq_index *ix, uint8_t *tiles) {
+  TileGeom g = ix->geom;
+  g.layout = kLayoutInline;
+  g.has_x1 = 0;
+  g.tile_stride = tile_stride_of(g.w16, g.layout, g.has_x1);
+  return TileDest{tiles, nullptr, g};
+}
 // geometric: half as much again as the capacity, at least what is needed (an empty storage gets exactly what is needed); otherwise
 // exactly what is needed.  BBQ_ERR_OOM without device memory.
 int make_room(bbq_index *ix, Storage &st, int64_t need_tiles, Room &r, bool geometric = true);

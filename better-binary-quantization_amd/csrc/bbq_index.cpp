@@ -66,13 +66,12 @@ int open_device(int device, DeviceCtx **ctx) {
 }
 
 void set_index_geometry(bbq_index *ix, int32_t dim, int32_t index_bits) {
-  ix->dim = dim;
+  ix->geom.dim = dim;
   ix->index_bits = index_bits;
   // a multi-bit index of dimension 1 is the one shape the reference's BATCH scorer accepts (the unpacked byte is read as a
   // packed row, src/batchDotProduct.ts:425-433): it is stored and scored as the packed 1-bit row it is taken for
-  ix->store_bits = dim == 1 ? 1 : store_bits_of(index_bits);
-  ix->pb = row_bytes_of(dim, ix->store_bits);
-  ix->w16 = (ix->pb + 15) / 16;
+  ix->geom.store_bits = dim == 1 ? 1 : store_bits_of(index_bits);
+  ix->geom.w16 = (pb_of(ix->geom) + 15) / 16;
 }
 
 int attach_index(bbq_index *ix, DeviceCtx *ctx, int device, int32_t dim, int32_t index_bits) {
@@ -80,7 +79,7 @@ int attach_index(bbq_index *ix, DeviceCtx *ctx, int device, int32_t dim, int32_t
   ix->device = device;
   ix->ctx = ctx;
   ix->slots = ctx->slots;
-  return ensure_aux_qbuf(ctx, qbuf_bytes_per_query_w(ix->w16));
+  return ensure_aux_qbuf(ctx, qbuf_bytes_per_query_w(ix->geom.w16));
 }
 
 // The view a launch gets: the stored view + which chunks it loads cache-resident.  The indexes that have launched sweeps on the device
@@ -110,8 +109,8 @@ LaunchView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin, i
   IndexView v = sto.view;
   const int64_t all_chunks = sto.n_chunks();
   if (n_chunks < 0) n_chunks = all_chunks - chunk_begin;
-  const int64_t chunk_bytes = (int64_t)kTilesPerChunk * v.tile_stride;
-  const int64_t own = ix->main.n_chunks() * (int64_t)kTilesPerChunk * ix->main.view.tile_stride;
+  const int64_t chunk_bytes = (int64_t)kTilesPerChunk * v.geom.tile_stride;
+  const int64_t own = ix->main.n_chunks() * (int64_t)kTilesPerChunk * ix->main.view.geom.tile_stride;
   const int64_t all = std::max<int64_t>(1, cache_sharers_bytes(ix, own));
   const int64_t budget = ix->opt_resident_mb >= 0 ? ((int64_t)ix->opt_resident_mb << 20)
                                             : (int64_t)((double)kResidentAutoBytes * ((double)own / (double)all));
@@ -201,9 +200,9 @@ int bbq_index_create_shard_opts(const uint8_t *codes, const double *corr, int64_
   // each storage is an append to an empty one.  Whether the index stores explicit component sums is decided once, over pilot and main
   ix->main.row_id_base = row_base;
   if (ix->has_pilot) rc = append_host_rows(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, Sums::kDecide);
-  const int had = ix->has_x1;
+  const int had = ix->geom.has_x1;
   if (rc == BBQ_OK) rc = append_host_rows(ix.get(), ix->main, codes, corr, n_rows, Sums::kDecide);
-  if (rc == BBQ_OK && ix->has_pilot && ix->has_x1 != had) {  // main needs explicit sums but pilot was built without: rebuild the pilot
+  if (rc == BBQ_OK && ix->has_pilot && ix->geom.has_x1 != had) {  // main needs explicit sums but pilot was built without: rebuild the pilot
     ix->pilot = Storage();
     rc = append_host_rows(ix.get(), ix->pilot, pilot_codes, pilot_corr, n_pilot, Sums::kDecide);
   }
@@ -229,8 +228,8 @@ void bbq_index_destroy(bbq_index *ix) {
 }
 
 int64_t bbq_index_size(const bbq_index *ix) { return ix ? ix->n_rows : 0; }
-int32_t bbq_index_dimension(const bbq_index *ix) { return ix ? ix->dim : 0; }
-int32_t bbq_index_bytes_per_row(const bbq_index *ix) { return ix ? ix->bytes_per_row : 0; }
+int32_t bbq_index_dimension(const bbq_index *ix) { return ix ? ix->geom.dim : 0; }
+int32_t bbq_index_bytes_per_row(const bbq_index *ix) { return ix ? bytes_per_row_of(ix->geom) : 0; }
 int32_t bbq_index_bits(const bbq_index *ix) { return ix ? ix->index_bits : 0; }
 
 int bbq_get_stats(bbq_index *ix, bbq_stats *out) {

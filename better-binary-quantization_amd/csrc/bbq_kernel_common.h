@@ -17,8 +17,6 @@ namespace bbq {
 #define BBQ_STREAM_LOAD(p) __builtin_nontemporal_load(p)
 #endif
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 // a tile's bytes: default cache policy for the resident part of the index (IndexView::resident_tiles), streamed otherwise.
 // `resident` must be wave-uniform (chunk_is_resident: decided per workgroup from blockIdx): a scalar branch, never both loads
 template <class T> __device__ __forceinline__ const T *stream_ptr(const T *p, int64_t nt_delta) {
@@ -30,7 +28,6 @@ template <class T> __device__ __forceinline__ const T *stream_ptr(const T *p, in
 __device__ __forceinline__ bool chunk_is_resident(int64_t chunk, const IndexView &v) {  // chunk comes from blockIdx: scalar
   return v.resident_share >= 0 ? (chunk & 63) < v.resident_share : chunk * kTilesPerChunk < v.resident_tiles;
 }
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 // ALL loads of a wave's tile in ONE two-way branch (W > 0): the W code chunks of the lane's row and its corrections - CORR 0: none,
 // 1: the compact word, 2: the inline f64 corrections (lower, upper | additional | component sum if stored).  Loads that are
@@ -39,15 +36,15 @@ template <int W, int CORR>
 __device__ __forceinline__ void load_tile(const uint8_t *__restrict__ tp, int lane, bool has_x1, bool resident, int64_t nt_delta,
                                           u32x4 (&c)[W], uint32_t &cw, f64x2 &lu, double &xadd, double &x1) {
   const u32x4 *__restrict__ cp = reinterpret_cast<const u32x4 *>(tp) + lane;
-  const uint8_t *__restrict__ cr = tp + (size_t)W * (kTileRows * 16);
+  const uint8_t *__restrict__ cr = tp + tile_corr_offset(W);
   if (resident) {  // scalar branch
 #pragma unroll
     for (int j = 0; j < W; ++j) c[j] = cp[j * kTileRows];
     if constexpr (CORR == 1) cw = *(reinterpret_cast<const uint32_t *>(cr) + lane);
     if constexpr (CORR == 2) {
       lu = *(reinterpret_cast<const f64x2 *>(cr) + lane);
-      xadd = *(reinterpret_cast<const double *>(cr + 1024) + lane);
-      if (has_x1) x1 = *(reinterpret_cast<const double *>(cr + 1536) + lane);
+      xadd = *(reinterpret_cast<const double *>(cr + kCorrAddOffset) + lane);
+      if (has_x1) x1 = *(reinterpret_cast<const double *>(cr + kCorrSumOffset) + lane);
     }
   } else {
     BBQ_BRANCH_FENCE();
@@ -58,8 +55,8 @@ __device__ __forceinline__ void load_tile(const uint8_t *__restrict__ tp, int la
     if constexpr (CORR == 1) cw = BBQ_STREAM_LOAD(reinterpret_cast<const uint32_t *>(crs) + lane);
     if constexpr (CORR == 2) {
       lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(crs) + lane);
-      xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(crs + 1024) + lane);
-      if (has_x1) x1 = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(crs + 1536) + lane);
+      xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(crs + kCorrAddOffset) + lane);
+      if (has_x1) x1 = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(crs + kCorrSumOffset) + lane);
     }
     BBQ_BRANCH_FENCE();
   }
@@ -197,8 +194,8 @@ __device__ __forceinline__ float tile_add_bound(const IndexView &v, int64_t tile
 // compact layout: the row's bf16 {lower, upper} word and the tile's additive bound give an upper bound of its score.  NaN (no bound)
 // passes; otherwise the row can only matter if even its upper bound beats the threshold
 __device__ __forceinline__ bool compact_bound_passes(bool valid, uint32_t qc, uint32_t cw, float aadd, double x1, const QueryParams &p, uint32_t theta) {
-  const double al = (double)__uint_as_float(cw << 16);
-  const double au = (double)__uint_as_float(cw & 0xffff0000u);
+  const double al = (double)compact_lower(cw);
+  const double au = (double)compact_upper(cw);
   const double ub = score_upper_bound((double)qc, al, au, (double)aadd, x1, p);
   const float ub32 = (float)ub;
   return valid && ((ub32 != ub32) || key_of_bits(__float_as_uint(ub32)) > theta);

@@ -1,21 +1,21 @@
 // bbq_kernels.hip - hand-written gfx950 (CDNA4) kernels of the binary-quantized scan + top-k path.
 //
-//   bbq_scan_kernel      (bbq_scan_body.h; instantiated here without a filter) the hot kernel: streams tile records from HBM with coalesced 16-byte loads
-//                        (lane r owns row r of a 64-row tile: no cross-lane reduction at all), ANDs them
-//                        with the query bit-planes staged once per workgroup in LDS, accumulates popcounts
-//                        per plane, evaluates the reference's float64 score formula in the reference's
-//                        operation order, rounds to f32 and either stores every score (DENSE) or appends
-//                        the rows above the per-query threshold to the chunk's candidate slots.
-//                        Replaces createDirectPackedBuffer + computeBatchFourBitDotProductDirectPacked /
-//                        computeBatchDotProductDirectPacked + computeBatch{FourBit,OneBit}SimilarityScores
-//                        (reference src/batchDotProduct.ts:22-49,420-436,478-617,
-//                        src/utils/computeBatchFourBitDotProductDirectPacked.ts:10-53) and the f32 store of
-//                        src/binaryQuantizationFormat.ts:353,378.
-//   bbq_finalize_kernel  per query: compacts the candidate slots of one launch into the row-ordered
-//                        candidate list, and radix-selects the k-th largest key seen so far = the threshold
-//                        of the next segment (a lower bound of the reference heap's minimum at that point,
-//                        src/binaryQuantizationFormat.ts:387-400).
-//   bbq_retile_kernel    index build: row-major packed rows + corrections -> tile records.
+//   bbq_scan_kernel         (bbq_scan_body.h; instantiated here without a filter, in bbq_filter_kernels.hip with one) the hot kernel: streams
+//                           tile records from HBM with coalesced 16-byte loads (lane r owns row r of a 64-row tile: no cross-lane
+//                           reduction at all), ANDs them with the query bit-planes staged once per workgroup in LDS, accumulates
+//                           popcounts per plane, evaluates the reference's float64 score formula in the reference's operation order,
+//                           rounds to f32 and either stores every score (DENSE) or appends the rows above the per-query threshold to
+//                           the chunk's candidate slots.  Replaces createDirectPackedBuffer +
+//                           computeBatchFourBitDotProductDirectPacked / computeBatchDotProductDirectPacked +
+//                           computeBatch{FourBit,OneBit}SimilarityScores (reference src/batchDotProduct.ts:22-49,420-436,478-617,
+//                           src/utils/computeBatchFourBitDotProductDirectPacked.ts:10-53) and the f32 store of
+//                           src/binaryQuantizationFormat.ts:353,378.
+//   bbq_scan_shared_kernel  the same sweep for NB queries per workgroup (every loaded row reused)
+//   bbq_finalize_kernel     per query: compacts the candidate slots of one launch into the row-ordered candidate list, and
+//                           radix-selects the k-th largest key seen so far = the threshold of the next segment (a lower bound of the
+//                           reference heap's minimum at that point, src/binaryQuantizationFormat.ts:387-400).
+//   bbq_pack_*_kernel       shard transport: per-query lists -> one packed buffer + offsets
+// and the launch wrappers of these (bbq_launch.h).  The kernels that WRITE tile records live in bbq_build_kernels.hip.
 //
 // HBM-bound integer/byte work: no MFMA.  Compiled with -ffp-contract=off; the pragma below repeats it.
 #include <hip/hip_runtime.h>
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_shared_kernel(const ScanA
   uint32_t nan_mask = 0;
 
   if (tile < n_tiles) {  // wave-uniform
-    const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.tile_stride;
+    const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
     const int64_t row = tile * kTileRows + lane;
     const bool valid = row < a.idx.n_rows;
     u32x4 c[W];
@@ -73,13 +73,13 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_shared_kernel(const ScanA
     double xadd = 0.0, x1 = 0.0;
     uint32_t cw = 0;
     float aadd = 0.0f;
-    load_tile<W, COMPACT ? 1 : 2>(tp, lane, a.idx.has_x1 != 0, chunk_is_resident(chunk, a.idx), a.idx.nt_delta, c, cw, lu, xadd, x1);
+    load_tile<W, COMPACT ? 1 : 2>(tp, lane, a.idx.geom.has_x1 != 0, chunk_is_resident(chunk, a.idx), a.idx.nt_delta, c, cw, lu, xadd, x1);
     bool have_exact = !COMPACT;
     if constexpr (COMPACT) aadd = tile_add_bound(a.idx, tile, s_qp[0].sim);  // the queries of one call share the similarity function
     uint32_t ones = 0;
 #pragma unroll
     for (int j = 0; j < W; ++j) ones += popc4(c[j]);
-    if (!a.idx.has_x1) x1 = (double)ones;
+    if (!a.idx.geom.has_x1) x1 = (double)ones;
 
 #pragma unroll 1
     for (int b = 0; b < nb; ++b) {
@@ -411,164 +411,6 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_finalize_kernel(const Fi
 }
 
 // ---------------------------------------------------------------------------------------------------
-// index build: row-major (codes [n][pb], corr [n][4]) -> tile records.  One thread per (row, chunk).
-// The rows handed over are the global rows [row0, n_rows) (row0 = 0: a creation; row0 = the old size: an append, DESIGN.md
-// "Appending rows"): thread (i, j) owns global row row0 + i, lanes below row0 are not touched, lanes from n_rows up to the end of the
-// last tile are written as padding.
-
-__device__ __forceinline__ uint32_t bf16_trunc_bits(double v) { return __float_as_uint((float)v) >> 16; }
-
-__global__ __launch_bounds__(256) void bbq_retile_kernel(const uint8_t *__restrict__ codes, const double *__restrict__ corr,
-                                                        int64_t n_rows, int32_t pb, uint8_t *__restrict__ tiles, int32_t w16,
-                                                        int32_t tile_stride, int32_t has_x1, int64_t n_rows_padded, int32_t layout,
-                                                        double *__restrict__ exact, int64_t row0) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t row = row0 + gid / (w16 + 1);
-  const int j = (int)(gid % (w16 + 1));
-  if (row >= n_rows_padded) return;
-  const int64_t tile = row / kTileRows;
-  const int r = (int)(row % kTileRows);
-  uint8_t *tp = tiles + tile * (int64_t)tile_stride;
-  if (j < w16) {
-    u32x4 v = {0, 0, 0, 0};
-    if (row < n_rows) {
-      uint32_t w[4] = {0, 0, 0, 0};
-      const uint8_t *src = codes + (row - row0) * (int64_t)pb;
-      for (int b = 0; b < 16; ++b) {
-        const int byte = j * 16 + b;
-        if (byte < pb) w[b >> 2] |= (uint32_t)src[byte] << (8 * (b & 3));
-      }
-      v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-    }
-    reinterpret_cast<u32x4 *>(tp)[j * kTileRows + r] = v;
-  } else {
-    uint8_t *cr = tp + (size_t)w16 * (kTileRows * 16);
-    f64x2 lu = {0.0, 0.0};
-    double add = 0.0, x1 = 0.0;
-    if (row < n_rows) {
-      const double *c = corr + (row - row0) * 4;
-      lu.x = c[0]; lu.y = c[1]; add = c[2]; x1 = c[3];
-    }
-    if (layout == kLayoutCompact) {
-      reinterpret_cast<uint32_t *>(cr)[r] = bf16_trunc_bits(lu.x) | (bf16_trunc_bits(lu.y) << 16);  // the additive term: bbq_tile_add_range_kernel
-      double *e = exact + row * 4;
-      e[0] = lu.x; e[1] = lu.y; e[2] = add; e[3] = 0.0;
-    } else {
-      reinterpret_cast<f64x2 *>(cr)[r] = lu;
-      reinterpret_cast<double *>(cr + 1024)[r] = add;
-      if (has_x1) reinterpret_cast<double *>(cr + 1536)[r] = x1;
-    }
-  }
-}
-
-// multi-bit index: unpacked rows (one byte per dimension, [n][dim]) -> store_bits-wide fields in tile records; the corrections
-// block is written exactly as above.  A code that is not below 2^index_bits raises *bad (the index is refused).
-__global__ __launch_bounds__(256) void bbq_retile_multibit_kernel(const uint8_t *__restrict__ codes, const double *__restrict__ corr,
-                                                                 int64_t n_rows, int32_t dim, int32_t store_bits, int32_t index_bits, uint8_t *__restrict__ tiles,
-                                                                 int32_t w16, int32_t tile_stride, int32_t has_x1, int64_t n_rows_padded,
-                                                                 int32_t layout, double *__restrict__ exact, uint32_t *__restrict__ bad, int64_t row0) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t row = row0 + gid / (w16 + 1);
-  const int j = (int)(gid % (w16 + 1));
-  if (row >= n_rows_padded) return;
-  const int64_t tile = row / kTileRows;
-  const int r = (int)(row % kTileRows);
-  uint8_t *tp = tiles + tile * (int64_t)tile_stride;
-  if (j < w16) {
-    uint32_t w[4] = {0, 0, 0, 0};
-    if (row < n_rows) {
-      const int per_dword = 32 / store_bits;
-      const uint8_t *src = codes + (row - row0) * (int64_t)dim;
-      const uint32_t limit = 1u << index_bits, field = (1u << store_bits) - 1u;  // values of an indexBits-bit quantizer are < 2^indexBits (include/bbq.h)
-      for (int t = 0; t < 4; ++t)
-        for (int f = 0; f < per_dword; ++f) {
-          const int d = (j * 4 + t) * per_dword + f;
-          if (d < dim) {
-            const uint32_t v = src[d];
-            if (v >= limit) atomicOr(bad, 1u);
-            w[t] |= (v & field) << (f * store_bits);
-          }
-        }
-    }
-    u32x4 v = {w[0], w[1], w[2], w[3]};
-    reinterpret_cast<u32x4 *>(tp)[j * kTileRows + r] = v;
-  } else {
-    uint8_t *cr = tp + (size_t)w16 * (kTileRows * 16);
-    f64x2 lu = {0.0, 0.0};
-    double add = 0.0, x1 = 0.0;
-    if (row < n_rows) {
-      const double *c = corr + (row - row0) * 4;
-      lu.x = c[0]; lu.y = c[1]; add = c[2]; x1 = c[3];
-    }
-    if (layout == kLayoutCompact) {
-      reinterpret_cast<uint32_t *>(cr)[r] = bf16_trunc_bits(lu.x) | (bf16_trunc_bits(lu.y) << 16);
-      double *e = exact + row * 4;
-      e[0] = lu.x; e[1] = lu.y; e[2] = add; e[3] = 0.0;
-    } else {
-      reinterpret_cast<f64x2 *>(cr)[r] = lu;
-      reinterpret_cast<double *>(cr + 1024)[r] = add;
-      if (has_x1) reinterpret_cast<double *>(cr + 1536)[r] = x1;
-    }
-  }
-}
-
-// does quantizedComponentSum equal the sum of the row's codes everywhere? (multi-bit rows, one byte per dimension)
-__global__ __launch_bounds__(256) void bbq_check_x1_multibit_kernel(const uint8_t *__restrict__ codes, const double *__restrict__ corr,
-                                                                   int64_t n_rows, int32_t dim, uint32_t *__restrict__ mismatch) {
-  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= n_rows) return;
-  const uint8_t *src = codes + row * (int64_t)dim;
-  uint32_t sum = 0;
-  for (int d = 0; d < dim; ++d) sum += src[d];
-  if (!(corr[row * 4 + 3] == (double)sum)) atomicOr(mismatch, 1u);
-}
-
-// compact layout: {min, max} of additionalCorrection over the valid rows of each tile, as f32 (one wave per tile; the f32
-// rounding is inside the bound's allowance for the additive term).  A NaN anywhere makes both ends NaN: no bound, exact path.
-// Runs over the tiles [tile0, ceil(n_rows / 64)): an append starts at the tile its first new row lands in.
-__global__ __launch_bounds__(256) void bbq_tile_add_range_kernel(const double *__restrict__ exact, int64_t n_rows, float *__restrict__ add_range,
-                                                                 int64_t tile0) {
-  const int lane = threadIdx.x & 63;
-  const int64_t tile = tile0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
-  if (tile >= n_tiles) return;
-  const int64_t row = tile * kTileRows + lane;
-  const bool valid = row < n_rows;
-  const double v = valid ? exact[row * 4 + 2] : 0.0;
-  bool nan = valid && (v != v);
-  double lo = valid ? v : __longlong_as_double(0x7ff0000000000000ll), hi = valid ? v : __longlong_as_double(0xfff0000000000000ll);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    lo = fmin(lo, __shfl_xor(lo, d, 64));
-    hi = fmax(hi, __shfl_xor(hi, d, 64));
-  }
-  nan = __any(nan);
-  if (lane == 0) {
-    add_range[tile * 2] = nan ? __uint_as_float(0x7fc00000u) : (float)lo;
-    add_range[tile * 2 + 1] = nan ? __uint_as_float(0x7fc00000u) : (float)hi;
-  }
-}
-
-// is every code of these multi-bit rows below 2^index_bits?  What bbq_retile_multibit_kernel reports while it writes, asked BEFORE
-// anything is written: an append that fails leaves the index as it was
-__global__ __launch_bounds__(256) void bbq_check_code_range_kernel(const uint8_t *__restrict__ codes, int64_t count, uint32_t limit,
-                                                                   uint32_t *__restrict__ bad) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count && codes[i] >= limit) atomicOr(bad, 1u);
-}
-
-// does quantizedComponentSum equal the row's popcount everywhere? (then it need not be stored)
-__global__ __launch_bounds__(256) void bbq_check_x1_kernel(const uint8_t *__restrict__ codes, const double *__restrict__ corr,
-                                                          int64_t n_rows, int32_t pb, uint32_t *__restrict__ mismatch) {
-  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= n_rows) return;
-  const uint8_t *src = codes + row * (int64_t)pb;
-  uint32_t ones = 0;
-  for (int b = 0; b < pb; ++b) ones += __popc((uint32_t)src[b]);
-  if (!(corr[row * 4 + 3] == (double)ones)) atomicOr(mismatch, 1u);
-}
-
-// ---------------------------------------------------------------------------------------------------
 // shard transport: per-query lists [nq][list_cap] -> one packed buffer + offsets (what goes over RCCL)
 
 __global__ __launch_bounds__(1024) void bbq_pack_offsets_kernel(const int32_t *__restrict__ counts /*[nq][2]*/, int32_t nq,
@@ -629,7 +471,7 @@ static hipError_t launch_shared_t(const ScanArgs &a, int nq, int nc, hipStream_t
 }
 template <int QB, bool COMPACT, int NB>
 static hipError_t launch_shared_w(const ScanArgs &a, int nq, int nc, hipStream_t s) {
-  switch (a.idx.w16) {
+  switch (a.idx.geom.w16) {
     case 1: return launch_shared_t<QB, 1, COMPACT, NB>(a, nq, nc, s);
     case 6: return launch_shared_t<QB, 6, COMPACT, NB>(a, nq, nc, s);
     case 8: return launch_shared_t<QB, 8, COMPACT, NB>(a, nq, nc, s);
@@ -648,22 +490,22 @@ static hipError_t launch_shared_q(const ScanArgs &a, int planes, int nq, int nc,
 }
 
 bool shared_sweep_supported(const ScanArgs &a, int share) {
-  const int w = a.idx.w16;
-  return a.idx.store_bits == 1 && (share == 4 || share == 8) && (w == 1 || w == 6 || w == 8 || w == 12) && (size_t)share * a.cap * 8 < 48 * 1024;
+  const int w = a.idx.geom.w16;
+  return a.idx.geom.store_bits == 1 && (share == 4 || share == 8) && (w == 1 || w == 6 || w == 8 || w == 12) && (size_t)share * a.cap * 8 < 48 * 1024;
 }
 
 // sparse segments only; `share` queries per workgroup read each row once
 hipError_t launch_scan_shared(const ScanArgs &a, int planes, int share, int n_queries, int n_chunks, hipStream_t s) {
   if (n_chunks <= 0 || n_queries <= 0) return hipSuccess;
-  const bool compact = a.idx.layout == kLayoutCompact;
+  const bool compact = a.idx.geom.layout == kLayoutCompact;
   if (share == 8) return compact ? launch_shared_q<true, 8>(a, planes, n_queries, n_chunks, s) : launch_shared_q<false, 8>(a, planes, n_queries, n_chunks, s);
   return compact ? launch_shared_q<true, 4>(a, planes, n_queries, n_chunks, s) : launch_shared_q<false, 4>(a, planes, n_queries, n_chunks, s);
 }
 
 hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries, int n_chunks, hipStream_t s) {
   if (n_chunks <= 0 || n_queries <= 0) return hipSuccess;
-  const int mode = (dense ? 1 : 0) | (a.idx.layout == kLayoutCompact ? 2 : 0);
-  if (a.idx.store_bits > 1) {
+  const int mode = (dense ? 1 : 0) | (a.idx.geom.layout == kLayoutCompact ? 2 : 0);
+  if (a.idx.geom.store_bits > 1) {
     switch (mode) {
       case 0: return launch_scan_mb<false, 0>(a, nullptr, planes, n_queries, n_chunks, s);
       case 1: return launch_scan_mb<false, 1>(a, nullptr, planes, n_queries, n_chunks, s);
@@ -695,55 +537,4 @@ hipError_t launch_pack(const int32_t *counts, const uint64_t *lists, int64_t lis
   hipLaunchKernelGGL(bbq_pack_copy_kernel, dim3((unsigned)nq), dim3(256), 0, s, lists, list_stride, (const int64_t *)offsets, packed, packed_cap);
   return hipGetLastError();
 }
-
-hipError_t launch_retile(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t pb, uint8_t *tiles, int32_t w16,
-                         int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, hipStream_t s, int64_t row0) {
-  const int64_t n_pad = (n_rows + kTileRows - 1) / kTileRows * kTileRows;
-  const int64_t threads = (n_pad - row0) * (w16 + 1);
-  if (threads <= 0) return hipSuccess;
-  const int64_t blocks = (threads + 255) / 256;
-  hipLaunchKernelGGL(bbq_retile_kernel, dim3((unsigned)blocks), dim3(256), 0, s, codes, corr, n_rows, pb, tiles, w16, tile_stride,
-                     has_x1, n_pad, layout, exact, row0);
-  return hipGetLastError();
-}
-
-hipError_t launch_retile_multibit(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t store_bits, int32_t index_bits, uint8_t *tiles,
-                                  int32_t w16, int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, uint32_t *bad, hipStream_t s,
-                                  int64_t row0) {
-  const int64_t n_pad = (n_rows + kTileRows - 1) / kTileRows * kTileRows;
-  const int64_t threads = (n_pad - row0) * (w16 + 1);
-  if (threads <= 0) return hipSuccess;
-  const int64_t blocks = (threads + 255) / 256;
-  hipLaunchKernelGGL(bbq_retile_multibit_kernel, dim3((unsigned)blocks), dim3(256), 0, s, codes, corr, n_rows, dim, store_bits, index_bits, tiles, w16,
-                     tile_stride, has_x1, n_pad, layout, exact, bad, row0);
-  return hipGetLastError();
-}
-
-hipError_t launch_check_x1_multibit(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, uint32_t *mismatch, hipStream_t s) {
-  if (n_rows == 0) return hipSuccess;
-  const int64_t blocks = (n_rows + 255) / 256;
-  hipLaunchKernelGGL(bbq_check_x1_multibit_kernel, dim3((unsigned)blocks), dim3(256), 0, s, codes, corr, n_rows, dim, mismatch);
-  return hipGetLastError();
-}
-
-hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0) {
-  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows - tile0;
-  if (n_tiles <= 0) return hipSuccess;
-  hipLaunchKernelGGL(bbq_tile_add_range_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, exact, n_rows, add_range, tile0);
-  return hipGetLastError();
-}
-
-hipError_t launch_check_code_range(const uint8_t *codes, int64_t count, int32_t index_bits, uint32_t *bad, hipStream_t s) {
-  if (count <= 0) return hipSuccess;
-  hipLaunchKernelGGL(bbq_check_code_range_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, codes, count, 1u << index_bits, bad);
-  return hipGetLastError();
-}
-
-hipError_t launch_check_x1(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t pb, uint32_t *mismatch, hipStream_t s) {
-  if (n_rows == 0) return hipSuccess;
-  const int64_t blocks = (n_rows + 255) / 256;
-  hipLaunchKernelGGL(bbq_check_x1_kernel, dim3((unsigned)blocks), dim3(256), 0, s, codes, corr, n_rows, pb, mismatch);
-  return hipGetLastError();
-}
-
 }  // namespace bbq

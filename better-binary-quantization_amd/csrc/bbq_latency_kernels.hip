@@ -48,7 +48,7 @@ __global__ __launch_bounds__(kLatThreads) void bbq_lat_scan_kernel(const LatScan
   const int64_t tile = chunk * kTilesPerChunk + wave;
   bool nan_seen = false;
   if (tile < n_tiles) {  // wave-uniform
-    const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.tile_stride;
+    const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
     const int64_t row = tile * kTileRows + lane;
     const bool valid = row < a.idx.n_rows;
     f64x2 lu = {0.0, 0.0};
@@ -56,11 +56,11 @@ __global__ __launch_bounds__(kLatThreads) void bbq_lat_scan_kernel(const LatScan
     uint32_t cw = 0;
     float aadd = 0.0f;
     u32x4 c[W];
-    load_tile<W, COMPACT ? 1 : 2>(tp, lane, a.idx.has_x1 != 0, chunk_is_resident(chunk, a.idx), a.idx.nt_delta, c, cw, lu, xadd, x1);
+    load_tile<W, COMPACT ? 1 : 2>(tp, lane, a.idx.geom.has_x1 != 0, chunk_is_resident(chunk, a.idx), a.idx.nt_delta, c, cw, lu, xadd, x1);
     if constexpr (COMPACT) aadd = tile_add_bound(a.idx, tile, p.sim);
     uint32_t ones;
     const uint32_t qc = tile_popcounts<QB, W>(c, s_planes, ones);
-    if (!a.idx.has_x1) x1 = (double)ones;
+    if (!a.idx.geom.has_x1) x1 = (double)ones;
     bool need_exact = true;
     if constexpr (COMPACT) {
       need_exact = compact_bound_passes(valid, qc, cw, aadd, x1, p, theta);
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(kLatThreads) void bbq_lat_pre_kernel(const LatPreAr
   const int64_t tile = (int64_t)blockIdx.x * kTilesPerChunk + wave;
   const int64_t row = tile * kTileRows + lane;
   const bool valid = row < (int64_t)a.rows && row < a.idx.n_rows;
-  const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.tile_stride;
+  const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
   uint32_t key = 0;
   if (tile * kTileRows < (int64_t)a.rows) {  // wave-uniform
     f64x2 lu = {0.0, 0.0};
@@ -106,11 +106,11 @@ __global__ __launch_bounds__(kLatThreads) void bbq_lat_pre_kernel(const LatPreAr
     uint32_t unused = 0;
     u32x4 c[W];
     // the prefix the threshold is sampled from is also the part of the index that stays cache-resident
-    load_tile<W, COMPACT ? 0 : 2>(tp, lane, a.idx.has_x1 != 0, chunk_is_resident((int64_t)blockIdx.x, a.idx), a.idx.nt_delta, c, unused, lu, xadd, x1);
+    load_tile<W, COMPACT ? 0 : 2>(tp, lane, a.idx.geom.has_x1 != 0, chunk_is_resident((int64_t)blockIdx.x, a.idx), a.idx.nt_delta, c, unused, lu, xadd, x1);
     if constexpr (COMPACT) exact_corrections<true>(a.idx.exact, valid ? row : 0, lu, xadd);
     uint32_t ones;
     const uint32_t qc = tile_popcounts<QB, W>(c, s_planes, ones);
-    if (!a.idx.has_x1) x1 = (double)ones;
+    if (!a.idx.geom.has_x1) x1 = (double)ones;
     const float s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
     const bool nan = valid && (s32 != s32);
     if (__any(nan) && lane == 0) atomicOr(a.flags, kFlagNaN);
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_lat_select_kernel(const 
 template <int QB, bool COMPACT>
 static hipError_t lat_pre_w(const LatPreArgs &a, hipStream_t s) {
   const dim3 grid((unsigned)(a.rows / kChunkRows)), block(kLatThreads);
-  switch (a.idx.w16) {
+  switch (a.idx.geom.w16) {
     case 6: hipLaunchKernelGGL((bbq_lat_pre_kernel<QB, 6, COMPACT>), grid, block, 0, s, a); break;
     case 8: hipLaunchKernelGGL((bbq_lat_pre_kernel<QB, 8, COMPACT>), grid, block, 0, s, a); break;
     case 12: hipLaunchKernelGGL((bbq_lat_pre_kernel<QB, 12, COMPACT>), grid, block, 0, s, a); break;
@@ -159,7 +159,7 @@ static hipError_t lat_pre_w(const LatPreArgs &a, hipStream_t s) {
 
 hipError_t launch_lat_pre(const LatPreArgs &a, int planes, hipStream_t s) {
   if (a.rows <= 0 || a.rows % kChunkRows != 0 || a.per_wave < 1 || a.per_wave > 4) return hipErrorInvalidValue;
-  const bool c = a.idx.layout == kLayoutCompact;
+  const bool c = a.idx.geom.layout == kLayoutCompact;
   switch (planes) {
     case 1: return c ? lat_pre_w<1, true>(a, s) : lat_pre_w<1, false>(a, s);
     case 2: return c ? lat_pre_w<2, true>(a, s) : lat_pre_w<2, false>(a, s);
@@ -178,7 +178,7 @@ hipError_t launch_lat_select(const uint32_t *pre_keys, int n_keys, int rank, uin
 template <int QB, bool COMPACT>
 static hipError_t lat_scan_w(const LatScanArgs &a, hipStream_t s) {
   const dim3 grid((unsigned)a.n_chunks), block(kLatThreads);
-  switch (a.idx.w16) {
+  switch (a.idx.geom.w16) {
     case 6: hipLaunchKernelGGL((bbq_lat_scan_kernel<QB, 6, COMPACT>), grid, block, 0, s, a); break;
     case 8: hipLaunchKernelGGL((bbq_lat_scan_kernel<QB, 8, COMPACT>), grid, block, 0, s, a); break;
     case 12: hipLaunchKernelGGL((bbq_lat_scan_kernel<QB, 12, COMPACT>), grid, block, 0, s, a); break;
@@ -188,13 +188,13 @@ static hipError_t lat_scan_w(const LatScanArgs &a, hipStream_t s) {
 }
 
 bool latency_path_supported(const IndexView &v, int planes) {
-  return v.store_bits == 1 && (v.w16 == 6 || v.w16 == 8 || v.w16 == 12) && (planes == 1 || planes == 2 || planes == 4 || planes == 8) &&
-         v.w16 * planes <= kLatPlaneMax;
+  return v.geom.store_bits == 1 && (v.geom.w16 == 6 || v.geom.w16 == 8 || v.geom.w16 == 12) && (planes == 1 || planes == 2 || planes == 4 || planes == 8) &&
+         v.geom.w16 * planes <= kLatPlaneMax;
 }
 
 hipError_t launch_lat_scan(const LatScanArgs &a, int planes, hipStream_t s) {
   if (a.n_chunks <= 0) return hipErrorInvalidValue;
-  const bool c = a.idx.layout == kLayoutCompact;
+  const bool c = a.idx.geom.layout == kLayoutCompact;
   switch (planes) {
     case 1: return c ? lat_scan_w<1, true>(a, s) : lat_scan_w<1, false>(a, s);
     case 2: return c ? lat_scan_w<2, true>(a, s) : lat_scan_w<2, false>(a, s);

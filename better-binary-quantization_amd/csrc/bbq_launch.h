@@ -1,4 +1,5 @@
-// bbq_launch.h - host-callable launch wrappers of the kernels in bbq_kernels.hip
+// bbq_launch.h - host-callable launch wrappers of every kernel file: the sweeps, finalize and pack (bbq_kernels.hip, bbq_filter_kernels.hip,
+// bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip) and the rerank (bbq_rerank_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbq_device.h"
@@ -24,22 +25,6 @@ hipError_t launch_finalize(const FinalizeArgs &a, int n_queries, hipStream_t s);
 // (flagged) when the packed buffer cannot take the sum
 hipError_t launch_pack(const int32_t *counts, const uint64_t *lists, int64_t list_stride, int64_t advertised_cap, int32_t nq, int64_t *offsets,
                        int32_t *flags_out, int64_t *total_out, uint64_t *packed, int64_t packed_cap, hipStream_t s);
-// the build kernels below that take row0 (tile0) write at a row offset: codes / corr are the rows [row0, n_rows) of the storage, the
-// first of them lands in lane row0 % 64 of tile row0 / 64 and nothing below row0 is touched (0: a creation)
-hipError_t launch_retile(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t pb, uint8_t *tiles, int32_t w16,
-                         int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, hipStream_t s, int64_t row0);
-// multi-bit index (store_bits 2 / 4 / 8): codes are unpacked rows [n][dim]; *bad is raised by a code that is not below 2^index_bits
-hipError_t launch_retile_multibit(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, int32_t store_bits, int32_t index_bits, uint8_t *tiles,
-                                  int32_t w16, int32_t tile_stride, int32_t has_x1, int32_t layout, double *exact, uint32_t *bad, hipStream_t s,
-                                  int64_t row0);
-// multi-bit rows [count bytes]: *bad is raised by a code that is not below 2^index_bits (nothing is written)
-hipError_t launch_check_code_range(const uint8_t *codes, int64_t count, int32_t index_bits, uint32_t *bad, hipStream_t s);
-hipError_t launch_check_x1_multibit(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t dim, uint32_t *mismatch, hipStream_t s);
-// compact layout: each tile's {min, max} of additionalCorrection (read from exact[]) -> add_range[tile][2]
-hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0);
-hipError_t launch_check_x1(const uint8_t *codes, const double *corr, int64_t n_rows, int32_t pb, uint32_t *mismatch,
-                           hipStream_t s);
-
 // latency path (bbq_latency_kernels.hip): false when this index shape has no instantiation (the caller takes the general path)
 bool latency_path_supported(const IndexView &v, int planes);
 hipError_t launch_lat_scan(const LatScanArgs &a, int planes, hipStream_t s);
@@ -47,21 +32,32 @@ hipError_t launch_lat_scan(const LatScanArgs &a, int planes, hipStream_t s);
 hipError_t launch_lat_pre(const LatPreArgs &a, int planes, hipStream_t s);
 hipError_t launch_lat_select(const uint32_t *pre_keys, int n_keys, int rank, uint32_t *theta, hipStream_t s);
 
-// index build on the device (bbq_build_kernels.hip); vT4 is the [ceil(dim/4)][npad] float4 transposed copy
+// index build on the device (bbq_build_kernels.hip).  Every wrapper that writes or reads tile records takes them as a TileDest
+// (records, side rows, geometry: bbq_device.h) and rows in the caller's shape as StagedRows.  Those that take row0 (tile0) work at a
+// row offset: the rows handed over are the rows [row0, n_rows) of the storage, the first of them lands in lane row0 % 64 of tile
+// row0 / 64 and nothing below row0 is touched (0: a creation).
+// vT4 is the [ceil(dim/4)][npad] float4 transposed copy of the fp32 rows
 hipError_t launch_build_transpose(const float *in, int64_t n, int32_t dim, int64_t npad, float *vT4, hipStream_t s);
 hipError_t launch_build_normalize(float *vT4, int64_t n, int32_t dim, int64_t npad, hipStream_t s);
 hipError_t launch_build_validate(const float *vT4, int64_t n, int32_t dim, int64_t npad, unsigned long long *first_bad, hipStream_t s);
 hipError_t launch_build_centroid(const float *vT4, int64_t n, int32_t dim, int64_t npad, float *centroid, hipStream_t s);
-// row0 > 0: the n vectors become the rows [row0, row0 + n) of the storage (corr_rm stays indexed by the vector)
-hipError_t launch_build_quantize1(const float *vT4, int64_t n, int32_t dim, int64_t npad, const float *centroid, int32_t sim,
-                                  double lambda, int32_t iters, uint8_t *tiles, double *exact, double *corr_rm, int32_t w16,
-                                  int32_t tile_stride, int32_t layout, hipStream_t s, int64_t row0);
+// 1-bit: the n vectors become the rows [row0, row0 + n) of `out`, quantized straight into their lanes (corr_rm, optional, stays indexed
+// by the vector).  A freshly quantized row's component sum is its popcount: `out` is a geometry with has_x1 = 0
+hipError_t launch_build_quantize1(const float *vT4, int64_t n, int64_t npad, const float *centroid, int32_t sim, double lambda, int32_t iters,
+                                  const TileDest &out, double *corr_rm, hipStream_t s, int64_t row0);
 // indexBits > 1: unpacked codes [n][dim] (one byte per dimension) + row-major corrections [n][4], both in device memory
 hipError_t launch_build_quantize_bits(const float *vT4, int64_t n, int32_t dim, int64_t npad, const float *centroid, int32_t sim,
                                       double lambda, int32_t iters, int32_t bits, uint8_t *codes_rm, double *corr_rm, hipStream_t s);
-// the n rows from row0 on -> codes_rm [n][pb]
-hipError_t launch_build_untile(const uint8_t *tiles, int64_t n, int32_t pb, int32_t w16, int32_t tile_stride, uint8_t *codes_rm,
-                               hipStream_t s, int64_t row0);
+// the n rows of `src` from row0 on -> codes_rm [n][pb] (1-bit rows)
+hipError_t launch_build_untile(const TileDest &src, int64_t n, uint8_t *codes_rm, hipStream_t s, int64_t row0);
+// rows in the caller's shape -> tile records.  Multi-bit rows: *bad is raised by a code that is not below 2^index_bits (1-bit: unused)
+hipError_t launch_retile(const TileDest &out, const StagedRows &in, int64_t n_rows, int64_t row0, int32_t index_bits, uint32_t *bad, hipStream_t s);
+// *mismatch is raised by a row whose quantizedComponentSum is not its popcount (1-bit) / the sum of its codes (multi-bit)
+hipError_t launch_check_x1(const StagedRows &in, int64_t n_rows, const TileGeom &g, uint32_t *mismatch, hipStream_t s);
+// multi-bit rows [count bytes]: *bad is raised by a code that is not below 2^index_bits (nothing is written)
+hipError_t launch_check_code_range(const uint8_t *codes, int64_t count, int32_t index_bits, uint32_t *bad, hipStream_t s);
+// compact layout: each tile's {min, max} of additionalCorrection (read from exact[]) -> add_range[tile][2]
+hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0);
 
 // exact rerank (bbq_rerank_kernels.hip): one wave per 64 candidates of a query; max_count = longest candidate list
 hipError_t launch_rerank(const RerankArgs &a, int n_queries, int64_t max_count, hipStream_t s);

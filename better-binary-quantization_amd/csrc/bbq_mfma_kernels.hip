@@ -63,12 +63,8 @@
 
 namespace bbq {
 
-typedef uint32_t u32x4m __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2m __attribute__((ext_vector_type(2)));
 typedef int i32x4m __attribute__((ext_vector_type(4)));
 typedef int i32x16m __attribute__((ext_vector_type(16)));
-typedef double f64x2m __attribute__((ext_vector_type(2)));
-typedef float f32x4m __attribute__((ext_vector_type(4)));
 typedef float f32x16m __attribute__((ext_vector_type(16)));
 typedef int i32x8m __attribute__((ext_vector_type(8)));
 
@@ -191,27 +187,27 @@ constexpr int kMfmaMaxChunksPerBlock = 16;
 
 template <int W, bool COMPACT>
 struct TileRegs {
-  u32x4m c[W];     // this lane's row: its code words
-  f64x2m lu;       // {lower, upper}
+  u32x4 c[W];     // this lane's row: its code words
+  f64x2 lu;       // {lower, upper}
   double add;      // additionalCorrection
   double x1;       // explicit quantizedComponentSum (has_x1 only)
 };
 
 template <int W, bool COMPACT>
 __device__ __forceinline__ void load_tile_regs(TileRegs<W, COMPACT> &t, const IndexView &idx, int64_t tile, int lane) {
-  const uint8_t *__restrict__ tp = idx.tiles + tile * (int64_t)idx.tile_stride;
+  const uint8_t *__restrict__ tp = idx.tiles + tile * (int64_t)idx.geom.tile_stride;
 #pragma unroll
-  for (int j = 0; j < W; ++j) t.c[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4m *>(tp) + lane + j * kTileRows);
-  const uint8_t *__restrict__ cr = tp + (size_t)W * (kTileRows * 16);
+  for (int j = 0; j < W; ++j) t.c[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(tp) + lane + j * kTileRows);
+  const uint8_t *__restrict__ cr = tp + tile_corr_offset(W);
   if constexpr (COMPACT) {
     const double *__restrict__ ex = idx.exact + (tile * kTileRows + lane) * 4;
-    t.lu = __builtin_nontemporal_load(reinterpret_cast<const f64x2m *>(ex));
+    t.lu = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(ex));
     t.add = __builtin_nontemporal_load(ex + 2);
     t.x1 = 0.0;
   } else {
-    t.lu = __builtin_nontemporal_load(reinterpret_cast<const f64x2m *>(cr) + lane);
-    t.add = __builtin_nontemporal_load(reinterpret_cast<const double *>(cr + 1024) + lane);
-    t.x1 = idx.has_x1 ? __builtin_nontemporal_load(reinterpret_cast<const double *>(cr + 1536) + lane) : 0.0;
+    t.lu = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(cr) + lane);
+    t.add = __builtin_nontemporal_load(reinterpret_cast<const double *>(cr + kCorrAddOffset) + lane);
+    t.x1 = idx.geom.has_x1 ? __builtin_nontemporal_load(reinterpret_cast<const double *>(cr + kCorrSumOffset) + lane) : 0.0;
   }
 }
 
@@ -242,7 +238,7 @@ __device__ __forceinline__ typename std::conditional<FP, f32x16m, i32x16m>::type
 // offset, waited for by hand) because they must stay where they are written - one step ahead of their use.  Left to the compiler
 // every step's fragment is read ahead of the loop (12 x 6 registers at 768-d: spills); volatile reads leave the LDS address space.
 template <int G, int STEPS, int W>
-__device__ __forceinline__ void fp_step(f32x16m &acc0, f32x16m &acc1, const u32x4m (&c)[W], u32x4m &bq, u32x2m &bq2, uint32_t addr16, uint32_t addr8) {
+__device__ __forceinline__ void fp_step(f32x16m &acc0, f32x16m &acc1, const u32x4 (&c)[W], u32x4 &bq, u32x2 &bq2, uint32_t addr16, uint32_t addr8) {
   // a lane supplies 32 of a step's 64 dimensions: ONE code word - word 2G of its row group's row n in the lower half-wave, word
   // 2G + 1 in the upper.  The tile's words were swapped in place for that (swap_code_words): [0] = {row n: 2G | row n: 2G + 1}, [1] =
   // the same of row 32 + n
@@ -271,7 +267,7 @@ __device__ __forceinline__ void fp_step(f32x16m &acc0, f32x16m &acc1, const u32x
 // groups, for every group of queries the workgroup serves (per group and step it was a swap and, for all but the last group, two
 // copies: the swap overwrites both of its operands)
 template <int W>
-__device__ __forceinline__ void swap_code_words(u32x4m (&c)[W]) {
+__device__ __forceinline__ void swap_code_words(u32x4 (&c)[W]) {
 #pragma unroll
   for (int j = 0; j < W; ++j) {
     const auto s0 = __builtin_amdgcn_permlane32_swap(c[j].x, c[j].y, false, false);
@@ -302,9 +298,9 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
   constexpr int gpb = G, nqb = gpb * kMfmaQueries;                                   // query slots of this workgroup (G = a.groups_per_block)
   const int scap = a.stage_cap, qcap = a.queue_cap;
   // per group: u32x4 [STEPS*2][32] 16 B per lane and step; FP: then u32x2 [STEPS*2][32], the rest of the lane's 32 FP6 values
-  f32x4m *s_qk = reinterpret_cast<f32x4m *>(smem + (size_t)gpb * QBYTES);            // [nqb] per-query constants -S * {zth/beta, ay/ly, y1, 1/beta}
-  f64x2m *s_lu = reinterpret_cast<f64x2m *>(s_qk + nqb);                             // [NW][64] {lower, upper} of every tile row, for the survivors' exact scores ...
-  f64x2m *s_ax = s_lu + NW * 64;                                                     // [NW][64] ... and {additionalCorrection, component sum}: no trip to memory there
+  f32x4 *s_qk = reinterpret_cast<f32x4 *>(smem + (size_t)gpb * QBYTES);            // [nqb] per-query constants -S * {zth/beta, ay/ly, y1, 1/beta}
+  f64x2 *s_lu = reinterpret_cast<f64x2 *>(s_qk + nqb);                             // [NW][64] {lower, upper} of every tile row, for the survivors' exact scores ...
+  f64x2 *s_ax = s_lu + NW * 64;                                                     // [NW][64] ... and {additionalCorrection, component sum}: no trip to memory there
   uint32_t *s_queue = reinterpret_cast<uint32_t *>(s_ax + NW * 64);                  // [NW][qcap]
   uint32_t *s_qcount = s_queue + NW * qcap;                                          // [NW] (+ padding to 16 B)
   QueryParams *s_qp = reinterpret_cast<QueryParams *>(s_qcount + 8);                 // [nqb]
@@ -338,7 +334,7 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
     if (lane < nqb) {
       QueryParams p{};
       uint32_t th = 0xFFFFFFFFu;
-      f32x4m qk;
+      f32x4 qk;
       // lanes without a query: the largest finite threshold - nothing of an ordinary row passes (a weird row's pairs are dropped later)
       qk.x = -3.0e38f; qk.y = 0.0f; qk.z = 0.0f; qk.w = 0.0f;
       if (lane < nb) {
@@ -376,14 +372,14 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
       }
     }
   } else {
-    const u32x4m *__restrict__ gb = reinterpret_cast<const u32x4m *>(a.qbytes + (size_t)group0 * QBYTES);
-    u32x4m *__restrict__ sb = reinterpret_cast<u32x4m *>(smem);
+    const u32x4 *__restrict__ gb = reinterpret_cast<const u32x4 *>(a.qbytes + (size_t)group0 * QBYTES);
+    u32x4 *__restrict__ sb = reinterpret_cast<u32x4 *>(smem);
     for (int i = tid - 64; i < ng * (QBYTES / 16); i += NT - 64) sb[i] = gb[i];
   }
   __syncthreads();
 
   const int sim = s_qp[0].sim;                  // uniform over the call
-  const float Df = (float)a.s.idx.dim;
+  const float Df = (float)a.s.idx.geom.dim;
 #pragma unroll 1
   for (int ci = 0; ci < cpb; ++ci) {
   const int lc = lc0 + ci;           // chunk index inside this launch
@@ -399,7 +395,7 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
     // (every constant but r1 first: the start-value MFMAs that do not need the popcount are issued in front of it)
     float rho;
     bool row_ok;
-    RowK mine = row_constants_early<FP>(t.lu.x, t.lu.y, t.add, a.s.idx.has_x1 ? fabsf((float)t.x1) * 1.0000002f : Df, Df, sim, s_gmax, rho, row_ok);
+    RowK mine = row_constants_early<FP>(t.lu.x, t.lu.y, t.add, a.s.idx.geom.has_x1 ? fabsf((float)t.x1) * 1.0000002f : Df, Df, sim, s_gmax, rho, row_ok);
     // (K first; the last step is the only one that needs the row's popcount)
     const auto b0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(mine.K), __float_as_uint(mine.r0), false, false);
     const auto b1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(mine.r2), __float_as_uint(mine.r3), false, false);
@@ -409,7 +405,7 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
     asm volatile("v_mov_b32 %0, 0" : "=v"(lds_off0));
     float aqf[3];
     {
-      const f32x4m qkm = s_qk[n + lds_off0];
+      const f32x4 qkm = s_qk[n + lds_off0];
       aqf[0] = h ? qkm.x : 1.0f;    // step 0: K x 1 + qk[0] r0
       aqf[1] = h ? qkm.w : qkm.z;   // step 1: qk[2] r2 + qk[3] r3
       aqf[2] = h ? 0.0f : qkm.y;    // step 2: qk[1] r1 (the row's popcount is in r1)
@@ -422,11 +418,11 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
 #pragma unroll
     for (int j = 0; j < W; ++j) ones += __popc(t.c[j].x) + __popc(t.c[j].y) + __popc(t.c[j].z) + __popc(t.c[j].w);
     double x1row = (double)ones;                 // quantizedComponentSum of a 1-bit row is its popcount ...
-    if (a.s.idx.has_x1) x1row = t.x1;            // ... unless the index says otherwise
+    if (a.s.idx.geom.has_x1) x1row = t.x1;            // ... unless the index says otherwise
     mine.r1 = row_ok ? -fmaf(rho, Df, (float)x1row) : 0.0f;
     s_lu[wave * 64 + lane] = t.lu;               // for the survivors' exact scores (any lane may score any row of the tile)
     {
-      f64x2m ax;
+      f64x2 ax;
       ax.x = t.add; ax.y = x1row;
       s_ax[wave * 64 + lane] = ax;
     }
@@ -451,8 +447,8 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
     asm volatile("v_mov_b32 %0, 0" : "=v"(lds_off));
     const int gq = g * kMfmaQueries;             // first query slot of this group
     const int nbg = min(kMfmaQueries, nb - gq);  // its queries (<= 0: none)
-    const u32x4m *__restrict__ s_B = reinterpret_cast<const u32x4m *>(smem + (size_t)g * QBYTES);
-    const u32x2m *__restrict__ s_B2 = reinterpret_cast<const u32x2m *>(smem + (size_t)g * QBYTES + (size_t)STEPS * 2 * 32 * 16);
+    const u32x4 *__restrict__ s_B = reinterpret_cast<const u32x4 *>(smem + (size_t)g * QBYTES);
+    const u32x2 *__restrict__ s_B2 = reinterpret_cast<const u32x2 *>(smem + (size_t)g * QBYTES + (size_t)STEPS * 2 * 32 * 16);
     // A operands of the start-value contraction (start_values): query n's constants, k = 0 in the lower half-wave, k = 1 in the upper
     float aq0, aq1, aq2;
     Acc acc0, acc1;
@@ -461,7 +457,7 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
       acc0 = start_values_finish<FP>(e0, aq2, rb[0][2]);
       acc1 = start_values_finish<FP>(e1, aq2, rb[1][2]);
     } else {
-      const f32x4m qkm = s_qk[gq + n + lds_off];
+      const f32x4 qkm = s_qk[gq + n + lds_off];
       aq0 = h ? qkm.x : 1.0f;
       aq1 = h ? qkm.w : qkm.z;
       aq2 = h ? 0.0f : qkm.y;
@@ -472,8 +468,8 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
     if constexpr (FP) {
       // LDS byte addresses of this lane's fragment of step 0 (the pointers are LDS pointers: their low 32 bits are the offset)
       const uint32_t addr16 = (uint32_t)(uintptr_t)(s_B + h * 32 + n + lds_off), addr8 = (uint32_t)(uintptr_t)(s_B2 + h * 32 + n + lds_off);
-      u32x4m bq;
-      u32x2m bq2;
+      u32x4 bq;
+      u32x2 bq2;
       // (the swapped words are the same for every group: named here, or their 96 masked forms are computed once and kept - spilled)
 #pragma unroll
       for (int j = 0; j < W; ++j) asm volatile("" : "+v"(t.c[j]));
@@ -486,7 +482,7 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
         // swap(w, w >> 4): [0] = {row n's word | row n's word >> 4}, [1] = {row 32+n's word | row 32+n's word >> 4}: the lower half-wave
         // supplies the low nibble of every byte, the upper one the high nibble, of the row group's row n
         const auto sw = __builtin_amdgcn_permlane32_swap(w, w >> 4, false, false);
-        const u32x4m bq = s_B[(w8 * 2 + h) * 32 + n + lds_off];
+        const u32x4 bq = s_B[(w8 * 2 + h) * 32 + n + lds_off];
         i32x4m Q;
         Q.x = (int)bq.x; Q.y = (int)bq.y; Q.z = (int)bq.z; Q.w = (int)bq.w;
         i32x4m R0, R1;
@@ -567,7 +563,7 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
         const int qc = (int)(e & 0xFFFFFu), rit = (int)((e >> 20) & 63u), qn = gq + (int)(e >> 26);
         const QueryParams pq = s_qp[qn];
         const int64_t row = tile * kTileRows + rit;
-        const f64x2m lu = s_lu[wave * 64 + rit], ax = s_ax[wave * 64 + rit];
+        const f64x2 lu = s_lu[wave * 64 + rit], ax = s_ax[wave * 64 + rit];
         const double lo = lu.x, up = lu.y, ad = ax.x, x1d = ax.y;
         const float s32 = (float)score_f64((double)qc, lo, up, ad, x1d, pq);
         bool nan = false;
@@ -625,13 +621,13 @@ static size_t mfma_smem_bytes(int w16, int stage_cap, bool fp, int gpb, int queu
 // (the int8 form up to 1024-d stays at one group: with two its fragment reads are scheduled across the groups and spill)
 constexpr bool mfma_two_groups_built(int w16, bool fp) { return fp || w16 > 8; }
 static int mfma_groups_per_block(const ScanArgs &a, int groups, bool fp) {
-  if (groups < 2 || !mfma_two_groups_built(a.idx.w16, fp)) return 1;
+  if (groups < 2 || !mfma_two_groups_built(a.idx.geom.w16, fp)) return 1;
   // the chunk slots' capacity says how many candidates the plan expects here (cap_for: lam + 8 sqrt(lam) + 16 for lam candidates per
   // chunk and query): up to 64 slots a tile and group has 4 lam <= 62 survivors on average, eight standard deviations below the queue
   if (a.cap > 64) return 1;
-  const size_t two = mfma_smem_bytes(a.idx.w16, std::min<int>(a.cap, kMfmaStageCapTwo), fp, 2, kMfmaQueueCapTwo);
+  const size_t two = mfma_smem_bytes(a.idx.geom.w16, std::min<int>(a.cap, kMfmaStageCapTwo), fp, 2, kMfmaQueueCapTwo);
   const size_t lds_alloc = (two + 1279) / 1280 * 1280;  // LDS is handed out in 1280-byte blocks
-  return (a.idx.w16 <= 8 ? 2 * lds_alloc <= 160 * 1024 : two <= 150 * 1024) ? 2 : 1;
+  return (a.idx.geom.w16 <= 8 ? 2 * lds_alloc <= 160 * 1024 : two <= 150 * 1024) ? 2 : 1;
 }
 
 template <int W, bool COMPACT, bool FP>
@@ -671,8 +667,8 @@ static hipError_t launch_mfma_w(const MfmaArgs &a, bool compact, bool fp, int nq
 
 // the sweep appends its candidates to the queries' lists (ScanArgs::append_lists): it has no chunk-slot output
 bool mfma_sweep_supported(const ScanArgs &a) {
-  const int w = a.idx.w16;
-  if (!a.append_lists || a.idx.store_bits != 1 || !(w == 1 || w == 6 || w == 8 || w == 12)) return false;
+  const int w = a.idx.geom.w16;
+  if (!a.append_lists || a.idx.geom.store_bits != 1 || !(w == 1 || w == 6 || w == 8 || w == 12)) return false;
   return mfma_smem_bytes(w, a.cap, false, 1, kMfmaQueueCap) <= 150 * 1024;
 }
 
@@ -687,8 +683,8 @@ hipError_t launch_scan_mfma(const ScanArgs &sa, const uint8_t *qbytes, const flo
   if (n_chunks <= 0 || n_queries <= 0) return hipSuccess;
   const bool fp = fp_scale > 0.0f;
   MfmaArgs a{sa, qbytes, qmax, n_queries, 1, fp_scale, 1, sa.cap, kMfmaQueueCap};
-  const bool compact = sa.idx.layout == kLayoutCompact;
-  switch (sa.idx.w16) {
+  const bool compact = sa.idx.geom.layout == kLayoutCompact;
+  switch (sa.idx.geom.w16) {
     case 1: return launch_mfma_w<1>(a, compact, fp, n_queries, n_chunks, s);
     case 6: return launch_mfma_w<6>(a, compact, fp, n_queries, n_chunks, s);
     case 8: return launch_mfma_w<8>(a, compact, fp, n_queries, n_chunks, s);

@@ -191,7 +191,7 @@ int multi_search_batch(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, 
   MultiState *ms = ix->multi;
   std::lock_guard<std::mutex> lk(ms->mu);
   const int64_t keff = std::min<int64_t>(k, ix->n_rows);  // thresholds are order statistics of rank min(k, N) (bbq_search_batch)
-  const int dim = ix->dim;
+  const int dim = ix->geom.dim;
   if (keff > kMaxFastK || ix->opt_force_dense) {
     for (int32_t q = 0; q < n_queries; ++q) {
       int rc = dense_query(ix, qquant + (size_t)q * dim, qcorr + (size_t)q * 4, query_bits, sim, k, out_idx + (int64_t)q * k,
@@ -381,16 +381,13 @@ int multi_set_option(bbq_index *ix, const char *name, int64_t v) {
 // the handle's own fields from its shards (every shard decides has_x1 - and with it a fallback to the inline layout - on its own
 // rows: the handle reports the widest)
 static void adopt_shard_geometry(bbq_index *ix, MultiState *ms) {
-  ix->bytes_per_row = 0;
-  ix->has_x1 = 0;
+  int32_t has_x1 = 0;
+  ix->geom.tile_stride = 0;
   for (const MultiShard &sh : ms->shards) {
-    if (sh.ix->bytes_per_row >= ix->bytes_per_row) {
-      ix->bytes_per_row = sh.ix->bytes_per_row;
-      ix->layout = sh.ix->layout;
-      ix->tile_stride = sh.ix->tile_stride;
-    }
-    ix->has_x1 = ix->has_x1 || sh.ix->has_x1;
+    if (sh.ix->geom.tile_stride >= ix->geom.tile_stride) ix->geom = sh.ix->geom;
+    has_x1 |= sh.ix->geom.has_x1;
   }
+  ix->geom.has_x1 = has_x1;
 }
 
 // a multi-device handle over shard indexes that already exist (loaded from files); takes ownership of them on success
@@ -432,7 +429,7 @@ int multi_save(bbq_index *ix, const char *prefix, const float *centroid, int32_t
     bounds.push_back(sh.r1 - sh.r0);
     if (sh.ix->has_pilot) pilot = std::max<int64_t>(pilot, sh.ix->pilot.view.n_rows);
   }
-  return write_manifest(prefix, (int32_t)ms->shards.size(), bounds.data(), ix->dim, ix->index_bits, sim, ix->n_rows, ix->centroid_dp, pilot, centroid);
+  return write_manifest(prefix, (int32_t)ms->shards.size(), bounds.data(), ix->geom.dim, ix->index_bits, sim, ix->n_rows, ix->centroid_dp, pilot, centroid);
 }
 
 int multi_get_stats(bbq_index *ix, bbq_stats *out) {

@@ -66,10 +66,6 @@ uint64_t fnv64_words(const void *data, size_t n, uint64_t h) {
 }
 constexpr uint64_t kFnvSeed = 0xcbf29ce484222325ull;
 
-int32_t expected_tile_stride(int32_t w16, int32_t layout, int32_t has_x1) {
-  return tile_stride_of(w16, layout, has_x1);
-}
-
 struct FileCloser {
   FILE *f;
   ~FileCloser() { if (f) fclose(f); }
@@ -91,7 +87,7 @@ int read_meta(const char *prefix, MetaHeader *h, std::vector<float> *centroid, u
     return fail(BBQ_ERR_INVALID_ARG, "%s: header fields out of range", path.c_str());
   const int32_t pb = row_bytes_of(h->dimensions, h->dimensions == 1 ? 1 : store_bits_of(h->indexBits));
   const int64_t n_tiles = (h->vectorCount + kTileRows - 1) / kTileRows;
-  if (h->w16 != (pb + 15) / 16 || h->tileStride != expected_tile_stride(h->w16, h->layout, h->hasX1) ||
+  if (h->w16 != (pb + 15) / 16 || h->tileStride != tile_stride_of(h->w16, h->layout, h->hasX1) ||
       (h->layout == kLayoutCompact && h->hasX1) || h->tilesBytes != n_tiles * h->tileStride ||
       h->exactBytes != (h->layout == kLayoutCompact ? compact_side_bytes(n_tiles) : 0) ||
       h->vectorDataLength != h->tilesBytes + h->exactBytes + px.pilotTilesBytes + px.pilotExactBytes || h->vectorDataOffset < 0)
@@ -216,19 +212,19 @@ int bbq_index_save(bbq_index *ix, const char *prefix, const float *centroid, int
   memcpy(h.magic, "BVEC", 4);
   h.version = ix->has_pilot ? kFileVersionPilot : kFileVersion;
   h.vectorSimilarityOrdinal = sim;
-  h.dimensions = ix->dim;
+  h.dimensions = ix->geom.dim;
   h.vectorCount = ix->n_rows;
   h.centroidSquareMagnitude = ix->centroid_dp;
   h.indexBits = ix->index_bits;
-  h.layout = ix->layout;
-  h.w16 = ix->w16;
-  h.tileStride = ix->tile_stride;
-  h.hasX1 = ix->has_x1;
+  h.layout = ix->geom.layout;
+  h.w16 = ix->geom.w16;
+  h.tileStride = ix->geom.tile_stride;
+  h.hasX1 = ix->geom.has_x1;
   h.tileRows = kTileRows;
-  h.tilesBytes = n_tiles * ix->tile_stride;
-  h.exactBytes = ix->layout == kLayoutCompact ? compact_side_bytes(n_tiles) : 0;
+  h.tilesBytes = n_tiles * ix->geom.tile_stride;
+  h.exactBytes = ix->geom.layout == kLayoutCompact ? compact_side_bytes(n_tiles) : 0;
   h.rowBase = ix->row_base;
-  PilotExt px{p_rows, p_tiles * ix->tile_stride, (ix->has_pilot && ix->layout == kLayoutCompact) ? compact_side_bytes(p_tiles) : 0};
+  PilotExt px{p_rows, p_tiles * ix->geom.tile_stride, (ix->has_pilot && ix->geom.layout == kLayoutCompact) ? compact_side_bytes(p_tiles) : 0};
   h.vectorDataOffset = 0;
   h.vectorDataLength = h.tilesBytes + h.exactBytes + px.pilotTilesBytes + px.pilotExactBytes;
   const std::string dpath = std::string(prefix) + ".veb", mpath = std::string(prefix) + ".vemb";
@@ -258,11 +254,11 @@ int bbq_index_save(bbq_index *ix, const char *prefix, const float *centroid, int
   if (!fc.f) return fail(BBQ_ERR_INVALID_ARG, "cannot create %s", mpath.c_str());
   uint64_t m = fnv64_words(&h, sizeof h, kFnvSeed);
   if (ix->has_pilot) m = fnv64_words(&px, sizeof px, m);
-  m = fnv64_words(centroid, (size_t)ix->dim * 4, m);
+  m = fnv64_words(centroid, (size_t)ix->geom.dim * 4, m);
   m = fnv64_words(&dsum, 8, m);
   const uint64_t sums[2] = {dsum, m};
   if (fwrite(&h, sizeof h, 1, fc.f) != 1 || (ix->has_pilot && fwrite(&px, sizeof px, 1, fc.f) != 1) ||
-      fwrite(centroid, 4, (size_t)ix->dim, fc.f) != (size_t)ix->dim || fwrite(sums, 8, 2, fc.f) != 2 || fflush(fc.f) != 0)
+      fwrite(centroid, 4, (size_t)ix->geom.dim, fc.f) != (size_t)ix->geom.dim || fwrite(sums, 8, 2, fc.f) != 2 || fflush(fc.f) != 0)
     return fail(BBQ_ERR_INVALID_ARG, "%s: write failed", mpath.c_str());
   return BBQ_OK;
 }
@@ -328,7 +324,7 @@ int bbq_index_load_multi(const char *prefix, int32_t n_devices, const int32_t *d
     if (rc != BBQ_OK) return bail(rc);
     shards.push_back(sh);
     devs.push_back(dev);
-    if (sh->multi || sh->dim != m.h.dimensions || sh->index_bits != m.h.indexBits || sh->row_base != m.bounds[(size_t)2 * s] || sh->n_rows != m.bounds[(size_t)2 * s + 1])
+    if (sh->multi || sh->geom.dim != m.h.dimensions || sh->index_bits != m.h.indexBits || sh->row_base != m.bounds[(size_t)2 * s] || sh->n_rows != m.bounds[(size_t)2 * s + 1])
       return bail(fail(BBQ_ERR_INVALID_ARG, "%s: shard %d does not match the manifest", prefix, s));
   }
   rc = multi_assemble(shards.data(), devs.data(), m.h.nShards, m.h.dimensions, m.h.indexBits, m.h.vectorCount, m.h.centroidSquareMagnitude, out);
@@ -363,15 +359,12 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
   std::unique_ptr<bbq_index> ix(new bbq_index());
   rc = attach_index(ix.get(), ctx, device, h.dimensions, h.indexBits);
   if (rc != BBQ_OK) return rc;
-  ix->w16 = h.w16;
   ix->row_base = h.rowBase;
   ix->centroid_dp = h.centroidSquareMagnitude;
   ix->has_pilot = px.pilotRows > 0;
   ix->want_compact = h.layout == kLayoutCompact;
-  ix->layout = h.layout;
-  ix->has_x1 = h.hasX1;
-  ix->tile_stride = h.tileStride;
-  ix->bytes_per_row = h.tileStride / kTileRows;
+  ix->geom.has_x1 = h.hasX1;
+  decide_layout(ix.get());  // read_meta has held the file's w16, layout and tileStride to exactly this
   auto bail = [&](int code) {
     destroy_unlocked(ix.release());
     return code;
@@ -413,50 +406,45 @@ int bbq_index_export(bbq_index *ix, uint8_t *codes, double *corr) {
   if (ix->multi) return multi_export(ix, codes, corr);
   std::lock_guard<std::mutex> lk(ix->ctx->mu);
   HIPCHK(hipSetDevice(ix->device));
-  const int64_t n_tiles = (ix->n_rows + kTileRows - 1) / kTileRows;
-  const int64_t group = std::max<int64_t>(1, (64ll << 20) / ix->tile_stride);  // tiles per piece
-  std::vector<uint8_t> buf((size_t)(group * ix->tile_stride));
+  const TileGeom &g = ix->geom;
+  const int64_t n_tiles = tiles_of(ix->n_rows);
+  const int64_t group = std::max<int64_t>(1, (64ll << 20) / g.tile_stride);  // tiles per piece
+  std::vector<uint8_t> buf((size_t)(group * g.tile_stride));
   std::vector<double> ex;
-  if (corr && ix->layout == kLayoutCompact) ex.resize((size_t)(group * kTileRows * 4));
-  const int pb = ix->pb, w16 = ix->w16;
+  if (corr && g.layout == kLayoutCompact) ex.resize((size_t)(group * kTileRows * 4));
+  // a byte of the caller's row is eight 1-bit fields of the stored row as they are, or one multi-bit field (one byte per dimension,
+  // src/binaryQuantizationFormat.ts:241-245): field i sits at bit i * field_bits of the stored row
+  const int field_bits = g.store_bits == 1 ? 8 : g.store_bits;
+  const int64_t out_bytes = caller_row_bytes(ix);
   for (int64_t t0 = 0; t0 < n_tiles; t0 += group) {
     const int64_t nt = std::min(group, n_tiles - t0);
-    HIPCHK(hipMemcpy(buf.data(), ix->main.d_tiles + t0 * ix->tile_stride, (size_t)(nt * ix->tile_stride), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(buf.data(), ix->main.d_tiles + t0 * g.tile_stride, (size_t)(nt * g.tile_stride), hipMemcpyDeviceToHost));
     if (!ex.empty())
       HIPCHK(hipMemcpy(ex.data(), ix->main.d_exact + t0 * kTileRows * 4, (size_t)(nt * kTileRows) * 32, hipMemcpyDeviceToHost));
     for (int64_t t = 0; t < nt; ++t) {
-      const uint8_t *tp = buf.data() + t * ix->tile_stride;
-      const uint8_t *cr = tp + (size_t)w16 * (kTileRows * 16);
+      const uint8_t *tp = buf.data() + t * g.tile_stride;
+      const uint8_t *cr = tp + tile_corr_offset(g.w16);
       for (int r = 0; r < kTileRows; ++r) {
         const int64_t row = (t0 + t) * kTileRows + r;
         if (row >= ix->n_rows) break;
         int ones = 0;  // popcount of a 1-bit row / component sum of a multi-bit row
-        if (ix->store_bits == 1) {
-          for (int b = 0; b < pb; ++b) {
-            const uint8_t v = tp[((size_t)(b >> 4) * kTileRows + r) * 16 + (b & 15)];
-            if (codes) codes[row * pb + b] = v;
-            ones += __builtin_popcount(v);
-          }
-        } else {  // fields back to one byte per dimension (src/binaryQuantizationFormat.ts:241-245)
-          const int sb = ix->store_bits;
-          for (int d = 0; d < ix->dim; ++d) {
-            const int bit = d * sb, b = bit >> 3;
-            const uint8_t byte = tp[((size_t)(b >> 4) * kTileRows + r) * 16 + (b & 15)];
-            const uint8_t v = (uint8_t)((byte >> (bit & 7)) & ((1u << sb) - 1u));
-            if (codes) codes[row * (int64_t)ix->dim + d] = v;
-            ones += v;
-          }
+        for (int64_t i = 0; i < out_bytes; ++i) {
+          const int64_t bit = i * field_bits, b = bit >> 3;
+          const uint8_t byte = tp[tile_chunk_offset((int)(b / kChunkBytes), r) + b % kChunkBytes];
+          const uint8_t v = (uint8_t)((byte >> (bit & 7)) & ((1u << field_bits) - 1u));
+          if (codes) codes[row * out_bytes + i] = v;
+          ones += g.store_bits == 1 ? __builtin_popcount(v) : v;
         }
         if (!corr) continue;
         double *c = corr + row * 4;
-        if (ix->layout == kLayoutCompact) {
+        if (g.layout == kLayoutCompact) {
           const double *e = ex.data() + ((size_t)t * kTileRows + r) * 4;
           c[0] = e[0]; c[1] = e[1]; c[2] = e[2];
           c[3] = (double)ones;  // compact layout is only chosen when every sum equals the popcount
         } else {
           memcpy(c, cr + r * 16, 16);
-          memcpy(c + 2, cr + 1024 + r * 8, 8);
-          if (ix->has_x1) memcpy(c + 3, cr + 1536 + r * 8, 8);
+          memcpy(c + 2, cr + kCorrAddOffset + r * 8, 8);
+          if (g.has_x1) memcpy(c + 3, cr + kCorrSumOffset + r * 8, 8);
           else c[3] = (double)ones;
         }
       }

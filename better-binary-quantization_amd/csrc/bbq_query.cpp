@@ -25,13 +25,13 @@ static int planes_for(const uint8_t *q, int64_t count) {
 }
 
 // bytes of staged query data per query (bit-planes, or the nibble / byte dwords of a multi-bit index)
-int64_t query_data_bytes(const bbq_index *ix, int planes) { return (int64_t)ix->w16 * query_units_per_chunk(planes, ix->store_bits) * 16; }
+int64_t query_data_bytes(const bbq_index *ix, int planes) { return (int64_t)ix->geom.w16 * query_units_per_chunk(planes, ix->geom.store_bits) * 16; }
 
 // kernel variant for a call: 1-bit index -> number of bit-planes the query values need; multi-bit index -> 4 (values <= 15: low
 // nibbles only) or 8
 int planes_of_call(const bbq_index *ix, const uint8_t *q, int64_t count, int one_bit) {
-  if (ix->store_bits == 1) return one_bit ? 1 : planes_for(q, count);
-  if (ix->store_bits == 8) return 8;
+  if (ix->geom.store_bits == 1) return one_bit ? 1 : planes_for(q, count);
+  if (ix->geom.store_bits == 8) return 8;
   return max_value(q, count) <= 15 ? 4 : 8;
 }
 
@@ -43,10 +43,10 @@ int planes_of_call(const bbq_index *ix, const uint8_t *q, int64_t count, int one
 void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const uint8_t *q, const double *qc, int planes,
                 int one_bit, int sim) {
   memset(planes_dst, 0, (size_t)query_data_bytes(ix, planes));
-  if (ix->store_bits == 1) {
+  if (ix->geom.store_bits == 1) {
     // eight dimensions (one byte of every plane) at a time: bit p of the eight query bytes, gathered MSB-first by one multiply -
     // source bit 8i (dimension 8*byte + i) goes to bit 63 - i of the product, no two partial products share a position
-    const int full = ix->dim >> 3;
+    const int full = ix->geom.dim >> 3;
     for (int byte = 0; byte < full; ++byte) {
       uint64_t x;
       memcpy(&x, q + (size_t)byte * 8, 8);
@@ -55,7 +55,7 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
       for (int p = 0; p < planes; ++p)
         planes_dst[((size_t)j * planes + p) * 16 + b] = (uint8_t)((((x >> p) & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56);
     }
-    for (int d = full * 8; d < ix->dim; ++d) {  // the last, partial byte
+    for (int d = full * 8; d < ix->geom.dim; ++d) {  // the last, partial byte
       const uint8_t v = q[d];
       if (!v) continue;
       const int byte = d >> 3, j = byte >> 4, b = byte & 15;
@@ -64,9 +64,9 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
         if ((v >> p) & 1) planes_dst[((size_t)j * planes + p) * 16 + b] |= bit;
     }
   } else {
-    const int sb = ix->store_bits, per = 32 / sb, qn = query_units_per_chunk(planes, sb);
+    const int sb = ix->geom.store_bits, per = 32 / sb, qn = query_units_per_chunk(planes, sb);
     uint32_t *dst = reinterpret_cast<uint32_t *>(planes_dst);
-    for (int d = 0; d < ix->dim; ++d) {
+    for (int d = 0; d < ix->geom.dim; ++d) {
       const uint32_t v = q[d];
       if (!v) continue;
       const int w = d / per, f = d % per;
@@ -91,9 +91,9 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
   // multi-bit index: the reference's batch scorer throws on unpacked rows and its per-row scorer answers
   // (src/binaryQuantizedScorer.ts:403-419): centroidDP is 0 for every query width but 1 (searchNearestNeighbors passes no
   // original query, :290) and MAXIMUM_INNER_PRODUCT is not divided by FOUR_BIT_SCALE (:207-209)
-  const bool per_row_form = ix->store_bits > 1;
+  const bool per_row_form = ix->geom.store_bits > 1;
   pp->cdp = (per_row_form && !one_bit) ? 0.0 : ix->centroid_dp;
-  pp->dimd = (double)ix->dim;
+  pp->dimd = (double)ix->geom.dim;
   pp->sim = sim;
   pp->one_bit = one_bit;
   pp->mip_plain = per_row_form ? 1 : 0;
@@ -105,8 +105,8 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
 // byte 4g + (p >> 3), bit (p & 7), i.e. dimension 32g + 8*(p >> 3) + 7 - (p & 7) (MSB-first packing,
 // src/optimizedScalarQuantizer.ts:420-446).  Layout: [group][g][h][n][16 B], n = query in its group of 32.
 static void fill_query_mfma(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q) {
-  const int words = ix->w16 * 4, group = q_in_batch / 32, n = q_in_batch % 32;
-  uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->w16, false);
+  const int words = ix->geom.w16 * 4, group = q_in_batch / 32, n = q_in_batch % 32;
+  uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->geom.w16, false);
   for (int g = 0; g < words; ++g)
     for (int h = 0; h < 2; ++h) {
       uint8_t *o = gb + (((size_t)g * 2 + h) * 32 + n) * 16;
@@ -114,7 +114,7 @@ static void fill_query_mfma(const bbq_index *ix, uint8_t *dst, int q_in_batch, c
         for (int i = 0; i < 4; ++i) {
           const int p = 4 * h + cc + 8 * i;
           const int d = 32 * g + 8 * (p >> 3) + 7 - (p & 7);
-          o[4 * cc + i] = d < ix->dim ? q[d] : 0;
+          o[4 * cc + i] = d < ix->geom.dim ? q[d] : 0;
         }
     }
 }
@@ -133,8 +133,8 @@ static uint32_t fp6_code_of_eighths(int eighths) {
 }
 
 static void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q, int scale8) {
-  const int steps = ix->w16 * 2, group = q_in_batch / 32, n = q_in_batch % 32;
-  uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->w16, true);
+  const int steps = ix->geom.w16 * 2, group = q_in_batch / 32, n = q_in_batch % 32;
+  uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->geom.w16, true);
   uint8_t *gb2 = gb + (size_t)steps * 2 * 32 * 16;
   // the value x 8: q/2, q/4, q/8, q/2 at scale8 = 2 (products q/4: values up to 15); twice that for values up to 7 (scale8 = 4,
   // products q/2), four times for values up to 3 (scale8 = 8, products q): the finest grain e2m3's range (7.5) allows
@@ -150,12 +150,12 @@ static void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch
       uint8_t bits[24];
       for (int cls = 0; cls < 4; ++cls) {
         uint64_t v48 = 0;
-        if (base + 32 <= ix->dim) {
+        if (base + 32 <= ix->geom.dim) {
           for (int j = 0; j < 8; ++j) v48 |= (uint64_t)lut[cls][q[base + off[j] - cls] & 15] << (6 * j);
         } else {
           for (int j = 0; j < 8; ++j) {
             const int d = base + off[j] - cls;
-            v48 |= (uint64_t)lut[cls][d < ix->dim ? (q[d] & 15) : 0] << (6 * j);
+            v48 |= (uint64_t)lut[cls][d < ix->geom.dim ? (q[d] & 15) : 0] << (6 * j);
           }
         }
         for (int b = 0; b < 6; ++b) bits[6 * cls + b] = (uint8_t)(v48 >> (8 * b));
@@ -173,21 +173,21 @@ MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryPa
   m.scale8 = c.maxq <= 3 ? 8 : c.maxq <= 7 ? 4 : 2;  // products of scale8 / 8 * q: the accumulator's quarter-unit grain is 1, 1/2 or 1/4 of a qcDist unit
   const int groups = (nq + 31) / 32;
   m.off_qbytes = (bytes + 15) / 16 * 16;
-  const size_t qbytes_len = (size_t)groups * (size_t)mfma_query_bytes_per_group(ix->w16, m.fp);
+  const size_t qbytes_len = (size_t)groups * (size_t)mfma_query_bytes_per_group(ix->geom.w16, m.fp);
   m.off_qmax = m.off_qbytes + qbytes_len;
   m.bytes = m.off_qmax + (size_t)groups * 16;
   memset(h_qbuf + m.off_qbytes, 0, qbytes_len);
   float *qm = reinterpret_cast<float *>(h_qbuf + m.off_qmax);
   for (int i = 0; i < 4 * groups; ++i) qm[i] = 0.f;
   for (int i = 0; i < nq; ++i) {
-    const uint8_t *qv = c.qquant + (size_t)(q_first + i) * ix->dim;
+    const uint8_t *qv = c.qquant + (size_t)(q_first + i) * ix->geom.dim;
     if (m.fp) fill_query_mfma_fp(ix, h_qbuf + m.off_qbytes, i, qv, m.scale8);
     else fill_query_mfma(ix, h_qbuf + m.off_qbytes, i, qv);
     float *g = qm + 4 * (i / 32);
     // upper bounds (rounded up) of the group's |ay / ly|, |y1|, 1 / (cs * ly) and of the sum of a query's values (the largest
     // qcDist there can be, whatever y1 the caller passed)
     double qsum = 0;
-    for (int d = 0; d < ix->dim; ++d) qsum += qv[d];
+    for (int d = 0; d < ix->geom.dim; ++d) qsum += qv[d];
     g[0] = std::max(g[0], (float)(fabs(hq[i].ay / hq[i].ly) * 1.000001));
     g[1] = std::max(g[1], (float)(fabs(hq[i].y1) * 1.000001));
     g[2] = std::max(g[2], (float)(1.0 / ((c.sim == 0 ? 2.0 : 1.0) * hq[i].ly) * 1.000001));
@@ -212,7 +212,7 @@ int validate_query_args(const bbq_index *ix, int32_t nq, const uint8_t *qquant, 
   if (query_bits < 1 || query_bits > 8) return fail(BBQ_ERR_INVALID_ARG, "queryBits必须在1-8之间");
   if (sim < 0 || sim > 2) return fail(BBQ_ERR_INVALID_ARG, "不支持的相似性函数: %d", sim);
   if (query_bits == 1 && !values_pending)  // (values_pending: the library's own quantizer is still producing them)
-    for (int64_t i = 0; i < (int64_t)nq * ix->dim; ++i)
+    for (int64_t i = 0; i < (int64_t)nq * ix->geom.dim; ++i)
       if (qquant[i] > 1) return fail(BBQ_ERR_INVALID_ARG, "1位量化值必须为0或1");
   return BBQ_OK;
 }

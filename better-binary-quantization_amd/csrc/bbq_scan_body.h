@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
   constexpr bool DENSE = (MODE & 1) != 0;
   constexpr bool COMPACT = (MODE & 2) != 0;
   constexpr int QU = query_units_per_chunk(QB, SB);
-  const int w16 = W > 0 ? W : a.idx.w16;
+  const int w16 = W > 0 ? W : a.idx.geom.w16;
   u32x4 *s_planes = reinterpret_cast<u32x4 *>(smem);
   uint64_t *s_ent = reinterpret_cast<uint64_t *>(smem + (size_t)w16 * QU * 16);
   // with a flood tier every passing row of the chunk is staged (it may have to move to the overflow area as a whole)
@@ -124,8 +124,8 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
   bool nan_seen = false;
 
   if (tile < n_tiles && (!FILT || aw != 0)) {  // wave-uniform
-    const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.tile_stride;
-    const uint8_t *__restrict__ cr = tp + (size_t)w16 * (kTileRows * 16);
+    const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
+    const uint8_t *__restrict__ cr = tp + tile_corr_offset(w16);
     const int64_t row = tile * kTileRows + lane;
     const bool valid = row < a.idx.n_rows && (!FILT || ((aw >> lane) & 1ull) != 0);
     const bool resident = chunk_is_resident(chunk, a.idx);
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
     constexpr int CORR = !COMPACT ? 2 : (DENSE ? 0 : 1);
     if constexpr (W > 0) {
       u32x4 c[W];
-      load_tile<W, CORR>(tp, lane, a.idx.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
+      load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
       if constexpr (COMPACT && DENSE) exact_corrections<true>(a.idx.exact, row, lu, xadd);
       if constexpr (COMPACT && !DENSE) aadd = tile_add_bound(a.idx, tile, p.sim);
       if constexpr (SB == 1) qc = tile_popcounts<QB, W>(c, s_planes, ones);
@@ -147,8 +147,8 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
     } else {  // a row width without a compiled kernel: streamed chunk by chunk
       if constexpr (!COMPACT) {
         lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(cr) + lane);
-        xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + 1024) + lane);
-        if (a.idx.has_x1) x1 = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + 1536) + lane);
+        xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + kCorrAddOffset) + lane);
+        if (a.idx.geom.has_x1) x1 = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + kCorrSumOffset) + lane);
       } else if constexpr (DENSE) {
         exact_corrections<true>(a.idx.exact, row, lu, xadd);
       } else {
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
       if constexpr (SB == 1) qc = tile_popcounts_any<QB>(tp, lane, w16, s_planes, ones);
       else tile_dot_multibit_any<QB, SB>(tp, lane, w16, s_planes, qc, ones);
     }
-    if (!a.idx.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
+    if (!a.idx.geom.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
 
     bool need_exact = true;
     if constexpr (COMPACT && !DENSE) {
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
 
 template <bool FILT, int QB, int W, int MODE, int SB = 1>
 static hipError_t launch_scan_t(const ScanArgs &a, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s) {
-  const int w16 = W > 0 ? W : a.idx.w16;
+  const int w16 = W > 0 ? W : a.idx.geom.w16;
   const size_t smem = (size_t)w16 * query_units_per_chunk(QB, SB) * 16 + ((MODE & 1) ? 0 : (size_t)((a.ovf || a.append_lists) ? kChunkRows : a.cap) * 8) + 16;
   dim3 grid((unsigned)n_chunks, (unsigned)n_queries, 1), block(kChunkRows, 1, 1);
   if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, const uint64_t *>), grid, block, smem, s, a, accept);
@@ -242,7 +242,7 @@ static hipError_t launch_scan_t(const ScanArgs &a, const uint64_t *accept, int n
 // multi-bit rows: compile-time widths for 768-d / 1024-d at 2 bits (12 / 16 chunks; 16 is also 512-d at 4 bits), runtime loop otherwise
 template <bool FILT, int QB, int MODE, int SB>
 static hipError_t launch_scan_mb_w(const ScanArgs &a, const uint64_t *accept, int nq, int nc, hipStream_t s) {
-  switch (a.idx.w16) {
+  switch (a.idx.geom.w16) {
     case 12: return launch_scan_t<FILT, QB, 12, MODE, SB>(a, accept, nq, nc, s);
     case 16: return launch_scan_t<FILT, QB, 16, MODE, SB>(a, accept, nq, nc, s);
     default: return launch_scan_t<FILT, QB, 0, MODE, SB>(a, accept, nq, nc, s);
@@ -250,7 +250,7 @@ static hipError_t launch_scan_mb_w(const ScanArgs &a, const uint64_t *accept, in
 }
 template <bool FILT, int MODE>
 static hipError_t launch_scan_mb(const ScanArgs &a, const uint64_t *accept, int planes, int nq, int nc, hipStream_t s) {
-  switch (a.idx.store_bits) {
+  switch (a.idx.geom.store_bits) {
     case 2: return planes > 4 ? launch_scan_mb_w<FILT, 8, MODE, 2>(a, accept, nq, nc, s) : launch_scan_mb_w<FILT, 4, MODE, 2>(a, accept, nq, nc, s);
     case 4: return planes > 4 ? launch_scan_mb_w<FILT, 8, MODE, 4>(a, accept, nq, nc, s) : launch_scan_mb_w<FILT, 4, MODE, 4>(a, accept, nq, nc, s);
     case 8: return launch_scan_t<FILT, 8, 0, MODE, 8>(a, accept, nq, nc, s);
@@ -260,7 +260,7 @@ static hipError_t launch_scan_mb(const ScanArgs &a, const uint64_t *accept, int 
 
 template <bool FILT, int QB, int MODE>
 static hipError_t launch_scan_w(const ScanArgs &a, const uint64_t *accept, int nq, int nc, hipStream_t s) {
-  switch (a.idx.w16) {
+  switch (a.idx.geom.w16) {
     case 1: return launch_scan_t<FILT, QB, 1, MODE>(a, accept, nq, nc, s);    // dim <= 128
     case 6: return launch_scan_t<FILT, QB, 6, MODE>(a, accept, nq, nc, s);    // dim 768
     case 8: return launch_scan_t<FILT, QB, 8, MODE>(a, accept, nq, nc, s);    // dim 1024
