@@ -11,38 +11,6 @@ using namespace bbq;
 
 namespace {
 
-// what an append can work on: a single-device root index without a pilot replica (the scope of the filters)
-int check_append_index(const bbq_index *ix, int64_t n, const char *who) {
-  if (!ix) return fail(BBQ_ERR_INVALID_ARG, "%s: null handle", who);
-  if (n < 0) return fail(BBQ_ERR_INVALID_ARG, "%s: n < 0", who);
-  if (ix->multi) return fail(BBQ_ERR_UNSUPPORTED, "%s is not supported on a multi-device index", who);
-  if (ix->has_pilot || ix->row_base != 0) return fail(BBQ_ERR_UNSUPPORTED, "%s is not supported on a row shard or an index with a pilot replica", who);
-  if (ix->n_rows + n > 0xFFFFFFFFll) return fail(BBQ_ERR_UNSUPPORTED, "more than 2^32 rows");
-  return BBQ_OK;
-}
-
-// the index made quiet: nothing of it in flight on the device.  Context mutex held, device current.
-int quiesce(bbq_index *ix, const char *who) {
-  if (ix->shard_begun != ix->shard_waited)
-    return fail(BBQ_ERR_INVALID_ARG, "%s: a bbq_shard_scan_begin batch of this index has not been waited for", who);
-  int rc = settle_shard_slots(ix->ctx, ix);
-  if (rc != BBQ_OK) return rc;
-  rc = drain(ix);
-  if (rc != BBQ_OK) return rc;
-  HIPCHK(hipStreamSynchronize(ix->ctx->aux_stream));
-  return BBQ_OK;
-}
-
-// the one function that allocates tile records: d_tiles and, for the compact layout, the side arrays for `cap` tiles
-int alloc_tiles(const bbq_index *ix, int64_t cap, DevBuf<uint8_t> &tiles, DevBuf<double> &exact) {
-  if (tiles.alloc((size_t)(cap * ix->geom.tile_stride)) != hipSuccess ||
-      (ix->geom.layout == kLayoutCompact && exact.alloc((size_t)compact_side_bytes(cap) / 8) != hipSuccess)) {
-    (void)hipGetLastError();
-    return fail(BBQ_ERR_OOM, "no device memory for %lld rows (%lld bytes of tiles)", (long long)(cap * kTileRows), (long long)(cap * ix->geom.tile_stride));
-  }
-  return BBQ_OK;
-}
-
 // host rows -> device scratch
 int stage_rows(const bbq_index *ix, const uint8_t *codes, const double *corr, int64_t n, DevBuf<uint8_t> &d_codes, DevBuf<double> &d_corr) {
   const int64_t pb = caller_row_bytes(ix);
@@ -53,15 +21,6 @@ int stage_rows(const bbq_index *ix, const uint8_t *codes, const double *corr, in
   }
   HIPCHK(hipMemcpyAsync(d_codes, codes, (size_t)(n * pb), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(d_corr, corr, (size_t)n * 32, hipMemcpyHostToDevice, s));
-  return BBQ_OK;
-}
-
-// what every write of the rows [row0, total) into `room` ends with: each touched tile's range of additive corrections (compact layout),
-// then the device has completed and the rows may be committed
-int finish_rows(const bbq_index *ix, const Room &room, int64_t row0, int64_t total) {
-  hipStream_t s = ix->ctx->aux_stream;
-  if (ix->geom.layout == kLayoutCompact) HIPCHK(launch_tile_add_range(room.d_exact, total, room.d_add_range, s, row0 / kTileRows));
-  HIPCHK(hipStreamSynchronize(s));
   return BBQ_OK;
 }
 
@@ -133,6 +92,47 @@ int append_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const
 }  // namespace
 
 namespace bbq {
+
+// what an append can work on: a single-device root index without a pilot replica (the scope of the filters)
+int check_append_index(const bbq_index *ix, int64_t n, const char *who) {
+  if (!ix) return fail(BBQ_ERR_INVALID_ARG, "%s: null handle", who);
+  if (n < 0) return fail(BBQ_ERR_INVALID_ARG, "%s: n < 0", who);
+  if (ix->multi) return fail(BBQ_ERR_UNSUPPORTED, "%s is not supported on a multi-device index", who);
+  if (ix->has_pilot || ix->row_base != 0) return fail(BBQ_ERR_UNSUPPORTED, "%s is not supported on a row shard or an index with a pilot replica", who);
+  if (ix->n_rows + n > 0xFFFFFFFFll) return fail(BBQ_ERR_UNSUPPORTED, "more than 2^32 rows");
+  return BBQ_OK;
+}
+
+// the index made quiet: nothing of it in flight on the device.  Context mutex held, device current.
+int quiesce(bbq_index *ix, const char *who) {
+  if (ix->shard_begun != ix->shard_waited)
+    return fail(BBQ_ERR_INVALID_ARG, "%s: a bbq_shard_scan_begin batch of this index has not been waited for", who);
+  int rc = settle_shard_slots(ix->ctx, ix);
+  if (rc != BBQ_OK) return rc;
+  rc = drain(ix);
+  if (rc != BBQ_OK) return rc;
+  HIPCHK(hipStreamSynchronize(ix->ctx->aux_stream));
+  return BBQ_OK;
+}
+
+// the one function that allocates tile records: d_tiles and, for the compact layout, the side arrays for `cap` tiles
+int alloc_tiles(const bbq_index *ix, int64_t cap, DevBuf<uint8_t> &tiles, DevBuf<double> &exact) {
+  if (tiles.alloc((size_t)(cap * ix->geom.tile_stride)) != hipSuccess ||
+      (ix->geom.layout == kLayoutCompact && exact.alloc((size_t)compact_side_bytes(cap) / 8) != hipSuccess)) {
+    (void)hipGetLastError();
+    return fail(BBQ_ERR_OOM, "no device memory for %lld rows (%lld bytes of tiles)", (long long)(cap * kTileRows), (long long)(cap * ix->geom.tile_stride));
+  }
+  return BBQ_OK;
+}
+
+// what every write of the rows [row0, total) into `room` ends with: each touched tile's range of additive corrections (compact layout),
+// then the device has completed and the rows may be committed
+int finish_rows(const bbq_index *ix, const Room &room, int64_t row0, int64_t total) {
+  hipStream_t s = ix->ctx->aux_stream;
+  if (ix->geom.layout == kLayoutCompact) HIPCHK(launch_tile_add_range(room.d_exact, total, room.d_add_range, s, row0 / kTileRows));
+  HIPCHK(hipStreamSynchronize(s));
+  return BBQ_OK;
+}
 
 int make_room(bbq_index *ix, Storage &st, int64_t need_tiles, Room &r, bool geometric) {
   if (need_tiles <= st.cap_tiles) {

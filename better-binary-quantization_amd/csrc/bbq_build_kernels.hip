@@ -17,6 +17,8 @@
 //   retile         row-major rows (packed 1-bit, or one byte per dimension) + corrections -> tile records
 //   check_x1       is every quantizedComponentSum the implied one (popcount / code sum)?   check_code_range: every multi-bit code in range?
 //   tile_add_range compact layout: each tile's {min, max} of additionalCorrection
+// and rows that are in tile records already:
+//   compact_tiles  the records gathered down to the rows a filter accepts, out of place (bbq_index_compact)
 // Every writer takes its destination as a TileDest and writes a row's corrections through write_corrections.
 //
 // All arithmetic follows the JavaScript number model; -ffp-contract=off.
@@ -534,6 +536,46 @@ __global__ __launch_bounds__(256) void bbq_untile_kernel(TileDest src, int64_t n
   }
 }
 
+// ------------------------------------------------------------------------------------------------ compact (tile records -> tile records)
+// The records of `src` gathered down to the rows a filter accepts (DESIGN.md "Removing rows"), out of place: a destination row never
+// lies behind its source row, so in place one workgroup would overwrite a tile another still has to read.  One wave per destination
+// tile, lane l owns new row 64 T + l: it finds its old row (compact_source_row, bbq_device.h), gathers the row's w16 code chunks -
+// 16-byte loads that are neighbours in the source wherever neighbours are kept, read once and therefore non-temporal; each store
+// is 1 KiB per wave, coalesced - and its corrections, which go out through write_corrections: the compact word is the same function of
+// {lower, upper} it was when the row was first written.  Lanes from `kept` to the end of the last tile are padding, as
+// bbq_retile_kernel leaves them.  src and out share one geometry.
+__global__ __launch_bounds__(256) void bbq_compact_tiles_kernel(TileDest out, TileDest src, CompactMap map) {
+  const int lane = threadIdx.x & 63, w16 = out.geom.w16;
+  const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t R0 = tile * kTileRows, R = R0 + lane;
+  if (R0 >= map.kept) return;  // uniform per wave: grid padding
+  const bool valid = R < map.kept;
+  const int64_t srow = valid ? compact_source_row(map, R0, R) : 0;
+  const uint8_t *sp = src.tiles + (srow / kTileRows) * (int64_t)src.geom.tile_stride;
+  const int sl = (int)(srow % kTileRows);
+  u32x4 *dp = reinterpret_cast<u32x4 *>(out.tiles + tile * (int64_t)out.geom.tile_stride);
+  for (int j = 0; j < w16; ++j) {
+    u32x4 c = {0, 0, 0, 0};
+    if (valid) c = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(sp) + tile_chunk_index(j, sl));
+    dp[tile_chunk_index(j, lane)] = c;
+  }
+  f64x2 lu = {0.0, 0.0};
+  double add = 0.0, x1 = 0.0;
+  if (valid) {
+    if (src.geom.layout == kLayoutCompact) {
+      const double *e = src.exact + srow * 4;
+      lu = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(e));
+      add = __builtin_nontemporal_load(e + 2);
+    } else {
+      const uint8_t *cr = sp + tile_corr_offset(w16);
+      lu = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(cr) + sl);
+      add = __builtin_nontemporal_load(reinterpret_cast<const double *>(cr + kCorrAddOffset) + sl);
+      if (src.geom.has_x1) x1 = __builtin_nontemporal_load(reinterpret_cast<const double *>(cr + kCorrSumOffset) + sl);
+    }
+  }
+  write_corrections(out, R, lu, add, x1);
+}
+
 // ------------------------------------------------------------------------------------------------ launch wrappers
 
 hipError_t launch_build_transpose(const float *in, int64_t n, int32_t dim, int64_t npad, float *vT4, hipStream_t s) {
@@ -585,6 +627,13 @@ hipError_t launch_retile(const TileDest &out, const StagedRows &in, int64_t n_ro
   const int64_t threads = (n_pad - row0) * (out.geom.w16 + 1);
   if (threads <= 0) return hipSuccess;
   hipLaunchKernelGGL(bbq_retile_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, out, in, n_rows, n_pad, row0, index_bits, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_compact_tiles(const TileDest &out, const TileDest &src, const CompactMap &map, hipStream_t s) {
+  const int64_t n_tiles = (map.kept + kTileRows - 1) / kTileRows;
+  if (n_tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_compact_tiles_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, out, src, map);
   return hipGetLastError();
 }
 

@@ -100,6 +100,45 @@ struct StagedRows {
   const double *corr;
 };
 
+// A compaction (DESIGN.md "Removing rows"): which old row becomes new row R.  accept[t] is the accept word of source tile t (bit l =
+// lane l, clear beyond the last row: a bbq_filter's d_bits), rank[t] the accepted rows in front of tile t, rank[src_tiles] = kept.
+struct CompactMap {
+  const uint64_t *accept;  // [src_tiles]
+  const uint32_t *rank;    // [src_tiles + 1] exclusive prefix of the words' popcounts
+  int64_t src_tiles;
+  int64_t kept;            // |A| = rows afterwards
+};
+// the source tile of new row R < kept: the t in [lo, hi] with rank[t] <= R < rank[t + 1] (the caller knows it lies in that range)
+__device__ __forceinline__ int64_t compact_source_tile(const CompactMap &m, int64_t R, int64_t lo, int64_t hi) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)m.rank[mid + 1] <= R) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// position of the k-th (from 0) set bit of w; w has more than k bits set
+__device__ __forceinline__ int select_bit64(uint64_t w, int k) {
+  int pos = 0;
+  uint32_t x = (uint32_t)w;
+  int c = __popc(x);
+  if (k >= c) { k -= c; pos = 32; x = (uint32_t)(w >> 32); }
+#pragma unroll
+  for (int width = 16; width >= 1; width >>= 1) {
+    c = __popc(x & ((1u << width) - 1u));
+    if (k >= c) { k -= c; pos += width; x >>= width; }
+  }
+  return pos;
+}
+// the old row behind new row R < kept, for the lanes of one wave that own 64 consecutive new rows [R0, R0 + 64): the wave's first and
+// last row bound every lane's search, and both are uniform
+__device__ __forceinline__ int64_t compact_source_row(const CompactMap &m, int64_t R0, int64_t R) {
+  const int64_t last = (R0 + kTileRows <= m.kept ? R0 + kTileRows : m.kept) - 1;
+  const int64_t t_lo = compact_source_tile(m, R0, 0, m.src_tiles - 1);
+  const int64_t t_hi = compact_source_tile(m, last, t_lo, m.src_tiles - 1);
+  const int64_t t = compact_source_tile(m, R, t_lo, t_hi);
+  return t * kTileRows + select_bit64(m.accept[t], (int)(R - (int64_t)m.rank[t]));
+}
+
 struct IndexView {
   const uint8_t *tiles;
   const double *exact;  // kLayoutCompact: [n_rows padded to 64][4]

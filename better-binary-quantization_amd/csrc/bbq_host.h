@@ -7,6 +7,7 @@
 //   bbq_multi.cpp    one index over several devices of a process
 //   bbq_append.cpp   the one path that writes rows into an index - creation and build are appends to an empty one - and the entry
 //                    points that grow an index in place (bbq_index_append*, bbq_index_reserve)
+//   bbq_compact.cpp  rows taken out of an index on the device (bbq_index_compact, bbq_index_remove_rows, bbq_filter_kept_rows)
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
@@ -286,6 +287,17 @@ inline TileDest scratch_tile_dest(const bbq_index *ix, uint8_t *tiles) {
   g.tile_stride = tile_stride_of(g.w16, g.layout, g.has_x1);
   return TileDest{tiles, nullptr, g};
 }
+// what can be written to: a single-device root index without a pilot replica that stays below 2^32 rows with n more (the scope of the
+// filters); `who` names the entry point in the message
+int check_append_index(const bbq_index *ix, int64_t n, const char *who);
+// the index made quiet: nothing of it in flight on the device (BBQ_ERR_INVALID_ARG while a bbq_shard_scan_begin batch has not been
+// waited for).  Context mutex held, device current.
+int quiesce(bbq_index *ix, const char *who);
+// the one function that allocates tile records: d_tiles and, for the compact layout, the side arrays for `cap` tiles (BBQ_ERR_OOM)
+int alloc_tiles(const bbq_index *ix, int64_t cap, DevBuf<uint8_t> &tiles, DevBuf<double> &exact);
+// what every write of the rows [row0, total) into `room` ends with: the touched tiles' add ranges (compact layout), then the device has
+// completed and the rows may be committed
+int finish_rows(const bbq_index *ix, const Room &room, int64_t row0, int64_t total);
 // geometric: half as much again as the capacity, at least what is needed (an empty storage gets exactly what is needed); otherwise
 // exactly what is needed.  BBQ_ERR_OOM without device memory.
 int make_room(bbq_index *ix, Storage &st, int64_t need_tiles, Room &r, bool geometric = true);

@@ -58,8 +58,13 @@ hipError_t launch_check_x1(const StagedRows &in, int64_t n_rows, const TileGeom 
 hipError_t launch_check_code_range(const uint8_t *codes, int64_t count, int32_t index_bits, uint32_t *bad, hipStream_t s);
 // compact layout: each tile's {min, max} of additionalCorrection (read from exact[]) -> add_range[tile][2]
 hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0);
+// the rows of `src` that map.accept keeps -> the rows [0, map.kept) of `out`, in order, padding lanes of the last tile included.  `out`
+// holds ceil(map.kept / 64) tiles of src's geometry and is not src (the gather runs out of place)
+hipError_t launch_compact_tiles(const TileDest &out, const TileDest &src, const CompactMap &map, hipStream_t s);
 
 // exact rerank (bbq_rerank_kernels.hip): one wave per 64 candidates of a query; max_count = longest candidate list
 hipError_t launch_rerank(const RerankArgs &a, int n_queries, int64_t max_count, hipStream_t s);
+// the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
+hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 
 }  // namespace bbq

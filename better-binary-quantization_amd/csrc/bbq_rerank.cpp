@@ -6,7 +6,7 @@
 #include <string.h>
 #include <memory>
 #include <string>
-#include "bbq_host.h"
+#include "bbq_search.h"
 
 using namespace bbq;
 
@@ -118,6 +118,34 @@ int bbq_vectors_append(bbq_vectors *v, const float *vectors, int64_t n) {
   HIPCHK(hipSetDevice(v->device));
   HIPCHK(hipStreamSynchronize(v->ctx->aux_stream));  // bbq_rerank_scores reads the rows on it
   return append_vectors(v, vectors, n, "bbq_vectors_append");
+}
+
+int bbq_vectors_compact(bbq_vectors *v, const bbq_filter *f) {
+  clear_error();
+  if (!v || !f) return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_compact: null handle");
+  if (f->device != v->device || f->ctx != v->ctx) return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_compact: the filter lives on another device than the vectors");
+  std::lock_guard<std::mutex> lk(v->ctx->mu);
+  HIPCHK(hipSetDevice(v->device));
+  if (f->n_rows != v->n)
+    return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_compact: the filter was made for %lld rows, the handle holds %lld", (long long)f->n_rows, (long long)v->n);
+  const int64_t kept = f->count;
+  if (kept == v->n) return BBQ_OK;
+  HIPCHK(hipStreamSynchronize(v->ctx->aux_stream));  // bbq_rerank_scores reads the rows on it
+  // out of place, as the index is compacted: exactly the kept rows afterwards, the old rows released behind the gather
+  DevBuf<float> kept_rows;
+  if (kept > 0) {
+    const hipError_t e = kept_rows.alloc((size_t)(kept * v->dim));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "bbq_vectors_compact: %lld x %d fp32: %s", (long long)kept, v->dim, hipGetErrorString(e)); }
+    DevBuf<uint32_t> d_rank;
+    CompactMap map;
+    const int rc = stage_compact_map(f, d_rank, &map);
+    if (rc != BBQ_OK) return rc;
+    HIPCHK(launch_compact_vectors(kept_rows, v->d, v->dim, map, v->ctx->aux_stream));
+    HIPCHK(hipStreamSynchronize(v->ctx->aux_stream));
+  }
+  v->d = std::move(kept_rows);
+  v->n = kept;
+  return BBQ_OK;
 }
 
 int64_t bbq_vectors_size(const bbq_vectors *v) { return v ? v->n : 0; }

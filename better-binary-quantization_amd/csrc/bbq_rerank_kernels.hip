@@ -73,7 +73,31 @@ __global__ __launch_bounds__(64) void bbq_rerank_kernel(RerankArgs a) {
   if (valid) a.out[c0 + lane] = r;
 }
 
+// bbq_vectors_compact: the fp32 rows a filter accepts, gathered out of place.  One wave per destination row - its source row is
+// uniform across the wave (the rank / select of the tile compaction, bbq_device.h) - and the row moves as coalesced pieces: 16 bytes
+// per lane where the row length allows.  The source is read once: non-temporal.
+__global__ __launch_bounds__(256) void bbq_compact_vectors_kernel(float *__restrict__ out, const float *__restrict__ src, int32_t dim, CompactMap map) {
+  const int lane = threadIdx.x & 63;
+  const int64_t R = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (R >= map.kept) return;  // uniform per wave
+  const int64_t t = compact_source_tile(map, R, 0, map.src_tiles - 1);
+  const int64_t srow = t * kTileRows + select_bit64(map.accept[t], (int)(R - (int64_t)map.rank[t]));
+  const float *s = src + srow * dim;
+  float *d = out + R * dim;
+  if ((dim & 3) == 0) {
+    for (int c = lane; c < dim / 4; c += 64) reinterpret_cast<f32x4 *>(d)[c] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(s) + c);
+  } else {
+    for (int c = lane; c < dim; c += 64) d[c] = __builtin_nontemporal_load(s + c);
+  }
+}
+
 }  // namespace
+
+hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s) {
+  if (map.kept <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_compact_vectors_kernel, dim3((unsigned)((map.kept + 3) / 4)), dim3(256), 0, s, out, src, dim, map);
+  return hipGetLastError();
+}
 
 hipError_t launch_rerank(const RerankArgs &a, int n_queries, int64_t max_count, hipStream_t s) {
   if (n_queries <= 0 || max_count <= 0) return hipSuccess;

@@ -76,6 +76,9 @@ int drain(bbq_index *ix);
 // ---- bbq_latency.cpp: *done = false with BBQ_OK sends the call on to the next, more general path
 int search_latency_presampled(const SearchCall &c, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done);
 int search_latency_chain(const SearchCall &c, int32_t *out_idx, float *out_score, int64_t *out_n, bool *done);
+// ---- bbq_compact.cpp: the map of a compaction by `f` - its accept words as they are on the device, and the ranks of its tiles
+// uploaded into d_rank (BBQ_ERR_OOM).  Context mutex held, device current; returns with the ranks on the device.
+int stage_compact_map(const bbq_filter *f, DevBuf<uint32_t> &d_rank, CompactMap *map);
 // ---- bbq_dense.cpp
 int dense_search_one(const SearchCall &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n);
 

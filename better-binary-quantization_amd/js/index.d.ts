@@ -56,6 +56,13 @@ export declare class BinaryQuantizationFormat {
    *  device index grows in place.  Not supported on a multi-device index (BBQ_DEVICES).  A RowFilter made before the call no longer
    *  fits the index.  Returns targetVectors. */
   appendVectors(targetVectors: BinarizedByteVectorValues, vectors: Float32Array[]): BinarizedByteVectorValues;
+  /** extension: targetVectors becomes the set over the rows `filter` accepts, in order (new ord of old row r = accepted rows below r); a
+   *  device copy is compacted on the device, the host copies follow.  `filter`: a RowFilter of targetVectors or anything createRowFilter
+   *  takes.  Not supported on a multi-device index (BBQ_DEVICES).  The filter used and every RowFilter made earlier no longer fit the
+   *  index.  Returns targetVectors. */
+  compactVectors(targetVectors: BinarizedByteVectorValues, filter: RowFilter | Uint8Array | Int32Array | number[] | ((ord: number) => boolean)): BinarizedByteVectorValues;
+  /** extension: drop the rows `ords` (any order, duplicates allowed): compactVectors over the complement.  Returns targetVectors. */
+  removeVectors(targetVectors: BinarizedByteVectorValues, ords: ArrayLike<number>): BinarizedByteVectorValues;
   quantizeQueryVector(queryVector: Float32Array, centroid: Float32Array): { quantizedQuery: Uint8Array; queryCorrections: QuantizationResult };
   searchNearestNeighbors(queryVector: Float32Array, targetVectors: BinarizedByteVectorValues, k: number): Array<{ index: number; score: number }>;
   /** extension: many independent queries per call, pipelined on the device */
@@ -104,6 +111,8 @@ export declare class DeviceVectors {
   trueScores(query: Float32Array, rows: ArrayLike<number>, similarityFunction?: VectorSimilarityFunction): Float64Array;
   /** extension: the fp32 rows of a block BinaryQuantizationFormat.appendVectors has added to the index get the next ords */
   append(vectors: Float32Array[]): DeviceVectors;
+  /** extension: the fp32 rows follow BinaryQuantizationFormat.compactVectors: the rows `filter` accepts are kept, in order, on the device */
+  compact(filter: RowFilter): DeviceVectors;
   dispose(): void;
 }
 export declare function createDeviceVectors(vectors: Float32Array[], device?: number): DeviceVectors;

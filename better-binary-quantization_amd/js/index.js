@@ -124,6 +124,22 @@ class BinarizedByteVectorValuesImpl {
     if (!this._rowBytes && n > 0) this._rowBytes = codes.length / n;
     this._size += n;
   }
+  /** the host copies follow a compaction - the rows `mask` keeps, in order - or (no mask: the accept set is on the device alone) are left to be fetched again: never a stale copy */
+  _compacted(mask, kept) {
+    if (!mask) {
+      if (kept !== this._size) this._codes = this._corr = null;
+    } else if (this._codes) {
+      const rb = this._rowBytes, c = new Uint8Array(kept * rb), r = new Float64Array(kept * 4);
+      for (let i = 0, o = 0; i < mask.length; i++) {
+        if (!mask[i]) continue;
+        c.set(this._codes.subarray(i * rb, (i + 1) * rb), o * rb);
+        r.set(this._corr.subarray(4 * i, 4 * i + 4), 4 * o);
+        o++;
+      }
+      this._codes = c; this._corr = r;
+    }
+    this._size = kept;
+  }
   /** tuning knobs of the device index (libbbq bbq_set_option), e.g. ('sweep_share', 32) for searchNearestNeighborsBatch */
   setDeviceOption(name, value) { native.setOption(this._deviceIndex(), name, value); }
   deviceStats() { return native.stats(this._deviceIndex()); }
@@ -465,6 +481,46 @@ class BinaryQuantizationFormat {
     return targetVectors;
   }
 
+  /**
+   * extension (not in the reference): targetVectors becomes the set over the rows `filter` accepts, in order - the new ord of old row r is
+   * the number of accepted rows below r.  `filter`: a RowFilter of targetVectors (createRowFilter) or anything createRowFilter takes (a
+   * Uint8Array mask, an Int32Array / array of ords, a predicate).  A device copy is compacted on the device (libbbq bbq_index_compact: the
+   * rows do not leave it, the memory of the removed rows is released) and the host copies follow; without a device copy the host rows are
+   * compacted alone.  Afterwards it is indistinguishable from the set quantizeVectors-then-selected would give: size(), vectorValue,
+   * getCorrectiveTerms, every search.  The filter used and every RowFilter made earlier no longer fit: make new ones.  A multi-device
+   * index (BBQ_DEVICES) throws the library's unsupported message.  On an error nothing has changed.  Returns targetVectors.
+   */
+  compactVectors(targetVectors, filter) {
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (filter === undefined || filter === null) throw new Error('行过滤器不能为空');
+    if (filter instanceof RowFilter) {
+      // the accept set lives on the device alone: the device copy is compacted and the host copies are left to be fetched again
+      targetVectors._compacted(null, native.indexCompact(targetVectors._deviceIndex(), filter._handle()));
+      return targetVectors;
+    }
+    const n = targetVectors.size(), mask = acceptMask(n, filter);
+    let kept = 0;
+    for (let i = 0; i < n; i++) if (mask[i]) kept++;
+    if (kept === n) return targetVectors;
+    if (targetVectors._device) {
+      const f = new RowFilter(targetVectors, mask);
+      try { native.indexCompact(targetVectors._device, f._handle()); } finally { f.dispose(); }
+    }
+    targetVectors._compacted(mask, kept);
+    return targetVectors;
+  }
+
+  /** extension: drop the rows `ords` (any order, duplicates allowed; an ord outside the set throws): compactVectors over the complement */
+  removeVectors(targetVectors, ords) {
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    const n = targetVectors.size(), mask = new Uint8Array(n).fill(1);
+    for (let i = 0; i < ords.length; i++) {
+      if (!Number.isInteger(ords[i]) || ords[i] < 0 || ords[i] >= n) throw new Error('向量索引 ' + ords[i] + ' 不存在');
+      mask[ords[i]] = 0;
+    }
+    return this.compactVectors(targetVectors, mask);
+  }
+
   /** quantizeQueryVector(queryVector, centroid) -> {quantizedQuery, queryCorrections}  (:271-299) */
   quantizeQueryVector(queryVector, centroid) {
     const q = this.quantizer;
@@ -801,11 +857,43 @@ class DeviceVectors {
     this.length += vectors.length;
     return this;
   }
+  /** extension: the fp32 rows follow a compaction of the index by the same RowFilter, on the device (libbbq bbq_vectors_compact) */
+  compact(filter) {
+    if (!(filter instanceof RowFilter)) throw new Error('compact needs createRowFilter(targetVectors, accept)');
+    this.length = native.vectorsCompact(this._handle(), filter._handle());
+    return this;
+  }
   _handle() { if (!this._h) throw new Error('向量不能为空'); return this._h; }
   dispose() { if (this._h) { native.vectorsDestroy(this._h); this._h = null; } }
 }
 function createDeviceVectors(vectors, device) { return new DeviceVectors(vectors, device); }
 
+// what createRowFilter and compactVectors take as an accept set, normalised: a Uint8Array mask over n rows or an Int32Array of ords
+function acceptArg(n, accept) {
+  let arg = accept;
+  if (typeof accept === 'function') {
+    arg = new Uint8Array(n);
+    for (let i = 0; i < n; i++) arg[i] = accept(i) ? 1 : 0;
+  } else if (Array.isArray(accept)) {
+    // Int32Array.from would wrap an ord outside int32 and drop a fraction: another row would be accepted in its place
+    for (let i = 0; i < accept.length; i++) if (!Number.isInteger(accept[i]) || accept[i] < 0 || accept[i] >= n) throw new Error('向量索引 ' + accept[i] + ' 不存在');
+    arg = Int32Array.from(accept);
+  }
+  if (!(arg instanceof Uint8Array) && !(arg instanceof Int32Array)) throw new Error('createRowFilter: accept is a Uint8Array mask, an Int32Array / array of ords, or a function');
+  if (arg instanceof Uint8Array && arg.length !== n) throw new Error('createRowFilter: a mask has one entry per vector');
+  return arg;
+}
+/** the same accept set as a Uint8Array mask over n rows (what compactVectors selects the host rows by) */
+function acceptMask(n, accept) {
+  const arg = acceptArg(n, accept);
+  if (arg instanceof Uint8Array) return arg;
+  const mask = new Uint8Array(n);
+  for (let i = 0; i < arg.length; i++) {
+    if (arg[i] < 0 || arg[i] >= n) throw new Error('向量索引 ' + arg[i] + ' 不存在');
+    mask[arg[i]] = 1;
+  }
+  return mask;
+}
 /**
  * extension (not in the reference): an accept set of the rows of `targetVectors`, resident on its device (libbbq bbq_filter_*), for
  * searchNearestNeighborsFiltered.  `accept`: a Uint8Array mask of length size() (non-zero = accepted), an Int32Array / array of ords
@@ -814,18 +902,7 @@ function createDeviceVectors(vectors, device) { return new DeviceVectors(vectors
 class RowFilter {
   constructor(targetVectors, accept) {
     if (!targetVectors) throw new Error('目标向量集合不能为空');
-    const n = targetVectors.size();
-    let arg = accept;
-    if (typeof accept === 'function') {
-      arg = new Uint8Array(n);
-      for (let i = 0; i < n; i++) arg[i] = accept(i) ? 1 : 0;
-    } else if (Array.isArray(accept)) {
-      // Int32Array.from would wrap an ord outside int32 and drop a fraction: another row would be accepted in its place
-      for (let i = 0; i < accept.length; i++) if (!Number.isInteger(accept[i]) || accept[i] < 0 || accept[i] >= n) throw new Error('向量索引 ' + accept[i] + ' 不存在');
-      arg = Int32Array.from(accept);
-    }
-    if (!(arg instanceof Uint8Array) && !(arg instanceof Int32Array)) throw new Error('createRowFilter: accept is a Uint8Array mask, an Int32Array / array of ords, or a function');
-    if (arg instanceof Uint8Array && arg.length !== n) throw new Error('createRowFilter: a mask has one entry per vector');
+    const arg = acceptArg(targetVectors.size(), accept);
     const r = native.filterCreate(targetVectors._deviceIndex(), arg);
     this._h = r.handle;
     this.count = r.count;

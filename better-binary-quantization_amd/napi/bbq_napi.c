@@ -417,6 +417,34 @@ static napi_value FilterDestroy(napi_env env, napi_callback_info info) {
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
+/* the filter behind a handle of filterCreate, or NULL with an exception pending */
+static const bbq_filter *unbox_filter(napi_env env, napi_value v, const char *who) {
+  void *fp = NULL;
+  if (napi_get_value_external(env, v, &fp) != napi_ok || !fp || !*(bbq_filter **)fp) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s: the filter is null", who);
+    napi_throw_error(env, "BBQ1", msg);
+    return NULL;
+  }
+  return *(bbq_filter **)fp;
+}
+
+/* indexCompact(index handle, filter handle) -> rows afterwards: the index becomes the index over the accepted rows, on the device
+ * (bbq_index_compact) */
+static napi_value IndexCompact(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  const bbq_filter *flt = unbox_filter(env, a[1], "bbq_index_compact");
+  if (!flt) return NULL;
+  int rc = bbq_index_compact(ix, flt);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value r;
+  NAPI_CALL(env, napi_create_double(env, (double)bbq_index_size(ix), &r));
+  return r;
+}
+
 /* searchFilteredBatch(index handle, filter handle, nq, qquant, qcorr, queryBits, sim, k) -> as searchBatch, rows strided by min(k, |A|) */
 static napi_value SearchFilteredBatch(napi_env env, napi_callback_info info) {
   napi_value a[8];
@@ -629,6 +657,21 @@ static napi_value VectorsAppend(napi_env env, napi_callback_info info) {
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
+/* vectorsCompact(vectors handle, filter handle) -> rows afterwards: the fp32 rows follow a compaction of the index (bbq_vectors_compact) */
+static napi_value VectorsCompact(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  bbq_vectors *v = unbox_vectors(env, a[0]);
+  if (!v) return NULL;
+  const bbq_filter *flt = unbox_filter(env, a[1], "bbq_vectors_compact");
+  if (!flt) return NULL;
+  int rc = bbq_vectors_compact(v, flt);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value r;
+  NAPI_CALL(env, napi_create_double(env, (double)bbq_vectors_size(v), &r));
+  return r;
+}
+
 /* vectorsDestroy(handle) */
 static napi_value VectorsDestroy(napi_env env, napi_callback_info info) {
   napi_value a[1];
@@ -825,6 +868,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"indexAppendRows", NULL, IndexAppendRows, NULL, NULL, NULL, napi_default, NULL},
       {"indexReserve", NULL, IndexReserve, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsAppend", NULL, VectorsAppend, NULL, NULL, NULL, napi_default, NULL},
+      {"indexCompact", NULL, IndexCompact, NULL, NULL, NULL, napi_default, NULL},
+      {"vectorsCompact", NULL, VectorsCompact, NULL, NULL, NULL, napi_default, NULL},
       {"searchBatch", NULL, SearchBatch, NULL, NULL, NULL, napi_default, NULL},
       {"filterCreate", NULL, FilterCreate, NULL, NULL, NULL, napi_default, NULL},
       {"filterDestroy", NULL, FilterDestroy, NULL, NULL, NULL, napi_default, NULL},

@@ -127,6 +127,50 @@ class BinaryQuantizationFormat:
         targetVectors._corr = np.concatenate([targetVectors._corr, corr])
         return targetVectors
 
+    def compactVectors(self, targetVectors, accept):
+        """extension: targetVectors becomes the set over the rows `accept` keeps - a bool mask of length size(), an array of ords, or
+        a predicate ord -> bool - in order: the new ord of old row r is the number of kept rows below r.  The resident index is
+        compacted on the device (bbq_index_compact; the rows do not leave it) and the host copies follow; without a device the host
+        copies alone.  Row filters made earlier no longer fit.  Returns targetVectors."""
+        if targetVectors is None:
+            raise Exception("目标向量集合不能为空")
+        n = targetVectors.size()
+        if callable(accept):
+            accept = np.fromiter((bool(accept(i)) for i in range(n)), np.bool_, n)
+        a = np.asarray(accept)
+        if a.dtype != np.bool_:
+            ords = np.asarray(a, np.int64).ravel()
+            bad = ords[(ords < 0) | (ords >= n)]
+            if bad.size:
+                raise Exception("向量索引 %d 不存在" % int(bad[0]))
+            a = np.zeros(n, np.bool_)
+            a[ords] = True
+        if a.shape != (n,):
+            raise Exception("a filter mask has one entry per row of the index")
+        try:
+            if targetVectors._device_index is not None:   # never a stale device copy: it is compacted with the host rows
+                with capi.Filter(targetVectors._device_index, a) as flt:
+                    targetVectors._device_index.compact(flt)
+            kept = capi.kept_rows(a)
+        except capi.BBQError as e:
+            raise Exception(str(e))
+        targetVectors._codes = targetVectors._codes[kept]
+        targetVectors._corr = targetVectors._corr[kept]
+        return targetVectors
+
+    def removeVectors(self, targetVectors, ords):
+        """extension: drop the rows `ords` (any order, duplicates allowed): compactVectors over the complement"""
+        if targetVectors is None:
+            raise Exception("目标向量集合不能为空")
+        n = targetVectors.size()
+        o = np.asarray(ords, np.int64).ravel()
+        bad = o[(o < 0) | (o >= n)]
+        if bad.size:
+            raise Exception("向量索引 %d 不存在" % int(bad[0]))
+        keep = np.ones(n, np.bool_)
+        keep[o] = False
+        return self.compactVectors(targetVectors, keep)
+
     def quantizeQueryVector(self, queryVector, centroid):
         qq, qc = capi.quantize_query(queryVector, centroid, capi.SIMS[self._sim], self._config["queryBits"], self._lambda,
                                      self._iters, search_path=False)

@@ -28,6 +28,7 @@ SYMBOLS = [
     "bbq_search_raw_batch",
     "bbq_filter_create", "bbq_filter_create_rows", "bbq_filter_destroy", "bbq_filter_count", "bbq_search_filtered_batch", "bbq_filter_plan",
     "bbq_index_append_rows", "bbq_index_append", "bbq_index_reserve", "bbq_index_capacity", "bbq_vectors_append", "bbq_quantize_rows",
+    "bbq_index_compact", "bbq_index_remove_rows", "bbq_vectors_compact", "bbq_filter_kept_rows",
 ]
 
 
@@ -149,6 +150,10 @@ def lib():
     L.bbq_index_capacity.argtypes = [vp]
     L.bbq_index_capacity.restype = i64
     L.bbq_vectors_append.argtypes = [vp, vp, i64]
+    L.bbq_index_compact.argtypes = [vp, vp]
+    L.bbq_index_remove_rows.argtypes = [vp, vp, i64]
+    L.bbq_vectors_compact.argtypes = [vp, vp]
+    L.bbq_filter_kept_rows.argtypes = [vp, i64, vp, i64, C.POINTER(i64)]
     L.bbq_quantize_rows.argtypes = [vp, i64, i32, vp, i32, i32, dbl, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(i32)]
     _lib = L
     return L
@@ -361,6 +366,18 @@ class Index:
         self.n = int(lib().bbq_index_size(self._h))
         return codes, corr
 
+    def compact(self, flt):
+        """bbq_index_compact: the index becomes the index over the rows `flt` (a Filter of this index) accepts, in order, on the
+        device.  The filter - and any made earlier - no longer fits afterwards; kept_rows(mask) tells the old ord of every new row."""
+        _chk(lib().bbq_index_compact(self._h, flt._h if flt is not None else None))
+        self.n = int(lib().bbq_index_size(self._h))
+
+    def remove_rows(self, rows):
+        """bbq_index_remove_rows: drop these ords (any order, duplicates allowed)"""
+        r = np.ascontiguousarray(np.asarray(rows, np.int64).ravel().clip(-2**31, 2**31 - 1), np.int32)
+        _chk(lib().bbq_index_remove_rows(self._h, _ptr(r), r.shape[0]))
+        self.n = int(lib().bbq_index_size(self._h))
+
     def reserve(self, rows):
         """room for `rows` rows in total without another reallocation (bbq_index_reserve)"""
         _chk(lib().bbq_index_reserve(self._h, int(rows)))
@@ -536,6 +553,16 @@ def filter_plan(mask, k_dev, first_segment_rows=4096, growth=8):
     return [tuple(int(v) for v in row) for row in segs[:n.value]]
 
 
+def kept_rows(mask):
+    """the old ord of every row a compaction by `mask` keeps, ascending (bbq_filter_kept_rows; host only)"""
+    m = np.ascontiguousarray(mask, np.bool_).ravel()
+    words = pack_mask(m)
+    out = np.zeros(m.shape[0], np.int32)
+    n = C.c_int64(0)
+    _chk(lib().bbq_filter_kept_rows(_ptr(words), m.shape[0], _ptr(out), out.shape[0], C.byref(n)))
+    return out[:n.value]
+
+
 class Filter:
     """an accept set of one Index, resident on its device (bbq_filter_*): `mask_or_rows` is a bool mask of length index.n or
     an integer array of row ids (any order, duplicates allowed).  Read-only after creation; any number of searches may share it."""
@@ -611,6 +638,11 @@ class Vectors:
         if v.ndim != 2 or v.shape[1] != self.dim:
             raise BBQError(ERR_DIM_MISMATCH, "向量维度不匹配")
         _chk(lib().bbq_vectors_append(self._h, _ptr(v), v.shape[0]))
+        self.n = int(lib().bbq_vectors_size(self._h))
+
+    def compact(self, flt):
+        """bbq_vectors_compact: the fp32 rows follow a compaction of the index by the same filter"""
+        _chk(lib().bbq_vectors_compact(self._h, flt._h if flt is not None else None))
         self.n = int(lib().bbq_vectors_size(self._h))
 
     def rerank_scores(self, queries, rows_per_query, true_sim=1):

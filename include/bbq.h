@@ -33,7 +33,8 @@ extern "C" {
 #define BBQ_ABI_VERSION 3  /* 2: multi-bit and multi-device indexes, bbq_stats.host_replays
                               3: creation options (corrections layout), asynchronous shard scans with shard-local answers,
                                  bbq_merge_answers, persistence of shards and multi-device indexes
-                              (still 3: filtered search - bbq_filter_*, bbq_search_filtered_batch - only adds symbols) */
+                              (still 3: filtered search - bbq_filter_*, bbq_search_filtered_batch - only adds symbols, as do the appends
+                              and the compaction - bbq_index_compact, bbq_index_remove_rows, bbq_vectors_compact, bbq_filter_kept_rows) */
 
 /* status codes */
 enum {
@@ -269,6 +270,37 @@ int bbq_filter_plan(const uint64_t *accept_bits, int64_t n_rows, int64_t k_dev, 
 int bbq_search_filtered_batch(bbq_index *idx, const bbq_filter *f, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
                               int32_t query_bits, int32_t sim, int64_t k, int32_t *out_idx, float *out_score, int64_t *out_n);
 
+/* ------------------------------------------------------------------------------------------
+ * Removing rows (new; the reference's index is immutable): a compaction makes the index the index over the rows a filter accepts,
+ * in order, without the rows leaving the device.  New ord of old row r = the number of accepted rows below r.  After
+ * bbq_index_compact(idx, f) the index is indistinguishable from one created whole (bbq_index_create_opts) over the kept rows with
+ * the same centroid_dp, index_bits and options: bbq_index_size == bbq_filter_count(f), bbq_index_capacity is whole tiles of exactly
+ * that many rows, every search entry point (indices, f32 score bits, order, ties), bbq_score_rows, rerank, bbq_shard_scan* on a root
+ * index, filtered search with a filter made afterwards, bbq_index_export, the bytes bbq_index_save writes (padding lanes of the last
+ * tile and every tile's add range included), and a later append.
+ * The record format is never re-decided by a compaction.  An index without explicit component sums - every built index and the
+ * normal created one - has its files equal the twin's unconditionally.  An index that stores explicit sums keeps storing them: its
+ * files equal the twin's exactly when the twin's own creation decides to store them, that is when a kept row still needs it; its
+ * answers and its export always match.
+ * Every row kept (|A| == size): BBQ_OK and nothing changes, capacity included.  |A| == 0: the index of zero rows.
+ * Strong guarantee: a call that fails - a filter of another size or device (BBQ_ERR_INVALID_ARG), out of memory (BBQ_ERR_OOM), a
+ * bbq_shard_scan_begin batch of this index that has not been waited for (BBQ_ERR_INVALID_ARG) - leaves the index exactly as it was.
+ * The rows are gathered OUT OF PLACE into new allocations and the old ones are released behind the gather: the peak is old + new,
+ * and afterwards the memory of the removed rows is free.
+ * Out of scope (BBQ_ERR_UNSUPPORTED), as for filters and appends: a multi-device handle, a non-root shard, an index with a pilot
+ * replica.  Updating a row in place and re-centring are not offered.  The call takes the device context's lock and first retires what
+ * the index has in flight, as an append does.
+ * The filter used, and any filter made earlier, no longer fits the new size: bbq_search_filtered_batch refuses it
+ * (BBQ_ERR_INVALID_ARG); make a new filter over the compacted index. */
+/* keep the rows f accepts, ascending; new ord of old row r = number of accepted rows below r */
+int bbq_index_compact(bbq_index *idx, const bbq_filter *f);
+/* convenience: drop these ords (any order, duplicates allowed; a row outside the index: BBQ_ERR_INVALID_ARG) */
+int bbq_index_remove_rows(bbq_index *idx, const int32_t *rows, int64_t n);
+/* host-only, no device: the accepted ords ascending = the old ord of every new row.  accept_bits as bbq_filter_create takes them
+ * (bits at and beyond n_rows are ignored), out_rows [cap]; *out_n = |A| even when cap is too small (then BBQ_ERR_INVALID_ARG and
+ * nothing is written) */
+int bbq_filter_kept_rows(const uint64_t *accept_bits, int64_t n_rows, int32_t *out_rows, int64_t cap, int64_t *out_n);
+
 /* Per-row results of computeBatchQuantizedScores (src/binaryQuantizedScorer.ts:389-400) for the
  * contiguous ords [row_begin, row_begin+row_count): bitDotProduct (integer qcDist), the f64 score and
  * its f32 rounding (src/binaryQuantizationFormat.ts:353,378).  Any output pointer may be NULL. */
@@ -389,6 +421,9 @@ int bbq_vectors_create(const float *vectors, int64_t n, int32_t dim, int32_t dev
 /* the fp32 side of the rerank recipe grows with the index (bbq_index_append*): the rows get the next ords; storage grows by half as
  * much again when it runs out.  On failure nothing has changed. */
 int bbq_vectors_append(bbq_vectors *v, const float *vectors, int64_t n);
+/* the fp32 side of the rerank recipe follows a compaction of the index (bbq_index_compact): f->n_rows must equal bbq_vectors_size(v),
+ * same device; the rows f accepts are kept, in order, gathered out of place on the device - storage afterwards is exactly |A| rows */
+int bbq_vectors_compact(bbq_vectors *v, const bbq_filter *f);
 void bbq_vectors_destroy(bbq_vectors *v);
 int64_t bbq_vectors_size(const bbq_vectors *v);
 int32_t bbq_vectors_dimension(const bbq_vectors *v);
