@@ -88,7 +88,8 @@ namespace bbq {
 
 // queries per launch sequence (sub-batch).  The largest sweep of a sub-batch should run for about a millisecond: shorter ones pay the
 // device's dependent-launch gaps and their own ramp (1.25 M rows x 2048 queries: 52.5 K q/s with 32 per sub-batch, 56.5 K with 64,
-// 57 K with 96-128; at 10 M rows 32 is as good as 64 and needs half the workspace).  A call should also be cut into at least four
+// 57 K with 96-128; at 10 M rows 32 is as good as 64 and needs half the workspace - also with the launch's queries co-scheduled per chunk,
+// l2_share_shift() below, where the sweep is bound by vector issue: 11.20-11.21 K q/s with 32, 11.33-11.34 K with 64).  A call should also be cut into at least four
 // sub-batches where it can: the first sub-batch's small segments run alone on the device and only the later ones hide theirs behind
 // another sub-batch's large sweep (1 M rows x 256 queries per call: 0.849 of the roofline end to end with 2 x 128, 0.855 with 4 x 64)
 int effective_batch(const bbq_index *ix, int64_t n_queries) {
@@ -99,6 +100,20 @@ int effective_batch(const bbq_index *ix, int64_t n_queries) {
   // the sweep on the matrix cores serves two groups of 32 queries per tile load (bbq_mfma_kernels.hip): 64 queries per launch chain
   if (ix->opt_share == 32 && q < 64 && (n_queries == 0 || n_queries > 32)) q = 64;
   return q;
+}
+
+// queries co-scheduled per chunk in a per-query sparse sweep (option l2_share; the launch caps it by its query count).  An explicit value
+// is taken as it is.  Automatic: kL2ShareAuto - except with resident_mb 0, the "no reuse across queries" mode that bench.py's strict
+// roofline figure is measured in: there every byte of every sweep has to come from HBM, so the launch keeps the plain order, in which
+// two queries' reads of a chunk lie a whole sweep apart.  Measured at 10 M x 768, 256 queries per call, 32 per launch, one box, alternating
+// (K q/s): 1: 7.60-7.61, 2: 9.07-9.11, 4: 10.22-10.27, 8: 10.76-10.77, 16: 11.01-11.03, 32: 11.20-11.21 - as many as a launch has.
+constexpr int kL2ShareAuto = 32;
+int l2_share_shift(const bbq_index *ix) {
+  int p = ix->opt_l2_share;
+  if (p < 0) p = ix->opt_resident_mb == 0 ? 1 : kL2ShareAuto;
+  int s = 0;
+  while ((1 << (s + 1)) <= p) ++s;
+  return s;
 }
 
 // ------------------------------------------------------------------------------------------------ plan
@@ -395,6 +410,7 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
     const LaunchView lv = launch_view(ix, sto, g.chunk_begin, g.n_chunks);
     resident += lv.resident_bytes;
     ScanArgs a = segment_scan_args(p, s, g, sto, lv.view, nq, qb);
+    a.l2_shift = l2_share_shift(ix);  // (read by the per-query sweep alone, and only by its sparse launches)
     const bool append_here = !g.dense && ((append && (ix->opt_append_last || !last)) || use_mfma);
     if (append_here) {
       a.append_lists = d_lists;

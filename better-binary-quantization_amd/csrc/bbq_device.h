@@ -64,6 +64,63 @@ struct TileGeom {
   int32_t layout;
   int32_t store_bits;   // 1: packed 1-bit rows; 2 / 4 / 8: multi-bit fields (indexBits 2 / 3-4 / 5-8)
 };
+// ---- the per-query sweep's workgroup -> (chunk, query) map (bbq_scan_kernel and its launch, bbq_scan_body.h).  P = 2^s queries are
+// co-scheduled per chunk (option l2_share): grid.x = 8 P ceil(n_chunks / 8), grid.y = ceil(n_queries / P).  The device deals the
+// workgroups of a row round-robin over its 8 XCDs, so L & 7 labels the workgroups that share an XCD - and its L2 - and the P
+// workgroups that sweep one chunk for P different queries are consecutive among the workgroups of one label: they are dispatched
+// back to back onto one XCD, the first of them brings the chunk's lines into that L2 and the others find them there (or in flight).
+// A speed choice only: the answer does not depend on where or when a workgroup runs.  s = 0 is the plain map, chunks fastest,
+// grid = (n_chunks, n_queries) without padding.  A workgroup whose chunk_local >= n_chunks or whose query >= n_queries has no work.
+struct SweepCoord {
+  int32_t chunk_local;  // chunk inside the launch: + ScanArgs::chunk_begin = the chunk of the index
+  int32_t query;
+};
+__host__ __device__ constexpr SweepCoord sweep_coord(uint32_t bx, uint32_t by, int s) {
+  return SweepCoord{(int32_t)(((bx >> (3 + s)) << 3) | (bx & 7u)), (int32_t)((by << s) + ((bx >> 3) & ((1u << s) - 1u)))};
+}
+__host__ __device__ constexpr uint32_t sweep_grid_x(int n_chunks, int s) { return s == 0 ? (uint32_t)n_chunks : ((uint32_t)(n_chunks + 7) / 8u * 8u) << s; }
+__host__ __device__ constexpr uint32_t sweep_grid_y(int n_queries, int s) { return ((uint32_t)n_queries + (1u << s) - 1u) >> s; }
+// The limit of the reordered grid: a launch's x extent in WORK-ITEMS, grid.x * kChunkRows, is a 32-bit count (the dispatch packet's
+// grid_size_x; the runtime refuses more with hipErrorInvalidConfiguration).  The plain grid has n_chunks * kChunkRows = the launch's rows
+// there, which fits for every index the library accepts (at most 2^32 - 1 rows); the reordered one has P times as many, so P = 32
+// fits up to 262 136 chunks (134 M rows) per launch, and a longer launch co-schedules fewer queries per chunk.
+constexpr uint64_t kGridWorkItemsMax = 0xFFFFFFFFull;
+__host__ __device__ constexpr bool sweep_grid_fits(int n_chunks, int s) { return (uint64_t)sweep_grid_x(n_chunks, s) * (uint64_t)kChunkRows <= kGridWorkItemsMax; }
+// the largest s <= want with 2^s <= n_queries - a launch co-schedules no more queries than it has - whose grid the device takes
+__host__ __device__ constexpr int sweep_shift_for(int want, int n_queries, int n_chunks) {
+  int s = want < 0 ? 0 : want;
+  while (s > 0 && ((1 << s) > n_queries || !sweep_grid_fits(n_chunks, s))) --s;
+  return s;
+}
+// the map hits every (chunk, query) pair of a launch exactly once: a pair covered twice would pass every parity test and only cost time
+constexpr bool sweep_map_is_exact(int n_chunks, int n_queries, int s) {
+  uint64_t hits[32] = {};  // one bit per pair (n_chunks * n_queries <= 2048)
+  const uint32_t gx = sweep_grid_x(n_chunks, s), gy = sweep_grid_y(n_queries, s);
+  int64_t covered = 0;
+  for (uint32_t y = 0; y < gy; ++y)
+    for (uint32_t x = 0; x < gx; ++x) {
+      const SweepCoord c = sweep_coord(x, y, s);
+      if (c.chunk_local < 0 || c.query < 0) return false;
+      if (c.chunk_local >= n_chunks || c.query >= n_queries) continue;
+      const int pair = c.query * n_chunks + c.chunk_local;
+      if (hits[pair >> 6] >> (pair & 63) & 1u) return false;
+      hits[pair >> 6] |= 1ull << (pair & 63);
+      ++covered;
+    }
+  return covered == (int64_t)n_chunks * n_queries;
+}
+static_assert(sweep_grid_x(38, 0) == 38 && sweep_grid_y(37, 0) == 37 && sweep_coord(21, 5, 0).chunk_local == 21 && sweep_coord(21, 5, 0).query == 5,
+              "s = 0 is the plain grid: (n_chunks, n_queries), blockIdx.x the chunk, blockIdx.y the query");
+static_assert(sweep_map_is_exact(38, 37, 0) && sweep_map_is_exact(38, 37, 5) && sweep_map_is_exact(38, 37, 3) && sweep_map_is_exact(38, 5, 2),
+              "n_chunks not a multiple of 8, n_queries not a multiple of P");
+static_assert(sweep_map_is_exact(2, 32, 5) && sweep_map_is_exact(7, 9, 1) && sweep_map_is_exact(1, 1, 0) && sweep_map_is_exact(8, 32, 4), "n_chunks < 8, = 8");
+static_assert(sweep_map_is_exact(19, 3, 5) && sweep_map_is_exact(16, 1, 3) && sweep_map_is_exact(40, 3, sweep_shift_for(5, 3, 40)), "n_queries < P");
+static_assert(sweep_shift_for(5, 3, 40) == 1 && sweep_shift_for(3, 32, 40) == 3 && sweep_shift_for(5, 1, 40) == 0 && sweep_shift_for(0, 7, 40) == 0, "the cap by the query count");
+// the cap by the grid's extent: 2^18 chunks x 32 queries would be 2^32 work-items in x
+static_assert(sweep_grid_fits(262136, 5) && !sweep_grid_fits(262137, 5) && !sweep_grid_fits(1 << 18, 5) && sweep_grid_fits(1 << 18, 4), "grid.x * kChunkRows <= 2^32 - 1");
+static_assert(sweep_shift_for(5, 32, 262136) == 5 && sweep_shift_for(5, 32, 1 << 18) == 4 && sweep_shift_for(5, 32, 1 << 19) == 3 && sweep_shift_for(5, 32, 1 << 20) == 2 &&
+              sweep_shift_for(5, 32, 4000000) == 1 && sweep_shift_for(5, 32, 8388607) == 0 && sweep_grid_fits(8388607, 0), "a long launch co-schedules fewer queries");
+
 constexpr int kChunkBytes = 16;
 // code chunk j of row r inside a record: its index among the record's chunks, and its byte offset
 __host__ __device__ constexpr int tile_chunk_index(int j, int r) { return j * kTileRows + r; }
@@ -184,7 +241,7 @@ struct ScanArgs {
   uint64_t *entries;           // [Q][n_chunks][cap], ascending by row inside a chunk
   uint32_t *flags;             // [Q]
   int32_t cap;
-  int32_t n_chunks;            // chunks in this launch (= gridDim.x)
+  int32_t n_chunks;            // chunks in this launch (the slot and count arrays' stride; the grid's x extent follows from it, sweep_grid_x)
   // flood tier (may be null): a chunk with more than `cap` candidates parks ALL of them, row-ordered, in a block of the
   // query's overflow area and leaves counts = kCountRedirect | n, entries[0] = block offset (bbq_scan_kernel only)
   uint64_t *ovf;               // [Q][ovf_cap]
@@ -203,6 +260,10 @@ struct ScanArgs {
   int32_t *dense_qcdist;       // or null
   double *dense_score64;       // or null
   int64_t dense_stride;
+  // the workgroup -> (chunk, query) map of bbq_scan_kernel (sweep_coord): l2_shift = s, 2^s queries co-scheduled per chunk.  The caller
+  // sets what it asks for (0: the plain grid); the launch caps it by its query count and by the grid's extent (sweep_shift_for) and fills in n_queries
+  int32_t l2_shift;
+  int32_t n_queries;
 };
 
 struct FinalizeArgs {

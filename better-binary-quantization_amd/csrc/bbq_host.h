@@ -197,6 +197,8 @@ struct bbq_index {
   int opt_resident_interleave = 1;  // the resident chunks of a launch are spread over its range (of every 64 chunks the first n) instead of being its head
   int opt_resident_mb = -1;  // MiB of its row range that ONE sweep launch loads with the default cache policy, so that they stay in the Infinity
                              // Cache from one query's sweep to the next (launch_view(), bbq_index.cpp); -1: this index's share of kResidentAutoBytes
+  int opt_l2_share = -1;  // queries whose workgroups sweep one chunk back to back on one XCD, so that all but the first read it through that
+                          // XCD's L2 (sweep_coord, bbq_device.h): 1 off, 2..32, -1: l2_share_shift()'s choice (bbq_core.cpp)
   int opt_latency_presample = 1;  // ... and on large indexes get their threshold from per-wave top keys of a prefix (two small launches) instead of two scan / finalize pairs
   int opt_latency_fused = 1;  // single-query calls take the three-launch latency path (bbq_latency_kernels.hip) when the index shape has one
   int opt_append_last = 1;  // append mode also for the last (largest) segment: its finalize launch gets cheaper, its sweep slower (one

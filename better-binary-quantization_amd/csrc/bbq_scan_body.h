@@ -70,7 +70,9 @@ __device__ __forceinline__ void tile_dot_multibit_any(const uint8_t *__restrict_
 }
 
 // MODE: 0 sparse / inline corrections, 1 dense / inline, 2 sparse / compact corrections + exact gather, 3 dense / compact
-// grid = (chunks of kChunkRows rows, queries); block = kChunkRows/64 waves: wave w handles tile w of its chunk (one row per lane)
+// grid = (chunks of kChunkRows rows, queries), or with ScanArgs::l2_shift = s > 0 the same pairs in the order that runs a chunk's 2^s
+// queries back to back on one XCD (sweep_coord, bbq_device.h); block = kChunkRows/64 waves: wave w handles tile w of its chunk (one
+// row per lane)
 // SB = bits per stored field: 1 = packed 1-bit rows (QB bit-planes of the query), 2 / 4 / 8 = multi-bit rows (QB = 4: query values
 // <= 15, QB = 8: any)
 // Accept: empty - the unfiltered sweep, exactly the kernel it was - or one `const uint64_t *`, the accept bitset of a filtered search
@@ -97,16 +99,23 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
   const uint32_t stage_cap = DENSE ? 0u : ((a.ovf || a.append_lists) ? (uint32_t)kChunkRows : (uint32_t)a.cap);
   uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_ent + stage_cap);
 
-  const int q = blockIdx.y;
+  // which chunk for which query: the one map of the launch (sweep_coord); a workgroup of the grid's padding has nothing to do
+  const SweepCoord wg = sweep_coord(blockIdx.x, blockIdx.y, a.l2_shift);
+  // It leaves in front of the first barrier, not here: with a return in the entry block the compiler of this build (ROCm 7.2) allocated
+  // bbq_scan_kernel<8, 0, 0, 4> 68 vector registers instead of 41, one wave of occupancy less.  To check again: build bbq_kernels.hip and
+  // bbq_filter_kernels.hip with -Rpass-analysis=kernel-resource-usage before and after moving the return, and compare VGPRs / Occupancy
+  // of every bbq_scan_kernel instantiation.  Until then it reads what query 0 would (its accept word only if the tile exists): in bounds, never used
+  const bool idle = wg.chunk_local >= a.n_chunks || wg.query >= a.n_queries;  // workgroup-uniform
+  const int q = idle ? 0 : wg.query;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
 
-  // the tile's accept word first: its address depends on blockIdx and the wave number alone, so the scalar load travels while the
+  // the tile's accept word first: its address depends on the workgroup's chunk and the wave number alone, so the scalar load travels while the
   // planes are staged and is there when the barrier opens (behind the barrier every wave paid its latency in front of its first HBM request)
   uint64_t aw = 0;
   if constexpr (FILT) {
-    const int64_t my_tile = (a.chunk_begin + blockIdx.x) * kTilesPerChunk + __builtin_amdgcn_readfirstlane(wave);
+    const int64_t my_tile = (a.chunk_begin + wg.chunk_local) * kTilesPerChunk + __builtin_amdgcn_readfirstlane(wave);
     if (my_tile < (a.idx.n_rows + kTileRows - 1) / kTileRows) aw = accept[my_tile];
   }
   {  // stage the query bit-planes once per workgroup
@@ -116,9 +125,10 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
   }
   const QueryParams p = a.qparams[q];
   const uint32_t theta = DENSE ? 0u : a.theta[q];
+  if (idle) return;
   __syncthreads();
 
-  const int64_t chunk = a.chunk_begin + blockIdx.x;
+  const int64_t chunk = a.chunk_begin + wg.chunk_local;
   const int64_t n_tiles = (a.idx.n_rows + kTileRows - 1) / kTileRows;
   const int64_t tile = chunk * kTilesPerChunk + wave;
   bool nan_seen = false;
@@ -196,7 +206,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
       return;
     }
     uint32_t cnt = *s_cnt;
-    uint64_t *__restrict__ slot0 = a.entries + ((size_t)q * a.n_chunks + blockIdx.x) * (size_t)a.cap;
+    uint64_t *__restrict__ slot0 = a.entries + ((size_t)q * a.n_chunks + wg.chunk_local) * (size_t)a.cap;
     uint64_t *__restrict__ out = slot0;
     uint32_t count_word = cnt;
     if (cnt > (uint32_t)a.cap) {  // workgroup-uniform
@@ -222,7 +232,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
       }
     }
     write_ranked(s_ent, cnt, out, tid, NT);
-    if (tid == 0) a.counts[(size_t)q * a.n_chunks + blockIdx.x] = count_word;
+    if (tid == 0) a.counts[(size_t)q * a.n_chunks + wg.chunk_local] = count_word;
   }
 }
 
@@ -230,10 +240,14 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
 // dispatch over the instantiations: FILT selects the kernel family, `accept` is its accept bitset (null without)
 
 template <bool FILT, int QB, int W, int MODE, int SB = 1>
-static hipError_t launch_scan_t(const ScanArgs &a, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s) {
+static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s) {
+  ScanArgs a = args;  // the map's parameters: what the kernel decodes its block index with is what the grid below is built from
+  a.n_chunks = n_chunks;
+  a.n_queries = n_queries;
+  a.l2_shift = (MODE & 1) ? 0 : sweep_shift_for(args.l2_shift, n_queries, n_chunks);  // a dense launch writes every row: nothing to co-schedule for
   const int w16 = W > 0 ? W : a.idx.geom.w16;
   const size_t smem = (size_t)w16 * query_units_per_chunk(QB, SB) * 16 + ((MODE & 1) ? 0 : (size_t)((a.ovf || a.append_lists) ? kChunkRows : a.cap) * 8) + 16;
-  dim3 grid((unsigned)n_chunks, (unsigned)n_queries, 1), block(kChunkRows, 1, 1);
+  dim3 grid(sweep_grid_x(n_chunks, a.l2_shift), sweep_grid_y(n_queries, a.l2_shift), 1), block(kChunkRows, 1, 1);
   if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, const uint64_t *>), grid, block, smem, s, a, accept);
   else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB>), grid, block, smem, s, a);
   return hipGetLastError();

@@ -4,9 +4,15 @@
 //   3 + workgroup barrier at the end and one count word written per workgroup   4 + per-query parameters loaded from global memory
 //   5 + the tile's side value (plain load)   6 + 0.3 survivors per chunk that gather 32 B of exact corrections and are written out
 //   hipcc --offload-arch=gfx950 -O3 -o scan_steps scan_steps.hip && ./scan_steps
+// ./scan_steps l2share [P ...]: step 6 over the 10 M-row index's large launch (15 430 chunks x 32 queries) with the grid reordered so
+// that the P workgroups that sweep one chunk for P queries are dispatched back to back onto one XCD (the library's sweep_coord map:
+// x = L & 7 labels the XCD, p = (L >> 3) & (P - 1), chunk = 8 (L >> (3 + s)) + x, query = blockIdx.y P + p); P = 1 is the plain grid.
+// Rate here; L2 hits and misses from a counter run of the same command (scripts/pmc_l2_hits.sh has the recipe).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string>
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint32_t popc4(u32x4 v) { return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w); }
@@ -16,12 +22,13 @@ struct QP { double ay, ly, y1, qadd, cdp, dimd; int sim, one_bit, mip, pad; };
 template <int STEP>
 __global__ __launch_bounds__(512) void k(const u32x4 *__restrict__ p, unsigned n_chunks, const u32x4 *__restrict__ planes, const QP *__restrict__ qps,
                                          const uint32_t *__restrict__ thetas, uint32_t *__restrict__ counts, uint64_t *__restrict__ entries, uint32_t *out,
-                                         const float *__restrict__ add_range, const double *__restrict__ exact) {
+                                         const float *__restrict__ add_range, const double *__restrict__ exact, int s, int n_queries) {
   __shared__ u32x4 s_planes[24];
   __shared__ uint64_t s_ent[512];
   __shared__ uint32_t s_cnt;
-  const unsigned c = blockIdx.x;
-  const int q = blockIdx.y;
+  const unsigned c = ((blockIdx.x >> (3 + s)) << 3) | (blockIdx.x & 7u);
+  const int q = (int)((blockIdx.y << s) + ((blockIdx.x >> 3) & ((1u << s) - 1u)));
+  if (c >= n_chunks || q >= n_queries) return;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const u32x4 *tp = p + ((size_t)c * 8 + wave) * (6400 / 16) + lane;
   const u32x4 *gp = planes + (size_t)q * 24;
@@ -108,7 +115,7 @@ static int run(const Bufs &b, size_t bytes, int reps, unsigned drop, const char 
   float best = 1e9f, sum = 0;
   for (int it = 0; it < 7; ++it) {
     CHK(hipEventRecord(e0));
-    hipLaunchKernelGGL((k<STEP>), dim3(n_chunks, reps), dim3(512), 0, 0, b.d, n_chunks, b.planes, b.qps, b.thetas, b.counts, b.entries, b.out, b.add_range, b.exact);
+    hipLaunchKernelGGL((k<STEP>), dim3(n_chunks, reps), dim3(512), 0, 0, b.d, n_chunks, b.planes, b.qps, b.thetas, b.counts, b.entries, b.out, b.add_range, b.exact, 0, reps);
     CHK(hipEventRecord(e1));
     CHK(hipEventSynchronize(e1));
     float ms; CHK(hipEventElapsedTime(&ms, e0, e1));
@@ -120,7 +127,27 @@ static int run(const Bufs &b, size_t bytes, int reps, unsigned drop, const char 
   return 0;
 }
 
-int main() {
+// the reordered grid: 2^s queries co-scheduled per chunk
+static int run_l2share(const Bufs &b, unsigned n_chunks, int nq, int s) {
+  hipEvent_t e0, e1;
+  CHK(hipEventCreate(&e0)); CHK(hipEventCreate(&e1));
+  const dim3 grid(s == 0 ? n_chunks : ((n_chunks + 7) / 8 * 8) << s, (unsigned)(nq + (1 << s) - 1) >> s);
+  float best = 1e9f, sum = 0;
+  for (int it = 0; it < 7; ++it) {
+    CHK(hipEventRecord(e0));
+    hipLaunchKernelGGL((k<6>), grid, dim3(512), 0, 0, b.d, n_chunks, b.planes, b.qps, b.thetas, b.counts, b.entries, b.out, b.add_range, b.exact, s, nq);
+    CHK(hipEventRecord(e1));
+    CHK(hipEventSynchronize(e1));
+    float ms; CHK(hipEventElapsedTime(&ms, e0, e1));
+    if (it >= 2) { sum += ms; if (ms < best) best = ms; }
+  }
+  const double by = (double)n_chunks * 51200 * nq;
+  printf("l2share P %2d  grid %7u x %2u  %u chunks x %d queries: avg %6.3f ms %7.1f GB/s  best %6.3f ms %7.1f GB/s\n", 1 << s, grid.x, grid.y, n_chunks, nq,
+         sum / 5, by / (sum / 5 * 1e-3) / 1e9, best, by / (best * 1e-3) / 1e9);
+  return 0;
+}
+
+int main(int argc, char **argv) {
   const size_t cap = (size_t)1100 << 20;
   Bufs b;
   CHK(hipMalloc((void **)&b.d, cap));
@@ -136,6 +163,17 @@ int main() {
   CHK(hipMalloc((void **)&b.out, 4)); CHK(hipMemset(b.out, 0, 4));
   CHK(hipMalloc((void **)&b.add_range, (size_t)22000 * 8 * 2 * 4)); CHK(hipMemset(b.add_range, 0, (size_t)22000 * 8 * 2 * 4));
   CHK(hipMalloc((void **)&b.exact, (size_t)22000 * 512 * 32)); CHK(hipMemset(b.exact, 0, (size_t)22000 * 512 * 32));
+  if (argc > 1 && std::string(argv[1]) == "l2share") {
+    const int all[] = {1, 2, 4, 8, 32};
+    for (int i = 0; i < (argc > 2 ? argc - 2 : 5); ++i) {
+      const int P = argc > 2 ? atoi(argv[i + 2]) : all[i];
+      int s = 0;
+      while ((1 << (s + 1)) <= P) ++s;
+      if (P < 1 || P > 32 || (1 << s) != P) { printf("P must be 1, 2, 4, 8, 16 or 32\n"); return 1; }
+      if (run_l2share(b, 15430, 32, s)) return 1;
+    }
+    return 0;
+  }
   {  // the library's large launch on the 1 M-row index: 1378 chunks starting at chunk 576, 128 queries; x extent as is / padded to 1384
     Bufs o = b;
     o.d = b.d + (size_t)576 * 51200 / 16;
