@@ -11,44 +11,6 @@ using namespace bbq;
 
 namespace {
 
-// host rows -> device scratch
-int stage_rows(const bbq_index *ix, const uint8_t *codes, const double *corr, int64_t n, DevBuf<uint8_t> &d_codes, DevBuf<double> &d_corr) {
-  const int64_t pb = caller_row_bytes(ix);
-  hipStream_t s = ix->ctx->aux_stream;
-  if (d_codes.alloc((size_t)(n * pb)) != hipSuccess || d_corr.alloc((size_t)n * 4) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(BBQ_ERR_OOM, "no device memory to stage %lld rows", (long long)n);
-  }
-  HIPCHK(hipMemcpyAsync(d_codes, codes, (size_t)(n * pb), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(d_corr, corr, (size_t)n * 32, hipMemcpyHostToDevice, s));
-  return BBQ_OK;
-}
-
-// quantizedComponentSum of a 1-bit row is its popcount (src/optimizedScalarQuantizer.ts:204-209), of a multi-bit row its code sum; while
-// that holds for every row the 8 bytes need not be stored or read.  An index that stores the sums already takes any row.  Nothing is
-// written: an append that is refused here has not touched even a padding lane.
-int check_device_rows(bbq_index *ix, const uint8_t *d_codes, const double *d_corr, int64_t n, Sums mode) {
-  const bool multibit = ix->geom.store_bits > 1, range = multibit && mode == Sums::kRequire;
-  if (n > 0 && (!ix->geom.has_x1 || range)) {
-    hipStream_t s = ix->ctx->aux_stream;
-    uint32_t flags[2] = {0, 0};  // a sum that is not the implied one; a code out of range
-    DevBuf<uint32_t> d_flags;
-    HIPCHK(d_flags.alloc(2));
-    HIPCHK(hipMemsetAsync(d_flags, 0, 8, s));
-    if (!ix->geom.has_x1) HIPCHK(launch_check_x1(StagedRows{d_codes, d_corr}, n, ix->geom, d_flags, s));
-    if (range) HIPCHK(launch_check_code_range(d_codes, n * ix->geom.dim, ix->index_bits, d_flags + 1, s));
-    HIPCHK(hipMemcpyAsync(flags, d_flags, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (flags[1]) return fail(BBQ_ERR_INVALID_ARG, "indexBits=%d: a quantized value is not below %d", ix->index_bits, 1 << ix->index_bits);
-    if (flags[0] && mode == Sums::kRequire)
-      return fail(BBQ_ERR_UNSUPPORTED, "a row's quantizedComponentSum is not its %s and the index stores no explicit sums: holding the row would mean "
-                  "re-tiling the whole index (create it over all rows instead)", multibit ? "code sum" : "popcount");
-    if (flags[0]) ix->geom.has_x1 = 1;
-  }
-  if (mode == Sums::kDecide) decide_layout(ix);  // decided once per index, over all its storages
-  return BBQ_OK;
-}
-
 // the checked rows written behind those `st` holds, and committed
 int write_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const double *d_corr, int64_t n) {
   const int64_t row0 = st.view.n_rows, total = row0 + n;
@@ -92,6 +54,44 @@ int append_device_rows(bbq_index *ix, Storage &st, const uint8_t *d_codes, const
 }  // namespace
 
 namespace bbq {
+
+// host rows -> device scratch
+int stage_rows(const bbq_index *ix, const uint8_t *codes, const double *corr, int64_t n, DevBuf<uint8_t> &d_codes, DevBuf<double> &d_corr) {
+  const int64_t pb = caller_row_bytes(ix);
+  hipStream_t s = ix->ctx->aux_stream;
+  if (d_codes.alloc((size_t)(n * pb)) != hipSuccess || d_corr.alloc((size_t)n * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(BBQ_ERR_OOM, "no device memory to stage %lld rows", (long long)n);
+  }
+  HIPCHK(hipMemcpyAsync(d_codes, codes, (size_t)(n * pb), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_corr, corr, (size_t)n * 32, hipMemcpyHostToDevice, s));
+  return BBQ_OK;
+}
+
+// quantizedComponentSum of a 1-bit row is its popcount (src/optimizedScalarQuantizer.ts:204-209), of a multi-bit row its code sum; while
+// that holds for every row the 8 bytes need not be stored or read.  An index that stores the sums already takes any row.  Nothing is
+// written: an append that is refused here has not touched even a padding lane.
+int check_device_rows(bbq_index *ix, const uint8_t *d_codes, const double *d_corr, int64_t n, Sums mode) {
+  const bool multibit = ix->geom.store_bits > 1, range = multibit && mode == Sums::kRequire;
+  if (n > 0 && (!ix->geom.has_x1 || range)) {
+    hipStream_t s = ix->ctx->aux_stream;
+    uint32_t flags[2] = {0, 0};  // a sum that is not the implied one; a code out of range
+    DevBuf<uint32_t> d_flags;
+    HIPCHK(d_flags.alloc(2));
+    HIPCHK(hipMemsetAsync(d_flags, 0, 8, s));
+    if (!ix->geom.has_x1) HIPCHK(launch_check_x1(StagedRows{d_codes, d_corr}, n, ix->geom, d_flags, s));
+    if (range) HIPCHK(launch_check_code_range(d_codes, n * ix->geom.dim, ix->index_bits, d_flags + 1, s));
+    HIPCHK(hipMemcpyAsync(flags, d_flags, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (flags[1]) return fail(BBQ_ERR_INVALID_ARG, "indexBits=%d: a quantized value is not below %d", ix->index_bits, 1 << ix->index_bits);
+    if (flags[0] && mode == Sums::kRequire)
+      return fail(BBQ_ERR_UNSUPPORTED, "a row's quantizedComponentSum is not its %s and the index stores no explicit sums: holding the row would mean "
+                  "re-tiling the whole index (create it over all rows instead)", multibit ? "code sum" : "popcount");
+    if (flags[0]) ix->geom.has_x1 = 1;
+  }
+  if (mode == Sums::kDecide) decide_layout(ix);  // decided once per index, over all its storages
+  return BBQ_OK;
+}
 
 // what an append can work on: a single-device root index without a pilot replica (the scope of the filters)
 int check_append_index(const bbq_index *ix, int64_t n, const char *who) {
@@ -216,45 +216,53 @@ int stage_vectors(DeviceCtx *ctx, const float *vectors, int64_t n, int32_t dim, 
   return BBQ_OK;
 }
 
-int quantize_into(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d_cen, int32_t sim, double lambda, int32_t iters, Sums mode,
-                  uint8_t *codes_out, double *corr_out) {
+int quantize_staged(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d_cen, int32_t sim, double lambda, int32_t iters,
+                    DevBuf<uint8_t> &d_codes, DevBuf<double> &d_corr, uint8_t *codes_out, double *corr_out) {
   hipStream_t st = ix->ctx->aux_stream;
-  const int32_t dim = ix->geom.dim, pb = pb_of(ix->geom);
-  const int64_t npad = tiles_of(n) * kTileRows;
-  DevBuf<double> d_corr;
-  DevBuf<uint8_t> d_codes;
+  const int32_t dim = ix->geom.dim;
+  const int64_t npad = tiles_of(n) * kTileRows, pb = ix->index_bits > 1 ? dim : pb_of(ix->geom);
+  if (d_codes.alloc((size_t)(n * pb)) != hipSuccess || d_corr.alloc((size_t)n * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(BBQ_ERR_OOM, "no device memory for %lld quantized rows", (long long)n);
+  }
+  DevBuf<uint8_t> d_tmp;  // lives until the device has completed
   if (ix->index_bits > 1) {
     // more than one bit: the kernel leaves what the reference keeps for such an index - one byte per dimension - and the corrections
     // in device memory; the tile records are built from there exactly as they are from a caller's rows
-    if (d_codes.alloc((size_t)n * dim) != hipSuccess || d_corr.alloc((size_t)n * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(BBQ_ERR_OOM, "no device memory for %lld quantized rows", (long long)n);
-    }
     HIPCHK(launch_build_quantize_bits(d_vT4, n, dim, npad, d_cen, sim, lambda, iters, ix->index_bits, d_codes, d_corr, st));  // :221-249
-    HIPCHK(hipStreamSynchronize(st));
-    d_vT4.reset();  // before the tile records are allocated
-    // the host copies first: nothing can fail behind the commit
-    if (corr_out) HIPCHK(hipMemcpy(corr_out, d_corr, (size_t)n * 32, hipMemcpyDeviceToHost));
-    if (codes_out) HIPCHK(hipMemcpy(codes_out, d_codes, (size_t)n * dim, hipMemcpyDeviceToHost));
-    return append_device_rows(ix, ix->main, d_codes, d_corr, n, mode);
-  }
-  if ((corr_out || ix->geom.has_x1) && d_corr.alloc((size_t)n * 4) != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "no device memory for the corrections"); }
-  if (ix->geom.has_x1) {
-    // an index with explicit sums (rare: it was created from rows whose sums are not their popcounts) takes freshly quantized rows as
-    // it takes a caller's, on the row-major path: packed codes from a scratch tile set without sums
-    DevBuf<uint8_t> d_tmp;
-    if (d_tmp.alloc((size_t)(npad / kTileRows) * scratch_tile_dest(ix, nullptr).geom.tile_stride) != hipSuccess || d_codes.alloc((size_t)n * pb) != hipSuccess) {
+  } else {
+    // 1-bit rows on the row-major path: packed codes from a scratch tile set without sums
+    if (d_tmp.alloc((size_t)(npad / kTileRows) * scratch_tile_dest(ix, nullptr).geom.tile_stride) != hipSuccess) {
       (void)hipGetLastError();
       return fail(BBQ_ERR_OOM, "no device memory for %lld quantized rows", (long long)n);
     }
     const TileDest tmp = scratch_tile_dest(ix, d_tmp);
     HIPCHK(launch_build_quantize1(d_vT4, n, npad, d_cen, sim, lambda, iters, tmp, d_corr, st, 0));
     HIPCHK(launch_build_untile(tmp, n, d_codes, st, 0));
-    HIPCHK(hipStreamSynchronize(st));
-    if (corr_out) HIPCHK(hipMemcpy(corr_out, d_corr, (size_t)n * 32, hipMemcpyDeviceToHost));
-    if (codes_out) HIPCHK(hipMemcpy(codes_out, d_codes, (size_t)n * pb, hipMemcpyDeviceToHost));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  d_vT4.reset();  // before the caller allocates what it writes the rows into
+  // the host copies first: nothing can fail behind the commit
+  if (corr_out) HIPCHK(hipMemcpy(corr_out, d_corr, (size_t)n * 32, hipMemcpyDeviceToHost));
+  if (codes_out) HIPCHK(hipMemcpy(codes_out, d_codes, (size_t)(n * pb), hipMemcpyDeviceToHost));
+  return BBQ_OK;
+}
+
+int quantize_into(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d_cen, int32_t sim, double lambda, int32_t iters, Sums mode,
+                  uint8_t *codes_out, double *corr_out) {
+  hipStream_t st = ix->ctx->aux_stream;
+  const int32_t pb = pb_of(ix->geom);
+  const int64_t npad = tiles_of(n) * kTileRows;
+  DevBuf<double> d_corr;
+  DevBuf<uint8_t> d_codes;
+  if (ix->index_bits > 1 || ix->geom.has_x1) {
+    // multi-bit rows, and an index with explicit sums (rare: it was created from rows whose sums are not their popcounts): freshly
+    // quantized rows are taken as a caller's are, from device memory in the caller's shape
+    const int rc = quantize_staged(ix, d_vT4, n, d_cen, sim, lambda, iters, d_codes, d_corr, codes_out, corr_out);
+    if (rc != BBQ_OK) return rc;
     return append_device_rows(ix, ix->main, d_codes, d_corr, n, mode);
   }
+  if (corr_out && d_corr.alloc((size_t)n * 4) != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "no device memory for the corrections"); }
   // 1-bit: one thread per vector quantizes straight into its lane of the tile records, from the partly filled last tile on; a freshly
   // quantized row's component sum IS its popcount, so there is nothing to check
   if (codes_out && d_codes.alloc((size_t)n * pb) != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "no device memory for the codes"); }

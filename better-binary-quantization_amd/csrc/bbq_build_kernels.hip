@@ -16,7 +16,8 @@
 // and rows that arrive quantized, in the caller's shape:
 //   retile         row-major rows (packed 1-bit, or one byte per dimension) + corrections -> tile records
 //   check_x1       is every quantizedComponentSum the implied one (popcount / code sum)?   check_code_range: every multi-bit code in range?
-//   tile_add_range compact layout: each tile's {min, max} of additionalCorrection
+//   scatter_rows   the same rows -> the lanes of the ords they replace, in place (bbq_index_update*)
+//   tile_add_range compact layout: each tile's {min, max} of additionalCorrection, over a tile range or a tile list
 // and rows that are in tile records already:
 //   compact_tiles  the records gathered down to the rows a filter accepts, out of place (bbq_index_compact)
 // Every writer takes its destination as a TileDest and writes a row's corrections through write_corrections.
@@ -472,6 +473,62 @@ __global__ __launch_bounds__(256) void bbq_retile_kernel(TileDest out, StagedRow
   reinterpret_cast<u32x4 *>(out.tiles + (row / kTileRows) * (int64_t)out.geom.tile_stride)[tile_chunk_index(j, (int)(row % kTileRows))] = v;
 }
 
+// ------------------------------------------------------------------------------------------------ scatter (rows replaced in place)
+// bbq_retile_kernel with a row map (DESIGN.md "Replacing rows"): staged row pos[i] becomes row ords[pos[i]] of the storage.  pos lists
+// the block's winners - one per distinct ord, ascending by ord (bbq_update_winners) - so every destination lane has exactly one writer
+// and no ordering between workgroups is needed; neighbouring threads write neighbouring lanes of one tile wherever neighbouring ords are
+// updated.  Thread (i, j) writes chunk j, one more thread per row its corrections.  Only the winners' lanes are written: no padding
+// lane, no lane of a row that is not named.  The host has validated the ords and, for multi-bit rows, the code range before the launch
+// (nothing of a refused block reaches the index): `bad` is the packer's and stays clear.
+// 16-byte chunk j of staged row i, as the tile records hold it (w starts as zeros): a packed 1-bit row is copied, a multi-bit row (one
+// byte per dimension) is packed into store_bits-wide fields, and a code that is not below 2^index_bits raises *bad.  The packing of
+// bbq_retile_kernel, which keeps its own copy: called from there the function changed that kernel's instruction stream (DESIGN.md
+// "Replacing rows").
+__device__ __forceinline__ void pack_row_chunk(const TileGeom &g, const StagedRows &in, int64_t i, int j, int32_t index_bits,
+                                               uint32_t *__restrict__ bad, uint32_t (&w)[4]) {
+  if (g.store_bits == 1) {
+    const int pb = pb_of(g);
+    const uint8_t *src = in.codes + i * (int64_t)pb;
+    for (int b = 0; b < 16; ++b) {
+      const int byte = j * 16 + b;
+      if (byte < pb) w[b >> 2] |= (uint32_t)src[byte] << (8 * (b & 3));
+    }
+  } else {
+    const int dim = g.dim, store_bits = g.store_bits, per_dword = 32 / store_bits;
+    const uint8_t *src = in.codes + i * (int64_t)dim;
+    const uint32_t limit = 1u << index_bits, field = (1u << store_bits) - 1u;  // values of an indexBits-bit quantizer are < 2^indexBits (include/bbq.h)
+    for (int t = 0; t < 4; ++t)
+      for (int f = 0; f < per_dword; ++f) {
+        const int d = (j * 4 + t) * per_dword + f;
+        if (d < dim) {
+          const uint32_t v = src[d];
+          if (v >= limit) atomicOr(bad, 1u);
+          w[t] |= (v & field) << (f * store_bits);
+        }
+      }
+  }
+}
+
+__global__ __launch_bounds__(256) void bbq_scatter_rows_kernel(TileDest out, StagedRows in, const int32_t *__restrict__ ords,
+                                                              const int64_t *__restrict__ pos, int64_t n_winners, int32_t index_bits,
+                                                              uint32_t *__restrict__ bad) {
+  const int w16 = out.geom.w16;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t i = gid / (w16 + 1);
+  const int j = (int)(gid % (w16 + 1));
+  if (i >= n_winners) return;
+  const int64_t p = pos[i], row = ords[p];
+  if (j == w16) {
+    const double *c = in.corr + p * 4;
+    write_corrections(out, row, f64x2{c[0], c[1]}, c[2], c[3]);
+    return;
+  }
+  uint32_t w[4] = {0, 0, 0, 0};
+  pack_row_chunk(out.geom, in, p, j, index_bits, bad, w);
+  const u32x4 v = {w[0], w[1], w[2], w[3]};
+  *reinterpret_cast<u32x4 *>(out.tiles + (row / kTileRows) * (int64_t)out.geom.tile_stride + tile_chunk_offset(j, (int)(row % kTileRows))) = v;
+}
+
 // does quantizedComponentSum equal the row's implied sum everywhere (then it need not be stored)?  The implied sum of a packed 1-bit row
 // is its popcount, of a multi-bit row (one byte per dimension) the sum of its codes: over the row_bytes bytes of the row either way
 __global__ __launch_bounds__(256) void bbq_check_x1_kernel(StagedRows in, int64_t n_rows, int32_t row_bytes, int32_t popcount,
@@ -486,13 +543,8 @@ __global__ __launch_bounds__(256) void bbq_check_x1_kernel(StagedRows in, int64_
 
 // compact layout: {min, max} of additionalCorrection over the valid rows of each tile, as f32 (one wave per tile; the f32
 // rounding is inside the bound's allowance for the additive term).  A NaN anywhere makes both ends NaN: no bound, exact path.
-// Runs over the tiles [tile0, ceil(n_rows / 64)): an append starts at the tile its first new row lands in.
-__global__ __launch_bounds__(256) void bbq_tile_add_range_kernel(const double *__restrict__ exact, int64_t n_rows, float *__restrict__ add_range,
-                                                                 int64_t tile0) {
-  const int lane = threadIdx.x & 63;
-  const int64_t tile = tile0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
-  if (tile >= n_tiles) return;
+// The per-tile body, one wave per tile, shared by the two kernels below.
+__device__ __forceinline__ void tile_add_range(const double *__restrict__ exact, int64_t n_rows, float *__restrict__ add_range, int64_t tile, int lane) {
   const int64_t row = tile * kTileRows + lane;
   const bool valid = row < n_rows;
   const double v = valid ? exact[row * 4 + 2] : 0.0;
@@ -508,6 +560,22 @@ __global__ __launch_bounds__(256) void bbq_tile_add_range_kernel(const double *_
     add_range[tile * 2] = nan ? __uint_as_float(0x7fc00000u) : (float)lo;
     add_range[tile * 2 + 1] = nan ? __uint_as_float(0x7fc00000u) : (float)hi;
   }
+}
+// Runs over the tiles [tile0, ceil(n_rows / 64)): an append starts at the tile its first new row lands in.
+__global__ __launch_bounds__(256) void bbq_tile_add_range_kernel(const double *__restrict__ exact, int64_t n_rows, float *__restrict__ add_range,
+                                                                 int64_t tile0) {
+  const int lane = threadIdx.x & 63;
+  const int64_t tile = tile0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows;
+  if (tile >= n_tiles) return;
+  tile_add_range(exact, n_rows, add_range, tile, lane);
+}
+// the same for the tiles listed (an update: the distinct tiles of the rows it replaced, each below ceil(n_rows / 64)); one wave per tile
+__global__ __launch_bounds__(256) void bbq_tile_add_range_list_kernel(const double *__restrict__ exact, int64_t n_rows, float *__restrict__ add_range,
+                                                                      const int64_t *__restrict__ tiles, int64_t n_listed) {
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= n_listed) return;  // uniform per wave
+  tile_add_range(exact, n_rows, add_range, tiles[t], threadIdx.x & 63);
 }
 
 // is every code of these multi-bit rows below 2^index_bits?  What bbq_retile_kernel reports while it writes, asked BEFORE
@@ -648,6 +716,20 @@ hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add
   const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows - tile0;
   if (n_tiles <= 0) return hipSuccess;
   hipLaunchKernelGGL(bbq_tile_add_range_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, exact, n_rows, add_range, tile0);
+  return hipGetLastError();
+}
+
+hipError_t launch_scatter_rows(const TileDest &out, const StagedRows &in, const int32_t *ords, const int64_t *pos, int64_t n_winners,
+                               int32_t index_bits, uint32_t *bad, hipStream_t s) {
+  const int64_t threads = n_winners * (out.geom.w16 + 1);
+  if (threads <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_scatter_rows_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, out, in, ords, pos, n_winners, index_bits, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_add_range_list(const double *exact, int64_t n_rows, float *add_range, const int64_t *tiles, int64_t n_listed, hipStream_t s) {
+  if (n_listed <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_tile_add_range_list_kernel, dim3((unsigned)((n_listed + 3) / 4)), dim3(256), 0, s, exact, n_rows, add_range, tiles, n_listed);
   return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@
 //   bbq_append.cpp   the one path that writes rows into an index - creation and build are appends to an empty one - and the entry
 //                    points that grow an index in place (bbq_index_append*, bbq_index_reserve)
 //   bbq_compact.cpp  rows taken out of an index on the device (bbq_index_compact, bbq_index_remove_rows, bbq_filter_kept_rows)
+//   bbq_update.cpp   rows of an index replaced in place (bbq_index_update*, bbq_update_winners)
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
@@ -311,11 +312,21 @@ void commit(bbq_index *ix, Storage &st, Room &r, int64_t n_rows);
 // rows are refused with BBQ_ERR_UNSUPPORTED, as are multi-bit codes not below 2^indexBits, before anything is written.  A storage
 // that holds neither rows nor room decides whatever the mode: nothing would have to be re-tiled.
 enum class Sums { kDecide, kRequire };
+// n rows in host memory, in the caller's shape -> device scratch (BBQ_ERR_OOM); the copies are enqueued on the aux stream
+int stage_rows(const bbq_index *ix, const uint8_t *codes, const double *corr, int64_t n, DevBuf<uint8_t> &d_codes, DevBuf<double> &d_corr);
+// staged rows asked what `mode` says about their component sums and, for multi-bit rows under kRequire, whether every code is below
+// 2^indexBits (BBQ_ERR_INVALID_ARG).  Nothing of the index is written; returns with the device done.
+int check_device_rows(bbq_index *ix, const uint8_t *d_codes, const double *d_corr, int64_t n, Sums mode);
 // n rows in host memory, in the caller's shape, become the rows behind those `st` holds
 int append_host_rows(bbq_index *ix, Storage &st, const uint8_t *codes, const double *corr, int64_t n, Sums mode);
 // n fp32 rows -> d_vT4, the [ceil(dim/4)][tiles_of(n) * 64] float4 transposed copy, normalized for COSINE and validated: the first NaN
 // / Infinity in row-major order is BBQ_ERR_NAN_INPUT / BBQ_ERR_INF_INPUT with its position in *bad_row, *bad_col (when non-null)
 int stage_vectors(DeviceCtx *ctx, const float *vectors, int64_t n, int32_t dim, int32_t sim, DevBuf<float> &d_vT4, int64_t *bad_row, int32_t *bad_col);
+// the n staged vectors quantized against d_cen into device scratch in the caller's shape (d_codes [n][caller_row_bytes], d_corr [n][4]),
+// without touching the index: what quantize_into hands to the row-major path and what an update scatters.  codes_out / corr_out
+// (optional) get all n rows.  Releases d_vT4.  1-bit rows go through a scratch tile set (launch_build_quantize1 + launch_build_untile).
+int quantize_staged(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d_cen, int32_t sim, double lambda, int32_t iters,
+                    DevBuf<uint8_t> &d_codes, DevBuf<double> &d_corr, uint8_t *codes_out, double *corr_out);
 // the n staged vectors quantized against d_cen become the rows behind those the main storage holds; codes_out / corr_out (optional) get
 // them in the caller's shape.  Releases d_vT4 as soon as it has been read where more memory is needed behind it.
 int quantize_into(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d_cen, int32_t sim, double lambda, int32_t iters, Sums mode,

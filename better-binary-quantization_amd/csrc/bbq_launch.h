@@ -58,6 +58,13 @@ hipError_t launch_check_x1(const StagedRows &in, int64_t n_rows, const TileGeom 
 hipError_t launch_check_code_range(const uint8_t *codes, int64_t count, int32_t index_bits, uint32_t *bad, hipStream_t s);
 // compact layout: each tile's {min, max} of additionalCorrection (read from exact[]) -> add_range[tile][2]
 hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0);
+// the same for the n_listed tiles named (each below ceil(n_rows / 64)): an update's touched tiles
+hipError_t launch_tile_add_range_list(const double *exact, int64_t n_rows, float *add_range, const int64_t *tiles, int64_t n_listed, hipStream_t s);
+// rows in the caller's shape -> the lanes of the rows they replace: staged row pos[i] becomes row ords[pos[i]] for the n_winners
+// entries of pos, which name distinct ords in ascending order (bbq_update_winners); nothing else is written.  ords are rows of `out`;
+// multi-bit codes have been range-checked (launch_check_code_range): *bad is the shared packer's and stays clear
+hipError_t launch_scatter_rows(const TileDest &out, const StagedRows &in, const int32_t *ords, const int64_t *pos, int64_t n_winners,
+                               int32_t index_bits, uint32_t *bad, hipStream_t s);
 // the rows of `src` that map.accept keeps -> the rows [0, map.kept) of `out`, in order, padding lanes of the last tile included.  `out`
 // holds ceil(map.kept / 64) tiles of src's geometry and is not src (the gather runs out of place)
 hipError_t launch_compact_tiles(const TileDest &out, const TileDest &src, const CompactMap &map, hipStream_t s);
@@ -66,5 +73,7 @@ hipError_t launch_compact_tiles(const TileDest &out, const TileDest &src, const 
 hipError_t launch_rerank(const RerankArgs &a, int n_queries, int64_t max_count, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
+// staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place
+hipError_t launch_scatter_vectors(float *out, const float *staged, int32_t dim, const int32_t *ords, const int64_t *pos, int64_t n_winners, hipStream_t s);
 
 }  // namespace bbq

@@ -148,6 +148,35 @@ int bbq_vectors_compact(bbq_vectors *v, const bbq_filter *f) {
   return BBQ_OK;
 }
 
+int bbq_vectors_update(bbq_vectors *v, const int32_t *ords, const float *vectors, int64_t n) {
+  clear_error();
+  if (!v) return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_update: vectors handle is null");
+  if (n < 0) return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_update: n < 0");
+  if (n == 0) return BBQ_OK;
+  if (!ords || !vectors) return fail(BBQ_ERR_INVALID_ARG, "bbq_vectors_update: null argument");
+  std::lock_guard<std::mutex> lk(v->ctx->mu);
+  HIPCHK(hipSetDevice(v->device));
+  std::vector<int64_t> pos;
+  int rc = update_winners(ords, n, v->n, pos);
+  if (rc != BBQ_OK) return rc;
+  hipStream_t st = v->ctx->aux_stream;
+  HIPCHK(hipStreamSynchronize(st));  // bbq_rerank_scores reads the rows on it
+  // the block staged as it came, then the winners scattered to their ords: nothing is written before every allocation has succeeded
+  DevBuf<float> staged;
+  DevBuf<int32_t> d_ords;
+  DevBuf<int64_t> d_pos;
+  const hipError_t e = staged.alloc((size_t)(n * v->dim));
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "bbq_vectors_update: %lld x %d fp32: %s", (long long)n, v->dim, hipGetErrorString(e)); }
+  rc = stage_winners(st, ords, n, pos, d_ords, d_pos);
+  if (rc != BBQ_OK) return rc;
+  const int64_t count = n * v->dim, piece = 64LL << 20;  // 256 MB pieces keep the runtime's pinned staging bounded
+  for (int64_t o = 0; o < count; o += piece)
+    HIPCHK(hipMemcpyAsync(staged + o, vectors + o, (size_t)std::min(piece, count - o) * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(launch_scatter_vectors(v->d, staged, v->dim, d_ords, d_pos, (int64_t)pos.size(), st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BBQ_OK;
+}
+
 int64_t bbq_vectors_size(const bbq_vectors *v) { return v ? v->n : 0; }
 int32_t bbq_vectors_dimension(const bbq_vectors *v) { return v ? v->dim : 0; }
 

@@ -91,7 +91,31 @@ __global__ __launch_bounds__(256) void bbq_compact_vectors_kernel(float *__restr
   }
 }
 
+// bbq_vectors_update: staged fp32 row pos[i] becomes row ords[pos[i]], in place.  pos lists the block's winners, one per distinct ord
+// (bbq_update_winners), so no two waves write one row.  One wave per winner, the row moves as coalesced pieces as above; the staged
+// rows are read once: non-temporal.
+__global__ __launch_bounds__(256) void bbq_scatter_vectors_kernel(float *__restrict__ out, const float *__restrict__ staged, int32_t dim,
+                                                                 const int32_t *__restrict__ ords, const int64_t *__restrict__ pos, int64_t n_winners) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n_winners) return;  // uniform per wave
+  const int64_t p = pos[i];
+  const float *s = staged + p * dim;
+  float *d = out + (int64_t)ords[p] * dim;
+  if ((dim & 3) == 0) {
+    for (int c = lane; c < dim / 4; c += 64) reinterpret_cast<f32x4 *>(d)[c] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(s) + c);
+  } else {
+    for (int c = lane; c < dim; c += 64) d[c] = __builtin_nontemporal_load(s + c);
+  }
+}
+
 }  // namespace
+
+hipError_t launch_scatter_vectors(float *out, const float *staged, int32_t dim, const int32_t *ords, const int64_t *pos, int64_t n_winners, hipStream_t s) {
+  if (n_winners <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bbq_scatter_vectors_kernel, dim3((unsigned)((n_winners + 3) / 4)), dim3(256), 0, s, out, staged, dim, ords, pos, n_winners);
+  return hipGetLastError();
+}
 
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s) {
   if (map.kept <= 0) return hipSuccess;

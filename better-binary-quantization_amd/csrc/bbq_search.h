@@ -81,6 +81,11 @@ int search_latency_chain(const SearchCall &c, int32_t *out_idx, float *out_score
 // ---- bbq_compact.cpp: the map of a compaction by `f` - its accept words as they are on the device, and the ranks of its tiles
 // uploaded into d_rank (BBQ_ERR_OOM).  Context mutex held, device current; returns with the ranks on the device.
 int stage_compact_map(const bbq_filter *f, DevBuf<uint32_t> &d_rank, CompactMap *map);
+// ---- bbq_update.cpp: the entries of an update block that take effect - positions into the block, ascending by ord, one per distinct
+// ord (its last occurrence); an ord outside [0, n_rows) is BBQ_ERR_INVALID_ARG.  Host only.  stage_winners uploads the block's ords
+// and the winner list (BBQ_ERR_OOM), enqueued on `s`.
+int update_winners(const int32_t *ords, int64_t n, int64_t n_rows, std::vector<int64_t> &pos);
+int stage_winners(hipStream_t s, const int32_t *ords, int64_t n, const std::vector<int64_t> &pos, DevBuf<int32_t> &d_ords, DevBuf<int64_t> &d_pos);
 // ---- bbq_dense.cpp
 int dense_search_one(const SearchCall &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n);
 

@@ -56,6 +56,9 @@ export declare class BinaryQuantizationFormat {
    *  device index grows in place.  Not supported on a multi-device index (BBQ_DEVICES).  A RowFilter made before the call no longer
    *  fits the index.  Returns targetVectors. */
   appendVectors(targetVectors: BinarizedByteVectorValues, vectors: Float32Array[]): BinarizedByteVectorValues;
+  /** extension: `vectors`, quantized against targetVectors' centroid as appendVectors quantizes them, replace the rows `ords` in place
+   *  (the last of equal ords wins); size, ords and RowFilters made earlier stay valid.  Returns targetVectors. */
+  updateVectors(targetVectors: BinarizedByteVectorValues, ords: Int32Array | number[], vectors: Float32Array[]): BinarizedByteVectorValues;
   /** extension: targetVectors becomes the set over the rows `filter` accepts, in order (new ord of old row r = accepted rows below r); a
    *  device copy is compacted on the device, the host copies follow.  `filter`: a RowFilter of targetVectors or anything createRowFilter
    *  takes.  Not supported on a multi-device index (BBQ_DEVICES).  The filter used and every RowFilter made earlier no longer fit the
@@ -111,6 +114,8 @@ export declare class DeviceVectors {
   trueScores(query: Float32Array, rows: ArrayLike<number>, similarityFunction?: VectorSimilarityFunction): Float64Array;
   /** extension: the fp32 rows of a block BinaryQuantizationFormat.appendVectors has added to the index get the next ords */
   append(vectors: Float32Array[]): DeviceVectors;
+  /** extension: the fp32 rows of a block BinaryQuantizationFormat.updateVectors has put into the index replace the rows `ords` */
+  update(ords: Int32Array | number[], vectors: Float32Array[]): DeviceVectors;
   /** extension: the fp32 rows follow BinaryQuantizationFormat.compactVectors: the rows `filter` accepts are kept, in order, on the device */
   compact(filter: RowFilter): DeviceVectors;
   dispose(): void;

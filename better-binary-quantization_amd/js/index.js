@@ -124,6 +124,16 @@ class BinarizedByteVectorValuesImpl {
     if (!this._rowBytes && n > 0) this._rowBytes = codes.length / n;
     this._size += n;
   }
+  /** the host copies follow an update: the rows of the block are patched in place, in the block's order - the last of equal ords wins, as on
+   *  the device - when copies exist; copies that do not exist yet are fetched from the updated device index later: never a stale copy */
+  _updated(ords, codes, corr) {
+    if (!this._codes) return;
+    const rb = this._rowBytes;
+    for (let i = 0; i < ords.length; i++) {
+      this._codes.set(codes.subarray(i * rb, (i + 1) * rb), ords[i] * rb);
+      this._corr.set(corr.subarray(4 * i, 4 * i + 4), 4 * ords[i]);
+    }
+  }
   /** the host copies follow a compaction - the rows `mask` keeps, in order - or (no mask: the accept set is on the device alone) are left to be fetched again: never a stale copy */
   _compacted(mask, kept) {
     if (!mask) {
@@ -478,6 +488,38 @@ class BinaryQuantizationFormat {
       if (targetVectors._device) native.indexAppendRows(targetVectors._device, r.codes, r.corr, vectors.length);  // a device copy that exists follows
     }
     targetVectors._appended(r.codes, r.corr, vectors.length);
+    return targetVectors;
+  }
+
+  /**
+   * extension (not in the reference, whose index is immutable): `vectors` quantized against targetVectors' centroid - as appendVectors
+   * quantizes them - REPLACE the rows `ords` (an Int32Array or array of ords, one per vector); among equal ords the last one wins.  The
+   * size and every ord stay, so a RowFilter made before the call stays valid.  The device index is updated in place (libbbq
+   * bbq_index_update); without a device the rows are quantized on the host, and a device copy that exists follows.  A multi-device
+   * index (BBQ_DEVICES) throws the library's unsupported message.  On an error nothing has changed.  Returns targetVectors.
+   */
+  updateVectors(targetVectors, ords, vectors) {
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (!ords || !vectors || ords.length !== vectors.length) throw new Error('ords 数量与向量数量不匹配');
+    if (vectors.length === 0) return targetVectors;
+    const dim = targetVectors.dimension(), q = this.quantizer, ib = targetVectors._indexBits, n = targetVectors.size();
+    for (let i = 0; i < vectors.length; i++) {
+      const v = vectors[i];
+      if (!v) throw new Error('向量 ' + i + ' 不能为空');
+      if (v.length !== dim) throw new Error('向量 ' + i + ' 维度 ' + v.length + ' 与第一个向量维度 ' + dim + ' 不匹配');
+    }
+    if (ib !== this.config.indexBits) throw new Error('indexBits ' + this.config.indexBits + ' 与目标向量集合的 ' + ib + ' 不匹配');
+    // Int32Array.from would wrap an ord outside int32 and drop a fraction: another row would be replaced in its place
+    for (let i = 0; i < ords.length; i++) if (!Number.isInteger(ords[i]) || ords[i] < 0 || ords[i] >= n) throw new Error('向量索引 ' + ords[i] + ' 不存在');
+    const o32 = Int32Array.from(ords), flat = flatten(vectors, dim), sim = simOrdinal(q.similarityFunction);
+    let r;
+    if (process.env.BBQ_HOST_QUANTIZER !== '1' && native.deviceCount() > 0) {
+      r = native.indexUpdate(targetVectors._deviceIndex(), o32, flat, vectors.length, dim, targetVectors.getCentroid(), sim, q.lambda, q.iters);
+    } else {
+      r = native.quantizeRows(flat, vectors.length, dim, targetVectors.getCentroid(), sim, ib, q.lambda, q.iters, Number(process.env.BBQ_THREADS || 0));
+      if (targetVectors._device) native.indexUpdateRows(targetVectors._device, o32, r.codes, r.corr, vectors.length);  // a device copy that exists follows
+    }
+    targetVectors._updated(o32, r.codes, r.corr);
     return targetVectors;
   }
 
@@ -855,6 +897,15 @@ class DeviceVectors {
     for (let i = 0; i < vectors.length; i++) if (!vectors[i] || vectors[i].length !== this.dim) throw new Error('向量维度不匹配');
     native.vectorsAppend(this._handle(), flatten(vectors, this.dim), vectors.length, this.dim);
     this.length += vectors.length;
+    return this;
+  }
+  /** extension: the fp32 rows of a block updateVectors has put into the index replace the rows `ords`; the last of equal ords wins (libbbq bbq_vectors_update) */
+  update(ords, vectors) {
+    if (!ords || !vectors || ords.length !== vectors.length) throw new Error('ords 数量与向量数量不匹配');
+    if (vectors.length === 0) return this;
+    for (let i = 0; i < vectors.length; i++) if (!vectors[i] || vectors[i].length !== this.dim) throw new Error('向量维度不匹配');
+    for (let i = 0; i < ords.length; i++) if (!Number.isInteger(ords[i]) || ords[i] < 0 || ords[i] >= this.length) throw new Error('向量索引 ' + ords[i] + ' 不存在');
+    native.vectorsUpdate(this._handle(), Int32Array.from(ords), flatten(vectors, this.dim), vectors.length, this.dim);
     return this;
   }
   /** extension: the fp32 rows follow a compaction of the index by the same RowFilter, on the device (libbbq bbq_vectors_compact) */

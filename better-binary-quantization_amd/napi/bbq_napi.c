@@ -297,6 +297,75 @@ static napi_value IndexAppendRows(napi_env env, napi_callback_info info) {
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
+/* indexUpdate(handle, ords Int32Array[n], flat Float32Array, n, dim, centroid Float32Array, sim, lambda, iters) -> {codes, corr}
+ * raw rows quantized on the device against the index's centroid replace the rows `ords` in place (bbq_index_update); codes / corr
+ * hold all n rows of the block */
+static napi_value IndexUpdate(napi_env env, napi_callback_info info) {
+  napi_value a[9];
+  if (!get_args(env, info, 9, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *ords, *vec, *cen; size_t ol, vlen, clen;
+  int64_t n, dim, sim, iters; double lambda;
+  if (!get_typed(env, a[1], napi_int32_array, &ords, &ol) || !get_typed(env, a[2], napi_float32_array, &vec, &vlen) || !get_i64(env, a[3], &n) ||
+      !get_i64(env, a[4], &dim) || !get_typed(env, a[5], napi_float32_array, &cen, &clen) || !get_i64(env, a[6], &sim) ||
+      !get_f64(env, a[7], &lambda) || !get_i64(env, a[8], &iters)) return NULL;
+  if (n < 0 || dim != bbq_index_dimension(ix) || (size_t)(n * dim) != vlen || clen != (size_t)dim || ol != (size_t)n) {
+    napi_throw_range_error(env, NULL, "bbq_napi: n*dim does not match the arrays or the index"); return NULL;
+  }
+  const int64_t ib = bbq_index_bits(ix);
+  void *codes, *corr;
+  napi_value tcodes = new_typed(env, napi_uint8_array, (size_t)n * (size_t)(ib == 1 ? (dim + 7) / 8 : dim), 1, &codes);
+  napi_value tcorr = new_typed(env, napi_float64_array, (size_t)n * 4, 8, &corr);
+  if (!tcodes || !tcorr) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_index_update(ix, (const int32_t *)ords, (const float *)vec, n, (const float *)cen, (int32_t)sim, lambda, (int32_t)iters,
+                            (uint8_t *)codes, (double *)corr, NULL, NULL);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "codes", tcodes); set_prop(env, o, "corr", tcorr);
+  return o;
+}
+
+/* indexUpdateRows(handle, ords Int32Array[n], codes Uint8Array, corr Float64Array, n): rows already quantized (bbq_index_update_rows) */
+static napi_value IndexUpdateRows(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!get_args(env, info, 5, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *ords, *codes, *corr; size_t ol, cl, rl;
+  int64_t n;
+  if (!get_typed(env, a[1], napi_int32_array, &ords, &ol) || !get_typed(env, a[2], napi_uint8_array, &codes, &cl) ||
+      !get_typed(env, a[3], napi_float64_array, &corr, &rl) || !get_i64(env, a[4], &n)) return NULL;
+  const int64_t dim = bbq_index_dimension(ix);
+  if (n < 0 || ol != (size_t)n || rl != (size_t)n * 4 || cl != (size_t)n * (size_t)(bbq_index_bits(ix) == 1 ? (dim + 7) / 8 : dim)) {
+    napi_throw_range_error(env, NULL, "bbq_napi: array sizes do not match n/dim"); return NULL;
+  }
+  int rc = bbq_index_update_rows(ix, (const int32_t *)ords, (const uint8_t *)codes, (const double *)corr, n);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
+/* updateWinners(ords Int32Array, rows) -> Float64Array: the positions into the block that take effect, ascending by ord, the last
+ * occurrence of every distinct ord (bbq_update_winners; host only) */
+static napi_value UpdateWinners(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  void *ords; size_t ol;
+  int64_t rows;
+  if (!get_typed(env, a[0], napi_int32_array, &ords, &ol) || !get_i64(env, a[1], &rows)) return NULL;
+  int64_t *pos = (int64_t *)calloc(ol + 1, sizeof(int64_t)), m = 0;
+  if (!pos) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_update_winners((const int32_t *)ords, (int64_t)ol, rows, pos, (int64_t)ol, &m);
+  if (rc != BBQ_OK) { free(pos); return throw_bbq(env, rc); }
+  void *out;
+  napi_value t = new_typed(env, napi_float64_array, (size_t)m, 8, &out);
+  if (!t) { free(pos); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  for (int64_t i = 0; i < m; ++i) ((double *)out)[i] = (double)pos[i];
+  free(pos);
+  return t;
+}
+
 /* indexReserve(handle, rows) -> capacity in rows (bbq_index_reserve, bbq_index_capacity) */
 static napi_value IndexReserve(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -657,6 +726,24 @@ static napi_value VectorsAppend(napi_env env, napi_callback_info info) {
   napi_value u; napi_get_undefined(env, &u); return u;
 }
 
+/* vectorsUpdate(handle, ords Int32Array[n], flat Float32Array, n, dim): the fp32 rows of an update block (bbq_vectors_update) */
+static napi_value VectorsUpdate(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!get_args(env, info, 5, a)) return NULL;
+  bbq_vectors *v = unbox_vectors(env, a[0]);
+  if (!v) return NULL;
+  void *ords, *vec; size_t ol, vlen;
+  int64_t n, dim;
+  if (!get_typed(env, a[1], napi_int32_array, &ords, &ol) || !get_typed(env, a[2], napi_float32_array, &vec, &vlen) || !get_i64(env, a[3], &n) ||
+      !get_i64(env, a[4], &dim)) return NULL;
+  if (n < 0 || dim != bbq_vectors_dimension(v) || (size_t)(n * dim) != vlen || ol != (size_t)n) {
+    napi_throw_range_error(env, NULL, "bbq_napi: n*dim does not match the arrays or the vectors"); return NULL;
+  }
+  int rc = bbq_vectors_update(v, (const int32_t *)ords, (const float *)vec, n);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
 /* vectorsCompact(vectors handle, filter handle) -> rows afterwards: the fp32 rows follow a compaction of the index (bbq_vectors_compact) */
 static napi_value VectorsCompact(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -866,6 +953,10 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"quantizeRows", NULL, QuantizeRows, NULL, NULL, NULL, napi_default, NULL},
       {"indexAppend", NULL, IndexAppend, NULL, NULL, NULL, napi_default, NULL},
       {"indexAppendRows", NULL, IndexAppendRows, NULL, NULL, NULL, napi_default, NULL},
+      {"indexUpdate", NULL, IndexUpdate, NULL, NULL, NULL, napi_default, NULL},
+      {"indexUpdateRows", NULL, IndexUpdateRows, NULL, NULL, NULL, napi_default, NULL},
+      {"updateWinners", NULL, UpdateWinners, NULL, NULL, NULL, napi_default, NULL},
+      {"vectorsUpdate", NULL, VectorsUpdate, NULL, NULL, NULL, napi_default, NULL},
       {"indexReserve", NULL, IndexReserve, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsAppend", NULL, VectorsAppend, NULL, NULL, NULL, napi_default, NULL},
       {"indexCompact", NULL, IndexCompact, NULL, NULL, NULL, napi_default, NULL},

@@ -127,6 +127,42 @@ class BinaryQuantizationFormat:
         targetVectors._corr = np.concatenate([targetVectors._corr, corr])
         return targetVectors
 
+    def updateVectors(self, targetVectors, ords, vectors):
+        """extension: `vectors` quantized against targetVectors' centroid - as appendVectors quantizes them - REPLACE the rows `ords`
+        in place; among equal ords the last one wins.  The size and every ord stay, so row filters made earlier stay valid.  On the
+        device when there is one (bbq_index_update), on the host otherwise.  Returns targetVectors."""
+        if targetVectors is None:
+            raise Exception("目标向量集合不能为空")
+        o = np.asarray(ords, np.int64).ravel()
+        if len(vectors) != o.shape[0]:
+            raise Exception("ords 数量 %d 与向量数量 %d 不匹配" % (o.shape[0], len(vectors)))
+        if len(vectors) == 0:
+            return targetVectors
+        dim = targetVectors.dimension()
+        for i, v in enumerate(vectors):
+            if len(v) != dim:
+                raise Exception("向量 %d 维度 %d 与第一个向量维度 %d 不匹配" % (i, len(v), dim))
+        if targetVectors._index_bits != self._config["indexBits"]:
+            raise Exception("indexBits %d 与目标向量集合的 %d 不匹配" % (self._config["indexBits"], targetVectors._index_bits))
+        bad = o[(o < 0) | (o >= targetVectors.size())]
+        if bad.size:
+            raise Exception("向量索引 %d 不存在" % int(bad[0]))
+        v = np.asarray(vectors, np.float32)
+        sim = capi.SIMS[self._sim]
+        try:
+            if capi.device_count() > 0:
+                codes, corr = targetVectors._device().update(o, v, targetVectors.getCentroid(), sim, self._lambda, self._iters)
+            else:
+                codes, corr = capi.quantize_rows(v, targetVectors.getCentroid(), sim, targetVectors._index_bits, self._lambda, self._iters)
+            win = capi.update_winners(o, targetVectors.size())
+        except capi.BBQError as e:
+            raise Exception(str(e))
+        # the host copies follow (new arrays: rows handed out earlier stay valid)
+        targetVectors._codes, targetVectors._corr = targetVectors._codes.copy(), targetVectors._corr.copy()
+        targetVectors._codes[o[win]] = codes[win]
+        targetVectors._corr[o[win]] = corr[win]
+        return targetVectors
+
     def compactVectors(self, targetVectors, accept):
         """extension: targetVectors becomes the set over the rows `accept` keeps - a bool mask of length size(), an array of ords, or
         a predicate ord -> bool - in order: the new ord of old row r is the number of kept rows below r.  The resident index is

@@ -29,6 +29,7 @@ SYMBOLS = [
     "bbq_filter_create", "bbq_filter_create_rows", "bbq_filter_destroy", "bbq_filter_count", "bbq_search_filtered_batch", "bbq_filter_plan",
     "bbq_index_append_rows", "bbq_index_append", "bbq_index_reserve", "bbq_index_capacity", "bbq_vectors_append", "bbq_quantize_rows",
     "bbq_index_compact", "bbq_index_remove_rows", "bbq_vectors_compact", "bbq_filter_kept_rows",
+    "bbq_index_update_rows", "bbq_index_update", "bbq_vectors_update", "bbq_update_winners",
 ]
 
 
@@ -154,6 +155,10 @@ def lib():
     L.bbq_index_remove_rows.argtypes = [vp, vp, i64]
     L.bbq_vectors_compact.argtypes = [vp, vp]
     L.bbq_filter_kept_rows.argtypes = [vp, i64, vp, i64, C.POINTER(i64)]
+    L.bbq_index_update_rows.argtypes = [vp, vp, vp, vp, i64]
+    L.bbq_index_update.argtypes = [vp, vp, vp, i64, vp, i32, dbl, i32, vp, vp, C.POINTER(i64), C.POINTER(i32)]
+    L.bbq_vectors_update.argtypes = [vp, vp, vp, i64]
+    L.bbq_update_winners.argtypes = [vp, i64, i64, vp, i64, C.POINTER(i64)]
     L.bbq_quantize_rows.argtypes = [vp, i64, i32, vp, i32, i32, dbl, i32, i32, vp, vp, C.POINTER(i64), C.POINTER(i32)]
     _lib = L
     return L
@@ -366,6 +371,32 @@ class Index:
         self.n = int(lib().bbq_index_size(self._h))
         return codes, corr
 
+    def update_rows(self, ords, codes, corr):
+        """bbq_index_update_rows: rows already quantized, in the shape the constructor takes them, replace the rows `ords` names in
+        place (the last of equal ords wins).  The size, and with it every filter, stays."""
+        o = _ords(ords)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        corr = np.ascontiguousarray(corr, np.float64)
+        width = (self.dim + 7) // 8 if self.index_bits == 1 else self.dim
+        if codes.ndim != 2 or codes.shape[1] != width or corr.shape != (codes.shape[0], 4) or o.shape[0] != codes.shape[0]:
+            raise BBQError(ERR_DIM_MISMATCH, "ords must be [n], codes [n, %d] and corr [n, 4]" % width)
+        _chk(lib().bbq_index_update_rows(self._h, _ptr(o), _ptr(codes), _ptr(corr), o.shape[0]))
+
+    def update(self, ords, vectors, centroid, sim, lam=0.1, iters=5, want_host_copy=True):
+        """bbq_index_update: raw fp32 rows quantized on the device against `centroid` (the one the index was built with) replace
+        the rows `ords` names in place.  Returns (codes, corr) of ALL rows of the block, or (None, None) unless want_host_copy.  A
+        NaN / Infinity raises BBQError with .bad_row / .bad_col (position inside `vectors`) and leaves the index as it was."""
+        o = _ords(ords)
+        v = np.ascontiguousarray(vectors, np.float32)
+        cen = np.ascontiguousarray(centroid, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.dim or cen.shape != (self.dim,) or o.shape[0] != v.shape[0]:
+            raise BBQError(ERR_DIM_MISMATCH, "向量维度不匹配")
+        n = v.shape[0]
+        codes = np.zeros((n, (self.dim + 7) // 8 if self.index_bits == 1 else self.dim), np.uint8) if want_host_copy else None
+        corr = np.zeros((n, 4), np.float64) if want_host_copy else None
+        _chk_pos(lambda br, bc: lib().bbq_index_update(self._h, _ptr(o), _ptr(v), n, _ptr(cen), int(sim), lam, iters, _ptr(codes), _ptr(corr), br, bc))
+        return codes, corr
+
     def compact(self, flt):
         """bbq_index_compact: the index becomes the index over the rows `flt` (a Filter of this index) accepts, in order, on the
         device.  The filter - and any made earlier - no longer fits afterwards; kept_rows(mask) tells the old ord of every new row."""
@@ -553,6 +584,21 @@ def filter_plan(mask, k_dev, first_segment_rows=4096, growth=8):
     return [tuple(int(v) for v in row) for row in segs[:n.value]]
 
 
+def _ords(ords):
+    """ords as the C ABI takes them: int32, values beyond its range clipped to its ends (out of range for every index either way)"""
+    return np.ascontiguousarray(np.asarray(ords, np.int64).ravel().clip(-2**31, 2**31 - 1), np.int32)
+
+
+def update_winners(ords, n_rows):
+    """the entries of an update block that take effect: positions into `ords`, ascending by ord, one per distinct ord - its last
+    occurrence (bbq_update_winners; host only)"""
+    o = _ords(ords)
+    out = np.zeros(o.shape[0], np.int64)
+    n = C.c_int64(0)
+    _chk(lib().bbq_update_winners(_ptr(o), o.shape[0], int(n_rows), _ptr(out), out.shape[0], C.byref(n)))
+    return out[:n.value]
+
+
 def kept_rows(mask):
     """the old ord of every row a compaction by `mask` keeps, ascending (bbq_filter_kept_rows; host only)"""
     m = np.ascontiguousarray(mask, np.bool_).ravel()
@@ -644,6 +690,14 @@ class Vectors:
         """bbq_vectors_compact: the fp32 rows follow a compaction of the index by the same filter"""
         _chk(lib().bbq_vectors_compact(self._h, flt._h if flt is not None else None))
         self.n = int(lib().bbq_vectors_size(self._h))
+
+    def update(self, ords, vectors):
+        """bbq_vectors_update: the fp32 rows follow an update of the index - `vectors` become the rows `ords` (the last of equal ords wins)"""
+        o = _ords(ords)
+        v = np.ascontiguousarray(vectors, np.float32)
+        if v.ndim != 2 or v.shape[1] != self.dim or o.shape[0] != v.shape[0]:
+            raise BBQError(ERR_DIM_MISMATCH, "向量维度不匹配")
+        _chk(lib().bbq_vectors_update(self._h, _ptr(o), _ptr(v), v.shape[0]))
 
     def rerank_scores(self, queries, rows_per_query, true_sim=1):
         """computeSimilarity(queries[q], vectors[r]) for r in rows_per_query[q]; returns a list of f64 arrays"""

@@ -34,7 +34,8 @@ extern "C" {
                               3: creation options (corrections layout), asynchronous shard scans with shard-local answers,
                                  bbq_merge_answers, persistence of shards and multi-device indexes
                               (still 3: filtered search - bbq_filter_*, bbq_search_filtered_batch - only adds symbols, as do the appends
-                              and the compaction - bbq_index_compact, bbq_index_remove_rows, bbq_vectors_compact, bbq_filter_kept_rows) */
+                              and the compaction - bbq_index_compact, bbq_index_remove_rows, bbq_vectors_compact, bbq_filter_kept_rows - and the
+                              in-place updates - bbq_index_update_rows, bbq_index_update, bbq_vectors_update, bbq_update_winners) */
 
 /* status codes */
 enum {
@@ -288,7 +289,7 @@ int bbq_search_filtered_batch(bbq_index *idx, const bbq_filter *f, int32_t n_que
  * The rows are gathered OUT OF PLACE into new allocations and the old ones are released behind the gather: the peak is old + new,
  * and afterwards the memory of the removed rows is free.
  * Out of scope (BBQ_ERR_UNSUPPORTED), as for filters and appends: a multi-device handle, a non-root shard, an index with a pilot
- * replica.  Updating a row in place and re-centring are not offered.  The call takes the device context's lock and first retires what
+ * replica.  Re-centring is not offered (giving an ord new contents: "Replacing rows" below).  The call takes the device context's lock and first retires what
  * the index has in flight, as an append does.
  * The filter used, and any filter made earlier, no longer fits the new size: bbq_search_filtered_batch refuses it
  * (BBQ_ERR_INVALID_ARG); make a new filter over the compacted index. */
@@ -300,6 +301,43 @@ int bbq_index_remove_rows(bbq_index *idx, const int32_t *rows, int64_t n);
  * (bits at and beyond n_rows are ignored), out_rows [cap]; *out_n = |A| even when cap is too small (then BBQ_ERR_INVALID_ARG and
  * nothing is written) */
 int bbq_filter_kept_rows(const uint64_t *accept_bits, int64_t n_rows, int32_t *out_rows, int64_t cap, int64_t *out_n);
+
+/* ------------------------------------------------------------------------------------------
+ * Replacing rows (new; the reference's index is immutable): an existing ord gets new contents, in place.  The ord is the id every
+ * caller holds; "row r replaced by v quantized against the centroid the index was built with" is defined by the reference exactly
+ * as an appended row is.  After an update the index is indistinguishable from one created whole (bbq_index_create_opts) over the
+ * same rows with the rows at ords[i] replaced, with the same centroid_dp, index_bits and options: bbq_index_size and
+ * bbq_index_capacity (both unchanged), every search entry point (indices, f32 score bits, order, ties), bbq_score_rows, rerank
+ * (together with bbq_vectors_update), bbq_shard_scan* on a root index, bbq_index_export, the bytes bbq_index_save writes (the
+ * untouched lanes, the padding lanes of the last tile and every touched tile's add range included), and a later append or
+ * compaction.
+ * Filters: the size does not change, so a bbq_filter made BEFORE an update still fits and still means the same ords;
+ * bbq_search_filtered_batch with it answers over the updated rows.
+ * Duplicates: among equal ords in one call the last one wins, as applying the block in order would; every row of the block is
+ * still validated, losers included.  n == 0: BBQ_OK, nothing changes.  An ord equal to the size is not an append: out of range.
+ * Strong guarantee: a call that fails - an ord outside [0, size) (BBQ_ERR_INVALID_ARG), NaN / Infinity (codes, messages and
+ * *bad_row / *bad_col as bbq_index_append, positions inside this call's block), a multi-bit code >= 2^indexBits
+ * (BBQ_ERR_INVALID_ARG), a row the record format cannot hold (BBQ_ERR_UNSUPPORTED), out of memory for the scratch (BBQ_ERR_OOM),
+ * a bbq_shard_scan_begin batch of this index that has not been waited for (BBQ_ERR_INVALID_ARG) - has not written a byte the index
+ * can see, not even in a padding lane: the block is staged, quantized and checked in scratch memory first, and the writes that
+ * follow go into allocations that already exist.
+ * The record format is never re-decided, as in a compaction.  An index without explicit component sums refuses a row whose
+ * quantizedComponentSum is not its popcount / code sum (BBQ_ERR_UNSUPPORTED, as an append does).  An index that stores explicit
+ * sums takes any row and keeps storing them: its files equal the twin's exactly when the twin's own creation decides to store
+ * them; its answers and its export always match.
+ * Out of scope (BBQ_ERR_UNSUPPORTED), as for appends: a multi-device handle, a non-root shard, an index with a pilot replica.
+ * Re-centring is not offered.  The call takes the device context's lock and first retires what the index has in flight, as an
+ * append does. */
+/* rows already quantized, shapes as bbq_index_append_rows; ords [n] */
+int bbq_index_update_rows(bbq_index *idx, const int32_t *ords, const uint8_t *codes, const double *corr, int64_t n);
+/* raw fp32 rows [n*dim] quantized ON THE DEVICE against `centroid`, arguments as bbq_index_append; codes_out / corr_out (host, may be
+ * NULL) get all n rows of the block, duplicate losers included.  (bbq_vectors_update, below, is the fp32 side of the rerank recipe.) */
+int bbq_index_update(bbq_index *idx, const int32_t *ords, const float *vectors, int64_t n, const float *centroid, int32_t sim,
+                     double lambda, int32_t iters, uint8_t *codes_out, double *corr_out, int64_t *bad_row, int32_t *bad_col);
+/* host only, no device: which entries of an update block take effect.  out_pos [cap] = positions i into the block, ascending by
+ * ords[i], one per distinct ord - the LAST occurrence; *out_n = their number even when cap is too small (then BBQ_ERR_INVALID_ARG,
+ * nothing written).  An ord outside [0, n_rows): BBQ_ERR_INVALID_ARG. */
+int bbq_update_winners(const int32_t *ords, int64_t n, int64_t n_rows, int64_t *out_pos, int64_t cap, int64_t *out_n);
 
 /* Per-row results of computeBatchQuantizedScores (src/binaryQuantizedScorer.ts:389-400) for the
  * contiguous ords [row_begin, row_begin+row_count): bitDotProduct (integer qcDist), the f64 score and
@@ -424,6 +462,9 @@ int bbq_vectors_append(bbq_vectors *v, const float *vectors, int64_t n);
 /* the fp32 side of the rerank recipe follows a compaction of the index (bbq_index_compact): f->n_rows must equal bbq_vectors_size(v),
  * same device; the rows f accepts are kept, in order, gathered out of place on the device - storage afterwards is exactly |A| rows */
 int bbq_vectors_compact(bbq_vectors *v, const bbq_filter *f);
+/* the fp32 side of the rerank recipe follows an update of the index (bbq_index_update*): vectors [n*dim] become the rows ords [n],
+ * the last of equal ords wins; an ord outside [0, bbq_vectors_size(v)): BBQ_ERR_INVALID_ARG.  On failure nothing has changed. */
+int bbq_vectors_update(bbq_vectors *v, const int32_t *ords, const float *vectors, int64_t n);
 void bbq_vectors_destroy(bbq_vectors *v);
 int64_t bbq_vectors_size(const bbq_vectors *v);
 int32_t bbq_vectors_dimension(const bbq_vectors *v);
