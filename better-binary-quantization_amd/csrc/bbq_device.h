@@ -367,6 +367,20 @@ struct RerankArgs {
   double *out;             // [offsets[Q]] computeSimilarity(query, row)
 };
 
+// scoring chosen rows (bbq_gather_kernels.hip): query q is scored against the rows ords[offsets[q] .. offsets[q+1]), one lane per entry
+constexpr int kGatherThreads = 256;  // entries per workgroup (four waves share the staged query)
+struct GatherArgs {
+  IndexView idx;
+  const uint4 *qplanes;        // [Q][w16][QU] staged query data, as ScanArgs::qplanes
+  const QueryParams *qparams;  // [Q]
+  const int64_t *offsets;      // [Q+1] ascending from 0
+  const int32_t *ords;         // [offsets[Q]] rows of idx, all in [0, idx.n_rows): the host has checked every one
+  // outputs, indexed like ords; each may be null
+  int32_t *out_qcdist;
+  double *out_score64;
+  float *out_score32;
+};
+
 constexpr int kFinalizeThreads = 1024;
 constexpr int kFinalizeJobs = 4096;      // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)
 constexpr int kFinalizeKeyCap = 12288;   // LDS key buffer of the finalize kernel (new keys + running top-k)

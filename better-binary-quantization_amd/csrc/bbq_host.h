@@ -10,6 +10,7 @@
 //   bbq_compact.cpp  rows taken out of an index on the device (bbq_index_compact, bbq_index_remove_rows, bbq_filter_kept_rows)
 //   bbq_update.cpp   rows of an index replaced in place (bbq_index_update*, bbq_update_winners)
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
+//   bbq_gather.cpp   scoring and ranking chosen rows (bbq_score_ords*, bbq_search_ords_batch)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
 // bbq_entry.h is the codec of the 64-bit entries, keys and answer headers; bbq_workqueue.h the host threads' job queue.
@@ -130,6 +131,7 @@ struct DeviceCtx {
   hipStream_t aux_stream = nullptr;   // dense path / bbq_score_rows / index build: never touches an in-flight slot
   DevBuf<uint8_t> d_aux_qbuf;
   DevBuf<uint32_t> d_aux_flags;
+  DevBuf<uint8_t> d_gather;          // grow-only scratch of bbq_score_ords* (bbq_gather.cpp): one launch's offsets, queries, ords and outputs
   int last_big_slot = -1;             // slot whose ev_big marks the end of the most recently enqueued big sweep
   // latency path (bbq_latency_kernels.hip): the answer of a single-query call lands in mapped, coherent host memory and the host
   // polls a sequence word behind it: [0] sequence, [8 ..) header + entries
@@ -343,6 +345,8 @@ int multi_search_batch(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, 
                        int64_t k, int32_t *out_idx, float *out_score, int64_t *out_n);
 int multi_score_rows(bbq_index *ix, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim, int64_t row_begin,
                      int64_t row_count, int32_t *out_qcdist, double *out_score64, float *out_score32);
+int multi_score_ords(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim,
+                     const int64_t *offsets, const int32_t *ords, int32_t *out_qcdist, double *out_score64, float *out_score32);
 int multi_export(bbq_index *ix, uint8_t *codes, double *corr);
 int multi_set_option(bbq_index *ix, const char *name, int64_t v);
 int multi_get_stats(bbq_index *ix, bbq_stats *out);

@@ -1,5 +1,5 @@
 // bbq_launch.h - host-callable launch wrappers of every kernel file: the sweeps, finalize and pack (bbq_kernels.hip, bbq_filter_kernels.hip,
-// bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip) and the rerank (bbq_rerank_kernels.hip)
+// bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip), the rerank (bbq_rerank_kernels.hip) and the scoring of chosen rows (bbq_gather_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbq_device.h"
@@ -71,6 +71,9 @@ hipError_t launch_compact_tiles(const TileDest &out, const TileDest &src, const 
 
 // exact rerank (bbq_rerank_kernels.hip): one wave per 64 candidates of a query; max_count = longest candidate list
 hipError_t launch_rerank(const RerankArgs &a, int n_queries, int64_t max_count, hipStream_t s);
+// scoring chosen rows (bbq_gather_kernels.hip): one workgroup per kGatherThreads entries of a query's list; max_count = longest list,
+// n_queries <= 65535; planes as launch_scan takes them
+hipError_t launch_score_ords(const GatherArgs &a, int planes, int n_queries, int64_t max_count, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 // staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place

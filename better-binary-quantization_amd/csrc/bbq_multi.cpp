@@ -346,6 +346,45 @@ int multi_score_rows(bbq_index *ix, const uint8_t *qquant, const double *qcorr, 
   return BBQ_OK;
 }
 
+// bbq_score_ords_batch on a multi-device handle: every list split by shard, each shard scores its entries (ords become positions among
+// the shard's own rows), the results scattered back to list positions.  The caller has checked offsets and ords.
+int multi_score_ords(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim,
+                     const int64_t *offsets, const int32_t *ords, int32_t *out_qcdist, double *out_score64, float *out_score32) {
+  MultiState *ms = ix->multi;
+  std::lock_guard<std::mutex> lk(ms->mu);
+  if (!out_qcdist && !out_score64 && !out_score32) return BBQ_OK;
+  std::vector<int64_t> sub_off((size_t)n_queries + 1), pos;
+  std::vector<int32_t> sub_ords, tqc;
+  std::vector<double> t64;
+  std::vector<float> t32;
+  for (MultiShard &sh : ms->shards) {
+    pos.clear();
+    sub_ords.clear();
+    for (int32_t q = 0; q < n_queries; ++q) {
+      sub_off[(size_t)q] = (int64_t)pos.size();
+      for (int64_t i = offsets[q]; i < offsets[q + 1]; ++i)
+        if (ords[i] >= sh.r0 && ords[i] < sh.r1) {
+          pos.push_back(i);
+          sub_ords.push_back((int32_t)(ords[i] - sh.r0));
+        }
+    }
+    sub_off[(size_t)n_queries] = (int64_t)pos.size();
+    if (pos.empty()) continue;
+    if (out_qcdist) tqc.resize(pos.size());
+    if (out_score64) t64.resize(pos.size());
+    if (out_score32) t32.resize(pos.size());
+    int rc = bbq_score_ords_batch(sh.ix, n_queries, qquant, qcorr, query_bits, sim, sub_off.data(), sub_ords.data(), out_qcdist ? tqc.data() : nullptr,
+                                  out_score64 ? t64.data() : nullptr, out_score32 ? t32.data() : nullptr);
+    if (rc != BBQ_OK) return rc;
+    for (size_t j = 0; j < pos.size(); ++j) {
+      if (out_qcdist) out_qcdist[pos[j]] = tqc[j];
+      if (out_score64) out_score64[pos[j]] = t64[j];
+      if (out_score32) out_score32[pos[j]] = t32[j];
+    }
+  }
+  return BBQ_OK;
+}
+
 int multi_export(bbq_index *ix, uint8_t *codes, double *corr) {
   MultiState *ms = ix->multi;
   std::lock_guard<std::mutex> lk(ms->mu);

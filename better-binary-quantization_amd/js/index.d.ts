@@ -42,7 +42,7 @@ export declare class BinaryQuantizedScorer {
   /** the single-row path of the reference (src/binaryQuantizedScorer.ts:69-301): host arithmetic, queryBits 1 or 4 */
   computeQuantizedScore(quantizedQuery: Uint8Array, queryCorrections: QuantizationResult, targetVectors: BinarizedByteVectorValues, targetOrd: number, queryBits: number, originalQueryVector?: Float32Array): QuantizedScoreResult;
   computeBatchQuantizedScores(quantizedQuery: Uint8Array, queryCorrections: QuantizationResult, targetVectors: BinarizedByteVectorValues,
-    targetOrds: number[], queryBits: number, originalQueryVector?: Float32Array): QuantizedScoreResult[];
+    targetOrds: number[] | Int32Array, queryBits: number, originalQueryVector?: Float32Array): QuantizedScoreResult[];
   /** src/binaryQuantizedScorer.ts:429-617 */
   computeOriginalScore(originalQuery: Float32Array, targetVector: Float32Array, similarityFunction: VectorSimilarityFunction): number;
   compareScores(originalScore: number, quantizedScore: number): { difference: number; relativeError: number; correlation: number };
@@ -72,6 +72,8 @@ export declare class BinaryQuantizationFormat {
   searchNearestNeighborsBatch(queryVectors: Float32Array[], targetVectors: BinarizedByteVectorValues, k: number): Array<Array<{ index: number; score: number }>>;
   /** extension: searchNearestNeighbors over the ords `filter` accepts (what the reference's loop returns when it visits only those, ascending) */
   searchNearestNeighborsFiltered(query: Float32Array, targetVectors: BinarizedByteVectorValues, filter: RowFilter, k: number): Array<{ index: number; score: number }>;
+  /** extension: searchNearestNeighbors over exactly the rows `ords` names, visited in the order given (any order, duplicates allowed); the list may differ from query to query */
+  searchNearestNeighborsInOrds(query: Float32Array, targetVectors: BinarizedByteVectorValues, ords: Int32Array | number[], k: number): Array<{ index: number; score: number }>;
   /** extension: the same for many queries per call; one filter serves all of them */
   searchNearestNeighborsBatchFiltered(queries: Float32Array[], targetVectors: BinarizedByteVectorValues, filter: RowFilter, k: number): Array<Array<{ index: number; score: number }>>;
   /** src/binaryQuantizationFormat.ts:483-566 with the double-pack bug fixed: binaryValues is the packed row */

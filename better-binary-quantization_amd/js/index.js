@@ -316,7 +316,7 @@ class BinaryQuantizedScorer {
 
   /**
    * computeBatchQuantizedScores(quantizedQuery, queryCorrections, targetVectors, targetOrds, queryBits, originalQueryVector?)
-   * src/binaryQuantizedScorer.ts:315-420.  Scores come from the device (bbq_score_rows).  Two corners follow the reference on the
+   * src/binaryQuantizedScorer.ts:315-420.  Scores come from the device (bbq_score_ords: the rows named and no others).  Two corners follow the reference on the
    * host, row by row:
    *  - originalQueryVector given with a multi-bit query on a 1-bit index: centroidDP = query . centroid instead of centroid . centroid
    *    (:372-381; searchNearestNeighbors never passes it) - the device's integer qcDist, the batch formula restated here;
@@ -339,16 +339,15 @@ class BinaryQuantizedScorer {
     }
     const qc = new Float64Array([queryCorrections.lowerInterval, queryCorrections.upperInterval,
       queryCorrections.additionalCorrection, queryCorrections.quantizedComponentSum]);
-    let lo = targetOrds[0], hi = targetOrds[0];
-    for (let i = 1; i < targetOrds.length; i++) { if (targetOrds[i] < lo) lo = targetOrds[i]; if (targetOrds[i] > hi) hi = targetOrds[i]; }
-    const r = native.scoreRows(targetVectors._deviceIndex(), quantizedQuery, qc, queryBits, simOrdinal(this.similarityFunction), lo, hi - lo + 1);
+    // exactly the rows named, in the order given: the device gathers them (bbq_score_ords) and the outputs are indexed like targetOrds
+    const r = native.scoreOrds(targetVectors._deviceIndex(), quantizedQuery, qc, queryBits, simOrdinal(this.similarityFunction), ordsAsInt32(targetOrds));
     const withQuery = !multibit && originalQueryVector && queryBits !== 1;
     const cdp = withQuery ? targetVectors.getCentroidDP(originalQueryVector) : 0, sim = this.similarityFunction, dimension = targetVectors.dimension();
-    return targetOrds.map(function (ord) {
+    return Array.prototype.map.call(targetOrds, function (ord, i) {
       const ic = targetVectors.getCorrectiveTerms(ord);
-      let score = r.score64[ord - lo];
-      if (withQuery) score = fourBitBatchScore(r.qcDist[ord - lo], queryCorrections, ic, dimension, cdp, sim);
-      return { score: score, bitDotProduct: r.qcDist[ord - lo], corrections: { query: queryCorrections, index: ic } };
+      let score = r.score64[i];
+      if (withQuery) score = fourBitBatchScore(r.qcDist[i], queryCorrections, ic, dimension, cdp, sim);
+      return { score: score, bitDotProduct: r.qcDist[i], corrections: { query: queryCorrections, index: ic } };
     });
   }
   /** computeOriginalScore(originalQuery, targetVector, similarityFunction): computeSimilarity on the fp32 vectors (:429-447) */
@@ -407,6 +406,17 @@ class BinaryQuantizedScorer {
 }
 
 /** rows are unpacked bytes and the reference's batch scorer throws on them (dimension 1 is the one width where it does not) */
+// ords as the addon takes them: an Int32Array (passed through) or any array-like of numbers, values beyond the int32 range clamped to
+// its ends (out of range for every index either way, so the library names them)
+function ordsAsInt32(ords) {
+  if (ords instanceof Int32Array) return ords;
+  const out = new Int32Array(ords.length);
+  for (let i = 0; i < ords.length; i++) {
+    const v = Math.trunc(Number(ords[i]));
+    out[i] = v !== v ? -1 : Math.max(-2147483648, Math.min(2147483647, v));
+  }
+  return out;
+}
 function isMultiBit(targetVectors) { return targetVectors._indexBits !== 1 && targetVectors.dimension() > 1; }
 
 /** computeBatchFourBitSimilarityScores for one row, src/batchDotProduct.ts:554-617 (used only for the originalQueryVector corner) */
@@ -656,6 +666,29 @@ class BinaryQuantizationFormat {
     if (k < 0) throw new Error('k值不能为负数');
     if (queryVector.length !== targetVectors.dimension()) throw new Error('查询向量维度与目标向量维度不匹配');
     return this.searchNearestNeighborsBatchFiltered([queryVector], targetVectors, filter, k)[0];
+  }
+
+  /**
+   * extension (not in the reference): searchNearestNeighbors over the rows `ords` names (an Int32Array or an array of ords; any order,
+   * duplicates allowed) - what the reference's loop (:349-411) returns when it visits exactly those ords IN THE ORDER GIVEN, with a
+   * heap of min(k, ords.length); the list may differ from query to query, which a RowFilter cannot.  Same validation and messages as
+   * searchNearestNeighbors; an ord that names no row throws '向量索引 <ord> 不存在'.  The device scores only the rows named.
+   */
+  searchNearestNeighborsInOrds(queryVector, targetVectors, ords, k) {
+    if (!queryVector) throw new Error('查询向量不能为空');
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (k < 0) throw new Error('k值不能为负数');
+    if (queryVector.length !== targetVectors.dimension()) throw new Error('查询向量维度与目标向量维度不匹配');
+    const flat = this._flatQueries([queryVector], targetVectors, k);
+    if (flat === null) return [];
+    const q = this.quantizer, sim = simOrdinal(q.similarityFunction), qb = this.config.queryBits;
+    const tNative = process.hrtime.bigint();
+    const qz = native.quantizeQueries(flat, 1, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, 1);
+    const r = native.searchOrds(targetVectors._deviceIndex(), qz.quantized, qz.corrections, qb, sim, k, ordsAsInt32(ords));
+    hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
+    const n = r.indices.length, res = new Array(n);
+    for (let j = 0; j < n; j++) res[j] = { index: r.indices[j], score: r.scores[j] };
+    return res;
   }
 
   /** extension (not in the reference): searchNearestNeighborsFiltered for many queries per call; one filter serves all of them */

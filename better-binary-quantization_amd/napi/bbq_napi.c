@@ -641,6 +641,64 @@ static napi_value ScoreRows(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* scoreOrds(handle, qquant, qcorr, queryBits, sim, ords Int32Array) -> {qcDist Int32Array, score64 Float64Array, score32 Float32Array}, indexed like ords
+ * (bbq_score_ords: any order, duplicates allowed; an ord that names no row throws the reference's message) */
+static napi_value ScoreOrds(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  if (!get_args(env, info, 6, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *qq, *qc, *ords; size_t ql, cl, n;
+  int64_t qb, sim;
+  if (!get_typed(env, a[1], napi_uint8_array, &qq, &ql) || !get_typed(env, a[2], napi_float64_array, &qc, &cl) ||
+      !get_i64(env, a[3], &qb) || !get_i64(env, a[4], &sim) || !get_typed(env, a[5], napi_int32_array, &ords, &n)) return NULL;
+  if (ql != (size_t)bbq_index_dimension(ix) || cl != 4) { napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return NULL; }
+  void *od, *o64, *o32;
+  napi_value td = new_typed(env, napi_int32_array, n, 4, &od);
+  napi_value t64 = new_typed(env, napi_float64_array, n, 8, &o64);
+  napi_value t32 = new_typed(env, napi_float32_array, n, 4, &o32);
+  if (!td || !t64 || !t32) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_score_ords(ix, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, (const int32_t *)ords, (int64_t)n, (int32_t *)od, (double *)o64, (float *)o32);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "qcDist", td); set_prop(env, o, "score64", t64); set_prop(env, o, "score32", t32);
+  return o;
+}
+
+/* searchOrds(handle, qquant, qcorr, queryBits, sim, k, ords Int32Array) -> {indices Int32Array, scores Float32Array} of min(k, ords.length) entries:
+ * the reference's loop over `ords` in the order given (bbq_search_ords_batch with one query) */
+static napi_value SearchOrds(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (!get_args(env, info, 7, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *qq, *qc, *ords; size_t ql, cl, n;
+  int64_t qb, sim, k;
+  if (!get_typed(env, a[1], napi_uint8_array, &qq, &ql) || !get_typed(env, a[2], napi_float64_array, &qc, &cl) ||
+      !get_i64(env, a[3], &qb) || !get_i64(env, a[4], &sim) || !get_i64(env, a[5], &k) || !get_typed(env, a[6], napi_int32_array, &ords, &n)) return NULL;
+  if (ql != (size_t)bbq_index_dimension(ix) || cl != 4) { napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return NULL; }
+  if (k < 0) { napi_throw_error(env, "BBQ7", "k值不能为负数"); return NULL; }
+  const int64_t keff = k < (int64_t)n ? k : (int64_t)n;
+  const int64_t offsets[2] = {0, (int64_t)n};
+  int64_t cnt = 0;
+  int32_t *idx = (int32_t *)malloc(((size_t)keff + 1) * sizeof(int32_t));
+  float *sc = (float *)malloc(((size_t)keff + 1) * sizeof(float));
+  if (!idx || !sc) { free(idx); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_search_ords_batch(ix, 1, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff, offsets, (const int32_t *)ords, idx, sc, &cnt);
+  if (rc != BBQ_OK) { free(idx); free(sc); return throw_bbq(env, rc); }
+  void *oi, *os;
+  napi_value ti = new_typed(env, napi_int32_array, (size_t)cnt, 4, &oi);
+  napi_value ts = new_typed(env, napi_float32_array, (size_t)cnt, 4, &os);
+  if (!ti || !ts) { free(idx); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  if (cnt > 0) { memcpy(oi, idx, (size_t)cnt * 4); memcpy(os, sc, (size_t)cnt * 4); }
+  free(idx); free(sc);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "indices", ti); set_prop(env, o, "scores", ts);
+  return o;
+}
+
 /* setOption(handle, name, value) */
 static napi_value SetOption(napi_env env, napi_callback_info info) {
   napi_value a[3];
@@ -968,6 +1026,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"searchRawBatch", NULL, SearchRawBatch, NULL, NULL, NULL, napi_default, NULL},
       {"searchRawInto", NULL, SearchRawInto, NULL, NULL, NULL, napi_default, NULL},
       {"scoreRows", NULL, ScoreRows, NULL, NULL, NULL, napi_default, NULL},
+      {"scoreOrds", NULL, ScoreOrds, NULL, NULL, NULL, napi_default, NULL},
+      {"searchOrds", NULL, SearchOrds, NULL, NULL, NULL, napi_default, NULL},
       {"setOption", NULL, SetOption, NULL, NULL, NULL, napi_default, NULL},
       {"stats", NULL, Stats, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsCreate", NULL, VectorsCreate, NULL, NULL, NULL, napi_default, NULL},

@@ -223,7 +223,30 @@ class BinaryQuantizationFormat:
             raise Exception("行过滤器不能为空")
         return self._search(queryVector, targetVectors, k, rowFilter)
 
-    def _search(self, queryVector, targetVectors, k, rowFilter):
+    def searchNearestNeighborsInOrds(self, queryVector, targetVectors, ords, k):
+        """extension: searchNearestNeighbors over exactly the rows `ords` names - what the reference's loop returns when it visits
+        those ords in the order given (any order, duplicates allowed), with a heap of min(k, len(ords)).  The list may differ from
+        query to query, which a row filter cannot; the device scores only the rows named."""
+        if ords is None:
+            raise Exception("目标向量序号不能为空")
+        return self._search(queryVector, targetVectors, k, None, ords)
+
+    def computeBatchQuantizedScores(self, quantizedQuery, queryCorrections, targetVectors, targetOrds, queryBits):
+        """BinaryQuantizedScorer.computeBatchQuantizedScores (src/binaryQuantizedScorer.ts:315-420) without its optional
+        originalQueryVector: [{score, bitDotProduct}] for the rows targetOrds names, in that order, scored on the device
+        (bbq_score_ords: those rows and no others)"""
+        if len(targetOrds) == 0:
+            return []
+        if targetVectors._index_bits != 1 and targetVectors.dimension() > 1 and queryBits not in (1, 4):
+            raise Exception("不支持的查询位数: %d，只支持1位和4位" % queryBits)
+        qc = np.array([queryCorrections[f] for f in ("lowerInterval", "upperInterval", "additionalCorrection", "quantizedComponentSum")], np.float64)
+        try:
+            d, s64, _ = targetVectors._device().score_ords(quantizedQuery, qc, queryBits, capi.SIMS[self._sim], targetOrds, want=(True, True, False))
+        except capi.BBQError as e:
+            raise Exception(str(e))
+        return [{"score": float(s), "bitDotProduct": int(b)} for s, b in zip(s64, d)]
+
+    def _search(self, queryVector, targetVectors, k, rowFilter, ords=None):
         if queryVector is None:
             raise Exception("查询向量不能为空")
         if targetVectors is None:
@@ -242,7 +265,9 @@ class BinaryQuantizationFormat:
         try:
             qq, qc = capi.quantize_query(queryVector, targetVectors.getCentroid(), sim, self._config["queryBits"], self._lambda,
                                          self._iters, search_path=True)
-            if rowFilter is None:
+            if ords is not None:
+                idx, sc = targetVectors._device().search_ords_batch(qq[None, :], qc[None, :], self._config["queryBits"], sim, k, [ords])[0]
+            elif rowFilter is None:
                 idx, sc = targetVectors._device().search(qq, qc, self._config["queryBits"], sim, k)
             else:
                 idx, sc = targetVectors._device().search_filtered(qq, qc, self._config["queryBits"], sim, k, rowFilter)

@@ -30,6 +30,7 @@ SYMBOLS = [
     "bbq_index_append_rows", "bbq_index_append", "bbq_index_reserve", "bbq_index_capacity", "bbq_vectors_append", "bbq_quantize_rows",
     "bbq_index_compact", "bbq_index_remove_rows", "bbq_vectors_compact", "bbq_filter_kept_rows",
     "bbq_index_update_rows", "bbq_index_update", "bbq_vectors_update", "bbq_update_winners",
+    "bbq_score_ords", "bbq_score_ords_batch", "bbq_search_ords_batch",
 ]
 
 
@@ -102,6 +103,9 @@ def lib():
     L.bbq_search_batch.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp]
     L.bbq_search_raw_batch.argtypes = [vp, i32, vp, vp, i32, i32, dbl, i32, i32, i64, vp, vp, vp, vp, vp, C.POINTER(i32)]
     L.bbq_score_rows.argtypes = [vp, vp, vp, i32, i32, i64, i64, vp, vp, vp]
+    L.bbq_score_ords.argtypes = [vp, vp, vp, i32, i32, vp, i64, vp, vp, vp]
+    L.bbq_score_ords_batch.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.bbq_search_ords_batch.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_create_rows.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_destroy.argtypes = [vp]
@@ -511,6 +515,44 @@ class Index:
         _chk(lib().bbq_score_rows(self._h, _ptr(qq), _ptr(qc), query_bits, sim, row_begin, row_count, _ptr(d), _ptr(s64), _ptr(s32)))
         return d, s64, s32
 
+    def score_ords(self, qquant, qcorr, query_bits, sim, ords, want=(True, True, True)):
+        """bbq_score_ords: (qcdist, score64, score32) of the rows `ords` names, in the order given (any order, duplicates allowed);
+        want = which of the three the library is asked for (the others come back None)"""
+        qq = np.ascontiguousarray(qquant, np.uint8)
+        qc = np.ascontiguousarray(qcorr, np.float64)
+        o = _ords(ords)
+        n = o.shape[0]
+        d = np.zeros(n, np.int32) if want[0] else None
+        s64 = np.zeros(n, np.float64) if want[1] else None
+        s32 = np.zeros(n, np.float32) if want[2] else None
+        _chk(lib().bbq_score_ords(self._h, _ptr(qq), _ptr(qc), query_bits, sim, _ptr(o), n, _ptr(d), _ptr(s64), _ptr(s32)))
+        return d, s64, s32
+
+    def score_ords_batch(self, qquant, qcorr, query_bits, sim, lists):
+        """bbq_score_ords_batch: query q against its own list.  `lists` is a list of ord arrays, one per query, or (offsets, ords).
+        Returns (qcdist, score64, score32), each indexed like the concatenated ords (list q at offsets[q] .. offsets[q+1]), and offsets."""
+        qq = np.ascontiguousarray(qquant, np.uint8)
+        qc = np.ascontiguousarray(qcorr, np.float64)
+        off, o = _lists(lists, qq.shape[0])
+        n = o.shape[0]
+        d, s64, s32 = np.zeros(n, np.int32), np.zeros(n, np.float64), np.zeros(n, np.float32)
+        _chk(lib().bbq_score_ords_batch(self._h, qq.shape[0], _ptr(qq), _ptr(qc), query_bits, sim, _ptr(off), _ptr(o), _ptr(d), _ptr(s64), _ptr(s32)))
+        return d, s64, s32, off
+
+    def search_ords_batch(self, qquant, qcorr, query_bits, sim, k, lists):
+        """bbq_search_ords_batch: exact top-k of every query over its own list, visited in the order given.  `lists` as
+        score_ords_batch takes them.  Returns a list of (idx, score) per query."""
+        qq = np.ascontiguousarray(qquant, np.uint8)
+        qc = np.ascontiguousarray(qcorr, np.float64)
+        nq = qq.shape[0]
+        off, o = _lists(lists, nq)
+        kk = max(int(k), 0)
+        idx = np.zeros((nq, kk), np.int32)
+        sc = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.int64)
+        _chk(lib().bbq_search_ords_batch(self._h, nq, _ptr(qq), _ptr(qc), query_bits, sim, k, _ptr(off), _ptr(o), _ptr(idx), _ptr(sc), _ptr(cnt)))
+        return [(idx[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)]
+
     def shard_scan_begin(self, qquant, qcorr, query_bits, sim, k, dev_packed_ptr, packed_cap, dev_offsets_ptr, dev_flags_ptr,
                          dev_answers_ptr=None, answers_stride=0):
         """enqueue the sweep of one batch (and its packing) and return; shard_scan_wait() later.  Two batches may be in flight."""
@@ -587,6 +629,21 @@ def filter_plan(mask, k_dev, first_segment_rows=4096, growth=8):
 def _ords(ords):
     """ords as the C ABI takes them: int32, values beyond its range clipped to its ends (out of range for every index either way)"""
     return np.ascontiguousarray(np.asarray(ords, np.int64).ravel().clip(-2**31, 2**31 - 1), np.int32)
+
+
+def _lists(lists, n_queries):
+    """one ord list per query as the C ABI takes them: (offsets int64 [n_queries + 1], ords int32).  A TUPLE is the pair
+    (offsets, ords), handed over as it is so that the library's own checks speak; any other sequence holds one array per query"""
+    if isinstance(lists, tuple):
+        if len(lists) != 2 or len(lists[0]) != n_queries + 1:
+            raise BBQError(ERR_INVALID_ARG, "(offsets, ords) with one offset per query and one more")
+        return np.ascontiguousarray(lists[0], np.int64), _ords(lists[1])
+    if len(lists) != n_queries:
+        raise BBQError(ERR_INVALID_ARG, "one ord list per query")
+    arrs = [_ords(a) for a in lists]
+    off = np.zeros(n_queries + 1, np.int64)
+    off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    return off, (np.concatenate(arrs) if arrs else np.zeros(0, np.int32))
 
 
 def update_winners(ords, n_rows):

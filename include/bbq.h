@@ -35,7 +35,8 @@ extern "C" {
                                  bbq_merge_answers, persistence of shards and multi-device indexes
                               (still 3: filtered search - bbq_filter_*, bbq_search_filtered_batch - only adds symbols, as do the appends
                               and the compaction - bbq_index_compact, bbq_index_remove_rows, bbq_vectors_compact, bbq_filter_kept_rows - and the
-                              in-place updates - bbq_index_update_rows, bbq_index_update, bbq_vectors_update, bbq_update_winners) */
+                              in-place updates - bbq_index_update_rows, bbq_index_update, bbq_vectors_update, bbq_update_winners - and the scoring of chosen rows -
+                              bbq_score_ords, bbq_score_ords_batch, bbq_search_ords_batch) */
 
 /* status codes */
 enum {
@@ -345,6 +346,41 @@ int bbq_update_winners(const int32_t *ords, int64_t n, int64_t n_rows, int64_t *
 int bbq_score_rows(bbq_index *idx, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim,
                    int64_t row_begin, int64_t row_count, int32_t *out_qcdist, double *out_score64,
                    float *out_score32);
+
+/* ------------------------------------------------------------------------------------------
+ * Scoring chosen rows (DESIGN.md "Scoring chosen rows"): computeBatchQuantizedScores(query, corrections, targetVectors, targetOrds,
+ * queryBits) (src/binaryQuantizedScorer.ts:315-420) for an ARBITRARY list of ords per query - a graph or IVF layer's neighbours, a
+ * metadata pre-filter's short candidate list, a tenant list that differs from query to query, another system's candidates.  The
+ * device gathers exactly the rows named: two ords at opposite ends of the index cost two rows, not the range between them.
+ * For every list position i of query q, out_*[i] is bit for bit what bbq_score_rows returns for row ords[i] with that query (integer
+ * qcDist, f64 score, its f32 rounding; a NaN score is delivered as NaN).  Any order of ords, duplicates allowed: each occurrence is
+ * scored.  offsets [n_queries + 1] ascending from 0, as bbq_rerank_scores takes them.  query_bits, sim and the multi-bit corners as
+ * bbq_score_rows.
+ * Nothing is written and nothing is launched when an argument is bad, when n_queries == 0 or when offsets[n_queries] == 0 (the last
+ * two: BBQ_OK).  An ord outside [0, bbq_index_size): BBQ_ERR_INVALID_ARG, "向量索引 <ord> 不存在" naming the first offending entry in
+ * list order (what the reference's loop throws on); every list is checked on the host before the first launch.
+ * Accepted handles: a single-device index - also a non-root shard or one with a pilot replica; ords are positions among the handle's
+ * own rows, as row_begin of bbq_score_rows is - and a multi-device handle (the lists are split by shard on the host).  The call takes
+ * the device context's lock and runs on the auxiliary stream, as bbq_score_rows does: it sees an append, a compaction or an update
+ * whole or not at all.  A long call is worked through in launches of at most 2^20 entries and 1024 queries: the device scratch stays
+ * below 21 MiB whatever the call's size. */
+/* n_queries queries at once: query q is scored against ords[offsets[q] .. offsets[q+1]).  Outputs are indexed like ords; any output
+ * pointer may be NULL. */
+int bbq_score_ords_batch(bbq_index *idx, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
+                         int32_t query_bits, int32_t sim, const int64_t *offsets, const int32_t *ords,
+                         int32_t *out_qcdist, double *out_score64, float *out_score32);
+/* one query, one list of n ords */
+int bbq_score_ords(bbq_index *idx, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim,
+                   const int32_t *ords, int64_t n, int32_t *out_qcdist, double *out_score64, float *out_score32);
+/* exact top-k over each query's own list: what the reference loop (src/binaryQuantizationFormat.ts:349-411) returns when it visits
+ * ords[offsets[q] .. offsets[q+1]) IN THE ORDER GIVEN, pushing (ord, f32 score) into a heap of min(k, list length) - indices, score
+ * bits and order, ties included, whatever the list's order; a duplicate is visited once per occurrence.  out_idx / out_score
+ * [n_queries*k] (query q at offset q*k), out_n [n_queries].  k < 0: BBQ_ERR_NEGATIVE_K; k == 0 or an empty list: out_n[q] = 0 (out_n is
+ * written whenever the arguments are good, also when every list is empty); no upper limit on k.  The device delivers the f32 scores,
+ * the host runs the literal heap over them on replay_threads threads. */
+int bbq_search_ords_batch(bbq_index *idx, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
+                          int32_t query_bits, int32_t sim, int64_t k, const int64_t *offsets, const int32_t *ords,
+                          int32_t *out_idx, float *out_score, int64_t *out_n);
 
 /* ------------------------------------------------------------------------------------------
  * Sharded search (one process per GPU).  bbq_shard_scan sweeps THIS shard for n_queries queries and
