@@ -280,7 +280,7 @@ int ensure_slot(const SearchCall &c, Slot &s, int nq, bool own_lists) {
   s.final_stride = std::max<int64_t>(s.final_stride, std::max<int64_t>(p.final_k, 126) + 2);
   // theta | flags | topk_counts | list_counts | ovf_counts | append_counts live in one control block in front of the staged queries: the copy that
   // brings a sub-batch's queries also resets them (the host twin's control part stays zero)
-  const int64_t ctrl_bytes = ((int64_t)Q * (24 + 4 * kAppendStride) + 255) / 256 * 256;  // the append counters sit one per 128-byte line (kAppendStride)
+  const int64_t ctrl_bytes = ((int64_t)Q * (28 + 4 * kAppendStride) + 255) / 256 * 256;  // the append counters sit one per 128-byte line (kAppendStride)
   const size_t block = (size_t)(ctrl_bytes + Q * s.qbuf_bytes);
   if (!valid || s.d_block.size() < block) {  // (the control layout depends on Q alone, and a larger Q is a larger block)
     s.ctrl_bytes = ctrl_bytes;
@@ -290,12 +290,14 @@ int ensure_slot(const SearchCall &c, Slot &s, int nq, bool own_lists) {
     memset(s.h_block, 0, (size_t)s.ctrl_bytes);
     s.d_qbuf = s.d_block + s.ctrl_bytes;
     s.h_qbuf = s.h_block + s.ctrl_bytes;
-    s.d_theta = reinterpret_cast<uint32_t *>(s.d_block.get());
-    s.d_flags = s.d_theta + Q;
-    s.d_topk_counts = reinterpret_cast<int32_t *>(s.d_theta + 2 * (size_t)Q);
-    s.d_list_counts = reinterpret_cast<int32_t *>(s.d_theta + 3 * (size_t)Q);
-    s.d_ovf_counts = s.d_theta + 5 * (size_t)Q;
-    s.d_append_counts = s.d_theta + 6 * (size_t)Q;
+    // (all-zero bytes are the reset state of every one of them: a zeroed Threshold is {key 0, z image -inf}, bbq_device.h)
+    s.d_theta = reinterpret_cast<Threshold *>(s.d_block.get());
+    uint32_t *words = reinterpret_cast<uint32_t *>(s.d_block.get());
+    s.d_flags = words + 2 * (size_t)Q;
+    s.d_topk_counts = reinterpret_cast<int32_t *>(words + 3 * (size_t)Q);
+    s.d_list_counts = reinterpret_cast<int32_t *>(words + 4 * (size_t)Q);
+    s.d_ovf_counts = words + 6 * (size_t)Q;
+    s.d_append_counts = words + 7 * (size_t)Q;
   }
   if (s.flood_cap > 0) HIPCHK(s.d_ovf.reserve((size_t)(Q * s.flood_cap)));
   HIPCHK(s.d_counts.reserve((size_t)(Q * s.chunks_cap)));
@@ -454,6 +456,7 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
       fl.timed_bytes = g.rows * ((nq + share - 1) / share) * row_bytes;
     }
     FinalizeArgs f = segment_finalize_args(slot_finalize_args(s, d_lists, d_list_counts, list_cap, append_here, c.k_dev), s, g, a);
+    f.qparams = a.qparams;  // the thresholds it writes carry their z images (store_threshold)
     if (last && p.final_k > 0 && (use_final || (ext && ext->answers))) {  // the answer: to the slot, or a shard's to its caller
       f.final_out = use_final ? s.d_final.get() : ext->answers;
       f.final_stride = (int32_t)(use_final ? s.final_stride : ext->answers_stride);

@@ -225,8 +225,31 @@ struct QueryParams {
   int32_t one_bit;
   int32_t mip_plain;  // 1: MAXIMUM_INNER_PRODUCT is scaleMaxInnerProductScore(t) without the division by FOUR_BIT_SCALE: the
                       // per-row scorer's form (src/binaryQuantizedScorer.ts:207-209), which answers for multi-bit indexes
-  int32_t pad_;
+  int32_t fast_bound; // 1: the f32 images below are usable and the compact layout's score bound is tested in f32 against the threshold's
+                      // z image (compact_bound_passes); 0: the f64 bound.  Decided by fill_query (fast_bound_images)
+  // f32 images for the f32 bound, each computed in f64 and rounded once (k2mf and tinyf rounded up)
+  float ayf, lyf;     // ay, ly
+  float c1f;          // ay * dim + ly * y1
+  float k2mf;         // 2^-20 * M, M >= |c1| + 2 (|ay| * x1max + |ly| * qcmax): the rounding allowance per unit of |al| + |au|
+  float tinyf;        // the absolute allowance (denormal corrections, underflow)
+  float csf, caf;     // z = cs * s + ca * add: (2, -1) EUCLIDEAN, (1, 1) otherwise
+  float padf_;
 };
+static_assert(sizeof(QueryParams) == 96 && sizeof(QueryParams) % 16 == 0, "QueryParams: staged in arrays behind 16-byte query data, and part of kernel arguments");
+
+// A query's threshold: the monotone key rows are tested against (a row is a candidate iff key(score) > key), and the same threshold
+// in the linear space of the score formula, z = cs * s + ca * add (z_threshold, bbq_kernel_common.h): score > threshold => z > z image.
+// The two live in ONE 8-byte word and are only ever written together (store_threshold): a key whose image is stale would reject rows
+// that belong to the answer.  The image is stored XOR the bits of -inf, so that all-zero bytes - what the host resets the control words
+// to - are {key 0, -inf}: everything is a candidate.
+struct Threshold {
+  uint32_t key;
+  uint32_t zenc;
+};
+static_assert(sizeof(Threshold) == 8, "one 8-byte word per query");
+constexpr uint32_t kZthXor = 0xff800000u;  // bits of -inf
+__host__ __device__ inline float threshold_z(const Threshold &t) { return __builtin_bit_cast(float, t.zenc ^ kZthXor); }
+__host__ __device__ inline Threshold make_threshold(uint32_t key, float z) { return Threshold{key, __builtin_bit_cast(uint32_t, z) ^ kZthXor}; }
 
 struct ScanArgs {
   IndexView idx;
@@ -236,7 +259,7 @@ struct ScanArgs {
   int64_t chunk_begin;         // first chunk of this launch inside idx
   int64_t row_id_base;         // global row id of idx row 0
   // sparse output (candidates above the per-query threshold)
-  const uint32_t *theta;       // [Q] monotone keys; a row is a candidate iff key(score) > theta
+  const Threshold *theta;      // [Q] monotone keys (and their z images); a row is a candidate iff key(score) > theta.key
   uint32_t *counts;            // [Q][n_chunks]
   uint64_t *entries;           // [Q][n_chunks][cap], ascending by row inside a chunk
   uint32_t *flags;             // [Q]
@@ -288,7 +311,9 @@ struct FinalizeArgs {
   // running top-k keys and the threshold for the next segment
   uint32_t *topk_keys;         // [Q][k]
   int32_t *topk_counts;        // [Q]
-  uint32_t *theta;             // [Q]
+  Threshold *theta;            // [Q] written through store_threshold alone
+  const QueryParams *qparams;  // [Q] the queries of the launch: a threshold's z image depends on its query.  Null: one query, `qp1`
+  QueryParams qp1;             // the single-query chain's query (it lives in kernel arguments, not in device memory)
   uint32_t *flags;             // [Q]
   int32_t k;
   int32_t need_theta;          // 0 on the last segment
@@ -328,7 +353,7 @@ struct LatScanArgs {
   int64_t chunk_begin;
   int32_t n_chunks;
   int32_t first;                     // 1: the dense prefix - threshold 0 (every row is listed), nothing listed before it
-  const uint32_t *theta;             // the query's control words (device memory), as ScanArgs has them per query
+  const Threshold *theta;            // the query's control words (device memory), as ScanArgs has them per query
   uint32_t *flags;
   const int32_t *list_counts;        // {count, flags}: entries the list holds from the earlier segments
   uint32_t *append_count;

@@ -86,7 +86,8 @@ struct Slot {
   int64_t ctrl_bytes = 0;
   // views into d_block / h_block, derived again whenever the block is reallocated (ensure_slot)
   uint8_t *d_qbuf = nullptr, *h_qbuf = nullptr;
-  uint32_t *d_theta = nullptr, *d_flags = nullptr, *d_append_counts = nullptr, *d_ovf_counts = nullptr;
+  Threshold *d_theta = nullptr;
+  uint32_t *d_flags = nullptr, *d_append_counts = nullptr, *d_ovf_counts = nullptr;
   int32_t *d_topk_counts = nullptr, *d_list_counts = nullptr;
   DevBuf<uint32_t> d_counts, d_topk;
   PinnedBuf<int32_t> h_list_counts;
@@ -202,6 +203,8 @@ struct bbq_index {
                              // Cache from one query's sweep to the next (launch_view(), bbq_index.cpp); -1: this index's share of kResidentAutoBytes
   int opt_l2_share = -1;  // queries whose workgroups sweep one chunk back to back on one XCD, so that all but the first read it through that
                           // XCD's L2 (sweep_coord, bbq_device.h): 1 off, 2..32, -1: l2_share_shift()'s choice (bbq_core.cpp)
+  int opt_fast_bound = 1;  // 1: the compact layout's score bound in f32 against the threshold's z image wherever the query's f32 images allow it
+                           // (fast_bound_images, bbq_query.cpp); 0: always the f64 bound.  The answers are the same either way
   int opt_latency_presample = 1;  // ... and on large indexes get their threshold from per-wave top keys of a prefix (two small launches) instead of two scan / finalize pairs
   int opt_latency_fused = 1;  // single-query calls take the three-launch latency path (bbq_latency_kernels.hip) when the index shape has one
   int opt_append_last = 1;  // append mode also for the last (largest) segment: its finalize launch gets cheaper, its sweep slower (one

@@ -4,6 +4,7 @@
 // selection.  Everything here is __forceinline__: each kernel file gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include "bbq_device.h"
 
 #pragma clang fp contract(off)
@@ -191,16 +192,99 @@ __device__ __forceinline__ double score_upper_bound(double qc, double al, double
 // the tile's additive-correction range in the compact layout: EUCLIDEAN scores fall with it (take the minimum), the others rise (maximum)
 __device__ __forceinline__ float tile_add_bound(const IndexView &v, int64_t tile, int sim) { return v.add_range[tile * 2 + (sim == 0 ? 0 : 1)]; }
 
+// ---- the threshold in the linear space of the score formula ------------------------------------------------------------------------
+// conservative lower edge, in z-space, of "score > theta" for one query.
+//   COSINE / MIP: z = s + xadd,  score = f(z + qadd - cdp) with f increasing
+//   EUCLIDEAN   : z = 2s - xadd, score = 1/(1 + qadd - z)  increasing in z while the denominator is positive
+// Returns zmin with:  exact f32 score > theta_score  =>  z > zmin.   -DBL_MAX accepts everything.
+__device__ __forceinline__ double z_threshold(uint32_t theta_key, const QueryParams &p) {
+  if (theta_key == 0u) return -DBL_MAX;
+  const uint32_t bits = bits_of_key(theta_key);
+  const double th = (double)__uint_as_float(bits);  // the threshold score (a float the reference produced)
+  if (!(th == th)) return -DBL_MAX;
+  double z;
+  if (p.sim == 1) {                 // max((1+t)/2, 0) > th  =>  t > 2 th - 1        (th >= 0 always for scores)
+    if (th < 0.0) return -DBL_MAX;
+    z = (2.0 * th - 1.0) - (p.qadd - p.cdp);
+  } else if (p.sim == 2) {
+    double t;
+    if (p.one_bit || p.mip_plain) t = th >= 1.0 ? th - 1.0 : (th > 0.0 ? 1.0 - 1.0 / th : -DBL_MAX);  // the two forms score_f64 has
+    else {
+      const double FBS = 1.0 / 15.0;
+      t = th >= 1.0 ? (th - 1.0) * FBS : (th > 0.0 ? (1.0 - 1.0 / th) * FBS : -DBL_MAX);
+    }
+    if (t == -DBL_MAX) return -DBL_MAX;
+    z = t - (p.qadd - p.cdp);
+  } else {                          // 1/(1+e) > th, e = qadd + xadd - 2s = qadd - z   =>  z > qadd + 1 - 1/th
+    if (!(th > 0.0)) return -DBL_MAX;
+    z = p.qadd + 1.0 - 1.0 / th;
+  }
+  if (!(fabs(z) <= DBL_MAX)) return -DBL_MAX;
+  return z - 1e-9 * (fabs(z) + fabs(p.qadd) + fabs(p.cdp) + 1.0);  // rounding allowance of this inversion
+}
+// ... rounded DOWN to f32: the z image of a threshold key (-inf accepts everything)
+__device__ __forceinline__ float z_threshold_f32(uint32_t theta_key, const QueryParams &p) {
+  const double z = z_threshold(theta_key, p);
+  const float zf = (float)z;  // to nearest; -DBL_MAX becomes -inf
+  if (!((double)zf > z)) return zf;
+  const uint32_t b = __float_as_uint(zf);  // the next float below zf (zf is no NaN and not -inf here)
+  return __uint_as_float((b << 1) == 0u ? 0x80000001u : (b & 0x80000000u) ? b + 1u : b - 1u);
+}
+// THE writer of a query's threshold: the key and its z image, one 8-byte store
+__device__ __forceinline__ void store_threshold(Threshold *dst, uint32_t key, const QueryParams &p) { *dst = make_threshold(key, z_threshold_f32(key, p)); }
+
 // compact layout: the row's bf16 {lower, upper} word and the tile's additive bound give an upper bound of its score.  NaN (no bound)
-// passes; otherwise the row can only matter if even its upper bound beats the threshold
-__device__ __forceinline__ bool compact_bound_passes(bool valid, uint32_t qc, uint32_t cw, float aadd, double x1, const QueryParams &p, uint32_t theta) {
+// passes; otherwise the row can only matter if even its upper bound beats the threshold.  `ones` = x1: the compact layout exists only
+// for indexes whose component sums are the rows' popcounts / code sums (set_index_geometry).
+//
+// Two forms of one test, chosen per query by a scalar branch (QueryParams::fast_bound, set by the host: fast_bound_images):
+//  * f64, through the similarity transform: score_upper_bound against the key;
+//  * f32, in z-space, against the threshold's z image (z_threshold_f32).  With g = ay x1 + ly qc and c1 = ay dim + ly y1 the raw score of
+//    the compact corrections is s = al (c1 - g) + au g, and  z = cs s + ca add.  99.9 % of the rows of a sweep exist only to fail this
+//    test, and in f64 it was a fifth of the sweep's vector instructions.
+// Error budget of the f32 form (u = 2^-24; M >= |ay| dim + |ly y1| + 2 (|ay| x1max + |ly| qcmax), so |g|, |c1 - g|, and every
+// term of the reference's sum t1..t4 per unit of |lower| + |upper|, are at most M; W = |al| + |au|, E = |al (c1 - g)| + |au g| <= W M):
+//  * the images ayf, lyf, c1f are within u of their values, (float)qc within u (exact below 2^24), (float)ones exact: the computed g is
+//    within 2.1 u M of g, the computed A = c1 - g within 5.1 u M, the two products and their sum add 3 u E: |s_f32 - s| <= 9.1 u W M;
+//  * the exact corrections differ from the compact ones by |lower - al| <= |al| kBf16Rel + 2^-132 (f32 rounding, truncation to bf16; the
+//    absolute part is what a subnormal f32 loses), so the exact row's s differs by at most kBf16Rel E + 2^-131 M - with E taken from the
+//    computed products (within u + 6 u W M / E of the true ones, the latter 2^-7 * 6 u W M more);
+//  * the reference's own f64 evaluation (2^-50 W M) and the z-space sums vanish beside these.
+//  Allowance: K1 E + 2^-20 W M + tiny, K1 = kBf16Rel (1 + 2^-18) (the 2^-18 pays the roundings of E and of the allowance itself),
+//  2^-20 = 16 u against the 9.2 u needed, tiny = max(2^-100, 2^-120 M) for the absolute parts: the 2^-131 M above, kAbsSlack of the
+//  additive term, and every f32 operation here whose result leaves the normal range (at most 2^-126 each, also with subnormals
+//  flushed; the host refuses images below the normal range and M < 2^-80, so that a flushed g or A, times |au| or |al|, stays inside
+//  the 2^-20 W M).  The additive term: ca add <= ca aadd + 2^-23 |aadd| (add_range is rounded to nearest), given 2^-21 |aadd|; the last
+//  line pays the roundings of the z-space sums.  Overflow or NaN anywhere ends as +inf or NaN: the row passes, as in the f64 form.
+//  tests/test_bound_f32_cpu.py restates this in numpy f32 and checks dominance over the exact score, fused and unfused.
+constexpr float kFastK1 = (float)(kBf16Rel * (1.0 + 1.0 / 262144.0));
+constexpr float kFastAddRel = 4.76837158203125e-07f;  // 2^-21
+__device__ __forceinline__ bool fast_bound_passes(bool valid, uint32_t qc, uint32_t cw, float aadd, uint32_t ones, const QueryParams &p, const Threshold &th) {
+  const float al = compact_lower(cw), au = compact_upper(cw);  // bf16 -> f32 is exact
+  const float g = fmaf(p.lyf, (float)qc, p.ayf * (float)ones);
+  const float A = p.c1f - g;
+  const float pa = al * A, pb = au * g;
+  const float s = pa + pb;
+  const float e = fabsf(pa) + fabsf(pb);
+  const float w = fabsf(al) + fabsf(au);
+  const float slack = fmaf(kFastK1, e, fmaf(w, p.k2mf, p.tinyf));
+  const float zc = fmaf(p.csf, s, p.caf * aadd);
+  const float zs = fmaf(p.csf, slack, kFastAddRel * fabsf(aadd));
+  const float z0 = zc + zs;
+  const float zup = fmaf(kFastAddRel, fabsf(z0), z0);
+  return valid && !(zup <= threshold_z(th));  // NaN anywhere passes -> exact path
+}
+__device__ __forceinline__ bool f64_bound_passes(bool valid, uint32_t qc, uint32_t cw, float aadd, double x1, const QueryParams &p, uint32_t theta) {
   const double al = (double)compact_lower(cw);
   const double au = (double)compact_upper(cw);
   const double ub = score_upper_bound((double)qc, al, au, (double)aadd, x1, p);
   const float ub32 = (float)ub;
   return valid && ((ub32 != ub32) || key_of_bits(__float_as_uint(ub32)) > theta);
 }
-
+__device__ __forceinline__ bool compact_bound_passes(bool valid, uint32_t qc, uint32_t cw, float aadd, uint32_t ones, double x1, const QueryParams &p,
+                                                     const Threshold &th) {
+  return p.fast_bound ? fast_bound_passes(valid, qc, cw, aadd, ones, p, th) : f64_bound_passes(valid, qc, cw, aadd, x1, p, th.key);  // per query: a scalar branch
+}
 // the row's exact corrections from the compact layout's side array: {lower, upper} and additionalCorrection.  STREAM: the dense paths,
 // which read every row once (non-temporal loads)
 template <bool STREAM = false>

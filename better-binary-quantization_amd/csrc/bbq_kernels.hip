@@ -41,7 +41,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_shared_kernel(const ScanA
   QueryParams *s_qp = reinterpret_cast<QueryParams *>(smem + (size_t)NB * W * QB * 16);  // [NB]
   uint64_t *s_ent = reinterpret_cast<uint64_t *>(s_qp + NB);                        // [NB][cap]
   uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_ent + (size_t)NB * a.cap);       // [NB]
-  uint32_t *s_theta = s_cnt + NB;                                                   // [NB]
+  Threshold *s_theta = reinterpret_cast<Threshold *>(s_cnt + NB);                   // [NB] (NB is even: 8-byte aligned)
 
   const int q0 = blockIdx.y * NB;
   const int nb = min(NB, nq_total - q0);
@@ -96,10 +96,12 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_shared_kernel(const ScanA
 #pragma unroll
       for (int pq = 0; pq < QB; ++pq) qc += acc[pq] << pq;
       const QueryParams p = s_qp[b];
-      const uint32_t theta = s_theta[b];
+      const uint32_t theta = s_theta[b].key;
       bool need_exact = valid;
       if constexpr (COMPACT) {
-        need_exact = compact_bound_passes(valid, qc, cw, aadd, x1, p, theta);
+        // the f64 form only: here the query's uniforms come out of LDS into vector registers, and with the f32 images beside them
+        // every attempt cost the compact instantiations a wave of occupancy (docs/dropped.md)
+        need_exact = f64_bound_passes(valid, qc, cw, aadd, x1, p, theta);
         if (need_exact && !have_exact) {
           exact_corrections(a.idx.exact, row, lu, xadd);
           have_exact = true;
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_finalize_kernel(const Fi
       if (M < (uint32_t)a.k) {
         // fewer than k rows seen so far: the reference heap is still filling, everything stays a candidate
         for (uint32_t i = tid; i < M; i += kFinalizeThreads) tk[i] = s_keys[i];
-        if (tid == 0) { a.topk_counts[q] = (int32_t)M; a.theta[q] = 0u; }
+        if (tid == 0) { a.topk_counts[q] = (int32_t)M; store_threshold(a.theta + q, 0u, a.qparams ? a.qparams[q] : a.qp1); }
       } else {
         const uint32_t th = block_select_kth_largest(s_keys, M, (uint32_t)a.k, s_hist, s_wave, s_misc + 8);  // exactly the k-th largest key among the M keys
         if (tid == 0) s_misc[2] = 0;
@@ -284,7 +286,7 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_finalize_kernel(const Fi
         __syncthreads();
         const uint32_t gt = s_misc[2];  // < k by construction
         for (uint32_t i = gt + tid; i < (uint32_t)a.k; i += kFinalizeThreads) tk[i] = th;
-        if (tid == 0) { a.topk_counts[q] = a.k; a.theta[q] = th; }
+        if (tid == 0) { a.topk_counts[q] = a.k; store_threshold(a.theta + q, th, a.qparams ? a.qparams[q] : a.qp1); }
       }
     }
   }
@@ -399,7 +401,7 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_finalize_kernel(const Fi
       if (a.done_flag) {
         // the next call's chain starts without a copy that would reset the control words: leave them clean
         a.flags[q] = 0u;
-        a.theta[q] = 0u;
+        store_threshold(a.theta + q, 0u, a.qp1);  // (the single-query chain: qparams is null)
         a.topk_counts[q] = 0;
         a.list_counts[2 * q] = 0;
         a.list_counts[2 * q + 1] = 0;
@@ -464,7 +466,7 @@ __global__ __launch_bounds__(256) void bbq_pack_copy_kernel(const uint64_t *__re
 
 template <int QB, int W, bool COMPACT, int NB>
 static hipError_t launch_shared_t(const ScanArgs &a, int nq, int nc, hipStream_t s) {
-  const size_t smem = (size_t)NB * W * QB * 16 + (size_t)NB * sizeof(QueryParams) + (size_t)NB * a.cap * 8 + (size_t)NB * 8 + 16;
+  const size_t smem = (size_t)NB * W * QB * 16 + (size_t)NB * sizeof(QueryParams) + (size_t)NB * a.cap * 8 + (size_t)NB * (4 + sizeof(Threshold)) + 16;
   dim3 grid((unsigned)nc, (unsigned)((nq + NB - 1) / NB), 1), block(kChunkRows, 1, 1);
   hipLaunchKernelGGL((bbq_scan_shared_kernel<QB, W, COMPACT, NB>), grid, block, smem, s, a, nq);
   return hipGetLastError();

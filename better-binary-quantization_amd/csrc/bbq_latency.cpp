@@ -116,13 +116,14 @@ int search_latency_presampled(const SearchCall &c, int32_t *out_idx, float *out_
   memcpy(pre.planes, a.planes, sizeof pre.planes);
   HIPCHK(launch_lat_pre(pre, c.planes, st));
   // rank k2 + 2: the sweep must list at least k2 + 1 rows for the selection to see the boundary of the answer
-  HIPCHK(launch_lat_select(ctx->d_pre_keys, (int)n_keys, (int)(k2 + 2), s.d_theta, st));
+  HIPCHK(launch_lat_select(ctx->d_pre_keys, (int)n_keys, (int)(k2 + 2), s.d_theta, a.p, st));
   a.chunk_begin = 0;
   a.n_chunks = (int32_t)ix->main.n_chunks();
   a.first = 0;
   HIPCHK(launch_lat_scan(a, c.planes, st));
   const uint64_t seq = ++ctx->lat_seq;
   FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, c.k_dev);
+  f.qp1 = a.p;
   f.emit = 1;
   answer_to_host(f, ctx, k2, seq);
   HIPCHK(launch_finalize(f, 1, st));
@@ -163,6 +164,7 @@ int search_latency_chain(const SearchCall &c, int32_t *out_idx, float *out_score
     a.first = i == 0 ? 1 : 0;
     HIPCHK(launch_lat_scan(a, c.planes, st));
     FinalizeArgs f = slot_finalize_args(s, s.d_lists, s.d_list_counts, s.list_cap, true, c.k_dev);
+    f.qp1 = a.p;  // (qparams stays null: the query is in no device buffer)
     f.emit = 1;
     f.need_theta = i + 1 < p.segs.size() ? 1 : 0;
     if (i + 1 == p.segs.size()) answer_to_host(f, ctx, p.final_k, seq);

@@ -40,7 +40,8 @@ __global__ __launch_bounds__(kLatThreads) void bbq_lat_scan_kernel(const LatScan
   }
   const QueryParams p = a.p;
   // the dense prefix runs with threshold 0: below the key of every number, so each of its rows is scored exactly and listed
-  const uint32_t theta = a.first ? 0u : *a.theta;
+  const Threshold th = a.first ? Threshold{0u, 0u} : *a.theta;
+  const uint32_t theta = th.key;
   __syncthreads();
 
   const int64_t chunk = a.chunk_begin + blockIdx.x;
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kLatThreads) void bbq_lat_scan_kernel(const LatScan
     if (!a.idx.geom.has_x1) x1 = (double)ones;
     bool need_exact = true;
     if constexpr (COMPACT) {
-      need_exact = compact_bound_passes(valid, qc, cw, aadd, x1, p, theta);
+      need_exact = compact_bound_passes(valid, qc, cw, aadd, ones, x1, p, th);
       if (need_exact) exact_corrections(a.idx.exact, row, lu, xadd);
     }
     if (need_exact) {
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(kLatThreads) void bbq_lat_pre_kernel(const LatPreAr
 }
 
 // step 2: theta := the rank-th largest of the sampled keys (0: fewer than rank keys, everything stays a candidate)
-__global__ __launch_bounds__(kFinalizeThreads) void bbq_lat_select_kernel(const uint32_t *__restrict__ pre_keys, int n_keys, int rank, uint32_t *theta) {
+__global__ __launch_bounds__(kFinalizeThreads) void bbq_lat_select_kernel(const uint32_t *__restrict__ pre_keys, int n_keys, int rank, Threshold *theta, const QueryParams p) {
   __shared__ uint32_t s_keys[kLatPreKeys];
   __shared__ uint32_t s_hist[512];
   __shared__ uint32_t s_wave[16];
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_lat_select_kernel(const 
   __syncthreads();
   uint32_t th = 0;
   if (n_keys >= rank) th = block_select_kth_largest(s_keys, (uint32_t)n_keys, (uint32_t)rank, s_hist, s_wave, s_misc);  // uniform
-  if (tid == 0) *theta = th;
+  if (tid == 0) store_threshold(theta, th, p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -169,9 +170,9 @@ hipError_t launch_lat_pre(const LatPreArgs &a, int planes, hipStream_t s) {
   }
 }
 
-hipError_t launch_lat_select(const uint32_t *pre_keys, int n_keys, int rank, uint32_t *theta, hipStream_t s) {
+hipError_t launch_lat_select(const uint32_t *pre_keys, int n_keys, int rank, Threshold *theta, const QueryParams &p, hipStream_t s) {
   if (n_keys < 0 || n_keys > kLatPreKeys || rank < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(bbq_lat_select_kernel, dim3(1), dim3(kFinalizeThreads), 0, s, pre_keys, n_keys, rank, theta);
+  hipLaunchKernelGGL(bbq_lat_select_kernel, dim3(1), dim3(kFinalizeThreads), 0, s, pre_keys, n_keys, rank, theta, p);
   return hipGetLastError();
 }
 

@@ -30,7 +30,7 @@ bool latency_path_supported(const IndexView &v, int planes);
 hipError_t launch_lat_scan(const LatScanArgs &a, int planes, hipStream_t s);
 // pre-sampled threshold: per-wave top keys of the first rows, then theta := the rank-th largest of them (0 when there are fewer)
 hipError_t launch_lat_pre(const LatPreArgs &a, int planes, hipStream_t s);
-hipError_t launch_lat_select(const uint32_t *pre_keys, int n_keys, int rank, uint32_t *theta, hipStream_t s);
+hipError_t launch_lat_select(const uint32_t *pre_keys, int n_keys, int rank, Threshold *theta, const QueryParams &p, hipStream_t s);
 
 // index build on the device (bbq_build_kernels.hip).  Every wrapper that writes or reads tile records takes them as a TileDest
 // (records, side rows, geometry: bbq_device.h) and rows in the caller's shape as StagedRows.  Those that take row0 (tile0) work at a

@@ -83,35 +83,7 @@ template <> struct MfmaNum<true> {   // S is chosen per call: 1/4 for query valu
   static constexpr float S = 0.25f, ulp = 0.0625f, bias = 786432.0f, mag_limit = 110000.0f, pass_all = 786432.0f + 131072.0f;
 };
 
-// conservative lower edge, in z-space, of "score > theta" for one query.
-//   COSINE / MIP: z = s + xadd,  score = f(z + qadd - cdp) with f increasing
-//   EUCLIDEAN   : z = 2s - xadd, score = 1/(1 + qadd - z)  increasing in z while the denominator is positive
-// Returns zmin with:  exact f32 score > theta_score  =>  z > zmin.   -DBL_MAX accepts everything.
-__device__ __forceinline__ double z_threshold(uint32_t theta_key, const QueryParams &p) {
-  if (theta_key == 0u) return -DBL_MAX;
-  const uint32_t bits = (theta_key & 0x80000000u) ? (theta_key & 0x7fffffffu) : ~theta_key;
-  const double th = (double)__uint_as_float(bits);  // the threshold score (a float the reference produced)
-  if (!(th == th)) return -DBL_MAX;
-  double z;
-  if (p.sim == 1) {                 // max((1+t)/2, 0) > th  =>  t > 2 th - 1        (th >= 0 always for scores)
-    if (th < 0.0) return -DBL_MAX;
-    z = (2.0 * th - 1.0) - (p.qadd - p.cdp);
-  } else if (p.sim == 2) {
-    double t;
-    if (p.one_bit) t = th >= 1.0 ? th - 1.0 : (th > 0.0 ? 1.0 - 1.0 / th : -DBL_MAX);
-    else {
-      const double FBS = 1.0 / 15.0;
-      t = th >= 1.0 ? (th - 1.0) * FBS : (th > 0.0 ? (1.0 - 1.0 / th) * FBS : -DBL_MAX);
-    }
-    if (t == -DBL_MAX) return -DBL_MAX;
-    z = t - (p.qadd - p.cdp);
-  } else {                          // 1/(1+e) > th, e = qadd + xadd - 2s = qadd - z   =>  z > qadd + 1 - 1/th
-    if (!(th > 0.0)) return -DBL_MAX;
-    z = p.qadd + 1.0 - 1.0 / th;
-  }
-  if (!(fabs(z) <= DBL_MAX)) return -DBL_MAX;
-  return z - 1e-9 * (fabs(z) + fabs(p.qadd) + fabs(p.cdp) + 1.0);  // rounding allowance of this inversion
-}
+// (z_threshold - the conservative lower edge, in z-space, of "score > theta" for one query - lives in bbq_kernel_common.h)
 
 // ---- the threshold on the integer ------------------------------------------------------------------------------------------------
 // With ax = lower, lx = upper - lower of the row, x1 its component sum, D the dimension, and ay, ly, y1 of the query
@@ -339,7 +311,7 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
       qk.x = -3.0e38f; qk.y = 0.0f; qk.z = 0.0f; qk.w = 0.0f;
       if (lane < nb) {
         p = a.s.qparams[q0 + lane];
-        th = a.s.theta[q0 + lane];
+        th = a.s.theta[q0 + lane].key;
         const double zt = z_threshold(th, p);
         const double beta = (p.sim == 0 ? 2.0 : 1.0) * p.ly;   // > 0 and finite: the host sends no other query here (mfma_query_ok)
         const double A = -(double)S * (zt / beta);

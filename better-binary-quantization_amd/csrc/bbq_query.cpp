@@ -1,5 +1,6 @@
 // bbq_query.cpp - query staging: bit-planes and multi-bit dwords, the int8 and FP6 MFMA operands, and the checks of a call's query
 // arguments.
+#include <float.h>
 #include <math.h>
 #include <string.h>
 #include "bbq_search.h"
@@ -33,6 +34,34 @@ int planes_of_call(const bbq_index *ix, const uint8_t *q, int64_t count, int one
   if (ix->geom.store_bits == 1) return one_bit ? 1 : planes_for(q, count);
   if (ix->geom.store_bits == 8) return 8;
   return max_value(q, count) <= 15 ? 4 : 8;
+}
+
+// a finite float that is zero or inside f32's normal range: an image the f32 bound can compute with under any denormal mode
+static bool f32_image_ok(double v, float f) { return fabs(v) <= DBL_MAX && fabsf(f) <= FLT_MAX && (f == 0.0f ? v == 0.0 : fabsf(f) >= FLT_MIN); }
+// the float at or above v > 0 (v far inside f32's range)
+static float f32_up(double v) {
+  const float f = (float)v;
+  return (double)f >= v ? f : nextafterf(f, INFINITY);
+}
+// The f32 images of a query for the f32 form of the compact layout's score bound (compact_bound_passes, bbq_kernel_common.h, which
+// holds the error budget these serve), each computed in f64 and rounded once; x1max / qcmax bound a row's component sum and qcDist.
+// fast_bound = 0 - the query keeps the f64 bound - when the option is off, or an image is non-finite, overflows f32 or is a nonzero value
+// below f32's normal range, or the magnitude M is outside [2^-80, 2^100] (below: a result flushed to zero would not stay inside the
+// allowance; above: the allowance itself overflows and every row would pass).
+void fast_bound_images(QueryParams *pp, double x1max, double qcmax, bool enable) {
+  const double c1 = pp->ay * pp->dimd + pp->ly * pp->y1;
+  const double M = (fabs(pp->ay) * pp->dimd + fabs(pp->ly * pp->y1) + 2.0 * (fabs(pp->ay) * x1max + fabs(pp->ly) * qcmax)) * 1.000001;
+  pp->ayf = (float)pp->ay;
+  pp->lyf = (float)pp->ly;
+  pp->c1f = (float)c1;
+  pp->csf = pp->sim == 0 ? 2.0f : 1.0f;
+  pp->caf = pp->sim == 0 ? -1.0f : 1.0f;
+  pp->padf_ = 0.0f;
+  const bool ok = enable && f32_image_ok(pp->ay, pp->ayf) && f32_image_ok(pp->ly, pp->lyf) && f32_image_ok(c1, pp->c1f) && M >= 0x1p-80 && M <= 0x1p100;
+  pp->k2mf = ok ? f32_up(M * 0x1p-20) : 0.0f;
+  pp->tinyf = ok ? f32_up(std::max(0x1p-100, M * 0x1p-120)) : 0.0f;
+  if (!ok) pp->ayf = pp->lyf = pp->c1f = 0.0f;
+  pp->fast_bound = ok ? 1 : 0;
 }
 
 // writes the query data and the score uniforms of one query into the staging buffer.
@@ -97,7 +126,9 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
   pp->sim = sim;
   pp->one_bit = one_bit;
   pp->mip_plain = per_row_form ? 1 : 0;
-  pp->pad_ = 0;
+  // the largest component sum and the largest qcDist a stored row can have, whatever y1 the caller passed
+  const double vmax = (double)((1 << ix->geom.store_bits) - 1), qmax = ix->geom.store_bits == 1 ? (double)((1 << planes) - 1) : (planes > 4 ? 255.0 : 15.0);
+  fast_bound_images(pp, pp->dimd * vmax, pp->dimd * vmax * qmax, ix->opt_fast_bound != 0 && !ix->geom.has_x1);
 }
 
 // MFMA shared sweep, int8 form (query values up to 127): the int8 query values in the order the code bits fall out of the packed

@@ -124,7 +124,8 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
     if (!DENSE && tid == 0) *s_cnt = 0;
   }
   const QueryParams p = a.qparams[q];
-  const uint32_t theta = DENSE ? 0u : a.theta[q];
+  const Threshold th = DENSE ? Threshold{0u, 0u} : a.theta[q];  // (one 8-byte scalar load: the key and its z image)
+  const uint32_t theta = th.key;
   if (idle) return;
   __syncthreads();
 
@@ -172,7 +173,11 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
 
     bool need_exact = true;
     if constexpr (COMPACT && !DENSE) {
-      need_exact = compact_bound_passes(valid, qc, cw, aadd, x1, p, theta);
+      // the f32 form of the bound wherever the query allows it - except in the one instantiation (filtered, 2-bit rows of 16 chunks, query
+      // values above 15) that it cost a wave of occupancy: 92 -> 98 vector registers with it, whatever its place in the code
+      constexpr bool F32_BOUND = !(FILT && SB == 2 && QB == 8 && W == 16);
+      if constexpr (F32_BOUND) need_exact = compact_bound_passes(valid, qc, cw, aadd, ones, x1, p, th);
+      else need_exact = f64_bound_passes(valid, qc, cw, aadd, x1, p, theta);
       if (need_exact) exact_corrections(a.idx.exact, row, lu, xadd);
     }
     if (need_exact) {

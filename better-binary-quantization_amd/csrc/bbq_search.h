@@ -58,6 +58,8 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
 struct MfmaStage { bool fp; int scale8; size_t off_qbytes, off_qmax, bytes; };
 MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryParams *hq, int64_t q_first, int nq, size_t bytes);
 bool mfma_query_ok(const QueryParams &p);
+// the f32 images of *pp's score uniforms and whether the f32 bound may use them (QueryParams::fast_bound)
+void fast_bound_images(QueryParams *pp, double x1max, double qcmax, bool enable);
 int validate_query_args(const bbq_index *ix, int32_t nq, const uint8_t *qquant, const double *qcorr, int32_t query_bits,
                         int32_t sim, int64_t k, bool values_pending = false);
 

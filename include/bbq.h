@@ -588,6 +588,9 @@ int bbq_reset_stats(bbq_index *idx);
  *     a launch order, never a different answer).  1: off, the plain order.  -1: the library's choice, 1 with resident_mb 0.  An explicit
  *     value holds whatever resident_mb says; a launch co-schedules no more queries than it has, and fewer per chunk when it sweeps more
  *     than 134 M rows (the grid's x extent is a 32-bit count of work-items)
+ *   fast_bound 0|1 (1): compact corrections: 1 tests the score bound of a row in f32 against the threshold's image in the linear space of
+ *     the score formula, for every query whose corrections have f32 images (others keep the f64 bound); 0: always the f64 bound through
+ *     the similarity transform.  A pre-filter in front of the exact score either way: never a different answer
  *   replay_threads 1..256 (half the host cores, at most 16)   flood_rows 0..2^24 (262144)   force_dense 0|1 (0)
  *   sweep_share 1|4|8|32 (1: every query sweeps the index itself; 32: shared sweep on the matrix cores, groups of 32 queries, two groups per load of the rows)
  *   device_select 0|1 (1: for k <= 1024 the device selects and sorts the answer itself whenever no two scores in or at the edge of it
