@@ -103,10 +103,15 @@ static double compute_loss(const float *w, int dim, double a, double b, int poin
 }
 
 /* src/optimizedScalarQuantizer.ts:280-353 */
-static void optimize_intervals(double iv[2], const float *w, int dim, double norm2, int points, double lambda, int iters) {
+/* tr (not NULL): tr[0] how it returned (ORC_EXIT_*), tr[1] steps accepted, tr[2] = 1 if a loss compared at :346 was NaN */
+static void optimize_intervals(double iv[2], const float *w, int dim, double norm2, int points, double lambda, int iters,
+                               int32_t *tr) {
+  int32_t none[3];
+  if (!tr) tr = none;
+  tr[0] = ORC_EXIT_ITERS; tr[1] = 0; tr[2] = 0;
   double initial_loss = compute_loss(w, dim, iv[0], iv[1], points, norm2, lambda);
   double scale = (1.0 - lambda) / norm2;
-  if (!isfinite(scale)) return;
+  if (!isfinite(scale)) { tr[0] = ORC_EXIT_SCALE; return; }
   for (int iter = 0; iter < iters; iter++) {
     double a = iv[0], b = iv[1];
     double step_inv = (double)(points - 1) / (b - a);
@@ -126,19 +131,20 @@ static void optimize_intervals(double iv[2], const float *w, int dim, double nor
     double m1 = scale * dax * dbx + lambda * dab;
     double m2 = scale * dbx * dbx + lambda * dbb;
     double det = m0 * m2 - m1 * m1;
-    if (fabs(det) < 1e-12) return;                                   /* isNearZero, constants.ts:74 */
+    if (fabs(det) < 1e-12) { tr[0] = ORC_EXIT_DET; return; }         /* isNearZero, constants.ts:74 */
     double a_opt = (m2 * dax - m1 * dbx) / det;
     double b_opt = (m0 * dbx - m1 * dax) / det;
-    if (fabs(iv[0] - a_opt) < 1e-8 && fabs(iv[1] - b_opt) < 1e-8) return;   /* isNearEqual, constants.ts:76 */
+    if (fabs(iv[0] - a_opt) < 1e-8 && fabs(iv[1] - b_opt) < 1e-8) { tr[0] = ORC_EXIT_CONVERGED; return; }   /* isNearEqual, constants.ts:76 */
     double new_loss = compute_loss(w, dim, a_opt, b_opt, points, norm2, lambda);
-    if (new_loss > initial_loss) return;
-    iv[0] = a_opt; iv[1] = b_opt; initial_loss = new_loss;
+    if (new_loss != new_loss || initial_loss != initial_loss) tr[2] = 1;
+    if (new_loss > initial_loss) { tr[0] = ORC_EXIT_LOSS_ROSE; return; }
+    iv[0] = a_opt; iv[1] = b_opt; initial_loss = new_loss; tr[1]++;
   }
 }
 
 /* src/optimizedScalarQuantizer.ts:108-227 */
-void orc_scalar_quantize(const float *vec, int dim, int bits, const float *centroid, int sim,
-                         double lambda, int iters, uint8_t *dest, double corr[4]) {
+void orc_scalar_quantize_trace(const float *vec, int dim, int bits, const float *centroid, int sim,
+                               double lambda, int iters, uint8_t *dest, double corr[4], int32_t trace[3]) {
   float *w = (float *)malloc(sizeof(float) * (size_t)(dim > 0 ? dim : 1));
   /* :155-164 centroid dot on the UNcentred input */
   double centroid_dot = 0;
@@ -166,7 +172,7 @@ void orc_scalar_quantize(const float *vec, int dim, int bits, const float *centr
   double iv[2];
   iv[0] = js_clamp(-g * std + mean, mn, mx);
   iv[1] = js_clamp(g * std + mean, mn, mx);
-  optimize_intervals(iv, w, dim, norm2, 1 << bits, lambda, iters);
+  optimize_intervals(iv, w, dim, norm2, 1 << bits, lambda, iters, trace);
   /* :192-216 */
   double a = iv[0], b = iv[1];
   int points = 1 << bits, n_steps = points - 1;
@@ -191,6 +197,10 @@ void orc_scalar_quantize(const float *vec, int dim, int bits, const float *centr
   corr[2] = (sim == ORC_EUCLIDEAN) ? norm2 : centroid_dot;          /* :219 */
   corr[3] = qsum;
   free(w);
+}
+void orc_scalar_quantize(const float *vec, int dim, int bits, const float *centroid, int sim,
+                         double lambda, int iters, uint8_t *dest, double corr[4]) {
+  orc_scalar_quantize_trace(vec, dim, bits, centroid, sim, lambda, iters, dest, corr, NULL);
 }
 
 /* src/optimizedScalarQuantizer.ts:420-446: MSB-first, last partial byte zero-padded in the low bits */

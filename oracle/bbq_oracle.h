@@ -43,6 +43,11 @@ double orc_cosine_similarity(const float *a, const float *b, int dim);
 /* src/optimizedScalarQuantizer.ts:108-227 (+ :245-265, :280-353, :373-407).  dest: one value per dim. */
 void orc_scalar_quantize(const float *vec, int dim, int bits, const float *centroid, int sim,
                          double lambda, int iters, uint8_t *dest, double corr[4]);
+/* the same function (orc_scalar_quantize is this with trace = NULL), which also says how optimizeIntervals (:280-353) ended:
+ * trace[0] = ORC_EXIT_*, trace[1] = steps accepted, trace[2] = 1 if a loss compared in `newLoss > initialLoss` was NaN */
+enum { ORC_EXIT_ITERS = 0, ORC_EXIT_SCALE = 1, ORC_EXIT_DET = 2, ORC_EXIT_CONVERGED = 3, ORC_EXIT_LOSS_ROSE = 4 };
+void orc_scalar_quantize_trace(const float *vec, int dim, int bits, const float *centroid, int sim,
+                               double lambda, int iters, uint8_t *dest, double corr[4], int32_t trace[3]);
 /* src/optimizedScalarQuantizer.ts:420-446.  returns 0, or -1 if a value is not 0/1 (the reference throws). */
 int orc_pack_binary(const uint8_t *bits, int dim, uint8_t *packed);
 

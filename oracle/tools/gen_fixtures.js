@@ -11,6 +11,7 @@
  *   centroidDP, integer qcDist per row, f64 score per row, final top-k (index, f32 score).
  *
  * Usage:  python3 oracle/tools/erase_ts.py && node oracle/tools/gen_fixtures.js [outdir]
+ *         (the quant_hostile_* cases read oracle/tools/quant_hostile_rows.json, which oracle/tools/pick_hostile_rows.py writes)
  * Output: tests/golden/*.json  (typed arrays as base64 of little-endian bytes)
  *
  * Runs on Node >= 12 (no `??`, no `?.`).  Needs /root/reference only through the
@@ -495,6 +496,27 @@ cases.push({ name: 'ib2_64d_cos_qb8_throws', sim: 'COSINE', qb: 8, ib: 2, lambda
 // dim 1: the one width where the batch scorer does NOT throw on unpacked rows (dim == ceil(dim/8))
 cases.push({ name: 'ib2_edge_dim1', sim: 'MAXIMUM_INNER_PRODUCT', qb: 4, ib: 2, lambda: 0.1, iters: 5, dim: 1, n: 6, k: 3, nq: 1, full: true,
   gen: { kind: 'inline', base: [[0.5], [-0.5], [2], [3], [-7], [0.25]], queries: [[1.5]] } });
+
+// hostile rows for the quantizer (tests/quant_hostile.py): 48 rows of 13 dimensions picked by oracle/tools/pick_hostile_rows.py so that,
+// over these cases, every exit of optimizeIntervals (src/optimizedScalarQuantizer.ts:280-353) is taken - non-finite scale, determinant,
+// converged, loss rose, iterations ran out (iters = 0 included) - and some rows carry NaN intervals; lambda 0 and 1 are valid input
+{
+  const hostile = JSON.parse(fs.readFileSync(path.join(__dirname, 'quant_hostile_rows.json'), 'utf8'));
+  const rowsOf = function (s) {
+    const buf = Buffer.from(s, 'base64');
+    const f = new Float32Array(buf.buffer.slice(buf.byteOffset, buf.byteOffset + buf.byteLength));
+    const out = [];
+    for (let i = 0; i < f.length; i += hostile.dim) out.push(Array.from(f.subarray(i, i + hostile.dim)));
+    return out;
+  };
+  SIMS.forEach(function (sim) {
+    [[1, 0, 5], [1, 1, 5], [2, 0.1, 0], [4, 1, 3]].forEach(function (g) {
+      cases.push({ name: 'quant_hostile_' + sim.slice(0, 3).toLowerCase() + '_ib' + g[0] + '_l' + g[1] + '_i' + g[2], sim: sim, qb: 4, ib: g[0], lambda: g[1], iters: g[2],
+        dim: hostile.dim, n: hostile.n, k: 10, ks: [1, 10, 48], nq: 2, full: true,
+        gen: { kind: 'inline', base: rowsOf(hostile.base_f32), queries: rowsOf(hostile.queries_f32) } });
+    });
+  });
+}
 
 const only = process.env.BBQ_ONLY ? new RegExp(process.env.BBQ_ONLY) : null;
 fs.mkdirSync(OUT, { recursive: true });

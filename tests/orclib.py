@@ -39,6 +39,7 @@ def lib():
         L.orc_dot_f32.argtypes = [f32p, f32p, C.c_int]
         L.orc_dot_f32.restype = C.c_double
         L.orc_scalar_quantize.argtypes = [f32p, C.c_int, C.c_int, f32p, C.c_int, C.c_double, C.c_int, u8p, f64p]
+        L.orc_scalar_quantize_trace.argtypes = [f32p, C.c_int, C.c_int, f32p, C.c_int, C.c_double, C.c_int, u8p, f64p, i32p]
         L.orc_pack_binary.argtypes = [u8p, C.c_int, u8p]
         L.orc_pack_binary.restype = C.c_int
         L.orc_build_index.argtypes = [f32p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, u8p, f64p, f32p]
@@ -130,6 +131,30 @@ def build_index_unpacked(base, sim, ib, lam=0.1, iters=5):
     cen = np.zeros(dim, np.float32)
     lib().orc_build_index_unpacked(f32p(base), n, dim, sim, ib, lam, iters, u8p(codes), f64p(corr), f32p(cen))
     return codes, corr, cen
+
+
+def quantize_trace(rows, cen, sim, bits, lam=0.1, iters=5):
+    """rows quantized against cen the way quantizeVectors does after its centroid (COSINE rows normalised first), with how each
+    row's optimizeIntervals ended: (codes [packed for bits == 1], corr f64 [n, 4], trace i32 [n, 3] = exit, accepted steps, NaN loss)"""
+    v = np.ascontiguousarray(rows, np.float32)
+    cen = np.ascontiguousarray(cen, np.float32)
+    n, dim = v.shape
+    L = lib()
+    codes = np.zeros((n, (dim + 7) // 8 if bits == 1 else dim), np.uint8)
+    corr = np.zeros((n, 4), np.float64)
+    trace = np.zeros((n, 3), np.int32)
+    row, dest = np.zeros(dim, np.float32), np.zeros(dim, np.uint8)
+    for i in range(n):
+        if sim == SIMS["COSINE"]:
+            L.orc_normalize(f32p(v[i]), dim, f32p(row))
+        else:
+            row[:] = v[i]
+        L.orc_scalar_quantize_trace(f32p(row), dim, bits, f32p(cen), sim, lam, iters, u8p(dest), f64p(corr[i]), i32p(trace[i]))
+        if bits == 1:
+            L.orc_pack_binary(u8p(dest), dim, u8p(codes[i]))
+        else:
+            codes[i] = dest
+    return codes, corr, trace
 
 
 def quantize_query(query, cen, sim, qb, lam=0.1, iters=5):
