@@ -362,6 +362,48 @@ def test_failed_append_multibit_code_out_of_range(compact, tmp_path):
         ix.close()
 
 
+@pytest.mark.parametrize("compact", [True, False])
+def test_an_emptied_index_decides_its_format_like_one_created_over_zero_rows(compact, tmp_path):
+    """The one place where "an index without explicit sums refuses a row whose quantizedComponentSum is not its popcount" does not
+    hold: an index that holds neither rows nor room.  A compaction to zero rows leaves "the index of zero rows", and that index - like
+    one created over zero rows - decides its record format at its next append: it takes the odd row and stores explicit sums from then
+    on, exactly as a twin created whole over those rows.  With room reserved first the format stays decided and the row is refused."""
+    sim, dim, n = 1, 96, 130
+    base = O.mulberry32(66, n * dim).reshape(n, dim)
+    codes, corr, cen = O.build_index(base, sim)
+    cdp = O.centroid_dp(cen)
+    odd = corr.copy()
+    odd[[3, 64], 3] += 2.0
+    orc = Oracle(codes, odd, dim, cen, sim, 4, O.mulberry32(67, 2 * dim).reshape(2, dim))
+    emptied, fresh, twin = make_index(codes, corr, dim, cdp, compact), make_index(codes[:0], corr[:0], dim, cdp, compact), make_index(codes, odd, dim, cdp, compact)
+    kept_room = make_index(codes, corr, dim, cdp, compact)
+    try:
+        with pytest.raises(B.BBQError) as e:             # while it holds rows, the index refuses the rows
+            emptied.append_rows(codes, odd)
+        assert e.value.code == capi.ERR_UNSUPPORTED
+        emptied.remove_rows(np.arange(n))
+        assert (emptied.n, emptied.capacity) == (0, 0)
+        want = file_bytes(twin, str(tmp_path / "twin"), cen, sim)
+        for ix, msg in ((emptied, "emptied"), (fresh, "created over zero rows")):
+            ix.append_rows(codes, odd)
+            assert (ix.n, ix.capacity, ix.bytes_per_row) == (n, twin.capacity, twin.bytes_per_row), msg
+            check_export(ix, codes, odd, msg)
+            assert file_bytes(ix, str(tmp_path / "grown"), cen, sim) == want, msg
+            orc.check_search(ix, [1, 10, n], msg, single=True)
+            orc.check_score_rows(ix, msg)
+        # emptied, but with room: the allocations exist in the format decided at creation, and the row is refused
+        kept_room.remove_rows(np.arange(n))
+        kept_room.reserve(64)
+        before = (kept_room.n, kept_room.capacity, file_bytes(kept_room, str(tmp_path / "before"), cen, sim))
+        with pytest.raises(B.BBQError) as e:
+            kept_room.append_rows(codes, odd)
+        assert e.value.code == capi.ERR_UNSUPPORTED
+        assert (kept_room.n, kept_room.capacity, file_bytes(kept_room, str(tmp_path / "after"), cen, sim)) == before
+    finally:
+        for h in (emptied, fresh, twin, kept_room):
+            h.close()
+
+
 # ------------------------------------------------------------------------------------------------ 5. capacity
 
 @pytest.mark.parametrize("compact", [True, False])

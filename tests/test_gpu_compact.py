@@ -22,7 +22,7 @@ RESET = {"force_dense": 0, "sweep_share": 1, "device_select": 1}
 
 
 class RowSet:
-    """one row set: the oracle's rows and, per query, its scores of all of them"""
+    """one row set: the fp32 rows, the oracle's rows quantized from them and, per query, its scores of all of them"""
 
     def __init__(self, name):
         if name == "seeded_1000x129":
@@ -35,6 +35,7 @@ class RowSet:
             self.sim, self.n, self.dim, self.ib, self.qb = O.SIMS[g["sim"]], g["n"], g["dim"], g["ib"], g["qb"]
             base, queries = O.golden_inputs(g)
             lam, iters = g["lambda"], g["iters"]
+        self.base, self.queries, self.lam, self.iters = base, queries, lam, iters
         self.codes, self.corr, self.cen = O.build_index(base, self.sim, lam, iters, ib=self.ib)
         self.cdp = O.centroid_dp(self.cen)
         self.orc = Oracle(self.codes, self.corr, self.dim, self.cen, self.sim, self.qb, queries, self.ib, lam, iters)
