@@ -118,18 +118,21 @@ int quiesce(bbq_index *ix, const char *who) {
 // the one function that allocates tile records: d_tiles and, for the compact layout, the side arrays for `cap` tiles
 int alloc_tiles(const bbq_index *ix, int64_t cap, DevBuf<uint8_t> &tiles, DevBuf<double> &exact) {
   if (tiles.alloc((size_t)(cap * ix->geom.tile_stride)) != hipSuccess ||
-      (ix->geom.layout == kLayoutCompact && exact.alloc((size_t)compact_side_bytes(cap) / 8) != hipSuccess)) {
+      (ix->geom.layout == kLayoutCompact && exact.alloc((size_t)compact_alloc_bytes(ix->geom, cap) / 8) != hipSuccess)) {
     (void)hipGetLastError();
     return fail(BBQ_ERR_OOM, "no device memory for %lld rows (%lld bytes of tiles)", (long long)(cap * kTileRows), (long long)(cap * ix->geom.tile_stride));
   }
   return BBQ_OK;
 }
 
-// what every write of the rows [row0, total) into `room` ends with: each touched tile's range of additive corrections (compact layout),
-// then the device has completed and the rows may be committed
+// what every write of the rows [row0, total) into `room` ends with: each touched tile's range of additive corrections and its rows'
+// component sums (compact layout), then the device has completed and the rows may be committed
 int finish_rows(const bbq_index *ix, const Room &room, int64_t row0, int64_t total) {
   hipStream_t s = ix->ctx->aux_stream;
-  if (ix->geom.layout == kLayoutCompact) HIPCHK(launch_tile_add_range(room.d_exact, total, room.d_add_range, s, row0 / kTileRows));
+  if (ix->geom.layout == kLayoutCompact) {
+    HIPCHK(launch_tile_add_range(room.d_exact, total, room.d_add_range, s, row0 / kTileRows));
+    HIPCHK(launch_tile_row_sums(tile_dest(ix, room), total, room.d_row_sums, s, row0 / kTileRows));
+  }
   HIPCHK(hipStreamSynchronize(s));
   return BBQ_OK;
 }
@@ -140,6 +143,7 @@ int make_room(bbq_index *ix, Storage &st, int64_t need_tiles, Room &r, bool geom
     r.d_tiles = st.d_tiles;
     r.d_exact = st.d_exact;
     r.d_add_range = const_cast<float *>(add_range_of(st.d_exact, st.cap_tiles));
+    r.d_row_sums = const_cast<uint16_t *>(row_sums_of(st.d_exact, st.cap_tiles, ix->geom));
     return BBQ_OK;
   }
   const int64_t cap = geometric ? std::max(need_tiles, st.cap_tiles + st.cap_tiles / 2) : need_tiles;
@@ -150,6 +154,7 @@ int make_room(bbq_index *ix, Storage &st, int64_t need_tiles, Room &r, bool geom
   r.d_tiles = r.tiles;
   r.d_exact = r.exact;
   r.d_add_range = const_cast<float *>(add_range_of(r.exact, cap));
+  r.d_row_sums = const_cast<uint16_t *>(row_sums_of(r.exact, cap, ix->geom));
   const int64_t used = tiles_of(st.view.n_rows);
   hipStream_t s = ix->ctx->aux_stream;
   if (used > 0) {
@@ -157,6 +162,7 @@ int make_room(bbq_index *ix, Storage &st, int64_t need_tiles, Room &r, bool geom
     if (ix->geom.layout == kLayoutCompact) {
       HIPCHK(hipMemcpyAsync(r.d_exact, st.d_exact, (size_t)(used * kTileRows) * 32, hipMemcpyDeviceToDevice, s));
       HIPCHK(hipMemcpyAsync(r.d_add_range, st.view.add_range, (size_t)used * 8, hipMemcpyDeviceToDevice, s));
+      if (r.d_row_sums) HIPCHK(hipMemcpyAsync(r.d_row_sums, st.view.row_sums, (size_t)row_sums_bytes(ix->geom, used), hipMemcpyDeviceToDevice, s));
     }
   }
   return BBQ_OK;

@@ -18,6 +18,7 @@
 //   check_x1       is every quantizedComponentSum the implied one (popcount / code sum)?   check_code_range: every multi-bit code in range?
 //   scatter_rows   the same rows -> the lanes of the ords they replace, in place (bbq_index_update*)
 //   tile_add_range compact layout: each tile's {min, max} of additionalCorrection, over a tile range or a tile list
+//   tile_row_sums  compact layout: each row's popcount / code sum from its stored codes, over the same tile range or tile list
 // and rows that are in tile records already:
 //   compact_tiles  the records gathered down to the rows a filter accepts, out of place (bbq_index_compact)
 // Every writer takes its destination as a TileDest and writes a row's corrections through write_corrections.
@@ -578,6 +579,40 @@ __global__ __launch_bounds__(256) void bbq_tile_add_range_list_kernel(const doub
   tile_add_range(exact, n_rows, add_range, tiles[t], threadIdx.x & 63);
 }
 
+// compact layout: row_sums[row] = the row's popcount (1-bit rows) or the sum of its store_bits-wide fields, over all w16 chunks of the
+// stored record (the padding behind the last dimension is zero) - the integer the sweep's own sum chain returns for the row
+// (tile_popcounts, tile_dot_multibit), as uint16: the array exists only where every sum fits (row_sums_fit).  One wave per tile, lane l
+// owns row 64 tile + l; lanes at and beyond n_rows get 0.
+__device__ __forceinline__ void tile_row_sums(const TileDest &src, int64_t n_rows, uint16_t *__restrict__ row_sums, int64_t tile, int lane) {
+  const u32x4 *__restrict__ cp = reinterpret_cast<const u32x4 *>(src.tiles + tile * (int64_t)src.geom.tile_stride);
+  const int sb = src.geom.store_bits;
+  const uint32_t mask = (1u << sb) - 1u;
+  uint32_t sum = 0;
+  for (int j = 0; j < src.geom.w16; ++j) {
+    const u32x4 c = cp[tile_chunk_index(j, lane)];
+    const uint32_t x[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (sb == 1) sum += (uint32_t)__popc(x[t]);
+      else
+        for (int f = 0; f < 32; f += sb) sum += (x[t] >> f) & mask;
+    }
+  }
+  const int64_t row = tile * kTileRows + lane;
+  row_sums[row] = row < n_rows ? (uint16_t)sum : (uint16_t)0;
+}
+__global__ __launch_bounds__(256) void bbq_tile_row_sums_kernel(TileDest src, int64_t n_rows, uint16_t *__restrict__ row_sums, int64_t tile0) {
+  const int64_t tile = tile0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tile >= (n_rows + kTileRows - 1) / kTileRows) return;
+  tile_row_sums(src, n_rows, row_sums, tile, threadIdx.x & 63);
+}
+__global__ __launch_bounds__(256) void bbq_tile_row_sums_list_kernel(TileDest src, int64_t n_rows, uint16_t *__restrict__ row_sums,
+                                                                     const int64_t *__restrict__ tiles, int64_t n_listed) {
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= n_listed) return;  // uniform per wave
+  tile_row_sums(src, n_rows, row_sums, tiles[t], threadIdx.x & 63);
+}
+
 // is every code of these multi-bit rows below 2^index_bits?  What bbq_retile_kernel reports while it writes, asked BEFORE
 // anything is written: an append that fails leaves the index as it was
 __global__ __launch_bounds__(256) void bbq_check_code_range_kernel(const uint8_t *__restrict__ codes, int64_t count, uint32_t limit,
@@ -730,6 +765,19 @@ hipError_t launch_scatter_rows(const TileDest &out, const StagedRows &in, const 
 hipError_t launch_tile_add_range_list(const double *exact, int64_t n_rows, float *add_range, const int64_t *tiles, int64_t n_listed, hipStream_t s) {
   if (n_listed <= 0) return hipSuccess;
   hipLaunchKernelGGL(bbq_tile_add_range_list_kernel, dim3((unsigned)((n_listed + 3) / 4)), dim3(256), 0, s, exact, n_rows, add_range, tiles, n_listed);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_row_sums(const TileDest &src, int64_t n_rows, uint16_t *row_sums, hipStream_t s, int64_t tile0) {
+  const int64_t n_tiles = (n_rows + kTileRows - 1) / kTileRows - tile0;
+  if (n_tiles <= 0 || !row_sums) return hipSuccess;
+  hipLaunchKernelGGL(bbq_tile_row_sums_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, src, n_rows, row_sums, tile0);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_row_sums_list(const TileDest &src, int64_t n_rows, uint16_t *row_sums, const int64_t *tiles, int64_t n_listed, hipStream_t s) {
+  if (n_listed <= 0 || !row_sums) return hipSuccess;
+  hipLaunchKernelGGL(bbq_tile_row_sums_list_kernel, dim3((unsigned)((n_listed + 3) / 4)), dim3(256), 0, s, src, n_rows, row_sums, tiles, n_listed);
   return hipGetLastError();
 }
 

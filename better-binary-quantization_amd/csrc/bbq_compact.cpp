@@ -52,6 +52,7 @@ int bbq_index_compact(bbq_index *ix, const bbq_filter *f) {
     room.d_tiles = room.tiles;
     room.d_exact = room.exact;
     room.d_add_range = const_cast<float *>(add_range_of(room.exact, room.cap_tiles));
+    room.d_row_sums = const_cast<uint16_t *>(row_sums_of(room.exact, room.cap_tiles, ix->geom));
     DevBuf<uint32_t> d_rank;
     CompactMap map;
     rc = stage_compact_map(f, d_rank, &map);

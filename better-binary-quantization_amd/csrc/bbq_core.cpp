@@ -116,6 +116,11 @@ int l2_share_shift(const bbq_index *ix) {
   return s;
 }
 
+// whether a per-query sparse sweep reads a row's component sum from the row_sums side array (where the storage has one) instead of counting
+// it (option row_sums).  An explicit 0 or 1 is taken as it is.  Automatic: yes - except with resident_mb 0, where every byte of every sweep
+// comes from HBM: there 2 B/row more cost time and the count is free, and the launch stays the one it was.
+bool row_sums_for_launch(const bbq_index *ix) { return ix->opt_row_sums < 0 ? ix->opt_resident_mb != 0 : ix->opt_row_sums != 0; }
+
 // ------------------------------------------------------------------------------------------------ plan
 
 static int cap_for(int64_t k, int64_t rows_before) {
@@ -413,6 +418,7 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
     resident += lv.resident_bytes;
     ScanArgs a = segment_scan_args(p, s, g, sto, lv.view, nq, qb);
     a.l2_shift = l2_share_shift(ix);  // (read by the per-query sweep alone, and only by its sparse launches)
+    a.idx.row_sums = row_sums_for_launch(ix) ? sto.view.row_sums : nullptr;  // (likewise; null where the storage has none)
     const bool append_here = !g.dense && ((append && (ix->opt_append_last || !last)) || use_mfma);
     if (append_here) {
       a.append_lists = d_lists;

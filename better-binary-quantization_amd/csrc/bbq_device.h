@@ -35,7 +35,9 @@ constexpr int kAppendStride = 32;        // uint32 words between two queries' co
 //   side array exact[row] = {lower, upper, additional, 0} as 4 doubles (32 B/row), followed by
 //   side array add_range[tile] = {min, max} of the tile's additionalCorrection as f32 (8 B per 64 rows, one broadcast load
 //   per wave): the bound takes whichever end makes the score larger; the additive term varies far less inside a tile than
-//   scores vary between rows
+//   scores vary between rows, followed (where a row's sum fits 16 bits, row_sums_fit) by
+//   side array row_sums[row] = the row's popcount / code sum as uint16 (128 B per tile, lanes beyond the last row 0): derived from the
+//   stored codes wherever add_range is written, never stored in a file; the per-query sparse sweep reads it instead of counting
 constexpr int kLayoutInline = 0;
 constexpr int kLayoutCompact = 1;
 // Multi-bit indexes (indexBits > 1; the reference keeps such rows as one byte per dimension,
@@ -144,6 +146,10 @@ __host__ __device__ inline int tile_stride_of(int w16, int layout, int has_x1) {
 }
 __host__ __device__ inline int pb_of(const TileGeom &g) { return row_bytes_of(g.dim, g.store_bits); }  // stored bytes per row, before the padding
 __host__ __device__ inline int bytes_per_row_of(const TileGeom &g) { return g.tile_stride / kTileRows; }
+// the compact layout's row_sums side array exists iff the largest possible component sum of a row fits its 16 bits
+__host__ __device__ inline bool row_sums_fit(const TileGeom &g) {
+  return g.layout == kLayoutCompact && (int64_t)g.dim * ((1 << g.store_bits) - 1) <= 65535;
+}
 // where the build kernels write: the records of a storage (or a scratch tile set), the compact layout's side rows, and their geometry
 struct TileDest {
   uint8_t *tiles;
@@ -208,9 +214,13 @@ struct IndexView {
   int64_t resident_share;  // >= 0: chunk c is resident iff (c & 63) < resident_share (the resident chunks spread over the whole sweep)
   int64_t nt_delta;        // always 0.  The streamed loads add it to their address so that the compiler sees two different addresses
                            // in the two branches: it merges loads that differ only in the cache policy into ONE plain load
+  const uint16_t *row_sums;  // kLayoutCompact: [tiles][64] each row's popcount / code sum, or null.  A storage's view holds the array where
+                             // it exists (row_sums_fit); a LAUNCH's view carries it only where the per-query sparse sweep is to read the
+                             // sum instead of counting it (option row_sums, row_sums_for_launch) - every other kernel ignores it
 };
 // the kernels' argument loads depend on these offsets
-static_assert(offsetof(IndexView, geom) == 32 && sizeof(TileGeom) == 24 && offsetof(IndexView, resident_tiles) == 56 && sizeof(IndexView) == 80,
+static_assert(offsetof(IndexView, geom) == 32 && sizeof(TileGeom) == 24 && offsetof(IndexView, resident_tiles) == 56 &&
+                  offsetof(IndexView, row_sums) == 80 && sizeof(IndexView) == 88,
               "IndexView layout");
 
 // Per-query uniforms of the score formula (src/batchDotProduct.ts:478-617)

@@ -43,9 +43,11 @@ constexpr int64_t kMaxFastK = 4096;  // beyond this the dense path is used: the 
 struct Storage {
   DevBuf<uint8_t> d_tiles;
   DevBuf<double> d_exact;     // kLayoutCompact: exact corrections, gathered for the rows whose bound passes; the per-tile
-                              // additive-correction ranges (view.add_range) live behind them in the same allocation
+                              // additive-correction ranges (view.add_range) and, where they exist, the rows' component sums
+                              // (view.row_sums) live behind them in the same allocation
   int64_t cap_tiles = 0;      // tiles both allocations hold (>= the tiles in use; more after bbq_index_reserve / an append that grew):
-                              // exact[] takes cap_tiles * 64 rows and add_range[] starts behind THAT, wherever the rows end
+                              // exact[] takes cap_tiles * 64 rows, add_range[] starts behind THAT, wherever the rows end, and
+                              // row_sums[] behind add_range[]'s cap_tiles entries
   IndexView view{};
   int64_t row_id_base = 0;
   int64_t n_chunks() const { return (view.n_rows + kChunkRows - 1) / kChunkRows; }
@@ -165,6 +167,14 @@ inline int64_t compact_side_bytes(int64_t n_tiles) { return n_tiles * kTileRows 
 inline const float *add_range_of(const double *d_exact, int64_t cap_tiles) {
   return d_exact ? reinterpret_cast<const float *>(d_exact + cap_tiles * kTileRows * 4) : nullptr;
 }
+// the rows' component sums, uint16 per row, behind the cap_tiles add ranges (8 bytes each: compact_side_bytes(cap_tiles) from the
+// start) - a derived array that no file holds; null where the geometry has none (row_sums_fit)
+inline int64_t row_sums_bytes(const TileGeom &g, int64_t n_tiles) { return row_sums_fit(g) ? n_tiles * kTileRows * 2 : 0; }
+inline const uint16_t *row_sums_of(const double *d_exact, int64_t cap_tiles, const TileGeom &g) {
+  return d_exact && row_sums_fit(g) ? reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint8_t *>(d_exact) + compact_side_bytes(cap_tiles)) : nullptr;
+}
+// bytes of a compact storage's side allocation for cap_tiles tiles
+inline int64_t compact_alloc_bytes(const TileGeom &g, int64_t cap_tiles) { return compact_side_bytes(cap_tiles) + row_sums_bytes(g, cap_tiles); }
 
 }  // namespace bbq
 
@@ -203,6 +213,8 @@ struct bbq_index {
                              // Cache from one query's sweep to the next (launch_view(), bbq_index.cpp); -1: this index's share of kResidentAutoBytes
   int opt_l2_share = -1;  // queries whose workgroups sweep one chunk back to back on one XCD, so that all but the first read it through that
                           // XCD's L2 (sweep_coord, bbq_device.h): 1 off, 2..32, -1: l2_share_shift()'s choice (bbq_core.cpp)
+  int opt_row_sums = -1;  // the per-query sparse sweep reads a row's component sum from the row_sums side array instead of counting it:
+                          // 0 never, 1 wherever the array exists, -1: row_sums_for_launch()'s choice (bbq_core.cpp)
   int opt_fast_bound = 1;  // 1: the compact layout's score bound in f32 against the threshold's z image wherever the query's f32 images allow it
                            // (fast_bound_images, bbq_query.cpp); 0: always the f64 bound.  The answers are the same either way
   int opt_latency_presample = 1;  // ... and on large indexes get their threshold from per-wave top keys of a prefix (two small launches) instead of two scan / finalize pairs
@@ -260,6 +272,7 @@ inline void set_storage_view(const bbq_index *ix, Storage &st, int64_t n_rows, i
   st.view.tiles = st.d_tiles;
   st.view.exact = st.d_exact;
   st.view.add_range = add_range_of(st.d_exact, st.cap_tiles);
+  st.view.row_sums = row_sums_of(st.d_exact, st.cap_tiles, ix->geom);
 }
 // bytes per row as the caller hands them over and gets them back: packed bits, or one byte per dimension for a multi-bit index
 inline int64_t caller_row_bytes(const bbq_index *ix) { return ix->geom.store_bits > 1 ? ix->geom.dim : pb_of(ix->geom); }
@@ -284,6 +297,7 @@ struct Room {
   uint8_t *d_tiles = nullptr;   // where the rows are written
   double *d_exact = nullptr;
   float *d_add_range = nullptr;
+  uint16_t *d_row_sums = nullptr;  // null: the geometry has none
 };
 // where the build kernels write the rows that go into `r`, and the scratch tile set quantize_into's explicit-sums branch packs codes
 // into: inline records of the index's row width without a component sum (a freshly quantized row's sum is its popcount)
@@ -303,8 +317,8 @@ int check_append_index(const bbq_index *ix, int64_t n, const char *who);
 int quiesce(bbq_index *ix, const char *who);
 // the one function that allocates tile records: d_tiles and, for the compact layout, the side arrays for `cap` tiles (BBQ_ERR_OOM)
 int alloc_tiles(const bbq_index *ix, int64_t cap, DevBuf<uint8_t> &tiles, DevBuf<double> &exact);
-// what every write of the rows [row0, total) into `room` ends with: the touched tiles' add ranges (compact layout), then the device has
-// completed and the rows may be committed
+// what every write of the rows [row0, total) into `room` ends with: the touched tiles' add ranges and row sums (compact layout), then
+// the device has completed and the rows may be committed
 int finish_rows(const bbq_index *ix, const Room &room, int64_t row0, int64_t total);
 // geometric: half as much again as the capacity, at least what is needed (an empty storage gets exactly what is needed); otherwise
 // exactly what is needed.  BBQ_ERR_OOM without device memory.

@@ -107,6 +107,7 @@ static int64_t cache_sharers_bytes(bbq_index *ix, int64_t own) {
 // keep in the cache is a part of ITS range (the launches of a sub-batch run one after the other, each over its own rows).
 LaunchView launch_view(bbq_index *ix, const Storage &sto, int64_t chunk_begin, int64_t n_chunks) {
   IndexView v = sto.view;
+  v.row_sums = nullptr;  // carried only by the launches of the per-query sparse sweep that are to read it (row_sums_for_launch)
   const int64_t all_chunks = sto.n_chunks();
   if (n_chunks < 0) n_chunks = all_chunks - chunk_begin;
   const int64_t chunk_bytes = (int64_t)kTilesPerChunk * v.geom.tile_stride;
@@ -268,6 +269,7 @@ int bbq_set_option(bbq_index *ix, const char *name, int64_t v) {
   else if (n == "resident_mb" && v >= -1 && v <= 1 << 20) ix->opt_resident_mb = (int)v;
   else if (n == "l2_share" && (v == -1 || (v >= 1 && v <= 32 && (v & (v - 1)) == 0))) ix->opt_l2_share = (int)v;
   else if (n == "fast_bound" && (v == 0 || v == 1)) ix->opt_fast_bound = (int)v;
+  else if (n == "row_sums" && v >= -1 && v <= 1) ix->opt_row_sums = (int)v;
   else if (n == "replay_threads" && v >= 1 && v <= 256) ix->opt_replay_threads = (int)v;
   else if (n == "force_dense" && (v == 0 || v == 1)) ix->opt_force_dense = (int)v;
   else if (n == "device_select" && (v == 0 || v == 1)) ix->opt_device_select = (int)v;

@@ -33,15 +33,18 @@ __device__ __forceinline__ bool chunk_is_resident(int64_t chunk, const IndexView
 // ALL loads of a wave's tile in ONE two-way branch (W > 0): the W code chunks of the lane's row and its corrections - CORR 0: none,
 // 1: the compact word, 2: the inline f64 corrections (lower, upper | additional | component sum if stored).  Loads that are
 // already in flight when the branch is reached make the compiler wait for them inside it (it assumes either arm may follow them).
-template <int W, int CORR>
+// RS: the lane's entry of the row_sums side array (rs points at it) is one more load of the tile, under the arm's cache policy -> rsum.
+template <int W, int CORR, bool RS = false>
 __device__ __forceinline__ void load_tile(const uint8_t *__restrict__ tp, int lane, bool has_x1, bool resident, int64_t nt_delta,
-                                          u32x4 (&c)[W], uint32_t &cw, f64x2 &lu, double &xadd, double &x1) {
+                                          u32x4 (&c)[W], uint32_t &cw, f64x2 &lu, double &xadd, double &x1,
+                                          const uint16_t *__restrict__ rs = nullptr, uint32_t *rsum = nullptr) {
   const u32x4 *__restrict__ cp = reinterpret_cast<const u32x4 *>(tp) + lane;
   const uint8_t *__restrict__ cr = tp + tile_corr_offset(W);
   if (resident) {  // scalar branch
 #pragma unroll
     for (int j = 0; j < W; ++j) c[j] = cp[j * kTileRows];
     if constexpr (CORR == 1) cw = *(reinterpret_cast<const uint32_t *>(cr) + lane);
+    if constexpr (RS) *rsum = *rs;
     if constexpr (CORR == 2) {
       lu = *(reinterpret_cast<const f64x2 *>(cr) + lane);
       xadd = *(reinterpret_cast<const double *>(cr + kCorrAddOffset) + lane);
@@ -54,6 +57,7 @@ __device__ __forceinline__ void load_tile(const uint8_t *__restrict__ tp, int la
 #pragma unroll
     for (int j = 0; j < W; ++j) c[j] = BBQ_STREAM_LOAD(cs + j * kTileRows);
     if constexpr (CORR == 1) cw = BBQ_STREAM_LOAD(reinterpret_cast<const uint32_t *>(crs) + lane);
+    if constexpr (RS) *rsum = BBQ_STREAM_LOAD(stream_ptr(rs, nt_delta));
     if constexpr (CORR == 2) {
       lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(crs) + lane);
       xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(crs + kCorrAddOffset) + lane);
@@ -108,35 +112,35 @@ template <int QB> __device__ __forceinline__ uint32_t plane_dot(const uint32_t (
 }
 
 // One tile = 64 rows, one row per lane.  W = compile-time number of 16-byte chunks per row: the chunks come in registers (load_tile).
-// Returns qcDist; `ones` = the row's popcount
-template <int QB, int W>
+// Returns qcDist; `ones` = the row's popcount - left alone with ONES false: the caller has it from the row_sums side array
+template <int QB, int W, bool ONES = true>
 __device__ __forceinline__ uint32_t tile_popcounts(const u32x4 (&c)[W], const u32x4 *__restrict__ s_planes, uint32_t &ones) {
   uint32_t acc[QB];
 #pragma unroll
   for (int p = 0; p < QB; ++p) acc[p] = 0;
-  ones = 0;
+  if constexpr (ONES) ones = 0;
 #pragma unroll
   for (int j = 0; j < W; ++j) {
 #pragma unroll
     for (int p = 0; p < QB; ++p) acc[p] = popc4_acc(c[j] & s_planes[j * QB + p], acc[p]);
-    ones = popc4_acc(c[j], ones);
+    if constexpr (ONES) ones = popc4_acc(c[j], ones);
   }
   return plane_dot<QB>(acc);
 }
 // any width (w16 chunks, known at run time): streamed chunk by chunk
-template <int QB>
+template <int QB, bool ONES = true>
 __device__ __forceinline__ uint32_t tile_popcounts_any(const uint8_t *__restrict__ tp, int lane, int w16, const u32x4 *__restrict__ s_planes,
                                                        uint32_t &ones) {
   const u32x4 *__restrict__ cp = reinterpret_cast<const u32x4 *>(tp) + lane;
   uint32_t acc[QB];
 #pragma unroll
   for (int p = 0; p < QB; ++p) acc[p] = 0;
-  ones = 0;
+  if constexpr (ONES) ones = 0;
   for (int j = 0; j < w16; ++j) {
     const u32x4 c = BBQ_STREAM_LOAD(cp + j * kTileRows);
 #pragma unroll
     for (int p = 0; p < QB; ++p) acc[p] += popc4(c & s_planes[j * QB + p]);
-    ones += popc4(c);
+    if constexpr (ONES) ones += popc4(c);
   }
   return plane_dot<QB>(acc);
 }

@@ -60,6 +60,11 @@ hipError_t launch_check_code_range(const uint8_t *codes, int64_t count, int32_t 
 hipError_t launch_tile_add_range(const double *exact, int64_t n_rows, float *add_range, hipStream_t s, int64_t tile0);
 // the same for the n_listed tiles named (each below ceil(n_rows / 64)): an update's touched tiles
 hipError_t launch_tile_add_range_list(const double *exact, int64_t n_rows, float *add_range, const int64_t *tiles, int64_t n_listed, hipStream_t s);
+// compact layout with a row_sums side array (row_sums_fit): each row's popcount / code sum, computed from the codes the tiles of `src`
+// hold -> row_sums[tile * 64 + lane], the lanes at and beyond n_rows 0.  Tiles [tile0, ceil(n_rows / 64)), or the n_listed tiles named:
+// launched wherever add_range is written, over the same tiles
+hipError_t launch_tile_row_sums(const TileDest &src, int64_t n_rows, uint16_t *row_sums, hipStream_t s, int64_t tile0);
+hipError_t launch_tile_row_sums_list(const TileDest &src, int64_t n_rows, uint16_t *row_sums, const int64_t *tiles, int64_t n_listed, hipStream_t s);
 // rows in the caller's shape -> the lanes of the rows they replace: staged row pos[i] becomes row ords[pos[i]] for the n_winners
 // entries of pos, which name distinct ords in ascending order (bbq_update_winners); nothing else is written.  ords are rows of `out`;
 // multi-bit codes have been range-checked (launch_check_code_range): *bad is the shared packer's and stays clear

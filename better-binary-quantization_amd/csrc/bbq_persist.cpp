@@ -392,6 +392,13 @@ int bbq_index_load(const char *prefix, int32_t device, bbq_index **out, float *c
     }
   }
   if (dsum != want_sum) return bail(fail(BBQ_ERR_INVALID_ARG, "%s: vector data checksum mismatch", dpath.c_str()));
+  // the rows' component sums are in no file: derived from the loaded codes, one launch per storage
+  if (ix->geom.layout == kLayoutCompact) {
+    hipStream_t s = ctx->aux_stream;
+    if (launch_tile_row_sums(tile_dest(ix.get(), room), h.vectorCount, room.d_row_sums, s, 0) != hipSuccess ||
+        launch_tile_row_sums(tile_dest(ix.get(), proom), px.pilotRows, proom.d_row_sums, s, 0) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return bail(fail(BBQ_ERR_HIP, "bbq_index_load: the row sums could not be rebuilt"));
+  }
   commit(ix.get(), st, room, h.vectorCount);
   if (ix->has_pilot) commit(ix.get(), pt, proom, px.pilotRows);
   if (centroid_out) memcpy(centroid_out, cen.data(), cen.size() * 4);

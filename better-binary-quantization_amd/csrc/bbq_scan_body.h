@@ -16,8 +16,9 @@ namespace bbq {
 // fields: one AND, one shift + AND); query values above 15 (QB == 8) are split into low and high nibbles,
 // q = lo + 16 hi, so the dot is dot(x, lo) + 16 dot(x, hi).  s_q holds, per row dword, the matching query dwords
 // (query_units_per_chunk; written by the host in exactly this order).  `sum` = the row's component sum (= quantizedComponentSum
-// of a freshly quantized row, src/optimizedScalarQuantizer.ts:204-209).
-template <int QB, int SB>
+// of a freshly quantized row, src/optimizedScalarQuantizer.ts:204-209) - left alone with SUM false: the caller has it from the row_sums
+// side array.
+template <int QB, int SB, bool SUM = true>
 __device__ __forceinline__ void dot_chunk_multibit(const u32x4 c, const uint32_t *__restrict__ sq, uint32_t &lo, uint32_t &hi, uint32_t &sum) {
   const uint32_t x[4] = {c.x, c.y, c.z, c.w};
   constexpr int QN = query_units_per_chunk(QB, SB);  // query dwords per row dword
@@ -32,39 +33,39 @@ __device__ __forceinline__ void dot_chunk_multibit(const u32x4 c, const uint32_t
         hi = __builtin_amdgcn_udot8(e, qw[2], hi, false);
         hi = __builtin_amdgcn_udot8(o, qw[3], hi, false);
       }
-      sum = __builtin_amdgcn_udot8(e + o, 0x11111111u, sum, false);  // nibbles of e + o are at most 6
+      if constexpr (SUM) sum = __builtin_amdgcn_udot8(e + o, 0x11111111u, sum, false);  // nibbles of e + o are at most 6
     } else if constexpr (SB == 4) {
       lo = __builtin_amdgcn_udot8(x[t], qw[0], lo, false);
       if constexpr (QB > 4) hi = __builtin_amdgcn_udot8(x[t], qw[1], hi, false);
-      sum = __builtin_amdgcn_udot8(x[t], 0x11111111u, sum, false);
+      if constexpr (SUM) sum = __builtin_amdgcn_udot8(x[t], 0x11111111u, sum, false);
     } else {
       lo = __builtin_amdgcn_udot4(x[t], qw[0], lo, false);
-      sum = __builtin_amdgcn_udot4(x[t], 0x01010101u, sum, false);
+      if constexpr (SUM) sum = __builtin_amdgcn_udot4(x[t], 0x01010101u, sum, false);
     }
   }
 }
 
-template <int QB, int W, int SB>
+template <int QB, int W, int SB, bool SUM = true>
 __device__ __forceinline__ void tile_dot_multibit(const u32x4 (&c)[W], const u32x4 *__restrict__ s_planes, uint32_t &qc, uint32_t &sum) {
   const uint32_t *__restrict__ sq = reinterpret_cast<const uint32_t *>(s_planes);
   constexpr int QN = query_units_per_chunk(QB, SB);
   uint32_t lo = 0, hi = 0;
-  sum = 0;
+  if constexpr (SUM) sum = 0;
 #pragma unroll
-  for (int j = 0; j < W; ++j) dot_chunk_multibit<QB, SB>(c[j], sq + j * 4 * QN, lo, hi, sum);
+  for (int j = 0; j < W; ++j) dot_chunk_multibit<QB, SB, SUM>(c[j], sq + j * 4 * QN, lo, hi, sum);
   qc = lo + (hi << 4);
 }
-template <int QB, int SB>
+template <int QB, int SB, bool SUM = true>
 __device__ __forceinline__ void tile_dot_multibit_any(const uint8_t *__restrict__ tp, int lane, int w16, const u32x4 *__restrict__ s_planes,
                                                       uint32_t &qc, uint32_t &sum) {
   const u32x4 *__restrict__ cp = reinterpret_cast<const u32x4 *>(tp) + lane;
   const uint32_t *__restrict__ sq = reinterpret_cast<const uint32_t *>(s_planes);
   constexpr int QN = query_units_per_chunk(QB, SB);
   uint32_t lo = 0, hi = 0;
-  sum = 0;
+  if constexpr (SUM) sum = 0;
   for (int j = 0; j < w16; ++j) {
     const u32x4 c = BBQ_STREAM_LOAD(cp + j * kTileRows);
-    dot_chunk_multibit<QB, SB>(c, sq + j * 4 * QN, lo, hi, sum);
+    dot_chunk_multibit<QB, SB, SUM>(c, sq + j * 4 * QN, lo, hi, sum);
   }
   qc = lo + (hi << 4);
 }
@@ -81,10 +82,14 @@ __device__ __forceinline__ void tile_dot_multibit_any(const uint8_t *__restrict_
 // valid row - it gathers no exact corrections, lists nothing and raises no NaN flag.  The end of the chunk (count word, flood tier,
 // append path) is the same for both.  (One kernel template and a parameter pack rather than a shared __device__ body under two
 // kernels: inlined through a function the unfiltered instantiations came out with other instruction schedules.)
-template <int QB, int W, int MODE, int SB = 1, class... Accept>
+// RS (MODE 2 only, chosen by the launch iff its view carries IndexView::row_sums): the row's popcount / code sum is not counted here - it is
+// the same for every query, segment and call - but loaded from the side array with the tile's other loads; the popcount loop and the
+// multi-bit dot run without their sum chain.  The value is what that chain returns, so the bound and the score are the same bits.
+template <int QB, int W, int MODE, int SB = 1, bool RS = false, class... Accept>
 __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, const Accept... accept_arg) {
   constexpr bool FILT = sizeof...(Accept) > 0;
   static_assert(sizeof...(Accept) <= 1 && !(FILT && (MODE & 1)), "at most the accept bitset, and a filtered sweep is sparse");
+  static_assert(!RS || (MODE & 3) == 2, "row sums are read by the sparse sweep of the compact layout alone");
   const uint64_t *__restrict__ accept = nullptr;
   if constexpr (FILT) accept = (accept_arg, ...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -150,11 +155,12 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
     constexpr int CORR = !COMPACT ? 2 : (DENSE ? 0 : 1);
     if constexpr (W > 0) {
       u32x4 c[W];
-      load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
+      if constexpr (RS) load_tile<W, CORR, true>(tp, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, a.idx.row_sums + row, &ones);
+      else load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
       if constexpr (COMPACT && DENSE) exact_corrections<true>(a.idx.exact, row, lu, xadd);
       if constexpr (COMPACT && !DENSE) aadd = tile_add_bound(a.idx, tile, p.sim);
-      if constexpr (SB == 1) qc = tile_popcounts<QB, W>(c, s_planes, ones);
-      else tile_dot_multibit<QB, W, SB>(c, s_planes, qc, ones);
+      if constexpr (SB == 1) qc = tile_popcounts<QB, W, !RS>(c, s_planes, ones);
+      else tile_dot_multibit<QB, W, SB, !RS>(c, s_planes, qc, ones);
     } else {  // a row width without a compiled kernel: streamed chunk by chunk
       if constexpr (!COMPACT) {
         lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(cr) + lane);
@@ -165,22 +171,28 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
       } else {
         cw = BBQ_STREAM_LOAD(reinterpret_cast<const uint32_t *>(cr) + lane);
         aadd = tile_add_bound(a.idx, tile, p.sim);
+        if constexpr (RS) ones = BBQ_STREAM_LOAD(a.idx.row_sums + row);
       }
-      if constexpr (SB == 1) qc = tile_popcounts_any<QB>(tp, lane, w16, s_planes, ones);
-      else tile_dot_multibit_any<QB, SB>(tp, lane, w16, s_planes, qc, ones);
+      if constexpr (SB == 1) qc = tile_popcounts_any<QB, !RS>(tp, lane, w16, s_planes, ones);
+      else tile_dot_multibit_any<QB, SB, !RS>(tp, lane, w16, s_planes, qc, ones);
     }
-    if (!a.idx.geom.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
+    // quantizedComponentSum of a freshly quantized row is its popcount / component sum (RS: converted where a double is needed, below)
+    if constexpr (!RS) if (!a.idx.geom.has_x1) x1 = (double)ones;
 
     bool need_exact = true;
     if constexpr (COMPACT && !DENSE) {
       // the f32 form of the bound wherever the query allows it - except in the one instantiation (filtered, 2-bit rows of 16 chunks, query
       // values above 15) that it cost a wave of occupancy: 92 -> 98 vector registers with it, whatever its place in the code
       constexpr bool F32_BOUND = !(FILT && SB == 2 && QB == 8 && W == 16);
-      if constexpr (F32_BOUND) need_exact = compact_bound_passes(valid, qc, cw, aadd, ones, x1, p, th);
+      if constexpr (RS) {  // the f32 form takes the integer; the sum becomes a double only inside the f64 form and for the exact score
+        if constexpr (F32_BOUND) need_exact = p.fast_bound ? fast_bound_passes(valid, qc, cw, aadd, ones, p, th) : f64_bound_passes(valid, qc, cw, aadd, (double)ones, p, theta);
+        else need_exact = f64_bound_passes(valid, qc, cw, aadd, (double)ones, p, theta);
+      } else if constexpr (F32_BOUND) need_exact = compact_bound_passes(valid, qc, cw, aadd, ones, x1, p, th);
       else need_exact = f64_bound_passes(valid, qc, cw, aadd, x1, p, theta);
       if (need_exact) exact_corrections(a.idx.exact, row, lu, xadd);
     }
     if (need_exact) {
+      if constexpr (RS) x1 = (double)ones;
       const double s64 = score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
       const float s32 = (float)s64;
       const uint32_t bits = __float_as_uint(s32);
@@ -244,6 +256,16 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
 // ---------------------------------------------------------------------------------------------------
 // dispatch over the instantiations: FILT selects the kernel family, `accept` is its accept bitset (null without)
 
+// The instantiations that keep counting the sum although the launch carries the row sums: their RS twin came out of this build's compiler
+// with a wave of occupancy less than they have (docs/dropped.md, "row sums"; F32_BOUND above is the precedent).  To check again: build both
+// kernel files with -Rpass-analysis=kernel-resource-usage and compare each RS instantiation's Occupancy with its twin's.
+template <bool FILT, int QB, int W, int SB>
+constexpr bool row_sums_twin() {
+  if (SB == 1 && W == 12 && (QB == 1 || (QB == 8 && FILT))) return false;
+  if (SB == 4 && (W == 12 || W == 16) && (QB == 8 || FILT)) return false;
+  return true;
+}
+
 template <bool FILT, int QB, int W, int MODE, int SB = 1>
 static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s) {
   ScanArgs a = args;  // the map's parameters: what the kernel decodes its block index with is what the grid below is built from
@@ -253,7 +275,14 @@ static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, in
   const int w16 = W > 0 ? W : a.idx.geom.w16;
   const size_t smem = (size_t)w16 * query_units_per_chunk(QB, SB) * 16 + ((MODE & 1) ? 0 : (size_t)((a.ovf || a.append_lists) ? kChunkRows : a.cap) * 8) + 16;
   dim3 grid(sweep_grid_x(n_chunks, a.l2_shift), sweep_grid_y(n_queries, a.l2_shift), 1), block(kChunkRows, 1, 1);
-  if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, const uint64_t *>), grid, block, smem, s, a, accept);
+  if constexpr ((MODE & 3) == 2 && row_sums_twin<FILT, QB, W, SB>()) {
+    if (a.idx.row_sums) {  // the launch's view carries the row sums: the sweep that reads them
+      if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, const uint64_t *>), grid, block, smem, s, a, accept);
+      else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true>), grid, block, smem, s, a);
+      return hipGetLastError();
+    }
+  }
+  if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, false, const uint64_t *>), grid, block, smem, s, a, accept);
   else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB>), grid, block, smem, s, a);
   return hipGetLastError();
 }

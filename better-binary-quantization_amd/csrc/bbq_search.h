@@ -67,6 +67,8 @@ int validate_query_args(const bbq_index *ix, int32_t nq, const uint8_t *qquant, 
 int effective_batch(const bbq_index *ix, int64_t n_queries = 0);
 // ScanArgs::l2_shift of a per-query sparse sweep: log2 of the queries co-scheduled per chunk (option l2_share)
 int l2_share_shift(const bbq_index *ix);
+// does a per-query sparse sweep of this index read the rows' component sums from the side array (option row_sums)?
+bool row_sums_for_launch(const bbq_index *ix);
 Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k = 0, bool latency = false);
 Plan build_filtered_plan(const bbq_index *ix, const bbq_filter &f, int64_t k, int64_t final_k, bool latency);
 int ensure_slot(const SearchCall &c, Slot &s, int nq, bool own_lists);

@@ -46,7 +46,7 @@ int check_update(const bbq_index *ix, const int32_t *ords, int64_t n, const char
 }
 
 // The n checked rows staged in device memory, in the caller's shape, replace the rows ords[] names: the winners `pos` go to their
-// lanes, then each touched tile's add range is recomputed over its valid rows as a creation computes it (compact layout).  Everything
+// lanes, then each touched tile's add range and row sums are recomputed as a creation computes them (compact layout).  Everything
 // that can fail without the device failing - the allocations - comes before the first write.
 int scatter_device_rows(bbq_index *ix, const int32_t *ords, int64_t n, const std::vector<int64_t> &pos, const uint8_t *d_codes, const double *d_corr) {
   hipStream_t s = ix->ctx->aux_stream;
@@ -71,7 +71,10 @@ int scatter_device_rows(bbq_index *ix, const int32_t *ords, int64_t n, const std
   rc = make_room(ix, st, tiles_of(st.view.n_rows), room);
   if (rc != BBQ_OK) return rc;
   HIPCHK(launch_scatter_rows(tile_dest(ix, room), StagedRows{d_codes, d_corr}, d_ords, d_pos, (int64_t)pos.size(), ix->index_bits, d_bad, s));
-  if (compact) HIPCHK(launch_tile_add_range_list(room.d_exact, st.view.n_rows, room.d_add_range, d_tiles, (int64_t)tiles.size(), s));
+  if (compact) {
+    HIPCHK(launch_tile_add_range_list(room.d_exact, st.view.n_rows, room.d_add_range, d_tiles, (int64_t)tiles.size(), s));
+    HIPCHK(launch_tile_row_sums_list(tile_dest(ix, room), st.view.n_rows, room.d_row_sums, d_tiles, (int64_t)tiles.size(), s));
+  }
   HIPCHK(hipStreamSynchronize(s));
   return BBQ_OK;
 }

@@ -588,6 +588,14 @@ int bbq_reset_stats(bbq_index *idx);
  *     a launch order, never a different answer).  1: off, the plain order.  -1: the library's choice, 1 with resident_mb 0.  An explicit
  *     value holds whatever resident_mb says; a launch co-schedules no more queries than it has, and fewer per chunk when it sweeps more
  *     than 134 M rows (the grid's x extent is a 32-bit count of work-items)
+ *   row_sums -1|0|1 (-1): compact corrections: 1 lets the per-query sweep read a row's component sum (its popcount / code sum) from a
+ *     derived side array of 2 B/row instead of counting it for every query again; 0: always count.  -1: the library's choice - read,
+ *     except with resident_mb 0, whose launches stay what they were.  An explicit value holds whatever resident_mb says.  The array
+ *     exists where dim * (2^store bits - 1) <= 65535 (elsewhere 1 is accepted and the sweep counts), and a few row widths keep counting
+ *     whatever the option says, because the reading kernel would run with fewer waves there: 1-bit rows of 1409..1536 dimensions at
+ *     queryBits 1 (filtered searches: also at queryBits 8), 4-bit rows of 353..384 and of 481..512 dimensions at queryBits 8
+ *     (filtered: also at 4).  No statistic tells which kernel ran.  The array is kept beside the rows through
+ *     every append, update and compaction, and is in no file: a load derives it again.  The same value either way: never a different answer
  *   fast_bound 0|1 (1): compact corrections: 1 tests the score bound of a row in f32 against the threshold's image in the linear space of
  *     the score formula, for every query whose corrections have f32 images (others keep the f64 bound); 0: always the f64 bound through
  *     the similarity transform.  A pre-filter in front of the exact score either way: never a different answer
