@@ -416,6 +416,28 @@ struct GatherArgs {
   float *out_score32;
 };
 
+// range search (bbq_range_kernels.hip): every row of the index whose f32 score key beats the caller's threshold, count-then-fill.  The
+// count pass leaves counts[q][chunk]; bbq_range_offsets_kernel turns them IN PLACE into each chunk's offset inside its query's answer
+// and lists the chunks that hold a row; the fill pass sweeps those chunks once more and writes every passing row at
+// base[q] + chunk_off[q][chunk] + its rank inside the chunk: the answer comes out ascending by row without an atomic.
+constexpr int kRangeOffsetsThreads = 1024;
+struct RangeArgs {
+  IndexView idx;
+  const uint4 *qplanes;        // [Q][w16][QU] staged query data, as ScanArgs::qplanes
+  const QueryParams *qparams;  // [Q]
+  const Threshold *theta;      // [Q] written by bbq_range_theta_kernel from the host's keys (bbq_range_key)
+  const uint64_t *accept;      // [tiles of idx] the accept words of a filter, or null: every row
+  int32_t n_chunks;            // chunks of idx: the stride of the three per-chunk arrays
+  int32_t q_first;             // the launch's first query (blockIdx.y counts from it)
+  uint32_t *counts;            // count pass: [Q][n_chunks] passing rows of each chunk
+  // fill pass
+  const uint32_t *chunk_off;   // [Q][n_chunks] passing rows of the query in front of each chunk (the counts, scanned in place)
+  const uint32_t *nonempty;    // [Q][n_chunks] the chunks with a passing row, ascending; n_nonempty[q] of them
+  const uint32_t *n_nonempty;  // [Q]
+  const int64_t *base;         // [Q] where the query's answer starts inside `out`
+  uint64_t *out;               // entries (row << 32 | f32 score bits) of the launch's queries, back to back
+};
+
 constexpr int kFinalizeThreads = 1024;
 constexpr int kFinalizeJobs = 4096;      // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)
 constexpr int kFinalizeKeyCap = 12288;   // LDS key buffer of the finalize kernel (new keys + running top-k)

@@ -11,6 +11,7 @@
 //   bbq_update.cpp   rows of an index replaced in place (bbq_index_update*, bbq_update_winners)
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
 //   bbq_gather.cpp   scoring and ranking chosen rows (bbq_score_ords*, bbq_search_ords_batch)
+//   bbq_range.cpp    range search: every row at or above a threshold (bbq_range_key, bbq_count_range_batch, bbq_search_range_batch)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
 // bbq_entry.h is the codec of the 64-bit entries, keys and answer headers; bbq_workqueue.h the host threads' job queue.
@@ -135,6 +136,7 @@ struct DeviceCtx {
   DevBuf<uint8_t> d_aux_qbuf;
   DevBuf<uint32_t> d_aux_flags;
   DevBuf<uint8_t> d_gather;          // grow-only scratch of bbq_score_ords* (bbq_gather.cpp): one launch's offsets, queries, ords and outputs
+  DevBuf<uint8_t> d_range;           // grow-only scratch of a range search's sub-batch (bbq_range.cpp): queries, thresholds, per-chunk counts and lists
   int last_big_slot = -1;             // slot whose ev_big marks the end of the most recently enqueued big sweep
   // latency path (bbq_latency_kernels.hip): the answer of a single-query call lands in mapped, coherent host memory and the host
   // polls a sequence word behind it: [0] sequence, [8 ..) header + entries

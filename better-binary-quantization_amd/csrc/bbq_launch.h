@@ -1,5 +1,6 @@
 // bbq_launch.h - host-callable launch wrappers of every kernel file: the sweeps, finalize and pack (bbq_kernels.hip, bbq_filter_kernels.hip,
-// bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip), the rerank (bbq_rerank_kernels.hip) and the scoring of chosen rows (bbq_gather_kernels.hip)
+// bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip), the rerank (bbq_rerank_kernels.hip), the scoring of chosen rows (bbq_gather_kernels.hip)
+// and the range search (bbq_range_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbq_device.h"
@@ -79,6 +80,16 @@ hipError_t launch_rerank(const RerankArgs &a, int n_queries, int64_t max_count, 
 // scoring chosen rows (bbq_gather_kernels.hip): one workgroup per kGatherThreads entries of a query's list; max_count = longest list,
 // n_queries <= 65535; planes as launch_scan takes them
 hipError_t launch_score_ords(const GatherArgs &a, int planes, int n_queries, int64_t max_count, hipStream_t s);
+// range search (bbq_range_kernels.hip), in the order a sub-batch launches them.  theta[q] = {keys[q], its z image for query q}
+hipError_t launch_range_theta(Threshold *theta, const uint32_t *keys, const QueryParams *qparams, int n_queries, hipStream_t s);
+// counts[q][chunk] = rows of the chunk that a.accept takes and whose score key beats theta[q], for the n_queries queries from a.q_first on
+// (n_queries <= 65535); planes as launch_scan takes them
+hipError_t launch_range_count(const RangeArgs &a, int planes, int n_queries, hipStream_t s);
+// per query: counts -> their exclusive prefix IN PLACE, totals[q] = their sum, nonempty[q][0 .. n_nonempty[q]) = the chunks with a count, ascending
+hipError_t launch_range_offsets(uint32_t *counts, uint32_t *nonempty, uint32_t *totals, uint32_t *n_nonempty, int n_chunks, int n_queries, hipStream_t s);
+// the passing rows of the n_queries queries from a.q_first on, as entries at a.out[a.base[q] + ...], ascending by row; max_nonempty = the
+// longest non-empty-chunk list among them
+hipError_t launch_range_fill(const RangeArgs &a, int planes, int n_queries, int64_t max_nonempty, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 // staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place

@@ -691,6 +691,34 @@ class BinaryQuantizationFormat {
     return res;
   }
 
+  /**
+   * extension (not in the reference): every row whose stored f32 score is >= threshold - what the reference's loop (:349-411) would collect
+   * if it kept every visited ord at or above the threshold and skipped the heap.  options.rowFilter: a RowFilter (createRowFilter) - only the
+   * rows it accepts; options.order: 'ord' (default, ascending ord) or 'score' (descending score, ties in ascending ord).  A row whose
+   * score is NaN is in no answer; a NaN threshold throws.  Same validation and messages as searchNearestNeighbors.  A multi-device
+   * index (BBQ_DEVICES) throws the library's unsupported message.
+   */
+  searchRange(queryVector, targetVectors, threshold, options) {
+    if (!queryVector) throw new Error('查询向量不能为空');
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    const filter = options && options.rowFilter != null ? options.rowFilter : null, order = (options && options.order) || 'ord';
+    if (order !== 'ord' && order !== 'score') throw new Error('order must be "ord" or "score"');
+    if (filter !== null && !(filter instanceof RowFilter)) throw new Error('searchRange needs createRowFilter(targetVectors, accept)');
+    if (typeof threshold !== 'number' || Number.isNaN(threshold)) throw new Error('阈值不能为NaN');
+    if (queryVector.length !== targetVectors.dimension()) throw new Error('查询向量维度与目标向量维度不匹配');
+    const flat = this._flatQueries([queryVector], targetVectors, 1);
+    const q = this.quantizer, sim = simOrdinal(q.similarityFunction), qb = this.config.queryBits;
+    const tNative = process.hrtime.bigint();
+    const qz = native.quantizeQueries(flat, 1, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, 1);
+    const r = native.searchRange(targetVectors._deviceIndex(), filter === null ? null : filter._handle(), qz.quantized, qz.corrections, qb, sim, threshold);
+    hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
+    const n = r.indices.length, res = new Array(n);
+    for (let j = 0; j < n; j++) res[j] = { index: r.indices[j], score: r.scores[j] };
+    // indices ascend, so they break ties: the order does not rest on the engine's sort being stable
+    if (order === 'score') res.sort(function (x, y) { return y.score > x.score ? 1 : y.score < x.score ? -1 : x.index - y.index; });
+    return res;
+  }
+
   /** extension (not in the reference): searchNearestNeighborsFiltered for many queries per call; one filter serves all of them */
   searchNearestNeighborsBatchFiltered(queryVectors, targetVectors, filter, k) {
     const flat = this._flatQueries(queryVectors, targetVectors, k);

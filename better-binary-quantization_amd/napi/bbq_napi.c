@@ -699,6 +699,43 @@ static napi_value SearchOrds(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* searchRange(handle, filter handle | null, qquant, qcorr, queryBits, sim, threshold) -> {indices Int32Array, scores Float32Array}: every row (of
+ * the filter, if one is given) whose f32 score is >= threshold, ascending by ord (bbq_count_range_batch, then bbq_search_range_batch with
+ * exactly that room).  A NaN threshold throws. */
+static napi_value SearchRange(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (!get_args(env, info, 7, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  const bbq_filter *flt = NULL;
+  napi_valuetype vt;
+  NAPI_CALL(env, napi_typeof(env, a[1], &vt));
+  if (vt != napi_null && vt != napi_undefined) {
+    flt = unbox_filter(env, a[1], "bbq_search_range_batch");
+    if (!flt) return NULL;
+  }
+  void *qq, *qc; size_t ql, cl;
+  int64_t qb, sim; double t;
+  if (!get_typed(env, a[2], napi_uint8_array, &qq, &ql) || !get_typed(env, a[3], napi_float64_array, &qc, &cl) ||
+      !get_i64(env, a[4], &qb) || !get_i64(env, a[5], &sim) || !get_f64(env, a[6], &t)) return NULL;
+  if (ql != (size_t)bbq_index_dimension(ix) || cl != 4) { napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return NULL; }
+  const float th = (float)t;
+  int64_t total = 0, offsets[2] = {0, 0};
+  int rc = bbq_count_range_batch(ix, flt, 1, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, &th, &total);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  void *oi, *os;
+  napi_value ti = new_typed(env, napi_int32_array, (size_t)total, 4, &oi);
+  napi_value ts = new_typed(env, napi_float32_array, (size_t)total, 4, &os);
+  if (!ti || !ts) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  rc = bbq_search_range_batch(ix, flt, 1, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, &th, total, offsets,
+                              total ? (int32_t *)oi : NULL, total ? (float *)os : NULL);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "indices", ti); set_prop(env, o, "scores", ts);
+  return o;
+}
+
 /* setOption(handle, name, value) */
 static napi_value SetOption(napi_env env, napi_callback_info info) {
   napi_value a[3];
@@ -1028,6 +1065,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"scoreRows", NULL, ScoreRows, NULL, NULL, NULL, napi_default, NULL},
       {"scoreOrds", NULL, ScoreOrds, NULL, NULL, NULL, napi_default, NULL},
       {"searchOrds", NULL, SearchOrds, NULL, NULL, NULL, napi_default, NULL},
+      {"searchRange", NULL, SearchRange, NULL, NULL, NULL, napi_default, NULL},
       {"setOption", NULL, SetOption, NULL, NULL, NULL, napi_default, NULL},
       {"stats", NULL, Stats, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsCreate", NULL, VectorsCreate, NULL, NULL, NULL, napi_default, NULL},

@@ -231,6 +231,35 @@ class BinaryQuantizationFormat:
             raise Exception("目标向量序号不能为空")
         return self._search(queryVector, targetVectors, k, None, ords)
 
+    def searchRange(self, queryVector, targetVectors, threshold, rowFilter=None, order="ord"):
+        """extension: every row (of `rowFilter`, createRowFilter, if given) whose stored f32 score is >= threshold - what the
+        reference's loop would collect if it kept every visited ord at or above the threshold and skipped the heap - as
+        [{index, score}] in ascending ord; order="score": descending score, ties in ascending ord.  A NaN score is in no answer;
+        a NaN threshold raises."""
+        if queryVector is None:
+            raise Exception("查询向量不能为空")
+        if targetVectors is None:
+            raise Exception("目标向量集合不能为空")
+        if order not in ("ord", "score"):
+            raise Exception('order must be "ord" or "score"')
+        if threshold is None or threshold != threshold:
+            raise Exception("阈值不能为NaN")
+        if len(queryVector) != targetVectors.dimension():
+            raise Exception("查询向量维度与目标向量维度不匹配")
+        sim = capi.SIMS[self._sim]
+        if targetVectors._index_bits != 1 and targetVectors.dimension() > 1 and self._config["queryBits"] not in (1, 4):
+            raise Exception("不支持的查询位数: %d，只支持1位和4位" % self._config["queryBits"])  # as _search refuses it
+        try:
+            qq, qc = capi.quantize_query(queryVector, targetVectors.getCentroid(), sim, self._config["queryBits"], self._lambda,
+                                         self._iters, search_path=True)
+            idx, sc, _ = targetVectors._device().search_range_batch(qq[None, :], qc[None, :], self._config["queryBits"], sim, [threshold], rowFilter)
+        except capi.BBQError as e:
+            raise Exception(str(e))
+        if order == "score":
+            by = np.argsort(-sc, kind="stable")  # no NaN among them
+            idx, sc = idx[by], sc[by]
+        return [{"index": int(i), "score": float(s)} for i, s in zip(idx, sc)]
+
     def computeBatchQuantizedScores(self, quantizedQuery, queryCorrections, targetVectors, targetOrds, queryBits):
         """BinaryQuantizedScorer.computeBatchQuantizedScores (src/binaryQuantizedScorer.ts:315-420) without its optional
         originalQueryVector: [{score, bitDotProduct}] for the rows targetOrds names, in that order, scored on the device

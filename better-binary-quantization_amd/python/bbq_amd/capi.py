@@ -31,6 +31,7 @@ SYMBOLS = [
     "bbq_index_compact", "bbq_index_remove_rows", "bbq_vectors_compact", "bbq_filter_kept_rows",
     "bbq_index_update_rows", "bbq_index_update", "bbq_vectors_update", "bbq_update_winners",
     "bbq_score_ords", "bbq_score_ords_batch", "bbq_search_ords_batch",
+    "bbq_range_key", "bbq_count_range_batch", "bbq_search_range_batch",
 ]
 
 
@@ -106,6 +107,9 @@ def lib():
     L.bbq_score_ords.argtypes = [vp, vp, vp, i32, i32, vp, i64, vp, vp, vp]
     L.bbq_score_ords_batch.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.bbq_search_ords_batch.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
+    L.bbq_range_key.argtypes = [C.c_float, C.POINTER(C.c_uint32)]
+    L.bbq_count_range_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
+    L.bbq_search_range_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, i64, vp, vp, vp]
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_create_rows.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_destroy.argtypes = [vp]
@@ -553,6 +557,37 @@ class Index:
         _chk(lib().bbq_search_ords_batch(self._h, nq, _ptr(qq), _ptr(qc), query_bits, sim, k, _ptr(off), _ptr(o), _ptr(idx), _ptr(sc), _ptr(cnt)))
         return [(idx[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)]
 
+    def _range_args(self, qquant, qcorr, thresholds):
+        qq = np.ascontiguousarray(qquant, np.uint8)
+        qc = np.ascontiguousarray(qcorr, np.float64)
+        th = np.ascontiguousarray(thresholds, np.float32).ravel()
+        if qq.ndim != 2 or (qq.shape[0] and qq.shape[1] != self.dim):
+            raise BBQError(ERR_DIM_MISMATCH, "查询向量维度与目标向量维度不匹配")
+        if th.shape[0] != qq.shape[0]:
+            raise BBQError(ERR_INVALID_ARG, "one threshold per query")
+        return qq, qc, th
+
+    def count_range_batch(self, qquant, qcorr, query_bits, sim, thresholds, row_filter=None):
+        """bbq_count_range_batch: per query, the number of rows (of `row_filter`, a Filter of this index, if given) whose f32 score
+        is >= its threshold"""
+        qq, qc, th = self._range_args(qquant, qcorr, thresholds)
+        cnt = np.zeros(qq.shape[0], np.int64)
+        _chk(lib().bbq_count_range_batch(self._h, row_filter._h if row_filter is not None else None, qq.shape[0], _ptr(qq), _ptr(qc), query_bits, sim,
+                                        _ptr(th), _ptr(cnt)))
+        return cnt
+
+    def search_range_batch(self, qquant, qcorr, query_bits, sim, thresholds, row_filter=None):
+        """bbq_search_range_batch: (idx, score, offsets) - query q's answer, ascending by ord, is idx / score [offsets[q], offsets[q+1]).
+        Counts first, allocates exactly, then fills."""
+        qq, qc, th = self._range_args(qquant, qcorr, thresholds)
+        nq = qq.shape[0]
+        total = int(self.count_range_batch(qq, qc, query_bits, sim, th, row_filter).sum())
+        off = np.zeros(nq + 1, np.int64)
+        idx, sc = np.zeros(total, np.int32), np.zeros(total, np.float32)
+        _chk(lib().bbq_search_range_batch(self._h, row_filter._h if row_filter is not None else None, nq, _ptr(qq), _ptr(qc), query_bits, sim,
+                                         _ptr(th), total, _ptr(off), _ptr(idx), _ptr(sc)))
+        return idx, sc, off
+
     def shard_scan_begin(self, qquant, qcorr, query_bits, sim, k, dev_packed_ptr, packed_cap, dev_offsets_ptr, dev_flags_ptr,
                          dev_answers_ptr=None, answers_stride=0):
         """enqueue the sweep of one batch (and its packing) and return; shard_scan_wait() later.  Two batches may be in flight."""
@@ -597,6 +632,13 @@ def merge_answers(blocks, n_queries, n_total, k, n_threads=1):
 
 def key_of_score(score):
     return int(lib().bbq_key_of_score(float(score)))
+
+
+def range_key(threshold):
+    """the key K with key_of_score(s) > K <=> s >= threshold for every non-NaN s (bbq_range_key; host only).  NaN raises."""
+    k = C.c_uint32(0)
+    _chk(lib().bbq_range_key(float(threshold), C.byref(k)))
+    return int(k.value)
 
 
 def file_shards(path_prefix):

@@ -36,7 +36,8 @@ extern "C" {
                               (still 3: filtered search - bbq_filter_*, bbq_search_filtered_batch - only adds symbols, as do the appends
                               and the compaction - bbq_index_compact, bbq_index_remove_rows, bbq_vectors_compact, bbq_filter_kept_rows - and the
                               in-place updates - bbq_index_update_rows, bbq_index_update, bbq_vectors_update, bbq_update_winners - and the scoring of chosen rows -
-                              bbq_score_ords, bbq_score_ords_batch, bbq_search_ords_batch) */
+                              bbq_score_ords, bbq_score_ords_batch, bbq_search_ords_batch - and the range search - bbq_range_key,
+                              bbq_count_range_batch, bbq_search_range_batch) */
 
 /* status codes */
 enum {
@@ -381,6 +382,37 @@ int bbq_score_ords(bbq_index *idx, const uint8_t *qquant, const double *qcorr, i
 int bbq_search_ords_batch(bbq_index *idx, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
                           int32_t query_bits, int32_t sim, int64_t k, const int64_t *offsets, const int32_t *ords,
                           int32_t *out_idx, float *out_score, int64_t *out_n);
+
+/* ------------------------------------------------------------------------------------------
+ * Range search (DESIGN.md "Range search"): every row whose score reaches a threshold - the query whose k the caller does not know.
+ * For query q with threshold t_q (an f32) the answer is every row r of the index that the filter, if one is given, accepts and whose
+ * f32 score - what bbq_score_rows delivers as out_score32 - satisfies score >= t_q as IEEE floats compare, delivered in ascending ord,
+ * each with that score: what the reference's loop (src/binaryQuantizationFormat.ts:349-411) would collect if it kept every visited ord
+ * whose stored f32 score is >= t and skipped the heap.  A row whose score is NaN is in no answer, whatever the threshold; t = -inf
+ * returns every accepted row with a non-NaN score, t = +inf the rows whose score is +inf, t = +0.0 and t = -0.0 the same answer.  A NaN
+ * threshold is BBQ_ERR_INVALID_ARG, checked for all queries before the first launch.  query_bits, sim and the multi-bit corners as
+ * bbq_score_rows.
+ * n_queries == 0, an index of zero rows and an empty filter: BBQ_OK with zeros, nothing is launched.  Accepted handles are those the
+ * filtered search accepts - a single-device root index without a pilot replica; a multi-device handle, a non-root shard and an index
+ * with a pilot replica: BBQ_ERR_UNSUPPORTED, with or without a filter.  The call takes the device context's lock and runs on the
+ * auxiliary stream, as bbq_score_rows and bbq_score_ords do: it sees an append, an update or a compaction whole or not at all.  It
+ * writes no bbq_stats field.  The sweep is count-then-fill and deterministic; a long call is worked through in sub-batches of at most
+ * 1024 queries and 64 MiB of per-chunk scratch and in fill launches of at most 2^20 entries (always at least one query): the device
+ * scratch stays below 64 MiB + max(8 MiB, 8 B x rows) + the staged queries.  A failed allocation: BBQ_ERR_OOM, nothing written. */
+/* host only: *out_key = K with  bbq_key_of_score(s) > K  <=>  s >= threshold  for every non-NaN s
+ * (bbq_key_of_score(t) - 1 with t = +-0 taken as -0.0f).  NaN: BBQ_ERR_INVALID_ARG. */
+int bbq_range_key(float threshold, uint32_t *out_key);
+/* f: NULL = all rows; otherwise a filter of this index (size / device as bbq_search_filtered_batch checks them).
+ * thresholds [n_queries].  out_counts [n_queries] = number of rows in each answer. */
+int bbq_count_range_batch(bbq_index *idx, const bbq_filter *f, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
+                          int32_t query_bits, int32_t sim, const float *thresholds, int64_t *out_counts);
+/* out_offsets [n_queries + 1] ascending from 0: query q's answer is out_idx / out_score [out_offsets[q], out_offsets[q+1]),
+ * ascending by ord.  cap = entries out_idx / out_score hold.  out_offsets is written whenever the arguments are good; when
+ * out_offsets[n_queries] > cap: BBQ_ERR_INVALID_ARG and nothing is written to out_idx / out_score (the precedent is
+ * bbq_filter_kept_rows) - the caller allocates and calls again.  out_idx / out_score may be NULL iff cap == 0. */
+int bbq_search_range_batch(bbq_index *idx, const bbq_filter *f, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
+                           int32_t query_bits, int32_t sim, const float *thresholds, int64_t cap,
+                           int64_t *out_offsets, int32_t *out_idx, float *out_score);
 
 /* ------------------------------------------------------------------------------------------
  * Sharded search (one process per GPU).  bbq_shard_scan sweeps THIS shard for n_queries queries and
