@@ -121,6 +121,13 @@ int l2_share_shift(const bbq_index *ix) {
 // comes from HBM: there 2 B/row more cost time and the count is free, and the launch stays the one it was.
 bool row_sums_for_launch(const bbq_index *ix) { return ix->opt_row_sums < 0 ? ix->opt_resident_mb != 0 : ix->opt_row_sums != 0; }
 
+// whether a call stages the digit masks of its queries next to their bit-planes (option digit_planes; 1 and -1 are the same): a 4-plane
+// query against 1-bit rows whose sparse sweeps read the row sums.  The launch takes the digit twin where both are there and the twin
+// exists (launch_scan_t); with resident_mb 0 the automatic row_sums is off and the launch stays the one it was.
+bool digit_planes_for_call(const bbq_index *ix, int planes) {
+  return ix->opt_digit_planes != 0 && ix->geom.store_bits == 1 && planes == 4 && row_sums_for_launch(ix) && row_sums_fit(ix->geom);
+}
+
 // ------------------------------------------------------------------------------------------------ plan
 
 static int cap_for(int64_t k, int64_t rows_before) {
@@ -392,6 +399,16 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
   for (int i = 0; i < nq && use_mfma; ++i) use_mfma = mfma_query_ok(hq[i]);
   const MfmaStage ms = use_mfma ? stage_queries_mfma(c, s.h_qbuf, hq, q_first, nq, bytes) : MfmaStage{};
   if (use_mfma) bytes = ms.bytes;
+  // the digit masks of a 4-plane query behind everything else: the per-query sparse sweeps take them where they have a digit twin
+  int32_t qdigits_at = 0;  // in 16-byte units behind the planes (ScanArgs::qdigits_at)
+  // (only where every sparse segment is a per-query sweep: a call with sweep_share 4 / 8 sweeps shared, and a segment of it that falls
+  // back to the per-query sweep runs planes)
+  if (!use_mfma && c.share == 1 && digit_planes_for_call(ix, c.planes)) {
+    const size_t db = (size_t)digit_bytes_per_query_w(ix->geom.w16);
+    for (int i = 0; i < nq; ++i) fill_query_digits(ix, s.h_qbuf + bytes + (size_t)i * db, hq + i, c.qquant + (size_t)(q_first + i) * ix->geom.dim);
+    qdigits_at = (int32_t)(bytes / 16);
+    bytes += (size_t)nq * db;
+  }
   hipStream_t st = s.stream;
   HIPCHK(hipMemcpyAsync(s.d_block, s.h_block, (size_t)s.ctrl_bytes + bytes, hipMemcpyHostToDevice, st));  // control words := 0, queries
   s.ctrl_clean = false;
@@ -419,6 +436,7 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
     ScanArgs a = segment_scan_args(p, s, g, sto, lv.view, nq, qb);
     a.l2_shift = l2_share_shift(ix);  // (read by the per-query sweep alone, and only by its sparse launches)
     a.idx.row_sums = row_sums_for_launch(ix) ? sto.view.row_sums : nullptr;  // (likewise; null where the storage has none)
+    a.qdigits_at = qdigits_at;                                               // (likewise; 0: the plane form)
     const bool append_here = !g.dense && ((append && (ix->opt_append_last || !last)) || use_mfma);
     if (append_here) {
       a.append_lists = d_lists;

@@ -52,6 +52,36 @@ __host__ __device__ inline int row_bytes_of(int dim, int store_bits) { return (d
 __host__ __device__ constexpr int query_units_per_chunk(int qb, int store_bits) {
   return store_bits == 1 ? qb : store_bits == 2 ? (qb > 4 ? 4 : 2) : store_bits == 4 ? (qb > 4 ? 2 : 1) : 1;
 }
+// ---- a 4-plane query against 1-bit rows as three planes of ternary digits (the digit form of the per-query sparse sweep, tile_digit_dot).
+// q - 4 = t0 + 3 t1 + 9 t2 with t0, t1 in {-1, 0, 1} and t2 in {0, 1}: balanced ternary of [-4, 11].  A digit plane is a pair of disjoint
+// masks - P where the digit is +1, N where it is -1 - and costs what a bit-plane costs, one bit operation and one popcount per row dword:
+//   pop(x & P) - pop(x & N) = pop((x & P) | (~x & N)) - pop(N),
+// a bit-field insert with the row word as the selector; pop(N) does not depend on the row.  The top digit is never negative: a plain AND.
+//   qcDist = sum_d q[d] x[d] = 4 ones + a0 + 3 a1 + 9 a2 - K,   a_i = sum over the row's dwords of pop(bfi(x, P_i, N_i)),   K = pop(N_0) + 3 pop(N_1)
+// with ones = the row's popcount (the row_sums side array): three planes instead of four, an exact integer below 2^32.
+// The staged form is kDigitMasks 16-byte masks per 16-byte chunk of a row, [j][5] = {P0, N0, P1, N1, P2}, packed like the rows; a padding
+// position is staged as the value 0 (bits in N0 and N1), so that a row bit there weighs 4 - 1 - 3 = 0 (fill_query_digits).  K travels in
+// QueryParams::digit_k.
+constexpr int kDigitOffset = 4;
+constexpr int kDigitMasks = 5;
+struct DigitTriple { int8_t t0, t1, t2; };
+constexpr DigitTriple kDigitTable[16] = {{-1, -1, 0}, {0, -1, 0}, {1, -1, 0}, {-1, 0, 0}, {0, 0, 0}, {1, 0, 0}, {-1, 1, 0}, {0, 1, 0},
+                                         {1, 1, 0},   {-1, -1, 1}, {0, -1, 1}, {1, -1, 1}, {-1, 0, 1}, {0, 0, 1}, {1, 0, 1}, {-1, 1, 1}};
+constexpr bool digit_table_is_exact() {
+  for (int q = 0; q < 16; ++q) {
+    const DigitTriple t = kDigitTable[q];
+    if (t.t0 < -1 || t.t0 > 1 || t.t1 < -1 || t.t1 > 1 || t.t2 < 0 || t.t2 > 1) return false;
+    if (q != kDigitOffset + t.t0 + 3 * t.t1 + 9 * t.t2) return false;
+  }
+  return true;
+}
+static_assert(digit_table_is_exact(), "q == 4 + t0 + 3 t1 + 9 t2 for every 4-bit value, and the top digit is never negative");
+// the masks a value sets, bit m = mask m of {P0, N0, P1, N1, P2}
+constexpr uint32_t digit_mask_bits(int q) {
+  const DigitTriple t = kDigitTable[q];
+  return (t.t0 > 0 ? 1u : 0u) | (t.t0 < 0 ? 2u : 0u) | (t.t1 > 0 ? 4u : 0u) | (t.t1 < 0 ? 8u : 0u) | (t.t2 > 0 ? 16u : 0u);
+}
+
 // ---- the tile record: the ONE definition of its bytes.  Every kernel that reads or writes a record, bbq_index_export on the host and
 // the file (<prefix>.veb holds the records as they are) take their offsets from here.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // one 16-byte code chunk
@@ -243,7 +273,7 @@ struct QueryParams {
   float k2mf;         // 2^-20 * M, M >= |c1| + 2 (|ay| * x1max + |ly| * qcmax): the rounding allowance per unit of |al| + |au|
   float tinyf;        // the absolute allowance (denormal corrections, underflow)
   float csf, caf;     // z = cs * s + ca * add: (2, -1) EUCLIDEAN, (1, 1) otherwise
-  float padf_;
+  uint32_t digit_k;   // K = pop(N_0) + 3 pop(N_1) of the query's digit masks (fill_query_digits); 0 where none are staged
 };
 static_assert(sizeof(QueryParams) == 96 && sizeof(QueryParams) % 16 == 0, "QueryParams: staged in arrays behind 16-byte query data, and part of kernel arguments");
 
@@ -280,6 +310,10 @@ struct ScanArgs {
   uint64_t *ovf;               // [Q][ovf_cap]
   uint32_t *ovf_counts;        // [Q] entries handed out so far
   int32_t ovf_cap;
+  // the digit form of a 4-plane query against 1-bit rows (kDigitMasks above): [Q][w16][kDigitMasks] masks staged IN ADDITION to the
+  // bit-planes and in the same buffer, qdigits_at 16-byte units behind qplanes; 0 - the caller staged none, and the launch runs the plane
+  // form.  Read by the sparse sweep of bbq_scan_kernel's DG twin alone
+  int32_t qdigits_at;
   // append mode (calls with few queries; null: chunk slots as above): a workgroup reserves room for its candidates right in the
   // query's list with ONE atomic and writes them there, unordered inside the segment - the finalize launch then has nothing to
   // compact (walking 19 K chunk counters cost it 20-30 us of a 250 us call).  The answer is selected on the device and does not
@@ -298,6 +332,8 @@ struct ScanArgs {
   int32_t l2_shift;
   int32_t n_queries;
 };
+// (qdigits_at fills what was padding: eight more bytes of kernel arguments moved the register allocation of three existing instantiations)
+static_assert(sizeof(ScanArgs) == 256 && offsetof(ScanArgs, qdigits_at) == 180 && offsetof(ScanArgs, append_lists) == 184, "ScanArgs layout");
 
 struct FinalizeArgs {
   // input: either slots of one sparse launch, or the dense f32 scores of the first segment

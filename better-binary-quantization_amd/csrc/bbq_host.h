@@ -217,6 +217,8 @@ struct bbq_index {
                           // XCD's L2 (sweep_coord, bbq_device.h): 1 off, 2..32, -1: l2_share_shift()'s choice (bbq_core.cpp)
   int opt_row_sums = -1;  // the per-query sparse sweep reads a row's component sum from the row_sums side array instead of counting it:
                           // 0 never, 1 wherever the array exists, -1: row_sums_for_launch()'s choice (bbq_core.cpp)
+  int opt_digit_planes = -1;  // a 4-plane query against 1-bit rows is swept in three ternary digit planes wherever the sweep reads the row sums
+                              // and has a digit twin: 0 never, 1 and -1 wherever it can (digit_planes_for_call, bbq_core.cpp)
   int opt_fast_bound = 1;  // 1: the compact layout's score bound in f32 against the threshold's z image wherever the query's f32 images allow it
                            // (fast_bound_images, bbq_query.cpp); 0: always the f64 bound.  The answers are the same either way
   int opt_latency_presample = 1;  // ... and on large indexes get their threshold from per-wave top keys of a prefix (two small launches) instead of two scan / finalize pairs

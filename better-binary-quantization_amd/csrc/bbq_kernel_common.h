@@ -145,6 +145,44 @@ __device__ __forceinline__ uint32_t tile_popcounts_any(const uint8_t *__restrict
   return plane_dot<QB>(acc);
 }
 
+// The digit form of a 4-plane query (bbq_device.h, kDigitMasks): qcDist of a 1-bit row from THREE planes of ternary digits instead of four
+// bit-planes.  s_digits holds {P0, N0, P1, N1, P2} per chunk; (x & P) | (~x & N) is one v_bfi_b32 with the row word as the selector, the top
+// digit a plain AND; `ones` = the row's popcount from the row_sums side array, k = QueryParams::digit_k.  u32 arithmetic on a value below 2^32.
+__device__ __forceinline__ u32x4 digit_select(u32x4 x, u32x4 p, u32x4 n) { return (x & p) | (~x & n); }
+__device__ __forceinline__ uint32_t digit_dot(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t ones, uint32_t k) {
+  return ((ones << 2) - k) + a0 + 3u * a1 + 9u * a2;
+}
+// same shape as tile_popcounts: the chunks in registers, the masks from LDS through wave-uniform addresses, the sums inside v_bcnt
+template <int W>
+__device__ __forceinline__ uint32_t tile_digit_dot(const u32x4 (&c)[W], const u32x4 *__restrict__ s_digits, uint32_t ones, uint32_t k) {
+  uint32_t a0 = 0, a1 = 0, a2 = 0;
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    const u32x4 *__restrict__ m = s_digits + j * kDigitMasks;
+    a0 = popc4_acc(digit_select(c[j], m[0], m[1]), a0);
+    a1 = popc4_acc(digit_select(c[j], m[2], m[3]), a1);
+    a2 = popc4_acc(c[j] & m[4], a2);
+    // 12 chunks: left alone, the compiler reads the masks of many chunks ahead of their use - 82 vector registers and 5 waves where the plane
+    // form has 69 and 7.  A compiler barrier behind each chunk keeps a chunk's five reads next to its use: 68 registers, 7 waves
+    if constexpr (W >= 12) BBQ_BRANCH_FENCE();
+  }
+  return digit_dot(a0, a1, a2, ones, k);
+}
+// any width: streamed chunk by chunk
+__device__ __forceinline__ uint32_t tile_digit_dot_any(const uint8_t *__restrict__ tp, int lane, int w16, const u32x4 *__restrict__ s_digits,
+                                                       uint32_t ones, uint32_t k) {
+  const u32x4 *__restrict__ cp = reinterpret_cast<const u32x4 *>(tp) + lane;
+  uint32_t a0 = 0, a1 = 0, a2 = 0;
+  for (int j = 0; j < w16; ++j) {
+    const u32x4 c = BBQ_STREAM_LOAD(cp + j * kTileRows);
+    const u32x4 *__restrict__ m = s_digits + j * kDigitMasks;
+    a0 += popc4(digit_select(c, m[0], m[1]));
+    a1 += popc4(digit_select(c, m[2], m[3]));
+    a2 += popc4(c & m[4]);
+  }
+  return digit_dot(a0, a1, a2, ones, k);
+}
+
 // Upper bound of the score when only the COMPACT corrections are known (kLayoutCompact).
 // The raw score s is linear in (lower, upper): with x1 and qcDist fixed,
 //     s(lower, upper) = lower * A + upper * B,   A = ay*(dim - x1) + ly*(y1 - qc),   B = ay*x1 + ly*qc,

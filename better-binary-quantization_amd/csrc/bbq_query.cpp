@@ -7,8 +7,11 @@
 
 namespace bbq {
 
-// per query: bit-planes (up to 8) + int8 values in MFMA fragment order + score uniforms + group maxima
-int64_t qbuf_bytes_per_query_w(int w16) { return (int64_t)w16 * 8 * 16 + (int64_t)w16 * 128 + (int64_t)sizeof(QueryParams) + 16; }
+// per query: bit-planes (up to 8) + digit masks (4-plane queries) + int8 values in MFMA fragment order + score uniforms + group maxima
+int64_t qbuf_bytes_per_query_w(int w16) {
+  return (int64_t)w16 * 8 * 16 + digit_bytes_per_query_w(w16) + (int64_t)w16 * 128 + (int64_t)sizeof(QueryParams) + 16;
+}
+int64_t digit_bytes_per_query_w(int w16) { return (int64_t)w16 * kDigitMasks * 16; }
 
 int max_value(const uint8_t *q, int64_t count) {
   uint8_t m = 0;
@@ -56,7 +59,7 @@ void fast_bound_images(QueryParams *pp, double x1max, double qcmax, bool enable)
   pp->c1f = (float)c1;
   pp->csf = pp->sim == 0 ? 2.0f : 1.0f;
   pp->caf = pp->sim == 0 ? -1.0f : 1.0f;
-  pp->padf_ = 0.0f;
+  pp->digit_k = 0;
   const bool ok = enable && f32_image_ok(pp->ay, pp->ayf) && f32_image_ok(pp->ly, pp->lyf) && f32_image_ok(c1, pp->c1f) && M >= 0x1p-80 && M <= 0x1p100;
   pp->k2mf = ok ? f32_up(M * 0x1p-20) : 0.0f;
   pp->tinyf = ok ? f32_up(std::max(0x1p-100, M * 0x1p-120)) : 0.0f;
@@ -129,6 +132,35 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
   // the largest component sum and the largest qcDist a stored row can have, whatever y1 the caller passed
   const double vmax = (double)((1 << ix->geom.store_bits) - 1), qmax = ix->geom.store_bits == 1 ? (double)((1 << planes) - 1) : (planes > 4 ? 255.0 : 15.0);
   fast_bound_images(pp, pp->dimd * vmax, pp->dimd * vmax * qmax, ix->opt_fast_bound != 0 && !ix->geom.has_x1);
+}
+
+// The digit form of a 4-plane query against a 1-bit index (bbq_device.h, kDigitTable): the masks [j][kDigitMasks] = {P0, N0, P1, N1, P2},
+// 16 bytes each and packed like the rows and the bit-planes (dim d -> byte d >> 3, bit 7 - (d & 7)), and K = pop(N0) + 3 pop(N1) into
+// pp->digit_k.  Staged in addition to the bit-planes fill_query writes: every kernel but the digit twin of the sparse sweep reads those.
+// Every value of q is at most 15 (planes == 4).
+// A PADDING position (dim .. w16 * 128 - 1) is staged as the value 0, digits (-1, -1, 0): bits in N0 and N1.  The form's 4 * ones counts
+// every bit the row stores, also one a caller left behind the last dimension of a partly used byte (the library stores a row's bytes as
+// they come, and such a bit is part of the row's sum wherever the compact layout holds it); as a 0 of the query it contributes
+// 4 - 1 - 3 = 0, as it does in the plane form, whose planes are 0 there.  A clear row bit there adds 1 + 3 to a0 + 3 a1 and to K alike.
+void fill_query_digits(const bbq_index *ix, uint8_t *digits_dst, QueryParams *pp, const uint8_t *q) {
+  static const struct Lut {
+    uint8_t of[16];
+    constexpr Lut() : of{} { for (int v = 0; v < 16; ++v) of[v] = (uint8_t)digit_mask_bits(v); }
+  } lut;
+  const int dim = ix->geom.dim;
+  uint32_t n0 = 0, n1 = 0;
+  for (int byte = 0; byte < ix->geom.w16 * 16; ++byte) {
+    // the mask bits of the byte's eight dimensions side by side, then bit m of all eight gathered MSB-first by one multiply (fill_query)
+    uint64_t x = 0;
+    const int nd = std::max(0, std::min(8, dim - byte * 8));
+    for (int i = 0; i < nd; ++i) x |= (uint64_t)lut.of[q[(size_t)byte * 8 + i] & 15] << (8 * i);
+    for (int i = nd; i < 8; ++i) x |= (uint64_t)lut.of[0] << (8 * i);  // padding: the value 0
+    uint8_t *dst = digits_dst + (size_t)(byte >> 4) * kDigitMasks * 16 + (byte & 15);
+    for (int m = 0; m < kDigitMasks; ++m) dst[m * 16] = (uint8_t)((((x >> m) & 0x0101010101010101ull) * 0x8040201008040201ull) >> 56);
+    n0 += (uint32_t)__builtin_popcount(dst[1 * 16]);
+    n1 += (uint32_t)__builtin_popcount(dst[3 * 16]);
+  }
+  pp->digit_k = n0 + 3u * n1;
 }
 
 // MFMA shared sweep, int8 form (query values up to 127): the int8 query values in the order the code bits fall out of the packed

@@ -85,18 +85,22 @@ __device__ __forceinline__ void tile_dot_multibit_any(const uint8_t *__restrict_
 // RS (MODE 2 only, chosen by the launch iff its view carries IndexView::row_sums): the row's popcount / code sum is not counted here - it is
 // the same for every query, segment and call - but loaded from the side array with the tile's other loads; the popcount loop and the
 // multi-bit dot run without their sum chain.  The value is what that chain returns, so the bound and the score are the same bits.
-template <int QB, int W, int MODE, int SB = 1, bool RS = false, class... Accept>
+// DG (RS, 1-bit rows and a 4-plane query only, chosen by the launch iff ScanArgs::qdigits_at is set as well): the digit form - the workgroup
+// stages the query's kDigitMasks ternary digit masks per chunk instead of its four bit-planes, and qcDist comes out of three popcount
+// chains and the row's sum (tile_digit_dot).  The same integer, so everything behind it is the same bits.
+template <int QB, int W, int MODE, int SB = 1, bool RS = false, bool DG = false, class... Accept>
 __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, const Accept... accept_arg) {
   constexpr bool FILT = sizeof...(Accept) > 0;
   static_assert(sizeof...(Accept) <= 1 && !(FILT && (MODE & 1)), "at most the accept bitset, and a filtered sweep is sparse");
   static_assert(!RS || (MODE & 3) == 2, "row sums are read by the sparse sweep of the compact layout alone");
+  static_assert(!DG || (RS && SB == 1 && QB == 4), "the digit form: a 4-plane query against 1-bit rows whose popcounts are at hand");
   const uint64_t *__restrict__ accept = nullptr;
   if constexpr (FILT) accept = (accept_arg, ...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = kChunkRows;
   constexpr bool DENSE = (MODE & 1) != 0;
   constexpr bool COMPACT = (MODE & 2) != 0;
-  constexpr int QU = query_units_per_chunk(QB, SB);
+  constexpr int QU = DG ? kDigitMasks : query_units_per_chunk(QB, SB);  // 16-byte units staged per chunk of a row
   const int w16 = W > 0 ? W : a.idx.geom.w16;
   u32x4 *s_planes = reinterpret_cast<u32x4 *>(smem);
   uint64_t *s_ent = reinterpret_cast<uint64_t *>(smem + (size_t)w16 * QU * 16);
@@ -123,8 +127,8 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
     const int64_t my_tile = (a.chunk_begin + wg.chunk_local) * kTilesPerChunk + __builtin_amdgcn_readfirstlane(wave);
     if (my_tile < (a.idx.n_rows + kTileRows - 1) / kTileRows) aw = accept[my_tile];
   }
-  {  // stage the query bit-planes once per workgroup
-    const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)q * w16 * QU;
+  {  // stage the query bit-planes (DG: its digit masks) once per workgroup
+    const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (DG ? (size_t)a.qdigits_at : 0) + (size_t)q * w16 * QU;
     for (int i = tid; i < w16 * QU; i += NT) s_planes[i] = gp[i];
     if (!DENSE && tid == 0) *s_cnt = 0;
   }
@@ -159,7 +163,8 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
       else load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
       if constexpr (COMPACT && DENSE) exact_corrections<true>(a.idx.exact, row, lu, xadd);
       if constexpr (COMPACT && !DENSE) aadd = tile_add_bound(a.idx, tile, p.sim);
-      if constexpr (SB == 1) qc = tile_popcounts<QB, W, !RS>(c, s_planes, ones);
+      if constexpr (DG) qc = tile_digit_dot<W>(c, s_planes, ones, p.digit_k);
+      else if constexpr (SB == 1) qc = tile_popcounts<QB, W, !RS>(c, s_planes, ones);
       else tile_dot_multibit<QB, W, SB, !RS>(c, s_planes, qc, ones);
     } else {  // a row width without a compiled kernel: streamed chunk by chunk
       if constexpr (!COMPACT) {
@@ -173,7 +178,8 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
         aadd = tile_add_bound(a.idx, tile, p.sim);
         if constexpr (RS) ones = BBQ_STREAM_LOAD(a.idx.row_sums + row);
       }
-      if constexpr (SB == 1) qc = tile_popcounts_any<QB, !RS>(tp, lane, w16, s_planes, ones);
+      if constexpr (DG) qc = tile_digit_dot_any(tp, lane, w16, s_planes, ones, p.digit_k);
+      else if constexpr (SB == 1) qc = tile_popcounts_any<QB, !RS>(tp, lane, w16, s_planes, ones);
       else tile_dot_multibit_any<QB, SB, !RS>(tp, lane, w16, s_planes, qc, ones);
     }
     // quantizedComponentSum of a freshly quantized row is its popcount / component sum (RS: converted where a double is needed, below)
@@ -266,6 +272,17 @@ constexpr bool row_sums_twin() {
   return true;
 }
 
+// The RS instantiations of a 4-plane query against 1-bit rows that have a digit twin (DG): those whose twin keeps at least its occupancy -
+// all of them do - AND was measured faster than the plane form on the device (Measurement; docs/dropped.md, "digit planes"):
+// 6, 8 and 12 chunks unfiltered, 6 chunks filtered.  One chunk (dim <= 128) gained nothing outside the run-to-run spread; the run-time
+// width and the filtered sweeps of 8 and 12 chunks were not measured.
+// To check again: as for row_sums_twin, each DG instantiation's Occupancy against its RS twin's, then an A/B of the width on one device.
+template <bool FILT, int QB, int W, int SB>
+constexpr bool digit_twin() {
+  if (SB != 1 || QB != 4 || !row_sums_twin<FILT, QB, W, SB>()) return false;
+  return W == 6 || (!FILT && (W == 8 || W == 12));
+}
+
 template <bool FILT, int QB, int W, int MODE, int SB = 1>
 static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s) {
   ScanArgs a = args;  // the map's parameters: what the kernel decodes its block index with is what the grid below is built from
@@ -273,16 +290,25 @@ static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, in
   a.n_queries = n_queries;
   a.l2_shift = (MODE & 1) ? 0 : sweep_shift_for(args.l2_shift, n_queries, n_chunks);  // a dense launch writes every row: nothing to co-schedule for
   const int w16 = W > 0 ? W : a.idx.geom.w16;
-  const size_t smem = (size_t)w16 * query_units_per_chunk(QB, SB) * 16 + ((MODE & 1) ? 0 : (size_t)((a.ovf || a.append_lists) ? kChunkRows : a.cap) * 8) + 16;
+  const size_t smem_out = ((MODE & 1) ? 0 : (size_t)((a.ovf || a.append_lists) ? kChunkRows : a.cap) * 8) + 16;
+  const size_t smem = (size_t)w16 * query_units_per_chunk(QB, SB) * 16 + smem_out;
   dim3 grid(sweep_grid_x(n_chunks, a.l2_shift), sweep_grid_y(n_queries, a.l2_shift), 1), block(kChunkRows, 1, 1);
+  if constexpr ((MODE & 3) == 2 && digit_twin<FILT, QB, W, SB>()) {
+    if (a.idx.row_sums && a.qdigits_at > 0) {  // ... and the caller staged the digit masks: three planes instead of four
+      const size_t smem_dg = (size_t)w16 * kDigitMasks * 16 + smem_out;
+      if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, true, const uint64_t *>), grid, block, smem_dg, s, a, accept);
+      else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, true>), grid, block, smem_dg, s, a);
+      return hipGetLastError();
+    }
+  }
   if constexpr ((MODE & 3) == 2 && row_sums_twin<FILT, QB, W, SB>()) {
     if (a.idx.row_sums) {  // the launch's view carries the row sums: the sweep that reads them
-      if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, const uint64_t *>), grid, block, smem, s, a, accept);
+      if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, false, const uint64_t *>), grid, block, smem, s, a, accept);
       else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true>), grid, block, smem, s, a);
       return hipGetLastError();
     }
   }
-  if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, false, const uint64_t *>), grid, block, smem, s, a, accept);
+  if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, false, false, const uint64_t *>), grid, block, smem, s, a, accept);
   else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB>), grid, block, smem, s, a);
   return hipGetLastError();
 }

@@ -54,6 +54,9 @@ int64_t query_data_bytes(const bbq_index *ix, int planes);
 int planes_of_call(const bbq_index *ix, const uint8_t *q, int64_t count, int one_bit);
 void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const uint8_t *q, const double *qc, int planes,
                 int one_bit, int sim);
+// the digit masks of a 4-plane query against a 1-bit index ([w16][kDigitMasks] 16-byte masks -> digits_dst) and their K -> pp->digit_k
+int64_t digit_bytes_per_query_w(int w16);
+void fill_query_digits(const bbq_index *ix, uint8_t *digits_dst, QueryParams *pp, const uint8_t *q);
 // the sub-batch's queries once more as matrix-core operands + group maxima behind the `bytes` already staged in h_qbuf
 struct MfmaStage { bool fp; int scale8; size_t off_qbytes, off_qmax, bytes; };
 MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryParams *hq, int64_t q_first, int nq, size_t bytes);
@@ -69,6 +72,8 @@ int effective_batch(const bbq_index *ix, int64_t n_queries = 0);
 int l2_share_shift(const bbq_index *ix);
 // does a per-query sparse sweep of this index read the rows' component sums from the side array (option row_sums)?
 bool row_sums_for_launch(const bbq_index *ix);
+// does a call with `planes` bit-planes stage the digit masks for its per-query sparse sweeps (option digit_planes)?
+bool digit_planes_for_call(const bbq_index *ix, int planes);
 Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k = 0, bool latency = false);
 Plan build_filtered_plan(const bbq_index *ix, const bbq_filter &f, int64_t k, int64_t final_k, bool latency);
 int ensure_slot(const SearchCall &c, Slot &s, int nq, bool own_lists);

@@ -628,6 +628,12 @@ int bbq_reset_stats(bbq_index *idx);
  *     queryBits 1 (filtered searches: also at queryBits 8), 4-bit rows of 353..384 and of 481..512 dimensions at queryBits 8
  *     (filtered: also at 4).  No statistic tells which kernel ran.  The array is kept beside the rows through
  *     every append, update and compaction, and is in no file: a load derives it again.  The same value either way: never a different answer
+ *   digit_planes -1|0|1 (-1): 1-bit index, compact corrections, queryBits 3..4 (query values that need four bit-planes): 1 and -1 let the
+ *     per-query sweep score a query in three planes of ternary digits (q - 4 = t0 + 3 t1 + 9 t2) and the row's component sum instead of
+ *     four bit-planes, wherever that sweep reads the sum (row_sums) - so never with resident_mb 0 and an automatic row_sums - and the
+ *     row is 6, 8 or 12 16-byte chunks wide (641..768, 897..1024, 1409..1536 dimensions; a filtered search: 641..768 only) - where it
+ *     was measured faster; 0: always bit-planes.  The digit masks are staged with the query in addition to its bit-planes (5 x 16 bytes per 128 dimensions).  The dot
+ *     product is the same exact integer either way: never a different answer
  *   fast_bound 0|1 (1): compact corrections: 1 tests the score bound of a row in f32 against the threshold's image in the linear space of
  *     the score formula, for every query whose corrections have f32 images (others keep the f64 bound); 0: always the f64 bound through
  *     the similarity transform.  A pre-filter in front of the exact score either way: never a different answer
