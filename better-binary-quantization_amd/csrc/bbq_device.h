@@ -474,6 +474,45 @@ struct RangeArgs {
   uint64_t *out;               // entries (row << 32 | f32 score bits) of the launch's queries, back to back
 };
 
+// span search (bbq_span_kernels.hip): the k best rows among each query's own contiguous spans of rows.  The score pass leaves the f32
+// score of every visited row of query q at scores[q's base + the row's position in q's visiting order]; the select pass finds each
+// selected query's (k + 1)-th largest score key and writes the rows above it.
+constexpr int kSpanSelectMax = 4096;  // largest k the select pass takes
+// one workgroup of the score pass: the rows [row_lo, row_hi) of one span, cut by the host at tile-aligned kChunkRows-row steps, so
+// row_lo >> 6 == first_tile and row_hi <= (first_tile + kTilesPerChunk) * 64
+struct SpanItem {
+  uint32_t query;       // of the sub-batch
+  uint32_t first_tile;  // wave w takes tile first_tile + w
+  uint32_t row_lo, row_hi;
+  int64_t out;          // scores[out + (r - row_lo)] takes row r
+};
+static_assert(sizeof(SpanItem) == 24, "SpanItem: staged in an array behind 8-byte data");
+struct SpanScoreArgs {
+  IndexView idx;
+  const uint4 *qplanes;        // [Q][w16][QU] staged query data, as ScanArgs::qplanes
+  const QueryParams *qparams;  // [Q]
+  const SpanItem *items;       // [grid.x] the launch's first item
+  float *scores;               // the sub-batch's scores, query by query
+};
+// a non-empty span of a query in its visiting order: position `pos` of the query's scores is row `begin`
+struct SpanRun { int64_t pos, begin; };
+// a query of the select pass
+struct SpanQuery {
+  int64_t score_off;  // its scores start at scores[score_off] ...
+  int64_t len;        // ... and there are len > k of them
+  int64_t run_first;  // its runs: runs[run_first .. run_first + n_runs)
+  int32_t n_runs;
+  int32_t pad;
+};
+struct SpanSelectArgs {
+  const float *scores;
+  const SpanQuery *sel;   // [grid.x]
+  const SpanRun *runs;
+  uint64_t *out;          // [grid.x][out_stride]: {rows above the cut | flags << 32}, the cut's f32 bits, then k entries if there are exactly k
+  int32_t k;              // 1 .. kSpanSelectMax
+  int32_t out_stride;     // >= k + 2
+};
+
 constexpr int kFinalizeThreads = 1024;
 constexpr int kFinalizeJobs = 4096;      // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)
 constexpr int kFinalizeKeyCap = 12288;   // LDS key buffer of the finalize kernel (new keys + running top-k)

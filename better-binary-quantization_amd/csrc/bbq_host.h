@@ -137,6 +137,7 @@ struct DeviceCtx {
   DevBuf<uint32_t> d_aux_flags;
   DevBuf<uint8_t> d_gather;          // grow-only scratch of bbq_score_ords* (bbq_gather.cpp): one launch's offsets, queries, ords and outputs
   DevBuf<uint8_t> d_range;           // grow-only scratch of a range search's sub-batch (bbq_range.cpp): queries, thresholds, per-chunk counts and lists
+  DevBuf<uint8_t> d_span;            // grow-only scratch of a span search's sub-batch (bbq_span.cpp): queries, span tables, work items, answer blocks, scores
   int last_big_slot = -1;             // slot whose ev_big marks the end of the most recently enqueued big sweep
   // latency path (bbq_latency_kernels.hip): the answer of a single-query call lands in mapped, coherent host memory and the host
   // polls a sequence word behind it: [0] sequence, [8 ..) header + entries

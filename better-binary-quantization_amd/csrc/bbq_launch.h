@@ -1,6 +1,6 @@
 // bbq_launch.h - host-callable launch wrappers of every kernel file: the sweeps, finalize and pack (bbq_kernels.hip, bbq_filter_kernels.hip,
 // bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip), the rerank (bbq_rerank_kernels.hip), the scoring of chosen rows (bbq_gather_kernels.hip)
-// and the range search (bbq_range_kernels.hip)
+// the range search (bbq_range_kernels.hip) and the span search (bbq_span_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbq_device.h"
@@ -90,6 +90,12 @@ hipError_t launch_range_offsets(uint32_t *counts, uint32_t *nonempty, uint32_t *
 // the passing rows of the n_queries queries from a.q_first on, as entries at a.out[a.base[q] + ...], ascending by row; max_nonempty = the
 // longest non-empty-chunk list among them
 hipError_t launch_range_fill(const RangeArgs &a, int planes, int n_queries, int64_t max_nonempty, hipStream_t s);
+// span search (bbq_span_kernels.hip).  The f32 scores of the rows of n_items work items (a.items[0 .. n_items), at most
+// kGridWorkItemsMax / kChunkRows of them) -> a.scores; planes as launch_scan takes them
+hipError_t launch_span_score(const SpanScoreArgs &a, int planes, int64_t n_items, hipStream_t s);
+// per selected query (a.sel[0 .. n_selected)): the exact (a.k + 1)-th largest of its scores, the number of rows above it and, when that
+// is a.k and no score is NaN, those rows as entries in any order -> the query's block of a.out
+hipError_t launch_span_select(const SpanSelectArgs &a, int n_selected, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 // staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place

@@ -1,0 +1,283 @@
+// bbq_span.cpp - span search: bbq_search_spans_batch (kernels: bbq_span_kernels.hip).  The host checks every span before the first
+// launch, plans the call in sub-batches and allocates what the largest of them needs, then works through them: stage the queries, the
+// span tables and the work items in one copy, launch the score pass and the select pass, bring back the answer blocks in one copy, sort
+// what the device selected and replay the reference's heap over the scores of the queries it could not prove.
+#include <string.h>
+#include <algorithm>
+#include <memory>
+#include <new>
+#include <thread>
+#include "bbq_search.h"
+
+using namespace bbq;
+
+namespace {
+
+// A sub-batch takes at most this many queries and this many bytes of scores, and always at least one query: a query whose spans hold
+// more rows than that has a sub-batch of its own.  A score launch takes at most kSpanMaxItems work items (the grid's x extent in
+// work-items is a 32-bit count).  The scratch is the context's (DeviceCtx::d_span) and only grows.
+constexpr int kSpanMaxQueries = 1024;
+constexpr int64_t kSpanScoreBytes = 64ll << 20;
+constexpr int64_t kSpanMaxItems = 1 << 22;
+static_assert((uint64_t)kSpanMaxItems * kChunkRows <= kGridWorkItemsMax, "one score launch");
+
+inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
+
+// work items of the non-empty span [b, e): cut at kChunkRows-row steps from the start of b's tile
+inline int64_t items_of_span(int64_t b, int64_t e) { return (e - (b & ~(int64_t)(kTileRows - 1)) + kChunkRows - 1) / kChunkRows; }
+
+// what a sub-batch of the call holds
+struct SubBatch {
+  int64_t q0 = 0;
+  int nq = 0;
+  int64_t n_items = 0, n_runs = 0, n_sel = 0, n_scores = 0;
+};
+
+// where a sub-batch keeps what in the scratch: [query data | query uniforms | selected queries | runs | items] come from the host in one
+// copy, the answer blocks go back in one, the scores stay unless a query's heap is replayed
+struct Layout {
+  size_t qdata, qparams, sel, runs, items, head_bytes, out, scores, bytes;
+  Layout(const SubBatch &b, size_t qb, size_t out_stride) {
+    qdata = 0;
+    qparams = qdata + (size_t)b.nq * qb;
+    sel = qparams + (size_t)b.nq * sizeof(QueryParams);
+    runs = sel + (size_t)b.n_sel * sizeof(SpanQuery);
+    items = runs + (size_t)b.n_runs * sizeof(SpanRun);
+    head_bytes = items + (size_t)b.n_items * sizeof(SpanItem);
+    out = align16(head_bytes);
+    scores = align16(out + (size_t)b.n_sel * out_stride * 8);
+    bytes = scores + (size_t)b.n_scores * 4;
+  }
+};
+static_assert(sizeof(SpanQuery) == 32 && sizeof(SpanRun) == 16 && sizeof(QueryParams) % 16 == 0, "every staged array starts 8-byte aligned");
+
+// every span of every query, in call order: inside the index, begin <= end, ascending and disjoint within a query.  len[q] = its rows
+int check_spans(int32_t n_queries, const int64_t *off, const int64_t *spans, int64_t n_rows, std::vector<int64_t> &len) {
+  len.assign((size_t)n_queries, 0);
+  for (int32_t q = 0; q < n_queries; ++q) {
+    int64_t prev_end = 0;
+    for (int64_t j = off[q]; j < off[q + 1]; ++j) {
+      const int64_t b = spans[2 * j], e = spans[2 * j + 1];
+      if (b < 0 || e < b || e > n_rows)
+        return fail(BBQ_ERR_INVALID_ARG, "bbq_search_spans_batch: query %d, span %lld: [%lld, %lld) is no span of an index of %lld rows", q,
+                    (long long)(j - off[q]), (long long)b, (long long)e, (long long)n_rows);
+      if (j > off[q] && b < prev_end)
+        return fail(BBQ_ERR_INVALID_ARG, "bbq_search_spans_batch: query %d, span %lld: [%lld, %lld) begins in front of the end of the span before it (%lld); spans ascend and do not overlap",
+                    q, (long long)(j - off[q]), (long long)b, (long long)e, (long long)prev_end);
+      prev_end = e;
+      len[(size_t)q] += e - b;
+    }
+  }
+  return BBQ_OK;
+}
+
+// does the select pass run for a query of `len` rows?
+inline bool selected(int64_t len, int64_t k) { return k >= 1 && k <= kSpanSelectMax && len > k; }
+
+// the call behind its argument checks, under the context's lock
+int spans_locked(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim, int64_t k,
+                 const int64_t *off, const int64_t *spans, int32_t *out_idx, float *out_score, int64_t *out_n, uint8_t *out_status) {
+  std::lock_guard<std::mutex> lk(ix->ctx->mu);
+  HIPCHK(hipSetDevice(ix->device));
+  // under the lock: the rows the check sees are the rows the kernel reads (an append or a compaction on another thread comes before or after)
+  std::vector<int64_t> len;
+  int rc = check_spans(n_queries, off, spans, ix->main.view.n_rows, len);
+  if (rc != BBQ_OK) return rc;
+  int64_t longest = 0;
+  for (int32_t q = 0; q < n_queries; ++q) longest = std::max(longest, len[(size_t)q]);
+  if (k > 0 && longest > 0 && (!out_idx || !out_score)) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_spans_batch: null output");
+  if (k == 0 || longest == 0) {  // nothing to score
+    for (int32_t q = 0; q < n_queries; ++q) out_n[q] = 0;
+    if (out_status) memset(out_status, 0, (size_t)n_queries);
+    return BBQ_OK;
+  }
+
+  const int one_bit = query_bits == 1 ? 1 : 0;
+  const int planes = planes_of_call(ix, qquant, (int64_t)n_queries * ix->geom.dim, one_bit);
+  const size_t qb = (size_t)query_data_bytes(ix, planes);
+  const size_t out_stride = (size_t)std::min<int64_t>(k, kSpanSelectMax) + 2;
+
+  // the plan: sub-batches, and the largest of everything they need
+  std::vector<SubBatch> subs;
+  size_t max_bytes = 0, max_head = 0, max_back = 0;
+  int64_t max_scores = 0;
+  for (int64_t q = 0; q < n_queries;) {
+    SubBatch b;
+    b.q0 = q;
+    while (q < n_queries && b.nq < kSpanMaxQueries && (b.nq == 0 || (b.n_scores + len[(size_t)q]) * 4 <= kSpanScoreBytes)) {
+      const int64_t L = len[(size_t)q];
+      for (int64_t j = off[q]; j < off[q + 1]; ++j)
+        if (spans[2 * j + 1] > spans[2 * j]) {
+          b.n_items += items_of_span(spans[2 * j], spans[2 * j + 1]);
+          if (selected(L, k)) ++b.n_runs;
+        }
+      if (selected(L, k)) ++b.n_sel;
+      b.n_scores += L;
+      ++b.nq;
+      ++q;
+    }
+    const Layout lo(b, qb, out_stride);
+    max_bytes = std::max(max_bytes, lo.bytes);
+    max_head = std::max(max_head, lo.head_bytes);
+    max_back = std::max(max_back, (size_t)b.n_sel * out_stride);
+    max_scores = std::max(max_scores, b.n_scores);
+    subs.push_back(b);
+  }
+  // everything large, before anything is written to the caller's arrays
+  {
+    const hipError_t e = ix->ctx->d_span.reserve(max_bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "span search: %zu bytes of scratch: %s", max_bytes, hipGetErrorString(e)); }
+  }
+  std::unique_ptr<uint8_t[]> head(new (std::nothrow) uint8_t[std::max<size_t>(max_head, 1)]);
+  std::unique_ptr<uint64_t[]> back(new (std::nothrow) uint64_t[std::max<size_t>(max_back, 1)]);
+  std::unique_ptr<float[]> h_scores(new (std::nothrow) float[(size_t)std::max<int64_t>(max_scores, 1)]);  // touched only where a heap is replayed
+  if (!head || !back || !h_scores) return fail(BBQ_ERR_OOM, "span search: host staging for %zu + %zu + %lld bytes", max_head, max_back * 8, (long long)max_scores * 4);
+
+  uint8_t *d = ix->ctx->d_span;
+  hipStream_t st = ix->ctx->aux_stream;
+  SpanScoreArgs sa{};
+  sa.idx = launch_view(ix, ix->main).view;
+  sa.idx.row_sums = row_sums_for_launch(ix) ? ix->main.view.row_sums : nullptr;
+  std::vector<int64_t> score_off, replay;  // per query of the sub-batch: where its scores start; the queries whose heap the host replays
+  std::vector<int32_t> sel_slot;           // per query of the sub-batch: its block among the selected, or -1
+  std::vector<uint64_t> ent;
+
+  for (const SubBatch &b : subs) {
+    const Layout lo(b, qb, out_stride);
+    SpanQuery *h_sel = reinterpret_cast<SpanQuery *>(head.get() + lo.sel);
+    SpanRun *h_runs = reinterpret_cast<SpanRun *>(head.get() + lo.runs);
+    SpanItem *h_items = reinterpret_cast<SpanItem *>(head.get() + lo.items);
+    score_off.assign((size_t)b.nq, 0);
+    sel_slot.assign((size_t)b.nq, -1);
+    int64_t n_items = 0, n_runs = 0, n_sel = 0, n_scores = 0;
+    for (int s = 0; s < b.nq; ++s) {
+      const int64_t q = b.q0 + s, L = len[(size_t)q];
+      fill_query(ix, head.get() + lo.qdata + (size_t)s * qb, reinterpret_cast<QueryParams *>(head.get() + lo.qparams) + s,
+                 qquant + (size_t)q * ix->geom.dim, qcorr + (size_t)q * 4, planes, one_bit, sim);
+      score_off[(size_t)s] = n_scores;
+      const bool sel = selected(L, k);
+      if (sel) {
+        sel_slot[(size_t)s] = (int32_t)n_sel;
+        h_sel[n_sel++] = SpanQuery{n_scores, L, n_runs, 0, 0};
+      }
+      int64_t pos = 0;  // of the span's first row in the query's visiting order
+      for (int64_t j = off[q]; j < off[q + 1]; ++j) {
+        const int64_t sb = spans[2 * j], se = spans[2 * j + 1];
+        if (se <= sb) continue;
+        if (sel) {
+          h_runs[n_runs++] = SpanRun{pos, sb};
+          ++h_sel[n_sel - 1].n_runs;
+        }
+        for (int64_t r0 = sb & ~(int64_t)(kTileRows - 1); r0 < se; r0 += kChunkRows) {
+          const int64_t r_lo = std::max(r0, sb), r_hi = std::min(r0 + kChunkRows, se);
+          h_items[n_items++] = SpanItem{(uint32_t)s, (uint32_t)(r_lo >> 6), (uint32_t)r_lo, (uint32_t)r_hi, n_scores + pos + (r_lo - sb)};
+        }
+        pos += se - sb;
+      }
+      n_scores += L;
+    }
+
+    if (n_scores > 0) {
+      HIPCHK(hipMemcpyAsync(d, head.get(), lo.head_bytes, hipMemcpyHostToDevice, st));
+      sa.qplanes = reinterpret_cast<const uint4 *>(d + lo.qdata);
+      sa.qparams = reinterpret_cast<const QueryParams *>(d + lo.qparams);
+      sa.scores = reinterpret_cast<float *>(d + lo.scores);
+      for (int64_t i0 = 0; i0 < n_items; i0 += kSpanMaxItems) {
+        sa.items = reinterpret_cast<const SpanItem *>(d + lo.items) + i0;
+        HIPCHK(launch_span_score(sa, planes, std::min(kSpanMaxItems, n_items - i0), st));
+      }
+      if (n_sel > 0) {
+        SpanSelectArgs se{};
+        se.scores = sa.scores;
+        se.sel = reinterpret_cast<const SpanQuery *>(d + lo.sel);
+        se.runs = reinterpret_cast<const SpanRun *>(d + lo.runs);
+        se.out = reinterpret_cast<uint64_t *>(d + lo.out);
+        se.k = (int32_t)k;
+        se.out_stride = (int32_t)out_stride;
+        HIPCHK(launch_span_select(se, (int)n_sel, st));
+        HIPCHK(hipMemcpyAsync(back.get(), d + lo.out, (size_t)n_sel * out_stride * 8, hipMemcpyDeviceToHost, st));
+      }
+      HIPCHK(hipStreamSynchronize(st));  // also: the staging is free for the next sub-batch
+    }
+
+    // what the device selected: exactly k rows above the cut and no NaN - sorted by descending score; two equal scores among them, or
+    // one equal to the cut, and the heap's history decides: replayed like the queries the device could not prove
+    replay.clear();
+    for (int s = 0; s < b.nq; ++s) {
+      const int64_t q = b.q0 + s, L = len[(size_t)q];
+      if (L == 0) {
+        out_n[q] = 0;
+        if (out_status) out_status[q] = 0;
+        continue;
+      }
+      bool proven = false;
+      if (sel_slot[(size_t)s] >= 0) {
+        const uint64_t *blk = back.get() + (size_t)sel_slot[(size_t)s] * out_stride;
+        if ((uint32_t)(blk[0] >> 32) == 0u && (int64_t)(uint32_t)blk[0] == k) {
+          ent.assign(blk + 2, blk + 2 + k);
+          std::sort(ent.begin(), ent.end(), [](uint64_t x, uint64_t y) { return entry_score(x) > entry_score(y); });
+          proven = entry_score(ent[(size_t)k - 1]) != entry_score(blk[1]);
+          for (int64_t i = 1; proven && i < k; ++i) proven = entry_score(ent[(size_t)i - 1]) != entry_score(ent[(size_t)i]);
+          if (proven) {
+            unpack_entries(ent.data(), k, out_idx + q * k, out_score + q * k);
+            out_n[q] = k;
+          }
+        }
+      }
+      if (out_status) out_status[q] = proven ? 0 : 1;
+      if (!proven) replay.push_back(s);
+    }
+    if (replay.empty()) continue;
+
+    // the reference loop (src/binaryQuantizationFormat.ts:383-411) over the query's rows in visiting order: the literal heap of min(k, rows)
+    int64_t replay_rows = 0;
+    for (int64_t s : replay) {
+      const int64_t L = len[(size_t)(b.q0 + s)];
+      HIPCHK(hipMemcpyAsync(h_scores.get() + score_off[(size_t)s], d + lo.scores + (size_t)score_off[(size_t)s] * 4, (size_t)L * 4, hipMemcpyDeviceToHost, st));
+      replay_rows += L;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    auto work = [&](size_t t, size_t T) {
+      for (size_t i = t; i < replay.size(); i += T) {
+        const int64_t s = replay[i], q = b.q0 + s;
+        const float *sc = h_scores.get() + score_off[(size_t)s];
+        HeapReplay hr(k, len[(size_t)q]);
+        for (int64_t j = off[q]; j < off[q + 1]; ++j)
+          for (int64_t r = spans[2 * j]; r < spans[2 * j + 1]; ++r) hr.offer(*sc++, (int32_t)r);
+        out_n[q] = hr.finish(out_idx + q * k, out_score + q * k);
+      }
+    };
+    const size_t T = std::min<size_t>((size_t)std::max(ix->opt_replay_threads, 1), replay.size());
+    if (T <= 1 || replay_rows < 4096) {
+      work(0, 1);
+    } else {
+      std::vector<std::thread> th;
+      for (size_t t = 0; t < T; ++t) th.emplace_back(work, t, T);
+      for (std::thread &x : th) x.join();
+    }
+  }
+  return BBQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bbq_search_spans_batch(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim, int64_t k,
+                           const int64_t *span_offsets, const int64_t *spans, int32_t *out_idx, float *out_score, int64_t *out_n, uint8_t *out_status) {
+  clear_error();
+  const int rc = validate_query_args(ix, n_queries, qquant, qcorr, query_bits, sim, k);
+  if (rc != BBQ_OK) return rc;
+  if (ix->multi) return fail(BBQ_ERR_UNSUPPORTED, "span search is not supported on a multi-device index");
+  if (ix->has_pilot || ix->row_base != 0) return fail(BBQ_ERR_UNSUPPORTED, "span search is not supported on a row shard or an index with a pilot replica");
+  if (n_queries == 0) return BBQ_OK;
+  if (!span_offsets) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_spans_batch: span_offsets is null");
+  if (span_offsets[0] != 0) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_spans_batch: span_offsets[0] must be 0");
+  for (int32_t q = 0; q < n_queries; ++q)
+    if (span_offsets[q + 1] < span_offsets[q]) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_spans_batch: span_offsets must ascend");
+  if (span_offsets[n_queries] > 0 && !spans) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_spans_batch: spans is null");
+  if (!out_n) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_spans_batch: out_n is null");
+  return spans_locked(ix, n_queries, qquant, qcorr, query_bits, sim, k, span_offsets, spans, out_idx, out_score, out_n, out_status);
+}
+
+}  // extern "C"

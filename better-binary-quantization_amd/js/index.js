@@ -417,6 +417,17 @@ function ordsAsInt32(ords) {
   }
   return out;
 }
+// spans as the addon takes them: a Float64Array of begin, end, begin, end, ... (passed through) or an array of [begin, end] pairs
+function spansAsFloat64(spans) {
+  if (spans instanceof Float64Array) return spans;
+  const out = new Float64Array(2 * spans.length);
+  for (let i = 0; i < spans.length; i++) {
+    if (!spans[i] || spans[i].length !== 2) throw new Error('a span is a [begin, end) pair');
+    out[2 * i] = Number(spans[i][0]);
+    out[2 * i + 1] = Number(spans[i][1]);
+  }
+  return out;
+}
 function isMultiBit(targetVectors) { return targetVectors._indexBits !== 1 && targetVectors.dimension() > 1; }
 
 /** computeBatchFourBitSimilarityScores for one row, src/batchDotProduct.ts:554-617 (used only for the originalQueryVector corner) */
@@ -685,6 +696,32 @@ class BinaryQuantizationFormat {
     const tNative = process.hrtime.bigint();
     const qz = native.quantizeQueries(flat, 1, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, 1);
     const r = native.searchOrds(targetVectors._deviceIndex(), qz.quantized, qz.corrections, qb, sim, k, ordsAsInt32(ords));
+    hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
+    const n = r.indices.length, res = new Array(n);
+    for (let j = 0; j < n; j++) res[j] = { index: r.indices[j], score: r.scores[j] };
+    return res;
+  }
+
+  /**
+   * extension (not in the reference): searchNearestNeighbors over the rows of `spans` - an array of [begin, end) pairs (or a Float64Array
+   * begin, end, begin, end, ...), end exclusive, ascending and disjoint; empty spans and an empty list are allowed - what the reference's
+   * loop (:349-411) returns when it visits exactly those rows, ascending, with a heap of min(k, rows visited).  The spans may differ from
+   * query to query, which a RowFilter cannot; the device streams them as whole tiles and selects the k best itself.  Same validation and
+   * messages as searchNearestNeighbors; a span that is none throws the library's message, which names it.  A multi-device index
+   * (BBQ_DEVICES) throws the library's unsupported message.
+   */
+  searchNearestNeighborsInSpans(queryVector, targetVectors, spans, k) {
+    if (!queryVector) throw new Error('查询向量不能为空');
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (!spans) throw new Error('行区间不能为空');
+    if (k < 0) throw new Error('k值不能为负数');
+    if (queryVector.length !== targetVectors.dimension()) throw new Error('查询向量维度与目标向量维度不匹配');
+    const flat = this._flatQueries([queryVector], targetVectors, k);
+    if (flat === null) return [];
+    const q = this.quantizer, sim = simOrdinal(q.similarityFunction), qb = this.config.queryBits;
+    const tNative = process.hrtime.bigint();
+    const qz = native.quantizeQueries(flat, 1, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, 1);
+    const r = native.searchSpans(targetVectors._deviceIndex(), qz.quantized, qz.corrections, qb, sim, k, spansAsFloat64(spans));
     hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
     const n = r.indices.length, res = new Array(n);
     for (let j = 0; j < n; j++) res[j] = { index: r.indices[j], score: r.scores[j] };

@@ -699,6 +699,55 @@ static napi_value SearchOrds(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* searchSpans(handle, qquant, qcorr, queryBits, sim, k, spans Float64Array [2 m] = begin, end (exclusive) of each span) ->
+ * {indices Int32Array, scores Float32Array, status}: the reference's loop over the rows of the spans, ascending (bbq_search_spans_batch
+ * with one query); status 0: the device selected the answer, 1: the host replayed the heap */
+static napi_value SearchSpans(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (!get_args(env, info, 7, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *qq, *qc, *sp; size_t ql, cl, n2;
+  int64_t qb, sim, k;
+  if (!get_typed(env, a[1], napi_uint8_array, &qq, &ql) || !get_typed(env, a[2], napi_float64_array, &qc, &cl) ||
+      !get_i64(env, a[3], &qb) || !get_i64(env, a[4], &sim) || !get_i64(env, a[5], &k) || !get_typed(env, a[6], napi_float64_array, &sp, &n2)) return NULL;
+  if (ql != (size_t)bbq_index_dimension(ix) || cl != 4) { napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return NULL; }
+  if (k < 0) { napi_throw_error(env, "BBQ7", "k值不能为负数"); return NULL; }
+  if (n2 % 2 != 0) { napi_throw_range_error(env, NULL, "bbq_napi: spans are pairs of begin and end"); return NULL; }
+  const int64_t size = bbq_index_size(ix);
+  const int64_t keff = k < size ? k : size;   /* no answer is longer than the index */
+  int64_t *s64 = (int64_t *)malloc((n2 + 1) * sizeof(int64_t));
+  int32_t *idx = (int32_t *)malloc(((size_t)keff + 1) * sizeof(int32_t));
+  float *sc = (float *)malloc(((size_t)keff + 1) * sizeof(float));
+  if (!s64 || !idx || !sc) { free(s64); free(idx); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  for (size_t i = 0; i < n2; ++i) {
+    const double v = ((const double *)sp)[i];
+    if (!(v >= -9007199254740992.0 && v <= 9007199254740992.0) || v != (double)(int64_t)v) {
+      free(s64); free(idx); free(sc);
+      napi_throw_range_error(env, NULL, "bbq_napi: a span's begin and end are integers");
+      return NULL;
+    }
+    s64[i] = (int64_t)v;
+  }
+  const int64_t offsets[2] = {0, (int64_t)(n2 / 2)};
+  int64_t cnt = 0;
+  uint8_t status = 0;
+  int rc = bbq_search_spans_batch(ix, 1, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff, offsets, s64, idx, sc, &cnt, &status);
+  free(s64);
+  if (rc != BBQ_OK) { free(idx); free(sc); return throw_bbq(env, rc); }
+  void *oi, *os;
+  napi_value ti = new_typed(env, napi_int32_array, (size_t)cnt, 4, &oi);
+  napi_value ts = new_typed(env, napi_float32_array, (size_t)cnt, 4, &os);
+  if (!ti || !ts) { free(idx); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  if (cnt > 0) { memcpy(oi, idx, (size_t)cnt * 4); memcpy(os, sc, (size_t)cnt * 4); }
+  free(idx); free(sc);
+  napi_value o, st;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  NAPI_CALL(env, napi_create_int32(env, (int32_t)status, &st));
+  set_prop(env, o, "indices", ti); set_prop(env, o, "scores", ts); set_prop(env, o, "status", st);
+  return o;
+}
+
 /* searchRange(handle, filter handle | null, qquant, qcorr, queryBits, sim, threshold) -> {indices Int32Array, scores Float32Array}: every row (of
  * the filter, if one is given) whose f32 score is >= threshold, ascending by ord (bbq_count_range_batch, then bbq_search_range_batch with
  * exactly that room).  A NaN threshold throws. */
@@ -1066,6 +1115,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"scoreOrds", NULL, ScoreOrds, NULL, NULL, NULL, napi_default, NULL},
       {"searchOrds", NULL, SearchOrds, NULL, NULL, NULL, napi_default, NULL},
       {"searchRange", NULL, SearchRange, NULL, NULL, NULL, napi_default, NULL},
+      {"searchSpans", NULL, SearchSpans, NULL, NULL, NULL, napi_default, NULL},
       {"setOption", NULL, SetOption, NULL, NULL, NULL, napi_default, NULL},
       {"stats", NULL, Stats, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsCreate", NULL, VectorsCreate, NULL, NULL, NULL, napi_default, NULL},

@@ -231,6 +231,15 @@ class BinaryQuantizationFormat:
             raise Exception("目标向量序号不能为空")
         return self._search(queryVector, targetVectors, k, None, ords)
 
+    def searchNearestNeighborsInSpans(self, queryVector, targetVectors, spans, k):
+        """extension: searchNearestNeighbors over the rows of `spans` - a list of (begin, end) pairs, end exclusive, ascending and
+        disjoint; empty spans and an empty list are allowed - what the reference's loop returns when it visits exactly those rows,
+        ascending, with a heap of min(k, rows visited).  The spans may differ from query to query, which a row filter cannot; the
+        device streams them as whole tiles and selects the k best itself."""
+        if spans is None:
+            raise Exception("行区间不能为空")
+        return self._search(queryVector, targetVectors, k, None, None, np.asarray(spans, np.int64).reshape(-1, 2))
+
     def searchRange(self, queryVector, targetVectors, threshold, rowFilter=None, order="ord"):
         """extension: every row (of `rowFilter`, createRowFilter, if given) whose stored f32 score is >= threshold - what the
         reference's loop would collect if it kept every visited ord at or above the threshold and skipped the heap - as
@@ -275,7 +284,7 @@ class BinaryQuantizationFormat:
             raise Exception(str(e))
         return [{"score": float(s), "bitDotProduct": int(b)} for s, b in zip(s64, d)]
 
-    def _search(self, queryVector, targetVectors, k, rowFilter, ords=None):
+    def _search(self, queryVector, targetVectors, k, rowFilter, ords=None, spans=None):
         if queryVector is None:
             raise Exception("查询向量不能为空")
         if targetVectors is None:
@@ -294,7 +303,9 @@ class BinaryQuantizationFormat:
         try:
             qq, qc = capi.quantize_query(queryVector, targetVectors.getCentroid(), sim, self._config["queryBits"], self._lambda,
                                          self._iters, search_path=True)
-            if ords is not None:
+            if spans is not None:
+                idx, sc = targetVectors._device().search_spans_batch(qq[None, :], qc[None, :], self._config["queryBits"], sim, k, [spans])[0][0]
+            elif ords is not None:
                 idx, sc = targetVectors._device().search_ords_batch(qq[None, :], qc[None, :], self._config["queryBits"], sim, k, [ords])[0]
             elif rowFilter is None:
                 idx, sc = targetVectors._device().search(qq, qc, self._config["queryBits"], sim, k)

@@ -32,6 +32,7 @@ SYMBOLS = [
     "bbq_index_update_rows", "bbq_index_update", "bbq_vectors_update", "bbq_update_winners",
     "bbq_score_ords", "bbq_score_ords_batch", "bbq_search_ords_batch",
     "bbq_range_key", "bbq_count_range_batch", "bbq_search_range_batch",
+    "bbq_search_spans_batch",
 ]
 
 
@@ -110,6 +111,7 @@ def lib():
     L.bbq_range_key.argtypes = [C.c_float, C.POINTER(C.c_uint32)]
     L.bbq_count_range_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
     L.bbq_search_range_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, i64, vp, vp, vp]
+    L.bbq_search_spans_batch.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp]
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_create_rows.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_destroy.argtypes = [vp]
@@ -557,6 +559,23 @@ class Index:
         _chk(lib().bbq_search_ords_batch(self._h, nq, _ptr(qq), _ptr(qc), query_bits, sim, k, _ptr(off), _ptr(o), _ptr(idx), _ptr(sc), _ptr(cnt)))
         return [(idx[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)]
 
+    def search_spans_batch(self, qquant, qcorr, query_bits, sim, k, spans):
+        """bbq_search_spans_batch: exact top-k of every query over its own contiguous spans of rows [begin, end), ascending and
+        disjoint.  `spans` is a list of (m, 2) arrays, one per query, or (offsets, spans).  Returns a list of (idx, score) per query
+        and the status array (0: the device selected the answer, 1: the host replayed the heap over the device's scores)."""
+        qq = np.ascontiguousarray(qquant, np.uint8)
+        qc = np.ascontiguousarray(qcorr, np.float64)
+        nq = qq.shape[0]
+        off, sp = _spans(spans, nq)
+        kk = max(int(k), 0)
+        idx = np.zeros((nq, kk), np.int32)
+        sc = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.int64)
+        status = np.zeros(nq, np.uint8)
+        _chk(lib().bbq_search_spans_batch(self._h, nq, _ptr(qq), _ptr(qc), query_bits, sim, k, _ptr(off), _ptr(sp), _ptr(idx), _ptr(sc), _ptr(cnt),
+                                         _ptr(status)))
+        return [(idx[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)], status
+
     def _range_args(self, qquant, qcorr, thresholds):
         qq = np.ascontiguousarray(qquant, np.uint8)
         qc = np.ascontiguousarray(qcorr, np.float64)
@@ -686,6 +705,21 @@ def _lists(lists, n_queries):
     off = np.zeros(n_queries + 1, np.int64)
     off[1:] = np.cumsum([a.shape[0] for a in arrs])
     return off, (np.concatenate(arrs) if arrs else np.zeros(0, np.int32))
+
+
+def _spans(spans, n_queries):
+    """one span list per query as the C ABI takes them: (offsets int64 [n_queries + 1], spans int64 [total, 2]).  A TUPLE is the pair
+    (offsets, spans), handed over as it is so that the library's own checks speak; any other sequence holds one (m, 2) array per query"""
+    if isinstance(spans, tuple):
+        if len(spans) != 2 or len(spans[0]) != n_queries + 1:
+            raise BBQError(ERR_INVALID_ARG, "(offsets, spans) with one offset per query and one more")
+        return np.ascontiguousarray(spans[0], np.int64), np.ascontiguousarray(np.asarray(spans[1], np.int64).reshape(-1, 2))
+    if len(spans) != n_queries:
+        raise BBQError(ERR_INVALID_ARG, "one span list per query")
+    arrs = [np.asarray(a, np.int64).reshape(-1, 2) for a in spans]
+    off = np.zeros(n_queries + 1, np.int64)
+    off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    return off, np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, 2), np.int64))
 
 
 def update_winners(ords, n_rows):

@@ -37,7 +37,7 @@ extern "C" {
                               and the compaction - bbq_index_compact, bbq_index_remove_rows, bbq_vectors_compact, bbq_filter_kept_rows - and the
                               in-place updates - bbq_index_update_rows, bbq_index_update, bbq_vectors_update, bbq_update_winners - and the scoring of chosen rows -
                               bbq_score_ords, bbq_score_ords_batch, bbq_search_ords_batch - and the range search - bbq_range_key,
-                              bbq_count_range_batch, bbq_search_range_batch) */
+                              bbq_count_range_batch, bbq_search_range_batch - and the span search - bbq_search_spans_batch) */
 
 /* status codes */
 enum {
@@ -413,6 +413,34 @@ int bbq_count_range_batch(bbq_index *idx, const bbq_filter *f, int32_t n_queries
 int bbq_search_range_batch(bbq_index *idx, const bbq_filter *f, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
                            int32_t query_bits, int32_t sim, const float *thresholds, int64_t cap,
                            int64_t *out_offsets, int32_t *out_idx, float *out_score);
+
+/* ------------------------------------------------------------------------------------------
+ * Span search (DESIGN.md "Span search"): exact top-k over a few contiguous runs of rows that differ from query to query - a coarse
+ * quantizer's probed clusters in a store that keeps its rows cluster by cluster, one tenant's block per query, a time window.
+ * Query q's spans are spans[2 j], spans[2 j + 1] = begin, end (exclusive) for j in [span_offsets[q], span_offsets[q + 1]); its answer
+ * is what the reference loop (src/binaryQuantizationFormat.ts:349-411) returns when it visits exactly the rows of those spans,
+ * ascending, pushing (ord, f32 score) into a heap of min(k, L_q), L_q = the total length of q's spans - indices, score bits and order,
+ * ties and NaN scores included: the answer of bbq_search_ords_batch over the expanded list and of bbq_search_filtered_batch with a
+ * filter of the span union.  The scores are bit for bit those of bbq_score_rows; query_bits, sim and the multi-bit corners as there.
+ * Spans: 0 <= begin <= end <= bbq_index_size, ascending and disjoint within a query (end_j <= begin_{j+1}); empty spans and empty
+ * lists are allowed.  A violation is BBQ_ERR_INVALID_ARG and the message names the first offending (query, span) in call order; every
+ * list is checked on the host before the first launch: nothing is launched and nothing is written.
+ * out_idx / out_score [n_queries*k] (query q at offset q*k), out_n [n_queries], as bbq_search_batch.  k < 0: BBQ_ERR_NEGATIVE_K;
+ * k == 0 or L_q == 0: out_n[q] = 0 (out_n is written whenever the arguments are good); no upper limit on k; n_queries == 0: BBQ_OK,
+ * nothing is launched.
+ * out_status [n_queries] (may be NULL): 0 - the device selected the answer, 1 - the host ran the literal heap over the device's scores
+ * of all of q's span rows.  It is 0 EXACTLY when L_q > k, 1 <= k <= 4096, no visited row's score is NaN and no two of the k + 1 largest
+ * visited scores compare equal as floats (+0.0 == -0.0): the condition under which the heap provably returns the k best in descending
+ * order.  0 as well for a query with k == 0 or L_q == 0.
+ * Accepted handles as for filters and the range search: a single-device root index without a pilot replica; anything else is
+ * BBQ_ERR_UNSUPPORTED.  The call takes the device context's lock and runs on the auxiliary stream: it sees an append, an update or a
+ * compaction whole or not at all.  It writes no bbq_stats field.  A long call is worked through in sub-batches of at most 1024 queries
+ * and 64 MiB of scores (always at least one query).  A failed allocation: BBQ_ERR_OOM, nothing written.  Out of scope: a filter
+ * combined with spans, spans in any other order. */
+int bbq_search_spans_batch(bbq_index *idx, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
+                           int32_t query_bits, int32_t sim, int64_t k,
+                           const int64_t *span_offsets, const int64_t *spans,
+                           int32_t *out_idx, float *out_score, int64_t *out_n, uint8_t *out_status);
 
 /* ------------------------------------------------------------------------------------------
  * Sharded search (one process per GPU).  bbq_shard_scan sweeps THIS shard for n_queries queries and
