@@ -476,7 +476,9 @@ struct RangeArgs {
 
 // span search (bbq_span_kernels.hip): the k best rows among each query's own contiguous spans of rows.  The score pass leaves the f32
 // score of every visited row of query q at scores[q's base + the row's position in q's visiting order]; the select pass finds each
-// selected query's (k + 1)-th largest score key and writes the rows above it.
+// selected query's (k + 1)-th largest score key and writes the rows above it.  With a row filter (bbq_search_spans_filtered_batch) only
+// the accepted rows of the spans are visited: the positions are those of the COMPACTED visiting order, and the score pass leaves each
+// accepted row's ord beside its score, in a parallel array the select pass reads only for its k winners.
 constexpr int kSpanSelectMax = 4096;  // largest k the select pass takes
 // one workgroup of the score pass: the rows [row_lo, row_hi) of one span, cut by the host at tile-aligned kChunkRows-row steps, so
 // row_lo >> 6 == first_tile and row_hi <= (first_tile + kTilesPerChunk) * 64
@@ -484,7 +486,7 @@ struct SpanItem {
   uint32_t query;       // of the sub-batch
   uint32_t first_tile;  // wave w takes tile first_tile + w
   uint32_t row_lo, row_hi;
-  int64_t out;          // scores[out + (r - row_lo)] takes row r
+  int64_t out;          // scores[out + (r - row_lo)] takes row r; filtered: out = the position of the item's first accepted row
 };
 static_assert(sizeof(SpanItem) == 24, "SpanItem: staged in an array behind 8-byte data");
 struct SpanScoreArgs {
@@ -493,6 +495,8 @@ struct SpanScoreArgs {
   const QueryParams *qparams;  // [Q]
   const SpanItem *items;       // [grid.x] the launch's first item
   float *scores;               // the sub-batch's scores, query by query
+  const uint64_t *accept;      // filtered: the filter's words (word t = tile t, bit l = lane l); null otherwise
+  uint32_t *ords;              // filtered: ords[i] = the row whose score is scores[i]
 };
 // a non-empty span of a query in its visiting order: position `pos` of the query's scores is row `begin`
 struct SpanRun { int64_t pos, begin; };
@@ -500,7 +504,7 @@ struct SpanRun { int64_t pos, begin; };
 struct SpanQuery {
   int64_t score_off;  // its scores start at scores[score_off] ...
   int64_t len;        // ... and there are len > k of them
-  int64_t run_first;  // its runs: runs[run_first .. run_first + n_runs)
+  int64_t run_first;  // its runs: runs[run_first .. run_first + n_runs); a filtered query has none
   int32_t n_runs;
   int32_t pad;
 };
@@ -508,6 +512,7 @@ struct SpanSelectArgs {
   const float *scores;
   const SpanQuery *sel;   // [grid.x]
   const SpanRun *runs;
+  const uint32_t *ords;   // filtered: the row of every score (SpanScoreArgs::ords), runs is unused; null otherwise
   uint64_t *out;          // [grid.x][out_stride]: {rows above the cut | flags << 32}, the cut's f32 bits, then k entries if there are exactly k
   int32_t k;              // 1 .. kSpanSelectMax
   int32_t out_stride;     // >= k + 2

@@ -91,10 +91,12 @@ hipError_t launch_range_offsets(uint32_t *counts, uint32_t *nonempty, uint32_t *
 // longest non-empty-chunk list among them
 hipError_t launch_range_fill(const RangeArgs &a, int planes, int n_queries, int64_t max_nonempty, hipStream_t s);
 // span search (bbq_span_kernels.hip).  The f32 scores of the rows of n_items work items (a.items[0 .. n_items), at most
-// kGridWorkItemsMax / kChunkRows of them) -> a.scores; planes as launch_scan takes them
+// kGridWorkItemsMax / kChunkRows of them) -> a.scores; planes as launch_scan takes them.  With a.accept (a filter's words) only the
+// accepted rows, compacted, and each one's ord -> a.ords beside its score
 hipError_t launch_span_score(const SpanScoreArgs &a, int planes, int64_t n_items, hipStream_t s);
 // per selected query (a.sel[0 .. n_selected)): the exact (a.k + 1)-th largest of its scores, the number of rows above it and, when that
-// is a.k and no score is NaN, those rows as entries in any order -> the query's block of a.out
+// is a.k and no score is NaN, those rows as entries in any order -> the query's block of a.out.  With a.ords a row's ord is read from
+// there (the compacted scores of a filtered call), from a.runs otherwise
 hipError_t launch_span_select(const SpanSelectArgs &a, int n_selected, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);

@@ -1,4 +1,4 @@
-// bbq_span_kernels.hip - span search (gfx950): bbq_search_spans_batch.
+// bbq_span_kernels.hip - span search (gfx950): bbq_search_spans_batch, bbq_search_spans_filtered_batch.
 //
 // The k best rows among a few contiguous runs of rows that differ from query to query.  Two passes.  The score pass streams every span as
 // whole tiles - a work item is up to kChunkRows rows of one span of one query - and leaves the f32 score of each visited row at the row's
@@ -7,6 +7,9 @@
 // buffer, by a radix select over the scores in global memory otherwise - and writes the k rows above it when there are exactly k and no
 // score is NaN: the case in which the heap provably ends up with those rows whatever its history was (DESIGN.md "Exact top-k").  The host
 // sorts them, checks them for equal scores and replays the heap over the scores where the device could not prove the answer.
+// With a row filter (FILT / ORDS below) only the accepted rows of the spans are visited: the score pass compacts them - an accepted row's
+// score and ord go to its position among the query's accepted rows, a position computed from the filter's words alone - and the select
+// pass, unchanged over the compacted scores, takes the ords of its k winners from that parallel array.
 // Rows are scored with the sweep's own functions (bbq_kernel_common.h, bbq_scan_body.h): every score is bit for bit what the dense sweep
 // writes for that row.
 #include <hip/hip_runtime.h>
@@ -25,7 +28,11 @@ namespace {
 // whose tile holds no row of [row_lo, row_hi) loads nothing.  QB / W / SB as bbq_scan_kernel takes them; COMPACT: the corrections layout
 // of the index - every row's exact corrections come from the side array, as in the dense sweep.  The row's component sum comes from the
 // row_sums side array where the launch's view carries it and is counted otherwise - the same value either way.
-template <int QB, int W, int SB, bool COMPACT>
+// FILT: a.accept holds one word per tile, bit l = lane l.  The wave's rows are those of its filter word that lie in [row_lo, row_hi) - a
+// bit of the same tile outside the span counts nowhere - and a wave without one returns before any tile load.  An accepted row's position
+// is item.out + the item's accepted rows in the tiles in front of the wave's + the accepted rows of the tile below the lane: words read at
+// wave-uniform addresses and popcounts, no atomic, the same positions on every run.  Rejected lanes write nothing.
+template <int QB, int W, int SB, bool COMPACT, bool FILT>
 __global__ __launch_bounds__(kChunkRows) void bbq_span_score_kernel(const SpanScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NT = kChunkRows;
@@ -47,7 +54,19 @@ __global__ __launch_bounds__(kChunkRows) void bbq_span_score_kernel(const SpanSc
   const int64_t tile = (int64_t)it.first_tile + __builtin_amdgcn_readfirstlane(wave);
   if (tile * kTileRows >= (int64_t)it.row_hi) return;  // wave-uniform: no row of the item in this tile (row_hi <= n_rows: the tile exists otherwise)
   const int64_t row = tile * kTileRows + lane;
-  const bool valid = row >= (int64_t)it.row_lo && row < (int64_t)it.row_hi;
+  uint64_t mine = 0;    // FILT: the wave's accepted rows of the item, bit l = lane l, and how many the item has in front of this tile:
+  uint32_t before = 0;  // wave-uniform both, kept in scalar registers until the score is there
+  if constexpr (FILT) {
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const uint64_t from_lo = ~0ull << (it.row_lo & 63u);  // the lanes of the item's first tile at or behind row_lo
+    const int64_t left = (int64_t)it.row_hi - tile * kTileRows;  // > 0; every tile in front of this one lies below row_hi as a whole
+    mine = a.accept[tile] & (left < kTileRows ? (1ull << left) - 1ull : ~0ull);
+    if (wave_u == 0) mine &= from_lo;
+    if (mine == 0) return;  // wave-uniform: no accepted row of the item in this tile
+#pragma unroll
+    for (int t = 0; t < kTilesPerChunk - 1; ++t)
+      if (t < wave_u) before += (uint32_t)__popcll(a.accept[(int64_t)it.first_tile + t] & (t == 0 ? from_lo : ~0ull));
+  }
   const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
   const uint8_t *__restrict__ cr = tp + tile_corr_offset(w16);
   const bool resident = chunk_is_resident(tile / kTilesPerChunk, a.idx);
@@ -91,7 +110,15 @@ __global__ __launch_bounds__(kChunkRows) void bbq_span_score_kernel(const SpanSc
   if (COMPACT || !a.idx.geom.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
 
   const float s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
-  if (valid) a.scores[it.out + (row - (int64_t)it.row_lo)] = s32;
+  if constexpr (FILT) {
+    if ((mine >> lane) & 1ull) {
+      const int64_t out = it.out + before + __popcll(mine & ((1ull << lane) - 1ull));
+      a.scores[out] = s32;
+      a.ords[out] = (uint32_t)row;
+    }
+  } else {
+    if (row >= (int64_t)it.row_lo && row < (int64_t)it.row_hi) a.scores[it.out + (row - (int64_t)it.row_lo)] = s32;
+  }
 }
 
 template <int QB, int W, int SB>
@@ -99,8 +126,14 @@ hipError_t launch_span_score_t(const SpanScoreArgs &a, unsigned n_items, hipStre
   const int w16 = W > 0 ? W : a.idx.geom.w16;
   const size_t smem = (size_t)w16 * query_units_per_chunk(QB, SB) * 16;
   dim3 grid(n_items, 1, 1), block(kChunkRows, 1, 1);
-  if (a.idx.geom.layout == kLayoutCompact) hipLaunchKernelGGL((bbq_span_score_kernel<QB, W, SB, true>), grid, block, smem, s, a);
-  else hipLaunchKernelGGL((bbq_span_score_kernel<QB, W, SB, false>), grid, block, smem, s, a);
+  const bool compact = a.idx.geom.layout == kLayoutCompact;
+  if (a.accept) {
+    if (compact) hipLaunchKernelGGL((bbq_span_score_kernel<QB, W, SB, true, true>), grid, block, smem, s, a);
+    else hipLaunchKernelGGL((bbq_span_score_kernel<QB, W, SB, false, true>), grid, block, smem, s, a);
+  } else {
+    if (compact) hipLaunchKernelGGL((bbq_span_score_kernel<QB, W, SB, true, false>), grid, block, smem, s, a);
+    else hipLaunchKernelGGL((bbq_span_score_kernel<QB, W, SB, false, false>), grid, block, smem, s, a);
+  }
   return hipGetLastError();
 }
 
@@ -218,7 +251,9 @@ __device__ __forceinline__ int64_t span_ord(const SpanRun *__restrict__ runs, in
 
 // one kFinalizeThreads workgroup per selected query (the host selects those with len > k and 1 <= k <= kSpanSelectMax).  Leaves in the
 // query's block of a.out: word 0 = {rows whose key lies above the cut | flags << 32}, word 1 = the cut's f32 score bits, and - when
-// exactly k rows lie above the cut and no score is NaN - those k rows as entries, in any order.
+// exactly k rows lie above the cut and no score is NaN - those k rows as entries, in any order.  ORDS: the scores are the compacted ones
+// of a filtered query and a winner's ord is a.ords' at its position; the runs are not read.
+template <bool ORDS>
 __global__ __launch_bounds__(kFinalizeThreads) void bbq_span_select_kernel(const SpanSelectArgs a) {
   constexpr int NT = kFinalizeThreads;
   __shared__ uint32_t s_keys[kFinalizeKeyCap];
@@ -297,7 +332,12 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_span_select_kernel(const
       if (lane == __ffsll((long long)m) - 1) base = atomicAdd(&s_red[2], (uint32_t)__popcll(m));
       base = (uint32_t)__builtin_amdgcn_readlane((int)base, __ffsll((long long)m) - 1);
       const uint32_t slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      if (in && slot < k) out[2 + slot] = candidate_entry(span_ord(a.runs + sq.run_first, sq.n_runs, i), sv[u]);  // (slot < k: there are `above` of them)
+      if (in && slot < k) {  // (slot < k: there are `above` of them)
+        int64_t ord;
+        if constexpr (ORDS) ord = (int64_t)a.ords[sq.score_off + i];
+        else ord = span_ord(a.runs + sq.run_first, sq.n_runs, i);
+        out[2 + slot] = candidate_entry(ord, sv[u]);
+      }
     }
   }
 }
@@ -306,6 +346,7 @@ __global__ __launch_bounds__(kFinalizeThreads) void bbq_span_select_kernel(const
 
 hipError_t launch_span_score(const SpanScoreArgs &a, int planes, int64_t n_items, hipStream_t s) {
   if (n_items <= 0) return hipSuccess;
+  if (a.accept && !a.ords) return hipErrorInvalidValue;
   if ((uint64_t)n_items * kChunkRows > kGridWorkItemsMax) return hipErrorInvalidValue;  // grid.x in work-items
   const unsigned n = (unsigned)n_items;
   switch (a.idx.geom.store_bits) {
@@ -326,7 +367,8 @@ hipError_t launch_span_score(const SpanScoreArgs &a, int planes, int64_t n_items
 hipError_t launch_span_select(const SpanSelectArgs &a, int n_selected, hipStream_t s) {
   if (n_selected <= 0) return hipSuccess;
   if (a.k < 1 || a.k > kSpanSelectMax || a.out_stride < a.k + 2) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(bbq_span_select_kernel, dim3((unsigned)n_selected, 1, 1), dim3(kFinalizeThreads, 1, 1), 0, s, a);
+  if (a.ords) hipLaunchKernelGGL(bbq_span_select_kernel<true>, dim3((unsigned)n_selected, 1, 1), dim3(kFinalizeThreads, 1, 1), 0, s, a);
+  else hipLaunchKernelGGL(bbq_span_select_kernel<false>, dim3((unsigned)n_selected, 1, 1), dim3(kFinalizeThreads, 1, 1), 0, s, a);
   return hipGetLastError();
 }
 

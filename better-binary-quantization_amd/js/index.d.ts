@@ -76,6 +76,8 @@ export declare class BinaryQuantizationFormat {
   searchNearestNeighborsInOrds(query: Float32Array, targetVectors: BinarizedByteVectorValues, ords: Int32Array | number[], k: number): Array<{ index: number; score: number }>;
   /** extension: searchNearestNeighbors over the rows of `spans` - [begin, end) pairs, end exclusive, ascending and disjoint, empty spans and an empty list allowed; the spans may differ from query to query and the device selects the k best itself */
   searchNearestNeighborsInSpans(query: Float32Array, targetVectors: BinarizedByteVectorValues, spans: Array<[number, number]> | Float64Array, k: number): Array<{ index: number; score: number }>;
+  /** extension: searchNearestNeighborsInSpans over the rows of the spans that `filter` accepts; the heap holds min(k, accepted rows visited) */
+  searchNearestNeighborsInSpansFiltered(query: Float32Array, targetVectors: BinarizedByteVectorValues, spans: Array<[number, number]> | Float64Array, filter: RowFilter, k: number): Array<{ index: number; score: number }>;
   /** extension: every row (of options.rowFilter, if given) whose stored f32 score is >= threshold, in ascending ord or, with order 'score', by descending score (ties in ascending ord); a NaN score is in no answer, a NaN threshold throws */
   searchRange(query: Float32Array, targetVectors: BinarizedByteVectorValues, threshold: number, options?: { rowFilter?: RowFilter | null; order?: 'ord' | 'score' }): Array<{ index: number; score: number }>;
   /** extension: the same for many queries per call; one filter serves all of them */

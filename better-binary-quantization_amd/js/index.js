@@ -729,6 +729,32 @@ class BinaryQuantizationFormat {
   }
 
   /**
+   * extension (not in the reference): searchNearestNeighborsInSpans over the rows `filter` (createRowFilter) accepts - what the reference's
+   * loop (:349-411) returns when it visits exactly the accepted rows of the spans, ascending, with a heap of min(k, accepted rows visited):
+   * deleted rows, one tenant's rows or a metadata predicate in a store that keeps its rows cluster by cluster.  Same validation and
+   * messages as searchNearestNeighborsInSpans; a filter of another index or of a size the index no longer has throws the library's
+   * message.
+   */
+  searchNearestNeighborsInSpansFiltered(queryVector, targetVectors, spans, filter, k) {
+    if (!queryVector) throw new Error('查询向量不能为空');
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (!spans) throw new Error('行区间不能为空');
+    if (!(filter instanceof RowFilter)) throw new Error('searchNearestNeighborsInSpansFiltered needs createRowFilter(targetVectors, accept)');
+    if (k < 0) throw new Error('k值不能为负数');
+    if (queryVector.length !== targetVectors.dimension()) throw new Error('查询向量维度与目标向量维度不匹配');
+    const flat = this._flatQueries([queryVector], targetVectors, k);
+    if (flat === null) return [];
+    const q = this.quantizer, sim = simOrdinal(q.similarityFunction), qb = this.config.queryBits;
+    const tNative = process.hrtime.bigint();
+    const qz = native.quantizeQueries(flat, 1, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, 1);
+    const r = native.searchSpansFiltered(targetVectors._deviceIndex(), filter._handle(), qz.quantized, qz.corrections, qb, sim, k, spansAsFloat64(spans));
+    hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
+    const n = r.indices.length, res = new Array(n);
+    for (let j = 0; j < n; j++) res[j] = { index: r.indices[j], score: r.scores[j] };
+    return res;
+  }
+
+  /**
    * extension (not in the reference): every row whose stored f32 score is >= threshold - what the reference's loop (:349-411) would collect
    * if it kept every visited ord at or above the threshold and skipped the heap.  options.rowFilter: a RowFilter (createRowFilter) - only the
    * rows it accepts; options.order: 'ord' (default, ascending ord) or 'score' (descending score, ties in ascending ord).  A row whose

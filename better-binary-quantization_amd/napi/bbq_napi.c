@@ -699,18 +699,12 @@ static napi_value SearchOrds(napi_env env, napi_callback_info info) {
   return o;
 }
 
-/* searchSpans(handle, qquant, qcorr, queryBits, sim, k, spans Float64Array [2 m] = begin, end (exclusive) of each span) ->
- * {indices Int32Array, scores Float32Array, status}: the reference's loop over the rows of the spans, ascending (bbq_search_spans_batch
- * with one query); status 0: the device selected the answer, 1: the host replayed the heap */
-static napi_value SearchSpans(napi_env env, napi_callback_info info) {
-  napi_value a[7];
-  if (!get_args(env, info, 7, a)) return NULL;
-  bbq_index *ix = unbox(env, a[0]);
-  if (!ix) return NULL;
+/* what searchSpans and searchSpansFiltered share: a = qquant, qcorr, queryBits, sim, k, spans; flt = the row filter, or NULL: every row */
+static napi_value search_spans(napi_env env, bbq_index *ix, const bbq_filter *flt, const napi_value *a) {
   void *qq, *qc, *sp; size_t ql, cl, n2;
   int64_t qb, sim, k;
-  if (!get_typed(env, a[1], napi_uint8_array, &qq, &ql) || !get_typed(env, a[2], napi_float64_array, &qc, &cl) ||
-      !get_i64(env, a[3], &qb) || !get_i64(env, a[4], &sim) || !get_i64(env, a[5], &k) || !get_typed(env, a[6], napi_float64_array, &sp, &n2)) return NULL;
+  if (!get_typed(env, a[0], napi_uint8_array, &qq, &ql) || !get_typed(env, a[1], napi_float64_array, &qc, &cl) ||
+      !get_i64(env, a[2], &qb) || !get_i64(env, a[3], &sim) || !get_i64(env, a[4], &k) || !get_typed(env, a[5], napi_float64_array, &sp, &n2)) return NULL;
   if (ql != (size_t)bbq_index_dimension(ix) || cl != 4) { napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return NULL; }
   if (k < 0) { napi_throw_error(env, "BBQ7", "k值不能为负数"); return NULL; }
   if (n2 % 2 != 0) { napi_throw_range_error(env, NULL, "bbq_napi: spans are pairs of begin and end"); return NULL; }
@@ -732,7 +726,8 @@ static napi_value SearchSpans(napi_env env, napi_callback_info info) {
   const int64_t offsets[2] = {0, (int64_t)(n2 / 2)};
   int64_t cnt = 0;
   uint8_t status = 0;
-  int rc = bbq_search_spans_batch(ix, 1, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff, offsets, s64, idx, sc, &cnt, &status);
+  int rc = flt ? bbq_search_spans_filtered_batch(ix, flt, 1, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff, offsets, s64, idx, sc, &cnt, &status)
+               : bbq_search_spans_batch(ix, 1, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff, offsets, s64, idx, sc, &cnt, &status);
   free(s64);
   if (rc != BBQ_OK) { free(idx); free(sc); return throw_bbq(env, rc); }
   void *oi, *os;
@@ -746,6 +741,29 @@ static napi_value SearchSpans(napi_env env, napi_callback_info info) {
   NAPI_CALL(env, napi_create_int32(env, (int32_t)status, &st));
   set_prop(env, o, "indices", ti); set_prop(env, o, "scores", ts); set_prop(env, o, "status", st);
   return o;
+}
+
+/* searchSpans(handle, qquant, qcorr, queryBits, sim, k, spans Float64Array [2 m] = begin, end (exclusive) of each span) ->
+ * {indices Int32Array, scores Float32Array, status}: the reference's loop over the rows of the spans, ascending (bbq_search_spans_batch
+ * with one query); status 0: the device selected the answer, 1: the host replayed the heap */
+static napi_value SearchSpans(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (!get_args(env, info, 7, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  return search_spans(env, ix, NULL, a + 1);
+}
+
+/* searchSpansFiltered(handle, filter handle, qquant, qcorr, queryBits, sim, k, spans) -> as searchSpans, over the rows of the spans that
+ * the filter accepts (bbq_search_spans_filtered_batch with one query) */
+static napi_value SearchSpansFiltered(napi_env env, napi_callback_info info) {
+  napi_value a[8];
+  if (!get_args(env, info, 8, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  const bbq_filter *flt = unbox_filter(env, a[1], "bbq_search_spans_filtered_batch");
+  if (!flt) return NULL;
+  return search_spans(env, ix, flt, a + 2);
 }
 
 /* searchRange(handle, filter handle | null, qquant, qcorr, queryBits, sim, threshold) -> {indices Int32Array, scores Float32Array}: every row (of
@@ -1116,6 +1134,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"searchOrds", NULL, SearchOrds, NULL, NULL, NULL, napi_default, NULL},
       {"searchRange", NULL, SearchRange, NULL, NULL, NULL, napi_default, NULL},
       {"searchSpans", NULL, SearchSpans, NULL, NULL, NULL, napi_default, NULL},
+      {"searchSpansFiltered", NULL, SearchSpansFiltered, NULL, NULL, NULL, napi_default, NULL},
       {"setOption", NULL, SetOption, NULL, NULL, NULL, napi_default, NULL},
       {"stats", NULL, Stats, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsCreate", NULL, VectorsCreate, NULL, NULL, NULL, napi_default, NULL},

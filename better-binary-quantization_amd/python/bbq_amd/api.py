@@ -240,6 +240,16 @@ class BinaryQuantizationFormat:
             raise Exception("行区间不能为空")
         return self._search(queryVector, targetVectors, k, None, None, np.asarray(spans, np.int64).reshape(-1, 2))
 
+    def searchNearestNeighborsInSpansFiltered(self, queryVector, targetVectors, spans, rowFilter, k):
+        """extension: searchNearestNeighborsInSpans over the rows `rowFilter` (createRowFilter) accepts - what the reference's loop
+        returns when it visits exactly the accepted rows of the spans, ascending, with a heap of min(k, accepted rows visited): deleted
+        rows, one tenant's rows or a metadata predicate in a store that keeps its rows cluster by cluster."""
+        if spans is None:
+            raise Exception("行区间不能为空")
+        if rowFilter is None:
+            raise Exception("行过滤器不能为空")
+        return self._search(queryVector, targetVectors, k, rowFilter, None, np.asarray(spans, np.int64).reshape(-1, 2))
+
     def searchRange(self, queryVector, targetVectors, threshold, rowFilter=None, order="ord"):
         """extension: every row (of `rowFilter`, createRowFilter, if given) whose stored f32 score is >= threshold - what the
         reference's loop would collect if it kept every visited ord at or above the threshold and skipped the heap - as
@@ -303,7 +313,9 @@ class BinaryQuantizationFormat:
         try:
             qq, qc = capi.quantize_query(queryVector, targetVectors.getCentroid(), sim, self._config["queryBits"], self._lambda,
                                          self._iters, search_path=True)
-            if spans is not None:
+            if spans is not None and rowFilter is not None:
+                idx, sc = targetVectors._device().search_spans_filtered_batch(qq[None, :], qc[None, :], self._config["queryBits"], sim, k, [spans], rowFilter)[0][0]
+            elif spans is not None:
                 idx, sc = targetVectors._device().search_spans_batch(qq[None, :], qc[None, :], self._config["queryBits"], sim, k, [spans])[0][0]
             elif ords is not None:
                 idx, sc = targetVectors._device().search_ords_batch(qq[None, :], qc[None, :], self._config["queryBits"], sim, k, [ords])[0]

@@ -32,7 +32,7 @@ SYMBOLS = [
     "bbq_index_update_rows", "bbq_index_update", "bbq_vectors_update", "bbq_update_winners",
     "bbq_score_ords", "bbq_score_ords_batch", "bbq_search_ords_batch",
     "bbq_range_key", "bbq_count_range_batch", "bbq_search_range_batch",
-    "bbq_search_spans_batch",
+    "bbq_search_spans_batch", "bbq_search_spans_filtered_batch",
 ]
 
 
@@ -112,6 +112,7 @@ def lib():
     L.bbq_count_range_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
     L.bbq_search_range_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, i64, vp, vp, vp]
     L.bbq_search_spans_batch.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp]
+    L.bbq_search_spans_filtered_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp]
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_create_rows.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_destroy.argtypes = [vp]
@@ -574,6 +575,23 @@ class Index:
         status = np.zeros(nq, np.uint8)
         _chk(lib().bbq_search_spans_batch(self._h, nq, _ptr(qq), _ptr(qc), query_bits, sim, k, _ptr(off), _ptr(sp), _ptr(idx), _ptr(sc), _ptr(cnt),
                                          _ptr(status)))
+        return [(idx[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)], status
+
+    def search_spans_filtered_batch(self, qquant, qcorr, query_bits, sim, k, spans, flt):
+        """bbq_search_spans_filtered_batch: search_spans_batch over the rows of the spans that `flt` (a Filter of this index) accepts;
+        one filter serves every query of the call, flt=None accepts every row.  Returns what search_spans_batch returns; the status
+        rule counts accepted rows."""
+        qq = np.ascontiguousarray(qquant, np.uint8)
+        qc = np.ascontiguousarray(qcorr, np.float64)
+        nq = qq.shape[0]
+        off, sp = _spans(spans, nq)
+        kk = max(int(k), 0)
+        idx = np.zeros((nq, kk), np.int32)
+        sc = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.int64)
+        status = np.zeros(nq, np.uint8)
+        _chk(lib().bbq_search_spans_filtered_batch(self._h, flt._h if flt is not None else None, nq, _ptr(qq), _ptr(qc), query_bits, sim, k,
+                                                  _ptr(off), _ptr(sp), _ptr(idx), _ptr(sc), _ptr(cnt), _ptr(status)))
         return [(idx[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)], status
 
     def _range_args(self, qquant, qcorr, thresholds):

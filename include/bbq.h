@@ -37,7 +37,8 @@ extern "C" {
                               and the compaction - bbq_index_compact, bbq_index_remove_rows, bbq_vectors_compact, bbq_filter_kept_rows - and the
                               in-place updates - bbq_index_update_rows, bbq_index_update, bbq_vectors_update, bbq_update_winners - and the scoring of chosen rows -
                               bbq_score_ords, bbq_score_ords_batch, bbq_search_ords_batch - and the range search - bbq_range_key,
-                              bbq_count_range_batch, bbq_search_range_batch - and the span search - bbq_search_spans_batch) */
+                              bbq_count_range_batch, bbq_search_range_batch - and the span search - bbq_search_spans_batch,
+                              bbq_search_spans_filtered_batch) */
 
 /* status codes */
 enum {
@@ -435,12 +436,33 @@ int bbq_search_range_batch(bbq_index *idx, const bbq_filter *f, int32_t n_querie
  * Accepted handles as for filters and the range search: a single-device root index without a pilot replica; anything else is
  * BBQ_ERR_UNSUPPORTED.  The call takes the device context's lock and runs on the auxiliary stream: it sees an append, an update or a
  * compaction whole or not at all.  It writes no bbq_stats field.  A long call is worked through in sub-batches of at most 1024 queries
- * and 64 MiB of scores (always at least one query).  A failed allocation: BBQ_ERR_OOM, nothing written.  Out of scope: a filter
- * combined with spans, spans in any other order. */
+ * and 64 MiB of scores (always at least one query).  A failed allocation: BBQ_ERR_OOM, nothing written.  A filter combined with
+ * spans: bbq_search_spans_filtered_batch below.  Out of scope: spans in any other order. */
 int bbq_search_spans_batch(bbq_index *idx, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
                            int32_t query_bits, int32_t sim, int64_t k,
                            const int64_t *span_offsets, const int64_t *spans,
                            int32_t *out_idx, float *out_score, int64_t *out_n, uint8_t *out_status);
+/* Filtered span search (DESIGN.md "Filtered span search"): the span search over the rows a filter accepts - deletions, one tenant's
+ * rows or a metadata predicate in a store that keeps its rows cluster by cluster.  Query q's answer is what the reference loop returns
+ * when it visits exactly the rows of q's spans that f accepts, ascending, pushing (original ord, f32 score) into a heap of
+ * min(k, A_q), A_q = the number of accepted rows in q's spans - indices, score bits and order, ties and NaN scores included: the answer
+ * of bbq_search_filtered_batch with a filter of (f AND the span union) and of bbq_search_ords_batch over the accepted ords of the spans;
+ * the scores are those of bbq_score_rows.
+ * f: a filter of this index, checked as bbq_search_filtered_batch checks it (another size - a filter made before an append, a removal
+ * or a compaction - or another device: BBQ_ERR_INVALID_ARG); NULL = all rows: the call is bbq_search_spans_batch, same answers and same
+ * statuses.  Spans, offsets, k, n_queries == 0 and null arguments are checked as there, the messages carry this function's name and
+ * name the first offending (query, span).  Every check runs under the context's lock before the first launch: nothing is launched and
+ * nothing is written.  k == 0 or A_q == 0: out_n[q] = 0, status 0.
+ * out_status follows the span search's rule with the accepted rows in place of the visited rows: 0 EXACTLY when A_q > k,
+ * 1 <= k <= 4096, no accepted visited row's score is NaN and no two of the k + 1 largest accepted scores compare equal as floats.  A
+ * NaN score on a rejected row changes nothing.
+ * Handles, lock, stream and bbq_stats as for the span search.  Sub-batches hold at most 1024 queries and 64 MiB of scratch, 8 bytes per
+ * accepted row (its score and its ord), always at least one query; a work item without an accepted row is never launched.  A failed
+ * allocation: BBQ_ERR_OOM, nothing written.  Out of scope: a filter per query, spans in any other order. */
+int bbq_search_spans_filtered_batch(bbq_index *idx, const bbq_filter *f, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
+                                    int32_t query_bits, int32_t sim, int64_t k,
+                                    const int64_t *span_offsets, const int64_t *spans,
+                                    int32_t *out_idx, float *out_score, int64_t *out_n, uint8_t *out_status);
 
 /* ------------------------------------------------------------------------------------------
  * Sharded search (one process per GPU).  bbq_shard_scan sweeps THIS shard for n_queries queries and
