@@ -518,8 +518,42 @@ struct SpanSelectArgs {
   int32_t out_stride;     // >= k + 2
 };
 
+// grouped search (bbq_group_kernels.hip): the k best GROUPS of rows - contiguous runs, a document's chunks - each through its best
+// accepted row, its representative.  The score pass sweeps every chunk for every query of a sub-batch and leaves each live group's
+// representative as a packed key in rep[q][slot]; the unpack pass turns the keys into the parallel scores / ords arrays the span
+// search's select pass takes.  The tables are those of one group set (bbq_groups, bbq_group.cpp), built once at its creation:
+//   starts[t]       bit l = row 64 t + l is the first row of a non-empty group (an empty group has no row and no bit); the row behind
+//                   the last one counts as a start too, and so does row 0 of the tile behind the last one (starts[tiles] = 1): every
+//                   group ends in front of a set bit
+//   first_group[t]  the group row 64 t lies in, counted over the non-empty groups
+//   slot[g]         of non-empty group g: its rank among the live groups - those with an accepted row - or -1
+struct GroupScoreArgs {
+  IndexView idx;
+  const uint4 *qplanes;         // [Q][w16][QU] staged query data, as ScanArgs::qplanes
+  const QueryParams *qparams;   // [Q]
+  const uint64_t *accept;       // the accept words of the group set's filter (word t = tile t, bit l = lane l); null: every row
+  const uint64_t *starts;       // [tiles + 1]
+  const uint32_t *first_group;  // [tiles + 1]
+  const int32_t *slot;          // [non-empty groups + 1]
+  unsigned long long *rep;      // [Q][live] cleared to 0 before the launch: only ever raised (group_key)
+  int64_t live;
+  int32_t n_chunks;             // chunks of idx: the grid's x extent follows from it (sweep_grid_x)
+  int32_t n_queries;
+  int32_t l2_shift;             // the workgroup -> (chunk, query) map, as ScanArgs::l2_shift: the launch caps it (sweep_shift_for)
+  int32_t pad;
+};
+// a row's packed key: larger = the better representative.  A NaN score ranks below every number, numbers in the order of their score
+// keys, and among equals the lowest ord wins.  Never 0 for a row of an index of at most kGroupMaxRows rows: 0 = nothing seen
+constexpr int64_t kGroupMaxRows = 0x7fffffff;
+__host__ __device__ inline unsigned long long group_key(uint32_t score_bits, bool is_nan, uint32_t ord) {
+  return ((unsigned long long)(is_nan ? 0u : key_of_bits(score_bits)) << 32) | (0x7fffffffu - ord);
+}
+constexpr uint32_t kGroupNaNBits = 0x7fc00000u;  // the score a representative with key 0 is unpacked to: a quiet NaN
+__host__ __device__ inline uint32_t group_key_score_bits(unsigned long long k) { return (uint32_t)(k >> 32) ? bits_of_key((uint32_t)(k >> 32)) : kGroupNaNBits; }
+__host__ __device__ inline uint32_t group_key_ord(unsigned long long k) { return 0x7fffffffu - (uint32_t)k; }
+
 constexpr int kFinalizeThreads = 1024;
-constexpr int kFinalizeJobs = 4096;      // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)
+constexpr int kFinalizeJobs = 4096;     // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)
 constexpr int kFinalizeKeyCap = 12288;   // LDS key buffer of the finalize kernel (new keys + running top-k)
 constexpr int kFinalizeCountCap = 24576; // chunk counters one launch stages in LDS, 16 bits each (12.6 M rows per segment; longer segments read them from memory)
 constexpr int kFinalizeLdsBytes = (kFinalizeKeyCap + 3 * kFinalizeJobs + 512 + 16 + 16) * 4 + kFinalizeCountCap * 2;  // 146 KB of the CU's 160 KB

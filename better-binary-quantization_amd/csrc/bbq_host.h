@@ -12,6 +12,8 @@
 //   bbq_build.cpp    quantizeVectors on the device (bbq_index_build)
 //   bbq_gather.cpp   scoring and ranking chosen rows (bbq_score_ords*, bbq_search_ords_batch)
 //   bbq_range.cpp    range search: every row at or above a threshold (bbq_range_key, bbq_count_range_batch, bbq_search_range_batch)
+//   bbq_span.cpp     span search: the k best rows of per-query row spans (bbq_search_spans_batch, bbq_search_spans_filtered_batch)
+//   bbq_group.cpp    grouped search: the k best groups of rows by their best row (bbq_groups_*, bbq_search_grouped_batch)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
 // bbq_entry.h is the codec of the 64-bit entries, keys and answer headers; bbq_workqueue.h the host threads' job queue.
@@ -137,7 +139,8 @@ struct DeviceCtx {
   DevBuf<uint32_t> d_aux_flags;
   DevBuf<uint8_t> d_gather;          // grow-only scratch of bbq_score_ords* (bbq_gather.cpp): one launch's offsets, queries, ords and outputs
   DevBuf<uint8_t> d_range;           // grow-only scratch of a range search's sub-batch (bbq_range.cpp): queries, thresholds, per-chunk counts and lists
-  DevBuf<uint8_t> d_span;            // grow-only scratch of a span search's sub-batch (bbq_span.cpp): queries, span tables, work items, answer blocks, scores
+  DevBuf<uint8_t> d_span;            // grow-only scratch of a span search's sub-batch (bbq_span.cpp): queries, span tables, work items, answer blocks, scores;
+                                     // and of a grouped search's (bbq_group.cpp): queries, answer blocks, the representatives' keys, scores and ords
   int last_big_slot = -1;             // slot whose ev_big marks the end of the most recently enqueued big sweep
   // latency path (bbq_latency_kernels.hip): the answer of a single-query call lands in mapped, coherent host memory and the host
   // polls a sequence word behind it: [0] sequence, [8 ..) header + entries
@@ -220,6 +223,8 @@ struct bbq_index {
                           // 0 never, 1 wherever the array exists, -1: row_sums_for_launch()'s choice (bbq_core.cpp)
   int opt_digit_planes = -1;  // a 4-plane query against 1-bit rows is swept in three ternary digit planes wherever the sweep reads the row sums
                               // and has a digit twin: 0 never, 1 and -1 wherever it can (digit_planes_for_call, bbq_core.cpp)
+  int opt_group_scratch_mb = 256;  // MiB of scratch a grouped search's sub-batch may take for its representatives, 16 B per live group and
+                                   // query (bbq_group.cpp): as many queries per score launch as fit, at least one
   int opt_fast_bound = 1;  // 1: the compact layout's score bound in f32 against the threshold's z image wherever the query's f32 images allow it
                            // (fast_bound_images, bbq_query.cpp); 0: always the f64 bound.  The answers are the same either way
   int opt_latency_presample = 1;  // ... and on large indexes get their threshold from per-wave top keys of a prefix (two small launches) instead of two scan / finalize pairs

@@ -270,6 +270,7 @@ int bbq_set_option(bbq_index *ix, const char *name, int64_t v) {
   else if (n == "l2_share" && (v == -1 || (v >= 1 && v <= 32 && (v & (v - 1)) == 0))) ix->opt_l2_share = (int)v;
   else if (n == "fast_bound" && (v == 0 || v == 1)) ix->opt_fast_bound = (int)v;
   else if (n == "row_sums" && v >= -1 && v <= 1) ix->opt_row_sums = (int)v;
+  else if (n == "group_scratch_mb" && v >= 1 && v <= 8192) ix->opt_group_scratch_mb = (int)v;
   else if (n == "digit_planes" && v >= -1 && v <= 1) ix->opt_digit_planes = (int)v;
   else if (n == "replay_threads" && v >= 1 && v <= 256) ix->opt_replay_threads = (int)v;
   else if (n == "force_dense" && (v == 0 || v == 1)) ix->opt_force_dense = (int)v;

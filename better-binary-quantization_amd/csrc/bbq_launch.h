@@ -1,6 +1,6 @@
 // bbq_launch.h - host-callable launch wrappers of every kernel file: the sweeps, finalize and pack (bbq_kernels.hip, bbq_filter_kernels.hip,
 // bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip), the rerank (bbq_rerank_kernels.hip), the scoring of chosen rows (bbq_gather_kernels.hip)
-// the range search (bbq_range_kernels.hip) and the span search (bbq_span_kernels.hip)
+// the range search (bbq_range_kernels.hip), the span search (bbq_span_kernels.hip) and the grouped search (bbq_group_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbq_device.h"
@@ -98,6 +98,12 @@ hipError_t launch_span_score(const SpanScoreArgs &a, int planes, int64_t n_items
 // is a.k and no score is NaN, those rows as entries in any order -> the query's block of a.out.  With a.ords a row's ord is read from
 // there (the compacted scores of a filtered call), from a.runs otherwise
 hipError_t launch_span_select(const SpanSelectArgs &a, int n_selected, hipStream_t s);
+// grouped search (bbq_group_kernels.hip).  Every chunk of a.idx for each of a.n_queries queries (<= 65535): the packed key of every live
+// group's best accepted row -> a.rep[q][slot], which the caller has cleared; planes as launch_scan takes them.  At most two global
+// atomics per workgroup - a max, so the result does not depend on their order
+hipError_t launch_group_score(const GroupScoreArgs &a, int planes, hipStream_t s);
+// rep[i] -> scores[i] (key 0: a quiet NaN), ords[i] for the n packed keys of a sub-batch
+hipError_t launch_group_unpack(const unsigned long long *rep, float *scores, uint32_t *ords, int64_t n, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 // staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place

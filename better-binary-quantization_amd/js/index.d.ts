@@ -78,6 +78,8 @@ export declare class BinaryQuantizationFormat {
   searchNearestNeighborsInSpans(query: Float32Array, targetVectors: BinarizedByteVectorValues, spans: Array<[number, number]> | Float64Array, k: number): Array<{ index: number; score: number }>;
   /** extension: searchNearestNeighborsInSpans over the rows of the spans that `filter` accepts; the heap holds min(k, accepted rows visited) */
   searchNearestNeighborsInSpansFiltered(query: Float32Array, targetVectors: BinarizedByteVectorValues, spans: Array<[number, number]> | Float64Array, filter: RowFilter, k: number): Array<{ index: number; score: number }>;
+  /** extension: the k best groups of `groups` (createRowGroups), each through its best accepted row - the reference's loop over each live group's best row, ascending, with a heap of min(k, live groups) */
+  searchNearestNeighborsGrouped(query: Float32Array, targetVectors: BinarizedByteVectorValues, groups: RowGroups, k: number): Array<{ index: number; score: number; group: number }>;
   /** extension: every row (of options.rowFilter, if given) whose stored f32 score is >= threshold, in ascending ord or, with order 'score', by descending score (ties in ascending ord); a NaN score is in no answer, a NaN threshold throws */
   searchRange(query: Float32Array, targetVectors: BinarizedByteVectorValues, threshold: number, options?: { rowFilter?: RowFilter | null; order?: 'ord' | 'score' }): Array<{ index: number; score: number }>;
   /** extension: the same for many queries per call; one filter serves all of them */
@@ -136,6 +138,16 @@ export declare class RowFilter {
   dispose(): void;
 }
 export declare function createRowFilter(targetVectors: BinarizedByteVectorValues, accept: Uint8Array | Int32Array | number[] | ((ord: number) => boolean)): RowFilter;
+/** extension: the groups of the rows of targetVectors - group g is the rows [offsets[g], offsets[g + 1]) - resident on its device; `filter` says which rows exist */
+export declare class RowGroups {
+  constructor(targetVectors: BinarizedByteVectorValues, offsets: number[] | Float64Array, filter?: RowFilter | null);
+  /** the number of groups, empty ones included */
+  readonly count: number;
+  /** the groups with at least one accepted row */
+  readonly live: number;
+  dispose(): void;
+}
+export declare function createRowGroups(targetVectors: BinarizedByteVectorValues, offsets: number[] | Float64Array, filter?: RowFilter | null): RowGroups;
 export declare function getOversampledTopKWithHeap(query: Float32Array, quantizedVectors: any, vectors: Float32Array[] | DeviceVectors, k: number, oversampleFactor: number, format: BinaryQuantizationFormat): TopKCandidate[];
 export declare function getOversampledTopKWithSort(query: Float32Array, quantizedVectors: any, vectors: Float32Array[] | DeviceVectors, k: number, oversampleFactor: number, format: BinaryQuantizationFormat): TopKCandidate[];
 /** extension: the whole recipe for many queries in one native call */

@@ -755,6 +755,30 @@ class BinaryQuantizationFormat {
   }
 
   /**
+   * extension (not in the reference): the k best GROUPS of `groups` (createRowGroups) - documents held as runs of chunk rows - each
+   * through its best accepted row: what the reference's loop (:349-411) returns when it visits exactly each live group's best row,
+   * ascending, with a heap of min(k, live groups) (libbbq bbq_search_grouped_batch).  Returns [{index, score, group}].  A group set of
+   * another index or of a size the index no longer has throws the library's message.
+   */
+  searchNearestNeighborsGrouped(queryVector, targetVectors, groups, k) {
+    if (!queryVector) throw new Error('查询向量不能为空');
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (!(groups instanceof RowGroups)) throw new Error('searchNearestNeighborsGrouped needs createRowGroups(targetVectors, offsets)');
+    if (k < 0) throw new Error('k值不能为负数');
+    if (queryVector.length !== targetVectors.dimension()) throw new Error('查询向量维度与目标向量维度不匹配');
+    const flat = this._flatQueries([queryVector], targetVectors, k);
+    if (flat === null) return [];
+    const q = this.quantizer, sim = simOrdinal(q.similarityFunction), qb = this.config.queryBits;
+    const tNative = process.hrtime.bigint();
+    const qz = native.quantizeQueries(flat, 1, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, 1);
+    const r = native.searchGrouped(targetVectors._deviceIndex(), groups._handle(), qz.quantized, qz.corrections, qb, sim, k);
+    hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
+    const n = r.indices.length, res = new Array(n);
+    for (let j = 0; j < n; j++) res[j] = { index: r.indices[j], score: r.scores[j], group: r.groups[j] };
+    return res;
+  }
+
+  /**
    * extension (not in the reference): every row whose stored f32 score is >= threshold - what the reference's loop (:349-411) would collect
    * if it kept every visited ord at or above the threshold and skipped the heap.  options.rowFilter: a RowFilter (createRowFilter) - only the
    * rows it accepts; options.order: 'ord' (default, ascending ord) or 'score' (descending score, ties in ascending ord).  A row whose
@@ -1086,6 +1110,27 @@ class RowFilter {
   dispose() { if (this._h) { native.filterDestroy(this._h); this._h = null; } }
 }
 function createRowFilter(targetVectors, accept) { return new RowFilter(targetVectors, accept); }
+/**
+ * extension (not in the reference): the groups of the rows of `targetVectors`, resident on its device (libbbq bbq_groups_*), for
+ * searchNearestNeighborsGrouped.  `offsets`: an array / Float64Array of groups + 1 entries - group g is the rows [offsets[g],
+ * offsets[g + 1]), offsets[0] === 0, ascending, the last one size().  `filter` (createRowFilter, optional) says which rows exist; it may
+ * be disposed before the group set.  Read-only; any number of searches may share it.  count: the groups; live: those with an accepted row.
+ */
+class RowGroups {
+  constructor(targetVectors, offsets, filter) {
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (!offsets) throw new Error('行分组不能为空');
+    if (filter !== undefined && filter !== null && !(filter instanceof RowFilter)) throw new Error('createRowGroups: the filter comes from createRowFilter(targetVectors, accept)');
+    const off = offsets instanceof Float64Array ? offsets : Float64Array.from(offsets, Number);
+    const r = native.groupsCreate(targetVectors._deviceIndex(), off, filter ? filter._handle() : null);
+    this._h = r.handle;
+    this.count = r.count;
+    this.live = r.live;
+  }
+  _handle() { if (!this._h) throw new Error('createRowGroups: the group set has been disposed'); return this._h; }
+  dispose() { if (this._h) { native.groupsDestroy(this._h); this._h = null; } }
+}
+function createRowGroups(targetVectors, offsets, filter) { return new RowGroups(targetVectors, offsets, filter); }
 
 // candidates of the oversampled search with their true scores; host arrays follow the reference line by line,
 // a DeviceVectors handle moves the similarity loop to the GPU (missing vectors cannot occur there: rows < length)
@@ -1231,7 +1276,7 @@ module.exports = Object.assign({}, require('./helpers'), {
   BinaryQuantizationFormat, OptimizedScalarQuantizer, BinaryQuantizedScorer, MinHeap,
   createBinaryQuantizationFormat, quickQuantize, quickSearch,
   getOversampledTopKWithHeap, getOversampledTopKWithSort, getOversampledTopKBatch, computeCosineSimilarity,
-  DeviceVectors, createDeviceVectors, RowFilter, createRowFilter, loadSiftVectors, loadSiftDataset, loadSiftQueries,
+  DeviceVectors, createDeviceVectors, RowFilter, createRowFilter, RowGroups, createRowGroups, loadSiftVectors, loadSiftDataset, loadSiftQueries,
   normalizeVector, computeCentroid, computeDotProduct, computeEuclideanDistance, computeEuclideanSimilarity, computeMaximumInnerProduct,
   computeSimilarity, computeQuantizedDotProduct, computeInt4BitDotProduct: computeQuantizedDotProduct, computeInt1BitDotProduct: computeQuantizedDotProduct,
   deviceCount: native.deviceCount,

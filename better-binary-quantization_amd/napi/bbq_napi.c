@@ -766,6 +766,110 @@ static napi_value SearchSpansFiltered(napi_env env, napi_callback_info info) {
   return search_spans(env, ix, flt, a + 2);
 }
 
+/* ---- grouped search (bbq_groups_*, bbq_search_grouped_batch) ---- */
+static void finalize_groups(napi_env env, void *data, void *hint) {
+  (void)env; (void)hint;
+  bbq_groups **box = (bbq_groups **)data;
+  if (*box) bbq_groups_destroy(*box);
+  free(box);
+}
+
+/* groupsCreate(index handle, offsets Float64Array [groups + 1], filter handle | null) -> {handle, count, live} */
+static napi_value GroupsCreate(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *op; size_t n;
+  if (!get_typed(env, a[1], napi_float64_array, &op, &n)) return NULL;
+  const bbq_filter *flt = NULL;
+  napi_valuetype vt;
+  NAPI_CALL(env, napi_typeof(env, a[2], &vt));
+  if (vt != napi_null && vt != napi_undefined) {
+    flt = unbox_filter(env, a[2], "bbq_groups_create");
+    if (!flt) return NULL;
+  }
+  if (n < 1) { napi_throw_range_error(env, NULL, "bbq_napi: group offsets hold one entry per group and one more"); return NULL; }
+  int64_t *off = (int64_t *)malloc(n * sizeof(int64_t));
+  bbq_groups **box = (bbq_groups **)calloc(1, sizeof *box);
+  if (!off || !box) { free(off); free(box); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  for (size_t i = 0; i < n; ++i) {
+    const double v = ((const double *)op)[i];
+    if (!(v >= -9007199254740992.0 && v <= 9007199254740992.0) || v != (double)(int64_t)v) {
+      free(off); free(box);
+      napi_throw_range_error(env, NULL, "bbq_napi: group offsets are integers");
+      return NULL;
+    }
+    off[i] = (int64_t)v;
+  }
+  int rc = bbq_groups_create(ix, off, (int64_t)n - 1, flt, box);
+  free(off);
+  if (rc != BBQ_OK) { free(box); return throw_bbq(env, rc); }
+  napi_value ext, o, cnt, live;
+  if (napi_create_external(env, box, finalize_groups, NULL, &ext) != napi_ok) { bbq_groups_destroy(*box); free(box); napi_throw_error(env, NULL, "bbq_napi: external"); return NULL; }
+  NAPI_CALL(env, napi_create_object(env, &o));
+  NAPI_CALL(env, napi_create_double(env, (double)bbq_groups_count(*box), &cnt));
+  NAPI_CALL(env, napi_create_double(env, (double)bbq_groups_live(*box), &live));
+  set_prop(env, o, "handle", ext); set_prop(env, o, "count", cnt); set_prop(env, o, "live", live);
+  return o;
+}
+
+/* groupsDestroy(handle) */
+static napi_value GroupsDestroy(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  void *p = NULL;
+  if (napi_get_value_external(env, a[0], &p) == napi_ok && p) {
+    bbq_groups **box = (bbq_groups **)p;
+    if (*box) { bbq_groups_destroy(*box); *box = NULL; }
+  }
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
+/* searchGrouped(handle, groups handle, qquant, qcorr, queryBits, sim, k) -> {indices Int32Array, scores Float32Array, groups Int32Array,
+ * status}: the k best groups, each through its best accepted row (bbq_search_grouped_batch with one query); status 0: the device
+ * selected the answer, 1: the host replayed the heap */
+static napi_value SearchGrouped(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (!get_args(env, info, 7, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *gp = NULL;
+  if (napi_get_value_external(env, a[1], &gp) != napi_ok || !gp || !*(bbq_groups **)gp) {
+    napi_throw_error(env, "BBQ1", "bbq_search_grouped_batch: the group set is null");
+    return NULL;
+  }
+  const bbq_groups *grp = *(bbq_groups **)gp;
+  void *qq, *qc; size_t ql, cl;
+  int64_t qb, sim, k;
+  if (!get_typed(env, a[2], napi_uint8_array, &qq, &ql) || !get_typed(env, a[3], napi_float64_array, &qc, &cl) ||
+      !get_i64(env, a[4], &qb) || !get_i64(env, a[5], &sim) || !get_i64(env, a[6], &k)) return NULL;
+  if (ql != (size_t)bbq_index_dimension(ix) || cl != 4) { napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return NULL; }
+  if (k < 0) { napi_throw_error(env, "BBQ7", "k值不能为负数"); return NULL; }
+  const int64_t live = bbq_groups_live(grp);
+  const int64_t keff = k < live ? k : live;   /* no answer is longer than the live groups */
+  int32_t *idx = (int32_t *)malloc(((size_t)keff + 1) * sizeof(int32_t));
+  int32_t *og = (int32_t *)malloc(((size_t)keff + 1) * sizeof(int32_t));
+  float *sc = (float *)malloc(((size_t)keff + 1) * sizeof(float));
+  if (!idx || !og || !sc) { free(idx); free(og); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int64_t cnt = 0;
+  uint8_t status = 0;
+  int rc = bbq_search_grouped_batch(ix, grp, 1, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff, idx, og, sc, &cnt, &status);
+  if (rc != BBQ_OK) { free(idx); free(og); free(sc); return throw_bbq(env, rc); }
+  void *oi, *os, *ogp;
+  napi_value ti = new_typed(env, napi_int32_array, (size_t)cnt, 4, &oi);
+  napi_value ts = new_typed(env, napi_float32_array, (size_t)cnt, 4, &os);
+  napi_value tg = new_typed(env, napi_int32_array, (size_t)cnt, 4, &ogp);
+  if (!ti || !ts || !tg) { free(idx); free(og); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  if (cnt > 0) { memcpy(oi, idx, (size_t)cnt * 4); memcpy(os, sc, (size_t)cnt * 4); memcpy(ogp, og, (size_t)cnt * 4); }
+  free(idx); free(og); free(sc);
+  napi_value o, st;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  NAPI_CALL(env, napi_create_int32(env, (int32_t)status, &st));
+  set_prop(env, o, "indices", ti); set_prop(env, o, "scores", ts); set_prop(env, o, "groups", tg); set_prop(env, o, "status", st);
+  return o;
+}
+
 /* searchRange(handle, filter handle | null, qquant, qcorr, queryBits, sim, threshold) -> {indices Int32Array, scores Float32Array}: every row (of
  * the filter, if one is given) whose f32 score is >= threshold, ascending by ord (bbq_count_range_batch, then bbq_search_range_batch with
  * exactly that room).  A NaN threshold throws. */
@@ -1135,6 +1239,9 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"searchRange", NULL, SearchRange, NULL, NULL, NULL, napi_default, NULL},
       {"searchSpans", NULL, SearchSpans, NULL, NULL, NULL, napi_default, NULL},
       {"searchSpansFiltered", NULL, SearchSpansFiltered, NULL, NULL, NULL, napi_default, NULL},
+      {"groupsCreate", NULL, GroupsCreate, NULL, NULL, NULL, napi_default, NULL},
+      {"groupsDestroy", NULL, GroupsDestroy, NULL, NULL, NULL, napi_default, NULL},
+      {"searchGrouped", NULL, SearchGrouped, NULL, NULL, NULL, napi_default, NULL},
       {"setOption", NULL, SetOption, NULL, NULL, NULL, napi_default, NULL},
       {"stats", NULL, Stats, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsCreate", NULL, VectorsCreate, NULL, NULL, NULL, napi_default, NULL},

@@ -250,6 +250,33 @@ class BinaryQuantizationFormat:
             raise Exception("行过滤器不能为空")
         return self._search(queryVector, targetVectors, k, rowFilter, None, np.asarray(spans, np.int64).reshape(-1, 2))
 
+    def searchNearestNeighborsGrouped(self, queryVector, targetVectors, rowGroups, k):
+        """extension: the k best groups of `rowGroups` (createRowGroups) - documents held as runs of chunk rows - each through its best
+        accepted row: what the reference's loop returns when it visits exactly each live group's best row, ascending, with a heap of
+        min(k, live groups).  Returns [{index, score, group}]."""
+        if queryVector is None:
+            raise Exception("查询向量不能为空")
+        if targetVectors is None:
+            raise Exception("目标向量集合不能为空")
+        if rowGroups is None:
+            raise Exception("行分组不能为空")
+        if k < 0:
+            raise Exception("k值不能为负数")
+        if len(queryVector) != targetVectors.dimension():
+            raise Exception("查询向量维度与目标向量维度不匹配")
+        if k == 0:
+            return []
+        sim = capi.SIMS[self._sim]
+        if targetVectors._index_bits != 1 and targetVectors.dimension() > 1 and self._config["queryBits"] not in (1, 4):
+            raise Exception("不支持的查询位数: %d，只支持1位和4位" % self._config["queryBits"])  # as _search refuses it
+        try:
+            qq, qc = capi.quantize_query(queryVector, targetVectors.getCentroid(), sim, self._config["queryBits"], self._lambda,
+                                         self._iters, search_path=True)
+            idx, sc, grp = targetVectors._device().search_grouped_batch(qq[None, :], qc[None, :], self._config["queryBits"], sim, k, rowGroups)[0][0]
+        except capi.BBQError as e:
+            raise Exception(str(e))
+        return [{"index": int(i), "score": float(s), "group": int(g)} for i, s, g in zip(idx, sc, grp)]
+
     def searchRange(self, queryVector, targetVectors, threshold, rowFilter=None, order="ord"):
         """extension: every row (of `rowFilter`, createRowFilter, if given) whose stored f32 score is >= threshold - what the
         reference's loop would collect if it kept every visited ord at or above the threshold and skipped the heap - as
@@ -348,6 +375,18 @@ def createRowFilter(targetVectors, accept):
         accept = np.fromiter((bool(accept(i)) for i in range(targetVectors.size())), np.bool_, targetVectors.size())
     try:
         return capi.Filter(targetVectors._device(), accept)
+    except capi.BBQError as e:
+        raise Exception(str(e))
+
+
+def createRowGroups(targetVectors, offsets, rowFilter=None):
+    """extension: the groups of `targetVectors` for searchNearestNeighborsGrouped: group g is the rows [offsets[g], offsets[g + 1]),
+    offsets[0] == 0, ascending, offsets[-1] == size(); `rowFilter` (createRowFilter) says which rows exist.  Returns a capi.Groups
+    (.count, .live, .close(), context manager)."""
+    if offsets is None:
+        raise Exception("行分组不能为空")
+    try:
+        return capi.Groups(targetVectors._device(), offsets, rowFilter)
     except capi.BBQError as e:
         raise Exception(str(e))
 

@@ -33,6 +33,7 @@ SYMBOLS = [
     "bbq_score_ords", "bbq_score_ords_batch", "bbq_search_ords_batch",
     "bbq_range_key", "bbq_count_range_batch", "bbq_search_range_batch",
     "bbq_search_spans_batch", "bbq_search_spans_filtered_batch",
+    "bbq_groups_create", "bbq_groups_destroy", "bbq_groups_count", "bbq_groups_live", "bbq_groups_plan", "bbq_search_grouped_batch",
 ]
 
 
@@ -113,6 +114,15 @@ def lib():
     L.bbq_search_range_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, i64, vp, vp, vp]
     L.bbq_search_spans_batch.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp]
     L.bbq_search_spans_filtered_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp]
+    L.bbq_groups_create.argtypes = [vp, vp, i64, vp, C.POINTER(vp)]
+    L.bbq_groups_destroy.argtypes = [vp]
+    L.bbq_groups_destroy.restype = None
+    L.bbq_groups_count.argtypes = [vp]
+    L.bbq_groups_count.restype = i64
+    L.bbq_groups_live.argtypes = [vp]
+    L.bbq_groups_live.restype = i64
+    L.bbq_groups_plan.argtypes = [vp, i64, i64, vp, vp, C.POINTER(i64)]
+    L.bbq_search_grouped_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_create_rows.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_destroy.argtypes = [vp]
@@ -594,6 +604,23 @@ class Index:
                                                   _ptr(off), _ptr(sp), _ptr(idx), _ptr(sc), _ptr(cnt), _ptr(status)))
         return [(idx[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)], status
 
+    def search_grouped_batch(self, qquant, qcorr, query_bits, sim, k, groups):
+        """bbq_search_grouped_batch: the k best groups of `groups` (a Groups of this index) for every query, each through its best
+        accepted row.  Returns a list of (idx, score, group) per query and the status array (0: the device selected the answer, 1: the
+        host replayed the heap over the device's representatives)."""
+        qq = np.ascontiguousarray(qquant, np.uint8)
+        qc = np.ascontiguousarray(qcorr, np.float64)
+        nq = qq.shape[0]
+        kk = max(int(k), 0)
+        idx = np.zeros((nq, kk), np.int32)
+        grp = np.zeros((nq, kk), np.int32)
+        sc = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.int64)
+        status = np.zeros(nq, np.uint8)
+        _chk(lib().bbq_search_grouped_batch(self._h, groups._h if groups is not None else None, nq, _ptr(qq), _ptr(qc), query_bits, sim, k,
+                                           _ptr(idx), _ptr(grp), _ptr(sc), _ptr(cnt), _ptr(status)))
+        return [(idx[q, :cnt[q]], sc[q, :cnt[q]], grp[q, :cnt[q]]) for q in range(nq)], status
+
     def _range_args(self, qquant, qcorr, thresholds):
         qq = np.ascontiguousarray(qquant, np.uint8)
         qc = np.ascontiguousarray(qcorr, np.float64)
@@ -790,6 +817,60 @@ class Filter:
     def close(self):
         if getattr(self, "_h", None):
             lib().bbq_filter_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def groups_plan(offsets, n_rows, mask=None):
+    """which groups of `offsets` are live under `mask` (a bool mask over the rows, or None: every row) and where they rank among the
+    live ones (bbq_groups_plan; host only): (slot int32 [n_groups], -1 for a group without an accepted row; L)"""
+    off = np.ascontiguousarray(offsets, np.int64).ravel()
+    n_groups = off.shape[0] - 1
+    words = pack_mask(mask) if mask is not None else None
+    if words is not None and len(mask) != n_rows:
+        raise BBQError(ERR_INVALID_ARG, "a mask has one entry per row")
+    slot = np.zeros(max(n_groups, 0), np.int32)
+    live = C.c_int64(0)
+    _chk(lib().bbq_groups_plan(_ptr(off) if off.shape[0] else None, n_groups, int(n_rows), _ptr(words), _ptr(slot), C.byref(live)))
+    return slot, int(live.value)
+
+
+class Groups:
+    """the groups of one Index, resident on its device (bbq_groups_*): group g is the rows [offsets[g], offsets[g + 1]); `row_filter` (a
+    Filter of the index, or None) says which rows exist for a grouped search.  Read-only after creation; any number of searches may
+    share it, and the filter may be closed before it."""
+
+    def __init__(self, index, offsets, row_filter=None):
+        off = np.ascontiguousarray(offsets, np.int64).ravel()
+        h = C.c_void_p()
+        _chk(lib().bbq_groups_create(index._h, _ptr(off) if off.shape[0] else None, off.shape[0] - 1, row_filter._h if row_filter is not None else None,
+                                    C.byref(h)))
+        self._h = h
+
+    @property
+    def count(self):
+        """the number of groups, empty ones included"""
+        return int(lib().bbq_groups_count(self._h)) if self._h else 0
+
+    @property
+    def live(self):
+        """L: the groups with at least one accepted row"""
+        return int(lib().bbq_groups_live(self._h)) if self._h else 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().bbq_groups_destroy(self._h)
             self._h = None
 
     def __enter__(self):

@@ -38,7 +38,8 @@ extern "C" {
                               in-place updates - bbq_index_update_rows, bbq_index_update, bbq_vectors_update, bbq_update_winners - and the scoring of chosen rows -
                               bbq_score_ords, bbq_score_ords_batch, bbq_search_ords_batch - and the range search - bbq_range_key,
                               bbq_count_range_batch, bbq_search_range_batch - and the span search - bbq_search_spans_batch,
-                              bbq_search_spans_filtered_batch) */
+                              bbq_search_spans_filtered_batch - and the grouped search - bbq_groups_create, bbq_groups_destroy,
+                              bbq_groups_count, bbq_groups_live, bbq_groups_plan, bbq_search_grouped_batch) */
 
 /* status codes */
 enum {
@@ -465,6 +466,47 @@ int bbq_search_spans_filtered_batch(bbq_index *idx, const bbq_filter *f, int32_t
                                     int32_t *out_idx, float *out_score, int64_t *out_n, uint8_t *out_status);
 
 /* ------------------------------------------------------------------------------------------
+ * Grouped search (DESIGN.md "Grouped search"): the k best GROUPS of rows, each through its best row - the k best documents of a store
+ * that holds a document as a run of chunk rows (Lucene's diversifying-children kNN query) - exact, in one call, on the device.
+ * A group set belongs to ONE single-device root index, as a filter does.  group_offsets [n_groups + 1]: group g is the rows
+ * [group_offsets[g], group_offsets[g + 1]); group_offsets[0] == 0, ascending (equal neighbours: an empty group), and
+ * group_offsets[n_groups] == bbq_index_size(idx).  Anything else is BBQ_ERR_INVALID_ARG.  f (may be NULL: every row): a filter of this
+ * index, checked as bbq_search_filtered_batch checks it; rows it rejects are never visited.  The group set copies the filter's words:
+ * the filter may be destroyed before the group set.  A group is LIVE if it has at least one accepted row; L = bbq_groups_live is the
+ * same for every query.  The device tables - a 64-bit word of group starts and a group number per tile, a slot per non-empty group,
+ * about 0.2 bytes per row - are built here, once.  At most 2^31 - 1 rows and groups.
+ * A query's REPRESENTATIVE of a live group is its accepted row with the greatest f32 score (bbq_score_rows' score), where a NaN score
+ * ranks below every number, numbers rank in the order of bbq_key_of_score (-0.0 below +0.0) and among rows of equal rank the lowest
+ * ord wins; a group whose accepted rows all score NaN is represented by the lowest of them, with a NaN score.
+ * bbq_search_grouped_batch: query q's answer is what the reference loop (src/binaryQuantizationFormat.ts:349-411) returns when it visits
+ * exactly the L representatives, ascending by ord, pushing (original ord, f32 score) into a heap of min(k, L) - the answer of
+ * bbq_search_ords_batch over the representatives: indices, score bits and order, ties and NaN included.
+ * out_idx / out_score [n_queries*k] (query q at offset q*k), out_n [n_queries], as bbq_search_batch; out_group [n_queries*k] (may be
+ * NULL): the group of each answer row.  k < 0: BBQ_ERR_NEGATIVE_K; k == 0 or L == 0: out_n[q] = 0; k > L: L results; no upper limit on k.
+ * out_status [n_queries] (may be NULL) follows the span search's rule over the representatives' scores: 0 - the device selected the
+ * answer - EXACTLY when L > k, 1 <= k <= 4096, no representative is NaN and no two of the k + 1 largest compare equal as floats;
+ * otherwise 1 - the host ran the literal heap over the device's representatives.  0 as well for k == 0 or L == 0.
+ * A group set made for another size or device (used after an append, a removal or a compaction): BBQ_ERR_INVALID_ARG, nothing launched,
+ * nothing written; after an in-place update it still serves.  A multi-device handle, a non-root shard or an index with a pilot
+ * replica: BBQ_ERR_UNSUPPORTED.  The call takes the device context's lock, runs on the auxiliary stream and writes no bbq_stats field.
+ * Every query streams the whole index - nothing is pruned.  A long call is worked through in sub-batches of at most 1024 queries and
+ * group_scratch_mb (bbq_set_option) of representatives, always at least one query.  A failed allocation: BBQ_ERR_OOM, nothing written.
+ * Results are byte-identical from run to run.  Out of scope: persisted group sets, a group set per query, groups that are not
+ * contiguous runs of rows, a sweep pruned by a bound on the k-th best group. */
+typedef struct bbq_groups bbq_groups;   /* opaque: the groups of one index, resident on that index's device */
+int bbq_groups_create(bbq_index *idx, const int64_t *group_offsets, int64_t n_groups, const bbq_filter *f, bbq_groups **out);
+void bbq_groups_destroy(bbq_groups *g);
+int64_t bbq_groups_count(const bbq_groups *g);   /* n_groups */
+int64_t bbq_groups_live(const bbq_groups *g);    /* L */
+/* Host only, no device: validates the offsets as bbq_groups_create does against n_rows rows; out_slot [n_groups]: the rank of group g
+ * among the live groups, or -1; *out_live = L.  accept_bits as bbq_filter_create takes them, or NULL: every row. */
+int bbq_groups_plan(const int64_t *group_offsets, int64_t n_groups, int64_t n_rows, const uint64_t *accept_bits,
+                    int32_t *out_slot, int64_t *out_live);
+int bbq_search_grouped_batch(bbq_index *idx, const bbq_groups *g, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
+                             int32_t query_bits, int32_t sim, int64_t k,
+                             int32_t *out_idx, int32_t *out_group, float *out_score, int64_t *out_n, uint8_t *out_status);
+
+/* ------------------------------------------------------------------------------------------
  * Sharded search (one process per GPU).  bbq_shard_scan sweeps THIS shard for n_queries queries and
  * leaves the shard's candidates - per query a superset of the rows that ever enter the reference's heap,
  * ascending by global row - PACKED in caller-provided DEVICE memory, so the host framework can move them
@@ -684,6 +726,8 @@ int bbq_reset_stats(bbq_index *idx);
  *     row is 6, 8 or 12 16-byte chunks wide (641..768, 897..1024, 1409..1536 dimensions; a filtered search: 641..768 only) - where it
  *     was measured faster; 0: always bit-planes.  The digit masks are staged with the query in addition to its bit-planes (5 x 16 bytes per 128 dimensions).  The dot
  *     product is the same exact integer either way: never a different answer
+ *   group_scratch_mb 1..8192 (256): MiB of device scratch a sub-batch of bbq_search_grouped_batch may take for its representatives, 16
+ *     bytes per live group and query: a score launch takes as many queries as fit (at most 1024, at least one).  Never a different answer
  *   fast_bound 0|1 (1): compact corrections: 1 tests the score bound of a row in f32 against the threshold's image in the linear space of
  *     the score formula, for every query whose corrections have f32 images (others keep the f64 bound); 0: always the f64 bound through
  *     the similarity transform.  A pre-filter in front of the exact score either way: never a different answer
