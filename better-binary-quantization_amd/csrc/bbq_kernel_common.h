@@ -34,13 +34,20 @@ __device__ __forceinline__ bool chunk_is_resident(int64_t chunk, const IndexView
 // 1: the compact word, 2: the inline f64 corrections (lower, upper | additional | component sum if stored).  Loads that are
 // already in flight when the branch is reached make the compiler wait for them inside it (it assumes either arm may follow them).
 // RS: the lane's entry of the row_sums side array (rs points at it) is one more load of the tile, under the arm's cache policy -> rsum.
-template <int W, int CORR, bool RS = false>
+// (A caller that uses the value behind a barrier passes rs as the aligned PAIR of entries the lane's own lies in, a uint32_t, and picks its half
+// there: a 16-bit value that lives across blocks is widened by the compiler where it is loaded, and that instruction waits for the load.)
+// `first` is called at the head of whichever arm is taken, in front of its loads: a load of the caller's own that has to be the oldest one in
+// flight (the sweep's query masks).  Issued in front of the branch instead, it is "just issued" on the path into either arm, and the
+// compiler's count at the join behind the arms makes whoever needs it wait for all of the tile's loads but the last.
+struct NoFirstLoad { __device__ __forceinline__ void operator()() const {} };
+template <int W, int CORR, bool RS = false, class RSrc = uint16_t, class First = NoFirstLoad>
 __device__ __forceinline__ void load_tile(const uint8_t *__restrict__ tp, int lane, bool has_x1, bool resident, int64_t nt_delta,
                                           u32x4 (&c)[W], uint32_t &cw, f64x2 &lu, double &xadd, double &x1,
-                                          const uint16_t *__restrict__ rs = nullptr, uint32_t *rsum = nullptr) {
+                                          const RSrc *__restrict__ rs = nullptr, uint32_t *rsum = nullptr, First first = First()) {
   const u32x4 *__restrict__ cp = reinterpret_cast<const u32x4 *>(tp) + lane;
   const uint8_t *__restrict__ cr = tp + tile_corr_offset(W);
   if (resident) {  // scalar branch
+    first();
 #pragma unroll
     for (int j = 0; j < W; ++j) c[j] = cp[j * kTileRows];
     if constexpr (CORR == 1) cw = *(reinterpret_cast<const uint32_t *>(cr) + lane);
@@ -52,6 +59,7 @@ __device__ __forceinline__ void load_tile(const uint8_t *__restrict__ tp, int la
     }
   } else {
     BBQ_BRANCH_FENCE();
+    first();
     const u32x4 *__restrict__ cs = stream_ptr(cp, nt_delta);
     const uint8_t *__restrict__ crs = stream_ptr(cr, nt_delta);
 #pragma unroll

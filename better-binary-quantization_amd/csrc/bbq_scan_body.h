@@ -70,6 +70,27 @@ __device__ __forceinline__ void tile_dot_multibit_any(const uint8_t *__restrict_
   qc = lo + (hi << 4);
 }
 
+// The instantiations whose waves issue their tile's loads in front of the query staging and the first barrier (EARLY in the kernel): the sparse
+// sweeps of a compile-time width.  The run-time width streams its row chunk by chunk behind the staging and dense launches are bound by their
+// writes: both keep their order.  An instantiation that the early order would cost a wave of occupancy is excluded here (docs/dropped.md,
+// "early loads").  To check again: build both kernel files with -Rpass-analysis=kernel-resource-usage with and without the exclusion and
+// compare VGPRs / Occupancy / ScratchSize of every bbq_scan_kernel instantiation (scripts/scan_resources.py).
+template <bool FILT, int QB, int W, int MODE, int SB, bool RS, bool DG>
+constexpr bool early_loads() {
+  if (W == 0 || (MODE & 1)) return false;
+  // The filtered family keeps its order: there the masks' load stands behind the branch on the tile's accept word, a memory round trip of
+  // its own, and where most tiles of a filter are empty most staging waves paid the two in series: measured at 10 M x 768-d, +3.4 % under
+  // dense filters, -9 % with 0.1 % of the rows accepted and -16 % with 1000 rows (Measurement; docs/dropped.md).
+  if (FILT) return false;
+  // the nine that came out of this build's compiler (ROCm 7.2) with a wave of occupancy less in the early order: five unfiltered sweeps of the
+  // inline layout at 12 chunks (72 -> 74 vector registers, 7 -> 6 waves) and one filtered sweep of the compact layout (72 -> 118, 7 -> 4)
+  if (MODE == 0 && W == 12 && !FILT && ((SB == 1 && QB <= 2) || (SB == 2 && QB == 4) || SB == 4)) return false;
+  if (MODE == 2 && W == 12 && SB == 1 && QB == 8 && !RS && FILT) return false;
+  // ... and three compact sweeps of 4-bit rows at 16 chunks that count the sum themselves (80 -> 82, 6 -> 5 waves)
+  if (MODE == 2 && W == 16 && SB == 4 && !RS && (QB == 8 || FILT)) return false;
+  return true;
+}
+
 // MODE: 0 sparse / inline corrections, 1 dense / inline, 2 sparse / compact corrections + exact gather, 3 dense / compact
 // grid = (chunks of kChunkRows rows, queries), or with ScanArgs::l2_shift = s > 0 the same pairs in the order that runs a chunk's 2^s
 // queries back to back on one XCD (sweep_coord, bbq_device.h); block = kChunkRows/64 waves: wave w handles tile w of its chunk (one
@@ -127,45 +148,108 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
     const int64_t my_tile = (a.chunk_begin + wg.chunk_local) * kTilesPerChunk + __builtin_amdgcn_readfirstlane(wave);
     if (my_tile < (a.idx.n_rows + kTileRows - 1) / kTileRows) aw = accept[my_tile];
   }
-  {  // stage the query bit-planes (DG: its digit masks) once per workgroup
-    const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (DG ? (size_t)a.qdigits_at : 0) + (size_t)q * w16 * QU;
+  // EARLY (early_loads, above): the wave's tile loads are issued in front of the staging and the barrier.  Nothing about a tile's address depends
+  // on the query, so the two memory round trips a workgroup used to pay one behind the other - the staging wave's masks, then, behind the barrier,
+  // every wave's tile - travel together: the query's scalar loads, the masks' load (into registers), the tile's loads, and only then the LDS
+  // write and the barrier, which waits for LDS alone.  The other order (run-time width, dense, early_loads' exceptions) stages first, as it always did.
+  constexpr bool EARLY = early_loads<FILT, QB, W, MODE, SB, RS, DG>();
+  const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (DG ? (size_t)a.qdigits_at : 0) + (size_t)q * w16 * QU;
+  if constexpr (!EARLY) {  // stage the query bit-planes (DG: its digit masks) once per workgroup
     for (int i = tid; i < w16 * QU; i += NT) s_planes[i] = gp[i];
     if (!DENSE && tid == 0) *s_cnt = 0;
   }
+  // (the query's uniforms stay in front of the tile's loads in the source: behind load_tile's compiler barriers they became vector loads)
   const QueryParams p = a.qparams[q];
   const Threshold th = DENSE ? Threshold{0u, 0u} : a.theta[q];  // (one 8-byte scalar load: the key and its z image)
   const uint32_t theta = th.key;
-  if (idle) return;
-  __syncthreads();
+  if constexpr (!EARLY) {
+    if (idle) return;
+    __syncthreads();
+  }
 
   const int64_t chunk = a.chunk_begin + wg.chunk_local;
   const int64_t n_tiles = (a.idx.n_rows + kTileRows - 1) / kTileRows;
   const int64_t tile = chunk * kTilesPerChunk + wave;
   bool nan_seen = false;
+  // wave-uniform.  (An idle workgroup of the early order has not left yet, and its chunk may well exist in the index: it loads nothing.)
+  // The early order decides it on the scalar unit, from the wave number as a scalar: its two arms below must be the two arms of a scalar
+  // branch, each ending in its own wait, and not two masked stretches of one path that the compiler could see skipped both.
+  bool has_tile;
+  if constexpr (EARLY) has_tile = !idle && chunk * kTilesPerChunk + __builtin_amdgcn_readfirstlane(wave) < n_tiles && (!FILT || aw != 0);
+  else has_tile = tile < n_tiles && (!FILT || aw != 0);
 
-  if (tile < n_tiles && (!FILT || aw != 0)) {  // wave-uniform
+  // the tile's registers: in the early order they are loaded in front of the barrier and used behind it
+  constexpr int CORR = !COMPACT ? 2 : (DENSE ? 0 : 1);
+  f64x2 lu = {0.0, 0.0};
+  double xadd = 0.0, x1 = 0.0;
+  uint32_t cw;
+  float aadd;
+  uint32_t qc, ones;
+  // (the early order leaves them unset: a wave without a tile never reads them, and set to zero here every wave of the early order paid
+  // two dozen moves - the tile's registers with them - in front of its loads, where the compiler put the no-tile path's values)
+  if constexpr (!EARLY) { cw = 0; aadd = 0.0f; ones = 0; }
+  u32x4 c[W > 0 ? W : 1];
+  (void)c;
+  if constexpr (EARLY) {
+    static_assert(W * QU <= NT, "one staging pass: every unit of the query has a thread");
+    // The masks' load and the LDS write stand in BOTH arms of this scalar branch - in the arm with a tile the load at the head of whichever
+    // arm load_tile takes - so that the masks are the oldest load in flight on every path and in flight nowhere else.  The loads return in
+    // order, so the staging threads wait for the masks and for nothing of the tile (vmcnt = the tile's loads), and the registers the masks
+    // came in are known to be free behind the barrier.  Loaded in front of the branch and written behind it, the compiler's count at the
+    // join was the no-tile arm's: vmcnt(0), the whole tile, in front of the LDS write and once more behind the barrier, for every wave.
+    // (The staging registers are set and read under one condition; initialised, the streamed arm copied and waited for them at once.)
+    if (has_tile) {
+      u32x4 staged;
+      auto load_masks = [&]() { if (tid < W * QU) staged = gp[tid]; };
+      const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
+      const int64_t row = tile * kTileRows + lane;
+      const bool resident = chunk_is_resident(chunk, a.idx);
+      // (the row's sum as the aligned pair of 16-bit entries it lies in - rows and lanes have the same parity, the side array covers whole
+      // tiles - and the lane's half picked behind the barrier: loaded as 16 bits, the value was widened here, in an instruction that waited
+      // for all but the tile's last load in front of the barrier)
+      if constexpr (RS) load_tile<W, CORR, true>(tp, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1,
+                                                 reinterpret_cast<const uint32_t *>(a.idx.row_sums + (row & ~(int64_t)1)), &ones, load_masks);
+      else load_tile<W, CORR, false>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, (const uint16_t *)nullptr, nullptr, load_masks);
+      // with the tile's loads, not behind the barrier: there it waited for the whole tile first
+      if constexpr (COMPACT) aadd = tile_add_bound(a.idx, tile, p.sim);
+      if (tid < W * QU) s_planes[tid] = staged;
+      asm volatile("; staged with the tile's loads in flight" ::: "memory");  // (the arms do not end alike: no common tail to merge)
+    } else {
+      u32x4 staged;
+      if (tid < W * QU) staged = gp[tid];
+      if (tid < W * QU) s_planes[tid] = staged;
+      asm volatile("; staged without a tile" ::: "memory");
+    }
+    if (tid == 0) *s_cnt = 0;
+    if (idle) return;
+    __syncthreads();  // LDS only: a wave that staged nothing passes it with its tile's loads in flight
+  }
+
+  if (has_tile) {
     const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
     const uint8_t *__restrict__ cr = tp + tile_corr_offset(w16);
     const int64_t row = tile * kTileRows + lane;
     const bool valid = row < a.idx.n_rows && (!FILT || ((aw >> lane) & 1ull) != 0);
-    const bool resident = chunk_is_resident(chunk, a.idx);
 
     // every load of the tile is issued up front: the row's code chunks and its corrections
-    f64x2 lu = {0.0, 0.0};
-    double xadd = 0.0, x1 = 0.0;
-    uint32_t cw = 0;
-    float aadd = 0.0f;
-    uint32_t qc, ones;
-    constexpr int CORR = !COMPACT ? 2 : (DENSE ? 0 : 1);
     if constexpr (W > 0) {
-      u32x4 c[W];
-      if constexpr (RS) load_tile<W, CORR, true>(tp, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, a.idx.row_sums + row, &ones);
-      else load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
-      if constexpr (COMPACT && DENSE) exact_corrections<true>(a.idx.exact, row, lu, xadd);
-      if constexpr (COMPACT && !DENSE) aadd = tile_add_bound(a.idx, tile, p.sim);
-      if constexpr (DG) qc = tile_digit_dot<W>(c, s_planes, ones, p.digit_k);
+      if constexpr (!EARLY) {
+        const bool resident = chunk_is_resident(chunk, a.idx);
+        if constexpr (RS) load_tile<W, CORR, true>(tp, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, a.idx.row_sums + row, &ones);
+        else load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
+        if constexpr (COMPACT && DENSE) exact_corrections<true>(a.idx.exact, row, lu, xadd);
+        if constexpr (COMPACT && !DENSE) aadd = tile_add_bound(a.idx, tile, p.sim);
+      }
+      if constexpr (DG) qc = tile_digit_dot<W>(c, s_planes, EARLY ? 0u : ones, p.digit_k);
       else if constexpr (SB == 1) qc = tile_popcounts<QB, W, !RS>(c, s_planes, ones);
       else tile_dot_multibit<QB, W, SB, !RS>(c, s_planes, qc, ones);
+      if constexpr (EARLY && RS) {
+        // the lane's half of the pair, picked BEHIND the dot product and kept there: the pair is the tile's last load but one, and scheduled
+        // in front of the popcounts the pick made them wait for the whole tile instead of counting the chunks down as they arrive
+        __builtin_amdgcn_sched_barrier(0);
+        ones = __builtin_amdgcn_ubfe(ones, (uint32_t)(lane & 1) << 4, 16u);
+        if constexpr (DG) qc += ones << 2;  // digit_dot's 4 * ones: u32 arithmetic, the same integer in either order
+      }
     } else {  // a row width without a compiled kernel: streamed chunk by chunk
       if constexpr (!COMPACT) {
         lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(cr) + lane);

@@ -8,6 +8,9 @@
 // that the P workgroups that sweep one chunk for P queries are dispatched back to back onto one XCD (the library's sweep_coord map:
 // x = L & 7 labels the XCD, p = (L >> 3) & (P - 1), chunk = 8 (L >> (3 + s)) + x, query = blockIdx.y P + p); P = 1 is the plain grid.
 // Rate here; L2 hits and misses from a counter run of the same command (scripts/pmc_l2_hits.sh has the recipe).
+// ./scan_steps early [rounds]: the same launch at P = 32 in four variants that alternate in one run - the present order (planes staged, barrier,
+// then the tile's loads), the tile's loads issued in front of the staging and the barrier, and each of the two with the arithmetic removed (the
+// loaded words are only folded into one): what this access shape delivers at P = 32 when nothing but the loads is left.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
@@ -19,7 +22,8 @@ __device__ __forceinline__ uint32_t popc4(u32x4 v) { return __popc(v.x) + __popc
 
 struct QP { double ay, ly, y1, qadd, cdp, dimd; int sim, one_bit, mip, pad; };
 
-template <int STEP>
+// VAR bit 0: the tile's loads in front of the staging and the barrier; bit 1: no arithmetic
+template <int STEP, int VAR = 0>
 __global__ __launch_bounds__(512) void k(const u32x4 *__restrict__ p, unsigned n_chunks, const u32x4 *__restrict__ planes, const QP *__restrict__ qps,
                                          const uint32_t *__restrict__ thetas, uint32_t *__restrict__ counts, uint64_t *__restrict__ entries, uint32_t *out,
                                          const float *__restrict__ add_range, const double *__restrict__ exact, int s, int n_queries) {
@@ -32,31 +36,53 @@ __global__ __launch_bounds__(512) void k(const u32x4 *__restrict__ p, unsigned n
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const u32x4 *tp = p + ((size_t)c * 8 + wave) * (6400 / 16) + lane;
   const u32x4 *gp = planes + (size_t)q * 24;
-  if (tid < 24) s_planes[tid] = gp[tid];
-  if (tid == 0) s_cnt = 0;
+  constexpr bool EARLY = (VAR & 1) != 0, NOARITH = (VAR & 2) != 0;
+  u32x4 staged = {0u, 0u, 0u, 0u};
+  if (EARLY) { if (tid < 24) staged = gp[tid]; }
+  else {
+    if (tid < 24) s_planes[tid] = gp[tid];
+    if (tid == 0) s_cnt = 0;
+  }
   QP qp;
   uint32_t theta = 0x7fffffffu;
   if (STEP >= 4) { qp = qps[q]; theta = thetas[q]; }
   else { qp.ay = -0.15; qp.ly = 0.02; qp.y1 = 5760.0; qp.qadd = -0.001; qp.cdp = 0.0009; qp.dimd = 768.0; qp.sim = 1; }
-  __syncthreads();
+  if (!EARLY) __syncthreads();
   u32x4 v[6];
 #pragma unroll
   for (int j = 0; j < 6; ++j) v[j] = __builtin_nontemporal_load(tp + j * 64);
   const uint32_t cc = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(tp - lane + 6 * 64) + lane);
   float addr_ = 0.f;
   if (STEP >= 5) addr_ = add_range[((size_t)c * 8 + wave) * 2 + 1];   // per-tile side value, plain load, one address per wave
+  if (EARLY) {
+    if (tid < 24) s_planes[tid] = staged;
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+  }
   uint32_t acc[4] = {0, 0, 0, 0}, ones = 0;
+  if (NOARITH) {   // every loaded word is used, and the planes are read, but nothing is counted
 #pragma unroll
-  for (int j = 0; j < 6; ++j) {
+    for (int j = 0; j < 6; ++j) { const u32x4 w = v[j] ^ s_planes[j * 4]; acc[j & 3] ^= w.x ^ w.y ^ w.z ^ w.w; }
+  } else {
 #pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] += popc4(v[j] & s_planes[j * 4 + b]);
-    ones += popc4(v[j]);
+    for (int j = 0; j < 6; ++j) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[b] += popc4(v[j] & s_planes[j * 4 + b]);
+      ones += popc4(v[j]);
+    }
   }
   const uint32_t qc = acc[0] + (acc[1] << 1) + (acc[2] << 2) + (acc[3] << 3);
   uint32_t r = qc + ones + cc;
   bool pass = false;
   float ub32 = 0.f;
-  if (STEP >= 1) {
+  if (NOARITH) {
+    if (STEP >= 5) r ^= __float_as_uint(addr_);
+    if (STEP >= 6) pass = ((c * 2654435761u + (unsigned)q * 40503u + tid * 2246822519u) >> 7) % 1700u == 0u;
+    if (STEP >= 6 && pass) {
+      const double *ex = exact + ((size_t)c * 512 + tid) * 4;
+      ub32 = (float)(ex[0] + ex[1] + ex[2]);
+    }
+  } else if (STEP >= 1) {
     const double al = (double)__uint_as_float(cc << 16), au = (double)__uint_as_float(cc & 0xffff0000u), x1 = (double)ones, qcd = (double)qc;
     const double lx = au - al;
     const double t1 = (al * qp.ay) * qp.dimd, t2 = (qp.ay * lx) * x1, t3 = (al * qp.ly) * qp.y1, t4 = (lx * qp.ly) * qcd;
@@ -128,22 +154,23 @@ static int run(const Bufs &b, size_t bytes, int reps, unsigned drop, const char 
 }
 
 // the reordered grid: 2^s queries co-scheduled per chunk
-static int run_l2share(const Bufs &b, unsigned n_chunks, int nq, int s) {
+template <int VAR = 0>
+static int run_l2share(const Bufs &b, unsigned n_chunks, int nq, int s, const char *label = "") {
   hipEvent_t e0, e1;
   CHK(hipEventCreate(&e0)); CHK(hipEventCreate(&e1));
   const dim3 grid(s == 0 ? n_chunks : ((n_chunks + 7) / 8 * 8) << s, (unsigned)(nq + (1 << s) - 1) >> s);
   float best = 1e9f, sum = 0;
   for (int it = 0; it < 7; ++it) {
     CHK(hipEventRecord(e0));
-    hipLaunchKernelGGL((k<6>), grid, dim3(512), 0, 0, b.d, n_chunks, b.planes, b.qps, b.thetas, b.counts, b.entries, b.out, b.add_range, b.exact, s, nq);
+    hipLaunchKernelGGL((k<6, VAR>), grid, dim3(512), 0, 0, b.d, n_chunks, b.planes, b.qps, b.thetas, b.counts, b.entries, b.out, b.add_range, b.exact, s, nq);
     CHK(hipEventRecord(e1));
     CHK(hipEventSynchronize(e1));
     float ms; CHK(hipEventElapsedTime(&ms, e0, e1));
     if (it >= 2) { sum += ms; if (ms < best) best = ms; }
   }
   const double by = (double)n_chunks * 51200 * nq;
-  printf("l2share P %2d  grid %7u x %2u  %u chunks x %d queries: avg %6.3f ms %7.1f GB/s  best %6.3f ms %7.1f GB/s\n", 1 << s, grid.x, grid.y, n_chunks, nq,
-         sum / 5, by / (sum / 5 * 1e-3) / 1e9, best, by / (best * 1e-3) / 1e9);
+  printf("l2share P %2d  grid %7u x %2u  %u chunks x %d queries: avg %6.3f ms %7.1f GB/s  best %6.3f ms %7.1f GB/s  %s\n", 1 << s, grid.x, grid.y, n_chunks, nq,
+         sum / 5, by / (sum / 5 * 1e-3) / 1e9, best, by / (best * 1e-3) / 1e9, label);
   return 0;
 }
 
@@ -171,6 +198,16 @@ int main(int argc, char **argv) {
       while ((1 << (s + 1)) <= P) ++s;
       if (P < 1 || P > 32 || (1 << s) != P) { printf("P must be 1, 2, 4, 8, 16 or 32\n"); return 1; }
       if (run_l2share(b, 15430, 32, s)) return 1;
+    }
+    return 0;
+  }
+  if (argc > 1 && std::string(argv[1]) == "early") {
+    const int rounds = argc > 2 ? atoi(argv[2]) : 3;
+    for (int r = 0; r < rounds; ++r) {
+      if (run_l2share<0>(b, 15430, 32, 5, "present order")) return 1;
+      if (run_l2share<1>(b, 15430, 32, 5, "tile loads first")) return 1;
+      if (run_l2share<2>(b, 15430, 32, 5, "present order, no arithmetic")) return 1;
+      if (run_l2share<3>(b, 15430, 32, 5, "tile loads first, no arithmetic")) return 1;
     }
     return 0;
   }
