@@ -395,7 +395,8 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
                c.planes, c.one_bit, c.sim);
   size_t bytes = (size_t)nq * qb + (size_t)nq * sizeof(QueryParams);
   // the matrix-core shared sweep appends its candidates to the lists, so it runs only where they are this slot's own
-  bool use_mfma = !ext && !c.filter && c.share == 32 && c.maxq <= 127 && ix->geom.store_bits == 1;
+  // (a filtered call with sweep_share 32 as well: its kernels take the filter's accept words)
+  bool use_mfma = !ext && c.share == 32 && c.maxq <= 127 && ix->geom.store_bits == 1;
   for (int i = 0; i < nq && use_mfma; ++i) use_mfma = mfma_query_ok(hq[i]);
   const MfmaStage ms = use_mfma ? stage_queries_mfma(c, s.h_qbuf, hq, q_first, nq, bytes) : MfmaStage{};
   if (use_mfma) bytes = ms.bytes;
@@ -445,8 +446,13 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
       a.append_cap = list_cap;
     }
     // how this segment is swept, decided once: on the matrix cores, shared between c.share queries, or (neither) every query on its own
-    const bool on_mfma = use_mfma && !g.dense && mfma_sweep_supported(a);
-    const bool shared = !on_mfma && !g.dense && c.share > 1 && shared_sweep_supported(a, c.share);
+    // A filtered plan has no dense first segment: its first segment runs with the zeroed threshold, and the matrix-core kernel flags
+    // a query without a usable threshold as overflowed.  So a filtered segment is swept there only behind k_dev accepted rows (the
+    // finalize launches behind them have left a threshold of that rank); the others, always the first, stay on the per-query filtered
+    // sweep, which appends to the same lists.
+    const bool theta_ready = !c.filter || c.filter->cum[(size_t)g.chunk_begin] >= c.k_dev;
+    const bool on_mfma = use_mfma && !g.dense && theta_ready && mfma_sweep_supported(a);
+    const bool shared = !on_mfma && !g.dense && !c.filter && c.share > 1 && shared_sweep_supported(a, c.share);
     const int my_slot = (int)(&s - ix->slots);
     // one big sweep at a time on the device - for the memory-bound sweeps, which share the Infinity Cache's budget.  The chains of the
     // matrix-core sweep are issue-bound and run side by side: serialised, the finalize launch and the launch gaps between a chain's two
@@ -455,11 +461,14 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
     if (chained && ix->ctx->last_big_slot >= 0 && ix->ctx->last_big_slot != my_slot)
       HIPCHK(hipStreamWaitEvent(st, ix->slots[ix->ctx->last_big_slot].ev_big, 0));
     if (g.dominant) HIPCHK(hipEventRecord(s.ev0, st));
-    if (on_mfma)
+    if (on_mfma && c.filter)
+      HIPCHK(launch_scan_mfma_filtered(a, c.filter->d_bits, s.d_qbuf + ms.off_qbytes, reinterpret_cast<const float *>(s.d_qbuf + ms.off_qmax),
+                                       ms.fp ? ms.scale8 / 8.0f : 0.0f, nq, (int)g.n_chunks, st));
+    else if (on_mfma)
       HIPCHK(launch_scan_mfma(a, s.d_qbuf + ms.off_qbytes, reinterpret_cast<const float *>(s.d_qbuf + ms.off_qmax), ms.fp ? ms.scale8 / 8.0f : 0.0f, nq, (int)g.n_chunks, st));
     else if (shared)
       HIPCHK(launch_scan_shared(a, c.planes, c.share, nq, (int)g.n_chunks, st));
-    else if (c.filter)  // (its plan has sparse segments only, and c.share == 1)
+    else if (c.filter)  // (its plan has sparse segments only; sweep_share 4 / 8 never reach a filtered call, 32 falls back to here)
       HIPCHK(launch_scan_filtered(a, c.filter->d_bits, c.planes, nq, (int)g.n_chunks, st));
     else
       HIPCHK(launch_scan(a, c.planes, g.dense, nq, (int)g.n_chunks, st));
@@ -732,8 +741,9 @@ static void reset_call_stats(bbq_index *ix) { ix->stats.candidates = ix->stats.d
 }  // namespace bbq
 
 // bbq_search_batch, and - with `feed` - bbq_search_raw_batch: the quantized queries of a sub-batch are waited for right before it is
-// enqueued; with `flt` - bbq_search_filtered_batch: the same call over the accepted rows only, always on the pipelined per-query
-// sweep (the single-query chains, the shared and the matrix-core sweeps derive their thresholds in ways of their own)
+// enqueued; with `flt` - bbq_search_filtered_batch: the same call over the accepted rows only, on the pipelined per-query sweep or,
+// with sweep_share 32, on the matrix-core sweep's filtered kernels behind the first k accepted rows (enqueue_subbatch).  The
+// single-query chains and the VALU shared sweep (sweep_share 4 / 8) take no filter: such a call sweeps per query
 static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits,
                              int32_t sim, int64_t k, int32_t *out_idx, float *out_score, int64_t *out_n, RawFeed *feed, int32_t *bad_query,
                              const bbq_filter *flt = nullptr) {
@@ -769,7 +779,7 @@ static int search_batch_impl(bbq_index *ix, int32_t n_queries, const uint8_t *qq
   if (flt) {
     c.filter = flt;
     c.n_eff = n_eff;
-    c.share = 1;
+    if (c.share != 32) c.share = 1;
   }
   if (feed) {  // the values are still being produced: the kernel variant follows from the bit width they are quantized to
     const int pq = query_bits <= 1 ? 1 : query_bits <= 2 ? 2 : query_bits <= 4 ? 4 : 8;

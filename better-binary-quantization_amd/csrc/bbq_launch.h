@@ -21,6 +21,11 @@ bool mfma_sweep_supported(const ScanArgs &a);
 int64_t mfma_query_bytes_per_group(int w16, bool fp);  // staged operand bytes of 32 queries
 int mfma_queries_per_tile_load(const ScanArgs &a, int n_queries, bool fp);  // 32, or 64 where a workgroup serves two groups per tile
 hipError_t launch_scan_mfma(const ScanArgs &a, const uint8_t *qbytes, const float *qmax, float fp_scale, int n_queries, int n_chunks, hipStream_t s);
+// ... of a filtered search: accept as launch_scan_filtered takes it.  Tiles without an accepted row are not loaded, a rejected row is
+// never a candidate; same shapes, same queries per tile load (mfma_sweep_supported, mfma_queries_per_tile_load).  Every query needs a
+// threshold already (the kernel flags one without as overflowed): the caller sweeps here only behind k accepted rows
+hipError_t launch_scan_mfma_filtered(const ScanArgs &a, const uint64_t *accept, const uint8_t *qbytes, const float *qmax, float fp_scale, int n_queries,
+                                     int n_chunks, hipStream_t s);
 hipError_t launch_finalize(const FinalizeArgs &a, int n_queries, hipStream_t s);
 // lists are [nq][list_stride]; a query may hold more than advertised_cap entries (a flood): such queries are only dropped
 // (flagged) when the packed buffer cannot take the sum

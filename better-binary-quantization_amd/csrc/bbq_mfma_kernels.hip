@@ -67,6 +67,10 @@ typedef int i32x4m __attribute__((ext_vector_type(4)));
 typedef int i32x16m __attribute__((ext_vector_type(16)));
 typedef float f32x16m __attribute__((ext_vector_type(16)));
 typedef int i32x8m __attribute__((ext_vector_type(8)));
+// the accept words of a filtered sweep as the kernel reads them: through the constant address space, so that a wave-uniform read is a
+// scalar load wherever it stands (a kernel that writes memory - this one appends candidates - reads a plain global pointer through the
+// vector unit once it has stored anything, and waits for every vector load in flight, the next tile's among them, to do it)
+typedef const __attribute__((address_space(4))) uint64_t *AcceptWords;
 
 constexpr int kMfmaQueries = 32;
 // The accumulator's start value lies in a binade whose ulp is the grain of the threshold:
@@ -75,12 +79,21 @@ constexpr int kMfmaQueries = 32;
 //                               value a multiple of 1/16: every partial sum is a multiple of 1/16 below 2^20, i.e. exact in f32
 // "bias" is the middle of the binade (1.5 x its lower end); the sum of the terms must stay below a quarter of the binade's lower end
 // so that every partial sum stays inside it.
+// "pass_none" (the filtered family: the start value of a row its filter rejects) mirrors pass_all below the bias: a value inside the
+// binade, a quarter of the binade's lower end below its middle.  The row's constants are zero, so its accumulator ends at exactly
+// pass_none + S * qcDist, and the largest S * qcDist a form admits is far below that margin:
+//   int8 form: 1536 dimensions x 127 = 195 072 < 2 097 152 (2^21), and 10 485 760 = pass_none >= 2^23: the sum stays in [2^23, bias)
+//   FP form:   1536 x 15 x S <= 23 040 for S = 1 (5 760 at S = 1/4, where 15 is reached; the values a larger S goes with are smaller)
+//              < 131 072 (2^17), and 655 360 = pass_none >= 2^19: the sum stays in [2^19, bias)
+// so no pair of a rejected row ends above the bias, whatever the query (tests/test_prefilter_reject_cpu.py restates this in numpy).
 template <bool FP> struct MfmaNum;
 template <> struct MfmaNum<false> {
-  static constexpr float S = 1.0f, ulp = 1.0f, bias = 12582912.0f, mag_limit = 4000000.0f, pass_all = 12582912.0f + 2097152.0f;
+  static constexpr float S = 1.0f, ulp = 1.0f, bias = 12582912.0f, mag_limit = 4000000.0f, pass_all = 12582912.0f + 2097152.0f,
+                         pass_none = 12582912.0f - 2097152.0f;
 };
 template <> struct MfmaNum<true> {   // S is chosen per call: 1/4 for query values up to 15, 1/2 up to 7, 1 up to 3 (MfmaArgs::fp_scale)
-  static constexpr float S = 0.25f, ulp = 0.0625f, bias = 786432.0f, mag_limit = 110000.0f, pass_all = 786432.0f + 131072.0f;
+  static constexpr float S = 0.25f, ulp = 0.0625f, bias = 786432.0f, mag_limit = 110000.0f, pass_all = 786432.0f + 131072.0f,
+                         pass_none = 786432.0f - 131072.0f;
 };
 
 // (z_threshold - the conservative lower edge, in z-space, of "score > theta" for one query - lives in bbq_kernel_common.h)
@@ -107,14 +120,17 @@ template <> struct MfmaNum<true> {   // S is chosen per call: 1/4 for query valu
 // gets zero constants and K = pass_all, a value inside the binade that no threshold reaches: every one of its pairs passes and is
 // scored exactly, and the difference to the start value is still qcDist.  A query that accepts everything (no threshold yet) is not
 // swept here at all: the prologue flags it, as its candidates would overflow every list of this kernel anyway.
+// A row that the filter of a filtered sweep rejects (FILT, `accepted` false) gets zero constants as well, and K = pass_none: none of
+// its pairs passes.  The reject comes last, so it holds for a weird row too: a rejected row is never scored, whatever it holds.
 struct RowK {
   float r0, r1, r2, r3, K;
 };
 // `x1` is what r1 is made of; `x1_bound` >= |x1| is what the magnitude budget uses - the dimension for a row whose component sum is
 // its popcount: every constant but r1 is then known before the popcount, and the start-value MFMAs that do not need r1 run in front
 // of it (start_values: K first)
-template <bool FP>
-__device__ __forceinline__ RowK row_constants_early(double al, double au, double add, float x1_bound, float D, int sim, const float *__restrict__ gmax, float &rho_out, bool &ok_out) {
+template <bool FP, bool FILT = false>
+__device__ __forceinline__ RowK row_constants_early(double al, double au, double add, float x1_bound, float D, int sim, const float *__restrict__ gmax, float &rho_out, bool &ok_out,
+                                                    bool accepted = true) {
   using N = MfmaNum<FP>;
   const float lxf = (float)(au - al), alf = (float)al, addf = (float)add;
   const float r0 = __builtin_amdgcn_rcpf(lxf);
@@ -126,12 +142,14 @@ __device__ __forceinline__ RowK row_constants_early(double al, double au, double
   k.r3 = (sim == 0 ? addf : -addf) * r0;
   // gmax: S * max over the workgroup's queries of |zth / beta|, |ay / ly|, |y1|, 1 / beta, and S * max sum of query values
   const float mag = fmaf(gmax[0], fabsf(r0), fmaf(gmax[1], fmaf(fabsf(rho), D, x1_bound), fmaf(gmax[2], fabsf(rho), fmaf(gmax[3], fabsf(k.r3), gmax[4]))));
-  const bool ok = lxf > 0.0f && mag < N::mag_limit;  // NaN anywhere: not ok
+  bool ok = lxf > 0.0f && mag < N::mag_limit;  // NaN anywhere: not ok
+  if constexpr (FILT) ok = ok && accepted;     // (a rejected row's r1 stays zero with the others: the caller sets it by `ok`)
   if (ok) {
     k.K = N::bias + N::ulp * ceilf(fmaf(mag, 9.5367431640625e-07f / N::ulp, 2.25f));  // whole ulps above 2.25 ulp + 2^-20 * mag: 3 for an ordinary row
   } else {
     k.r0 = k.r2 = k.r3 = 0.0f;
     k.K = N::pass_all;
+    if constexpr (FILT) k.K = accepted ? N::pass_all : N::pass_none;
   }
   rho_out = rho;
   ok_out = ok;
@@ -256,8 +274,30 @@ __host__ __device__ constexpr int mfma_query_bytes(int w16, bool fp) { return fp
 // constants are derived once, then each group runs its own contraction and test.  With ONE group per tile load the 10 M-row sweep reads
 // 120 B per row and 32 queries - 1.2 GB in ~175 us, within a few per cent of what the memory side delivers - so both bounds are met at
 // once; two groups halve the bytes, the popcounts, the conversions and the loads per query.
-template <int W, bool COMPACT, bool FP, int G>
-__global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kernel(const MfmaArgs a) {
+//
+// Accept: empty - the unfiltered sweep, exactly the kernel it was - or one `const uint64_t *`, the accept words of a filtered search (FILT;
+// accept[tile] bit l = tile row l, bits at and beyond n_rows clear: bbq_filter.cpp), as in bbq_scan_kernel (bbq_scan_body.h).  The
+// filtered family differs in three places:
+//  * a tile whose accept word is zero is skipped: no load, no constants, no popcount, no contraction.  The word is wave-uniform (a wave's
+//    tile IS one word) and read through the scalar unit.  A wave WALKS the tiles of its slot that have an accepted row: where the
+//    unfiltered kernel loads the slot's tile of the next chunk - behind the last group's contraction, into the same registers - this one
+//    loads the slot's next tile whose word is not zero, however many chunks ahead, and goes there next; a skipped tile is never the
+//    current one, so the load behind it needs no place of its own (a second load site in the loop cost a copy of the whole tile and
+//    spills).  The first tile in front of the prologue is found the same way.  The word of the next chunk's tile is requested at the
+//    head of the current tile and arrives with the tile's first LDS reads, a contraction ahead of the branch on it: a wave never waits
+//    for a word and then for the tile's loads in series in front of a tile it sweeps (docs/dropped.md, "The early order in the filtered
+//    family": what that cost the per-query sweep).  Only behind a run of EMPTY tiles does it wait for words, one scalar-cache round
+//    trip each (the waves of a workgroup read consecutive words, one 64-byte line per chunk).
+//  * a rejected row of a partly accepted tile gets zero constants and K = pass_none (row_constants_early): none of its pairs survives the
+//    pre-filter, so it is never scored and its NaN raises no flag; the survivors' path tests the accept bit once more next to rows_here.
+//  * nothing else: two groups per tile load, LDS layout, survivor queue, staging and append path are the unfiltered kernel's.
+template <int W, bool COMPACT, bool FP, int G, class... Accept>
+__global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kernel(const MfmaArgs a, const Accept... accept_arg) {
+  constexpr bool FILT = sizeof...(Accept) > 0;
+  static_assert(sizeof...(Accept) <= 1, "at most the accept words");
+  const uint64_t *__restrict__ accept = nullptr;
+  if constexpr (FILT) accept = (accept_arg, ...);
+  (void)accept;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using N = MfmaNum<FP>;
   using Acc = typename std::conditional<FP, f32x16m, i32x16m>::type;
@@ -295,7 +335,30 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
   const int cpb = a.chunks_per_block;
   const int lc0 = blockIdx.x * cpb;
   TileRegs<W, COMPACT> t;
-  {
+  // FILT: a wave walks only the tiles of its slot whose accept word is not zero, each wave at its own pace (nothing below synchronises the
+  // waves before the staged lists are flushed).  ci_first = the workgroup's chunk its walk begins at, ci_step = where it goes from the
+  // current one, cend = its end, aw = the accept word of its current tile, awords[c * kTilesPerChunk] = the word of its tile in chunk c:
+  // all wave-uniform, in scalar registers
+  int ci_first = 0, ci_step = 0, cend = 0;
+  uint64_t aw = 0;
+  AcceptWords awords = nullptr;
+  (void)ci_first, (void)ci_step, (void)cend, (void)aw, (void)awords;
+  if constexpr (FILT) {
+    const int64_t t0 = (a.s.chunk_begin + lc0) * kTilesPerChunk + __builtin_amdgcn_readfirstlane(wave);
+    // chunks of this workgroup that exist in the launch and hold a tile of this slot (<= 0: none)
+    cend = (int)max((int64_t)0, min((int64_t)min(cpb, a.s.n_chunks - lc0), (n_tiles - t0 + kTilesPerChunk - 1) / kTilesPerChunk));
+    awords = (AcceptWords)accept + t0;
+    // (the words a wave waits for in front of loads: behind them stands the prologue, not a tile)
+    for (; ci_first < cend; ++ci_first) {
+      aw = awords[(int64_t)ci_first * kTilesPerChunk];
+      if (aw != 0) break;
+    }
+    // (the lane through an empty asm, as at the loads in the walk: what is derived from it here is otherwise shared with the flush at
+    // the kernel's end and kept - spilled, in the widest instantiations - across all of it)
+    int lane_first = lane;
+    asm volatile("" : "+v"(lane_first));
+    if (ci_first < cend) load_tile_regs<W, COMPACT>(t, a.s.idx, t0 + (int64_t)ci_first * kTilesPerChunk, lane_first);
+  } else {
     const int64_t t0 = (a.s.chunk_begin + lc0) * kTilesPerChunk + wave;
     if (lc0 < a.s.n_chunks && t0 < n_tiles) load_tile_regs<W, COMPACT>(t, a.s.idx, t0, lane);
   }
@@ -318,6 +381,10 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
         if (A < 1.0e30) {  // (also false for NaN)
           qk.x = A > -3.0e38 ? (float)A : -3.0e38f;            // a threshold beyond every score: nothing passes
           qk.y = (float)(-(double)S * (p.ay / p.ly));
+          // FILT: kept finite.  mfma_query_ok admits |ay / ly| up to 1e60, an infinite f32: every row is weird for such a query (its
+          // magnitude budget is infinite), so this constant only ever meets r1 = 0 - where inf x 0 would make a rejected row's start
+          // value NaN - whose bits compare above the bias - instead of pass_none
+          if constexpr (FILT) qk.y = fminf(fmaxf(qk.y, -3.0e38f), 3.0e38f);
           qk.z = (float)(-(double)S * p.y1);
           qk.w = (float)(-(double)S / beta);
           if (fabsf(qk.x) < 1.0e30f) atomicMax(reinterpret_cast<uint32_t *>(s_gmax), __float_as_uint(fabsf(qk.x) * 1.0000002f));  // non-negative floats order like their bits
@@ -353,7 +420,7 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
   const int sim = s_qp[0].sim;                  // uniform over the call
   const float Df = (float)a.s.idx.geom.dim;
 #pragma unroll 1
-  for (int ci = 0; ci < cpb; ++ci) {
+  for (int ci = FILT ? ci_first : 0; ci < (FILT ? cend : cpb); ci = FILT ? ci_step : ci + 1) {   // (FILT: to the next chunk with a tile to sweep)
   const int lc = lc0 + ci;           // chunk index inside this launch
   if (lc >= a.s.n_chunks) break;     // block-uniform
   const int64_t chunk = a.s.chunk_begin + lc;
@@ -361,13 +428,20 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
   // tile, the next tile's address - is 64-bit vector arithmetic)
   const int64_t tile_v = chunk * kTilesPerChunk + wave;
   const int64_t tile = ((int64_t)__builtin_amdgcn_readfirstlane((int)(tile_v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)tile_v);
+  // FILT: where the walk goes from here (set where the next tile is loaded) and the accept word of the slot's tile in the next chunk,
+  // requested here: a tile ahead of the branch on it (read at a clamped index: nothing is read for it beyond the walk's end)
+  uint64_t aw_next = 0, aw_ahead = 0;
+  (void)aw_next, (void)aw_ahead;
+  if constexpr (FILT) ci_step = cend;
+  if constexpr (FILT) aw_ahead = awords[(int64_t)min(ci + 1, cend - 1) * kTilesPerChunk];
 
-  if (tile < n_tiles) {  // wave-uniform
+  if (tile < n_tiles) {  // wave-uniform (FILT: always - the walk stops at tiles that exist and have an accepted row)
     // ---- my row's constants (tile row `lane`), then both row groups' through one swap each: [0] = row n, [1] = row 32 + n
     // (every constant but r1 first: the start-value MFMAs that do not need the popcount are issued in front of it)
     float rho;
     bool row_ok;
-    RowK mine = row_constants_early<FP>(t.lu.x, t.lu.y, t.add, a.s.idx.geom.has_x1 ? fabsf((float)t.x1) * 1.0000002f : Df, Df, sim, s_gmax, rho, row_ok);
+    RowK mine = row_constants_early<FP, FILT>(t.lu.x, t.lu.y, t.add, a.s.idx.geom.has_x1 ? fabsf((float)t.x1) * 1.0000002f : Df, Df, sim, s_gmax, rho, row_ok,
+                                              !FILT || ((aw >> lane) & 1ull) != 0);
     // (K first; the last step is the only one that needs the row's popcount)
     const auto b0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(mine.K), __float_as_uint(mine.r0), false, false);
     const auto b1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(mine.r2), __float_as_uint(mine.r3), false, false);
@@ -439,7 +513,11 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
     // ---- the contraction: C[m = query][n = row of the group] += sum over the k-steps
     if constexpr (FP) {
       // LDS byte addresses of this lane's fragment of step 0 (the pointers are LDS pointers: their low 32 bits are the offset)
-      const uint32_t addr16 = (uint32_t)(uintptr_t)(s_B + h * 32 + n + lds_off), addr8 = (uint32_t)(uintptr_t)(s_B2 + h * 32 + n + lds_off);
+      // (FILT: from the lane's coordinates as they pass through an empty asm - derived here, a few instructions per tile and group; kept
+      // across the walk, as the unfiltered kernel keeps them, they were spilled in the 1024-d instantiations, which have no register left)
+      int hq = h, nq = n;
+      if constexpr (FILT) asm volatile("" : "+v"(hq), "+v"(nq));
+      const uint32_t addr16 = (uint32_t)(uintptr_t)(s_B + hq * 32 + nq + lds_off), addr8 = (uint32_t)(uintptr_t)(s_B2 + hq * 32 + nq + lds_off);
       u32x4 bq;
       u32x2 bq2;
       // (the swapped words are the same for every group: named here, or their 96 masked forms are computed once and kept - spilled)
@@ -471,7 +549,27 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
       // being carried around the loop in four registers that the two-group kernel does not have)
       int lane_here = lane;
       asm volatile("" : "+v"(lane_here));
-      if (ci + 1 < cpb && lc + 1 < a.s.n_chunks && tn < n_tiles) load_tile_regs<W, COMPACT>(t, a.s.idx, tn, lane_here);
+      if constexpr (FILT) {
+        // the slot's next tile with an accepted row: the next chunk's (its word was requested a tile ago) or, behind tiles without one,
+        // a later chunk's - one scalar read each, through the scalar cache, where the workgroup's waves share one line per chunk
+        int cn = ci + 1;
+        uint64_t wn = aw_ahead;
+        while (cn < cend && wn == 0) {
+          ++cn;
+          wn = awords[(int64_t)min(cn, cend - 1) * kTilesPerChunk];
+        }
+        if (cn < cend) {
+          load_tile_regs<W, COMPACT>(t, a.s.idx, tile + (int64_t)(cn - ci) * kTilesPerChunk, lane_here);
+        } else {
+          // the walk ends here and nothing reads the tile's corrections again: said so, or they are kept across the contraction for
+          // this path (the inline 1024-d FP instantiation of two groups spilled 16 bytes for it)
+          t.lu.x = t.lu.y = t.add = t.x1 = 0.0;
+        }
+        ci_step = cn;
+        aw_next = wn;
+      } else {
+        if (ci + 1 < cpb && lc + 1 < a.s.n_chunks && tn < n_tiles) load_tile_regs<W, COMPACT>(t, a.s.idx, tn, lane_here);
+      }
     }
     // ---- any accumulator above the bias?
     // (compared as integers in both forms: positive floats order like their bits, a negative start value - a lane without a query - is
@@ -517,7 +615,8 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
           const bool above = abits(av) > (int)__float_as_uint(N::bias);
           if (__any(above)) {  // wave-uniform: most accumulators have no survivor in any lane
             const int m = (r & 3) + 8 * (r >> 2) + 4 * h2;
-            if (above && m < nbg && rit < rows_here) {
+            // (FILT: the accept bit as a second guard - a rejected row's pairs end below the bias, this keeps it so by construction)
+            if (above && m < nbg && rit < rows_here && (!FILT || ((aw >> rit) & 1ull) != 0)) {
               uint32_t qc;
               if constexpr (FP) qc = (uint32_t)((av - init[r]) * (1.0f / S));   // both on the 1/16 grid inside one binade: exact (S is a power of two)
               else qc = (uint32_t)(av - init[r]);
@@ -559,6 +658,7 @@ __global__ __launch_bounds__(kChunkRows, W <= 8 ? 4 : 2) void bbq_scan_mfma_kern
     }
     }  // groups of this workgroup
   }
+  if constexpr (FILT) aw = aw_next;
   }  // chunks of this workgroup
   // the workgroup's staged candidates go to the queries' lists (unordered inside the segment; the finalize launch takes its keys from
   // there and the rare host replay sorts)
@@ -603,7 +703,7 @@ static int mfma_groups_per_block(const ScanArgs &a, int groups, bool fp) {
 }
 
 template <int W, bool COMPACT, bool FP>
-static hipError_t launch_mfma_t(MfmaArgs a, int nq, int nc, hipStream_t s) {
+static hipError_t launch_mfma_t(MfmaArgs a, const uint64_t *accept, int nq, int nc, hipStream_t s) {
   const int groups = (nq + kMfmaQueries - 1) / kMfmaQueries;
   a.groups_per_block = mfma_groups_per_block(a.s, groups, FP);
   a.stage_cap = a.groups_per_block == 2 ? std::min<int>(a.s.cap, kMfmaStageCapTwo) : a.s.cap;
@@ -619,6 +719,18 @@ static hipError_t launch_mfma_t(MfmaArgs a, int nq, int nc, hipStream_t s) {
   if (cpb > 12) cpb = std::min<int64_t>(kMfmaMaxChunksPerBlock, std::max<int64_t>(4, (int64_t)llround(sqrt((double)units / 220.0))));
   a.chunks_per_block = (int)cpb;
   dim3 grid((unsigned)((nc + a.chunks_per_block - 1) / a.chunks_per_block), (unsigned)grid_y, 1), block(kChunkRows, 1, 1);
+  if (accept) {  // the filtered family (same shapes, same LDS; the accept words as the kernel's second argument)
+    auto kern = bbq_scan_mfma_kernel<W, COMPACT, FP, 1, const uint64_t *>;
+    if constexpr (mfma_two_groups_built(W, FP)) {
+      if (a.groups_per_block == 2) kern = bbq_scan_mfma_kernel<W, COMPACT, FP, 2, const uint64_t *>;
+    }
+    if (smem > 64 * 1024) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, block, smem, s, a, accept);
+    return hipGetLastError();
+  }
   auto kern = bbq_scan_mfma_kernel<W, COMPACT, FP, 1>;
   if constexpr (mfma_two_groups_built(W, FP)) {
     if (a.groups_per_block == 2) kern = bbq_scan_mfma_kernel<W, COMPACT, FP, 2>;
@@ -632,9 +744,9 @@ static hipError_t launch_mfma_t(MfmaArgs a, int nq, int nc, hipStream_t s) {
 }
 
 template <int W>
-static hipError_t launch_mfma_w(const MfmaArgs &a, bool compact, bool fp, int nq, int nc, hipStream_t s) {
-  if (compact) return fp ? launch_mfma_t<W, true, true>(a, nq, nc, s) : launch_mfma_t<W, true, false>(a, nq, nc, s);
-  return fp ? launch_mfma_t<W, false, true>(a, nq, nc, s) : launch_mfma_t<W, false, false>(a, nq, nc, s);
+static hipError_t launch_mfma_w(const MfmaArgs &a, const uint64_t *accept, bool compact, bool fp, int nq, int nc, hipStream_t s) {
+  if (compact) return fp ? launch_mfma_t<W, true, true>(a, accept, nq, nc, s) : launch_mfma_t<W, true, false>(a, accept, nq, nc, s);
+  return fp ? launch_mfma_t<W, false, true>(a, accept, nq, nc, s) : launch_mfma_t<W, false, false>(a, accept, nq, nc, s);
 }
 
 // the sweep appends its candidates to the queries' lists (ScanArgs::append_lists): it has no chunk-slot output
@@ -650,19 +762,31 @@ int mfma_queries_per_tile_load(const ScanArgs &a, int n_queries, bool fp) {
   return kMfmaQueries * mfma_groups_per_block(a, (n_queries + kMfmaQueries - 1) / kMfmaQueries, fp);
 }
 
-hipError_t launch_scan_mfma(const ScanArgs &sa, const uint8_t *qbytes, const float *qmax, float fp_scale, int n_queries, int n_chunks, hipStream_t s) {
+// accept: null - the unfiltered sweep - or the accept words of a filtered one
+static hipError_t launch_scan_mfma_any(const ScanArgs &sa, const uint64_t *accept, const uint8_t *qbytes, const float *qmax, float fp_scale, int n_queries, int n_chunks,
+                                       hipStream_t s) {
   if (!sa.append_lists) return hipErrorInvalidValue;
   if (n_chunks <= 0 || n_queries <= 0) return hipSuccess;
   const bool fp = fp_scale > 0.0f;
   MfmaArgs a{sa, qbytes, qmax, n_queries, 1, fp_scale, 1, sa.cap, kMfmaQueueCap};
   const bool compact = sa.idx.geom.layout == kLayoutCompact;
   switch (sa.idx.geom.w16) {
-    case 1: return launch_mfma_w<1>(a, compact, fp, n_queries, n_chunks, s);
-    case 6: return launch_mfma_w<6>(a, compact, fp, n_queries, n_chunks, s);
-    case 8: return launch_mfma_w<8>(a, compact, fp, n_queries, n_chunks, s);
-    case 12: return launch_mfma_w<12>(a, compact, fp, n_queries, n_chunks, s);
+    case 1: return launch_mfma_w<1>(a, accept, compact, fp, n_queries, n_chunks, s);
+    case 6: return launch_mfma_w<6>(a, accept, compact, fp, n_queries, n_chunks, s);
+    case 8: return launch_mfma_w<8>(a, accept, compact, fp, n_queries, n_chunks, s);
+    case 12: return launch_mfma_w<12>(a, accept, compact, fp, n_queries, n_chunks, s);
     default: return hipErrorInvalidValue;
   }
+}
+
+hipError_t launch_scan_mfma(const ScanArgs &sa, const uint8_t *qbytes, const float *qmax, float fp_scale, int n_queries, int n_chunks, hipStream_t s) {
+  return launch_scan_mfma_any(sa, nullptr, qbytes, qmax, fp_scale, n_queries, n_chunks, s);
+}
+
+hipError_t launch_scan_mfma_filtered(const ScanArgs &sa, const uint64_t *accept, const uint8_t *qbytes, const float *qmax, float fp_scale, int n_queries, int n_chunks,
+                                     hipStream_t s) {
+  if (!accept) return hipErrorInvalidValue;
+  return launch_scan_mfma_any(sa, accept, qbytes, qmax, fp_scale, n_queries, n_chunks, s);
 }
 
 }  // namespace bbq

@@ -255,8 +255,9 @@ int bbq_search_raw_batch(bbq_index *idx, int32_t n_queries, const float *queries
  * A filter belongs to ONE single-device index (its size, its device), owns its device memory, is read-only after creation and may
  * be shared by any number of calls and threads.  Using it with an index of another size or device: BBQ_ERR_INVALID_ARG.
  * Out of scope: a multi-device handle (bbq_index_create_multi), a non-root shard and an index with a pilot replica return
- * BBQ_ERR_UNSUPPORTED.  A filtered call always takes the pipelined per-query sweep (sweep_share and the latency_* options do not
- * change its path); k > 4096 and force_dense take the dense path over the accepted rows. */
+ * BBQ_ERR_UNSUPPORTED.  A filtered call takes the pipelined per-query sweep, or with sweep_share 32 the matrix-core shared sweep
+ * behind the first k accepted rows (sweep_share 4 / 8 and the latency_* options do not change its path); k > 4096 and force_dense
+ * take the dense path over the accepted rows. */
 typedef struct bbq_filter bbq_filter;   /* opaque: an accept set of one index, resident on that index's device */
 /* accept_bits [ceil(n_rows/64)] little-endian words: row r is accepted iff (accept_bits[r >> 6] >> (r & 63)) & 1; bits at and beyond
  * n_rows are ignored.  n_words must be ceil(bbq_index_size(idx)/64). */
@@ -732,7 +733,8 @@ int bbq_reset_stats(bbq_index *idx);
  *     the score formula, for every query whose corrections have f32 images (others keep the f64 bound); 0: always the f64 bound through
  *     the similarity transform.  A pre-filter in front of the exact score either way: never a different answer
  *   replay_threads 1..256 (half the host cores, at most 16)   flood_rows 0..2^24 (262144)   force_dense 0|1 (0)
- *   sweep_share 1|4|8|32 (1: every query sweeps the index itself; 32: shared sweep on the matrix cores, groups of 32 queries, two groups per load of the rows)
+ *   sweep_share 1|4|8|32 (1: every query sweeps the index itself; 32: shared sweep on the matrix cores, groups of 32 queries, two groups per load of the rows;
+ *     32 also serves bbq_search_filtered_batch - tiles without an accepted row are not loaded; 4 and 8 do not: a filtered call sweeps per query under them)
  *   device_select 0|1 (1: for k <= 1024 the device selects and sorts the answer itself whenever no two scores in or at the edge of it
  *   compare equal - then the reference heap provably returns that order - and the host replays the heap only for the rest)
  *   latency_queries 0..1024 (4), latency_growth 2..4096 (64): calls with at most latency_queries queries walk the index in

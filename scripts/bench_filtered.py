@@ -4,6 +4,7 @@ interleaved call by call so that drift of the box hits all of them alike.  Print
 
   python scripts/bench_filtered.py                 # 10 M x 768 synthetic rows, queryBits 4, k = 100, 256 queries per call
   python scripts/bench_filtered.py --rows 2000000 --steps 6 --check 1
+  python scripts/bench_filtered.py --sweep-share 32   # every leg, the unfiltered one too, on the matrix-core shared sweep (profiles/filtered_search_shared.json)
 
 Legs: (a) unfiltered, (b) all-ones filter = the cost of the mechanism, (c) random filters at 50 / 10 / 1 / 0.1 %, (d) a contiguous 10 %
 block at the end of the index, (e) 1000 random rows.  Per leg: q/s (host clock around calls that return with their answers), the
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--check", type=int, default=1, help="queries per filtered leg held to the oracle (0: none)")
     ap.add_argument("--legs", default="", help="comma-separated subset of the legs (default: all), e.g. unfiltered,all_ones for a profiler run")
+    ap.add_argument("--sweep-share", type=int, default=1, choices=(1, 32), help="the index's sweep_share option for every leg (1: the per-query sweeps)")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
     import torch  # noqa: F401  (first: one HIP runtime for torch and libbbq, as bench.py does)
@@ -46,6 +48,8 @@ def main():
     codes, corr = bench.synth_rows(1, 0, n, (dim + 7) // 8)
     cdp = float(B.centroid_dp(bench.synth_centroid(dim)))
     ix = B.Index(codes, corr, dim, cdp, device=args.device)
+    if args.sweep_share != 1:
+        ix.set_option("sweep_share", args.sweep_share)
     rng = np.random.default_rng(41)
     masks = {"all_ones": np.ones(n, bool)}
     for name, share in (("random_50pct", 0.5), ("random_10pct", 0.1), ("random_1pct", 0.01), ("random_0.1pct", 0.001)):
@@ -98,6 +102,8 @@ def main():
                 checked += 1
     res = {"metric": "filtered_search_qps", "rows": n, "dim": dim, "k": k, "query_bits": QB, "queries_per_call": Q, "timed_calls_per_leg": args.steps,
            "bytes_per_row": ix.bytes_per_row, "answers_checked_against_oracle": checked, "legs": {}}
+    if args.sweep_share != 1:
+        res["sweep_share"] = args.sweep_share
     base = args.steps * Q / seconds["unfiltered"]
     for leg in legs:
         s = stats[leg]
