@@ -128,6 +128,17 @@ bool digit_planes_for_call(const bbq_index *ix, int planes) {
   return ix->opt_digit_planes != 0 && ix->geom.store_bits == 1 && planes == 4 && row_sums_for_launch(ix) && row_sums_fit(ix->geom);
 }
 
+// tiles a wave of a per-query sparse sweep takes one after the other (option tiles_per_wave; the launch ignores it wherever it has no such
+// twin, launch_scan_t).  An explicit 1, 2, 4 or 8 is taken as it is.  Automatic: per row width, the fastest value that passed BOTH tests -
+// its twin comes out of the compiler without scratch and with no fewer waves per SIMD than the one-tile kernel (scripts/scan_resources.py),
+// and its slowest run was faster than the parent's fastest by more than the parent's own spread (Measurement) - and 1 where
+// none did.  768-d: 2 (58 registers, 8 waves like the one-tile kernel; +23 %).  4 and 8 tiles were faster still at every width, and 2 at
+// 1024-d and 1536-d was faster than 1, but each of those twins reports a wave or two fewer: docs/dropped.md, "tiles per wave".
+int tiles_per_wave_for(const bbq_index *ix) {
+  if (ix->opt_tiles_per_wave > 0) return ix->opt_tiles_per_wave;
+  return ix->geom.w16 == 6 ? 2 : 1;
+}
+
 // ------------------------------------------------------------------------------------------------ plan
 
 static int cap_for(int64_t k, int64_t rows_before) {
@@ -471,7 +482,7 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
     else if (c.filter)  // (its plan has sparse segments only; sweep_share 4 / 8 never reach a filtered call, 32 falls back to here)
       HIPCHK(launch_scan_filtered(a, c.filter->d_bits, c.planes, nq, (int)g.n_chunks, st));
     else
-      HIPCHK(launch_scan(a, c.planes, g.dense, nq, (int)g.n_chunks, st));
+      HIPCHK(launch_scan(a, c.planes, g.dense, nq, (int)g.n_chunks, st, c.share == 1 ? tiles_per_wave_for(ix) : 1));
     if (chained) {
       HIPCHK(hipEventRecord(s.ev_big, st));
       ix->ctx->last_big_slot = my_slot;

@@ -116,6 +116,8 @@ __host__ __device__ constexpr uint32_t sweep_grid_y(int n_queries, int s) { retu
 // grid_size_x; the runtime refuses more with hipErrorInvalidConfiguration).  The plain grid has n_chunks * kChunkRows = the launch's rows
 // there, which fits for every index the library accepts (at most 2^32 - 1 rows); the reordered one has P times as many, so P = 32
 // fits up to 262 136 chunks (134 M rows) per launch, and a longer launch co-schedules fewer queries per chunk.
+// (The extent is grid.x times the BLOCK size: a launch with several tiles per wave - kChunkRows / TPW threads, bbq_scan_body.h - has a TPW-th
+// of the work-items on the same grid, so the limit of the one-tile kernel, which is the one tested here, holds for every TPW.)
 constexpr uint64_t kGridWorkItemsMax = 0xFFFFFFFFull;
 __host__ __device__ constexpr bool sweep_grid_fits(int n_chunks, int s) { return (uint64_t)sweep_grid_x(n_chunks, s) * (uint64_t)kChunkRows <= kGridWorkItemsMax; }
 // the largest s <= want with 2^s <= n_queries - a launch co-schedules no more queries than it has - whose grid the device takes

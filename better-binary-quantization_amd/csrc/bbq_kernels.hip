@@ -504,7 +504,7 @@ hipError_t launch_scan_shared(const ScanArgs &a, int planes, int share, int n_qu
   return compact ? launch_shared_q<true, 4>(a, planes, n_queries, n_chunks, s) : launch_shared_q<false, 4>(a, planes, n_queries, n_chunks, s);
 }
 
-hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries, int n_chunks, hipStream_t s) {
+hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries, int n_chunks, hipStream_t s, int tiles_per_wave) {
   if (n_chunks <= 0 || n_queries <= 0) return hipSuccess;
   const int mode = (dense ? 1 : 0) | (a.idx.geom.layout == kLayoutCompact ? 2 : 0);
   if (a.idx.geom.store_bits > 1) {
@@ -518,7 +518,7 @@ hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries,
   switch (mode) {
     case 0: return launch_scan_q<false, 0>(a, nullptr, planes, n_queries, n_chunks, s);
     case 1: return launch_scan_q<false, 1>(a, nullptr, planes, n_queries, n_chunks, s);
-    case 2: return launch_scan_q<false, 2>(a, nullptr, planes, n_queries, n_chunks, s);
+    case 2: return launch_scan_q<false, 2>(a, nullptr, planes, n_queries, n_chunks, s, tiles_per_wave);
     default: return launch_scan_q<false, 3>(a, nullptr, planes, n_queries, n_chunks, s);
   }
 }

@@ -8,7 +8,9 @@
 namespace bbq {
 
 // planes: number of query bit-planes (1, 2, 4 or 8); multi-bit index: 4 (query values <= 15) or 8
-hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries, int n_chunks, hipStream_t s);
+// tiles_per_wave (1, 2, 4 or 8): tiles a wave of the sparse sweep takes one after the other where the launch has such a twin (tiles_twin,
+// bbq_scan_body.h); 1 - and everywhere else - one tile per wave.  A speed choice only
+hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries, int n_chunks, hipStream_t s, int tiles_per_wave = 1);
 // the sparse sweep of a filtered search: accept[tile] = the tile's accept word (bit l = row l of the tile), one word per tile of a.idx
 hipError_t launch_scan_filtered(const ScanArgs &a, const uint64_t *accept, int planes, int n_queries, int n_chunks, hipStream_t s);
 // shared sweep: `share` (4 or 8) queries per workgroup reuse every loaded row (sparse segments, fixed-width dims only)

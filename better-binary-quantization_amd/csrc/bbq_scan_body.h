@@ -91,6 +91,162 @@ constexpr bool early_loads() {
   return true;
 }
 
+// ---- several tiles per wave (TPW in the kernel; option tiles_per_wave).  A workgroup of the TPW form has kTilesPerChunk / TPW waves and wave w
+// sweeps the TPW consecutive tiles wave_first_tile(TPW, w) ... + TPW - 1 of its chunk one after the other: what belongs to the workgroup or is
+// wave-uniform - the map, the query's uniforms, the staging and its barrier, the residency test, the tile's addresses, the end of the chunk -
+// is executed once for TPW tiles instead of once per tile.
+__host__ __device__ constexpr int wave_first_tile(int tpw, int wave) { return wave * tpw; }
+// the map covers the tiles of a chunk exactly once: a tile swept twice would list its rows twice, one left out would only lose rows
+constexpr bool wave_tiles_are_exact(int tpw) {
+  if (tpw < 1 || kTilesPerChunk % tpw != 0) return false;
+  int hits[kTilesPerChunk] = {};
+  for (int w = 0; w < kTilesPerChunk / tpw; ++w)
+    for (int t = 0; t < tpw; ++t) {
+      const int tile = wave_first_tile(tpw, w) + t;
+      if (tile < 0 || tile >= kTilesPerChunk) return false;
+      ++hits[tile];
+    }
+  for (int i = 0; i < kTilesPerChunk; ++i)
+    if (hits[i] != 1) return false;
+  return true;
+}
+static_assert(wave_tiles_are_exact(1) && wave_tiles_are_exact(2) && wave_tiles_are_exact(4) && wave_tiles_are_exact(8), "1, 2, 4 and 8 tiles per wave");
+static_assert(!wave_tiles_are_exact(0) && !wave_tiles_are_exact(3) && !wave_tiles_are_exact(16), "no other count divides a chunk's tiles");
+
+// The end of a chunk for a workgroup of NT threads, as bbq_scan_kernel's body has it (sparse modes): the second barrier, then the append
+// path, or the chunk's slot - the flood tier where the slot does not hold the candidates - and the count word.  Used by the kernels with
+// several tiles per wave alone; the one-tile kernels keep theirs inline.
+template <int NT>
+__device__ __forceinline__ void sweep_chunk_end(const ScanArgs &a, const SweepCoord wg, const int q, uint64_t *s_ent, uint32_t *s_cnt) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  if (a.append_lists) {  // workgroup-uniform
+    const uint32_t cnt = *s_cnt;
+    if (cnt == 0) return;
+    __syncthreads();  // everyone has read *s_cnt: it takes the reserved offset
+    append_to_list<NT>(s_ent, cnt, a.append_counts + (size_t)q * kAppendStride, a.append_base[2 * q], a.append_lists + (size_t)q * a.append_cap,
+                       a.append_cap, a.flags + q, s_cnt);
+    return;
+  }
+  uint32_t cnt = *s_cnt;
+  uint64_t *__restrict__ slot0 = a.entries + ((size_t)q * a.n_chunks + wg.chunk_local) * (size_t)a.cap;
+  uint64_t *__restrict__ out = slot0;
+  uint32_t count_word = cnt;
+  if (cnt > (uint32_t)a.cap) {  // workgroup-uniform
+    bool parked = false;
+    if (a.ovf) {
+      // flood (e.g. rows stored cluster by cluster and this is the query's cluster): one block of the query's overflow
+      // area takes the whole chunk, so the list stays row-ordered and the query stays on the sparse path
+      __syncthreads();  // everyone has read *s_cnt
+      if (tid == 0) *s_cnt = atomicAdd(a.ovf_counts + q, cnt);
+      __syncthreads();
+      const uint32_t off = *s_cnt;
+      if ((uint64_t)off + cnt <= (uint64_t)a.ovf_cap) {
+        out = a.ovf + (size_t)q * a.ovf_cap + off;
+        count_word = kCountRedirect | cnt;
+        if (tid == 0) slot0[0] = off;
+        parked = true;
+      }
+    }
+    if (!parked) {
+      if (tid == 0) atomicOr(a.flags + q, kFlagOverflow);
+      cnt = min(cnt, (uint32_t)a.cap);
+      count_word = cnt;
+    }
+  }
+  write_ranked(s_ent, cnt, out, tid, NT);
+  if (tid == 0) a.counts[(size_t)q * a.n_chunks + wg.chunk_local] = count_word;
+}
+
+// The sweep of a wave's TPW > 1 tiles: the digit form of the unfiltered compact sweep (MODE 2, RS, DG) in the early order, nothing else.
+// Tile 0 is loaded in front of the staging and the barrier exactly as the TPW = 1 kernel loads its one tile (the same two arms of the scalar
+// branch, the masks the oldest load in flight); tile t + 1's loads are issued as soon as tile t's popcounts are done - its code registers are
+// dead there - so the bound and the exact path of tile t run with them in flight, and no two tiles' codes are held at once.  The loop over the
+// wave's tiles is unrolled: as a loop, the next tile's correction word, row sum and additive bound came back in registers of their own and
+// the copies at the back edge waited for every load of the tile.  A tile's addresses are the first tile's plus constant strides (tile_stride,
+// the 128 bytes of a tile's row sums, the 8 of its add_range).  A wave whose next tile lies beyond the index leaves: the tiles are consecutive.
+// Per row it computes what the kernel computes: the same integer, the same bound, the same f64 score.  false: an idle workgroup, which leaves.
+template <int W, int TPW, int NT>
+__device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepCoord wg, const bool idle, const int q, u32x4 *s_planes, uint64_t *s_ent,
+                                                 uint32_t *s_cnt, const uint32_t stage_cap, bool &nan_seen) {
+  constexpr int QU = kDigitMasks;
+  static_assert(W * QU <= NT, "one staging pass: every unit of the query has a thread");
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)a.qdigits_at + (size_t)q * W * QU;
+  const QueryParams p = a.qparams[q];
+  const Threshold th = a.theta[q];
+  const uint32_t theta = th.key;
+  const int64_t chunk = a.chunk_begin + wg.chunk_local;
+  const int64_t n_tiles = (a.idx.n_rows + kTileRows - 1) / kTileRows;
+  const int64_t tile0 = chunk * kTilesPerChunk + wave_first_tile(TPW, wave);
+  const bool has_tile = !idle && tile0 < n_tiles;  // wave-uniform, decided on the scalar unit
+  const bool resident = chunk_is_resident(chunk, a.idx);
+  const int64_t tile_stride = a.idx.geom.tile_stride;
+  // the addresses of the wave's first tile
+  const uint8_t *__restrict__ tp = a.idx.tiles + tile0 * tile_stride;
+  const uint32_t *__restrict__ rs = reinterpret_cast<const uint32_t *>(a.idx.row_sums + ((tile0 * kTileRows + lane) & ~(int64_t)1));
+  const float *__restrict__ ar = a.idx.add_range + tile0 * 2 + (p.sim == 0 ? 0 : 1);  // tile_add_bound's choice
+  u32x4 c[W];
+  uint32_t cw, ones;
+  float aadd;
+  f64x2 lu = {0.0, 0.0};
+  double xadd = 0.0, x1 = 0.0;
+  if (has_tile) {
+    u32x4 staged;
+    auto load_masks = [&]() { if (tid < W * QU) staged = gp[tid]; };
+    load_tile<W, 1, true>(tp, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, rs, &ones, load_masks);
+    aadd = *ar;
+    if (tid < W * QU) s_planes[tid] = staged;
+    asm volatile("; staged with the first tile's loads in flight" ::: "memory");
+  } else {
+    u32x4 staged;
+    if (tid < W * QU) staged = gp[tid];
+    if (tid < W * QU) s_planes[tid] = staged;
+    asm volatile("; staged without a tile" ::: "memory");
+  }
+  if (tid == 0) *s_cnt = 0;
+  if (idle) return false;
+  __syncthreads();  // LDS only: a wave that staged nothing passes it with its tile's loads in flight
+  if (!has_tile) return true;
+
+  const int64_t tiles_left = n_tiles - tile0;
+  const int my_tiles = tiles_left < TPW ? (int)tiles_left : TPW;  // >= 1, wave-uniform
+  const int64_t row0 = tile0 * kTileRows;
+  const uint32_t pick_at = (uint32_t)(lane & 1) << 4;  // the lane's half of its pair of row sums
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) {
+    uint32_t qc = tile_digit_dot<W>(c, s_planes, 0u, p.digit_k);
+    __builtin_amdgcn_sched_barrier(0);  // (the loads below and the pick of the sum stay behind the popcounts, as the pick does in the TPW = 1 kernel)
+    const uint32_t sum = __builtin_amdgcn_ubfe(ones, pick_at, 16u);
+    qc += sum << 2;  // digit_dot's 4 * ones: u32 arithmetic, the same integer in either order
+    const uint32_t cw_t = cw;
+    const float aadd_t = aadd;
+    const bool more = t + 1 < TPW && t + 1 < my_tiles;
+    if (more) {  // the next tile's loads, its codes into the registers this tile is done with
+      load_tile<W, 1, true>(tp + (t + 1) * tile_stride, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, rs + (t + 1) * (kTileRows / 2), &ones);
+      aadd = ar[(t + 1) * 2];
+    }
+    const int64_t rows_left = a.idx.n_rows - (row0 + t * kTileRows);  // > 0: the tile exists
+    const bool valid = (uint32_t)lane < (uint32_t)(rows_left < kTileRows ? rows_left : kTileRows);
+    const bool need_exact = p.fast_bound ? fast_bound_passes(valid, qc, cw_t, aadd_t, sum, p, th) : f64_bound_passes(valid, qc, cw_t, aadd_t, (double)sum, p, theta);
+    if (need_exact) {
+      const int64_t row = row0 + t * kTileRows + lane;
+      exact_corrections(a.idx.exact, row, lu, xadd);
+      const double s64 = score_f64((double)qc, lu.x, lu.y, xadd, (double)sum, p);
+      const float s32 = (float)s64;
+      if (valid && (s32 != s32)) nan_seen = true;
+      if (valid && (s32 == s32) && key_of_bits(__float_as_uint(s32)) > theta) {
+        const uint32_t slot = atomicAdd(s_cnt, 1u);
+        if (slot < stage_cap) s_ent[slot] = candidate_entry(a.row_id_base + row, s32);
+      }
+    }
+    if (!more) break;
+  }
+  return true;
+}
+
 // MODE: 0 sparse / inline corrections, 1 dense / inline, 2 sparse / compact corrections + exact gather, 3 dense / compact
 // grid = (chunks of kChunkRows rows, queries), or with ScanArgs::l2_shift = s > 0 the same pairs in the order that runs a chunk's 2^s
 // queries back to back on one XCD (sweep_coord, bbq_device.h); block = kChunkRows/64 waves: wave w handles tile w of its chunk (one
@@ -109,16 +265,19 @@ constexpr bool early_loads() {
 // DG (RS, 1-bit rows and a 4-plane query only, chosen by the launch iff ScanArgs::qdigits_at is set as well): the digit form - the workgroup
 // stages the query's kDigitMasks ternary digit masks per chunk instead of its four bit-planes, and qcDist comes out of three popcount
 // chains and the row's sum (tile_digit_dot).  The same integer, so everything behind it is the same bits.
-template <int QB, int W, int MODE, int SB = 1, bool RS = false, bool DG = false, class... Accept>
-__global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, const Accept... accept_arg) {
+// TPW (the unfiltered DG twins of tiles_twin alone, chosen by the launch from its tiles_per_wave): tiles per wave - the workgroup has
+// kTilesPerChunk / TPW waves and wave w sweeps TPW consecutive tiles of the chunk (sweep_wave_tiles, above).  1: one tile per wave, the kernel as it was.
+template <int QB, int W, int MODE, int SB = 1, bool RS = false, bool DG = false, int TPW = 1, class... Accept>
+__global__ __launch_bounds__(kChunkRows / TPW) void bbq_scan_kernel(const ScanArgs a, const Accept... accept_arg) {
   constexpr bool FILT = sizeof...(Accept) > 0;
+  static_assert(wave_tiles_are_exact(TPW) && (TPW == 1 || (DG && !FILT && MODE == 2 && W > 0)), "several tiles per wave: the unfiltered digit form of a compile-time width");
   static_assert(sizeof...(Accept) <= 1 && !(FILT && (MODE & 1)), "at most the accept bitset, and a filtered sweep is sparse");
   static_assert(!RS || (MODE & 3) == 2, "row sums are read by the sparse sweep of the compact layout alone");
   static_assert(!DG || (RS && SB == 1 && QB == 4), "the digit form: a 4-plane query against 1-bit rows whose popcounts are at hand");
   const uint64_t *__restrict__ accept = nullptr;
   if constexpr (FILT) accept = (accept_arg, ...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int NT = kChunkRows;
+  constexpr int NT = kChunkRows / TPW;  // the workgroup's threads
   constexpr bool DENSE = (MODE & 1) != 0;
   constexpr bool COMPACT = (MODE & 2) != 0;
   constexpr int QU = DG ? kDigitMasks : query_units_per_chunk(QB, SB);  // 16-byte units staged per chunk of a row
@@ -140,6 +299,18 @@ __global__ __launch_bounds__(kChunkRows) void bbq_scan_kernel(const ScanArgs a, 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
+
+  // Several tiles per wave: the wave's tiles, the NaN vote and the end of the chunk, then out.  (A block of its own in front of the kernel's
+  // body, which stays the text it was: with the body inside an else the one-tile instantiations came out of this build's compiler with
+  // other scalar code and, 66 of them, two more vector instructions per wave.  For the same reason the end of the chunk is written out
+  // twice, here through sweep_chunk_end: called from the body below, the unfiltered instantiations get other schedules.)
+  if constexpr (TPW > 1) {
+    bool nan_seen = false;
+    if (!sweep_wave_tiles<W, TPW, NT>(a, wg, idle, q, s_planes, s_ent, s_cnt, stage_cap, nan_seen)) return;
+    if (__any(nan_seen) && lane == 0) atomicOr(a.flags + q, kFlagNaN);
+    sweep_chunk_end<NT>(a, wg, q, s_ent, s_cnt);
+    return;
+  }
 
   // the tile's accept word first: its address depends on the workgroup's chunk and the wave number alone, so the scalar load travels while the
   // planes are staged and is there when the barrier opens (behind the barrier every wave paid its latency in front of its first HBM request)
@@ -367,8 +538,25 @@ constexpr bool digit_twin() {
   return W == 6 || (!FILT && (W == 8 || W == 12));
 }
 
+// The DG instantiations that have twins with several tiles per wave (TPW 2, 4 and 8): the unfiltered ones of 6, 8 and 12 chunks.  At all three
+// W * kDigitMasks <= 64, so even a workgroup of one wave stages its query in one pass.  The filtered family keeps one tile per wave: its
+// has-a-tile test needs an accept word per tile.  Which TPW a launch takes by default is decided per width from measurements, on the host
+// (tiles_per_wave_for, bbq_core.cpp).  To check again: scripts/scan_resources.py - each twin without scratch and with no fewer waves per SIMD
+// than its TPW = 1 twin - then an A/B of the width on one device.
+template <bool FILT, int QB, int W, int SB>
+constexpr bool tiles_twin() {
+  return !FILT && digit_twin<FILT, QB, W, SB>() && (W == 6 || W == 8 || W == 12);
+}
+template <int QB, int W, int MODE, int SB, int TPW>
+static void launch_tiles_twin(const ScanArgs &a, dim3 grid, size_t smem, hipStream_t s) {
+  hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, true, TPW>), grid, dim3(kChunkRows / TPW, 1, 1), smem, s, a);
+}
+
+// tiles_per_wave: 1, 2, 4 or 8 - a host-side parameter of the launch, not a kernel argument (ScanArgs keeps its size): it selects the TPW twin
+// where the launch has one (tiles_twin, and the digit twin's own conditions) and is ignored everywhere else.  Same grid, same dynamic LDS;
+// the block is kChunkRows / TPW threads.
 template <bool FILT, int QB, int W, int MODE, int SB = 1>
-static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s) {
+static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s, int tiles_per_wave = 1) {
   ScanArgs a = args;  // the map's parameters: what the kernel decodes its block index with is what the grid below is built from
   a.n_chunks = n_chunks;
   a.n_queries = n_queries;
@@ -380,19 +568,27 @@ static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, in
   if constexpr ((MODE & 3) == 2 && digit_twin<FILT, QB, W, SB>()) {
     if (a.idx.row_sums && a.qdigits_at > 0) {  // ... and the caller staged the digit masks: three planes instead of four
       const size_t smem_dg = (size_t)w16 * kDigitMasks * 16 + smem_out;
-      if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, true, const uint64_t *>), grid, block, smem_dg, s, a, accept);
+      if constexpr (tiles_twin<FILT, QB, W, SB>()) {
+        switch (tiles_per_wave) {
+          case 2: launch_tiles_twin<QB, W, MODE, SB, 2>(a, grid, smem_dg, s); return hipGetLastError();
+          case 4: launch_tiles_twin<QB, W, MODE, SB, 4>(a, grid, smem_dg, s); return hipGetLastError();
+          case 8: launch_tiles_twin<QB, W, MODE, SB, 8>(a, grid, smem_dg, s); return hipGetLastError();
+          default: break;
+        }
+      }
+      if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, true, 1, const uint64_t *>), grid, block, smem_dg, s, a, accept);
       else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, true>), grid, block, smem_dg, s, a);
       return hipGetLastError();
     }
   }
   if constexpr ((MODE & 3) == 2 && row_sums_twin<FILT, QB, W, SB>()) {
     if (a.idx.row_sums) {  // the launch's view carries the row sums: the sweep that reads them
-      if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, false, const uint64_t *>), grid, block, smem, s, a, accept);
+      if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, false, 1, const uint64_t *>), grid, block, smem, s, a, accept);
       else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true>), grid, block, smem, s, a);
       return hipGetLastError();
     }
   }
-  if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, false, false, const uint64_t *>), grid, block, smem, s, a, accept);
+  if constexpr (FILT) hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, false, false, 1, const uint64_t *>), grid, block, smem, s, a, accept);
   else hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB>), grid, block, smem, s, a);
   return hipGetLastError();
 }
@@ -417,23 +613,23 @@ static hipError_t launch_scan_mb(const ScanArgs &a, const uint64_t *accept, int 
 }
 
 template <bool FILT, int QB, int MODE>
-static hipError_t launch_scan_w(const ScanArgs &a, const uint64_t *accept, int nq, int nc, hipStream_t s) {
+static hipError_t launch_scan_w(const ScanArgs &a, const uint64_t *accept, int nq, int nc, hipStream_t s, int tpw = 1) {
   switch (a.idx.geom.w16) {
-    case 1: return launch_scan_t<FILT, QB, 1, MODE>(a, accept, nq, nc, s);    // dim <= 128
-    case 6: return launch_scan_t<FILT, QB, 6, MODE>(a, accept, nq, nc, s);    // dim 768
-    case 8: return launch_scan_t<FILT, QB, 8, MODE>(a, accept, nq, nc, s);    // dim 1024
-    case 12: return launch_scan_t<FILT, QB, 12, MODE>(a, accept, nq, nc, s);  // dim 1536
-    default: return launch_scan_t<FILT, QB, 0, MODE>(a, accept, nq, nc, s);
+    case 1: return launch_scan_t<FILT, QB, 1, MODE>(a, accept, nq, nc, s, tpw);    // dim <= 128
+    case 6: return launch_scan_t<FILT, QB, 6, MODE>(a, accept, nq, nc, s, tpw);    // dim 768
+    case 8: return launch_scan_t<FILT, QB, 8, MODE>(a, accept, nq, nc, s, tpw);    // dim 1024
+    case 12: return launch_scan_t<FILT, QB, 12, MODE>(a, accept, nq, nc, s, tpw);  // dim 1536
+    default: return launch_scan_t<FILT, QB, 0, MODE>(a, accept, nq, nc, s, tpw);
   }
 }
 
 template <bool FILT, int MODE>
-static hipError_t launch_scan_q(const ScanArgs &a, const uint64_t *accept, int planes, int nq, int nc, hipStream_t s) {
+static hipError_t launch_scan_q(const ScanArgs &a, const uint64_t *accept, int planes, int nq, int nc, hipStream_t s, int tpw = 1) {
   switch (planes) {
-    case 1: return launch_scan_w<FILT, 1, MODE>(a, accept, nq, nc, s);
-    case 2: return launch_scan_w<FILT, 2, MODE>(a, accept, nq, nc, s);
-    case 4: return launch_scan_w<FILT, 4, MODE>(a, accept, nq, nc, s);
-    default: return launch_scan_w<FILT, 8, MODE>(a, accept, nq, nc, s);
+    case 1: return launch_scan_w<FILT, 1, MODE>(a, accept, nq, nc, s, tpw);
+    case 2: return launch_scan_w<FILT, 2, MODE>(a, accept, nq, nc, s, tpw);
+    case 4: return launch_scan_w<FILT, 4, MODE>(a, accept, nq, nc, s, tpw);
+    default: return launch_scan_w<FILT, 8, MODE>(a, accept, nq, nc, s, tpw);
   }
 }
 

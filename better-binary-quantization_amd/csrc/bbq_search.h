@@ -74,6 +74,8 @@ int l2_share_shift(const bbq_index *ix);
 bool row_sums_for_launch(const bbq_index *ix);
 // does a call with `planes` bit-planes stage the digit masks for its per-query sparse sweeps (option digit_planes)?
 bool digit_planes_for_call(const bbq_index *ix, int planes);
+// tiles per wave of the per-query sparse sweeps of an index (option tiles_per_wave): what launch_scan takes
+int tiles_per_wave_for(const bbq_index *ix);
 Plan build_plan(const bbq_index *ix, int64_t k, int64_t final_k = 0, bool latency = false);
 Plan build_filtered_plan(const bbq_index *ix, const bbq_filter &f, int64_t k, int64_t final_k, bool latency);
 int ensure_slot(const SearchCall &c, Slot &s, int nq, bool own_lists);

@@ -727,6 +727,11 @@ int bbq_reset_stats(bbq_index *idx);
  *     row is 6, 8 or 12 16-byte chunks wide (641..768, 897..1024, 1409..1536 dimensions; a filtered search: 641..768 only) - where it
  *     was measured faster; 0: always bit-planes.  The digit masks are staged with the query in addition to its bit-planes (5 x 16 bytes per 128 dimensions).  The dot
  *     product is the same exact integer either way: never a different answer
+ *   tiles_per_wave -1|1|2|4|8 (-1): tiles (64 rows) a wave of the per-query sweep takes one after the other where digit_planes applies to
+ *     an unfiltered search (6, 8 or 12 chunks): the workgroup has 8 / tiles_per_wave waves, and what belongs to the workgroup or the wave -
+ *     addresses, the query's uniforms, staging, the end of the chunk - is executed once for that many tiles.  -1: the library's choice per row
+ *     width - 2 at 641..768 dimensions, 1 elsewhere; an explicit value holds wherever the kernel exists and means 1 elsewhere (filtered
+ *     searches, other widths and query widths, resident_mb 0 with an automatic row_sums).  Never a different answer
  *   group_scratch_mb 1..8192 (256): MiB of device scratch a sub-batch of bbq_search_grouped_batch may take for its representatives, 16
  *     bytes per live group and query: a score launch takes as many queries as fit (at most 1024, at least one).  Never a different answer
  *   fast_bound 0|1 (1): compact corrections: 1 tests the score bound of a row in f32 against the threshold's image in the linear space of

@@ -47,6 +47,10 @@ def table(csrc):
             continue
         v = out[n]
         key = m.group(1).replace("(bool)", "").replace("unsigned long const*", "accept")
+        parts = key.split(", ")
+        if len(parts) > 6 and parts[6] == "1":  # TPW = 1 is the kernel a tree without the parameter has: the same key for both
+            del parts[6]
+            key = ", ".join(parts)
         res[key] = (v["VGPRs"], v["Occupancy"], v["ScratchSize"])
     return res
 
@@ -62,7 +66,7 @@ def main():
         return
     before, after = table(sys.argv[1]), table(sys.argv[2])
     lost = scratch = changed = 0
-    print("%-44s %-16s %-16s" % ("bbq_scan_kernel<QB, W, MODE, SB, RS, DG[, accept]>", "before", "after"))
+    print("%-44s %-16s %-16s" % ("bbq_scan_kernel<QB, W, MODE, SB, RS, DG[, TPW > 1][, accept]>", "before", "after"))
     for k in sorted(set(before) | set(after)):
         b, a = before.get(k), after.get(k)
         mark = ""
