@@ -554,6 +554,36 @@ constexpr uint32_t kGroupNaNBits = 0x7fc00000u;  // the score a representative w
 __host__ __device__ inline uint32_t group_key_score_bits(unsigned long long k) { return (uint32_t)(k >> 32) ? bits_of_key((uint32_t)(k >> 32)) : kGroupNaNBits; }
 __host__ __device__ inline uint32_t group_key_ord(unsigned long long k) { return 0x7fffffffu - (uint32_t)k; }
 
+// MaxSim search (bbq_maxsim_kernels.hip): a query is a run of token vectors and a live group scores the sum, in ascending token, of its
+// representatives' f32 scores for them.  A query's tokens are worked through in blocks of at most kMaxSimTokenBlock: a block's score
+// pass leaves the packed key of every (token, live group) in rep[token of the block][slot] - the grouped search's pass with the block's
+// token vectors as its queries, or the fused pass that loads a tile once for all of a query's tokens of the block - and the accumulate
+// pass adds them into acc[query][slot], an f64 that lives across the blocks; behind a query's last block it leaves scores[query][slot]
+// and ords[query][slot] = the slot's group number, which the span search's select pass takes as they are.
+// kMaxSimTokenBlock: the fused pass keeps a block's planes (64 W bytes a token, W <= 12), uniforms (96) and edge slots (128) in LDS -
+// 31 KB at the widest row, under the 40 KB at which four workgroups of eight waves, all a CU holds, still fit its 160 KB.
+constexpr int kMaxSimTokenBlock = 32;
+constexpr int kMaxSimFirst = 1, kMaxSimLast = 2;  // MaxSimQuery::flags
+struct MaxSimQuery {
+  int32_t vec_first;  // its first token vector of this block among the block's staged vectors; the rest follow it
+  int32_t n_tok;      // 1 .. kMaxSimTokenBlock
+  int32_t query;      // of the sub-batch: its row of acc, scores and ords
+  int32_t flags;      // kMaxSimFirst: the block holds its token 0 - acc is initialised, not read; kMaxSimLast: its last token - scores and ords are written
+};
+struct MaxSimAccArgs {
+  const unsigned long long *rep;  // [the block's vectors][live]
+  const MaxSimQuery *queries;     // [grid.y]
+  double *acc;                    // [sub-batch's queries][live]
+  float *scores;                  // the same shape
+  uint32_t *ords;                 // the same shape
+  const int32_t *live_group;      // [live] the group number of every slot
+  int64_t live;
+};
+struct MaxSimScoreArgs {
+  GroupScoreArgs g;            // qplanes / qparams / rep: per staged VECTOR of the block; n_queries: the length of `queries`
+  const MaxSimQuery *queries;  // a workgroup is one chunk for one of them
+};
+
 constexpr int kFinalizeThreads = 1024;
 constexpr int kFinalizeJobs = 4096;     // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)
 constexpr int kFinalizeKeyCap = 12288;   // LDS key buffer of the finalize kernel (new keys + running top-k)

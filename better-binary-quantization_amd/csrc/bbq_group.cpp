@@ -14,21 +14,6 @@
 
 using namespace bbq;
 
-// A group set (include/bbq.h): read-only after creation, so any number of calls and threads may share it.  It keeps its own copy of
-// the filter's words, on both sides: the filter may go before it does.
-struct bbq_groups {
-  int device = 0;
-  DeviceCtx *ctx = nullptr;
-  int64_t n_rows = 0;    // rows of the index it was made for
-  int64_t n_groups = 0;
-  int64_t live = 0;      // L
-  bool filtered = false;
-  std::vector<int64_t> offsets;   // [n_groups + 1] the caller's
-  DevBuf<uint64_t> d_words;       // [tiles + 1] starts, then - filtered - [tiles] accept
-  DevBuf<uint32_t> d_index;       // [tiles + 1] first_group, then [non-empty groups + 1] slot
-  int64_t n_nonempty = 0;
-};
-
 namespace {
 
 // A sub-batch takes at most this many queries and - by default - this many bytes of scratch for the representatives (16 B per live
@@ -73,12 +58,16 @@ void plan_groups(const int64_t *off, int64_t n_groups, const uint64_t *bits, int
   if (nonempty) *nonempty = ne;
 }
 
+}  // namespace
+
 // what a group set can be made for, and searched on: a single-device root index (DESIGN.md "Grouped search", out of scope)
-int check_group_index(const bbq_index *ix) {
+int bbq::check_group_index(const bbq_index *ix) {
   if (ix->multi) return fail(BBQ_ERR_UNSUPPORTED, "grouped search is not supported on a multi-device index");
   if (ix->has_pilot || ix->row_base != 0) return fail(BBQ_ERR_UNSUPPORTED, "grouped search is not supported on a row shard or an index with a pilot replica");
   return BBQ_OK;
 }
+
+namespace {
 
 // where a sub-batch of nq queries keeps what in the scratch: [query data | query uniforms | selected queries] come from the host in
 // one copy, the answer blocks go back in one, the packed keys, the scores and the ords stay unless a query's heap is replayed
@@ -319,15 +308,19 @@ int bbq_groups_create(bbq_index *ix, const int64_t *group_offsets, int64_t n_gro
     ne_slot[o++] = slot[(size_t)i];
   }
   ne_slot[ne] = -1;  // the rows behind the last one: no group
+  std::vector<int32_t> live_group((size_t)std::max<int64_t>(g->live, 1));  // the MaxSim search's table: slot -> group number
+  for (int64_t i = 0; i < n_groups; ++i)
+    if (slot[(size_t)i] >= 0) live_group[(size_t)slot[(size_t)i]] = (int32_t)i;
   if (n_rows & 63) words[(size_t)(n_rows >> 6)] |= 1ull << (n_rows & 63);
   words[(size_t)n_tiles] = 1ull;
   index[(size_t)n_tiles] = (uint32_t)ne;
   if (f) std::copy(f->h_bits.begin(), f->h_bits.begin() + n_tiles, words.begin() + n_tiles + 1);
   HIPCHK(hipSetDevice(ix->device));
-  if (g->d_words.alloc(words.size()) != hipSuccess || g->d_index.alloc(index.size()) != hipSuccess) {
+  if (g->d_words.alloc(words.size()) != hipSuccess || g->d_index.alloc(index.size()) != hipSuccess || g->d_live_group.alloc(live_group.size()) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(BBQ_ERR_OOM, "bbq_groups_create: %zu bytes of device tables", words.size() * 8 + index.size() * 4);
+    return fail(BBQ_ERR_OOM, "bbq_groups_create: %zu bytes of device tables", words.size() * 8 + index.size() * 4 + live_group.size() * 4);
   }
+  HIPCHK(hipMemcpy(g->d_live_group, live_group.data(), live_group.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(g->d_words, words.data(), words.size() * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(g->d_index, index.data(), index.size() * 4, hipMemcpyHostToDevice));
   *out = g.release();

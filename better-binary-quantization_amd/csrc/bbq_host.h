@@ -227,6 +227,8 @@ struct bbq_index {
                               // and has a digit twin: 0 never, 1 and -1 wherever it can (digit_planes_for_call, bbq_core.cpp)
   int opt_group_scratch_mb = 256;  // MiB of scratch a grouped search's sub-batch may take for its representatives, 16 B per live group and
                                    // query (bbq_group.cpp): as many queries per score launch as fit, at least one
+  int opt_maxsim_fused = -1;  // the MaxSim search's score pass: 1 the fused kernel wherever it exists, 0 the grouped search's kernel per token
+                              // vector, -1 what was measured faster (bbq_maxsim.cpp).  The answers are the same either way
   int opt_fast_bound = 1;  // 1: the compact layout's score bound in f32 against the threshold's z image wherever the query's f32 images allow it
                            // (fast_bound_images, bbq_query.cpp); 0: always the f64 bound.  The answers are the same either way
   int opt_latency_presample = 1;  // ... and on large indexes get their threshold from per-wave top keys of a prefix (two small launches) instead of two scan / finalize pairs

@@ -271,6 +271,7 @@ int bbq_set_option(bbq_index *ix, const char *name, int64_t v) {
   else if (n == "fast_bound" && (v == 0 || v == 1)) ix->opt_fast_bound = (int)v;
   else if (n == "row_sums" && v >= -1 && v <= 1) ix->opt_row_sums = (int)v;
   else if (n == "group_scratch_mb" && v >= 1 && v <= 8192) ix->opt_group_scratch_mb = (int)v;
+  else if (n == "maxsim_fused" && v >= -1 && v <= 1) ix->opt_maxsim_fused = (int)v;
   else if (n == "digit_planes" && v >= -1 && v <= 1) ix->opt_digit_planes = (int)v;
   else if (n == "tiles_per_wave" && (v == -1 || v == 1 || v == 2 || v == 4 || v == 8)) ix->opt_tiles_per_wave = (int)v;
   else if (n == "replay_threads" && v >= 1 && v <= 256) ix->opt_replay_threads = (int)v;

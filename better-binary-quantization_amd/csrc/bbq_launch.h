@@ -111,6 +111,13 @@ hipError_t launch_span_select(const SpanSelectArgs &a, int n_selected, hipStream
 hipError_t launch_group_score(const GroupScoreArgs &a, int planes, hipStream_t s);
 // rep[i] -> scores[i] (key 0: a quiet NaN), ords[i] for the n packed keys of a sub-batch
 hipError_t launch_group_unpack(const unsigned long long *rep, float *scores, uint32_t *ords, int64_t n, hipStream_t s);
+// MaxSim search (bbq_maxsim_kernels.hip).  The accumulate pass of one token block for the n_queries (<= 65535) entries of a.queries
+hipError_t launch_maxsim_accumulate(const MaxSimAccArgs &a, int n_queries, hipStream_t s);
+// is there a fused score kernel for this index and plane count?  (4 planes against 1-bit rows of 6, 8 or 12 chunks)
+bool maxsim_fused_exists(const TileGeom &geom, int planes);
+// the fused score pass of one token block: every chunk of a.g.idx for each of a.g.n_queries entries of a.queries -> a.g.rep, which the
+// caller has cleared.  hipErrorInvalidValue where maxsim_fused_exists says no: the caller asks first
+hipError_t launch_maxsim_score(const MaxSimScoreArgs &a, int planes, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 // staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place

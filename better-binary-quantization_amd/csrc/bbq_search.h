@@ -15,6 +15,22 @@ struct bbq_filter {
   int64_t first_chunk = -1, last_chunk = -1;  // the first and the last chunk that holds an accepted row (-1: none)
 };
 
+// A group set (include/bbq.h, bbq_group.cpp): read-only after creation, so any number of calls and threads may share it.  It keeps its
+// own copy of the filter's words: the filter may go before it does.
+struct bbq_groups {
+  int device = 0;
+  bbq::DeviceCtx *ctx = nullptr;
+  int64_t n_rows = 0;    // rows of the index it was made for
+  int64_t n_groups = 0;
+  int64_t live = 0;      // L
+  bool filtered = false;
+  std::vector<int64_t> offsets;        // [n_groups + 1] the caller's
+  bbq::DevBuf<uint64_t> d_words;       // [tiles + 1] starts, then - filtered - [tiles] accept
+  bbq::DevBuf<uint32_t> d_index;       // [tiles + 1] first_group, then [non-empty groups + 1] slot
+  bbq::DevBuf<int32_t> d_live_group;   // [max(L, 1)] the group number of every slot: what the MaxSim search answers with (bbq_maxsim.cpp)
+  int64_t n_nonempty = 0;
+};
+
 #pragma GCC visibility push(hidden)  // internal: none of this joins the library's dynamic symbols
 namespace bbq {
 
@@ -97,6 +113,8 @@ int stage_compact_map(const bbq_filter *f, DevBuf<uint32_t> &d_rank, CompactMap 
 // and the winner list (BBQ_ERR_OOM), enqueued on `s`.
 int update_winners(const int32_t *ords, int64_t n, int64_t n_rows, std::vector<int64_t> &pos);
 int stage_winners(hipStream_t s, const int32_t *ords, int64_t n, const std::vector<int64_t> &pos, DevBuf<int32_t> &d_ords, DevBuf<int64_t> &d_pos);
+// ---- bbq_group.cpp: what a group set can be made for, and searched on - a single-device root index
+int check_group_index(const bbq_index *ix);
 // ---- bbq_dense.cpp
 int dense_search_one(const SearchCall &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n);
 

@@ -80,6 +80,8 @@ export declare class BinaryQuantizationFormat {
   searchNearestNeighborsInSpansFiltered(query: Float32Array, targetVectors: BinarizedByteVectorValues, spans: Array<[number, number]> | Float64Array, filter: RowFilter, k: number): Array<{ index: number; score: number }>;
   /** extension: the k best groups of `groups` (createRowGroups), each through its best accepted row - the reference's loop over each live group's best row, ascending, with a heap of min(k, live groups) */
   searchNearestNeighborsGrouped(query: Float32Array, targetVectors: BinarizedByteVectorValues, groups: RowGroups, k: number): Array<{ index: number; score: number; group: number }>;
+  /** extension: the k best groups for a query of several token vectors (MaxSim, late interaction): a group scores the ordered sum of its best accepted row's score for every vector */
+  searchNearestNeighborsMaxSim(queryVectors: Float32Array[], targetVectors: BinarizedByteVectorValues, groups: RowGroups, k: number): Array<{ group: number; score: number }>;
   /** extension: every row (of options.rowFilter, if given) whose stored f32 score is >= threshold, in ascending ord or, with order 'score', by descending score (ties in ascending ord); a NaN score is in no answer, a NaN threshold throws */
   searchRange(query: Float32Array, targetVectors: BinarizedByteVectorValues, threshold: number, options?: { rowFilter?: RowFilter | null; order?: 'ord' | 'score' }): Array<{ index: number; score: number }>;
   /** extension: the same for many queries per call; one filter serves all of them */

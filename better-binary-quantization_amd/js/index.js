@@ -779,6 +779,29 @@ class BinaryQuantizationFormat {
   }
 
   /**
+   * extension (not in the reference): the k best GROUPS of `groups` (createRowGroups) for a query that is a bag of token vectors - late
+   * interaction, MaxSim: a group scores the sum over queryVectors, in their order, of its best accepted row's score for each, added in
+   * f64 and rounded once.  What the reference's loop (:349-411) returns when it visits the live groups, ascending, with a heap of
+   * min(k, live groups) (libbbq bbq_search_maxsim_batch).  Every vector is quantized the way searchNearestNeighborsGrouped quantizes its
+   * one.  Returns [{group, score}].
+   */
+  searchNearestNeighborsMaxSim(queryVectors, targetVectors, groups, k) {
+    if (!queryVectors || queryVectors.length === 0) throw new Error('查询向量不能为空');
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (!(groups instanceof RowGroups)) throw new Error('searchNearestNeighborsMaxSim needs createRowGroups(targetVectors, offsets)');
+    const flat = this._flatQueries(queryVectors, targetVectors, k);
+    if (flat === null) return [];
+    const q = this.quantizer, sim = simOrdinal(q.similarityFunction), qb = this.config.queryBits;
+    const tNative = process.hrtime.bigint();
+    const qz = native.quantizeQueries(flat, queryVectors.length, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, 1);
+    const r = native.searchMaxSim(targetVectors._deviceIndex(), groups._handle(), qz.quantized, qz.corrections, qb, sim, k);
+    hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
+    const n = r.groups.length, res = new Array(n);
+    for (let j = 0; j < n; j++) res[j] = { group: r.groups[j], score: r.scores[j] };
+    return res;
+  }
+
+  /**
    * extension (not in the reference): every row whose stored f32 score is >= threshold - what the reference's loop (:349-411) would collect
    * if it kept every visited ord at or above the threshold and skipped the heap.  options.rowFilter: a RowFilter (createRowFilter) - only the
    * rows it accepts; options.order: 'ord' (default, ascending ord) or 'score' (descending score, ties in ascending ord).  A row whose

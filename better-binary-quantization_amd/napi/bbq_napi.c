@@ -870,6 +870,50 @@ static napi_value SearchGrouped(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* searchMaxSim(handle, groups handle, qquant [T * dim], qcorr [T * 4], queryBits, sim, k) -> {groups Int32Array, scores Float32Array,
+ * status}: the k best groups for ONE query of T >= 1 token vectors, each group scoring the ordered sum of its best accepted rows' scores
+ * (bbq_search_maxsim_batch with one query); status 0: the device selected the answer, 1: the host replayed the heap */
+static napi_value SearchMaxSim(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (!get_args(env, info, 7, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  void *gp = NULL;
+  if (napi_get_value_external(env, a[1], &gp) != napi_ok || !gp || !*(bbq_groups **)gp) {
+    napi_throw_error(env, "BBQ1", "bbq_search_maxsim_batch: the group set is null");
+    return NULL;
+  }
+  const bbq_groups *grp = *(bbq_groups **)gp;
+  void *qq, *qc; size_t ql, cl;
+  int64_t qb, sim, k;
+  if (!get_typed(env, a[2], napi_uint8_array, &qq, &ql) || !get_typed(env, a[3], napi_float64_array, &qc, &cl) ||
+      !get_i64(env, a[4], &qb) || !get_i64(env, a[5], &sim) || !get_i64(env, a[6], &k)) return NULL;
+  const size_t dim = (size_t)bbq_index_dimension(ix);
+  if (dim == 0 || ql == 0 || ql % dim != 0 || cl != ql / dim * 4) { napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return NULL; }
+  if (k < 0) { napi_throw_error(env, "BBQ7", "k值不能为负数"); return NULL; }
+  const int64_t live = bbq_groups_live(grp);
+  const int64_t keff = k < live ? k : live;   /* no answer is longer than the live groups */
+  const int64_t voff[2] = {0, (int64_t)(ql / dim)};
+  int32_t *og = (int32_t *)malloc(((size_t)keff + 1) * sizeof(int32_t));
+  float *sc = (float *)malloc(((size_t)keff + 1) * sizeof(float));
+  if (!og || !sc) { free(og); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int64_t cnt = 0;
+  uint8_t status = 0;
+  int rc = bbq_search_maxsim_batch(ix, grp, 1, voff, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff, og, sc, &cnt, &status);
+  if (rc != BBQ_OK) { free(og); free(sc); return throw_bbq(env, rc); }
+  void *os, *ogp;
+  napi_value ts = new_typed(env, napi_float32_array, (size_t)cnt, 4, &os);
+  napi_value tg = new_typed(env, napi_int32_array, (size_t)cnt, 4, &ogp);
+  if (!ts || !tg) { free(og); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  if (cnt > 0) { memcpy(os, sc, (size_t)cnt * 4); memcpy(ogp, og, (size_t)cnt * 4); }
+  free(og); free(sc);
+  napi_value o, st;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  NAPI_CALL(env, napi_create_int32(env, (int32_t)status, &st));
+  set_prop(env, o, "groups", tg); set_prop(env, o, "scores", ts); set_prop(env, o, "status", st);
+  return o;
+}
+
 /* searchRange(handle, filter handle | null, qquant, qcorr, queryBits, sim, threshold) -> {indices Int32Array, scores Float32Array}: every row (of
  * the filter, if one is given) whose f32 score is >= threshold, ascending by ord (bbq_count_range_batch, then bbq_search_range_batch with
  * exactly that room).  A NaN threshold throws. */
@@ -1242,6 +1286,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"groupsCreate", NULL, GroupsCreate, NULL, NULL, NULL, napi_default, NULL},
       {"groupsDestroy", NULL, GroupsDestroy, NULL, NULL, NULL, napi_default, NULL},
       {"searchGrouped", NULL, SearchGrouped, NULL, NULL, NULL, napi_default, NULL},
+      {"searchMaxSim", NULL, SearchMaxSim, NULL, NULL, NULL, napi_default, NULL},
       {"setOption", NULL, SetOption, NULL, NULL, NULL, napi_default, NULL},
       {"stats", NULL, Stats, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsCreate", NULL, VectorsCreate, NULL, NULL, NULL, napi_default, NULL},

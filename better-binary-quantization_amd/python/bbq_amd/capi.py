@@ -34,6 +34,7 @@ SYMBOLS = [
     "bbq_range_key", "bbq_count_range_batch", "bbq_search_range_batch",
     "bbq_search_spans_batch", "bbq_search_spans_filtered_batch",
     "bbq_groups_create", "bbq_groups_destroy", "bbq_groups_count", "bbq_groups_live", "bbq_groups_plan", "bbq_search_grouped_batch",
+    "bbq_search_maxsim_batch", "bbq_maxsim_reduce", "bbq_maxsim_token_block",
 ]
 
 
@@ -123,6 +124,10 @@ def lib():
     L.bbq_groups_live.restype = i64
     L.bbq_groups_plan.argtypes = [vp, i64, i64, vp, vp, C.POINTER(i64)]
     L.bbq_search_grouped_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
+    L.bbq_search_maxsim_batch.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp]
+    L.bbq_maxsim_reduce.argtypes = [vp, i64, i64, vp]
+    L.bbq_maxsim_token_block.argtypes = []
+    L.bbq_maxsim_token_block.restype = i32
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_create_rows.argtypes = [vp, vp, i64, C.POINTER(vp)]
     L.bbq_filter_destroy.argtypes = [vp]
@@ -621,6 +626,28 @@ class Index:
                                            _ptr(idx), _ptr(grp), _ptr(sc), _ptr(cnt), _ptr(status)))
         return [(idx[q, :cnt[q]], sc[q, :cnt[q]], grp[q, :cnt[q]]) for q in range(nq)], status
 
+    def search_maxsim_batch(self, token_lists, query_bits, sim, k, groups):
+        """bbq_search_maxsim_batch: the k best groups of `groups` (a Groups of this index) for every query, a query being a bag of token
+        vectors and a group scoring the ordered f64 sum of its representatives' scores.  token_lists: per query a pair (qquant uint8
+        [T, dim], qcorr float64 [T, 4]), T >= 1.  Returns a list of (group, score) per query and the status array (0: the device selected
+        the answer, 1: the host replayed the heap over the device's sums)."""
+        nq = len(token_lists)
+        off = np.zeros(nq + 1, np.int64)
+        for q, (tq, _) in enumerate(token_lists):
+            off[q + 1] = off[q] + np.asarray(tq).reshape(-1, self.dim).shape[0]
+        qq = np.ascontiguousarray(np.concatenate([np.asarray(t[0], np.uint8).reshape(-1, self.dim) for t in token_lists]) if nq else np.zeros((0, self.dim), np.uint8))
+        qc = np.ascontiguousarray(np.concatenate([np.asarray(t[1], np.float64).reshape(-1, 4) for t in token_lists]) if nq else np.zeros((0, 4), np.float64))
+        if qc.shape[0] != qq.shape[0]:
+            raise BBQError(ERR_INVALID_ARG, "one correction row per token vector")
+        kk = max(int(k), 0)
+        grp = np.zeros((nq, kk), np.int32)
+        sc = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.int64)
+        status = np.zeros(nq, np.uint8)
+        _chk(lib().bbq_search_maxsim_batch(self._h, groups._h if groups is not None else None, nq, _ptr(off), _ptr(qq), _ptr(qc), query_bits, sim, k,
+                                          _ptr(grp), _ptr(sc), _ptr(cnt), _ptr(status)))
+        return [(grp[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)], status
+
     def _range_args(self, qquant, qcorr, thresholds):
         qq = np.ascontiguousarray(qquant, np.uint8)
         qc = np.ascontiguousarray(qcorr, np.float64)
@@ -844,6 +871,22 @@ def groups_plan(offsets, n_rows, mask=None):
     live = C.c_int64(0)
     _chk(lib().bbq_groups_plan(_ptr(off) if off.shape[0] else None, n_groups, int(n_rows), _ptr(words), _ptr(slot), C.byref(live)))
     return slot, int(live.value)
+
+
+def maxsim_reduce(rep_scores):
+    """bbq_maxsim_reduce (host only): rep_scores float32 [n_vectors, n_groups], the representatives' scores of every token vector ->
+    float32 [n_groups], each group's ordered f64 sum rounded once"""
+    r = np.ascontiguousarray(rep_scores, np.float32)
+    if r.ndim != 2:
+        raise BBQError(ERR_INVALID_ARG, "rep_scores is [n_vectors, n_groups]")
+    out = np.zeros(r.shape[1], np.float32)
+    _chk(lib().bbq_maxsim_reduce(_ptr(r), r.shape[0], r.shape[1], _ptr(out)))
+    return out
+
+
+def maxsim_token_block():
+    """bbq_maxsim_token_block: the tokens of a query a MaxSim search works through at a time"""
+    return int(lib().bbq_maxsim_token_block())
 
 
 class Groups:

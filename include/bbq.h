@@ -39,7 +39,8 @@ extern "C" {
                               bbq_score_ords, bbq_score_ords_batch, bbq_search_ords_batch - and the range search - bbq_range_key,
                               bbq_count_range_batch, bbq_search_range_batch - and the span search - bbq_search_spans_batch,
                               bbq_search_spans_filtered_batch - and the grouped search - bbq_groups_create, bbq_groups_destroy,
-                              bbq_groups_count, bbq_groups_live, bbq_groups_plan, bbq_search_grouped_batch) */
+                              bbq_groups_count, bbq_groups_live, bbq_groups_plan, bbq_search_grouped_batch - and the MaxSim search -
+                              bbq_search_maxsim_batch, bbq_maxsim_reduce, bbq_maxsim_token_block) */
 
 /* status codes */
 enum {
@@ -508,6 +509,41 @@ int bbq_search_grouped_batch(bbq_index *idx, const bbq_groups *g, int32_t n_quer
                              int32_t *out_idx, int32_t *out_group, float *out_score, int64_t *out_n, uint8_t *out_status);
 
 /* ------------------------------------------------------------------------------------------
+ * MaxSim search (DESIGN.md "MaxSim search"): the k best GROUPS of a group set for queries that are bags of token vectors - the
+ * late-interaction score of ColBERT / ColPali, Lucene's late-interaction field, Elasticsearch's rank_vectors over bit-quantized
+ * vectors - exact, in one call, summed on the device.  Query q owns the token vectors [vec_offsets[q], vec_offsets[q + 1]) of the
+ * n_vectors = vec_offsets[n_queries] vectors in qquant / qcorr, which are laid out as bbq_search_batch lays out n_vectors queries.
+ * vec_offsets [n_queries + 1]: vec_offsets[0] == 0, ascending, and every query has at least one vector; anything else is
+ * BBQ_ERR_INVALID_ARG naming the first offending query, with nothing launched and nothing written.
+ * For a live group and token t, m_t is the f32 score of that token vector's REPRESENTATIVE of the group, exactly as the grouped
+ * search defines it (a NaN score if all accepted rows of the group score NaN).  The group's score is
+ *   S = (float)((double)m_0 + (double)m_1 + ...)
+ * - the f64 adds strictly in ascending t, starting from m_0 and not from 0.0 (a single -0.0 stays -0.0), one rounding to f32 at the
+ * end, no contraction, no reassociation; a NaN m_t makes S NaN.  bbq_maxsim_reduce (host only, no device) is this sum in plain C over
+ * rep_scores[t * n_groups + slot] -> out [n_groups], n_vectors >= 1: the normative statement.
+ * bbq_search_maxsim_batch: query q's answer is what the reference loop (src/binaryQuantizationFormat.ts:349-411) returns when it visits
+ * exactly the L live groups in ascending group number, pushing (group number, S) into a heap of min(k, L): group numbers, score bits
+ * and order, ties and NaN included.  out_group / out_score [n_queries*k] (query q at offset q*k), out_n [n_queries].  k < 0:
+ * BBQ_ERR_NEGATIVE_K; k == 0 or L == 0: out_n[q] = 0; k > L: L results; n_queries == 0: BBQ_OK, nothing launched.
+ * out_status [n_queries] (may be NULL) is the span search's rule over the S values: 0 - the device selected the answer - EXACTLY when
+ * L > k, 1 <= k <= 4096, no S is NaN and no two of the k + 1 largest compare equal as floats; otherwise 1 - the host ran the literal
+ * heap over the device's S in slot order.  0 as well for k == 0 or L == 0.
+ * With one vector per query the groups, score bits, order and statuses are those of bbq_search_grouped_batch.
+ * Handles, lock and stream as bbq_search_grouped_batch: a group set made for another size or device is BBQ_ERR_INVALID_ARG, nothing
+ * launched, nothing written; a multi-device handle, a non-root shard or an index with a pilot replica is BBQ_ERR_UNSUPPORTED; the call
+ * takes the device context's lock, runs on the auxiliary stream and writes no bbq_stats field.  Every token vector scores the whole
+ * index - nothing is pruned.  A query's tokens are worked through in blocks of at most bbq_maxsim_token_block() tokens, whose keys cost
+ * 8 bytes per token of the block and live group - not per token of the query; a long call in sub-batches of at most 1024 queries and
+ * group_scratch_mb (bbq_set_option) of scratch, always at least one query and one token block.  A failed allocation: BBQ_ERR_OOM,
+ * nothing written.  Results are byte-identical from run to run and under either value of maxsim_fused (bbq_set_option).
+ * Out of scope: returning each answer's per-token best rows, a group set per query, per-token weights, any pruning. */
+int bbq_search_maxsim_batch(bbq_index *idx, const bbq_groups *g, int32_t n_queries, const int64_t *vec_offsets,
+                            const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim, int64_t k,
+                            int32_t *out_group, float *out_score, int64_t *out_n, uint8_t *out_status);
+int bbq_maxsim_reduce(const float *rep_scores, int64_t n_vectors, int64_t n_groups, float *out);   /* host only */
+int32_t bbq_maxsim_token_block(void);   /* tokens of a block, the same for every index */
+
+/* ------------------------------------------------------------------------------------------
  * Sharded search (one process per GPU).  bbq_shard_scan sweeps THIS shard for n_queries queries and
  * leaves the shard's candidates - per query a superset of the rows that ever enter the reference's heap,
  * ascending by global row - PACKED in caller-provided DEVICE memory, so the host framework can move them
@@ -734,6 +770,11 @@ int bbq_reset_stats(bbq_index *idx);
  *     searches, other widths and query widths, resident_mb 0 with an automatic row_sums).  Never a different answer
  *   group_scratch_mb 1..8192 (256): MiB of device scratch a sub-batch of bbq_search_grouped_batch may take for its representatives, 16
  *     bytes per live group and query: a score launch takes as many queries as fit (at most 1024, at least one).  Never a different answer
+ *     The same budget bounds a sub-batch of bbq_search_maxsim_batch: 8 bytes per token of a block and 16 per query, per live group
+ *   maxsim_fused -1|0|1 (-1): the score pass of bbq_search_maxsim_batch.  0: the grouped search's score kernel, every token vector of a
+ *     block as one of its queries; 1: wherever it exists - 4 query bit-planes against 1-bit rows of 6, 8 or 12 16-byte chunks - the fused
+ *     kernel, which loads a tile once for all tokens of a query's block; -1: the fused kernel, which was measured faster at 1 M rows of each
+ *     of its three widths (profiles/maxsim_search*.json).  Never a different answer
  *   fast_bound 0|1 (1): compact corrections: 1 tests the score bound of a row in f32 against the threshold's image in the linear space of
  *     the score formula, for every query whose corrections have f32 images (others keep the f64 bound); 0: always the f64 bound through
  *     the similarity transform.  A pre-filter in front of the exact score either way: never a different answer
