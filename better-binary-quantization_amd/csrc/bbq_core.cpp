@@ -132,11 +132,18 @@ bool digit_planes_for_call(const bbq_index *ix, int planes) {
 // twin, launch_scan_t).  An explicit 1, 2, 4 or 8 is taken as it is.  Automatic: per row width, the fastest value that passed BOTH tests -
 // its twin comes out of the compiler without scratch and with no fewer waves per SIMD than the one-tile kernel (scripts/scan_resources.py),
 // and its slowest run was faster than the parent's fastest by more than the parent's own spread (Measurement) - and 1 where
-// none did.  768-d: 2 (58 registers, 8 waves like the one-tile kernel; +23 %).  4 and 8 tiles were faster still at every width, and 2 at
-// 1024-d and 1536-d was faster than 1, but each of those twins reports a wave or two fewer: docs/dropped.md, "tiles per wave".
+// none did.  With the exact path behind the tile loop (sweep_deferred_exact, bbq_scan_body.h) every twin holds 90-91 scalar registers and:
+// 768-d: 8 (58 vector registers, 8 waves like the one-tile kernel; 2 and 4 tiles: 54 and 60, 8 waves, measured slower).  1024-d: 4 (64
+// registers, 8 waves like the one-tile kernel; 2 tiles, 62 / 8, was slower, 8 tiles faster still but reports 7 waves at 66 registers).
+// 1536-d: 1 - every twin reports fewer waves than the one-tile kernel's 7 (78 / 80 / 82 registers, 6 / 6 / 5 waves) although each was
+// measured faster: docs/dropped.md, "tiles per wave".
 int tiles_per_wave_for(const bbq_index *ix) {
   if (ix->opt_tiles_per_wave > 0) return ix->opt_tiles_per_wave;
-  return ix->geom.w16 == 6 ? 2 : 1;
+  switch (ix->geom.w16) {
+    case 6: return 8;
+    case 8: return 4;
+    default: return 1;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ plan

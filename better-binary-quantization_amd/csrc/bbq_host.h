@@ -222,7 +222,7 @@ struct bbq_index {
   int opt_row_sums = -1;  // the per-query sparse sweep reads a row's component sum from the row_sums side array instead of counting it:
                           // 0 never, 1 wherever the array exists, -1: row_sums_for_launch()'s choice (bbq_core.cpp)
   int opt_tiles_per_wave = -1;  // tiles a wave of the per-query sparse sweep takes one after the other where the launch has such a twin: 1, 2, 4, 8;
-                                // -1: the value measured fastest for the index's row width (tiles_per_wave_for, bbq_core.cpp)
+                                // -1: per row width, the fastest value whose kernel keeps the one-tile kernel's waves - 8 at 6 chunks, 4 at 8 (tiles_per_wave_for, bbq_core.cpp)
   int opt_digit_planes = -1;  // a 4-plane query against 1-bit rows is swept in three ternary digit planes wherever the sweep reads the row sums
                               // and has a digit twin: 0 never, 1 and -1 wherever it can (digit_planes_for_call, bbq_core.cpp)
   int opt_group_scratch_mb = 256;  // MiB of scratch a grouped search's sub-batch may take for its representatives, 16 B per live group and

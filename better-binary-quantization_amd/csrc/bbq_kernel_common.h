@@ -309,7 +309,9 @@ __device__ __forceinline__ void store_threshold(Threshold *dst, uint32_t key, co
 //  tests/test_bound_f32_cpu.py restates this in numpy f32 and checks dominance over the exact score, fused and unfused.
 constexpr float kFastK1 = (float)(kBf16Rel * (1.0 + 1.0 / 262144.0));
 constexpr float kFastAddRel = 4.76837158203125e-07f;  // 2^-21
-__device__ __forceinline__ bool fast_bound_passes(bool valid, uint32_t qc, uint32_t cw, float aadd, uint32_t ones, const QueryParams &p, const Threshold &th) {
+// (P: QueryParams, or the f32 images alone - the sweep of several tiles per wave keeps nothing else of the query in its tile loop)
+template <class P>
+__device__ __forceinline__ bool fast_bound_passes(bool valid, uint32_t qc, uint32_t cw, float aadd, uint32_t ones, const P &p, const Threshold &th) {
   const float al = compact_lower(cw), au = compact_upper(cw);  // bf16 -> f32 is exact
   const float g = fmaf(p.lyf, (float)qc, p.ayf * (float)ones);
   const float A = p.c1f - g;

@@ -161,23 +161,58 @@ __device__ __forceinline__ void sweep_chunk_end(const ScanArgs &a, const SweepCo
 // The sweep of a wave's TPW > 1 tiles: the digit form of the unfiltered compact sweep (MODE 2, RS, DG) in the early order, nothing else.
 // Tile 0 is loaded in front of the staging and the barrier exactly as the TPW = 1 kernel loads its one tile (the same two arms of the scalar
 // branch, the masks the oldest load in flight); tile t + 1's loads are issued as soon as tile t's popcounts are done - its code registers are
-// dead there - so the bound and the exact path of tile t run with them in flight, and no two tiles' codes are held at once.  The loop over the
+// dead there - so the bound of tile t runs with them in flight, and no two tiles' codes are held at once.  The loop over the
 // wave's tiles is unrolled: as a loop, the next tile's correction word, row sum and additive bound came back in registers of their own and
 // the copies at the back edge waited for every load of the tile.  A tile's addresses are the first tile's plus constant strides (tile_stride,
 // the 128 bytes of a tile's row sums, the 8 of its add_range).  A wave whose next tile lies beyond the index leaves: the tiles are consecutive.
-// Per row it computes what the kernel computes: the same integer, the same bound, the same f64 score.  false: an idle workgroup, which leaves.
+// Per row it computes what the kernel computes: the same integer and the same f32 bound.  What only the rows that pass the bound need - the
+// f64 bound of a query without f32 images, the exact corrections, the f64 score, the key test, the candidate - is NOT in the tile loop
+// (99.9 % of the rows never get there, and unrolled TPW times it held the f64 half of the query, the side array's base and the f64 temporaries
+// live across every tile: 103 scalar registers and a wave less at 4 and 8 tiles): a passing row leaves one deferred entry in LDS
+// (deferred_entry) and sweep_deferred_exact, behind the loop, takes the entries one per lane.  The loop reads the f32 half of QueryParams alone.
+// n_def: the wave's deferred entries (wave-uniform).  false: an idle workgroup, which leaves.
+
+// A deferred entry: the row's place in its chunk and its qcDist, which is all the exact path needs - the sum, the correction word and the
+// tile's additive bound are read again there.
+constexpr int kDeferredRowShift = 16;
+template <int W> constexpr bool deferred_entry_fits() {
+  // qcDist of a 1-bit row against a 4-plane query is at most 15 per set bit, 128 bits per 16-byte chunk; a chunk has kChunkRows rows
+  return 15 * 128 * W < (1 << kDeferredRowShift) && kChunkRows <= (1 << (32 - kDeferredRowShift));
+}
+__device__ __forceinline__ uint32_t deferred_entry(uint32_t row_in_chunk, uint32_t qc) { return (row_in_chunk << kDeferredRowShift) | qc; }
+// Entry i of wave `wave` of NW: batch-major - the waves' i-th batches of 64 lie side by side - so that the entries of batch b of ALL waves lie
+// below those of batch b + 1 (the in-place layout of sweep_deferred_exact depends on it).  One wave: i.
+// Where the list lies (deferred_list_bytes is the launch's side of it): in the upper half of s_ent where s_ent holds a whole chunk's candidates -
+// the flood tier, the append mode - and behind the count words everywhere else.
+__host__ __device__ constexpr size_t deferred_list_bytes(bool stages_whole_chunk) { return stages_whole_chunk ? 0 : (size_t)kChunkRows * 4; }
+__device__ __forceinline__ uint32_t *deferred_list(uint64_t *s_ent, uint32_t *s_cnt, uint32_t stage_cap) {
+  return stage_cap == (uint32_t)kChunkRows ? reinterpret_cast<uint32_t *>(s_ent) + kChunkRows : s_cnt + 4;
+}
+template <int NW> __device__ __forceinline__ uint32_t deferred_pos(uint32_t i, int wave) {
+  return (i >> 6) * (uint32_t)(NW * 64) + (uint32_t)wave * 64u + (i & 63u);
+}
+// the f32 half of QueryParams: what the tile loop reads of the query
+struct FastBoundParams {
+  float ayf, lyf, c1f, k2mf, tinyf, csf, caf;
+};
+
 template <int W, int TPW, int NT>
-__device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepCoord wg, const bool idle, const int q, u32x4 *s_planes, uint64_t *s_ent,
-                                                 uint32_t *s_cnt, const uint32_t stage_cap, bool &nan_seen) {
+__device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepCoord wg, const bool idle, const int q, u32x4 *s_planes, uint32_t *s_def,
+                                                 uint32_t *s_cnt, uint32_t &n_def) {
   constexpr int QU = kDigitMasks;
+  constexpr int NW = NT / 64;
   static_assert(W * QU <= NT, "one staging pass: every unit of the query has a thread");
+  static_assert(deferred_entry_fits<W>(), "a deferred entry holds the row in its chunk and qcDist in 32 bits");
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)a.qdigits_at + (size_t)q * W * QU;
-  const QueryParams p = a.qparams[q];
+  const QueryParams *__restrict__ qp = a.qparams + q;
+  const FastBoundParams p = {qp->ayf, qp->lyf, qp->c1f, qp->k2mf, qp->tinyf, qp->csf, qp->caf};
+  const int32_t sim = qp->sim, fast_bound = qp->fast_bound;
+  const uint32_t digit_k = qp->digit_k;
   const Threshold th = a.theta[q];
-  const uint32_t theta = th.key;
+  n_def = 0;
   const int64_t chunk = a.chunk_begin + wg.chunk_local;
   const int64_t n_tiles = (a.idx.n_rows + kTileRows - 1) / kTileRows;
   const int64_t tile0 = chunk * kTilesPerChunk + wave_first_tile(TPW, wave);
@@ -187,11 +222,11 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
   // the addresses of the wave's first tile
   const uint8_t *__restrict__ tp = a.idx.tiles + tile0 * tile_stride;
   const uint32_t *__restrict__ rs = reinterpret_cast<const uint32_t *>(a.idx.row_sums + ((tile0 * kTileRows + lane) & ~(int64_t)1));
-  const float *__restrict__ ar = a.idx.add_range + tile0 * 2 + (p.sim == 0 ? 0 : 1);  // tile_add_bound's choice
+  const float *__restrict__ ar = a.idx.add_range + tile0 * 2 + (sim == 0 ? 0 : 1);  // tile_add_bound's choice
   u32x4 c[W];
   uint32_t cw, ones;
   float aadd;
-  f64x2 lu = {0.0, 0.0};
+  f64x2 lu = {0.0, 0.0};  // (load_tile's inline corrections: not loaded here)
   double xadd = 0.0, x1 = 0.0;
   if (has_tile) {
     u32x4 staged;
@@ -206,7 +241,10 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
     if (tid < W * QU) s_planes[tid] = staged;
     asm volatile("; staged without a tile" ::: "memory");
   }
-  if (tid == 0) *s_cnt = 0;
+  if (tid == 0) {
+    s_cnt[0] = 0;
+    if constexpr (NW > 1) s_cnt[1] = 0;  // the longest deferred list of the workgroup's waves (sweep_deferred_exact)
+  }
   if (idle) return false;
   __syncthreads();  // LDS only: a wave that staged nothing passes it with its tile's loads in flight
   if (!has_tile) return true;
@@ -215,9 +253,10 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
   const int my_tiles = tiles_left < TPW ? (int)tiles_left : TPW;  // >= 1, wave-uniform
   const int64_t row0 = tile0 * kTileRows;
   const uint32_t pick_at = (uint32_t)(lane & 1) << 4;  // the lane's half of its pair of row sums
+  const uint32_t row_in_chunk0 = (uint32_t)(wave_first_tile(TPW, wave) * kTileRows + lane);
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
-    uint32_t qc = tile_digit_dot<W>(c, s_planes, 0u, p.digit_k);
+    uint32_t qc = tile_digit_dot<W>(c, s_planes, 0u, digit_k);
     __builtin_amdgcn_sched_barrier(0);  // (the loads below and the pick of the sum stay behind the popcounts, as the pick does in the TPW = 1 kernel)
     const uint32_t sum = __builtin_amdgcn_ubfe(ones, pick_at, 16u);
     qc += sum << 2;  // digit_dot's 4 * ones: u32 arithmetic, the same integer in either order
@@ -230,21 +269,78 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
     }
     const int64_t rows_left = a.idx.n_rows - (row0 + t * kTileRows);  // > 0: the tile exists
     const bool valid = (uint32_t)lane < (uint32_t)(rows_left < kTileRows ? rows_left : kTileRows);
-    const bool need_exact = p.fast_bound ? fast_bound_passes(valid, qc, cw_t, aadd_t, sum, p, th) : f64_bound_passes(valid, qc, cw_t, aadd_t, (double)sum, p, theta);
-    if (need_exact) {
-      const int64_t row = row0 + t * kTileRows + lane;
-      exact_corrections(a.idx.exact, row, lu, xadd);
-      const double s64 = score_f64((double)qc, lu.x, lu.y, xadd, (double)sum, p);
-      const float s32 = (float)s64;
-      if (valid && (s32 != s32)) nan_seen = true;
-      if (valid && (s32 == s32) && key_of_bits(__float_as_uint(s32)) > theta) {
-        const uint32_t slot = atomicAdd(s_cnt, 1u);
-        if (slot < stage_cap) s_ent[slot] = candidate_entry(a.row_id_base + row, s32);
-      }
+    // a query without f32 images defers every valid row: its f64 bound stands in front of the exact path, behind the loop
+    const bool pass = fast_bound ? fast_bound_passes(valid, qc, cw_t, aadd_t, sum, p, th) : valid;
+    // The entry's place: the wave's running count plus the passing lanes below this one.  No atomic, and where nobody passes - nearly every
+    // tile - a scalar branch over all of it.
+    const unsigned long long passing = __ballot(pass);
+    if (passing) {
+      const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(passing >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)passing, 0u));
+      if (pass) s_def[deferred_pos<NW>(n_def + below, wave)] = deferred_entry(row_in_chunk0 + (uint32_t)(t * kTileRows), qc);
+      n_def += (uint32_t)__popcll(passing);
     }
     if (!more) break;
   }
   return true;
+}
+
+// The exact path of a chunk's deferred rows, once per chunk behind the tile loop: a rolled loop over batches of 64 entries, one entry per lane.
+// A row of a query without f32 images passes its f64 bound first (the row's correction word and its tile's additive bound are read again);
+// then the exact corrections, the f64 score, the NaN vote, the key test and the candidate, as the one-tile kernel has them.  The f64 half of
+// QueryParams is loaded HERE, behind the tile loop's last barrier-free stretch, so that it is live in no tile.
+// In place (the flood tier and the append mode, where s_ent holds kChunkRows candidates and LDS must not grow: 32 workgroups of one wave share
+// a CU's 160 KB): the deferred list is the upper half of s_ent, 4-byte entries, and the candidates grow from the bottom as entries are
+// consumed.  Every batch, ALL waves read their entries, THEN a barrier, then candidates are written: after the batches 0 .. b, m <= 64 NW (b + 1)
+// entries are consumed and at most m candidates lie in [0, 8 m) bytes, while the unread batches start at 4 kChunkRows + 4 * 64 NW (b + 1) -
+// never below 8 m for 64 NW (b + 1) <= kChunkRows - and a wave that is already writing batch b + 1 has passed that batch's barrier, so all of
+// batch b + 1 is read.  Elsewhere (s_ent holds `cap` candidates) the list has 4 kChunkRows bytes of its own behind the count words.
+template <int W, int TPW, int NT>
+__device__ __forceinline__ void sweep_deferred_exact(const ScanArgs &a, const SweepCoord wg, const int q, const uint32_t *s_def, uint64_t *s_ent,
+                                                     uint32_t *s_cnt, const uint32_t stage_cap, const uint32_t n_def, bool &nan_seen) {
+  constexpr int NW = NT / 64;
+  static_assert(NW * TPW * 64 == kChunkRows, "the workgroup's waves cover the chunk: at most kChunkRows deferred entries, batch b of all waves below batch b + 1");
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint32_t n_max = n_def;  // workgroup-uniform: the batches every wave takes part in
+  if constexpr (NW > 1) {
+    if (lane == 0 && n_def != 0) atomicMax(s_cnt + 1, n_def);
+    __syncthreads();
+    n_max = __builtin_amdgcn_readfirstlane(s_cnt[1]);
+  }
+  if (n_max == 0) return;
+  const QueryParams p = a.qparams[q];
+  const uint32_t theta = a.theta[q].key;
+  const int64_t chunk_row0 = (a.chunk_begin + wg.chunk_local) * (int64_t)kChunkRows;
+  for (uint32_t base = 0; base < n_max; base += 64) {
+    const uint32_t i = base + lane;
+    const bool have = i < n_def;
+    uint32_t e = 0;
+    if (have) e = s_def[deferred_pos<NW>(i, wave)];
+    __syncthreads();  // every lane of the workgroup has read its entry of this batch: candidates may take their place
+    if (have) {
+      const uint32_t qc = e & ((1u << kDeferredRowShift) - 1u);
+      const int64_t row = chunk_row0 + (e >> kDeferredRowShift);
+      const uint32_t sum = a.idx.row_sums[row];
+      bool need_exact = true;
+      if (!p.fast_bound) {
+        const int64_t tile = row / kTileRows;
+        const uint32_t cw = *(reinterpret_cast<const uint32_t *>(a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride + tile_corr_offset(W)) + (row & (kTileRows - 1)));
+        need_exact = f64_bound_passes(true, qc, cw, tile_add_bound(a.idx, tile, p.sim), (double)sum, p, theta);
+      }
+      if (need_exact) {
+        f64x2 lu;
+        double xadd;
+        exact_corrections(a.idx.exact, row, lu, xadd);
+        const double s64 = score_f64((double)qc, lu.x, lu.y, xadd, (double)sum, p);
+        const float s32 = (float)s64;
+        if (s32 != s32) nan_seen = true;
+        if ((s32 == s32) && key_of_bits(__float_as_uint(s32)) > theta) {
+          const uint32_t slot = atomicAdd(s_cnt, 1u);
+          if (slot < stage_cap) s_ent[slot] = candidate_entry(a.row_id_base + row, s32);
+        }
+      }
+    }
+  }
 }
 
 // MODE: 0 sparse / inline corrections, 1 dense / inline, 2 sparse / compact corrections + exact gather, 3 dense / compact
@@ -306,7 +402,10 @@ __global__ __launch_bounds__(kChunkRows / TPW) void bbq_scan_kernel(const ScanAr
   // twice, here through sweep_chunk_end: called from the body below, the unfiltered instantiations get other schedules.)
   if constexpr (TPW > 1) {
     bool nan_seen = false;
-    if (!sweep_wave_tiles<W, TPW, NT>(a, wg, idle, q, s_planes, s_ent, s_cnt, stage_cap, nan_seen)) return;
+    uint32_t n_def;
+    uint32_t *s_def = deferred_list(s_ent, s_cnt, stage_cap);
+    if (!sweep_wave_tiles<W, TPW, NT>(a, wg, idle, q, s_planes, s_def, s_cnt, n_def)) return;
+    sweep_deferred_exact<W, TPW, NT>(a, wg, q, s_def, s_ent, s_cnt, stage_cap, n_def, nan_seen);
     if (__any(nan_seen) && lane == 0) atomicOr(a.flags + q, kFlagNaN);
     sweep_chunk_end<NT>(a, wg, q, s_ent, s_cnt);
     return;
@@ -553,8 +652,9 @@ static void launch_tiles_twin(const ScanArgs &a, dim3 grid, size_t smem, hipStre
 }
 
 // tiles_per_wave: 1, 2, 4 or 8 - a host-side parameter of the launch, not a kernel argument (ScanArgs keeps its size): it selects the TPW twin
-// where the launch has one (tiles_twin, and the digit twin's own conditions) and is ignored everywhere else.  Same grid, same dynamic LDS;
-// the block is kChunkRows / TPW threads.
+// where the launch has one (tiles_twin, and the digit twin's own conditions) and is ignored everywhere else.  Same grid; the block is
+// kChunkRows / TPW threads; the same dynamic LDS with the flood tier or in the append mode, and 2 KB more - the twins' deferred list
+// (deferred_list_bytes) - without either.
 template <bool FILT, int QB, int W, int MODE, int SB = 1>
 static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s, int tiles_per_wave = 1) {
   ScanArgs a = args;  // the map's parameters: what the kernel decodes its block index with is what the grid below is built from
@@ -569,10 +669,12 @@ static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, in
     if (a.idx.row_sums && a.qdigits_at > 0) {  // ... and the caller staged the digit masks: three planes instead of four
       const size_t smem_dg = (size_t)w16 * kDigitMasks * 16 + smem_out;
       if constexpr (tiles_twin<FILT, QB, W, SB>()) {
+        // (a cap of kChunkRows without either is the whole chunk as well: deferred_list tests the staged entries, as here)
+        const size_t smem_tw = smem_dg + deferred_list_bytes(a.ovf || a.append_lists || a.cap == kChunkRows);
         switch (tiles_per_wave) {
-          case 2: launch_tiles_twin<QB, W, MODE, SB, 2>(a, grid, smem_dg, s); return hipGetLastError();
-          case 4: launch_tiles_twin<QB, W, MODE, SB, 4>(a, grid, smem_dg, s); return hipGetLastError();
-          case 8: launch_tiles_twin<QB, W, MODE, SB, 8>(a, grid, smem_dg, s); return hipGetLastError();
+          case 2: launch_tiles_twin<QB, W, MODE, SB, 2>(a, grid, smem_tw, s); return hipGetLastError();
+          case 4: launch_tiles_twin<QB, W, MODE, SB, 4>(a, grid, smem_tw, s); return hipGetLastError();
+          case 8: launch_tiles_twin<QB, W, MODE, SB, 8>(a, grid, smem_tw, s); return hipGetLastError();
           default: break;
         }
       }

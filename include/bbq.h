@@ -766,7 +766,7 @@ int bbq_reset_stats(bbq_index *idx);
  *   tiles_per_wave -1|1|2|4|8 (-1): tiles (64 rows) a wave of the per-query sweep takes one after the other where digit_planes applies to
  *     an unfiltered search (6, 8 or 12 chunks): the workgroup has 8 / tiles_per_wave waves, and what belongs to the workgroup or the wave -
  *     addresses, the query's uniforms, staging, the end of the chunk - is executed once for that many tiles.  -1: the library's choice per row
- *     width - 2 at 641..768 dimensions, 1 elsewhere; an explicit value holds wherever the kernel exists and means 1 elsewhere (filtered
+ *     width - 8 at 641..768 dimensions, 4 at 897..1024, 1 elsewhere; an explicit value holds wherever the kernel exists and means 1 elsewhere (filtered
  *     searches, other widths and query widths, resident_mb 0 with an automatic row_sums).  Never a different answer
  *   group_scratch_mb 1..8192 (256): MiB of device scratch a sub-batch of bbq_search_grouped_batch may take for its representatives, 16
  *     bytes per live group and query: a score launch takes as many queries as fit (at most 1024, at least one).  Never a different answer
