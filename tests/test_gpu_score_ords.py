@@ -14,8 +14,8 @@ pytestmark = pytest.mark.gpu
 
 FIXTURES = (["c1_1000x128_cos_qb4"]                                                            # w16 1, two chunks, a partial last tile
             + ["m_768d_%s_qb%d" % (s, q) for s in ("cos", "euc", "max") for q in (1, 4)]        # compiled width 6
-            + ["m_1024d_max_qb8"]                                                              # width 8
-            + ["m_%s_%s_qb%d" % (d, s, q) for d in ("100d", "72d") for s in ("cos", "euc", "max") for q in (1, 4)]  # run-time width
+            + ["m_1024d_max_qb8", "m_1024d_cos_qb4", "m_1024d_euc_qb1"]                        # width 8 at 8, 4 and 1 planes
+            + ["m_%s_%s_qb%d" % (d, s, q) for d in ("100d", "72d") for s in ("cos", "euc", "max") for q in (1, 4)]  # w16 1 with a ragged last chunk
             + ["qb2_128d_cos", "qb3_96d_mip",
                "ib2_1024d_cos_qb4",                                                            # multi-bit, width 16
                "ib4_96d_euc_qb4", "ib8_64d_cos_qb4", "ib3_72d_cos_qb4",
