@@ -132,16 +132,17 @@ bool digit_planes_for_call(const bbq_index *ix, int planes) {
 // twin, launch_scan_t).  An explicit 1, 2, 4 or 8 is taken as it is.  Automatic: per row width, the fastest value that passed BOTH tests -
 // its twin comes out of the compiler without scratch and with no fewer waves per SIMD than the one-tile kernel (scripts/scan_resources.py),
 // and its slowest run was faster than the parent's fastest by more than the parent's own spread (Measurement) - and 1 where
-// none did.  With the exact path behind the tile loop (sweep_deferred_exact, bbq_scan_body.h) every twin holds 90-91 scalar registers and:
-// 768-d: 8 (58 vector registers, 8 waves like the one-tile kernel; 2 and 4 tiles: 54 and 60, 8 waves, measured slower).  1024-d: 4 (64
-// registers, 8 waves like the one-tile kernel; 2 tiles, 62 / 8, was slower, 8 tiles faster still but reports 7 waves at 66 registers).
-// 1536-d: 1 - every twin reports fewer waves than the one-tile kernel's 7 (78 / 80 / 82 registers, 6 / 6 / 5 waves) although each was
+// none did.  With the exact path behind the tile loop (sweep_deferred_exact) and the tile loop's loads through buffer descriptors
+// (sweep_wave_tiles, bbq_scan_body.h) every twin holds 88-90 scalar registers and:
+// 768-d: 8 (50 vector registers, 8 waves like the one-tile kernel; 2 and 4 tiles: 51, 8 waves, measured slower).  1024-d: 8 (58
+// registers, 8 waves like the one-tile kernel, 1.6 % above 4 tiles' fastest run, 5 x their spread; 2 and 4 tiles: 59 / 8).
+// 1536-d: 1 - every twin reports 6 waves against the one-tile kernel's 7 (75 / 75 / 74 registers against 68) although each was
 // measured faster: docs/dropped.md, "tiles per wave".
 int tiles_per_wave_for(const bbq_index *ix) {
   if (ix->opt_tiles_per_wave > 0) return ix->opt_tiles_per_wave;
   switch (ix->geom.w16) {
     case 6: return 8;
-    case 8: return 4;
+    case 8: return 8;
     default: return 1;
   }
 }

@@ -160,11 +160,12 @@ __device__ __forceinline__ void sweep_chunk_end(const ScanArgs &a, const SweepCo
 
 // The sweep of a wave's TPW > 1 tiles: the digit form of the unfiltered compact sweep (MODE 2, RS, DG) in the early order, nothing else.
 // Tile 0 is loaded in front of the staging and the barrier exactly as the TPW = 1 kernel loads its one tile (the same two arms of the scalar
-// branch, the masks the oldest load in flight); tile t + 1's loads are issued as soon as tile t's popcounts are done - its code registers are
-// dead there - so the bound of tile t runs with them in flight, and no two tiles' codes are held at once.  The loop over the
-// wave's tiles is unrolled: as a loop, the next tile's correction word, row sum and additive bound came back in registers of their own and
-// the copies at the back edge waited for every load of the tile.  A tile's addresses are the first tile's plus constant strides (tile_stride,
-// the 128 bytes of a tile's row sums, the 8 of its add_range).  A wave whose next tile lies beyond the index leaves: the tiles are consecutive.
+// branch, the masks the oldest load in flight); tile t + 1's nine loads are issued behind tile t's bound - the code registers and the three
+// small words' registers are all dead there, so nothing is copied and no two tiles' codes are held at once - and its popcounts count the
+// chunks down as they arrive.  The loop over the wave's tiles is unrolled: as a loop, the next tile's words came back in registers of their
+// own and the copies at the back edge waited for every load of the tile.  The loads go through a buffer descriptor per tile, rebased with
+// scalar arithmetic (tile_buffer, above); a lane's offsets are computed once per wave.  A wave whose next tile lies beyond the index leaves:
+// the tiles are consecutive.  The rows beyond the index - in its last tile alone - are taken out of the bound's ballot by a scalar mask.
 // Per row it computes what the kernel computes: the same integer and the same f32 bound.  What only the rows that pass the bound need - the
 // f64 bound of a query without f32 images, the exact corrections, the f64 score, the key test, the candidate - is NOT in the tile loop
 // (99.9 % of the rows never get there, and unrolled TPW times it held the f64 half of the query, the side array's base and the f64 temporaries
@@ -196,6 +197,168 @@ struct FastBoundParams {
   float ayf, lyf, c1f, k2mf, tinyf, csf, caf;
 };
 
+// ---- the tile loop's loads: buffer loads through descriptors built on the scalar unit.  With 64-bit vector addresses every tile paid five or
+// six vector instructions for the next tile's addresses (the lane's 64-bit pointer rebuilt, its carry beyond the 4 KB of the instruction's
+// offset, the correction word's and the row sums' offsets) and held three address pairs in vector registers across the loop.  Here a lane's
+// part of an address is one 32-bit offset computed once per wave (16 and 4 bytes per lane for codes and correction word, 4 per pair of lanes for the row sums), a tile's base is the
+// descriptor's - rebased per tile with scalar arithmetic, so that no offset grows with the index - the chunk's offset is the instruction's
+// 12 bits and, beyond them, a multiple of 4 KB in a scalar register.  The descriptor's size is the tile's (the wave's tiles' add_range); every access
+// is in range by construction, as the 64-bit form's were - the size is no second line of defence for the part in the scalar offset.  STREAM: the streamed arm's cache policy (`nt`, what
+// __builtin_nontemporal_load gives the 64-bit form).  The compiler counts these loads in vmcnt like any other.
+constexpr int kBufferWord3 = 0x00020000;  // a raw buffer of dwords
+constexpr int kBufferImmBits = 12;        // the instruction's own offset
+template <class T> __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_buffer(const T *base, int bytes) {  // both wave-uniform
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(base), 0, bytes, kBufferWord3);
+}
+template <bool STREAM> __device__ __forceinline__ u32x4 buffer_load16(__amdgpu_buffer_rsrc_t r, uint32_t lane_off, int off, int soff = 0) {
+  constexpr int imm = (1 << kBufferImmBits) - 1;
+  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(lane_off + (uint32_t)(off & imm)), (off & ~imm) + soff, STREAM ? 2 : 0));
+}
+template <bool STREAM> __device__ __forceinline__ uint32_t buffer_load4(__amdgpu_buffer_rsrc_t r, uint32_t lane_off, int off, int soff = 0) {
+  constexpr int imm = (1 << kBufferImmBits) - 1;
+  return __builtin_amdgcn_raw_buffer_load_b32(r, (int)(lane_off + (uint32_t)(off & imm)), (off & ~imm) + soff, STREAM ? 2 : 0);
+}
+// a lane's offsets into its tile, computed once per wave
+struct LaneOffsets {
+  uint32_t code;  // its 16 bytes of a chunk
+  uint32_t word;  // its correction word
+  uint32_t sum;   // the aligned pair of row sums its own lies in
+};
+// the wave's TPW tiles' entries of the two side arrays.  The row sums: a scalar base, which a load takes with the lane's 32-bit offset and a
+// constant (two scalar registers where a descriptor takes four).  The additive bounds: a descriptor, read without any vector offset - as a
+// scalar base the compiler kept it in a pair of vector registers and read it back into scalar ones, two instructions, for every tile.
+struct WaveSides {
+  const char *sums;             // row_sums of the wave's first tile
+  __amdgpu_buffer_rsrc_t adds;  // add_range of the wave's tiles
+  int add_at;                   // tile_add_bound's choice, in bytes
+};
+template <int W, bool STREAM>
+__device__ __forceinline__ void buffer_load_codes(__amdgpu_buffer_rsrc_t tile, const LaneOffsets &lo, u32x4 (&c)[W]) {
+#pragma unroll
+  for (int j = 0; j < W; ++j) c[j] = buffer_load16<STREAM>(tile, lo.code, j * (kTileRows * kChunkBytes));
+}
+// Called once per tile in front of its loads: the lane's offsets pass through an empty asm, in place.  Seen as ONE value across the unrolled
+// tiles, offset + 1024, + 2048 and + 3072 were formed once in front of the loop and held in three more vector registers, in another block than
+// the loads, where they no longer fold into the instruction's offset.
+// (An empty asm on a value, as bbq_mfma_kernels.hip has them: no instruction, but it pins what THIS build's compiler does with the value - to
+// check again, scripts/scan_resources.py: the twins' registers, and its count of v_pk_* in them.)
+__device__ __forceinline__ void per_tile(LaneOffsets &lo) { asm("" : "+v"(lo.code), "+v"(lo.word), "+v"(lo.sum)); }
+// tile t's three small words: the correction word, the row's sum, the additive bound (default policy in both arms, as it always was).
+// The sum as the aligned PAIR of 16-bit entries the lane's own lies in, a 32-bit load, its half picked behind the popcounts (load_tile's
+// rule, bbq_kernel_common.h): loaded as 16 bits, the compiler widened the value at the head of the next block - an instruction in front of
+// the tile's first popcount that waited for all of the tile's loads but the last.
+template <int W, bool STREAM, bool ADD = true>
+__device__ __forceinline__ void buffer_load_words(__amdgpu_buffer_rsrc_t tile, const WaveSides &ws, const LaneOffsets &lo, int t,
+                                                  uint32_t &cw, uint32_t &ones, float &aadd) {
+  cw = buffer_load4<STREAM>(tile, lo.word, (int)tile_corr_offset(W));
+  // (without stream_ptr's other address: the arm's fences alone keep the two arms' loads apart - both forms are in the machine code - and
+  // a second base was two more scalar registers, which the loop does not have)
+  const uint32_t *__restrict__ rs = reinterpret_cast<const uint32_t *>(ws.sums + lo.sum + t * (kTileRows * 2));
+  if constexpr (STREAM) ones = BBQ_STREAM_LOAD(rs);
+  else ones = *rs;
+  // (the folded bound has the additive bounds of all the wave's tiles from one load in front of the loop)
+  if constexpr (ADD) aadd = __builtin_bit_cast(float, buffer_load4<false>(ws.adds, 0u, t * 8, ws.add_at));
+}
+
+// tile_digit_dot for the tile loop: the same three chains, the same integer.  The first chain starts at -k (u32 arithmetic: the same sum
+// modulo 2^32, and qcDist is below 2^32) instead of 0, so that digit_dot's subtraction is the accumulator's initial move; the row's sum is
+// added by the caller.  12 chunks: tile_digit_dot's compiler barrier behind each chunk does not order the chunks' arithmetic, and the
+// scheduler, given the codes of a whole tile at once, formed the selections of two and three chunks ahead of their popcounts - 92 vector
+// registers in the 2-tile kernel; a scheduling barrier keeps each chunk's work together (this build's scheduler: scripts/scan_resources.py).
+template <int W>
+__device__ __forceinline__ uint32_t tile_digit_sums(const u32x4 (&c)[W], const u32x4 *__restrict__ s_digits, uint32_t k) {
+  uint32_t a0 = 0u - k, a1 = 0, a2 = 0;
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    const u32x4 *__restrict__ m = s_digits + j * kDigitMasks;
+    a0 = popc4_acc(digit_select(c[j], m[0], m[1]), a0);
+    a1 = popc4_acc(digit_select(c[j], m[2], m[3]), a1);
+    a2 = popc4_acc(c[j] & m[4], a2);
+    if constexpr (W >= 12) {
+      BBQ_BRANCH_FENCE();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  return a0 + 3u * a1 + 9u * a2;
+}
+
+// fast_bound_passes for the tile loop: the same operations in the same order on the same values - the same verdict for every row - but
+// (1) against a threshold image that is NaN for a query without f32 images, so that such a query passes every row without a branch around
+// the bound, (2) without the validity, which the loop applies to the ballot on the scalar unit, and (3) with two values passed through an
+// empty asm: left alone, the compiler packs the bound's pairs of like operations into v_pk_*_f32 - half rate on this device - and pays four
+// moves per row to line their operands up.  (Which pairs it packs is this build's choice: scripts/scan_resources.py counts the v_pk_* left in
+// the twins, 0 with these two.)
+__device__ __forceinline__ float keep_unpacked(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ bool tile_bound_passes(uint32_t qc, uint32_t cw, float aadd, uint32_t ones, const FastBoundParams &p, float tinyf, float thz) {
+  const float al = compact_lower(cw), au = compact_upper(cw);
+  const float g = fmaf(p.lyf, (float)qc, p.ayf * (float)ones);
+  const float A = p.c1f - g;
+  const float pa = keep_unpacked(al * A), pb = au * g;
+  const float s = pa + pb;
+  const float e = fabsf(pa) + fabsf(pb);
+  const float w = fabsf(al) + fabsf(au);
+  const float slack = fmaf(kFastK1, e, fmaf(w, p.k2mf, tinyf));
+  const float zc = keep_unpacked(fmaf(p.csf, s, p.caf * aadd));
+  const float zs = fmaf(p.csf, slack, kFastAddRel * fabsf(aadd));
+  const float z0 = zc + zs;
+  const float zup = fmaf(kFastAddRel, fabsf(z0), z0);
+  return !(zup <= thz);  // NaN anywhere passes -> exact path
+}
+
+// ---- the bound, folded (kFoldedBound; the tile loop's other form, tile_bound_passes, stays for the comparison of the two).
+// The same inequality as fast_bound_passes, split into a per-row side and a per-tile threshold:
+//     row side   r = s + K1 e + k2m w            s = al (c1 - g) + au g,  e = |al (c1 - g)| + |au g|,  w = |al| + |au|
+//     tile side  T = ((zth - ca aadd) - pad) / cs,   pad = 2^-21 |aadd| + 2^-21 |zth - ca aadd| + cs tiny
+// and the row passes unless r <= T.  g comes from the three digit counts and the row's sum without forming qcDist:
+//     g = ly D + b sum,   D = a0 + 3 a1 + 9 a2 - K (an integer, exact in f32: |D| < 2^24),   b = 4 ly + ay,
+// which is ay sum + ly qc because qc = D + 4 sum (digit_dot).  qcDist itself is formed inside the rare passing branch, for the deferred entry.
+// T is computed ONCE per wave for all its tiles, lane t for tile t (the wave's add_range entries are one load), and read per tile with
+// v_readlane into a scalar register: the row's compare reads it from there.  Per row the fold takes out the two products with aadd, two FMAs,
+// the z-space sum, the final inflation and one integer addition.
+// Error budget, on top of the one above fast_bound_passes (u = 2^-24; M, W, E as there; the twins sweep 1-bit rows with a 4-plane query,
+// so qcmax = 15 x1max):
+//  * g.  |ly D| <= |ly| (qcmax + 4 x1max) = 1.27 |ly| qcmax and |b sum| <= (4 |ly| + |ay|) x1max.  lyf is within u of ly, the computed
+//    b = fl(4 lyf + ayf) within 2 u (4 |ly| + |ay|) of b, D and sum are exact as floats, the product b sum and the FMA round once each
+//    (u |b sum|, u |g| <= u M / 2): with x = 2 |ly| qcmax, y = 2 |ay| x1max, x + y <= M, the computed g is within
+//    u (1.04 x + 1.5 y + 0.5 M) <= 2.0 u M of g - inside the 2.1 u M the budget above gives g, so |s_f32 - s| <= 9.1 u W M stands.
+//  * the row side.  K1 e + k2m w is computed with the same two roundings as before (a product and an FMA where there were two FMAs: the
+//    2^-18 in K1 pays them); r = fl(s + slack) adds one rounding, u |r| <= u (1.01 W M + slack): 1.02 u W M of the 6.8 u W M that
+//    2^-20 = 16 u leaves above the 9.2 u needed, and u slack of the 2^-18.
+//  * the tile side.  ca aadd is exact (ca = +-1), the division by cs exact (cs = 1 or 2); num = fl(zth - ca aadd), pad and fl(num - pad)
+//    round five times, each by at most u of a magnitude <= |num| (1 + 2^-20) + pad: 2^-21 |num| = 8 u |num| pays them, 2^-21 |aadd| pays the
+//    2^-23 |aadd| that add_range's rounding to nearest needs, cs tiny the absolute parts (tiny is scaled by cs on the row side of
+//    fast_bound_passes as well) and what leaves the normal range here (at most 2^-126 per operation, tiny >= 2^-100).
+//  * zth is already the conservative image (z_threshold_f32 rounds down), so T <= the true (zth - ca aadd - 2^-23 |aadd| - cs tiny) / cs
+//    and  r <= T  implies  cs (s + allowance) + ca aadd + ... <= zth: the row's exact score cannot beat the threshold.
+//  * NaN and overflow pass.  s = +-inf needs an infinite product or sum, then e = +inf (e >= |s| before rounding), slack = +inf and r is
+//    +inf or NaN: never -inf, so r <= T is false.  zth = -inf gives num = -inf, pad = +inf, T = -inf: every row passes.  A NaN zth (a query
+//    without f32 images) or an infinite or NaN aadd gives T = -inf or NaN: every row passes.
+//  tests/test_bound_folded_cpu.py restates both sides in numpy f32, fused and unfused, and checks dominance over the exact score.
+constexpr bool kFoldedBound = true;
+struct FoldedBoundParams {
+  float lyf, bf, c1f, k2mf;  // b = 4 ly + ay from the images
+};
+__device__ __forceinline__ float tile_threshold(float aadd, const FastBoundParams &p, float thz) {
+  const float num = thz - p.caf * aadd;
+  const float pad = fmaf(kFastAddRel, fabsf(aadd), fmaf(kFastAddRel, fabsf(num), p.csf * p.tinyf));
+  return (num - pad) * (p.csf == 2.0f ? 0.5f : 1.0f);  // 1 / cs, exact: cs is 1 or 2 (QueryParams::csf)
+}
+__device__ __forceinline__ bool folded_bound_passes(uint32_t d, uint32_t cw, uint32_t sum, const FoldedBoundParams &p, float tile_th) {
+  const float al = compact_lower(cw), au = compact_upper(cw);
+  const float g = fmaf(p.lyf, (float)(int32_t)d, p.bf * (float)sum);
+  const float A = p.c1f - g;
+  const float pa = keep_unpacked(al * A), pb = au * g;
+  const float s = pa + pb;
+  const float e = fabsf(pa) + fabsf(pb);
+  const float w = fabsf(al) + fabsf(au);
+  const float slack = fmaf(kFastK1, e, w * p.k2mf);
+  const float r = s + slack;
+  return !(r <= tile_th);  // NaN anywhere passes -> exact path
+}
+
 template <int W, int TPW, int NT>
 __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepCoord wg, const bool idle, const int q, u32x4 *s_planes, uint32_t *s_def,
                                                  uint32_t *s_cnt, uint32_t &n_def) {
@@ -212,27 +375,59 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
   const int32_t sim = qp->sim, fast_bound = qp->fast_bound;
   const uint32_t digit_k = qp->digit_k;
   const Threshold th = a.theta[q];
+  // a query without f32 images defers every valid row - its f64 bound stands in front of the exact path, behind the loop: no row fails a NaN
+  const float thz = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fast_bound ? threshold_z(th) : __builtin_nanf(""))));
+  // (tinyf is the addend of an FMA whose other factor is a scalar as well, and an instruction reads one scalar register: kept in a vector
+  // register for the wave, or every tile pays the move.  Through a vector load of its own - a lane offset the compiler cannot see through:
+  // copied out of the scalar load that brings the images, it took all eight of them into vector registers.  This build's compiler again:
+  // scripts/scan_resources.py shows it as +8 registers in every twin)
+  float tinyv = 0.0f;
+  if constexpr (!kFoldedBound) {
+    uint32_t lane_zero = 0;
+    asm("" : "+v"(lane_zero));
+    tinyv = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(&qp->tinyf) + lane_zero);
+  }
+  // the folded bound's per-row constants (b = 4 ly + ay: uniform, kept in a scalar register)
+  const FoldedBoundParams pf = {p.lyf, __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fmaf(4.0f, p.lyf, p.ayf)))), p.c1f, p.k2mf};
   n_def = 0;
   const int64_t chunk = a.chunk_begin + wg.chunk_local;
   const int64_t n_tiles = (a.idx.n_rows + kTileRows - 1) / kTileRows;
   const int64_t tile0 = chunk * kTilesPerChunk + wave_first_tile(TPW, wave);
   const bool has_tile = !idle && tile0 < n_tiles;  // wave-uniform, decided on the scalar unit
   const bool resident = chunk_is_resident(chunk, a.idx);
-  const int64_t tile_stride = a.idx.geom.tile_stride;
-  // the addresses of the wave's first tile
+  const int tile_stride = a.idx.geom.tile_stride;
+  // what the wave has of the index: its tiles and its rows (both wave-uniform, 0 without a tile)
+  const int64_t tiles_left = n_tiles - tile0, rows_left = a.idx.n_rows - tile0 * kTileRows;
+  const int my_tiles = !has_tile ? 0 : tiles_left < TPW ? (int)tiles_left : TPW;
+  const int my_rows = !has_tile ? 0 : rows_left < TPW * kTileRows ? (int)rows_left : TPW * kTileRows;
+  // the wave's first tile, and the TPW tiles' entries of the two side arrays
   const uint8_t *__restrict__ tp = a.idx.tiles + tile0 * tile_stride;
-  const uint32_t *__restrict__ rs = reinterpret_cast<const uint32_t *>(a.idx.row_sums + ((tile0 * kTileRows + lane) & ~(int64_t)1));
-  const float *__restrict__ ar = a.idx.add_range + tile0 * 2 + (sim == 0 ? 0 : 1);  // tile_add_bound's choice
+  const WaveSides ws = {reinterpret_cast<const char *>(a.idx.row_sums + tile0 * kTileRows), tile_buffer(a.idx.add_range + tile0 * 2, my_tiles * 8), sim == 0 ? 0 : 4};
+  LaneOffsets lo = {(uint32_t)lane << 4, (uint32_t)lane << 2, (uint32_t)(lane >> 1) << 2};
   u32x4 c[W];
   uint32_t cw, ones;
   float aadd;
-  f64x2 lu = {0.0, 0.0};  // (load_tile's inline corrections: not loaded here)
-  double xadd = 0.0, x1 = 0.0;
   if (has_tile) {
     u32x4 staged;
-    auto load_masks = [&]() { if (tid < W * QU) staged = gp[tid]; };
-    load_tile<W, 1, true>(tp, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, rs, &ones, load_masks);
-    aadd = *ar;
+    // (load_tile's shape: both arms of one scalar branch, the masks the oldest load in flight of whichever is taken, the streamed one fenced)
+    const __amdgpu_buffer_rsrc_t tb = tile_buffer(tp, tile_stride);
+    if (resident) {
+      if (tid < W * QU) staged = gp[tid];
+      buffer_load_codes<W, false>(tb, lo, c);
+      buffer_load_words<W, false, !kFoldedBound>(tb, ws, lo, 0, cw, ones, aadd);
+    } else {
+      BBQ_BRANCH_FENCE();
+      if (tid < W * QU) staged = gp[tid];
+      buffer_load_codes<W, true>(tb, lo, c);
+      buffer_load_words<W, true, !kFoldedBound>(tb, ws, lo, 0, cw, ones, aadd);
+      BBQ_BRANCH_FENCE();
+    }
+    // the folded bound: lane t takes tile t's additive bound (the wave's last tile's in the lanes beyond: in range, never used), the
+    // youngest load of tile 0 - the popcounts' countdown does not wait for it
+    if constexpr (kFoldedBound) {
+      const int t_lane = lane < my_tiles ? lane : my_tiles - 1;
+      aadd = __builtin_bit_cast(float, buffer_load4<false>(ws.adds, (uint32_t)t_lane * 8u, 0, ws.add_at));
+    }
     if (tid < W * QU) s_planes[tid] = staged;
     asm volatile("; staged with the first tile's loads in flight" ::: "memory");
   } else {
@@ -249,37 +444,66 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
   __syncthreads();  // LDS only: a wave that staged nothing passes it with its tile's loads in flight
   if (!has_tile) return true;
 
-  const int64_t tiles_left = n_tiles - tile0;
-  const int my_tiles = tiles_left < TPW ? (int)tiles_left : TPW;  // >= 1, wave-uniform
-  const int64_t row0 = tile0 * kTileRows;
   const uint32_t pick_at = (uint32_t)(lane & 1) << 4;  // the lane's half of its pair of row sums
-  const uint32_t row_in_chunk0 = (uint32_t)(wave_first_tile(TPW, wave) * kTileRows + lane);
+  const uint32_t row_in_chunk0 = (uint32_t)(wave_first_tile(TPW, wave) * kTileRows);  // (scalar: the lane is added where a row is deferred)
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
-    uint32_t qc = tile_digit_dot<W>(c, s_planes, 0u, digit_k);
-    __builtin_amdgcn_sched_barrier(0);  // (the loads below and the pick of the sum stay behind the popcounts, as the pick does in the TPW = 1 kernel)
-    const uint32_t sum = __builtin_amdgcn_ubfe(ones, pick_at, 16u);
-    qc += sum << 2;  // digit_dot's 4 * ones: u32 arithmetic, the same integer in either order
-    const uint32_t cw_t = cw;
-    const float aadd_t = aadd;
-    const bool more = t + 1 < TPW && t + 1 < my_tiles;
-    if (more) {  // the next tile's loads, its codes into the registers this tile is done with
-      load_tile<W, 1, true>(tp + (t + 1) * tile_stride, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, rs + (t + 1) * (kTileRows / 2), &ones);
-      aadd = ar[(t + 1) * 2];
-    }
-    const int64_t rows_left = a.idx.n_rows - (row0 + t * kTileRows);  // > 0: the tile exists
-    const bool valid = (uint32_t)lane < (uint32_t)(rows_left < kTileRows ? rows_left : kTileRows);
-    // a query without f32 images defers every valid row: its f64 bound stands in front of the exact path, behind the loop
-    const bool pass = fast_bound ? fast_bound_passes(valid, qc, cw_t, aadd_t, sum, p, th) : valid;
+    uint32_t qc = tile_digit_sums<W>(c, s_planes, digit_k);
+    __builtin_amdgcn_sched_barrier(0);  // (the bound and the loads below stay behind the popcounts, as the pick of the sum does in the TPW = 1 kernel)
+    // The bound's verdicts as a mask in a scalar pair, straight from its compare; the rows beyond the index - in the index's last tile alone -
+    // are taken out of it there.  (1 <= rows_here: the tile exists.)
+    auto verdicts = [&]() {
+      const uint32_t sum = __builtin_amdgcn_ubfe(ones, pick_at, 16u);  // the lane's half of the pair
+      bool pass;
+      if constexpr (kFoldedBound) {
+        // (the wave's thresholds once, behind the first tile's popcounts: lane t has tile t's; aadd becomes the thresholds' register)
+        if (t == 0) aadd = tile_threshold(aadd, p, thz);
+        const float tile_th = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, aadd), t));
+        pass = folded_bound_passes(qc, cw, sum, pf, tile_th);
+      }
+      if constexpr (!kFoldedBound) {
+        qc += sum << 2;  // digit_dot's 4 * ones: u32 arithmetic, the same integer in either order
+        pass = tile_bound_passes(qc, cw, aadd, sum, p, tinyv, thz);
+      }
+      unsigned long long passing = __builtin_amdgcn_ballot_w64(pass);
+      const int rows_here = my_rows - t * kTileRows;
+      if (rows_here < kTileRows) passing &= (1ull << rows_here) - 1ull;
+      return passing;
+    };
     // The entry's place: the wave's running count plus the passing lanes below this one.  No atomic, and where nobody passes - nearly every
     // tile - a scalar branch over all of it.
-    const unsigned long long passing = __ballot(pass);
-    if (passing) {
-      const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(passing >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)passing, 0u));
-      if (pass) s_def[deferred_pos<NW>(n_def + below, wave)] = deferred_entry(row_in_chunk0 + (uint32_t)(t * kTileRows), qc);
-      n_def += (uint32_t)__popcll(passing);
+    auto defer = [&](const unsigned long long passing) {
+      if (passing) {
+        // (the folded bound never formed qcDist: a deferred row's, here, from this tile's pair of row sums)
+        if constexpr (kFoldedBound) qc += __builtin_amdgcn_ubfe(ones, pick_at, 16u) << 2;
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(passing >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)passing, 0u));
+        if (__builtin_amdgcn_inverse_ballot_w64(passing)) s_def[deferred_pos<NW>(n_def + below, wave)] = deferred_entry(row_in_chunk0 + (uint32_t)(t * kTileRows) + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), qc);
+        n_def += (uint32_t)__popcll(passing);
+      }
+    };
+    const unsigned long long passing = verdicts();
+    if constexpr (kFoldedBound) defer(passing);  // in front of the next tile's loads: it reads this tile's row sums once more
+    // The next tile's loads BEHIND the bound, which was this tile's last use of the registers the three small words land in - issued in front
+    // of it, with the codes behind the popcounts, they came back in registers of their own, and the copies stood behind a wait for the whole
+    // tile in front of the next one's loads.  All nine under ONE scalar branch on the cache policy, as load_tile has them: with the words
+    // under a branch of their own, the compiler's count where the arms join made the popcounts wait for the words behind the codes.
+    if (t + 1 < TPW && t + 1 < my_tiles) {
+      per_tile(lo);
+      const __amdgpu_buffer_rsrc_t tb = tile_buffer(tp + (int64_t)(t + 1) * tile_stride, tile_stride);
+      if (resident) {
+        buffer_load_codes<W, false>(tb, lo, c);
+        buffer_load_words<W, false, !kFoldedBound>(tb, ws, lo, t + 1, cw, ones, aadd);
+      } else {
+        BBQ_BRANCH_FENCE();
+        buffer_load_codes<W, true>(tb, lo, c);
+        buffer_load_words<W, true, !kFoldedBound>(tb, ws, lo, t + 1, cw, ones, aadd);
+        BBQ_BRANCH_FENCE();
+      }
+      if constexpr (!kFoldedBound) defer(passing);
+    } else {  // (the wave's last tile: an arm of its own - as the negation of the condition above, a condition that lives across blocks, the
+      if constexpr (!kFoldedBound) defer(passing);  // way out went through a v_cndmask / v_cmp pair per tile)
+      break;
     }
-    if (!more) break;
   }
   return true;
 }

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Registers, occupancy and scratch of EVERY bbq_scan_kernel instantiation, from the compiler's own remarks (no device needed).
 
-  scripts/scan_resources.py CSRC_DIR                  one line per instantiation: VGPRs / occupancy (waves per SIMD) / scratch bytes per lane
+  scripts/scan_resources.py CSRC_DIR                  one line per instantiation: VGPRs / occupancy (waves per SIMD) / scratch bytes per lane;
+                                                      fails if a kernel with several tiles per wave exceeds its recorded registers / waves (TWIN_BUDGET) or has any v_pk_*_f32 left
   scripts/scan_resources.py BEFORE_DIR AFTER_DIR      the two side by side, the rows that differ marked, lost waves and new scratch counted
 
 CSRC_DIR is a copy of better-binary-quantization_amd/csrc (e.g. `git archive HEAD better-binary-quantization_amd/csrc | tar -x -C DIR`
@@ -55,14 +56,63 @@ def table(csrc):
     return res
 
 
+def packed_f32_in_twins(csrc):
+    """v_pk_*_f32 instructions in the kernels with several tiles per wave (bbq_kernels.hip): their bound is written so that the compiler does
+    not pack it (tile_bound_passes, bbq_scan_body.h); name -> count"""
+    flags = [f for f in FLAGS if not f.startswith("-Rpass")]
+    flags[flags.index("-c")] = "-S"
+    flags[flags.index("/dev/null")] = "-"
+    r = subprocess.run([HIPCC] + flags + [FILES[0]], cwd=csrc, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+    if r.returncode != 0:
+        sys.exit("compile of %s/%s to assembly failed" % (csrc, FILES[0]))
+    out, name = {}, None
+    for line in r.stdout.splitlines():
+        m = re.match(r"(_ZN3bbq15bbq_scan_kernelILi\d+ELi\d+ELi\d+ELi\d+ELb1ELb1ELi([248])E\S*):", line)
+        if m:
+            name = m.group(1)
+            out[name] = 0
+        elif name and line.startswith("\t.size\t" + name):
+            name = None
+        elif name and re.match(r"\tv_pk_\w+_f32", line):
+            out[name] += 1
+    return out
+
+
+# What the kernels with several tiles per wave came out of the compiler with when their tile loop was last changed (ROCm 7.2): vector
+# registers and waves per SIMD by TPW, per chunks of a row.  Their loop holds values in place with empty asms and a scheduling barrier
+# (per_tile, keep_unpacked, tile_digit_sums in bbq_scan_body.h), each of which pins what that compiler did: a twin above its line here - more
+# registers, fewer waves, any scratch - means a later compiler does something else with them.
+TWIN_BUDGET = {6: {2: (51, 8), 4: (51, 8), 8: (50, 8)}, 8: {2: (59, 8), 4: (59, 8), 8: (58, 8)}, 12: {2: (75, 6), 4: (75, 6), 8: (74, 6)}}
+
+
+def twins_over_budget(res):
+    over = []
+    for key, (vgprs, waves, scratch) in res.items():
+        parts = key.split(", ")
+        if len(parts) < 7 or not parts[6].isdigit() or int(parts[6]) < 2:
+            continue
+        budget = TWIN_BUDGET.get(int(parts[1]), {}).get(int(parts[6]))
+        if budget and (vgprs > budget[0] or waves < budget[1] or scratch > 0):
+            over.append("%s: %d registers / %d waves / %d scratch, recorded %d / %d / 0" % (key, vgprs, waves, scratch, budget[0], budget[1]))
+    return over
+
+
 def fmt(v):
     return "%d / %d / %d" % v if v else "-"
 
 
 def main():
     if len(sys.argv) == 2:
-        for k, v in sorted(table(sys.argv[1]).items()):
+        res = table(sys.argv[1])
+        for k, v in sorted(res.items()):
             print("%-44s %s" % (k, fmt(v)))
+        over = twins_over_budget(res)
+        if over:
+            sys.exit("kernels with several tiles per wave above their recorded resources:\n  " + "\n  ".join(over))
+        pk = packed_f32_in_twins(sys.argv[1])
+        print("\nv_pk_*_f32 in the %d kernels with several tiles per wave: %d" % (len(pk), sum(pk.values())))
+        if sum(pk.values()):
+            sys.exit("the twins' bound is packed again: see tile_bound_passes (bbq_scan_body.h)")
         return
     before, after = table(sys.argv[1]), table(sys.argv[2])
     lost = scratch = changed = 0
