@@ -576,12 +576,43 @@ struct MaxSimAccArgs {
   double *acc;                    // [sub-batch's queries][live]
   float *scores;                  // the same shape
   uint32_t *ords;                 // the same shape
-  const int32_t *live_group;      // [live] the group number of every slot
+  const int32_t *live_group;      // [live] the group number of every slot; null (MaxSim over chosen groups): ords is not written
   int64_t live;
 };
 struct MaxSimScoreArgs {
   GroupScoreArgs g;            // qplanes / qparams / rep: per staged VECTOR of the block; n_queries: the length of `queries`
   const MaxSimQuery *queries;  // a workgroup is one chunk for one of them
+};
+
+// MaxSim over chosen groups (bbq_maxsim_cand_kernels.hip): a query scores its own candidate list, groups of a group set in the caller's
+// order, duplicates included.  The rows of a query's candidates, back to back in list order, are its EXPANDED rows; a lane of the score
+// pass is one of them.  The host stages one record per candidate - never a row list - and per query one more behind them, {0, total}.
+// Entry e of a query is its e-th candidate: token t's key goes to rep[vec_first + t][e], the rows of the three keyed arrays `stride`
+// entries long (the longest list of the sub-batch); MaxSimAccArgs::live is that stride and live_group is null.
+constexpr int kMaxSimCandThreads = 256;  // expanded rows per workgroup (four waves share the staged token block)
+constexpr int64_t kMaxSimCandMaxRows = 0x7fffffff;  // of one query's expanded rows
+struct MaxSimCand {
+  uint32_t first_row;  // the candidate group's first row
+  uint32_t pos;        // its first row's position among the query's expanded rows: the prefix sum of the group lengths in front of it
+};
+struct MaxSimCandQuery {
+  int64_t rec_first;  // its records: recs[rec_first .. rec_first + n_cand], the last one the terminator
+  int32_t n_cand;     // >= 1 for a query that is launched
+  int32_t total;      // its expanded rows = recs[rec_first + n_cand].pos
+};
+static_assert(sizeof(MaxSimCand) == 8 && sizeof(MaxSimCandQuery) == 16, "staged in arrays behind 8-byte data");
+struct MaxSimCandArgs {
+  IndexView idx;
+  const uint4 *qplanes;           // [the block's vectors][w16][QU] staged query data, as ScanArgs::qplanes
+  const QueryParams *qparams;     // [the block's vectors]
+  const uint64_t *accept;         // the accept words of the group set's filter; null: every row
+  const MaxSimQuery *queries;     // [grid.y] the token block of each query that has one; .query indexes cq
+  const MaxSimCandQuery *cq;      // [sub-batch's queries]
+  const MaxSimCand *recs;
+  unsigned long long *rep;        // [the block's vectors][stride] cleared to 0 before the launch: only ever raised (group_key)
+  int64_t stride;
+  int32_t tok_pass;               // tokens a workgroup stages in LDS at a time: kMaxSimTokenBlock unless the row is too wide for that
+  int32_t pad;
 };
 
 constexpr int kFinalizeThreads = 1024;

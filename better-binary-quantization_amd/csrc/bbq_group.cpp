@@ -289,6 +289,7 @@ int bbq_groups_create(bbq_index *ix, const int64_t *group_offsets, int64_t n_gro
   const uint64_t *bits = f ? f->h_bits.data() : nullptr;
   std::vector<int32_t> slot((size_t)n_groups);
   plan_groups(group_offsets, n_groups, bits, slot.data(), &g->live, &g->n_nonempty);
+  g->slot = slot;
   if (n_rows == 0) {  // nothing to sweep: every call answers with nothing
     *out = g.release();
     return BBQ_OK;

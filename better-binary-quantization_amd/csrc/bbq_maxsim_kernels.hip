@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kMaxSimAccThreads) void bbq_maxsim_accumulate_kerne
   for (; t < mq.n_tok; ++t) acc = acc + (double)__uint_as_float(group_key_score_bits(k[(size_t)t * (size_t)a.live]));
   if (mq.flags & kMaxSimLast) {
     a.scores[at] = (float)acc;
-    a.ords[at] = (uint32_t)a.live_group[slot];
+    if (a.live_group) a.ords[at] = (uint32_t)a.live_group[slot];  // null: the caller's entries are not slots of the group set
   } else {
     a.acc[at] = acc;
   }
@@ -235,7 +235,7 @@ hipError_t launch_maxsim_accumulate(const MaxSimAccArgs &a, int n_queries, hipSt
   if (n_queries <= 0 || a.live <= 0) return hipSuccess;
   const int64_t blocks = (a.live + kMaxSimAccThreads - 1) / kMaxSimAccThreads;
   if (n_queries > 65535 || blocks > 0x7fffffffll || (uint64_t)blocks * kMaxSimAccThreads > kGridWorkItemsMax) return hipErrorInvalidValue;
-  if (!a.rep || !a.queries || !a.acc || !a.scores || !a.ords || !a.live_group) return hipErrorInvalidValue;
+  if (!a.rep || !a.queries || !a.acc || !a.scores || (a.live_group && !a.ords)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bbq_maxsim_accumulate_kernel, dim3((unsigned)blocks, n_queries, 1), dim3(kMaxSimAccThreads, 1, 1), 0, s, a);
   return hipGetLastError();
 }

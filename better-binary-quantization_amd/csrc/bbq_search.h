@@ -25,6 +25,7 @@ struct bbq_groups {
   int64_t live = 0;      // L
   bool filtered = false;
   std::vector<int64_t> offsets;        // [n_groups + 1] the caller's
+  std::vector<int32_t> slot;           // [n_groups] a group's rank among the live groups or -1: what a candidate list is checked against (bbq_maxsim_groups.cpp)
   bbq::DevBuf<uint64_t> d_words;       // [tiles + 1] starts, then - filtered - [tiles] accept
   bbq::DevBuf<uint32_t> d_index;       // [tiles + 1] first_group, then [non-empty groups + 1] slot
   bbq::DevBuf<int32_t> d_live_group;   // [max(L, 1)] the group number of every slot: what the MaxSim search answers with (bbq_maxsim.cpp)

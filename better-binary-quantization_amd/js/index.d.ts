@@ -82,6 +82,10 @@ export declare class BinaryQuantizationFormat {
   searchNearestNeighborsGrouped(query: Float32Array, targetVectors: BinarizedByteVectorValues, groups: RowGroups, k: number): Array<{ index: number; score: number; group: number }>;
   /** extension: the k best groups for a query of several token vectors (MaxSim, late interaction): a group scores the ordered sum of its best accepted row's score for every vector */
   searchNearestNeighborsMaxSim(queryVectors: Float32Array[], targetVectors: BinarizedByteVectorValues, groups: RowGroups, k: number): Array<{ group: number; score: number }>;
+  /** extension: searchNearestNeighborsMaxSim over the candidate groups `groupNumbers` alone, visited in the order given, duplicates included; every candidate must be a live group */
+  searchNearestNeighborsMaxSimInGroups(queryVectors: Float32Array[], targetVectors: BinarizedByteVectorValues, groups: RowGroups, groupNumbers: Int32Array | number[], k: number): Array<{ group: number; score: number }>;
+  /** extension: the MaxSim score of every candidate group, in list order */
+  computeMaxSimGroupScores(queryVectors: Float32Array[], targetVectors: BinarizedByteVectorValues, groups: RowGroups, groupNumbers: Int32Array | number[]): Float32Array;
   /** extension: every row (of options.rowFilter, if given) whose stored f32 score is >= threshold, in ascending ord or, with order 'score', by descending score (ties in ascending ord); a NaN score is in no answer, a NaN threshold throws */
   searchRange(query: Float32Array, targetVectors: BinarizedByteVectorValues, threshold: number, options?: { rowFilter?: RowFilter | null; order?: 'ord' | 'score' }): Array<{ index: number; score: number }>;
   /** extension: the same for many queries per call; one filter serves all of them */

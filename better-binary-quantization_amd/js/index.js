@@ -801,6 +801,53 @@ class BinaryQuantizationFormat {
     return res;
   }
 
+  // the shared front of the two calls over chosen groups: checks, the candidates as an Int32Array, the quantized token vectors
+  _maxSimGroupsArgs(who, queryVectors, targetVectors, groups, groupNumbers, k) {
+    if (!queryVectors || queryVectors.length === 0) throw new Error('查询向量不能为空');
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    if (!(groups instanceof RowGroups)) throw new Error(who + ' needs createRowGroups(targetVectors, offsets)');
+    if (!groupNumbers) throw new Error('候选分组不能为空');
+    const flat = this._flatQueries(queryVectors, targetVectors, k);
+    if (flat === null) return null;
+    const cand = groupNumbers instanceof Int32Array ? groupNumbers : Int32Array.from(groupNumbers, (g) => {
+      if (!Number.isInteger(g) || g < -2147483648 || g > 2147483647) throw new Error('候选分组必须是整数: ' + g);
+      return g;
+    });
+    const q = this.quantizer, sim = simOrdinal(q.similarityFunction), qb = this.config.queryBits;
+    const qz = native.quantizeQueries(flat, queryVectors.length, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, 1);
+    return { cand, qz, sim, qb };
+  }
+
+  /**
+   * extension (not in the reference): searchNearestNeighborsMaxSim over the candidate groups `groupNumbers` alone - the second stage of
+   * late interaction, behind a first stage that nominated them.  What the reference's loop (:349-411) returns when it visits exactly
+   * those groups of `groups`, in the order given and a duplicate once per occurrence, with a heap of min(k, candidates) (libbbq
+   * bbq_search_maxsim_groups_batch).  Every candidate must be a live group of the set: anything else throws the library's message, which
+   * names the first offending position.  Returns [{group, score}].
+   */
+  searchNearestNeighborsMaxSimInGroups(queryVectors, targetVectors, groups, groupNumbers, k) {
+    const tNative = process.hrtime.bigint();
+    const a = this._maxSimGroupsArgs('searchNearestNeighborsMaxSimInGroups', queryVectors, targetVectors, groups, groupNumbers, k);
+    if (a === null) return [];
+    const r = native.searchMaxSimGroups(targetVectors._deviceIndex(), groups._handle(), a.qz.quantized, a.qz.corrections, a.qb, a.sim, k, a.cand);
+    hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
+    const n = r.groups.length, res = new Array(n);
+    for (let j = 0; j < n; j++) res[j] = { group: r.groups[j], score: r.scores[j] };
+    return res;
+  }
+
+  /**
+   * extension (not in the reference): the MaxSim score of every candidate group, in list order, as a Float32Array - the scores
+   * searchNearestNeighborsMaxSimInGroups ranks (libbbq bbq_score_maxsim_groups_batch)
+   */
+  computeMaxSimGroupScores(queryVectors, targetVectors, groups, groupNumbers) {
+    const tNative = process.hrtime.bigint();
+    const a = this._maxSimGroupsArgs('computeMaxSimGroupScores', queryVectors, targetVectors, groups, groupNumbers, 1);
+    const s = native.scoreMaxSimGroups(targetVectors._deviceIndex(), groups._handle(), a.qz.quantized, a.qz.corrections, a.qb, a.sim, a.cand);
+    hostClock.insideAddonNs += process.hrtime.bigint() - tNative;
+    return s;
+  }
+
   /**
    * extension (not in the reference): every row whose stored f32 score is >= threshold - what the reference's loop (:349-411) would collect
    * if it kept every visited ord at or above the threshold and skipped the heap.  options.rowFilter: a RowFilter (createRowFilter) - only the

@@ -914,7 +914,77 @@ static napi_value SearchMaxSim(napi_env env, napi_callback_info info) {
   return o;
 }
 
-/* searchRange(handle, filter handle | null, qquant, qcorr, queryBits, sim, threshold) -> {indices Int32Array, scores Float32Array}: every row (of
+/* the arguments scoreMaxSimGroups and searchMaxSimGroups share: (handle, groups handle, qquant [T * dim], qcorr [T * 4], queryBits, sim, ...) */
+static int maxsim_groups_args(napi_env env, napi_value *a, const char *fn, bbq_index **ix, const bbq_groups **grp, void **qq, void **qc, int64_t *qb,
+                              int64_t *sim, int64_t *n_tok) {
+  *ix = unbox(env, a[0]);
+  if (!*ix) return 0;
+  void *gp = NULL;
+  if (napi_get_value_external(env, a[1], &gp) != napi_ok || !gp || !*(bbq_groups **)gp) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s: the group set is null", fn);
+    napi_throw_error(env, "BBQ1", msg);
+    return 0;
+  }
+  *grp = *(bbq_groups **)gp;
+  size_t ql, cl;
+  if (!get_typed(env, a[2], napi_uint8_array, qq, &ql) || !get_typed(env, a[3], napi_float64_array, qc, &cl) || !get_i64(env, a[4], qb) ||
+      !get_i64(env, a[5], sim)) return 0;
+  const size_t dim = (size_t)bbq_index_dimension(*ix);
+  if (dim == 0 || ql == 0 || ql % dim != 0 || cl != ql / dim * 4) { napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return 0; }
+  *n_tok = (int64_t)(ql / dim);
+  return 1;
+}
+
+/* scoreMaxSimGroups(handle, groups handle, qquant, qcorr, queryBits, sim, candidates Int32Array) -> Float32Array: the MaxSim score of every
+ * candidate group, in list order, for ONE query of T >= 1 token vectors (bbq_score_maxsim_groups_batch with one query) */
+static napi_value ScoreMaxSimGroups(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  if (!get_args(env, info, 7, a)) return NULL;
+  bbq_index *ix; const bbq_groups *grp; void *qq, *qc, *cg; int64_t qb, sim, n_tok; size_t nc;
+  if (!maxsim_groups_args(env, a, "bbq_score_maxsim_groups_batch", &ix, &grp, &qq, &qc, &qb, &sim, &n_tok)) return NULL;
+  if (!get_typed(env, a[6], napi_int32_array, &cg, &nc)) return NULL;
+  const int64_t voff[2] = {0, n_tok}, coff[2] = {0, (int64_t)nc};
+  void *os;
+  napi_value ts = new_typed(env, napi_float32_array, nc, 4, &os);
+  if (!ts) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_score_maxsim_groups_batch(ix, grp, 1, voff, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, coff, (const int32_t *)cg,
+                                         (float *)os);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  return ts;
+}
+
+/* searchMaxSimGroups(handle, groups handle, qquant, qcorr, queryBits, sim, k, candidates Int32Array) -> {groups Int32Array, scores
+ * Float32Array}: the k best of the candidates, visited in list order (bbq_search_maxsim_groups_batch with one query) */
+static napi_value SearchMaxSimGroups(napi_env env, napi_callback_info info) {
+  napi_value a[8];
+  if (!get_args(env, info, 8, a)) return NULL;
+  bbq_index *ix; const bbq_groups *grp; void *qq, *qc, *cg; int64_t qb, sim, n_tok, k; size_t nc;
+  if (!maxsim_groups_args(env, a, "bbq_search_maxsim_groups_batch", &ix, &grp, &qq, &qc, &qb, &sim, &n_tok)) return NULL;
+  if (!get_i64(env, a[6], &k) || !get_typed(env, a[7], napi_int32_array, &cg, &nc)) return NULL;
+  if (k < 0) { napi_throw_error(env, "BBQ7", "k值不能为负数"); return NULL; }
+  const int64_t keff = k < (int64_t)nc ? k : (int64_t)nc;   /* no answer is longer than the list */
+  const int64_t voff[2] = {0, n_tok}, coff[2] = {0, (int64_t)nc};
+  int32_t *og = (int32_t *)malloc(((size_t)keff + 1) * sizeof(int32_t));
+  float *sc = (float *)malloc(((size_t)keff + 1) * sizeof(float));
+  if (!og || !sc) { free(og); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int64_t cnt = 0;
+  int rc = bbq_search_maxsim_groups_batch(ix, grp, 1, voff, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff, coff,
+                                          (const int32_t *)cg, og, sc, &cnt);
+  if (rc != BBQ_OK) { free(og); free(sc); return throw_bbq(env, rc); }
+  void *os, *ogp;
+  napi_value ts = new_typed(env, napi_float32_array, (size_t)cnt, 4, &os);
+  napi_value tg = new_typed(env, napi_int32_array, (size_t)cnt, 4, &ogp);
+  if (!ts || !tg) { free(og); free(sc); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  if (cnt > 0) { memcpy(os, sc, (size_t)cnt * 4); memcpy(ogp, og, (size_t)cnt * 4); }
+  free(og); free(sc);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "groups", tg); set_prop(env, o, "scores", ts);
+  return o;
+}
+
+/* searchRange(handle, filter handle | null, qquant, qcorr, queryBits, sim, threshold) ->{indices Int32Array, scores Float32Array}: every row (of
  * the filter, if one is given) whose f32 score is >= threshold, ascending by ord (bbq_count_range_batch, then bbq_search_range_batch with
  * exactly that room).  A NaN threshold throws. */
 static napi_value SearchRange(napi_env env, napi_callback_info info) {
@@ -1287,6 +1357,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"groupsDestroy", NULL, GroupsDestroy, NULL, NULL, NULL, napi_default, NULL},
       {"searchGrouped", NULL, SearchGrouped, NULL, NULL, NULL, napi_default, NULL},
       {"searchMaxSim", NULL, SearchMaxSim, NULL, NULL, NULL, napi_default, NULL},
+      {"scoreMaxSimGroups", NULL, ScoreMaxSimGroups, NULL, NULL, NULL, napi_default, NULL},
+      {"searchMaxSimGroups", NULL, SearchMaxSimGroups, NULL, NULL, NULL, napi_default, NULL},
       {"setOption", NULL, SetOption, NULL, NULL, NULL, napi_default, NULL},
       {"stats", NULL, Stats, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsCreate", NULL, VectorsCreate, NULL, NULL, NULL, napi_default, NULL},

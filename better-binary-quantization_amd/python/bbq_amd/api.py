@@ -309,6 +309,39 @@ class BinaryQuantizationFormat:
             raise Exception(str(e))
         return [{"group": int(g), "score": float(s)} for g, s in zip(grp, sc)]
 
+    def searchNearestNeighborsMaxSimInGroups(self, queryVectors, targetVectors, rowGroups, groupNumbers, k):
+        """extension: searchNearestNeighborsMaxSim over the candidate groups `groupNumbers` alone - the second stage of late interaction,
+        behind a first stage that nominated them.  What the reference's loop returns when it visits exactly those groups of `rowGroups`,
+        in the order given and a duplicate once per occurrence, with a heap of min(k, candidates).  Every candidate must be a live group.
+        Returns [{group, score}]."""
+        if queryVectors is None or len(queryVectors) == 0:
+            raise Exception("查询向量不能为空")
+        if targetVectors is None:
+            raise Exception("目标向量集合不能为空")
+        if rowGroups is None:
+            raise Exception("行分组不能为空")
+        if groupNumbers is None:
+            raise Exception("候选分组不能为空")
+        if k < 0:
+            raise Exception("k值不能为负数")
+        for v in queryVectors:
+            if v is None:
+                raise Exception("查询向量不能为空")
+            if len(v) != targetVectors.dimension():
+                raise Exception("查询向量维度与目标向量维度不匹配")
+        sim = capi.SIMS[self._sim]
+        if targetVectors._index_bits != 1 and targetVectors.dimension() > 1 and self._config["queryBits"] not in (1, 4):
+            raise Exception("不支持的查询位数: %d，只支持1位和4位" % self._config["queryBits"])  # as _search refuses it
+        try:
+            pairs = [capi.quantize_query(v, targetVectors.getCentroid(), sim, self._config["queryBits"], self._lambda, self._iters, search_path=True)
+                     for v in queryVectors]
+            tokens = (np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs]))
+            cand = np.asarray(groupNumbers, np.int64).reshape(-1)
+            grp, sc = targetVectors._device().search_maxsim_groups_batch([tokens], self._config["queryBits"], sim, k, rowGroups, [cand])[0]
+        except capi.BBQError as e:
+            raise Exception(str(e))
+        return [{"group": int(g), "score": float(s)} for g, s in zip(grp, sc)]
+
     def searchRange(self, queryVector, targetVectors, threshold, rowFilter=None, order="ord"):
         """extension: every row (of `rowFilter`, createRowFilter, if given) whose stored f32 score is >= threshold - what the
         reference's loop would collect if it kept every visited ord at or above the threshold and skipped the heap - as

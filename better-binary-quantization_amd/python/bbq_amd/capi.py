@@ -35,6 +35,7 @@ SYMBOLS = [
     "bbq_search_spans_batch", "bbq_search_spans_filtered_batch",
     "bbq_groups_create", "bbq_groups_destroy", "bbq_groups_count", "bbq_groups_live", "bbq_groups_plan", "bbq_search_grouped_batch",
     "bbq_search_maxsim_batch", "bbq_maxsim_reduce", "bbq_maxsim_token_block",
+    "bbq_score_maxsim_groups_batch", "bbq_search_maxsim_groups_batch",
 ]
 
 
@@ -126,6 +127,8 @@ def lib():
     L.bbq_search_grouped_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
     L.bbq_search_maxsim_batch.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp]
     L.bbq_maxsim_reduce.argtypes = [vp, i64, i64, vp]
+    L.bbq_score_maxsim_groups_batch.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp]
+    L.bbq_search_maxsim_groups_batch.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
     L.bbq_maxsim_token_block.argtypes = []
     L.bbq_maxsim_token_block.restype = i32
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
@@ -632,13 +635,7 @@ class Index:
         [T, dim], qcorr float64 [T, 4]), T >= 1.  Returns a list of (group, score) per query and the status array (0: the device selected
         the answer, 1: the host replayed the heap over the device's sums)."""
         nq = len(token_lists)
-        off = np.zeros(nq + 1, np.int64)
-        for q, (tq, _) in enumerate(token_lists):
-            off[q + 1] = off[q] + np.asarray(tq).reshape(-1, self.dim).shape[0]
-        qq = np.ascontiguousarray(np.concatenate([np.asarray(t[0], np.uint8).reshape(-1, self.dim) for t in token_lists]) if nq else np.zeros((0, self.dim), np.uint8))
-        qc = np.ascontiguousarray(np.concatenate([np.asarray(t[1], np.float64).reshape(-1, 4) for t in token_lists]) if nq else np.zeros((0, 4), np.float64))
-        if qc.shape[0] != qq.shape[0]:
-            raise BBQError(ERR_INVALID_ARG, "one correction row per token vector")
+        off, qq, qc = self._maxsim_tokens(token_lists)
         kk = max(int(k), 0)
         grp = np.zeros((nq, kk), np.int32)
         sc = np.zeros((nq, kk), np.float32)
@@ -647,6 +644,44 @@ class Index:
         _chk(lib().bbq_search_maxsim_batch(self._h, groups._h if groups is not None else None, nq, _ptr(off), _ptr(qq), _ptr(qc), query_bits, sim, k,
                                           _ptr(grp), _ptr(sc), _ptr(cnt), _ptr(status)))
         return [(grp[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)], status
+
+    def _maxsim_tokens(self, token_lists):
+        """(vec_offsets int64 [nq + 1], qquant uint8 [vectors, dim], qcorr float64 [vectors, 4]) of per-query (qquant, qcorr) pairs"""
+        nq = len(token_lists)
+        off = np.zeros(nq + 1, np.int64)
+        for q, (tq, _) in enumerate(token_lists):
+            off[q + 1] = off[q] + np.asarray(tq).reshape(-1, self.dim).shape[0]
+        qq = np.ascontiguousarray(np.concatenate([np.asarray(t[0], np.uint8).reshape(-1, self.dim) for t in token_lists]) if nq else np.zeros((0, self.dim), np.uint8))
+        qc = np.ascontiguousarray(np.concatenate([np.asarray(t[1], np.float64).reshape(-1, 4) for t in token_lists]) if nq else np.zeros((0, 4), np.float64))
+        if qc.shape[0] != qq.shape[0]:
+            raise BBQError(ERR_INVALID_ARG, "one correction row per token vector")
+        return off, qq, qc
+
+    def score_maxsim_groups_batch(self, token_lists, query_bits, sim, groups, cand_lists):
+        """bbq_score_maxsim_groups_batch: the MaxSim score of every candidate group of every query.  token_lists as search_maxsim_batch
+        takes them; cand_lists: per query an int array of group numbers of `groups`, in any order, duplicates allowed (or (offsets,
+        groups) as score_ords_batch takes its lists).  Returns (scores float32 [total], offsets int64 [nq + 1])."""
+        nq = len(token_lists)
+        off, qq, qc = self._maxsim_tokens(token_lists)
+        coff, cg = _lists(cand_lists, nq)
+        out = np.zeros(cg.shape[0], np.float32)
+        _chk(lib().bbq_score_maxsim_groups_batch(self._h, groups._h if groups is not None else None, nq, _ptr(off), _ptr(qq), _ptr(qc), query_bits, sim,
+                                                _ptr(coff), _ptr(cg), _ptr(out)))
+        return out, coff
+
+    def search_maxsim_groups_batch(self, token_lists, query_bits, sim, k, groups, cand_lists):
+        """bbq_search_maxsim_groups_batch: the k best of every query's own candidate groups by their MaxSim score, visited in the order
+        given.  Arguments as score_maxsim_groups_batch takes them.  Returns a list of (group, score) per query."""
+        nq = len(token_lists)
+        off, qq, qc = self._maxsim_tokens(token_lists)
+        coff, cg = _lists(cand_lists, nq)
+        kk = max(int(k), 0)
+        grp = np.zeros((nq, kk), np.int32)
+        sc = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.int64)
+        _chk(lib().bbq_search_maxsim_groups_batch(self._h, groups._h if groups is not None else None, nq, _ptr(off), _ptr(qq), _ptr(qc), query_bits, sim, k,
+                                                 _ptr(coff), _ptr(cg), _ptr(grp), _ptr(sc), _ptr(cnt)))
+        return [(grp[q, :cnt[q]], sc[q, :cnt[q]]) for q in range(nq)]
 
     def _range_args(self, qquant, qcorr, thresholds):
         qq = np.ascontiguousarray(qquant, np.uint8)

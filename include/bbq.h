@@ -40,7 +40,8 @@ extern "C" {
                               bbq_count_range_batch, bbq_search_range_batch - and the span search - bbq_search_spans_batch,
                               bbq_search_spans_filtered_batch - and the grouped search - bbq_groups_create, bbq_groups_destroy,
                               bbq_groups_count, bbq_groups_live, bbq_groups_plan, bbq_search_grouped_batch - and the MaxSim search -
-                              bbq_search_maxsim_batch, bbq_maxsim_reduce, bbq_maxsim_token_block) */
+                              bbq_search_maxsim_batch, bbq_maxsim_reduce, bbq_maxsim_token_block - and MaxSim over chosen groups -
+                              bbq_score_maxsim_groups_batch, bbq_search_maxsim_groups_batch) */
 
 /* status codes */
 enum {
@@ -542,6 +543,44 @@ int bbq_search_maxsim_batch(bbq_index *idx, const bbq_groups *g, int32_t n_queri
                             int32_t *out_group, float *out_score, int64_t *out_n, uint8_t *out_status);
 int bbq_maxsim_reduce(const float *rep_scores, int64_t n_vectors, int64_t n_groups, float *out);   /* host only */
 int32_t bbq_maxsim_token_block(void);   /* tokens of a block, the same for every index */
+
+/* ------------------------------------------------------------------------------------------
+ * MaxSim over chosen groups (DESIGN.md "MaxSim over chosen groups"): the second stage of late interaction.  A first stage - one of
+ * this library's searches per token, a grouped or a span search, another system - nominates candidate groups per query; these two
+ * calls score and rank exactly those.  Queries, vec_offsets, qquant / qcorr, query_bits, sim and the multi-bit corners are exactly as
+ * bbq_search_maxsim_batch takes them, with the same checks and wording under this function's name.
+ * cand_offsets [n_queries + 1]: cand_offsets[0] == 0, ascending, equal neighbours = an empty list; query q's candidates are the group
+ * numbers cand_groups[cand_offsets[q] .. cand_offsets[q + 1]) of the group set g, in any order; a duplicate is scored and visited once
+ * per occurrence.  A group number outside [0, bbq_groups_count(g)) or a group that is not live - it is empty, or g's filter rejects
+ * every one of its rows - is BBQ_ERR_INVALID_ARG naming the first offending (query, position, group) in call order: every list is
+ * checked on the host, under the context's lock, before the first launch, with nothing launched and nothing written.
+ * bbq_score_maxsim_groups_batch: out_score[i] (indexed like cand_groups) is, bit for bit, the S bbq_search_maxsim_batch defines for
+ * group cand_groups[i] and that query - per token the representative's f32 score by the grouped search's rule over the group's
+ * accepted rows, the f64 adds strictly in ascending token from m_0, one rounding at the end, a NaN m_t makes S NaN; bbq_maxsim_reduce
+ * stays the normative statement of the sum.
+ * bbq_search_maxsim_groups_batch: query q's answer is what the reference loop (src/binaryQuantizationFormat.ts:349-411) returns when
+ * it visits q's candidates IN THE ORDER GIVEN, pushing (group number, S) into a heap of min(k, list length): group numbers, score bits
+ * and order, ties and NaN included, whatever the list's order.  out_group / out_score [n_queries*k] (query q at offset q*k), out_n
+ * [n_queries].  k < 0: BBQ_ERR_NEGATIVE_K; k == 0 or an empty list: out_n[q] = 0; no upper limit on k.  The device delivers the S
+ * values and the host runs the literal heap on replay_threads threads (bbq_set_option), as bbq_search_ords_batch does: there is no
+ * out_status.  n_queries == 0 or cand_offsets[n_queries] == 0: BBQ_OK, nothing launched (the search call still writes out_n).
+ * Handles, lock, stream, bbq_stats and stale group sets as bbq_search_maxsim_batch: a group set made for another size or device is
+ * BBQ_ERR_INVALID_ARG; a multi-device handle, a non-root shard or an index with a pilot replica is BBQ_ERR_UNSUPPORTED; after an
+ * in-place update the set still serves.  What travels to the device is one 8-byte record per candidate, never a row list, and what
+ * comes back is one f32 per candidate.  The rows of one query's candidates, duplicates counted, may number at most 2^31 - 1
+ * (BBQ_ERR_INVALID_ARG).  A long call is worked through in sub-batches of at most 1024 queries and group_scratch_mb (bbq_set_option) of
+ * scratch - 8 bytes per token of a block and 12 per query, per entry of the call's longest list - always at least one query and one
+ * token block; the scratch does not grow with the call.  A failed allocation: BBQ_ERR_OOM, nothing written.  Results are
+ * byte-identical from run to run.
+ * Out of scope: a device-side select over the candidates, returning the per-token best rows, per-token weights, candidates given as
+ * row spans or ord lists instead of groups of a group set, multi-device handles and shards, any pruning. */
+int bbq_score_maxsim_groups_batch(bbq_index *idx, const bbq_groups *g, int32_t n_queries, const int64_t *vec_offsets,
+                                  const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim,
+                                  const int64_t *cand_offsets, const int32_t *cand_groups, float *out_score);
+int bbq_search_maxsim_groups_batch(bbq_index *idx, const bbq_groups *g, int32_t n_queries, const int64_t *vec_offsets,
+                                   const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim, int64_t k,
+                                   const int64_t *cand_offsets, const int32_t *cand_groups,
+                                   int32_t *out_group, float *out_score, int64_t *out_n);
 
 /* ------------------------------------------------------------------------------------------
  * Sharded search (one process per GPU).  bbq_shard_scan sweeps THIS shard for n_queries queries and
