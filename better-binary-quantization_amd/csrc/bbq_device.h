@@ -615,6 +615,47 @@ struct MaxSimCandArgs {
   int32_t pad;
 };
 
+// Exact MaxSim rerank (bbq_maxsim_rerank_kernels.hip): the candidate lists and records of MaxSim over chosen groups, scored against the
+// fp32 rows of a bbq_vectors with computeSimilarity's f64 chain.  A workgroup is one wave: 64 expanded rows of one query, each row loaded
+// once per token block and run against every token of the block.  A query's block takes tp = its token count rounded up to
+// kMaxSimRerankTokenGroup vector SLOTS: MaxSimQuery::vec_first counts slots (a multiple of the group), its token t of the block at column
+// j is tokens[vec_first * dim + j * tp + t] - the host widens the raw f32 to f64, which is exact, lays a column's tokens side by side, so
+// that the tokens of a run of columns are one contiguous, 64-byte aligned piece for the kernel to stage, and pads with 0.0 - and
+// na[vec_first + t] is the token's squared norm, the reference's na chain, which depends on the token alone.  Token t's key goes to
+// rep[vec_first + t][e]; a slot that pads is never written or read.
+constexpr int kMaxSimRerankThreads = 64;    // expanded rows per workgroup
+constexpr int kMaxSimRerankTokenGroup = 8;  // tokens a chain step takes together: a query pays for whole groups
+struct MaxSimRerankArgs {
+  const float *vecs;              // [n_rows][dim] the fp32 rows, row-major
+  const double *tokens;           // the block's token vectors, as above; 16-byte aligned
+  const double *na;               // [the block's slots]; read for COSINE only
+  const uint64_t *accept;         // the accept words of the group set's filter; null: every row
+  const MaxSimQuery *queries;     // [grid.y] the token block of each query that has one; .query indexes cq
+  const MaxSimCandQuery *cq;      // [sub-batch's queries]
+  const MaxSimCand *recs;
+  unsigned long long *rep;        // [the block's slots][stride] cleared to 0 before the launch: only ever raised (true_key)
+  int64_t stride;
+  int32_t dim;
+  int32_t sim;                    // 0 EUCLIDEAN, 1 COSINE, 2 MAXIMUM_INNER_PRODUCT
+};
+// an f64 score's key: larger = the greater score, -0.0 below +0.0; a NaN's is 1, below every number's (-Inf: 0x000fffffffffffff);
+// 0 = nothing seen
+constexpr unsigned long long kTrueNaNBits = 0x7ff8000000000000ull;  // the one NaN the exact MaxSim calls write
+__host__ __device__ inline unsigned long long true_key(unsigned long long bits, bool is_nan) {
+  return is_nan ? 1ull : (bits >> 63) ? ~bits : bits | 0x8000000000000000ull;
+}
+__host__ __device__ inline unsigned long long true_key_bits(unsigned long long k) {
+  return k <= 1ull ? kTrueNaNBits : (k >> 63) ? k ^ 0x8000000000000000ull : ~k;
+}
+// the accumulate pass behind it: acc[query][entry] takes the block's decoded keys in ascending token, from the first token's and not
+// from 0.0; behind a query's last block a NaN sum is replaced by kTrueNaNBits
+struct MaxSimTrueAccArgs {
+  const unsigned long long *rep;  // [the block's slots][stride]
+  const MaxSimQuery *queries;     // [grid.y]
+  double *acc;                    // [sub-batch's queries][stride]: lives across the blocks, the true scores behind the last
+  int64_t stride;
+};
+
 constexpr int kFinalizeThreads = 1024;
 constexpr int kFinalizeJobs = 4096;     // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)
 constexpr int kFinalizeKeyCap = 12288;   // LDS key buffer of the finalize kernel (new keys + running top-k)

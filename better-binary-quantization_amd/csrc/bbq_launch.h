@@ -1,7 +1,7 @@
 // bbq_launch.h - host-callable launch wrappers of every kernel file: the sweeps, finalize and pack (bbq_kernels.hip, bbq_filter_kernels.hip,
 // bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip), the rerank (bbq_rerank_kernels.hip), the scoring of chosen rows (bbq_gather_kernels.hip)
 // the range search (bbq_range_kernels.hip), the span search (bbq_span_kernels.hip), the grouped search (bbq_group_kernels.hip), the MaxSim
-// search (bbq_maxsim_kernels.hip) and MaxSim over chosen groups (bbq_maxsim_cand_kernels.hip)
+// search (bbq_maxsim_kernels.hip), MaxSim over chosen groups (bbq_maxsim_cand_kernels.hip) and the exact MaxSim rerank (bbq_maxsim_rerank_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbq_device.h"
@@ -123,6 +123,12 @@ hipError_t launch_maxsim_score(const MaxSimScoreArgs &a, int planes, hipStream_t
 // entries of a.queries the expanded rows of its candidate list, `longest` (<= kMaxSimCandMaxRows) the most of any of them -> a.rep, which
 // the caller has cleared; planes as launch_scan takes them.  The launch sets a.tok_pass.  launch_maxsim_accumulate follows it
 hipError_t launch_maxsim_cand_score(const MaxSimCandArgs &a, int planes, int n_queries, int64_t longest, hipStream_t s);
+// exact MaxSim rerank (bbq_maxsim_rerank_kernels.hip).  The score pass of one token block: for each of the n_queries (<= 65535) entries
+// of a.queries the expanded rows of its candidate list, `longest` (<= kMaxSimCandMaxRows) the most of any of them, against the block's
+// tokens -> a.rep, which the caller has cleared
+hipError_t launch_maxsim_rerank_score(const MaxSimRerankArgs &a, int n_queries, int64_t longest, hipStream_t s);
+// its accumulate pass for the same entries of a.queries
+hipError_t launch_maxsim_true_accumulate(const MaxSimTrueAccArgs &a, int n_queries, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 // staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place

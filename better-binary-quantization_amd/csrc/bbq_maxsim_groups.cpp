@@ -53,22 +53,8 @@ int score_locked(const char *fn, bbq_index *ix, const bbq_groups *gs, int32_t n_
                 (long long)gs->n_rows, gs->device, (long long)ix->main.view.n_rows, ix->device);
   // every list, in call order, before anything is launched or written
   int64_t longest_list = 0;
-  for (int32_t q = 0; q < n_queries; ++q) {
-    int64_t rows = 0;
-    for (int64_t i = coff[q]; i < coff[q + 1]; ++i) {
-      const int32_t g = cand[i];
-      if (g < 0 || g >= gs->n_groups)
-        return fail(BBQ_ERR_INVALID_ARG, "%s: query %d, position %lld: group %d is not a group of the set (%lld groups)", fn, q, (long long)(i - coff[q]), g,
-                    (long long)gs->n_groups);
-      if (gs->slot[(size_t)g] < 0)
-        return fail(BBQ_ERR_INVALID_ARG, "%s: query %d, position %lld: group %d is not live (it is empty or its rows are all filtered out)", fn, q,
-                    (long long)(i - coff[q]), g);
-      rows += gs->offsets[(size_t)g + 1] - gs->offsets[(size_t)g];
-    }
-    if (rows > kMaxSimCandMaxRows)
-      return fail(BBQ_ERR_INVALID_ARG, "%s: query %d: its candidates hold %lld rows, more than %lld", fn, q, (long long)rows, (long long)kMaxSimCandMaxRows);
-    longest_list = std::max(longest_list, coff[q + 1] - coff[q]);
-  }
+  const int rc = check_maxsim_cand_lists(fn, gs, n_queries, coff, cand, &longest_list);
+  if (rc != BBQ_OK) return rc;
   if (!out) return BBQ_OK;
 
   constexpr int TB = kMaxSimTokenBlock;
@@ -122,21 +108,7 @@ int score_locked(const char *fn, bbq_index *ix, const bbq_groups *gs, int32_t n_
     // the lists, once per sub-batch: a record per candidate and a terminator per query
     MaxSimCandQuery *h_cq = reinterpret_cast<MaxSimCandQuery *>(head.get() + lo.cq);
     MaxSimCand *h_rec = reinterpret_cast<MaxSimCand *>(head.get() + lo.recs);
-    int64_t at = 0;
-    for (int s = 0; s < nq; ++s) {
-      const int64_t beg = coff[q0 + s], n = coff[q0 + s + 1] - beg;
-      int64_t pos = 0;
-      h_cq[s].rec_first = at;
-      for (int64_t i = 0; i < n; ++i) {
-        const size_t g = (size_t)cand[beg + i];
-        h_rec[at++] = MaxSimCand{(uint32_t)gs->offsets[g], (uint32_t)pos};
-        pos += gs->offsets[g + 1] - gs->offsets[g];
-      }
-      h_rec[at++] = MaxSimCand{0u, (uint32_t)pos};
-      h_cq[s].n_cand = (int32_t)n;
-      h_cq[s].total = (int32_t)pos;
-      longest_rows = std::max(longest_rows, pos);
-    }
+    longest_rows = stage_maxsim_cand_records(gs, nq, coff + q0, cand, h_cq, h_rec);
     float *d_scores = reinterpret_cast<float *>(d + lo.scores);
 
     for (int64_t t0 = 0; t0 < longest_tok; t0 += TB) {  // the token block [t0, t0 + TB) of every query that has one and a candidate
@@ -190,15 +162,8 @@ int check_call(const char *fn, bbq_index *ix, const bbq_groups *g, int32_t n_que
   *total = 0;
   if (!ix) return fail(BBQ_ERR_INVALID_ARG, "目标向量集合不能为空");
   if (n_queries < 0) return fail(BBQ_ERR_INVALID_ARG, "n_queries < 0");
-  if (n_queries > 0) {
-    if (!vec_offsets) return fail(BBQ_ERR_INVALID_ARG, "%s: vec_offsets is null", fn);
-    if (vec_offsets[0] != 0) return fail(BBQ_ERR_INVALID_ARG, "%s: vec_offsets[0] must be 0 (query 0)", fn);
-    for (int32_t q = 0; q < n_queries; ++q)
-      if (vec_offsets[q + 1] <= vec_offsets[q])
-        return fail(BBQ_ERR_INVALID_ARG, "%s: query %d has no token vector or vec_offsets descends: [%lld, %lld)", fn, q, (long long)vec_offsets[q],
-                    (long long)vec_offsets[q + 1]);
-    if (vec_offsets[n_queries] > 0x7fffffffll) return fail(BBQ_ERR_INVALID_ARG, "%s: more than 2^31 - 1 token vectors", fn);
-  }
+  const int rcv = check_maxsim_vec_offsets(fn, n_queries, vec_offsets);
+  if (rcv != BBQ_OK) return rcv;
   const int32_t n_vectors = n_queries > 0 ? (int32_t)vec_offsets[n_queries] : 0;
   const int rc = validate_query_args(ix, n_vectors, qquant, qcorr, query_bits, sim, k);
   if (rc != BBQ_OK) return rc;
@@ -209,16 +174,78 @@ int check_call(const char *fn, bbq_index *ix, const bbq_groups *g, int32_t n_que
     *done = true;
     return BBQ_OK;
   }
-  if (!cand_offsets) return fail(BBQ_ERR_INVALID_ARG, "%s: cand_offsets is null", fn);
-  if (cand_offsets[0] != 0) return fail(BBQ_ERR_INVALID_ARG, "%s: cand_offsets[0] must be 0 (query 0)", fn);
-  for (int32_t q = 0; q < n_queries; ++q)
-    if (cand_offsets[q + 1] < cand_offsets[q])
-      return fail(BBQ_ERR_INVALID_ARG, "%s: cand_offsets descends at query %d: [%lld, %lld)", fn, q, (long long)cand_offsets[q], (long long)cand_offsets[q + 1]);
+  const int rc3 = check_maxsim_cand_offsets(fn, n_queries, cand_offsets);
+  if (rc3 != BBQ_OK) return rc3;
   *total = cand_offsets[n_queries];
   return BBQ_OK;
 }
 
 }  // namespace
+
+// ---- what the exact MaxSim rerank (bbq_maxsim_rerank.cpp) shares with the calls of this file
+
+int bbq::check_maxsim_vec_offsets(const char *fn, int32_t n_queries, const int64_t *vec_offsets) {
+  if (n_queries > 0) {
+    if (!vec_offsets) return fail(BBQ_ERR_INVALID_ARG, "%s: vec_offsets is null", fn);
+    if (vec_offsets[0] != 0) return fail(BBQ_ERR_INVALID_ARG, "%s: vec_offsets[0] must be 0 (query 0)", fn);
+    for (int32_t q = 0; q < n_queries; ++q)
+      if (vec_offsets[q + 1] <= vec_offsets[q])
+        return fail(BBQ_ERR_INVALID_ARG, "%s: query %d has no token vector or vec_offsets descends: [%lld, %lld)", fn, q, (long long)vec_offsets[q],
+                    (long long)vec_offsets[q + 1]);
+    if (vec_offsets[n_queries] > 0x7fffffffll) return fail(BBQ_ERR_INVALID_ARG, "%s: more than 2^31 - 1 token vectors", fn);
+  }
+  return BBQ_OK;
+}
+
+int bbq::check_maxsim_cand_offsets(const char *fn, int32_t n_queries, const int64_t *cand_offsets) {
+  if (!cand_offsets) return fail(BBQ_ERR_INVALID_ARG, "%s: cand_offsets is null", fn);
+  if (cand_offsets[0] != 0) return fail(BBQ_ERR_INVALID_ARG, "%s: cand_offsets[0] must be 0 (query 0)", fn);
+  for (int32_t q = 0; q < n_queries; ++q)
+    if (cand_offsets[q + 1] < cand_offsets[q])
+      return fail(BBQ_ERR_INVALID_ARG, "%s: cand_offsets descends at query %d: [%lld, %lld)", fn, q, (long long)cand_offsets[q], (long long)cand_offsets[q + 1]);
+  return BBQ_OK;
+}
+
+int bbq::check_maxsim_cand_lists(const char *fn, const bbq_groups *gs, int32_t n_queries, const int64_t *coff, const int32_t *cand, int64_t *longest) {
+  int64_t longest_list = 0;
+  for (int32_t q = 0; q < n_queries; ++q) {
+    int64_t rows = 0;
+    for (int64_t i = coff[q]; i < coff[q + 1]; ++i) {
+      const int32_t g = cand[i];
+      if (g < 0 || g >= gs->n_groups)
+        return fail(BBQ_ERR_INVALID_ARG, "%s: query %d, position %lld: group %d is not a group of the set (%lld groups)", fn, q, (long long)(i - coff[q]), g,
+                    (long long)gs->n_groups);
+      if (gs->slot[(size_t)g] < 0)
+        return fail(BBQ_ERR_INVALID_ARG, "%s: query %d, position %lld: group %d is not live (it is empty or its rows are all filtered out)", fn, q,
+                    (long long)(i - coff[q]), g);
+      rows += gs->offsets[(size_t)g + 1] - gs->offsets[(size_t)g];
+    }
+    if (rows > kMaxSimCandMaxRows)
+      return fail(BBQ_ERR_INVALID_ARG, "%s: query %d: its candidates hold %lld rows, more than %lld", fn, q, (long long)rows, (long long)kMaxSimCandMaxRows);
+    longest_list = std::max(longest_list, coff[q + 1] - coff[q]);
+  }
+  *longest = longest_list;
+  return BBQ_OK;
+}
+
+int64_t bbq::stage_maxsim_cand_records(const bbq_groups *gs, int nq, const int64_t *coff, const int32_t *cand, MaxSimCandQuery *h_cq, MaxSimCand *h_rec) {
+  int64_t longest_rows = 0, at = 0;
+  for (int s = 0; s < nq; ++s) {
+    const int64_t beg = coff[s], n = coff[s + 1] - beg;
+    int64_t pos = 0;
+    h_cq[s].rec_first = at;
+    for (int64_t i = 0; i < n; ++i) {
+      const size_t g = (size_t)cand[beg + i];
+      h_rec[at++] = MaxSimCand{(uint32_t)gs->offsets[g], (uint32_t)pos};
+      pos += gs->offsets[g + 1] - gs->offsets[g];
+    }
+    h_rec[at++] = MaxSimCand{0u, (uint32_t)pos};
+    h_cq[s].n_cand = (int32_t)n;
+    h_cq[s].total = (int32_t)pos;
+    longest_rows = std::max(longest_rows, pos);
+  }
+  return longest_rows;
+}
 
 extern "C" {
 

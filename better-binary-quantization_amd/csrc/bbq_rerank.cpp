@@ -10,19 +10,6 @@
 
 using namespace bbq;
 
-struct bbq_vectors {
-  int device = 0;
-  DeviceCtx *ctx = nullptr;
-  DevBuf<float> d;      // [cap][dim], the first n rows in use (bbq_vectors_append grows it like the index grows)
-  int64_t n = 0;
-  int32_t dim = 0;
-  // grow-only staging for bbq_rerank_scores
-  DevBuf<float> d_q;
-  DevBuf<int64_t> d_off;
-  DevBuf<int32_t> d_rows;
-  DevBuf<double> d_out;
-};
-
 namespace {
 
 // staging that a larger call outgrows is replaced with half as much again
@@ -30,8 +17,6 @@ template <class T>
 hipError_t grow_staging(DevBuf<T> &b, int64_t need) {
   return (int64_t)b.size() >= need ? hipSuccess : b.alloc((size_t)(need + need / 2 + 64));
 }
-
-struct Ranked { double score; int32_t pos; };
 
 // Array.prototype.sort((a, b) => b.trueScore - a.trueScore), src/topKSelector.ts:75,112: stable; an element of the right
 // run overtakes one of the left run only when the comparator says so (> 0), whatever it says for NaN
@@ -75,6 +60,25 @@ int append_vectors(bbq_vectors *v, const float *vectors, int64_t n, const char *
 }
 
 }  // namespace
+
+// the reference's two selectors over the true scores t[0 .. cnt) of one query -> r, best first: 0 the heap of k, drained and stably
+// sorted (src/topKSelector.ts:40-76), 1 the stable descending sort, first k (:102-114)
+void bbq::rerank_select(int32_t selector, int64_t k, const double *t, int64_t cnt, std::vector<Ranked> &r) {
+  r.clear();
+  if (selector == 0) {
+    std::vector<int32_t> tag((size_t)k + 1);
+    std::vector<double> tsc((size_t)k + 1);
+    HeapReplay h(k, INT64_MAX);
+    for (int64_t i = 0; i < cnt; ++i) h.offer64(t[i], (int32_t)i);
+    const int64_t m = h.drain_ascending(tag.data(), tsc.data());
+    for (int64_t j = 0; j < m; ++j) r.push_back(Ranked{tsc[j], tag[j]});
+    sort_desc_stable(r);
+  } else {
+    for (int64_t i = 0; i < cnt; ++i) r.push_back(Ranked{t[i], (int32_t)i});
+    sort_desc_stable(r);
+    if ((int64_t)r.size() > k) r.resize((size_t)k);
+  }
+}
 
 extern "C" {
 
@@ -258,23 +262,8 @@ int bbq_search_rerank_batch(bbq_index *ix, bbq_vectors *v, int32_t n_queries, co
   rc = bbq_rerank_scores(v, n_queries, queries, off.data(), rows.data(), true_sim, ts.data());
   if (rc != BBQ_OK) return rc;
   std::vector<Ranked> r;
-  std::vector<int32_t> tag((size_t)k + 1);
-  std::vector<double> tsc((size_t)k + 1);
   for (int32_t q = 0; q < n_queries; ++q) {
-    const int64_t cnt = cn[q];
-    const double *t = ts.data() + off[q];
-    r.clear();
-    if (selector == 0) {  // src/topKSelector.ts:40-76
-      HeapReplay h(k, INT64_MAX);
-      for (int64_t i = 0; i < cnt; ++i) h.offer64(t[i], (int32_t)i);
-      const int64_t m = h.drain_ascending(tag.data(), tsc.data());
-      for (int64_t j = 0; j < m; ++j) r.push_back(Ranked{tsc[j], tag[j]});
-      sort_desc_stable(r);
-    } else {  // :102-114
-      for (int64_t i = 0; i < cnt; ++i) r.push_back(Ranked{t[i], (int32_t)i});
-      sort_desc_stable(r);
-      if ((int64_t)r.size() > k) r.resize((size_t)k);
-    }
+    rerank_select(selector, k, ts.data() + off[q], cn[q], r);
     for (size_t j = 0; j < r.size(); ++j) {
       out_idx[(int64_t)q * k + j] = cidx[(int64_t)q * kk + r[j].pos];
       out_quantized[(int64_t)q * k + j] = csc[(int64_t)q * kk + r[j].pos];

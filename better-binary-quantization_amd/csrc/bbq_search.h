@@ -32,6 +32,20 @@ struct bbq_groups {
   int64_t n_nonempty = 0;
 };
 
+// The original fp32 rows resident on one GPU (bbq_rerank.cpp): what the exact rerank calls score against.
+struct bbq_vectors {
+  int device = 0;
+  bbq::DeviceCtx *ctx = nullptr;
+  bbq::DevBuf<float> d;      // [cap][dim], the first n rows in use (bbq_vectors_append grows it like the index grows)
+  int64_t n = 0;
+  int32_t dim = 0;
+  // grow-only staging for bbq_rerank_scores
+  bbq::DevBuf<float> d_q;
+  bbq::DevBuf<int64_t> d_off;
+  bbq::DevBuf<int32_t> d_rows;
+  bbq::DevBuf<double> d_out;
+};
+
 #pragma GCC visibility push(hidden)  // internal: none of this joins the library's dynamic symbols
 namespace bbq {
 
@@ -116,6 +130,21 @@ int update_winners(const int32_t *ords, int64_t n, int64_t n_rows, std::vector<i
 int stage_winners(hipStream_t s, const int32_t *ords, int64_t n, const std::vector<int64_t> &pos, DevBuf<int32_t> &d_ords, DevBuf<int64_t> &d_pos);
 // ---- bbq_group.cpp: what a group set can be made for, and searched on - a single-device root index
 int check_group_index(const bbq_index *ix);
+// ---- bbq_maxsim_groups.cpp: the checks of a MaxSim call's token offsets and candidate lists, in the wording of `fn`, and the records
+// of a sub-batch's lists.  check_maxsim_cand_lists: every group of every list is a live group of gs, the first offender named, at most
+// kMaxSimCandMaxRows expanded rows a query; *longest = the longest list.  stage_maxsim_cand_records: coff = the sub-batch's first query's
+// entry of the call's offsets; one record per candidate and a terminator per query -> h_rec, the queries -> h_cq; returns the most
+// expanded rows of any query
+int check_maxsim_vec_offsets(const char *fn, int32_t n_queries, const int64_t *vec_offsets);
+int check_maxsim_cand_offsets(const char *fn, int32_t n_queries, const int64_t *cand_offsets);
+int check_maxsim_cand_lists(const char *fn, const bbq_groups *gs, int32_t n_queries, const int64_t *coff, const int32_t *cand, int64_t *longest);
+int64_t stage_maxsim_cand_records(const bbq_groups *gs, int nq, const int64_t *coff, const int32_t *cand, MaxSimCandQuery *h_cq, MaxSimCand *h_rec);
+// ---- bbq_rerank.cpp: a candidate's true score and its position in the candidate list; the two selectors of the rerank recipes
+struct Ranked { double score; int32_t pos; };
+void rerank_select(int32_t selector, int64_t k, const double *t, int64_t cnt, std::vector<Ranked> &r);
+// ---- bbq_maxsim_rerank.cpp: bbq_rerank_maxsim_groups_batch behind its argument checks, under a scratch budget of scratch_mb MiB
+int rerank_maxsim_groups(const char *fn, bbq_vectors *v, const bbq_groups *gs, int32_t n_queries, const int64_t *voff, const float *queries, int32_t true_sim,
+                         const int64_t *coff, const int32_t *cand, double *out, int scratch_mb);
 // ---- bbq_dense.cpp
 int dense_search_one(const SearchCall &c, int64_t qi, int32_t *out_idx, float *out_score, int64_t *out_n);
 

@@ -158,6 +158,10 @@ export declare function getOversampledTopKWithHeap(query: Float32Array, quantize
 export declare function getOversampledTopKWithSort(query: Float32Array, quantizedVectors: any, vectors: Float32Array[] | DeviceVectors, k: number, oversampleFactor: number, format: BinaryQuantizationFormat): TopKCandidate[];
 /** extension: the whole recipe for many queries in one native call */
 export declare function getOversampledTopKBatch(queries: Float32Array[], quantizedVectors: any, vectors: DeviceVectors, k: number, oversampleFactor: number, format: BinaryQuantizationFormat, selector?: 'heap' | 'sort'): TopKCandidate[][];
+/** extension: the exact MaxSim score of every candidate group, in list order - per token the greatest computeSimilarity among the group's accepted fp32 rows, summed in f64 in token order (bbq_rerank_maxsim_groups_batch) */
+export declare function computeMaxSimGroupTrueScores(queryVectors: Float32Array[], vectors: DeviceVectors, rowGroups: RowGroups, groupNumbers: Int32Array | number[], similarity?: VectorSimilarityFunction): Float64Array;
+/** extension: searchNearestNeighborsMaxSim with k * oversampleFactor, exact MaxSim scores of the returned groups, then the heap or the sort selector over them (bbq_search_maxsim_rerank_batch) */
+export declare function getOversampledMaxSimTopK(queryVectors: Float32Array[], targetVectors: BinarizedByteVectorValues, vectors: DeviceVectors, rowGroups: RowGroups, k: number, oversampleFactor: number, format: BinaryQuantizationFormat, selector?: 'heap' | 'sort'): Array<{ group: number; quantizedScore: number; trueScore: number }>;
 export declare const DEFAULT_CONFIG: { readonly queryBits: 4; readonly indexBits: 1; readonly quantizer: { readonly similarityFunction: VectorSimilarityFunction.COSINE; readonly lambda: 0.1; readonly iters: 5 } };
 export declare function createBinaryQuantizationFormat(config?: BinaryQuantizationConfig): BinaryQuantizationFormat;
 export declare function quickQuantize(vectors: Float32Array[], similarityFunction?: VectorSimilarityFunction): { quantizedVectors: BinarizedByteVectorValues; queryQuantizer: OptimizedScalarQuantizer };

@@ -1270,6 +1270,51 @@ function getOversampledTopKBatch(queries, quantizedVectors, deviceVectors, k, ov
   return out;
 }
 
+/**
+ * extension (not in the reference): the exact MaxSim score of every candidate group, in list order, as a Float64Array (libbbq
+ * bbq_rerank_maxsim_groups_batch).  queryVectors: the query's RAW token vectors; vectors: createDeviceVectors(original rows); rowGroups:
+ * createRowGroups over the same rows; a group scores the f64 sum over the tokens, in their order, of the greatest
+ * computeSimilarity(token, row) among its accepted rows.  similarity: a VectorSimilarityFunction, default COSINE.
+ */
+function computeMaxSimGroupTrueScores(queryVectors, vectors, rowGroups, groupNumbers, similarity) {
+  if (!queryVectors || queryVectors.length === 0) throw new Error('查询向量不能为空');
+  if (!(vectors instanceof DeviceVectors)) throw new Error('computeMaxSimGroupTrueScores needs createDeviceVectors(vectors)');
+  if (!(rowGroups instanceof RowGroups)) throw new Error('computeMaxSimGroupTrueScores needs createRowGroups(targetVectors, offsets)');
+  if (!groupNumbers) throw new Error('候选分组不能为空');
+  const sim = similarity === undefined ? 1 : simOrdinal(similarity);
+  for (let i = 0; i < queryVectors.length; i++) if (!queryVectors[i] || queryVectors[i].length !== vectors.dim) throw new Error('向量维度不匹配');
+  const cand = groupNumbers instanceof Int32Array ? groupNumbers : Int32Array.from(groupNumbers, (g) => {
+    if (!Number.isInteger(g) || g < -2147483648 || g > 2147483647) throw new Error('候选分组必须是整数: ' + g);
+    return g;
+  });
+  return native.rerankMaxSimGroups(vectors._handle(), rowGroups._handle(), flatten(queryVectors, vectors.dim), sim, cand);
+}
+
+/**
+ * extension (not in the reference): the late-interaction recall recipe for one query in one native call (libbbq
+ * bbq_search_maxsim_rerank_batch): searchNearestNeighborsMaxSim with k * oversampleFactor, the exact MaxSim scores of the returned
+ * groups on `vectors` (COSINE, as the reference's selectors), then the selector ('heap' | 'sort') of getOversampledTopKWith{Heap,Sort}
+ * over the true scores.  Returns [{group, quantizedScore, trueScore}].
+ */
+function getOversampledMaxSimTopK(queryVectors, targetVectors, vectors, rowGroups, k, oversampleFactor, format, selector) {
+  if (!queryVectors || queryVectors.length === 0) throw new Error('查询向量不能为空');
+  if (!targetVectors) throw new Error('目标向量集合不能为空');
+  if (!(vectors instanceof DeviceVectors)) throw new Error('getOversampledMaxSimTopK needs createDeviceVectors(vectors)');
+  if (!(rowGroups instanceof RowGroups)) throw new Error('getOversampledMaxSimTopK needs createRowGroups(targetVectors, offsets)');
+  if (k < 0) throw new Error('k值不能为负数');
+  if (k === 0) return [];
+  const dim = targetVectors.dimension();
+  for (let i = 0; i < queryVectors.length; i++) if (!queryVectors[i] || queryVectors[i].length !== dim) throw new Error('查询向量维度与目标向量维度不匹配');
+  const q = format.getQuantizer(), sim = simOrdinal(q.similarityFunction), qb = format.getConfig().queryBits;
+  const flat = flatten(queryVectors, dim);
+  const qz = native.quantizeQueries(flat, queryVectors.length, targetVectors.getCentroid(), sim, qb, q.lambda, q.iters, 1);
+  const r = native.searchMaxSimRerank(targetVectors._deviceIndex(), vectors._handle(), rowGroups._handle(), flat, qz.quantized, qz.corrections, qb, sim, k,
+    oversampleFactor, selector === 'sort' ? 1 : 0, 1);
+  const n = r.groups.length, res = new Array(n);
+  for (let j = 0; j < n; j++) res[j] = { group: r.groups[j], quantizedScore: r.quantized[j], trueScore: r.trueScores[j] };
+  return res;
+}
+
 // ------------------------------------------------------------------ .fvecs / .ivecs (tests/benchmarks/siftDataLoader.ts:27-127)
 
 /** loadSiftVectors(filePath, maxVectors = 10000) -> {vectors: [{dimension, values}], count, dimension}; little-endian records */
@@ -1345,7 +1390,7 @@ module.exports = Object.assign({}, require('./helpers'), {
   QUERY_BITS, INDEX_BITS, FOUR_BIT_SCALE, DEFAULT_LAMBDA, DEFAULT_ITERS,
   BinaryQuantizationFormat, OptimizedScalarQuantizer, BinaryQuantizedScorer, MinHeap,
   createBinaryQuantizationFormat, quickQuantize, quickSearch,
-  getOversampledTopKWithHeap, getOversampledTopKWithSort, getOversampledTopKBatch, computeCosineSimilarity,
+  getOversampledTopKWithHeap, getOversampledTopKWithSort, getOversampledTopKBatch, computeMaxSimGroupTrueScores, getOversampledMaxSimTopK, computeCosineSimilarity,
   DeviceVectors, createDeviceVectors, RowFilter, createRowFilter, RowGroups, createRowGroups, loadSiftVectors, loadSiftDataset, loadSiftQueries,
   normalizeVector, computeCentroid, computeDotProduct, computeEuclideanDistance, computeEuclideanSimilarity, computeMaximumInnerProduct,
   computeSimilarity, computeQuantizedDotProduct, computeInt4BitDotProduct: computeQuantizedDotProduct, computeInt1BitDotProduct: computeQuantizedDotProduct,

@@ -1213,6 +1213,85 @@ static napi_value SearchRerankBatch(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* the group set of the exact MaxSim rerank calls */
+static const bbq_groups *unbox_groups(napi_env env, napi_value v, const char *fn) {
+  void *gp = NULL;
+  if (napi_get_value_external(env, v, &gp) != napi_ok || !gp || !*(bbq_groups **)gp) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s: the group set is null", fn);
+    napi_throw_error(env, "BBQ1", msg);
+    return NULL;
+  }
+  return *(bbq_groups **)gp;
+}
+
+/* rerankMaxSimGroups(vectors, groups handle, tokens Float32Array[T * dim], trueSim, candidates Int32Array) -> Float64Array: the exact MaxSim
+ * score of every candidate group, in list order, for ONE query of T >= 1 raw token vectors (bbq_rerank_maxsim_groups_batch with one query) */
+static napi_value RerankMaxSimGroups(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!get_args(env, info, 5, a)) return NULL;
+  bbq_vectors *v = unbox_vectors(env, a[0]);
+  if (!v) return NULL;
+  const bbq_groups *grp = unbox_groups(env, a[1], "bbq_rerank_maxsim_groups_batch");
+  if (!grp) return NULL;
+  void *q, *cg; size_t ql, nc;
+  int64_t sim;
+  if (!get_typed(env, a[2], napi_float32_array, &q, &ql) || !get_i64(env, a[3], &sim) || !get_typed(env, a[4], napi_int32_array, &cg, &nc)) return NULL;
+  const size_t dim = (size_t)bbq_vectors_dimension(v);
+  if (dim == 0 || ql == 0 || ql % dim != 0) { napi_throw_error(env, "BBQ6", "向量维度不匹配"); return NULL; }
+  const int64_t voff[2] = {0, (int64_t)(ql / dim)}, coff[2] = {0, (int64_t)nc};
+  void *out;
+  napi_value t = new_typed(env, napi_float64_array, nc, 8, &out);
+  if (!t) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_rerank_maxsim_groups_batch(v, grp, 1, voff, (const float *)q, (int32_t)sim, coff, (const int32_t *)cg, (double *)out);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  return t;
+}
+
+/* searchMaxSimRerank(index, vectors, groups handle, tokens Float32Array[T * dim], qquant Uint8Array[T * dim], qcorr Float64Array[T * 4], queryBits,
+ * sim, k, factor, selector, trueSim) -> {groups Int32Array, quantized Float32Array, trueScores Float64Array}: the whole recipe for ONE query
+ * (bbq_search_maxsim_rerank_batch with one query) */
+static napi_value SearchMaxSimRerank(napi_env env, napi_callback_info info) {
+  napi_value a[12];
+  if (!get_args(env, info, 12, a)) return NULL;
+  bbq_index *ix = unbox(env, a[0]);
+  if (!ix) return NULL;
+  bbq_vectors *v = unbox_vectors(env, a[1]);
+  if (!v) return NULL;
+  const bbq_groups *grp = unbox_groups(env, a[2], "bbq_search_maxsim_rerank_batch");
+  if (!grp) return NULL;
+  void *q, *qq, *qc; size_t fl, ql, cl;
+  int64_t qb, sim, k, factor, selector, tsim;
+  if (!get_typed(env, a[3], napi_float32_array, &q, &fl) || !get_typed(env, a[4], napi_uint8_array, &qq, &ql) ||
+      !get_typed(env, a[5], napi_float64_array, &qc, &cl) || !get_i64(env, a[6], &qb) || !get_i64(env, a[7], &sim) || !get_i64(env, a[8], &k) ||
+      !get_i64(env, a[9], &factor) || !get_i64(env, a[10], &selector) || !get_i64(env, a[11], &tsim)) return NULL;
+  const size_t dim = (size_t)bbq_index_dimension(ix);
+  if (dim == 0 || ql == 0 || ql % dim != 0 || fl != ql || cl != ql / dim * 4) { napi_throw_error(env, "BBQ6", "查询向量维度与目标向量维度不匹配"); return NULL; }
+  if (k < 0) { napi_throw_error(env, "BBQ7", "k值不能为负数"); return NULL; }
+  const int64_t live = bbq_groups_live(grp);
+  const int64_t keff = k < live ? k : live;   /* no answer is longer than the live groups */
+  const int64_t voff[2] = {0, (int64_t)(ql / dim)};
+  int32_t *og = (int32_t *)malloc(((size_t)keff + 1) * sizeof(int32_t));
+  float *sq = (float *)malloc(((size_t)keff + 1) * sizeof(float));
+  double *st = (double *)malloc(((size_t)keff + 1) * sizeof(double));
+  if (!og || !sq || !st) { free(og); free(sq); free(st); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int64_t cnt = 0;
+  int rc = bbq_search_maxsim_rerank_batch(ix, v, grp, 1, voff, (const float *)q, (const uint8_t *)qq, (const double *)qc, (int32_t)qb, (int32_t)sim, keff,
+                                          (int32_t)factor, (int32_t)selector, (int32_t)tsim, og, sq, st, &cnt);
+  if (rc != BBQ_OK) { free(og); free(sq); free(st); return throw_bbq(env, rc); }
+  void *pg, *pq, *pt;
+  napi_value tg = new_typed(env, napi_int32_array, (size_t)cnt, 4, &pg);
+  napi_value tq = new_typed(env, napi_float32_array, (size_t)cnt, 4, &pq);
+  napi_value tt = new_typed(env, napi_float64_array, (size_t)cnt, 8, &pt);
+  if (!tg || !tq || !tt) { free(og); free(sq); free(st); napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  if (cnt > 0) { memcpy(pg, og, (size_t)cnt * 4); memcpy(pq, sq, (size_t)cnt * 4); memcpy(pt, st, (size_t)cnt * 8); }
+  free(og); free(sq); free(st);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "groups", tg); set_prop(env, o, "quantized", tq); set_prop(env, o, "trueScores", tt);
+  return o;
+}
+
 /* ---- on-disk format (bbq_index_save / bbq_index_load / bbq_index_export) */
 static int get_path(napi_env env, napi_value v, char *buf, size_t cap) {
   size_t len = 0;
@@ -1365,6 +1444,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"vectorsDestroy", NULL, VectorsDestroy, NULL, NULL, NULL, napi_default, NULL},
       {"rerankScores", NULL, RerankScores, NULL, NULL, NULL, napi_default, NULL},
       {"searchRerankBatch", NULL, SearchRerankBatch, NULL, NULL, NULL, napi_default, NULL},
+      {"rerankMaxSimGroups", NULL, RerankMaxSimGroups, NULL, NULL, NULL, napi_default, NULL},
+      {"searchMaxSimRerank", NULL, SearchMaxSimRerank, NULL, NULL, NULL, napi_default, NULL},
       {"indexSave", NULL, IndexSave, NULL, NULL, NULL, napi_default, NULL},
       {"indexLoad", NULL, IndexLoad, NULL, NULL, NULL, napi_default, NULL},
       {"indexExport", NULL, IndexExport, NULL, NULL, NULL, napi_default, NULL},

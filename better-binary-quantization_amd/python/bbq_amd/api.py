@@ -342,6 +342,42 @@ class BinaryQuantizationFormat:
             raise Exception(str(e))
         return [{"group": int(g), "score": float(s)} for g, s in zip(grp, sc)]
 
+    def searchNearestNeighborsMaxSimReranked(self, queryVectors, targetVectors, vectors, rowGroups, k, oversampleFactor, selector="heap"):
+        """extension: the late-interaction recall recipe - searchNearestNeighborsMaxSim with k * oversampleFactor, the exact MaxSim
+        scores of the returned groups on `vectors` (createDeviceVectors over the original rows; COSINE, as the reference's selectors),
+        then the 'heap' or the 'sort' selector of getOversampledTopKWith{Heap,Sort} over the true scores.  Returns [{group,
+        quantizedScore, trueScore}]."""
+        if queryVectors is None or len(queryVectors) == 0:
+            raise Exception("查询向量不能为空")
+        if targetVectors is None:
+            raise Exception("目标向量集合不能为空")
+        if not isinstance(vectors, capi.Vectors):
+            raise Exception("searchNearestNeighborsMaxSimReranked needs createDeviceVectors(vectors)")
+        if rowGroups is None:
+            raise Exception("行分组不能为空")
+        if k < 0:
+            raise Exception("k值不能为负数")
+        for v in queryVectors:
+            if v is None:
+                raise Exception("查询向量不能为空")
+            if len(v) != targetVectors.dimension():
+                raise Exception("查询向量维度与目标向量维度不匹配")
+        if k == 0:
+            return []
+        sim = capi.SIMS[self._sim]
+        if targetVectors._index_bits != 1 and targetVectors.dimension() > 1 and self._config["queryBits"] not in (1, 4):
+            raise Exception("不支持的查询位数: %d，只支持1位和4位" % self._config["queryBits"])  # as _search refuses it
+        try:
+            pairs = [capi.quantize_query(v, targetVectors.getCentroid(), sim, self._config["queryBits"], self._lambda, self._iters, search_path=True)
+                     for v in queryVectors]
+            tokens = (np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs]))
+            raw = np.stack([np.asarray(v, np.float32) for v in queryVectors])
+            grp, qs, ts = capi.search_maxsim_rerank_batch(targetVectors._device(), vectors, rowGroups, [raw], [tokens], self._config["queryBits"], sim, k,
+                                                          oversampleFactor, 1 if selector == "sort" else 0, 1)[0]
+        except capi.BBQError as e:
+            raise Exception(str(e))
+        return [{"group": int(g), "quantizedScore": float(q), "trueScore": float(t)} for g, q, t in zip(grp, qs, ts)]
+
     def searchRange(self, queryVector, targetVectors, threshold, rowFilter=None, order="ord"):
         """extension: every row (of `rowFilter`, createRowFilter, if given) whose stored f32 score is >= threshold - what the
         reference's loop would collect if it kept every visited ord at or above the threshold and skipped the heap - as

@@ -36,6 +36,7 @@ SYMBOLS = [
     "bbq_groups_create", "bbq_groups_destroy", "bbq_groups_count", "bbq_groups_live", "bbq_groups_plan", "bbq_search_grouped_batch",
     "bbq_search_maxsim_batch", "bbq_maxsim_reduce", "bbq_maxsim_token_block",
     "bbq_score_maxsim_groups_batch", "bbq_search_maxsim_groups_batch",
+    "bbq_maxsim_reduce_true", "bbq_rerank_maxsim_groups_batch", "bbq_search_maxsim_rerank_batch",
 ]
 
 
@@ -129,6 +130,9 @@ def lib():
     L.bbq_maxsim_reduce.argtypes = [vp, i64, i64, vp]
     L.bbq_score_maxsim_groups_batch.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp]
     L.bbq_search_maxsim_groups_batch.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
+    L.bbq_maxsim_reduce_true.argtypes = [vp, i64, i64, vp]
+    L.bbq_rerank_maxsim_groups_batch.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    L.bbq_search_maxsim_rerank_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp]
     L.bbq_maxsim_token_block.argtypes = []
     L.bbq_maxsim_token_block.restype = i32
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
@@ -919,6 +923,25 @@ def maxsim_reduce(rep_scores):
     return out
 
 
+def maxsim_reduce_true(rep_true):
+    """bbq_maxsim_reduce_true (host only): rep_true float64 [n_vectors, n_groups], every token vector's greatest true score of every
+    group -> float64 [n_groups], each group's ordered f64 sum, a NaN sum as the one quiet NaN 0x7ff8000000000000"""
+    r = np.ascontiguousarray(rep_true, np.float64)
+    if r.ndim != 2:
+        raise BBQError(ERR_INVALID_ARG, "rep_true is [n_vectors, n_groups]")
+    out = np.zeros(r.shape[1], np.float64)
+    _chk(lib().bbq_maxsim_reduce_true(_ptr(r), r.shape[0], r.shape[1], _ptr(out)))
+    return out
+
+
+def _raw_tokens(token_lists, dim):
+    """(vec_offsets int64 [nq + 1], queries float32 [vectors, dim]) of per-query raw fp32 token arrays [T, dim]"""
+    arrs = [np.asarray(t, np.float32).reshape(-1, dim) for t in token_lists]
+    off = np.zeros(len(arrs) + 1, np.int64)
+    off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    return off, np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, dim), np.float32))
+
+
 def maxsim_token_block():
     """bbq_maxsim_token_block: the tokens of a query a MaxSim search works through at a time"""
     return int(lib().bbq_maxsim_token_block())
@@ -1024,6 +1047,40 @@ class Vectors:
         out = np.zeros(int(off[-1]), np.float64)
         _chk(lib().bbq_rerank_scores(self._h, q.shape[0], _ptr(q), _ptr(off), _ptr(rows), true_sim, _ptr(out)))
         return [out[off[i]:off[i + 1]] for i in range(len(lists))]
+
+    def rerank_maxsim_groups_batch(self, token_lists, groups, cand_lists, true_sim=1):
+        """bbq_rerank_maxsim_groups_batch: the exact MaxSim score of every candidate group of every query.  token_lists: per query its
+        raw fp32 token vectors [T, dim], T >= 1; cand_lists: per query an int array of group numbers of `groups`, in any order,
+        duplicates allowed (or (offsets, groups) as score_ords_batch takes its lists).  Returns (true scores float64 [total], offsets
+        int64 [nq + 1])."""
+        nq = len(token_lists)
+        off, q = _raw_tokens(token_lists, self.dim)
+        coff, cg = _lists(cand_lists, nq)
+        out = np.zeros(cg.shape[0], np.float64)
+        _chk(lib().bbq_rerank_maxsim_groups_batch(self._h, groups._h if groups is not None else None, nq, _ptr(off), _ptr(q), true_sim, _ptr(coff), _ptr(cg),
+                                                 _ptr(out)))
+        return out, coff
+
+
+def search_maxsim_rerank_batch(index, vectors, groups, raw_token_lists, token_lists, query_bits, sim, k, factor, selector=0, true_sim=1):
+    """bbq_search_maxsim_rerank_batch: the MaxSim search with k * factor on `index`, the exact MaxSim scores of the returned groups on
+    `vectors`, the reference's selector (0 heap, 1 sort).  raw_token_lists: per query its raw fp32 token vectors [T, dim]; token_lists:
+    the same tokens quantized, as Index.search_maxsim_batch takes them.  Returns a list of (group int32, quantized f32, true f64) per query."""
+    nq = len(token_lists)
+    if len(raw_token_lists) != nq:
+        raise BBQError(ERR_INVALID_ARG, "one raw token array per query")
+    off, qq, qc = index._maxsim_tokens(token_lists)
+    roff, q = _raw_tokens(raw_token_lists, index.dim)
+    if roff.tolist() != off.tolist():
+        raise BBQError(ERR_INVALID_ARG, "as many raw token vectors as quantized ones, query by query")
+    kk = max(int(k), 0)
+    grp = np.zeros((nq, kk), np.int32)
+    qs = np.zeros((nq, kk), np.float32)
+    ts = np.zeros((nq, kk), np.float64)
+    cnt = np.zeros(nq, np.int64)
+    _chk(lib().bbq_search_maxsim_rerank_batch(index._h, vectors._h if vectors is not None else None, groups._h if groups is not None else None, nq, _ptr(off),
+                                             _ptr(q), _ptr(qq), _ptr(qc), query_bits, sim, k, factor, selector, true_sim, _ptr(grp), _ptr(qs), _ptr(ts), _ptr(cnt)))
+    return [(grp[i, :cnt[i]], qs[i, :cnt[i]], ts[i, :cnt[i]]) for i in range(nq)]
 
 
 def search_rerank_batch(index, vectors, queries, qquant, qcorr, query_bits, sim, k, factor, selector=0, true_sim=1):

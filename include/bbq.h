@@ -41,7 +41,8 @@ extern "C" {
                               bbq_search_spans_filtered_batch - and the grouped search - bbq_groups_create, bbq_groups_destroy,
                               bbq_groups_count, bbq_groups_live, bbq_groups_plan, bbq_search_grouped_batch - and the MaxSim search -
                               bbq_search_maxsim_batch, bbq_maxsim_reduce, bbq_maxsim_token_block - and MaxSim over chosen groups -
-                              bbq_score_maxsim_groups_batch, bbq_search_maxsim_groups_batch) */
+                              bbq_score_maxsim_groups_batch, bbq_search_maxsim_groups_batch - and the exact MaxSim rerank -
+                              bbq_maxsim_reduce_true, bbq_rerank_maxsim_groups_batch, bbq_search_maxsim_rerank_batch) */
 
 /* status codes */
 enum {
@@ -722,6 +723,48 @@ int bbq_search_rerank_batch(bbq_index *idx, bbq_vectors *v, int32_t n_queries, c
                             const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim, int64_t k,
                             int32_t factor, int32_t selector, int32_t true_sim, int32_t *out_idx,
                             float *out_quantized, double *out_true, int64_t *out_n);
+
+/* ------------------------------------------------------------------------------------------
+ * Exact MaxSim rerank (DESIGN.md "Exact MaxSim rerank"): the third stage of late interaction - the candidate groups a MaxSim call
+ * nominated, rescored against the fp32 rows of a bbq_vectors.  A query is a run of RAW fp32 token vectors: vec_offsets as
+ * bbq_search_maxsim_batch takes and checks it, queries [vec_offsets[n_queries] * dim], not normalised, exactly as bbq_rerank_scores
+ * takes a query.
+ * Definitions.  For a token vector q_t and a row r, c(t, r) is the f64 bbq_rerank_scores returns for that pair under true_sim:
+ * computeSimilarity, accumulated in index order, bit for bit.  For a live group G of a group set, M_t(G) is the greatest c(t, r) over
+ * the rows of G that the set's filter accepts: a NaN ranks below every number, numbers rank by value with -0.0 below +0.0, and if every
+ * accepted row gives NaN, M_t is NaN.  The group's true score is
+ *   T = M_0 + M_1 + ...
+ * - the adds f64, strictly in ascending token, starting from M_0 and not from 0.0, no contraction, no reassociation; a NaN result,
+ * from a NaN M_t or from +Inf + -Inf, is written as the quiet NaN 0x7ff8000000000000, so host and device agree byte for byte.
+ * bbq_maxsim_reduce_true (host only, no device) is this sum in plain C over rep_true[t * n_groups + g] -> out [n_groups],
+ * n_vectors >= 1: the normative statement, as bbq_maxsim_reduce is for the f32 sums.
+ * bbq_rerank_maxsim_groups_batch: out_true[i] (indexed like cand_groups) is T for group cand_groups[i] of g and that query.
+ * cand_offsets / cand_groups as bbq_score_maxsim_groups_batch takes and checks them, with the same wording under this function's name:
+ * range, liveness, the first offending (query, position, group) named, any order, a duplicate scored per occurrence, at most 2^31 - 1
+ * expanded rows a query - on the host, under the context's lock, before the first launch; on refusal nothing is launched and nothing
+ * written.  true_sim outside 0 .. 2 is refused with bbq_rerank_scores' message.  bbq_vectors_size(v) must equal the row count the group
+ * set was made for and v must live on its device, otherwise BBQ_ERR_INVALID_ARG: a set made stale by an append or a compaction is
+ * refused; after bbq_vectors_update the set still serves.  Non-finite inputs are not refused: they propagate by IEEE arithmetic, as in
+ * bbq_rerank_scores.  n_queries == 0 or an empty total list: BBQ_OK, nothing launched.  One 8-byte record per candidate travels to the
+ * device and one f64 per candidate comes back; no row list is staged, and a candidate's fp32 row is read once per token block, not
+ * once per token.  A long call is worked through in sub-batches of at most 1024 queries and 256 MiB of scratch (the recipe call:
+ * group_scratch_mb of its index) - per query 8 bytes per token of a block and 8 more, per entry of the call's longest list, and the
+ * f64 image of a token block - in token blocks of bbq_maxsim_token_block() tokens; the scratch does not grow with the call.  A failed
+ * allocation: BBQ_ERR_OOM, nothing written.  Results are byte-identical from run to run.
+ * bbq_search_maxsim_rerank_batch is the whole recipe, defined by composition: (1) bbq_search_maxsim_batch with k * factor; (2) the
+ * call above over each query's returned groups, in returned order; (3) bbq_search_rerank_batch's two selectors over the true scores -
+ * selector 0 the heap of k, drained and stably sorted, selector 1 the stable descending sort, first k; NaN as there.  out_group /
+ * out_quantized (the MaxSim search's f32 sums) / out_true [n_queries*k] (query q at offset q*k), out_n [n_queries].  Argument checks,
+ * k == 0, factor < 1 and a k * factor that overflows as bbq_search_rerank_batch; handle restrictions as bbq_search_maxsim_batch.
+ * Out of scope: a device-side select over the true scores, per-token best rows, multi-device handles and shards. */
+int bbq_maxsim_reduce_true(const double *rep_true, int64_t n_vectors, int64_t n_groups, double *out);   /* host only */
+int bbq_rerank_maxsim_groups_batch(bbq_vectors *v, const bbq_groups *g, int32_t n_queries, const int64_t *vec_offsets,
+                                   const float *queries, int32_t true_sim, const int64_t *cand_offsets,
+                                   const int32_t *cand_groups, double *out_true);
+int bbq_search_maxsim_rerank_batch(bbq_index *idx, bbq_vectors *v, const bbq_groups *g, int32_t n_queries,
+                                   const int64_t *vec_offsets, const float *queries, const uint8_t *qquant, const double *qcorr,
+                                   int32_t query_bits, int32_t sim, int64_t k, int32_t factor, int32_t selector, int32_t true_sim,
+                                   int32_t *out_group, float *out_quantized, double *out_true, int64_t *out_n);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side quantizer (multithreaded C++): what the JS host calls for quantizeVectors /
