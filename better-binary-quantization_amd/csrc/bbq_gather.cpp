@@ -1,9 +1,8 @@
 // bbq_gather.cpp - scoring and ranking chosen rows: bbq_score_ords, bbq_score_ords_batch, bbq_search_ords_batch (kernel:
 // bbq_gather_kernels.hip).  The host checks every list before the first launch, stages queries, offsets and ords, works through a
 // long call in launches of bounded size and brings back only the outputs asked for; the search replays the reference's heap over the
-// f32 scores in list order.
+// f32 scores in list order (replay_lists, bbq_replay.cpp).
 #include <string.h>
-#include <thread>
 #include "bbq_search.h"
 
 using namespace bbq;
@@ -18,8 +17,6 @@ constexpr int kGatherMaxQueries = 1024;
 
 // entries [beg, end) of the call's ords: a whole list, or a piece of one longer than a launch takes
 struct ListPiece { int32_t q; int64_t beg, end; };
-
-inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
 
 // offsets as bbq_rerank_scores takes them; *total = offsets[n_queries]
 int check_offsets(const char *who, int32_t n_queries, const int64_t *offsets, int64_t *total) {
@@ -59,10 +56,8 @@ int score_ords_single(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, c
   const size_t max_q = std::min<size_t>(pieces.size(), (size_t)kGatherMaxQueries), max_e = (size_t)std::min<int64_t>(total, kGatherMaxEntries);
   const size_t head_cap = align16((max_q + 1) * 8) + max_q * (qb + sizeof(QueryParams));
   const size_t at_ords = align16(head_cap), at_qc = at_ords + align16(max_e * 4), at_32 = at_qc + align16(max_e * 4), at_64 = at_32 + align16(max_e * 4);
-  {
-    const hipError_t e = ix->ctx->d_gather.reserve(at_64 + max_e * 8);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "bbq_score_ords: %zu bytes of scratch: %s", at_64 + max_e * 8, hipGetErrorString(e)); }
-  }
+  rc = reserve_scratch(ix->ctx->d_gather, at_64 + max_e * 8, "bbq_score_ords");
+  if (rc != BBQ_OK) return rc;
   uint8_t *d = ix->ctx->d_gather;
   hipStream_t st = ix->ctx->aux_stream;
   std::vector<uint8_t> head(head_cap);
@@ -164,24 +159,7 @@ int bbq_search_ords_batch(bbq_index *ix, int32_t n_queries, const uint8_t *qquan
     rc = score_ords_checked(ix, n_queries, qquant, qcorr, query_bits, sim, offsets, ords, nullptr, nullptr, k > 0 ? s32.data() : nullptr);
     if (rc != BBQ_OK) return rc;
   }
-  // the reference loop (src/binaryQuantizationFormat.ts:383-411) over each list IN THE ORDER GIVEN: the literal heap of min(k, length)
-  auto work = [&](int32_t lo, int32_t hi) {
-    for (int32_t q = lo; q < hi; ++q) {
-      const int64_t beg = offsets[q], len = offsets[q + 1] - beg;
-      if (k == 0 || len == 0) { out_n[q] = 0; continue; }
-      HeapReplay hr(k, len);
-      for (int64_t i = 0; i < len; ++i) hr.offer(s32[(size_t)(beg + i)], ords[beg + i]);
-      out_n[q] = hr.finish(out_idx + (int64_t)q * k, out_score + (int64_t)q * k);
-    }
-  };
-  const int T = (int)std::min<int64_t>(std::max(ix->opt_replay_threads, 1), n_queries);
-  if (T <= 1 || total < 4096) {
-    work(0, n_queries);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t) th.emplace_back(work, (int32_t)((int64_t)n_queries * t / T), (int32_t)((int64_t)n_queries * (t + 1) / T));
-    for (std::thread &x : th) x.join();
-  }
+  replay_lists(n_queries, offsets, ords, s32.data(), k, ix->opt_replay_threads, out_idx, out_score, out_n);  // in the order given
   return BBQ_OK;
 }
 

@@ -1,15 +1,14 @@
 // bbq_group.cpp - grouped search: bbq_groups_*, bbq_search_grouped_batch (kernels: bbq_group_kernels.hip, and the span search's select
 // pass).  A group set is made once for one index: its offsets are checked, the live groups - those with a row the bound filter accepts -
-// are numbered on the host, and three small tables go to the device (GroupScoreArgs, bbq_device.h).  A call then follows the span
-// search's host path (bbq_span.cpp): sub-batches bounded by scratch, the queries staged in one copy, the score pass, the unpack pass and
-// the select pass over the live groups' representatives, the answer blocks back in one copy, the device's k sorted and proven, and the
-// reference's heap replayed over the representatives of the queries it could not prove.  Every query of a call has the same number of
-// representatives, L: whether the select pass runs is decided once per call.
+// are numbered on the host, and three small tables go to the device (GroupScoreArgs, bbq_device.h).  A call works through sub-batches
+// bounded by scratch: the queries staged in one copy, the score pass, the unpack pass and the span search's select pass over the live
+// groups' representatives, the answer blocks back in one copy, and the end every select-pass search has (finish_selected,
+// bbq_select.cpp): the device's k proven, the reference's heap replayed over the other queries' representatives.  Every query of a
+// call has the same number of representatives, L: whether the select pass runs is decided once per call.
 #include <string.h>
 #include <algorithm>
 #include <memory>
 #include <new>
-#include <thread>
 #include "bbq_search.h"
 
 using namespace bbq;
@@ -19,8 +18,6 @@ namespace {
 // A sub-batch takes at most this many queries and - by default - this many bytes of scratch for the representatives (16 B per live
 // group and query: the packed key, the score, the ord), and always at least one query.
 constexpr int kGroupMaxQueries = 1024;
-
-inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
 
 // accepted rows of [b, e), b < e: is there one?  bits == null: every row
 inline bool any_accepted(const uint64_t *bits, int64_t b, int64_t e) {
@@ -65,6 +62,20 @@ int bbq::check_group_index(const bbq_index *ix) {
   if (ix->multi) return fail(BBQ_ERR_UNSUPPORTED, "grouped search is not supported on a multi-device index");
   if (ix->has_pilot || ix->row_base != 0) return fail(BBQ_ERR_UNSUPPORTED, "grouped search is not supported on a row shard or an index with a pilot replica");
   return BBQ_OK;
+}
+
+GroupScoreArgs bbq::group_score_args(bbq_index *ix, const bbq_groups *gs) {
+  const int64_t n_tiles = tiles_of(gs->n_rows);
+  GroupScoreArgs ga{};
+  ga.idx = main_launch_view(ix);
+  ga.starts = gs->d_words.get();
+  ga.accept = gs->filtered ? gs->d_words.get() + n_tiles + 1 : nullptr;
+  ga.first_group = gs->d_index.get();
+  ga.slot = reinterpret_cast<const int32_t *>(gs->d_index.get() + n_tiles + 1);
+  ga.live = gs->live;
+  ga.n_chunks = (int32_t)ix->main.n_chunks();
+  ga.l2_shift = l2_share_shift(ix);
+  return ga;
 }
 
 namespace {
@@ -119,10 +130,8 @@ int grouped_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const
   const int per = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kGroupMaxQueries, n_queries), budget / (16 * L)));
   const Layout big(per, sel ? per : 0, L, qb, out_stride);
   // everything large, before anything is written to the caller's arrays
-  {
-    const hipError_t e = ix->ctx->d_span.reserve(big.bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "grouped search: %zu bytes of scratch: %s", big.bytes, hipGetErrorString(e)); }
-  }
+  const int rc_scratch = reserve_scratch(ix->ctx->d_span, big.bytes, "grouped search");
+  if (rc_scratch != BBQ_OK) return rc_scratch;
   const size_t back_words = sel ? (size_t)per * out_stride : 0;
   const size_t host_rows = (size_t)per * (size_t)L;
   std::unique_ptr<uint8_t[]> head(new (std::nothrow) uint8_t[std::max<size_t>(big.head_bytes, 1)]);
@@ -134,19 +143,16 @@ int grouped_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const
 
   uint8_t *d = ix->ctx->d_span;
   hipStream_t st = ix->ctx->aux_stream;
-  const int64_t n_tiles = tiles_of(gs->n_rows);
-  GroupScoreArgs ga{};
-  ga.idx = launch_view(ix, ix->main).view;
-  ga.idx.row_sums = row_sums_for_launch(ix) ? ix->main.view.row_sums : nullptr;
-  ga.starts = gs->d_words.get();
-  ga.accept = gs->filtered ? gs->d_words.get() + n_tiles + 1 : nullptr;
-  ga.first_group = gs->d_index.get();
-  ga.slot = reinterpret_cast<const int32_t *>(gs->d_index.get() + n_tiles + 1);
-  ga.live = L;
-  ga.n_chunks = (int32_t)ix->main.n_chunks();
-  ga.l2_shift = l2_share_shift(ix);
-  std::vector<int64_t> replay;  // the queries of the sub-batch whose heap the host replays
-  std::vector<uint64_t> ent;
+  GroupScoreArgs ga = group_score_args(ix, gs);
+  std::vector<SelectQuery> sq((size_t)per);  // every query of a sub-batch: L scores from s * L on, and block s where the select pass runs
+  SelectTail t{};
+  t.back = back.get();
+  t.h_scores = h_scores.get();
+  t.h_ords = h_ords.get();
+  t.k = k;
+  t.out_stride = out_stride;
+  t.stream = st;
+  t.threads = ix->opt_replay_threads;
 
   for (int64_t q0 = 0; q0 < n_queries; q0 += per) {
     const int nq = (int)std::min<int64_t>(per, n_queries - q0);
@@ -182,61 +188,17 @@ int grouped_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const
     }
     HIPCHK(hipStreamSynchronize(st));  // also: the staging is free for the next sub-batch
 
-    // what the device selected: exactly k representatives above the cut and no NaN - sorted by descending score; two equal scores among
-    // them, or one equal to the cut, and the heap's history decides: replayed like the queries the device could not prove
-    replay.clear();
-    for (int s = 0; s < nq; ++s) {
-      const int64_t q = q0 + s;
-      bool proven = false;
-      if (sel) {
-        const uint64_t *blk = back.get() + (size_t)s * out_stride;
-        if ((uint32_t)(blk[0] >> 32) == 0u && (int64_t)(uint32_t)blk[0] == k) {
-          ent.assign(blk + 2, blk + 2 + k);
-          std::sort(ent.begin(), ent.end(), [](uint64_t x, uint64_t y) { return entry_score(x) > entry_score(y); });
-          proven = entry_score(ent[(size_t)k - 1]) != entry_score(blk[1]);
-          for (int64_t i = 1; proven && i < k; ++i) proven = entry_score(ent[(size_t)i - 1]) != entry_score(ent[(size_t)i]);
-          if (proven) {
-            unpack_entries(ent.data(), k, out_idx + q * k, out_score + q * k);
-            out_n[q] = k;
-          }
-        }
-      }
-      if (out_status) out_status[q] = proven ? 0 : 1;
-      if (!proven) replay.push_back(s);
-    }
-    if (!replay.empty()) {
-      // the reference loop (src/binaryQuantizationFormat.ts:383-411) over the query's representatives in ascending ord: the literal heap
-      // of min(k, L) (they come back query by query, or in one copy where they are at least half of the sub-batch's)
-      auto bring_back = [&](int64_t first, int64_t rows) {
-        hipError_t e = hipMemcpyAsync(h_scores.get() + first, d_scores + first, (size_t)rows * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_ords.get() + first, d_ords + first, (size_t)rows * 4, hipMemcpyDeviceToHost, st);
-        return e;
-      };
-      if (2 * (int64_t)replay.size() >= nq) {
-        HIPCHK(bring_back(0, (int64_t)nq * L));
-      } else {
-        for (int64_t s : replay) HIPCHK(bring_back(s * L, L));
-      }
-      HIPCHK(hipStreamSynchronize(st));
-      auto work = [&](size_t t, size_t T) {
-        for (size_t i = t; i < replay.size(); i += T) {
-          const int64_t s = replay[i], q = q0 + s;
-          const float *sc = h_scores.get() + s * L;
-          const uint32_t *od = h_ords.get() + s * L;
-          HeapReplay hr(k, L);
-          for (int64_t r = 0; r < L; ++r) hr.offer(sc[r], (int32_t)od[r]);
-          out_n[q] = hr.finish(out_idx + q * k, out_score + q * k);
-        }
-      };
-      const size_t T = std::min<size_t>((size_t)std::max(ix->opt_replay_threads, 1), replay.size());
-      if (T <= 1 || (int64_t)replay.size() * L < 4096) {
-        work(0, 1);
-      } else {
-        std::vector<std::thread> th;
-        for (size_t t = 0; t < T; ++t) th.emplace_back(work, t, T);
-        for (std::thread &x : th) x.join();
-      }
-    }
+    for (int s = 0; s < nq; ++s) sq[(size_t)s] = SelectQuery{L, (int64_t)s * L, sel ? s : -1};
+    t.queries = sq.data();
+    t.nq = nq;
+    t.d_scores = d_scores;
+    t.d_ords = d_ords;
+    t.out_tag = out_idx + q0 * k;
+    t.out_score = out_score + q0 * k;
+    t.out_n = out_n + q0;
+    t.out_status = out_status ? out_status + q0 : nullptr;
+    const int rc = finish_selected(t);  // the representatives of a replayed query in ascending ord
+    if (rc != BBQ_OK) return rc;
     if (out_group)
       for (int s = 0; s < nq; ++s)
         for (int64_t j = 0; j < out_n[q0 + s]; ++j) out_group[(q0 + s) * k + j] = group_of(gs->offsets, out_idx[(q0 + s) * k + j]);

@@ -14,6 +14,9 @@
 //   bbq_range.cpp    range search: every row at or above a threshold (bbq_range_key, bbq_count_range_batch, bbq_search_range_batch)
 //   bbq_span.cpp     span search: the k best rows of per-query row spans (bbq_search_spans_batch, bbq_search_spans_filtered_batch)
 //   bbq_group.cpp    grouped search: the k best groups of rows by their best row (bbq_groups_*, bbq_search_grouped_batch)
+//   bbq_maxsim.cpp   MaxSim search: the k best groups by the sum of their best rows over a query's token vectors (bbq_search_maxsim_batch)
+//   bbq_select.cpp   what the three above end with: the device's selected answers proven, the rest replayed on the host (finish_selected)
+//   bbq_maxsim_groups.cpp, bbq_maxsim_rerank.cpp   MaxSim over chosen groups, quantized and exact (bbq_*_maxsim_groups_batch, bbq_search_maxsim_rerank_batch)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
 // bbq_entry.h is the codec of the 64-bit entries, keys and answer headers; bbq_workqueue.h the host threads' job queue.
@@ -140,7 +143,8 @@ struct DeviceCtx {
   DevBuf<uint8_t> d_gather;          // grow-only scratch of bbq_score_ords* (bbq_gather.cpp): one launch's offsets, queries, ords and outputs
   DevBuf<uint8_t> d_range;           // grow-only scratch of a range search's sub-batch (bbq_range.cpp): queries, thresholds, per-chunk counts and lists
   DevBuf<uint8_t> d_span;            // grow-only scratch of a span search's sub-batch (bbq_span.cpp): queries, span tables, work items, answer blocks, scores;
-                                     // and of a grouped search's (bbq_group.cpp): queries, answer blocks, the representatives' keys, scores and ords
+                                     // of a grouped search's (bbq_group.cpp): queries, answer blocks, the representatives' keys, scores and ords; and of
+                                     // the MaxSim calls' (bbq_maxsim*.cpp).  What bbq_select.cpp's finish_selected brings scores and ords back from
   int last_big_slot = -1;             // slot whose ev_big marks the end of the most recently enqueued big sweep
   // latency path (bbq_latency_kernels.hip): the answer of a single-query call lands in mapped, coherent host memory and the host
   // polls a sequence word behind it: [0] sequence, [8 ..) header + entries
@@ -165,6 +169,15 @@ int64_t qbuf_bytes_per_query_w(int w16);
 // returns the (lazily created, never destroyed) context of a device; call with hipSetDevice(device) done
 int get_ctx(int device, DeviceCtx **out);
 int ensure_aux_qbuf(DeviceCtx *c, int64_t bytes);
+// where the next array of a scratch layout starts: the 16-byte boundary at or behind byte b
+inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
+// a context's grow-only scratch holds `bytes`, or BBQ_ERR_OOM in the words of `what` - before anything is written to the caller's arrays
+inline int reserve_scratch(DevBuf<uint8_t> &scratch, size_t bytes, const char *what) {
+  const hipError_t e = scratch.reserve(bytes);
+  if (e == hipSuccess) return BBQ_OK;
+  (void)hipGetLastError();
+  return fail(BBQ_ERR_OOM, "%s: %zu bytes of scratch: %s", what, bytes, hipGetErrorString(e));
+}
 // default number of host threads (heap replays, query quantization): half the cores, at most 16
 inline int default_host_threads() { return (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2)); }
 // bytes of the compact layout's side arrays for n_tiles tiles: exact corrections + add ranges (an allocation: n_tiles = its capacity;

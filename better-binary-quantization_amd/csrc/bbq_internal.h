@@ -1,7 +1,9 @@
 // bbq_internal.h - host-side internals of libbbq shared between translation units
 #pragma once
 #include <stdint.h>
+#include <algorithm>
 #include <string>
+#include <thread>
 #include <vector>
 #include "../../include/bbq.h"
 #include "bbq_entry.h"
@@ -48,5 +50,32 @@ class HeapReplay {
   int64_t k2_;
   int64_t mutations_ = 0;
 };
+
+// fn(i) for every i of [0, n) on at most T threads, thread t taking t, t + T, ...; T <= 1 or n <= 1: on the calling thread.  What the
+// calls write must be disjoint - then how the indices are dealt changes no result.  When threads pay is the caller's decision.
+template <class Fn>
+void for_each_index(int64_t T, int64_t n, Fn fn) {
+  T = std::min(T, n);
+  if (T <= 1) {
+    for (int64_t i = 0; i < n; ++i) fn(i);
+    return;
+  }
+  std::vector<std::thread> th;
+  for (int64_t t = 0; t < T; ++t)
+    th.emplace_back([=] { for (int64_t i = t; i < n; i += T) fn(i); });
+  for (std::thread &x : th) x.join();
+}
+
+// One answer block of the select pass (SpanSelectArgs::out, bbq_device.h): {scores above the cut | NaN seen << 32}, the cut's f32 bits,
+// then the entries.  Proven - the reference's heap returns exactly these k, by descending score - when there are exactly k above the cut,
+// no NaN, no two of them score equal and the k-th does not equal the cut; otherwise the heap's history decides and the caller replays
+// it.  ent: the k entries by descending score when proven, scratch otherwise.
+bool prove_selected(const uint64_t *blk, int64_t k, std::vector<uint64_t> &ent);
+
+// The reference loop (src/binaryQuantizationFormat.ts:383-411) over each of n_lists lists IN THE ORDER GIVEN: the literal heap of
+// min(k, length) over (scores[i], tags[i]), i in [offsets[q], offsets[q + 1]) -> out_tag / out_score [q][k], out_n[q].  An empty list
+// or k == 0 answers 0.  On `threads` threads once the lists hold 4096 entries.
+void replay_lists(int32_t n_lists, const int64_t *offsets, const int32_t *tags, const float *scores, int64_t k, int threads, int32_t *out_tag,
+                  float *out_score, int64_t *out_n);
 
 }  // namespace bbq

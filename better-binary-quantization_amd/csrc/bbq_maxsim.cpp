@@ -1,15 +1,15 @@
 // bbq_maxsim.cpp - MaxSim search: bbq_search_maxsim_batch, bbq_maxsim_reduce, bbq_maxsim_token_block (kernels: bbq_maxsim_kernels.hip, the
 // grouped search's score pass and the span search's select pass).  A query is a run of token vectors and a live group of a group set
-// (bbq_group.cpp) scores the ordered f64 sum of its representatives' f32 scores.  A call follows the grouped search's host path: sub-batches
+// (bbq_group.cpp) scores the ordered f64 sum of its representatives' f32 scores.  A call works through sub-batches
 // bounded by scratch, and inside a sub-batch the queries' tokens in blocks of at most kMaxSimTokenBlock - a block's vectors staged in one
-// copy, its keys cleared, the score pass (fused where the option and the shape allow, the grouped search's kernel with the block's
-// vectors as its queries otherwise) and the accumulate pass - then the select pass over the sums, the answer blocks back in one copy, the
-// device's k sorted and proven, and the reference's heap replayed over the sums of the queries it could not prove.
+// copy (stage_maxsim_token_block, which MaxSim over chosen groups shares), its keys cleared, the score pass (fused where the option and
+// the shape allow, the grouped search's kernel with the block's vectors as its queries otherwise) and the accumulate pass - then the
+// select pass over the sums, the answer blocks back in one copy, and the end every select-pass search has (finish_selected,
+// bbq_select.cpp): the device's k proven, the reference's heap replayed over the other queries' sums.
 #include <string.h>
 #include <algorithm>
 #include <memory>
 #include <new>
-#include <thread>
 #include "bbq_search.h"
 
 using namespace bbq;
@@ -20,8 +20,6 @@ constexpr int kMaxSimMaxQueries = 1024;  // of a sub-batch: 32 768 vectors in a 
 // maxsim_fused -1: the fused kernel wherever it exists.  At 1 M rows of 768, 1024 and 1536 dimensions (profiles/maxsim_search*.json) the
 // slowest of its three runs beat the fastest of the unfused path's by more than that path's spread on every leg: 1.4 to 1.7 times faster
 constexpr bool kMaxSimFusedDefault = true;
-
-inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
 
 // where a sub-batch of nq queries whose widest token block has nv vectors keeps what in the scratch: [query data | query uniforms | the
 // block's queries | selected queries] come from the host in one copy per block, the answer blocks go back in one; the keys of a block,
@@ -81,10 +79,8 @@ int maxsim_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const 
   }
   const Layout big(per, widest, sel ? per : 0, L, qb, out_stride);
   // everything large, before anything is written to the caller's arrays
-  {
-    const hipError_t e = ix->ctx->d_span.reserve(big.bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "MaxSim search: %zu bytes of scratch: %s", big.bytes, hipGetErrorString(e)); }
-  }
+  const int rc_scratch = reserve_scratch(ix->ctx->d_span, big.bytes, "MaxSim search");
+  if (rc_scratch != BBQ_OK) return rc_scratch;
   const size_t back_words = sel ? (size_t)per * out_stride : 0;
   const size_t host_rows = (size_t)per * (size_t)L;
   std::unique_ptr<uint8_t[]> head(new (std::nothrow) uint8_t[std::max<size_t>(big.head_bytes, 1)]);
@@ -96,20 +92,19 @@ int maxsim_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const 
 
   uint8_t *d = ix->ctx->d_span;
   hipStream_t st = ix->ctx->aux_stream;
-  const int64_t n_tiles = tiles_of(gs->n_rows);
   MaxSimScoreArgs ma{};
   GroupScoreArgs &ga = ma.g;
-  ga.idx = launch_view(ix, ix->main).view;
-  ga.idx.row_sums = row_sums_for_launch(ix) ? ix->main.view.row_sums : nullptr;
-  ga.starts = gs->d_words.get();
-  ga.accept = gs->filtered ? gs->d_words.get() + n_tiles + 1 : nullptr;
-  ga.first_group = gs->d_index.get();
-  ga.slot = reinterpret_cast<const int32_t *>(gs->d_index.get() + n_tiles + 1);
-  ga.live = L;
-  ga.n_chunks = (int32_t)ix->main.n_chunks();
-  ga.l2_shift = l2_share_shift(ix);
-  std::vector<int64_t> replay;  // the queries of the sub-batch whose heap the host replays
-  std::vector<uint64_t> ent;
+  ga = group_score_args(ix, gs);
+  const MaxSimTokens tk{voff, qquant, qcorr, planes, one_bit, sim};
+  std::vector<SelectQuery> sq((size_t)per);  // every query of a sub-batch: L sums from s * L on, and block s where the select pass runs
+  SelectTail t{};
+  t.back = back.get();
+  t.h_scores = h_scores.get();
+  t.h_ords = h_ords.get();
+  t.k = k;
+  t.out_stride = out_stride;
+  t.stream = st;
+  t.threads = ix->opt_replay_threads;
 
   for (int64_t q0 = 0; q0 < n_queries; q0 += per) {
     const int nq = (int)std::min<int64_t>(per, n_queries - q0);
@@ -125,20 +120,9 @@ int maxsim_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const 
     for (int s = 0; sel && s < nq; ++s) h_sel[s] = SpanQuery{(int64_t)s * L, L, 0, 0, 0};
 
     for (int64_t t0 = 0; t0 < longest; t0 += TB) {  // the token block [t0, t0 + TB) of every query that has one
-      MaxSimQuery *h_mq = reinterpret_cast<MaxSimQuery *>(head.get() + lo.mq);
       int n_mq = 0;
-      int32_t v = 0;  // vectors staged so far
-      for (int s = 0; s < nq; ++s) {
-        const int64_t first = voff[q0 + s], T = voff[q0 + s + 1] - first;
-        if (T <= t0) continue;
-        const int n_tok = (int)std::min<int64_t>(TB, T - t0);
-        h_mq[n_mq++] = MaxSimQuery{v, n_tok, s, (t0 == 0 ? kMaxSimFirst : 0) | (t0 + n_tok == T ? kMaxSimLast : 0)};
-        for (int t = 0; t < n_tok; ++t, ++v) {
-          const int64_t vec = first + t0 + t;
-          fill_query(ix, head.get() + lo.qdata + (size_t)v * qb, reinterpret_cast<QueryParams *>(head.get() + lo.qparams) + v,
-                     qquant + (size_t)vec * ix->geom.dim, qcorr + (size_t)vec * 4, planes, one_bit, sim);
-        }
-      }
+      const int32_t v = stage_maxsim_token_block(ix, tk, q0, nq, t0, [](int) { return true; }, head.get() + lo.qdata, qb,
+                                                 reinterpret_cast<QueryParams *>(head.get() + lo.qparams), reinterpret_cast<MaxSimQuery *>(head.get() + lo.mq), &n_mq);
       HIPCHK(hipMemcpyAsync(d, head.get(), lo.head_bytes, hipMemcpyHostToDevice, st));
       HIPCHK(hipMemsetAsync(d + lo.rep, 0, (size_t)v * (size_t)L * 8, st));
       ga.qplanes = reinterpret_cast<const uint4 *>(d + lo.qdata);
@@ -177,66 +161,39 @@ int maxsim_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const 
     }
     HIPCHK(hipStreamSynchronize(st));  // also: the staging is free for the next sub-batch
 
-    // what the device selected: exactly k sums above the cut and no NaN - sorted by descending score; two equal sums among them, or one
-    // equal to the cut, and the heap's history decides: replayed like the queries the device could not prove
-    replay.clear();
-    for (int s = 0; s < nq; ++s) {
-      const int64_t q = q0 + s;
-      bool proven = false;
-      if (sel) {
-        const uint64_t *blk = back.get() + (size_t)s * out_stride;
-        if ((uint32_t)(blk[0] >> 32) == 0u && (int64_t)(uint32_t)blk[0] == k) {
-          ent.assign(blk + 2, blk + 2 + k);
-          std::sort(ent.begin(), ent.end(), [](uint64_t x, uint64_t y) { return entry_score(x) > entry_score(y); });
-          proven = entry_score(ent[(size_t)k - 1]) != entry_score(blk[1]);
-          for (int64_t i = 1; proven && i < k; ++i) proven = entry_score(ent[(size_t)i - 1]) != entry_score(ent[(size_t)i]);
-          if (proven) {
-            unpack_entries(ent.data(), k, out_group + q * k, out_score + q * k);
-            out_n[q] = k;
-          }
-        }
-      }
-      if (out_status) out_status[q] = proven ? 0 : 1;
-      if (!proven) replay.push_back(s);
-    }
-    if (!replay.empty()) {
-      // the reference loop (src/binaryQuantizationFormat.ts:383-411) over the live groups in ascending group number: the literal heap of
-      // min(k, L) (the sums come back query by query, or in one copy where they are at least half of the sub-batch's)
-      auto bring_back = [&](int64_t first, int64_t rows) {
-        hipError_t e = hipMemcpyAsync(h_scores.get() + first, d_scores + first, (size_t)rows * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_ords.get() + first, d_ords + first, (size_t)rows * 4, hipMemcpyDeviceToHost, st);
-        return e;
-      };
-      if (2 * (int64_t)replay.size() >= nq) {
-        HIPCHK(bring_back(0, (int64_t)nq * L));
-      } else {
-        for (int64_t s : replay) HIPCHK(bring_back(s * L, L));
-      }
-      HIPCHK(hipStreamSynchronize(st));
-      auto work = [&](size_t t, size_t T) {
-        for (size_t i = t; i < replay.size(); i += T) {
-          const int64_t s = replay[i], q = q0 + s;
-          const float *sc = h_scores.get() + s * L;
-          const uint32_t *od = h_ords.get() + s * L;
-          HeapReplay hr(k, L);
-          for (int64_t r = 0; r < L; ++r) hr.offer(sc[r], (int32_t)od[r]);
-          out_n[q] = hr.finish(out_group + q * k, out_score + q * k);
-        }
-      };
-      const size_t T = std::min<size_t>((size_t)std::max(ix->opt_replay_threads, 1), replay.size());
-      if (T <= 1 || (int64_t)replay.size() * L < 4096) {
-        work(0, 1);
-      } else {
-        std::vector<std::thread> th;
-        for (size_t t = 0; t < T; ++t) th.emplace_back(work, t, T);
-        for (std::thread &x : th) x.join();
-      }
-    }
+    for (int s = 0; s < nq; ++s) sq[(size_t)s] = SelectQuery{L, (int64_t)s * L, sel ? s : -1};
+    t.queries = sq.data();
+    t.nq = nq;
+    t.d_scores = d_scores;
+    t.d_ords = d_ords;
+    t.out_tag = out_group + q0 * k;
+    t.out_score = out_score + q0 * k;
+    t.out_n = out_n + q0;
+    t.out_status = out_status ? out_status + q0 : nullptr;
+    const int rc = finish_selected(t);  // the sums of a replayed query over the live groups in ascending group number
+    if (rc != BBQ_OK) return rc;
   }
   return BBQ_OK;
 }
 
 }  // namespace
+
+int32_t bbq::stage_maxsim_token_block(const bbq_index *ix, const MaxSimTokens &tk, int64_t q0, int nq, int64_t t0, const std::function<bool(int)> &takes_part,
+                                      uint8_t *h_qdata, size_t qb, QueryParams *h_qparams, MaxSimQuery *h_mq, int *n_mq) {
+  int32_t v = 0;  // vectors staged so far
+  *n_mq = 0;
+  for (int s = 0; s < nq; ++s) {
+    const int64_t first = tk.voff[q0 + s], T = tk.voff[q0 + s + 1] - first;
+    if (T <= t0 || !takes_part(s)) continue;
+    const int n_tok = (int)std::min<int64_t>(kMaxSimTokenBlock, T - t0);
+    h_mq[(*n_mq)++] = MaxSimQuery{v, n_tok, s, (t0 == 0 ? kMaxSimFirst : 0) | (t0 + n_tok == T ? kMaxSimLast : 0)};
+    for (int t = 0; t < n_tok; ++t, ++v) {
+      const int64_t vec = first + t0 + t;
+      fill_query(ix, h_qdata + (size_t)v * qb, h_qparams + v, tk.qquant + (size_t)vec * ix->geom.dim, tk.qcorr + (size_t)vec * 4, tk.planes, tk.one_bit, tk.sim);
+    }
+  }
+  return v;
+}
 
 extern "C" {
 
@@ -259,15 +216,8 @@ int bbq_search_maxsim_batch(bbq_index *ix, const bbq_groups *g, int32_t n_querie
   clear_error();
   if (!ix) return fail(BBQ_ERR_INVALID_ARG, "目标向量集合不能为空");
   if (n_queries < 0) return fail(BBQ_ERR_INVALID_ARG, "n_queries < 0");
-  if (n_queries > 0) {
-    if (!vec_offsets) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_maxsim_batch: vec_offsets is null");
-    if (vec_offsets[0] != 0) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_maxsim_batch: vec_offsets[0] must be 0 (query 0)");
-    for (int32_t q = 0; q < n_queries; ++q)
-      if (vec_offsets[q + 1] <= vec_offsets[q])
-        return fail(BBQ_ERR_INVALID_ARG, "bbq_search_maxsim_batch: query %d has no token vector or vec_offsets descends: [%lld, %lld)", q, (long long)vec_offsets[q],
-                    (long long)vec_offsets[q + 1]);
-    if (vec_offsets[n_queries] > 0x7fffffffll) return fail(BBQ_ERR_INVALID_ARG, "bbq_search_maxsim_batch: more than 2^31 - 1 token vectors");
-  }
+  const int rcv = check_maxsim_vec_offsets("bbq_search_maxsim_batch", n_queries, vec_offsets);
+  if (rcv != BBQ_OK) return rcv;
   const int32_t n_vectors = n_queries > 0 ? (int32_t)vec_offsets[n_queries] : 0;
   const int rc = validate_query_args(ix, n_vectors, qquant, qcorr, query_bits, sim, k);
   if (rc != BBQ_OK) return rc;

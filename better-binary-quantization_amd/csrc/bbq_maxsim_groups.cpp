@@ -3,15 +3,14 @@
 // groups of a group set, in the caller's order, duplicates included; every list entry scores the MaxSim sum bbq_search_maxsim_batch
 // defines for its group.  The host checks every list - a group number out of range or a group that is not live - under the context's
 // lock before the first launch, stages ONE record per candidate (the group's first row and its position among the query's expanded
-// rows) and never a row list, and follows the MaxSim search's host path (bbq_maxsim.cpp): sub-batches bounded by scratch, and inside a
-// sub-batch the queries' tokens in blocks of at most kMaxSimTokenBlock - a block's vectors and the records staged in one copy, its keys
-// cleared, the score pass and the accumulate pass - then the f32 sums back in one copy.  The search call replays the reference's heap
-// over the sums in list order, as bbq_search_ords_batch does over its scores.
+// rows) and never a row list, and works through sub-batches bounded by scratch, and inside a sub-batch the queries' tokens in blocks of at
+// most kMaxSimTokenBlock - a block's vectors (the MaxSim search's stage_maxsim_token_block, bbq_maxsim.cpp) and the records staged in one
+// copy, its keys cleared, the score pass and the accumulate pass - then the f32 sums back in one copy.  The search call replays the
+// reference's heap over the sums in list order (replay_lists, bbq_replay.cpp), as bbq_search_ords_batch does over its scores.
 #include <string.h>
 #include <algorithm>
 #include <memory>
 #include <new>
-#include <thread>
 #include "bbq_search.h"
 
 using namespace bbq;
@@ -19,8 +18,6 @@ using namespace bbq;
 namespace {
 
 constexpr int kCandMaxQueries = 1024;  // of a sub-batch
-
-inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
 
 // where a sub-batch of nq queries with n_rec records whose widest token block has nv vectors keeps what in the scratch: [query data |
 // query uniforms | the block's queries | the queries' lists | records] come from the host in one copy per block; the keys of a block
@@ -77,10 +74,8 @@ int score_locked(const char *fn, bbq_index *ix, const bbq_groups *gs, int32_t n_
   }
   const Layout big(per, widest, most_rec, longest_list, qb);
   // everything large, before anything is written to the caller's array
-  {
-    const hipError_t e = ix->ctx->d_span.reserve(big.bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "MaxSim over chosen groups: %zu bytes of scratch: %s", big.bytes, hipGetErrorString(e)); }
-  }
+  const int rc_scratch = reserve_scratch(ix->ctx->d_span, big.bytes, "MaxSim over chosen groups");
+  if (rc_scratch != BBQ_OK) return rc_scratch;
   const size_t host_scores = (size_t)per * (size_t)longest_list;
   std::unique_ptr<uint8_t[]> head(new (std::nothrow) uint8_t[std::max<size_t>(big.head_bytes, 1)]);
   std::unique_ptr<float[]> h_scores(new (std::nothrow) float[host_scores]);
@@ -88,11 +83,10 @@ int score_locked(const char *fn, bbq_index *ix, const bbq_groups *gs, int32_t n_
 
   uint8_t *d = ix->ctx->d_span;
   hipStream_t st = ix->ctx->aux_stream;
-  const int64_t n_tiles = tiles_of(gs->n_rows);
   MaxSimCandArgs ca{};
-  ca.idx = launch_view(ix, ix->main).view;
-  ca.idx.row_sums = row_sums_for_launch(ix) ? ix->main.view.row_sums : nullptr;
-  ca.accept = gs->filtered ? gs->d_words.get() + n_tiles + 1 : nullptr;
+  ca.idx = main_launch_view(ix);
+  ca.accept = gs->filtered ? gs->d_words.get() + tiles_of(gs->n_rows) + 1 : nullptr;
+  const MaxSimTokens tk{voff, qquant, qcorr, planes, one_bit, sim};
 
   for (int64_t q0 = 0; q0 < n_queries; q0 += per) {
     const int nq = (int)std::min<int64_t>(per, n_queries - q0);
@@ -112,20 +106,9 @@ int score_locked(const char *fn, bbq_index *ix, const bbq_groups *gs, int32_t n_
     float *d_scores = reinterpret_cast<float *>(d + lo.scores);
 
     for (int64_t t0 = 0; t0 < longest_tok; t0 += TB) {  // the token block [t0, t0 + TB) of every query that has one and a candidate
-      MaxSimQuery *h_mq = reinterpret_cast<MaxSimQuery *>(head.get() + lo.mq);
       int n_mq = 0;
-      int32_t v = 0;  // vectors staged so far
-      for (int s = 0; s < nq; ++s) {
-        const int64_t first = voff[q0 + s], T = voff[q0 + s + 1] - first;
-        if (T <= t0 || h_cq[s].n_cand == 0) continue;
-        const int n_tok = (int)std::min<int64_t>(TB, T - t0);
-        h_mq[n_mq++] = MaxSimQuery{v, n_tok, s, (t0 == 0 ? kMaxSimFirst : 0) | (t0 + n_tok == T ? kMaxSimLast : 0)};
-        for (int t = 0; t < n_tok; ++t, ++v) {
-          const int64_t vec = first + t0 + t;
-          fill_query(ix, head.get() + lo.qdata + (size_t)v * qb, reinterpret_cast<QueryParams *>(head.get() + lo.qparams) + v,
-                     qquant + (size_t)vec * ix->geom.dim, qcorr + (size_t)vec * 4, planes, one_bit, sim);
-        }
-      }
+      const int32_t v = stage_maxsim_token_block(ix, tk, q0, nq, t0, [&](int s) { return h_cq[s].n_cand != 0; }, head.get() + lo.qdata, qb,
+                                                 reinterpret_cast<QueryParams *>(head.get() + lo.qparams), reinterpret_cast<MaxSimQuery *>(head.get() + lo.mq), &n_mq);
       HIPCHK(hipMemcpyAsync(d, head.get(), lo.head_bytes, hipMemcpyHostToDevice, st));
       HIPCHK(hipMemsetAsync(d + lo.rep, 0, (size_t)v * (size_t)E * 8, st));
       ca.qplanes = reinterpret_cast<const uint4 *>(d + lo.qdata);
@@ -280,24 +263,7 @@ int bbq_search_maxsim_groups_batch(bbq_index *ix, const bbq_groups *g, int32_t n
     rc = score_locked(fn, ix, g, n_queries, vec_offsets, qquant, qcorr, query_bits, sim, cand_offsets, cand_groups, k > 0 ? s32.get() : nullptr);
     if (rc != BBQ_OK) return rc;
   }
-  // the reference loop (src/binaryQuantizationFormat.ts:383-411) over each list IN THE ORDER GIVEN: the literal heap of min(k, length)
-  auto work = [&](int32_t lo, int32_t hi) {
-    for (int32_t q = lo; q < hi; ++q) {
-      const int64_t beg = cand_offsets[q], len = cand_offsets[q + 1] - beg;
-      if (k == 0 || len == 0) { out_n[q] = 0; continue; }
-      HeapReplay hr(k, len);
-      for (int64_t i = 0; i < len; ++i) hr.offer(s32[(size_t)(beg + i)], cand_groups[beg + i]);
-      out_n[q] = hr.finish(out_group + (int64_t)q * k, out_score + (int64_t)q * k);
-    }
-  };
-  const int T = (int)std::min<int64_t>(std::max(ix->opt_replay_threads, 1), n_queries);
-  if (T <= 1 || total < 4096) {
-    work(0, n_queries);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t) th.emplace_back(work, (int32_t)((int64_t)n_queries * t / T), (int32_t)((int64_t)n_queries * (t + 1) / T));
-    for (std::thread &x : th) x.join();
-  }
+  replay_lists(n_queries, cand_offsets, cand_groups, s32.get(), k, ix->opt_replay_threads, out_group, out_score, out_n);  // in the order given
   return BBQ_OK;
 }
 

@@ -3,7 +3,7 @@
 // every list entry scores T = M_0 + M_1 + ..., M_t the greatest computeSimilarity of token t against the group's accepted fp32 rows,
 // which stay resident in HBM (bbq_vectors).  The lists are checked and staged by the functions MaxSim over chosen groups uses
 // (bbq_maxsim_groups.cpp): one 8-byte record per candidate goes to the device, never a row list, and one f64 per candidate comes back.
-// The host path is that file's: sub-batches bounded by scratch, inside a sub-batch the queries' tokens in blocks of at most
+// The host path has that file's shape: sub-batches bounded by scratch, inside a sub-batch the queries' tokens in blocks of at most
 // kMaxSimTokenBlock - a block's token vectors and the records staged in one copy, its keys cleared, the score pass and the accumulate
 // pass.  The recipe call composes the MaxSim search, this rerank and the two selectors of bbq_search_rerank_batch (bbq_rerank.cpp).
 #include <string.h>
@@ -20,7 +20,6 @@ constexpr int kRerankMaxQueries = 1024;  // of a sub-batch
 constexpr int TB = kMaxSimTokenBlock;
 constexpr int TG = kMaxSimRerankTokenGroup;
 
-inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
 inline int64_t slots_of(int64_t n_tok) { return (n_tok + TG - 1) / TG * TG; }  // of one query's token block
 
 // where a sub-batch of nq queries with n_rec records whose widest token block has nv vector slots keeps what in the scratch: [the block's
@@ -73,10 +72,8 @@ int bbq::rerank_maxsim_groups(const char *fn, bbq_vectors *v, const bbq_groups *
   }
   const Layout big(per, widest, most_rec, longest_list, dim);
   // everything large, before anything is written to the caller's array
-  {
-    const hipError_t e = v->ctx->d_span.reserve(big.bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "exact MaxSim rerank: %zu bytes of scratch: %s", big.bytes, hipGetErrorString(e)); }
-  }
+  const int rc_scratch = reserve_scratch(v->ctx->d_span, big.bytes, "exact MaxSim rerank");
+  if (rc_scratch != BBQ_OK) return rc_scratch;
   const size_t host_sums = (size_t)per * (size_t)longest_list;
   std::unique_ptr<uint8_t[]> head(new (std::nothrow) uint8_t[std::max<size_t>(big.head_bytes, 1)]);
   std::unique_ptr<double[]> h_sums(new (std::nothrow) double[host_sums]);

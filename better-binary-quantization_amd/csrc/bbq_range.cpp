@@ -18,8 +18,6 @@ constexpr int kRangeMaxQueries = 1024;
 constexpr int64_t kRangeChunkBytes = 64ll << 20;
 constexpr int64_t kRangeMaxEntries = 1 << 20;
 
-inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
-
 // where a sub-batch of nq queries keeps what in the scratch: [query data | query uniforms | keys] come from the host in one copy,
 // [totals | list lengths] go back in one
 struct Layout {
@@ -137,16 +135,12 @@ int range_locked(bbq_index *ix, const bbq_filter *f, int32_t n_queries, const ui
   r.planes = planes_of_call(ix, qquant, (int64_t)n_queries * ix->geom.dim, r.one_bit);
   r.qb = (size_t)query_data_bytes(ix, r.planes);
   r.n_chunks = ix->main.n_chunks();
-  r.a.idx = launch_view(ix, ix->main).view;
-  r.a.idx.row_sums = row_sums_for_launch(ix) ? ix->main.view.row_sums : nullptr;
+  r.a.idx = main_launch_view(ix);
   r.a.accept = f ? f->d_bits.get() : nullptr;
   r.a.n_chunks = (int32_t)r.n_chunks;
   const int64_t sub = std::min<int64_t>({(int64_t)n_queries, (int64_t)kRangeMaxQueries, std::max<int64_t>(1, kRangeChunkBytes / (r.n_chunks * 8))});
-  {
-    const size_t bytes = Layout((size_t)sub, r.qb, (size_t)r.n_chunks).bytes;
-    const hipError_t e = ix->ctx->d_range.reserve(bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "range search: %zu bytes of scratch: %s", bytes, hipGetErrorString(e)); }
-  }
+  const int rc_scratch = reserve_scratch(ix->ctx->d_range, Layout((size_t)sub, r.qb, (size_t)r.n_chunks).bytes, "range search");
+  if (rc_scratch != BBQ_OK) return rc_scratch;
   const bool one_sub = sub >= n_queries;
   // every query's total first: the count entry point's answer, and what the caller's cap is held against before anything is filled.  A
   // call of several sub-batches counts each of them again in front of its fill (the scratch holds one sub-batch's offsets)

@@ -12,7 +12,6 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
-#include <thread>
 #include <vector>
 #include "bbq_internal.h"
 
@@ -97,6 +96,29 @@ int64_t HeapReplay::drain_ascending(int32_t *out_tag, double *out_score) {
   return n;
 }
 
+bool prove_selected(const uint64_t *blk, int64_t k, std::vector<uint64_t> &ent) {
+  if ((uint32_t)(blk[0] >> 32) != 0u || (int64_t)(uint32_t)blk[0] != k) return false;
+  ent.assign(blk + 2, blk + 2 + k);
+  std::sort(ent.begin(), ent.end(), [](uint64_t x, uint64_t y) { return entry_score(x) > entry_score(y); });
+  bool proven = entry_score(ent[(size_t)k - 1]) != entry_score(blk[1]);
+  for (int64_t i = 1; proven && i < k; ++i) proven = entry_score(ent[(size_t)i - 1]) != entry_score(ent[(size_t)i]);
+  return proven;
+}
+
+void replay_lists(int32_t n_lists, const int64_t *offsets, const int32_t *tags, const float *scores, int64_t k, int threads, int32_t *out_tag,
+                  float *out_score, int64_t *out_n) {
+  for_each_index(n_lists > 0 && offsets[n_lists] >= 4096 ? threads : 1, n_lists, [=](int64_t q) {
+    const int64_t beg = offsets[q], len = offsets[q + 1] - beg;
+    if (k == 0 || len == 0) {
+      out_n[q] = 0;
+      return;
+    }
+    HeapReplay hr(k, len);
+    for (int64_t i = 0; i < len; ++i) hr.offer(scores[beg + i], tags[beg + i]);
+    out_n[q] = hr.finish(out_tag + q * k, out_score + q * k);
+  });
+}
+
 }  // namespace bbq
 
 // offers the entries of one list to the heap; false at the first row that does not ascend (*prev: the last row offered, -1 none)
@@ -108,14 +130,6 @@ static bool offer_ascending(bbq::HeapReplay &h, const bbq_cand *l, int64_t n, in
     h.offer(bbq::entry_score(l[j]), (int32_t)row);
   }
   return true;
-}
-
-// work(lo, hi) over [0, n) on T threads (T <= 1: on this one)
-template <class F> static void run_split(int T, int32_t n, F &work) {
-  if (T <= 1) return work(0, n);
-  std::vector<std::thread> th;
-  for (int t = 0; t < T; ++t) th.emplace_back(work, (int32_t)((int64_t)n * t / T), (int32_t)((int64_t)n * (t + 1) / T));
-  for (auto &x : th) x.join();
 }
 
 extern "C" {
@@ -149,18 +163,13 @@ int bbq_replay_batch(int32_t n_sources, const bbq_cand *const *packed, const int
   if (k == 0 || n_queries == 0) return BBQ_OK;
   if (!out_idx || !out_score) return bbq::fail(BBQ_ERR_INVALID_ARG, "bbq_replay_batch: null output");
   std::vector<int> bad((size_t)n_queries, 0);
-  auto work = [&](int32_t lo, int32_t hi) {
-    for (int32_t q = lo; q < hi; ++q) {
-      bbq::HeapReplay h(k, n_total);
-      int64_t prev = -1;
-      for (int32_t s = 0; s < n_sources && !bad[(size_t)q]; ++s)
-        if (!offer_ascending(h, packed[s] + offsets[s][q], offsets[s][q + 1] - offsets[s][q], &prev)) bad[(size_t)q] = 1;
-      out_n[q] = h.finish(out_idx + (int64_t)q * k, out_score + (int64_t)q * k);
-    }
-  };
-  int T = n_threads > 0 ? n_threads : 1;
-  if (T > n_queries) T = n_queries;
-  run_split(T, n_queries, work);
+  bbq::for_each_index(n_threads, n_queries, [&](int64_t q) {
+    bbq::HeapReplay h(k, n_total);
+    int64_t prev = -1;
+    for (int32_t s = 0; s < n_sources && !bad[(size_t)q]; ++s)
+      if (!offer_ascending(h, packed[s] + offsets[s][q], offsets[s][q + 1] - offsets[s][q], &prev)) bad[(size_t)q] = 1;
+    out_n[q] = h.finish(out_idx + q * k, out_score + q * k);
+  });
   for (int32_t q = 0; q < n_queries; ++q)
     if (bad[(size_t)q]) return bbq::fail(BBQ_ERR_INVALID_ARG, "bbq_replay_batch: candidates of query %d not in ascending row order", q);
   return BBQ_OK;
@@ -234,7 +243,7 @@ int bbq_merge_answers(int32_t n_sources, const uint64_t *const *answers, const i
   };
   int T = n_threads > 0 ? n_threads : 1;
   if (T > n_queries / 64) T = std::max(1, n_queries / 64);  // a query merges in a few microseconds: threads only pay for large batches
-  run_split(T, n_queries, work);
+  bbq::for_each_index(T, T, [&](int64_t t) { work((int32_t)((int64_t)n_queries * t / T), (int32_t)((int64_t)n_queries * (t + 1) / T)); });  // a piece per thread: its scratch is made once
   for (int32_t q = 0; q < n_queries; ++q)
     if (bad[(size_t)q]) return bbq::fail(BBQ_ERR_INVALID_ARG, "bbq_merge_answers: query %d: an answer block claims more entries than its stride holds", q);
   return BBQ_OK;

@@ -1,6 +1,7 @@
 // bbq_search.h - what the search-side translation units share on top of bbq_host.h: the one object of a call, and the functions
 // that cross a file boundary (their comments stand at the definitions).
 #pragma once
+#include <functional>
 #include "bbq_host.h"
 
 // The accept set of a filtered search (bbq_filter.cpp): read-only after creation, so any number of calls and threads may share it.
@@ -103,6 +104,12 @@ int effective_batch(const bbq_index *ix, int64_t n_queries = 0);
 int l2_share_shift(const bbq_index *ix);
 // does a per-query sparse sweep of this index read the rows' component sums from the side array (option row_sums)?
 bool row_sums_for_launch(const bbq_index *ix);
+// the view a launch over the whole main storage gets, with that decision applied.  Context mutex held by the caller
+inline IndexView main_launch_view(bbq_index *ix) {
+  IndexView v = launch_view(ix, ix->main).view;
+  v.row_sums = row_sums_for_launch(ix) ? ix->main.view.row_sums : nullptr;
+  return v;
+}
 // does a call with `planes` bit-planes stage the digit masks for its per-query sparse sweeps (option digit_planes)?
 bool digit_planes_for_call(const bbq_index *ix, int planes);
 // tiles per wave of the per-query sparse sweeps of an index (option tiles_per_wave): what launch_scan takes
@@ -128,8 +135,45 @@ int stage_compact_map(const bbq_filter *f, DevBuf<uint32_t> &d_rank, CompactMap 
 // and the winner list (BBQ_ERR_OOM), enqueued on `s`.
 int update_winners(const int32_t *ords, int64_t n, int64_t n_rows, std::vector<int64_t> &pos);
 int stage_winners(hipStream_t s, const int32_t *ords, int64_t n, const std::vector<int64_t> &pos, DevBuf<int32_t> &d_ords, DevBuf<int64_t> &d_pos);
-// ---- bbq_group.cpp: what a group set can be made for, and searched on - a single-device root index
+// ---- bbq_select.cpp: how a sub-batch of the span, grouped and MaxSim searches ends.  The device has scored every row (representative,
+// sum) of every query into one array, selected k of them for the queries with a block, and the blocks are on the host: each block is
+// proven (prove_selected, bbq_replay.cpp) and unpacked, and the reference's heap replayed over the scores of every other query.
+struct SelectQuery {
+  int64_t len;    // its scores; 0: it answers with nothing, status 0
+  int64_t first;  // they start here in the score array; the sub-batch's scores are [0, sum of len)
+  int32_t block;  // its answer block among those brought back, or -1: the device did not select
+};
+struct SelectTail {
+  const SelectQuery *queries;
+  int nq;
+  const float *d_scores;    // the sub-batch's scores on the device ...
+  const uint32_t *d_ords;   // ... and the row (group) behind each, or null: `walk` knows them
+  const uint64_t *back;     // [blocks][out_stride] the answer blocks, on the host
+  float *h_scores;          // host room for the scores ...
+  uint32_t *h_ords;         // ... and the ords: touched only where a heap is replayed
+  int64_t k;
+  size_t out_stride;
+  hipStream_t stream;       // idle on entry and on return
+  int threads;              // option replay_threads
+  int32_t *out_tag;         // the outputs, from the sub-batch's first query on: [nq][k] out_idx or out_group, ...
+  float *out_score;
+  int64_t *out_n;
+  uint8_t *out_status;      // ... or null
+};
+// without an ord array: offers query s's rows to the heap in visiting order, scores[i] the score of the i-th
+using RowWalk = std::function<void(int64_t s, const float *scores, HeapReplay &hr)>;
+int finish_selected(const SelectTail &t, const RowWalk &walk = nullptr);
+// ---- bbq_group.cpp: what a group set can be made for, and searched on - a single-device root index; and the score pass's arguments
+// that follow from an index and a group set of it: the launch view, the set's tables, L, the chunks and the L2 share (the queries and
+// rep are the sub-batch's).  Context mutex held by the caller
 int check_group_index(const bbq_index *ix);
+GroupScoreArgs group_score_args(bbq_index *ix, const bbq_groups *gs);
+// ---- bbq_maxsim.cpp: the token block [t0, t0 + kMaxSimTokenBlock) of the sub-batch of nq queries from query q0 of the call on, staged:
+// a MaxSimQuery for every query s of the sub-batch that has the block and takes_part(s), in query order -> h_mq (*n_mq of them), and
+// its token vectors behind one another as queries of a score pass -> h_qdata (qb bytes each) / h_qparams.  Returns the vectors staged
+struct MaxSimTokens { const int64_t *voff; const uint8_t *qquant; const double *qcorr; int planes, one_bit, sim; };  // of the call
+int32_t stage_maxsim_token_block(const bbq_index *ix, const MaxSimTokens &tk, int64_t q0, int nq, int64_t t0, const std::function<bool(int)> &takes_part,
+                                 uint8_t *h_qdata, size_t qb, QueryParams *h_qparams, MaxSimQuery *h_mq, int *n_mq);
 // ---- bbq_maxsim_groups.cpp: the checks of a MaxSim call's token offsets and candidate lists, in the wording of `fn`, and the records
 // of a sub-batch's lists.  check_maxsim_cand_lists: every group of every list is a live group of gs, the first offender named, at most
 // kMaxSimCandMaxRows expanded rows a query; *longest = the longest list.  stage_maxsim_cand_records: coff = the sub-batch's first query's

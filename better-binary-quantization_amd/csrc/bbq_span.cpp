@@ -1,15 +1,14 @@
 // bbq_span.cpp - span search: bbq_search_spans_batch, bbq_search_spans_filtered_batch (kernels: bbq_span_kernels.hip).  The host checks
 // every span before the first launch, plans the call in sub-batches and allocates what the largest of them needs, then works through
 // them: stage the queries, the span tables and the work items in one copy, launch the score pass and the select pass, bring back the
-// answer blocks in one copy, sort what the device selected and replay the reference's heap over the scores of the queries it could not
-// prove.  With a row filter the same call is planned in ACCEPTED rows, counted from the filter's host copy: a query's length is the
+// answer blocks in one copy, and end as every select-pass search does (finish_selected, bbq_select.cpp): what the device selected is
+// proven, the reference's heap replayed over the scores of the other queries.  With a row filter the same call is planned in ACCEPTED rows, counted from the filter's host copy: a query's length is the
 // number of accepted rows in its spans, an item's `out` the position of its first accepted row among them, an item without an accepted
 // row is not staged, and the device leaves each accepted row's ord beside its score - the ords a replay offers to the heap.
 #include <string.h>
 #include <algorithm>
 #include <memory>
 #include <new>
-#include <thread>
 #include "bbq_search.h"
 
 using namespace bbq;
@@ -23,8 +22,6 @@ constexpr int kSpanMaxQueries = 1024;
 constexpr int64_t kSpanScoreBytes = 64ll << 20;
 constexpr int64_t kSpanMaxItems = 1 << 22;
 static_assert((uint64_t)kSpanMaxItems * kChunkRows <= kGridWorkItemsMax, "one score launch");
-
-inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
 
 // work items of the non-empty span [b, e): cut at kChunkRows-row steps from the start of b's tile
 inline int64_t items_of_span(int64_t b, int64_t e) { return (e - (b & ~(int64_t)(kTileRows - 1)) + kChunkRows - 1) / kChunkRows; }
@@ -177,10 +174,8 @@ int spans_locked(const char *fn, bbq_index *ix, const bbq_filter *f, int32_t n_q
     subs.push_back(b);
   }
   // everything large, before anything is written to the caller's arrays
-  {
-    const hipError_t e = ix->ctx->d_span.reserve(max_bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(BBQ_ERR_OOM, "span search: %zu bytes of scratch: %s", max_bytes, hipGetErrorString(e)); }
-  }
+  rc = reserve_scratch(ix->ctx->d_span, max_bytes, "span search");
+  if (rc != BBQ_OK) return rc;
   std::unique_ptr<uint8_t[]> head(new (std::nothrow) uint8_t[std::max<size_t>(max_head, 1)]);
   std::unique_ptr<uint64_t[]> back(new (std::nothrow) uint64_t[std::max<size_t>(max_back, 1)]);
   std::unique_ptr<float[]> h_scores(new (std::nothrow) float[(size_t)std::max<int64_t>(max_scores, 1)]);  // touched only where a heap is replayed
@@ -191,12 +186,17 @@ int spans_locked(const char *fn, bbq_index *ix, const bbq_filter *f, int32_t n_q
   uint8_t *d = ix->ctx->d_span;
   hipStream_t st = ix->ctx->aux_stream;
   SpanScoreArgs sa{};
-  sa.idx = launch_view(ix, ix->main).view;
-  sa.idx.row_sums = row_sums_for_launch(ix) ? ix->main.view.row_sums : nullptr;
+  sa.idx = main_launch_view(ix);
   sa.accept = f ? f->d_bits.get() : nullptr;
-  std::vector<int64_t> score_off, replay;  // per query of the sub-batch: where its scores start; the queries whose heap the host replays
-  std::vector<int32_t> sel_slot;           // per query of the sub-batch: its block among the selected, or -1
-  std::vector<uint64_t> ent;
+  std::vector<SelectQuery> sq;  // per query of the sub-batch: its rows, where its scores start, its block among the selected or -1
+  SelectTail t{};
+  t.back = back.get();
+  t.h_scores = h_scores.get();
+  t.h_ords = h_ords.get();
+  t.k = k;
+  t.out_stride = out_stride;
+  t.stream = st;
+  t.threads = ix->opt_replay_threads;
 
   acc = f ? cut_acc.data() : nullptr;
   for (const SubBatch &b : subs) {
@@ -204,19 +204,15 @@ int spans_locked(const char *fn, bbq_index *ix, const bbq_filter *f, int32_t n_q
     SpanQuery *h_sel = reinterpret_cast<SpanQuery *>(head.get() + lo.sel);
     SpanRun *h_runs = reinterpret_cast<SpanRun *>(head.get() + lo.runs);
     SpanItem *h_items = reinterpret_cast<SpanItem *>(head.get() + lo.items);
-    score_off.assign((size_t)b.nq, 0);
-    sel_slot.assign((size_t)b.nq, -1);
+    sq.resize((size_t)b.nq);
     int64_t n_items = 0, n_runs = 0, n_sel = 0, n_scores = 0;
     for (int s = 0; s < b.nq; ++s) {
       const int64_t q = b.q0 + s, L = len[(size_t)q];
       fill_query(ix, head.get() + lo.qdata + (size_t)s * qb, reinterpret_cast<QueryParams *>(head.get() + lo.qparams) + s,
                  qquant + (size_t)q * ix->geom.dim, qcorr + (size_t)q * 4, planes, one_bit, sim);
-      score_off[(size_t)s] = n_scores;
       const bool sel = selected(L, k);
-      if (sel) {
-        sel_slot[(size_t)s] = (int32_t)n_sel;
-        h_sel[n_sel++] = SpanQuery{n_scores, L, n_runs, 0, 0};
-      }
+      sq[(size_t)s] = SelectQuery{L, n_scores, sel ? (int32_t)n_sel : -1};
+      if (sel) h_sel[n_sel++] = SpanQuery{n_scores, L, n_runs, 0, 0};
       int64_t pos = 0;  // of the next item's first visited row in the query's (filtered: compacted) visiting order
       for (int64_t j = off[q]; j < off[q + 1]; ++j) {
         const int64_t sb = spans[2 * j], se = spans[2 * j + 1];
@@ -258,74 +254,20 @@ int spans_locked(const char *fn, bbq_index *ix, const bbq_filter *f, int32_t n_q
       HIPCHK(hipStreamSynchronize(st));  // also: the staging is free for the next sub-batch
     }
 
-    // what the device selected: exactly k rows above the cut and no NaN - sorted by descending score; two equal scores among them, or
-    // one equal to the cut, and the heap's history decides: replayed like the queries the device could not prove
-    replay.clear();
-    for (int s = 0; s < b.nq; ++s) {
-      const int64_t q = b.q0 + s, L = len[(size_t)q];
-      if (L == 0) {
-        out_n[q] = 0;
-        if (out_status) out_status[q] = 0;
-        continue;
-      }
-      bool proven = false;
-      if (sel_slot[(size_t)s] >= 0) {
-        const uint64_t *blk = back.get() + (size_t)sel_slot[(size_t)s] * out_stride;
-        if ((uint32_t)(blk[0] >> 32) == 0u && (int64_t)(uint32_t)blk[0] == k) {
-          ent.assign(blk + 2, blk + 2 + k);
-          std::sort(ent.begin(), ent.end(), [](uint64_t x, uint64_t y) { return entry_score(x) > entry_score(y); });
-          proven = entry_score(ent[(size_t)k - 1]) != entry_score(blk[1]);
-          for (int64_t i = 1; proven && i < k; ++i) proven = entry_score(ent[(size_t)i - 1]) != entry_score(ent[(size_t)i]);
-          if (proven) {
-            unpack_entries(ent.data(), k, out_idx + q * k, out_score + q * k);
-            out_n[q] = k;
-          }
-        }
-      }
-      if (out_status) out_status[q] = proven ? 0 : 1;
-      if (!proven) replay.push_back(s);
-    }
-    if (replay.empty()) continue;
-
-    // the reference loop (src/binaryQuantizationFormat.ts:383-411) over the query's rows in visiting order: the literal heap of min(k, rows)
-    // (their scores - and ords - come back query by query, or in one copy where they are at least half of the sub-batch's: a filter
-    // that leaves a query no more than k rows does so for most queries of a call, and a copy costs more than its few hundred bytes)
-    int64_t replay_rows = 0;
-    for (int64_t s : replay) replay_rows += len[(size_t)(b.q0 + s)];
-    auto bring_back = [&](int64_t first, int64_t rows) {
-      hipError_t e = hipMemcpyAsync(h_scores.get() + first, d + lo.scores + (size_t)first * 4, (size_t)rows * 4, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess && f) e = hipMemcpyAsync(h_ords.get() + first, d + lo.ords + (size_t)first * 4, (size_t)rows * 4, hipMemcpyDeviceToHost, st);
-      return e;
-    };
-    if (2 * replay_rows >= n_scores) {
-      HIPCHK(bring_back(0, n_scores));
-    } else {
-      for (int64_t s : replay) HIPCHK(bring_back(score_off[(size_t)s], len[(size_t)(b.q0 + s)]));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    auto work = [&](size_t t, size_t T) {
-      for (size_t i = t; i < replay.size(); i += T) {
-        const int64_t s = replay[i], q = b.q0 + s;
-        const float *sc = h_scores.get() + score_off[(size_t)s];
-        HeapReplay hr(k, len[(size_t)q]);
-        if (f) {  // the accepted rows as the device wrote them: what it wrote is what is checked
-          const uint32_t *od = h_ords.get() + score_off[(size_t)s];
-          for (int64_t r = 0; r < len[(size_t)q]; ++r) hr.offer(sc[r], (int32_t)od[r]);
-        } else {
-          for (int64_t j = off[q]; j < off[q + 1]; ++j)
-            for (int64_t r = spans[2 * j]; r < spans[2 * j + 1]; ++r) hr.offer(*sc++, (int32_t)r);
-        }
-        out_n[q] = hr.finish(out_idx + q * k, out_score + q * k);
-      }
-    };
-    const size_t T = std::min<size_t>((size_t)std::max(ix->opt_replay_threads, 1), replay.size());
-    if (T <= 1 || replay_rows < 4096) {
-      work(0, 1);
-    } else {
-      std::vector<std::thread> th;
-      for (size_t t = 0; t < T; ++t) th.emplace_back(work, t, T);
-      for (std::thread &x : th) x.join();
-    }
+    // what the device selected is proven or replayed (bbq_select.cpp); without a filter the rows of a replayed query are its spans
+    t.queries = sq.data();
+    t.nq = b.nq;
+    t.d_scores = sa.scores;
+    t.d_ords = sa.ords;
+    t.out_tag = out_idx + b.q0 * k;
+    t.out_score = out_score + b.q0 * k;
+    t.out_n = out_n + b.q0;
+    t.out_status = out_status ? out_status + b.q0 : nullptr;
+    rc = finish_selected(t, [&](int64_t s, const float *sc, HeapReplay &hr) {
+      for (int64_t j = off[b.q0 + s]; j < off[b.q0 + s + 1]; ++j)
+        for (int64_t r = spans[2 * j]; r < spans[2 * j + 1]; ++r) hr.offer(*sc++, (int32_t)r);
+    });
+    if (rc != BBQ_OK) return rc;
   }
   return BBQ_OK;
 }

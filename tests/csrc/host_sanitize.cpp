@@ -1,5 +1,6 @@
 // Exercises the host-only part of libbbq (quantizer, heap replay, error plumbing: bbq_quantizer.cpp + bbq_replay.cpp, no HIP) through
-// the C ABI; built by tests/test_sanitizers_cpu.py with -fsanitize=address,undefined and with -fsanitize=thread.  GPU sanitizers are
+// the C ABI and, for what has no entry point of its own - the proof of a selected answer block, the thread fan-out, the list-order
+// replay - through bbq_internal.h; built by tests/test_sanitizers_cpu.py with -fsanitize=address,undefined and with -fsanitize=thread.  GPU sanitizers are
 // not available on this pool, so this is where memory and thread errors of the host code are looked for.
 #include <math.h>
 #include <stdint.h>
@@ -8,6 +9,7 @@
 #include <string.h>
 #include <vector>
 #include "../../include/bbq.h"
+#include "../../better-binary-quantization_amd/csrc/bbq_internal.h"  // the host-only internals next to HeapReplay: prove_selected, for_each_index, replay_lists
 
 static uint32_t rng_state = 12345;
 static float frand() {
@@ -106,6 +108,78 @@ int main() {
     int64_t n1 = 0;
     CHECK(bbq_replay(1, pp, nullptr, n_total, 5, nullptr, nullptr, &n1) == BBQ_ERR_INVALID_ARG);
     CHECK(bbq_replay_batch(S, pp, po, Q, n_total, -1, 2, nullptr, nullptr, nullptr) != BBQ_OK);
+  }
+  {  // the proof of one answer block of the select pass: {above the cut | NaN seen << 32}, the cut, then the entries
+    auto entry = [](uint32_t row, float score) {
+      uint32_t b;
+      memcpy(&b, &score, 4);
+      return ((uint64_t)row << 32) | b;
+    };
+    auto block = [&](uint32_t count, uint32_t nan_seen, float cut, std::vector<float> scores) {
+      std::vector<uint64_t> blk = {(uint64_t)count | ((uint64_t)nan_seen << 32), entry(0, cut)};
+      for (size_t i = 0; i < scores.size(); ++i) blk.push_back(entry(100 + (uint32_t)i, scores[i]));
+      return blk;
+    };
+    std::vector<uint64_t> ent;
+    int32_t rows[4];
+    float sc[4];
+    const std::vector<uint64_t> clean = block(4, 0, 0.5f, {2.f, 9.f, 1.f, 4.f});  // k distinct scores above the cut, unsorted
+    CHECK(bbq::prove_selected(clean.data(), 4, ent) && ent.size() == 4);
+    bbq::unpack_entries(ent.data(), 4, rows, sc);
+    CHECK(rows[0] == 101 && rows[1] == 103 && rows[2] == 100 && rows[3] == 102);
+    CHECK(sc[0] == 9.f && sc[1] == 4.f && sc[2] == 2.f && sc[3] == 1.f);
+    CHECK(!bbq::prove_selected(block(4, 1, 0.5f, {2.f, 9.f, 1.f, 4.f}).data(), 4, ent));  // the NaN word
+    CHECK(!bbq::prove_selected(block(3, 0, 0.5f, {2.f, 9.f, 1.f, 4.f}).data(), 4, ent));  // a count other than k: fewer ...
+    CHECK(!bbq::prove_selected(block(5, 0, 0.5f, {2.f, 9.f, 1.f, 4.f}).data(), 4, ent));  // ... and more
+    CHECK(!bbq::prove_selected(block(4, 0, 0.5f, {2.f, 9.f, 2.f, 4.f}).data(), 4, ent));  // two equal neighbours once sorted
+    CHECK(!bbq::prove_selected(block(4, 0, 0.f, {2.f, 9.f, -0.f, 4.f}).data(), 4, ent));  // the k-th equals the cut (+0.0 == -0.0)
+    CHECK(!bbq::prove_selected(block(4, 0, 1.f, {2.f, 9.f, 1.f, 4.f}).data(), 4, ent));   // the same, bit for bit
+    const std::vector<uint64_t> one = block(1, 0, 3.f, {7.f});  // k = 1
+    CHECK(bbq::prove_selected(one.data(), 1, ent) && ent.size() == 1);
+    bbq::unpack_entries(ent.data(), 1, rows, sc);
+    CHECK(rows[0] == 100 && sc[0] == 7.f);
+    CHECK(!bbq::prove_selected(block(1, 0, 7.f, {7.f}).data(), 1, ent));
+  }
+  {  // the fan-out: every index exactly once, whatever the thread count - one thread, four, more threads than indices, none
+    for (int T : {1, 4, 0})
+      for (int64_t n : {(int64_t)0, (int64_t)1, (int64_t)3, (int64_t)1000}) {  // n = 3 < T = 4
+        std::vector<int> hits((size_t)n, 0);
+        bbq::for_each_index(T, n, [&](int64_t i) { ++hits[(size_t)i]; });
+        for (int h : hits) CHECK(h == 1);
+      }
+  }
+  {  // the list-order replay: on one thread and on four, below and above its thread threshold, the same answers as bbq_replay's heap
+    const int Q = 9;
+    const int64_t k = 5;
+    for (int64_t len : {(int64_t)7, (int64_t)700}) {
+      std::vector<int64_t> off = {0};
+      std::vector<int32_t> tags;
+      std::vector<float> scores;
+      for (int q = 0; q < Q; ++q) {
+        for (int64_t i = 0; i < (q == 4 ? 0 : len + q); ++i) {  // list 4 is empty
+          tags.push_back((int32_t)((i * 37 + q) % 1000));   // not ascending: the order given is the order offered
+          scores.push_back((float)((i * 31 + q * 17) % 23) * 0.125f);
+        }
+        off.push_back((int64_t)tags.size());
+      }
+      std::vector<int32_t> t1((size_t)(Q * k), -1), t4((size_t)(Q * k), -1);
+      std::vector<float> s1((size_t)(Q * k), -1.f), s4((size_t)(Q * k), -1.f);
+      std::vector<int64_t> n1((size_t)Q, -1), n4((size_t)Q, -1);
+      bbq::replay_lists(Q, off.data(), tags.data(), scores.data(), k, 1, t1.data(), s1.data(), n1.data());
+      bbq::replay_lists(Q, off.data(), tags.data(), scores.data(), k, 4, t4.data(), s4.data(), n4.data());
+      CHECK(t1 == t4 && s1 == s4 && n1 == n4 && n1[4] == 0 && n1[0] == k);
+      for (int q = 0; q < Q; ++q) {
+        bbq::HeapReplay hr(k, off[(size_t)q + 1] - off[(size_t)q]);
+        for (int64_t i = off[(size_t)q]; i < off[(size_t)q + 1]; ++i) hr.offer(scores[(size_t)i], tags[(size_t)i]);
+        int32_t ht[5];
+        float hs[5];
+        CHECK(hr.finish(ht, hs) == n1[(size_t)q]);
+        CHECK(memcmp(ht, t1.data() + q * k, (size_t)n1[(size_t)q] * 4) == 0 && memcmp(hs, s1.data() + q * k, (size_t)n1[(size_t)q] * 4) == 0);
+      }
+      std::vector<int64_t> n0((size_t)Q, -1);
+      bbq::replay_lists(Q, off.data(), tags.data(), scores.data(), 0, 4, nullptr, nullptr, n0.data());  // k = 0 answers nothing
+      for (int64_t c : n0) CHECK(c == 0);
+    }
   }
   printf("host sanitize ok\n");
   return 0;
