@@ -5,7 +5,8 @@ operations.
 Dominance: a row whose exact f32 score beats a threshold must pass the bound against that threshold's z image - checked for every
 row against the threshold ONE KEY below its own score, over hostile magnitudes, all similarities, 1-bit and multi-bit rows, with the
 fused multiply-adds evaluated fused and unfused, and with the z image one ulp lower.  Rows whose score is +0 are left out: one key
-below +0 is -0.0, and a threshold is always the key of a real score, or 0.
+below +0 is -0.0, and a threshold is always the key of a real score, or 0.  (True of the sweep.  A range search's key comes from any
+f32 the caller likes: tests/test_range_hostile_cpu.py covers those keys, +0 rows included.)
 Tightness: on the benchmark's distributions the f32 bound passes at most 1.25 x the rows the f64 bound passes, + 2."""
 import functools
 
@@ -79,10 +80,13 @@ def bits_of_key(k):
     return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32)
 
 
-def z_image(key, qadd, cdp, sim, plain):
-    """z_threshold_f32 for an array of keys: z_threshold in f64, rounded down to f32 (-inf accepts everything)"""
+NEG = -np.finfo(np.float64).max
+
+
+def z_f64(key, qadd, cdp, sim, plain):
+    """z_threshold for an array of keys - any keys, the NaN patterns a range key of -inf is included: the conservative lower edge in
+    z-space of "score > the float of the key", in f64 (-DBL_MAX accepts everything)"""
     key = np.asarray(key, np.uint32)
-    NEG = -np.finfo(np.float64).max
     with np.errstate(all="ignore"):
         th = bits_of_key(key).view(F32).astype(np.float64)
         if sim == 1:
@@ -94,7 +98,13 @@ def z_image(key, qadd, cdp, sim, plain):
         else:
             z = np.where(th > 0.0, qadd + 1.0 - 1.0 / th, NEG)
         z = np.where((key == 0) | np.isnan(th) | ~(np.abs(z) <= -NEG), NEG, z)
-        z = np.where(z == NEG, NEG, z - 1e-9 * (np.abs(z) + abs(qadd) + abs(cdp) + 1.0))
+        return np.where(z == NEG, NEG, z - 1e-9 * (np.abs(z) + abs(qadd) + abs(cdp) + 1.0))
+
+
+def z_image(key, qadd, cdp, sim, plain):
+    """z_threshold_f32 for an array of keys: z_threshold in f64, rounded down to f32 (-inf accepts everything)"""
+    z = z_f64(key, qadd, cdp, sim, plain)
+    with np.errstate(all="ignore"):
         zf = z.astype(F32)
         return np.where(zf.astype(np.float64) > z, np.nextafter(zf, F32(-np.inf)), zf).astype(F32)
 
