@@ -189,7 +189,7 @@ def tiles_per_wave_of(m, option=-1):
 
 
 def latency_supported(m):
-    """latency_path_supported (bbq_latency_kernels.hip) for a query of 4 planes: kLatPlaneMax = 48 is not reached at these widths"""
+    """latency_path_supported (bbq_latency_kernels.hip) for a query of 4 planes: kLatPlaneMax = 96 is not reached at these widths"""
     return m.ib == 1 and w16_of(m.dim) in LATENCY_W16
 
 
