@@ -385,8 +385,9 @@ struct FinalizeArgs {
   uint64_t seq;
   // Shard mode (bbq_shard_scan_begin's dev_answers, include/bbq.h): this storage is one row shard of a larger index and the running top
   // keys may include rows of a pilot replica, so the launch cannot prove an answer by itself.  It leaves what the merge needs instead:
-  // slot 1 = {m, unproven}, slot 2 = the cut = the (k2 + 1)-th largest key over every row this shard has seen (0: it has seen at most
-  // k2), then the m <= k2 listed rows above the cut, descending by score.  No tie check here: the merge checks the global answer.
+  // slot 1 = {m, unproven}, slot 2 = the cut: at most the (k2 + 1)-th largest key of the rows this shard has seen, equal to it unless an
+  // earlier segment overflowed the key buffer (m_use < m_new: the running top keys are a subset's); 0: it has seen at most k2.  Then the
+  // m <= k2 listed rows above the cut, descending by score.  No tie check here: the merge checks the global answer.
   int32_t final_shard;
 };
 constexpr int kFinalSelectMax = 1024;  // largest k2 the finalize kernel selects and sorts itself

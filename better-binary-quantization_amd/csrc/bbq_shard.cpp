@@ -48,7 +48,8 @@ int bbq_shard_scan_begin(bbq_index *ix, int32_t n_queries, const uint8_t *qquant
   if (ix->shard_begun - ix->shard_waited >= 2) return fail(BBQ_ERR_INVALID_ARG, "bbq_shard_scan_begin: two batches are already in flight on this index (wait for one first)");
   SearchCall c(ix, qquant, qcorr, planes_of_call(ix, qquant, (int64_t)n_queries * ix->geom.dim, query_bits == 1), query_bits, sim, k);
   // with answers the shard runs with rank k + 1, like the single index does: its last finalize launch then knows the (k + 1)-th largest
-  // key of everything it has seen (the cut) and the rows above it.  Lists for rank k + 1 are supersets of the lists for rank k.
+  // key of everything it has seen (the cut) and the rows above it.  Lists for rank k + 1 are supersets of the lists for rank k where
+  // both ranks plan the same segments (4 k and 4 (k + 1) can round to different first segments); either list replays to the same answer.
   const bool answers = dev_answers != nullptr;
   c.k_dev = answers ? k + 1 : k;
   const Plan plan = build_plan(ix, c.k_dev, answers ? k : 0);

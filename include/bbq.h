@@ -615,13 +615,16 @@ int bbq_shard_scan(bbq_index *idx, int32_t n_queries, const uint8_t *qquant, con
  *                   Per query:
  *       [0]  entries in the packed list | flags << 32
  *       [1]  m = number of answer entries | unproven << 32   (unproven != 0: flags, or more keys than the launch can select among - take the packed list)
- *       [2]  cut: the monotone key (bbq_key_of_score) of the (k+1)-th largest f32 score among ALL rows this shard has seen - its own
- *            and its pilot replica's -, 0 when it has seen at most k rows
+ *       [2]  cut: a monotone key (bbq_key_of_score), at most that of the (k+1)-th largest f32 score among ALL rows this shard has seen -
+ *            its own and its pilot replica's - and equal to it unless an earlier segment overflowed the key buffer (a flood: the
+ *            running top keys are then those of the entries that fitted, a subset of the rows seen; more than k own rows can lie above
+ *            such a cut, and the block is then left unproven); 0 when the shard has seen at most k rows
  *       [3 .. 3+m)  the shard's OWN rows whose score key is above the cut, (row << 32 | f32 bits), descending by score (m <= k)
- *   The cut never exceeds the key of the global (k+1)-th largest score (it is an order statistic of a subset of the rows), so the
- *   union of all shards' answer entries contains every row above max(cut): bbq_merge_answers selects the global answer from them and
- *   proves it (DESIGN.md "Exact top-k": when no two of the k+1 largest scores compare equal the reference heap returns exactly the
- *   k best rows in descending order, whatever its history); only for a query it cannot prove are the packed lists needed (heap replay).
+ *   The cut never exceeds the key of the global (k+1)-th largest score (it is an order statistic of a subset of the rows) and a proven
+ *   block holds every own row above its cut, so the union of all shards' answer entries contains every row above max(cut):
+ *   bbq_merge_answers selects the global answer from them and proves it (DESIGN.md "Exact top-k": when no two of the k+1 largest
+ *   scores compare equal the reference heap returns exactly the k best rows in descending order, whatever its history); only for a
+ *   query it cannot prove are the packed lists needed (heap replay).
  *   What travels per shard and query is (k + 3) x 8 bytes instead of the ~1.1 K-entry list.
  */
 int bbq_shard_scan_begin(bbq_index *idx, int32_t n_queries, const uint8_t *qquant, const double *qcorr,

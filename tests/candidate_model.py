@@ -25,7 +25,8 @@ Rules the model takes from the source where the source says otherwise than one w
 
 The model REFUSES (Refused) what is not a function of the scores alone: a segment that is not the last and brings more new keys than the
 finalize kernel's LDS holds beside the running top keys ("m_use = min(m_new, kFinalizeKeyCap - tcount)": the threshold is then taken over
-the entries that fit - in append mode whichever arrived first), an index with a pilot replica, a multi-device handle."""
+the entries that fit - in append mode whichever arrived first).  An index with a pilot replica and a multi-device handle are not this
+model's either: tests/shard_model.py models a row shard's scan - its lists, its cut and its answer block - and the handle built on it."""
 import collections
 import functools
 
@@ -285,6 +286,11 @@ def rows(fam, kind):
     for a in (codes, corr):
         a.setflags(write=False)
     return codes, corr
+
+
+def ordinary_rows(fam, n, salt=0):
+    """(codes, corr) of n ordinary rows of the family's shape under its seed + salt: for a recipe that needs more rows than the family has"""
+    return H._ordinary(_seed(fam) + salt, n, fam._replace(n=n))
 
 
 def score(fam, codes, corr, qq, qc, sim, query_bits=None):

@@ -9,25 +9,12 @@ import pytest
 
 import orclib as O
 from bbqlib import capi as B
+from shard_model import shard_block      # the numpy block lives with the model tests/test_gpu_shard_model.py holds the device's to
 
 
 def key_of(s32):
     b = s32.view(np.uint32).astype(np.int64)
     return np.where(b & 0x80000000, (~b) & 0xFFFFFFFF, b | 0x80000000)
-
-
-def shard_block(s32, keys, r0, r1, pilot, k, stride):
-    blk = np.zeros(stride, np.uint64)
-    seen = np.unique(np.concatenate([np.arange(0, pilot if r0 > 0 else 0), np.arange(r0, r1)])).astype(np.int64)
-    ks = np.sort(keys[seen])[::-1]
-    cut = int(ks[k]) if len(ks) >= k + 1 else 0
-    own = np.arange(r0, r1)
-    own = own[keys[own] > cut]
-    own = own[np.argsort(-keys[own], kind="stable")]
-    assert len(own) <= k
-    blk[1], blk[2] = len(own), cut
-    blk[3:3 + len(own)] = (own.astype(np.uint64) << np.uint64(32)) | s32[own].view(np.uint32).astype(np.uint64)
-    return blk
 
 
 def run_case(rng, n, k, shards, pilot, levels):
