@@ -657,6 +657,53 @@ struct MaxSimTrueAccArgs {
   int64_t stride;
 };
 
+// Exact search (bbq_exact_kernels.hip): the true top-k of a block of independent raw queries over the CONTIGUOUS fp32 rows of a
+// bbq_vectors, a slab of rows at a time.  The score pass is the exact MaxSim rerank's chain with the row known from the lane: a wave is
+// the 64 rows of one accept word, a workgroup runs them against one block of up to kExactQueryBlock queries and leaves
+// keys[query][row - row0] = true_key of c(query, row), 0 for a row the filter rejects; a wave without an accepted row loads and writes
+// nothing.  The queries are staged as MaxSimRerankArgs::tokens are: block b's slots start at b * kExactQueryBlock, its tp = its query
+// count rounded up to kMaxSimRerankTokenGroup, query t of the block at column j is queries[b * kExactQueryBlock * dim + j * tp + t],
+// na[b * kExactQueryBlock + t] its squared norm.  The select pass keeps per query the best kk (key, row) pairs seen so far, sorted by
+// key descending and row ascending - a strict order, so the list is the answer - and folds a slab into it: a key is looked at only if
+// it beats the list's last key (every row of a later slab is behind every listed row, so an equal key loses), what passes is merged in
+// by sorting list and candidates together.  It reads the accept word itself and never a key the score pass did not write.
+constexpr int kExactQueryBlock = 32;
+constexpr int kExactSelectThreads = 1024;
+constexpr int kExactSelectMax = 4096;                     // largest kk the select pass takes
+constexpr int kExactSelectSlots = 2 * kExactSelectMax;    // (key, row) pairs it sorts at a time: the list and a tile of candidates
+constexpr int kExactSelectTile = 4 * kExactSelectThreads; // rows it tests between two barriers: four consecutive keys a thread
+constexpr int kExactSelectLdsBytes = kExactSelectSlots * 12;
+struct ExactScoreArgs {
+  const float *vecs;              // [n][dim] the fp32 rows, row-major
+  const double *queries;          // the sub-batch's queries, as above; 16-byte aligned
+  const double *na;               // [slots]; read for COSINE only
+  const uint64_t *accept;         // the accept words of a filter (word t = rows 64 t .. 64 t + 63); null: every row
+  unsigned long long *keys;       // [sub-batch's queries][stride]
+  int64_t n;                      // rows in use
+  int64_t row0;                   // the slab's first row, a multiple of 64
+  int64_t stride;                 // slab rows the key rows are long
+  int32_t n_queries;              // of the sub-batch
+  int32_t dim;
+  int32_t sim;                    // 0 EUCLIDEAN, 1 COSINE, 2 MAXIMUM_INNER_PRODUCT
+  int32_t pad;
+};
+struct ExactSelectArgs {
+  const unsigned long long *keys; // [grid.x][stride]
+  const uint64_t *accept;         // as ExactScoreArgs::accept
+  unsigned long long *list_keys;  // [grid.x][kk] the running lists, best first
+  int32_t *list_rows;             // [grid.x][kk]
+  int32_t *list_count;            // [grid.x] cleared before the first slab
+  int64_t n, row0, stride;        // as ExactScoreArgs'
+  int32_t rows;                   // rows of this slab: [row0, row0 + rows), rows <= stride, row0 + rows <= n rounded up to 64
+  int32_t kk;                     // 1 .. kExactSelectMax
+};
+// the accept word of the 64 rows from row w * 64 on: the filter's, or every row below n
+__host__ __device__ inline unsigned long long exact_accept_word(const uint64_t *accept, int64_t n, int64_t w) {
+  if (accept) return accept[w];
+  const int64_t left = n - w * 64;
+  return left >= 64 ? ~0ull : left <= 0 ? 0ull : (1ull << left) - 1ull;
+}
+
 constexpr int kFinalizeThreads = 1024;
 constexpr int kFinalizeJobs = 4096;     // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)
 constexpr int kFinalizeKeyCap = 12288;   // LDS key buffer of the finalize kernel (new keys + running top-k)

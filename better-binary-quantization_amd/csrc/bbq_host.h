@@ -18,6 +18,7 @@
 //   bbq_select.cpp   what the three above end with: the device's selected answers proven, the rest replayed on the host (finish_selected)
 //   bbq_maxsim_groups.cpp, bbq_maxsim_rerank.cpp   MaxSim over chosen groups, quantized and exact (bbq_*_maxsim_groups_batch, bbq_search_maxsim_rerank_batch)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
+//   bbq_exact.cpp    exact search over the fp32 rows (bbq_true_topk, bbq_vectors_search_batch, bbq_vectors_set_option)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
 // bbq_entry.h is the codec of the 64-bit entries, keys and answer headers; bbq_workqueue.h the host threads' job queue.
 // HIP memory and events are held in the owning types of bbq_mem.h: what a struct below owns goes with it.

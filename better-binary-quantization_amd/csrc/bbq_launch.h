@@ -1,7 +1,8 @@
 // bbq_launch.h - host-callable launch wrappers of every kernel file: the sweeps, finalize and pack (bbq_kernels.hip, bbq_filter_kernels.hip,
 // bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip), the rerank (bbq_rerank_kernels.hip), the scoring of chosen rows (bbq_gather_kernels.hip)
 // the range search (bbq_range_kernels.hip), the span search (bbq_span_kernels.hip), the grouped search (bbq_group_kernels.hip), the MaxSim
-// search (bbq_maxsim_kernels.hip), MaxSim over chosen groups (bbq_maxsim_cand_kernels.hip) and the exact MaxSim rerank (bbq_maxsim_rerank_kernels.hip)
+// search (bbq_maxsim_kernels.hip), MaxSim over chosen groups (bbq_maxsim_cand_kernels.hip), the exact MaxSim rerank (bbq_maxsim_rerank_kernels.hip) and the
+// exact search (bbq_exact_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbq_device.h"
@@ -129,6 +130,11 @@ hipError_t launch_maxsim_cand_score(const MaxSimCandArgs &a, int planes, int n_q
 hipError_t launch_maxsim_rerank_score(const MaxSimRerankArgs &a, int n_queries, int64_t longest, hipStream_t s);
 // its accumulate pass for the same entries of a.queries
 hipError_t launch_maxsim_true_accumulate(const MaxSimTrueAccArgs &a, int n_queries, hipStream_t s);
+// exact search (bbq_exact_kernels.hip).  The score pass of one slab: the rows [a.row0, a.row0 + rows) against every query block of the
+// sub-batch -> a.keys; rows a multiple of 64 unless the slab is the last
+hipError_t launch_exact_score(const ExactScoreArgs &a, int64_t rows, hipStream_t s);
+// its select pass: the slab folded into the running list of each of the n_queries queries
+hipError_t launch_exact_select(const ExactSelectArgs &a, int n_queries, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 // staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place

@@ -45,6 +45,11 @@ struct bbq_vectors {
   bbq::DevBuf<int64_t> d_off;
   bbq::DevBuf<int32_t> d_rows;
   bbq::DevBuf<double> d_out;
+  // grow-only staging for bbq_vectors_search_batch (bbq_exact.cpp): a sub-batch's queries, running lists and slab keys on the device,
+  // the staged queries and the returned lists on the host
+  bbq::DevBuf<uint8_t> d_exact;
+  bbq::PinnedBuf<uint8_t> h_exact_in, h_exact_out;
+  int64_t opt_exact_slab_rows = 0;  // rows scored between two select passes; 0: what the scratch budget gives (bbq_exact.cpp)
 };
 
 #pragma GCC visibility push(hidden)  // internal: none of this joins the library's dynamic symbols

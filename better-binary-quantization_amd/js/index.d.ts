@@ -134,6 +134,10 @@ export declare class DeviceVectors {
   update(ords: Int32Array | number[], vectors: Float32Array[]): DeviceVectors;
   /** extension: the fp32 rows follow BinaryQuantizationFormat.compactVectors: the rows `filter` accepts are kept, in order, on the device */
   compact(filter: RowFilter): DeviceVectors;
+  /** extension: the exact top-k of every raw query over the resident rows (those `filter` accepts), scored in f64 and selected on the device: descending, equal scores by ascending row, a NaN last (bbq_vectors_search_batch); default COSINE */
+  trueTopK(queries: Float32Array[], k: number, similarityFunction?: VectorSimilarityFunction, filter?: RowFilter | null): Array<Array<{ index: number; trueScore: number }>>;
+  /** extension: 'exact_slab_rows', the rows trueTopK scores between two select passes (0: automatic); never changes an answer */
+  setOption(name: string, value: number): DeviceVectors;
   dispose(): void;
 }
 export declare function createDeviceVectors(vectors: Float32Array[], device?: number): DeviceVectors;
@@ -156,6 +160,8 @@ export declare class RowGroups {
 export declare function createRowGroups(targetVectors: BinarizedByteVectorValues, offsets: number[] | Float64Array, filter?: RowFilter | null): RowGroups;
 export declare function getOversampledTopKWithHeap(query: Float32Array, quantizedVectors: any, vectors: Float32Array[] | DeviceVectors, k: number, oversampleFactor: number, format: BinaryQuantizationFormat): TopKCandidate[];
 export declare function getOversampledTopKWithSort(query: Float32Array, quantizedVectors: any, vectors: Float32Array[] | DeviceVectors, k: number, oversampleFactor: number, format: BinaryQuantizationFormat): TopKCandidate[];
+/** getTrueTopK, tests/recall-common.ts:143-149: the indices of the k rows of greatest computeCosineSimilarity; with DeviceVectors every row is scored and the k best are selected on the device */
+export declare function getTrueTopK(query: Float32Array, vectors: Float32Array[] | DeviceVectors, k: number): number[];
 /** extension: the whole recipe for many queries in one native call */
 export declare function getOversampledTopKBatch(queries: Float32Array[], quantizedVectors: any, vectors: DeviceVectors, k: number, oversampleFactor: number, format: BinaryQuantizationFormat, selector?: 'heap' | 'sort'): TopKCandidate[][];
 /** extension: the exact MaxSim score of every candidate group, in list order - per token the greatest computeSimilarity among the group's accepted fp32 rows, summed in f64 in token order (bbq_rerank_maxsim_groups_batch) */

@@ -1132,6 +1132,33 @@ class DeviceVectors {
     this.length = native.vectorsCompact(this._handle(), filter._handle());
     return this;
   }
+  /**
+   * extension: the exact top-k of every raw query over the resident rows - those `filter` (createRowFilter over the same rows) accepts
+   * - scored and selected on the device (libbbq bbq_vectors_search_batch): computeSimilarity in f64 against every row, descending, equal
+   * scores by ascending row, a NaN last.  Returns one [{index, trueScore}] per query, min(k, accepted rows) long.
+   */
+  trueTopK(queries, k, similarityFunction, filter) {
+    if (!queries) throw new Error('查询向量不能为空');
+    if (!Number.isInteger(k)) throw new Error('k值必须是整数');
+    if (k < 0) throw new Error('k值不能为负数');
+    if (filter !== undefined && filter !== null && !(filter instanceof RowFilter)) throw new Error('trueTopK: the filter comes from createRowFilter(targetVectors, accept)');
+    for (let i = 0; i < queries.length; i++) {
+      if (!queries[i]) throw new Error('查询向量不能为空');
+      if (queries[i].length !== this.dim) throw new Error('向量维度不匹配');
+    }
+    const sim = similarityFunction === undefined ? 1 : simOrdinal(similarityFunction);
+    const nq = queries.length;
+    const r = native.vectorsSearchBatch(this._handle(), filter ? filter._handle() : null, nq, nq ? flatten(queries, this.dim) : new Float32Array(0), sim, k);
+    const out = [];
+    for (let i = 0; i < nq; i++) {
+      const res = [], n = r.counts[i], base = i * r.stride;
+      for (let j = 0; j < n; j++) res.push({ index: r.indices[base + j], trueScore: r.trueScores[base + j] });
+      out.push(res);
+    }
+    return out;
+  }
+  /** extension: 'exact_slab_rows', the rows trueTopK scores between two select passes; 0: automatic (libbbq bbq_vectors_set_option) */
+  setOption(name, value) { native.vectorsSetOption(this._handle(), String(name), value); return this; }
   _handle() { if (!this._h) throw new Error('向量不能为空'); return this._h; }
   dispose() { if (this._h) { native.vectorsDestroy(this._h); this._h = null; } }
 }
@@ -1238,6 +1265,18 @@ function getOversampledTopKWithSort(query, quantizedVectors, vectors, k, oversam
   const cands = rerankCandidates(query, results, vectors).filter(function (c) { return c !== null; });
   cands.sort(function (a, b) { return b.trueScore - a.trueScore; });
   return cands.slice(0, k);
+}
+
+/**
+ * getTrueTopK, tests/recall-common.ts:143-149: the indices of the k rows of greatest computeCosineSimilarity, equal scores in row order.
+ * `vectors`: createDeviceVectors(original rows) - every row is scored and the k best are selected on the device - or the reference's
+ * Float32Array[], which follows it line by line on the host.
+ */
+function getTrueTopK(query, vectors, k) {
+  if (vectors instanceof DeviceVectors) return vectors.trueTopK([query], k)[0].map(function (r) { return r.index; });
+  const scored = vectors.map(function (v, index) { return { index: index, score: computeCosineSimilarity(query, v) }; });
+  scored.sort(function (a, b) { return b.score - a.score; });
+  return scored.slice(0, k).map(function (r) { return r.index; });
 }
 
 /**
@@ -1390,7 +1429,7 @@ module.exports = Object.assign({}, require('./helpers'), {
   QUERY_BITS, INDEX_BITS, FOUR_BIT_SCALE, DEFAULT_LAMBDA, DEFAULT_ITERS,
   BinaryQuantizationFormat, OptimizedScalarQuantizer, BinaryQuantizedScorer, MinHeap,
   createBinaryQuantizationFormat, quickQuantize, quickSearch,
-  getOversampledTopKWithHeap, getOversampledTopKWithSort, getOversampledTopKBatch, computeMaxSimGroupTrueScores, getOversampledMaxSimTopK, computeCosineSimilarity,
+  getOversampledTopKWithHeap, getOversampledTopKWithSort, getTrueTopK, getOversampledTopKBatch, computeMaxSimGroupTrueScores, getOversampledMaxSimTopK, computeCosineSimilarity,
   DeviceVectors, createDeviceVectors, RowFilter, createRowFilter, RowGroups, createRowGroups, loadSiftVectors, loadSiftDataset, loadSiftQueries,
   normalizeVector, computeCentroid, computeDotProduct, computeEuclideanDistance, computeEuclideanSimilarity, computeMaximumInnerProduct,
   computeSimilarity, computeQuantizedDotProduct, computeInt4BitDotProduct: computeQuantizedDotProduct, computeInt1BitDotProduct: computeQuantizedDotProduct,

@@ -1175,6 +1175,59 @@ static napi_value RerankScores(napi_env env, napi_callback_info info) {
   return t;
 }
 
+/* vectorsSearchBatch(vectors, filter handle | null, nq, queries Float32Array[nq*dim], trueSim, k) -> {indices Int32Array[nq*k], trueScores
+ * Float64Array[nq*k], counts Float64Array[nq], stride}: the exact top-k of every raw query over the resident rows (bbq_vectors_search_batch) */
+static napi_value VectorsSearchBatch(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  if (!get_args(env, info, 6, a)) return NULL;
+  bbq_vectors *v = unbox_vectors(env, a[0]);
+  if (!v) return NULL;
+  const bbq_filter *flt = NULL;
+  napi_valuetype ft;
+  NAPI_CALL(env, napi_typeof(env, a[1], &ft));
+  if (ft != napi_null && ft != napi_undefined) {
+    flt = unbox_filter(env, a[1], "bbq_vectors_search_batch");
+    if (!flt) return NULL;
+  }
+  void *q; size_t ql;
+  int64_t nq, sim, k;
+  if (!get_i64(env, a[2], &nq) || !get_typed(env, a[3], napi_float32_array, &q, &ql) || !get_i64(env, a[4], &sim) || !get_i64(env, a[5], &k)) return NULL;
+  if (nq < 0 || nq > 0x7fffffff || ql != (size_t)nq * (size_t)bbq_vectors_dimension(v)) { napi_throw_error(env, "BBQ6", "向量维度不匹配"); return NULL; }
+  if (k < 0) { napi_throw_error(env, "BBQ7", "k值不能为负数"); return NULL; }
+  if (k > 4096) k = 4097;  /* the same answer - min(k, accepted rows) beyond 4096 is refused either way - from arrays that stay small */
+  void *oi, *ot, *on;
+  napi_value ti = new_typed(env, napi_int32_array, (size_t)(nq * k), 4, &oi);
+  napi_value tt = new_typed(env, napi_float64_array, (size_t)(nq * k), 8, &ot);
+  napi_value tn = new_typed(env, napi_float64_array, (size_t)nq, 8, &on);
+  if (!ti || !tt || !tn) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int64_t *cnt = (int64_t *)calloc((size_t)nq + 1, sizeof(int64_t));
+  if (!cnt) { napi_throw_error(env, NULL, "bbq_napi: allocation failed"); return NULL; }
+  int rc = bbq_vectors_search_batch(v, flt, (int32_t)nq, (const float *)q, (int32_t)sim, k, (int32_t *)oi, (double *)ot, cnt);
+  if (rc != BBQ_OK) { free(cnt); return throw_bbq(env, rc); }
+  for (int64_t i = 0; i < nq; ++i) ((double *)on)[i] = (double)cnt[i];
+  free(cnt);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_prop(env, o, "indices", ti); set_prop(env, o, "trueScores", tt); set_prop(env, o, "counts", tn);
+  napi_value kv; napi_create_double(env, (double)k, &kv); set_prop(env, o, "stride", kv);
+  return o;
+}
+
+/* vectorsSetOption(vectors, name, value) (bbq_vectors_set_option) */
+static napi_value VectorsSetOption(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return NULL;
+  bbq_vectors *v = unbox_vectors(env, a[0]);
+  if (!v) return NULL;
+  char name[64]; size_t nl = 0;
+  int64_t value;
+  if (napi_get_value_string_utf8(env, a[1], name, sizeof name, &nl) != napi_ok) { napi_throw_type_error(env, NULL, "bbq_napi: option name must be a string"); return NULL; }
+  if (!get_i64(env, a[2], &value)) return NULL;
+  int rc = bbq_vectors_set_option(v, name, value);
+  if (rc != BBQ_OK) return throw_bbq(env, rc);
+  napi_value u; napi_get_undefined(env, &u); return u;
+}
+
 /* searchRerankBatch(index, vectors, nq, queries Float32Array, qquant Uint8Array, qcorr Float64Array, queryBits, sim, k, factor, selector, trueSim)
  *   -> {indices Int32Array[nq*k], quantized Float32Array[nq*k], trueScores Float64Array[nq*k], counts Float64Array[nq], stride} */
 static napi_value SearchRerankBatch(napi_env env, napi_callback_info info) {
@@ -1443,6 +1496,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"vectorsCreate", NULL, VectorsCreate, NULL, NULL, NULL, napi_default, NULL},
       {"vectorsDestroy", NULL, VectorsDestroy, NULL, NULL, NULL, napi_default, NULL},
       {"rerankScores", NULL, RerankScores, NULL, NULL, NULL, napi_default, NULL},
+      {"vectorsSearchBatch", NULL, VectorsSearchBatch, NULL, NULL, NULL, napi_default, NULL},
+      {"vectorsSetOption", NULL, VectorsSetOption, NULL, NULL, NULL, napi_default, NULL},
       {"searchRerankBatch", NULL, SearchRerankBatch, NULL, NULL, NULL, napi_default, NULL},
       {"rerankMaxSimGroups", NULL, RerankMaxSimGroups, NULL, NULL, NULL, napi_default, NULL},
       {"searchMaxSimRerank", NULL, SearchMaxSimRerank, NULL, NULL, NULL, napi_default, NULL},

@@ -530,3 +530,24 @@ def getOversampledTopKWithHeap(query, quantizedVectors, vectors, k, oversampleFa
 
 def getOversampledTopKWithSort(query, quantizedVectors, vectors, k, oversampleFactor, format):
     return _oversampled(query, quantizedVectors, vectors, k, oversampleFactor, format, 1)
+
+
+def getTrueTopK(query, vectors, k, similarity=VectorSimilarityFunction.COSINE, filter=None):
+    """getTrueTopK, tests/recall-common.ts:143-149: the indices of the k rows of greatest similarity to `query`, equal scores in row
+    order - every row scored in f64 and the k best selected on the device (bbq_vectors_search_batch).  `vectors`: a capi.Vectors
+    (createDeviceVectors) or the rows themselves, uploaded for the call; `filter` (createRowFilter over the same rows): only the rows it
+    accepts.  Returns a list of ints."""
+    if k < 0:
+        raise Exception("k值不能为负数")
+    owned = not isinstance(vectors, capi.Vectors)
+    dv = createDeviceVectors(vectors) if owned else vectors
+    try:
+        if similarity not in capi.SIMS:
+            raise Exception("不支持的相似性函数: %s" % similarity)
+        idx, _, cnt = dv.search_batch(np.ascontiguousarray(query, np.float32)[None, :], k, capi.SIMS[similarity], filter)
+    except capi.BBQError as e:
+        raise Exception(str(e))
+    finally:
+        if owned:
+            dv.close()
+    return [int(i) for i in idx[0, :int(cnt[0])]]

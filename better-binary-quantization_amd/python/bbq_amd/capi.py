@@ -37,6 +37,7 @@ SYMBOLS = [
     "bbq_search_maxsim_batch", "bbq_maxsim_reduce", "bbq_maxsim_token_block",
     "bbq_score_maxsim_groups_batch", "bbq_search_maxsim_groups_batch",
     "bbq_maxsim_reduce_true", "bbq_rerank_maxsim_groups_batch", "bbq_search_maxsim_rerank_batch",
+    "bbq_true_topk", "bbq_vectors_search_batch", "bbq_vectors_set_option",
 ]
 
 
@@ -133,6 +134,9 @@ def lib():
     L.bbq_maxsim_reduce_true.argtypes = [vp, i64, i64, vp]
     L.bbq_rerank_maxsim_groups_batch.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.bbq_search_maxsim_rerank_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp]
+    L.bbq_true_topk.argtypes = [vp, i64, vp, i64, vp, vp, C.POINTER(i64)]
+    L.bbq_vectors_search_batch.argtypes = [vp, vp, i32, vp, i32, i64, vp, vp, vp]
+    L.bbq_vectors_set_option.argtypes = [vp, C.c_char_p, i64]
     L.bbq_maxsim_token_block.argtypes = []
     L.bbq_maxsim_token_block.restype = i32
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
@@ -934,6 +938,25 @@ def maxsim_reduce_true(rep_true):
     return out
 
 
+def true_topk(scores, k, accept=None):
+    """bbq_true_topk (host only): the exact search's ranking over one row of f64 scores - by true_key descending, equal keys by
+    ascending row, a NaN below every number and written as 0x7ff8000000000000 - `accept` a bool mask over the rows or None: every row.
+    Returns (rows int32 [m], scores float64 [m]), m = min(k, accepted rows)"""
+    s = np.ascontiguousarray(scores, np.float64).ravel()
+    words = None
+    if accept is not None:
+        m = np.ascontiguousarray(accept, np.bool_).ravel()
+        if m.shape[0] != s.shape[0]:
+            raise BBQError(ERR_INVALID_ARG, "a mask has one entry per row")
+        words = pack_mask(m)
+    cap = max(min(int(k), s.shape[0]), 0)
+    idx = np.zeros(cap, np.int32)
+    out = np.zeros(cap, np.float64)
+    n = C.c_int64(0)
+    _chk(lib().bbq_true_topk(_ptr(s), s.shape[0], _ptr(words), int(k), _ptr(idx), _ptr(out), C.byref(n)))
+    return idx[:n.value], out[:n.value]
+
+
 def _raw_tokens(token_lists, dim):
     """(vec_offsets int64 [nq + 1], queries float32 [vectors, dim]) of per-query raw fp32 token arrays [T, dim]"""
     arrs = [np.asarray(t, np.float32).reshape(-1, dim) for t in token_lists]
@@ -1047,6 +1070,27 @@ class Vectors:
         out = np.zeros(int(off[-1]), np.float64)
         _chk(lib().bbq_rerank_scores(self._h, q.shape[0], _ptr(q), _ptr(off), _ptr(rows), true_sim, _ptr(out)))
         return [out[off[i]:off[i + 1]] for i in range(len(lists))]
+
+    def set_option(self, name, value):
+        """bbq_vectors_set_option: "exact_slab_rows", the rows search_batch scores between two select passes (0: automatic)"""
+        _chk(lib().bbq_vectors_set_option(self._h, name.encode(), int(value)))
+
+    def search_batch(self, queries, k, true_sim=1, row_filter=None):
+        """bbq_vectors_search_batch: the exact top-k of every raw fp32 query over the rows (those `row_filter` accepts), the
+        reference's getTrueTopK on the device.  Returns (rows int32 [nq, m], true scores float64 [nq, m], counts int64 [nq]), m = min(k,
+        rows of the handle) - a k beyond the rows asks for the same answer; row q holds counts[q] = min(k, accepted rows) answers,
+        best first"""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise BBQError(ERR_DIM_MISMATCH, "向量维度不匹配")
+        k = min(int(k), self.n)
+        nq, kk = q.shape[0], max(k, 0)
+        idx = np.full((nq, kk), -1, np.int32)
+        out = np.zeros((nq, kk), np.float64)
+        cnt = np.zeros(max(nq, 1), np.int64)
+        _chk(lib().bbq_vectors_search_batch(self._h, row_filter._h if row_filter is not None else None, nq, _ptr(q), int(true_sim), int(k), _ptr(idx), _ptr(out),
+                                            _ptr(cnt)))
+        return idx, out, cnt[:nq]
 
     def rerank_maxsim_groups_batch(self, token_lists, groups, cand_lists, true_sim=1):
         """bbq_rerank_maxsim_groups_batch: the exact MaxSim score of every candidate group of every query.  token_lists: per query its

@@ -42,7 +42,8 @@ extern "C" {
                               bbq_groups_count, bbq_groups_live, bbq_groups_plan, bbq_search_grouped_batch - and the MaxSim search -
                               bbq_search_maxsim_batch, bbq_maxsim_reduce, bbq_maxsim_token_block - and MaxSim over chosen groups -
                               bbq_score_maxsim_groups_batch, bbq_search_maxsim_groups_batch - and the exact MaxSim rerank -
-                              bbq_maxsim_reduce_true, bbq_rerank_maxsim_groups_batch, bbq_search_maxsim_rerank_batch) */
+                              bbq_maxsim_reduce_true, bbq_rerank_maxsim_groups_batch, bbq_search_maxsim_rerank_batch - and the exact search -
+                              bbq_true_topk, bbq_vectors_search_batch, bbq_vectors_set_option) */
 
 /* status codes */
 enum {
@@ -768,6 +769,39 @@ int bbq_search_maxsim_rerank_batch(bbq_index *idx, bbq_vectors *v, const bbq_gro
                                    const int64_t *vec_offsets, const float *queries, const uint8_t *qquant, const double *qcorr,
                                    int32_t query_bits, int32_t sim, int64_t k, int32_t factor, int32_t selector, int32_t true_sim,
                                    int32_t *out_group, float *out_quantized, double *out_true, int64_t *out_n);
+
+/* ------------------------------------------------------------------------------------------
+ * Exact search (DESIGN.md "Exact search"): the true top-k of raw fp32 queries over the rows a bbq_vectors keeps on the device - the
+ * reference's getTrueTopK (tests/recall-common.ts:143-149: computeCosineSimilarity against every row, a stable sort by descending
+ * score, the first k), the ground truth of every recall figure it publishes; for true_sim 0 and 2 the same sort over computeSimilarity
+ * (src/vectorSimilarity.ts:14-126).
+ * Definitions.  c(q, r) is the f64 bbq_rerank_scores returns for raw query q and row r under true_sim: computeSimilarity, accumulated
+ * in index order, bit for bit.  A is the set of rows f accepts; f == NULL: every row.  The rows of A are ranked by the 64-bit key of
+ * c's bits, descending - key = 1 for a NaN, ~bits for a negative number, bits | 2^63 otherwise (true_key, bbq_device.h) - and rows of
+ * equal key by ascending row: numbers by value, a NaN below every number, NaNs among themselves by row.  (-0.0 would rank below +0.0,
+ * but cannot arise: every chain starts from +0.0 and the Euclidean score is 1 / (1 + sqrt(.)).)  The answer of query q is the first
+ * min(k, |A|) rows of that ranking: out_idx / out_true [n_queries*k] (query q at offset q*k), out_n [n_queries] the number written; a
+ * NaN is written as 0x7ff8000000000000.  On finite inputs that is getTrueTopK: a stable descending sort leaves equal scores in row order.
+ * bbq_true_topk (host only, no device) is that ranking in plain C over one row of scores [n] - accept_bits NULL or [ceil(n / 64)] words,
+ * bit l of word t = row 64 t + l - into out_idx / out_true [min(k, |A|)] and *out_n: the normative statement.
+ * bbq_vectors_search_batch computes it on the device: queries [n_queries*dim] raw fp32, NOT normalised, exactly as bbq_rerank_scores
+ * takes them.  f->n_rows must equal bbq_vectors_size(v) on the same device, as bbq_vectors_compact demands, otherwise
+ * BBQ_ERR_INVALID_ARG; true_sim outside 0 .. 2 is refused with bbq_rerank_scores' message; k < 0: BBQ_ERR_NEGATIVE_K; k == 0,
+ * n_queries == 0 or |A| == 0: BBQ_OK, out_n = 0, nothing launched; min(k, |A|) > 4096: BBQ_ERR_UNSUPPORTED (bbq_rerank_scores over the
+ * accepted rows and a sort on the host serve there).  Non-finite inputs are not refused: they propagate by IEEE arithmetic.  The checks
+ * run under the context's lock before the first launch; after bbq_vectors_append, _update or _compact the call answers over the rows as
+ * they now are.  A row is read once per block of 32 queries; a call is worked through in sub-batches of at most 1024 queries and slabs
+ * of rows whose keys, 8 bytes per (query, row), stay under 256 MiB of scratch inside the handle; k x (row, score) per query is the only
+ * copy back.  A failed allocation: BBQ_ERR_OOM, no answer written.  Results are byte-identical from run to run.
+ * bbq_vectors_set_option: "exact_slab_rows", the rows scored between two select passes - 0 (automatic: what the scratch allows) or a
+ * multiple of 256 in 256 .. 2^24.  A speed and scratch choice: it never changes an answer.  An unknown name or a value out of range:
+ * BBQ_ERR_INVALID_ARG.
+ * Out of scope: multi-device handles and shards, spans or row lists (bbq_rerank_scores takes lists), k beyond 4096. */
+int bbq_true_topk(const double *scores, int64_t n, const uint64_t *accept_bits, int64_t k, int32_t *out_idx, double *out_true,
+                  int64_t *out_n);                                                                      /* host only */
+int bbq_vectors_search_batch(bbq_vectors *v, const bbq_filter *f, int32_t n_queries, const float *queries, int32_t true_sim,
+                             int64_t k, int32_t *out_idx, double *out_true, int64_t *out_n);
+int bbq_vectors_set_option(bbq_vectors *v, const char *name, int64_t value);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side quantizer (multithreaded C++): what the JS host calls for quantizeVectors /
