@@ -18,6 +18,7 @@
 #include "bbq_device.h"
 #include "bbq_kernel_common.h"
 #include "bbq_launch.h"
+#include "bbq_rowlist.h"
 #include "bbq_scan_body.h"
 
 #pragma clang fp contract(off)
@@ -44,41 +45,25 @@ __global__ __launch_bounds__(kGatherThreads) void bbq_score_ords_kernel(const Ga
   const int64_t i = c0 + tid;
   const bool valid = i < end;
   const int64_t r = a.ords[valid ? i : c0];
-  {  // stage the query's planes once per workgroup
-    const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)q * w16 * QU;
-    for (int j = tid; j < w16 * QU; j += kGatherThreads) s_planes[j] = gp[j];
-  }
+  stage_query_planes<kGatherThreads>(s_planes, reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)q * w16 * QU, w16 * QU, tid);
   const QueryParams p = a.qparams[q];
   __syncthreads();
   if (c0 + (tid & ~63) >= end) return;  // wave-uniform: a whole wave beyond the list
 
   const uint8_t *__restrict__ tp = a.idx.tiles + (r >> 6) * (int64_t)a.idx.geom.tile_stride;
   const int lr = (int)(r & 63);
-  const uint8_t *__restrict__ cr = tp + tile_corr_offset(w16);
   f64x2 lu = {0.0, 0.0};
   double xadd = 0.0, x1 = 0.0;
   uint32_t qc, ones;
-  auto load_corrections = [&] {
-    if constexpr (COMPACT) {
-      exact_corrections(a.idx.exact, r, lu, xadd);
-    } else {
-      lu = *(reinterpret_cast<const f64x2 *>(cr) + lr);
-      xadd = *(reinterpret_cast<const double *>(cr + kCorrAddOffset) + lr);
-      if (a.idx.geom.has_x1) x1 = *(reinterpret_cast<const double *>(cr + kCorrSumOffset) + lr);
-    }
-  };
+  u32x4 c[W > 0 ? W : 1];
+  load_row<W, COMPACT>(a.idx, tp, lr, r, w16, false, c, lu, xadd, x1, ones);  // (the sum is counted: no side array here)
   if constexpr (W > 0) {
-    u32x4 c[W];
-#pragma unroll
-    for (int j = 0; j < W; ++j) c[j] = *reinterpret_cast<const u32x4 *>(tp + tile_chunk_offset(j, lr));
-    load_corrections();
     // nothing crosses this line: left to itself the scheduler issues the later chunks behind the first popcounts, which wait for
     // the first chunk - a second round trip for the row
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (SB == 1) qc = tile_popcounts<QB, W>(c, s_planes, ones);
     else tile_dot_multibit<QB, W, SB>(c, s_planes, qc, ones);
   } else {  // a row width without a compiled kernel: the sweep's chunk loop
-    load_corrections();
     if constexpr (SB == 1) qc = tile_popcounts_any<QB>(tp, lr, w16, s_planes, ones);
     else tile_dot_multibit_any<QB, SB>(tp, lr, w16, s_planes, qc, ones);
   }
@@ -102,44 +87,13 @@ hipError_t launch_gather_t(const GatherArgs &a, int n_queries, int64_t max_count
   return hipGetLastError();
 }
 
-// the compiled row widths are the sweep's (launch_scan_w, launch_scan_mb_w)
-template <int QB>
-hipError_t launch_gather_w(const GatherArgs &a, int nq, int64_t mc, hipStream_t s) {
-  switch (a.idx.geom.w16) {
-    case 1: return launch_gather_t<QB, 1, 1>(a, nq, mc, s);    // dim <= 128
-    case 6: return launch_gather_t<QB, 6, 1>(a, nq, mc, s);    // dim 768
-    case 8: return launch_gather_t<QB, 8, 1>(a, nq, mc, s);    // dim 1024
-    case 12: return launch_gather_t<QB, 12, 1>(a, nq, mc, s);  // dim 1536
-    default: return launch_gather_t<QB, 0, 1>(a, nq, mc, s);
-  }
-}
-template <int QB, int SB>
-hipError_t launch_gather_mb_w(const GatherArgs &a, int nq, int64_t mc, hipStream_t s) {
-  switch (a.idx.geom.w16) {
-    case 12: return launch_gather_t<QB, 12, SB>(a, nq, mc, s);
-    case 16: return launch_gather_t<QB, 16, SB>(a, nq, mc, s);
-    default: return launch_gather_t<QB, 0, SB>(a, nq, mc, s);
-  }
-}
-
 }  // namespace
 
 hipError_t launch_score_ords(const GatherArgs &a, int planes, int n_queries, int64_t max_count, hipStream_t s) {
   if (n_queries <= 0 || max_count <= 0) return hipSuccess;
   if (n_queries > 65535 || (uint64_t)max_count + kGatherThreads > kGridWorkItemsMax) return hipErrorInvalidValue;  // grid.y, and grid.x in work-items
-  switch (a.idx.geom.store_bits) {
-    case 1:
-      switch (planes) {
-        case 1: return launch_gather_w<1>(a, n_queries, max_count, s);
-        case 2: return launch_gather_w<2>(a, n_queries, max_count, s);
-        case 4: return launch_gather_w<4>(a, n_queries, max_count, s);
-        default: return launch_gather_w<8>(a, n_queries, max_count, s);
-      }
-    case 2: return planes > 4 ? launch_gather_mb_w<8, 2>(a, n_queries, max_count, s) : launch_gather_mb_w<4, 2>(a, n_queries, max_count, s);
-    case 4: return planes > 4 ? launch_gather_mb_w<8, 4>(a, n_queries, max_count, s) : launch_gather_mb_w<4, 4>(a, n_queries, max_count, s);
-    case 8: return launch_gather_t<8, 0, 8>(a, n_queries, max_count, s);
-    default: return hipErrorInvalidValue;
-  }
+  return rowlist_ladder(a.idx.geom, planes,
+                        [&](auto qb, auto w, auto sb) { return launch_gather_t<qb(), w(), sb()>(a, n_queries, max_count, s); });
 }
 
 }  // namespace bbq

@@ -13,6 +13,7 @@
 #include "bbq_device.h"
 #include "bbq_kernel_common.h"
 #include "bbq_launch.h"
+#include "bbq_rowlist.h"
 #include "bbq_scan_body.h"
 
 #pragma clang fp contract(off)
@@ -21,9 +22,7 @@ namespace bbq {
 
 namespace {
 
-constexpr int kGroupEdges = 2 * kTilesPerChunk;  // LDS slots of a workgroup's edge segments: two per wave
 constexpr int kGroupUnpackThreads = 256;
-static_assert(kGroupEdges <= 64, "one wave merges the edge segments");
 
 // grid = sweep_grid_x(n_chunks, s) x sweep_grid_y(n_queries, s), decoded by sweep_coord as bbq_scan_kernel decodes it (s = a.l2_shift:
 // 2^s queries of a chunk dispatched next to each other); block = kChunkRows / 64 waves: wave w takes tile w of the chunk.  QB / W / SB /
@@ -51,10 +50,7 @@ __global__ __launch_bounds__(kChunkRows) void bbq_group_score_kernel(const Group
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  {  // stage the query's planes once per workgroup
-    const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)q * w16 * QU;
-    for (int i = tid; i < w16 * QU; i += NT) s_planes[i] = gp[i];
-  }
+  stage_query_planes<NT>(s_planes, reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)q * w16 * QU, w16 * QU, tid);
   if (tid < kGroupEdges) s_key[tid] = 0ull;
   const QueryParams p = a.qparams[q];
   __syncthreads();
@@ -75,59 +71,16 @@ __global__ __launch_bounds__(kChunkRows) void bbq_group_score_kernel(const Group
   if (mine != 0) {  // wave-uniform
     const int64_t row = tile * kTileRows + lane;
     const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
-    const uint8_t *__restrict__ cr = tp + tile_corr_offset(w16);
     const bool resident = chunk_is_resident(tile / kTilesPerChunk, a.idx);
-    const bool rs = COMPACT && a.idx.row_sums != nullptr;  // uniform over the launch
+    const RowTerms rt = tile_row_terms<QB, W, SB, COMPACT>(a.idx, tp, row, lane, w16, resident, s_planes);
 
-    f64x2 lu = {0.0, 0.0};
-    double xadd = 0.0, x1 = 0.0;
-    uint32_t cw = 0;
-    uint32_t qc, ones = 0;
-    constexpr int CORR = COMPACT ? 0 : 2;
-    if constexpr (W > 0) {
-      u32x4 c[W];
-      if (rs) {
-        load_tile<W, CORR, true>(tp, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, a.idx.row_sums + row, &ones);
-        if constexpr (COMPACT) exact_corrections<true>(a.idx.exact, row, lu, xadd);
-        if constexpr (SB == 1) qc = tile_popcounts<QB, W, false>(c, s_planes, ones);
-        else tile_dot_multibit<QB, W, SB, false>(c, s_planes, qc, ones);
-      } else {
-        load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
-        if constexpr (COMPACT) exact_corrections<true>(a.idx.exact, row, lu, xadd);
-        if constexpr (SB == 1) qc = tile_popcounts<QB, W>(c, s_planes, ones);
-        else tile_dot_multibit<QB, W, SB>(c, s_planes, qc, ones);
-      }
-    } else {  // a row width without a compiled kernel: streamed chunk by chunk
-      if constexpr (!COMPACT) {
-        lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(cr) + lane);
-        xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + kCorrAddOffset) + lane);
-        if (a.idx.geom.has_x1) x1 = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + kCorrSumOffset) + lane);
-      } else {
-        exact_corrections<true>(a.idx.exact, row, lu, xadd);
-      }
-      if (rs) {
-        ones = BBQ_STREAM_LOAD(a.idx.row_sums + row);
-        if constexpr (SB == 1) qc = tile_popcounts_any<QB, false>(tp, lane, w16, s_planes, ones);
-        else tile_dot_multibit_any<QB, SB, false>(tp, lane, w16, s_planes, qc, ones);
-      } else {
-        if constexpr (SB == 1) qc = tile_popcounts_any<QB>(tp, lane, w16, s_planes, ones);
-        else tile_dot_multibit_any<QB, SB>(tp, lane, w16, s_planes, qc, ones);
-      }
-    }
-    if (COMPACT || !a.idx.geom.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
-
-    const float s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
+    const float s32 = (float)score_f64((double)rt.qc, rt.lu.x, rt.lu.y, rt.xadd, rt.x1, p);
     unsigned long long key = ((mine >> lane) & 1ull) ? group_key(__float_as_uint(s32), s32 != s32, (uint32_t)row) : 0ull;
 
-    // the segmented maximum: lane l takes the keys of the lanes between its segment's first lane and itself
     const uint64_t st = a.starts[tile];  // wave-uniform
     const uint64_t heads = st | 1ull;
-    const int head = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));  // the first lane of this lane's segment
-#pragma unroll
-    for (int d = 1; d < kTileRows; d <<= 1) {
-      const unsigned long long o = __shfl_up(key, (unsigned)d, kTileRows);
-      if (lane - d >= head && o > key) key = o;
-    }
+    const int head = segment_head(heads, lane);
+    key = segment_max(key, head, lane);
     const bool is_end = lane == kTileRows - 1 || ((heads >> (lane + 1)) & 1ull);
     if (is_end && key != 0ull) {
       const uint32_t grp = a.first_group[tile] + (uint32_t)__popcll((st >> 1) & ((1ull << lane) - 1ull));
@@ -145,28 +98,9 @@ __global__ __launch_bounds__(kChunkRows) void bbq_group_score_kernel(const Group
   __syncthreads();
   if (wave != 0) return;
 
-  // the edge segments of the workgroup, in row order: those of one group folded into the first of them
   const unsigned long long mk = lane < kGroupEdges ? s_key[lane] : 0ull;
   const uint32_t mg = lane < kGroupEdges ? s_grp[lane] : 0u;
-  unsigned long long best = mk;
-  bool leader = mk != 0ull;
-#pragma unroll
-  for (int j = 0; j < kGroupEdges; ++j) {
-    const unsigned long long kj = __shfl(mk, j, kTileRows);
-    const uint32_t gj = (uint32_t)__shfl((int)mg, j, kTileRows);
-    if (mk != 0ull && kj != 0ull && gj == mg) {
-      if (kj > best) best = kj;
-      if (j < lane) leader = false;
-    }
-  }
-  if (leader) {
-    const int64_t next_tile = first_tile + kTilesPerChunk < n_tiles ? first_tile + kTilesPerChunk : n_tiles;
-    const bool cut_lo = !(a.starts[first_tile] & 1ull) && mg == a.first_group[first_tile];  // the group began in front of the chunk
-    const bool cut_hi = !(a.starts[next_tile] & 1ull) && mg == a.first_group[next_tile];    // ... goes on behind it
-    unsigned long long *dst = rep + a.slot[mg];
-    if (cut_lo || cut_hi) atomicMax(dst, best);
-    else *dst = best;
-  }
+  fold_group_edges(a, mk, mg, rep, first_tile, n_tiles, lane);
 }
 
 __global__ __launch_bounds__(kGroupUnpackThreads) void bbq_group_unpack_kernel(const unsigned long long *__restrict__ rep, float *__restrict__ scores,
@@ -196,45 +130,13 @@ hipError_t launch_group_score_t(const GroupScoreArgs &args, hipStream_t s) {
   return hipGetLastError();
 }
 
-// the compiled row widths are the sweep's (launch_scan_w, launch_scan_mb_w)
-template <int QB>
-hipError_t launch_group_score_w(const GroupScoreArgs &a, hipStream_t s) {
-  switch (a.idx.geom.w16) {
-    case 1: return launch_group_score_t<QB, 1, 1>(a, s);    // dim <= 128
-    case 6: return launch_group_score_t<QB, 6, 1>(a, s);    // dim 768
-    case 8: return launch_group_score_t<QB, 8, 1>(a, s);    // dim 1024
-    case 12: return launch_group_score_t<QB, 12, 1>(a, s);  // dim 1536
-    default: return launch_group_score_t<QB, 0, 1>(a, s);
-  }
-}
-template <int QB, int SB>
-hipError_t launch_group_score_mb_w(const GroupScoreArgs &a, hipStream_t s) {
-  switch (a.idx.geom.w16) {
-    case 12: return launch_group_score_t<QB, 12, SB>(a, s);
-    case 16: return launch_group_score_t<QB, 16, SB>(a, s);
-    default: return launch_group_score_t<QB, 0, SB>(a, s);
-  }
-}
-
 }  // namespace
 
 hipError_t launch_group_score(const GroupScoreArgs &a, int planes, hipStream_t s) {
   if (a.n_chunks <= 0 || a.n_queries <= 0 || a.live <= 0) return hipSuccess;
   if (a.n_queries > 65535 || a.idx.n_rows > kGroupMaxRows || !a.starts || !a.first_group || !a.slot || !a.rep) return hipErrorInvalidValue;
   if ((int64_t)a.n_chunks != (a.idx.n_rows + kChunkRows - 1) / kChunkRows) return hipErrorInvalidValue;  // the tables are those of the whole index
-  switch (a.idx.geom.store_bits) {
-    case 1:
-      switch (planes) {
-        case 1: return launch_group_score_w<1>(a, s);
-        case 2: return launch_group_score_w<2>(a, s);
-        case 4: return launch_group_score_w<4>(a, s);
-        default: return launch_group_score_w<8>(a, s);
-      }
-    case 2: return planes > 4 ? launch_group_score_mb_w<8, 2>(a, s) : launch_group_score_mb_w<4, 2>(a, s);
-    case 4: return planes > 4 ? launch_group_score_mb_w<8, 4>(a, s) : launch_group_score_mb_w<4, 4>(a, s);
-    case 8: return launch_group_score_t<8, 0, 8>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  return rowlist_ladder(a.idx.geom, planes, [&](auto qb, auto w, auto sb) { return launch_group_score_t<qb(), w(), sb()>(a, s); });
 }
 
 hipError_t launch_group_unpack(const unsigned long long *rep, float *scores, uint32_t *ords, int64_t n, hipStream_t s) {

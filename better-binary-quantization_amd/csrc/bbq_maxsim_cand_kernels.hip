@@ -18,6 +18,7 @@
 #include "bbq_device.h"
 #include "bbq_kernel_common.h"
 #include "bbq_launch.h"
+#include "bbq_rowlist.h"
 #include "bbq_scan_body.h"
 
 #pragma clang fp contract(off)
@@ -26,7 +27,6 @@ namespace bbq {
 
 namespace {
 
-constexpr int kParamUnits = sizeof(QueryParams) / 16;
 constexpr size_t kCandLdsMax = 64 * 1024;  // what a launch asks for without an attribute; four workgroups of a CU's 160 KB at the default shapes
 
 // LDS of a workgroup: [tok_pass][w16 * QU] planes | [tok_pass] QueryParams
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(kMaxSimCandThreads) void bbq_maxsim_cand_kernel(con
 
   // the lane's segment, once: the lanes of its candidate inside this wave
   const uint64_t heads = __ballot(!valid || xc == rc.pos) | 1ull;
-  const int head = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));  // the first lane of this lane's segment
+  const int head = segment_head(heads, lane);
   const bool is_end = valid && (lane == kTileRows - 1 || ((heads >> (lane + 1)) & 1ull));
   const int64_t wave_x = x - lane;
   const bool whole = (int64_t)rc.pos >= wave_x && (int64_t)next_pos <= wave_x + kTileRows;  // no other wave of the launch sees this entry
@@ -94,19 +94,7 @@ __global__ __launch_bounds__(kMaxSimCandThreads) void bbq_maxsim_cand_kernel(con
   u32x4 c[W > 0 ? W : 1];
   (void)c;
   if (active) {
-    if constexpr (W > 0) {
-#pragma unroll
-      for (int j = 0; j < W; ++j) c[j] = *reinterpret_cast<const u32x4 *>(tp + tile_chunk_offset(j, lr));
-    }
-    if constexpr (COMPACT) {
-      exact_corrections(a.idx.exact, r, lu, xadd);
-    } else {
-      const uint8_t *__restrict__ cr = tp + tile_corr_offset(w16);
-      lu = *(reinterpret_cast<const f64x2 *>(cr) + lr);
-      xadd = *(reinterpret_cast<const double *>(cr + kCorrAddOffset) + lr);
-      if (a.idx.geom.has_x1) x1 = *(reinterpret_cast<const double *>(cr + kCorrSumOffset) + lr);
-    }
-    if (rs) ones = a.idx.row_sums[r];
+    load_row<W, COMPACT>(a.idx, tp, lr, r, w16, rs, c, lu, xadd, x1, ones);
     // nothing crosses this line: every load of the row is in flight before the staging below and the first popcount wait for anything
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -115,26 +103,15 @@ __global__ __launch_bounds__(kMaxSimCandThreads) void bbq_maxsim_cand_kernel(con
   for (int t0 = 0; t0 < n_tok; t0 += tok_pass) {  // one pass for every compiled width
     const int np = n_tok - t0 < tok_pass ? n_tok - t0 : tok_pass;
     if (t0 > 0) __syncthreads();  // the last pass's readers are done
-    {  // stage the pass's planes and uniforms once per workgroup: the tokens of a query lie back to back
-      const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)(mq.vec_first + t0) * PU;
-      for (int i = tid; i < np * PU; i += NT) s_planes[i] = gp[i];
-      const u32x4 *__restrict__ gq = reinterpret_cast<const u32x4 *>(a.qparams + mq.vec_first + t0);
-      u32x4 *sq = reinterpret_cast<u32x4 *>(s_params);
-      for (int i = tid; i < np * kParamUnits; i += NT) sq[i] = gq[i];
-    }
+    stage_token_block<NT>(s_planes, s_params, reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)(mq.vec_first + t0) * PU,
+                          a.qparams + mq.vec_first + t0, np, PU, tid);  // the pass's
     __syncthreads();
     if (!active) continue;  // wave-uniform; the barriers above are reached by every wave
     if constexpr (W > 0) {
-      if (t0 == 0 && !rs) {  // the row's popcount does not depend on the token
-#pragma unroll
-        for (int j = 0; j < W; ++j) ones = popc4_acc(c[j], ones);
-      }
+      if (t0 == 0 && !rs) ones = row_popcount(c, ones);
     }
     for (int t = 0; t < np; ++t) {
-      QueryParams p = s_params[t];
-      p.sim = __builtin_amdgcn_readfirstlane(p.sim);  // the same in every lane: the score's branches stay scalar
-      p.one_bit = __builtin_amdgcn_readfirstlane(p.one_bit);
-      p.mip_plain = __builtin_amdgcn_readfirstlane(p.mip_plain);
+      const QueryParams p = token_params(s_params, t);
       const u32x4 *pl = s_planes + t * PU;
       uint32_t qc;
       if constexpr (W > 0) {
@@ -149,12 +126,7 @@ __global__ __launch_bounds__(kMaxSimCandThreads) void bbq_maxsim_cand_kernel(con
       }
       const double xs = (COMPACT || !a.idx.geom.has_x1) ? (double)ones : x1;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
       const float s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, xs, p);
-      unsigned long long key = accepted ? group_key(__float_as_uint(s32), s32 != s32, (uint32_t)r) : 0ull;
-#pragma unroll
-      for (int d = 1; d < kTileRows; d <<= 1) {
-        const unsigned long long o = __shfl_up(key, (unsigned)d, kTileRows);
-        if (lane - d >= head && o > key) key = o;
-      }
+      const unsigned long long key = segment_max(accepted ? group_key(__float_as_uint(s32), s32 != s32, (uint32_t)r) : 0ull, head, lane);
       if (is_end && key != 0ull) {
         unsigned long long *dst = rep + (size_t)(t0 + t) * (size_t)a.stride;
         if (whole) *dst = key;
@@ -184,37 +156,15 @@ hipError_t launch_cand_t(const MaxSimCandArgs &args, int n_queries, int64_t long
   return hipGetLastError();
 }
 
-// the register-resident widths are the sweep's compiled widths of 1-bit rows (launch_scan_w)
-template <int QB>
-hipError_t launch_cand_w(const MaxSimCandArgs &a, int nq, int64_t longest, hipStream_t s) {
-  switch (a.idx.geom.w16) {
-    case 1: return launch_cand_t<QB, 1, 1>(a, nq, longest, s);    // dim <= 128
-    case 6: return launch_cand_t<QB, 6, 1>(a, nq, longest, s);    // dim 768
-    case 8: return launch_cand_t<QB, 8, 1>(a, nq, longest, s);    // dim 1024
-    case 12: return launch_cand_t<QB, 12, 1>(a, nq, longest, s);  // dim 1536
-    default: return launch_cand_t<QB, 0, 1>(a, nq, longest, s);
-  }
-}
-
 }  // namespace
 
 hipError_t launch_maxsim_cand_score(const MaxSimCandArgs &a, int planes, int n_queries, int64_t longest, hipStream_t s) {
   if (n_queries <= 0 || longest <= 0) return hipSuccess;
   if (n_queries > 65535 || longest > kMaxSimCandMaxRows || a.idx.n_rows > kGroupMaxRows) return hipErrorInvalidValue;  // grid.y; grid.x in work-items; the key's ord
   if (!a.queries || !a.cq || !a.recs || !a.rep || a.stride <= 0) return hipErrorInvalidValue;
-  switch (a.idx.geom.store_bits) {
-    case 1:
-      switch (planes) {
-        case 1: return launch_cand_w<1>(a, n_queries, longest, s);
-        case 2: return launch_cand_w<2>(a, n_queries, longest, s);
-        case 4: return launch_cand_w<4>(a, n_queries, longest, s);
-        default: return launch_cand_w<8>(a, n_queries, longest, s);
-      }
-    case 2: return planes > 4 ? launch_cand_t<8, 0, 2>(a, n_queries, longest, s) : launch_cand_t<4, 0, 2>(a, n_queries, longest, s);
-    case 4: return planes > 4 ? launch_cand_t<8, 0, 4>(a, n_queries, longest, s) : launch_cand_t<4, 0, 4>(a, n_queries, longest, s);
-    case 8: return launch_cand_t<8, 0, 8>(a, n_queries, longest, s);
-    default: return hipErrorInvalidValue;
-  }
+  // the register-resident widths are those of 1-bit rows: a multi-bit row takes the run-time width
+  return rowlist_ladder<MultiBitRows::kRunTimeWidth>(
+      a.idx.geom, planes, [&](auto qb, auto w, auto sb) { return launch_cand_t<qb(), w(), sb()>(a, n_queries, longest, s); });
 }
 
 }  // namespace bbq

@@ -13,6 +13,7 @@
 #include "bbq_device.h"
 #include "bbq_kernel_common.h"
 #include "bbq_launch.h"
+#include "bbq_rowlist.h"
 #include "bbq_scan_body.h"
 
 #pragma clang fp contract(off)
@@ -21,10 +22,7 @@ namespace bbq {
 
 namespace {
 
-constexpr int kGroupEdges = 2 * kTilesPerChunk;  // LDS slots of a workgroup's edge segments per token: two per wave
 constexpr int kMaxSimAccThreads = 256;
-constexpr int kParamUnits = sizeof(QueryParams) / 16;
-static_assert(kGroupEdges <= 64, "one wave merges a token's edge segments");
 
 // LDS of a fused workgroup: [TB][W * QU] planes | [TB] QueryParams | [TB][kGroupEdges] keys | [kGroupEdges] groups
 constexpr size_t maxsim_lds_bytes(int w16, int qu) {
@@ -54,14 +52,9 @@ __global__ __launch_bounds__(kChunkRows) void bbq_maxsim_score_kernel(const MaxS
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  {  // stage the block's planes and uniforms once per workgroup: the tokens of a query lie back to back
-    const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)mq.vec_first * PU;
-    for (int i = tid; i < n_tok * PU; i += NT) s_planes[i] = gp[i];
-    const u32x4 *__restrict__ gq = reinterpret_cast<const u32x4 *>(a.qparams + mq.vec_first);
-    u32x4 *sq = reinterpret_cast<u32x4 *>(s_params);
-    for (int i = tid; i < n_tok * kParamUnits; i += NT) sq[i] = gq[i];
-    for (int i = tid; i < n_tok * kGroupEdges; i += NT) s_key[i] = 0ull;
-  }
+  stage_token_block<NT>(s_planes, s_params, reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)mq.vec_first * PU, a.qparams + mq.vec_first,
+                        n_tok, PU, tid);  // the block's
+  for (int i = tid; i < n_tok * kGroupEdges; i += NT) s_key[i] = 0ull;
   __syncthreads();
 
   const int64_t n_tiles = (a.idx.n_rows + kTileRows - 1) / kTileRows;
@@ -96,17 +89,14 @@ __global__ __launch_bounds__(kChunkRows) void bbq_maxsim_score_kernel(const MaxS
       load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
     }
     if constexpr (COMPACT) exact_corrections<true>(a.idx.exact, row, lu, xadd);
-    if (!rs) {  // the row's popcount does not depend on the token
-#pragma unroll
-      for (int j = 0; j < W; ++j) ones = popc4_acc(c[j], ones);
-    }
+    if (!rs) ones = row_popcount(c, ones);
     if (COMPACT || !a.idx.geom.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount
 
     // the lane's segment, once: its first lane, whether it ends here, where its key goes
     const bool accepted = (mine >> lane) & 1ull;
     const uint64_t st = a.starts[tile];  // wave-uniform
     const uint64_t heads = st | 1ull;
-    const int head = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));  // the first lane of this lane's segment
+    const int head = segment_head(heads, lane);
     const bool is_end = lane == kTileRows - 1 || ((heads >> (lane + 1)) & 1ull);
     bool whole = false;
     int32_t slot = -1;
@@ -122,19 +112,11 @@ __global__ __launch_bounds__(kChunkRows) void bbq_maxsim_score_kernel(const MaxS
     }
 
     for (int t = 0; t < n_tok; ++t) {
-      QueryParams p = s_params[t];
-      p.sim = __builtin_amdgcn_readfirstlane(p.sim);  // the same in every lane: the score's branches stay scalar
-      p.one_bit = __builtin_amdgcn_readfirstlane(p.one_bit);
-      p.mip_plain = __builtin_amdgcn_readfirstlane(p.mip_plain);
+      const QueryParams p = token_params(s_params, t);
       uint32_t unused = 0;
       const uint32_t qc = tile_popcounts<QB, W, false>(c, s_planes + t * PU, unused);
       const float s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
-      unsigned long long key = accepted ? group_key(__float_as_uint(s32), s32 != s32, (uint32_t)row) : 0ull;
-#pragma unroll
-      for (int d = 1; d < kTileRows; d <<= 1) {
-        const unsigned long long o = __shfl_up(key, (unsigned)d, kTileRows);
-        if (lane - d >= head && o > key) key = o;
-      }
+      const unsigned long long key = segment_max(accepted ? group_key(__float_as_uint(s32), s32 != s32, (uint32_t)row) : 0ull, head, lane);
       if (is_end && key != 0ull) {
         if (whole) rep[(size_t)t * (size_t)a.live + slot] = key;  // the whole group: no other lane of the launch writes its slot for this token
         else s_key[t * kGroupEdges + e] = key;
@@ -144,28 +126,10 @@ __global__ __launch_bounds__(kChunkRows) void bbq_maxsim_score_kernel(const MaxS
   __syncthreads();
 
   // per token the edge segments of the workgroup, in row order: those of one group folded into the first of them
-  const int64_t next_tile = first_tile + kTilesPerChunk < n_tiles ? first_tile + kTilesPerChunk : n_tiles;
   const uint32_t mg = lane < kGroupEdges ? s_grp[lane] : 0u;
   for (int t = wave; t < n_tok; t += kTilesPerChunk) {
     const unsigned long long mk = lane < kGroupEdges ? s_key[t * kGroupEdges + lane] : 0ull;
-    unsigned long long best = mk;
-    bool leader = mk != 0ull;
-#pragma unroll
-    for (int j = 0; j < kGroupEdges; ++j) {
-      const unsigned long long kj = __shfl(mk, j, kTileRows);
-      const uint32_t gj = (uint32_t)__shfl((int)mg, j, kTileRows);
-      if (mk != 0ull && kj != 0ull && gj == mg) {
-        if (kj > best) best = kj;
-        if (j < lane) leader = false;
-      }
-    }
-    if (leader) {
-      const bool cut_lo = !(a.starts[first_tile] & 1ull) && mg == a.first_group[first_tile];  // the group began in front of the chunk
-      const bool cut_hi = !(a.starts[next_tile] & 1ull) && mg == a.first_group[next_tile];    // ... goes on behind it
-      unsigned long long *dst = rep + (size_t)t * (size_t)a.live + a.slot[mg];
-      if (cut_lo || cut_hi) atomicMax(dst, best);
-      else *dst = best;
-    }
+    fold_group_edges(a, mk, mg, rep + (size_t)t * (size_t)a.live, first_tile, n_tiles, lane);
   }
 }
 

@@ -10,6 +10,7 @@
 #include "bbq_device.h"
 #include "bbq_kernel_common.h"
 #include "bbq_launch.h"
+#include "bbq_rowlist.h"
 #include "bbq_scan_body.h"
 
 #pragma clang fp contract(off)
@@ -79,11 +80,8 @@ __global__ __launch_bounds__(kChunkRows) void bbq_range_kernel(const RangeArgs a
   // the tile's accept word first, as in the filtered sweep: the scalar load travels while the planes are staged
   uint64_t aw = 0;
   if (tile < n_tiles) aw = a.accept ? a.accept[tile] : ~0ull;
-  {  // stage the query's planes once per workgroup
-    const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)q * w16 * QU;
-    for (int i = tid; i < w16 * QU; i += NT) s_planes[i] = gp[i];
-    if (!FILL && tid == 0) s_wave[0] = 0;
-  }
+  stage_query_planes<NT>(s_planes, reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)q * w16 * QU, w16 * QU, tid);
+  if (!FILL && tid == 0) s_wave[0] = 0;
   const QueryParams p = a.qparams[q];
   const Threshold th = a.theta[q];
   __syncthreads();
@@ -93,55 +91,18 @@ __global__ __launch_bounds__(kChunkRows) void bbq_range_kernel(const RangeArgs a
   float s32 = 0.0f;
   if (aw != 0) {  // wave-uniform
     const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
-    const uint8_t *__restrict__ cr = tp + tile_corr_offset(w16);
     const bool valid = row < a.idx.n_rows && ((aw >> lane) & 1ull) != 0;
     const bool resident = chunk_is_resident(chunk, a.idx);
-    const bool rs = COMPACT && a.idx.row_sums != nullptr;  // uniform over the launch
-
-    f64x2 lu = {0.0, 0.0};
-    double xadd = 0.0, x1 = 0.0;
-    uint32_t cw = 0;
-    float aadd = 0.0f;
-    uint32_t qc, ones = 0;
-    constexpr int CORR = COMPACT ? 1 : 2;
-    if constexpr (W > 0) {
-      u32x4 c[W];
-      if (rs) {
-        load_tile<W, CORR, true>(tp, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, a.idx.row_sums + row, &ones);
-        if constexpr (SB == 1) qc = tile_popcounts<QB, W, false>(c, s_planes, ones);
-        else tile_dot_multibit<QB, W, SB, false>(c, s_planes, qc, ones);
-      } else {
-        load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
-        if constexpr (SB == 1) qc = tile_popcounts<QB, W>(c, s_planes, ones);
-        else tile_dot_multibit<QB, W, SB>(c, s_planes, qc, ones);
-      }
-    } else {  // a row width without a compiled kernel: streamed chunk by chunk
-      if constexpr (!COMPACT) {
-        lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(cr) + lane);
-        xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + kCorrAddOffset) + lane);
-        if (a.idx.geom.has_x1) x1 = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + kCorrSumOffset) + lane);
-      } else {
-        cw = BBQ_STREAM_LOAD(reinterpret_cast<const uint32_t *>(cr) + lane);
-      }
-      if (rs) {
-        ones = BBQ_STREAM_LOAD(a.idx.row_sums + row);
-        if constexpr (SB == 1) qc = tile_popcounts_any<QB, false>(tp, lane, w16, s_planes, ones);
-        else tile_dot_multibit_any<QB, SB, false>(tp, lane, w16, s_planes, qc, ones);
-      } else {
-        if constexpr (SB == 1) qc = tile_popcounts_any<QB>(tp, lane, w16, s_planes, ones);
-        else tile_dot_multibit_any<QB, SB>(tp, lane, w16, s_planes, qc, ones);
-      }
-    }
-    if (COMPACT || !a.idx.geom.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
+    RowTerms rt = tile_row_terms<QB, W, SB, COMPACT, true>(a.idx, tp, row, lane, w16, resident, s_planes);
 
     bool need_exact = true;
     if constexpr (COMPACT) {
-      aadd = tile_add_bound(a.idx, tile, p.sim);
-      need_exact = compact_bound_passes(valid, qc, cw, aadd, ones, x1, p, th);
-      if (need_exact) exact_corrections(a.idx.exact, row, lu, xadd);
+      const float aadd = tile_add_bound(a.idx, tile, p.sim);
+      need_exact = compact_bound_passes(valid, rt.qc, rt.cw, aadd, rt.ones, rt.x1, p, th);
+      if (need_exact) exact_corrections(a.idx.exact, row, rt.lu, rt.xadd);
     }
     if (need_exact) {
-      s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
+      s32 = (float)score_f64((double)rt.qc, rt.lu.x, rt.lu.y, rt.xadd, rt.x1, p);
       bool nan_seen = false;  // a NaN score is in no answer and raises nothing here
       pass = exact_key_passes(valid, s32, th.key, nan_seen);
     }
@@ -180,42 +141,11 @@ hipError_t launch_range_t(const RangeArgs &a, bool fill, unsigned gx, int n_quer
   return hipGetLastError();
 }
 
-// the compiled row widths are the sweep's (launch_scan_w, launch_scan_mb_w)
-template <int QB>
-hipError_t launch_range_w(const RangeArgs &a, bool fill, unsigned gx, int nq, hipStream_t s) {
-  switch (a.idx.geom.w16) {
-    case 1: return launch_range_t<QB, 1, 1>(a, fill, gx, nq, s);    // dim <= 128
-    case 6: return launch_range_t<QB, 6, 1>(a, fill, gx, nq, s);    // dim 768
-    case 8: return launch_range_t<QB, 8, 1>(a, fill, gx, nq, s);    // dim 1024
-    case 12: return launch_range_t<QB, 12, 1>(a, fill, gx, nq, s);  // dim 1536
-    default: return launch_range_t<QB, 0, 1>(a, fill, gx, nq, s);
-  }
-}
-template <int QB, int SB>
-hipError_t launch_range_mb_w(const RangeArgs &a, bool fill, unsigned gx, int nq, hipStream_t s) {
-  switch (a.idx.geom.w16) {
-    case 12: return launch_range_t<QB, 12, SB>(a, fill, gx, nq, s);
-    case 16: return launch_range_t<QB, 16, SB>(a, fill, gx, nq, s);
-    default: return launch_range_t<QB, 0, SB>(a, fill, gx, nq, s);
-  }
-}
-
 hipError_t launch_range(const RangeArgs &a, int planes, bool fill, int64_t gx, int n_queries, hipStream_t s) {
   if (n_queries <= 0 || gx <= 0) return hipSuccess;
   if (n_queries > 65535 || gx > a.n_chunks || (uint64_t)gx * kChunkRows > kGridWorkItemsMax) return hipErrorInvalidValue;  // grid.y, and grid.x in work-items
-  switch (a.idx.geom.store_bits) {
-    case 1:
-      switch (planes) {
-        case 1: return launch_range_w<1>(a, fill, (unsigned)gx, n_queries, s);
-        case 2: return launch_range_w<2>(a, fill, (unsigned)gx, n_queries, s);
-        case 4: return launch_range_w<4>(a, fill, (unsigned)gx, n_queries, s);
-        default: return launch_range_w<8>(a, fill, (unsigned)gx, n_queries, s);
-      }
-    case 2: return planes > 4 ? launch_range_mb_w<8, 2>(a, fill, (unsigned)gx, n_queries, s) : launch_range_mb_w<4, 2>(a, fill, (unsigned)gx, n_queries, s);
-    case 4: return planes > 4 ? launch_range_mb_w<8, 4>(a, fill, (unsigned)gx, n_queries, s) : launch_range_mb_w<4, 4>(a, fill, (unsigned)gx, n_queries, s);
-    case 8: return launch_range_t<8, 0, 8>(a, fill, (unsigned)gx, n_queries, s);
-    default: return hipErrorInvalidValue;
-  }
+  return rowlist_ladder(a.idx.geom, planes,
+                        [&](auto qb, auto w, auto sb) { return launch_range_t<qb(), w(), sb()>(a, fill, (unsigned)gx, n_queries, s); });
 }
 
 }  // namespace

@@ -16,6 +16,7 @@
 #include "bbq_device.h"
 #include "bbq_kernel_common.h"
 #include "bbq_launch.h"
+#include "bbq_rowlist.h"
 #include "bbq_scan_body.h"
 
 #pragma clang fp contract(off)
@@ -44,7 +45,9 @@ __global__ __launch_bounds__(kChunkRows) void bbq_span_score_kernel(const SpanSc
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  {  // stage the query's planes once per workgroup
+  {  // stage the query's planes once per workgroup.  (Written out, not stage_query_planes: with no branch of the kernel's own between the
+     // wave number and its readfirstlane, this build's compiler moves the shift behind it and the 24 unfiltered kernels of the inline layout
+     // at a compiled width come out with 52 scalar registers for 54 - harmless, but not the kernel it was)
     const u32x4 *__restrict__ gp = reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)q * w16 * QU;
     for (int i = tid; i < w16 * QU; i += NT) s_planes[i] = gp[i];
   }
@@ -68,48 +71,10 @@ __global__ __launch_bounds__(kChunkRows) void bbq_span_score_kernel(const SpanSc
       if (t < wave_u) before += (uint32_t)__popcll(a.accept[(int64_t)it.first_tile + t] & (t == 0 ? from_lo : ~0ull));
   }
   const uint8_t *__restrict__ tp = a.idx.tiles + tile * (int64_t)a.idx.geom.tile_stride;
-  const uint8_t *__restrict__ cr = tp + tile_corr_offset(w16);
   const bool resident = chunk_is_resident(tile / kTilesPerChunk, a.idx);
-  const bool rs = COMPACT && a.idx.row_sums != nullptr;  // uniform over the launch
+  const RowTerms rt = tile_row_terms<QB, W, SB, COMPACT>(a.idx, tp, row, lane, w16, resident, s_planes);
 
-  f64x2 lu = {0.0, 0.0};
-  double xadd = 0.0, x1 = 0.0;
-  uint32_t cw = 0;
-  uint32_t qc, ones = 0;
-  constexpr int CORR = COMPACT ? 0 : 2;
-  if constexpr (W > 0) {
-    u32x4 c[W];
-    if (rs) {
-      load_tile<W, CORR, true>(tp, lane, false, resident, a.idx.nt_delta, c, cw, lu, xadd, x1, a.idx.row_sums + row, &ones);
-      if constexpr (COMPACT) exact_corrections<true>(a.idx.exact, row, lu, xadd);
-      if constexpr (SB == 1) qc = tile_popcounts<QB, W, false>(c, s_planes, ones);
-      else tile_dot_multibit<QB, W, SB, false>(c, s_planes, qc, ones);
-    } else {
-      load_tile<W, CORR>(tp, lane, a.idx.geom.has_x1 != 0, resident, a.idx.nt_delta, c, cw, lu, xadd, x1);
-      if constexpr (COMPACT) exact_corrections<true>(a.idx.exact, row, lu, xadd);
-      if constexpr (SB == 1) qc = tile_popcounts<QB, W>(c, s_planes, ones);
-      else tile_dot_multibit<QB, W, SB>(c, s_planes, qc, ones);
-    }
-  } else {  // a row width without a compiled kernel: streamed chunk by chunk
-    if constexpr (!COMPACT) {
-      lu = BBQ_STREAM_LOAD(reinterpret_cast<const f64x2 *>(cr) + lane);
-      xadd = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + kCorrAddOffset) + lane);
-      if (a.idx.geom.has_x1) x1 = BBQ_STREAM_LOAD(reinterpret_cast<const double *>(cr + kCorrSumOffset) + lane);
-    } else {
-      exact_corrections<true>(a.idx.exact, row, lu, xadd);
-    }
-    if (rs) {
-      ones = BBQ_STREAM_LOAD(a.idx.row_sums + row);
-      if constexpr (SB == 1) qc = tile_popcounts_any<QB, false>(tp, lane, w16, s_planes, ones);
-      else tile_dot_multibit_any<QB, SB, false>(tp, lane, w16, s_planes, qc, ones);
-    } else {
-      if constexpr (SB == 1) qc = tile_popcounts_any<QB>(tp, lane, w16, s_planes, ones);
-      else tile_dot_multibit_any<QB, SB>(tp, lane, w16, s_planes, qc, ones);
-    }
-  }
-  if (COMPACT || !a.idx.geom.has_x1) x1 = (double)ones;  // quantizedComponentSum of a freshly quantized row is its popcount / component sum
-
-  const float s32 = (float)score_f64((double)qc, lu.x, lu.y, xadd, x1, p);
+  const float s32 = (float)score_f64((double)rt.qc, rt.lu.x, rt.lu.y, rt.xadd, rt.x1, p);
   if constexpr (FILT) {
     if ((mine >> lane) & 1ull) {
       const int64_t out = it.out + before + __popcll(mine & ((1ull << lane) - 1ull));
@@ -135,26 +100,6 @@ hipError_t launch_span_score_t(const SpanScoreArgs &a, unsigned n_items, hipStre
     else hipLaunchKernelGGL((bbq_span_score_kernel<QB, W, SB, false, false>), grid, block, smem, s, a);
   }
   return hipGetLastError();
-}
-
-// the compiled row widths are the sweep's (launch_scan_w, launch_scan_mb_w)
-template <int QB>
-hipError_t launch_span_score_w(const SpanScoreArgs &a, unsigned n, hipStream_t s) {
-  switch (a.idx.geom.w16) {
-    case 1: return launch_span_score_t<QB, 1, 1>(a, n, s);    // dim <= 128
-    case 6: return launch_span_score_t<QB, 6, 1>(a, n, s);    // dim 768
-    case 8: return launch_span_score_t<QB, 8, 1>(a, n, s);    // dim 1024
-    case 12: return launch_span_score_t<QB, 12, 1>(a, n, s);  // dim 1536
-    default: return launch_span_score_t<QB, 0, 1>(a, n, s);
-  }
-}
-template <int QB, int SB>
-hipError_t launch_span_score_mb_w(const SpanScoreArgs &a, unsigned n, hipStream_t s) {
-  switch (a.idx.geom.w16) {
-    case 12: return launch_span_score_t<QB, 12, SB>(a, n, s);
-    case 16: return launch_span_score_t<QB, 16, SB>(a, n, s);
-    default: return launch_span_score_t<QB, 0, SB>(a, n, s);
-  }
 }
 
 // ---- the select pass ----------------------------------------------------------------------------------------------------------------
@@ -349,19 +294,7 @@ hipError_t launch_span_score(const SpanScoreArgs &a, int planes, int64_t n_items
   if (a.accept && !a.ords) return hipErrorInvalidValue;
   if ((uint64_t)n_items * kChunkRows > kGridWorkItemsMax) return hipErrorInvalidValue;  // grid.x in work-items
   const unsigned n = (unsigned)n_items;
-  switch (a.idx.geom.store_bits) {
-    case 1:
-      switch (planes) {
-        case 1: return launch_span_score_w<1>(a, n, s);
-        case 2: return launch_span_score_w<2>(a, n, s);
-        case 4: return launch_span_score_w<4>(a, n, s);
-        default: return launch_span_score_w<8>(a, n, s);
-      }
-    case 2: return planes > 4 ? launch_span_score_mb_w<8, 2>(a, n, s) : launch_span_score_mb_w<4, 2>(a, n, s);
-    case 4: return planes > 4 ? launch_span_score_mb_w<8, 4>(a, n, s) : launch_span_score_mb_w<4, 4>(a, n, s);
-    case 8: return launch_span_score_t<8, 0, 8>(a, n, s);
-    default: return hipErrorInvalidValue;
-  }
+  return rowlist_ladder(a.idx.geom, planes, [&](auto qb, auto w, auto sb) { return launch_span_score_t<qb(), w(), sb()>(a, n, s); });
 }
 
 hipError_t launch_span_select(const SpanSelectArgs &a, int n_selected, hipStream_t s) {

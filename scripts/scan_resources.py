@@ -4,6 +4,10 @@
   scripts/scan_resources.py CSRC_DIR                  one line per instantiation: VGPRs / occupancy (waves per SIMD) / scratch bytes per lane;
                                                       fails if a kernel with several tiles per wave exceeds its recorded registers / waves (TWIN_BUDGET) or has any v_pk_*_f32 left
   scripts/scan_resources.py BEFORE_DIR AFTER_DIR      the two side by side, the rows that differ marked, lost waves and new scratch counted
+  scripts/scan_resources.py BEFORE_DIR AFTER_DIR --files A.hip,B.hip
+                                                      the same for EVERY kernel of the named files, by demangled name: the code object's register,
+                                                      scratch and LDS records and the occupancy remark, and the instruction counts; fails if the
+                                                      two trees' kernel symbols or any record differ
 
 CSRC_DIR is a copy of better-binary-quantization_amd/csrc (e.g. `git archive HEAD better-binary-quantization_amd/csrc | tar -x -C DIR`
 for the parent).  Compiles bbq_kernels.hip and bbq_filter_kernels.hip for the device only, with the Makefile's flags.
@@ -101,7 +105,71 @@ def fmt(v):
     return "%d / %d / %d" % v if v else "-"
 
 
+RECORD = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
+
+
+def kernel_records(csrc, f):
+    """every kernel of one file, by demangled name: its code object's .vgpr_count / .sgpr_count / .private_segment_fixed_size /
+    .group_segment_fixed_size, the compiler's Occupancy remark, and its instructions (lines of its text that are no label, directive or comment)"""
+    flags = [x for x in FLAGS if x not in ("-c", "-o", "/dev/null")] + ["-S", "-o", "-"]
+    r = subprocess.run([HIPCC] + flags + [f], cwd=csrc, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    if r.returncode != 0:
+        sys.exit("compile of %s/%s failed:\n%s" % (csrc, f, r.stderr[-3000:]))
+    occ, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+        m = re.search(r"remark:\s+Occupancy \[waves/SIMD\]: (\d+)", line)
+        if m and name:
+            occ[name] = int(m.group(1))
+    meta, cur, insts, name = [], None, {}, None
+    for line in r.stdout.splitlines():
+        m = re.match(r"(  - |    )\.(\w+):\s+(\S+)$", line)       # a kernel's own keys in amdhsa.kernels (its arguments' lie deeper)
+        if m:
+            if m.group(1) == "  - ":
+                cur = {}
+                meta.append(cur)
+            cur[m.group(2)] = m.group(3)
+            continue
+        m = re.match(r"(\w+):", line)
+        if m and m.group(1) in occ:
+            name = m.group(1)
+            insts[name] = 0
+        elif name and line.startswith("\t.size\t" + name):
+            name = None
+        elif name and re.match(r"\t[a-z]\w*(\s|$)", line):
+            insts[name] += 1
+    meta = {k["name"]: k for k in meta if "name" in k}
+    assert set(meta) == set(occ) == set(insts), (f, sorted(set(meta) ^ set(occ)))
+    names = sorted(meta)
+    dem = subprocess.run(["c++filt"], input="\n".join(names), stdout=subprocess.PIPE, text=True).stdout.splitlines()
+    return {re.sub(r"\(.*\)$", "", d.replace("void bbq::(anonymous namespace)::", "").replace("(bool)", "")):
+            tuple(int(meta[n][k]) for k in RECORD) + (occ[n], insts[n]) for n, d in zip(names, dem)}
+
+
+def compare_files(before_dir, after_dir, files):
+    with ThreadPoolExecutor(4) as ex:
+        before = list(ex.map(lambda f: kernel_records(before_dir, f), files))
+        after = list(ex.map(lambda f: kernel_records(after_dir, f), files))
+    print("per kernel: %s / occupancy [waves/SIMD]; then instructions before -> after" % " / ".join("." + k for k in RECORD))
+    bad = 0
+    for f, b, a in zip(files, before, after):
+        differ = sorted(k for k in set(b) | set(a) if (b.get(k) or (None,))[:-1] != (a.get(k) or (None,))[:-1])
+        bad += len(differ)
+        print("\n%s: %d kernels before, %d after; the same symbols: %s; records that differ: %d; instructions %d -> %d" % (
+            f, len(b), len(a), "yes" if set(b) == set(a) else "NO", len(differ), sum(v[-1] for v in b.values()), sum(v[-1] for v in a.values())))
+        for k in sorted(set(b) | set(a)):
+            vb, va = b.get(k), a.get(k)
+            rec = lambda v: " / ".join(str(x) for x in v[:-1]) if v else "-"
+            print("  %-64s %-24s %-24s %6s -> %-6s %s" % (k, rec(vb), rec(va), vb[-1] if vb else "-", va[-1] if va else "-", "DIFFERS" if k in differ else ""))
+    if bad:
+        sys.exit("%d kernels whose records differ" % bad)
+
+
 def main():
+    if len(sys.argv) == 5 and sys.argv[3] == "--files":
+        return compare_files(sys.argv[1], sys.argv[2], sys.argv[4].split(","))
     if len(sys.argv) == 2:
         res = table(sys.argv[1])
         for k, v in sorted(res.items()):

@@ -1,6 +1,7 @@
 """CPU: the width matrix of tests/rowlist_cells.py held to the code and to its own conditions.  The cells' compiled() values are exactly
-the (store_bits, planes or QB, W) arms the five row-list launchers name - read out of the .hip files, so a width added later without a
-cell fails here; every W class meets every similarity; and every cell's seeded input still exercises what it is there for: the plane
+the (store_bits, planes or QB, W) arms of the one ladder the row-list launchers share (rowlist_ladder, csrc/bbq_rowlist.h) - read out of
+that header, so a width added later without a cell fails here, and every launcher file is held to calling it and having no arm of its
+own; every W class meets every similarity; and every cell's seeded input still exercises what it is there for: the plane
 count its kernel is compiled for, thresholds that select some rows and leave some, span and group cases in which a tie sends a query
 to the heap - and, in every W class, cases the device answers.  A cell that fails a condition gets another seed in rowlist_cells.SEEDS."""
 import itertools
@@ -19,16 +20,20 @@ from test_range_key_cpu import range_answer
 
 CSRC = os.path.join(O.ROOT, "better-binary-quantization_amd", "csrc")
 LAUNCHERS = ("bbq_gather_kernels.hip", "bbq_range_kernels.hip", "bbq_span_kernels.hip", "bbq_group_kernels.hip")
+CAND_LAUNCHER = "bbq_maxsim_cand_kernels.hip"
 FUSED_LAUNCHER = "bbq_maxsim_kernels.hip"
+LADDER = "bbq_rowlist.h"
 
-# the arms of the switches, one regular expression per shape of arm
-W_ARM = re.compile(r"^\s*(?:case (\d+)|default): return launch_\w+_t<QB, (\d+), (1|SB)>\(")          # switch (...geom.w16), 1-bit and multi-bit
-PLANES_ARM = re.compile(r"^\s*(?:case (\d+)|default): return launch_\w+_w<(\d+)>\(")                  # switch (planes), 1-bit rows
-QB_ARM = re.compile(r"^\s*case (\d+): return planes > 4 \? launch_\w+_mb_w<(\d+), (\d+)>\(.*?\) : launch_\w+_mb_w<(\d+), (\d+)>\(")
-BYTE_ARM = re.compile(r"^\s*case 8: return launch_\w+_t<(\d+), (\d+), (\d+)>\(")                      # 8-bit rows
+# the arms of the ladder's switches, one regular expression per shape of arm
+W_ARM = re.compile(r"^\s*(?:case (\d+)|default): return f\(Int<QB>\{\}, Int<(\d+)>\{\}, Int<(1|SB)>\{\}\);")  # switch (w16), 1-bit and multi-bit
+PLANES_ARM = re.compile(r"^\s*(?:case (\d+)|default): return rowlist_width<(\d+)>\(geom\.w16, f\);")          # switch (planes), 1-bit rows
+QB_ARM = re.compile(r"^\s*case (\d+): return planes > 4 \? rowlist_width_mb<(\d+), (\d+), MB>\(geom\.w16, f\) : rowlist_width_mb<(\d+), (\d+), MB>\(geom\.w16, f\);")
+BYTE_ARM = re.compile(r"^\s*case 8: return f\(Int<(\d+)>\{\}, Int<(\d+)>\{\}, Int<(\d+)>\{\}\);")              # 8-bit rows
 FUSED_ARM = re.compile(r"^\s*(?:case (\d+)|default): return launch_maxsim_score_t<(\d+)>\(")
 ANY_ARM = re.compile(r"^\s*(case \d+|default):")
 NO_KERNEL = re.compile(r"^\s*(case 1:\s*$|default: return hipErrorInvalidValue;)")                   # the nested planes switch; an unknown store_bits
+LADDER_CALL = re.compile(r"\browlist_ladder(<[^>(]*>)?\(")                                            # a call, with or without a policy
+NO_MULTI_BIT_WIDTHS = "<MultiBitRows::kRunTimeWidth>"
 
 
 def _lines(name):
@@ -36,8 +41,8 @@ def _lines(name):
         return f.read().splitlines()
 
 
-def launcher_arms(name):
-    """every (store_bits, planes or QB, W) a launcher file dispatches to; every case / default line of the file has to be one this
+def ladder_arms(name=LADDER):
+    """every (store_bits, planes or QB, W) the ladder dispatches to; every case / default line of the header has to be one this
     parser knows, so an arm of a new shape fails here instead of going unseen"""
     w_one, w_multi, planes, qb_sb, bytes_arm = set(), set(), set(), set(), set()
     for line in _lines(name):
@@ -81,12 +86,37 @@ def fused_arms():
     return {(1, 4, w) for w in widths}
 
 
+def ladder_calls(name):
+    """the policies of a launcher file's calls of the ladder ('' = the default: multi-bit rows have compiled widths); the file names no
+    arm of its own"""
+    lines = _lines(name)
+    own = [l.strip() for l in lines if ANY_ARM.match(l)]
+    assert not own, "%s: arms outside the ladder: %s" % (name, own)
+    assert any('#include "%s"' % LADDER in l for l in lines), name
+    return [m.group(1) or "" for l in lines for m in LADDER_CALL.finditer(l)]
+
+
 @pytest.mark.parametrize("name", LAUNCHERS)
 def test_the_cells_cover_every_arm_of_the_launcher(name):
-    arms = launcher_arms(name)
+    assert ladder_calls(name) == [""]                                    # the launcher takes the shared ladder, whole
+    arms = ladder_arms()
     covered = {C.compiled(c) for c in C.CELLS}
     assert covered == arms, "without a cell: %s; cells without an arm: %s" % (sorted(arms - covered), sorted(covered - arms))
     assert len(arms) == 4 * 5 + 2 * 2 * 3 + 1
+
+
+def test_the_candidate_launcher_takes_the_ladder_without_multi_bit_widths():
+    assert ladder_calls(CAND_LAUNCHER) == [NO_MULTI_BIT_WIDTHS]
+    # ... and the ladder gives that policy the run-time width for every multi-bit row: its switch over the compiled widths stands under the
+    # other policy, which is the default
+    text = "\n".join(_lines(LADDER))
+    assert text.count("template <MultiBitRows MB = MultiBitRows::kCompiledWidths, class F>") == 1
+    m = re.search(r"\n  if constexpr \(MB == MultiBitRows::kCompiledWidths\) \{\n    switch \(w16\) \{\n(.*?)\n    \}\n  \} else \{\n"
+                  r"    return f\(Int<QB>\{\}, Int<0>\{\}, Int<SB>\{\}\);\n  \}\n\}", text, re.S)
+    assert m, "rowlist_width_mb no longer has the shape this test reads"
+    arms = m.group(1).splitlines()
+    assert arms and all(W_ARM.match(l) and W_ARM.match(l).group(3) == "SB" for l in arms), arms
+    assert sum(bool(W_ARM.match(l)) and W_ARM.match(l).group(3) == "SB" for l in _lines(LADDER)) == len(arms)   # no multi-bit arm elsewhere
 
 
 def test_the_cells_cover_every_width_of_the_fused_maxsim_kernel():
