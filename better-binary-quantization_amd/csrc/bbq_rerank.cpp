@@ -202,10 +202,11 @@ int bbq_rerank_scores(bbq_vectors *v, int32_t n_queries, const float *queries, c
   const int64_t total = offsets[n_queries];
   if (total == 0) return BBQ_OK;
   if (!rows || !out_true) return fail(BBQ_ERR_INVALID_ARG, "bbq_rerank_scores: null argument");
-  for (int64_t i = 0; i < total; ++i)
-    if (rows[i] < 0 || rows[i] >= v->n) return fail(BBQ_ERR_INVALID_ARG, "基础向量%d不存在", rows[i]);
   std::lock_guard<std::mutex> lk(v->ctx->mu);
   HIPCHK(hipSetDevice(v->device));
+  // under the lock: the row count the check sees is the one the kernel reads (an append or a compaction on another thread comes before or after)
+  for (int64_t i = 0; i < total; ++i)
+    if (rows[i] < 0 || rows[i] >= v->n) return fail(BBQ_ERR_INVALID_ARG, "基础向量%d不存在", rows[i]);
   HIPCHK(grow_staging(v->d_q, (int64_t)n_queries * v->dim));
   HIPCHK(grow_staging(v->d_off, (int64_t)n_queries + 1));
   HIPCHK(grow_staging(v->d_rows, total));
