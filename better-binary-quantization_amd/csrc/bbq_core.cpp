@@ -147,6 +147,13 @@ int tiles_per_wave_for(const bbq_index *ix) {
   }
 }
 
+// chunks (4 dwords each) of the unit digit plane that the many-tile digit sweep leaves behind its bound: the staged twin of bbq_scan_body.h
+// (768-d, 8 tiles per wave, 1 chunk) wherever the launch would take that width's 8-tile kernel, 0 everywhere else.  Not an option: the one
+// twin that is built is the one whose slowest run beat the parent's fastest by more than the parent's spread (profiles/staged_bound.json;
+// DESIGN.md, Measurement: 10 M rows, 19.55-19.63 K q/s against 19.21-19.32 K); 8 dwords at 768-d and either at 1024-d did not
+// (docs/dropped.md, "staged bound") and are not built.  tiles_per_wave 1, 2 or 4 selects a kernel without stages.
+int staged_bound_for(const bbq_index *ix) { return ix->geom.w16 == 6 && tiles_per_wave_for(ix) == 8 ? 1 : 0; }
+
 // ------------------------------------------------------------------------------------------------ plan
 
 static int cap_for(int64_t k, int64_t rows_before) {
@@ -421,6 +428,7 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
   if (use_mfma) bytes = ms.bytes;
   // the digit masks of a 4-plane query behind everything else: the per-query sparse sweeps take them where they have a digit twin
   int32_t qdigits_at = 0;  // in 16-byte units behind the planes (ScanArgs::qdigits_at)
+  int staged_chunks = 0;   // the staged twins' stage-one words are staged behind the masks, for this many chunks (launch_scan)
   // (only where every sparse segment is a per-query sweep: a call with sweep_share 4 / 8 sweeps shared, and a segment of it that falls
   // back to the per-query sweep runs planes)
   if (!use_mfma && c.share == 1 && digit_planes_for_call(ix, c.planes)) {
@@ -428,6 +436,16 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
     for (int i = 0; i < nq; ++i) fill_query_digits(ix, s.h_qbuf + bytes + (size_t)i * db, hq + i, c.qquant + (size_t)(q_first + i) * ix->geom.dim);
     qdigits_at = (int32_t)(bytes / 16);
     bytes += (size_t)nq * db;
+    // ... and behind the masks of all nq, the stage-one words of each for the staged twins - where every query of the sub-batch has its f32
+    // images: one without them passes every row in stage one and would pay stage two for every tile
+    staged_chunks = staged_bound_for(ix);
+    for (int i = 0; i < nq && staged_chunks; ++i)
+      if (!hq[i].fast_bound) staged_chunks = 0;
+    if (staged_chunks) {
+      for (int i = 0; i < nq; ++i)
+        staged_bound_words(ix->geom.w16, staged_chunks, s.h_qbuf + (size_t)qdigits_at * 16 + (size_t)i * db, hq + i, reinterpret_cast<uint32_t *>(s.h_qbuf + bytes + (size_t)i * kStagedWordsBytes));
+      bytes += (size_t)nq * kStagedWordsBytes;
+    }
   }
   hipStream_t st = s.stream;
   HIPCHK(hipMemcpyAsync(s.d_block, s.h_block, (size_t)s.ctrl_bytes + bytes, hipMemcpyHostToDevice, st));  // control words := 0, queries
@@ -490,7 +508,9 @@ int enqueue_subbatch(const SearchCall &c, Slot &s, int64_t q_first, int nq, cons
     else if (c.filter)  // (its plan has sparse segments only; sweep_share 4 / 8 never reach a filtered call, 32 falls back to here)
       HIPCHK(launch_scan_filtered(a, c.filter->d_bits, c.planes, nq, (int)g.n_chunks, st));
     else
-      HIPCHK(launch_scan(a, c.planes, g.dense, nq, (int)g.n_chunks, st, c.share == 1 ? tiles_per_wave_for(ix) : 1));
+      // (the stages only behind a segment that left a threshold: against the first segment's every tile has a passing row)
+      HIPCHK(launch_scan(a, c.planes, g.dense, nq, (int)g.n_chunks, st, c.share == 1 ? tiles_per_wave_for(ix) : 1,
+                         !g.dense && &g != &p.segs.front() && staged_chunks == 1));
     if (chained) {
       HIPCHK(hipEventRecord(s.ev_big, st));
       ix->ctx->last_big_slot = my_slot;

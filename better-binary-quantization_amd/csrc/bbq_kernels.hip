@@ -504,7 +504,7 @@ hipError_t launch_scan_shared(const ScanArgs &a, int planes, int share, int n_qu
   return compact ? launch_shared_q<true, 4>(a, planes, n_queries, n_chunks, s) : launch_shared_q<false, 4>(a, planes, n_queries, n_chunks, s);
 }
 
-hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries, int n_chunks, hipStream_t s, int tiles_per_wave) {
+hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries, int n_chunks, hipStream_t s, int tiles_per_wave, bool staged) {
   if (n_chunks <= 0 || n_queries <= 0) return hipSuccess;
   const int mode = (dense ? 1 : 0) | (a.idx.geom.layout == kLayoutCompact ? 2 : 0);
   if (a.idx.geom.store_bits > 1) {
@@ -518,10 +518,12 @@ hipError_t launch_scan(const ScanArgs &a, int planes, bool dense, int n_queries,
   switch (mode) {
     case 0: return launch_scan_q<false, 0>(a, nullptr, planes, n_queries, n_chunks, s);
     case 1: return launch_scan_q<false, 1>(a, nullptr, planes, n_queries, n_chunks, s);
-    case 2: return launch_scan_q<false, 2>(a, nullptr, planes, n_queries, n_chunks, s, tiles_per_wave);
+    case 2: return launch_scan_q<false, 2>(a, nullptr, planes, n_queries, n_chunks, s, tiles_per_wave, staged);
     default: return launch_scan_q<false, 3>(a, nullptr, planes, n_queries, n_chunks, s);
   }
 }
+
+int64_t staged_launch_count() { return staged_launches.load(std::memory_order_relaxed); }
 
 hipError_t launch_finalize(const FinalizeArgs &a, int n_queries, hipStream_t s) {
   static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(bbq_finalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

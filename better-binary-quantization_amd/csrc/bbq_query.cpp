@@ -9,7 +9,7 @@ namespace bbq {
 
 // per query: bit-planes (up to 8) + digit masks (4-plane queries) + int8 values in MFMA fragment order + score uniforms + group maxima
 int64_t qbuf_bytes_per_query_w(int w16) {
-  return (int64_t)w16 * 8 * 16 + digit_bytes_per_query_w(w16) + (int64_t)w16 * 128 + (int64_t)sizeof(QueryParams) + 16;
+  return (int64_t)w16 * 8 * 16 + digit_bytes_per_query_w(w16) + kStagedWordsBytes + (int64_t)w16 * 128 + (int64_t)sizeof(QueryParams) + 16;
 }
 int64_t digit_bytes_per_query_w(int w16) { return (int64_t)w16 * kDigitMasks * 16; }
 
@@ -143,13 +143,15 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
 // they come, and such a bit is part of the row's sum wherever the compact layout holds it); as a 0 of the query it contributes
 // 4 - 1 - 3 = 0, as it does in the plane form, whose planes are 0 there.  A clear row bit there adds 1 + 3 to a0 + 3 a1 and to K alike.
 void fill_query_digits(const bbq_index *ix, uint8_t *digits_dst, QueryParams *pp, const uint8_t *q) {
+  fill_query_digits_w(ix->geom.dim, ix->geom.w16, digits_dst, pp, q);
+}
+void fill_query_digits_w(int dim, int w16, uint8_t *digits_dst, QueryParams *pp, const uint8_t *q) {
   static const struct Lut {
     uint8_t of[16];
     constexpr Lut() : of{} { for (int v = 0; v < 16; ++v) of[v] = (uint8_t)digit_mask_bits(v); }
   } lut;
-  const int dim = ix->geom.dim;
   uint32_t n0 = 0, n1 = 0;
-  for (int byte = 0; byte < ix->geom.w16 * 16; ++byte) {
+  for (int byte = 0; byte < w16 * 16; ++byte) {
     // the mask bits of the byte's eight dimensions side by side, then bit m of all eight gathered MSB-first by one multiply (fill_query)
     uint64_t x = 0;
     const int nd = std::max(0, std::min(8, dim - byte * 8));
@@ -161,6 +163,46 @@ void fill_query_digits(const bbq_index *ix, uint8_t *digits_dst, QueryParams *pp
     n1 += (uint32_t)__builtin_popcount(dst[3 * 16]);
   }
   pp->digit_k = n0 + 3u * n1;
+}
+
+// The stage-one words of a query for the staged twins of the many-tile digit sweep (sweep_wave_tiles, STG = staged_chunks; bbq_scan_body.h):
+// the unit digit plane of the row's last staged_chunks chunks stays unresolved in stage one.  Per dword j of them a row's contribution to D is
+// pop(x & P0_j) - pop(x & N0_j), anywhere in [-L_j, U_j] with U_j = pop(P0_j), L_j = pop(N0_j) (a padding position is staged in N0 and counts
+// in L: a row bit there is legal).  With U, L their sums and D_res the rest of D,
+//     D in [D_res - L, D_res + U],   D' = D_res + m,  m = floor((U - L) / 2),   |D - D'| <= h = U - m  (>= m + L; an integer),
+// and stage one's integer is D' = a0_res + 3 a1 + 9 a2 - K' with K' = K - L - m (u32 arithmetic, as K's), K - K' = L + m for stage two.
+// The row side of the folded bound, r = s + K1 e + k2m w, has |r(D) - r(D')| <= |ly| |D - D'| w (1 + K1): s and e depend on D through
+// g = ly D + b sum alone, ds/dg = au - al and e is convex and piecewise linear in g with slopes within +-w.  So
+//     k2m' = 3 k2m + h |ly| (1 + 2 K1),  rounded up,
+// in place of k2m makes stage one's r' at D' at least the bound's r at D, in the arithmetic the kernel does:
+//  * exactly evaluated, r'(D') >= r(D) + 2 k2m w + K1 h |ly| w;
+//  * the f32 evaluation of r at D and of r' at D' are each within k2m w = 2^-20 w M of the exact one (the budget above folded_bound_passes:
+//    9.1 u W M for s, 1.02 u W M and u slack for the row side, of 16 u W M; D' is an integer within h <= 64 staged_chunks of a legal D,
+//    inside the 2 x that M leaves above qcmax), which the 2 k2m w pay; the product w k2m' rounds once, u (3 k2m + 1.02 h |ly|) w, paid by the
+//    second K1 h |ly| w = 2^-7 h |ly| w wherever h >= 1, and where h = 0 stage one's D' IS D and k2m' >= k2m.
+//  * NaN, overflow, infinite thresholds.  A NaN threshold image (a query without f32 images, a non-finite additive bound) passes every row
+//    in both stages; the kernel turns a tile threshold of +inf into NaN.  Against any other threshold T < +inf: r' = NaN passes; an
+//    overflow in stage one needs an infinite product or sum, then e' = +inf and r' is +inf or NaN, which passes.  A row whose r overflows
+//    at D while r' stays finite at D' - |al| or |au| above 2^27, a product within h |ly| w of the largest float - is judged by r', which
+//    is then a valid bound computed without overflow: stage one may reject it, and its exact score is below the threshold.  Such a row is
+//    the one case where the kernel without stages would have deferred a row that the staged one does not; neither lists it.
+// A query without f32 images (fast_bound 0) gets k2m' = 0 like its k2m: its threshold image is NaN in the kernel.
+void staged_bound_words(int w16, int staged_chunks, const uint8_t *digits, const QueryParams *pp, uint32_t *words) {
+  uint32_t U = 0, L = 0;
+  for (int j = w16 - staged_chunks; j < w16; ++j)
+    for (int b = 0; b < 16; ++b) {
+      U += (uint32_t)__builtin_popcount(digits[((size_t)j * kDigitMasks + 0) * 16 + b]);
+      L += (uint32_t)__builtin_popcount(digits[((size_t)j * kDigitMasks + 1) * 16 + b]);
+    }
+  const int32_t m = (int32_t)floor(((double)U - (double)L) / 2.0);
+  const uint32_t h = (uint32_t)((int32_t)U - m);
+  const uint32_t rest = (uint32_t)((int32_t)L + m);  // K - K'
+  const double k1 = 0x1p-7 * 1.0001;  // >= kFastK1 (bbq_kernel_common.h)
+  const double wide = 3.0 * (double)pp->k2mf + (double)h * fabs((double)pp->lyf) * (1.0 + 2.0 * k1);
+  words[0] = pp->digit_k - rest;
+  words[1] = __builtin_bit_cast(uint32_t, pp->fast_bound ? f32_up(wide * (1.0 + 0x1p-40)) : 0.0f);
+  words[2] = rest;
+  words[3] = h;  // (not read by the kernel: for the tests)
 }
 
 // MFMA shared sweep, int8 form (query values up to 127): the int8 query values in the order the code bits fall out of the packed
@@ -281,3 +323,29 @@ int validate_query_args(const bbq_index *ix, int32_t nq, const uint8_t *qquant, 
 }
 
 }  // namespace bbq
+
+extern "C" {
+
+// host only, for the tests: the digit masks fill_query_digits stages for one 4-plane query and the stage-one words staged_bound_words makes of them
+int bbq_staged_bound_words(const uint8_t *qquant, int32_t dim, float lyf, float k2mf, int32_t fast_bound, int32_t staged_chunks,
+                           uint8_t *out_masks, uint32_t *out_digit_k, uint32_t *out_words) {
+  using namespace bbq;
+  clear_error();
+  if (!qquant || !out_masks || !out_digit_k || !out_words) return fail(BBQ_ERR_INVALID_ARG, "bbq_staged_bound_words: null");
+  const int w16 = (dim + 127) / 128;
+  if (dim < 1 || staged_chunks < 1 || staged_chunks >= w16) return fail(BBQ_ERR_INVALID_ARG, "bbq_staged_bound_words: 1 <= staged_chunks < chunks of a row");
+  for (int32_t d = 0; d < dim; ++d)
+    if (qquant[d] > 15) return fail(BBQ_ERR_INVALID_ARG, "bbq_staged_bound_words: a 4-plane query");
+  QueryParams p{};
+  p.lyf = lyf;
+  p.k2mf = k2mf;
+  p.fast_bound = fast_bound;
+  fill_query_digits_w(dim, w16, out_masks, &p, qquant);
+  *out_digit_k = p.digit_k;
+  staged_bound_words(w16, staged_chunks, out_masks, &p, out_words);
+  return BBQ_OK;
+}
+
+int64_t bbq_staged_launches(void) { return bbq::staged_launch_count(); }
+
+}  // extern "C"

@@ -3,6 +3,7 @@
 // translation unit instantiates its own kernels only.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include "bbq_device.h"
 #include "bbq_kernel_common.h"
 
@@ -265,13 +266,15 @@ __device__ __forceinline__ void buffer_load_words(__amdgpu_buffer_rsrc_t tile, c
 // added by the caller.  12 chunks: tile_digit_dot's compiler barrier behind each chunk does not order the chunks' arithmetic, and the
 // scheduler, given the codes of a whole tile at once, formed the selections of two and three chunks ahead of their popcounts - 92 vector
 // registers in the 2-tile kernel; a scheduling barrier keeps each chunk's work together (this build's scheduler: scripts/scan_resources.py).
-template <int W>
+// STG (the staged twins, bbq_scan_staged_kernel below): the unit plane of the row's last STG chunks is left out - with k = K' (staged_bound_words,
+// bbq_query.cpp) the sum is the midpoint of the interval D lies in - and tile_digit_tail adds what was left out.
+template <int W, int STG = 0>
 __device__ __forceinline__ uint32_t tile_digit_sums(const u32x4 (&c)[W], const u32x4 *__restrict__ s_digits, uint32_t k) {
   uint32_t a0 = 0u - k, a1 = 0, a2 = 0;
 #pragma unroll
   for (int j = 0; j < W; ++j) {
     const u32x4 *__restrict__ m = s_digits + j * kDigitMasks;
-    a0 = popc4_acc(digit_select(c[j], m[0], m[1]), a0);
+    if (j < W - STG) a0 = popc4_acc(digit_select(c[j], m[0], m[1]), a0);
     a1 = popc4_acc(digit_select(c[j], m[2], m[3]), a1);
     a2 = popc4_acc(c[j] & m[4], a2);
     if constexpr (W >= 12) {
@@ -280,6 +283,16 @@ __device__ __forceinline__ uint32_t tile_digit_sums(const u32x4 (&c)[W], const u
     }
   }
   return a0 + 3u * a1 + 9u * a2;
+}
+// stage two of a staged twin: the unit plane of the last STG chunks on top of d (= stage one's sum - (K - K')): the integer tile_digit_sums<W> gives
+template <int W, int STG>
+__device__ __forceinline__ uint32_t tile_digit_tail(const u32x4 (&c)[W], const u32x4 *__restrict__ s_digits, uint32_t d) {
+#pragma unroll
+  for (int j = W - STG; j < W; ++j) {
+    const u32x4 *__restrict__ m = s_digits + j * kDigitMasks;
+    d = popc4_acc(digit_select(c[j], m[0], m[1]), d);
+  }
+  return d;
 }
 
 // fast_bound_passes for the tile loop: the same operations in the same order on the same values - the same verdict for every row - but
@@ -359,7 +372,18 @@ __device__ __forceinline__ bool folded_bound_passes(uint32_t d, uint32_t cw, uin
   return !(r <= tile_th);  // NaN anywhere passes -> exact path
 }
 
-template <int W, int TPW, int NT>
+// STG > 0 (the staged twins): the bound in two stages.  Stage one leaves the unit digit plane of the row's last STG chunks (n = 4 STG dwords)
+// unresolved: D', the midpoint of the interval the row's D lies in, against k2m' = k2m widened by the interval's half-width (both per query,
+// from the host: staged_bound_words, bbq_query.cpp, which holds the error budget) - the same per-row instructions as the bound itself, 2 n
+// fewer in front of it.  A tile without a passing row - nearly every tile behind a threshold of a few hundred thousand rows - goes on to the
+// next tile's loads.  Stage two, under ONE scalar branch in front of those loads, with the tile's codes still in registers: the rest of the
+// unit plane, the true D, and the unchanged bound with the unchanged k2m.  What is deferred is what stage two passes: the rows and the
+// integers of the kernel without stages.  A threshold of +inf becomes NaN for both stages (every row on to the exact path, which keeps
+// none): against +inf a row whose r is NaN at D and +inf at D' would pass the one bound and fail the other.
+#ifdef BBQ_COUNT_STAGES
+static __device__ unsigned long long stage_counts[4];
+#endif
+template <int W, int TPW, int NT, int STG = 0>
 __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepCoord wg, const bool idle, const int q, u32x4 *s_planes, uint32_t *s_def,
                                                  uint32_t *s_cnt, uint32_t &n_def) {
   constexpr int QU = kDigitMasks;
@@ -373,7 +397,16 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
   const QueryParams *__restrict__ qp = a.qparams + q;
   const FastBoundParams p = {qp->ayf, qp->lyf, qp->c1f, qp->k2mf, qp->tinyf, qp->csf, qp->caf};
   const int32_t sim = qp->sim, fast_bound = qp->fast_bound;
-  const uint32_t digit_k = qp->digit_k;
+  uint32_t digit_k = qp->digit_k;
+  // the staged twins: the query's stage-one words, one 16-byte unit per query behind the launch's digit masks {K', k2m', K - K', 0}
+  float k2m_staged = 0.0f;
+  uint32_t digit_k_rest = 0;
+  if constexpr (STG > 0) {
+    const uint32_t *__restrict__ sw = reinterpret_cast<const uint32_t *>(reinterpret_cast<const u32x4 *>(a.qplanes) + (size_t)a.qdigits_at + (size_t)a.n_queries * W * QU + q);
+    digit_k = sw[0];
+    k2m_staged = __builtin_bit_cast(float, sw[1]);
+    digit_k_rest = sw[2];
+  }
   const Threshold th = a.theta[q];
   // a query without f32 images defers every valid row - its f64 bound stands in front of the exact path, behind the loop: no row fails a NaN
   const float thz = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fast_bound ? threshold_z(th) : __builtin_nanf(""))));
@@ -389,6 +422,7 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
   }
   // the folded bound's per-row constants (b = 4 ly + ay: uniform, kept in a scalar register)
   const FoldedBoundParams pf = {p.lyf, __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fmaf(4.0f, p.lyf, p.ayf)))), p.c1f, p.k2mf};
+  const FoldedBoundParams pf_staged = {pf.lyf, pf.bf, pf.c1f, k2m_staged};
   n_def = 0;
   const int64_t chunk = a.chunk_begin + wg.chunk_local;
   const int64_t n_tiles = (a.idx.n_rows + kTileRows - 1) / kTileRows;
@@ -448,18 +482,21 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
   const uint32_t row_in_chunk0 = (uint32_t)(wave_first_tile(TPW, wave) * kTileRows);  // (scalar: the lane is added where a row is deferred)
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
-    uint32_t qc = tile_digit_sums<W>(c, s_planes, digit_k);
+    uint32_t qc = tile_digit_sums<W, STG>(c, s_planes, digit_k);
     __builtin_amdgcn_sched_barrier(0);  // (the bound and the loads below stay behind the popcounts, as the pick of the sum does in the TPW = 1 kernel)
     // The bound's verdicts as a mask in a scalar pair, straight from its compare; the rows beyond the index - in the index's last tile alone -
     // are taken out of it there.  (1 <= rows_here: the tile exists.)
-    auto verdicts = [&]() {
+    auto verdicts = [&](const FoldedBoundParams &pfx, const bool stage_two) {
       const uint32_t sum = __builtin_amdgcn_ubfe(ones, pick_at, 16u);  // the lane's half of the pair
       bool pass;
       if constexpr (kFoldedBound) {
         // (the wave's thresholds once, behind the first tile's popcounts: lane t has tile t's; aadd becomes the thresholds' register)
-        if (t == 0) aadd = tile_threshold(aadd, p, thz);
+        if (t == 0 && !stage_two) {
+          aadd = tile_threshold(aadd, p, thz);
+          if constexpr (STG > 0) aadd = aadd == __builtin_inff() ? __builtin_nanf("") : aadd;
+        }
         const float tile_th = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, aadd), t));
-        pass = folded_bound_passes(qc, cw, sum, pf, tile_th);
+        pass = folded_bound_passes(qc, cw, sum, pfx, tile_th);
       }
       if constexpr (!kFoldedBound) {
         qc += sum << 2;  // digit_dot's 4 * ones: u32 arithmetic, the same integer in either order
@@ -481,7 +518,25 @@ __device__ __forceinline__ bool sweep_wave_tiles(const ScanArgs &a, const SweepC
         n_def += (uint32_t)__popcll(passing);
       }
     };
-    const unsigned long long passing = verdicts();
+    unsigned long long passing = verdicts(STG > 0 ? pf_staged : pf, false);
+#ifdef BBQ_COUNT_STAGES
+    const bool stage_one_passed = passing != 0;
+#endif
+    if constexpr (STG > 0) {
+      static_assert(kFoldedBound && STG < W, "the stages are the folded bound's, and stage one resolves at least a chunk");
+      if (passing) {  // wave-uniform: some row passes the widened bound
+        qc = tile_digit_tail<W, STG>(c, s_planes, qc - digit_k_rest);
+        passing = verdicts(pf, true);
+      }
+    }
+#ifdef BBQ_COUNT_STAGES  // the counting build (scripts/staged_bound_counts.sh): tiles, tiles whose first ballot is non-zero, tiles that defer, rows deferred
+    if (lane == 0) {
+      atomicAdd(&stage_counts[0], 1ull);
+      if (stage_one_passed) atomicAdd(&stage_counts[1], 1ull);
+      if (passing) atomicAdd(&stage_counts[2], 1ull);
+      atomicAdd(&stage_counts[3], (unsigned long long)__popcll(passing));
+    }
+#endif
     if constexpr (kFoldedBound) defer(passing);  // in front of the next tile's loads: it reads this tile's row sums once more
     // The next tile's loads BEHIND the bound, which was this tile's last use of the registers the three small words land in - issued in front
     // of it, with the codes behind the popcounts, they came back in registers of their own, and the copies stood behind a wait for the whole
@@ -565,6 +620,31 @@ __device__ __forceinline__ void sweep_deferred_exact(const ScanArgs &a, const Sw
       }
     }
   }
+}
+
+// The staged twin of bbq_scan_kernel<4, W, 2, 1, true, true, TPW> (sweep_wave_tiles, STG): the same arguments, grid, block and LDS, the same
+// candidates.  A kernel of its own name, so that no existing instantiation's changes.  The launch takes it only where the host staged the
+// queries' stage-one words for this STG (launch_scan_t).
+template <int W, int TPW, int STG>
+__global__ __launch_bounds__(kChunkRows / TPW) void bbq_scan_staged_kernel(const ScanArgs a) {
+  static_assert(wave_tiles_are_exact(TPW) && TPW > 1 && STG > 0 && STG < W, "several tiles per wave, and a stage one that resolves something");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int NT = kChunkRows / TPW;
+  u32x4 *s_planes = reinterpret_cast<u32x4 *>(smem);
+  uint64_t *s_ent = reinterpret_cast<uint64_t *>(smem + (size_t)W * kDigitMasks * 16);
+  const uint32_t stage_cap = (a.ovf || a.append_lists) ? (uint32_t)kChunkRows : (uint32_t)a.cap;
+  uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_ent + stage_cap);
+  const SweepCoord wg = sweep_coord(blockIdx.x, blockIdx.y, a.l2_shift);
+  const bool idle = wg.chunk_local >= a.n_chunks || wg.query >= a.n_queries;  // workgroup-uniform
+  const int q = idle ? 0 : wg.query;
+  const int lane = threadIdx.x & 63;
+  bool nan_seen = false;
+  uint32_t n_def;
+  uint32_t *s_def = deferred_list(s_ent, s_cnt, stage_cap);
+  if (!sweep_wave_tiles<W, TPW, NT, STG>(a, wg, idle, q, s_planes, s_def, s_cnt, n_def)) return;
+  sweep_deferred_exact<W, TPW, NT>(a, wg, q, s_def, s_ent, s_cnt, stage_cap, n_def, nan_seen);
+  if (__any(nan_seen) && lane == 0) atomicOr(a.flags + q, kFlagNaN);
+  sweep_chunk_end<NT>(a, wg, q, s_ent, s_cnt);
 }
 
 // MODE: 0 sparse / inline corrections, 1 dense / inline, 2 sparse / compact corrections + exact gather, 3 dense / compact
@@ -870,9 +950,37 @@ template <bool FILT, int QB, int W, int SB>
 constexpr bool tiles_twin() {
   return !FILT && digit_twin<FILT, QB, W, SB>() && (W == 6 || W == 8 || W == 12);
 }
+// The staged twin (bbq_scan_staged_kernel<6, 8, 1>): one chunk of the unit digit plane behind the bound, at 6 chunks and 8 tiles per wave - the
+// one that was measured faster (staged_bound_for, bbq_core.cpp).  staged: the host staged the queries' stage-one words for it.
+// staged_launches: the twin's launches of this process (bbq_staged_launches, for the tests: nothing else shows which kernel a launch took).
+inline std::atomic<int64_t> staged_launches{0};
+#ifdef BBQ_COUNT_STAGES
+// the counting build: every launch of a kernel with several tiles per wave waits for its end and prints its counts (never the product's build)
+static void print_stage_counts(const ScanArgs &a, hipStream_t s, int tpw, bool staged) {
+  unsigned long long c[4] = {0, 0, 0, 0};
+  hipStreamSynchronize(s);
+  hipMemcpyFromSymbol(c, HIP_SYMBOL(stage_counts), sizeof c);
+  fprintf(stderr, "stage_counts chunks %d queries %d tiles_per_wave %d staged %d: tiles %llu first_ballot_nonzero %llu deferring %llu rows_deferred %llu\n",
+          a.n_chunks, a.n_queries, tpw, staged ? 1 : 0, c[0], c[1], c[2], c[3]);
+  const unsigned long long zero[4] = {0, 0, 0, 0};
+  hipMemcpyToSymbol(HIP_SYMBOL(stage_counts), zero, sizeof zero);
+}
+#define BBQ_PRINT_STAGE_COUNTS(staged) print_stage_counts(a, s, TPW, staged)
+#else
+#define BBQ_PRINT_STAGE_COUNTS(staged) ((void)0)
+#endif
 template <int QB, int W, int MODE, int SB, int TPW>
-static void launch_tiles_twin(const ScanArgs &a, dim3 grid, size_t smem, hipStream_t s) {
+static void launch_tiles_twin(const ScanArgs &a, dim3 grid, size_t smem, hipStream_t s, bool staged = false) {
+  if constexpr (QB == 4 && W == 6 && MODE == 2 && SB == 1 && TPW == 8) {
+    if (staged) {
+      hipLaunchKernelGGL((bbq_scan_staged_kernel<W, TPW, 1>), grid, dim3(kChunkRows / TPW, 1, 1), smem, s, a);
+      staged_launches.fetch_add(1, std::memory_order_relaxed);
+      BBQ_PRINT_STAGE_COUNTS(true);
+      return;
+    }
+  }
   hipLaunchKernelGGL((bbq_scan_kernel<QB, W, MODE, SB, true, true, TPW>), grid, dim3(kChunkRows / TPW, 1, 1), smem, s, a);
+  BBQ_PRINT_STAGE_COUNTS(false);
 }
 
 // tiles_per_wave: 1, 2, 4 or 8 - a host-side parameter of the launch, not a kernel argument (ScanArgs keeps its size): it selects the TPW twin
@@ -880,7 +988,8 @@ static void launch_tiles_twin(const ScanArgs &a, dim3 grid, size_t smem, hipStre
 // kChunkRows / TPW threads; the same dynamic LDS with the flood tier or in the append mode, and 2 KB more - the twins' deferred list
 // (deferred_list_bytes) - without either.
 template <bool FILT, int QB, int W, int MODE, int SB = 1>
-static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s, int tiles_per_wave = 1) {
+static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, int n_queries, int n_chunks, hipStream_t s, int tiles_per_wave = 1,
+                                bool staged = false) {
   ScanArgs a = args;  // the map's parameters: what the kernel decodes its block index with is what the grid below is built from
   a.n_chunks = n_chunks;
   a.n_queries = n_queries;
@@ -898,7 +1007,7 @@ static hipError_t launch_scan_t(const ScanArgs &args, const uint64_t *accept, in
         switch (tiles_per_wave) {
           case 2: launch_tiles_twin<QB, W, MODE, SB, 2>(a, grid, smem_tw, s); return hipGetLastError();
           case 4: launch_tiles_twin<QB, W, MODE, SB, 4>(a, grid, smem_tw, s); return hipGetLastError();
-          case 8: launch_tiles_twin<QB, W, MODE, SB, 8>(a, grid, smem_tw, s); return hipGetLastError();
+          case 8: launch_tiles_twin<QB, W, MODE, SB, 8>(a, grid, smem_tw, s, staged); return hipGetLastError();
           default: break;
         }
       }
@@ -939,10 +1048,10 @@ static hipError_t launch_scan_mb(const ScanArgs &a, const uint64_t *accept, int 
 }
 
 template <bool FILT, int QB, int MODE>
-static hipError_t launch_scan_w(const ScanArgs &a, const uint64_t *accept, int nq, int nc, hipStream_t s, int tpw = 1) {
+static hipError_t launch_scan_w(const ScanArgs &a, const uint64_t *accept, int nq, int nc, hipStream_t s, int tpw = 1, bool staged = false) {
   switch (a.idx.geom.w16) {
     case 1: return launch_scan_t<FILT, QB, 1, MODE>(a, accept, nq, nc, s, tpw);    // dim <= 128
-    case 6: return launch_scan_t<FILT, QB, 6, MODE>(a, accept, nq, nc, s, tpw);    // dim 768
+    case 6: return launch_scan_t<FILT, QB, 6, MODE>(a, accept, nq, nc, s, tpw, staged);  // dim 768
     case 8: return launch_scan_t<FILT, QB, 8, MODE>(a, accept, nq, nc, s, tpw);    // dim 1024
     case 12: return launch_scan_t<FILT, QB, 12, MODE>(a, accept, nq, nc, s, tpw);  // dim 1536
     default: return launch_scan_t<FILT, QB, 0, MODE>(a, accept, nq, nc, s, tpw);
@@ -950,11 +1059,11 @@ static hipError_t launch_scan_w(const ScanArgs &a, const uint64_t *accept, int n
 }
 
 template <bool FILT, int MODE>
-static hipError_t launch_scan_q(const ScanArgs &a, const uint64_t *accept, int planes, int nq, int nc, hipStream_t s, int tpw = 1) {
+static hipError_t launch_scan_q(const ScanArgs &a, const uint64_t *accept, int planes, int nq, int nc, hipStream_t s, int tpw = 1, bool staged = false) {
   switch (planes) {
     case 1: return launch_scan_w<FILT, 1, MODE>(a, accept, nq, nc, s, tpw);
     case 2: return launch_scan_w<FILT, 2, MODE>(a, accept, nq, nc, s, tpw);
-    case 4: return launch_scan_w<FILT, 4, MODE>(a, accept, nq, nc, s, tpw);
+    case 4: return launch_scan_w<FILT, 4, MODE>(a, accept, nq, nc, s, tpw, staged);
     default: return launch_scan_w<FILT, 8, MODE>(a, accept, nq, nc, s, tpw);
   }
 }

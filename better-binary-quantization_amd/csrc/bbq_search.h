@@ -94,6 +94,11 @@ void fill_query(const bbq_index *ix, uint8_t *planes_dst, QueryParams *pp, const
 // the digit masks of a 4-plane query against a 1-bit index ([w16][kDigitMasks] 16-byte masks -> digits_dst) and their K -> pp->digit_k
 int64_t digit_bytes_per_query_w(int w16);
 void fill_query_digits(const bbq_index *ix, uint8_t *digits_dst, QueryParams *pp, const uint8_t *q);
+void fill_query_digits_w(int dim, int w16, uint8_t *digits_dst, QueryParams *pp, const uint8_t *q);
+// a query's stage-one words for the staged twins of the many-tile digit sweep, from its digit masks: {K', k2m', K - K', 0} (bbq_query.cpp)
+constexpr int kStagedWordsBytes = 16;
+void staged_bound_words(int w16, int staged_chunks, const uint8_t *digits, const QueryParams *pp, uint32_t *words);
+int staged_bound_for(const bbq_index *ix);
 // the sub-batch's queries once more as matrix-core operands + group maxima behind the `bytes` already staged in h_qbuf
 struct MfmaStage { bool fp; int scale8; size_t off_qbytes, off_qmax, bytes; };
 MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryParams *hq, int64_t q_first, int nq, size_t bytes);

@@ -38,6 +38,7 @@ SYMBOLS = [
     "bbq_score_maxsim_groups_batch", "bbq_search_maxsim_groups_batch",
     "bbq_maxsim_reduce_true", "bbq_rerank_maxsim_groups_batch", "bbq_search_maxsim_rerank_batch",
     "bbq_true_topk", "bbq_vectors_search_batch", "bbq_vectors_set_option",
+    "bbq_staged_bound_words", "bbq_staged_launches",
 ]
 
 
@@ -114,6 +115,10 @@ def lib():
     L.bbq_score_ords_batch.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.bbq_search_ords_batch.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
     L.bbq_range_key.argtypes = [C.c_float, C.POINTER(C.c_uint32)]
+    if hasattr(L, "bbq_staged_launches"):  # (BBQ_LIB may name an older build, for comparisons: it has neither)
+        L.bbq_staged_bound_words.argtypes = [vp, i32, C.c_float, C.c_float, i32, i32, vp, vp, vp]
+        L.bbq_staged_launches.argtypes = []
+        L.bbq_staged_launches.restype = i64
     L.bbq_count_range_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp]
     L.bbq_search_range_batch.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, i64, vp, vp, vp]
     L.bbq_search_spans_batch.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp]
@@ -766,6 +771,21 @@ def merge_answers(blocks, n_queries, n_total, k, n_threads=1):
 
 def key_of_score(score):
     return int(lib().bbq_key_of_score(float(score)))
+
+
+def staged_bound_words(qquant, lyf, k2mf, fast_bound, staged_chunks):
+    """bbq_staged_bound_words (host only): (masks uint8 [w16, 5, 16], K, words uint32 [4]) of one queryBits-4 query"""
+    q = np.ascontiguousarray(qquant, np.uint8)
+    w16 = (len(q) + 127) // 128
+    masks = np.zeros((w16, 5, 16), np.uint8)
+    k, words = C.c_uint32(0), np.zeros(4, np.uint32)
+    _chk(lib().bbq_staged_bound_words(q.ctypes.data, len(q), float(lyf), float(k2mf), int(fast_bound), int(staged_chunks), masks.ctypes.data, C.addressof(k), words.ctypes.data))
+    return masks, int(k.value), words
+
+
+def staged_launches():
+    """launches of this process that took the sweep's staged twin so far (bbq_staged_launches)"""
+    return int(lib().bbq_staged_launches())
 
 
 def range_key(threshold):

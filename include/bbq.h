@@ -409,6 +409,14 @@ int bbq_search_ords_batch(bbq_index *idx, int32_t n_queries, const uint8_t *qqua
 /* host only: *out_key = K with  bbq_key_of_score(s) > K  <=>  s >= threshold  for every non-NaN s
  * (bbq_key_of_score(t) - 1 with t = +-0 taken as -0.0f).  NaN: BBQ_ERR_INVALID_ARG. */
 int bbq_range_key(float threshold, uint32_t *out_key);
+/* host only, for tests of the staged sweep: the digit masks staged for one queryBits-4 query of `dim` dimensions (out_masks:
+ * ceil(dim / 128) x 5 masks of 16 bytes, {P0, N0, P1, N1, P2} per 128 dimensions, packed like the rows), their K (out_digit_k) and the
+ * stage-one words the sweep's staged twin reads when the unit digit plane of the last staged_chunks x 4 dwords stays behind the bound:
+ * out_words[4] = {K', bits of k2m', K - K', the interval's half-width h}.  lyf, k2mf, fast_bound: the query's f32 images. */
+int bbq_staged_bound_words(const uint8_t *qquant, int32_t dim, float lyf, float k2mf, int32_t fast_bound, int32_t staged_chunks,
+                           uint8_t *out_masks, uint32_t *out_digit_k, uint32_t *out_words);
+/* launches of this process that took the sweep's staged twin so far (for tests: no answer shows which kernel a launch took) */
+int64_t bbq_staged_launches(void);
 /* f: NULL = all rows; otherwise a filter of this index (size / device as bbq_search_filtered_batch checks them).
  * thresholds [n_queries].  out_counts [n_queries] = number of rows in each answer. */
 int bbq_count_range_batch(bbq_index *idx, const bbq_filter *f, int32_t n_queries, const uint8_t *qquant, const double *qcorr,

@@ -32,7 +32,7 @@ pass 4 TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum TA_TA_BUSY_sum || exit 
 python3 - $OUT <<'PY'
 import csv, sys, os, collections
 out = sys.argv[1]
-tr = [r for r in csv.DictReader(open(os.path.join(out, "kernel_trace.csv"))) if "bbq_scan_kernel" in r["Kernel_Name"]]
+tr = [r for r in csv.DictReader(open(os.path.join(out, "kernel_trace.csv"))) if "bbq_scan_kernel" in r["Kernel_Name"] or "bbq_scan_staged_kernel" in r["Kernel_Name"]]
 def gsz(r): return int(r["Grid_Size_X"]) * int(r["Grid_Size_Y"]) if "Grid_Size_X" in r else int(r["Grid_Size"])
 big = max(gsz(r) for r in tr)
 d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) for r in tr if gsz(r) == big]
@@ -40,7 +40,7 @@ name = [r["Kernel_Name"] for r in tr if gsz(r) == big][0]
 dur = sum(d) / len(d) * 1e-9
 pl = collections.defaultdict(list)
 for i in range(1, 5):
-    rows = [r for r in csv.DictReader(open(os.path.join(out, "pmc%d.csv" % i))) if "bbq_scan_kernel" in r["Kernel_Name"]]
+    rows = [r for r in csv.DictReader(open(os.path.join(out, "pmc%d.csv" % i))) if "bbq_scan_kernel" in r["Kernel_Name"] or "bbq_scan_staged_kernel" in r["Kernel_Name"]]
     b = max(int(r["Grid_Size"]) for r in rows)
     for r in rows:
         if int(r["Grid_Size"]) == b: pl[r["Counter_Name"]].append(float(r["Counter_Value"]))

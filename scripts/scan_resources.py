@@ -89,6 +89,26 @@ def packed_f32_in_twins(csrc):
 TWIN_BUDGET = {6: {2: (51, 8), 4: (51, 8), 8: (50, 8)}, 8: {2: (59, 8), 4: (59, 8), 8: (58, 8)}, 12: {2: (75, 6), 4: (75, 6), 8: (74, 6)}}
 
 
+# ... and the staged twin (bbq_scan_staged_kernel<W, TPW, STG>): a twin ships only with its parent's registers and waves
+STAGED_BUDGET = {(6, 8, 1): (50, 8)}
+
+
+def staged_twins(csrc):
+    """bbq_scan_staged_kernel<W, TPW, STG> -> (VGPRs, waves, scratch), from the same remarks"""
+    text = remarks(csrc, FILES[0])
+    out, name = {}, None
+    for line in text.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            continue
+        m = re.search(r"remark:\s+(VGPRs|Occupancy \[waves/SIMD\]|ScratchSize \[bytes/lane\]): (\d+)", line)
+        k = re.match(r"_ZN3bbq22bbq_scan_staged_kernelILi(\d+)ELi(\d+)ELi(\d+)E", name or "")
+        if m and k:
+            out.setdefault(tuple(int(x) for x in k.groups()), {})[m.group(1).split()[0]] = int(m.group(2))
+    return {k: (v["VGPRs"], v["Occupancy"], v["ScratchSize"]) for k, v in out.items()}
+
+
 def twins_over_budget(res):
     over = []
     for key, (vgprs, waves, scratch) in res.items():
@@ -175,6 +195,14 @@ def main():
         for k, v in sorted(res.items()):
             print("%-44s %s" % (k, fmt(v)))
         over = twins_over_budget(res)
+        staged = staged_twins(sys.argv[1])
+        for k, v in sorted(staged.items()):
+            print("%-44s %s" % ("bbq_scan_staged_kernel<%d, %d, %d>" % k, fmt(v)))
+            b = STAGED_BUDGET.get(k)
+            if b and (v[0] > b[0] or v[1] < b[1] or v[2] > 0):
+                over.append("staged twin %s: %d registers / %d waves / %d scratch, recorded %d / %d / 0" % (k, v[0], v[1], v[2], b[0], b[1]))
+        if set(staged) != set(STAGED_BUDGET):
+            over.append("staged twins built %s, recorded %s" % (sorted(staged), sorted(STAGED_BUDGET)))
         if over:
             sys.exit("kernels with several tiles per wave above their recorded resources:\n  " + "\n  ".join(over))
         pk = packed_f32_in_twins(sys.argv[1])
