@@ -439,6 +439,10 @@ struct RerankArgs {
   const int64_t *offsets;  // [Q+1]
   const int32_t *rows;     // [offsets[Q]] row numbers, all in [0, n)
   double *out;             // [offsets[Q]] computeSimilarity(query, row)
+  // lists of a fixed stride (the exact search's survivors): when counts is set, query q's candidates are rows[q * stride ..
+  // q * stride + min(counts[q], stride)), out indexed alike, and offsets is not read
+  const int32_t *counts;   // [Q] or null
+  int64_t stride;
 };
 
 // scoring chosen rows (bbq_gather_kernels.hip): query q is scored against the rows ords[offsets[q] .. offsets[q+1]), one lane per entry
@@ -703,6 +707,104 @@ __host__ __device__ inline unsigned long long exact_accept_word(const uint64_t *
   const int64_t left = n - w * 64;
   return left >= 64 ? ~0ull : left <= 0 ? 0ull : (1ull << left) - 1ull;
 }
+
+// Exact search, the prefilter (bbq_exact_prefilter_kernels.hip; DESIGN.md "Exact search", the bound).  An f32 dot product s of a query
+// and a row, summed in any order, products fused or rounded, denormal operands and results flushed or kept, and the f32 sums of squares
+// of both, computed under the same freedom, give an interval [lo, hi] of f64 that contains the c(q, r) bbq_rerank_scores returns.
+// exact_side is what one vector contributes - bounds of its norm and of the norm's inverse, outward - and exact_interval joins two
+// sides and the dot product in a few multiply-adds: the kernel evaluates a side once per row and the host once per query.  Every
+// step is rounded outward by kExactSlop, far above the handful of 2^-53 roundings it covers.
+constexpr double kExactUnit32 = 1.0 / 8388608.0;             // 2^-23: the f32 unit roundoff were the unit to truncate; round-to-nearest is half
+constexpr double kExactUnit64 = 1.0 / 9007199254740992.0;    // 2^-53
+constexpr double kExactSlop = 1.0 / 1099511627776.0;         // 2^-40
+constexpr double kExactTiny = 1.1754943508222875e-38;        // 2^-126: the most one flushed f32 operation loses
+constexpr int32_t kExactBoundMaxDim = 1 << 18;               // beyond it (dim + 2) 2^-23 is no small number: every interval is unknown
+struct ExactSide {
+  double up;      // >= ||x||; +Inf: nothing is known of this vector
+  double inv_lo;  // <= 1 / ||x||
+  double inv_up;  // >= 1 / ||x||; 0: the f32 sum of squares may have underflowed - ||x|| has no lower bound (COSINE: unknown)
+  double pad;
+};
+__host__ __device__ inline double exact_gamma32(int32_t dim) {
+  const double t = (double)(dim + 2) * kExactUnit32;
+  return t / (1.0 - t);
+}
+__host__ __device__ inline ExactSide exact_side(int32_t dim, float sumsq) {
+  ExactSide e{__builtin_inf(), 0.0, 0.0, 0.0};
+  const double n = (double)sumsq, g = exact_gamma32(dim);
+  if (!(n >= 0.0) || n > 3.0e38 || dim < 1 || dim > kExactBoundMaxDim) return e;  // NaN, Inf, nonsense
+  const double lost = (double)dim * 4.0 * kExactTiny;  // dim products and dim sums, each flushed at most once, grown by at most (1 + u)^dim <= 2
+  e.up = sqrt((n + lost) / (1.0 - g) * (1.0 + kExactSlop)) * (1.0 + kExactSlop);
+  e.inv_lo = 1.0 / e.up * (1.0 - kExactSlop);
+  if (n >= lost * 16777216.0) {  // the flushed part is below 2^-24 of the sum
+    const double dn = sqrt(n * (1.0 - 2.0 * kExactUnit32) / (1.0 + g) * (1.0 - kExactSlop)) * (1.0 - kExactSlop);
+    e.inv_up = 1.0 / dn * (1.0 + kExactSlop);
+  }
+  return e;
+}
+// sim: 1 COSINE, 2 MAXIMUM_INNER_PRODUCT.  Unknown: lo = NaN, which ranks below every number, hi = +Inf.  lo is never +0.0 and hi
+// never -0.0, so the keys of lo <= c <= hi are ordered as the numbers are.
+__host__ __device__ inline void exact_interval(int32_t dim, int32_t sim, double s, const ExactSide &q, const ExactSide &r, double *lo, double *hi) {
+  *lo = __builtin_nan("");
+  *hi = __builtin_inf();
+  const double p_up = q.up * r.up * (1.0 + kExactSlop);
+  if (!(s == s) || !(p_up < 8.5e37) || s > 3.0e38 || s < -3.0e38) return;  // a NaN, an infinity, or a dot product that may have overflowed
+  const double g = exact_gamma32(dim) * (1.0 + kExactSlop);
+  const double g64 = (double)(4 * (int64_t)dim + 64) * kExactUnit64;
+  // what flushing can cost s: per term one flushed operand (at most 2^-126 times the other), one flushed product and one flushed
+  // sum, grown by (1 + u)^dim <= 2
+  const double eta = (double)dim * 2.0 * kExactTiny * (2.0 + q.up + r.up) * (1.0 + kExactSlop);
+  double l, h;
+  if (sim == 2) {
+    const double e = ((g + g64) * p_up + eta + 8.0 * kExactUnit64 * (s < 0 ? -s : s)) * (1.0 + kExactSlop);
+    l = s - e;
+    h = s + e;
+  } else {
+    if (q.inv_up == 0.0 || r.inv_up == 0.0) return;
+    const double sp = s + eta, sm = s - eta;
+    const double w_up = q.inv_up * r.inv_up * (1.0 + kExactSlop), w_lo = q.inv_lo * r.inv_lo * (1.0 - kExactSlop);
+    h = (sp >= 0 ? sp * w_up : sp * w_lo) + g;
+    l = (sm >= 0 ? sm * w_lo : sm * w_up) - g;
+    h = (h < 1.0 ? h : 1.0) + (g64 + kExactSlop * g);  // the real cosine is in [-1, 1]; c is within g64 of it
+    l = (l > -1.0 ? l : -1.0) - (g64 + kExactSlop * g);
+  }
+  if (!(l == l) || !(h == h)) return;
+  *lo = l == 0.0 ? -0.0 : l;
+  *hi = h == 0.0 ? 0.0 : h;
+}
+constexpr bool exact_prefilter_serves(int32_t sim) { return sim == 1 || sim == 2; }  // EUCLIDEAN keeps the f64 sweep
+
+// The prefilter pass of one slab: the rows against blocks of kExactPreQueries queries on v_mfma_f32_32x32x2_f32, a workgroup
+// kExactPreRows rows (one wave: the 64 rows of an accept word).  lo_keys / hi_keys [sub-batch's queries][stride]: true_key of the
+// interval's ends, lo_keys 0 for a row the filter rejects (hi_keys then unwritten); a wave without an accepted row writes nothing.
+constexpr int kExactPreQueries = 64;
+constexpr int kExactPreWaves = 4;
+constexpr int kExactPreRows = 64 * kExactPreWaves;
+constexpr int kExactPreCols = 32;                   // columns per stage
+constexpr int kExactPreStride = kExactPreCols + 4;  // words a staged row or query takes: 16-byte aligned pieces, eight rows a bank group apart
+struct ExactPrefilterArgs {
+  const float *vecs;              // [n][dim] the fp32 rows, row-major
+  const float *queries;           // [sub-batch's queries][dim] raw fp32
+  const ExactSide *sides;         // [sub-batch's queries] exact_side of each query's f32 sum of squares
+  const uint64_t *accept;         // as ExactScoreArgs::accept
+  unsigned long long *lo_keys, *hi_keys;
+  int64_t n, row0, stride;        // as ExactScoreArgs'
+  int32_t n_queries, dim, sim, pad;
+};
+// The compaction behind the select pass over lo_keys: one workgroup per query appends, in row order and by a prefix sum, every
+// accepted row of the slab whose hi key is at or above the list's last key - every accepted row while the list is short of kk - to
+// surv_rows[query][cap].  surv_count counts what passed, beyond cap too: a query that overflows is answered by the f64 sweep.
+struct ExactCompactArgs {
+  const unsigned long long *hi_keys;   // [grid.x][stride]
+  const uint64_t *accept;
+  const unsigned long long *list_keys; // [grid.x][kk]
+  const int32_t *list_count;           // [grid.x]
+  int32_t *surv_rows;                  // [grid.x][cap]
+  int32_t *surv_count;                 // [grid.x] cleared before the first slab
+  int64_t n, row0, stride;
+  int32_t rows, kk, cap, pad;
+};
+inline int64_t exact_survivor_cap(int64_t kk) { return 2 * kk + 1024; }
 
 constexpr int kFinalizeThreads = 1024;
 constexpr int kFinalizeJobs = 4096;     // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)

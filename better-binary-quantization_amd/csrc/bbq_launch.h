@@ -137,6 +137,11 @@ hipError_t launch_maxsim_true_accumulate(const MaxSimTrueAccArgs &a, int n_queri
 hipError_t launch_exact_score(const ExactScoreArgs &a, int64_t rows, hipStream_t s);
 // its select pass: the slab folded into the running list of each of the n_queries queries
 hipError_t launch_exact_select(const ExactSelectArgs &a, int n_queries, hipStream_t s);
+// its prefilter (bbq_exact_prefilter_kernels.hip).  The prefilter pass of one slab, a.row0 a multiple of kExactPreRows: the ends of
+// every pair's interval as keys; COSINE and MAXIMUM_INNER_PRODUCT
+hipError_t launch_exact_prefilter(const ExactPrefilterArgs &a, int64_t rows, hipStream_t s);
+// the compaction behind the select pass over the lower ends: the slab's rows that may still be in an answer, appended per query
+hipError_t launch_exact_compact(const ExactCompactArgs &a, int n_queries, hipStream_t s);
 // the fp32 rows [n][dim] of `src` that map.accept keeps (word t = rows 64 t .. 64 t + 63) -> the rows [0, map.kept) of `out`, out of place
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 // staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place

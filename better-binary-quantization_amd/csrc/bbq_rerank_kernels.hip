@@ -19,7 +19,8 @@ constexpr int kRrLoads = 64 * kRrCols / 64;   // loads per lane per stage (= 32)
 
 __global__ __launch_bounds__(64) void bbq_rerank_kernel(RerankArgs a) {
   const int q = blockIdx.y;
-  const int64_t beg = a.offsets[q], end = a.offsets[q + 1];
+  const int64_t beg = a.counts ? (int64_t)q * a.stride : a.offsets[q];
+  const int64_t end = a.counts ? beg + min((int64_t)max(a.counts[q], 0), a.stride) : a.offsets[q + 1];
   const int64_t c0 = beg + (int64_t)blockIdx.x * 64;
   if (c0 >= end) return;  // uniform per workgroup
   const int lane = threadIdx.x;

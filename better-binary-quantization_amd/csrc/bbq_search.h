@@ -50,6 +50,8 @@ struct bbq_vectors {
   bbq::DevBuf<uint8_t> d_exact;
   bbq::PinnedBuf<uint8_t> h_exact_in, h_exact_out;
   int64_t opt_exact_slab_rows = 0;  // rows scored between two select passes; 0: what the scratch budget gives (bbq_exact.cpp)
+  int64_t opt_exact_prefilter = -1; // -1 the library's choice, 0 the f64 sweep alone, 1 the prefilter wherever it exists
+  int64_t exact_stats[4] = {0, 0, 0, 0};  // of the last bbq_vectors_search_batch: bbq_vectors_exact_stats
 };
 
 #pragma GCC visibility push(hidden)  // internal: none of this joins the library's dynamic symbols

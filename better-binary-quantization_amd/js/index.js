@@ -1157,7 +1157,8 @@ class DeviceVectors {
     }
     return out;
   }
-  /** extension: 'exact_slab_rows', the rows trueTopK scores between two select passes; 0: automatic (libbbq bbq_vectors_set_option) */
+  /** extension: 'exact_slab_rows', the rows trueTopK scores between two select passes; 0: automatic - and 'exact_prefilter', -1 the
+   * library's choice, 0 the f64 sweep alone, 1 the f32 prefilter on the matrix cores (libbbq bbq_vectors_set_option) */
   setOption(name, value) { native.vectorsSetOption(this._handle(), String(name), value); return this; }
   _handle() { if (!this._h) throw new Error('向量不能为空'); return this._h; }
   dispose() { if (this._h) { native.vectorsDestroy(this._h); this._h = null; } }

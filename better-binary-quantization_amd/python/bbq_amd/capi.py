@@ -37,7 +37,7 @@ SYMBOLS = [
     "bbq_search_maxsim_batch", "bbq_maxsim_reduce", "bbq_maxsim_token_block",
     "bbq_score_maxsim_groups_batch", "bbq_search_maxsim_groups_batch",
     "bbq_maxsim_reduce_true", "bbq_rerank_maxsim_groups_batch", "bbq_search_maxsim_rerank_batch",
-    "bbq_true_topk", "bbq_vectors_search_batch", "bbq_vectors_set_option",
+    "bbq_true_topk", "bbq_vectors_search_batch", "bbq_vectors_set_option", "bbq_exact_bound", "bbq_vectors_exact_stats",
     "bbq_staged_bound_words", "bbq_staged_launches",
 ]
 
@@ -142,6 +142,8 @@ def lib():
     L.bbq_true_topk.argtypes = [vp, i64, vp, i64, vp, vp, C.POINTER(i64)]
     L.bbq_vectors_search_batch.argtypes = [vp, vp, i32, vp, i32, i64, vp, vp, vp]
     L.bbq_vectors_set_option.argtypes = [vp, C.c_char_p, i64]
+    L.bbq_exact_bound.argtypes = [i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.bbq_vectors_exact_stats.argtypes = [vp, vp]
     L.bbq_maxsim_token_block.argtypes = []
     L.bbq_maxsim_token_block.restype = i32
     L.bbq_filter_create.argtypes = [vp, vp, i64, C.POINTER(vp)]
@@ -977,6 +979,15 @@ def true_topk(scores, k, accept=None):
     return idx[:n.value], out[:n.value]
 
 
+def exact_bound(dim, true_sim, dot, query_sumsq, row_sumsq):
+    """bbq_exact_bound (host only): the interval (lo, hi) of f64 that holds c(q, r) for an f32 dot product and f32 sums of squares
+    computed in any order; unknown: (NaN, +Inf)"""
+    lo, hi = C.c_double(0), C.c_double(0)
+    _chk(lib().bbq_exact_bound(int(dim), int(true_sim), float(np.float32(dot)), float(np.float32(query_sumsq)), float(np.float32(row_sumsq)),
+                               C.byref(lo), C.byref(hi)))
+    return lo.value, hi.value
+
+
 def _raw_tokens(token_lists, dim):
     """(vec_offsets int64 [nq + 1], queries float32 [vectors, dim]) of per-query raw fp32 token arrays [T, dim]"""
     arrs = [np.asarray(t, np.float32).reshape(-1, dim) for t in token_lists]
@@ -1092,8 +1103,15 @@ class Vectors:
         return [out[off[i]:off[i + 1]] for i in range(len(lists))]
 
     def set_option(self, name, value):
-        """bbq_vectors_set_option: "exact_slab_rows", the rows search_batch scores between two select passes (0: automatic)"""
+        """bbq_vectors_set_option: "exact_slab_rows", the rows search_batch scores between two select passes (0: automatic);
+        "exact_prefilter", -1 the library's choice, 0 the f64 sweep alone, 1 the f32 prefilter on the matrix cores wherever it exists"""
         _chk(lib().bbq_vectors_set_option(self._h, name.encode(), int(value)))
+
+    def exact_stats(self):
+        """bbq_vectors_exact_stats of the last search_batch: {prefilter_pairs, f64_pairs, fallbacks, f64_pairs_max_query}"""
+        out = np.zeros(4, np.int64)
+        _chk(lib().bbq_vectors_exact_stats(self._h, _ptr(out)))
+        return dict(zip(("prefilter_pairs", "f64_pairs", "fallbacks", "f64_pairs_max_query"), (int(x) for x in out)))
 
     def search_batch(self, queries, k, true_sim=1, row_filter=None):
         """bbq_vectors_search_batch: the exact top-k of every raw fp32 query over the rows (those `row_filter` accepts), the

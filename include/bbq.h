@@ -802,9 +802,29 @@ int bbq_search_maxsim_rerank_batch(bbq_index *idx, bbq_vectors *v, const bbq_gro
  * of rows whose keys, 8 bytes per (query, row), stay under 256 MiB of scratch inside the handle; k x (row, score) per query is the only
  * copy back.  A failed allocation: BBQ_ERR_OOM, no answer written.  Results are byte-identical from run to run.
  * bbq_vectors_set_option: "exact_slab_rows", the rows scored between two select passes - 0 (automatic: what the scratch allows) or a
- * multiple of 256 in 256 .. 2^24.  A speed and scratch choice: it never changes an answer.  An unknown name or a value out of range:
- * BBQ_ERR_INVALID_ARG.
+ * multiple of 256 in 256 .. 2^24 - and "exact_prefilter", -1, 0 or 1 (below).  Speed and scratch choices: they never change an answer.
+ * An unknown name or a value out of range: BBQ_ERR_INVALID_ARG.
+ * The prefilter (DESIGN.md "Exact search", the bound).  Under COSINE and MAXIMUM_INNER_PRODUCT the rows can be pruned before the f64
+ * chains: an f32 dot product on the matrix cores gives every pair an interval that holds c(q, r), the rows whose upper end cannot reach
+ * the k-th largest lower end are dropped, the others - every row of the answer and every row that ties or overlaps the cut - run the
+ * chain.  The answer is the same bytes.  bbq_exact_bound (host only, no device) is the normative statement of the interval, as
+ * bbq_true_topk is of the ranking: for an f32 dot product `dot` of a query and a row of `dim` components - summed in any order, the
+ * products fused or rounded, denormal operands and results flushed or kept - and f32 sums of squares of both under the same freedom,
+ * *out_lo <= c(q, r) <= *out_hi.  Where nothing can be said - dot or a sum of squares not finite, a product of norms near the f32
+ * range, under COSINE a sum of squares below dim * 2^-100, which may have underflowed - the interval is unknown: *out_lo = NaN, which
+ * ranks below every number, *out_hi = +Inf.  lo is never +0.0 and hi never -0.0.  EUCLIDEAN has no interval: BBQ_ERR_UNSUPPORTED, and
+ * its searches keep the f64 sweep whatever the option says.
+ * "exact_prefilter": 0 - the f64 sweep alone, what the call launched before the prefilter existed; 1 - the prefilter wherever it
+ * exists; -1 (the default) - the library's choice per similarity, today the f64 sweep for all three (README "Exact search": the
+ * measurement that would turn it on).  A query keeps at most 2 * min(k, |A|) + 1024 survivors; when one overflows - every row ties,
+ * every interval is unknown - its sub-batch is answered by the f64 sweep.  With the prefilter a slab's keys take 16 bytes per pair.
+ * bbq_vectors_exact_stats: the last bbq_vectors_search_batch of the handle - out[0] the pairs the prefilter swept, out[1] the pairs
+ * scored in f64 (the survivors; a sub-batch that fell back adds its every pair), out[2] the sub-batches that fell back, out[3] the
+ * most pairs any one query scored in f64.
  * Out of scope: multi-device handles and shards, spans or row lists (bbq_rerank_scores takes lists), k beyond 4096. */
+int bbq_exact_bound(int32_t dim, int32_t true_sim, float dot, float query_sumsq, float row_sumsq, double *out_lo,
+                    double *out_hi);                                                                    /* host only */
+int bbq_vectors_exact_stats(bbq_vectors *v, int64_t out[4]);
 int bbq_true_topk(const double *scores, int64_t n, const uint64_t *accept_bits, int64_t k, int32_t *out_idx, double *out_true,
                   int64_t *out_n);                                                                      /* host only */
 int bbq_vectors_search_batch(bbq_vectors *v, const bbq_filter *f, int32_t n_queries, const float *queries, int32_t true_sim,

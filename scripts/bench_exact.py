@@ -7,7 +7,9 @@ process, the ways interleaved call by call so that drift of the box hits both al
 Ways:
   (y)   the yardstick: bbq_rerank_scores over each query's accepted rows - the list 0 .. n-1, or the filter's rows - and a stable
         descending sort of each query's scores on the host, first k; the row lists, offsets and score buffers are made once and reused
-  (n)   bbq_vectors_search_batch
+  (n)   bbq_vectors_search_batch with exact_prefilter 0: the f64 sweep alone, launch for launch the call before the prefilter existed
+  (p)   bbq_vectors_search_batch with exact_prefilter 1: the f32 prefilter on the matrix cores, the f64 chain for the survivors
+--ways picks the ways that run (default yn; np compares the prefilter with the sweep alone - profiles/exact_search_prefilter.json).
 The bytes of (y) and (n) - rows and f64 scores - are compared on every leg before anything is timed.
 Legs: k = 10 and k = 100, each without a filter, under a random filter that accepts 10 % of the rows, and under one that accepts 1 000
 rows.  Per leg the ways run three times in alternation, each run the median of the timed calls (host clock around calls that return
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--runs", type=int, default=3, help="alternating runs per leg")
     ap.add_argument("--only-new", type=int, default=0, help="1: time the new call alone, unfiltered (for a kernel trace, or a size the yardstick cannot take)")
     ap.add_argument("--slab-rows", type=int, default=0, help="exact_slab_rows")
+    ap.add_argument("--ways", default="yn", help="the ways to run, of y, n and p; the first is the one the others are held against")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
     if args.steps < 7:
@@ -51,6 +54,9 @@ def main():
     n, dim, nq, SIM = args.rows, args.dim, args.queries, args.true_sim
     rng = np.random.default_rng(73)
     ix = None
+    if args.only_new and args.ways == "yn":
+        args.ways = "n"
+    with_y = "y" in args.ways
     if not args.only_new:  # the filters hang on an index of n rows; the search reads the fp32 rows alone
         codes, corr = bench.synth_rows(1, 0, n, (dim + 7) // 8)
         ix = B.Index(codes, corr, dim, float(B.centroid_dp(bench.synth_centroid(dim))), device=args.device, corrections="compact")
@@ -77,22 +83,29 @@ def main():
         flt = capi.Filter(ix, accept) if accept is not None else None
         rows = np.arange(n, dtype=np.int32) if accept is None else np.flatnonzero(accept).astype(np.int32)
         a = len(rows)
-        if not args.only_new:  # the yardstick's lists and buffers, made once
+        if with_y:  # the yardstick's lists and buffers, made once
             ords = np.ascontiguousarray(np.tile(rows, nq))
             ooff = (np.arange(nq + 1, dtype=np.int64) * a)
             c64 = np.empty(nq * a, np.float64)
         for k in (10, 100):
             kk = min(k, a)
-            out = {w: (np.full((nq, k), -1, np.int32), np.zeros((nq, k), np.float64)) for w in "yn"}
+            out = {w: (np.full((nq, k), -1, np.int32), np.zeros((nq, k), np.float64)) for w in "ynp"}
             cnt = np.zeros(nq, np.int64)
 
-            def way_n():
+            def search(w, pre):
+                V.set_option("exact_prefilter", pre)
                 t0 = time.perf_counter()
-                rc = L.bbq_vectors_search_batch(V._h, flt._h if flt is not None else None, nq, queries.ctypes.data, SIM, k, out["n"][0].ctypes.data,
-                                                out["n"][1].ctypes.data, cnt.ctypes.data)
+                rc = L.bbq_vectors_search_batch(V._h, flt._h if flt is not None else None, nq, queries.ctypes.data, SIM, k, out[w][0].ctypes.data,
+                                                out[w][1].ctypes.data, cnt.ctypes.data)
                 dt = time.perf_counter() - t0
                 assert rc == 0, L.bbq_last_error().decode()
                 return dt
+
+            def way_n():
+                return search("n", 0)
+
+            def way_p():
+                return search("p", 1)
 
             def way_y():
                 t0 = time.perf_counter()
@@ -106,13 +119,15 @@ def main():
                 return time.perf_counter() - t0
 
             # the answers first: nothing is timed before the two ways agree
-            way_n()
-            assert (cnt == kk).all()
-            if not args.only_new:
-                way_y()
-                assert out["y"][0].tobytes() == out["n"][0].tobytes() and out["y"][1].tobytes() == out["n"][1].tobytes(), \
-                    "filter %s, k %d: the yardstick's bytes and the new call's differ" % (fname, k)
-            ways = {"n": way_n} if args.only_new else {"y": way_y, "n": way_n}
+            ways = {w: {"y": way_y, "n": way_n, "p": way_p}[w] for w in args.ways}
+            pre_stats = None
+            for w, f in ways.items():
+                f()
+                assert w == "y" or (cnt == kk).all()
+                if w == "p":
+                    pre_stats = V.exact_stats()
+                assert out[w][0].tobytes() == out[args.ways[0]][0].tobytes() and out[w][1].tobytes() == out[args.ways[0]][1].tobytes(), \
+                    "filter %s, k %d: the bytes of ways %s and %s differ" % (fname, k, args.ways[0], w)
             runs = {w: [] for w in ways}
             for r in range(args.runs):
                 t = {w: [] for w in ways}
@@ -123,10 +138,18 @@ def main():
                             t[w].append(dt)
                 for w in ways:
                     runs[w].append(med(t[w]))
-            rec = {"filter": fname, "accepted_rows": a, "k": k, "pairs_per_call": nq * a, "fma_per_call": nq * a * dim,
-                   "new_s_per_call_runs": [round(x, 6) for x in runs["n"]], "new_s_per_call": round(med(runs["n"]), 6),
-                   "new_pairs_per_s": round(nq * a / med(runs["n"]), 1)}
-            if not args.only_new:
+            rec = {"filter": fname, "accepted_rows": a, "k": k, "pairs_per_call": nq * a, "fma_per_call": nq * a * dim}
+            if "n" in runs:
+                rec.update({"new_s_per_call_runs": [round(x, 6) for x in runs["n"]], "new_s_per_call": round(med(runs["n"]), 6),
+                            "new_pairs_per_s": round(nq * a / med(runs["n"]), 1)})
+            if "p" in runs:
+                rec.update({"prefilter_s_per_call_runs": [round(x, 6) for x in runs["p"]], "prefilter_s_per_call": round(med(runs["p"]), 6),
+                            "prefilter_stats": pre_stats, "bytes_agree": True})
+            if "p" in runs and "n" in runs:  # the rule a default is held to: the prefilter's slowest run against the sweep's fastest and its spread
+                n_fast, n_slow, p_slow = min(runs["n"]), max(runs["n"]), max(runs["p"])
+                rec.update({"prefilter_speedup_over_sweep": round(med(runs["n"]) / med(runs["p"]), 2),
+                            "prefilter_slowest_beats_sweep_fastest_by_more_than_its_spread": bool(p_slow < n_fast - (n_slow - n_fast))})
+            if with_y and "n" in runs:
                 y_fast, y_slow, n_slow = min(runs["y"]), max(runs["y"]), max(runs["n"])
                 rec.update({"yardstick_s_per_call_runs": [round(x, 6) for x in runs["y"]], "yardstick_s_per_call": round(med(runs["y"]), 6),
                             "new_speedup_over_yardstick": round(med(runs["y"]) / med(runs["n"]), 2),
