@@ -27,30 +27,12 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include "bbq_device.h"
+#include "bbq_jsmath.h"  // Math.min / Math.max / Math.round as V8 evaluates them
 #include "bbq_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace bbq {
-
-// Math.min / Math.max / Math.round as V8 evaluates them
-__device__ __forceinline__ double jmin(double a, double b) {
-  if (a != a || b != b) return __longlong_as_double(0x7ff8000000000000ll);
-  if (a == 0.0 && b == 0.0) return (__double_as_longlong(a) < 0 || __double_as_longlong(b) < 0) ? -0.0 : 0.0;
-  return a < b ? a : b;
-}
-__device__ __forceinline__ double jmax(double a, double b) {
-  if (a != a || b != b) return __longlong_as_double(0x7ff8000000000000ll);
-  if (a == 0.0 && b == 0.0) return (__double_as_longlong(a) < 0 && __double_as_longlong(b) < 0) ? -0.0 : 0.0;
-  return a > b ? a : b;
-}
-__device__ __forceinline__ double jclamp(double x, double lo, double hi) { return jmin(jmax(x, lo), hi); }
-__device__ __forceinline__ double jround(double x) {
-  if (x != x || fabs(x) == __longlong_as_double(0x7ff0000000000000ll)) return x;
-  double r = floor(x);
-  if (x - r >= 0.5) r += 1.0;
-  return r;
-}
 
 // ------------------------------------------------------------------------------------------------ transpose_in
 // block 256 threads: tile of 64 vectors x 16 float4 (64 dims) through LDS, both sides coalesced

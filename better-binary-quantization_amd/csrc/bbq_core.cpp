@@ -921,6 +921,12 @@ int bbq_search_raw_batch(bbq_index *ix, int32_t n_queries, const float *queries,
   double *qc = qcorr_out;
   if (!qq) { own_q.resize((size_t)n_queries * dim); qq = own_q.data(); }
   if (!qc) { own_c.resize((size_t)n_queries * 4); qc = own_c.data(); }
+  // option device_queries: all queries through the device quantizer (bbq_query_device.cpp), then the search of prepared queries
+  if (device_queries_for_call(ix)) {
+    int rc = bbq_quantize_queries_device(ix, n_queries, queries, centroid, sim, query_bits, lambda, iters, qq, qc, bad_query);
+    if (rc != BBQ_OK) return rc;
+    return search_batch_impl(ix, n_queries, qq, qc, query_bits, sim, k, out_idx, out_score, out_n, nullptr, nullptr);
+  }
   const int T = n_threads > 0 ? n_threads : default_host_threads();
   // few queries, k == 0 (the quantizer's errors still surface, as in the reference's order of checks) or a multi-device handle
   // (its rounds take whole arrays): quantize first, then search

@@ -806,6 +806,26 @@ struct ExactCompactArgs {
 };
 inline int64_t exact_survivor_cap(int64_t kk) { return 2 * kk + 1024; }
 
+// ---- query quantization (bbq_query_kernels.hip): one wave - a workgroup of 64 threads - per query.  Its LDS: the chain rows, then the
+// query's working vector, a whole number of rounds of 64 f32
+constexpr int kQueryQuantChains = 5;      // most chains one phase advances: the five sums of an optimizeIntervals iteration
+constexpr int kQueryQuantRowStride = 65;  // f64 a chain row takes: 64 terms and one of padding - row c starts 2 c banks on, so the
+                                          // chain lanes' reads of one step fall on different banks
+constexpr int kQueryQuantLdsMax = 65536;  // what a workgroup gets without asking the runtime for more
+constexpr int64_t query_quant_lds_bytes(int64_t dim) { return kQueryQuantChains * kQueryQuantRowStride * 8 + (dim + 63) / 64 * 256; }
+constexpr int32_t kQueryQuantMaxDim = (kQueryQuantLdsMax - kQueryQuantChains * kQueryQuantRowStride * 8) / 256 * 64;  // 15680
+// status[q]: 0, or the first NaN / Infinity of the query as the quantizer reads it (behind the normalisations): kind << 30 | position
+constexpr uint32_t kQueryQuantNaN = 1u, kQueryQuantInf = 2u;
+struct QueryQuantArgs {
+  const float *queries;   // [n][dim] row-major, as uploaded
+  const float *centroid;  // [dim]
+  uint8_t *qquant;        // [n][dim] one byte per dimension
+  double *qcorr;          // [n][4] {lower, upper, additional correction, component sum}
+  uint32_t *status;       // [n]
+  double lambda;
+  int32_t dim, sim, bits, iters;
+};
+
 constexpr int kFinalizeThreads = 1024;
 constexpr int kFinalizeJobs = 4096;     // non-empty chunks one finalize launch copies entry-parallel (more: thread by thread)
 constexpr int kFinalizeKeyCap = 12288;   // LDS key buffer of the finalize kernel (new keys + running top-k)

@@ -19,6 +19,7 @@
 //   bbq_maxsim_groups.cpp, bbq_maxsim_rerank.cpp   MaxSim over chosen groups, quantized and exact (bbq_*_maxsim_groups_batch, bbq_search_maxsim_rerank_batch)
 //   bbq_rerank.cpp   oversample + exact rerank (bbq_vectors_*, bbq_rerank_scores, bbq_search_rerank_batch)
 //   bbq_exact.cpp    exact search over the fp32 rows (bbq_true_topk, bbq_vectors_search_batch, bbq_vectors_set_option)
+//   bbq_query_device.cpp  raw queries quantized on the device (bbq_quantize_queries_device, option device_queries)
 //   bbq_persist.cpp  on-disk format (bbq_index_save / load / file_info / export)
 // bbq_entry.h is the codec of the 64-bit entries, keys and answer headers; bbq_workqueue.h the host threads' job queue.
 // HIP memory and events are held in the owning types of bbq_mem.h: what a struct below owns goes with it.
@@ -146,6 +147,7 @@ struct DeviceCtx {
   DevBuf<uint8_t> d_span;            // grow-only scratch of a span search's sub-batch (bbq_span.cpp): queries, span tables, work items, answer blocks, scores;
                                      // of a grouped search's (bbq_group.cpp): queries, answer blocks, the representatives' keys, scores and ords; and of
                                      // the MaxSim calls' (bbq_maxsim*.cpp).  What bbq_select.cpp's finish_selected brings scores and ords back from
+  DevBuf<uint8_t> d_query_quant;     // grow-only scratch of a sub-batch of bbq_quantize_queries_device (bbq_query_device.cpp): raw queries, centroid, bytes, corrections, status words
   int last_big_slot = -1;             // slot whose ev_big marks the end of the most recently enqueued big sweep
   // latency path (bbq_latency_kernels.hip): the answer of a single-query call lands in mapped, coherent host memory and the host
   // polls a sequence word behind it: [0] sequence, [8 ..) header + entries
@@ -245,6 +247,8 @@ struct bbq_index {
                               // vector, -1 what was measured faster (bbq_maxsim.cpp).  The answers are the same either way
   int opt_fast_bound = 1;  // 1: the compact layout's score bound in f32 against the threshold's z image wherever the query's f32 images allow it
                            // (fast_bound_images, bbq_query.cpp); 0: always the f64 bound.  The answers are the same either way
+  int opt_device_queries = -1;  // bbq_search_raw_batch quantizes its queries on the device (bbq_query_device.cpp) instead of on host threads: 1 wherever
+                                // device_queries_for_call says it can, 0 never; -1: the library's choice, host threads.  The answers are the same either way
   int opt_latency_presample = 1;  // ... and on large indexes get their threshold from per-wave top keys of a prefix (two small launches) instead of two scan / finalize pairs
   int opt_latency_fused = 1;  // single-query calls take the three-launch latency path (bbq_latency_kernels.hip) when the index shape has one
   int opt_append_last = 1;  // append mode also for the last (largest) segment: its finalize launch gets cheaper, its sweep slower (one
@@ -384,6 +388,11 @@ int quantize_into(bbq_index *ix, DevBuf<float> &d_vT4, int64_t n, const float *d
 int settle_shard_slots(DeviceCtx *ctx, bbq_index *owner);
 // every f32 score of one query on this (single-device) index, to host memory [n_rows]
 int dense_scores_host(bbq_index *ix, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim, float *out);
+// bbq_query_device.cpp.  Does bbq_search_raw_batch quantize this handle's queries on the device?  Option device_queries 1 on a
+// single-device root index whose dimension the kernel takes; everything else keeps host threads
+bool device_queries_for_call(const bbq_index *ix);
+// bbq_set_option's part for the option of that file: false when `name` is not "device_queries"; otherwise *rc is the call's answer
+bool set_device_queries_option(bbq_index *ix, const char *name, int64_t v, int *rc);
 // multi-device index (bbq_multi.cpp): what the entry points of a handle with ix->multi != nullptr dispatch to
 void multi_destroy(bbq_index *ix);
 int multi_search_batch(bbq_index *ix, int32_t n_queries, const uint8_t *qquant, const double *qcorr, int32_t query_bits, int32_t sim,

@@ -260,6 +260,8 @@ int bbq_reset_stats(bbq_index *ix) {
 int bbq_set_option(bbq_index *ix, const char *name, int64_t v) {
   if (!ix || !name) return fail(BBQ_ERR_INVALID_ARG, "bbq_set_option: null");
   if (ix->multi) return multi_set_option(ix, name, v);
+  int rc;
+  if (set_device_queries_option(ix, name, v, &rc)) return rc;  // device_queries -1|0|1: parsed beside the call it steers (bbq_query_device.cpp)
   const std::string n(name);
   if (n == "batch_queries" && v >= 0 && v <= 1024) ix->opt_batch = (int)v;  // 0: by index size
   else if (n == "pipeline_slots" && v >= 1 && v <= kMaxSlots) ix->opt_slots = (int)v;

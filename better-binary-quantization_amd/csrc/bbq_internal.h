@@ -12,6 +12,8 @@ namespace bbq {
 
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void clear_error();
+// the argument checks every entry point of the quantizer starts with (bbq_quantizer.cpp), with their messages
+int check_quantizer_args(const void *a, const void *b, int32_t dim, int32_t sim, int32_t bits, double lambda, int32_t iters);
 
 // Exact replay of the reference's top-k loop (src/binaryQuantizationFormat.ts:383-411, src/minHeap.ts:9-130).
 // Feed rows in ascending global row order; rows that are skipped must be rows that cannot change the

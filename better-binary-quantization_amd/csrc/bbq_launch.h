@@ -2,7 +2,7 @@
 // bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip), the rerank (bbq_rerank_kernels.hip), the scoring of chosen rows (bbq_gather_kernels.hip)
 // the range search (bbq_range_kernels.hip), the span search (bbq_span_kernels.hip), the grouped search (bbq_group_kernels.hip), the MaxSim
 // search (bbq_maxsim_kernels.hip), MaxSim over chosen groups (bbq_maxsim_cand_kernels.hip), the exact MaxSim rerank (bbq_maxsim_rerank_kernels.hip) and the
-// exact search (bbq_exact_kernels.hip)
+// exact search (bbq_exact_kernels.hip), the query quantizer (bbq_query_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bbq_device.h"
@@ -146,5 +146,9 @@ hipError_t launch_exact_compact(const ExactCompactArgs &a, int n_queries, hipStr
 hipError_t launch_compact_vectors(float *out, const float *src, int32_t dim, const CompactMap &map, hipStream_t s);
 // staged fp32 row pos[i] -> row ords[pos[i]] of `out` [rows][dim], for the n_winners entries of pos (distinct ords), in place
 hipError_t launch_scatter_vectors(float *out, const float *staged, int32_t dim, const int32_t *ords, const int64_t *pos, int64_t n_winners, hipStream_t s);
+// query quantization (bbq_query_kernels.hip): bbq_quantize_queries for the n_queries queries of a.queries, one wave each -> a.qquant,
+// a.qcorr, a.status (bbq_device.h); a query with a status writes nothing else.  a.dim <= kQueryQuantMaxDim (its working vector lives in
+// the workgroup's LDS): hipErrorInvalidValue beyond, as for every argument out of range
+hipError_t launch_quantize_queries(const QueryQuantArgs &a, int n_queries, hipStream_t s);
 
 }  // namespace bbq

@@ -182,7 +182,9 @@ void parallel_rows(int64_t n, int n_threads, F f) {
   for (auto &x : th) x.join();
 }
 
-int check_common(const void *a, const void *b, int32_t dim, int32_t sim, int32_t bits, double lambda, int32_t iters) {
+}  // namespace
+
+int bbq::check_quantizer_args(const void *a, const void *b, int32_t dim, int32_t sim, int32_t bits, double lambda, int32_t iters) {
   if (!a || !b) return bbq::fail(BBQ_ERR_INVALID_ARG, "输入向量不能为空");
   if (dim <= 0) return bbq::fail(BBQ_ERR_INVALID_ARG, "dimension must be positive");
   if (sim < 0 || sim > 2) return bbq::fail(BBQ_ERR_INVALID_ARG, "不支持的相似性函数: %d", sim);
@@ -190,8 +192,6 @@ int check_common(const void *a, const void *b, int32_t dim, int32_t sim, int32_t
   if (iters < 0 || lambda != lambda) return bbq::fail(BBQ_ERR_INVALID_ARG, "bad lambda/iters");
   return BBQ_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -260,7 +260,7 @@ int bbq_quantize_vectors(const float *vectors, int64_t n, int32_t dim, int32_t s
   bbq::clear_error();
   if (n == 0) return bbq::fail(BBQ_ERR_EMPTY, "向量集合不能为空");  // src/binaryQuantizationFormat.ts:169-171
   if (n < 0) return bbq::fail(BBQ_ERR_INVALID_ARG, "n < 0");
-  int rc = check_common(vectors, codes, dim, sim, index_bits, lambda, iters);
+  int rc = bbq::check_quantizer_args(vectors, codes, dim, sim, index_bits, lambda, iters);
   if (rc != BBQ_OK) return rc;
   if (!corr || !centroid) return bbq::fail(BBQ_ERR_INVALID_ARG, "null output");
 
@@ -288,7 +288,7 @@ int bbq_quantize_rows(const float *vectors, int64_t n, int32_t dim, const float 
   bbq::clear_error();
   if (n < 0) return bbq::fail(BBQ_ERR_INVALID_ARG, "n < 0");
   if (n == 0) return BBQ_OK;
-  int rc = check_common(vectors, codes, dim, sim, index_bits, lambda, iters);
+  int rc = bbq::check_quantizer_args(vectors, codes, dim, sim, index_bits, lambda, iters);
   if (rc != BBQ_OK) return rc;
   if (!corr || !centroid) return bbq::fail(BBQ_ERR_INVALID_ARG, "null output");
   std::vector<float> norm;
@@ -302,7 +302,7 @@ int bbq_quantize_rows(const float *vectors, int64_t n, int32_t dim, const float 
 static int quantize_query_impl(const float *query, int32_t dim, const float *centroid, int32_t sim, int32_t qb, double lambda,
                                int32_t iters, uint8_t *qquant, double *qcorr, int normalisations) {
   bbq::clear_error();
-  int rc = check_common(query, centroid, dim, sim, qb, lambda, iters);
+  int rc = bbq::check_quantizer_args(query, centroid, dim, sim, qb, lambda, iters);
   if (rc != BBQ_OK) return rc;
   if (!qquant || !qcorr) return bbq::fail(BBQ_ERR_INVALID_ARG, "null output");
   std::vector<float> p(query, query + dim), t((size_t)dim);
@@ -336,7 +336,7 @@ int bbq_quantize_queries(const float *queries, int32_t n, int32_t dim, const flo
   if (bad_query) *bad_query = -1;
   if (n < 0) return bbq::fail(BBQ_ERR_INVALID_ARG, "n < 0");
   if (n == 0) return BBQ_OK;
-  int rc = check_common(queries, centroid, dim, sim, qb, lambda, iters);
+  int rc = bbq::check_quantizer_args(queries, centroid, dim, sim, qb, lambda, iters);
   if (rc != BBQ_OK) return rc;
   if (!qquant || !qcorr) return bbq::fail(BBQ_ERR_INVALID_ARG, "null output");
   int T = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();

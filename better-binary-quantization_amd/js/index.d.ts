@@ -67,6 +67,9 @@ export declare class BinaryQuantizationFormat {
   /** extension: drop the rows `ords` (any order, duplicates allowed): compactVectors over the complement.  Returns targetVectors. */
   removeVectors(targetVectors: BinarizedByteVectorValues, ords: ArrayLike<number>): BinarizedByteVectorValues;
   quantizeQueryVector(queryVector: Float32Array, centroid: Float32Array): { quantizedQuery: Uint8Array; queryCorrections: QuantizationResult };
+  /** extension: searchNearestNeighbors' query preparation for many queries at once, on the device that holds targetVectors: the
+   *  quantized bytes [n * dim] and corrections [n * 4] the host quantizer gives, bit for bit.  Not on a multi-device index (BBQ_DEVICES). */
+  quantizeQueriesOnDevice(queryVectors: Float32Array[], targetVectors: BinarizedByteVectorValues): { quantized: Uint8Array; corrections: Float64Array };
   searchNearestNeighbors(queryVector: Float32Array, targetVectors: BinarizedByteVectorValues, k: number): Array<{ index: number; score: number }>;
   /** extension: many independent queries per call, pipelined on the device */
   searchNearestNeighborsBatch(queryVectors: Float32Array[], targetVectors: BinarizedByteVectorValues, k: number): Array<Array<{ index: number; score: number }>>;

@@ -592,6 +592,24 @@ class BinaryQuantizationFormat {
     return { quantizedQuery: r.quantizedQuery, queryCorrections: corrObject(r.corrections, 0) };
   }
 
+  /**
+   * extension (not in the reference): searchNearestNeighbors' query preparation (:337-347) for many queries at once, on the device that
+   * holds targetVectors -> {quantized Uint8Array[n * dim], corrections Float64Array[n * 4]}: the bytes native.quantizeQueries returns
+   */
+  quantizeQueriesOnDevice(queryVectors, targetVectors) {
+    if (!queryVectors) throw new Error('查询向量不能为空');
+    if (!targetVectors) throw new Error('目标向量集合不能为空');
+    const dim = targetVectors.dimension(), q = this.quantizer;
+    const flat = new Float32Array(queryVectors.length * dim);
+    for (let i = 0; i < queryVectors.length; i++) {
+      if (!queryVectors[i]) throw new Error('查询向量不能为空');
+      if (queryVectors[i].length !== dim) throw new Error('查询向量维度与目标向量维度不匹配');
+      flat.set(queryVectors[i], i * dim);
+    }
+    return native.quantizeQueriesDevice(targetVectors._deviceIndex(), flat, queryVectors.length, targetVectors.getCentroid(),
+      simOrdinal(q.similarityFunction), this.config.queryBits, q.lambda, q.iters);
+  }
+
   /** searchNearestNeighbors(queryVector, targetVectors, k) -> Array<{index, score}>  (:308-412) */
   searchNearestNeighbors(queryVector, targetVectors, k) {
     if (!queryVector) throw new Error('查询向量不能为空');

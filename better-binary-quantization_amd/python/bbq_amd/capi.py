@@ -39,6 +39,7 @@ SYMBOLS = [
     "bbq_maxsim_reduce_true", "bbq_rerank_maxsim_groups_batch", "bbq_search_maxsim_rerank_batch",
     "bbq_true_topk", "bbq_vectors_search_batch", "bbq_vectors_set_option", "bbq_exact_bound", "bbq_vectors_exact_stats",
     "bbq_staged_bound_words", "bbq_staged_launches",
+    "bbq_quantize_queries_device",
 ]
 
 
@@ -168,6 +169,8 @@ def lib():
     L.bbq_quantize_query.argtypes = [vp, i32, vp, i32, i32, dbl, i32, vp, vp]
     L.bbq_quantize_query_vector.argtypes = [vp, i32, vp, i32, i32, dbl, i32, vp, vp]
     L.bbq_quantize_queries.argtypes = [vp, i32, i32, vp, i32, i32, dbl, i32, i32, vp, vp, C.POINTER(i32)]
+    if hasattr(L, "bbq_quantize_queries_device"):  # (BBQ_LIB may name an older build, for comparisons)
+        L.bbq_quantize_queries_device.argtypes = [vp, i32, vp, vp, i32, i32, dbl, i32, vp, vp, C.POINTER(i32)]
     L.bbq_centroid_dp.argtypes = [vp, i32]
     L.bbq_centroid_dp.restype = dbl
     L.bbq_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -543,6 +546,24 @@ class Index:
         _chk(lib().bbq_search_raw_batch(self._h, nq, _ptr(q), _ptr(cen), sim, query_bits, lam, iters, n_threads, k, _ptr(idx), _ptr(sc), _ptr(cnt),
                                        _ptr(qq), _ptr(qc), C.byref(bad)))
         return (idx, sc, cnt, qq, qc) if want_quantized else (idx, sc, cnt)
+
+    def quantize_queries(self, queries, centroid, sim, query_bits=4, lam=0.1, iters=5):
+        """quantize_queries on this index's device (bbq_quantize_queries_device): (qquant [n, dim], qcorr [n, 4]), the host's bytes.
+        A NaN / Infinity raises the host's BBQError with .bad_query set to the lowest offending query."""
+        q = np.ascontiguousarray(queries, np.float32)
+        cen = np.ascontiguousarray(centroid, np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim or cen.shape != (self.dim,):
+            raise BBQError(ERR_DIM_MISMATCH, "查询向量维度与目标向量维度不匹配")
+        n = q.shape[0]
+        qq = np.zeros((n, self.dim), np.uint8)
+        qc = np.zeros((n, 4), np.float64)
+        bad = C.c_int32(-1)
+        rc = lib().bbq_quantize_queries_device(self._h, n, _ptr(q), _ptr(cen), sim, query_bits, lam, iters, _ptr(qq), _ptr(qc), C.byref(bad))
+        if rc != OK:
+            e = BBQError(rc, lib().bbq_last_error().decode("utf-8", "replace"))
+            e.bad_query = bad.value
+            raise e
+        return qq, qc
 
     def score_rows(self, qquant, qcorr, query_bits, sim, row_begin=0, row_count=None):
         qq = np.ascontiguousarray(qquant, np.uint8)

@@ -859,6 +859,18 @@ int bbq_quantize_query(const float *query, int32_t dim, const float *centroid, i
 int bbq_quantize_queries(const float *queries, int32_t n, int32_t dim, const float *centroid, int32_t sim,
                          int32_t query_bits, double lambda, int32_t iters, int32_t n_threads, uint8_t *qquant,
                          double *qcorr, int32_t *bad_query);
+/* bbq_quantize_queries on idx's device instead of on host threads: the same qquant [n*dim] and qcorr [n*4], bit for bit, for the n
+ * queries [n*dim] of idx's dimension - normalizeVector twice under COSINE, the NaN / Infinity check, scalarQuantize at query_bits.
+ * One wave per query (bbq_query_kernels.hip): every sum of the reference is accumulated in its index order.  The queries go up in
+ * sub-batches of at most 4096; dim bytes and four f64 per query come back.  The argument checks are bbq_quantize_queries', with its
+ * messages, before anything is launched; n == 0: BBQ_OK.  With a NaN / Infinity in a query as the quantizer reads it, *bad_query (may
+ * be NULL) is the lowest such query of the call, the code and message are what bbq_quantize_query gives for it, and the outputs are
+ * unspecified.  A query's working vector lives in one workgroup's LDS: an index of more than 15680 dimensions is BBQ_ERR_UNSUPPORTED,
+ * as are a multi-device handle and a row shard.  Serializes with the other calls on idx's device; slower than the host for a single
+ * query (the chains are as long, and a launch and the copies come on top). */
+int bbq_quantize_queries_device(bbq_index *idx, int32_t n, const float *queries, const float *centroid, int32_t sim,
+                                int32_t query_bits, double lambda, int32_t iters, uint8_t *qquant, double *qcorr,
+                                int32_t *bad_query);
 /* quantizeQueryVector alone, src/binaryQuantizationFormat.ts:271-299 (normalises once for COSINE) */
 int bbq_quantize_query_vector(const float *query, int32_t dim, const float *centroid, int32_t sim,
                               int32_t query_bits, double lambda, int32_t iters, uint8_t *qquant, double *qcorr);
@@ -928,6 +940,10 @@ int bbq_reset_stats(bbq_index *idx);
  *   replay_threads 1..256 (half the host cores, at most 16)   flood_rows 0..2^24 (262144)   force_dense 0|1 (0)
  *   sweep_share 1|4|8|32 (1: every query sweeps the index itself; 32: shared sweep on the matrix cores, groups of 32 queries, two groups per load of the rows;
  *     32 also serves bbq_search_filtered_batch - tiles without an accepted row are not loaded; 4 and 8 do not: a filtered call sweeps per query under them)
+ *   device_queries -1|0|1 (-1): 1 lets bbq_search_raw_batch quantize all its queries on the device (bbq_quantize_queries_device) and then
+ *     search them as prepared queries, instead of quantizing them on host threads while the sub-batches in front are on the device; 0 and
+ *     -1 - the library's choice - keep host threads, as do a multi-device handle and an index of more than 15680 dimensions under any
+ *     value.  The quantized queries are the same bytes either way: never a different answer, error or bad_query
  *   device_select 0|1 (1: for k <= 1024 the device selects and sorts the answer itself whenever no two scores in or at the edge of it
  *   compare equal - then the reference heap provably returns that order - and the host replays the heap only for the rest)
  *   latency_queries 0..1024 (4), latency_growth 2..4096 (64): calls with at most latency_queries queries walk the index in
