@@ -890,7 +890,8 @@ typedef struct {
   int64_t total_scan_bytes;   /* and their algorithmic bytes */
   int64_t total_scan_launches;
   int64_t host_replays;       /* queries of the last call whose heap was replayed on the host (equal scores in or at the edge of the
-                                 answer, k > 1024, device_select 0); the others were selected and sorted by the last finalize launch */
+                                 answer, k > 1024, device_select 0, a last segment that lists more rows than the last finalize launch
+                                 selects from); the others were selected and sorted by the last finalize launch */
   int64_t resident_bytes;     /* bytes of ONE query's sweep of the index (all launches of its sub-batch; pilot replica included) that are
                                  loaded with the default cache policy, so that they stay in the device's 256 MiB Infinity Cache from one
                                  query's sweep to the next (option resident_mb, per launch); the rest is streamed with non-temporal loads.

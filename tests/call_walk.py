@@ -5,7 +5,7 @@ and holds every answer to the oracle.
 What the walks are after is the state a device context (DeviceCtx, bbq_host.h) carries from one call into the next, whatever index the
 next call is made on: the pipeline slots' grow-only buffers and the capacities the kernels take as strides, Slot::ctrl_clean, the
 latency answer block and its sequence word, sub-batches of an asynchronous sharded scan that stay busy across API calls, the scratch
-d_span / d_range / d_gather and the staging inside bbq_vectors, the cache bookkeeping and the options.  So the members of the CAST live
+d_span / d_range / d_gather / d_query_quant, the staging and the per-pair scratch inside bbq_vectors, the cache bookkeeping and the options.  So the members of the CAST live
 for a whole walk, a step names a member and a kind of call, and a walk is made of five things, shuffled block by block:
 
   * the TRANSITIONS: short fixed sequences the code marks as delicate - each entry's comment names the line it stems from;
@@ -34,6 +34,7 @@ K_LAT_PRE_KEYS = 12288        # kLatPreKeys, bbq_device.h
 PRESAMPLE_MIN_ROWS = 262144   # search_latency_presampled, bbq_latency.cpp: "N < 262144"
 LATENCY_W16 = (6, 8, 12)      # latency_path_supported, bbq_latency_kernels.hip
 TOKEN_BLOCK = 32              # kMaxSimTokenBlock (bbq_maxsim_token_block); the GPU test asserts it
+QUERY_QUANT_MAX_DIM = 15680   # kQueryQuantMaxDim, bbq_device.h: the widest query the device quantizer holds in one workgroup's LDS
 EUCLIDEAN, COSINE, MAXIMUM_INNER_PRODUCT = 0, 1, 2
 DEFAULT_SEEDS = 3             # BBQ_CALL_WALK_SEEDS asks for more
 FREE_STEPS = 60               # freely drawn steps a walk adds to its blocks: about a quarter of its steps
@@ -61,21 +62,24 @@ MAX_ROWS = {"ties": 6000, "multi": 1500}
 
 KINDS = ("search", "search_batch", "search_filtered_batch", "search_raw_batch", "range", "search_spans", "search_spans_filtered",
          "search_grouped", "search_maxsim", "maxsim_groups", "rerank", "maxsim_rerank", "score_rows", "score_ords", "search_ords",
-         "shard_scan", "shard_begin", "shard_wait", "set_option", "stats", "reset_stats", "refused", "recreate", "append", "save")
+         "shard_scan", "shard_begin", "shard_wait", "set_option", "stats", "reset_stats", "refused", "recreate", "append", "save",
+         "quantize_queries", "exact_search")
 READ_ONLY = tuple(k for k in KINDS if k not in ("append", "recreate", "set_option", "shard_scan", "shard_begin", "shard_wait", "save", "reset_stats"))
 D_SPAN_USERS = ("search_spans", "search_spans_filtered", "search_grouped", "search_maxsim", "maxsim_groups", "maxsim_rerank")   # bbq_host.h, DeviceCtx::d_span
 
 _ROOT_KINDS = ("search", "search_batch", "search_filtered_batch", "search_raw_batch", "range", "search_spans", "search_spans_filtered", "search_grouped",
-               "search_maxsim", "maxsim_groups", "score_rows", "score_ords", "search_ords", "set_option", "stats", "reset_stats", "refused", "recreate", "save")
+               "search_maxsim", "maxsim_groups", "score_rows", "score_ords", "search_ords", "set_option", "stats", "reset_stats", "refused", "recreate", "save",
+               "quantize_queries")
 ADMITS = {
-    "wide": _ROOT_KINDS + ("rerank", "maxsim_rerank"),
+    "wide": _ROOT_KINDS + ("rerank", "maxsim_rerank", "exact_search"),
     "ties": _ROOT_KINDS + ("append",),
     "multi": _ROOT_KINDS + ("append",),
     # 25 MB of rows: the calls that walk all of them for every query stay few, and no group set
-    "long": ("search", "search_batch", "search_filtered_batch", "range", "search_spans", "score_ords", "stats", "set_option", "refused"),
+    "long": ("search", "search_batch", "search_filtered_batch", "range", "search_spans", "score_ords", "stats", "set_option", "refused", "quantize_queries"),
     "shard": ("shard_scan", "shard_begin", "shard_wait", "stats", "set_option", "recreate", "save", "refused"),
-    # the root shard is an ordinary index: it searches, and a batch of its own may be in flight when it is asked to append
-    "root": ("search", "search_batch", "shard_scan", "shard_begin", "shard_wait", "stats", "recreate", "refused"),
+    # the root shard is an ordinary index: it searches, a batch of its own may be in flight when it is asked to append, and - row base 0,
+    # no pilot - the device quantizer takes its handle, with a batch in flight as well
+    "root": ("search", "search_batch", "shard_scan", "shard_begin", "shard_wait", "stats", "recreate", "refused", "quantize_queries"),
 }
 
 # include/bbq.h, bbq_set_option: (name, the values a walk sets - the first is the default, None where the default depends on the host)
@@ -85,7 +89,7 @@ OPTIONS = (
     ("tiles_per_wave", (-1, 1, 2, 4, 8)), ("group_scratch_mb", (256, 1)), ("maxsim_fused", (-1, 0, 1)), ("fast_bound", (1, 0)),
     ("replay_threads", (None, 1, 4)), ("flood_rows", (262144, 1 << 20)), ("force_dense", (0, 1)), ("sweep_share", (1, 4, 8, 32)),
     ("device_select", (1, 0)), ("latency_queries", (4, 0, 1)), ("latency_growth", (64, 2, 4096)), ("append_last", (1, 0)),
-    ("latency_fused", (1, 0)), ("latency_presample", (1, 0)),
+    ("latency_fused", (1, 0)), ("latency_presample", (1, 0)), ("device_queries", (-1, 1, 0)),
 )
 # the call an option is set in front of and behind: (member, kind, shape overrides)
 OPTION_CALLS = {
@@ -100,6 +104,7 @@ OPTION_CALLS = {
     "sweep_share": ("wide", "search_batch", {"nq": 70, "k": 10}), "device_select": ("ties", "search_batch", {"nq": 5, "k": 10}),
     "latency_queries": ("wide", "search_batch", {"nq": 2, "k": 10}), "latency_growth": ("wide", "search", {"k": 10}),
     "append_last": ("wide", "search", {"k": 10}), "latency_fused": ("wide", "search", {"k": 100}), "latency_presample": ("long", "search", {"k": 10}),
+    "device_queries": ("wide", "search_raw_batch", {"nq": 70, "k": 10}),
 }
 
 # a call that must fail before any launch: (what, the member it is made on, the documented code's name in capi)
@@ -112,6 +117,7 @@ REFUSALS = (
     ("wait_with_nothing_in_flight", "shard", "ERR_INVALID_ARG"),  # bbq_shard_scan_wait, bbq_shard.cpp: "no batch in flight"
     ("third_begin", "shard", "ERR_INVALID_ARG"),                  # bbq_shard_scan_begin, bbq_shard.cpp: "two batches are already in flight"
     ("append_with_unwaited_batch", "root", "ERR_INVALID_ARG"),    # include/bbq.h, append section
+    ("quantize_on_a_shard", "shard", "ERR_UNSUPPORTED"),          # bbq_quantize_queries_device, bbq_query_device.cpp: "not supported on a row shard"
 )
 
 
@@ -122,6 +128,12 @@ def refusals_of(member):
 
 
 NQS = (1, 2, 5, 33, 70, 130)
+QUANT_BITS = (1, 3, 4, 7)     # the queryBits a quantize_queries step draws
+HOSTILE = ("mixed", "extreme", "overflow", "identical")     # quant_hostile.BATCHES: the batches a quantize_queries step mixes in
+NONFINITE = "nonfinite"       # ... and one the quantizer refuses: a NaN in query nq // 2, an Infinity in the last one (nonfinite_queries)
+HOSTILE_N = 130               # the rows of the hostile batch a step takes its first nq from (the largest of NQS)
+TOUR_HOSTILE = {"wide": NONFINITE, "ties": "extreme", "multi": "overflow", "long": "mixed", "root": "identical"}    # of the member tour's step
+EXACT_NQS, EXACT_PREFILTER, EXACT_SLAB_ROWS = (1, 5, 33, 70), (-1, 0, 1), (0, 256)     # of an exact_search step
 RAGGED = (1, 2, 0, 63, 64, 65, 0, 7, 20, 3, 130)   # the sizes a ragged group set cycles through
 
 
@@ -159,6 +171,14 @@ def group_mask(member, n, which):
 def live_groups(off, mask):
     has = np.add.reduceat(np.concatenate([mask, [False]]).astype(np.int64), np.minimum(off[:-1], len(mask)))
     return np.flatnonzero((np.diff(off) > 0) & (has > 0)).astype(np.int64)
+
+
+def nonfinite_queries(q):
+    """a copy of the queries [nq, dim] with a NaN in query nq // 2 and an Infinity in the last one: the lowest bad query is nq // 2"""
+    q = np.array(q, np.float32)
+    q[len(q) // 2, 1 % q.shape[1]] = np.nan
+    q[-1, 0] = np.inf
+    return q
 
 
 def queries_of(step, pool):
@@ -226,13 +246,48 @@ def plan_segments(n, k, first_segment_rows=4096, growth=64):
     return segs
 
 
-def matrix_core_sweep(m, n_eff, k, opts, query_bits=None):
+def sweep_maxq(query_bits, feed):
+    """c.maxq (search_batch_impl, bbq_core.cpp): with a feed 2^query_bits - 1, whatever the values; without one 15 for values of at most
+    four planes, else the largest value, which 2^query_bits - 1 bounds"""
+    return (1 << query_bits) - 1 if feed or query_bits > 4 else 15
+
+
+def matrix_core_sweep(m, n_eff, k, opts, query_bits=None, feed=False):
     """does a batch search sweep on the matrix cores?  enqueue_subbatch (bbq_core.cpp): "use_mfma = !ext && c.share == 32 && c.maxq <= 127
     && ix->geom.store_bits == 1", every query's score uniforms finite (mfma_query_ok, bbq_query.cpp: any query quantized from finite
-    values); search_batch_impl: not on the dense path, maxq 15 for a query of at most four planes or 2^query_bits - 1 with a feed"""
+    values); search_batch_impl: not on the dense path, maxq from sweep_maxq - `feed` says whether the call has one: a raw call under
+    device_queries 1 has none (raw_call_prepares), its maxq and planes are those of bbq_search_batch on the same bytes"""
     o = lambda name, default: default if opts.get(name) is None else opts[name]
-    maxq = 15 if (query_bits or m.qb) <= 4 else 255
+    maxq = sweep_maxq(query_bits or m.qb, feed)
     return o("sweep_share", 1) == 32 and maxq <= 127 and m.ib == 1 and not o("force_dense", 0) and min(k, n_eff) <= K_MAX_FAST_K
+
+
+def device_queries_for_call(m, opts):
+    """device_queries_for_call (bbq_query_device.cpp): the option at 1 on a single-device index (every member of the cast is one) without
+    a pilot replica, with row base 0 and at most kQueryQuantMaxDim dimensions"""
+    row_base = m.rows[0] if m.rows else 0
+    return opts.get("device_queries") == 1 and not m.pilot and row_base == 0 and m.dim <= QUERY_QUANT_MAX_DIM
+
+
+def raw_call_prepares(m, nq, k, opts):
+    """where bbq_search_raw_batch (bbq_core.cpp) gets its quantized queries from: "device" - bbq_quantize_queries_device, then
+    search_batch_impl WITHOUT a feed; "host" - bbq_quantize_queries first, at most 64 queries or k == 0, without a feed as well; "feed" -
+    host threads beside the sweeps.  Without a feed the call is bbq_search_batch on the same bytes: planes and maxq come from the
+    values, one query takes the single-query chains"""
+    if device_queries_for_call(m, opts):
+        return "device"
+    return "host" if nq <= 64 or k == 0 else "feed"
+
+
+def raw_query_path(m, n, k, nq, opts):
+    """(raw_call_prepares, single_query_path) of a raw call: a feed never takes the chains ("!feed", search_batch_impl)"""
+    prepares = raw_call_prepares(m, nq, k, opts)
+    return prepares, single_query_path(m, n, k, opts) if nq == 1 and prepares != "feed" else "general"
+
+
+def exact_refused(k, accepted):
+    """bbq_vectors_search_batch (bbq_exact.cpp): "if (kk > kMaxFastK)" with kk = min(k, accepted rows) - BBQ_ERR_UNSUPPORTED, nothing launched"""
+    return min(k, accepted) > K_MAX_FAST_K
 
 
 def single_query_path(m, n, k, opts):
@@ -260,6 +315,7 @@ class State:
         self.src = {name: np.arange(n, dtype=np.int64) for name, n in APPEND_POOL.items()}
         self.options = {name: {} for name in CAST}
         self.inflight = {name: [] for name in CAST}
+        self.vectors = {"exact_prefilter": -1, "exact_slab_rows": 0}    # the options in force on WITH_VECTORS' bbq_vectors: an exact_search sets both
 
     def in_flight(self):
         return sum(len(v) for v in self.inflight.values())
@@ -378,6 +434,13 @@ class _Draw:
             s.update(q0=self.q0(member), nq=nq, lists=lists, k=self.pick([1, 10, max(len(l) for l in lists) + 1]))
         elif kind in ("shard_scan", "shard_begin"):
             s.update(q0=self.q0(member), nq=self.pick([1, 5, 33]), k=self.pick([1, 10, 100]))
+        elif kind == "quantize_queries":
+            # the member's pool queries; one step in three takes every other query (the even places) from a hostile batch at its dimension
+            s.update(q0=self.q0(member), nq=self.pick(NQS), sim=int(self.pick([0, 1, 2])), qb=int(self.pick(QUANT_BITS)),
+                     hostile=self.pick(HOSTILE + (NONFINITE,)) if int(rng.integers(3)) == 0 else None)
+        elif kind == "exact_search":
+            s.update(q0=self.q0(member), nq=self.pick(EXACT_NQS), k=self.pick([1, 10, 100, K_MAX_FAST_K, n + 5]), sim=int(self.pick([0, 1, 2])),
+                     filter=self.pick([None, "sparse", "dense"]), prefilter=int(self.pick(EXACT_PREFILTER)), slab=int(self.pick(EXACT_SLAB_ROWS)))
         elif kind == "set_option":
             name, values = self.pick([o for o in OPTIONS if o[0] != "force_dense"])   # (a free draw never ends a member's sweeps for good)
             s.update(option=name, value=self.pick([v for v in values if v is not None and v != st.options[member].get(name, values[0])]))
@@ -432,6 +495,8 @@ class _Draw:
         elif kind == "append":
             st.src[member] = np.concatenate([st.src[member], s["rows"]])
             st.n[member] = len(st.src[member])
+        elif kind == "exact_search":       # the player sets both in front of the call and leaves them in force
+            st.vectors = {"exact_prefilter": s["prefilter"], "exact_slab_rows": s["slab"]}
         return s
 
 
@@ -468,6 +533,26 @@ TRANSITIONS = {
     # the matrix-core sweep appended.  The option stays in force behind the block: `wide` sweeps shared until a chain's block resets it
     "matrix_core_sweeps": (("set_option", "wide"), ("search_batch", "wide"), ("search_filtered_batch", "wide"), ("search_raw_batch", "wide"),
                            ("search_batch", "wide"), ("search_filtered_batch", "wide")),
+    # DeviceCtx::d_query_quant (bbq_host.h) is one grow-only scratch for every index of the device; "const Layout lay(std::min(n, kSubBatch),
+    # dim);" (bbq_quantize_queries_device, bbq_query_device.cpp) places the centroid, the outputs and the status words behind n x dim
+    # floats, so they move with every call, and the centroid is uploaded into it once per call: 96-d x 5, 768-d x 130 - the scratch
+    # grows -, 64-d x 2 - every offset falls into what the call before wrote -, and the first call again
+    "quantize_across_dimensions": (("quantize_queries", "multi"), ("quantize_queries", "wide"), ("quantize_queries", "ties"), ("quantize_queries", "multi")),
+    # "hipStream_t st = ctx->aux_stream;" (bbq_query_device.cpp): the stream a root shard's asynchronous batch runs on (bbq_shard.cpp); the
+    # root member has row base 0 and no pilot, so the quantizer takes its handle while its batch is in flight, and a raw call under
+    # device_queries 1 on another index settles the batch's slots (settle_shard_slots, search_batch_impl) behind a device quantization
+    "quantize_beside_a_batch_in_flight": (("shard_begin", "root"), ("quantize_queries", "root"), ("search_raw_batch", "ties"), ("shard_wait", "root")),
+    # "if (device_queries_for_call(ix)) {" (bbq_search_raw_batch, bbq_core.cpp) hands on to search_batch_impl with a null feed: ONE raw query
+    # takes the single-query chain ("if (n_queries == 1 && plan.latency && !feed && !flt) {") behind a launch on aux_stream, under 1, 0 and 1
+    "single_raw_query_on_the_chain": (("set_option", "wide"), ("search_raw_batch", "wide"), ("set_option", "wide"), ("search_raw_batch", "wide"),
+                                      ("set_option", "wide"), ("search_raw_batch", "wide")),
+    # the per-pair scratch of bbq_vectors_search_batch is 16 bytes with the prefilter and 8 without, exact_slab_rows 0 is "what the scratch
+    # allows", the survivor lists hold 2 kk + 1024 entries (bbq_exact.cpp): kk 4096 and 5 queries, then the f64 sweep alone with 70, then
+    # slabs of 256 rows with kk 1, then EUCLIDEAN - no prefilter, whatever the option says -, then the two other users of the handle's staging
+    "exact_prefilter_slabs_and_staging": (("exact_search", "wide"), ("exact_search", "wide"), ("exact_search", "wide"), ("exact_search", "wide"),
+                                          ("rerank", "wide"), ("maxsim_rerank", "wide")),
+    # the bbq_vectors outlives the index beside it: its filters are made again for the new index (bbq_filter holds rows and a device, no index)
+    "exact_search_around_a_recreate": (("exact_search", "wide"), ("recreate", "wide"), ("exact_search", "wide")),
 }
 _FIXED = {   # the shapes a transition needs fixed
     "general_then_latency": ({"nq": 5, "k": 10}, {"k": 10}),
@@ -478,6 +563,15 @@ _FIXED = {   # the shapes a transition needs fixed
     "long_rerank_then_one_row": ({"shape": "long_lists"}, {"shape": "one_row"}),
     "matrix_core_sweeps": ({"option": "sweep_share", "value": 32}, {"nq": 70, "k": 10}, {"nq": 70, "k": 100, "filter": "dense"}, {"nq": 70, "k": 10},
                            {"nq": 130, "k": K_FINAL_SELECT_MAX + 1}, {"nq": 33, "k": 10, "filter": "sparse"}),
+    "quantize_across_dimensions": ({"nq": 5}, {"nq": 130}, {"nq": 2}, {"same": 0}),
+    "quantize_beside_a_batch_in_flight": ({}, {"nq": 33, "hostile": NONFINITE}, {"nq": 70, "k": 10}, {}),    # a refusal on aux_stream beside the batch
+    "single_raw_query_on_the_chain": ({"option": "device_queries", "value": 1}, {"nq": 1, "k": 10}, {"option": "device_queries", "value": 0}, {"same": 1},
+                                      {"option": "device_queries", "value": 1}, {"same": 1}),
+    "exact_prefilter_slabs_and_staging": ({"prefilter": 1, "k": K_MAX_FAST_K, "nq": 5, "sim": COSINE, "filter": None},
+                                          {"prefilter": 0, "slab": 0, "nq": 70, "k": 10, "sim": COSINE},
+                                          {"prefilter": 1, "slab": 256, "nq": 70, "k": 1, "sim": MAXIMUM_INNER_PRODUCT},
+                                          {"prefilter": 1, "slab": 0, "sim": EUCLIDEAN}, {}, {}),
+    "exact_search_around_a_recreate": ({"prefilter": 1, "sim": COSINE, "nq": 33, "k": 10, "filter": "dense"}, {}, {"same": 0}),
 }
 
 
@@ -518,14 +612,17 @@ def _transition(d, name):
     chains it names back on the default latency options, a shard it begins a batch on idle"""
     out = []
     fixed = _FIXED.get(name, ({},) * len(TRANSITIONS[name]))
-    for member in sorted({m for k, m in TRANSITIONS[name] if k == "search"}):
-        ks = [fx["k"] for (kind, mem), fx in zip(TRANSITIONS[name], fixed) if kind == "search" and mem == member and "k" in fx]
+    chained = lambda kind, fx: kind == "search" or (kind == "search_raw_batch" and fx.get("nq") == 1)    # the steps that are about a chain
+    for member in sorted({m for (k, m), fx in zip(TRANSITIONS[name], fixed) if chained(k, fx)}):
+        ks = [fx["k"] for (kind, mem), fx in zip(TRANSITIONS[name], fixed) if chained(kind, fx) and mem == member and "k" in fx]
         out += _restore(d, member, name + ":pre", max(ks))
     for member in sorted({m for k, m in TRANSITIONS[name] if k == "shard_begin"}):
         while d.st.inflight[member]:
             out.append(d.done(d.step("shard_wait", member, name + ":pre")))
     if name == "matrix_core_sweeps" and d.st.options["wide"].get("force_dense", 0):
         out.append(d.done(d.step("set_option", "wide", name + ":pre", option="force_dense", value=0)))
+    if name == "quantize_beside_a_batch_in_flight" and d.st.options["ties"].get("device_queries") != 1:
+        out.append(d.done(d.step("set_option", "ties", name + ":pre", option="device_queries", value=1)))
     body = []
     for (kind, member), fx in zip(TRANSITIONS[name], fixed):
         if "same" in fx:
@@ -670,6 +767,8 @@ def walk(seed):
             if what == "call" and kind == "search_batch":     # the member tour's batch searches take the k values beside the two limits
                 n = d.st.n[member]
                 over["k"] = {"wide": K_FINAL_SELECT_MAX + 1, "ties": K_MAX_FAST_K + 1, "multi": n + 3, "long": K_FINAL_SELECT_MAX + 1, "root": n}[member]
+            if what == "call" and kind == "quantize_queries":     # ... and its quantizations every batch of quant_hostile and the refused one
+                over["hostile"] = TOUR_HOSTILE[member]
             out += pre + [d.done(d.step(kind, member, what, **over))]
     for member in CAST:
         while d.st.inflight[member]:
@@ -687,6 +786,9 @@ def read_only_walk(seed, member="ties", steps=30):
         kind = kinds[int(rng.integers(len(kinds)))] if i >= len(kinds) else kinds[i]
         if kind == "refused":
             out.append(d.step(kind, member, "threads", what=d.pick(["filter_of_another_size", "group_outside_the_set"])))
+        elif kind == "quantize_queries":     # a refused batch would show in the thread's bbq_last_error, which that test holds empty
+            s = d.step(kind, member, "threads")
+            out.append(dict(s, hostile=None if s["hostile"] == NONFINITE else s["hostile"]))
         else:
             out.append(d.step(kind, member, "threads"))
     return out
@@ -708,7 +810,8 @@ def describe(step):
         return str(a) if len(a) <= 10 else "[%s, ... %d entries ..., %s]" % (", ".join(map(str, a[:5])), len(a), ", ".join(map(str, a[-2:])))
 
     parts = [step["kind"], "on", step["member"]]
-    for key in ("what", "option", "value", "shape", "q0", "nq", "k", "filter", "groups", "tokens", "ranks", "true_sim", "factor", "selector"):
+    for key in ("what", "option", "value", "shape", "q0", "nq", "k", "sim", "qb", "hostile", "filter", "prefilter", "slab", "groups", "tokens", "ranks",
+                "true_sim", "factor", "selector"):
         if key in step:
             parts.append("%s=%s" % (key, step[key]))
     for key in ("spans", "cand", "lists", "rows"):

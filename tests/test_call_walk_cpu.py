@@ -3,7 +3,8 @@ and the host rules the cast leans on, restated in call_walk and held to the sour
 kernel or which chain a member reaches fails here instead of leaving the walks on another path than their comments name.  Over the
 default seeds (BBQ_CALL_WALK_SEEDS for more, never fewer than the default): every kind occurs, every listed transition occurs with the
 paths it is about (the matrix-core sweeps under sweep_share 32 among them), every option takes every listed value with the same call on
-both sides, every member is the target of every kind it admits,
+both sides - device_queries, parsed outside bbq_index.cpp, among them -, every member is the target of every kind it admits, the device
+quantizer and the exact search with its prefilter are kinds like any other and have their own transitions,
 a shard batch is in flight across a step of every kind, every refusal is made, and every walk ends with nothing in flight."""
 import os
 import re
@@ -104,12 +105,112 @@ def test_every_walk_sweeps_wide_on_the_matrix_cores():
         for s, (opts, _, n) in W.replay(walk(seed)):
             if s["via"] == "matrix_core_sweeps" and s["kind"] != "set_option":
                 n_eff = int(W.mask_of("wide", n, s["filter"]).sum()) if "filter" in s else n
-                assert opts.get("sweep_share") == 32 and W.matrix_core_sweep(wide, n_eff, s["k"], opts), (seed, W.describe(s), opts)
+                feed = s["kind"] == "search_raw_batch" and W.raw_call_prepares(wide, s["nq"], s["k"], opts) == "feed"
+                assert opts.get("sweep_share") == 32 and W.matrix_core_sweep(wide, n_eff, s["k"], opts, feed=feed), (seed, W.describe(s), opts)
                 seen.append((s["kind"], s["nq"], s["k"] > W.K_FINAL_SELECT_MAX))
         assert ("search_batch", 70, False) in seen and ("search_raw_batch", 70, False) in seen and ("search_batch", 130, True) in seen, (seed, seen)
         assert {nq for kind, nq, _ in seen if kind == "search_filtered_batch"} == {70, 33}, (seed, seen)
     assert not W.matrix_core_sweep(wide, wide.n0, 10, {}) and not W.matrix_core_sweep(wide, wide.n0, 10, {"sweep_share": 4})
     assert not W.matrix_core_sweep(wide, wide.n0, 10, {"sweep_share": 32, "force_dense": 1}) and not W.matrix_core_sweep(W.CAST["multi"], 200, 10, {"sweep_share": 32})
+
+
+def test_the_raw_calls_under_device_queries_take_the_paths_they_name():
+    """the rule, held to its source lines; one raw query on `wide` reaches the chain under 1, 0 and 1 in every walk; the option block's 70
+    queries go through the device and through the feed; `ties` answers a device-quantized raw call while root's batch is in flight"""
+    core, dev = _source("bbq_core.cpp"), _source("bbq_query_device.cpp")
+    assert "return ix->opt_device_queries == 1 && !ix->multi && !ix->has_pilot && ix->row_base == 0 && ix->geom.dim <= kQueryQuantMaxDim;" in dev
+    assert re.search(r"constexpr int32_t kQueryQuantMaxDim = .*;  // %d\n" % W.QUERY_QUANT_MAX_DIM, _source("bbq_device.h"))
+    assert "a query's working vector lives in one workgroup's LDS, which holds at most %d" in dev and "15680" in _source("bbq.h")
+    assert re.search(r"if \(device_queries_for_call\(ix\)\) \{\s*int rc = bbq_quantize_queries_device\(ix, n_queries, queries, centroid, sim, query_bits, lambda, iters, "
+                     r"qq, qc, bad_query\);\s*if \(rc != BBQ_OK\) return rc;\s*return search_batch_impl\(ix, n_queries, qq, qc, query_bits, sim, k, out_idx, out_score, "
+                     r"out_n, nullptr, nullptr\);", core)
+    assert "if (n_queries <= 64 || k == 0 || ix->multi) {" in core
+    assert "c.planes = planes_of_call(ix, qquant, (int64_t)n_queries * ix->geom.dim, query_bits == 1);" in core
+    assert "hipStream_t st = ctx->aux_stream;" in dev and "const Layout lay(std::min(n, kSubBatch), dim);" in dev
+    assert "HIPCHK(hipMemcpyAsync(base + lay.centroid, centroid, (size_t)dim * sizeof(float), hipMemcpyHostToDevice, st));" in dev
+    assert 'return fail(BBQ_ERR_UNSUPPORTED, "bbq_quantize_queries_device is not supported on a row shard");' in dev
+    wide, ties, shard, root = (W.CAST[m] for m in ("wide", "ties", "shard", "root"))
+    on = {"device_queries": 1}
+    assert W.device_queries_for_call(wide, on) and W.device_queries_for_call(root, on) and not W.device_queries_for_call(shard, on)
+    assert not W.device_queries_for_call(wide, {}) and not W.device_queries_for_call(wide, {"device_queries": 0}) and not W.device_queries_for_call(wide, {"device_queries": -1})
+    assert not W.device_queries_for_call(wide._replace(dim=W.QUERY_QUANT_MAX_DIM + 1), on) and W.device_queries_for_call(wide._replace(dim=W.QUERY_QUANT_MAX_DIM), on)
+    assert [W.raw_call_prepares(wide, nq, 10, {}) for nq in (1, 64, 65, 70)] == ["host", "host", "feed", "feed"] and W.raw_call_prepares(wide, 70, 0, {}) == "host"
+    assert [W.raw_call_prepares(wide, nq, 10, on) for nq in (1, 70)] == ["device", "device"]
+    # the forms of tests/rawbatch_cells.py: S = 1 and S = 1/2 need the feed; without one every query of at most four planes runs maxq 15
+    assert [W.sweep_maxq(qb, True) for qb in (1, 2, 3, 4, 7, 8)] == [1, 3, 7, 15, 127, 255] and [W.sweep_maxq(qb, False) for qb in (1, 2, 3, 4, 7)] == [15, 15, 15, 15, 127]
+    share = {"sweep_share": 32}
+    assert W.matrix_core_sweep(wide, wide.n0, 10, share, query_bits=8) is False and not W.matrix_core_sweep(wide, wide.n0, 10, share, query_bits=8, feed=True)
+    assert W.matrix_core_sweep(wide, wide.n0, 10, dict(share, **on), query_bits=3) and W.matrix_core_sweep(wide, wide.n0, 10, share, query_bits=3, feed=True)
+    for seed in SEEDS:
+        single, block, beside = [], [], []
+        for s, (opts, in_flight, n) in W.replay(walk(seed)):
+            if s["kind"] != "search_raw_batch":
+                continue
+            m = W.CAST[s["member"]]
+            if s["via"] == "single_raw_query_on_the_chain":
+                single.append(W.raw_query_path(m, n, s["k"], s["nq"], opts))
+            elif s["via"] == "option:device_queries":
+                block.append(W.raw_query_path(m, n, s["k"], s["nq"], opts)[0])
+            elif s["via"] == "quantize_beside_a_batch_in_flight":
+                beside.append((W.raw_call_prepares(m, s["nq"], s["k"], opts), in_flight > 0))
+        assert single == [("device", "chain"), ("host", "chain"), ("device", "chain")], (seed, single)
+        assert beside == [("device", True)], (seed, beside)
+        if block:
+            assert len(block) == 3 and block.count("device") == 1 and block.count("feed") == 2, (seed, block)
+    assert sum(any(s["via"] == "option:device_queries" for s in walk(seed)) for seed in range(W.DEFAULT_SEEDS)) == 1
+
+
+def test_the_quantize_steps_cross_dimensions_sizes_and_hostile_batches():
+    import quant_hostile as Q
+    assert W.HOSTILE == Q.BATCHES and W.HOSTILE_N == max(W.NQS)
+    for seed in SEEDS:
+        mine = [s for s in walk(seed) if s["via"] == "quantize_across_dimensions"]
+        assert [(W.CAST[s["member"]].dim, s["nq"]) for s in mine] == [(96, 5), (768, 130), (64, 2), (96, 5)], seed
+        assert W.describe(mine[0]) == W.describe(mine[3])
+    steps = [s for _, _, s in all_steps() if s["kind"] == "quantize_queries"]
+    assert {s["sim"] for s in steps} == {0, 1, 2} and {s["qb"] for s in steps} == set(W.QUANT_BITS) and {s["nq"] for s in steps} == set(W.NQS)
+    assert {s["hostile"] for s in steps} == {None, W.NONFINITE} | set(W.HOSTILE) == {None} | set(W.TOUR_HOSTILE.values())
+    for seed in SEEDS:            # in every walk the quantizer refuses a batch on `root` while root's own batch is in flight
+        assert [s["hostile"] for s, (_, in_flight, _) in W.replay(walk(seed)) if s["via"] == "quantize_beside_a_batch_in_flight" and s["kind"] == "quantize_queries"
+                and in_flight > 0] == [W.NONFINITE]
+    bad = W.nonfinite_queries(np.ones((5, 3), np.float32))
+    assert np.isnan(bad[2, 1]) and np.isinf(bad[4, 0]) and np.isfinite(bad[:2]).all() and not np.isfinite(W.nonfinite_queries(np.ones((1, 1), np.float32))).any()
+    assert {s["member"] for s in steps} == {m for m in W.CAST if "quantize_queries" in W.ADMITS[m]} == {"wide", "ties", "multi", "long", "root"}
+    assert any(s["kind"] == "refused" and s["what"] == "quantize_on_a_shard" for _, _, s in all_steps())
+
+
+def test_the_exact_steps_change_the_scratch_under_a_live_handle():
+    ex = _source("bbq_exact.cpp")
+    n = W.CAST["wide"].n0
+    assert W.WITH_VECTORS == "wide" and [m for m in W.CAST if "exact_search" in W.ADMITS[m]] == ["wide"]
+    assert "inline int64_t exact_survivor_cap(int64_t kk) { return 2 * kk + 1024; }" in _source("bbq_device.h")
+    assert "const int64_t pair_bytes = pre ? 16 : 8;" in ex and "if (S == 0) S = std::max(kExactSlabStep, std::min(kExactSlabMax, kExactScratchBytes / (pair_bytes * (int64_t)per)" in ex
+    assert "const bool pre = exact_prefilter_serves(true_sim) && (v->opt_exact_prefilter == 1 || (v->opt_exact_prefilter < 0 && kExactPrefilterDefault[true_sim]));" in ex
+    assert "constexpr bool kExactPrefilterDefault[3] = {false, false, false};" in ex            # -1 is the f64 sweep: what the player's read-out conditions say
+    assert "if (kk > kMaxFastK)" in ex                                                          # min(k, accepted rows) beyond 4096 is refused: exact_refused
+    assert W.exact_refused(n + 5, n) and W.exact_refused(n + 5, 4097) and not W.exact_refused(n + 5, 4096) and not W.exact_refused(W.K_MAX_FAST_K, n)
+    for seed in SEEDS:
+        steps = walk(seed)
+        mine = [s for s in steps if s["via"] == "exact_prefilter_slabs_and_staging" and s["kind"] == "exact_search"]
+        assert [(s["prefilter"], s["nq"], s["k"], s["sim"]) for s in mine[:3]] == [(1, 5, W.K_MAX_FAST_K, 1), (0, 70, 10, 1), (1, 70, 1, 2)], seed
+        assert (mine[1]["slab"], mine[2]["slab"]) == (0, 256) and (mine[3]["prefilter"], mine[3]["slab"], mine[3]["sim"]) == (1, 0, 0) and mine[0]["filter"] is None
+        a, b, c = [s for s in steps if s["via"] == "exact_search_around_a_recreate"]
+        assert W.describe(a) == W.describe(c) and a["prefilter"] == 1 and a["sim"] in (1, 2) and b["kind"] == "recreate" and a["filter"] == "dense"
+    steps = [s for _, _, s in all_steps() if s["kind"] == "exact_search"]
+    assert {s["prefilter"] for s in steps} == set(W.EXACT_PREFILTER) and {s["slab"] for s in steps} == set(W.EXACT_SLAB_ROWS)
+    assert {s["nq"] for s in steps} == set(W.EXACT_NQS) and {s["sim"] for s in steps} == {0, 1, 2} and {s["filter"] for s in steps} == {None, "sparse", "dense"}
+    assert {s["k"] for s in steps} >= {1, 10, W.K_MAX_FAST_K, n + 5}
+    # consecutive exact steps of a walk set change the per-pair size (prefilter on / off under COSINE or MIP) and the slab rule both ways
+    pre = lambda s: s["prefilter"] == 1 and s["sim"] != 0
+    pairs = [(a, b) for seed in SEEDS for a, b in zip(*[[s for s in walk(seed) if s["kind"] == "exact_search"][i:] for i in (0, 1)])]
+    assert {(pre(a), pre(b)) for a, b in pairs} == {(False, False), (False, True), (True, False), (True, True)}
+    assert {(a["slab"], b["slab"]) for a, b in pairs} == {(0, 0), (0, 256), (256, 0), (256, 256)}
+    # replay() carries the options in force on the vectors behind every step
+    d = W._Draw(np.random.default_rng(0), 0)
+    for s in walk(0):
+        d.done(s)
+        if s["kind"] == "exact_search":
+            assert d.st.vectors == {"exact_prefilter": s["prefilter"], "exact_slab_rows": s["slab"]}
 
 
 def test_every_ordered_pair_of_the_d_span_users_occurs():
@@ -125,8 +226,9 @@ def test_every_option_takes_two_values_around_the_same_call():
     names = [n for n, _ in W.OPTIONS]
     for n in names:
         assert re.search(r"\b%s\b" % n, header), n
-    # every name bbq_set_option knows is in the list
-    known = set(re.findall(r'n == "([a-z0-9_]+)"', _source("bbq_index.cpp")))
+    # every name bbq_set_option knows is in the list: the chain of bbq_index.cpp, and what bbq_query_device.cpp compares the name with
+    known = set(re.findall(r'n == "([a-z0-9_]+)"', _source("bbq_index.cpp"))) | set(re.findall(r'strcmp\(name, "([a-z0-9_]+)"\)', _source("bbq_query_device.cpp")))
+    assert "device_queries" in known and "if (set_device_queries_option(ix, name, v, &rc)) return rc;" in _source("bbq_index.cpp")
     assert known == set(names), known ^ set(names)
     assert set(W.OPTION_CALLS) == set(names)
     values = {n: set() for n in names}
@@ -200,7 +302,7 @@ def test_the_k_and_query_counts_of_the_edges_are_drawn():
     assert {s["nq"] for _, _, s in all_steps() if s["kind"] == "search_batch"} >= {1, 5, 33, 70, 130}
     counts = {c for _, _, s in all_steps() if "tokens" in s for _, c in s["tokens"]}
     assert counts == {1, W.TOKEN_BLOCK, W.TOKEN_BLOCK + 1}
-    assert {s["nq"] for _, _, s in all_steps() if s["kind"] == "search_raw_batch"} == {5, 70}
+    assert {s["nq"] for _, _, s in all_steps() if s["kind"] == "search_raw_batch"} == {1, 5, 70}      # 1: single_raw_query_on_the_chain
     assert {s["shape"] for _, _, s in all_steps() if s["kind"] == "rerank"} >= {"long_lists", "one_row"}
 
 
@@ -208,7 +310,7 @@ def test_read_only_walks_hold_read_only_kinds():
     for seed in range(4):
         steps = W.read_only_walk(seed)
         assert {s["kind"] for s in steps} <= set(W.READ_ONLY) and all(s["member"] == "ties" for s in steps)
-        assert any(s["kind"] == "refused" for s in steps)
+        assert any(s["kind"] == "refused" for s in steps) and not any(s.get("hostile") == W.NONFINITE for s in steps)
         assert {s["kind"] for s in steps} >= {"search_batch", "search_filtered_batch", "search_spans", "search_grouped", "search_maxsim", "range", "score_ords"}
 
 
@@ -218,6 +320,9 @@ def test_the_constants_are_the_sources():
     assert "constexpr int kFinalSelectMax = %d;" % W.K_FINAL_SELECT_MAX in device
     assert "constexpr int64_t kMaxFastK = %d;" % W.K_MAX_FAST_K in host
     assert "constexpr int kLatPreKeys = %d;" % W.K_LAT_PRE_KEYS in device
+    assert "constexpr int kFinalizeKeyCap = %d;" % W.K_LAT_PRE_KEYS in device       # the GPU player's selection_fits
+    assert "m_new <= (uint32_t)kFinalizeKeyCap - tcount && a.k == k2 + 1;" in _source("bbq_kernels.hip")
+    assert "p.growth = latency ? ix->opt_latency_growth : ix->opt_growth;" in _source("bbq_core.cpp")
     assert "constexpr int kTileRows = %d;" % W.TILE in device
     assert "N < %d" % W.PRESAMPLE_MIN_ROWS in latency
     assert re.search(r"#define BBQ_CHUNK_ROWS %d\b" % W.CHUNK, device) and "BBQ_CHUNK_ROWS" not in _source("Makefile")

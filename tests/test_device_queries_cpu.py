@@ -28,3 +28,22 @@ def test_refused_without_a_device(kw, text):
 def test_nothing_to_do_and_the_option():
     assert _call(n=0)[:2] == (capi.OK, -1)
     assert capi.lib().bbq_set_option(None, b"device_queries", 1) == capi.ERR_INVALID_ARG
+
+
+def test_the_raw_call_hands_device_quantized_queries_on_without_a_feed():
+    """bbq_search_raw_batch under device_queries 1 (csrc/bbq_core.cpp): the whole batch through the device quantizer, then search_batch_impl
+    with a null feed and a null bad_query - planes, maxq and the single-query chains are bbq_search_batch's on the same bytes, which is
+    what tests/call_walk.py (raw_call_prepares) and the device_queries tests of tests/test_gpu_rawbatch_sweeps.py rest on"""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "better-binary-quantization_amd", "csrc", "bbq_core.cpp"), encoding="utf-8") as f:
+        core = f.read()
+    block = re.search(r"  // option device_queries: all queries through the device quantizer \(bbq_query_device\.cpp\), then the search of prepared queries\n"
+                      r"  if \(device_queries_for_call\(ix\)\) \{\n"
+                      r"    int rc = bbq_quantize_queries_device\(ix, n_queries, queries, centroid, sim, query_bits, lambda, iters, qq, qc, bad_query\);\n"
+                      r"    if \(rc != BBQ_OK\) return rc;\n"
+                      r"    return search_batch_impl\(ix, n_queries, qq, qc, query_bits, sim, k, out_idx, out_score, out_n, nullptr, nullptr\);\n"
+                      r"  \}\n", core)
+    assert block, "the composition of bbq_search_raw_batch under device_queries 1 has changed: the call walk's model restates it"
+    assert core.index("if (device_queries_for_call(ix)) {") < core.index("if (n_queries <= 64 || k == 0 || ix->multi) {") < core.index("RawFeed feed;")
+    assert "if (n_queries == 1 && plan.latency && !feed && !flt) {" in core and "if (feed) {  // the values are still being produced" in core

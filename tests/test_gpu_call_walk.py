@@ -4,14 +4,19 @@ for a whole walk; a step is one call of one kind on one member, and after EVERY 
 score bits, order, counts and statuses, bit for bit (canon32, canon64), no tolerances.  Expected values come from the oracle alone -
 O.score_all and O.true_similarity, the numpy models of the MaxSim calls, O.heap_topk and O.rerank_select - computed once per member and
 query pool and shared by the walks; the comparisons are the existing helpers' (Oracle.check_search, assert_spans, assert_filtered,
-assert_grouped, assert_maxsim, assert_lists, assert_range).  A failure names seed, step, the step's line (call_walk.describe), the
+assert_grouped, assert_maxsim, assert_lists, assert_range).  Two kinds have no quantized scores behind them: quantize_queries - the
+device quantizer's bytes, code, bad_query and message are bbq_quantize_queries', and for the first and last query the oracle's - and
+exact_search - bbq_vectors_search_batch under the exact_prefilter and exact_slab_rows of the step, held to exact_model.topk over
+exact_model.scores, computed once per similarity, with the read-out of bbq_vectors_exact_stats saying which sweep ran.  A failure names seed, step, the step's line (call_walk.describe), the
 options in force and what is in flight: the listing up to there replays it as a fixed sequence.  A BBQ_ERR_HIP from any call ends the
 whole pytest session and closes no handle (test_gpu_mutation_walk.located).
 
 Statistics are checked where include/bbq.h defines them as "of the last call": after bbq_search_batch, bbq_search_filtered_batch and
 bbq_search_raw_batch dense_fallbacks is the number of queries on the dense path - every query under force_dense or k > 4096
 (dense_search_one books one each, bbq_dense.cpp), none otherwise: no pool has a NaN score - and host_replays is the number of queries
-under device_select 0 or k > 1024, and 0 where the oracle says every answer's k + 1 best scores are pairwise different.  `candidates` is
+under device_select 0 or k > 1024, and 0 where the oracle says every answer's k + 1 best scores are pairwise different and the plan's
+last segment lists no more than the last finalize launch selects from (Play.selection_fits: 1024 answers of one query on `long`, off its
+chains, are two segments, and the second lists a fifth of 258 048 rows).  `candidates` is
 not asserted: it sums the lengths of the device's candidate lists, which follow from thresholds that the finalize launches of one
 sub-batch derive in stream order - deterministic for one call as far as the code shows - but under sweep_share the lists also hold what
 a shared sweep's survivor queues let through, and a query that overflowed there is swept again alone: nothing in include/bbq.h pins
@@ -31,7 +36,9 @@ import numpy as np
 import pytest
 
 import call_walk as W
+import exact_model as EM
 import orclib as O
+import quant_hostile as QH
 import maxsim_model as MM
 import maxsim_rerank_model as MR
 import test_groups_cpu as GC
@@ -41,6 +48,7 @@ import test_gpu_grouped as GG
 import test_gpu_maxsim as GM
 import test_gpu_maxsim_groups as GMG
 import test_gpu_range as GR
+import test_gpu_device_queries as DQ
 from bbqlib import bbq_amd as B, capi
 from test_gpu_append import Oracle, canon32, canon64, check_export, make_index
 from test_gpu_mutation_walk import located, refused
@@ -104,7 +112,13 @@ class Source:
                 arr.setflags(write=False)
         for arr in (self.codes, self.corr, self.qq, self.qc, self.raw):
             arr.setflags(write=False)
-        self._true = {}
+        self._true, self._exact = {}, {}
+
+    def exact(self, sim):
+        """exact_model.scores of every pool query and every row, f64 [pool, n]: computed once per similarity"""
+        if sim not in self._exact:
+            self._exact[sim] = EM.scores(self.raw, self.base, sim)
+        return self._exact[sim]
 
     def true(self, p, rows, true_sim):
         """computeSimilarity of raw pool query p and the fp32 rows `rows`, f64, from the oracle; every pair computed once"""
@@ -150,7 +164,7 @@ class Live:
         self.options, self.inflight = {}, []
         self.ix = self.dv = None
         self.filters, self.groups, self.masks = {}, {}, {}
-        self._scores, self._heaps = {}, {}
+        self._scores, self._heaps, self._exact_heaps = {}, {}, {}
         self.create()
 
     @property
@@ -213,6 +227,13 @@ class Live:
             self._heaps[(p, k)] = O.heap_topk(self.s32(p), k)
         return self._heaps[(p, k)]
 
+    def exact_topk(self, p, sim, k, which):
+        """exact_model.topk of pool query p over the rows the member's filter `which` accepts (None: all): (rows, score bits)"""
+        key = (int(p), sim, k, which)
+        if key not in self._exact_heaps:
+            self._exact_heaps[key] = EM.topk(self.src_of.exact(sim)[p], k, self.masks[which] if which else None)
+        return self._exact_heaps[key]
+
     def grew(self, rows):
         self.rows = np.concatenate([self.rows, rows])
         self._scores, self._heaps = {}, {}
@@ -240,7 +261,10 @@ class Play:
         self.live = {name: Live(name, tmp) for name in (members or W.CAST)}
         self.transitions = set()
         self.stats_are_mine = True     # no other thread calls the indexes of this walk
-        self.stat_checks = {"dense": 0, "all replayed": 0, "all proven": 0, "ties: replays not pinned": 0}
+        self.stat_checks = {"dense": 0, "all replayed": 0, "all proven": 0, "ties: replays not pinned": 0, "a last segment beyond the selection: replays not pinned": 0}
+        self.raw_answers = {}          # (member, its rows, the step's line) -> the bytes a raw call returned: an option changes none of them
+        self.exact_readouts = []       # printed, not bounded: tests/test_gpu_exact_prefilter.py owns the bounds on the survivors
+        self.quantized = {"equal to the host": 0, "refused as the host refuses": 0}
 
     def close(self):
         for lv in self.live.values():
@@ -254,6 +278,19 @@ class Play:
                                                                                         lv.options or "defaults", flight or "nothing")
 
     # ------------------------------------------------------------------------------------------------ searches
+    def selection_fits(self, lv, nq, k, s32):
+        """the last finalize launch selects an answer only from a last segment whose list fits its key buffer beside the k + 1 running
+        keys ("m_new <= (uint32_t)kFinalizeKeyCap - tcount", bbq_kernels.hip); a longer list is replayed on the host.  From the oracle:
+        the plan of an unfiltered call (call_walk.plan_segments; "p.growth = latency ? ix->opt_latency_growth : ix->opt_growth;"), the
+        threshold the segments in front leave - their k + 1 best score - and the rows of the last segment at or above it"""
+        n, keff = len(s32), min(k, len(s32))
+        growth = lv.opt("latency_growth") if nq <= lv.opt("latency_queries") else lv.opt("segment_growth")
+        first = W.plan_segments(n, k, lv.opt("first_segment_rows"), growth)[-1][0]
+        if first == 0:
+            return True
+        theta = np.sort(s32[:first])[::-1][keff]
+        return int((s32[first:] >= theta).sum()) <= W.K_LAT_PRE_KEYS - (keff + 1)
+
     def check_stats(self, lv, nq, k, scores_of_queries):
         """candidates is left alone (the module's docstring says why)"""
         if not self.stats_are_mine:
@@ -269,6 +306,9 @@ class Play:
         if keff > W.K_FINAL_SELECT_MAX or not lv.opt("device_select"):
             assert st["host_replays"] == nq, "the host replays every query: %s" % st
             self.stat_checks["all replayed"] += 1
+        elif n_eff == lv.n and not all(self.selection_fits(lv, nq, k, s) for s in scores_of_queries):
+            assert 0 <= st["host_replays"] <= nq, st
+            self.stat_checks["a last segment beyond the selection: replays not pinned"] += 1
         elif all(provable(s, keff) for s in scores_of_queries):
             assert st["host_replays"] == 0, "every answer's k + 1 best scores are pairwise different: %s" % st
             self.stat_checks["all proven"] += 1
@@ -316,6 +356,59 @@ class Play:
             np.testing.assert_array_equal(idx[qi, :cnt[qi]], wi, err_msg="%s q%d" % (msg, qi))
             np.testing.assert_array_equal(canon32(sc[qi, :cnt[qi]]), canon32(ws), err_msg="%s q%d" % (msg, qi))
         self.check_stats(lv, len(pqs), k, [lv.s32(p) for p in pqs])
+        # the same call on the same rows, whatever was set in between (device_queries in its option block and in the chain's transition):
+        # every returned array byte for byte
+        key, now = (lv.name, lv.n, W.describe(s)), tuple(a.tobytes() for a in (idx, sc, cnt, qq, qc))
+        assert self.raw_answers.setdefault(key, now) == now, msg + ": the bytes of the same raw call under the options before differ"
+
+    def quantize_queries(self, lv, s, msg):
+        src = lv.src_of
+        q = np.array(src.raw[W.queries_of(s, lv.m.pool)], np.float32)
+        if s["hostile"] == W.NONFINITE:
+            q = W.nonfinite_queries(q)
+        elif s["hostile"]:
+            q[0::2] = QH.batch(s["hostile"], W.HOSTILE_N, lv.m.dim)[:len(q)][0::2]
+        args = (q, src.cen, s["sim"], s["qb"], LAM, ITERS)
+        want, got = DQ._call(None, *args), DQ._call(lv.ix, *args)
+        if got[0] == capi.ERR_HIP:
+            raise B.BBQError(got[0], got[2])
+        assert got[:3] == want[:3], "%s: (code, bad_query, message) %r, the host call's %r" % (msg, got[:3], want[:3])
+        if s["hostile"] == W.NONFINITE:
+            assert want[0] in (capi.ERR_NAN_INPUT, capi.ERR_INF_INPUT) and want[1] == len(q) // 2, "%s: %r" % (msg, want[:3])
+        if want[0] != capi.OK:
+            self.quantized["refused as the host refuses"] += 1
+            return
+        np.testing.assert_array_equal(got[3], want[3], err_msg=msg + ": qquant")
+        np.testing.assert_array_equal(canon64(got[4]), canon64(want[4]), err_msg=msg + ": qcorr")
+        for r in sorted({0, len(q) - 1}):
+            oq, oc = O.quantize_query(q[r], src.cen, s["sim"], s["qb"], LAM, ITERS)
+            np.testing.assert_array_equal(got[3][r], oq, err_msg="%s: the oracle's qquant, query %d" % (msg, r))
+            np.testing.assert_array_equal(canon64(got[4][r]), canon64(oc), err_msg="%s: the oracle's qcorr, query %d" % (msg, r))
+        self.quantized["equal to the host"] += 1
+
+    def exact_search(self, lv, s, msg):
+        src, k, sim, which = lv.src_of, s["k"], s["sim"], s["filter"]
+        pqs = W.queries_of(s, lv.m.pool)
+        lv.dv.set_option("exact_prefilter", s["prefilter"])
+        lv.dv.set_option("exact_slab_rows", s["slab"])
+        flt = lv.filters[which] if which else None
+        accepted = int(lv.masks[which].sum()) if which else lv.n
+        if W.exact_refused(k, accepted):
+            refused(lambda: lv.dv.search_batch(src.raw[pqs], k, sim, flt), capi.ERR_UNSUPPORTED, msg)
+            assert not any(lv.dv.exact_stats().values()), msg
+            return
+        want = [lv.exact_topk(p, sim, k, which) for p in pqs]      # the model holds on the CPU (exact_model.topk asserts it) before the device runs
+        idx, out, cnt = lv.dv.search_batch(src.raw[pqs], k, sim, flt)
+        st = lv.dv.exact_stats()
+        for qi, (rows, bits) in enumerate(want):
+            assert cnt[qi] == len(rows) == min(k, accepted), "%s q%d: count %d" % (msg, qi, cnt[qi])
+            np.testing.assert_array_equal(idx[qi, :cnt[qi]], rows, err_msg="%s q%d: rows" % (msg, qi))
+            np.testing.assert_array_equal(EM.canon64(out[qi, :cnt[qi]]), bits, err_msg="%s q%d: score bits" % (msg, qi))
+        if s["prefilter"] == 1 and sim != W.EUCLIDEAN:
+            assert st["prefilter_pairs"] > 0, "%s: the prefilter did not run: %s" % (msg, st)
+            self.exact_readouts.append((len(pqs), k, accepted, s["slab"], st["f64_pairs"], st["f64_pairs_max_query"], st["fallbacks"]))
+        else:
+            assert st["prefilter_pairs"] == 0 and st["fallbacks"] == 0, "%s: the f64 sweep alone was asked for: %s" % (msg, st)
 
     def range(self, lv, s, msg):
         pqs, src = W.queries_of(s, lv.m.pool), lv.src_of
@@ -514,6 +607,9 @@ class Play:
         elif what == "append_with_unwaited_batch":
             assert lv.inflight
             call = lambda: lv.ix.append_rows(src.codes[:5], src.corr[:5])
+        elif what == "quantize_on_a_shard":
+            assert lv.m.pilot or lv.rows[0] != 0
+            call = lambda: lv.ix.quantize_queries(src.raw[p:p + 1], src.cen, src.sim)
         else:
             raise ValueError(what)
         refused(call, code, msg)
@@ -524,7 +620,8 @@ class Play:
         s, msg = self.steps[i], self.msg(i)
         lv, kind = self.live[s["member"]], s["kind"]
         if kind in ("search", "search_batch", "search_filtered_batch", "search_raw_batch", "range", "search_spans", "search_spans_filtered", "search_grouped",
-                      "search_maxsim", "maxsim_groups", "rerank", "maxsim_rerank", "score_rows", "score_ords", "search_ords"):
+                      "search_maxsim", "maxsim_groups", "rerank", "maxsim_rerank", "score_rows", "score_ords", "search_ords", "quantize_queries",
+                      "exact_search"):
             getattr(self, kind)(lv, s, msg)
         elif kind == "shard_scan":
             assert not lv.inflight, msg         # begin + wait, and waits are taken in begin order: the walk draws it on an idle member
@@ -599,6 +696,8 @@ def test_walk_of_mixed_calls_equals_the_oracle(seed, tmp_path):
     played(play)
     print("call walk seed %d: %d steps, %d distinct transitions between kinds, %.2f s (the oracle's pools: %.2f s before it); statistics held: %s"
           % (seed, len(play.steps), len(play.transitions), time.perf_counter() - t1, t1 - t0, play.stat_checks))
+    print("call walk seed %d: device quantizations %s; exact searches behind the prefilter (queries, k, accepted rows, slab rows, f64 pairs, most of a "
+          "query, fallbacks): %s" % (seed, play.quantized, play.exact_readouts))
 
 
 # ---------------------------------------------------------------------------------------------------- threads

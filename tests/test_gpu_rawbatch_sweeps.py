@@ -9,9 +9,16 @@ has no sweep of its own to fall back to and is counted in dense_fallbacks: dense
 dense prefix and the matrix-core sweep's lists.  tests/test_rawbatch_cells_cpu.py holds the inputs to the conditions under which a wrong
 dot product recovered from an accumulator shows in an answer.
 
+Option device_queries 1 takes the feed away: the queries are quantized on the device first and the call goes on as bbq_search_batch on
+their bytes (bbq_search_raw_batch, csrc/bbq_core.cpp), so planes and maxq follow from the values and every cell of at most four bits
+runs S = 1/4.  include/bbq.h promises "never a different answer, error or bad_query": the second half of this file runs every compact
+cell, the two-sub-batch cells and the hostile cells under both values - the cell's own quantized queries, the oracle's answers, and every
+returned array byte for byte between the two values - and holds code, bad_query and bbq_last_error of refused batches to each other.
+
 A BBQ_ERR_HIP from any call ends the whole pytest session (test_gpu_mutation_walk.located): nothing more is started on a device that has
 failed, not even the close of the handle."""
 import contextlib
+import ctypes
 
 import numpy as np
 import pytest
@@ -20,7 +27,7 @@ import orclib as O
 import rawbatch_cells as C
 import test_gpu_mutation_walk as MW
 from test_gpu_score_ords import canon32
-from bbqlib import bbq_amd as B
+from bbqlib import bbq_amd as B, capi
 
 pytestmark = pytest.mark.gpu
 
@@ -154,3 +161,157 @@ def test_raw_call_k_edges_and_refused_query():
             raise e.value
         assert e.value.code == B.capi.ERR_NAN_INPUT
         _assert_answers(_raw(ix, cell), c.want, msg + " after the refused call")
+
+
+# ---------------------------------------------------------------------------------------------------- option device_queries
+COMPACT = [c for c, layout in MAIN if layout == "compact"]
+
+
+def _both_values(ix, cell, msg, want, k=C.K):
+    """the 70-query raw call under device_queries 1 - the cell's quantized queries and corrections bit for bit, `want`, no dense fallback -
+    and then under 0 on the same handle: every returned array byte for byte"""
+    c = C.case(cell)
+    ix.set_option("device_queries", 1)
+    on = _raw(ix, cell, k=k, want_quantized=True)
+    np.testing.assert_array_equal(on[3], c.qq, err_msg=msg + ": the quantized queries")
+    np.testing.assert_array_equal(on[4].view(np.uint64), c.qc.view(np.uint64), err_msg=msg + ": the query corrections")
+    _assert_answers(on, want, msg + " device_queries 1")
+    fallbacks = ix.stats()["dense_fallbacks"]
+    ix.set_option("device_queries", 0)
+    off = _raw(ix, cell, k=k, want_quantized=True)
+    _assert_answers(off, want, msg + " device_queries 0")
+    for name, a, b in zip(("idx", "score", "count", "qquant", "qcorr"), on, off):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), "%s: %s differs between device_queries 1 and 0" % (msg, name)
+    return fallbacks
+
+
+@pytest.mark.parametrize("cell", COMPACT, ids=C.cell_id)
+def test_raw_call_device_queries_on_every_compact_cell(cell):
+    """one sub-batch of 70, flood_rows 0: without a feed the call sweeps the form bbq_search_batch runs on these bytes, and answers as the
+    feed's form does"""
+    msg = "device_queries %s %s" % (C.cell_id(cell), C.form_w(cell))
+    with _open(cell, "compact", msg, flood_rows=0, batch_queries=128) as ix:
+        assert _both_values(ix, cell, msg, C.case(cell).want) == 0, msg + ": dense_fallbacks under device_queries 1"
+
+
+@pytest.mark.parametrize("cell", SECOND_SUBBATCH, ids=C.cell_id)
+def test_raw_call_device_queries_second_subbatch(cell):
+    """batch_queries 64: the second sub-batch's queries were all quantized before the first was enqueued"""
+    msg = "device_queries, two sub-batches %s %s" % (C.cell_id(cell), C.form_w(cell))
+    with _open(cell, "compact", msg, flood_rows=0, batch_queries=64) as ix:
+        assert _both_values(ix, cell, msg, C.case(cell).want) == 0, msg + ": dense_fallbacks under device_queries 1"
+
+
+@pytest.mark.parametrize("cell", C.HOSTILE_CELLS, ids=C.cell_id)
+def test_raw_call_device_queries_hostile_rows(cell):
+    """rows no threshold can bound (default flood_rows: a query may fall back): both values, K and K_DEEP, the oracle's answers"""
+    h = C.hostile(cell)
+    msg = "device_queries, hostile %s %s" % (C.cell_id(cell), C.form_w(cell))
+    with _open(cell, "compact", msg, corr=h.corr) as ix:
+        for k, want in ((C.K, h.want), (C.K_DEEP, h.deep)):
+            _both_values(ix, cell, "%s k = %d" % (msg, k), want, k=k)
+
+
+def _raw_call(ix, queries, cen, sim, query_bits, k):
+    """bbq_search_raw_batch itself: (code, bad_query, bbq_last_error's text, idx, score, count bytes)"""
+    q, cen = np.ascontiguousarray(queries, np.float32), np.ascontiguousarray(cen, np.float32)
+    nq, kk = q.shape[0], max(int(k), 0)
+    idx, sc, cnt, bad = np.zeros((nq, kk), np.int32), np.zeros((nq, kk), np.float32), np.zeros(nq, np.int64), ctypes.c_int32(-9)
+    L = capi.lib()
+    rc = L.bbq_search_raw_batch(ix._h, nq, q.ctypes.data, cen.ctypes.data, sim, query_bits, 0.1, 5, 3, k, idx.ctypes.data, sc.ctypes.data, cnt.ctypes.data,
+                                None, None, ctypes.byref(bad))
+    text = L.bbq_last_error().decode("utf-8") if rc else ""
+    if rc == capi.ERR_HIP:
+        raise B.BBQError(rc, text)
+    return rc, bad.value, text, idx.tobytes(), sc.tobytes(), cnt.tobytes()
+
+
+def _bad_batches(good, n):
+    """(name, queries, the lowest bad query or None): with 70 queries and batch_queries 64 both bad queries lie in the second sub-batch"""
+    lo, hi = (66, 68) if n == 70 else (2, 5)
+    nan, inf, both, zero = (good[:n].copy() for _ in range(4))
+    nan[lo, 5] = np.nan
+    inf[hi, 7] = np.inf
+    both[lo, 4], both[hi, 7] = np.inf, np.nan
+    zero[lo] = 0.0
+    return ("NaN", nan, lo), ("Infinity", inf, hi), ("Infinity below NaN", both, lo), ("a zero query", zero, None)
+
+
+@pytest.mark.parametrize("sim", [0, 1, 2])
+def test_raw_call_errors_are_the_same_under_device_queries(sim):
+    """200 rows x 13-d, batch_queries 64, 8 and 70 raw queries: a NaN, an Infinity, both (the lower one in the second sub-batch), a zero
+    query - k 10 (the feed beside the sweeps for 70), k 0 (quantize first), k 5000 (beyond the rows), and k 10 under force_dense (the
+    dense path, which waits on the feed query by query): code, bad_query and message of device_queries 0 and 1 are equal, the lowest
+    bad query is named, and the next raw call on the handle answers as before"""
+    rng = np.random.default_rng(9300 + sim)
+    base, good = rng.standard_normal((200, 13)).astype(np.float32), rng.standard_normal((70, 13)).astype(np.float32)
+    codes, corr, cen = B.quantize_vectors(base, sim, 1)
+    ix = B.Index(codes, corr, 13, B.centroid_dp(cen))
+    msg = "error parity, sim %d" % sim
+    try:
+        with MW.located(msg):
+            ix.set_option("batch_queries", 64)
+            for dense in (0, 1):
+                ix.set_option("force_dense", dense)
+                for n in (8, 70):
+                    before = {}
+                    for value in (0, 1):
+                        ix.set_option("device_queries", value)
+                        before[value] = _raw_call(ix, good[:n], cen, sim, 4, 10)
+                        assert before[value][:2] == (capi.OK, -1), msg
+                    assert before[0] == before[1], "%s: %d good queries answer differently" % (msg, n)
+                    for k in ((10,) if dense else (10, 0, 5000)):
+                        for name, q, lowest in _bad_batches(good, n):
+                            w = "%s, force_dense %d, %d queries, k %d, %s" % (msg, dense, n, k, name)
+                            got = {}
+                            for value in (0, 1):
+                                ix.set_option("device_queries", value)
+                                got[value] = _raw_call(ix, q, cen, sim, 4, k)
+                                if got[value][0] != capi.OK:      # a refused call leaves nothing behind
+                                    assert _raw_call(ix, good[:n], cen, sim, 4, 10) == before[value], "%s: the raw call after the refused one, device_queries %d" % (w, value)
+                            print("%s: %r" % (w, got[1][:3]))
+                            assert got[0][:2] == got[1][:2], "%s: (code, bad_query) %r under device_queries 0, %r under 1" % (w, got[0][:2], got[1][:2])
+                            assert got[0][2] == got[1][2], "%s: bbq_last_error %r under device_queries 0, %r under 1" % (w, got[0][2], got[1][2])
+                            if lowest is None:
+                                assert got[1][0] == capi.OK and got[0] == got[1], w + ": a zero query is no error, and the answers are the same"
+                            else:
+                                assert got[1][0] in (capi.ERR_NAN_INPUT, capi.ERR_INF_INPUT) and got[1][1] == lowest, "%s: %r" % (w, got[1][:3])
+    except pytest.exit.Exception:
+        ix._h = None
+        raise
+    ix.close()
+
+
+@pytest.mark.parametrize("dim", [15680, 15681], ids=["the widest device query", "one dimension more: host threads"])
+def test_raw_call_at_the_limit_of_the_device_quantizer(dim):
+    """one row; 3 and 70 raw queries: under device_queries 1 an index of 15681 dimensions quietly quantizes on host threads
+    (device_queries_for_call, csrc/bbq_query_device.cpp), one of 15680 on the device - the bytes are bbq_quantize_queries' and those of
+    the call under 0 either way"""
+    rng = np.random.default_rng(9400)
+    queries, cen = rng.standard_normal((70, dim)).astype(np.float32), rng.standard_normal(dim).astype(np.float32)
+    row = rng.integers(0, 256, (1, (dim + 7) // 8), dtype=np.uint8)
+    row[0, -1] &= 0xff << (8 * ((dim + 7) // 8) - dim) & 0xff      # the padding bits of the last byte stay zero
+    ix = B.Index(row, np.array([[-0.1, 0.1, 0.5, float(np.unpackbits(row).sum())]]), dim, 0.25)
+    hq, hc = B.quantize_queries(queries, cen, 1, 4)
+    msg = "%d dimensions" % dim
+    try:
+        with MW.located(msg):
+            for nq in (3, 70):
+                res = {}
+                for value in (0, 1):
+                    ix.set_option("device_queries", value)
+                    res[value] = ix.search_raw_batch(queries[:nq], cen, 1, 4, 10, want_quantized=True)
+                    assert (res[value][2] == 1).all() and (res[value][0][:, 0] == 0).all(), msg
+                    np.testing.assert_array_equal(res[value][3], hq[:nq], err_msg="%s, device_queries %d: qquant" % (msg, value))
+                    np.testing.assert_array_equal(res[value][4].view(np.uint64), hc[:nq].view(np.uint64), err_msg="%s, device_queries %d: qcorr" % (msg, value))
+                assert all(a.tobytes() == b.tobytes() for a, b in zip(res[0], res[1])), "%s, %d queries" % (msg, nq)
+            if dim > 15680:      # the quantizer itself refuses the handle that the option quietly passes by
+                with pytest.raises(B.BBQError) as e:
+                    ix.quantize_queries(queries[:2], cen, 1)
+                if e.value.code == capi.ERR_HIP:
+                    raise e.value
+                assert e.value.code == capi.ERR_UNSUPPORTED
+    except pytest.exit.Exception:
+        ix._h = None
+        raise
+    ix.close()
