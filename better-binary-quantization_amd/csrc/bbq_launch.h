@@ -1,6 +1,6 @@
 // bbq_launch.h - host-callable launch wrappers of every kernel file: the sweeps, finalize and pack (bbq_kernels.hip, bbq_filter_kernels.hip,
 // bbq_mfma_kernels.hip, bbq_latency_kernels.hip), the index build (bbq_build_kernels.hip), the rerank (bbq_rerank_kernels.hip), the scoring of chosen rows (bbq_gather_kernels.hip)
-// the range search (bbq_range_kernels.hip), the span search (bbq_span_kernels.hip), the grouped search (bbq_group_kernels.hip), the MaxSim
+// the range search (bbq_range_kernels.hip, bbq_range_mfma_kernels.hip), the span search (bbq_span_kernels.hip), the grouped search (bbq_group_kernels.hip), the MaxSim
 // search (bbq_maxsim_kernels.hip), MaxSim over chosen groups (bbq_maxsim_cand_kernels.hip), the exact MaxSim rerank (bbq_maxsim_rerank_kernels.hip) and the
 // exact search (bbq_exact_kernels.hip), the query quantizer (bbq_query_kernels.hip)
 #pragma once
@@ -25,6 +25,7 @@ hipError_t launch_scan_shared(const ScanArgs &a, int planes, int share, int n_qu
 // query's interval width positive and finite
 bool mfma_sweep_supported(const ScanArgs &a);
 int64_t mfma_query_bytes_per_group(int w16, bool fp);  // staged operand bytes of 32 queries
+int mfma_queue_cap(int groups_per_block);  // survivors a wave's queue holds per tile and group (1 or 2 groups per workgroup)
 int mfma_queries_per_tile_load(const ScanArgs &a, int n_queries, bool fp);  // 32, or 64 where a workgroup serves two groups per tile
 hipError_t launch_scan_mfma(const ScanArgs &a, const uint8_t *qbytes, const float *qmax, float fp_scale, int n_queries, int n_chunks, hipStream_t s);
 // ... of a filtered search: accept as launch_scan_filtered takes it.  Tiles without an accepted row are not loaded, a rejected row is
@@ -96,6 +97,14 @@ hipError_t launch_range_theta(Threshold *theta, const uint32_t *keys, const Quer
 // counts[q][chunk] = rows of the chunk that a.accept takes and whose score key beats theta[q], for the n_queries queries from a.q_first on
 // (n_queries <= 65535); planes as launch_scan takes them
 hipError_t launch_range_count(const RangeArgs &a, int planes, int n_queries, hipStream_t s);
+// the same counts on the matrix cores, 32 or 64 queries per tile load (bbq_range_mfma_kernels.hip; sweep_share 32): for a 1-bit index of
+// a compiled width (range_mfma_supported) and the first n_queries queries of the sub-batch (a.q_first 0), staged once more as
+// matrix-core operands (qbytes, qmax, fp_scale as launch_scan_mfma takes them).  The caller has cleared a.counts and set recount[q] for
+// every query without a positive finite interval width; the kernel counts the others and sets recount[q] for those it cannot count (a
+// key below every score, a full survivor queue): a query with recount[q] set has garbage counts, which launch_range_count overwrites
+bool range_mfma_supported(const TileGeom &g);
+int range_mfma_queries_per_tile_load(const TileGeom &g, int n_queries, bool fp);  // 32, or 64 where a workgroup serves two groups per tile
+hipError_t launch_range_count_mfma(const RangeArgs &a, const uint8_t *qbytes, const float *qmax, float fp_scale, uint32_t *recount, int n_queries, hipStream_t s);
 // per query: counts -> their exclusive prefix IN PLACE, totals[q] = their sum, nonempty[q][0 .. n_nonempty[q]) = the chunks with a count, ascending
 hipError_t launch_range_offsets(uint32_t *counts, uint32_t *nonempty, uint32_t *totals, uint32_t *n_nonempty, int n_chunks, int n_queries, hipStream_t s);
 // the passing rows of the n_queries queries from a.q_first on, as entries at a.out[a.base[q] + ...], ascending by row; max_nonempty = the

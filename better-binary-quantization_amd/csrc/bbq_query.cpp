@@ -270,7 +270,9 @@ static void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch
     }
 }
 
-// second copy of a sub-batch's queries as MFMA operands in fragment order + per-group maxima for the rows' magnitude budget
+// second copy of a sub-batch's queries as MFMA operands in fragment order + per-group maxima for the rows' magnitude budget.
+// A query the matrix cores cannot take (!mfma_query_ok: the range search keeps such queries in the sub-batch and counts them on their
+// own; a search stages none) leaves its operand bytes zero and does not enter its group's maxima
 MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryParams *hq, int64_t q_first, int nq, size_t bytes) {
   const bbq_index *ix = c.ix;
   MfmaStage m{};
@@ -285,6 +287,7 @@ MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryPa
   float *qm = reinterpret_cast<float *>(h_qbuf + m.off_qmax);
   for (int i = 0; i < 4 * groups; ++i) qm[i] = 0.f;
   for (int i = 0; i < nq; ++i) {
+    if (!mfma_query_ok(hq[i])) continue;
     const uint8_t *qv = c.qquant + (size_t)(q_first + i) * ix->geom.dim;
     if (m.fp) fill_query_mfma_fp(ix, h_qbuf + m.off_qbytes, i, qv, m.scale8);
     else fill_query_mfma(ix, h_qbuf + m.off_qbytes, i, qv);

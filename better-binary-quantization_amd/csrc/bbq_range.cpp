@@ -1,6 +1,6 @@
 // bbq_range.cpp - range search: bbq_range_key, bbq_count_range_batch, bbq_search_range_batch (kernels: bbq_range_kernels.hip).  The
 // host turns every threshold into a key, checks everything before the first launch and works through the call in sub-batches: stage
-// the queries, launch theta, count and offsets, bring back each query's total and the length of its list of non-empty chunks - where
+// the queries, launch theta, count (per query, or with sweep_share 32 shared on the matrix cores) and offsets, bring back each query's total and the length of its list of non-empty chunks - where
 // the count entry point stops - then fill in launches of bounded size and unpack their entries into the caller's arrays.
 #include <string.h>
 #include "bbq_search.h"
@@ -17,23 +17,31 @@ namespace {
 constexpr int kRangeMaxQueries = 1024;
 constexpr int64_t kRangeChunkBytes = 64ll << 20;
 constexpr int64_t kRangeMaxEntries = 1 << 20;
+// sweep_share 32: calls of fewer queries than this keep the per-query count.  Measured at 1 M x 768 (profiles/range_search_shared.json):
+// the shared count takes 0.11 - 0.12 ms whatever the call holds up to 8 queries, the per-query count 0.05 ms for one query and 0.14 ms
+// for eight - a call of one query loses on every leg (2.3 x), a call of eight wins without a filter and under a 50 % filter
+// (1.1 - 1.24 x) and loses under a 1 % filter (0.77 x); 32 queries and more win on every selective leg
+constexpr int kRangeSharedMinQueries = 8;
 
-// where a sub-batch of nq queries keeps what in the scratch: [query data | query uniforms | keys] come from the host in one copy,
-// [totals | list lengths] go back in one
+// where a sub-batch of nq queries keeps what in the scratch: [query data | query uniforms | keys | matrix-core operands and group
+// maxima, where the count runs there] come from the host in one copy, [totals | list lengths] go back in one
 struct Layout {
-  size_t qdata, qparams, keys, head_bytes, theta, base, totals, n_nonempty, counts, nonempty, bytes;
-  Layout(size_t nq, size_t qb, size_t n_chunks) {
+  size_t qdata, qparams, keys, plain_bytes, head_bytes, theta, base, totals, n_nonempty, counts, nonempty, recount, bytes;
+  // mfma_group_bytes: what stage_queries_mfma puts behind the plain head per group of 32 queries (0: the count runs per query)
+  Layout(size_t nq, size_t qb, size_t n_chunks, size_t mfma_group_bytes) {
     qdata = 0;
     qparams = qdata + nq * qb;
     keys = qparams + nq * sizeof(QueryParams);
-    head_bytes = keys + nq * 4;
+    plain_bytes = keys + nq * 4;
+    head_bytes = mfma_group_bytes ? align16(plain_bytes) + (nq + 31) / 32 * mfma_group_bytes : plain_bytes;
     theta = align16(head_bytes);
     base = align16(theta + nq * sizeof(Threshold));
     totals = align16(base + nq * 8);
     n_nonempty = totals + nq * 4;
     counts = align16(n_nonempty + nq * 4);
     nonempty = counts + nq * n_chunks * 4;
-    bytes = nonempty + nq * n_chunks * 4;
+    recount = nonempty + nq * n_chunks * 4;  // [nq] the matrix-core count's flags
+    bytes = recount + nq * 4;
   }
 };
 
@@ -61,21 +69,43 @@ struct RangeRun {
   size_t qb;
   int64_t n_chunks;
   RangeArgs a{};
+  // the count pass on the matrix cores (sweep_share 32): decided for the call - the index qualifies and no query value is above 127
+  bool mfma = false;
+  int maxq = 255;
+  size_t mfma_group_bytes = 0;   // Layout's
+  Event ev0, ev1;                // around a matrix-core count launch, for the stats
+  std::vector<uint32_t> flags;   // [nq] the recount flags of the sub-batch, as staged and as they come back
   std::vector<uint8_t> head;
   int64_t *d_base = nullptr;   // RangeArgs::base of the sub-batch counted last, for the host to fill
   std::vector<uint32_t> back;  // [totals | list lengths] of the sub-batch counted last
 
   // queries [q0, q0 + nq) counted: the device holds their offsets and lists, `back` their totals and list lengths
   int count(int64_t q0, int nq) {
-    const Layout lo((size_t)nq, qb, (size_t)n_chunks);
+    const Layout lo((size_t)nq, qb, (size_t)n_chunks, mfma_group_bytes);
     uint8_t *d = ix->ctx->d_range;
     hipStream_t st = ix->ctx->aux_stream;
     head.resize(lo.head_bytes);
+    const QueryParams *hq = reinterpret_cast<const QueryParams *>(head.data() + lo.qparams);
     for (int s = 0; s < nq; ++s)
       fill_query(ix, head.data() + lo.qdata + (size_t)s * qb, reinterpret_cast<QueryParams *>(head.data() + lo.qparams) + s,
                  qquant + (size_t)(q0 + s) * ix->geom.dim, qcorr + (size_t)(q0 + s) * 4, planes, one_bit, sim);
     memcpy(head.data() + lo.keys, keys + q0, (size_t)nq * 4);
-    HIPCHK(hipMemcpyAsync(d, head.data(), lo.head_bytes, hipMemcpyHostToDevice, st));
+    // the matrix cores count the sub-batch if they can take one of its queries; the others are flagged for the per-query recount below
+    bool on_mfma = false;
+    MfmaStage ms{};
+    if (mfma) {
+      flags.assign((size_t)nq, 0u);
+      for (int s = 0; s < nq; ++s) {
+        flags[(size_t)s] = mfma_query_ok(hq[s]) ? 0u : 1u;
+        on_mfma = on_mfma || flags[(size_t)s] == 0u;
+      }
+    }
+    if (on_mfma) {  // (a SearchCall for the staging alone: the index, the queries, sim and the call's largest query value)
+      SearchCall c(ix, qquant, qcorr, planes, one_bit ? 1 : 4, sim, 0);
+      c.maxq = maxq;
+      ms = stage_queries_mfma(c, head.data(), hq, q0, nq, lo.plain_bytes);
+    }
+    HIPCHK(hipMemcpyAsync(d, head.data(), on_mfma ? ms.bytes : lo.plain_bytes, hipMemcpyHostToDevice, st));
     a.qplanes = reinterpret_cast<const uint4 *>(d + lo.qdata);
     a.qparams = reinterpret_cast<const QueryParams *>(d + lo.qparams);
     a.theta = reinterpret_cast<const Threshold *>(d + lo.theta);
@@ -87,7 +117,39 @@ struct RangeRun {
     d_base = reinterpret_cast<int64_t *>(d + lo.base);
     a.base = d_base;
     HIPCHK(launch_range_theta(reinterpret_cast<Threshold *>(d + lo.theta), reinterpret_cast<const uint32_t *>(d + lo.keys), a.qparams, nq, st));
-    HIPCHK(launch_range_count(a, planes, nq, st));
+    if (on_mfma) {
+      uint32_t *d_recount = reinterpret_cast<uint32_t *>(d + lo.recount);
+      HIPCHK(hipMemcpyAsync(d_recount, flags.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemsetAsync(a.counts, 0, (size_t)nq * (size_t)n_chunks * 4, st));
+      HIPCHK(hipEventRecord(ev0, st));
+      HIPCHK(launch_range_count_mfma(a, d + ms.off_qbytes, reinterpret_cast<const float *>(d + ms.off_qmax), ms.fp ? ms.scale8 / 8.0f : 0.0f, d_recount, nq, st));
+      HIPCHK(hipEventRecord(ev1, st));
+      HIPCHK(hipMemcpyAsync(flags.data(), d_recount, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      // every maximal run of flagged queries is counted per query: plain stores over every chunk's word of those queries
+      for (int s = 0; s < nq;) {
+        if (flags[(size_t)s] == 0u) { ++s; continue; }
+        int e = s + 1;
+        while (e < nq && flags[(size_t)e] != 0u) ++e;
+        a.q_first = s;
+        HIPCHK(launch_range_count(a, planes, e - s, st));
+        s = e;
+      }
+      a.q_first = 0;
+      // the read-out, as enqueue_subbatch records its dominant launch: rows x queries, and the bytes of a sweep that loads every row -
+      // its codes and its exact corrections - once for the queries of a tile load
+      float ms_count = 0;
+      if (hipEventElapsedTime(&ms_count, ev0, ev1) == hipSuccess) {
+        const TileGeom &g = a.idx.geom;
+        const int64_t rows = a.idx.n_rows, share = range_mfma_queries_per_tile_load(g, nq, ms.fp);
+        const int64_t row_bytes = g.layout == kLayoutCompact ? (int64_t)g.w16 * 16 + 24 : (int64_t)g.tile_stride / kTileRows;
+        ix->stats.last_scan_ms = ms_count;
+        ix->stats.last_scan_rows = rows * nq;
+        ix->stats.last_scan_bytes = rows * ((nq + share - 1) / share) * row_bytes;
+      }
+    } else {
+      HIPCHK(launch_range_count(a, planes, nq, st));
+    }
     HIPCHK(launch_range_offsets(a.counts, reinterpret_cast<uint32_t *>(d + lo.nonempty), reinterpret_cast<uint32_t *>(d + lo.totals),
                                 reinterpret_cast<uint32_t *>(d + lo.n_nonempty), (int)n_chunks, nq, st));
     back.resize((size_t)nq * 2);
@@ -139,7 +201,16 @@ int range_locked(bbq_index *ix, const bbq_filter *f, int32_t n_queries, const ui
   r.a.accept = f ? f->d_bits.get() : nullptr;
   r.a.n_chunks = (int32_t)r.n_chunks;
   const int64_t sub = std::min<int64_t>({(int64_t)n_queries, (int64_t)kRangeMaxQueries, std::max<int64_t>(1, kRangeChunkBytes / (r.n_chunks * 8))});
-  const int rc_scratch = reserve_scratch(ix->ctx->d_range, Layout((size_t)sub, r.qb, (size_t)r.n_chunks).bytes, "range search");
+  if (ix->opt_share == 32 && range_mfma_supported(r.a.idx.geom)) {
+    r.maxq = max_value(qquant, (int64_t)n_queries * ix->geom.dim);
+    r.mfma = r.maxq <= 127 && n_queries >= kRangeSharedMinQueries;
+  }
+  if (r.mfma) {
+    r.mfma_group_bytes = (size_t)mfma_query_bytes_per_group(ix->geom.w16, r.maxq <= 15) + 16;
+    HIPCHK(r.ev0.create());
+    HIPCHK(r.ev1.create());
+  }
+  const int rc_scratch = reserve_scratch(ix->ctx->d_range, Layout((size_t)sub, r.qb, (size_t)r.n_chunks, r.mfma_group_bytes).bytes, "range search");
   if (rc_scratch != BBQ_OK) return rc_scratch;
   const bool one_sub = sub >= n_queries;
   // every query's total first: the count entry point's answer, and what the caller's cap is held against before anything is filled.  A

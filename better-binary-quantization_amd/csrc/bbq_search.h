@@ -104,6 +104,8 @@ int staged_bound_for(const bbq_index *ix);
 // the sub-batch's queries once more as matrix-core operands + group maxima behind the `bytes` already staged in h_qbuf
 struct MfmaStage { bool fp; int scale8; size_t off_qbytes, off_qmax, bytes; };
 MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryParams *hq, int64_t q_first, int nq, size_t bytes);
+// (the range search calls it through a SearchCall of its own that carries the index, the queries, sim and maxq: a query of its
+// sub-batch that is not mfma_query_ok is left out - zero operand bytes, not in the maxima; a search stages no such query)
 bool mfma_query_ok(const QueryParams &p);
 // the f32 images of *pp's score uniforms and whether the f32 bound may use them (QueryParams::fast_bound)
 void fast_bound_images(QueryParams *pp, double x1max, double qcmax, bool enable);

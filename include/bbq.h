@@ -418,7 +418,9 @@ int bbq_staged_bound_words(const uint8_t *qquant, int32_t dim, float lyf, float 
 /* launches of this process that took the sweep's staged twin so far (for tests: no answer shows which kernel a launch took) */
 int64_t bbq_staged_launches(void);
 /* f: NULL = all rows; otherwise a filter of this index (size / device as bbq_search_filtered_batch checks them).
- * thresholds [n_queries].  out_counts [n_queries] = number of rows in each answer. */
+ * thresholds [n_queries].  out_counts [n_queries] = number of rows in each answer.
+ * With sweep_share 32 the count pass of both calls runs shared on the matrix cores (see bbq_set_option) and records its launch in
+ * last_scan_ms / last_scan_rows / last_scan_bytes of bbq_get_stats - the only stats a range call writes; the answers are the same bytes. */
 int bbq_count_range_batch(bbq_index *idx, const bbq_filter *f, int32_t n_queries, const uint8_t *qquant, const double *qcorr,
                           int32_t query_bits, int32_t sim, const float *thresholds, int64_t *out_counts);
 /* out_offsets [n_queries + 1] ascending from 0: query q's answer is out_idx / out_score [out_offsets[q], out_offsets[q+1]),
@@ -940,7 +942,11 @@ int bbq_reset_stats(bbq_index *idx);
  *     the similarity transform.  A pre-filter in front of the exact score either way: never a different answer
  *   replay_threads 1..256 (half the host cores, at most 16)   flood_rows 0..2^24 (262144)   force_dense 0|1 (0)
  *   sweep_share 1|4|8|32 (1: every query sweeps the index itself; 32: shared sweep on the matrix cores, groups of 32 queries, two groups per load of the rows;
- *     32 also serves bbq_search_filtered_batch - tiles without an accepted row are not loaded; 4 and 8 do not: a filtered call sweeps per query under them)
+ *     32 also serves bbq_search_filtered_batch - tiles without an accepted row are not loaded; 4 and 8 do not: a filtered call sweeps per query under them;
+ *     32 also serves the count pass of bbq_count_range_batch / bbq_search_range_batch on 1-bit indexes of the compiled widths (dimension
+ *     up to 128, 641..768, 897..1024, 1409..1536) for query values up to 127: one load of the rows counts for 32 or 64 queries, a query
+ *     the shared count cannot take is counted per query inside the same call, and the answers do not change; a call of fewer than 8
+ *     queries keeps the per-query count, which is faster there (kRangeSharedMinQueries, bbq_range.cpp: measured crossover))
  *   device_queries -1|0|1 (-1): 1 lets bbq_search_raw_batch quantize all its queries on the device (bbq_quantize_queries_device) and then
  *     search them as prepared queries, instead of quantizing them on host threads while the sub-batches in front are on the device; 0 and
  *     -1 - the library's choice - keep host threads, as do a multi-device handle and an index of more than 15680 dimensions under any
