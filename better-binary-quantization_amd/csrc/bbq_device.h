@@ -587,6 +587,8 @@ struct MaxSimAccArgs {
 struct MaxSimScoreArgs {
   GroupScoreArgs g;            // qplanes / qparams / rep: per staged VECTOR of the block; n_queries: the length of `queries`
   const MaxSimQuery *queries;  // a workgroup is one chunk for one of them
+  const uint8_t *qops;         // the matrix-core pass alone (bbq_maxsim_mfma_kernels.hip): per entry of `queries` its block's token vectors as FP6
+                               // operands at scale8 2, fill_query_mfma_fp's layout with token t as query t of the group; a missing token's bytes zero
 };
 
 // MaxSim over chosen groups (bbq_maxsim_cand_kernels.hip): a query scores its own candidate list, groups of a group set in the caller's

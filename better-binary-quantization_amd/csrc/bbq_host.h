@@ -244,7 +244,8 @@ struct bbq_index {
   int opt_group_scratch_mb = 256;  // MiB of scratch a grouped search's sub-batch may take for its representatives, 16 B per live group and
                                    // query (bbq_group.cpp): as many queries per score launch as fit, at least one
   int opt_maxsim_fused = -1;  // the MaxSim search's score pass: 1 the fused kernel wherever it exists, 0 the grouped search's kernel per token
-                              // vector, -1 what was measured faster (bbq_maxsim.cpp).  The answers are the same either way
+                              // vector, -1 what was measured faster (bbq_maxsim.cpp), 2 the matrix-core kernel wherever it exists (elsewhere as 1).
+                              // The answers are the same every way
   int opt_fast_bound = 1;  // 1: the compact layout's score bound in f32 against the threshold's z image wherever the query's f32 images allow it
                            // (fast_bound_images, bbq_query.cpp); 0: always the f64 bound.  The answers are the same either way
   int opt_device_queries = -1;  // bbq_search_raw_batch quantizes its queries on the device (bbq_query_device.cpp) instead of on host threads: 1 wherever

@@ -131,6 +131,11 @@ bool maxsim_fused_exists(const TileGeom &geom, int planes);
 // the fused score pass of one token block: every chunk of a.g.idx for each of a.g.n_queries entries of a.queries -> a.g.rep, which the
 // caller has cleared.  hipErrorInvalidValue where maxsim_fused_exists says no: the caller asks first
 hipError_t launch_maxsim_score(const MaxSimScoreArgs &a, int planes, hipStream_t s);
+// the same pass on the matrix cores (bbq_maxsim_mfma_kernels.hip; maxsim_fused 2): the shapes of maxsim_fused_exists, whose 4 planes say
+// that every token's quantized value is at most 15 - what the FP6 operands hold.  a.qops: mfma_query_bytes_per_group(w16, true) per entry
+// of a.queries.  The same keys in the same places; hipErrorInvalidValue exactly where launch_maxsim_score refuses, and without a.qops
+bool maxsim_mfma_exists(const TileGeom &geom, int planes);
+hipError_t launch_maxsim_mfma(const MaxSimScoreArgs &a, int planes, hipStream_t s);
 // MaxSim over chosen groups (bbq_maxsim_cand_kernels.hip).  The score pass of one token block: for each of the n_queries (<= 65535)
 // entries of a.queries the expanded rows of its candidate list, `longest` (<= kMaxSimCandMaxRows) the most of any of them -> a.rep, which
 // the caller has cleared; planes as launch_scan takes them.  The launch sets a.tok_pass.  launch_maxsim_accumulate follows it

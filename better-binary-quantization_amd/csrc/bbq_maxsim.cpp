@@ -3,7 +3,8 @@
 // (bbq_group.cpp) scores the ordered f64 sum of its representatives' f32 scores.  A call works through sub-batches
 // bounded by scratch, and inside a sub-batch the queries' tokens in blocks of at most kMaxSimTokenBlock - a block's vectors staged in one
 // copy (stage_maxsim_token_block, which MaxSim over chosen groups shares), its keys cleared, the score pass (fused where the option and
-// the shape allow, the grouped search's kernel with the block's vectors as its queries otherwise) and the accumulate pass - then the
+// the shape allow - on the vector ALUs or, maxsim_fused 2, on the matrix cores (bbq_maxsim_mfma_kernels.hip), the block's vectors staged
+// once more as FP6 operands -, the grouped search's kernel with the block's vectors as its queries otherwise) and the accumulate pass - then the
 // select pass over the sums, the answer blocks back in one copy, and the end every select-pass search has (finish_selected,
 // bbq_select.cpp): the device's k proven, the reference's heap replayed over the other queries' sums.
 #include <string.h>
@@ -24,14 +25,18 @@ constexpr bool kMaxSimFusedDefault = true;
 // where a sub-batch of nq queries whose widest token block has nv vectors keeps what in the scratch: [query data | query uniforms | the
 // block's queries | selected queries] come from the host in one copy per block, the answer blocks go back in one; the keys of a block,
 // the sums, the scores and the group numbers stay unless a query's heap is replayed
+// `ops` (the matrix-core score pass alone, 0 otherwise): bytes of a block's token vectors as matrix-core operands, one record per query
+// of the block behind the head's other arrays - a block copies the records of the queries it has
 struct Layout {
-  size_t qdata, qparams, mq, sel, head_bytes, out, rep, acc, scores, ords, bytes;
-  Layout(int nq, int64_t nv, int n_sel, int64_t live, size_t qb, size_t out_stride) {
+  size_t qdata, qparams, mq, sel, qops, head_bytes, out, rep, acc, scores, ords, bytes;
+  Layout(int nq, int64_t nv, int n_sel, int64_t live, size_t qb, size_t out_stride, size_t ops) {
     qdata = 0;
     qparams = qdata + (size_t)nv * qb;
     mq = qparams + (size_t)nv * sizeof(QueryParams);
     sel = mq + (size_t)nq * sizeof(MaxSimQuery);
     head_bytes = sel + (size_t)n_sel * sizeof(SpanQuery);
+    qops = ops ? align16(head_bytes) : head_bytes;
+    head_bytes = qops + (size_t)nq * ops;
     out = align16(head_bytes);
     rep = align16(out + (size_t)n_sel * out_stride * 8);
     acc = rep + (size_t)nv * (size_t)live * 8;
@@ -66,18 +71,22 @@ int maxsim_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const 
   const size_t qb = (size_t)query_data_bytes(ix, planes);
   const size_t out_stride = (size_t)std::min<int64_t>(k, kSpanSelectMax) + 2;
   const bool sel = k >= 1 && k <= kSpanSelectMax && L > k;  // does the select pass run?  The same for every query of the call
-  const bool fused = maxsim_fused_exists(ix->geom, planes) && (ix->opt_maxsim_fused == 1 || (ix->opt_maxsim_fused < 0 && kMaxSimFusedDefault));
+  // maxsim_fused 2: the matrix-core kernel where it exists, and what 1 does where it does not
+  const bool mfma = ix->opt_maxsim_fused == 2 && maxsim_mfma_exists(ix->geom, planes);
+  const bool fused = !mfma && maxsim_fused_exists(ix->geom, planes) && (ix->opt_maxsim_fused >= 1 || (ix->opt_maxsim_fused < 0 && kMaxSimFusedDefault));
+  const size_t ops = mfma ? (size_t)mfma_query_bytes_per_group(ix->geom.w16, true) : 0;
 
-  // the plan: sub-batches of equal size, the last one shorter; a query costs the keys of one token block, its sum, its score and its group
+  // the plan: sub-batches of equal size, the last one shorter; a query costs the keys of one token block, its sum, its score and its
+  // group - and, on the matrix cores, its block's operand bytes
   const int64_t budget = (int64_t)ix->opt_group_scratch_mb << 20;
-  const int per = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kMaxSimMaxQueries, n_queries), budget / ((8 * TB + 16) * L)));
+  const int per = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kMaxSimMaxQueries, n_queries), budget / ((8 * TB + 16) * L + (int64_t)ops)));
   int64_t widest = 0;  // vectors of the widest token block of any sub-batch
   for (int64_t q0 = 0; q0 < n_queries; q0 += per) {
     int64_t nv = 0;
     for (int64_t q = q0; q < std::min<int64_t>(q0 + per, n_queries); ++q) nv += std::min<int64_t>(TB, voff[q + 1] - voff[q]);
     widest = std::max(widest, nv);
   }
-  const Layout big(per, widest, sel ? per : 0, L, qb, out_stride);
+  const Layout big(per, widest, sel ? per : 0, L, qb, out_stride, ops);
   // everything large, before anything is written to the caller's arrays
   const int rc_scratch = reserve_scratch(ix->ctx->d_span, big.bytes, "MaxSim search");
   if (rc_scratch != BBQ_OK) return rc_scratch;
@@ -113,7 +122,7 @@ int maxsim_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const 
       nv += std::min<int64_t>(TB, voff[q0 + s + 1] - voff[q0 + s]);
       longest = std::max(longest, voff[q0 + s + 1] - voff[q0 + s]);
     }
-    const Layout lo(nq, nv, sel ? nq : 0, L, qb, out_stride);  // nv: the sub-batch's first block is its widest
+    const Layout lo(nq, nv, sel ? nq : 0, L, qb, out_stride, ops);  // nv: the sub-batch's first block is its widest
     float *d_scores = reinterpret_cast<float *>(d + lo.scores);
     uint32_t *d_ords = reinterpret_cast<uint32_t *>(d + lo.ords);
     SpanQuery *h_sel = reinterpret_cast<SpanQuery *>(head.get() + lo.sel);
@@ -123,13 +132,24 @@ int maxsim_locked(bbq_index *ix, const bbq_groups *gs, int32_t n_queries, const 
       int n_mq = 0;
       const int32_t v = stage_maxsim_token_block(ix, tk, q0, nq, t0, [](int) { return true; }, head.get() + lo.qdata, qb,
                                                  reinterpret_cast<QueryParams *>(head.get() + lo.qparams), reinterpret_cast<MaxSimQuery *>(head.get() + lo.mq), &n_mq);
-      HIPCHK(hipMemcpyAsync(d, head.get(), lo.head_bytes, hipMemcpyHostToDevice, st));
+      if (mfma) {  // the block's token vectors once more, as the FP6 operands of one query group per query: products of 1/4 (values to 15)
+        const MaxSimQuery *h_mq = reinterpret_cast<const MaxSimQuery *>(head.get() + lo.mq);
+        memset(head.get() + lo.qops, 0, (size_t)n_mq * ops);  // a missing token's operand bytes stay zero
+        for (int i = 0; i < n_mq; ++i)
+          for (int tok = 0; tok < h_mq[i].n_tok; ++tok)
+            fill_query_mfma_fp(ix, head.get() + lo.qops + (size_t)i * ops, tok, qquant + (size_t)(voff[q0 + h_mq[i].query] + t0 + tok) * ix->geom.dim, 2);
+      }
+      HIPCHK(hipMemcpyAsync(d, head.get(), lo.qops + (size_t)n_mq * ops, hipMemcpyHostToDevice, st));
       HIPCHK(hipMemsetAsync(d + lo.rep, 0, (size_t)v * (size_t)L * 8, st));
       ga.qplanes = reinterpret_cast<const uint4 *>(d + lo.qdata);
       ga.qparams = reinterpret_cast<const QueryParams *>(d + lo.qparams);
       ga.rep = reinterpret_cast<unsigned long long *>(d + lo.rep);
       ma.queries = reinterpret_cast<const MaxSimQuery *>(d + lo.mq);
-      if (fused) {
+      if (mfma) {
+        ga.n_queries = n_mq;
+        ma.qops = d + lo.qops;
+        HIPCHK(launch_maxsim_mfma(ma, planes, st));
+      } else if (fused) {
         ga.n_queries = n_mq;
         HIPCHK(launch_maxsim_score(ma, planes, st));
       } else {

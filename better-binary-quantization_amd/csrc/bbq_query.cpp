@@ -237,7 +237,7 @@ static uint32_t fp6_code_of_eighths(int eighths) {
   return ((uint32_t)e << 3) | (uint32_t)((eighths >> (e - 1)) - 8);   // exact: the low e - 1 bits of eighths are zero for q <= 15
 }
 
-static void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q, int scale8) {
+void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q, int scale8) {
   const int steps = ix->geom.w16 * 2, group = q_in_batch / 32, n = q_in_batch % 32;
   uint8_t *gb = dst + (size_t)group * mfma_query_bytes_per_group(ix->geom.w16, true);
   uint8_t *gb2 = gb + (size_t)steps * 2 * 32 * 16;

@@ -104,6 +104,9 @@ int staged_bound_for(const bbq_index *ix);
 // the sub-batch's queries once more as matrix-core operands + group maxima behind the `bytes` already staged in h_qbuf
 struct MfmaStage { bool fp; int scale8; size_t off_qbytes, off_qmax, bytes; };
 MfmaStage stage_queries_mfma(const SearchCall &c, uint8_t *h_qbuf, const QueryParams *hq, int64_t q_first, int nq, size_t bytes);
+// one query (values <= 15) as FP6 operands into its place - query q_in_batch % 32 of group q_in_batch / 32 - of cleared group records at
+// dst, mfma_query_bytes_per_group(w16, true) bytes each; every product is scale8 / 8 times the query value (2: values up to 15)
+void fill_query_mfma_fp(const bbq_index *ix, uint8_t *dst, int q_in_batch, const uint8_t *q, int scale8);
 // (the range search calls it through a SearchCall of its own that carries the index, the queries, sim and maxq: a query of its
 // sub-batch that is not mfma_query_ok is left out - zero operand bytes, not in the maxima; a search stages no such query)
 bool mfma_query_ok(const QueryParams &p);

@@ -933,10 +933,13 @@ int bbq_reset_stats(bbq_index *idx);
  *   group_scratch_mb 1..8192 (256): MiB of device scratch a sub-batch of bbq_search_grouped_batch may take for its representatives, 16
  *     bytes per live group and query: a score launch takes as many queries as fit (at most 1024, at least one).  Never a different answer
  *     The same budget bounds a sub-batch of bbq_search_maxsim_batch: 8 bytes per token of a block and 16 per query, per live group
- *   maxsim_fused -1|0|1 (-1): the score pass of bbq_search_maxsim_batch.  0: the grouped search's score kernel, every token vector of a
+ *   maxsim_fused -1|0|1|2 (-1): the score pass of bbq_search_maxsim_batch.  0: the grouped search's score kernel, every token vector of a
  *     block as one of its queries; 1: wherever it exists - 4 query bit-planes against 1-bit rows of 6, 8 or 12 16-byte chunks - the fused
  *     kernel, which loads a tile once for all tokens of a query's block; -1: the fused kernel, which was measured faster at 1 M rows of each
- *     of its three widths (profiles/maxsim_search*.json).  Never a different answer
+ *     of its three widths (profiles/maxsim_search*.json); 2: for the same shapes the matrix-core kernel - a block's 32 token vectors are
+ *     one query group of v_mfma_scale_f32_32x32x64_f8f6f4 against the rows' codes, and only the f64 score, the key and the group maximum
+ *     stay per (token, row) pair; a sub-batch's scratch then also holds 3072 bytes per 16-byte row chunk and query - and wherever that
+ *     kernel does not exist, what 1 does.  Never a different answer
  *   fast_bound 0|1 (1): compact corrections: 1 tests the score bound of a row in f32 against the threshold's image in the linear space of
  *     the score formula, for every query whose corrections have f32 images (others keep the f64 bound); 0: always the f64 bound through
  *     the similarity transform.  A pre-filter in front of the exact score either way: never a different answer

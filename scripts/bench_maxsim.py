@@ -9,10 +9,12 @@ Ways:
   (a)   bbq_score_rows per token vector over all rows, the group maxima (numpy), bbq_maxsim_reduce and the reference's heap on the host
   (b)   bbq_search_maxsim_batch with maxsim_fused 0: the grouped search's score kernel, every token vector one of its queries
   (c)   bbq_search_maxsim_batch with maxsim_fused 1: the fused score kernel, a tile loaded once for all tokens of a query's block
-The answers of the three ways are compared byte for byte on every leg.
+  (d)   bbq_search_maxsim_batch with maxsim_fused 2: the matrix-core score kernel, a block's tokens one query group of the MFMA
+The answers of the ways are compared byte for byte on every leg.  (d) is judged against (c) by the rule below, losses included.
 Legs: groups of 1..16 rows (8.5 on average) and groups of 1 000 rows; k = 10 and 100; without a filter and under a random filter that
-accepts 90 % of the rows.  Per leg, (b) and (c) run three times in alternation, each run the median of the timed calls (host clock around
-calls that return with their results); (a) is timed in the first run only.  The rule for maxsim_fused -1: fused only if on EVERY leg the
+accepts 90 % of the rows.  Per leg, (b), (c) and (d) run three times in alternation - a round is one call of each of the three, so a
+call of (b) or (c) now stands between calls of the other two kernels and (d)'s larger upload - each run the median of the timed calls
+(host clock around calls that return with their results); (a) is timed in the first run only.  The rule for maxsim_fused -1: fused only if on EVERY leg the
 slowest of (c)'s three runs beats the fastest of (b)'s by more than (b)'s spread (its slowest run minus its fastest)."""
 import argparse
 import json
@@ -83,11 +85,11 @@ def main():
             nonempty = np.nonzero(np.diff(off) > 0)[0]
             starts = off[nonempty]
             for k in (int(x) for x in args.ks.split(",")):
-                out = {w: (np.ones((nq, k), np.int32), np.ones((nq, k), np.float32), np.ones(nq, np.int64), np.ones(nq, np.uint8)) for w in "abc"}
+                out = {w: (np.ones((nq, k), np.int32), np.ones((nq, k), np.float32), np.ones(nq, np.int64), np.ones(nq, np.uint8)) for w in "abcd"}
 
                 def device_call(way):
                     grp, sc, cnt, status = out[way]
-                    ix.set_option("maxsim_fused", 0 if way == "b" else 1)
+                    ix.set_option("maxsim_fused", "bcd".index(way))
                     t0 = time.perf_counter()
                     rc = L.bbq_search_maxsim_batch(ix._h, groups._h, nq, voff.ctypes.data, qq.ctypes.data, qc.ctypes.data, QB, SIM, k, grp.ctypes.data,
                                                    sc.ctypes.data, cnt.ctypes.data, status.ctypes.data)
@@ -115,12 +117,12 @@ def main():
                         sc[q, :len(oi)] = osc
                     return time.perf_counter() - t0
 
-                runs = {"b": [], "c": []}
+                runs = {"b": [], "c": [], "d": []}
                 t_a = []
                 for r in range(args.runs):
-                    t = {"b": [], "c": [], "a": []}
+                    t = {"b": [], "c": [], "d": [], "a": []}
                     for c in range(args.warmup + args.steps):  # interleaved: one call of every way per round
-                        d = {"b": device_call("b"), "c": device_call("c")}
+                        d = {"b": device_call("b"), "c": device_call("c"), "d": device_call("d")}
                         if r == 0 and not args.skip_a:
                             d["a"] = way_a()
                         if c >= args.warmup:
@@ -128,24 +130,32 @@ def main():
                                 t[w].append(v)
                     runs["b"].append(med(t["b"]))
                     runs["c"].append(med(t["c"]))
+                    runs["d"].append(med(t["d"]))
                     if t["a"]:
                         t_a = t["a"]
                 ix.set_option("maxsim_fused", -1)
                 want = min(k, groups.live)
-                ways = "bc" if args.skip_a else "abc"
+                ways = "bcd" if args.skip_a else "abcd"
                 for w in ways:
                     assert (out[w][2] == want).all()
                     assert out[w][0][:, :want].tobytes() == out["b"][0][:, :want].tobytes() and out[w][1][:, :want].tobytes() == out["b"][1][:, :want].tobytes(), \
                         "%s accept %g k %d: way (%s) and way (b) differ" % (lname, acc, k, w)
-                assert out["b"][3].tobytes() == out["c"][3].tobytes()
+                assert out["b"][3].tobytes() == out["c"][3].tobytes() == out["d"][3].tobytes()
                 b_fast, b_slow, c_slow = min(runs["b"]), max(runs["b"]), max(runs["c"])
                 wins = c_slow < b_fast - (b_slow - b_fast)
                 fused_wins_everywhere &= wins
+                c_fast, d_slow = min(runs["c"]), max(runs["d"])
+                mfma_wins = d_slow < c_fast - (c_slow - c_fast)        # the same rule, (d) against (c)
+                mfma_loses = min(runs["d"]) > c_slow + (d_slow - min(runs["d"]))
                 rec = {"groups": lname, "n_groups": int(groups.count), "live_groups": int(groups.live), "filter_accepts": acc, "k": k,
                        "unfused_s_per_call_runs": [round(x, 6) for x in runs["b"]], "fused_s_per_call_runs": [round(x, 6) for x in runs["c"]],
                        "unfused_s_per_call": round(med(runs["b"]), 6), "fused_s_per_call": round(med(runs["c"]), 6),
                        "fused_speedup_over_unfused": round(med(runs["b"]) / med(runs["c"]), 3),
                        "fused_slowest_beats_unfused_fastest_by_more_than_its_spread": bool(wins),
+                       "mfma_s_per_call_runs": [round(x, 6) for x in runs["d"]], "mfma_s_per_call": round(med(runs["d"]), 6),
+                       "mfma_speedup_over_fused": round(med(runs["c"]) / med(runs["d"]), 3),
+                       "mfma_slowest_beats_fused_fastest_by_more_than_its_spread": bool(mfma_wins),
+                       "fused_slowest_beats_mfma_fastest_by_more_than_its_spread": bool(mfma_loses),
                        "status1_share": round(float(out["b"][3].mean()), 4), "answers_agree": True}
                 if t_a:
                     best_new = min(med(runs["b"]), med(runs["c"]))
@@ -154,7 +164,7 @@ def main():
                                 "fused_speedup_over_score_rows_and_host_reduce": round(med(t_a) / med(runs["c"]), 2),
                                 "faster_than_the_exact_way": bool(best_new < med(t_a))})
                 res["legs"].append(rec)
-                print("bench_maxsim: %s accept %g k %d: unfused %.6f fused %.6f s per call%s" % (lname, acc, k, med(runs["b"]), med(runs["c"]),
+                print("bench_maxsim: %s accept %g k %d: unfused %.6f fused %.6f mfma %.6f s per call%s" % (lname, acc, k, med(runs["b"]), med(runs["c"]), med(runs["d"]),
                                                                                               ", host way %.3f" % med(t_a) if t_a else ""), file=sys.stderr, flush=True)
             groups.close()
             if flt is not None:
